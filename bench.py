@@ -26,6 +26,11 @@ Prints ONE JSON line on rank 0.
 
 `--dry-run` (CPU, no GPU, gloo): every rank joins the process group, builds its tile of the scene and takes part in the
 same collectives with stand-in payloads; the printed line carries n_gpus and "dry_run": true.  It checks the launch path.
+
+`--dump-outputs DIR`: after the timed steps, the per-point labels of the last timed step (what a caller of the timed path
+receives) go to DIR/point_labels.npy (DIR/point_labels_rank<r>.npy with N > 1 ranks) as float32, or float64 where float32
+would not hold them exactly; at most 64 MB in all, else a fixed seeded sample (dump_outputs).  The scenes are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -47,6 +52,32 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); 6290 GB/s
 # per launch x that mean / 2.39 GHz / 1024 SIMDs / the kernel's duration of THIS run.
 VALU_CLOCK_GHZ = 2.39
 N_SIMD = 1024
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES, seed=0):
+    """Write every array of `arrays` (name -> array) flattened to out_dir/<name>.npy in float32, or in float64 where float32
+    would not hold its values exactly.  When they exceed `budget` bytes together, every array keeps the same share of its
+    elements: a sample drawn with a fixed seed, in ascending index order, so equal outputs give equal files.
+    Returns name -> {dtype, elements written, elements}."""
+    import numpy as np
+    flat = {}
+    for name, a in arrays.items():
+        a = np.asarray(a).ravel()
+        f = a.astype(np.float32)
+        flat[name] = f if np.array_equal(f, a, equal_nan=True) else a.astype(np.float64)
+    room = budget - 1024 * len(flat)     # leave room for the .npy headers
+    total = sum(a.nbytes for a in flat.values())
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, a in flat.items():
+        n = a.size
+        if total > room:
+            k = int(n * room / total)
+            a = a[np.sort(np.random.default_rng(seed).choice(n, k, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        info[name] = {"dtype": str(a.dtype), "written": int(a.size), "elements": int(n)}
+    return info
 
 
 def spawn_ranks(args):
@@ -250,7 +281,12 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="CPU only: exercise the launch path and the collectives (gloo), no engine")
     ap.add_argument("--native", action="store_true", help="tiled runs through libvgs_tiles.so (the default for --gpus > 1; with --gpus 1: a one-rank communicator)")
     ap.add_argument("--python-twin", action="store_true", help="tiled runs through the Python twin of the native driver (dist.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's per-point labels to DIR/*.npy (float32, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the engine: a dry run computes no labels")
 
     have_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.gpus > 1 and not have_launcher:
@@ -333,6 +369,7 @@ def main():
         def step():
             tiles_drv.run()
         runner = tiles_drv
+        labels_of = lambda: tiles_drv.point_labels()[0]
     elif world == 1:
         eng = v.Engine(p)
         eng.set_points_device(d_xyz.data_ptr(), d_xyz.shape[0], 12, keep=d_xyz)
@@ -340,6 +377,7 @@ def main():
         def step():
             eng.run()
         runner = eng
+        labels_of = eng.point_labels
     else:
         from vgs_svgs_segmentation_amd.dist import TiledSegmenter
         seg = TiledSegmenter(p, dist, tiles=tiles, rank=rank, world=world, pitch=50.0 * (n_per / 10_000_000) ** 0.5)
@@ -348,6 +386,7 @@ def main():
         def step():
             seg.run()
         runner = seg.engine
+        labels_of = seg.point_labels
 
     for _ in range(args.warmup):
         step()
@@ -376,6 +415,12 @@ def main():
         t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's labels, read back before anything below runs the engine again (the clusters timing does)
+        name = "point_labels" if world == 1 else f"point_labels_rank{rank}"
+        dumped = dump_outputs(args.dump_outputs, {name: labels_of()}, DUMP_BYTES // world)
 
     per_rank = None
     if tiles_drv is not None:
@@ -555,6 +600,8 @@ def main():
             out["clusters_ms"] = cl
         if h2h is not None:
             out["host_to_host"] = h2h
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if world == 1 and not native and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(xyz, p, runner.adjacency_counts(), runner.point_voxel())
         print(json.dumps(out))

@@ -57,3 +57,33 @@ def test_bench_refuses_a_mismatched_launcher():
 def test_bench_fails_when_a_rank_fails():
     r = _run(["--gpus", "2", "--dry-run", "--points", "20000", "--steps", "1"], env_extra={"VGS_BENCH_FAIL_RANK": "1"})
     assert r.returncode != 0
+
+
+def test_bench_refuses_zero_steps_and_a_dry_run_dump(tmp_path):
+    """ms_per_step is the timed region over --steps: zero steps would make it meaningless; a dry run has no labels to dump."""
+    r = _run(["--dry-run", "--points", "1000", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+    r = _run(["--dry-run", "--points", "1000", "--dump-outputs", str(tmp_path)])
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+
+
+def test_dump_outputs_float_files_within_budget(tmp_path):
+    """--dump-outputs writes float32 where that is exact (float64 otherwise) and keeps to its byte budget with a seeded sample."""
+    import importlib.util
+
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    labels = np.arange(-1, 20000, dtype=np.int32)
+    wide = np.array([2 ** 24 + 1, -1], dtype=np.int32)
+    info = bench.dump_outputs(str(tmp_path / "a"), {"labels": labels, "wide": wide})
+    a, w = np.load(tmp_path / "a" / "labels.npy"), np.load(tmp_path / "a" / "wide.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, labels) and info["labels"]["written"] == labels.size
+    assert w.dtype == np.float64 and np.array_equal(w, wide)
+    budget = 1024 + 4 * 5000
+    for d in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / d), {"labels": labels}, budget=budget)
+        assert os.path.getsize(tmp_path / d / "labels.npy") <= budget and info["labels"]["elements"] == labels.size
+    b, c = np.load(tmp_path / "b" / "labels.npy"), np.load(tmp_path / "c" / "labels.npy")
+    assert 0 < b.size <= 5000 and np.array_equal(b, c) and np.all(np.diff(b) > 0) and np.isin(b, labels).all()

@@ -76,3 +76,18 @@ def test_native_driver_costs_what_the_plain_engine_costs(gpu):
     assert abs(b - a) <= 0.12 * a + 0.1, (a, b, native["driver"]["per_rank"][0]["tiles_ms"])
     r0 = native["driver"]["per_rank"][0]
     assert 0.1 < r0["hbm_in_use_gb"] < r0["hbm_total_gb"]
+
+
+def test_dump_outputs_are_the_timed_labels(gpu, tmp_path):
+    """--dump-outputs writes the per-point labels of the last timed step: those of a plain engine run on the same seeded cloud."""
+    import numpy as np
+    out = _run(["--points", "400000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-host-to-host", "--no-clusters",
+                "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["dump_outputs"]["arrays"]["point_labels"]["dtype"] == "float32"
+    dumped = np.load(tmp_path / "point_labels.npy")
+    eng = gpu.Engine(gpu.default_params(2, voxel_size=0.1))
+    eng.set_points(gpu.scenes.urban_scene(400000))
+    eng.run()
+    labels = eng.point_labels()
+    eng.close()
+    assert dumped.dtype == np.float32 and dumped.shape == labels.shape and np.array_equal(dumped, labels)

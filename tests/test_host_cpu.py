@@ -64,15 +64,14 @@ def test_parse_task_file_svgs(vgs, tmp_path):
 
 
 def test_parse_reference_task_files_if_present(vgs):
-    ref = "/root/reference/Task_File_VGS.txt"
-    if not os.path.exists(ref):
-        pytest.skip("reference not mounted (GPU box)")
-    p, inn, out = vgs.parse_task_file(ref)
+    """The stock task files (tests/golden/task_*_stock.txt: the reference's line layout and parameter values) parse to the defaults."""
+    golden = os.path.join(ROOT, "tests", "golden")
+    p, inn, out = vgs.parse_task_file(os.path.join(golden, "task_vgs_stock.txt"))
     d = vgs.default_params(2)
     assert (inn, out) == ("Town_Test.pcd", "Town_Test_VGS.pcd")
     for k in ("voxel_size", "graph_size", "sig_p", "sig_n", "sig_o", "sig_e", "sig_c", "sig_w", "cut_thred", "points_min", "adjacency_min", "voxels_min"):
         assert getattr(p, k) == getattr(d, k), k
-    p3, _, _ = vgs.parse_task_file("/root/reference/Task_File_SVGS.txt")
+    p3, _, _ = vgs.parse_task_file(os.path.join(golden, "task_svgs_stock.txt"))
     d3 = vgs.default_params(3)
     for k in ("voxel_size", "seed_size", "graph_size", "sig_w", "cut_thred", "color_impt", "spatial_impt", "normal_impt", "adjacency_min"):
         assert getattr(p3, k) == getattr(d3, k), k
