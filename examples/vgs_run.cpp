@@ -3,8 +3,12 @@
 // the input PCD, segment, write the coloured clusters as PCD -- what `main` around the reference's `test` drivers does
 // with input_vector[12]/[15] (input path / name) and [18]/[21] (output path / name), minus the viewer.
 //   usage: vgs_run <task file> [--in <file.pcd|.ply>] [--out <file.pcd>] [--seed <n>] [--ascii] [--debug-meshes <prefix>]
+//                  [--segments <file.csv>]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
+// --segments writes one CSV row per kept cluster (getClusterDescriptors, row i = cluster i of the output): label, n_points, n_nodes,
+// bbox (6), centroid (3), eigenvalues (3, ascending), normal (3), major axis (3), the eight eigen features -- doubles as %.17g, floats as
+// %.9g, so every value reads back exactly.
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
 #include <cstdio>
 #include <cstdlib>
@@ -15,9 +19,32 @@
 #include "drivers.hpp"
 #include "point_clouds_io.hpp"
 
+static int writeSegmentsCsv(const std::string& path, const std::vector<pcl::ClusterDescriptor>& desc) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "label,n_points,n_nodes,min_x,min_y,min_z,max_x,max_y,max_z,cx,cy,cz,l0,l1,l2,nx,ny,nz,ax,ay,az,"
+                  "f0,f1,f2,f3,f4,f5,f6,f7\n");
+  for (size_t i = 0; i < desc.size(); ++i) {
+    const pcl::ClusterDescriptor& d = desc[i];
+    std::fprintf(f, "%zu,%lld,%d", i, (long long)d.n_points, (int)d.n_nodes);
+    for (int a = 0; a < 6; ++a) std::fprintf(f, ",%.9g", (double)d.bbox[a]);
+    for (int a = 0; a < 3; ++a) std::fprintf(f, ",%.17g", d.centroid[a]);
+    for (int a = 0; a < 3; ++a) std::fprintf(f, ",%.17g", d.evals[a]);
+    for (int r = 0; r < 3; ++r) std::fprintf(f, ",%.17g", d.evecs[3 * r + 0]);   // normal: eigenvector of the smallest eigenvalue
+    for (int r = 0; r < 3; ++r) std::fprintf(f, ",%.17g", d.evecs[3 * r + 2]);   // major axis: eigenvector of the largest
+    for (int a = 0; a < 8; ++a) std::fprintf(f, ",%.9g", (double)d.eigen8[a]);
+    std::fprintf(f, "\n");
+  }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
 int main(int argc, char** argv) {
-  if (argc < 2) { std::fprintf(stderr, "usage: %s <task file> [--in file.pcd] [--out file.pcd] [--seed n] [--ascii]\n", argv[0]); return 2; }
-  std::string in_file, out_file, debug_prefix;
+  if (argc < 2) {
+    std::fprintf(stderr, "usage: %s <task file> [--in file.pcd] [--out file.pcd] [--seed n] [--ascii] [--debug-meshes prefix] [--segments file.csv]\n",
+                 argv[0]);
+    return 2;
+  }
+  std::string in_file, out_file, debug_prefix, segments_file;
   uint64_t seed = 0;
   bool ascii = false;
   for (int a = 2; a < argc; ++a) {
@@ -26,6 +53,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--seed") && a + 1 < argc) seed = std::strtoull(argv[++a], nullptr, 10);
     else if (!std::strcmp(argv[a], "--ascii")) ascii = true;
     else if (!std::strcmp(argv[a], "--debug-meshes") && a + 1 < argc) debug_prefix = argv[++a];
+    else if (!std::strcmp(argv[a], "--segments") && a + 1 < argc) segments_file = argv[++a];
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
   const std::vector<std::string> task = inputTaskTxtFile(argv[1]);
@@ -44,14 +72,20 @@ int main(int argc, char** argv) {
   if ((ply ? inputPointCloudData2(in_file, cloud) : inputPointCloudData(in_file, cloud)) != 0) return 1;
   std::vector<std::vector<int>> clusters;
   DriverSummary sum;
+  std::vector<pcl::ClusterDescriptor> desc;
+  std::vector<pcl::ClusterDescriptor>* want = segments_file.empty() ? nullptr : &desc;
   try {
-    if (method == 2) { if (segmentationVGS(cloud, task, clusters, &sum, debug_prefix) != 0) { std::fprintf(stderr, "cannot write the debug meshes\n"); return 1; } }
-    else segmentationSVGS(cloud, task, clusters, &sum);
+    if (method == 2) {
+      if (segmentationVGS(cloud, task, clusters, &sum, debug_prefix, 0.0, want) != 0) { std::fprintf(stderr, "cannot write the debug meshes\n"); return 1; }
+    } else {
+      segmentationSVGS(cloud, task, clusters, &sum, want);
+    }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "error: %s\n", e.what());
     return 1;
   }
   if (saveColoredClusters(out_file, cloud, clusters, seed, !ascii) != 0) return 1;
+  if (want && writeSegmentsCsv(segments_file, desc) != 0) { std::fprintf(stderr, "cannot write %s\n", segments_file.c_str()); return 1; }
   std::printf("%d %ld %ld %ld %ld %ld %ld\n", method, sum.points, sum.voxels, sum.supervoxels, sum.clusters, sum.kept, sum.labelled);
   return 0;
 }

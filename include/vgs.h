@@ -202,6 +202,28 @@ vgs_status vgs_get_clusters_ordered(vgs_ctx* ctx, int32_t order, int64_t* offset
  * offsets_dev[kept + 1] (int64), point_idx_dev[offsets[kept]] (int32) -- made by one stable sort of the leaf order by label; valid
  * until the next run of the stages.  vgs_get_clusters[_ordered] with the default order copies exactly these to the host. */
 vgs_status vgs_get_clusters_device(vgs_ctx* ctx, const int64_t** offsets_dev, const int32_t** point_idx_dev);
+/* Per-segment descriptors (no reference counterpart: what a caller does next with getClusterIdx).  Row k describes exactly the points
+ * whose label (vgs_get_point_labels) is k, K = counts[VGS_N_KEPT] rows; every array is K rows long and any pointer may be NULL:
+ *   n_points   int64   points with label k
+ *   n_nodes    int32   voxels (VGS) or supervoxels (SVGS) with label k
+ *   bbox6      float   min x, y, z, max x, y, z of the points (exact: min / max of the input floats)
+ *   centroid3  double  mean of the points
+ *   cov6       double  population covariance (1/n): xx, xy, xz, yy, yz, zz
+ *   evals3     double  eigenvalues of cov6, ascending, clamped to >= 0
+ *   evecs9     double  [r*3+j] = component r of eigenvector j (vm_eigen33's layout): column 0 the normal, column 2 the major axis; each
+ *                      column's component of largest magnitude is positive (lowest index on a tie)
+ *   eigen8     float   vm_eigen_features (csrc/vgs_math.h) of the float-rounded eigenvalues, in the order of the context's method (the
+ *                      eight features of vgs_get_attributes' eigen8, so node and segment features compare directly)
+ * A segment of one point has zero covariance, eigenvalues and features and identity eigenvectors.  Computed on the device on the first
+ * request after a run (fp64 sums about a point of the segment, a fixed summation order: bit-identical from call to call) and cached until
+ * the next run.  VGS_E_STATE before the context is segmented and for a tile context (vgs_set_owned_region / vgs_set_own_point_range);
+ * K = 0 writes nothing. */
+vgs_status vgs_get_segment_descriptors(vgs_ctx* ctx, int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6,
+                                       double* evals3, double* evecs9, float* eigen8);
+/* the same table left in HBM: device pointers (any may be NULL), valid until the next run of the stages */
+vgs_status vgs_get_segment_descriptors_device(vgs_ctx* ctx, const int64_t** n_points, const int32_t** n_nodes, const float** bbox6,
+                                              const double** centroid3, const double** cov6, const double** evals3, const double** evecs9,
+                                              const float** eigen8);
 
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.

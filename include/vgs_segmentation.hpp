@@ -93,6 +93,41 @@ inline void check(vgs_ctx* c, vgs_status s, const char* what) {
 struct CtxDeleter { void operator()(vgs_ctx* c) const { vgs_destroy(c); } };
 }  // namespace vgs_detail
 
+// Extension (no VS / SS line): the geometric descriptor of one kept cluster, as vgs_get_segment_descriptors (include/vgs.h) defines it
+struct ClusterDescriptor {
+  int64_t n_points = 0;   // points of the cluster
+  int32_t n_nodes = 0;    // voxels (VGS) or supervoxels (SVGS)
+  float bbox[6] = {0, 0, 0, 0, 0, 0};   // min x, y, z, max x, y, z
+  double centroid[3] = {0, 0, 0};
+  double cov[6] = {0, 0, 0, 0, 0, 0};   // population covariance: xx, xy, xz, yy, yz, zz
+  double evals[3] = {0, 0, 0};          // ascending
+  double evecs[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // [r*3+j] = component r of eigenvector j: column 0 the normal, column 2 the major axis
+  float eigen8[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the eight eigen features of the method (as the per-node ones)
+};
+
+namespace vgs_detail {
+// one row per kept cluster, in label order -- the order of getClusterIdx (cluster k of either order holds the points labelled k)
+inline std::vector<ClusterDescriptor> cluster_descriptors(vgs_ctx* c, int64_t k) {
+  std::vector<ClusterDescriptor> out((size_t)k);
+  if (k == 0) return out;
+  std::vector<int64_t> np((size_t)k);
+  std::vector<int32_t> nn((size_t)k);
+  std::vector<float> bb((size_t)k * 6), e8((size_t)k * 8);
+  std::vector<double> ce((size_t)k * 3), cv((size_t)k * 6), ev((size_t)k * 3), vv((size_t)k * 9);
+  check(c, vgs_get_segment_descriptors(c, np.data(), nn.data(), bb.data(), ce.data(), cv.data(), ev.data(), vv.data(), e8.data()),
+        "vgs_get_segment_descriptors");
+  for (size_t i = 0; i < (size_t)k; ++i) {
+    ClusterDescriptor& d = out[i];
+    d.n_points = np[i]; d.n_nodes = nn[i];
+    for (int a = 0; a < 6; ++a) { d.bbox[a] = bb[6 * i + a]; d.cov[a] = cv[6 * i + a]; }
+    for (int a = 0; a < 3; ++a) { d.centroid[a] = ce[3 * i + a]; d.evals[a] = ev[3 * i + a]; }
+    for (int a = 0; a < 9; ++a) d.evecs[a] = vv[9 * i + a];
+    for (int a = 0; a < 8; ++a) d.eigen8[a] = e8[8 * i + a];
+  }
+  return out;
+}
+}  // namespace vgs_detail
+
 template <typename PointT>
 class VoxelBasedSegmentation {
  public:
@@ -202,6 +237,11 @@ class VoxelBasedSegmentation {
     drawn_ = true;
     if (colored_cloud && cloud_) vgs_color::color_clusters(*cloud_, getClusterIdx(), seed, *colored_cloud);
   }
+  // Extension (no VS line): descriptor i describes getClusterIdx()[i]; empty before drawColorMapofPointsinClusters, like getClusterIdx
+  std::vector<ClusterDescriptor> getClusterDescriptors() {
+    if (!drawn_) return {};
+    return vgs_detail::cluster_descriptors(ctx(), count(VGS_N_KEPT));
+  }
 
   vgs_ctx* ctx() { return ctx_.get(); }
 
@@ -292,6 +332,8 @@ class SuperVoxelBasedSegmentation {
   void drawColorMapofPointsinClusters(const PCXYZRGBPtr& colored_cloud, uint64_t seed = 0) {  // the reference's signature (SS:613)
     if (colored_cloud && cloud_) vgs_color::color_clusters(*cloud_, getClusterIdx(), seed, *colored_cloud);
   }
+  // Extension (no SS line): descriptor i describes getClusterIdx()[i]
+  std::vector<ClusterDescriptor> getClusterDescriptors() { return vgs_detail::cluster_descriptors(ctx(), count(VGS_N_KEPT)); }
   vgs_ctx* ctx() { return ctx_.get(); }
 
  private:

@@ -259,6 +259,25 @@ class Engine:
         self._ck(self._L.vgs_get_clusters_device(self._h, C.byref(po), C.byref(pi)))
         return po.value, pi.value
 
+    # per segment: (field, dtype, values per segment) of vgs_get_segment_descriptors, in its argument order
+    DESCRIPTOR_FIELDS = (("n_points", np.int64, 1), ("n_nodes", np.int32, 1), ("bbox6", np.float32, 6), ("centroid3", np.float64, 3),
+                         ("cov6", np.float64, 6), ("evals3", np.float64, 3), ("evecs9", np.float64, 9), ("eigen8", np.float32, 8))
+
+    def segment_descriptors(self):
+        """Geometric descriptors of the kept segments, row k = the points labelled k (include/vgs.h, vgs_get_segment_descriptors): a dict
+        of numpy arrays n_points (K,), n_nodes (K,), bbox6 (K, 6), centroid3 (K, 3), cov6 (K, 6: xx xy xz yy yz zz), evals3 (K, 3,
+        ascending), evecs9 (K, 9: [r*3+j] = component r of eigenvector j), eigen8 (K, 8).  Computed on the device, cached until the next run."""
+        K = self.counts()["kept"]
+        out = {name: np.zeros((K, w) if w > 1 else K, dtype=dt) for name, dt, w in self.DESCRIPTOR_FIELDS}
+        self._ck(self._L.vgs_get_segment_descriptors(self._h, *(_ptr(out[name]) for name, _, _ in self.DESCRIPTOR_FIELDS)))
+        return out
+
+    def segment_descriptors_device(self):
+        """The same table left in HBM: {field: device pointer}, valid until the next run."""
+        ps = [C.c_void_p() for _ in self.DESCRIPTOR_FIELDS]
+        self._ck(self._L.vgs_get_segment_descriptors_device(self._h, *(C.byref(p) for p in ps)))
+        return {name: p.value for (name, _, _), p in zip(self.DESCRIPTOR_FIELDS, ps)}
+
     # ---- a sequence of clouds: uploads of the next cloud and downloads of the last labels overlap the stages
     def stage_points(self, xyz):
         """Start the copy of the NEXT cloud (ideally a pinned array, see pinned_empty) and return at once."""
@@ -368,6 +387,12 @@ class VoxelBasedSegmentation:
         off, idx = self._eng.clusters("reference")
         return [idx[off[k]:off[k + 1]].tolist() for k in range(len(off) - 1)]
 
+    def getClusterDescriptors(self):
+        """Extension (no VS line): descriptor i describes getClusterIdx()[i] -- both are in label order (Engine.segment_descriptors)."""
+        if not self._drawn:
+            return {name: np.zeros((0, w) if w > 1 else 0, dtype=dt) for name, dt, w in Engine.DESCRIPTOR_FIELDS}
+        return self._eng.segment_descriptors()
+
     @property
     def engine(self):
         return self._eng
@@ -439,6 +464,10 @@ class SuperVoxelBasedSegmentation:
     def getClusterIdx(self):                                                          # SS:130
         off, idx = self._eng.clusters("reference")
         return [idx[off[k]:off[k + 1]].tolist() for k in range(len(off) - 1)]
+
+    def getClusterDescriptors(self):
+        """Extension (no SS line): descriptor i describes getClusterIdx()[i] -- both are in label order (Engine.segment_descriptors)."""
+        return self._eng.segment_descriptors()
 
     @property
     def engine(self):

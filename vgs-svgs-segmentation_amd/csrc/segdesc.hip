@@ -1,0 +1,376 @@
+// segdesc.hip -- per-segment geometric descriptors of the kept segments (no reference counterpart: what a caller of getClusterIdx
+// computes next).  Descriptor k covers exactly the points whose label (vgs_get_point_labels) is k: point count, node count, exact
+// float bounding box, fp64 centroid and population covariance, a double-precision Jacobi eigensolve, and vm_eigen_features.
+//
+// Data flow (everything already sits in HBM in the right order: xs/ys/zs hold the points sorted by node, vox_start gives each node's
+// run, vox_label its kept label):
+//   1. one stable radix sort of the node ids by label (V keys, not N points): the nodes of segment k are one run of the sorted list
+//   2. per sorted node its run length, exclusive scan -> vp: the "virtual" position of the node's first point in the concatenation of all
+//      segments' points in label order; per segment its node run (a binary search in the sorted keys) and ceil(points / SD_CHUNK) chunks,
+//      exclusive scan -> the first chunk of every segment
+//   3. k_sd_chunks: one workgroup per chunk of <= SD_CHUNK virtual points (a chunk never crosses a segment, it may split a node); it reads
+//      its nodes' runs of xs/ys/zs and writes one partial record: sums of d = p - a and of d d^T in fp64, min and max, where the anchor a
+//      is the segment's first point (its first node's first point) -- the same anchor in every chunk of the segment, so the partials add
+//   4. k_sd_final: one wavefront per segment folds its partials, then computes centroid, covariance, eigen decomposition and features
+// Determinism: every sum has a fixed shape -- which point a lane reads depends on (chunk, lane, step) only, the lanes fold by a fixed
+// butterfly, the waves in index order, the partials of a segment by lane stride then butterfly.  No atomics.  Balance: a segment of
+// millions of points is spread over its chunks like any other; a segment of a few hundred points costs one workgroup.
+// Scratch: own buffers only (sd_*), nothing another getter reads.  Computed on request and cached until the next run (sd_valid).
+#include <cstring>
+#include <string.h>
+
+#include <rocprim/rocprim.hpp>
+
+#include "vgs_context.hpp"
+
+#define SD_TB 256                   // threads of a chunk workgroup
+#define SD_PPT 8                    // points per thread of a chunk
+#define SD_CHUNK (SD_TB * SD_PPT)   // virtual points per chunk
+#define SD_REC 16                   // doubles per partial record: sum d[3], sum dd^T[6] (xx xy xz yy yz zz), min[3], max[3], (pad)
+
+// key of node v: its kept label, K for the nodes of dropped clusters (they sort behind every kept segment)
+__global__ void k_sd_keys(const int32_t* __restrict__ vox_label, int64_t V, uint32_t K, uint32_t* __restrict__ key, uint32_t* __restrict__ ids) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const int32_t l = vox_label[v];
+  key[v] = l < 0 ? K : (uint32_t)l;
+  ids[v] = (uint32_t)v;
+}
+
+// run length of the node at sorted position i (0 for dropped nodes and for the sentinel i = V)
+__global__ void k_sd_runlen(const uint32_t* __restrict__ key, const uint32_t* __restrict__ ids, const uint32_t* __restrict__ vox_start, int64_t V,
+                            uint32_t K, uint32_t* __restrict__ len) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > V) return;
+  uint32_t n = 0;
+  if (i < V && key[i] < K) { const uint32_t v = ids[i]; n = vox_start[v + 1] - vox_start[v]; }
+  len[i] = n;
+}
+
+__device__ __forceinline__ uint32_t sd_lower_bound(const uint32_t* __restrict__ key, uint32_t n, uint32_t k) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (key[mid] < k) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+
+// per segment k < K: first sorted node (seg_node[k], seg_node[K] = end of the kept nodes) and number of chunks (nchunk[K] = 0)
+__global__ void k_sd_segments(const uint32_t* __restrict__ key, uint32_t V, uint32_t K, const uint32_t* __restrict__ vp,
+                              uint32_t* __restrict__ seg_node, uint32_t* __restrict__ nchunk) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > K) return;
+  const uint32_t n0 = sd_lower_bound(key, V, k);
+  seg_node[k] = n0;
+  if (k == K) { nchunk[k] = 0; return; }
+  const uint32_t n1 = sd_lower_bound(key, V, k + 1);
+  const uint32_t pts = vp[n1] - vp[n0];
+  const uint32_t ch = (pts + SD_CHUNK - 1) / SD_CHUNK;
+  nchunk[k] = ch > 0 ? ch : 1u;   // (a kept segment holds at least one point; the guard keeps the chunk -> segment search well defined)
+}
+
+__device__ __forceinline__ double sd_wave_sum(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+  return x;
+}
+__device__ __forceinline__ float sd_wave_min(float x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x = fminf(x, __shfl_xor(x, m, 64));
+  return x;
+}
+__device__ __forceinline__ float sd_wave_max(float x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x = fmaxf(x, __shfl_xor(x, m, 64));
+  return x;
+}
+
+// One workgroup per chunk of SD_CHUNK virtual points of one segment.  Grid: an upper bound of the number of chunks (floor(Nf / SD_CHUNK) +
+// K + 1); workgroups past the real number leave at once.
+__global__ __launch_bounds__(SD_TB) void k_sd_chunks(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                     const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                     const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                     const uint32_t* __restrict__ seg_chunk, uint32_t K, double* __restrict__ part) {
+  __shared__ uint32_t s_vp[SD_CHUNK];    // virtual start of the chunk's nodes
+  __shared__ uint32_t s_dl[SD_CHUNK];    // sorted position - virtual position of the same (mod 2^32)
+  __shared__ double s_red[SD_TB / 64][SD_REC];
+  const uint32_t c = blockIdx.x;
+  if (c >= seg_chunk[K]) return;
+  // segment of chunk c: the last k with seg_chunk[k] <= c (every segment has at least one chunk)
+  uint32_t lo = 0, hi = K - 1;
+  while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (seg_chunk[mid] <= c) lo = mid; else hi = mid - 1; }
+  const uint32_t k = lo;
+  const uint32_t n0 = seg_node[k], n1 = seg_node[k + 1];
+  const uint32_t a = vp[n0] + (c - seg_chunk[k]) * SD_CHUNK;
+  const uint32_t b = min(a + SD_CHUNK, vp[n1]);
+  if (n1 <= n0 || a >= b) {   // (cannot happen for a kept segment; an empty record keeps the fold well defined)
+    if (threadIdx.x < SD_REC) {
+      const int f = threadIdx.x;
+      part[(size_t)c * SD_REC + f] = f < 9 ? 0.0 : (f < 12 ? __builtin_huge_val() : (f < 15 ? -__builtin_huge_val() : 0.0));
+    }
+    return;
+  }
+  // nodes that overlap [a, b): the last node starting at or before a ... the last node starting before b.  Every node of a kept segment
+  // holds a point, so vp rises strictly inside the segment and they are at most b - a <= SD_CHUNK nodes.
+  uint32_t i0 = n0, i1 = n1 - 1;
+  while (i0 < i1) { const uint32_t mid = (i0 + i1 + 1) >> 1; if (vp[mid] <= a) i0 = mid; else i1 = mid - 1; }
+  uint32_t j0 = i0 + 1, j1 = n1;
+  while (j0 < j1) { const uint32_t mid = (j0 + j1) >> 1; if (vp[mid] < b) j0 = mid + 1; else j1 = mid; }
+  const uint32_t m = min(j0 - i0, (uint32_t)SD_CHUNK);   // (the bound above; the clamp only guards the LDS arrays)
+  for (uint32_t t = threadIdx.x; t < m; t += SD_TB) {
+    const uint32_t i = i0 + t, q = vp[i];
+    s_vp[t] = q;
+    s_dl[t] = vox_start[ids[i]] - q;
+  }
+  // the anchor: the segment's first point, the same for every chunk of the segment
+  const uint32_t pa = vox_start[ids[n0]];
+  const double ax = (double)xs[pa], ay = (double)ys[pa], az = (double)zs[pa];
+  __syncthreads();
+  double sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
+  float mnx = __builtin_huge_valf(), mny = __builtin_huge_valf(), mnz = __builtin_huge_valf();
+  float mxx = -__builtin_huge_valf(), mxy = -__builtin_huge_valf(), mxz = -__builtin_huge_valf();
+#pragma unroll 2
+  for (int it = 0; it < SD_PPT; ++it) {
+    const uint32_t q = a + (uint32_t)it * SD_TB + threadIdx.x;
+    if (q < b) {
+      uint32_t l = 0, h = m - 1;   // the last node of the chunk that starts at or before q
+      while (l < h) { const uint32_t mid = (l + h + 1) >> 1; if (s_vp[mid] <= q) l = mid; else h = mid - 1; }
+      const uint32_t pos = q + s_dl[l];
+      const float x = xs[pos], y = ys[pos], z = zs[pos];
+      mnx = fminf(mnx, x); mny = fminf(mny, y); mnz = fminf(mnz, z);
+      mxx = fmaxf(mxx, x); mxy = fmaxf(mxy, y); mxz = fmaxf(mxz, z);
+      // exact differences (two floats, one double); products and sums in fp64
+      const double dx = (double)x - ax, dy = (double)y - ay, dz = (double)z - az;
+      sx += dx; sy += dy; sz += dz;
+      sxx += dx * dx; sxy += dx * dy; sxz += dx * dz; syy += dy * dy; syz += dy * dz; szz += dz * dz;
+    }
+  }
+  sx = sd_wave_sum(sx); sy = sd_wave_sum(sy); sz = sd_wave_sum(sz);
+  sxx = sd_wave_sum(sxx); sxy = sd_wave_sum(sxy); sxz = sd_wave_sum(sxz); syy = sd_wave_sum(syy); syz = sd_wave_sum(syz); szz = sd_wave_sum(szz);
+  mnx = sd_wave_min(mnx); mny = sd_wave_min(mny); mnz = sd_wave_min(mnz);
+  mxx = sd_wave_max(mxx); mxy = sd_wave_max(mxy); mxz = sd_wave_max(mxz);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    double* r = s_red[w];
+    r[0] = sx; r[1] = sy; r[2] = sz; r[3] = sxx; r[4] = sxy; r[5] = sxz; r[6] = syy; r[7] = syz; r[8] = szz;
+    r[9] = mnx; r[10] = mny; r[11] = mnz; r[12] = mxx; r[13] = mxy; r[14] = mxz; r[15] = 0.0;
+  }
+  __syncthreads();
+  if (threadIdx.x < SD_REC) {   // the waves in index order
+    const int f = threadIdx.x;
+    double v = s_red[0][f];
+    if (f < 9) { for (int u = 1; u < SD_TB / 64; ++u) v += s_red[u][f]; }
+    else if (f < 12) { for (int u = 1; u < SD_TB / 64; ++u) v = fmin(v, s_red[u][f]); }
+    else if (f < 15) { for (int u = 1; u < SD_TB / 64; ++u) v = fmax(v, s_red[u][f]); }
+    part[(size_t)c * SD_REC + f] = v;
+  }
+}
+
+// One Jacobi rotation that zeroes A[p][q] (Numerical Recipes' jacobi: A' = J^T A J, W' = W J; r = the third index)
+template <int p, int q>
+__device__ __forceinline__ void sd_jacobi_rotate(double (&A)[3][3], double (&W)[3][3]) {
+  constexpr int r = 3 - p - q;
+  const double apq = A[p][q];
+  if (apq == 0.0) return;
+  const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+  const double t = fabs(theta) > 1e150 ? 0.5 / theta : (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+  const double arp = A[r][p], arq = A[r][q];
+  A[p][p] -= t * apq;
+  A[q][q] += t * apq;
+  A[p][q] = 0.0; A[q][p] = 0.0;
+  const double nrp = cs * arp - sn * arq, nrq = sn * arp + cs * arq;
+  A[r][p] = nrp; A[p][r] = nrp; A[r][q] = nrq; A[q][r] = nrq;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double wp = W[i][p], wq = W[i][q];
+    W[i][p] = cs * wp - sn * wq;
+    W[i][q] = sn * wp + cs * wq;
+  }
+}
+
+template <int a, int b>
+__device__ __forceinline__ void sd_order_pair(double (&d)[3], double (&W)[3][3]) {
+  if (d[a] > d[b]) {
+    const double t = d[a]; d[a] = d[b]; d[b] = t;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { const double u = W[i][a]; W[i][a] = W[i][b]; W[i][b] = u; }
+  }
+}
+
+// one wavefront per segment: fold its partials (lane stride, then butterfly), then everything per segment on lane 0
+__global__ __launch_bounds__(256) void k_sd_final(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                  const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                  const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                  const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part, uint32_t n_part, uint32_t K, int svgs,
+                                                  int64_t* __restrict__ o_npts, int32_t* __restrict__ o_nnodes, float* __restrict__ o_bbox,
+                                                  double* __restrict__ o_cen, double* __restrict__ o_cov, double* __restrict__ o_eval,
+                                                  double* __restrict__ o_evec, float* __restrict__ o_eig8) {
+  const uint32_t k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (k >= K) return;   // (whole wavefronts; no barrier follows)
+  const uint32_t c0 = seg_chunk[k], c1 = min(seg_chunk[k + 1], n_part);   // (the bound only guards the records: the chunks fit, see the launch)
+  double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double mn[3] = {__builtin_huge_val(), __builtin_huge_val(), __builtin_huge_val()};
+  double mx[3] = {-__builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val()};
+  for (uint32_t c = c0 + lane; c < c1; c += 64) {
+    const double* r = part + (size_t)c * SD_REC;
+#pragma unroll
+    for (int f = 0; f < 9; ++f) s[f] += r[f];
+#pragma unroll
+    for (int f = 0; f < 3; ++f) { mn[f] = fmin(mn[f], r[9 + f]); mx[f] = fmax(mx[f], r[12 + f]); }
+  }
+#pragma unroll
+  for (int f = 0; f < 9; ++f) s[f] = sd_wave_sum(s[f]);
+#pragma unroll
+  for (int f = 0; f < 3; ++f) { mn[f] = (double)sd_wave_min((float)mn[f]); mx[f] = (double)sd_wave_max((float)mx[f]); }
+  if (lane != 0) return;
+  const uint32_t n0 = seg_node[k], n1 = seg_node[k + 1];
+  const uint32_t n = vp[n1] - vp[n0];
+  const uint32_t pa = vox_start[ids[n0]];
+  const double anc[3] = {(double)xs[pa], (double)ys[pa], (double)zs[pa]};
+  o_npts[k] = (int64_t)n;
+  o_nnodes[k] = (int32_t)(n1 - n0);
+#pragma unroll
+  for (int f = 0; f < 3; ++f) { o_bbox[6 * (size_t)k + f] = (float)mn[f]; o_bbox[6 * (size_t)k + 3 + f] = (float)mx[f]; }
+  const double inv = 1.0 / (double)n;
+  const double md[3] = {s[0] * inv, s[1] * inv, s[2] * inv};
+#pragma unroll
+  for (int f = 0; f < 3; ++f) o_cen[3 * (size_t)k + f] = anc[f] + md[f];
+  // population covariance about the mean: E[d d^T] - E[d] E[d]^T, d relative to a point of the segment
+  double cv[6];
+  cv[0] = s[3] * inv - md[0] * md[0]; cv[1] = s[4] * inv - md[0] * md[1]; cv[2] = s[5] * inv - md[0] * md[2];
+  cv[3] = s[6] * inv - md[1] * md[1]; cv[4] = s[7] * inv - md[1] * md[2]; cv[5] = s[8] * inv - md[2] * md[2];
+  if (n == 1) { for (int f = 0; f < 6; ++f) cv[f] = 0.0; }
+#pragma unroll
+  for (int f = 0; f < 6; ++f) o_cov[6 * (size_t)k + f] = cv[f];
+  // cyclic Jacobi in fp64 until the off-diagonal part is negligible against the diagonal
+  double A[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
+  double W[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  for (int sweep = 0; sweep < 32; ++sweep) {
+    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
+    const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
+    if (off == 0.0 || off <= 1e-36 * dia) break;
+    sd_jacobi_rotate<0, 1>(A, W);
+    sd_jacobi_rotate<0, 2>(A, W);
+    sd_jacobi_rotate<1, 2>(A, W);
+  }
+  double d[3] = {A[0][0], A[1][1], A[2][2]};
+  sd_order_pair<0, 1>(d, W);
+  sd_order_pair<1, 2>(d, W);
+  sd_order_pair<0, 1>(d, W);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    // sign: the component of largest magnitude is positive (lowest index on a tie)
+    double best = W[0][j];
+    if (fabs(W[1][j]) > fabs(best)) best = W[1][j];
+    if (fabs(W[2][j]) > fabs(best)) best = W[2][j];
+    if (best < 0.0) { W[0][j] = -W[0][j]; W[1][j] = -W[1][j]; W[2][j] = -W[2][j]; }
+    d[j] = d[j] > 0.0 ? d[j] : 0.0;
+    o_eval[3 * (size_t)k + j] = d[j];
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o_evec[9 * (size_t)k + 3 * r + j] = W[r][j];
+  const float ef[3] = {(float)d[0], (float)d[1], (float)d[2]};
+  float F[8];
+  vm_eigen_features(ef, svgs, F);
+#pragma unroll
+  for (int f = 0; f < 8; ++f) o_eig8[8 * (size_t)k + f] = F[f];
+}
+
+static bool vgs_is_tile(const vgs_ctx* c) { return c->have_region || c->n_own >= 0; }
+
+// The table in HBM, K = counts[VGS_N_KEPT] rows; valid until the next run of the stages.
+vgs_status vgs_segdesc_on_device(vgs_ctx* c) {
+  if (c->sd_valid) return VGS_OK;
+  const int64_t K = c->counts[VGS_N_KEPT], V = c->V, nf = c->Nf;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  const size_t k1 = (size_t)(K > 0 ? K : 1);
+  VGS_HIP_TRY(c, c->sd_npts.ensure(k1)); VGS_HIP_TRY(c, c->sd_nnodes.ensure(k1));
+  VGS_HIP_TRY(c, c->sd_bbox.ensure(6 * k1)); VGS_HIP_TRY(c, c->sd_eig8.ensure(8 * k1));
+  VGS_HIP_TRY(c, c->sd_cen.ensure(3 * k1)); VGS_HIP_TRY(c, c->sd_cov.ensure(6 * k1));
+  VGS_HIP_TRY(c, c->sd_eval.ensure(3 * k1)); VGS_HIP_TRY(c, c->sd_evec.ensure(9 * k1));
+  if (K == 0 || V == 0 || nf == 0) { c->sd_valid = true; return VGS_OK; }
+  VGS_HIP_TRY(c, c->sd_key.ensure(2 * (size_t)V)); VGS_HIP_TRY(c, c->sd_ids.ensure(2 * (size_t)V));
+  VGS_HIP_TRY(c, c->sd_vp.ensure(2 * ((size_t)V + 1)));
+  VGS_HIP_TRY(c, c->sd_seg.ensure(3 * ((size_t)K + 1)));
+  uint32_t *key_in = c->sd_key.p, *key_out = key_in + V, *ids_in = c->sd_ids.p, *ids_out = ids_in + V;
+  uint32_t *len = c->sd_vp.p, *vp = len + V + 1;
+  uint32_t *seg_node = c->sd_seg.p, *nchunk = seg_node + K + 1, *seg_chunk = nchunk + K + 1;
+  const int TB = 256;
+  hipLaunchKernelGGL(k_sd_keys, dim3((unsigned)((V + TB - 1) / TB)), dim3(TB), 0, c->stream, c->vox_label.p, V, (uint32_t)K, key_in, ids_in);
+  unsigned bits = 1;
+  while (bits < 32 && (1ull << bits) <= (unsigned long long)K) ++bits;   // keys 0 .. K
+  size_t t_sort = 0, t_scan1 = 0, t_scan2 = 0;
+  VGS_HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, t_sort, key_in, key_out, ids_in, ids_out, (size_t)V, 0, bits, c->stream));
+  VGS_HIP_TRY(c, rocprim::exclusive_scan(nullptr, t_scan1, len, vp, 0u, (size_t)V + 1, rocprim::plus<uint32_t>(), c->stream));
+  VGS_HIP_TRY(c, rocprim::exclusive_scan(nullptr, t_scan2, nchunk, seg_chunk, 0u, (size_t)K + 1, rocprim::plus<uint32_t>(), c->stream));
+  size_t t_max = t_sort > t_scan1 ? t_sort : t_scan1;
+  if (t_scan2 > t_max) t_max = t_scan2;
+  VGS_HIP_TRY(c, c->sd_tmp.ensure(t_max));
+  VGS_HIP_TRY(c, rocprim::radix_sort_pairs(c->sd_tmp.p, t_sort, key_in, key_out, ids_in, ids_out, (size_t)V, 0, bits, c->stream));
+  hipLaunchKernelGGL(k_sd_runlen, dim3((unsigned)((V + 1 + TB - 1) / TB)), dim3(TB), 0, c->stream, key_out, ids_out, c->vox_start.p, V,
+                     (uint32_t)K, len);
+  VGS_HIP_TRY(c, rocprim::exclusive_scan(c->sd_tmp.p, t_scan1, len, vp, 0u, (size_t)V + 1, rocprim::plus<uint32_t>(), c->stream));
+  hipLaunchKernelGGL(k_sd_segments, dim3((unsigned)((K + 1 + TB - 1) / TB)), dim3(TB), 0, c->stream, key_out, (uint32_t)V, (uint32_t)K, vp,
+                     seg_node, nchunk);
+  VGS_HIP_TRY(c, rocprim::exclusive_scan(c->sd_tmp.p, t_scan2, nchunk, seg_chunk, 0u, (size_t)K + 1, rocprim::plus<uint32_t>(), c->stream));
+  // sum over segments of ceil(n_k / SD_CHUNK) <= floor(Nf / SD_CHUNK) + K: launched without reading the real number back
+  const int64_t n_chunks_max = nf / SD_CHUNK + K + 1;
+  VGS_HIP_TRY(c, c->sd_part.ensure((size_t)n_chunks_max * SD_REC));
+  hipLaunchKernelGGL(k_sd_chunks, dim3((unsigned)n_chunks_max), dim3(SD_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, ids_out, vp,
+                     seg_node, seg_chunk, (uint32_t)K, c->sd_part.p);
+  hipLaunchKernelGGL(k_sd_final, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, ids_out, vp,
+                     seg_node, seg_chunk, c->sd_part.p, (uint32_t)n_chunks_max, (uint32_t)K, c->P.method == 3 ? 1 : 0, c->sd_npts.p, c->sd_nnodes.p, c->sd_bbox.p,
+                     c->sd_cen.p, c->sd_cov.p, c->sd_eval.p, c->sd_evec.p, c->sd_eig8.p);
+  VGS_HIP_TRY(c, hipGetLastError());
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->sd_valid = true;
+  return VGS_OK;
+}
+
+static vgs_status sd_check(vgs_ctx* c, const char* fn) {
+  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
+  if (vgs_is_tile(c)) {
+    c->err = std::string(fn) + ": a tile context (owned region / own point range) holds only part of its segments; descriptors need the whole cloud in one context";
+    return VGS_E_STATE;
+  }
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_get_segment_descriptors(vgs_ctx* c, int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6,
+                                                  double* evals3, double* evecs9, float* eigen8) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = sd_check(c, "vgs_get_segment_descriptors");
+  if (s != VGS_OK) return s;
+  const size_t K = (size_t)c->counts[VGS_N_KEPT];
+  if (K == 0) return VGS_OK;
+  if ((s = vgs_segdesc_on_device(c)) != VGS_OK) return s;
+  if (n_points) VGS_HIP_TRY(c, hipMemcpy(n_points, c->sd_npts.p, K * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (n_nodes) VGS_HIP_TRY(c, hipMemcpy(n_nodes, c->sd_nnodes.p, K * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (bbox6) VGS_HIP_TRY(c, hipMemcpy(bbox6, c->sd_bbox.p, 6 * K * sizeof(float), hipMemcpyDeviceToHost));
+  if (centroid3) VGS_HIP_TRY(c, hipMemcpy(centroid3, c->sd_cen.p, 3 * K * sizeof(double), hipMemcpyDeviceToHost));
+  if (cov6) VGS_HIP_TRY(c, hipMemcpy(cov6, c->sd_cov.p, 6 * K * sizeof(double), hipMemcpyDeviceToHost));
+  if (evals3) VGS_HIP_TRY(c, hipMemcpy(evals3, c->sd_eval.p, 3 * K * sizeof(double), hipMemcpyDeviceToHost));
+  if (evecs9) VGS_HIP_TRY(c, hipMemcpy(evecs9, c->sd_evec.p, 9 * K * sizeof(double), hipMemcpyDeviceToHost));
+  if (eigen8) VGS_HIP_TRY(c, hipMemcpy(eigen8, c->sd_eig8.p, 8 * K * sizeof(float), hipMemcpyDeviceToHost));
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_get_segment_descriptors_device(vgs_ctx* c, const int64_t** n_points, const int32_t** n_nodes, const float** bbox6,
+                                                         const double** centroid3, const double** cov6, const double** evals3,
+                                                         const double** evecs9, const float** eigen8) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = sd_check(c, "vgs_get_segment_descriptors_device");
+  if (s != VGS_OK) return s;
+  if ((s = vgs_segdesc_on_device(c)) != VGS_OK) return s;
+  if (n_points) *n_points = c->sd_npts.p;
+  if (n_nodes) *n_nodes = c->sd_nnodes.p;
+  if (bbox6) *bbox6 = c->sd_bbox.p;
+  if (centroid3) *centroid3 = c->sd_cen.p;
+  if (cov6) *cov6 = c->sd_cov.p;
+  if (evals3) *evals3 = c->sd_eval.p;
+  if (evecs9) *evecs9 = c->sd_evec.p;
+  if (eigen8) *eigen8 = c->sd_eig8.p;
+  return VGS_OK;
+}

@@ -248,6 +248,16 @@ struct vgs_ctx {
   DevBuf<int64_t> cl_off;
   DevBuf<int32_t> cl_idx;
   bool cl_valid = false;
+  // per-segment descriptors (segdesc.hip): the table of the kept segments, computed on request, valid until the next run (sd_valid); the
+  // sort, scans and partial records of that computation use their own scratch (no getter reads it)
+  DevBuf<uint32_t> sd_key, sd_ids, sd_vp, sd_seg;
+  DevBuf<uint8_t> sd_tmp;
+  DevBuf<double> sd_part;
+  DevBuf<int64_t> sd_npts;
+  DevBuf<int32_t> sd_nnodes;
+  DevBuf<float> sd_bbox, sd_eig8;
+  DevBuf<double> sd_cen, sd_cov, sd_eval, sd_evec;
+  bool sd_valid = false;
   DevBuf<uint64_t> counters;   // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 
@@ -374,6 +384,7 @@ vgs_status vgs_ensure_point_labels(vgs_ctx* c);   // merge.hip
 vgs_status vgs_localcut_finish(vgs_ctx* c, unsigned int* n_deferred);  // waits for them, checks the stage's flags (called by the merge stage)
 vgs_status vgs_stage_merge(vgs_ctx* c);
 vgs_status vgs_clusters_on_device(vgs_ctx* c);   // clusters.hip
+vgs_status vgs_segdesc_on_device(vgs_ctx* c);    // segdesc.hip
 vgs_status vgs_stage_vccs(vgs_ctx* c);
 vgs_status vgs_stage_svgs_group(vgs_ctx* c);
 vgs_status vgs_stage_svgs_neighbours(vgs_ctx* c);
