@@ -735,14 +735,10 @@ vgs_status vgs_run_adjacency(vgs_ctx* c, bool full, uint64_t* out_key, uint32_t*
     hipLaunchKernelGGL((k_adjacency<2048, false>), dim3(g2), dim3(64), 0, c->stream, c->vox_code.p, row_ids, U, (const Brick*)c->hkey.p, c->hbits,
                        c->offsets.p, c->n_off, c->adj_R, c->box.depth, res_f, mnx, mny, mnz, r2, c->node.p, c->adj_stride, out_key, out_cnt, out_nall, gt,
                        c->adj_gstride, c->adj_ngroups, c->adj_nvals.p, list1, d_n1, list2, off, d_n2);
-    if (c->K.no_adj_wide)
-      hipLaunchKernelGGL((k_adjacency<8192, false>), dim3(g2), dim3(64), 0, c->stream, c->vox_code.p, row_ids, U, (const Brick*)c->hkey.p, c->hbits,
-                         c->offsets.p, c->n_off, c->adj_R, c->box.depth, res_f, mnx, mny, mnz, r2, c->node.p, c->adj_stride, out_key, out_cnt, out_nall, gt,
-                         c->adj_gstride, c->adj_ngroups, c->adj_nvals.p, list2, d_n2, (uint32_t*)nullptr, off, d_n2);
-    else   // a workgroup per row (round 6)
-      hipLaunchKernelGGL((k_adjacency_wide<512>), dim3(g2), dim3(512), 0, c->stream, c->vox_code.p, row_ids, (const Brick*)c->hkey.p, c->hbits,
-                         c->offsets.p, c->n_off, c->adj_R, c->box.depth, res_f, mnx, mny, mnz, r2, c->adj_stride, out_key, out_cnt, out_nall, gt,
-                         c->adj_gstride, c->adj_ngroups, c->adj_nvals.p, (const uint32_t*)list2, (const unsigned int*)d_n2, off);
+    // rows above 2048 used neighbours: a workgroup per row
+    hipLaunchKernelGGL((k_adjacency_wide<512>), dim3(g2), dim3(512), 0, c->stream, c->vox_code.p, row_ids, (const Brick*)c->hkey.p, c->hbits,
+                       c->offsets.p, c->n_off, c->adj_R, c->box.depth, res_f, mnx, mny, mnz, r2, c->adj_stride, out_key, out_cnt, out_nall, gt,
+                       c->adj_gstride, c->adj_ngroups, c->adj_nvals.p, (const uint32_t*)list2, (const unsigned int*)d_n2, off);
   } else if (c->n_off <= 1024) {
     if (full) LAUNCH_ADJ(1024, true, vgs_xcd_grid(U), nullptr, nullptr, nullptr); else LAUNCH_ADJ(1024, false, vgs_xcd_grid(U), nullptr, nullptr, nullptr);
   } else if (c->n_off <= 8192) {

@@ -819,11 +819,10 @@ vgs_status vgs_stage_localcut(vgs_ctx* c) {
   const bool early_sizes = vgs_can_split_readback(c);
 #endif
   unsigned int* d_ncls = (unsigned int*)(c->counters.p + 44);   // words 44-46: A + A1, B, C, D, C0
-  const int max_c0 = c->K.no_c0 ? WAVE_B : WAVE_C0;   // VGS_NO_C0: class C takes them all
   const bool dense_ = !c->K.no_dense;
   const int sample = (c->pl_enabled && dense_ && !c->K.no_vote) ? c->K.vote_period : 0;   // a power of two: one voxel in so many is a sample
   if (early_sizes) {
-    hipLaunchKernelGGL(k_count_classes, dim3((unsigned)((U + 1023) / 1024)), dim3(1024), 0, c->stream, c->adj_cnt.p, U, WAVE_A, WAVE_B, WAVE_C, max_c0, d_ncls, sample, 1024);
+    hipLaunchKernelGGL(k_count_classes, dim3((unsigned)((U + 1023) / 1024)), dim3(1024), 0, c->stream, c->adj_cnt.p, U, WAVE_A, WAVE_B, WAVE_C, WAVE_C0, d_ncls, sample, 1024);
     vgs_status sb = vgs_readback_begin(c, d_ncls, 28);
     if (sb != VGS_OK) return sb;
   }
@@ -836,7 +835,7 @@ vgs_status vgs_stage_localcut(vgs_ctx* c) {
   const int a1_max = c->K.a1_max;
   hipLaunchKernelGGL(k_classify, dim3((unsigned)((U + 1023) / 1024)), dim3(1024), 0, c->stream, c->adj_cnt.p, c->adj_cnt.p, U,
                      0, WAVE_A, WAVE_B, WAVE_C, c->used_ids.p, c->nl_enabled ? c->nl_cnt.p : (const uint8_t*)nullptr, c->nl_tot.p, a1_max, ids_a, ids_b, ids_c,
-                     ids_d, ids_a1, d_nabc, max_c0, ids_c0, sample, ids_s);
+                     ids_d, ids_a1, d_nabc, WAVE_C0, ids_c0, sample, ids_s);
   unsigned int nabc[LC_NCLASS] = {0, 0, 0, 0, 0, 0, 0};
   unsigned int n_bulk = 0;   // A + A1
   unsigned int n_above_d = ~0u;   // neighbourhoods above 1024 voxels (~0: not counted -- the diagnostics path without the early counts)

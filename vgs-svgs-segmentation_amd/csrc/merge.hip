@@ -86,7 +86,9 @@ __global__ __launch_bounds__(64) void k_cross(const uint32_t* __restrict__ used_
   const uint16_t* orow = (cbits != nullptr && adj_off != nullptr) ? adj_off + u * adj_stride : nullptr;
   const bool own_bits = orow != nullptr && orow[0] != 0xffffu;
   int kept = 0;
-  uint32_t best = i;  // first hook of the union-find (see k_cc_init): smallest mutual neighbour below i
+  // first hook of the union-find (ECL-CC style): every used voxel points at its smallest trusted mutual neighbour below it.  Ids only
+  // decrease along parent links, so this is a forest; it already joins most of every large segment without atomics.
+  uint32_t best = i;
   for (int k = sub; k < n; k += W) {
     uint8_t mflag = 0;
     if (crow[k]) {
@@ -152,7 +154,7 @@ __global__ __launch_bounds__(64) void k_cross(const uint32_t* __restrict__ used_
   }
   for (int o = W / 2; o > 0; o >>= 1) kept += __shfl_xor(kept, o, 64);
   if (sub == 0) csize[i] = (uint32_t)kept;
-  if (parent) {  // single-tile runs: the hook needs no ownership test, so it is taken here instead of re-reading the row
+  if (parent) {  // (null: a row put off while the unions ran early takes no first hook, its parent may have moved)
     for (int o = W / 2; o > 0; o >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int)best, o, 64); best = other < best ? other : best; }
     if (sub == 0) parent[i] = best;
   }
@@ -253,32 +255,6 @@ __global__ void k_merge_init(uint32_t* __restrict__ parent, uint32_t* __restrict
                              uint8_t* __restrict__ cc_flags, uint32_t* __restrict__ csz, int64_t n) {
   int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (v < n) { parent[v] = (uint32_t)v; csize[v] = 0u; attach[v] = -1; cc_flags[v] = 0; csz[v] = 0u; }
-}
-
-// first hook (ECL-CC style): every used voxel points at its smallest trusted neighbour with a smaller id.  Ids only
-// decrease along parent links, so this is a forest; it already joins most of every large segment without atomics.
-__global__ __launch_bounds__(64) void k_cc_init(const uint32_t* __restrict__ used_ids, int64_t U, const uint64_t* __restrict__ adj_key,
-                                                const uint32_t* __restrict__ adj_cnt, int adj_stride, const uint8_t* __restrict__ mutual,
-                                                const int32_t* __restrict__ attach, const uint8_t* __restrict__ owned,
-                                                uint32_t* __restrict__ parent) {
-  const int64_t u = vgs_xcd_item(blockIdx.x, U);
-  if (u >= U) return;
-  const uint32_t i = used_ids[u];
-  const int n = (int)adj_cnt[u];
-  const uint64_t* row = adj_key + u * adj_stride;
-  const uint8_t* mrow = mutual + u * adj_stride;
-  uint32_t best = i;
-  for (int k = threadIdx.x; k < n; k += 64) {
-    if (!mrow[k]) continue;
-    const uint32_t t = (uint32_t)row[k];
-    if (t < best && (!owned || owned[i] || owned[t])) best = t;
-  }
-  if (threadIdx.x == 0) {
-    const int32_t t = attach[i];
-    if (t >= 0 && (uint32_t)t < best && (!owned || owned[i])) best = (uint32_t)t;
-  }
-  for (int o = 32; o > 0; o >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int)best, o, 64); best = other < best ? other : best; }
-  if (threadIdx.x == 0) parent[i] = best;
 }
 
 // UM_ROWS rows per wavefront, 64 / UM_ROWS lanes each: a row holds about 120 entries, so a whole wavefront per row spends
@@ -532,16 +508,14 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     mutual = c->conn.p + (size_t)U * c->adj_stride;  // second half holds the mutual flags
     const uint16_t* gt = (c->P.method == 2 && c->adj_have_gtab) ? c->adj_gtab.p : nullptr;
     const float inv_res2 = 1.0f / (c->P.voxel_size * c->P.voxel_size);
-    // Tiled runs (round 5): which voxels this rank owns depends on the voxel lattice, the region and the points' sources only, so it is
-    // known NOW, not behind closestCheck -- the first hook is taken in k_cross under the ownership test and the unions of the final rows run
-    // beside the hand-over kernels as in a single-context run (the native driver's merge stage was 0.35 ms longer than the plain one's).
-    const bool tile_early = c->have_region && !c->K.no_tile_early;
-    if (tile_early) { vgs_status so = vgs_compute_owned(c); if (so != VGS_OK) return so; }
-    const uint8_t* owned_early = tile_early ? c->owned.p : (const uint8_t*)nullptr;
-    uint32_t* cross_parent = (c->have_region && !tile_early) ? nullptr : c->parent.p;
+    // Tiled runs: which voxels this rank owns depends on the voxel lattice, the region and the points' sources only, so it is known
+    // NOW, not behind closestCheck -- the first hook is taken in k_cross under the ownership test and the unions of the final rows run
+    // beside the hand-over kernels as in a single-context run.
+    if (c->have_region) { vgs_status so = vgs_compute_owned(c); if (so != VGS_OK) return so; }
+    const uint8_t* owned_early = c->have_region ? c->owned.p : (const uint8_t*)nullptr;
     unsigned int* d_ndefer = (unsigned int*)(c->counters.p + 13);   // zeroed with the local cut's counters
     // runs whose hand-over kernels are still running: the unions of the final rows go beside them (see below)
-    const bool early_union = (!c->have_region || tile_early) && c->lc_tail.open && !c->K.no_overlap && !c->K.no_early_union;
+    const bool early_union = c->lc_tail.open && !c->K.no_overlap;
     if (early_union) VGS_HIP_TRY(c, c->lc_defer_flag.ensure((size_t)U));
     // connect bits of the cuts (method 2, rows with lattice offsets): the lattice lookup of k_cross
     const bool use_bits = c->cb_enabled && c->P.method == 2 && c->adj_have_off;
@@ -556,7 +530,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     const LcGate g_first = {(c->lc_tail.open && c->lc_tail.gated) ? (const unsigned int*)(c->counters.p + 57) : (const unsigned int*)nullptr, LC_FEW};
     const size_t first_lds = (c->lc_tail.open && c->K.cross_lds_kb > 0) ? (size_t)c->K.cross_lds_kb * 1024 : 0;
     hipLaunchKernelGGL(k_cross, dim3(vgs_xcd_grid((U + CX_ROWS - 1) / CX_ROWS)), dim3(64), first_lds, c->stream, c->used_ids.p, c->used_rank.p, U, c->adj_key.p, c->adj_cnt.p,
-                       c->adj_stride, c->conn.p, mutual, c->csize.p, cross_parent, gt, c->adj_gstride, c->adj_nrank.p, inv_res2,
+                       c->adj_stride, c->conn.p, mutual, c->csize.p, c->parent.p, gt, c->adj_gstride, c->adj_nrank.p, inv_res2,
                        c->lc_tail.open ? c->lc_pending.p : (const uint8_t*)nullptr, c->lc_defer.p, d_ndefer, (const uint32_t*)nullptr, 0,
                        cb_off, cb_lut, cb_bits, c->cb_words, early_union ? c->lc_defer_flag.p : (uint8_t*)nullptr, g_first, owned_early);
     if (early_union) {
@@ -580,7 +554,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
       // whatever they left (hooks, unions of rows whose flags nobody wrote this run) goes, and crossValidation takes every row now
       hipLaunchKernelGGL(k_merge_init, dim3(nbV), dim3(TB), 0, c->stream, c->parent.p, c->csize.p, c->attach.p, c->cc_flags.p, c->csz.p, V);
       hipLaunchKernelGGL(k_cross, dim3(vgs_xcd_grid((U + CX_ROWS - 1) / CX_ROWS)), dim3(64), 0, c->stream, c->used_ids.p, c->used_rank.p, U, c->adj_key.p, c->adj_cnt.p,
-                         c->adj_stride, c->conn.p, mutual, c->csize.p, cross_parent, gt, c->adj_gstride, c->adj_nrank.p, inv_res2,
+                         c->adj_stride, c->conn.p, mutual, c->csize.p, c->parent.p, gt, c->adj_gstride, c->adj_nrank.p, inv_res2,
                          (const uint8_t*)nullptr, c->lc_defer.p, d_ndefer, (const uint32_t*)nullptr, 0, cb_off, cb_lut, cb_bits, c->cb_words, (uint8_t*)nullptr,
                          LcGate{nullptr, 0u}, owned_early);
       compressed = false; united = false;
@@ -588,7 +562,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     }
     if (n_defer > 0) {
       hipLaunchKernelGGL(k_cross, dim3((n_defer + CX_ROWS - 1) / CX_ROWS), dim3(64), 0, c->stream, c->used_ids.p, c->used_rank.p, U, c->adj_key.p, c->adj_cnt.p,
-                         c->adj_stride, c->conn.p, mutual, c->csize.p, early_union ? (uint32_t*)nullptr : cross_parent, gt, c->adj_gstride, c->adj_nrank.p, inv_res2,
+                         c->adj_stride, c->conn.p, mutual, c->csize.p, early_union ? (uint32_t*)nullptr : c->parent.p, gt, c->adj_gstride, c->adj_nrank.p, inv_res2,
                          (const uint8_t*)nullptr, c->lc_defer.p, d_ndefer, c->lc_defer.p, (int)n_defer, cb_off, cb_lut, cb_bits, c->cb_words, (uint8_t*)nullptr, LcGate{nullptr, 0u});
       if (early_union)
         hipLaunchKernelGGL(k_union_mutual, dim3((n_defer + UM_ROWS - 1) / UM_ROWS), dim3(64), 0, c->stream, c->used_ids.p, U, c->adj_key.p, c->adj_cnt.p,
@@ -601,8 +575,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     hipLaunchKernelGGL(k_cc_candidates, dim3((unsigned)((U + TB - 1) / TB)), dim3(TB), 0, c->stream, c->used_ids.p, U, c->adj_mused.p,
                        c->csize.p, MP.adjacency_min, c->cc_flags.p, c->work_ids.p, d_ncand);
     // Two host round trips of closestCheck (the number of candidates, the fixed-point flag) hide behind work that does not depend
-    // on it: the pointer jumping over the first hooks, and the unions of the mutual edges (round 4; single-context runs only --
-    // a tile's unions depend on ownership, which is computed behind closestCheck)
+    // on it: the pointer jumping over the first hooks, and the unions of the mutual edges (single-context runs only)
     const bool hide = !c->have_region && vgs_can_split_readback(c) && !early_union;
     if (hide) {
       vgs_status sb = vgs_readback_begin(c, d_ncand, 4);
@@ -645,11 +618,8 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     VGS_HIP_TRY(c, c->conn.ensure(16));
   }
   // connected components
-  const bool owned_known = c->have_region && U > 0 && !c->K.no_tile_early;   // (computed at the head of the stage, first hooks taken by k_cross)
-  if (c->have_region && !owned_known) { vgs_status so = vgs_compute_owned(c); if (so != VGS_OK) return so; }
-  if (U > 0 && c->have_region && !owned_known)
-    hipLaunchKernelGGL(k_cc_init, dim3(vgs_xcd_grid(U)), dim3(64), 0, c->stream, c->used_ids.p, U, c->adj_key.p, c->adj_cnt.p, c->adj_stride, mutual,
-                       c->attach.p, c->have_region ? c->owned.p : nullptr, c->parent.p);
+  // (with used voxels, ownership was computed at the head of the stage and k_cross took the first hooks; k_flatten needs it either way)
+  if (c->have_region && U == 0) { vgs_status so = vgs_compute_owned(c); if (so != VGS_OK) return so; }
   if (U > 0 && !compressed) hipLaunchKernelGGL(k_compress, dim3(nbV), dim3(TB), 0, c->stream, c->parent.p, V);
   if (U > 0 && !united)
     hipLaunchKernelGGL(k_union_mutual, dim3((unsigned)((U + UM_ROWS - 1) / UM_ROWS)), dim3(64), 0, c->stream, c->used_ids.p, U, c->adj_key.p, c->adj_cnt.p,

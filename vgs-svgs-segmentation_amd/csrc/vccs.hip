@@ -37,42 +37,6 @@ __global__ void k_vccs_centroid(const float* __restrict__ xs, const float* __res
   cen[3 * v + 0] = sx / cnt; cen[3 * v + 1] = sy / cnt; cen[3 * v + 2] = sz / cnt;
 }
 
-// 26-neighbour table (offset order of vccs_common.h) and the voxel normal from the neighbourhood's centroids.
-// Neighbours are looked up in the brick table (a few MB, L2 resident) instead of a per-voxel hash.
-__global__ void k_vccs_neighbours(const uint64_t* __restrict__ vox_code, int64_t V, int depth, const Brick* __restrict__ bricks, uint32_t hbits,
-                                  const float* __restrict__ cen, int32_t* __restrict__ nbr, float* __restrict__ nrm, int4* __restrict__ nbr4) {
-  int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  int quad[28];
-  for (int k = 26; k < 28; ++k) quad[k] = -1;
-  const uint64_t code = vox_code[v];
-  const uint32_t kx = vm_compact21(code >> 2), ky = vm_compact21(code >> 1), kz = vm_compact21(code);
-  const uint32_t lim = 1u << depth;
-  float pts[27 * 3];
-  int np = 0;
-  pts[0] = cen[3 * v]; pts[1] = cen[3 * v + 1]; pts[2] = cen[3 * v + 2];
-  np = 1;
-  for (int o = 0; o < 26; ++o) {
-    int dx, dy, dz;
-    vccs_offset(o, &dx, &dy, &dz);
-    const uint32_t nx = kx + (uint32_t)dx, ny = ky + (uint32_t)dy, nz = kz + (uint32_t)dz;
-    int t = -1;
-    if (nx < lim && ny < lim && nz < lim) { bool unused_flag; t = brick_find(bricks, hbits, nx, ny, nz, &unused_flag); }
-    nbr[(int64_t)o * V + v] = t;   // [26][V]: a wavefront reads one offset of 64 consecutive voxels
-    quad[o] = t;
-    if (nrm && t >= 0) { pts[3 * np] = cen[3 * t]; pts[3 * np + 1] = cen[3 * t + 1]; pts[3 * np + 2] = cen[3 * t + 2]; ++np; }
-  }
-  if (nrm) {   // (vccs_mode 1 has its own two-ring normals and passes null)
-    float n[3];
-    vccs_normal_from_points(pts, np, n);
-    nrm[3 * v] = n[0]; nrm[3 * v + 1] = n[1]; nrm[3 * v + 2] = n[2];
-  }
-  // the same table four entries to a load ([7][V] of int4: the expansion rounds read it 54 times and are bound by their number of
-  // vector-memory instructions, not by bytes)
-  if (nbr4)
-    for (int k = 0; k < 7; ++k) nbr4[(int64_t)k * V + v] = make_int4(quad[4 * k], quad[4 * k + 1], quad[4 * k + 2], quad[4 * k + 3]);
-}
-
 // ---------------------------------------------------------------- seeding
 __global__ void k_vccs_cell_codes(const float* __restrict__ cen, int64_t V, float min_x, float min_y, float min_z, float seed,
                                   uint64_t* __restrict__ code, uint32_t* __restrict__ id) {
@@ -151,11 +115,8 @@ __global__ void k_vccs_plant(const unsigned long long* __restrict__ seed_key, in
   count[k] = 1;
 }
 
-// one synchronous round: every voxel looks at the labels its 26 neighbours (and itself) had at the start of the round.
-// The per-supervoxel sums move with the voxels that change owner.  A workgroup's 256 voxels are neighbours in space (Morton
-// order) and belong to a handful of supervoxels, so their contributions are first added up in a small LDS table keyed by
-// label and only the table goes to memory: one global atomic per (workgroup, supervoxel, component) instead of fourteen
-// per voxel that changes -- the contended 64-bit atomics were half of the stage's time.  Integer sums: any order, same result.
+// slots of a workgroup's LDS table keyed by label (k_vccs_reseed): a workgroup's 256 voxels are neighbours in space (Morton order)
+// and belong to a handful of supervoxels, so their contributions are first combined in the table and only the table goes to memory
 #define VX_SLOTS 128
 // The best offer among the labels of the 26 neighbours.  A voxel on a border sees two to four other supervoxels, each through
 // several neighbours, and the evaluation of one label is a gather of the supervoxel's state and a wait for it: the DISTINCT labels
@@ -210,86 +171,16 @@ __device__ __forceinline__ void vccs_best_offer(const int (&nl)[26], int own, co
     }
   }
 }
-__global__ __launch_bounds__(256) void k_vccs_expand(int64_t V, const int4* __restrict__ nbr4, const float* __restrict__ cen,
-                              const float* __restrict__ nrm, const int32_t* __restrict__ label_in, const float* __restrict__ dist_in,
-                              const VccsState* __restrict__ st, float w_s_over_seed, float w_n, int32_t* __restrict__ label_out,
-                              float* __restrict__ dist_out, long long* __restrict__ sums, unsigned int* __restrict__ count) {
-  __shared__ int s_key[VX_SLOTS];
-  __shared__ unsigned long long s_sum[VX_SLOTS][6];
-  __shared__ int s_cnt[VX_SLOTS];
-  for (int k = threadIdx.x; k < VX_SLOTS; k += blockDim.x) {
-    s_key[k] = -1; s_cnt[k] = 0;
-    for (int a = 0; a < 6; ++a) s_sum[k][a] = 0ull;
-  }
-  __syncthreads();
-  int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v < V) {
-    int best_l = label_in[v];
-    float best_d = dist_in[v];
-    const float c[3] = {cen[3 * v], cen[3 * v + 1], cen[3 * v + 2]};
-    const float n[3] = {nrm[3 * v], nrm[3 * v + 1], nrm[3 * v + 2]};
-    const int own = best_l;
-    // all 26 neighbour ids, then all 26 labels: independent loads in flight together (the serial walk was latency bound)
-    int nl[26];
-    // (Round 4 measured this table as 16-bit rank differences -- voxels are in Morton order, a spatial neighbour is almost always
-    // within +-32 k ranks; 52 instead of 104 bytes per voxel and round: the stage went from 12.6 to 16.9 ms.  The kernel is bound by
-    // its 52 vector-memory instructions per thread, not by HBM bytes; the escape path for far neighbours adds 26 masked loads.)
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      const int4 q = nbr4[(int64_t)k * V + v];
-      nl[4 * k] = q.x; nl[4 * k + 1] = q.y;
-      if (k < 6) { nl[4 * k + 2] = q.z; nl[4 * k + 3] = q.w; }
-    }
-#pragma unroll
-    for (int o = 0; o < 26; ++o) nl[o] = nl[o] >= 0 ? label_in[nl[o]] : -1;
-    vccs_best_offer(nl, own, c, n, st, w_s_over_seed, w_n, best_l, best_d);
-    label_out[v] = best_l;
-    dist_out[v] = best_d;
-    // moving this voxel's contribution from its old owner to the new one gives exactly the sums a full re-accumulation
-    // would (and after the first rounds only the frontier moves)
-    if (best_l != own) {
-      long long f[6];
-      for (int a = 0; a < 3; ++a) { f[a] = vccs_fix_pos(c[a]); f[3 + a] = vccs_fix_nrm(n[a]); }
-      for (int side = 0; side < 2; ++side) {
-        const int l = side ? best_l : own;
-        if (l < 0) continue;
-        const long long sgn = side ? 1 : -1;
-        // slot of label l in the workgroup's table (open addressing); a full table sends the contribution straight to memory
-        int slot = -1;
-        unsigned int h = ((unsigned int)l * 2654435761u) >> 25;   // 7 bits
-        for (int probe = 0; probe < VX_SLOTS; ++probe) {
-          const int prev = atomicCAS(&s_key[h], -1, l);
-          if (prev == -1 || prev == l) { slot = (int)h; break; }
-          h = (h + 1) & (VX_SLOTS - 1);
-        }
-        if (slot >= 0) {
-          for (int a = 0; a < 6; ++a) atomicAdd(&s_sum[slot][a], (unsigned long long)(sgn * f[a]));
-          atomicAdd(&s_cnt[slot], (int)sgn);
-        } else {
-          for (int a = 0; a < 6; ++a) atomicAdd((unsigned long long*)&sums[6 * l + a], (unsigned long long)(sgn * f[a]));
-          if (side) atomicAdd(&count[l], 1u); else atomicSub(&count[l], 1u);
-        }
-      }
-    }
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < VX_SLOTS; k += blockDim.x) {
-    const int l = s_key[k];
-    if (l < 0) continue;
-    for (int a = 0; a < 6; ++a) { const unsigned long long x = s_sum[k][a]; if (x) atomicAdd((unsigned long long*)&sums[6 * l + a], x); }
-    const int dc = s_cnt[k];
-    if (dc > 0) atomicAdd(&count[l], (unsigned int)dc); else if (dc < 0) atomicSub(&count[l], (unsigned int)(-dc));
-  }
-}
 
-// ---------------------------------------------------------------- expansion over tiles (round 4)
-// The round above is bound by its vector-memory instructions: per voxel seven loads of neighbour ids and 26 divergent gathers of
-// their labels, 216 B through the memory pipeline.  Voxels are sorted by Morton code, so an aligned 8 x 8 x 8 block of lattice
-// cells -- a TILE -- is one contiguous run of the voxel array (about 60 voxels on a scanned surface).  One wavefront takes one tile:
-// it writes the labels of the tile's own voxels (a coalesced load) and of the voxels in the one-cell shell around it (a list built
-// once per run: at most seven tiles see a voxel in their shell) into a 10 x 10 x 10 array in LDS, and every voxel then reads its
-// 26 neighbours from there (the array is first filled with "no voxel": four 16-byte LDS stores per lane).  Per voxel and round
-// that is 4 B of label, 2 B of cell index and about 12 B of shell instead of the 216.  Same synchronous round, same result.
+// ---------------------------------------------------------------- expansion over tiles
+// One synchronous round: every voxel looks at the labels its 26 neighbours (and itself) had at the start of the round.  Gathering
+// them through a per-voxel neighbour table makes the round bound by its vector-memory instructions: seven loads of neighbour ids and
+// 26 divergent gathers of their labels, 216 B per voxel through the memory pipeline.  Voxels are sorted by Morton code, so an aligned
+// 8 x 8 x 8 block of lattice cells -- a TILE -- is one contiguous run of the voxel array (about 60 voxels on a scanned surface).  One
+// wavefront takes one tile: it writes the labels of the tile's own voxels (a coalesced load) and of the voxels in the one-cell shell
+// around it (a list built once per run: at most seven tiles see a voxel in their shell) into a 10 x 10 x 10 array in LDS, and every
+// voxel then reads its 26 neighbours from there (the array is first filled with "no voxel": four 16-byte LDS stores per lane).  Per
+// voxel and round that is 4 B of label, 2 B of cell index and about 12 B of shell instead of the 216.
 #define VT_CELLS 1000
 #define VT_SHELL 488
 __device__ __forceinline__ void vt_sync() {
@@ -309,9 +200,9 @@ __global__ void k_vccs_tile_starts(const uint32_t* __restrict__ head, const uint
   if (head[v]) tile_start[scan[v] - 1u] = (uint32_t)v;
   if (v == V - 1) tile_start[scan[v]] = (uint32_t)V;
 }
-// Round 4, second step: the same arrangement BUILDS the tiles.  The wavefront writes the ids of its own voxels into the 10^3 array,
-// looks the 488 cells of the shell up in the brick table (five times fewer probes than 26 per voxel), and the array then answers
-// "who is my neighbour" for the normals: the [26][V] neighbour table of k_vccs_neighbours is neither written nor read.
+// The same arrangement BUILDS the tiles.  The wavefront writes the ids of its own voxels into the 10^3 array, looks the 488 cells of
+// the shell up in the brick table (five times fewer probes than 26 per voxel), and the array then answers "who is my neighbour" for
+// the normals: no per-voxel neighbour table is built.
 __global__ __launch_bounds__(64) void k_vccs_tile_setup(const uint64_t* __restrict__ vox_code, int depth, const Brick* __restrict__ bricks, uint32_t hbits,
                                                         const float* __restrict__ cen, const uint32_t* __restrict__ tile_start, uint16_t* __restrict__ cell,
                                                         float* __restrict__ nrm, uint2* __restrict__ halo, unsigned long long pool_cap,
@@ -361,7 +252,7 @@ __global__ __launch_bounds__(64) void k_vccs_tile_setup(const uint64_t* __restri
   const bool fits = off + (unsigned long long)n <= pool_cap;   // always (a voxel lies in the shell of at most seven tiles)
   if (fits) for (int i = lane; i < n; i += 64) halo[off + (unsigned long long)i] = s_ent[i];
   if (lane == 0) meta[t] = fits ? make_uint2((uint32_t)off, (uint32_t)n) : make_uint2(0u, 0u);
-  // the voxel normals from the neighbourhood's centroids, neighbours in the order of vccs_offset as k_vccs_neighbours takes them
+  // the voxel normals from the neighbourhood's centroids, neighbours in the order of vccs_offset (the oracle's order)
   // (vccs_mode 1 has its own two-ring normals: nrm is null)
   if (nrm == nullptr) return;
   for (uint32_t v = ts + (uint32_t)lane; v < te; v += 64u) {
@@ -529,19 +420,6 @@ __global__ __launch_bounds__(64) void k_vccs_expand_tiles(int T, const uint32_t*
   }
 }
 
-__global__ void k_vccs_accumulate(int64_t V, const int32_t* __restrict__ label, const float* __restrict__ cen, const float* __restrict__ nrm,
-                                  long long* __restrict__ sums /* 6 per supervoxel */, unsigned int* __restrict__ count) {
-  int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  const int l = label[v];
-  if (l < 0) return;
-  for (int a = 0; a < 3; ++a) {
-    atomicAdd((unsigned long long*)&sums[6 * l + a], (unsigned long long)vccs_fix_pos(cen[3 * v + a]));
-    atomicAdd((unsigned long long*)&sums[6 * l + 3 + a], (unsigned long long)vccs_fix_nrm(nrm[3 * v + a]));
-  }
-  atomicAdd(&count[l], 1u);
-}
-
 __global__ void k_vccs_update(int K, const long long* __restrict__ sums, const unsigned int* __restrict__ count, VccsState* __restrict__ st) {
   int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= K) return;
@@ -550,7 +428,7 @@ __global__ void k_vccs_update(int K, const long long* __restrict__ sums, const u
 }
 
 // refinement: new seed = member voxel closest to the supervoxel centroid (smallest (distance^2, voxel id) key).  The minimum
-// is first taken per workgroup in an LDS table keyed by label (see k_vccs_expand), then once per table entry in memory.
+// is first taken per workgroup in an LDS table keyed by label (VX_SLOTS), then once per table entry in memory.
 __global__ __launch_bounds__(256) void k_vccs_reseed(int64_t V, const int32_t* __restrict__ label, const float* __restrict__ cen,
                                                      const VccsState* __restrict__ st, unsigned long long* __restrict__ seed_key) {
   __shared__ int s_key[VX_SLOTS];
@@ -607,55 +485,16 @@ __global__ void k_vccs_point_labels(const uint32_t* __restrict__ perm, const uin
 // Divergences from PCL that remain: the lattice is the class's own octree's (PCL's adjacency octree anchors at the
 // cloud's minimum corner) and the seed grid hangs on it; re-seeding searches the supervoxel's own voxels (PCL: kd-tree over all);
 // refineNormals is skipped; FLANN's tie order is replaced by (distance, voxel id); centroid sums are fixed point.
-__device__ __forceinline__ int vccs_nbr27(const int32_t* __restrict__ nbr, int64_t V, int64_t v, int o) {
-  int dx, dy, dz;
-  vccs_offset27(o, &dx, &dy, &dz);
-  if (dx == 0 && dy == 0 && dz == 0) return (int)v;
-  return nbr[(int64_t)vccs_index26(dx, dy, dz) * V + v];
-}
-
-// owner == null: computeVoxelData's two-ring normals of every voxel.  owner != null (round 5): SupervoxelHelper::refineNormals -- only the
-// leaves of the voxel's own supervoxel count, in both rings, the voxel itself is not listed up front, an unowned voxel keeps its normal
-__global__ void k_pcl_accu1(int64_t V, const int32_t* __restrict__ nbr, const float* __restrict__ cen, VccsAccu* __restrict__ A1,
-                            const int32_t* __restrict__ owner) {
-  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= V) return;
-  const int k = owner ? owner[t] : 0;
-  if (k < 0) return;
-  VccsAccu A;
-  vccs_accu_zero(&A);
-  for (int o = 0; o < 27; ++o) { const int u = vccs_nbr27(nbr, V, t, o); if (u >= 0 && (!owner || owner[u] == k)) vccs_accu_point(&A, &cen[3 * (int64_t)u]); }
-  A1[t] = A;
-}
-
-__global__ void k_pcl_normals(int64_t V, const int32_t* __restrict__ nbr, const float* __restrict__ cen, const VccsAccu* __restrict__ A1,
-                              float* __restrict__ nrm, const int32_t* __restrict__ owner) {
-  int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  const int k = owner ? owner[v] : 0;
-  if (k < 0) return;
-  VccsAccu A;
-  vccs_accu_zero(&A);
-  if (!owner) vccs_accu_point(&A, &cen[3 * v]);
-  for (int o = 0; o < 27; ++o) {
-    const int t = vccs_nbr27(nbr, V, v, o);
-    if (t < 0 || (owner && owner[t] != k)) continue;
-    vccs_accu_point(&A, &cen[3 * (int64_t)t]);
-    const VccsAccu B = A1[t];
-    vccs_accu_add(&A, &B);
-  }
-  float n[3];
-  vccs_accu_normal(&A, &cen[3 * v], n);
-  nrm[3 * v] = n[0]; nrm[3 * v + 1] = n[1]; nrm[3 * v + 2] = n[2];
-}
-
-// The same two kernels over the tiles of k_vccs_tile_setup (round 6): the tile's 10^3 array of voxel ids -- its own voxels and the shell, from
-// the lists the live sweeps use -- answers "who is my neighbour at offset o", so the [26][V] table (26 x 4 bytes per voxel and kernel: three
-// quarters of either kernel's traffic) is neither read nor, over tiles, built.  Same neighbours in the same order (vccs_offset27: dx outermost),
-// same operations: the accumulators and normals are bit for bit those of k_pcl_accu1 / k_pcl_normals.
+// computeVoxelData's two-ring normals over the tiles of k_vccs_tile_setup, in two kernels: the first (NORMALS false) writes every voxel's
+// 1-ring accumulator, the second adds the 1-rings of the voxel's 27-neighbourhood up and turns them into the normal.  owner == null: the
+// normals of every voxel.  owner != null: SupervoxelHelper::refineNormals -- only the leaves of the voxel's own supervoxel count, in both
+// rings, the voxel itself is not listed up front, an unowned voxel keeps its normal.
+// The tile's 10^3 array of voxel ids -- its own voxels and the shell, from the lists the live sweeps use -- answers "who is my neighbour at
+// offset o", so no per-voxel neighbour table (26 x 4 bytes per voxel and kernel: three quarters of either kernel's traffic) is built or read.
+// Neighbours in the order of vccs_offset27 (dx outermost), the operations of vccs_accu_*: the oracle's accumulators and normals, bit for bit.
 // What the neighbours contribute to both kernels -- owner and centroid -- is staged in LDS once per tile as well (entry = the tile's voxels, then
-// its shell); the second kernel reads the first one's 40-byte accumulators from L2, a kilobyte per voxel, and that is what it waits for with or
-// without the table.  A tile with more entries than the arrays hold (a solid block: up to 1000) reads everything from memory as before.
+// its shell); the second kernel reads the first one's 40-byte accumulators from L2, a kilobyte per voxel, and that is what it waits for.  A
+// tile with more entries than the arrays hold (a solid block: up to 1000) reads everything from memory.
 #define VTN_TB 128
 #ifndef VTN_CAP
 #define VTN_CAP 448
@@ -855,121 +694,6 @@ __global__ void k_pcl_plant_again(const unsigned long long* __restrict__ seed_ke
   atomicMax(&owner[(uint32_t)seed_key[k]], k);
 }
 
-// The offers a voxel gets in one round, folded in label order: the supervoxels < limit that touch it through a live leaf of
-// its 27-neighbourhood (itself included).  Returns the owner after the fold; *d_out its recorded distance.
-__device__ __forceinline__ int vccs_pcl_fold(int64_t V, int64_t v, const int32_t* __restrict__ nbr, const int32_t* __restrict__ owner0,
-                                             const float* __restrict__ dist0, const uint8_t* __restrict__ live, const float* __restrict__ cen,
-                                             const float* __restrict__ nrm, const VccsState* __restrict__ st, float w_s_over_seed, float w_n, int limit,
-                                             float* d_out) {
-  int lab[27];
-  int nl = 0;
-  const int own = owner0[v];
-  for (int o = 0; o < 27; ++o) {
-    const int l = vccs_nbr27(nbr, V, v, o);
-    if (l < 0) continue;
-    const int s = owner0[l];
-    // an offer of the voxel's own owner changes nothing as long as nobody else offers: it is kept in the list only for the case
-    // that another supervoxel takes the voxel first, so the live flag of such a leaf is not even loaded when it cannot matter
-    if (s < 0 || s >= limit) continue;
-    if (!live[l]) continue;
-    int pos = nl;
-    bool dup = false;
-    for (int q = 0; q < nl; ++q) if (lab[q] == s) { dup = true; break; }
-    if (dup) continue;
-    while (pos > 0 && lab[pos - 1] > s) { lab[pos] = lab[pos - 1]; --pos; }   // insertion: ascending labels
-    lab[pos] = s;
-    ++nl;
-  }
-  int cur = own;
-  float cd = dist0[v];
-  if (nl == 0 || (nl == 1 && lab[0] == own)) { *d_out = cd; return cur; }   // interior voxel: nobody else reaches it
-  const float c[3] = {cen[3 * v], cen[3 * v + 1], cen[3 * v + 2]};
-  const float n[3] = {nrm[3 * v], nrm[3 * v + 1], nrm[3 * v + 2]};
-  for (int q = 0; q < nl; ++q) {
-    const int s = lab[q];
-    if (s == cur) continue;
-    const float d = vccs_distance(c, n, st[s].c, st[s].n, w_s_over_seed, w_n);
-    if (d < cd) { cd = d; cur = s; }
-  }
-  *d_out = cd;
-  return cur;
-}
-
-// one sweep of the live flags: a leaf of S is live iff the offers of the supervoxels before S leave it with S
-__global__ void k_pcl_live(int64_t V, const int32_t* __restrict__ nbr, const int32_t* __restrict__ owner0, const float* __restrict__ dist0,
-                           const uint8_t* __restrict__ live_in, const float* __restrict__ cen, const float* __restrict__ nrm,
-                           const VccsState* __restrict__ st, float w_s_over_seed, float w_n, uint8_t* __restrict__ live_out,
-                           unsigned int* __restrict__ changed) {
-  int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  const int s = owner0[v];
-  uint8_t l = 0;
-  if (s >= 0) {
-    float d;
-    l = vccs_pcl_fold(V, v, nbr, owner0, dist0, live_in, cen, nrm, st, w_s_over_seed, w_n, s, &d) == s ? 1 : 0;
-  }
-  live_out[v] = l;
-  if (l != live_in[v]) atomicOr(changed, 1u);
-}
-
-__global__ void k_pcl_live_init(int64_t V, const int32_t* __restrict__ owner, uint8_t* __restrict__ live) {
-  int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v < V) live[v] = owner[v] >= 0 ? 1 : 0;
-}
-
-__global__ void k_pcl_claim(int64_t V, const int32_t* __restrict__ nbr, const int32_t* __restrict__ owner0, const float* __restrict__ dist0,
-                            const uint8_t* __restrict__ live, const float* __restrict__ cen, const float* __restrict__ nrm,
-                            const VccsState* __restrict__ st, float w_s_over_seed, float w_n, int32_t* __restrict__ owner1, float* __restrict__ dist1) {
-  int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  float d;
-  owner1[v] = vccs_pcl_fold(V, v, nbr, owner0, dist0, live, cen, nrm, st, w_s_over_seed, w_n, 0x7fffffff, &d);
-  dist1[v] = d;
-}
-
-// per-supervoxel sums of all leaves: added up per workgroup in an LDS table keyed by label first (a workgroup's 256 voxels are
-// neighbours in space and belong to a handful of supervoxels), one global atomic per (workgroup, supervoxel, component)
-__global__ __launch_bounds__(256) void k_pcl_accumulate(int64_t V, const int32_t* __restrict__ label, const float* __restrict__ cen,
-                                                        const float* __restrict__ nrm, long long* __restrict__ sums, unsigned int* __restrict__ count) {
-  __shared__ int s_key[VX_SLOTS];
-  __shared__ unsigned long long s_sum[VX_SLOTS][6];
-  __shared__ int s_cnt[VX_SLOTS];
-  for (int k = threadIdx.x; k < VX_SLOTS; k += blockDim.x) {
-    s_key[k] = -1; s_cnt[k] = 0;
-    for (int a = 0; a < 6; ++a) s_sum[k][a] = 0ull;
-  }
-  __syncthreads();
-  int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v < V) {
-    const int l = label[v];
-    if (l >= 0) {
-      long long f[6];
-      for (int a = 0; a < 3; ++a) { f[a] = vccs_fix_pos(cen[3 * v + a]); f[3 + a] = vccs_fix_nrm(nrm[3 * v + a]); }
-      int slot = -1;
-      unsigned int h = ((unsigned int)l * 2654435761u) >> 25;   // 7 bits
-      for (int probe = 0; probe < VX_SLOTS; ++probe) {
-        const int prev = atomicCAS(&s_key[h], -1, l);
-        if (prev == -1 || prev == l) { slot = (int)h; break; }
-        h = (h + 1) & (VX_SLOTS - 1);
-      }
-      if (slot >= 0) {
-        for (int a = 0; a < 6; ++a) atomicAdd(&s_sum[slot][a], (unsigned long long)f[a]);
-        atomicAdd(&s_cnt[slot], 1);
-      } else {   // a full table sends the contribution straight to memory
-        for (int a = 0; a < 6; ++a) atomicAdd((unsigned long long*)&sums[6 * l + a], (unsigned long long)f[a]);
-        atomicAdd(&count[l], 1u);
-      }
-    }
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < VX_SLOTS; k += blockDim.x) {
-    const int l = s_key[k];
-    if (l < 0) continue;
-    for (int a = 0; a < 6; ++a) { const unsigned long long x = s_sum[k][a]; if (x) atomicAdd((unsigned long long*)&sums[6 * l + a], x); }
-    if (s_cnt[k] > 0) atomicAdd(&count[l], (unsigned int)s_cnt[k]);
-  }
-}
-
 __global__ void k_pcl_update(int K, const long long* __restrict__ sums, const unsigned int* __restrict__ count, VccsState* __restrict__ st,
                              uint8_t* __restrict__ alive) {
   int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -983,12 +707,12 @@ __global__ void k_pcl_max_label(int K, const uint8_t* __restrict__ alive, unsign
   if (k < K && alive[k]) atomicMax(out, (unsigned int)(k + 1));
 }
 
-// ---- vccs_mode 1 over tiles (round 4).  The live sweeps and the final claim read, for each of a voxel's 27 cells, the owner and the
+// ---- vccs_mode 1's rounds over tiles.  The live sweeps and the final claim read, for each of a voxel's 27 cells, the owner and the
 // live flag: both travel in one word, P = owner << 1 | live (-1: no owner), staged per tile in the 10^3 LDS array of
 // k_vccs_expand_tiles.  The fold -- distinct owners below the limit that reach the voxel through a live leaf, in ascending label
 // order, an offer strictly below the recorded distance taking the voxel -- enumerates them as successive minima (vccs_enum_next: the
-// keys ARE the labels, so the order is the sequential one) instead of an insertion sort over 27 gathered values.
-// (round 5: also marks every tile "changed" for the round's first sweep -- was a memset per round between two dependent kernels)
+// keys ARE the labels, so the order is the sequential one).
+// (k_pclt_init also marks every tile "changed" for the round's first sweep: no memset between two dependent kernels)
 __global__ void k_pclt_init(int64_t V, const int32_t* __restrict__ owner, int32_t* __restrict__ P, uint32_t* __restrict__ tchg, int NT) {
   int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (v < V) { const int s = owner[v]; P[v] = s < 0 ? -1 : ((s << 1) | 1); }
@@ -996,7 +720,7 @@ __global__ void k_pclt_init(int64_t V, const int32_t* __restrict__ owner, int32_
 }
 template <bool CLAIM>
 __global__ __launch_bounds__(64) void k_pclt_sweep(const uint32_t* __restrict__ tile_start, const uint2* __restrict__ meta, const uint2* __restrict__ halo,
-                                                   const uint16_t* __restrict__ cell, const int32_t* P_in /* may be P_out: in-place sweeps */, const float* __restrict__ dist0,
+                                                   const uint16_t* __restrict__ cell, const int32_t* P_in /* the live sweeps pass P_out: in place */, const float* __restrict__ dist0,
                                                    const float* __restrict__ cen, const float* __restrict__ nrm, const VccsState* __restrict__ st,
                                                    float w_s_over_seed, float w_n, int32_t* P_out, unsigned int* __restrict__ changed,
                                                    int32_t* __restrict__ owner1, float* __restrict__ dist1, long long* __restrict__ sums,
@@ -1005,16 +729,12 @@ __global__ __launch_bounds__(64) void k_pclt_sweep(const uint32_t* __restrict__ 
                                                    unsigned int* __restrict__ dbg_moved = nullptr) {
   // A sweep's output for a tile is a function of the flags in its window -- its own voxels and the shell, which lie in the tile and in
   // the tiles on its 26 sides.  If none of these changed a flag in the previous sweep, the window is what it was then and so is the
-  // output: the tile copies its flags and is done.  From the second sweep of a round on most tiles are that quiet.
+  // output: the tile's flags already hold it, and the tile is done.  From the second sweep of a round on most tiles are that quiet.
   if (!CLAIM && tchg_in) {
     const int t = (int)blockIdx.x, lane = threadIdx.x;
     uint32_t f = 0u;
     if (lane < 27) { const int nt = lane == 13 ? t : nbr_tiles[(int64_t)t * 27 + lane]; if (nt >= 0) f = tchg_in[nt]; }
     if (__ballot(f != 0u) == 0ull) {
-      if (P_out != P_in) {   // (in place -- round 6 -- a quiet tile has nothing to copy)
-        const uint32_t ts = tile_start[t], te = tile_start[t + 1];
-        for (uint32_t v = ts + (uint32_t)lane; v < te; v += 64u) P_out[v] = P_in[v];
-      }
       if (lane == 0) tchg_out[t] = 0u;
       return;
     }
@@ -1172,53 +892,38 @@ static vgs_status vgs_stage_vccs_pcl(vgs_ctx* c) {
   const unsigned nbV = (unsigned)((V + TB - 1) / TB);
   DevBuf<float>& cen = c->vc_cen; DevBuf<float>& nrm = c->vc_nrm; DevBuf<float>& dist = c->vc_dist;
   VGS_HIP_TRY(c, cen.ensure(3 * V)); VGS_HIP_TRY(c, nrm.ensure(3 * V)); VGS_HIP_TRY(c, dist.ensure(2 * V));
-  const bool tiles = !c->K.no_vccs_tiles;
-  const bool tile_normals = tiles && !c->K.vccs_nbr_normals;   // (round 6) the two-ring normals over the tiles: no [26][V] neighbour table
-  if (!tile_normals) VGS_HIP_TRY(c, c->vc_nbr.ensure(26 * V));
   VGS_HIP_TRY(c, c->vc_label.ensure(2 * V));
   static_assert(sizeof(VccsAccu) == 40, "VccsAccu");
-  VGS_HIP_TRY(c, c->vc_accu.ensure(10 * (size_t)V)); VGS_HIP_TRY(c, c->vc_live.ensure(2 * (size_t)V));
+  VGS_HIP_TRY(c, c->vc_accu.ensure(10 * (size_t)V));
   VGS_HIP_TRY(c, c->counters.ensure(64));
   hipLaunchKernelGGL(k_vccs_centroid, dim3(nbV), dim3(TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, V, cen.p);
   { vgs_status bs = vgs_build_bricks(c, nullptr); if (bs != VGS_OK) return bs; }
-  // the 26-neighbour table (no 1-ring normals: the 2-ring ones follow)
-  if (!tile_normals)
-    hipLaunchKernelGGL(k_vccs_neighbours, dim3(nbV), dim3(TB), 0, c->stream, c->vox_code.p, V, c->box.depth, (const Brick*)c->hkey.p, c->hbits, cen.p,
-                       c->vc_nbr.p, (float*)nullptr, (int4*)nullptr);
-  // tiles for the live sweeps and the claim (k_pclt_sweep)
-  int NT = 0;
-  if (tiles) {
-    VGS_HIP_TRY(c, c->head_flag.ensure(V + 1)); VGS_HIP_TRY(c, c->perm_a.ensure(V + 1));
-    size_t scan_bytes_t = 0;
-    VGS_HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_bytes_t, c->head_flag.p, c->perm_a.p, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
-    VGS_HIP_TRY(c, c->sort_tmp.ensure(scan_bytes_t));
-    VGS_HIP_TRY(c, c->vc_tile_start.ensure(V + 1));
-    hipLaunchKernelGGL(k_vccs_tile_heads, dim3(nbV), dim3(TB), 0, c->stream, c->vox_code.p, V, c->head_flag.p);
-    VGS_HIP_TRY(c, rocprim::inclusive_scan(c->sort_tmp.p, scan_bytes_t, c->head_flag.p, c->perm_a.p, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
-    VGS_HIP_TRY(c, c->vc_tile_of.ensure(V));
-    hipLaunchKernelGGL(k_vccs_tile_starts, dim3(nbV), dim3(TB), 0, c->stream, c->head_flag.p, c->perm_a.p, V, c->vc_tile_start.p, c->vc_tile_of.p);
-    uint32_t T32 = 0;
-    VGS_READBACK(c, &T32, c->perm_a.p + (V - 1), 4);
-    NT = (int)T32;
-    const unsigned long long pool_cap = 7ull * (unsigned long long)V;
-    VGS_HIP_TRY(c, c->vc_cell.ensure(V)); VGS_HIP_TRY(c, c->vc_halo.ensure(pool_cap));
-    VGS_HIP_TRY(c, c->vc_tile_meta.ensure(NT)); VGS_HIP_TRY(c, c->vc_pool.ensure(1)); VGS_HIP_TRY(c, c->vc_plive.ensure(2 * (size_t)V));
-    VGS_HIP_TRY(c, c->vc_nbr_tiles.ensure(27 * (size_t)NT)); VGS_HIP_TRY(c, c->vc_tchg.ensure(2 * (size_t)NT));
-    VGS_HIP_TRY(c, hipMemsetAsync(c->vc_pool.p, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_vccs_tile_setup, dim3((unsigned)NT), dim3(64), 0, c->stream, c->vox_code.p, c->box.depth, (const Brick*)c->hkey.p, c->hbits, cen.p,
-                       c->vc_tile_start.p, c->vc_cell.p, (float*)nullptr, (uint2*)c->vc_halo.p, pool_cap, (unsigned long long*)c->vc_pool.p,
-                       (uint2*)c->vc_tile_meta.p, (const uint32_t*)c->vc_tile_of.p, c->vc_nbr_tiles.p);
-  }
+  // tiles for the two-ring normals, the live sweeps and the claim
+  VGS_HIP_TRY(c, c->head_flag.ensure(V + 1)); VGS_HIP_TRY(c, c->perm_a.ensure(V + 1));
+  size_t scan_bytes_t = 0;
+  VGS_HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_bytes_t, c->head_flag.p, c->perm_a.p, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
+  VGS_HIP_TRY(c, c->sort_tmp.ensure(scan_bytes_t));
+  VGS_HIP_TRY(c, c->vc_tile_start.ensure(V + 1));
+  hipLaunchKernelGGL(k_vccs_tile_heads, dim3(nbV), dim3(TB), 0, c->stream, c->vox_code.p, V, c->head_flag.p);
+  VGS_HIP_TRY(c, rocprim::inclusive_scan(c->sort_tmp.p, scan_bytes_t, c->head_flag.p, c->perm_a.p, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
+  VGS_HIP_TRY(c, c->vc_tile_of.ensure(V));
+  hipLaunchKernelGGL(k_vccs_tile_starts, dim3(nbV), dim3(TB), 0, c->stream, c->head_flag.p, c->perm_a.p, V, c->vc_tile_start.p, c->vc_tile_of.p);
+  uint32_t T32 = 0;
+  VGS_READBACK(c, &T32, c->perm_a.p + (V - 1), 4);
+  const int NT = (int)T32;
+  const unsigned long long pool_cap = 7ull * (unsigned long long)V;
+  VGS_HIP_TRY(c, c->vc_cell.ensure(V)); VGS_HIP_TRY(c, c->vc_halo.ensure(pool_cap));
+  VGS_HIP_TRY(c, c->vc_tile_meta.ensure(NT)); VGS_HIP_TRY(c, c->vc_pool.ensure(1)); VGS_HIP_TRY(c, c->vc_plive.ensure(V));
+  VGS_HIP_TRY(c, c->vc_nbr_tiles.ensure(27 * (size_t)NT)); VGS_HIP_TRY(c, c->vc_tchg.ensure(2 * (size_t)NT));
+  VGS_HIP_TRY(c, hipMemsetAsync(c->vc_pool.p, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_vccs_tile_setup, dim3((unsigned)NT), dim3(64), 0, c->stream, c->vox_code.p, c->box.depth, (const Brick*)c->hkey.p, c->hbits, cen.p,
+                     c->vc_tile_start.p, c->vc_cell.p, (float*)nullptr, (uint2*)c->vc_halo.p, pool_cap, (unsigned long long*)c->vc_pool.p,
+                     (uint2*)c->vc_tile_meta.p, (const uint32_t*)c->vc_tile_of.p, c->vc_nbr_tiles.p);
   auto two_ring_normals = [&](const int32_t* owner) {   // computeVoxelData (owner == null) / SupervoxelHelper::refineNormals
-    if (tile_normals) {
-      hipLaunchKernelGGL(k_pclt_normals<false>, dim3((unsigned)NT), dim3(VTN_TB), 0, c->stream, c->vc_tile_start.p, (const uint2*)c->vc_tile_meta.p, (const uint2*)c->vc_halo.p,
-                         c->vc_cell.p, cen.p, (VccsAccu*)c->vc_accu.p, (float*)nullptr, owner);
-      hipLaunchKernelGGL(k_pclt_normals<true>, dim3((unsigned)NT), dim3(VTN_TB), 0, c->stream, c->vc_tile_start.p, (const uint2*)c->vc_tile_meta.p, (const uint2*)c->vc_halo.p,
-                         c->vc_cell.p, cen.p, (VccsAccu*)c->vc_accu.p, nrm.p, owner);
-    } else {
-      hipLaunchKernelGGL(k_pcl_accu1, dim3(nbV), dim3(TB), 0, c->stream, V, c->vc_nbr.p, cen.p, (VccsAccu*)c->vc_accu.p, owner);
-      hipLaunchKernelGGL(k_pcl_normals, dim3(nbV), dim3(TB), 0, c->stream, V, c->vc_nbr.p, cen.p, (const VccsAccu*)c->vc_accu.p, nrm.p, owner);
-    }
+    hipLaunchKernelGGL(k_pclt_normals<false>, dim3((unsigned)NT), dim3(VTN_TB), 0, c->stream, c->vc_tile_start.p, (const uint2*)c->vc_tile_meta.p, (const uint2*)c->vc_halo.p,
+                       c->vc_cell.p, cen.p, (VccsAccu*)c->vc_accu.p, (float*)nullptr, owner);
+    hipLaunchKernelGGL(k_pclt_normals<true>, dim3((unsigned)NT), dim3(VTN_TB), 0, c->stream, c->vc_tile_start.p, (const uint2*)c->vc_tile_meta.p, (const uint2*)c->vc_halo.p,
+                       c->vc_cell.p, cen.p, (VccsAccu*)c->vc_accu.p, nrm.p, owner);
   };
   two_ring_normals(nullptr);
   // ---- seeds ----
@@ -1276,9 +981,8 @@ static vgs_status vgs_stage_vccs_pcl(vgs_ctx* c) {
   const float w_s_over_seed = c->P.spatial_impt / seed, w_n = c->P.normal_impt;
   int32_t* own[2] = {c->vc_label.p, c->vc_label.p + V};
   float* dst[2] = {dist.p, dist.p + V};
-  uint8_t* live[2] = {c->vc_live.p, c->vc_live.p + V};
-  int32_t* plive[2] = {tiles ? c->vc_plive.p : nullptr, tiles ? c->vc_plive.p + V : nullptr};
-  uint32_t* tchg[2] = {tiles ? c->vc_tchg.p : nullptr, tiles ? c->vc_tchg.p + NT : nullptr};   // per tile: a flag changed in that sweep
+  int32_t* const plive = c->vc_plive.p;
+  uint32_t* tchg[2] = {c->vc_tchg.p, c->vc_tchg.p + NT};   // per tile: a flag changed in that sweep
   // the sweeps' change counters: a ring of words zeroed once per pass (was a memset in front of every batch of sweeps: 80 per step)
   constexpr int RING = 4096;
   VGS_HIP_TRY(c, c->vc_ring.ensure(RING));
@@ -1290,10 +994,9 @@ static vgs_status vgs_stage_vccs_pcl(vgs_ctx* c) {
   if (c->K.debug) { VGS_HIP_TRY(c, c->vc_dbg.ensure(128)); VGS_HIP_TRY(c, hipMemsetAsync(c->vc_dbg.p, 0, 512, c->stream)); dbg_moved = c->vc_dbg.p; }
   hipLaunchKernelGGL(k_pcl_reset, dim3(nbV), dim3(TB), 0, c->stream, V, own[cur], dst[cur]);
   hipLaunchKernelGGL(k_pcl_plant_first, dim3(nbK), dim3(TB), 0, c->stream, seeds, K, cen.p, nrm.p, own[cur], state, c->vc_alive.p);
-  if (tiles) hipLaunchKernelGGL(k_pclt_seed_sums, dim3(nbK), dim3(TB), 0, c->stream, K, (const int32_t*)seeds, (const unsigned long long*)nullptr, (const uint8_t*)nullptr,
-                                cen.p, nrm.p, c->vc_sums.p, c->vc_count.p, (const int32_t*)nullptr);
+  hipLaunchKernelGGL(k_pclt_seed_sums, dim3(nbK), dim3(TB), 0, c->stream, K, (const int32_t*)seeds, (const unsigned long long*)nullptr, (const uint8_t*)nullptr,
+                     cen.p, nrm.p, c->vc_sums.p, c->vc_count.p, (const int32_t*)nullptr);
   int dbg_settled[16] = {0};   // VGS_DEBUG: rounds by the index of their first sweep that changed nothing
-  const bool inplace = tiles && !c->K.vccs_pingpong;   // (VGS_VCCS_PINGPONG: the sweeps alternate between two flag arrays, as until round 5)
   for (int pass = 0; pass < 6; ++pass) {
     if (pass > 0) {
       // refineSupervoxels: refineNormals of every supervoxel (from its own leaves), reseedSupervoxels (nearest of all voxels), expansion
@@ -1302,59 +1005,45 @@ static vgs_status vgs_stage_vccs_pcl(vgs_ctx* c) {
                          (const Brick*)c->hkey.p, c->hbits, c->box.depth, c->box.min[0], c->box.min[1], c->box.min[2], c->box.res, res, seed_key);
       hipLaunchKernelGGL(k_pcl_reset, dim3(nbV), dim3(TB), 0, c->stream, V, own[cur], dst[cur]);
       hipLaunchKernelGGL(k_pcl_plant_again, dim3(nbK), dim3(TB), 0, c->stream, seed_key, K, c->vc_alive.p, own[cur]);
-      if (tiles) hipLaunchKernelGGL(k_pclt_seed_sums, dim3(nbK), dim3(TB), 0, c->stream, K, (const int32_t*)nullptr, (const unsigned long long*)seed_key,
-                                    (const uint8_t*)c->vc_alive.p, cen.p, nrm.p, c->vc_sums.p, c->vc_count.p, (const int32_t*)own[cur]);
+      hipLaunchKernelGGL(k_pclt_seed_sums, dim3(nbK), dim3(TB), 0, c->stream, K, (const int32_t*)nullptr, (const unsigned long long*)seed_key,
+                         (const uint8_t*)c->vc_alive.p, cen.p, nrm.p, c->vc_sums.p, c->vc_count.p, (const int32_t*)own[cur]);
     }
     for (int it = 1; it < depth; ++it) {
       int lc = 0;
-      if (tiles) hipLaunchKernelGGL(k_pclt_init, dim3(nbV), dim3(TB), 0, c->stream, V, own[cur], plive[lc], tchg[lc], NT);   // (NT <= V) the first sweep of a round works every tile
-      else hipLaunchKernelGGL(k_pcl_live_init, dim3(nbV), dim3(TB), 0, c->stream, V, own[cur], live[lc]);
+      hipLaunchKernelGGL(k_pclt_init, dim3(nbV), dim3(TB), 0, c->stream, V, own[cur], plive, tchg[lc], NT);   // (NT <= V) the first sweep of a round works every tile
       // fixed point of the live flags: the recursion is on smaller labels, so it ends -- a sweep that changes nothing is the proof.
-      // Sweeps go out in pairs with one read-back per pair (a sweep at the fixed point changes nothing, so a spare one is harmless):
-      // half the host round trips.  Leaving the loop without that proof would give labels that differ from the sequential
-      // order silently: it is an error.
-      // Over tiles a sweep at the fixed point costs a few microseconds (every tile is quiet), a host round trip costs thirty: the first
-      // batch of a round is four sweeps (a round needs four or five; six were measured slower than pairs), later ones are pairs.
+      // Sweeps go out in batches with one read-back per batch (a sweep at the fixed point changes nothing, so a spare one is harmless).
+      // Leaving the loop without that proof would give labels that differ from the sequential order silently: it is an error.
+      // A sweep at the fixed point costs a few microseconds (every tile is quiet), a host round trip costs thirty: the first batch of a
+      // round is four sweeps (a round needs four or five; six were measured slower than pairs), later ones are pairs.
       bool settled = false;
-      for (int sweep = 0, nb = tiles ? 4 : 2; sweep < 4096 && !settled; sweep += nb, nb = 2) {
+      for (int sweep = 0, nb = 4; sweep < 4096 && !settled; sweep += nb, nb = 2) {
         unsigned int ch[6] = {1u, 1u, 1u, 1u, 1u, 1u};
         if (ring_at + nb > RING) { VGS_HIP_TRY(c, hipMemsetAsync(d_ring, 0, (size_t)RING * 4, c->stream)); ring_at = 0; }
         unsigned int* const d_chg = d_ring + ring_at;
         ring_at += nb;
         for (int k = 0; k < nb; ++k) {
-          if (tiles)
-            // In place (round 6): a tile reads its window from the one flag array and writes its own voxels back into it.  Another tile may
-            // read them before or after -- an asynchronous iteration, and the fixed point of the live flags is unique (the recursion is on
-            // smaller labels), so it is reached whatever the order; the proof of arrival is unchanged (a sweep in which nobody wrote read only
-            // final values), and so is the quiet-tile test (a tile whose window tiles wrote nothing in the last sweep read what is there now).
-            // Quiet tiles then copy nothing, and news travels within a sweep.  The per-tile change flags still alternate.
-            hipLaunchKernelGGL(k_pclt_sweep<false>, dim3((unsigned)NT), dim3(64), 0, c->stream, c->vc_tile_start.p, (const uint2*)c->vc_tile_meta.p,
-                               (const uint2*)c->vc_halo.p, c->vc_cell.p, plive[inplace ? 0 : lc], dst[cur], cen.p, nrm.p, state, w_s_over_seed, w_n, plive[inplace ? 0 : (lc ^ 1)],
-                               d_chg + k, (int32_t*)nullptr, (float*)nullptr, (long long*)nullptr, (unsigned int*)nullptr,
-                               (const int32_t*)c->vc_nbr_tiles.p, (const uint32_t*)tchg[lc], tchg[lc ^ 1]);
-          else
-            hipLaunchKernelGGL(k_pcl_live, dim3(nbV), dim3(TB), 0, c->stream, V, c->vc_nbr.p, own[cur], dst[cur], live[lc], cen.p, nrm.p, state, w_s_over_seed, w_n,
-                               live[lc ^ 1], d_chg + k);
+          // In place: a tile reads its window from the one flag array and writes its own voxels back into it.  Another tile may read
+          // them before or after -- an asynchronous iteration.  The fixed point of the live flags is unique (the recursion is on smaller
+          // labels), so it is reached whatever the order.  A sweep in which nobody wrote read only final values, so it still proves
+          // arrival; a tile whose window tiles wrote nothing in the last sweep reads what is there now, so the quiet-tile test holds.
+          // The per-tile change flags alternate between two arrays.
+          hipLaunchKernelGGL(k_pclt_sweep<false>, dim3((unsigned)NT), dim3(64), 0, c->stream, c->vc_tile_start.p, (const uint2*)c->vc_tile_meta.p,
+                             (const uint2*)c->vc_halo.p, c->vc_cell.p, plive, dst[cur], cen.p, nrm.p, state, w_s_over_seed, w_n, plive,
+                             d_chg + k, (int32_t*)nullptr, (float*)nullptr, (long long*)nullptr, (unsigned int*)nullptr,
+                             (const int32_t*)c->vc_nbr_tiles.p, (const uint32_t*)tchg[lc], tchg[lc ^ 1]);
           lc ^= 1;
         }
         VGS_READBACK(c, ch, d_chg, 4 * (size_t)nb);
-        for (int k = 0; k < nb; ++k) { if (!settled && !ch[k] && c->K.debug) ++dbg_settled[std::min(sweep + k, 15)]; settled = settled || !ch[k]; }   // (after an unchanged sweep the two flag arrays are equal: either is the fixed point)
+        for (int k = 0; k < nb; ++k) { if (!settled && !ch[k] && c->K.debug) ++dbg_settled[std::min(sweep + k, 15)]; settled = settled || !ch[k]; }
       }
       if (!settled) { c->err = "svgs_supervoxels (vccs_mode 1): the live flags did not reach their fixed point in 4096 sweeps"; return VGS_E_STATE; }
-      if (tiles)
-        hipLaunchKernelGGL(k_pclt_sweep<true>, dim3((unsigned)NT), dim3(64), 0, c->stream, c->vc_tile_start.p, (const uint2*)c->vc_tile_meta.p,
-                           (const uint2*)c->vc_halo.p, c->vc_cell.p, plive[inplace ? 0 : lc], dst[cur], cen.p, nrm.p, state, w_s_over_seed, w_n, (int32_t*)nullptr,
-                           (unsigned int*)nullptr, own[cur ^ 1], dst[cur ^ 1], c->vc_sums.p, c->vc_count.p, (const int32_t*)nullptr,
-                           (const uint32_t*)nullptr, (uint32_t*)nullptr, dbg_moved ? dbg_moved + pass * 16 + it : (unsigned int*)nullptr);
-      else
-        hipLaunchKernelGGL(k_pcl_claim, dim3(nbV), dim3(TB), 0, c->stream, V, c->vc_nbr.p, own[cur], dst[cur], live[lc], cen.p, nrm.p, state, w_s_over_seed, w_n,
-                           own[cur ^ 1], dst[cur ^ 1]);
+      // the claim moves the sums with the voxels that change owner: integers, the totals of a full re-accumulation
+      hipLaunchKernelGGL(k_pclt_sweep<true>, dim3((unsigned)NT), dim3(64), 0, c->stream, c->vc_tile_start.p, (const uint2*)c->vc_tile_meta.p,
+                         (const uint2*)c->vc_halo.p, c->vc_cell.p, plive, dst[cur], cen.p, nrm.p, state, w_s_over_seed, w_n, (int32_t*)nullptr,
+                         (unsigned int*)nullptr, own[cur ^ 1], dst[cur ^ 1], c->vc_sums.p, c->vc_count.p, (const int32_t*)nullptr,
+                         (const uint32_t*)nullptr, (uint32_t*)nullptr, dbg_moved ? dbg_moved + pass * 16 + it : (unsigned int*)nullptr);
       cur ^= 1;
-      if (!tiles) {   // (over tiles the claim moved the sums with the voxels that changed owner: integers, the same totals)
-        VGS_HIP_TRY(c, hipMemsetAsync(c->vc_sums.p, 0, 6 * (size_t)K * sizeof(long long), c->stream));
-        VGS_HIP_TRY(c, hipMemsetAsync(c->vc_count.p, 0, (size_t)K * 4, c->stream));
-        hipLaunchKernelGGL(k_pcl_accumulate, dim3(nbV), dim3(TB), 0, c->stream, V, own[cur], cen.p, nrm.p, c->vc_sums.p, c->vc_count.p);
-      }
       hipLaunchKernelGGL(k_pcl_update, dim3(nbK), dim3(TB), 0, c->stream, K, c->vc_sums.p, c->vc_count.p, state, c->vc_alive.p);
     }
   }
@@ -1432,11 +1121,6 @@ vgs_status vgs_stage_vccs(vgs_ctx* c) {
   VGS_HIP_TRY(c, c->vc_label.ensure(2 * V));
   hipLaunchKernelGGL(k_vccs_centroid, dim3(nbV), dim3(TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, V, cen.p);
   { vgs_status bs = vgs_build_bricks(c, nullptr); if (bs != VGS_OK) return bs; }
-  if (c->K.no_vccs_tiles) {
-    VGS_HIP_TRY(c, c->vc_nbr.ensure(26 * V)); VGS_HIP_TRY(c, c->vc_nbr4.ensure(28 * (size_t)V));
-    hipLaunchKernelGGL(k_vccs_neighbours, dim3(nbV), dim3(TB), 0, c->stream, c->vox_code.p, V, c->box.depth, (const Brick*)c->hkey.p, c->hbits, cen.p,
-                       c->vc_nbr.p, nrm.p, (int4*)c->vc_nbr4.p);
-  }
   // ---- seeds: one per occupied seed_res cell, snapped to the voxel nearest to the cell centre ----
   const float seed = c->P.seed_size;
   const float mnx = (float)c->box.min[0], mny = (float)c->box.min[1], mnz = (float)c->box.min[2];
@@ -1445,18 +1129,15 @@ vgs_status vgs_stage_vccs(vgs_ctx* c) {
   VGS_HIP_TRY(c, c->head_flag.ensure(V + 1)); VGS_HIP_TRY(c, c->perm_a.ensure(V + 1));
   // ---- tiles of the expansion rounds (k_vccs_expand_tiles): runs of equal code >> 9, numbered by a scan; their number comes back with
   // the number of seeds below
-  const bool tiles = !c->K.no_vccs_tiles;
   uint32_t T32 = 0;
-  if (tiles) {
-    size_t scan_bytes_t = 0;
-    VGS_HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_bytes_t, c->head_flag.p, c->perm_a.p, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
-    VGS_HIP_TRY(c, c->sort_tmp.ensure(scan_bytes_t));
-    VGS_HIP_TRY(c, c->vc_tile_start.ensure(V + 1));
-    hipLaunchKernelGGL(k_vccs_tile_heads, dim3(nbV), dim3(TB), 0, c->stream, c->vox_code.p, V, c->head_flag.p);
-    VGS_HIP_TRY(c, rocprim::inclusive_scan(c->sort_tmp.p, scan_bytes_t, c->head_flag.p, c->perm_a.p, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
-    hipLaunchKernelGGL(k_vccs_tile_starts, dim3(nbV), dim3(TB), 0, c->stream, c->head_flag.p, c->perm_a.p, V, c->vc_tile_start.p, (uint32_t*)nullptr);
-    VGS_HIP_TRY(c, hipMemcpyAsync(&T32, c->perm_a.p + (V - 1), 4, hipMemcpyDeviceToHost, c->stream));
-  }
+  size_t scan_bytes_t = 0;
+  VGS_HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_bytes_t, c->head_flag.p, c->perm_a.p, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
+  VGS_HIP_TRY(c, c->sort_tmp.ensure(scan_bytes_t));
+  VGS_HIP_TRY(c, c->vc_tile_start.ensure(V + 1));
+  hipLaunchKernelGGL(k_vccs_tile_heads, dim3(nbV), dim3(TB), 0, c->stream, c->vox_code.p, V, c->head_flag.p);
+  VGS_HIP_TRY(c, rocprim::inclusive_scan(c->sort_tmp.p, scan_bytes_t, c->head_flag.p, c->perm_a.p, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
+  hipLaunchKernelGGL(k_vccs_tile_starts, dim3(nbV), dim3(TB), 0, c->stream, c->head_flag.p, c->perm_a.p, V, c->vc_tile_start.p, (uint32_t*)nullptr);
+  VGS_HIP_TRY(c, hipMemcpyAsync(&T32, c->perm_a.p + (V - 1), 4, hipMemcpyDeviceToHost, c->stream));
   hipLaunchKernelGGL(k_vccs_cell_codes, dim3(nbV), dim3(TB), 0, c->stream, cen.p, V, mnx, mny, mnz, seed, c->cell_code_a.p, c->cell_id_a.p);
   size_t sort_bytes = 0, scan_bytes = 0;
   VGS_HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_bytes, c->cell_code_a.p, c->cell_code_b.p, c->cell_id_a.p, c->cell_id_b.p, (size_t)V, 0, 63, c->stream));
@@ -1472,15 +1153,13 @@ vgs_status vgs_stage_vccs(vgs_ctx* c) {
   const int K = (int)K32;
   const unsigned nbK = (unsigned)((K + TB - 1) / TB);
   const int NT = (int)T32;
-  if (tiles) {
-    const unsigned long long pool_cap = 7ull * (unsigned long long)V;   // a voxel lies in the shell of at most seven tiles
-    VGS_HIP_TRY(c, c->vc_cell.ensure(V)); VGS_HIP_TRY(c, c->vc_halo.ensure(pool_cap));
-    VGS_HIP_TRY(c, c->vc_tile_meta.ensure(NT)); VGS_HIP_TRY(c, c->vc_pool.ensure(1));
-    VGS_HIP_TRY(c, hipMemsetAsync(c->vc_pool.p, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_vccs_tile_setup, dim3((unsigned)NT), dim3(64), 0, c->stream, c->vox_code.p, c->box.depth, (const Brick*)c->hkey.p, c->hbits, cen.p,
-                       c->vc_tile_start.p, c->vc_cell.p, nrm.p, (uint2*)c->vc_halo.p, pool_cap, (unsigned long long*)c->vc_pool.p, (uint2*)c->vc_tile_meta.p,
-                       (const uint32_t*)nullptr, (int32_t*)nullptr);
-  }
+  const unsigned long long pool_cap = 7ull * (unsigned long long)V;   // a voxel lies in the shell of at most seven tiles
+  VGS_HIP_TRY(c, c->vc_cell.ensure(V)); VGS_HIP_TRY(c, c->vc_halo.ensure(pool_cap));
+  VGS_HIP_TRY(c, c->vc_tile_meta.ensure(NT)); VGS_HIP_TRY(c, c->vc_pool.ensure(1));
+  VGS_HIP_TRY(c, hipMemsetAsync(c->vc_pool.p, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_vccs_tile_setup, dim3((unsigned)NT), dim3(64), 0, c->stream, c->vox_code.p, c->box.depth, (const Brick*)c->hkey.p, c->hbits, cen.p,
+                     c->vc_tile_start.p, c->vc_cell.p, nrm.p, (uint2*)c->vc_halo.p, pool_cap, (unsigned long long*)c->vc_pool.p, (uint2*)c->vc_tile_meta.p,
+                     (const uint32_t*)nullptr, (int32_t*)nullptr);
   VGS_HIP_TRY(c, c->vc_seedkey.ensure(K)); VGS_HIP_TRY(c, c->vc_sums.ensure(6 * (size_t)K)); VGS_HIP_TRY(c, c->vc_count.ensure(K));
   VGS_HIP_TRY(c, c->vc_state.ensure(6 * (size_t)K));
   VccsState* state = (VccsState*)c->vc_state.p;
@@ -1503,13 +1182,9 @@ vgs_status vgs_stage_vccs(vgs_ctx* c) {
     hipLaunchKernelGGL(k_vccs_reset, dim3(nbV), dim3(TB), 0, c->stream, V, lab[cur], dst[cur]);
     hipLaunchKernelGGL(k_vccs_plant, dim3(nbK), dim3(TB), 0, c->stream, seed_key, K, cen.p, nrm.p, lab[cur], dst[cur], state, c->vc_sums.p, c->vc_count.p);
     for (int it = 0; it < T; ++it) {
-      if (tiles)
-        hipLaunchKernelGGL(k_vccs_expand_tiles, dim3((unsigned)NT), dim3(64), 0, c->stream, NT, c->vc_tile_start.p, (const uint2*)c->vc_tile_meta.p,
-                           (const uint2*)c->vc_halo.p, c->vc_cell.p, cen.p, nrm.p, lab[cur], dst[cur], state, w_s_over_seed, w_n,
-                           lab[cur ^ 1], dst[cur ^ 1], c->vc_sums.p, c->vc_count.p);
-      else
-        hipLaunchKernelGGL(k_vccs_expand, dim3(nbV), dim3(TB), 0, c->stream, V, (const int4*)c->vc_nbr4.p, cen.p, nrm.p, lab[cur], dst[cur], state, w_s_over_seed, w_n,
-                           lab[cur ^ 1], dst[cur ^ 1], c->vc_sums.p, c->vc_count.p);
+      hipLaunchKernelGGL(k_vccs_expand_tiles, dim3((unsigned)NT), dim3(64), 0, c->stream, NT, c->vc_tile_start.p, (const uint2*)c->vc_tile_meta.p,
+                         (const uint2*)c->vc_halo.p, c->vc_cell.p, cen.p, nrm.p, lab[cur], dst[cur], state, w_s_over_seed, w_n,
+                         lab[cur ^ 1], dst[cur ^ 1], c->vc_sums.p, c->vc_count.p);
       cur ^= 1;
       hipLaunchKernelGGL(k_vccs_update, dim3(nbK), dim3(TB), 0, c->stream, K, c->vc_sums.p, c->vc_count.p, state);
     }

@@ -91,24 +91,15 @@ struct VgsKnobs {
   bool no_overlap = false;   // VGS_NO_OVERLAP
   bool no_near = false;      // VGS_NO_NEAR
   bool no_adjmasks = false;  // VGS_NO_ADJMASKS
-  bool no_packed_sort = false;   // VGS_NO_PACKED_SORT: (code, index) pairs through the voxelize sort instead of one packed key
-  bool no_early_union = false;   // VGS_NO_EARLY_UNION: the union-find runs behind closestCheck as in rounds 1-3
   int vote_period = 64;          // VGS_VOTE_PERIOD (power of two): one voxel in so many of the one-wavefront classes runs as a sample
-  bool no_tile_early = false;    // VGS_NO_TILE_EARLY: a tile's first hooks and unions wait behind closestCheck (rounds 3-4)
   int cross_lds_kb = 0;          // VGS_CROSS_LDS: KB of (unused) LDS per wavefront of crossValidation's FIRST pass and its unions -- caps how many
                                  // of them a CU holds beside the hand-over kernel's workgroups, which need four wave slots at once
-  bool no_vccs_tiles = false;    // VGS_NO_VCCS_TILES: the supervoxel expansion rounds gather their 26 labels through the neighbour table
-  bool no_c0 = false;            // VGS_NO_C0: no separate class for neighbourhoods of 129..320 voxels
-  bool vccs_pingpong = false;    // VGS_VCCS_PINGPONG: (vccs_mode 1) the live-flag sweeps alternate between two arrays (A/B twin of round 6's in-place sweeps)
-  bool no_adj_wide = false;      // VGS_NO_ADJ_WIDE: rows above 2048 used neighbours keep the one-wavefront general kernel (A/B twin of round 6's workgroup per row)
-  bool no_grow_prefix = false;   // VGS_NO_GROW_PREFIX: the octree box grows by one scan launch and one adopt launch per step from the first point on
   bool no_sort32 = false;        // VGS_NO_SORT32: the one-wavefront classes of the local cut keep the 64-bit sort network (A/B twin of round 6's one-word keys)
   bool no_pg_xl = false;         // VGS_NO_PG_XL: no extra-large pair-list instantiation (neighbourhoods above 1024 voxels take the hand-over path)
   bool no_connbits = false;  // VGS_NO_CONNBITS: crossValidation searches the neighbour's row (the path of rounds 1-3)
   bool no_pairlists = false; // VGS_NO_PAIRLISTS: no pair lists (pairlist.hpp); hand-overs and wide classes take the kernels of round 4
   bool no_vote = false;      // VGS_NO_VOTE: every one-wavefront voxel tries the lazy schedule (LwParams::vote off)
   int vote_force = 0;        // VGS_VOTE_FORCE (diagnostics): every one-wavefront voxel that is not a sample is handed over
-  bool vccs_nbr_normals = false; // VGS_VCCS_NBR_NORMALS: vccs_mode 1's two-ring normals from the [26][V] neighbour table, as until round 6
   int ho_grid = -1;          // VGS_HO_GRID: workgroups of the hand-over kernels of the one-wavefront classes (-1: as many as the device holds at once; 0: one per row up to 16384)
   int pg_min_frac = 8;       // VGS_PG_MINFRAC: hand-overs go through the pair lists when they are more than 1/N of the used voxels (0: never)
   int pg_wide = 1;           // VGS_PG_WIDE: neighbourhoods above 128 voxels are cut from the pair lists (0: the multi-wavefront shell classes)
@@ -278,12 +269,11 @@ struct vgs_ctx {
   DevBuf<uint32_t> cell_id_a, cell_id_b, cell_start;
   // VCCS-style supervoxel stage
   DevBuf<float> vc_cen, vc_nrm, vc_dist, vc_state;
-  DevBuf<int32_t> vc_nbr, vc_label;
-  DevBuf<int32_t> vc_nbr4;    // vc_nbr once more as [7][V] int4 (28 entries per voxel, two unused): four neighbours to a load for the expansion rounds
+  DevBuf<int32_t> vc_label;
   DevBuf<uint32_t> vc_tile_start;   // expansion over tiles (vccs.hip): start of every 8^3 tile's run of voxels
   DevBuf<uint32_t> vc_tile_of, vc_tchg;        // vccs_mode 1: tile of every voxel; per tile "a live flag changed in that sweep" (two sweeps' worth)
   DevBuf<int32_t> vc_nbr_tiles;                // vccs_mode 1: the tiles on the 26 sides of a tile ([NT][27], -1: none)
-  DevBuf<int32_t> vc_plive;                    // vccs_mode 1 over tiles: owner << 1 | live, two sweeps' worth
+  DevBuf<int32_t> vc_plive;                    // vccs_mode 1: owner << 1 | live of every voxel, swept in place
   DevBuf<uint16_t> vc_cell;                    // a voxel's cell in its tile's 10^3 label array
   DevBuf<unsigned int> vc_ring;   // (vccs_mode 1) the sweeps' change counters of a pass
   DevBuf<unsigned int> vc_dbg;    // (vccs_mode 1, VGS_DEBUG) lanes that moved a voxel, per pass and round
@@ -292,7 +282,7 @@ struct vgs_ctx {
   DevBuf<long long> vc_sums;
   DevBuf<uint32_t> vc_count;
   DevBuf<float> vc_accu;        // vccs_mode 1: 1-ring covariance accumulators (10 floats per voxel)
-  DevBuf<uint8_t> vc_live, vc_alive;   // vccs_mode 1: leaf is expanded from at its owner's turn (two sweeps' worth); supervoxel still exists
+  DevBuf<uint8_t> vc_alive;   // vccs_mode 1: supervoxel still exists
 
   // multi-GPU
   bool have_region = false;

@@ -350,12 +350,10 @@ vgs_status vgs_grow_box_from(vgs_ctx* c, OctreeBox& box, bool record_epochs) {
   // trip or two: the points come in random order), enough to keep the HBM pipes full on the one scan that reads everything
   const int blocks = (int)std::max<int64_t>(8, std::min<int64_t>((c->N / 4 + 255) / 256 + 1, (int64_t)c->K.fv_blocks));
   // the first points in one launch (k_grow_prefix); the first batch of whole-cloud scans behind it is then two pairs, not eight
-  const bool prefix = !c->K.no_grow_prefix;
-  if (prefix)
-    hipLaunchKernelGGL(k_grow_prefix, dim3(1), dim3(1024), 0, c->stream, c->xyz, c->stride_f, std::min<int64_t>(c->N, 8192), d_g, pinned);
+  hipLaunchKernelGGL(k_grow_prefix, dim3(1), dim3(1024), 0, c->stream, c->xyz, c->stride_f, std::min<int64_t>(c->N, 8192), d_g, pinned);
   for (int batch = 0; batch < 64; ++batch) {
     // a scene grows its box about log2(extent / voxel) times; pairs queued after the last growth return at once
-    for (int k = 0; k < ((prefix && batch == 0) ? 2 : 8); ++k) {
+    for (int k = 0; k < (batch == 0 ? 2 : 8); ++k) {
       hipLaunchKernelGGL(k_first_violation, dim3(blocks), dim3(256), 0, c->stream, c->xyz, c->stride_f, c->N, d_g);
       hipLaunchKernelGGL(k_adopt, dim3(1), dim3(1), 0, c->stream, c->xyz, c->stride_f, d_g, pinned);
     }
@@ -390,7 +388,7 @@ static vgs_status voxelize_sorted_table(vgs_ctx* c) {
   const unsigned key_bits = (unsigned)(c->code_bits + 1);
   int idx_bits = 1;
   while (idx_bits < 32 && ((int64_t)1 << idx_bits) < N) ++idx_bits;
-  const int pack_shift = (sizeof(KeyT) == 8 && (int)key_bits + idx_bits <= 64 && !c->K.no_packed_sort) ? idx_bits : 0;
+  const int pack_shift = (sizeof(KeyT) == 8 && (int)key_bits + idx_bits <= 64) ? idx_bits : 0;
   hipLaunchKernelGGL((k_make_codes<KeyT>), dim3(nb), dim3(TB), 0, c->stream, c->xyz, c->stride_f, N, (const GrowState*)c->grow_state.p, c->box.res,
                      c->code_bits, code_a, c->perm_a.p, pack_shift);
 
