@@ -5,6 +5,7 @@
 #define VGS_EXAMPLE_DRIVERS_HPP_
 
 #include <cstdlib>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -12,14 +13,20 @@
 #include "vgs_debug_export.hpp"
 
 struct DriverSummary { long points = 0, voxels = 0, supervoxels = 0, clusters = 0, kept = 0, labelled = 0; };
+// what the drivers hand back of the cluster adjacency graph: getClusterGraph() and getClusterAdjacency() of the same run
+struct DriverGraph {
+  std::vector<pcl::ClusterEdge> edges;
+  std::multimap<uint32_t, uint32_t> adjacency;
+};
 
 // debug_prefix: when not empty, the reference's three voxel drawings (VS:510, 654, 1016) are written as
 // <prefix>_voxels.ply, <prefix>_clustered_voxels.ply, <prefix>_normals.ply
 // descriptors: when not null, receives getClusterDescriptors() (one per entry of clusters_points_idx, same order)
+// graph: when not null, receives getClusterGraph() and getClusterAdjacency() (cluster indices of clusters_points_idx)
 inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>& input_vector,
                            std::vector<std::vector<int>>& clusters_points_idx, DriverSummary* sum = nullptr,
                            const std::string& debug_prefix = std::string(), double ctor_resolution = 0.0,
-                           std::vector<pcl::ClusterDescriptor>* descriptors = nullptr) {
+                           std::vector<pcl::ClusterDescriptor>* descriptors = nullptr, DriverGraph* graph = nullptr) {
   float voxel_size = 0.15f, graph_size = 0.5f, sig_p = 0.2f, sig_n = 0.2f, sig_o = 0.2f, sig_e = 0.2f, sig_c = 0.2f, sig_w = 2.0f,
         cut_thred = 0.3f;
   int points_min = 10, adjacency_min = 3, voxels_min = 3;
@@ -53,6 +60,7 @@ inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>&
   voxel_structure.drawColorMapofPointsinClusters(clustered_cloud);
   clusters_points_idx = voxel_structure.getClusterIdx();
   if (descriptors) *descriptors = voxel_structure.getClusterDescriptors();
+  if (graph) { graph->edges = voxel_structure.getClusterGraph(); voxel_structure.getClusterAdjacency(graph->adjacency); }
   if (sum) {
     sum->points = (long)input_cloud->points.size(); sum->voxels = voxels; sum->clusters = voxel_structure.getClusterNum();
     sum->kept = (long)clusters_points_idx.size();
@@ -75,7 +83,7 @@ inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>&
 
 inline int segmentationSVGS(PCXYZPtr input_cloud, const std::vector<std::string>& input_vector,
                             std::vector<std::vector<int>>& clusters_points_idx, DriverSummary* sum = nullptr,
-                            std::vector<pcl::ClusterDescriptor>* descriptors = nullptr) {
+                            std::vector<pcl::ClusterDescriptor>* descriptors = nullptr, DriverGraph* graph = nullptr) {
   // Task_File_SVGS.txt values
   float voxel_size = 0.05f, seed_size = 0.25f, graph_size = 0.5f, sig_p = 0.2f, sig_n = 0.2f, sig_o = 0.2f, sig_e = 0.2f, sig_c = 0.2f,
         sig_w = 1.0f, sig_a = 0.0f, sig_b = 0.25f, cut_thred = 0.5f;
@@ -108,6 +116,7 @@ inline int segmentationSVGS(PCXYZPtr input_cloud, const std::vector<std::string>
   supervoxel_structure.drawColorMapofPointsinClusters(clustered_cloud);               // test:159-160
   clusters_points_idx = supervoxel_structure.getClusterIdx();
   if (descriptors) *descriptors = supervoxel_structure.getClusterDescriptors();
+  if (graph) { graph->edges = supervoxel_structure.getClusterGraph(); supervoxel_structure.getClusterAdjacency(graph->adjacency); }
   if (sum) {
     sum->points = (long)input_cloud->points.size(); sum->voxels = supervoxel_structure.getVoxelNum();
     sum->supervoxels = supervoxel_structure.getSuperVoxelNum(); sum->clusters = supervoxel_structure.getClusterNum();

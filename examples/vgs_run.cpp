@@ -3,13 +3,18 @@
 // the input PCD, segment, write the coloured clusters as PCD -- what `main` around the reference's `test` drivers does
 // with input_vector[12]/[15] (input path / name) and [18]/[21] (output path / name), minus the viewer.
 //   usage: vgs_run <task file> [--in <file.pcd|.ply>] [--out <file.pcd>] [--seed <n>] [--ascii] [--debug-meshes <prefix>]
-//                  [--segments <file.csv>]
+//                  [--segments <file.csv>] [--segment-graph <file.csv>] [--segment-adjacency <file.txt>]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
 // --segments writes one CSV row per kept cluster (getClusterDescriptors, row i = cluster i of the output): label, n_points, n_nodes,
 // bbox (6), centroid (3), eigenvalues (3, ascending), normal (3), major axis (3), the eight eigen features -- doubles as %.17g, floats as
 // %.9g, so every value reads back exactly.
+// --segment-graph writes one CSV row per edge of the cluster adjacency graph (getClusterGraph, ascending (a, b), cluster indices of the
+// output): a, b, n_pairs, n_finite, nodes_a, nodes_b, w_mean (w_sum / n_finite, NaN without a finite weight), w_min, w_max -- doubles as
+// %.17g, floats as %.9g.  --segment-adjacency writes getClusterAdjacency (PCL's getSupervoxelAdjacency idiom: both directions of every
+// edge), one "a,b" line per multimap entry in its iteration order.
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,13 +43,33 @@ static int writeSegmentsCsv(const std::string& path, const std::vector<pcl::Clus
   return std::fclose(f) == 0 ? 0 : -1;
 }
 
+static int writeGraphCsv(const std::string& path, const std::vector<pcl::ClusterEdge>& g) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "a,b,n_pairs,n_finite,nodes_a,nodes_b,w_mean,w_min,w_max\n");
+  for (const pcl::ClusterEdge& e : g) {
+    const double mean = e.n_finite > 0 ? e.w_sum / (double)e.n_finite : std::nan("");
+    std::fprintf(f, "%d,%d,%lld,%lld,%d,%d,%.17g,%.9g,%.9g\n", (int)e.a, (int)e.b, (long long)e.n_pairs, (long long)e.n_finite, (int)e.nodes_a,
+                 (int)e.nodes_b, mean, (double)e.w_min, (double)e.w_max);
+  }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
+static int writeAdjacency(const std::string& path, const std::multimap<uint32_t, uint32_t>& adj) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  for (const auto& kv : adj) std::fprintf(f, "%u,%u\n", kv.first, kv.second);
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: %s <task file> [--in file.pcd] [--out file.pcd] [--seed n] [--ascii] [--debug-meshes prefix] [--segments file.csv]\n",
+    std::fprintf(stderr, "usage: %s <task file> [--in file.pcd] [--out file.pcd] [--seed n] [--ascii] [--debug-meshes prefix] [--segments file.csv] "
+                 "[--segment-graph file.csv] [--segment-adjacency file.txt]\n",
                  argv[0]);
     return 2;
   }
-  std::string in_file, out_file, debug_prefix, segments_file;
+  std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file;
   uint64_t seed = 0;
   bool ascii = false;
   for (int a = 2; a < argc; ++a) {
@@ -54,6 +79,8 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--ascii")) ascii = true;
     else if (!std::strcmp(argv[a], "--debug-meshes") && a + 1 < argc) debug_prefix = argv[++a];
     else if (!std::strcmp(argv[a], "--segments") && a + 1 < argc) segments_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--segment-graph") && a + 1 < argc) graph_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--segment-adjacency") && a + 1 < argc) adjacency_file = argv[++a];
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
   const std::vector<std::string> task = inputTaskTxtFile(argv[1]);
@@ -74,11 +101,13 @@ int main(int argc, char** argv) {
   DriverSummary sum;
   std::vector<pcl::ClusterDescriptor> desc;
   std::vector<pcl::ClusterDescriptor>* want = segments_file.empty() ? nullptr : &desc;
+  DriverGraph graph;
+  DriverGraph* want_graph = (graph_file.empty() && adjacency_file.empty()) ? nullptr : &graph;
   try {
     if (method == 2) {
-      if (segmentationVGS(cloud, task, clusters, &sum, debug_prefix, 0.0, want) != 0) { std::fprintf(stderr, "cannot write the debug meshes\n"); return 1; }
+      if (segmentationVGS(cloud, task, clusters, &sum, debug_prefix, 0.0, want, want_graph) != 0) { std::fprintf(stderr, "cannot write the debug meshes\n"); return 1; }
     } else {
-      segmentationSVGS(cloud, task, clusters, &sum, want);
+      segmentationSVGS(cloud, task, clusters, &sum, want, want_graph);
     }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "error: %s\n", e.what());
@@ -86,6 +115,11 @@ int main(int argc, char** argv) {
   }
   if (saveColoredClusters(out_file, cloud, clusters, seed, !ascii) != 0) return 1;
   if (want && writeSegmentsCsv(segments_file, desc) != 0) { std::fprintf(stderr, "cannot write %s\n", segments_file.c_str()); return 1; }
+  if (!graph_file.empty() && writeGraphCsv(graph_file, graph.edges) != 0) { std::fprintf(stderr, "cannot write %s\n", graph_file.c_str()); return 1; }
+  if (!adjacency_file.empty() && writeAdjacency(adjacency_file, graph.adjacency) != 0) {
+    std::fprintf(stderr, "cannot write %s\n", adjacency_file.c_str());
+    return 1;
+  }
   std::printf("%d %ld %ld %ld %ld %ld %ld\n", method, sum.points, sum.voxels, sum.supervoxels, sum.clusters, sum.kept, sum.labelled);
   return 0;
 }

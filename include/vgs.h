@@ -224,6 +224,28 @@ vgs_status vgs_get_segment_descriptors(vgs_ctx* ctx, int64_t* n_points, int32_t*
 vgs_status vgs_get_segment_descriptors_device(vgs_ctx* ctx, const int64_t** n_points, const int32_t** n_nodes, const float** bbox6,
                                               const double** centroid3, const double** cov6, const double** evals3, const double** evecs9,
                                               const float** eigen8);
+/* Segment adjacency graph (no reference counterpart: which kept segments touch, and how strongly the local cut's weight links them).
+ *   A node is a voxel (VGS) or a supervoxel (SVGS).  Only used nodes with a kept label >= 0 take part; unused voxels and the nodes of
+ *   clusters dropped by the size filter are ignored.
+ *   An edge is an unordered pair of kept labels a < b with at least one node pair {u, v} such that u has label a, v has label b, and v is
+ *   in u's stored adjacency row (the adjacency stage's own predicate: float d2 < graph_size^2 between centres or centroids).
+ *   Edges are listed in ascending (a, b) order; E = their number.  Per edge (every array E rows, any pointer may be NULL):
+ *     seg_ab    int32 x2  a, b
+ *     n_pairs   int64     node pairs {u, v} as above, each counted once
+ *     n_finite  int64     those pairs whose weight is not NaN
+ *     nodes_ab  int32 x2  the nodes of a with at least one such neighbour in b, and the nodes of b with one in a
+ *     w_sum     double    sum of the non-NaN weights w(u, v) = vm_pair_weight(node[min(u, v)], node[max(u, v)], W) -- the lower node id first,
+ *                         exactly the entry vgs_get_local_weights reports for that ordered pair -- summed in fp64 in a fixed order
+ *     w_min     float     min of the non-NaN weights (NaN when n_finite == 0)
+ *     w_max     float     max of the non-NaN weights (NaN when n_finite == 0)
+ * n_edges is required and always written; a call with every array NULL is the size query.  Computed on the device on the first request
+ * after a run (no atomics, fixed summation shapes: bit-identical from call to call and engine to engine) and cached until the next run.
+ * VGS_E_STATE before the context is segmented and for a tile context; K <= 1 kept segments gives E = 0. */
+vgs_status vgs_get_segment_graph(vgs_ctx* ctx, int64_t* n_edges, int32_t* seg_ab, int64_t* n_pairs, int64_t* n_finite, int32_t* nodes_ab,
+                                 double* w_sum, float* w_min, float* w_max);
+/* the same table left in HBM: device pointers (any may be NULL), valid until the next run of the stages */
+vgs_status vgs_get_segment_graph_device(vgs_ctx* ctx, int64_t* n_edges, const int32_t** seg_ab, const int64_t** n_pairs, const int64_t** n_finite,
+                                        const int32_t** nodes_ab, const double** w_sum, const float** w_min, const float** w_max);
 
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.

@@ -16,6 +16,7 @@
 #define VGS_SEGMENTATION_HPP_
 
 #include <cstdint>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -125,6 +126,47 @@ inline std::vector<ClusterDescriptor> cluster_descriptors(vgs_ctx* c, int64_t k)
     for (int a = 0; a < 8; ++a) d.eigen8[a] = e8[8 * i + a];
   }
   return out;
+}
+}  // namespace vgs_detail
+
+// Extension (no VS / SS line): one edge of the adjacency graph of the kept clusters, as vgs_get_segment_graph (include/vgs.h) defines it
+struct ClusterEdge {
+  int32_t a = 0, b = 0;        // cluster indices (getClusterIdx order), a < b
+  int64_t n_pairs = 0;         // node pairs {u, v} of a and b inside graph_size of each other
+  int64_t n_finite = 0;        // ... whose weight is not NaN
+  int32_t nodes_a = 0, nodes_b = 0;   // nodes of a with a neighbour in b, nodes of b with a neighbour in a
+  double w_sum = 0;            // sum of the finite local-cut weights of those pairs
+  float w_min = 0, w_max = 0;  // their min and max (NaN when n_finite == 0)
+};
+
+namespace vgs_detail {
+// every edge once, in ascending (a, b) order
+inline std::vector<ClusterEdge> cluster_graph(vgs_ctx* c) {
+  int64_t E = 0;
+  check(c, vgs_get_segment_graph(c, &E, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "vgs_get_segment_graph");
+  std::vector<ClusterEdge> out((size_t)E);
+  if (E == 0) return out;
+  std::vector<int32_t> ab((size_t)E * 2), nd((size_t)E * 2);
+  std::vector<int64_t> np((size_t)E), nf((size_t)E);
+  std::vector<double> ws((size_t)E);
+  std::vector<float> mn((size_t)E), mx((size_t)E);
+  check(c, vgs_get_segment_graph(c, &E, ab.data(), np.data(), nf.data(), nd.data(), ws.data(), mn.data(), mx.data()), "vgs_get_segment_graph");
+  for (size_t i = 0; i < out.size(); ++i) {
+    ClusterEdge& e = out[i];
+    e.a = ab[2 * i]; e.b = ab[2 * i + 1];
+    e.n_pairs = np[i]; e.n_finite = nf[i];
+    e.nodes_a = nd[2 * i]; e.nodes_b = nd[2 * i + 1];
+    e.w_sum = ws[i]; e.w_min = mn[i]; e.w_max = mx[i];
+  }
+  return out;
+}
+// PCL's getSupervoxelAdjacency idiom: both directions of every edge, keyed by cluster index
+inline void cluster_adjacency(const std::vector<ClusterEdge>& g, std::multimap<uint32_t, uint32_t>& adjacency) {
+  adjacency.clear();
+  for (const ClusterEdge& e : g) {
+    adjacency.insert(std::make_pair((uint32_t)e.a, (uint32_t)e.b));
+    adjacency.insert(std::make_pair((uint32_t)e.b, (uint32_t)e.a));
+  }
 }
 }  // namespace vgs_detail
 
@@ -242,6 +284,13 @@ class VoxelBasedSegmentation {
     if (!drawn_) return {};
     return vgs_detail::cluster_descriptors(ctx(), count(VGS_N_KEPT));
   }
+  // Extension (no VS line): the adjacency graph of the kept clusters, indices as getClusterIdx; empty before drawColorMapofPointsinClusters
+  std::vector<ClusterEdge> getClusterGraph() {
+    if (!drawn_) return {};
+    return vgs_detail::cluster_graph(ctx());
+  }
+  // Extension (no VS line): PCL's getSupervoxelAdjacency idiom over getClusterGraph -- both directions of every edge
+  void getClusterAdjacency(std::multimap<uint32_t, uint32_t>& adjacency) { vgs_detail::cluster_adjacency(getClusterGraph(), adjacency); }
 
   vgs_ctx* ctx() { return ctx_.get(); }
 
@@ -334,6 +383,10 @@ class SuperVoxelBasedSegmentation {
   }
   // Extension (no SS line): descriptor i describes getClusterIdx()[i]
   std::vector<ClusterDescriptor> getClusterDescriptors() { return vgs_detail::cluster_descriptors(ctx(), count(VGS_N_KEPT)); }
+  // Extension (no SS line): the adjacency graph of the kept clusters, indices as getClusterIdx
+  std::vector<ClusterEdge> getClusterGraph() { return vgs_detail::cluster_graph(ctx()); }
+  // Extension (no SS line): PCL's getSupervoxelAdjacency idiom over getClusterGraph -- both directions of every edge
+  void getClusterAdjacency(std::multimap<uint32_t, uint32_t>& adjacency) { vgs_detail::cluster_adjacency(getClusterGraph(), adjacency); }
   vgs_ctx* ctx() { return ctx_.get(); }
 
  private:

@@ -96,6 +96,8 @@ SYMBOLS = [
     ("vgs_get_clusters_device", C.c_int, [_P, _P, _P]),
     ("vgs_get_segment_descriptors", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_segment_descriptors_device", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_get_segment_graph", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_get_segment_graph_device", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_grid_state_init", C.c_int, [C.POINTER(VgsGridState)]),
     ("vgs_grid_advance", C.c_int, [_P, C.POINTER(VgsGridState)]),
     ("vgs_points_bbox", C.c_int, [_P, _P, C.POINTER(C.c_int64)]),

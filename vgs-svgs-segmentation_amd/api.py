@@ -278,6 +278,28 @@ class Engine:
         self._ck(self._L.vgs_get_segment_descriptors_device(self._h, *(C.byref(p) for p in ps)))
         return {name: p.value for (name, _, _), p in zip(self.DESCRIPTOR_FIELDS, ps)}
 
+    # per edge: (field, dtype, values per edge) of vgs_get_segment_graph, in its argument order
+    GRAPH_FIELDS = (("seg_ab", np.int32, 2), ("n_pairs", np.int64, 1), ("n_finite", np.int64, 1), ("nodes_ab", np.int32, 2),
+                    ("w_sum", np.float64, 1), ("w_min", np.float32, 1), ("w_max", np.float32, 1))
+
+    def segment_graph(self):
+        """Adjacency graph of the kept segments (include/vgs.h, vgs_get_segment_graph): a dict of numpy arrays seg_ab (E, 2: a < b),
+        n_pairs (E,), n_finite (E,), nodes_ab (E, 2), w_sum (E,), w_min (E,), w_max (E,), edges in ascending (a, b) order.  The labels
+        are those of point_labels / getClusterIdx.  Computed on the device, cached until the next run."""
+        E = C.c_int64(0)
+        self._ck(self._L.vgs_get_segment_graph(self._h, C.byref(E), *([None] * len(self.GRAPH_FIELDS))))
+        out = {name: np.zeros((E.value, w) if w > 1 else E.value, dtype=dt) for name, dt, w in self.GRAPH_FIELDS}
+        if E.value:
+            self._ck(self._L.vgs_get_segment_graph(self._h, C.byref(E), *(_ptr(out[name]) for name, _, _ in self.GRAPH_FIELDS)))
+        return out
+
+    def segment_graph_device(self):
+        """The same table left in HBM: (E, {field: device pointer}), valid until the next run."""
+        E = C.c_int64(0)
+        ps = [C.c_void_p() for _ in self.GRAPH_FIELDS]
+        self._ck(self._L.vgs_get_segment_graph_device(self._h, C.byref(E), *(C.byref(p) for p in ps)))
+        return E.value, {name: p.value for (name, _, _), p in zip(self.GRAPH_FIELDS, ps)}
+
     # ---- a sequence of clouds: uploads of the next cloud and downloads of the last labels overlap the stages
     def stage_points(self, xyz):
         """Start the copy of the NEXT cloud (ideally a pinned array, see pinned_empty) and return at once."""
@@ -393,6 +415,12 @@ class VoxelBasedSegmentation:
             return {name: np.zeros((0, w) if w > 1 else 0, dtype=dt) for name, dt, w in Engine.DESCRIPTOR_FIELDS}
         return self._eng.segment_descriptors()
 
+    def getClusterGraph(self):
+        """Extension (no VS line): the adjacency graph of the kept clusters, labels = getClusterIdx() indices (Engine.segment_graph)."""
+        if not self._drawn:
+            return {name: np.zeros((0, w) if w > 1 else 0, dtype=dt) for name, dt, w in Engine.GRAPH_FIELDS}
+        return self._eng.segment_graph()
+
     @property
     def engine(self):
         return self._eng
@@ -468,6 +496,10 @@ class SuperVoxelBasedSegmentation:
     def getClusterDescriptors(self):
         """Extension (no SS line): descriptor i describes getClusterIdx()[i] -- both are in label order (Engine.segment_descriptors)."""
         return self._eng.segment_descriptors()
+
+    def getClusterGraph(self):
+        """Extension (no SS line): the adjacency graph of the kept clusters, labels = getClusterIdx() indices (Engine.segment_graph)."""
+        return self._eng.segment_graph()
 
     @property
     def engine(self):

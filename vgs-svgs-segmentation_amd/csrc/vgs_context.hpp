@@ -71,6 +71,21 @@ struct Epoch {  // keys of points with index >= first use this box
 
 #define VGS_MAX_EPOCHS 96
 
+// segment graph (seggraph.hip): one record per (used node u, neighbour label B != u's label A) -- over u's neighbours v > u of label B --
+// and one partial per chunk of an edge's sorted records
+struct SgRec {
+  double w_sum;
+  uint32_t cnt_lt, n_finite;
+  int32_t a, b;   // A, B
+  float w_min, w_max;
+};
+struct SgPart {
+  double w_sum;
+  int64_t n_pairs, n_finite;
+  int32_t nodes_a, nodes_b;
+  float w_min, w_max;
+};
+
 enum Stage { ST_NONE = 0, ST_POINTS = 1, ST_VOXELS = 2, ST_FEATURES = 3, ST_ADJACENCY = 4, ST_SEGMENTED = 5 };
 
 // Diagnostics / schedule-tuning knobs (none changes a result).  Read from the environment ONCE, when the context is created
@@ -249,6 +264,20 @@ struct vgs_ctx {
   DevBuf<float> sd_bbox, sd_eig8;
   DevBuf<double> sd_cen, sd_cov, sd_eval, sd_evec;
   bool sd_valid = false;
+  // segment adjacency graph (seggraph.hip): the edge table of the kept segments, computed on request, valid until the next run (sg_valid);
+  // its effective labels, per-row records, sort, scans and partials use their own scratch (no getter reads it)
+  DevBuf<int32_t> sg_lab;
+  DevBuf<uint32_t> sg_nrec, sg_ridx, sg_ework, sg_meta;
+  DevBuf<uint64_t> sg_roff, sg_rkey;
+  DevBuf<SgRec> sg_rec;
+  DevBuf<SgPart> sg_part;
+  DevBuf<uint8_t> sg_tmp;
+  DevBuf<int32_t> sg_ab, sg_nodes;
+  DevBuf<int64_t> sg_npairs, sg_nfin;
+  DevBuf<double> sg_wsum;
+  DevBuf<float> sg_wmin, sg_wmax;
+  int64_t sg_E = 0;
+  bool sg_valid = false;
   DevBuf<uint64_t> counters;   // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 
@@ -375,6 +404,7 @@ vgs_status vgs_localcut_finish(vgs_ctx* c, unsigned int* n_deferred);  // waits 
 vgs_status vgs_stage_merge(vgs_ctx* c);
 vgs_status vgs_clusters_on_device(vgs_ctx* c);   // clusters.hip
 vgs_status vgs_segdesc_on_device(vgs_ctx* c);    // segdesc.hip
+vgs_status vgs_seggraph_on_device(vgs_ctx* c);   // seggraph.hip
 vgs_status vgs_stage_vccs(vgs_ctx* c);
 vgs_status vgs_stage_svgs_group(vgs_ctx* c);
 vgs_status vgs_stage_svgs_neighbours(vgs_ctx* c);
