@@ -1,0 +1,32 @@
+// examples/segments_csv.hpp -- the --segments CSV of the front ends (vgs_run, vgs_tiles_run): one row per kept cluster, row i = cluster
+// i (label i): label, n_points, n_nodes, bbox (6), centroid (3), eigenvalues (3, ascending), normal (3), major axis (3), the eight eigen
+// features -- doubles as %.17g, floats as %.9g, so every value reads back exactly.  One writer, so the two front ends cannot drift apart.
+#ifndef VGS_EXAMPLES_SEGMENTS_CSV_HPP_
+#define VGS_EXAMPLES_SEGMENTS_CSV_HPP_
+
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "vgs_segmentation.hpp"
+
+inline int writeSegmentsCsv(const std::string& path, const std::vector<pcl::ClusterDescriptor>& desc) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "label,n_points,n_nodes,min_x,min_y,min_z,max_x,max_y,max_z,cx,cy,cz,l0,l1,l2,nx,ny,nz,ax,ay,az,"
+                  "f0,f1,f2,f3,f4,f5,f6,f7\n");
+  for (size_t i = 0; i < desc.size(); ++i) {
+    const pcl::ClusterDescriptor& d = desc[i];
+    std::fprintf(f, "%zu,%lld,%d", i, (long long)d.n_points, (int)d.n_nodes);
+    for (int a = 0; a < 6; ++a) std::fprintf(f, ",%.9g", (double)d.bbox[a]);
+    for (int a = 0; a < 3; ++a) std::fprintf(f, ",%.17g", d.centroid[a]);
+    for (int a = 0; a < 3; ++a) std::fprintf(f, ",%.17g", d.evals[a]);
+    for (int r = 0; r < 3; ++r) std::fprintf(f, ",%.17g", d.evecs[3 * r + 0]);   // normal: eigenvector of the smallest eigenvalue
+    for (int r = 0; r < 3; ++r) std::fprintf(f, ",%.17g", d.evecs[3 * r + 2]);   // major axis: eigenvector of the largest
+    for (int a = 0; a < 8; ++a) std::fprintf(f, ",%.9g", (double)d.eigen8[a]);
+    std::fprintf(f, "\n");
+  }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
+#endif  // VGS_EXAMPLES_SEGMENTS_CSV_HPP_

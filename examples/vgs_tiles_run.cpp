@@ -8,6 +8,8 @@
 //       vgs_tiles_run --emulate 2x2 --pitch 6.1 --voxel 0.1 <prefix>
 //   Rank r reads its points from <prefix>.<r>.f32 (packed float32 xyz) and writes one int32 label per point to
 //   <prefix>.<r>.labels.i32.  Prints "<world> <kept segments> <points of rank 0> <boundary records of rank 0>".
+//   --segments <file.csv>: every rank takes part in vgs_tiles_get_segment_descriptors (a collective) and rank 0 writes the table of the
+//   global segments in the CSV format of vgs_run --segments (examples/segments_csv.hpp).
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <sys/socket.h>
@@ -23,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "segments_csv.hpp"
 #include "vgs_tiles.h"
 
 static bool read_f32(const std::string& path, std::vector<float>& out) {
@@ -45,7 +48,7 @@ static bool write_i32(const std::string& path, const std::vector<int32_t>& v) {
   return put == v.size();
 }
 
-struct Job { vgs_params p; int tx, ty; double pitch; std::string prefix; };
+struct Job { vgs_params p; int tx, ty; double pitch; std::string prefix, segments; };
 
 // one rank: load, run, save; returns 0 on success
 static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world, int64_t* kept, int64_t* n_pts, int64_t* n_rec, std::string* err) {
@@ -61,6 +64,30 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
       (s = vgs_tiles_get_point_labels(t, labels.data(), kept)) != VGS_OK) {
     *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
     rc = 1;
+  }
+  if (rc == 0 && !J.segments.empty()) {
+    // the descriptors of the global segments: a collective of every rank, the same table on each; rank 0 writes it
+    const size_t k = (size_t)*kept;
+    std::vector<int64_t> np(k + 1);
+    std::vector<int32_t> nn(k + 1);
+    std::vector<float> bb(6 * k + 1), e8(8 * k + 1);
+    std::vector<double> ce(3 * k + 1), cv(6 * k + 1), ev(3 * k + 1), vv(9 * k + 1);
+    int64_t K = 0;
+    if (vgs_tiles_get_segment_descriptors(t, &K, np.data(), nn.data(), bb.data(), ce.data(), cv.data(), ev.data(), vv.data(), e8.data()) != VGS_OK) {
+      *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+      rc = 1;
+    } else if (rank == 0) {
+      std::vector<pcl::ClusterDescriptor> desc(k);
+      for (size_t i = 0; i < k; ++i) {
+        pcl::ClusterDescriptor& d = desc[i];
+        d.n_points = np[i]; d.n_nodes = nn[i];
+        for (int a = 0; a < 6; ++a) { d.bbox[a] = bb[6 * i + a]; d.cov[a] = cv[6 * i + a]; }
+        for (int a = 0; a < 3; ++a) { d.centroid[a] = ce[3 * i + a]; d.evals[a] = ev[3 * i + a]; }
+        for (int a = 0; a < 9; ++a) d.evecs[a] = vv[9 * i + a];
+        for (int a = 0; a < 8; ++a) d.eigen8[a] = e8[8 * i + a];
+      }
+      if (writeSegmentsCsv(J.segments, desc) != 0) { *err = "cannot write " + J.segments; rc = 1; }
+    }
   }
   if (rc == 0) {
     labels.resize((size_t)n);
@@ -122,10 +149,11 @@ int main(int argc, char** argv) {
     } else if (!std::strcmp(argv[a], "--pitch") && a + 1 < argc) J.pitch = std::atof(argv[++a]);
     else if (!std::strcmp(argv[a], "--voxel") && a + 1 < argc) J.p.voxel_size = (float)std::atof(argv[++a]);
     else if (!std::strcmp(argv[a], "--graph") && a + 1 < argc) J.p.graph_size = (float)std::atof(argv[++a]);
+    else if (!std::strcmp(argv[a], "--segments") && a + 1 < argc) J.segments = argv[++a];
     else if (argv[a][0] != '-') J.prefix = argv[a];
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
-  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] <prefix>\n", argv[0]); return 2; }
+  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] <prefix>\n", argv[0]); return 2; }
   const int world = J.tx * J.ty;
   int64_t kept = 0, n_pts = 0, n_rec = 0;
   if (mode == 1) {

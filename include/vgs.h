@@ -224,6 +224,28 @@ vgs_status vgs_get_segment_descriptors(vgs_ctx* ctx, int64_t* n_points, int32_t*
 vgs_status vgs_get_segment_descriptors_device(vgs_ctx* ctx, const int64_t** n_points, const int32_t** n_nodes, const float** bbox6,
                                               const double** centroid3, const double** cov6, const double** evals3, const double** evecs9,
                                               const float** eigen8);
+/* Per-segment moments of a tile context (the tiled driver, include/vgs_tiles.h: vgs_tiles_get_segment_descriptors builds the global table
+ * from them).  After vgs_apply_tile_labels, vox_label holds GLOBAL labels 0 .. K-1 (K = kept_global).  One record per label k for which
+ * this context has an own labelled point (input index in the vgs_set_own_point_range range) or an owned voxel (vgs_set_owned_region),
+ * in ascending label order; every array holds up to K records and any may be NULL; *n_records is written:
+ *   label      int32   k
+ *   n_points   int64   own points with label k
+ *   n_nodes    int32   owned voxels with label k
+ *   bbox6      float   min x, y, z, max x, y, z of those own points (+inf / -inf without one)
+ *   anchor3    float   the first own point of k in the order of the descriptor chunks (sorted nodes, each node's points in order); 0 without one
+ *   s9         double  sum d (x, y, z) and sum d d^T (xx, xy, xz, yy, yz, zz) over the own points, d = p - anchor in fp64
+ * Computed on the device every call (no cache: the driver keeps the table).  VGS_E_STATE before the context is segmented and for a
+ * context that is not a tile context. */
+vgs_status vgs_get_own_segment_moments(vgs_ctx* ctx, int64_t K, int64_t* n_records, int32_t* label, int64_t* n_points, int32_t* n_nodes,
+                                       float* bbox6, float* anchor3, double* s9);
+/* The descriptor table from moments already folded per label (K rows, the layout of vgs_get_own_segment_moments without `label`; the
+ * anchor a point of the segment, s9 about it): the per-segment algebra of vgs_get_segment_descriptors -- centroid, covariance, Jacobi,
+ * sign rule, features, the same device code -- on this context's GPU.  Writes the eight arrays of vgs_get_segment_descriptors (any may be
+ * NULL; n_points / n_nodes / bbox6 pass through).  Uses the context's descriptor buffers: a cached table of the context itself is
+ * dropped. */
+vgs_status vgs_segment_descriptors_from_moments(vgs_ctx* ctx, int64_t K, const int64_t* n_points, const int32_t* n_nodes, const float* bbox6,
+                                                const float* anchor3, const double* s9, int64_t* n_points_out, int32_t* n_nodes_out,
+                                                float* bbox6_out, double* centroid3, double* cov6, double* evals3, double* evecs9, float* eigen8);
 /* Segment adjacency graph (no reference counterpart: which kept segments touch, and how strongly the local cut's weight links them).
  *   A node is a voxel (VGS) or a supervoxel (SVGS).  Only used nodes with a kept label >= 0 take part; unused voxels and the nodes of
  *   clusters dropped by the size filter are ignored.

@@ -10,7 +10,8 @@
  * Protocol per run (csrc/tiles.cpp): shared octree grid (all-gather of the tiles' bounding boxes, the growth replayed on the
  * host, a GPU scan + broadcast only where a box leaves the step open) -> the four stages on tile + halo -> unique boundary
  * voxels (code, local root, owned voxels of that root) and the number of purely local segments leave the GPU -> ncclAllGather
- * -> the same union-find over (rank, root) on every rank, size filter on global sizes -> labels applied on the GPU.
+ * -> the same union-find over (rank, root) on every rank, size filter on global sizes -> labels applied on the GPU.  Per-segment
+ * descriptors on request afterwards: a second collective of their own (vgs_tiles_get_segment_descriptors).
  */
 #ifndef VGS_TILES_H_
 #define VGS_TILES_H_
@@ -88,6 +89,34 @@ vgs_status vgs_tiles_get_exchange(vgs_tiles* t, int64_t* bytes_sent, int64_t* by
 vgs_status vgs_tiles_merge_boundary(int world, const int64_t* rec_off, const uint64_t* code, const int32_t* root, const int32_t* cnt,
                                     const int64_t* kept_local, int voxels_min, int64_t* base, int64_t* uoff, int32_t* uroot, int32_t* ulabel,
                                     int64_t* kept_total);
+/* Per-segment descriptors over all ranks: the fields, layout and conventions of vgs_get_segment_descriptors (include/vgs.h), K =
+ * kept_global rows (vgs_tiles_get_point_labels); row k describes exactly the points, over all ranks, that vgs_tiles_get_point_labels
+ * labels k.  n_points, bbox6, centroid3 and cov6 are those points' count, exact float box, fp64 mean and population covariance; n_nodes
+ * counts the voxels of the shared grid that hold label k, each once, by the rank that owns it (the voxel sizes the boundary merge's
+ * `> voxels_min` filter sums).
+ * A call with every array pointer NULL only writes *K (no collective).  Otherwise the call is COLLECTIVE: after one vgs_tiles_run every
+ * rank makes it, and every rank receives the same bytes, bit-identical from call to call and from run to run on the same input and
+ * layout.  Protocol (csrc/tiles.cpp): each rank's moments of its own points and owned voxels (vgs_get_own_segment_moments, one small
+ * pipeline on its GPU) -> ONE all_gather_varlen of those records with a status word -> the same host fold on every rank
+ * (vgs_tiles_fold_moments) -> the per-segment algebra on the rank's GPU (vgs_segment_descriptors_from_moments).  The table is cached:
+ * a second call makes no collective; the next vgs_tiles_run or vgs_tiles_set_points drops it.  Failures as in vgs_tiles_run: a rank
+ * whose local step fails still joins the exchange with its status word, returns its own error, and every other rank returns VGS_E_PEER
+ * naming it (tests inject one with VGS_TILES_FAIL_AT=descriptors).  VGS_E_STATE (no collective) before a run.  vgs_tiles_run itself
+ * gains no launch and no collective. */
+vgs_status vgs_tiles_get_segment_descriptors(vgs_tiles* t, int64_t* K, int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3,
+                                             double* cov6, double* evals3, double* evecs9, float* eigen8);
+/* host wall time of the last descriptor collective on this rank, milliseconds: own moments on the GPU (with their download), the
+ * exchange, the fold, the algebra on the GPU (with upload and download), total */
+enum { VGS_TILES_D_MOMENTS = 0, VGS_TILES_D_EXCHANGE = 1, VGS_TILES_D_FOLD = 2, VGS_TILES_D_ALGEBRA = 3, VGS_TILES_D_TOTAL = 4, VGS_TILES_D_COUNT = 5 };
+vgs_status vgs_tiles_get_descriptor_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_D_COUNT */);
+/* The descriptor fold on its own (host arithmetic, no context, no GPU; for tests): rank r's records are entries rec_off[r] .. rec_off[r+1]
+ * of label / n_points / n_nodes / bbox6 / anchor3 / s9 (vgs_get_own_segment_moments).  Outputs: K rows of folded moments, every pointer
+ * required.  Per label, ranks in ascending order: the anchor a is the anchor of the lowest rank with n_points > 0; with delta = a_r - a in
+ * fp64, S1 += S1_r + n_r delta and S2 += S2_r + S1_r delta^T + delta S1_r^T + n_r delta delta^T; n_points and n_nodes add, boxes take min
+ * and max.  A row no record reaches: zero counts, sums and anchor, box +inf / -inf.  VGS_E_ARG for a label outside 0 .. K-1. */
+vgs_status vgs_tiles_fold_moments(int world, const int64_t* rec_off, const int32_t* label, const int64_t* n_points, const int32_t* n_nodes,
+                                  const float* bbox6, const float* anchor3, const double* s9, int64_t K, int64_t* n_points_out,
+                                  int32_t* n_nodes_out, float* bbox6_out, float* anchor3_out, double* s9_out);
 /* the rank's engine context (read-only use: counts, stage times) */
 vgs_ctx* vgs_tiles_context(vgs_tiles* t);
 

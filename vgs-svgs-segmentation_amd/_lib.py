@@ -96,6 +96,8 @@ SYMBOLS = [
     ("vgs_get_clusters_device", C.c_int, [_P, _P, _P]),
     ("vgs_get_segment_descriptors", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_segment_descriptors_device", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_get_own_segment_moments", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_segment_descriptors_from_moments", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_segment_graph", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_segment_graph_device", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_grid_state_init", C.c_int, [C.POINTER(VgsGridState)]),

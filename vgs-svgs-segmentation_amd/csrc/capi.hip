@@ -228,6 +228,7 @@ void vgs_destroy(vgs_ctx* c) {
   c->nl_cnt.release(); c->nl_tot.release(); c->nl_ent.release(); c->lc_ctab.release(); c->pl_state.release(); c->pl_ent.release(); c->pl_work.release();
   c->sd_key.release(); c->sd_ids.release(); c->sd_vp.release(); c->sd_seg.release(); c->sd_tmp.release(); c->sd_part.release();
   c->sd_npts.release(); c->sd_nnodes.release(); c->sd_bbox.release(); c->sd_eig8.release(); c->sd_cen.release(); c->sd_cov.release(); c->sd_eval.release(); c->sd_evec.release();
+  c->sd_apos.release(); c->sd_mom.release();
   c->sg_lab.release(); c->sg_nrec.release(); c->sg_ridx.release(); c->sg_ework.release(); c->sg_meta.release(); c->sg_roff.release(); c->sg_rkey.release(); c->sg_rec.release(); c->sg_part.release(); c->sg_tmp.release();
   c->sg_ab.release(); c->sg_nodes.release(); c->sg_npairs.release(); c->sg_nfin.release(); c->sg_wsum.release(); c->sg_wmin.release(); c->sg_wmax.release();
   c->cl_off.release(); c->cl_idx.release(); c->conn.release(); c->evals.release(); c->lc_pending.release(); c->lc_defer.release(); c->lc_defer_flag.release(); c->csize.release(); c->attach.release(); c->cc_flags.release(); c->parent.release(); c->csz.release();

@@ -16,8 +16,12 @@
 // butterfly, the waves in index order, the partials of a segment by lane stride then butterfly.  No atomics.  Balance: a segment of
 // millions of points is spread over its chunks like any other; a segment of a few hundred points costs one workgroup.
 // Scratch: own buffers only (sd_*), nothing another getter reads.  Computed on request and cached until the next run (sd_valid).
+// Tile contexts (the tiled driver, include/vgs_tiles.h): the same steps over global labels with own points only (k_sd_own_anchor,
+// k_sd_chunks_own, k_sd_own_records) give this rank's moment records; the driver folds all ranks' records on the host and
+// k_sd_algebra turns them into the table with the per-segment algebra k_sd_final runs (sd_segment_algebra, one copy).
 #include <cstring>
 #include <string.h>
+#include <vector>
 
 #include <rocprim/rocprim.hpp>
 
@@ -28,12 +32,12 @@
 #define SD_CHUNK (SD_TB * SD_PPT)   // virtual points per chunk
 #define SD_REC 16                   // doubles per partial record: sum d[3], sum dd^T[6] (xx xy xz yy yz zz), min[3], max[3], (pad)
 
-// key of node v: its kept label, K for the nodes of dropped clusters (they sort behind every kept segment)
+// key of node v: its kept label, K for the nodes of dropped clusters (they sort behind every kept segment; so would a label >= K)
 __global__ void k_sd_keys(const int32_t* __restrict__ vox_label, int64_t V, uint32_t K, uint32_t* __restrict__ key, uint32_t* __restrict__ ids) {
   const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= V) return;
   const int32_t l = vox_label[v];
-  key[v] = l < 0 ? K : (uint32_t)l;
+  key[v] = (l < 0 || (uint32_t)l >= K) ? K : (uint32_t)l;
   ids[v] = (uint32_t)v;
 }
 
@@ -83,12 +87,25 @@ __device__ __forceinline__ float sd_wave_max(float x) {
   return x;
 }
 
+// Empty partial record: zero sums and count, +inf min, -inf max
+__device__ __forceinline__ void sd_empty_record(double* __restrict__ rec) {
+  if (threadIdx.x < SD_REC) {
+    const int f = threadIdx.x;
+    rec[f] = f < 9 ? 0.0 : (f < 12 ? __builtin_huge_val() : (f < 15 ? -__builtin_huge_val() : 0.0));
+  }
+}
+
 // One workgroup per chunk of SD_CHUNK virtual points of one segment.  Grid: an upper bound of the number of chunks (floor(Nf / SD_CHUNK) +
-// K + 1); workgroups past the real number leave at once.
-__global__ __launch_bounds__(SD_TB) void k_sd_chunks(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
-                                                     const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
-                                                     const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
-                                                     const uint32_t* __restrict__ seg_chunk, uint32_t K, double* __restrict__ part) {
+// K + 1); workgroups past the real number leave at once.  OWN (tile contexts, k_sd_chunks_own): only the points whose input index
+// perm[pos] lies in [own_first, own_end) count -- in the sums, the min / max and the point count (field 15) -- and the anchor is the
+// segment's first own point (anchor_pos[k], from k_sd_own_anchor); a segment without own points writes an empty record.
+template <bool OWN>
+__device__ __forceinline__ void sd_chunk_body(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                              const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                              const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                              const uint32_t* __restrict__ seg_chunk, uint32_t K, double* __restrict__ part,
+                                              const uint32_t* __restrict__ perm, int64_t own_first, int64_t own_end,
+                                              const uint32_t* __restrict__ anchor_pos) {
   __shared__ uint32_t s_vp[SD_CHUNK];    // virtual start of the chunk's nodes
   __shared__ uint32_t s_dl[SD_CHUNK];    // sorted position - virtual position of the same (mod 2^32)
   __shared__ double s_red[SD_TB / 64][SD_REC];
@@ -102,10 +119,13 @@ __global__ __launch_bounds__(SD_TB) void k_sd_chunks(const float* __restrict__ x
   const uint32_t a = vp[n0] + (c - seg_chunk[k]) * SD_CHUNK;
   const uint32_t b = min(a + SD_CHUNK, vp[n1]);
   if (n1 <= n0 || a >= b) {   // (cannot happen for a kept segment; an empty record keeps the fold well defined)
-    if (threadIdx.x < SD_REC) {
-      const int f = threadIdx.x;
-      part[(size_t)c * SD_REC + f] = f < 9 ? 0.0 : (f < 12 ? __builtin_huge_val() : (f < 15 ? -__builtin_huge_val() : 0.0));
-    }
+    sd_empty_record(part + (size_t)c * SD_REC);
+    return;
+  }
+  // the anchor: the segment's first point (OWN: its first own point), the same for every chunk of the segment
+  const uint32_t pa = OWN ? anchor_pos[k] : vox_start[ids[n0]];
+  if (OWN && pa == 0xffffffffu) {   // no own point in this segment: nothing counts
+    sd_empty_record(part + (size_t)c * SD_REC);
     return;
   }
   // nodes that overlap [a, b): the last node starting at or before a ... the last node starting before b.  Every node of a kept segment
@@ -120,11 +140,9 @@ __global__ __launch_bounds__(SD_TB) void k_sd_chunks(const float* __restrict__ x
     s_vp[t] = q;
     s_dl[t] = vox_start[ids[i]] - q;
   }
-  // the anchor: the segment's first point, the same for every chunk of the segment
-  const uint32_t pa = vox_start[ids[n0]];
   const double ax = (double)xs[pa], ay = (double)ys[pa], az = (double)zs[pa];
   __syncthreads();
-  double sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
+  double sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0, cnt = 0;
   float mnx = __builtin_huge_valf(), mny = __builtin_huge_valf(), mnz = __builtin_huge_valf();
   float mxx = -__builtin_huge_valf(), mxy = -__builtin_huge_valf(), mxz = -__builtin_huge_valf();
 #pragma unroll 2
@@ -134,6 +152,11 @@ __global__ __launch_bounds__(SD_TB) void k_sd_chunks(const float* __restrict__ x
       uint32_t l = 0, h = m - 1;   // the last node of the chunk that starts at or before q
       while (l < h) { const uint32_t mid = (l + h + 1) >> 1; if (s_vp[mid] <= q) l = mid; else h = mid - 1; }
       const uint32_t pos = q + s_dl[l];
+      if (OWN) {
+        const int64_t o = (int64_t)perm[pos];
+        if (o < own_first || o >= own_end) continue;
+        cnt += 1.0;
+      }
       const float x = xs[pos], y = ys[pos], z = zs[pos];
       mnx = fminf(mnx, x); mny = fminf(mny, y); mnz = fminf(mnz, z);
       mxx = fmaxf(mxx, x); mxy = fmaxf(mxy, y); mxz = fmaxf(mxz, z);
@@ -145,23 +168,67 @@ __global__ __launch_bounds__(SD_TB) void k_sd_chunks(const float* __restrict__ x
   }
   sx = sd_wave_sum(sx); sy = sd_wave_sum(sy); sz = sd_wave_sum(sz);
   sxx = sd_wave_sum(sxx); sxy = sd_wave_sum(sxy); sxz = sd_wave_sum(sxz); syy = sd_wave_sum(syy); syz = sd_wave_sum(syz); szz = sd_wave_sum(szz);
+  if (OWN) cnt = sd_wave_sum(cnt);
   mnx = sd_wave_min(mnx); mny = sd_wave_min(mny); mnz = sd_wave_min(mnz);
   mxx = sd_wave_max(mxx); mxy = sd_wave_max(mxy); mxz = sd_wave_max(mxz);
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     double* r = s_red[w];
     r[0] = sx; r[1] = sy; r[2] = sz; r[3] = sxx; r[4] = sxy; r[5] = sxz; r[6] = syy; r[7] = syz; r[8] = szz;
-    r[9] = mnx; r[10] = mny; r[11] = mnz; r[12] = mxx; r[13] = mxy; r[14] = mxz; r[15] = 0.0;
+    r[9] = mnx; r[10] = mny; r[11] = mnz; r[12] = mxx; r[13] = mxy; r[14] = mxz; r[15] = OWN ? cnt : 0.0;
   }
   __syncthreads();
   if (threadIdx.x < SD_REC) {   // the waves in index order
     const int f = threadIdx.x;
     double v = s_red[0][f];
-    if (f < 9) { for (int u = 1; u < SD_TB / 64; ++u) v += s_red[u][f]; }
+    if (f < 9 || (OWN && f == 15)) { for (int u = 1; u < SD_TB / 64; ++u) v += s_red[u][f]; }
     else if (f < 12) { for (int u = 1; u < SD_TB / 64; ++u) v = fmin(v, s_red[u][f]); }
     else if (f < 15) { for (int u = 1; u < SD_TB / 64; ++u) v = fmax(v, s_red[u][f]); }
     part[(size_t)c * SD_REC + f] = v;
   }
+}
+
+__global__ __launch_bounds__(SD_TB) void k_sd_chunks(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                     const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                     const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                     const uint32_t* __restrict__ seg_chunk, uint32_t K, double* __restrict__ part) {
+  sd_chunk_body<false>(xs, ys, zs, vox_start, ids, vp, seg_node, seg_chunk, K, part, nullptr, 0, 0, nullptr);
+}
+
+__global__ __launch_bounds__(SD_TB) void k_sd_chunks_own(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                         const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                         const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                         const uint32_t* __restrict__ seg_chunk, uint32_t K, double* __restrict__ part,
+                                                         const uint32_t* __restrict__ perm, int64_t own_first, int64_t own_end,
+                                                         const uint32_t* __restrict__ anchor_pos) {
+  sd_chunk_body<true>(xs, ys, zs, vox_start, ids, vp, seg_node, seg_chunk, K, part, perm, own_first, own_end, anchor_pos);
+}
+
+// Tile contexts: one wavefront per segment finds its first own point in the chunks' order (sorted nodes, each node's run in order):
+// 64 nodes at a time, each lane scans its node's run, the lowest lane that found one wins.  anchor_pos[k] = its sorted position, or
+// 0xffffffff when the segment holds no own point here.
+__global__ __launch_bounds__(256) void k_sd_own_anchor(const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                       const uint32_t* __restrict__ seg_node, const uint32_t* __restrict__ perm,
+                                                       int64_t own_first, int64_t own_end, uint32_t K, uint32_t* __restrict__ anchor_pos) {
+  const uint32_t k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (k >= K) return;   // (whole wavefronts; no barrier follows)
+  const uint32_t n0 = seg_node[k], n1 = seg_node[k + 1];
+  uint32_t found = 0xffffffffu;
+  for (uint32_t base = n0; base < n1; base += 64) {
+    const uint32_t i = base + lane;
+    uint32_t p = 0xffffffffu;
+    if (i < n1) {
+      const uint32_t v = ids[i], e = vox_start[v + 1];
+      for (uint32_t j = vox_start[v]; j < e; ++j) {
+        const int64_t o = (int64_t)perm[j];
+        if (o >= own_first && o < own_end) { p = j; break; }
+      }
+    }
+    const uint64_t hit = __ballot(p != 0xffffffffu);
+    if (hit) { found = __shfl(p, __ffsll((unsigned long long)hit) - 1, 64); break; }
+  }
+  if (lane == 0) anchor_pos[k] = found;
 }
 
 // One Jacobi rotation that zeroes A[p][q] (Numerical Recipes' jacobi: A' = J^T A J, W' = W J; r = the third index)
@@ -196,52 +263,55 @@ __device__ __forceinline__ void sd_order_pair(double (&d)[3], double (&W)[3][3])
   }
 }
 
-// one wavefront per segment: fold its partials (lane stride, then butterfly), then everything per segment on lane 0
-__global__ __launch_bounds__(256) void k_sd_final(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
-                                                  const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
-                                                  const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
-                                                  const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part, uint32_t n_part, uint32_t K, int svgs,
-                                                  int64_t* __restrict__ o_npts, int32_t* __restrict__ o_nnodes, float* __restrict__ o_bbox,
-                                                  double* __restrict__ o_cen, double* __restrict__ o_cov, double* __restrict__ o_eval,
-                                                  double* __restrict__ o_evec, float* __restrict__ o_eig8) {
-  const uint32_t k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const uint32_t lane = threadIdx.x & 63;
-  if (k >= K) return;   // (whole wavefronts; no barrier follows)
-  const uint32_t c0 = seg_chunk[k], c1 = min(seg_chunk[k + 1], n_part);   // (the bound only guards the records: the chunks fit, see the launch)
-  double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  double mn[3] = {__builtin_huge_val(), __builtin_huge_val(), __builtin_huge_val()};
-  double mx[3] = {-__builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val()};
+// The partials c0 .. c1 of one segment folded by one wavefront: lane stride, then butterfly; min / max come back as float values.
+// CNT: field 15 (the own-point count of k_sd_chunks_own) too.
+template <bool CNT>
+__device__ __forceinline__ void sd_fold_partials(const double* __restrict__ part, uint32_t c0, uint32_t c1, uint32_t lane, double (&s)[9],
+                                                 double (&mn)[3], double (&mx)[3], double& cnt) {
+#pragma unroll
+  for (int f = 0; f < 9; ++f) s[f] = 0.0;
+#pragma unroll
+  for (int f = 0; f < 3; ++f) { mn[f] = __builtin_huge_val(); mx[f] = -__builtin_huge_val(); }
+  if (CNT) cnt = 0.0;
   for (uint32_t c = c0 + lane; c < c1; c += 64) {
     const double* r = part + (size_t)c * SD_REC;
 #pragma unroll
     for (int f = 0; f < 9; ++f) s[f] += r[f];
 #pragma unroll
     for (int f = 0; f < 3; ++f) { mn[f] = fmin(mn[f], r[9 + f]); mx[f] = fmax(mx[f], r[12 + f]); }
+    if (CNT) cnt += r[15];
   }
 #pragma unroll
   for (int f = 0; f < 9; ++f) s[f] = sd_wave_sum(s[f]);
+  if (CNT) cnt = sd_wave_sum(cnt);
 #pragma unroll
   for (int f = 0; f < 3; ++f) { mn[f] = (double)sd_wave_min((float)mn[f]); mx[f] = (double)sd_wave_max((float)mx[f]); }
-  if (lane != 0) return;
-  const uint32_t n0 = seg_node[k], n1 = seg_node[k + 1];
-  const uint32_t n = vp[n1] - vp[n0];
-  const uint32_t pa = vox_start[ids[n0]];
-  const double anc[3] = {(double)xs[pa], (double)ys[pa], (double)zs[pa]};
-  o_npts[k] = (int64_t)n;
-  o_nnodes[k] = (int32_t)(n1 - n0);
+}
+
+// Row k of the table from a segment's folded moments: n points, n_nodes nodes, min / max, the anchor (a point of the segment, as
+// doubles) and s = sum d, sum d d^T (xx xy xz yy yz zz) with d = p - anchor.  Centroid, population covariance, cyclic Jacobi in fp64,
+// the sign rule and the features.  The one copy of this algebra: k_sd_final (one context) and k_sd_algebra (moments folded over tiles)
+// both call it, so equal moments give equal bytes.
+__device__ __forceinline__ void sd_segment_algebra(size_t k, int64_t n, int32_t n_nodes, const double (&mn)[3], const double (&mx)[3],
+                                                   const double (&anc)[3], const double (&s)[9], int svgs, int64_t* __restrict__ o_npts,
+                                                   int32_t* __restrict__ o_nnodes, float* __restrict__ o_bbox, double* __restrict__ o_cen,
+                                                   double* __restrict__ o_cov, double* __restrict__ o_eval, double* __restrict__ o_evec,
+                                                   float* __restrict__ o_eig8) {
+  o_npts[k] = n;
+  o_nnodes[k] = n_nodes;
 #pragma unroll
-  for (int f = 0; f < 3; ++f) { o_bbox[6 * (size_t)k + f] = (float)mn[f]; o_bbox[6 * (size_t)k + 3 + f] = (float)mx[f]; }
-  const double inv = 1.0 / (double)n;
+  for (int f = 0; f < 3; ++f) { o_bbox[6 * k + f] = (float)mn[f]; o_bbox[6 * k + 3 + f] = (float)mx[f]; }
+  const double inv = n > 0 ? 1.0 / (double)n : 0.0;   // (n = 0: no point anywhere -- zero moments about the anchor)
   const double md[3] = {s[0] * inv, s[1] * inv, s[2] * inv};
 #pragma unroll
-  for (int f = 0; f < 3; ++f) o_cen[3 * (size_t)k + f] = anc[f] + md[f];
+  for (int f = 0; f < 3; ++f) o_cen[3 * k + f] = anc[f] + md[f];
   // population covariance about the mean: E[d d^T] - E[d] E[d]^T, d relative to a point of the segment
   double cv[6];
   cv[0] = s[3] * inv - md[0] * md[0]; cv[1] = s[4] * inv - md[0] * md[1]; cv[2] = s[5] * inv - md[0] * md[2];
   cv[3] = s[6] * inv - md[1] * md[1]; cv[4] = s[7] * inv - md[1] * md[2]; cv[5] = s[8] * inv - md[2] * md[2];
-  if (n == 1) { for (int f = 0; f < 6; ++f) cv[f] = 0.0; }
+  if (n <= 1) { for (int f = 0; f < 6; ++f) cv[f] = 0.0; }
 #pragma unroll
-  for (int f = 0; f < 6; ++f) o_cov[6 * (size_t)k + f] = cv[f];
+  for (int f = 0; f < 6; ++f) o_cov[6 * k + f] = cv[f];
   // cyclic Jacobi in fp64 until the off-diagonal part is negligible against the diagonal
   double A[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
   double W[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
@@ -265,32 +335,96 @@ __global__ __launch_bounds__(256) void k_sd_final(const float* __restrict__ xs, 
     if (fabs(W[2][j]) > fabs(best)) best = W[2][j];
     if (best < 0.0) { W[0][j] = -W[0][j]; W[1][j] = -W[1][j]; W[2][j] = -W[2][j]; }
     d[j] = d[j] > 0.0 ? d[j] : 0.0;
-    o_eval[3 * (size_t)k + j] = d[j];
+    o_eval[3 * k + j] = d[j];
   }
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int j = 0; j < 3; ++j) o_evec[9 * (size_t)k + 3 * r + j] = W[r][j];
+    for (int j = 0; j < 3; ++j) o_evec[9 * k + 3 * r + j] = W[r][j];
   const float ef[3] = {(float)d[0], (float)d[1], (float)d[2]};
   float F[8];
   vm_eigen_features(ef, svgs, F);
 #pragma unroll
-  for (int f = 0; f < 8; ++f) o_eig8[8 * (size_t)k + f] = F[f];
+  for (int f = 0; f < 8; ++f) o_eig8[8 * k + f] = F[f];
+}
+
+// one wavefront per segment: fold its partials (lane stride, then butterfly), then everything per segment on lane 0
+__global__ __launch_bounds__(256) void k_sd_final(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                  const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                  const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                  const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part, uint32_t n_part, uint32_t K, int svgs,
+                                                  int64_t* __restrict__ o_npts, int32_t* __restrict__ o_nnodes, float* __restrict__ o_bbox,
+                                                  double* __restrict__ o_cen, double* __restrict__ o_cov, double* __restrict__ o_eval,
+                                                  double* __restrict__ o_evec, float* __restrict__ o_eig8) {
+  const uint32_t k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (k >= K) return;   // (whole wavefronts; no barrier follows)
+  const uint32_t c0 = seg_chunk[k], c1 = min(seg_chunk[k + 1], n_part);   // (the bound only guards the records: the chunks fit, see the launch)
+  double s[9], mn[3], mx[3], cnt;
+  sd_fold_partials<false>(part, c0, c1, lane, s, mn, mx, cnt);
+  if (lane != 0) return;
+  const uint32_t n0 = seg_node[k], n1 = seg_node[k + 1];
+  const uint32_t n = vp[n1] - vp[n0];
+  const uint32_t pa = vox_start[ids[n0]];
+  const double anc[3] = {(double)xs[pa], (double)ys[pa], (double)zs[pa]};
+  sd_segment_algebra(k, (int64_t)n, (int32_t)(n1 - n0), mn, mx, anc, s, svgs, o_npts, o_nnodes, o_bbox, o_cen, o_cov, o_eval, o_evec, o_eig8);
+}
+
+// Tile contexts: one wavefront per segment folds the partials of k_sd_chunks_own exactly as k_sd_final does, counts the segment's
+// owned voxels (lane stride, then butterfly) and writes its moment record: SD_MREC doubles = own points, owned voxels, min[3], max[3]
+// (float values), anchor[3] (the first own point's floats; 0 without one), sum d[3], sum d d^T[6].
+#define SD_MREC 20
+__global__ __launch_bounds__(256) void k_sd_own_records(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                        const uint32_t* __restrict__ ids, const uint32_t* __restrict__ seg_node,
+                                                        const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part, uint32_t n_part,
+                                                        const uint32_t* __restrict__ anchor_pos, const uint8_t* __restrict__ owned, uint32_t K,
+                                                        double* __restrict__ mom) {
+  const uint32_t k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (k >= K) return;   // (whole wavefronts; no barrier follows)
+  const uint32_t c0 = seg_chunk[k], c1 = min(seg_chunk[k + 1], n_part);
+  double s[9], mn[3], mx[3], cnt;
+  sd_fold_partials<true>(part, c0, c1, lane, s, mn, mx, cnt);
+  const uint32_t n0 = seg_node[k], n1 = seg_node[k + 1];
+  uint32_t no = 0;
+  for (uint32_t i = n0 + lane; i < n1; i += 64) no += owned[ids[i]] ? 1u : 0u;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) no += __shfl_xor(no, m, 64);
+  if (lane != 0) return;
+  const uint32_t pa = anchor_pos[k];
+  double* r = mom + (size_t)k * SD_MREC;
+  r[0] = cnt;
+  r[1] = (double)no;
+#pragma unroll
+  for (int f = 0; f < 3; ++f) { r[2 + f] = mn[f]; r[5 + f] = mx[f]; }
+  r[8] = pa != 0xffffffffu ? (double)xs[pa] : 0.0;
+  r[9] = pa != 0xffffffffu ? (double)ys[pa] : 0.0;
+  r[10] = pa != 0xffffffffu ? (double)zs[pa] : 0.0;
+#pragma unroll
+  for (int f = 0; f < 9; ++f) r[11 + f] = s[f];
+}
+
+// Moments folded over the ranks (same record layout as k_sd_own_records) -> the table: one thread per segment, sd_segment_algebra
+__global__ __launch_bounds__(256) void k_sd_algebra(const double* __restrict__ mom, uint32_t K, int svgs, int64_t* __restrict__ o_npts,
+                                                    int32_t* __restrict__ o_nnodes, float* __restrict__ o_bbox, double* __restrict__ o_cen,
+                                                    double* __restrict__ o_cov, double* __restrict__ o_eval, double* __restrict__ o_evec,
+                                                    float* __restrict__ o_eig8) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K) return;
+  const double* r = mom + (size_t)k * SD_MREC;
+  const double mn[3] = {r[2], r[3], r[4]}, mx[3] = {r[5], r[6], r[7]}, anc[3] = {r[8], r[9], r[10]};
+  const double s[9] = {r[11], r[12], r[13], r[14], r[15], r[16], r[17], r[18], r[19]};
+  sd_segment_algebra(k, (int64_t)r[0], (int32_t)r[1], mn, mx, anc, s, svgs, o_npts, o_nnodes, o_bbox, o_cen, o_cov, o_eval, o_evec, o_eig8);
 }
 
 static bool vgs_is_tile(const vgs_ctx* c) { return c->have_region || c->n_own >= 0; }
 
-// The table in HBM, K = counts[VGS_N_KEPT] rows; valid until the next run of the stages.
-vgs_status vgs_segdesc_on_device(vgs_ctx* c) {
-  if (c->sd_valid) return VGS_OK;
-  const int64_t K = c->counts[VGS_N_KEPT], V = c->V, nf = c->Nf;
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  const size_t k1 = (size_t)(K > 0 ? K : 1);
-  VGS_HIP_TRY(c, c->sd_npts.ensure(k1)); VGS_HIP_TRY(c, c->sd_nnodes.ensure(k1));
-  VGS_HIP_TRY(c, c->sd_bbox.ensure(6 * k1)); VGS_HIP_TRY(c, c->sd_eig8.ensure(8 * k1));
-  VGS_HIP_TRY(c, c->sd_cen.ensure(3 * k1)); VGS_HIP_TRY(c, c->sd_cov.ensure(6 * k1));
-  VGS_HIP_TRY(c, c->sd_eval.ensure(3 * k1)); VGS_HIP_TRY(c, c->sd_evec.ensure(9 * k1));
-  if (K == 0 || V == 0 || nf == 0) { c->sd_valid = true; return VGS_OK; }
+// Steps 1-2 for labels 0 .. K-1 and the launch of step 3's grid bound: sorted node ids, virtual positions, per segment its first sorted
+// node and first chunk.  Pointers into the sd_* scratch.
+struct SdPrep { uint32_t *ids, *vp, *seg_node, *seg_chunk; int64_t n_chunks_max; };
+
+static vgs_status sd_prepare(vgs_ctx* c, int64_t K, SdPrep& o) {
+  const int64_t V = c->V, nf = c->Nf;
   VGS_HIP_TRY(c, c->sd_key.ensure(2 * (size_t)V)); VGS_HIP_TRY(c, c->sd_ids.ensure(2 * (size_t)V));
   VGS_HIP_TRY(c, c->sd_vp.ensure(2 * ((size_t)V + 1)));
   VGS_HIP_TRY(c, c->sd_seg.ensure(3 * ((size_t)K + 1)));
@@ -316,12 +450,34 @@ vgs_status vgs_segdesc_on_device(vgs_ctx* c) {
                      seg_node, nchunk);
   VGS_HIP_TRY(c, rocprim::exclusive_scan(c->sd_tmp.p, t_scan2, nchunk, seg_chunk, 0u, (size_t)K + 1, rocprim::plus<uint32_t>(), c->stream));
   // sum over segments of ceil(n_k / SD_CHUNK) <= floor(Nf / SD_CHUNK) + K: launched without reading the real number back
-  const int64_t n_chunks_max = nf / SD_CHUNK + K + 1;
-  VGS_HIP_TRY(c, c->sd_part.ensure((size_t)n_chunks_max * SD_REC));
-  hipLaunchKernelGGL(k_sd_chunks, dim3((unsigned)n_chunks_max), dim3(SD_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, ids_out, vp,
-                     seg_node, seg_chunk, (uint32_t)K, c->sd_part.p);
-  hipLaunchKernelGGL(k_sd_final, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, ids_out, vp,
-                     seg_node, seg_chunk, c->sd_part.p, (uint32_t)n_chunks_max, (uint32_t)K, c->P.method == 3 ? 1 : 0, c->sd_npts.p, c->sd_nnodes.p, c->sd_bbox.p,
+  o.n_chunks_max = nf / SD_CHUNK + K + 1;
+  VGS_HIP_TRY(c, c->sd_part.ensure((size_t)o.n_chunks_max * SD_REC));
+  o.ids = ids_out; o.vp = vp; o.seg_node = seg_node; o.seg_chunk = seg_chunk;
+  return VGS_OK;
+}
+
+static vgs_status sd_ensure_table(vgs_ctx* c, size_t k1) {
+  VGS_HIP_TRY(c, c->sd_npts.ensure(k1)); VGS_HIP_TRY(c, c->sd_nnodes.ensure(k1));
+  VGS_HIP_TRY(c, c->sd_bbox.ensure(6 * k1)); VGS_HIP_TRY(c, c->sd_eig8.ensure(8 * k1));
+  VGS_HIP_TRY(c, c->sd_cen.ensure(3 * k1)); VGS_HIP_TRY(c, c->sd_cov.ensure(6 * k1));
+  VGS_HIP_TRY(c, c->sd_eval.ensure(3 * k1)); VGS_HIP_TRY(c, c->sd_evec.ensure(9 * k1));
+  return VGS_OK;
+}
+
+// The table in HBM, K = counts[VGS_N_KEPT] rows; valid until the next run of the stages.
+vgs_status vgs_segdesc_on_device(vgs_ctx* c) {
+  if (c->sd_valid) return VGS_OK;
+  const int64_t K = c->counts[VGS_N_KEPT], V = c->V, nf = c->Nf;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  vgs_status s = sd_ensure_table(c, (size_t)(K > 0 ? K : 1));
+  if (s != VGS_OK) return s;
+  if (K == 0 || V == 0 || nf == 0) { c->sd_valid = true; return VGS_OK; }
+  SdPrep P;
+  if ((s = sd_prepare(c, K, P)) != VGS_OK) return s;
+  hipLaunchKernelGGL(k_sd_chunks, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, P.ids, P.vp,
+                     P.seg_node, P.seg_chunk, (uint32_t)K, c->sd_part.p);
+  hipLaunchKernelGGL(k_sd_final, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, P.ids, P.vp,
+                     P.seg_node, P.seg_chunk, c->sd_part.p, (uint32_t)P.n_chunks_max, (uint32_t)K, c->P.method == 3 ? 1 : 0, c->sd_npts.p, c->sd_nnodes.p, c->sd_bbox.p,
                      c->sd_cen.p, c->sd_cov.p, c->sd_eval.p, c->sd_evec.p, c->sd_eig8.p);
   VGS_HIP_TRY(c, hipGetLastError());
   VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -372,5 +528,91 @@ extern "C" vgs_status vgs_get_segment_descriptors_device(vgs_ctx* c, const int64
   if (evals3) *evals3 = c->sd_eval.p;
   if (evecs9) *evecs9 = c->sd_evec.p;
   if (eigen8) *eigen8 = c->sd_eig8.p;
+  return VGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ tile contexts (include/vgs_tiles.h)
+// This rank's moments of the global labels 0 .. K-1: the pipeline above over vox_label (global after vgs_apply_tile_labels), with the
+// own-point chunks, the first own point as anchor, and the owned-voxel count.  Dense on the device (K records), compact on the host.
+extern "C" vgs_status vgs_get_own_segment_moments(vgs_ctx* c, int64_t K, int64_t* n_records, int32_t* label, int64_t* n_points, int32_t* n_nodes,
+                                                  float* bbox6, float* anchor3, double* s9) {
+  if (!c || !n_records || K < 0 || K >= (int64_t)0xffffffffLL) return VGS_E_ARG;
+  if (c->stage < ST_SEGMENTED) { c->err = "vgs_get_own_segment_moments: segment first"; return VGS_E_STATE; }
+  if (!c->have_region || c->n_own < 0) {
+    c->err = "vgs_get_own_segment_moments: a tile context (vgs_set_owned_region and vgs_set_own_point_range) only";
+    return VGS_E_STATE;
+  }
+  *n_records = 0;
+  const int64_t V = c->V, nf = c->Nf;
+  if (K == 0 || V == 0 || nf == 0) return VGS_OK;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  SdPrep P;
+  vgs_status s = sd_prepare(c, K, P);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, c->sd_apos.ensure((size_t)K));
+  VGS_HIP_TRY(c, c->sd_mom.ensure((size_t)K * SD_MREC));
+  const int64_t own_end = c->own_first + c->n_own;
+  const unsigned waves_grid = (unsigned)((K + 3) / 4);
+  hipLaunchKernelGGL(k_sd_own_anchor, dim3(waves_grid), dim3(256), 0, c->stream, c->vox_start.p, P.ids, P.seg_node, c->perm_b.p, c->own_first,
+                     own_end, (uint32_t)K, c->sd_apos.p);
+  hipLaunchKernelGGL(k_sd_chunks_own, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, P.ids, P.vp,
+                     P.seg_node, P.seg_chunk, (uint32_t)K, c->sd_part.p, c->perm_b.p, c->own_first, own_end, c->sd_apos.p);
+  hipLaunchKernelGGL(k_sd_own_records, dim3(waves_grid), dim3(256), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, P.ids, P.seg_node, P.seg_chunk,
+                     c->sd_part.p, (uint32_t)P.n_chunks_max, c->sd_apos.p, c->owned.p, (uint32_t)K, c->sd_mom.p);
+  VGS_HIP_TRY(c, hipGetLastError());
+  std::vector<double> m((size_t)K * SD_MREC);
+  VGS_HIP_TRY(c, hipMemcpyAsync(m.data(), c->sd_mom.p, m.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int64_t n = 0;
+  for (int64_t k = 0; k < K; ++k) {
+    const double* r = m.data() + (size_t)k * SD_MREC;
+    if (r[0] == 0.0 && r[1] == 0.0) continue;   // neither an own point nor an owned voxel of this label here
+    if (label) label[n] = (int32_t)k;
+    if (n_points) n_points[n] = (int64_t)r[0];
+    if (n_nodes) n_nodes[n] = (int32_t)r[1];
+    if (bbox6) for (int f = 0; f < 6; ++f) bbox6[6 * n + f] = (float)r[2 + f];
+    if (anchor3) for (int f = 0; f < 3; ++f) anchor3[3 * n + f] = (float)r[8 + f];
+    if (s9) for (int f = 0; f < 9; ++f) s9[9 * n + f] = r[11 + f];
+    ++n;
+  }
+  *n_records = n;
+  return VGS_OK;
+}
+
+// The table from moments folded over the ranks: uploaded as SD_MREC records, k_sd_algebra, the caller's arrays written back.
+extern "C" vgs_status vgs_segment_descriptors_from_moments(vgs_ctx* c, int64_t K, const int64_t* n_points, const int32_t* n_nodes, const float* bbox6,
+                                                           const float* anchor3, const double* s9, int64_t* n_points_out, int32_t* n_nodes_out,
+                                                           float* bbox6_out, double* centroid3, double* cov6, double* evals3, double* evecs9,
+                                                           float* eigen8) {
+  if (!c || K < 0 || K >= (int64_t)0xffffffffLL || (K > 0 && (!n_points || !n_nodes || !bbox6 || !anchor3 || !s9))) return VGS_E_ARG;
+  if (K == 0) return VGS_OK;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<double> m((size_t)K * SD_MREC);
+  for (int64_t k = 0; k < K; ++k) {
+    double* r = m.data() + (size_t)k * SD_MREC;
+    r[0] = (double)n_points[k];
+    r[1] = (double)n_nodes[k];
+    for (int f = 0; f < 6; ++f) r[2 + f] = (double)bbox6[6 * k + f];
+    for (int f = 0; f < 3; ++f) r[8 + f] = (double)anchor3[3 * k + f];
+    for (int f = 0; f < 9; ++f) r[11 + f] = s9[9 * k + f];
+  }
+  c->sd_valid = false;   // (the table buffers now hold these rows)
+  vgs_status s = sd_ensure_table(c, (size_t)K);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, c->sd_mom.ensure(m.size()));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->sd_mom.p, m.data(), m.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_sd_algebra, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, c->sd_mom.p, (uint32_t)K, c->P.method == 3 ? 1 : 0,
+                     c->sd_npts.p, c->sd_nnodes.p, c->sd_bbox.p, c->sd_cen.p, c->sd_cov.p, c->sd_eval.p, c->sd_evec.p, c->sd_eig8.p);
+  VGS_HIP_TRY(c, hipGetLastError());
+  const size_t k = (size_t)K;
+  if (n_points_out) VGS_HIP_TRY(c, hipMemcpyAsync(n_points_out, c->sd_npts.p, k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  if (n_nodes_out) VGS_HIP_TRY(c, hipMemcpyAsync(n_nodes_out, c->sd_nnodes.p, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (bbox6_out) VGS_HIP_TRY(c, hipMemcpyAsync(bbox6_out, c->sd_bbox.p, 6 * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (centroid3) VGS_HIP_TRY(c, hipMemcpyAsync(centroid3, c->sd_cen.p, 3 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (cov6) VGS_HIP_TRY(c, hipMemcpyAsync(cov6, c->sd_cov.p, 6 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (evals3) VGS_HIP_TRY(c, hipMemcpyAsync(evals3, c->sd_eval.p, 3 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (evecs9) VGS_HIP_TRY(c, hipMemcpyAsync(evecs9, c->sd_evec.p, 9 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (eigen8) VGS_HIP_TRY(c, hipMemcpyAsync(eigen8, c->sd_eig8.p, 8 * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VGS_OK;
 }

@@ -195,6 +195,57 @@ void merge_boundary_compact(const std::vector<RankRecords>& rec, const std::vect
   kept_total = next_label;
 }
 
+// ------------------------------------------------------------------------------------------------ descriptor moments
+// One rank's moments of one global label (vgs_get_own_segment_moments); the payload of the descriptor exchange.  Its first entry is the
+// header: label = the rank's status word, n_points = its record count.
+struct MomentRec {
+  int32_t label = 0, n_nodes = 0;
+  int64_t n_points = 0;
+  float bbox[6] = {0, 0, 0, 0, 0, 0};
+  float anchor[3] = {0, 0, 0};
+  float pad = 0;
+  double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
+static_assert(sizeof(MomentRec) == 128, "MomentRec is the exchange's wire format");
+
+// The moments of every global label 0 .. K-1 from the ranks' records, the same bytes on every rank: per label, ranks in ascending order.
+// The anchor is the lowest rank's with own points; another rank's sums move to it by delta = a_r - a (exact in fp64: a float minus a
+// float): S1 += S1_r + n_r delta, S2 += S2_r + S1_r delta^T + delta S1_r^T + n_r delta delta^T.  Counts add, boxes take min / max.
+// Returns false if a record names a label outside 0 .. K-1.
+bool fold_moments(const std::vector<std::vector<MomentRec>>& ranks, int64_t K, std::vector<int64_t>& npts, std::vector<int32_t>& nnodes,
+                  std::vector<float>& bbox, std::vector<float>& anchor, std::vector<double>& s9) {
+  const float inf = __builtin_huge_valf();
+  npts.assign((size_t)K, 0); nnodes.assign((size_t)K, 0); anchor.assign(3 * (size_t)K, 0.0f); s9.assign(9 * (size_t)K, 0.0);
+  bbox.assign(6 * (size_t)K, 0.0f);
+  for (int64_t k = 0; k < K; ++k) for (int a = 0; a < 3; ++a) { bbox[6 * (size_t)k + a] = inf; bbox[6 * (size_t)k + 3 + a] = -inf; }
+  for (const std::vector<MomentRec>& R : ranks)
+    for (const MomentRec& m : R) {
+      if (m.label < 0 || (int64_t)m.label >= K) return false;
+      const size_t k = (size_t)m.label;
+      nnodes[k] += m.n_nodes;
+      for (int a = 0; a < 3; ++a) { bbox[6 * k + a] = std::min(bbox[6 * k + a], m.bbox[a]); bbox[6 * k + 3 + a] = std::max(bbox[6 * k + 3 + a], m.bbox[3 + a]); }
+      if (m.n_points <= 0) continue;
+      double* S = s9.data() + 9 * k;
+      if (npts[k] == 0) {   // the first rank with points: its anchor, its sums as they are
+        for (int a = 0; a < 3; ++a) anchor[3 * k + a] = m.anchor[a];
+        for (int f = 0; f < 9; ++f) S[f] = m.s[f];
+        npts[k] = m.n_points;
+        continue;
+      }
+      const double n = (double)m.n_points;
+      double d[3];
+      for (int a = 0; a < 3; ++a) d[a] = (double)m.anchor[a] - (double)anchor[3 * k + a];
+      for (int a = 0; a < 3; ++a) S[a] += m.s[a] + n * d[a];
+      static const int I[6] = {0, 0, 0, 1, 1, 2}, J[6] = {0, 1, 2, 1, 2, 2};
+      for (int f = 0; f < 6; ++f) {
+        const int i = I[f], j = J[f];
+        S[3 + f] += m.s[3 + f] + m.s[i] * d[j] + d[i] * m.s[j] + n * d[i] * d[j];
+      }
+      npts[k] += m.n_points;
+    }
+  return true;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ driver
@@ -210,9 +261,18 @@ struct vgs_tiles {
   int64_t exch_sent = 0, exch_recv = 0; int exch_calls = 0;   // the last run's boundary exchange: bytes this rank sent / received, collectives it took
   double times[VGS_TILES_T_COUNT] = {0};   // last run, milliseconds of host wall time per phase (vgs_tiles_get_times)
   int strict_region = 0;      // VGS_TILES_OPT_STRICT_REGION
-  int fail_phase = 0;         // tests (VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT): 1 grid, 2 stages, 3 points, 4 upload (behind the last collective of set_points)
+  int fail_phase = 0;         // tests (VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT): 1 grid, 2 stages, 3 points, 4 upload (behind the last collective of set_points),
+                              // 5 descriptors (before the descriptor exchange)
   vgs_status pending = VGS_OK;   // a local failure behind a call's last collective: the status word of the next collective carries it
   bool warned_outside = false;
+  bool ran = false;              // the last vgs_tiles_run completed here
+  // the global descriptor table of the last run (vgs_tiles_get_segment_descriptors), K = kept rows; valid until the next run / set_points
+  bool desc_valid = false;
+  std::vector<int64_t> d_npts;
+  std::vector<int32_t> d_nnodes;
+  std::vector<float> d_bbox, d_eig8;
+  std::vector<double> d_cen, d_cov, d_eval, d_evec;
+  double dtimes[VGS_TILES_D_COUNT] = {0};   // the last descriptor collective, milliseconds of host wall time per phase
   std::string err;
 };
 
@@ -262,7 +322,7 @@ vgs_status vgs_tiles_create(const vgs_params* p, int comm_kind, void* comm_handl
     // failure injection for the tests of the agreed-status protocol; read once, here
     const char* fr = std::getenv("VGS_TILES_FAIL_RANK");
     const char* fa = std::getenv("VGS_TILES_FAIL_AT");
-    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : 0;
+    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : !std::strcmp(fa, "descriptors") ? 5 : 0;
   }
   vgs_status s = vgs_create(p, &t->ctx);
   if (s != VGS_OK) { delete t->comm; delete t; return s; }
@@ -295,6 +355,7 @@ vgs_status vgs_tiles_get_times(vgs_tiles* t, double* ms, int32_t n) {
 vgs_status vgs_tiles_set_points(vgs_tiles* t, const float* xyz, int64_t n, int32_t stride_bytes) {
   if (!t || (!xyz && n > 0) || n < 0 || (stride_bytes != 12 && stride_bytes != 16)) return VGS_E_ARG;
   Comm& c = *t->comm;
+  t->ran = false; t->desc_valid = false;
   const int sf = stride_bytes / 4;
   if (!(t->pitch > 0)) {   // the largest x-extent over the ranks
     float mn = 3.0e38f, mx = -3.0e38f;
@@ -431,6 +492,7 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
   if (!t) return VGS_E_ARG;
   Comm& c = *t->comm;
   vgs_status carry = t->pending;   // a local failure behind the last collective of the previous call (upload, label write-back) travels now
+  t->ran = false; t->desc_valid = false;
   double t0 = now_ms();
   vgs_status s = chain_grid(t, carry);
   if (s != VGS_OK) return s;
@@ -513,6 +575,115 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
   double t6 = now_ms();
   t->times[VGS_TILES_T_LABELS] = t6 - t5;
   t->times[VGS_TILES_T_TOTAL] = t6 - t0;
+  t->ran = true;
+  return VGS_OK;
+}
+
+// Descriptors over the ranks: this rank's moments (one small pipeline on its GPU) -> ONE all_gather_varlen of the records with a header
+// of status word and record count -> the same host fold on every rank -> the per-segment algebra on this rank's GPU.  Same bytes on every
+// rank: the fold's inputs and order are the same everywhere, and the algebra is one deterministic device function of its inputs.
+vgs_status vgs_tiles_get_segment_descriptors(vgs_tiles* t, int64_t* K, int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3,
+                                             double* cov6, double* evals3, double* evecs9, float* eigen8) {
+  if (!t) return VGS_E_ARG;
+  if (K) *K = t->kept;
+  if (!n_points && !n_nodes && !bbox6 && !centroid3 && !cov6 && !evals3 && !evecs9 && !eigen8) return VGS_OK;   // size query: no collective
+  if (!t->desc_valid) {
+    // a rank whose last call failed behind its last collective still comes, with that status; one that never ran does not (nor do its peers)
+    if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_descriptors: vgs_tiles_run first");
+    Comm& c = *t->comm;
+    const int64_t Kg = t->kept;
+    vgs_status carry = t->pending;
+    if (t->fail_phase == 5 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=descriptors"; }
+    const double t0 = now_ms();
+    std::vector<MomentRec> payload(1);
+    if (carry == VGS_OK && Kg > 0) {
+      const size_t k1 = (size_t)Kg;
+      std::vector<int32_t> lab(k1), nn(k1);
+      std::vector<int64_t> np(k1);
+      std::vector<float> bb(6 * k1), an(3 * k1);
+      std::vector<double> sm(9 * k1);
+      int64_t n = 0;
+      TCARRY(vgs_get_own_segment_moments(t->ctx, Kg, &n, lab.data(), np.data(), nn.data(), bb.data(), an.data(), sm.data()));
+      if (carry == VGS_OK) {
+        payload.resize(1 + (size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+          MomentRec& m = payload[1 + (size_t)i];
+          m.label = lab[(size_t)i]; m.n_nodes = nn[(size_t)i]; m.n_points = np[(size_t)i];
+          for (int a = 0; a < 6; ++a) m.bbox[a] = bb[6 * (size_t)i + a];
+          for (int a = 0; a < 3; ++a) m.anchor[a] = an[3 * (size_t)i + a];
+          for (int f = 0; f < 9; ++f) m.s[f] = sm[9 * (size_t)i + f];
+        }
+      }
+    }
+    payload[0].label = (int32_t)carry;
+    payload[0].n_points = (int64_t)payload.size() - 1;
+    const double t1 = now_ms();
+    std::vector<std::vector<MomentRec>> gathered;
+    TCOMM(all_gather_varlen(c, payload, gathered));
+    const double t2 = now_ms();
+    {
+      int bad = -1;
+      for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].empty() || gathered[(size_t)r][0].label != 0) bad = r;
+      vgs_status a = agreed(t, carry, bad, "descriptors");
+      if (a != VGS_OK) return a;
+    }
+    for (std::vector<MomentRec>& g : gathered) g.erase(g.begin());   // the headers
+    std::vector<int64_t> npts;
+    std::vector<int32_t> nnodes;
+    std::vector<float> bbox, anchor;
+    std::vector<double> s9;
+    if (!fold_moments(gathered, Kg, npts, nnodes, bbox, anchor, s9)) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_descriptors: a rank sent a label >= kept_global");
+    const double t3 = now_ms();
+    const size_t k1 = (size_t)Kg;
+    t->d_npts.resize(k1); t->d_nnodes.resize(k1); t->d_bbox.resize(6 * k1); t->d_cen.resize(3 * k1); t->d_cov.resize(6 * k1);
+    t->d_eval.resize(3 * k1); t->d_evec.resize(9 * k1); t->d_eig8.resize(8 * k1);
+    // (local, behind the collective: the rank returns its error and keeps it for the next collective, as the label write-back does)
+    const vgs_status sa = vgs_segment_descriptors_from_moments(t->ctx, Kg, npts.data(), nnodes.data(), bbox.data(), anchor.data(), s9.data(),
+                                                               t->d_npts.data(), t->d_nnodes.data(), t->d_bbox.data(), t->d_cen.data(), t->d_cov.data(),
+                                                               t->d_eval.data(), t->d_evec.data(), t->d_eig8.data());
+    if (sa != VGS_OK) { t->pending = sa; return tfail(t, sa, std::string("vgs_segment_descriptors_from_moments: ") + vgs_last_error_string(t->ctx)); }
+    const double t4 = now_ms();
+    t->dtimes[VGS_TILES_D_MOMENTS] = t1 - t0; t->dtimes[VGS_TILES_D_EXCHANGE] = t2 - t1; t->dtimes[VGS_TILES_D_FOLD] = t3 - t2;
+    t->dtimes[VGS_TILES_D_ALGEBRA] = t4 - t3; t->dtimes[VGS_TILES_D_TOTAL] = t4 - t0;
+    t->desc_valid = true;
+  }
+  auto put = [](const auto& v, auto* dst) { if (dst) std::copy(v.begin(), v.end(), dst); };
+  put(t->d_npts, n_points); put(t->d_nnodes, n_nodes); put(t->d_bbox, bbox6); put(t->d_cen, centroid3); put(t->d_cov, cov6);
+  put(t->d_eval, evals3); put(t->d_evec, evecs9); put(t->d_eig8, eigen8);
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_descriptor_times(vgs_tiles* t, double* ms, int32_t n) {
+  if (!t || !ms || n < 0 || n > VGS_TILES_D_COUNT) return VGS_E_ARG;
+  for (int i = 0; i < n; ++i) ms[i] = t->dtimes[i];
+  return VGS_OK;
+}
+
+// host arithmetic only (tests): the descriptor fold on flattened per-rank records
+vgs_status vgs_tiles_fold_moments(int world, const int64_t* rec_off, const int32_t* label, const int64_t* n_points, const int32_t* n_nodes,
+                                  const float* bbox6, const float* anchor3, const double* s9, int64_t K, int64_t* n_points_out,
+                                  int32_t* n_nodes_out, float* bbox6_out, float* anchor3_out, double* s9_out) {
+  if (world < 1 || !rec_off || K < 0 || !n_points_out || !n_nodes_out || !bbox6_out || !anchor3_out || !s9_out) return VGS_E_ARG;
+  if (rec_off[world] > 0 && (!label || !n_points || !n_nodes || !bbox6 || !anchor3 || !s9)) return VGS_E_ARG;
+  std::vector<std::vector<MomentRec>> ranks((size_t)world);
+  for (int r = 0; r < world; ++r) {
+    if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
+    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) {
+      MomentRec m;
+      m.label = label[i]; m.n_nodes = n_nodes[i]; m.n_points = n_points[i];
+      for (int a = 0; a < 6; ++a) m.bbox[a] = bbox6[6 * i + a];
+      for (int a = 0; a < 3; ++a) m.anchor[a] = anchor3[3 * i + a];
+      for (int f = 0; f < 9; ++f) m.s[f] = s9[9 * i + f];
+      ranks[(size_t)r].push_back(m);
+    }
+  }
+  std::vector<int64_t> np;
+  std::vector<int32_t> nn;
+  std::vector<float> bb, an;
+  std::vector<double> sm;
+  if (!fold_moments(ranks, K, np, nn, bb, an, sm)) return VGS_E_ARG;
+  std::copy(np.begin(), np.end(), n_points_out); std::copy(nn.begin(), nn.end(), n_nodes_out);
+  std::copy(bb.begin(), bb.end(), bbox6_out); std::copy(an.begin(), an.end(), anchor3_out); std::copy(sm.begin(), sm.end(), s9_out);
   return VGS_OK;
 }
 

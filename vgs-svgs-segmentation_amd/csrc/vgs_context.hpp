@@ -264,6 +264,9 @@ struct vgs_ctx {
   DevBuf<float> sd_bbox, sd_eig8;
   DevBuf<double> sd_cen, sd_cov, sd_eval, sd_evec;
   bool sd_valid = false;
+  // tile contexts (vgs_get_own_segment_moments / vgs_segment_descriptors_from_moments): first own point per segment, moment records
+  DevBuf<uint32_t> sd_apos;
+  DevBuf<double> sd_mom;
   // segment adjacency graph (seggraph.hip): the edge table of the kept segments, computed on request, valid until the next run (sg_valid);
   // its effective labels, per-row records, sort, scans and partials use their own scratch (no getter reads it)
   DevBuf<int32_t> sg_lab;

@@ -24,6 +24,9 @@ _TL = None
 _RCCL = None
 
 T_NAMES = ("grid", "stages", "records", "exchange", "merge", "labels", "total")
+D_NAMES = ("moments", "exchange", "fold", "algebra", "total")   # vgs_tiles_get_descriptor_times
+# per record / row: (field, dtype, values) of vgs_get_own_segment_moments and vgs_tiles_fold_moments, in their argument order
+MOMENT_FIELDS = (("n_points", np.int64, 1), ("n_nodes", np.int32, 1), ("bbox6", np.float32, 6), ("anchor3", np.float32, 3), ("s9", np.float64, 9))
 COMM_RCCL, COMM_LOCAL, COMM_CALLBACKS = 0, 1, 2
 OPT_STRICT_REGION = 1
 
@@ -72,8 +75,36 @@ def lib():
         L.vgs_tiles_local_group_abort.argtypes = [P]
         L.vgs_tiles_merge_boundary.restype = C.c_int
         L.vgs_tiles_merge_boundary.argtypes = [C.c_int, P, P, P, P, P, C.c_int, P, P, P, P, P]
+        L.vgs_tiles_get_segment_descriptors.restype = C.c_int
+        L.vgs_tiles_get_segment_descriptors.argtypes = [P, P, P, P, P, P, P, P, P, P]
+        L.vgs_tiles_get_descriptor_times.restype = C.c_int
+        L.vgs_tiles_get_descriptor_times.argtypes = [P, P, C.c_int32]
+        L.vgs_tiles_fold_moments.restype = C.c_int
+        L.vgs_tiles_fold_moments.argtypes = [C.c_int, P, P, P, P, P, P, P, C.c_int64, P, P, P, P, P]
         _TL = L
     return _TL
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def fold_moments(records, K):
+    """vgs_tiles_fold_moments (host arithmetic, no GPU): records[r] = rank r's dict of MOMENT_FIELDS arrays plus "label" (int32), as
+    vgs_get_own_segment_moments gives them; returns the K folded rows as a dict of MOMENT_FIELDS arrays."""
+    world = len(records)
+    n = [len(r["label"]) for r in records]
+    off = np.zeros(world + 1, dtype=np.int64)
+    off[1:] = np.cumsum(n)
+    flat = {"label": np.ascontiguousarray(np.concatenate([r["label"] for r in records]).astype(np.int32))}
+    for name, dt, w in MOMENT_FIELDS:
+        flat[name] = np.ascontiguousarray(np.concatenate([np.asarray(r[name], dtype=dt).reshape(-1, w) for r in records]).reshape(-1))
+    out = {name: np.zeros((K, w) if w > 1 else K, dtype=dt) for name, dt, w in MOMENT_FIELDS}
+    st = lib().vgs_tiles_fold_moments(world, _vp(off), _vp(flat["label"]), *(_vp(flat[name]) for name, _, _ in MOMENT_FIELDS), int(K),
+                                      *(_vp(out[name]) for name, _, _ in MOMENT_FIELDS))
+    if st != 0:
+        raise VgsError(st, "vgs_tiles_fold_moments")
+    return out
 
 
 # ---- RCCL through ctypes: the three calls a caller needs to hand the driver a communicator ---------------------------------------
@@ -242,6 +273,41 @@ class NativeTiles:
         kept = C.c_int64(0)
         self._ck(self._L.vgs_tiles_get_point_labels(self._h, out.ctypes.data_as(C.c_void_p), C.byref(kept)))
         return out[:self.n], int(kept.value)
+
+    def segment_descriptors(self):
+        """COLLECTIVE (every rank calls it after run()): the descriptors of the global segments over all ranks, row k = the points
+        point_labels() labels k on any rank -- the dict of Engine.segment_descriptors(), the same bytes on every rank
+        (include/vgs_tiles.h, vgs_tiles_get_segment_descriptors).  Cached until the next run() or set_points()."""
+        from .api import Engine
+        K = C.c_int64(0)
+        self._ck(self._L.vgs_tiles_get_segment_descriptors(self._h, C.byref(K), *([None] * len(Engine.DESCRIPTOR_FIELDS))))
+        k = int(K.value)
+        out = {name: np.zeros((k, w) if w > 1 else k, dtype=dt) for name, dt, w in Engine.DESCRIPTOR_FIELDS}
+        if k == 0:
+            return out
+        self._ck(self._L.vgs_tiles_get_segment_descriptors(self._h, C.byref(K), *(_vp(out[name]) for name, _, _ in Engine.DESCRIPTOR_FIELDS)))
+        return out
+
+    def descriptor_times(self):
+        """the last descriptor collective's phases on this rank, milliseconds (D_NAMES)"""
+        t = np.zeros(len(D_NAMES), dtype=np.float64)
+        self._ck(self._L.vgs_tiles_get_descriptor_times(self._h, _vp(t), len(D_NAMES)))
+        return dict(zip(D_NAMES, (float(x) for x in t)))
+
+    def own_segment_moments(self, K):
+        """this rank's moment records of the global labels 0 .. K-1 (vgs_get_own_segment_moments on its context; local, no collective):
+        a dict of MOMENT_FIELDS arrays plus label"""
+        L = _lib.lib()
+        h = self._ctx()
+        K = int(K)
+        out = {"label": np.zeros(max(K, 1), dtype=np.int32)}
+        for name, dt, w in MOMENT_FIELDS:
+            out[name] = np.zeros((max(K, 1), w) if w > 1 else max(K, 1), dtype=dt)
+        n = C.c_int64(0)
+        st = L.vgs_get_own_segment_moments(h, K, C.byref(n), _vp(out["label"]), *(_vp(out[name]) for name, _, _ in MOMENT_FIELDS))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        return {name: a[:n.value] for name, a in out.items()}
 
     def info(self):
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
