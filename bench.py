@@ -5,13 +5,20 @@ Contract: `python bench.py --gpus N --steps K --warmup W`.  A step = one full pa
 -> adjacency -> local cuts -> merge -> per-point labels) over one synthetic scene.
 
 N = 1 workload: BASELINE.json configs[2] "URB10M" (10 M points, voxel 0.1 m, Task_File_VGS defaults) -- the
-configuration the metric is quoted on.  Two timed regions, both K steps after W warm-up steps:
-  * `value` / `ms_per_step`: inputs resident in HBM when the region starts, labels left in HBM (the task contract's
-    definition of `value`);
-  * `host_to_host`: SURVEY.md 8d / BASELINE.md 2 -- float32 xyz in HOST memory in, int32 labels in HOST memory out, H2D and
-    D2H inside the region.  The clouds come as a sequence: cloud k+1's upload and cloud k-1's label download run on copy
-    streams beside cloud k's stages (vgs_stage_points / vgs_commit_points / vgs_get_point_labels_async, include/vgs.h);
-    `latency_ms_median` is one cloud on its own (set_points -> run -> labels, nothing overlapped, median of 5).
+configuration the metric is quoted on.  `value` / `ms_per_step`: K steps after W warm-up steps, inputs resident in HBM when
+the region starts, labels left in HBM (the task contract's definition of `value`).  `stage_ms` and `roofline` come from the
+same timed steps.  A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs), print.
+
+`--full` adds what takes runs of its own (N = 1, plain engine; each `--no-*` option still leaves its part out):
+  * `host_to_host` (--no-host-to-host): SURVEY.md 8d / BASELINE.md 2 -- float32 xyz in HOST memory in, int32 labels in HOST
+    memory out, H2D and D2H inside the region, K steps after max(W, 1) warm-up steps.  The clouds come as a sequence: cloud
+    k+1's upload and cloud k-1's label download run on copy streams beside cloud k's stages (vgs_stage_points /
+    vgs_commit_points / vgs_get_point_labels_async, include/vgs.h); `latency_ms_median` is one cloud on its own
+    (set_points -> run -> labels, nothing overlapped, median of 5); `two_contexts` deals the sequence to two engines;
+  * `clusters_ms` (--no-clusters): getClusterIdx after one more run of the engine; `--clusters-reference` adds the
+    reference's own element order;
+  * `cpu_baseline` (--no-cpu-baseline): the oracle's single-thread port on a 5 % tile of the scene, extrapolated to the scene.
+
 N > 1: weak scaling, every rank owns one 10 M-point tile of the URB80M layout (configs[4]); tiles are segmented on one
 shared grid and boundary segments are merged with one all-gather of boundary records.  The driver is the NATIVE one
 (include/vgs_tiles.h = csrc/tiles.cpp, libvgs_tiles.so, through vgs-svgs-segmentation_amd/tiles_native.py): every rank creates
@@ -274,10 +281,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--points", type=int, default=10_000_000, help="points per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-to-host", action="store_true")
-    ap.add_argument("--no-clusters", action="store_true", help="skip the getClusterIdx timing (extras, outside the metric)")
-    ap.add_argument("--clusters-reference", action="store_true", help="also time getClusterIdx in the reference's own element order")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own beside the headline figure: host-to-host leg, getClusterIdx timing, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-to-host", action="store_true", help="with --full: skip the host-to-host leg")
+    ap.add_argument("--no-clusters", action="store_true", help="with --full: skip the getClusterIdx timing (extras, outside the metric)")
+    ap.add_argument("--clusters-reference", action="store_true", help="with --full: also time getClusterIdx in the reference's own element order")
     ap.add_argument("--dry-run", action="store_true", help="CPU only: exercise the launch path and the collectives (gloo), no engine")
     ap.add_argument("--native", action="store_true", help="tiled runs through libvgs_tiles.so (the default for --gpus > 1; with --gpus 1: a one-rank communicator)")
     ap.add_argument("--python-twin", action="store_true", help="tiled runs through the Python twin of the native driver (dist.py)")
@@ -287,6 +296,8 @@ def main():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and args.dry_run:
         ap.error("--dump-outputs needs the engine: a dry run computes no labels")
+    if args.clusters_reference and not args.full:
+        ap.error("--clusters-reference is part of the getClusterIdx timing: it needs --full")
 
     have_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.gpus > 1 and not have_launcher:
@@ -434,7 +445,7 @@ def main():
 
     # ---- host -> host (single GPU): pinned staging buffers, uploads and downloads beside the stages -----------------
     h2h = None
-    if world == 1 and not native and not args.no_host_to_host:
+    if args.full and world == 1 and not native and not args.no_host_to_host:
         hx = v.pinned_empty(xyz.shape, np.float32)        # the caller's cloud in host memory (a PCD reader's buffer)
         hx[...] = xyz
         hl = [v.pinned_empty((xyz.shape[0],), np.int32) for _ in range(2)]
@@ -558,7 +569,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
-            "value_definition": "inputs resident in HBM, labels left in HBM (task contract); host_to_host is the SURVEY 8d metric",
+            "value_definition": "inputs resident in HBM, labels left in HBM (task contract); host_to_host (--full) is the SURVEY 8d metric",
             "config": {"workload": workload, "points_per_gpu": n_per, "voxels": V, "used_voxels": c["used"], "adjacency_entries": E,
                        "segments": c["kept"], "pair_evaluations": c["pairs"],
                        "parallelism": "single GPU" if world == 1 else f"{world} spatial tiles, shared grid, one all-gather of boundary labels ({'RCCL, native driver' if rccl_comm is not None else backend})"},
@@ -582,7 +593,7 @@ def main():
             out["ranks"] = rccl_ranks if rccl_ranks is not None else world
         elif world > 1:
             out["driver"] = {"kind": "python twin: vgs-svgs-segmentation_amd/dist.py (test harness)"}
-        if world == 1 and not native and not args.no_clusters:
+        if args.full and world == 1 and not native and not args.no_clusters:
             # getClusterIdx, the reference's end product (voxel_segmentation.h:117; test:74-76) -- outside the metric, beside it:
             # the lists made on the device and left in HBM (csrc/clusters.hip), the same copied to host memory (vgs_get_clusters),
             # and, on request, the reference's own element order (host walk over lists the device compacts: csrc/cutorder.hip)
@@ -602,7 +613,7 @@ def main():
             out["host_to_host"] = h2h
         if dumped is not None:
             out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-        if world == 1 and not native and not args.no_cpu_baseline:
+        if args.full and world == 1 and not native and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(xyz, p, runner.adjacency_counts(), runner.point_voxel())
         print(json.dumps(out))
     if tiles_drv is not None:

@@ -67,6 +67,15 @@ def test_bench_refuses_zero_steps_and_a_dry_run_dump(tmp_path):
     assert r.returncode != 0 and "--dump-outputs" in r.stderr
 
 
+def test_bench_clusters_reference_needs_full():
+    """--clusters-reference times part of the getClusterIdx leg, which only --full runs: alone it is refused, not ignored."""
+    r = _run(["--dry-run", "--points", "1000", "--clusters-reference"])
+    assert r.returncode != 0 and "--full" in r.stderr
+    r = _run(["--dry-run", "--points", "1000", "--steps", "1", "--warmup", "0", "--full", "--clusters-reference"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _json_line(r.stdout)["dry_run"] is True
+
+
 def test_dump_outputs_float_files_within_budget(tmp_path):
     """--dump-outputs writes float32 where that is exact (float64 otherwise) and keeps to its byte budget with a seeded sample."""
     import importlib.util

@@ -1,4 +1,4 @@
-"""bench.py end to end on the GPU box at reduced sizes: the single-GPU line with its host-to-host leg, and the N > 1 branch
+"""bench.py end to end on an MI355X at reduced sizes: the plain single-GPU line, the --full one with its host-to-host leg, and the N > 1 branch
 (TiledSegmenter + process group) with two ranks sharing the one GPU over gloo (VGS_BENCH_BACKEND / VGS_BENCH_SINGLE_DEVICE:
 a 1-GPU box cannot run RCCL with two ranks)."""
 import json
@@ -23,7 +23,7 @@ def _run(args, env_extra=None, timeout=600):
 
 
 def test_single_gpu_line(gpu):
-    out = _run(["--points", "400000", "--steps", "3", "--warmup", "1"])
+    out = _run(["--points", "400000", "--steps", "3", "--warmup", "1", "--full"])
     assert out["n_gpus"] == 1 and out["value"] > 0 and out["unit"] == "points/s" and out["dtype"] == "f32"
     assert set(out["roofline"]) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"}
     h = out["host_to_host"]
@@ -32,6 +32,15 @@ def test_single_gpu_line(gpu):
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and cb["cpu_lean"]["value"] >= cb["value"]
     assert cb["cpu_lean_all_cores"]["cores"] >= 1 and cb["cpu_lean_all_cores"]["value"] > 0
     assert out["stage_ms"]["labels"] > 0.0
+    assert out["clusters_ms"]["clusters"] == out["config"]["segments"]
+
+
+def test_plain_line_is_the_headline_alone(gpu):
+    """Without --full the line carries the timed steps' figures and nothing that takes runs of its own."""
+    out = _run(["--points", "400000", "--steps", "3", "--warmup", "1"])
+    assert out["n_gpus"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+    assert out["stage_ms"]["labels"] > 0.0 and out["roofline"]["kernel_ms"] > 0.0
+    assert not {"host_to_host", "clusters_ms", "cpu_baseline"} & set(out)
 
 
 def test_two_ranks_on_one_gpu(gpu):

@@ -25,12 +25,12 @@ PY
 then exit 2; fi
 cd /tmp; export TMPDIR=/tmp
 has() { [[ " $parts " == *" $1 "* ]]; }
-bench="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-to-host"
+bench="python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-host-to-host"   # 7 steps + the clusters leg's run
 
 if has bench; then
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_b -o kt -- $bench > $out/${tag}_bench_stdout.txt 2>&1
   cp /tmp/kt_b/kt_kernel_stats.csv $out/${tag}_bench_kernel_stats.csv
-  python3 $R/bench.py --steps 20 --warmup 3 > $out/${tag}_bench_line.json 2> $out/${tag}_bench_stderr.txt
+  python3 $R/bench.py --steps 20 --warmup 3 --full > $out/${tag}_bench_line.json 2> $out/${tag}_bench_stderr.txt
   # the native tiled driver with the world one GPU can form (multi-GPU pre-flight: what the driver costs beside the plain engine)
   python3 $R/bench.py --gpus 1 --native --steps 10 --warmup 3 --no-cpu-baseline --no-host-to-host > $out/${tag}_bench_native_line.json 2> $out/${tag}_bench_native_stderr.txt
 fi
@@ -45,7 +45,7 @@ if has pmc; then
 fi
 if has timeline; then
   rm -rf /tmp/kt_step
-  timeout 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d /tmp/kt_step -o kt -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-host-to-host > /dev/null 2>&1
+  timeout 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d /tmp/kt_step -o kt -- python3 $R/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-host-to-host > /dev/null 2>&1
   python3 $R/tools/step_timeline.py /tmp/kt_step/kt_kernel_trace.csv > $out/${tag}_step_timeline.txt 2>&1
   python3 - /tmp/kt_step/kt_memory_copy_trace.csv >> $out/${tag}_step_timeline.txt 2>&1 <<'PY'
 import csv, sys, collections

@@ -101,7 +101,7 @@ def bench_block(tag):
         return None
     r = line["roofline"]
     out = [f"#### Config 3 = the bench: URB10M, VGS, voxel 0.1 m (BASELINE configs[2])", ""]
-    out.append(f"`profiles/{tag}_bench_line.json` (`python bench.py --steps 20 --warmup 3`): **{line['ms_per_step']:.3f} ms per step = {line['value'] / 1e9:.3f}·10⁹ points/s** device-resident; "
+    out.append(f"`profiles/{tag}_bench_line.json` (`python bench.py --steps 20 --warmup 3 --full`): **{line['ms_per_step']:.3f} ms per step = {line['value'] / 1e9:.3f}·10⁹ points/s** device-resident; "
                f"host xyz in → host labels out {line['host_to_host']['ms_per_step'] if 'ms_per_step' in line.get('host_to_host', {}) else line['host_to_host'].get('ms_per_cloud', float('nan')):.2f} ms "
                f"({line['host_to_host']['value'] / 1e9:.3f}·10⁹ points/s); CPU baseline (faithful port, 1 core) {line['cpu_baseline']['value']:.0f} points/s.")
     cfgl = line["config"]
