@@ -206,7 +206,8 @@ vgs_status vgs_get_clusters_device(vgs_ctx* ctx, const int64_t** offsets_dev, co
  * whose label (vgs_get_point_labels) is k, K = counts[VGS_N_KEPT] rows; every array is K rows long and any pointer may be NULL:
  *   n_points   int64   points with label k
  *   n_nodes    int32   voxels (VGS) or supervoxels (SVGS) with label k
- *   bbox6      float   min x, y, z, max x, y, z of the points (exact: min / max of the input floats)
+ *   bbox6      float   min x, y, z, max x, y, z of the points (exact: min / max of the input floats; a bound that is zero may carry
+ *                      either sign when the segment holds both +0.0 and -0.0 there; the sign is not specified)
  *   centroid3  double  mean of the points
  *   cov6       double  population covariance (1/n): xx, xy, xz, yy, yz, zz
  *   evals3     double  eigenvalues of cov6, ascending, clamped to >= 0

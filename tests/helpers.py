@@ -100,6 +100,272 @@ def assert_p2(lab_test, lab_ref, point_voxel, used=None, agreement=0.995, iou=0.
     return r
 
 
+# ---------------------------------------------------------------- per-segment descriptors: numpy float64 reference
+SD_CHUNK = 2048   # virtual points per chunk of csrc/segdesc.hip (SD_TB * SD_PPT)
+
+
+def ref_descriptors(xyz, labels, K):
+    """Two-pass mean, centred covariance (1/n), eigh -- float64 over the float32 points labelled 0 .. K-1.  A label that no point carries
+    gets n_points 0, the empty box (+inf, -inf) and NaN moments.  zero_signs (K, 6): the segment holds both +0.0 and -0.0 in that box
+    entry's coordinate, where include/vgs.h lets a zero bound carry either sign."""
+    m = labels >= 0
+    lab = labels[m].astype(np.int64)
+    x32 = xyz[m, :3]
+    x = x32.astype(np.float64)
+    n = np.bincount(lab, minlength=K).astype(np.int64)
+    pairs = [(0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.stack([np.bincount(lab, x[:, a], minlength=K) for a in range(3)], axis=1) / n[:, None]
+        mean = mean + np.stack([np.bincount(lab, x[:, a] - mean[lab, a], minlength=K) for a in range(3)], axis=1) / n[:, None]
+        d = x - mean[lab]
+        cov = np.stack([np.bincount(lab, d[:, i] * d[:, j], minlength=K) for i, j in pairs], axis=1) / n[:, None]
+    order = np.argsort(lab, kind="stable")
+    starts = np.concatenate([[0], np.cumsum(n)[:-1]])
+    xs = x32[order]
+    has = n > 0
+    bbox = np.empty((K, 6), dtype=np.float32)
+    bbox[:, :3], bbox[:, 3:] = np.inf, -np.inf
+    if has.any():   # (reduceat over an empty run would return the next run's first point)
+        bbox[has] = np.concatenate([np.minimum.reduceat(xs, starts[has], axis=0), np.maximum.reduceat(xs, starts[has], axis=0)], axis=1)
+    zero = x32 == 0
+    pos, neg = zero & ~np.signbit(x32), zero & np.signbit(x32)
+    both = np.stack([(np.bincount(lab, pos[:, a], minlength=K) > 0) & (np.bincount(lab, neg[:, a], minlength=K) > 0) for a in range(3)], axis=1)
+    M = np.zeros((K, 3, 3))
+    for c, (i, j) in enumerate(pairs):
+        M[:, i, j] = cov[:, c]
+        M[:, j, i] = cov[:, c]
+    w = np.full((K, 3), np.nan)
+    v = np.full((K, 3, 3), np.nan)
+    if has.any():
+        w[has], v[has] = np.linalg.eigh(M[has])
+    return dict(n_points=n, bbox6=bbox, centroid3=mean, cov6=cov, evals3=w, evecs=v, zero_signs=np.concatenate([both, both], axis=1))
+
+
+def ref_features(ev, svgs):
+    """vm_eigen_features (csrc/vgs_math.h) in float32 numpy, from ascending eigenvalues."""
+    ev = ev.astype(np.float32)
+    F = np.zeros((ev.shape[0], 8), dtype=np.float32)
+    with np.errstate(all="ignore"):
+        s = np.sqrt(ev[:, 0] * ev[:, 0] + ev[:, 1] * ev[:, 1] + ev[:, 2] * ev[:, 2])
+        e3, e2, e1 = ev[:, 0] / s, ev[:, 1] / s, ev[:, 2] / s
+        sm = e1 + e2 + e3
+        cur = e3 / sm
+        z1 = e1 == 0
+        lin = np.where(z1, np.float32(0), (e1 - e2) / e1)
+        pla = np.where(z1, np.float32(1), (e2 - e3) / e1)
+        sca = np.where(z1, np.float32(0), e3 / e1)
+        ani = np.where((z1 if svgs else e2 == 0), np.float32(0), (e1 - e3) / e1)
+        prod = e1 * e2 * e3
+        ent = np.where(prod == 0, np.float32(0), -1.0 * (e1 * np.log(e1) + e2 * np.log(e2) + e3 * np.log(e3)))
+        omn = np.where(prod == 0, np.float32(0), np.exp(np.log(prod) * np.float32(0.33333334)))
+    cols = [lin, pla, sca, ani, cur] if svgs else [lin, pla, sca, cur, ani]
+    F[:] = np.stack(cols + [ent, sm, omn], axis=1).astype(np.float32)
+    F[(ev == 0).all(axis=1)] = 0
+    return F
+
+
+def same_box(got, ref, zero_signs):
+    """Box entries equal bit for bit, except a zero bound in a coordinate where the segment holds both +0.0 and -0.0 (zero_signs of
+    ref_descriptors): include/vgs.h lets it carry either sign, so it compares by value."""
+    got, ref = np.asarray(got, np.float32), np.asarray(ref, np.float32)
+    if got.shape != ref.shape:
+        return False
+    return bool(((got.view(np.uint32) == ref.view(np.uint32)) | (zero_signs & (got == 0) & (ref == 0))).all())
+
+
+def check_descriptors(eng, xyz, svgs):
+    K = eng.counts()["kept"]
+    got = eng.segment_descriptors()
+    labels = eng.point_labels()
+    assert K > 0 and labels.max() == K - 1
+    ref = ref_descriptors(xyz, labels, K)
+    assert np.array_equal(got["n_points"], ref["n_points"])
+    _, kept = eng.node_labels()
+    assert np.array_equal(got["n_nodes"], np.bincount(kept[kept >= 0], minlength=K).astype(np.int32))
+    assert same_box(got["bbox6"], ref["bbox6"], ref["zero_signs"])
+    c = got["centroid3"]
+    assert (np.abs(c - ref["centroid3"]) <= 1e-9 * (1 + np.linalg.norm(ref["centroid3"], axis=1))[:, None]).all()
+    tr = ref["cov6"][:, [0, 3, 5]].sum(axis=1)
+    assert (np.abs(got["cov6"] - ref["cov6"]) <= 1e-8 * tr[:, None] + 1e-30).all()
+    lmax = ref["evals3"][:, 2]
+    assert (got["evals3"] >= 0).all() and (np.diff(got["evals3"], axis=1) >= 0).all()
+    assert (np.abs(got["evals3"] - np.maximum(ref["evals3"], 0)) <= 1e-8 * lmax[:, None] + 1e-30).all()
+    V = got["evecs9"].reshape(K, 3, 3)   # [k, r, j] = component r of eigenvector j
+    assert np.allclose(np.einsum("kri,krj->kij", V, V), np.eye(3)[None], atol=1e-10)
+    for j in range(3):
+        col = V[:, :, j]
+        big = col[np.arange(K), np.argmax(np.abs(col), axis=1)]   # argmax: the lowest index on a tie
+        assert (big > 0).all(), j
+        w = ref["evals3"]
+        gap = np.minimum(np.abs(w[:, j] - w[:, j - 1]) if j > 0 else np.inf, np.abs(w[:, j + 1] - w[:, j]) if j < 2 else np.inf)
+        sel = gap >= 1e-3 * lmax
+        dots = np.abs((col * ref["evecs"][:, :, j]).sum(axis=1))
+        assert (dots[sel] >= 1 - 1e-6).all(), (j, dots[sel].min())
+    one = got["n_points"] == 1
+    assert (got["cov6"][one] == 0).all() and (got["eigen8"][one] == 0).all()
+    assert (V[one] == np.eye(3)[None]).all()
+    np.testing.assert_allclose(got["eigen8"], ref_features(got["evals3"], svgs), rtol=1e-5, atol=1e-6)
+    return got
+
+
+# ---------------------------------------------------------------- segment adjacency graph: numpy ground truth
+def graph_truth(lab, off, idx, K, weight=None, sample=None, seed=0):
+    """The segment graph by its definition (include/vgs.h), independent of any engine.  lab: effective label of every node (-1: takes no
+    part); (off, idx): the stored adjacency rows as CSR; K: kept segments; weight(u, v) -> float32 w(u, v) for arrays of node ids u < v
+    (None: counts only).  sample: weights of that many seeded edges, or of the given edge rows (returned as 'wsel'); None: of every edge.
+    Also returned: 'key' (the sort key min(a, b) * K + max(a, b) of every edge) and 'row_labels' (distinct boundary labels per row)."""
+    lab = np.asarray(lab).astype(np.int64)
+    off = np.asarray(off).astype(np.int64)
+    V = lab.shape[0]
+    assert lab.max(initial=-1) < K
+    u = np.repeat(np.arange(V, dtype=np.int64), np.diff(off))
+    v = np.asarray(idx).astype(np.int64)
+    m = (lab[u] >= 0) & (lab[v] >= 0) & (lab[u] != lab[v])
+    u, v = u[m], v[m]
+    # the predicate is symmetric: every directed pair appears both ways
+    assert np.array_equal(np.unique(u * V + v), np.unique(v * V + u))
+    la, lb = lab[u], lab[v]
+    key = np.minimum(la, lb) * K + np.maximum(la, lb)
+    keys = np.unique(key)
+    E = keys.shape[0]
+    eid = np.searchsorted(keys, key)
+    lt = u < v
+    Kd = max(int(K), 1)
+    out = dict(seg_ab=np.stack([keys // Kd, keys % Kd], axis=1).astype(np.int32).reshape(E, 2),
+               n_pairs=np.bincount(eid[lt], minlength=E).astype(np.int64))
+    nk = np.unique(u * K + lb)
+    nu, nb = nk // Kd, nk % Kd
+    na_ = lab[nu]
+    e2 = np.searchsorted(keys, np.minimum(na_, nb) * K + np.maximum(na_, nb))
+    side_a = na_ < nb
+    out["nodes_ab"] = np.stack([np.bincount(e2[side_a], minlength=E), np.bincount(e2[~side_a], minlength=E)], axis=1).astype(np.int32).reshape(E, 2)
+    out["key"] = keys
+    out["row_labels"] = np.bincount(nu, minlength=V)
+    if weight is None:
+        return out
+    if sample is None:
+        wsel = np.arange(E)
+    elif np.ndim(sample) == 0:
+        wsel = np.arange(E) if sample >= E else np.sort(np.random.default_rng(seed).choice(E, size=int(sample), replace=False))
+    else:
+        wsel = np.unique(np.asarray(sample, dtype=np.int64))
+    take = lt & np.isin(eid, wsel)
+    w = np.asarray(weight(u[take], v[take]), dtype=np.float32)
+    ei = eid[take]
+    fin = ~np.isnan(w)
+    out["n_finite"] = np.bincount(ei[fin], minlength=E).astype(np.int64)
+    out["w_sum"] = np.bincount(ei[fin], weights=w[fin].astype(np.float64), minlength=E)
+    mn = np.full(E, np.inf, dtype=np.float32)
+    mx = np.full(E, -np.inf, dtype=np.float32)
+    np.minimum.at(mn, ei[fin], w[fin])
+    np.maximum.at(mx, ei[fin], w[fin])
+    none = out["n_finite"] == 0
+    mn[none] = np.nan
+    mx[none] = np.nan
+    out["w_min"], out["w_max"] = mn, mx
+    out["wsel"] = wsel
+    return out
+
+
+def graph_inputs(eng):
+    """(effective labels, row offsets, row ids, K) of an engine: a used node keeps its kept label, every other node gets -1."""
+    off, idx = eng.lists("adjacency")
+    _, kept = eng.node_labels()
+    used = eng.attributes()["used"].astype(bool)
+    return np.where(used, kept, -1).astype(np.int64), off, idx, eng.counts()["kept"]
+
+
+def pair_weights(eng, u, v):
+    """w(u, v) for u < v from Engine.local_weights(u): the entry of the ordered pair (u first) of u's own local graph."""
+    w = np.empty(u.shape[0], dtype=np.float32)
+    order = np.argsort(u, kind="stable")
+    us, starts = np.unique(u[order], return_index=True)
+    ends = np.append(starts[1:], order.shape[0])
+    for node, s, e in zip(us.tolist(), starts.tolist(), ends.tolist()):
+        ids, W = eng.local_weights(node)
+        srt = np.argsort(ids)
+        sel = order[s:e]
+        pv = srt[np.searchsorted(ids[srt], v[sel])]
+        assert np.array_equal(ids[pv], v[sel])
+        pu = int(np.nonzero(ids == node)[0][0])
+        w[sel] = W[pu, pv]
+    return w
+
+
+def ref_graph(eng, sample=None, seed=0):
+    """The table by definition (graph_truth) over the engine's own rows, node labels and local-cut weights."""
+    lab, off, idx, K = graph_inputs(eng)
+    return graph_truth(lab, off, idx, K, lambda a, b: pair_weights(eng, a, b), sample=sample, seed=seed)
+
+
+def check_graph(eng, sample=None, ref=None):
+    got = eng.segment_graph()
+    if ref is None:
+        ref = ref_graph(eng, sample=sample)
+    E = ref["seg_ab"].shape[0]
+    assert got["seg_ab"].shape == (E, 2)
+    for k in ("seg_ab", "n_pairs", "nodes_ab"):
+        assert np.array_equal(got[k], ref[k]), k
+    s = ref["wsel"]
+    assert np.array_equal(got["n_finite"][s], ref["n_finite"][s])
+    assert np.array_equal(got["w_min"][s].view(np.uint32), ref["w_min"][s].view(np.uint32))
+    assert np.array_equal(got["w_max"][s].view(np.uint32), ref["w_max"][s].view(np.uint32))
+    rs, gs = ref["w_sum"][s], got["w_sum"][s]
+    assert (np.abs(gs - rs) <= 1e-10 * np.abs(rs) + 1e-300).all()
+    # invariants of the definition
+    a, b = got["seg_ab"][:, 0], got["seg_ab"][:, 1]
+    assert (a < b).all() and (a >= 0).all() and (b < eng.counts()["kept"]).all()
+    assert (np.diff(a.astype(np.int64) * (1 << 32) + b) > 0).all()   # ascending (a, b), each edge once
+    na, nb = got["nodes_ab"][:, 0].astype(np.int64), got["nodes_ab"][:, 1].astype(np.int64)
+    assert (np.maximum(na, nb) <= got["n_pairs"]).all() and (got["n_pairs"] <= na * nb).all()
+    assert (got["n_finite"] <= got["n_pairs"]).all()
+    return got
+
+
+# ---------------------------------------------------------------- which structural limits of the two tables a scene reaches
+def segment_limits(K, point_labels, node_label=None, node_points=None, truth=None, graph=None):
+    """The limits of csrc/segdesc.hip and csrc/seggraph.hip that a scene reaches, from numpy alone:
+      K; seg_points and seg_mod (every segment's points, and those modulo SD_CHUNK);
+      with node_label / node_points (kept label and points of every node; a segment's nodes in ascending id, the descriptor's order):
+      max_node_points, first_node_chunks (most chunks a segment's first node covers), nodes_on_chunk_start (nodes other than a segment's
+      first whose first point starts a chunk);
+      with truth (graph_truth's dict): max_key (the largest sort key min(a, b) * K + max(a, b)), max_row_labels (most distinct boundary
+      labels in one row), max_edge_records (most records of one edge = nodes_ab[0] + nodes_ab[1]);
+      with graph (a table with n_pairs / n_finite): nan_edges (0 < n_finite < n_pairs) and no_finite_edges (n_finite == 0)."""
+    pl = np.asarray(point_labels)
+    seg = np.bincount(pl[pl >= 0], minlength=K).astype(np.int64)
+    out = dict(K=int(K), seg_points=seg, seg_mod=seg % SD_CHUNK)
+    if node_label is not None:
+        nl = np.asarray(node_label).astype(np.int64)
+        npt = np.asarray(node_points).astype(np.int64)
+        sel = np.nonzero(nl >= 0)[0]
+        order = sel[np.argsort(nl[sel], kind="stable")]   # segments in label order, each one's nodes ascending
+        lab_s, pts_s = nl[order], npt[order]
+        first = np.ones(order.shape[0], dtype=bool)
+        first[1:] = lab_s[1:] != lab_s[:-1]
+        vp = np.concatenate([[0], np.cumsum(pts_s)[:-1]]).astype(np.int64)
+        at = vp - np.maximum.accumulate(np.where(first, vp, 0))   # the node's first point inside its segment
+        out["max_node_points"] = int(pts_s.max(initial=0))
+        out["first_node_chunks"] = int(((pts_s[first] + SD_CHUNK - 1) // SD_CHUNK).max(initial=0))
+        out["nodes_on_chunk_start"] = int((~first & (at % SD_CHUNK == 0)).sum())
+    if truth is not None:
+        out["max_key"] = int(truth["key"].max(initial=0))
+        out["max_row_labels"] = int(truth["row_labels"].max(initial=0))
+        out["max_edge_records"] = int(truth["nodes_ab"].astype(np.int64).sum(axis=1).max(initial=0))
+    if graph is not None:
+        out["nan_edges"] = int(((graph["n_finite"] > 0) & (graph["n_finite"] < graph["n_pairs"])).sum())
+        out["no_finite_edges"] = int((graph["n_finite"] == 0).sum())
+    return out
+
+
+def engine_limits(eng, truth=None, graph=None):
+    """segment_limits of an engine's segmentation (nodes: its voxels or supervoxels, their points from the point-to-node map)."""
+    _, kept = eng.node_labels()
+    pv = eng.point_voxel()
+    npts = np.bincount(pv[pv >= 0], minlength=kept.shape[0])
+    return segment_limits(eng.counts()["kept"], eng.point_labels(), kept, npts, truth=truth, graph=graph)
+
+
 def canonical_labels(lab):
     """Relabel so that equal partitions give equal arrays: label = smallest member index of the class."""
     lab = np.asarray(lab)

@@ -7,90 +7,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers import check_descriptors
+
 pytestmark = pytest.mark.gpu
-
-
-# ---------------------------------------------------------------- numpy reference
-def ref_descriptors(xyz, labels, K):
-    """Two-pass mean, centred covariance (1/n), eigh -- float64 over the float32 points labelled 0 .. K-1."""
-    m = labels >= 0
-    lab = labels[m].astype(np.int64)
-    x32 = xyz[m, :3]
-    x = x32.astype(np.float64)
-    n = np.bincount(lab, minlength=K).astype(np.int64)
-    mean = np.stack([np.bincount(lab, x[:, a], minlength=K) for a in range(3)], axis=1) / n[:, None]
-    mean = mean + np.stack([np.bincount(lab, x[:, a] - mean[lab, a], minlength=K) for a in range(3)], axis=1) / n[:, None]
-    d = x - mean[lab]
-    pairs = [(0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)]
-    cov = np.stack([np.bincount(lab, d[:, i] * d[:, j], minlength=K) for i, j in pairs], axis=1) / n[:, None]
-    order = np.argsort(lab, kind="stable")
-    starts = np.concatenate([[0], np.cumsum(n)[:-1]])
-    xs = x32[order]
-    bbox = np.concatenate([np.minimum.reduceat(xs, starts, axis=0), np.maximum.reduceat(xs, starts, axis=0)], axis=1)
-    M = np.empty((K, 3, 3))
-    for c, (i, j) in enumerate(pairs):
-        M[:, i, j] = cov[:, c]
-        M[:, j, i] = cov[:, c]
-    w, v = np.linalg.eigh(M)
-    return dict(n_points=n, bbox6=bbox.astype(np.float32), centroid3=mean, cov6=cov, evals3=w, evecs=v)
-
-
-def ref_features(ev, svgs):
-    """vm_eigen_features (csrc/vgs_math.h) in float32 numpy, from ascending eigenvalues."""
-    ev = ev.astype(np.float32)
-    F = np.zeros((ev.shape[0], 8), dtype=np.float32)
-    with np.errstate(all="ignore"):
-        s = np.sqrt(ev[:, 0] * ev[:, 0] + ev[:, 1] * ev[:, 1] + ev[:, 2] * ev[:, 2])
-        e3, e2, e1 = ev[:, 0] / s, ev[:, 1] / s, ev[:, 2] / s
-        sm = e1 + e2 + e3
-        cur = e3 / sm
-        z1 = e1 == 0
-        lin = np.where(z1, np.float32(0), (e1 - e2) / e1)
-        pla = np.where(z1, np.float32(1), (e2 - e3) / e1)
-        sca = np.where(z1, np.float32(0), e3 / e1)
-        ani = np.where((z1 if svgs else e2 == 0), np.float32(0), (e1 - e3) / e1)
-        prod = e1 * e2 * e3
-        ent = np.where(prod == 0, np.float32(0), -1.0 * (e1 * np.log(e1) + e2 * np.log(e2) + e3 * np.log(e3)))
-        omn = np.where(prod == 0, np.float32(0), np.exp(np.log(prod) * np.float32(0.33333334)))
-    cols = [lin, pla, sca, ani, cur] if svgs else [lin, pla, sca, cur, ani]
-    F[:] = np.stack(cols + [ent, sm, omn], axis=1).astype(np.float32)
-    F[(ev == 0).all(axis=1)] = 0
-    return F
-
-
-def check_descriptors(eng, xyz, svgs):
-    K = eng.counts()["kept"]
-    got = eng.segment_descriptors()
-    labels = eng.point_labels()
-    assert K > 0 and labels.max() == K - 1
-    ref = ref_descriptors(xyz, labels, K)
-    assert np.array_equal(got["n_points"], ref["n_points"])
-    _, kept = eng.node_labels()
-    assert np.array_equal(got["n_nodes"], np.bincount(kept[kept >= 0], minlength=K).astype(np.int32))
-    assert np.array_equal(got["bbox6"].view(np.uint32), ref["bbox6"].view(np.uint32))
-    c = got["centroid3"]
-    assert (np.abs(c - ref["centroid3"]) <= 1e-9 * (1 + np.linalg.norm(ref["centroid3"], axis=1))[:, None]).all()
-    tr = ref["cov6"][:, [0, 3, 5]].sum(axis=1)
-    assert (np.abs(got["cov6"] - ref["cov6"]) <= 1e-8 * tr[:, None] + 1e-30).all()
-    lmax = ref["evals3"][:, 2]
-    assert (got["evals3"] >= 0).all() and (np.diff(got["evals3"], axis=1) >= 0).all()
-    assert (np.abs(got["evals3"] - np.maximum(ref["evals3"], 0)) <= 1e-8 * lmax[:, None] + 1e-30).all()
-    V = got["evecs9"].reshape(K, 3, 3)   # [k, r, j] = component r of eigenvector j
-    assert np.allclose(np.einsum("kri,krj->kij", V, V), np.eye(3)[None], atol=1e-10)
-    for j in range(3):
-        col = V[:, :, j]
-        big = col[np.arange(K), np.argmax(np.abs(col), axis=1)]   # argmax: the lowest index on a tie
-        assert (big > 0).all(), j
-        w = ref["evals3"]
-        gap = np.minimum(np.abs(w[:, j] - w[:, j - 1]) if j > 0 else np.inf, np.abs(w[:, j + 1] - w[:, j]) if j < 2 else np.inf)
-        sel = gap >= 1e-3 * lmax
-        dots = np.abs((col * ref["evecs"][:, :, j]).sum(axis=1))
-        assert (dots[sel] >= 1 - 1e-6).all(), (j, dots[sel].min())
-    one = got["n_points"] == 1
-    assert (got["cov6"][one] == 0).all() and (got["eigen8"][one] == 0).all()
-    assert (V[one] == np.eye(3)[None]).all()
-    np.testing.assert_allclose(got["eigen8"], ref_features(got["evals3"], svgs), rtol=1e-5, atol=1e-6)
-    return got
 
 
 def _vgs(gpu, xyz, **kw):

@@ -8,105 +8,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import oracle_params, ragged_sets
+from helpers import check_graph, oracle_params, ragged_sets
 
 pytestmark = pytest.mark.gpu
 
 FIELDS = ("seg_ab", "n_pairs", "n_finite", "nodes_ab", "w_sum", "w_min", "w_max")
-
-
-# ---------------------------------------------------------------- numpy ground truth
-def node_pairs(eng):
-    """Directed boundary pairs (u, v) of the stored rows between used nodes of different kept labels, the effective labels and K."""
-    off, idx = eng.lists("adjacency")
-    _, kept = eng.node_labels()
-    used = eng.attributes()["used"].astype(bool)
-    lab = np.where(used, kept, -1).astype(np.int64)
-    V = lab.shape[0]
-    u = np.repeat(np.arange(V, dtype=np.int64), np.diff(off))
-    v = idx.astype(np.int64)
-    m = (lab[u] >= 0) & (lab[v] >= 0) & (lab[u] != lab[v])
-    u, v = u[m], v[m]
-    # the predicate is symmetric: every directed pair appears both ways
-    assert np.array_equal(np.unique(u * V + v), np.unique(v * V + u))
-    return u, v, lab, eng.counts()["kept"], off, idx
-
-
-def pair_weights(eng, u, v):
-    """w(u, v) for u < v from Engine.local_weights(u): the entry of the ordered pair (u first) of u's own local graph."""
-    w = np.empty(u.shape[0], dtype=np.float32)
-    order = np.argsort(u, kind="stable")
-    us, starts = np.unique(u[order], return_index=True)
-    ends = np.append(starts[1:], order.shape[0])
-    for node, s, e in zip(us.tolist(), starts.tolist(), ends.tolist()):
-        ids, W = eng.local_weights(node)
-        srt = np.argsort(ids)
-        sel = order[s:e]
-        pv = srt[np.searchsorted(ids[srt], v[sel])]
-        assert np.array_equal(ids[pv], v[sel])
-        pu = int(np.nonzero(ids == node)[0][0])
-        w[sel] = W[pu, pv]
-    return w
-
-
-def ref_graph(eng, sample=None, seed=0):
-    """The table by definition.  sample: weights only for that many seeded edges (their rows are returned as 'wsel')."""
-    u, v, lab, K, _, _ = node_pairs(eng)
-    la, lb = lab[u], lab[v]
-    key = np.minimum(la, lb) * K + np.maximum(la, lb)
-    keys = np.unique(key)
-    E = keys.shape[0]
-    eid = np.searchsorted(keys, key)
-    lt = u < v
-    out = dict(seg_ab=np.stack([keys // K, keys % K], axis=1).astype(np.int32), n_pairs=np.bincount(eid[lt], minlength=E).astype(np.int64))
-    nk = np.unique(u * K + lb)
-    nu, nb = nk // K, nk % K
-    na_ = lab[nu]
-    e2 = np.searchsorted(keys, np.minimum(na_, nb) * K + np.maximum(na_, nb))
-    side_a = na_ < nb
-    out["nodes_ab"] = np.stack([np.bincount(e2[side_a], minlength=E), np.bincount(e2[~side_a], minlength=E)], axis=1).astype(np.int32)
-    wsel = np.arange(E)
-    if sample is not None and sample < E:
-        wsel = np.sort(np.random.default_rng(seed).choice(E, size=sample, replace=False))
-    take = lt & np.isin(eid, wsel)
-    w = pair_weights(eng, u[take], v[take])
-    ei = eid[take]
-    fin = ~np.isnan(w)
-    out["n_finite"] = np.bincount(ei[fin], minlength=E).astype(np.int64)
-    out["w_sum"] = np.bincount(ei[fin], weights=w[fin].astype(np.float64), minlength=E)
-    mn = np.full(E, np.inf, dtype=np.float32)
-    mx = np.full(E, -np.inf, dtype=np.float32)
-    np.minimum.at(mn, ei[fin], w[fin])
-    np.maximum.at(mx, ei[fin], w[fin])
-    none = out["n_finite"] == 0
-    mn[none] = np.nan
-    mx[none] = np.nan
-    out["w_min"], out["w_max"] = mn, mx
-    out["wsel"] = wsel
-    return out
-
-
-def check_graph(eng, sample=None):
-    got = eng.segment_graph()
-    ref = ref_graph(eng, sample=sample)
-    E = ref["seg_ab"].shape[0]
-    assert got["seg_ab"].shape == (E, 2)
-    for k in ("seg_ab", "n_pairs", "nodes_ab"):
-        assert np.array_equal(got[k], ref[k]), k
-    s = ref["wsel"]
-    assert np.array_equal(got["n_finite"][s], ref["n_finite"][s])
-    assert np.array_equal(got["w_min"][s].view(np.uint32), ref["w_min"][s].view(np.uint32))
-    assert np.array_equal(got["w_max"][s].view(np.uint32), ref["w_max"][s].view(np.uint32))
-    rs, gs = ref["w_sum"][s], got["w_sum"][s]
-    assert (np.abs(gs - rs) <= 1e-10 * np.abs(rs) + 1e-300).all()
-    # invariants of the definition
-    a, b = got["seg_ab"][:, 0], got["seg_ab"][:, 1]
-    assert (a < b).all() and (a >= 0).all() and (b < eng.counts()["kept"]).all()
-    assert (np.diff(a.astype(np.int64) * (1 << 32) + b) > 0).all()   # ascending (a, b), each edge once
-    na, nb = got["nodes_ab"][:, 0].astype(np.int64), got["nodes_ab"][:, 1].astype(np.int64)
-    assert (np.maximum(na, nb) <= got["n_pairs"]).all() and (got["n_pairs"] <= na * nb).all()
-    assert (got["n_finite"] <= got["n_pairs"]).all()
-    return got
 
 
 def check_boxes(eng, got):

@@ -15,7 +15,7 @@ import threading
 import numpy as np
 import pytest
 
-from test_gpu_segment_desc import ref_descriptors, ref_features
+from helpers import ref_descriptors, ref_features
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,7 +36,7 @@ def _parts(gpu, tiles, n_per=N_PER, shift=None):
     return parts
 
 
-def _ranks(gpu, tiles, pitch, parts, body, center=(0.0, 0.0), timeout=300.0):
+def _ranks(gpu, tiles, pitch, parts, body, center=(0.0, 0.0), timeout=300.0, params=None):
     """one rank of the native driver per tile, threads of this process; body(rank, driver, points) -> anything.  Exceptions come back as
     results; a rank still inside the driver after `timeout` fails the test."""
     from vgs_svgs_segmentation_amd import tiles_native as tn
@@ -46,7 +46,8 @@ def _ranks(gpu, tiles, pitch, parts, body, center=(0.0, 0.0), timeout=300.0):
 
     def rank_main(r):
         try:
-            t = tn.NativeTiles(gpu.default_params(2, voxel_size=0.1), tn.COMM_LOCAL, grp.handle, r, world, tiles, pitch, center=center)
+            p = params if params is not None else gpu.default_params(2, voxel_size=0.1)
+            t = tn.NativeTiles(p, tn.COMM_LOCAL, grp.handle, r, world, tiles, pitch, center=center)
             try:
                 out[r] = body(r, t, parts[r])
             finally:
@@ -95,7 +96,7 @@ def _collect(r, t, xyz):
                 times=t.descriptor_times())
 
 
-def _check_against_points(gpu, parts, out):
+def _check_against_points(gpu, parts, out, params=None):
     world = len(parts)
     for r, o in enumerate(out):
         assert not isinstance(o, Exception), (r, o)
@@ -130,7 +131,7 @@ def _check_against_points(gpu, parts, out):
     assert (d["cov6"][one] == 0).all() and (V[one] == np.eye(3)[None]).all()
     np.testing.assert_allclose(d["eigen8"], ref_features(d["evals3"], False), rtol=1e-5, atol=1e-6)
     # n_nodes: the distinct voxels of the shared grid among each segment's points -- the grid of one engine over the union, rank order
-    eng = gpu.Engine(gpu.default_params(2, voxel_size=0.1))
+    eng = gpu.Engine(params if params is not None else gpu.default_params(2, voxel_size=0.1))
     eng.set_points(xyz)
     eng.run()
     pv = eng.point_voxel()
