@@ -1,9 +1,12 @@
 // examples/segments_csv.hpp -- the --segments CSV of the front ends (vgs_run, vgs_tiles_run): one row per kept cluster, row i = cluster
 // i (label i): label, n_points, n_nodes, bbox (6), centroid (3), eigenvalues (3, ascending), normal (3), major axis (3), the eight eigen
 // features -- doubles as %.17g, floats as %.9g, so every value reads back exactly.  One writer, so the two front ends cannot drift apart.
+// The --segment-graph CSV of the same front ends: one row per edge, ascending (a, b): a, b, n_pairs, n_finite, nodes_a, nodes_b, w_mean
+// (w_sum / n_finite, NaN without a finite weight), w_min, w_max.
 #ifndef VGS_EXAMPLES_SEGMENTS_CSV_HPP_
 #define VGS_EXAMPLES_SEGMENTS_CSV_HPP_
 
+#include <cmath>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -25,6 +28,18 @@ inline int writeSegmentsCsv(const std::string& path, const std::vector<pcl::Clus
     for (int r = 0; r < 3; ++r) std::fprintf(f, ",%.17g", d.evecs[3 * r + 2]);   // major axis: eigenvector of the largest
     for (int a = 0; a < 8; ++a) std::fprintf(f, ",%.9g", (double)d.eigen8[a]);
     std::fprintf(f, "\n");
+  }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
+inline int writeGraphCsv(const std::string& path, const std::vector<pcl::ClusterEdge>& g) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "a,b,n_pairs,n_finite,nodes_a,nodes_b,w_mean,w_min,w_max\n");
+  for (const pcl::ClusterEdge& e : g) {
+    const double mean = e.n_finite > 0 ? e.w_sum / (double)e.n_finite : std::nan("");
+    std::fprintf(f, "%d,%d,%lld,%lld,%d,%d,%.17g,%.9g,%.9g\n", (int)e.a, (int)e.b, (long long)e.n_pairs, (long long)e.n_finite, (int)e.nodes_a,
+                 (int)e.nodes_b, mean, (double)e.w_min, (double)e.w_max);
   }
   return std::fclose(f) == 0 ? 0 : -1;
 }

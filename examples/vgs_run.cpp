@@ -25,18 +25,6 @@
 #include "point_clouds_io.hpp"
 #include "segments_csv.hpp"
 
-static int writeGraphCsv(const std::string& path, const std::vector<pcl::ClusterEdge>& g) {
-  FILE* f = std::fopen(path.c_str(), "w");
-  if (!f) return -1;
-  std::fprintf(f, "a,b,n_pairs,n_finite,nodes_a,nodes_b,w_mean,w_min,w_max\n");
-  for (const pcl::ClusterEdge& e : g) {
-    const double mean = e.n_finite > 0 ? e.w_sum / (double)e.n_finite : std::nan("");
-    std::fprintf(f, "%d,%d,%lld,%lld,%d,%d,%.17g,%.9g,%.9g\n", (int)e.a, (int)e.b, (long long)e.n_pairs, (long long)e.n_finite, (int)e.nodes_a,
-                 (int)e.nodes_b, mean, (double)e.w_min, (double)e.w_max);
-  }
-  return std::fclose(f) == 0 ? 0 : -1;
-}
-
 static int writeAdjacency(const std::string& path, const std::multimap<uint32_t, uint32_t>& adj) {
   FILE* f = std::fopen(path.c_str(), "w");
   if (!f) return -1;

@@ -10,6 +10,8 @@
 //   <prefix>.<r>.labels.i32.  Prints "<world> <kept segments> <points of rank 0> <boundary records of rank 0>".
 //   --segments <file.csv>: every rank takes part in vgs_tiles_get_segment_descriptors (a collective) and rank 0 writes the table of the
 //   global segments in the CSV format of vgs_run --segments (examples/segments_csv.hpp).
+//   --segment-graph <file.csv>: every rank takes part in vgs_tiles_get_segment_graph (a collective) and rank 0 writes the adjacency graph
+//   of the global segments in the CSV format of vgs_run --segment-graph.  The two can be combined.
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <sys/socket.h>
@@ -48,7 +50,7 @@ static bool write_i32(const std::string& path, const std::vector<int32_t>& v) {
   return put == v.size();
 }
 
-struct Job { vgs_params p; int tx, ty; double pitch; std::string prefix, segments; };
+struct Job { vgs_params p; int tx, ty; double pitch; std::string prefix, segments, graph; };
 
 // one rank: load, run, save; returns 0 on success
 static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world, int64_t* kept, int64_t* n_pts, int64_t* n_rec, std::string* err) {
@@ -88,6 +90,28 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
       }
       if (writeSegmentsCsv(J.segments, desc) != 0) { *err = "cannot write " + J.segments; rc = 1; }
     }
+  }
+  if (rc == 0 && !J.graph.empty()) {
+    // the adjacency graph of the global segments: the first call is a collective of every rank and leaves the table cached
+    int64_t E = 0;
+    std::vector<pcl::ClusterEdge> edges;
+    vgs_status sg = vgs_tiles_get_segment_graph(t, &E, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (sg == VGS_OK && rank == 0 && E > 0) {
+      const size_t e1 = (size_t)E;
+      std::vector<int32_t> ab(2 * e1), nd(2 * e1);
+      std::vector<int64_t> np(e1), nf(e1);
+      std::vector<double> ws(e1);
+      std::vector<float> mn(e1), mx(e1);
+      sg = vgs_tiles_get_segment_graph(t, &E, ab.data(), np.data(), nf.data(), nd.data(), ws.data(), mn.data(), mx.data());
+      edges.resize(e1);
+      for (size_t i = 0; i < e1; ++i) {
+        pcl::ClusterEdge& e = edges[i];
+        e.a = ab[2 * i]; e.b = ab[2 * i + 1]; e.n_pairs = np[i]; e.n_finite = nf[i]; e.nodes_a = nd[2 * i]; e.nodes_b = nd[2 * i + 1];
+        e.w_sum = ws[i]; e.w_min = mn[i]; e.w_max = mx[i];
+      }
+    }
+    if (sg != VGS_OK) { *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t); rc = 1; }
+    else if (rank == 0 && writeGraphCsv(J.graph, edges) != 0) { *err = "cannot write " + J.graph; rc = 1; }
   }
   if (rc == 0) {
     labels.resize((size_t)n);
@@ -150,10 +174,11 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--voxel") && a + 1 < argc) J.p.voxel_size = (float)std::atof(argv[++a]);
     else if (!std::strcmp(argv[a], "--graph") && a + 1 < argc) J.p.graph_size = (float)std::atof(argv[++a]);
     else if (!std::strcmp(argv[a], "--segments") && a + 1 < argc) J.segments = argv[++a];
+    else if (!std::strcmp(argv[a], "--segment-graph") && a + 1 < argc) J.graph = argv[++a];
     else if (argv[a][0] != '-') J.prefix = argv[a];
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
-  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] <prefix>\n", argv[0]); return 2; }
+  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] <prefix>\n", argv[0]); return 2; }
   const int world = J.tx * J.ty;
   int64_t kept = 0, n_pts = 0, n_rec = 0;
   if (mode == 1) {

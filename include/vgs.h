@@ -269,6 +269,26 @@ vgs_status vgs_get_segment_graph(vgs_ctx* ctx, int64_t* n_edges, int32_t* seg_ab
 /* the same table left in HBM: device pointers (any may be NULL), valid until the next run of the stages */
 vgs_status vgs_get_segment_graph_device(vgs_ctx* ctx, int64_t* n_edges, const int32_t** seg_ab, const int64_t** n_pairs, const int64_t** n_finite,
                                         const int32_t** nodes_ab, const double** w_sum, const float** w_min, const float** w_max);
+/* The segment graph of a tile context (the tiled driver, include/vgs_tiles.h: vgs_tiles_get_segment_graph folds the ranks' tables).
+ * After vgs_apply_tile_labels an owned voxel holds its GLOBAL label, but a voxel of the halo holds one only if its local component has an
+ * owned voxel.  vgs_set_halo_labels brings the rest: n (voxel code, global label) pairs taken from the OTHER ranks' boundary records
+ * (label -1 = dropped; several pairs of one code must agree).  Every code this context holds without owning it gets that label in a table
+ * of the graph's own; vox_label, the point labels and the descriptors are not touched.  A voxel of another rank without a pair stays
+ * "unknown".  The table holds until the next run of the stages or the next vgs_apply_tile_labels; without a call every voxel of another
+ * rank is unknown. */
+vgs_status vgs_set_halo_labels(vgs_ctx* ctx, const uint64_t* code, const int32_t* label, int64_t n);
+/* This context's share of the graph over the global labels 0 .. K-1 (K = kept_global): the table of vgs_get_segment_graph -- fields, edge
+ * order, NaN rules -- restricted to what this rank counts: the node pairs {u, v} whose lower-id endpoint u it OWNS (whoever owns v), and
+ * in nodes_ab the nodes it owns.  Effective labels: vox_label for an owned used voxel, the halo table for any other.  Summed over the
+ * ranks (counts add, w_sum adds, w_min / w_max over the ranks with n_finite > 0) the tables give the graph of the whole scene, each
+ * contribution from exactly one rank.  VGS_E_UNSUPPORTED, with the count in the message, if the row of an owned voxel holds a used voxel
+ * of another rank whose label is unknown; VGS_E_ARG if a label is not below K.  n_edges is required; every array holds up to *n_edges
+ * rows and any may be NULL.  Two-call protocol (as vgs_get_boundary_roots): a call with every array NULL computes the table on the
+ * device and returns its size; a call with arrays copies that table if K is the same and neither the labels nor the halo table changed
+ * since, and computes it otherwise.  Nothing else is cached: the driver keeps the folded table.  VGS_E_STATE before the context is
+ * segmented and for a context that is not a tile context. */
+vgs_status vgs_get_own_segment_graph(vgs_ctx* ctx, int64_t K, int64_t* n_edges, int32_t* seg_ab, int64_t* n_pairs, int64_t* n_finite,
+                                     int32_t* nodes_ab, double* w_sum, float* w_min, float* w_max);
 
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.

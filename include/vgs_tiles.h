@@ -11,7 +11,8 @@
  * host, a GPU scan + broadcast only where a box leaves the step open) -> the four stages on tile + halo -> unique boundary
  * voxels (code, local root, owned voxels of that root) and the number of purely local segments leave the GPU -> ncclAllGather
  * -> the same union-find over (rank, root) on every rank, size filter on global sizes -> labels applied on the GPU.  Per-segment
- * descriptors on request afterwards: a second collective of their own (vgs_tiles_get_segment_descriptors).
+ * descriptors on request afterwards: a second collective of their own (vgs_tiles_get_segment_descriptors).  The segment adjacency graph
+ * on request: a third collective of its own (vgs_tiles_get_segment_graph).
  */
 #ifndef VGS_TILES_H_
 #define VGS_TILES_H_
@@ -117,6 +118,53 @@ vgs_status vgs_tiles_get_descriptor_times(vgs_tiles* t, double* ms, int32_t n /*
 vgs_status vgs_tiles_fold_moments(int world, const int64_t* rec_off, const int32_t* label, const int64_t* n_points, const int32_t* n_nodes,
                                   const float* bbox6, const float* anchor3, const double* s9, int64_t K, int64_t* n_points_out,
                                   int32_t* n_nodes_out, float* bbox6_out, float* anchor3_out, double* s9_out);
+/* Segment adjacency graph over all ranks.
+ * vgs_tiles_get_segment_graph returns the table of vgs_get_segment_graph (include/vgs.h) with the same fields, types, edge order and NaN
+ * rules.  It is taken over the voxels of the shared grid and the global labels 0 .. kept_global-1 that vgs_tiles_get_point_labels reports.
+ *   * A node is a used voxel of the shared grid with a kept global label.
+ *   * An edge is a label pair a < b with a node pair {u, v}, v in u's stored adjacency row.
+ *   * w(u, v) = vm_pair_weight(node[lower id], node[higher id]).  "Lower id" means the larger voxel code.  Every rank numbers its voxels
+ *     in descending code order of the same grid, so the comparison v > u gives the same answer on every rank.
+ * Counting rule.  It makes each contribution exist on exactly one rank:
+ *   * A node pair {u, v} is counted by the rank that OWNS its lower-id endpoint u (vgs_set_owned_region), whoever owns v.
+ *   * A node u of a "with a neighbour in b" (nodes_ab) is counted by the rank that owns u.
+ * So a rank walks the rows of its owned used voxels only, and those rows include halo voxels.  The halo is 2 * graph_size + voxel_size
+ * wide and the strips are assembled in rank order, so a halo voxel inside an owned voxel's row is complete and carries the same node
+ * record as on its owner.  Its label comes from its owner: every owned voxel with a voxel of another rank in its row is a boundary voxel
+ * of the run's exchange, so the records every rank already holds name (code, global label) of every such voxel; the driver hands them to
+ * the context (vgs_set_halo_labels) and a used halo voxel in an owned row without one fails the call (VGS_E_UNSUPPORTED, the count in the
+ * message) instead of shrinking the table.
+ *
+ * n_edges is required.  The call is COLLECTIVE whenever the table is not cached -- also with every array NULL, the size query, because the
+ * size is not known before the ranks' tables meet: after one vgs_tiles_run every rank makes the first call.  Once it has returned VGS_OK
+ * the table is cached on this rank: further calls (the size query, then the call with arrays of *n_edges rows; any pointer may be NULL)
+ * make no collective and may be made by any rank alone, until the next vgs_tiles_run or vgs_tiles_set_points drops the table.
+ * Protocol (csrc/tiles.cpp): the halo labels from the kept boundary records -> this rank's partial table (vgs_get_own_segment_graph, one
+ * small pipeline on its GPU) -> ONE all_gather_varlen of 48-byte edge records behind a header of record count and status word -> the
+ * same host fold on every rank (vgs_tiles_fold_edges).  Every rank receives the same bytes, bit-identical from call to call and from run
+ * to run on the same input and layout.  Failures as in vgs_tiles_run: a rank whose local step fails still joins the exchange with its
+ * status word, returns its own error, and every other rank returns VGS_E_PEER naming it (tests inject one with VGS_TILES_FAIL_AT=graph).
+ * VGS_E_STATE (no collective) before a run.  vgs_tiles_run itself gains no launch and no collective; the point labels and the
+ * descriptors are not touched. */
+vgs_status vgs_tiles_get_segment_graph(vgs_tiles* t, int64_t* n_edges, int32_t* seg_ab, int64_t* n_pairs, int64_t* n_finite, int32_t* nodes_ab,
+                                       double* w_sum, float* w_min, float* w_max);
+/* host wall time of the last graph collective on this rank, milliseconds: the halo labels (list and upload), the own table on the GPU (with
+ * its download), the exchange, the fold, total */
+enum { VGS_TILES_G_HALO = 0, VGS_TILES_G_OWN = 1, VGS_TILES_G_EXCHANGE = 2, VGS_TILES_G_FOLD = 3, VGS_TILES_G_TOTAL = 4, VGS_TILES_G_COUNT = 5 };
+vgs_status vgs_tiles_get_graph_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_G_COUNT */);
+/* the last graph collective's payload on this rank: (code, label) pairs handed to its context, edges of its own table, bytes it put into
+ * the all-gather (header included, before padding to the largest rank's) */
+vgs_status vgs_tiles_get_graph_payload(vgs_tiles* t, int64_t* halo_labels, int64_t* own_edges, int64_t* bytes_sent);
+/* The edge fold on its own (host arithmetic, no context, no GPU; for tests): rank r's table is rows rec_off[r] .. rec_off[r+1] (rec_off[0]
+ * = 0) of seg_ab / n_pairs / n_finite / nodes_ab / w_sum / w_min / w_max, ascending in (a, b), over the labels 0 .. K-1.  The tables are
+ * merged by (a, b); per edge the ranks are taken in ascending order: n_pairs, n_finite and nodes_ab add, w_sum adds in fp64 in that
+ * order starting from 0, w_min / w_max are the smallest / largest over the ranks with n_finite > 0 (the others' values are ignored) and NaN
+ * when the total n_finite is 0.  *n_edges rows are written, at most rec_off[world]; any output array may be NULL.  VGS_E_ARG for a label
+ * outside 0 .. K-1, for a >= b, and for a rank table that is not strictly ascending. */
+vgs_status vgs_tiles_fold_edges(int world, const int64_t* rec_off, const int32_t* seg_ab, const int64_t* n_pairs, const int64_t* n_finite,
+                                const int32_t* nodes_ab, const double* w_sum, const float* w_min, const float* w_max, int64_t K,
+                                int64_t* n_edges, int32_t* seg_ab_out, int64_t* n_pairs_out, int64_t* n_finite_out, int32_t* nodes_ab_out,
+                                double* w_sum_out, float* w_min_out, float* w_max_out);
 /* the rank's engine context (read-only use: counts, stage times) */
 vgs_ctx* vgs_tiles_context(vgs_tiles* t);
 

@@ -246,6 +246,61 @@ bool fold_moments(const std::vector<std::vector<MomentRec>>& ranks, int64_t K, s
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------ segment graph
+// One edge of one rank's partial table (vgs_get_own_segment_graph); the payload of the graph exchange.  Its first entry is the header:
+// a = the rank's status word, n_pairs = its record count.
+struct EdgeRec {
+  int32_t a = 0, b = 0;
+  int64_t n_pairs = 0, n_finite = 0;
+  int32_t nodes_a = 0, nodes_b = 0;
+  double w_sum = 0;
+  float w_min = 0, w_max = 0;
+};
+static_assert(sizeof(EdgeRec) == 48, "EdgeRec is the exchange's wire format");
+
+// The edge table of the whole scene from the ranks' partial tables, the same bytes on every rank: the tables are merged by (a, b); per
+// edge the ranks are taken in ascending order.  Counts add, w_sum adds in fp64 in that order, w_min / w_max take the smaller / larger of
+// the ranks with n_finite > 0 (NaN when there is none).  Returns false for a label outside 0 .. K-1, a >= b, or a rank table that is not
+// strictly ascending in (a, b).
+bool fold_edges(const std::vector<std::vector<EdgeRec>>& ranks, int64_t K, std::vector<EdgeRec>& out) {
+  struct Ref { uint64_t key; int32_t rank; uint32_t idx; };
+  std::vector<Ref> refs;
+  size_t total = 0;
+  for (const std::vector<EdgeRec>& R : ranks) total += R.size();
+  refs.reserve(total);
+  for (size_t r = 0; r < ranks.size(); ++r) {
+    const std::vector<EdgeRec>& R = ranks[r];
+    uint64_t prev = 0;
+    for (size_t i = 0; i < R.size(); ++i) {
+      const EdgeRec& e = R[i];
+      if (e.a < 0 || e.b < 0 || (int64_t)e.a >= K || (int64_t)e.b >= K || e.a >= e.b) return false;
+      const uint64_t key = (uint64_t)e.a * (uint64_t)K + (uint64_t)e.b;   // K < 2^31: below 2^62
+      if (i > 0 && key <= prev) return false;
+      prev = key;
+      refs.push_back(Ref{key, (int32_t)r, (uint32_t)i});
+    }
+  }
+  std::sort(refs.begin(), refs.end(), [](const Ref& x, const Ref& y) { return x.key != y.key ? x.key < y.key : x.rank < y.rank; });
+  out.clear();
+  for (size_t k = 0; k < refs.size();) {
+    EdgeRec f;
+    bool have = false;
+    const uint64_t key = refs[k].key;
+    for (; k < refs.size() && refs[k].key == key; ++k) {
+      const EdgeRec& e = ranks[(size_t)refs[k].rank][refs[k].idx];
+      f.a = e.a; f.b = e.b;
+      f.n_pairs += e.n_pairs; f.n_finite += e.n_finite; f.nodes_a += e.nodes_a; f.nodes_b += e.nodes_b;
+      f.w_sum += e.w_sum;
+      if (e.n_finite <= 0) continue;
+      if (!have) { f.w_min = e.w_min; f.w_max = e.w_max; have = true; }
+      else { if (e.w_min < f.w_min) f.w_min = e.w_min; if (e.w_max > f.w_max) f.w_max = e.w_max; }
+    }
+    if (!have) { f.w_min = __builtin_nanf(""); f.w_max = __builtin_nanf(""); }
+    out.push_back(f);
+  }
+  return true;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ driver
@@ -262,7 +317,7 @@ struct vgs_tiles {
   double times[VGS_TILES_T_COUNT] = {0};   // last run, milliseconds of host wall time per phase (vgs_tiles_get_times)
   int strict_region = 0;      // VGS_TILES_OPT_STRICT_REGION
   int fail_phase = 0;         // tests (VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT): 1 grid, 2 stages, 3 points, 4 upload (behind the last collective of set_points),
-                              // 5 descriptors (before the descriptor exchange)
+                              // 5 descriptors (before the descriptor exchange), 6 graph (before the graph exchange)
   vgs_status pending = VGS_OK;   // a local failure behind a call's last collective: the status word of the next collective carries it
   bool warned_outside = false;
   bool ran = false;              // the last vgs_tiles_run completed here
@@ -273,6 +328,15 @@ struct vgs_tiles {
   std::vector<float> d_bbox, d_eig8;
   std::vector<double> d_cen, d_cov, d_eval, d_evec;
   double dtimes[VGS_TILES_D_COUNT] = {0};   // the last descriptor collective, milliseconds of host wall time per phase
+  // what the last run's boundary exchange brought (vgs_tiles_get_segment_graph turns it into the halo labels): every rank's records
+  // (code, root) and the global label of every (rank, root)
+  std::vector<RankRecords> run_rec;
+  std::vector<std::vector<int32_t>> run_uroot, run_ulabel;
+  // the global edge table of the last run (vgs_tiles_get_segment_graph); valid until the next run / set_points
+  bool graph_valid = false;
+  std::vector<EdgeRec> graph;
+  double gtimes[VGS_TILES_G_COUNT] = {0};   // the last graph collective, milliseconds of host wall time per phase
+  int64_t g_halo = 0, g_own = 0, g_bytes = 0;   // its payload: halo labels handed to the context, own edges, bytes sent
   std::string err;
 };
 
@@ -322,7 +386,7 @@ vgs_status vgs_tiles_create(const vgs_params* p, int comm_kind, void* comm_handl
     // failure injection for the tests of the agreed-status protocol; read once, here
     const char* fr = std::getenv("VGS_TILES_FAIL_RANK");
     const char* fa = std::getenv("VGS_TILES_FAIL_AT");
-    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : !std::strcmp(fa, "descriptors") ? 5 : 0;
+    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : !std::strcmp(fa, "descriptors") ? 5 : !std::strcmp(fa, "graph") ? 6 : 0;
   }
   vgs_status s = vgs_create(p, &t->ctx);
   if (s != VGS_OK) { delete t->comm; delete t; return s; }
@@ -355,7 +419,7 @@ vgs_status vgs_tiles_get_times(vgs_tiles* t, double* ms, int32_t n) {
 vgs_status vgs_tiles_set_points(vgs_tiles* t, const float* xyz, int64_t n, int32_t stride_bytes) {
   if (!t || (!xyz && n > 0) || n < 0 || (stride_bytes != 12 && stride_bytes != 16)) return VGS_E_ARG;
   Comm& c = *t->comm;
-  t->ran = false; t->desc_valid = false;
+  t->ran = false; t->desc_valid = false; t->graph_valid = false;
   const int sf = stride_bytes / 4;
   if (!(t->pitch > 0)) {   // the largest x-extent over the ranks
     float mn = 3.0e38f, mx = -3.0e38f;
@@ -492,7 +556,7 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
   if (!t) return VGS_E_ARG;
   Comm& c = *t->comm;
   vgs_status carry = t->pending;   // a local failure behind the last collective of the previous call (upload, label write-back) travels now
-  t->ran = false; t->desc_valid = false;
+  t->ran = false; t->desc_valid = false; t->graph_valid = false;
   double t0 = now_ms();
   vgs_status s = chain_grid(t, carry);
   if (s != VGS_OK) return s;
@@ -575,6 +639,8 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
   double t6 = now_ms();
   t->times[VGS_TILES_T_LABELS] = t6 - t5;
   t->times[VGS_TILES_T_TOTAL] = t6 - t0;
+  for (RankRecords& R : rec) { R.cnt.clear(); R.cnt.shrink_to_fit(); }
+  t->run_rec.swap(rec); t->run_uroot.swap(uroot); t->run_ulabel.swap(ulabel);   // (kept for the segment graph's halo labels; nothing is copied)
   t->ran = true;
   return VGS_OK;
 }
@@ -656,6 +722,144 @@ vgs_status vgs_tiles_get_segment_descriptors(vgs_tiles* t, int64_t* K, int64_t* 
 vgs_status vgs_tiles_get_descriptor_times(vgs_tiles* t, double* ms, int32_t n) {
   if (!t || !ms || n < 0 || n > VGS_TILES_D_COUNT) return VGS_E_ARG;
   for (int i = 0; i < n; ++i) ms[i] = t->dtimes[i];
+  return VGS_OK;
+}
+
+// The segment graph over the ranks: the halo labels from the run's own boundary records -> this rank's partial table (one small pipeline
+// on its GPU over the rows of its owned voxels) -> ONE all_gather_varlen of the edge records with a header of record count and status word
+// -> the same host fold on every rank.
+vgs_status vgs_tiles_get_segment_graph(vgs_tiles* t, int64_t* n_edges, int32_t* seg_ab, int64_t* n_pairs, int64_t* n_finite, int32_t* nodes_ab,
+                                       double* w_sum, float* w_min, float* w_max) {
+  if (!t || !n_edges) return VGS_E_ARG;
+  *n_edges = 0;
+  if (!t->graph_valid) {
+    if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_graph: vgs_tiles_run first");
+    Comm& c = *t->comm;
+    const int64_t Kg = t->kept;
+    vgs_status carry = t->pending;
+    if (t->fail_phase == 6 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=graph"; }
+    const double t0 = now_ms();
+    // (code, global label) of every boundary record of the other ranks: a voxel this rank holds in its halo and counts pairs with has one
+    std::vector<uint64_t> hcode;
+    std::vector<int32_t> hlab;
+    if (carry == VGS_OK && t->run_rec.size() == (size_t)c.world) {
+      for (int r = 0; r < c.world; ++r) {
+        if (r == c.rank) continue;
+        const RankRecords& R = t->run_rec[(size_t)r];
+        const std::vector<int32_t>& ur = t->run_uroot[(size_t)r];
+        const std::vector<int32_t>& ul = t->run_ulabel[(size_t)r];
+        for (size_t k = 0; k < R.code.size(); ++k) {
+          const size_t j = (size_t)(std::lower_bound(ur.begin(), ur.end(), R.root[k]) - ur.begin());
+          hcode.push_back(R.code[k]);
+          hlab.push_back(ul[j]);
+        }
+      }
+    }
+    const uint64_t no_code = 0;
+    const int32_t no_lab = 0;
+    TCARRY(vgs_set_halo_labels(t->ctx, hcode.empty() ? &no_code : hcode.data(), hlab.empty() ? &no_lab : hlab.data(), (int64_t)hcode.size()));
+    const double t1 = now_ms();
+    std::vector<EdgeRec> payload(1);
+    if (carry == VGS_OK) {
+      int64_t E = 0;
+      TCARRY(vgs_get_own_segment_graph(t->ctx, Kg, &E, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+      if (carry == VGS_OK && E > 0) {
+        const size_t e1 = (size_t)E;
+        std::vector<int32_t> ab(2 * e1), nd(2 * e1);
+        std::vector<int64_t> np(e1), nf(e1);
+        std::vector<double> ws(e1);
+        std::vector<float> mn(e1), mx(e1);
+        TCARRY(vgs_get_own_segment_graph(t->ctx, Kg, &E, ab.data(), np.data(), nf.data(), nd.data(), ws.data(), mn.data(), mx.data()));
+        if (carry == VGS_OK) {
+          payload.resize(1 + e1);
+          for (size_t i = 0; i < e1; ++i) {
+            EdgeRec& e = payload[1 + i];
+            e.a = ab[2 * i]; e.b = ab[2 * i + 1]; e.n_pairs = np[i]; e.n_finite = nf[i]; e.nodes_a = nd[2 * i]; e.nodes_b = nd[2 * i + 1];
+            e.w_sum = ws[i]; e.w_min = mn[i]; e.w_max = mx[i];
+          }
+        }
+      }
+    }
+    payload[0].a = (int32_t)carry;
+    payload[0].n_pairs = (int64_t)payload.size() - 1;
+    const double t2 = now_ms();
+    std::vector<std::vector<EdgeRec>> gathered;
+    TCOMM(all_gather_varlen(c, payload, gathered));
+    const double t3 = now_ms();
+    {
+      int bad = -1;
+      for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].empty() || gathered[(size_t)r][0].a != 0) bad = r;
+      vgs_status a = agreed(t, carry, bad, "graph");
+      if (a != VGS_OK) return a;
+    }
+    for (std::vector<EdgeRec>& g : gathered) g.erase(g.begin());   // the headers
+    if (!fold_edges(gathered, Kg, t->graph)) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_graph: a rank sent a table that is not sorted or names a label >= kept_global");
+    const double t4 = now_ms();
+    t->gtimes[VGS_TILES_G_HALO] = t1 - t0; t->gtimes[VGS_TILES_G_OWN] = t2 - t1; t->gtimes[VGS_TILES_G_EXCHANGE] = t3 - t2;
+    t->gtimes[VGS_TILES_G_FOLD] = t4 - t3; t->gtimes[VGS_TILES_G_TOTAL] = t4 - t0;
+    t->g_halo = (int64_t)hcode.size(); t->g_own = (int64_t)payload.size() - 1; t->g_bytes = (int64_t)(payload.size() * sizeof(EdgeRec));
+    t->graph_valid = true;
+  }
+  const size_t E = t->graph.size();
+  *n_edges = (int64_t)E;
+  for (size_t i = 0; i < E; ++i) {
+    const EdgeRec& e = t->graph[i];
+    if (seg_ab) { seg_ab[2 * i] = e.a; seg_ab[2 * i + 1] = e.b; }
+    if (n_pairs) n_pairs[i] = e.n_pairs;
+    if (n_finite) n_finite[i] = e.n_finite;
+    if (nodes_ab) { nodes_ab[2 * i] = e.nodes_a; nodes_ab[2 * i + 1] = e.nodes_b; }
+    if (w_sum) w_sum[i] = e.w_sum;
+    if (w_min) w_min[i] = e.w_min;
+    if (w_max) w_max[i] = e.w_max;
+  }
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_graph_times(vgs_tiles* t, double* ms, int32_t n) {
+  if (!t || !ms || n < 0 || n > VGS_TILES_G_COUNT) return VGS_E_ARG;
+  for (int i = 0; i < n; ++i) ms[i] = t->gtimes[i];
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_graph_payload(vgs_tiles* t, int64_t* halo_labels, int64_t* own_edges, int64_t* bytes_sent) {
+  if (!t) return VGS_E_ARG;
+  if (halo_labels) *halo_labels = t->g_halo;
+  if (own_edges) *own_edges = t->g_own;
+  if (bytes_sent) *bytes_sent = t->g_bytes;
+  return VGS_OK;
+}
+
+// host arithmetic only (tests): the edge fold on flattened per-rank tables
+vgs_status vgs_tiles_fold_edges(int world, const int64_t* rec_off, const int32_t* seg_ab, const int64_t* n_pairs, const int64_t* n_finite,
+                                const int32_t* nodes_ab, const double* w_sum, const float* w_min, const float* w_max, int64_t K,
+                                int64_t* n_edges, int32_t* seg_ab_out, int64_t* n_pairs_out, int64_t* n_finite_out, int32_t* nodes_ab_out,
+                                double* w_sum_out, float* w_min_out, float* w_max_out) {
+  if (world < 1 || !rec_off || K < 0 || K >= (int64_t)0x7fffffffLL || !n_edges) return VGS_E_ARG;
+  *n_edges = 0;
+  if (rec_off[0] != 0) return VGS_E_ARG;
+  for (int r = 0; r < world; ++r) if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
+  if (rec_off[world] > 0 && (!seg_ab || !n_pairs || !n_finite || !nodes_ab || !w_sum || !w_min || !w_max)) return VGS_E_ARG;
+  std::vector<std::vector<EdgeRec>> ranks((size_t)world);
+  for (int r = 0; r < world; ++r)
+    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) {
+      EdgeRec e;
+      e.a = seg_ab[2 * i]; e.b = seg_ab[2 * i + 1]; e.n_pairs = n_pairs[i]; e.n_finite = n_finite[i]; e.nodes_a = nodes_ab[2 * i];
+      e.nodes_b = nodes_ab[2 * i + 1]; e.w_sum = w_sum[i]; e.w_min = w_min[i]; e.w_max = w_max[i];
+      ranks[(size_t)r].push_back(e);
+    }
+  std::vector<EdgeRec> out;
+  if (!fold_edges(ranks, K, out)) return VGS_E_ARG;
+  *n_edges = (int64_t)out.size();
+  for (size_t i = 0; i < out.size(); ++i) {
+    const EdgeRec& e = out[i];
+    if (seg_ab_out) { seg_ab_out[2 * i] = e.a; seg_ab_out[2 * i + 1] = e.b; }
+    if (n_pairs_out) n_pairs_out[i] = e.n_pairs;
+    if (n_finite_out) n_finite_out[i] = e.n_finite;
+    if (nodes_ab_out) { nodes_ab_out[2 * i] = e.nodes_a; nodes_ab_out[2 * i + 1] = e.nodes_b; }
+    if (w_sum_out) w_sum_out[i] = e.w_sum;
+    if (w_min_out) w_min_out[i] = e.w_min;
+    if (w_max_out) w_max_out[i] = e.w_max;
+  }
   return VGS_OK;
 }
 

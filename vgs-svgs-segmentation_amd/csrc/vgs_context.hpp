@@ -281,7 +281,14 @@ struct vgs_ctx {
   DevBuf<float> sg_wmin, sg_wmax;
   int64_t sg_E = 0;
   bool sg_valid = false;
-  DevBuf<uint64_t> counters;   // device-side counters (pairs, flags)
+  // tile contexts (vgs_set_halo_labels / vgs_get_own_segment_graph): the global label of every voxel this rank does not own (SG_UNKNOWN
+  // without a record), the (code, label) upload, per-row counts of unknown neighbours
+  DevBuf<int32_t> sg_halo, sg_hlab;
+  DevBuf<uint64_t> sg_hcode;
+  DevBuf<uint32_t> sg_nunk;
+  bool sg_halo_valid = false;
+  int64_t sg_own_K = -1;   // the key space of the tile table the sg_* outputs hold (-1: none)
+  DevBuf<uint64_t> counters;  // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 
   int64_t counts[VGS_N_COUNTS] = {0};

@@ -25,6 +25,7 @@ _RCCL = None
 
 T_NAMES = ("grid", "stages", "records", "exchange", "merge", "labels", "total")
 D_NAMES = ("moments", "exchange", "fold", "algebra", "total")   # vgs_tiles_get_descriptor_times
+G_NAMES = ("halo", "own", "exchange", "fold", "total")          # vgs_tiles_get_graph_times
 # per record / row: (field, dtype, values) of vgs_get_own_segment_moments and vgs_tiles_fold_moments, in their argument order
 MOMENT_FIELDS = (("n_points", np.int64, 1), ("n_nodes", np.int32, 1), ("bbox6", np.float32, 6), ("anchor3", np.float32, 3), ("s9", np.float64, 9))
 COMM_RCCL, COMM_LOCAL, COMM_CALLBACKS = 0, 1, 2
@@ -81,6 +82,14 @@ def lib():
         L.vgs_tiles_get_descriptor_times.argtypes = [P, P, C.c_int32]
         L.vgs_tiles_fold_moments.restype = C.c_int
         L.vgs_tiles_fold_moments.argtypes = [C.c_int, P, P, P, P, P, P, P, C.c_int64, P, P, P, P, P]
+        L.vgs_tiles_get_segment_graph.restype = C.c_int
+        L.vgs_tiles_get_segment_graph.argtypes = [P, P, P, P, P, P, P, P, P]
+        L.vgs_tiles_get_graph_times.restype = C.c_int
+        L.vgs_tiles_get_graph_times.argtypes = [P, P, C.c_int32]
+        L.vgs_tiles_get_graph_payload.restype = C.c_int
+        L.vgs_tiles_get_graph_payload.argtypes = [P, P, P, P]
+        L.vgs_tiles_fold_edges.restype = C.c_int
+        L.vgs_tiles_fold_edges.argtypes = [C.c_int, P, P, P, P, P, P, P, P, C.c_int64, P, P, P, P, P, P, P, P]
         _TL = L
     return _TL
 
@@ -105,6 +114,31 @@ def fold_moments(records, K):
     if st != 0:
         raise VgsError(st, "vgs_tiles_fold_moments")
     return out
+
+
+def _graph_fields():
+    from .api import Engine
+    return Engine.GRAPH_FIELDS
+
+
+def fold_edges(tables, K):
+    """vgs_tiles_fold_edges (host arithmetic, no GPU): tables[r] = rank r's partial edge table, a dict of Engine.GRAPH_FIELDS arrays
+    ascending in (a, b); returns the folded table over the labels 0 .. K-1 as the same dict."""
+    F = _graph_fields()
+    world = len(tables)
+    n = [np.asarray(t["seg_ab"]).reshape(-1, 2).shape[0] for t in tables]
+    off = np.zeros(world + 1, dtype=np.int64)
+    off[1:] = np.cumsum(n)
+    flat = {name: np.ascontiguousarray(np.concatenate([np.asarray(t[name], dtype=dt).reshape(-1, w) for t in tables]).reshape(-1))
+            for name, dt, w in F}
+    total = max(int(off[-1]), 1)
+    out = {name: np.zeros((total, w) if w > 1 else total, dtype=dt) for name, dt, w in F}
+    E = C.c_int64(0)
+    st = lib().vgs_tiles_fold_edges(world, _vp(off), *(_vp(flat[name]) for name, _, _ in F), int(K), C.byref(E),
+                                    *(_vp(out[name]) for name, _, _ in F))
+    if st != 0:
+        raise VgsError(st, "vgs_tiles_fold_edges")
+    return {name: a[:E.value].copy() for name, a in out.items()}
 
 
 # ---- RCCL through ctypes: the three calls a caller needs to hand the driver a communicator ---------------------------------------
@@ -293,6 +327,45 @@ class NativeTiles:
         t = np.zeros(len(D_NAMES), dtype=np.float64)
         self._ck(self._L.vgs_tiles_get_descriptor_times(self._h, _vp(t), len(D_NAMES)))
         return dict(zip(D_NAMES, (float(x) for x in t)))
+
+    def segment_graph(self):
+        """COLLECTIVE on its first call after run() (every rank makes it): the adjacency graph of the global segments over all ranks,
+        labels = point_labels() on any rank -- the dict of Engine.segment_graph(), the same bytes on every rank (include/vgs_tiles.h,
+        vgs_tiles_get_segment_graph).  Cached until the next run() or set_points(): later calls make no collective."""
+        F = _graph_fields()
+        E = C.c_int64(0)
+        self._ck(self._L.vgs_tiles_get_segment_graph(self._h, C.byref(E), *([None] * len(F))))
+        out = {name: np.zeros((E.value, w) if w > 1 else E.value, dtype=dt) for name, dt, w in F}
+        if E.value:
+            self._ck(self._L.vgs_tiles_get_segment_graph(self._h, C.byref(E), *(_vp(out[name]) for name, _, _ in F)))
+        return out
+
+    def graph_times(self):
+        """the last graph collective's phases on this rank, milliseconds (G_NAMES)"""
+        t = np.zeros(len(G_NAMES), dtype=np.float64)
+        self._ck(self._L.vgs_tiles_get_graph_times(self._h, _vp(t), len(G_NAMES)))
+        return dict(zip(G_NAMES, (float(x) for x in t)))
+
+    def graph_payload(self):
+        """the last graph collective's payload on this rank: halo labels handed to the context, edges of its own table, bytes sent"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self._L.vgs_tiles_get_graph_payload(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(halo_labels=a.value, own_edges=b.value, bytes_sent=c.value)
+
+    def own_segment_graph(self, K):
+        """this rank's partial edge table over the global labels 0 .. K-1 (vgs_get_own_segment_graph on its context; local, no
+        collective; the halo labels are those of the last segment_graph() collective, if any)"""
+        L = _lib.lib()
+        h = self._ctx()
+        F = _graph_fields()
+        E = C.c_int64(0)
+        st = L.vgs_get_own_segment_graph(h, int(K), C.byref(E), *([None] * len(F)))
+        out = {name: np.zeros((E.value, w) if w > 1 else E.value, dtype=dt) for name, dt, w in F}
+        if st == 0 and E.value:
+            st = L.vgs_get_own_segment_graph(h, int(K), C.byref(E), *(_vp(out[name]) for name, _, _ in F))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        return out
 
     def own_segment_moments(self, K):
         """this rank's moment records of the global labels 0 .. K-1 (vgs_get_own_segment_moments on its context; local, no collective):
