@@ -23,8 +23,8 @@ key_b = 8   # 64-bit codes on URB10M (34 key bits)
 # kernel, algorithmic bytes per call, what they are
 spec = [
     ("k_make_codes", (12 + key_b + 4) * N, "xyz in; code + index out"),
-    ("k_heads", (key_b + 4) * N, "sorted codes in; run-head flags out"),
-    ("k_voxel_table", (key_b + 4 + 4 + 4) * N, "codes, heads, scan in; point->voxel out (+ V table entries)"),
+    ("k_run_counts", (key_b + 4) * N, "sorted keys in; unpacked order out (+ two counts per tile of 2048 keys)"),
+    ("k_voxel_runs", (key_b + 4) * N + 12 * V, "sorted keys in; point->voxel out, V table entries (code 8 + first point 4)"),
     ("k_gather_points", (4 + 12 + 12) * N, "order in; xyz gathered (12 B random reads); SoA out"),
     ("k_features", 12 * N + 64 * V, "leaf-order points in; 64-byte voxel records out"),
     ("k_point_labels", (4 + 4 + 4) * N, "order + point->voxel in; labels scattered out"),

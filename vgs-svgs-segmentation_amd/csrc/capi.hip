@@ -221,7 +221,7 @@ void vgs_destroy(vgs_ctx* c) {
   if (c->s_d2h) (void)hipStreamSynchronize(c->s_d2h);
   c->xyz_buf[0].release(); c->xyz_buf[1].release(); c->pt_label_alt.release(); c->grow_state.release();
   c->code_a.release(); c->code_b.release(); c->perm_a.release(); c->perm_b.release(); c->sort_tmp.release();
-  c->head_flag.release(); c->pt_vox.release(); c->vox_code.release(); c->vox_start.release();
+  c->head_flag.release(); c->pt_vox.release(); c->vox_tile.release(); c->vox_code.release(); c->vox_start.release();
   c->xs.release(); c->ys.release(); c->zs.release();
   c->node.release(); c->used_ids.release(); c->used_rank.release();
   c->hkey.release(); c->hval.release(); c->offsets.release(); c->adj_masks.release(); c->adj_gtab.release(); c->adj_nvals.release(); c->adj_nrank.release(); c->adj_key.release(); c->adj_off.release(); c->adj_cnt.release(); c->adj_mused.release();

@@ -166,7 +166,9 @@ struct vgs_ctx {
   DevBuf<uint32_t> perm_a, perm_b;
   DevBuf<uint8_t> sort_tmp;
   DevBuf<uint64_t> grow_state;         // GrowState of the box growth (voxelize.hip)
-  DevBuf<uint32_t> head_flag, pt_vox;  // per sorted position
+  DevBuf<uint32_t> pt_vox;             // per sorted position
+  DevBuf<uint32_t> vox_tile;           // per tile of the sorted keys: run heads (then heads in front of the tile), valid keys
+  DevBuf<uint32_t> head_flag;          // flags in front of a scan: scratch of the later stages (features, merge, supervoxels, boundary records)
   DevBuf<uint64_t> vox_code;
   DevBuf<uint32_t> vox_start;
   DevBuf<float> xs, ys, zs;  // points in sorted order (SoA)

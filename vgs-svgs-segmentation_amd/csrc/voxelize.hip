@@ -259,38 +259,146 @@ __global__ void k_make_codes(const float* __restrict__ xyz, int stride_f, int64_
   perm[i] = (uint32_t)i;
 }
 
-// run heads in the sorted code array (invalid codes == 0 sit at the tail of the descending order)
+// ---------------------------------------------------------------------------------------------
+// sorted keys -> voxel table, in two passes over the keys (invalid codes == 0 sit at the tail of the descending order)
+// ---------------------------------------------------------------------------------------------
+// A tile is VR_TILE consecutive sorted keys, one workgroup, VR_KPT consecutive keys per thread.  A run head is a valid key whose code
+// differs from its predecessor's; the first key of a tile looks at the last key of the tile in front.  Pass 1 (k_run_counts) counts the
+// heads and the valid keys of every tile, one workgroup (k_tile_offsets) turns the per-tile head counts into offsets and the totals,
+// pass 2 (k_voxel_runs) recomputes the flags, scans them inside the workgroup and writes the table.  No workgroup waits for another.
+#define VR_TB 512
+#define VR_KPT 4
+#define VR_TILE (VR_TB * VR_KPT)
+
+// the thread's VR_KPT raw keys (0 behind the end) and the raw key in front of them (the lane in front holds it, except for a wavefront's first lane)
 template <typename KeyT>
-__global__ void k_heads(const KeyT* __restrict__ code, int64_t n, uint32_t* __restrict__ head, int pack_shift, uint32_t* __restrict__ perm_out) {
-  int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < n) {
-    const uint64_t raw = (uint64_t)code[j];
-    const uint64_t c = raw >> pack_shift;
-    head[j] = (c != 0 && (j == 0 || ((uint64_t)code[j - 1] >> pack_shift) != c)) ? 1u : 0u;
-    if (pack_shift > 0) perm_out[j] = (uint32_t)(raw & ((1ull << pack_shift) - 1ull));   // the sorted order, unpacked for everybody downstream
+__device__ __forceinline__ void vr_load(const KeyT* __restrict__ code, int64_t n, int64_t j0, KeyT (&k)[VR_KPT], KeyT& prev) {
+  struct alignas(sizeof(KeyT) * VR_KPT) Vec { KeyT v[VR_KPT]; };
+  if (j0 + VR_KPT <= n) {
+    const Vec q = *(const Vec*)(code + j0);   // j0 is a multiple of VR_KPT
+#pragma unroll
+    for (int i = 0; i < VR_KPT; ++i) k[i] = q.v[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < VR_KPT; ++i) k[i] = (j0 + i < n) ? code[j0 + i] : (KeyT)0;
+  }
+  prev = (KeyT)__shfl_up(k[VR_KPT - 1], 1, 64);
+  if ((threadIdx.x & 63) == 0) prev = (j0 > 0 && j0 < n) ? code[j0 - 1] : (KeyT)0;
+}
+// head flags of the thread's keys as a bit mask; valid = number of non-zero codes among them
+__device__ __forceinline__ uint32_t vr_flags(const uint64_t (&c)[VR_KPT], uint64_t cprev, bool first, uint32_t& valid) {
+  uint32_t m = 0;
+  valid = 0;
+#pragma unroll
+  for (int i = 0; i < VR_KPT; ++i) {
+    const uint64_t before = i == 0 ? cprev : c[i - 1];
+    if (c[i] != 0) { ++valid; if ((i == 0 && first) || before != c[i]) m |= 1u << i; }
+  }
+  return m;
+}
+
+// pass 1: heads and valid keys per tile; with packed keys also the sorted order, unpacked for everybody downstream (the gather of the
+// points reads it before the host knows V, so it cannot wait for pass 2)
+template <typename KeyT>
+__global__ __launch_bounds__(VR_TB) void k_run_counts(const KeyT* __restrict__ code, int64_t n, int pack_shift, uint32_t* __restrict__ perm_out,
+                                                      uint32_t* __restrict__ tile_heads, uint32_t* __restrict__ tile_valid) {
+  __shared__ uint32_t s_h[VR_TB / 64], s_v[VR_TB / 64];
+  const int64_t j0 = (int64_t)blockIdx.x * VR_TILE + (int64_t)threadIdx.x * VR_KPT;
+  KeyT k[VR_KPT], kp;
+  vr_load(code, n, j0, k, kp);
+  uint64_t c[VR_KPT];
+#pragma unroll
+  for (int i = 0; i < VR_KPT; ++i) c[i] = (uint64_t)k[i] >> pack_shift;
+  uint32_t valid;
+  uint32_t heads = (uint32_t)__popc(vr_flags(c, (uint64_t)kp >> pack_shift, j0 == 0, valid));
+  if (pack_shift > 0) {
+    const uint64_t low = (1ull << pack_shift) - 1ull;
+    if (j0 + VR_KPT <= n) {
+      *(uint4*)(perm_out + j0) = make_uint4((uint32_t)((uint64_t)k[0] & low), (uint32_t)((uint64_t)k[1] & low), (uint32_t)((uint64_t)k[2] & low),
+                                            (uint32_t)((uint64_t)k[3] & low));
+    } else {
+#pragma unroll
+      for (int i = 0; i < VR_KPT; ++i) if (j0 + i < n) perm_out[j0 + i] = (uint32_t)((uint64_t)k[i] & low);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) { heads += __shfl_down(heads, o, 64); valid += __shfl_down(valid, o, 64); }
+  if ((threadIdx.x & 63) == 0) { s_h[threadIdx.x >> 6] = heads; s_v[threadIdx.x >> 6] = valid; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t h = 0, v = 0;
+    for (int w = 0; w < VR_TB / 64; ++w) { h += s_h[w]; v += s_v[w]; }
+    tile_heads[blockIdx.x] = h;
+    tile_valid[blockIdx.x] = v;
+  }
+}
+static_assert(VR_KPT == 4, "k_run_counts and k_voxel_runs store four 32-bit words per thread at once");
+
+// one workgroup: per-tile head counts -> exclusive offsets (in place); cnt[0] = valid keys = finite points, cnt[1] = heads = voxels
+__global__ __launch_bounds__(1024) void k_tile_offsets(uint32_t* __restrict__ tile_heads, const uint32_t* __restrict__ tile_valid, int64_t n_tiles,
+                                                       unsigned long long* __restrict__ cnt) {
+  __shared__ unsigned long long s_h[1024], s_v[16];
+  const int tid = threadIdx.x;
+  const int64_t per = (n_tiles + 1023) / 1024;
+  const int64_t lo = (int64_t)tid * per < n_tiles ? (int64_t)tid * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
+  unsigned long long h = 0, v = 0;
+  for (int64_t t = lo; t < hi; ++t) { h += tile_heads[t]; v += tile_valid[t]; }
+  s_h[tid] = h;
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  if ((tid & 63) == 0) s_v[tid >> 6] = v;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {   // inclusive scan of the threads' sums
+    const unsigned long long add = tid >= o ? s_h[tid - o] : 0ull;
+    __syncthreads();
+    s_h[tid] += add;
+    __syncthreads();
+  }
+  uint32_t run = (uint32_t)(s_h[tid] - h);   // (the voxel count fits 32 bits: at most one voxel per point)
+  for (int64_t t = lo; t < hi; ++t) { const uint32_t x = tile_heads[t]; tile_heads[t] = run; run += x; }
+  if (tid == 0) {
+    unsigned long long vt = 0;
+    for (int w = 0; w < 16; ++w) vt += s_v[w];
+    cnt[0] = vt;
+    cnt[1] = s_h[1023];
   }
 }
 
-// number of valid (non-zero) codes = index of the first zero in the descending array
+// pass 2: voxel of every sorted point, and at every run head the voxel's table entry (code under `mask`, first point); the entry behind the
+// last voxel closes the last run with the number of finite points
 template <typename KeyT>
-__global__ void k_count_valid(const KeyT* __restrict__ code, int64_t n, unsigned long long* __restrict__ n_valid, int pack_shift) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) { int64_t mid = (lo + hi) >> 1; if (((uint64_t)code[mid] >> pack_shift) != 0) lo = mid + 1; else hi = mid; }
-  *n_valid = (unsigned long long)lo;
-}
-__global__ void k_copy_last(const uint32_t* __restrict__ scan, int64_t n, unsigned long long* __restrict__ out) { *out = (unsigned long long)scan[n - 1]; }
-
-template <typename KeyT>
-__global__ void k_voxel_table(const KeyT* __restrict__ code, const uint32_t* __restrict__ head,
-                              const uint32_t* __restrict__ scan, int64_t n, uint64_t mask, uint32_t* __restrict__ pt_vox,
-                              uint64_t* __restrict__ vox_code, uint32_t* __restrict__ vox_start, int pack_shift) {
-  int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  uint64_t c = (uint64_t)code[j] >> pack_shift;
-  if (c == 0) { pt_vox[j] = 0xffffffffu; return; }
-  uint32_t v = scan[j] - 1u;
-  pt_vox[j] = v;
-  if (head[j]) { vox_code[v] = c & mask; vox_start[v] = (uint32_t)j; }
+__global__ __launch_bounds__(VR_TB) void k_voxel_runs(const KeyT* __restrict__ code, int64_t n, int pack_shift, const uint32_t* __restrict__ tile_off,
+                                                      uint64_t mask, uint32_t* __restrict__ pt_vox, uint64_t* __restrict__ vox_code,
+                                                      uint32_t* __restrict__ vox_start, uint32_t n_vox, uint32_t n_finite) {
+  __shared__ uint32_t s_w[VR_TB / 64];
+  const int64_t j0 = (int64_t)blockIdx.x * VR_TILE + (int64_t)threadIdx.x * VR_KPT;
+  KeyT k[VR_KPT], kp;
+  vr_load(code, n, j0, k, kp);
+  uint64_t c[VR_KPT];
+#pragma unroll
+  for (int i = 0; i < VR_KPT; ++i) c[i] = (uint64_t)k[i] >> pack_shift;
+  uint32_t valid;
+  const uint32_t m = vr_flags(c, (uint64_t)kp >> pack_shift, j0 == 0, valid);
+  const uint32_t mine = (uint32_t)__popc(m);
+  uint32_t incl = mine;   // inclusive scan over the wavefront, then over the workgroup's wavefronts
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o, 64); if (lane >= o) incl += up; }
+  if (lane == 63) s_w[wave] = incl;
+  __syncthreads();
+  uint32_t run = tile_off[blockIdx.x] + incl - mine;
+  for (int w = 0; w < wave; ++w) run += s_w[w];
+  if (blockIdx.x == 0 && threadIdx.x == 0) vox_start[n_vox] = n_finite;
+  if (j0 >= n) return;
+  uint32_t out[VR_KPT];
+#pragma unroll
+  for (int i = 0; i < VR_KPT; ++i) {
+    if ((m >> i) & 1u) { vox_code[run] = c[i] & mask; vox_start[run] = (uint32_t)(j0 + i); ++run; }
+    out[i] = c[i] != 0 ? run - 1u : 0xffffffffu;
+  }
+  if (j0 + VR_KPT <= n) {
+    *(uint4*)(pt_vox + j0) = make_uint4(out[0], out[1], out[2], out[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < VR_KPT; ++i) if (j0 + i < n) pt_vox[j0 + i] = out[i];
+  }
 }
 
 __global__ void k_gather_points(const float* __restrict__ xyz, int stride_f, const uint32_t* __restrict__ perm, int64_t nf,
@@ -300,8 +408,6 @@ __global__ void k_gather_points(const float* __restrict__ xyz, int stride_f, con
   const float* p = xyz + (int64_t)perm[j] * stride_f;
   xs[j] = p[0]; ys[j] = p[1]; zs[j] = p[2];
 }
-
-__global__ void k_set_u32(uint32_t* p, uint32_t v) { *p = v; }
 
 // ---------------------------------------------------------------------------------------------
 // host driver
@@ -376,7 +482,7 @@ static vgs_status grow_box(vgs_ctx* c) {
   return vgs_grow_box_from(c, c->box, true);
 }
 
-// codes -> stable descending sort -> run heads -> voxel table (KeyT as k_make_codes)
+// codes -> stable descending sort -> run counts per tile -> voxel table (KeyT as k_make_codes)
 template <typename KeyT>
 static vgs_status voxelize_sorted_table(vgs_ctx* c) {
   const int64_t N = c->N;
@@ -409,18 +515,16 @@ static vgs_status voxelize_sorted_table(vgs_ctx* c) {
   };
   size_t tmp_bytes = 0;
   VGS_HIP_TRY(c, sort_pairs(nullptr, tmp_bytes));
-  size_t scan_bytes = 0;
-  VGS_HIP_TRY(c, rocprim::inclusive_scan(nullptr, scan_bytes, c->head_flag.p, c->perm_a.p, (size_t)N, rocprim::plus<uint32_t>(), c->stream));
-  VGS_HIP_TRY(c, c->sort_tmp.ensure(std::max(tmp_bytes, scan_bytes)));
+  VGS_HIP_TRY(c, c->sort_tmp.ensure(tmp_bytes));
   VGS_HIP_TRY(c, sort_pairs(c->sort_tmp.p, tmp_bytes));
-  // sorted: code_b, perm_b
-  unsigned long long* d_cnt = (unsigned long long*)c->counters.p;
-  VGS_HIP_TRY(c, hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), c->stream));
-  hipLaunchKernelGGL((k_heads<KeyT>), dim3(nb), dim3(TB), 0, c->stream, code_b, N, c->head_flag.p, pack_shift, c->perm_b.p);
-  hipLaunchKernelGGL((k_count_valid<KeyT>), dim3(1), dim3(1), 0, c->stream, code_b, N, d_cnt, pack_shift);
-  uint32_t* scan = c->perm_a.p;  // perm_a is free after the sort
-  VGS_HIP_TRY(c, rocprim::inclusive_scan(c->sort_tmp.p, scan_bytes, c->head_flag.p, scan, (size_t)N, rocprim::plus<uint32_t>(), c->stream));
-  hipLaunchKernelGGL(k_copy_last, dim3(1), dim3(1), 0, c->stream, scan, N, d_cnt + 1);   // number of voxels next to the number of finite points
+  // sorted: code_b, perm_b (packed keys: perm_b is written by pass 1)
+  const int64_t n_tiles = (N + VR_TILE - 1) / VR_TILE;
+  VGS_HIP_TRY(c, c->vox_tile.ensure((size_t)(2 * n_tiles)));
+  uint32_t* tile_heads = c->vox_tile.p;            // after k_tile_offsets: heads in front of the tile
+  uint32_t* tile_valid = c->vox_tile.p + n_tiles;
+  unsigned long long* d_cnt = (unsigned long long*)c->counters.p;   // number of finite points, number of voxels
+  hipLaunchKernelGGL((k_run_counts<KeyT>), dim3((unsigned)n_tiles), dim3(VR_TB), 0, c->stream, code_b, N, pack_shift, c->perm_b.p, tile_heads, tile_valid);
+  hipLaunchKernelGGL(k_tile_offsets, dim3(1), dim3(1024), 0, c->stream, tile_heads, tile_valid, n_tiles, d_cnt);
   unsigned long long h2[2] = {0, 0};
   if (vgs_can_split_readback(c)) {
     // the leaf-order gather of the points needs the sorted order only, not the counts: it runs while the host fetches them.  All N
@@ -439,9 +543,8 @@ static vgs_status voxelize_sorted_table(vgs_ctx* c) {
   c->V = (int64_t)v_total;
   VGS_HIP_TRY(c, c->vox_code.ensure(c->V + 1)); VGS_HIP_TRY(c, c->vox_start.ensure(c->V + 1));
   const uint64_t mask = (c->code_bits >= 64) ? ~0ull : ((1ull << c->code_bits) - 1ull);
-  hipLaunchKernelGGL((k_voxel_table<KeyT>), dim3(nb), dim3(TB), 0, c->stream, code_b, c->head_flag.p, scan, N, mask, c->pt_vox.p,
-                     c->vox_code.p, c->vox_start.p, pack_shift);
-  hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, c->stream, c->vox_start.p + c->V, (uint32_t)c->Nf);
+  hipLaunchKernelGGL((k_voxel_runs<KeyT>), dim3((unsigned)n_tiles), dim3(VR_TB), 0, c->stream, code_b, N, pack_shift, tile_heads, mask, c->pt_vox.p,
+                     c->vox_code.p, c->vox_start.p, v_total, (uint32_t)c->Nf);
   return VGS_OK;
 }
 
@@ -459,7 +562,7 @@ vgs_status vgs_stage_voxelize(vgs_ctx* c) {
 
   VGS_HIP_TRY(c, c->code_a.ensure(N)); VGS_HIP_TRY(c, c->code_b.ensure(N));
   VGS_HIP_TRY(c, c->perm_a.ensure(N)); VGS_HIP_TRY(c, c->perm_b.ensure(N));
-  VGS_HIP_TRY(c, c->head_flag.ensure(N)); VGS_HIP_TRY(c, c->pt_vox.ensure(N));
+  VGS_HIP_TRY(c, c->pt_vox.ensure(N));
   const int TB = 256;
   c->gathered = false;
   st = (c->code_bits + 1 <= 32) ? voxelize_sorted_table<uint32_t>(c) : voxelize_sorted_table<uint64_t>(c);
