@@ -23,10 +23,12 @@ struct DriverGraph {
 // <prefix>_voxels.ply, <prefix>_clustered_voxels.ply, <prefix>_normals.ply
 // descriptors: when not null, receives getClusterDescriptors() (one per entry of clusters_points_idx, same order)
 // graph: when not null, receives getClusterGraph() and getClusterAdjacency() (cluster indices of clusters_points_idx)
+// boxes: when not null, receives getClusterBoxes(box_frame) (one per entry of clusters_points_idx, same order)
 inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>& input_vector,
                            std::vector<std::vector<int>>& clusters_points_idx, DriverSummary* sum = nullptr,
                            const std::string& debug_prefix = std::string(), double ctor_resolution = 0.0,
-                           std::vector<pcl::ClusterDescriptor>* descriptors = nullptr, DriverGraph* graph = nullptr) {
+                           std::vector<pcl::ClusterDescriptor>* descriptors = nullptr, DriverGraph* graph = nullptr,
+                           std::vector<pcl::ClusterBox>* boxes = nullptr, int box_frame = VGS_BOX_PRINCIPAL) {
   float voxel_size = 0.15f, graph_size = 0.5f, sig_p = 0.2f, sig_n = 0.2f, sig_o = 0.2f, sig_e = 0.2f, sig_c = 0.2f, sig_w = 2.0f,
         cut_thred = 0.3f;
   int points_min = 10, adjacency_min = 3, voxels_min = 3;
@@ -61,6 +63,7 @@ inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>&
   clusters_points_idx = voxel_structure.getClusterIdx();
   if (descriptors) *descriptors = voxel_structure.getClusterDescriptors();
   if (graph) { graph->edges = voxel_structure.getClusterGraph(); voxel_structure.getClusterAdjacency(graph->adjacency); }
+  if (boxes) *boxes = voxel_structure.getClusterBoxes(box_frame);
   if (sum) {
     sum->points = (long)input_cloud->points.size(); sum->voxels = voxels; sum->clusters = voxel_structure.getClusterNum();
     sum->kept = (long)clusters_points_idx.size();
@@ -83,7 +86,8 @@ inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>&
 
 inline int segmentationSVGS(PCXYZPtr input_cloud, const std::vector<std::string>& input_vector,
                             std::vector<std::vector<int>>& clusters_points_idx, DriverSummary* sum = nullptr,
-                            std::vector<pcl::ClusterDescriptor>* descriptors = nullptr, DriverGraph* graph = nullptr) {
+                            std::vector<pcl::ClusterDescriptor>* descriptors = nullptr, DriverGraph* graph = nullptr,
+                            std::vector<pcl::ClusterBox>* boxes = nullptr, int box_frame = VGS_BOX_PRINCIPAL) {
   // Task_File_SVGS.txt values
   float voxel_size = 0.05f, seed_size = 0.25f, graph_size = 0.5f, sig_p = 0.2f, sig_n = 0.2f, sig_o = 0.2f, sig_e = 0.2f, sig_c = 0.2f,
         sig_w = 1.0f, sig_a = 0.0f, sig_b = 0.25f, cut_thred = 0.5f;
@@ -117,6 +121,7 @@ inline int segmentationSVGS(PCXYZPtr input_cloud, const std::vector<std::string>
   clusters_points_idx = supervoxel_structure.getClusterIdx();
   if (descriptors) *descriptors = supervoxel_structure.getClusterDescriptors();
   if (graph) { graph->edges = supervoxel_structure.getClusterGraph(); supervoxel_structure.getClusterAdjacency(graph->adjacency); }
+  if (boxes) *boxes = supervoxel_structure.getClusterBoxes(box_frame);
   if (sum) {
     sum->points = (long)input_cloud->points.size(); sum->voxels = supervoxel_structure.getVoxelNum();
     sum->supervoxels = supervoxel_structure.getSuperVoxelNum(); sum->clusters = supervoxel_structure.getClusterNum();

@@ -3,6 +3,8 @@
 // features -- doubles as %.17g, floats as %.9g, so every value reads back exactly.  One writer, so the two front ends cannot drift apart.
 // The --segment-graph CSV of the same front ends: one row per edge, ascending (a, b): a, b, n_pairs, n_finite, nodes_a, nodes_b, w_mean
 // (w_sum / n_finite, NaN without a finite weight), w_min, w_max.
+// The --segment-boxes CSV of vgs_run: one row per kept cluster, row i = cluster i: label, center (3), half (3), frame (9: [r*3+j] =
+// component r of axis j), lo (3), hi (3), every value as %.17g.
 #ifndef VGS_EXAMPLES_SEGMENTS_CSV_HPP_
 #define VGS_EXAMPLES_SEGMENTS_CSV_HPP_
 
@@ -40,6 +42,23 @@ inline int writeGraphCsv(const std::string& path, const std::vector<pcl::Cluster
     const double mean = e.n_finite > 0 ? e.w_sum / (double)e.n_finite : std::nan("");
     std::fprintf(f, "%d,%d,%lld,%lld,%d,%d,%.17g,%.9g,%.9g\n", (int)e.a, (int)e.b, (long long)e.n_pairs, (long long)e.n_finite, (int)e.nodes_a,
                  (int)e.nodes_b, mean, (double)e.w_min, (double)e.w_max);
+  }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
+inline int writeBoxesCsv(const std::string& path, const std::vector<pcl::ClusterBox>& boxes) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "label,cx,cy,cz,hx,hy,hz,w00,w01,w02,w10,w11,w12,w20,w21,w22,lo0,lo1,lo2,hi0,hi1,hi2\n");
+  for (size_t i = 0; i < boxes.size(); ++i) {
+    const pcl::ClusterBox& b = boxes[i];
+    std::fprintf(f, "%zu", i);
+    for (int a = 0; a < 3; ++a) std::fprintf(f, ",%.17g", b.center[a]);
+    for (int a = 0; a < 3; ++a) std::fprintf(f, ",%.17g", b.half[a]);
+    for (int a = 0; a < 9; ++a) std::fprintf(f, ",%.17g", b.frame[a]);
+    for (int a = 0; a < 3; ++a) std::fprintf(f, ",%.17g", b.lo[a]);
+    for (int a = 0; a < 3; ++a) std::fprintf(f, ",%.17g", b.hi[a]);
+    std::fprintf(f, "\n");
   }
   return std::fclose(f) == 0 ? 0 : -1;
 }

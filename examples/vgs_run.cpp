@@ -4,6 +4,7 @@
 // with input_vector[12]/[15] (input path / name) and [18]/[21] (output path / name), minus the viewer.
 //   usage: vgs_run <task file> [--in <file.pcd|.ply>] [--out <file.pcd>] [--seed <n>] [--ascii] [--debug-meshes <prefix>]
 //                  [--segments <file.csv>] [--segment-graph <file.csv>] [--segment-adjacency <file.txt>]
+//                  [--segment-boxes <file.csv> [--box-frame principal|upright]]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
 // --segments writes one CSV row per kept cluster (getClusterDescriptors, row i = cluster i of the output): label, n_points, n_nodes,
@@ -13,6 +14,8 @@
 // output): a, b, n_pairs, n_finite, nodes_a, nodes_b, w_mean (w_sum / n_finite, NaN without a finite weight), w_min, w_max -- doubles as
 // %.17g, floats as %.9g.  --segment-adjacency writes getClusterAdjacency (PCL's getSupervoxelAdjacency idiom: both directions of every
 // edge), one "a,b" line per multimap entry in its iteration order.
+// --segment-boxes writes one CSV row per kept cluster (getClusterBoxes, row i = cluster i of the output): label, center (3), half (3),
+// frame (9), lo (3), hi (3), every value as %.17g; --box-frame selects the frame, principal (the default) or upright.
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
 #include <cmath>
 #include <cstdio>
@@ -35,11 +38,12 @@ static int writeAdjacency(const std::string& path, const std::multimap<uint32_t,
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::fprintf(stderr, "usage: %s <task file> [--in file.pcd] [--out file.pcd] [--seed n] [--ascii] [--debug-meshes prefix] [--segments file.csv] "
-                 "[--segment-graph file.csv] [--segment-adjacency file.txt]\n",
+                 "[--segment-graph file.csv] [--segment-adjacency file.txt] [--segment-boxes file.csv [--box-frame principal|upright]]\n",
                  argv[0]);
     return 2;
   }
-  std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file;
+  std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file, boxes_file;
+  int box_frame = VGS_BOX_PRINCIPAL;
   uint64_t seed = 0;
   bool ascii = false;
   for (int a = 2; a < argc; ++a) {
@@ -51,6 +55,13 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--segments") && a + 1 < argc) segments_file = argv[++a];
     else if (!std::strcmp(argv[a], "--segment-graph") && a + 1 < argc) graph_file = argv[++a];
     else if (!std::strcmp(argv[a], "--segment-adjacency") && a + 1 < argc) adjacency_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--segment-boxes") && a + 1 < argc) boxes_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--box-frame") && a + 1 < argc) {
+      ++a;
+      if (!std::strcmp(argv[a], "principal")) box_frame = VGS_BOX_PRINCIPAL;
+      else if (!std::strcmp(argv[a], "upright")) box_frame = VGS_BOX_UPRIGHT;
+      else { std::fprintf(stderr, "--box-frame %s: principal or upright\n", argv[a]); return 2; }
+    }
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
   const std::vector<std::string> task = inputTaskTxtFile(argv[1]);
@@ -73,11 +84,13 @@ int main(int argc, char** argv) {
   std::vector<pcl::ClusterDescriptor>* want = segments_file.empty() ? nullptr : &desc;
   DriverGraph graph;
   DriverGraph* want_graph = (graph_file.empty() && adjacency_file.empty()) ? nullptr : &graph;
+  std::vector<pcl::ClusterBox> boxes;
+  std::vector<pcl::ClusterBox>* want_boxes = boxes_file.empty() ? nullptr : &boxes;
   try {
     if (method == 2) {
-      if (segmentationVGS(cloud, task, clusters, &sum, debug_prefix, 0.0, want, want_graph) != 0) { std::fprintf(stderr, "cannot write the debug meshes\n"); return 1; }
+      if (segmentationVGS(cloud, task, clusters, &sum, debug_prefix, 0.0, want, want_graph, want_boxes, box_frame) != 0) { std::fprintf(stderr, "cannot write the debug meshes\n"); return 1; }
     } else {
-      segmentationSVGS(cloud, task, clusters, &sum, want, want_graph);
+      segmentationSVGS(cloud, task, clusters, &sum, want, want_graph, want_boxes, box_frame);
     }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "error: %s\n", e.what());
@@ -86,6 +99,7 @@ int main(int argc, char** argv) {
   if (saveColoredClusters(out_file, cloud, clusters, seed, !ascii) != 0) return 1;
   if (want && writeSegmentsCsv(segments_file, desc) != 0) { std::fprintf(stderr, "cannot write %s\n", segments_file.c_str()); return 1; }
   if (!graph_file.empty() && writeGraphCsv(graph_file, graph.edges) != 0) { std::fprintf(stderr, "cannot write %s\n", graph_file.c_str()); return 1; }
+  if (want_boxes && writeBoxesCsv(boxes_file, boxes) != 0) { std::fprintf(stderr, "cannot write %s\n", boxes_file.c_str()); return 1; }
   if (!adjacency_file.empty() && writeAdjacency(adjacency_file, graph.adjacency) != 0) {
     std::fprintf(stderr, "cannot write %s\n", adjacency_file.c_str());
     return 1;

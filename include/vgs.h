@@ -247,6 +247,30 @@ vgs_status vgs_get_own_segment_moments(vgs_ctx* ctx, int64_t K, int64_t* n_recor
 vgs_status vgs_segment_descriptors_from_moments(vgs_ctx* ctx, int64_t K, const int64_t* n_points, const int32_t* n_nodes, const float* bbox6,
                                                 const float* anchor3, const double* s9, int64_t* n_points_out, int32_t* n_nodes_out,
                                                 float* bbox6_out, double* centroid3, double* cov6, double* evals3, double* evecs9, float* eigen8);
+/* Oriented bounding boxes of the kept segments (no reference counterpart: the size of a segment along its own axes; the principal frame is
+ * the PCA box of pcl::MomentOfInertiaEstimation::getOBB).  Row k describes exactly the points whose label is k, K = counts[VGS_N_KEPT]
+ * rows; every array is K rows of doubles and any pointer may be NULL.  With c the centroid3 row of vgs_get_segment_descriptors, W the
+ * frame ([r*3+j] = component r of axis j, evecs9's layout), d = p - c in fp64 and t_j(p) = (W[0][j] dx + W[1][j] dy) + W[2][j] dz:
+ *   center3    c[r] + ((W[r][0] mid[0] + W[r][1] mid[1]) + W[r][2] mid[2]), mid = (lo + hi) / 2: the centre of the box
+ *   half3      (hi - lo) / 2: the half extent along axis j
+ *   frame9     W as used
+ *   lo3, hi3   min and max of t_j over the points of the segment (a bound that is zero may carry either sign, as in bbox6)
+ * frame selects W:
+ *   VGS_BOX_PRINCIPAL  the evecs9 row of the descriptor table, byte for byte: axis 0 the normal, axis 2 the major axis
+ *   VGS_BOX_UPRIGHT    axis 2 = (0, 0, 1) exactly; axes 0 and 1 the eigenvectors of the block (xx, xy; xy, yy) of cov6 -- one Jacobi
+ *                      rotation in fp64 -- by ascending eigenvalue (axis 0 minor, axis 1 major; xy = 0 with xx <= yy gives the identity),
+ *                      each with evecs9's sign rule and a z component of exactly 0
+ * Every product and sum above is a single fp64 operation in the association written (no FMA) and min / max do not depend on the order, so
+ * lo3, hi3, half3 and center3 are an exact function of the float points, c and W: bit-identical from call to call and engine to engine.  A
+ * segment of one point gives lo = hi = half = 0 and center = that point.  Computed on the device on the first request after a run (the
+ * descriptor table first, if it is not cached; then a second pass over the points) and cached per frame until the next run; both frames
+ * may be cached at once.  frame9 is the table's own copy: vgs_segment_descriptors_from_moments does not change a cached box table.
+ * VGS_E_ARG for another frame value; VGS_E_STATE before the context is segmented and for a tile context; K = 0 writes nothing. */
+enum { VGS_BOX_PRINCIPAL = 0, VGS_BOX_UPRIGHT = 1 };
+vgs_status vgs_get_segment_boxes(vgs_ctx* ctx, int32_t frame, double* center3, double* half3, double* frame9, double* lo3, double* hi3);
+/* the same table left in HBM: device pointers (any may be NULL), valid until the next run of the stages */
+vgs_status vgs_get_segment_boxes_device(vgs_ctx* ctx, int32_t frame, const double** center3, const double** half3, const double** frame9,
+                                        const double** lo3, const double** hi3);
 /* Segment adjacency graph (no reference counterpart: which kept segments touch, and how strongly the local cut's weight links them).
  *   A node is a voxel (VGS) or a supervoxel (SVGS).  Only used nodes with a kept label >= 0 take part; unused voxels and the nodes of
  *   clusters dropped by the size filter are ignored.

@@ -129,6 +129,30 @@ inline std::vector<ClusterDescriptor> cluster_descriptors(vgs_ctx* c, int64_t k)
 }
 }  // namespace vgs_detail
 
+// Extension (no VS / SS line): the oriented bounding box of one kept cluster, as vgs_get_segment_boxes (include/vgs.h) defines it
+struct ClusterBox {
+  double center[3] = {0, 0, 0};   // centre of the box
+  double half[3] = {0, 0, 0};     // half extent along axis j
+  double frame[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // [r*3+j] = component r of axis j
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};     // min and max of the projections of (p - centroid) onto axis j
+};
+
+namespace vgs_detail {
+// one row per kept cluster, in label order -- the order of getClusterIdx
+inline std::vector<ClusterBox> cluster_boxes(vgs_ctx* c, int64_t k, int frame) {
+  std::vector<ClusterBox> out((size_t)k);
+  std::vector<double> ce((size_t)k * 3 + 1), ha((size_t)k * 3 + 1), fr((size_t)k * 9 + 1), lo((size_t)k * 3 + 1), hi((size_t)k * 3 + 1);
+  // (called for k = 0 too: the state and frame checks are the library's)
+  check(c, vgs_get_segment_boxes(c, (int32_t)frame, ce.data(), ha.data(), fr.data(), lo.data(), hi.data()), "vgs_get_segment_boxes");
+  for (size_t i = 0; i < (size_t)k; ++i) {
+    ClusterBox& b = out[i];
+    for (int a = 0; a < 3; ++a) { b.center[a] = ce[3 * i + a]; b.half[a] = ha[3 * i + a]; b.lo[a] = lo[3 * i + a]; b.hi[a] = hi[3 * i + a]; }
+    for (int a = 0; a < 9; ++a) b.frame[a] = fr[9 * i + a];
+  }
+  return out;
+}
+}  // namespace vgs_detail
+
 // Extension (no VS / SS line): one edge of the adjacency graph of the kept clusters, as vgs_get_segment_graph (include/vgs.h) defines it
 struct ClusterEdge {
   int32_t a = 0, b = 0;        // cluster indices (getClusterIdx order), a < b
@@ -284,6 +308,11 @@ class VoxelBasedSegmentation {
     if (!drawn_) return {};
     return vgs_detail::cluster_descriptors(ctx(), count(VGS_N_KEPT));
   }
+  // Extension (no VS line): box i bounds getClusterIdx()[i]; empty before drawColorMapofPointsinClusters, like getClusterDescriptors
+  std::vector<ClusterBox> getClusterBoxes(int frame = VGS_BOX_PRINCIPAL) {
+    if (!drawn_) return {};
+    return vgs_detail::cluster_boxes(ctx(), count(VGS_N_KEPT), frame);
+  }
   // Extension (no VS line): the adjacency graph of the kept clusters, indices as getClusterIdx; empty before drawColorMapofPointsinClusters
   std::vector<ClusterEdge> getClusterGraph() {
     if (!drawn_) return {};
@@ -383,6 +412,8 @@ class SuperVoxelBasedSegmentation {
   }
   // Extension (no SS line): descriptor i describes getClusterIdx()[i]
   std::vector<ClusterDescriptor> getClusterDescriptors() { return vgs_detail::cluster_descriptors(ctx(), count(VGS_N_KEPT)); }
+  // Extension (no SS line): box i bounds getClusterIdx()[i]
+  std::vector<ClusterBox> getClusterBoxes(int frame = VGS_BOX_PRINCIPAL) { return vgs_detail::cluster_boxes(ctx(), count(VGS_N_KEPT), frame); }
   // Extension (no SS line): the adjacency graph of the kept clusters, indices as getClusterIdx
   std::vector<ClusterEdge> getClusterGraph() { return vgs_detail::cluster_graph(ctx()); }
   // Extension (no SS line): PCL's getSupervoxelAdjacency idiom over getClusterGraph -- both directions of every edge

@@ -278,6 +278,30 @@ class Engine:
         self._ck(self._L.vgs_get_segment_descriptors_device(self._h, *(C.byref(p) for p in ps)))
         return {name: p.value for (name, _, _), p in zip(self.DESCRIPTOR_FIELDS, ps)}
 
+    # per segment: (field, dtype, values per segment) of vgs_get_segment_boxes, in its argument order; BOX_FRAMES: its frame argument
+    BOX_FIELDS = (("center3", np.float64, 3), ("half3", np.float64, 3), ("frame9", np.float64, 9), ("lo3", np.float64, 3),
+                  ("hi3", np.float64, 3))
+    BOX_FRAMES = {"principal": 0, "upright": 1}
+
+    def _box_frame(self, frame):
+        return int(self.BOX_FRAMES.get(frame, frame))   # (a name, or the C value: another one is the library's VGS_E_ARG)
+
+    def segment_boxes(self, frame="principal"):
+        """Oriented bounding boxes of the kept segments, row k = the points labelled k (include/vgs.h, vgs_get_segment_boxes): a dict of
+        float64 arrays center3 (K, 3), half3 (K, 3), frame9 (K, 9: [r*3+j] = component r of axis j), lo3 (K, 3), hi3 (K, 3).
+        frame="principal": the segment's PCA axes (evecs9 of segment_descriptors); "upright": z stays z, the horizontal axes are the PCA
+        of the xy covariance.  Computed on the device, cached per frame until the next run."""
+        K = self.counts()["kept"]
+        out = {name: np.zeros((K, w), dtype=dt) for name, dt, w in self.BOX_FIELDS}
+        self._ck(self._L.vgs_get_segment_boxes(self._h, self._box_frame(frame), *(_ptr(out[name]) for name, _, _ in self.BOX_FIELDS)))
+        return out
+
+    def segment_boxes_device(self, frame="principal"):
+        """The same table left in HBM: {field: device pointer}, valid until the next run."""
+        ps = [C.c_void_p() for _ in self.BOX_FIELDS]
+        self._ck(self._L.vgs_get_segment_boxes_device(self._h, self._box_frame(frame), *(C.byref(p) for p in ps)))
+        return {name: p.value for (name, _, _), p in zip(self.BOX_FIELDS, ps)}
+
     # per edge: (field, dtype, values per edge) of vgs_get_segment_graph, in its argument order
     GRAPH_FIELDS = (("seg_ab", np.int32, 2), ("n_pairs", np.int64, 1), ("n_finite", np.int64, 1), ("nodes_ab", np.int32, 2),
                     ("w_sum", np.float64, 1), ("w_min", np.float32, 1), ("w_max", np.float32, 1))
@@ -415,6 +439,12 @@ class VoxelBasedSegmentation:
             return {name: np.zeros((0, w) if w > 1 else 0, dtype=dt) for name, dt, w in Engine.DESCRIPTOR_FIELDS}
         return self._eng.segment_descriptors()
 
+    def getClusterBoxes(self, frame="principal"):
+        """Extension (no VS line): box i bounds getClusterIdx()[i] -- both are in label order (Engine.segment_boxes)."""
+        if not self._drawn:
+            return {name: np.zeros((0, w), dtype=dt) for name, dt, w in Engine.BOX_FIELDS}
+        return self._eng.segment_boxes(frame)
+
     def getClusterGraph(self):
         """Extension (no VS line): the adjacency graph of the kept clusters, labels = getClusterIdx() indices (Engine.segment_graph)."""
         if not self._drawn:
@@ -496,6 +526,10 @@ class SuperVoxelBasedSegmentation:
     def getClusterDescriptors(self):
         """Extension (no SS line): descriptor i describes getClusterIdx()[i] -- both are in label order (Engine.segment_descriptors)."""
         return self._eng.segment_descriptors()
+
+    def getClusterBoxes(self, frame="principal"):
+        """Extension (no SS line): box i bounds getClusterIdx()[i] -- both are in label order (Engine.segment_boxes)."""
+        return self._eng.segment_boxes(frame)
 
     def getClusterGraph(self):
         """Extension (no SS line): the adjacency graph of the kept clusters, labels = getClusterIdx() indices (Engine.segment_graph)."""

@@ -475,6 +475,7 @@ extern "C" vgs_status vgs_get_local_weights(vgs_ctx* c, int32_t node_id, int32_t
 vgs_status vgs_stage_merge(vgs_ctx* c) {
   c->cl_valid = false;   // (clusters.hip: the cluster lists on the device belong to the labels of the last run)
   c->sd_valid = false;   // (segdesc.hip: so do the segment descriptors)
+  c->sb_valid[0] = c->sb_valid[1] = false;   // (segbox.hip: and the oriented boxes)
   c->sg_valid = false; c->sg_halo_valid = false; c->sg_own_K = -1;   // (seggraph.hip: and the segment graph)
   const int64_t V = c->V, U = c->U, N = c->N;
   c->bnd_unique = -1;  // tile protocol results belong to the previous segmentation

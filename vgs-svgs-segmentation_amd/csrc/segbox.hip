@@ -1,0 +1,265 @@
+// segbox.hip -- oriented bounding boxes of the kept segments (no reference counterpart: the size of a segment along its own axes, what
+// pcl::MomentOfInertiaEstimation::getOBB gives for one cluster).  Row k covers exactly the points whose label is k.  Two frames:
+//   VGS_BOX_PRINCIPAL  the segment's PCA axes, the evecs9 row of the descriptor table byte for byte
+//   VGS_BOX_UPRIGHT    axis 2 = (0, 0, 1); axes 0 and 1 the eigenvectors of the xy block of the descriptor's cov6 (one Jacobi rotation in fp64,
+//                      sd_jacobi_rotate's formulae), ascending eigenvalue, evecs9's sign rule
+// The extents are min / max of projections onto axes that the descriptor pass produces, so they are a second pass over the points.
+// Data flow: the descriptor table first (vgs_segdesc_on_device: centroid3, evecs9, cov6), k_sb_frames writes the frame of every segment
+// into the box table's own buffer, sd_prepare gives the decomposition of segdesc.hip (nodes sorted by label, virtual positions, chunks of
+// SD_CHUNK virtual points that never cross a segment and may split a node), then
+//   k_sb_chunks  one workgroup per chunk: t_j = (W[0][j] dx + W[1][j] dy) + W[2][j] dz for d = p - c in fp64, per-lane min / max, wavefront
+//                butterfly, the waves through LDS, one partial of SB_REC doubles
+//   k_sb_final   one wavefront per segment folds its partials and writes lo3, hi3, half3 = (hi - lo) / 2 and
+//                center3[r] = c[r] + ((W[r][0] mid[0] + W[r][1] mid[1]) + W[r][2] mid[2]), mid = (lo + hi) / 2
+// Exact arithmetic: every product and sum above is one IEEE fp64 operation in the stated association (the build passes
+// -ffp-contract=off: no FMA), and min / max do not depend on the order, so the table is a function of the points, c and W alone -- a
+// float64 restatement reproduces it to the bit (tests/segment_boxes_ref.py).  A zero bound may carry either sign, as in bbox6.
+// No atomics.  The chunk kernel takes c and W as arrays per label, so a rank of the tiled driver could run it over its own points about a
+// centroid and frame handed in.  Scratch: sb_part and the sd_* scratch of sd_prepare, nothing a getter reads.  Cached per frame until the
+// next run (sb_valid[frame]); vgs_segment_descriptors_from_moments may overwrite the descriptor buffers afterwards, the box table keeps
+// the frame its extents were taken in.
+#include <string.h>
+
+#include "vgs_context.hpp"
+
+#define SB_REC 6   // doubles per partial record: min t[3], max t[3]
+
+// The frame of segment k.  Principal: the evecs9 row.  Upright: see the header.  One thread per segment.
+__global__ __launch_bounds__(256) void k_sb_frames(const double* __restrict__ evec, const double* __restrict__ cov, uint32_t K, int upright,
+                                                   double* __restrict__ frame) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K) return;
+  double* o = frame + (size_t)k * 9;
+  if (!upright) {
+#pragma unroll
+    for (int f = 0; f < 9; ++f) o[f] = evec[(size_t)k * 9 + f];
+    return;
+  }
+  // one Jacobi rotation that zeroes A[0][1] of the xy block (sd_jacobi_rotate<0, 1> without the third index): A' = J^T A J, W' = W J
+  double a00 = cov[(size_t)k * 6 + 0], a11 = cov[(size_t)k * 6 + 3];
+  const double apq = cov[(size_t)k * 6 + 1];
+  double W[2][2] = {{1, 0}, {0, 1}};
+  if (apq != 0.0) {
+    const double theta = (a11 - a00) / (2.0 * apq);
+    const double t = fabs(theta) > 1e150 ? 0.5 / theta : (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+    a00 -= t * apq;
+    a11 += t * apq;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const double wp = W[i][0], wq = W[i][1];
+      W[i][0] = cs * wp - sn * wq;
+      W[i][1] = sn * wp + cs * wq;
+    }
+  }
+  if (a00 > a11) {   // ascending eigenvalue: axis 0 minor, axis 1 major (strictly greater only: xy = 0 with xx <= yy stays the identity)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { const double u = W[i][0]; W[i][0] = W[i][1]; W[i][1] = u; }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    // sign: the component of largest magnitude is positive (lowest index on a tie); the z component is 0 and stays +0
+    double best = W[0][j];
+    if (fabs(W[1][j]) > fabs(best)) best = W[1][j];
+    if (best < 0.0) { W[0][j] = -W[0][j]; W[1][j] = -W[1][j]; }
+  }
+  o[0] = W[0][0]; o[1] = W[0][1]; o[2] = 0.0;
+  o[3] = W[1][0]; o[4] = W[1][1]; o[5] = 0.0;
+  o[6] = 0.0;     o[7] = 0.0;     o[8] = 1.0;
+}
+
+__device__ __forceinline__ double sb_wave_min(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x = fmin(x, __shfl_xor(x, m, 64));
+  return x;
+}
+__device__ __forceinline__ double sb_wave_max(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x = fmax(x, __shfl_xor(x, m, 64));
+  return x;
+}
+
+// Empty partial record: +inf min, -inf max
+__device__ __forceinline__ void sb_empty_record(double* __restrict__ rec) {
+  if (threadIdx.x < SB_REC) rec[threadIdx.x] = threadIdx.x < 3 ? __builtin_huge_val() : -__builtin_huge_val();
+}
+
+// One workgroup per chunk of SD_CHUNK virtual points of one segment: the chunk -> segment -> nodes walk of segdesc.hip's sd_chunk_body
+// (same staging arrays, same point of every lane and step), the projections of the header, one partial record.  Grid: the bound of
+// sd_prepare; workgroups past the real number of chunks leave at once.  cen / frame: 3 and 9 doubles per label.
+__global__ __launch_bounds__(SD_TB) void k_sb_chunks(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                     const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                     const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                     const uint32_t* __restrict__ seg_chunk, uint32_t K, const double* __restrict__ cen,
+                                                     const double* __restrict__ frame, double* __restrict__ part) {
+  __shared__ uint32_t s_vp[SD_CHUNK];    // virtual start of the chunk's nodes
+  __shared__ uint32_t s_dl[SD_CHUNK];    // sorted position - virtual position of the same (mod 2^32)
+  __shared__ double s_red[SD_TB / 64][SB_REC];
+  const uint32_t c = blockIdx.x;
+  if (c >= seg_chunk[K]) return;
+  // segment of chunk c: the last k with seg_chunk[k] <= c (every segment has at least one chunk)
+  uint32_t lo = 0, hi = K - 1;
+  while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (seg_chunk[mid] <= c) lo = mid; else hi = mid - 1; }
+  const uint32_t k = lo;
+  const uint32_t n0 = seg_node[k], n1 = seg_node[k + 1];
+  const uint32_t a = vp[n0] + (c - seg_chunk[k]) * SD_CHUNK;
+  const uint32_t b = min(a + SD_CHUNK, vp[n1]);
+  if (n1 <= n0 || a >= b) {   // (cannot happen for a kept segment; an empty record keeps the fold well defined)
+    sb_empty_record(part + (size_t)c * SB_REC);
+    return;
+  }
+  // nodes that overlap [a, b): the last node starting at or before a ... the last node starting before b; at most b - a <= SD_CHUNK nodes
+  uint32_t i0 = n0, i1 = n1 - 1;
+  while (i0 < i1) { const uint32_t mid = (i0 + i1 + 1) >> 1; if (vp[mid] <= a) i0 = mid; else i1 = mid - 1; }
+  uint32_t j0 = i0 + 1, j1 = n1;
+  while (j0 < j1) { const uint32_t mid = (j0 + j1) >> 1; if (vp[mid] < b) j0 = mid + 1; else j1 = mid; }
+  const uint32_t m = min(j0 - i0, (uint32_t)SD_CHUNK);   // (the bound above; the clamp only guards the LDS arrays)
+  for (uint32_t t = threadIdx.x; t < m; t += SD_TB) {
+    const uint32_t i = i0 + t, q = vp[i];
+    s_vp[t] = q;
+    s_dl[t] = vox_start[ids[i]] - q;
+  }
+  const double* cc = cen + (size_t)k * 3;
+  const double* ww = frame + (size_t)k * 9;
+  const double cx = cc[0], cy = cc[1], cz = cc[2];
+  const double w00 = ww[0], w01 = ww[1], w02 = ww[2], w10 = ww[3], w11 = ww[4], w12 = ww[5], w20 = ww[6], w21 = ww[7], w22 = ww[8];
+  __syncthreads();
+  double mn0 = __builtin_huge_val(), mn1 = __builtin_huge_val(), mn2 = __builtin_huge_val();
+  double mx0 = -__builtin_huge_val(), mx1 = -__builtin_huge_val(), mx2 = -__builtin_huge_val();
+#pragma unroll 2
+  for (int it = 0; it < SD_PPT; ++it) {
+    const uint32_t q = a + (uint32_t)it * SD_TB + threadIdx.x;
+    if (q < b) {
+      uint32_t l = 0, h = m - 1;   // the last node of the chunk that starts at or before q
+      while (l < h) { const uint32_t mid = (l + h + 1) >> 1; if (s_vp[mid] <= q) l = mid; else h = mid - 1; }
+      const uint32_t pos = q + s_dl[l];
+      // exact differences (a float against a double), then one fp64 operation per product and sum, in this association
+      const double dx = (double)xs[pos] - cx, dy = (double)ys[pos] - cy, dz = (double)zs[pos] - cz;
+      const double t0 = (w00 * dx + w10 * dy) + w20 * dz;
+      const double t1 = (w01 * dx + w11 * dy) + w21 * dz;
+      const double t2 = (w02 * dx + w12 * dy) + w22 * dz;
+      mn0 = fmin(mn0, t0); mn1 = fmin(mn1, t1); mn2 = fmin(mn2, t2);
+      mx0 = fmax(mx0, t0); mx1 = fmax(mx1, t1); mx2 = fmax(mx2, t2);
+    }
+  }
+  mn0 = sb_wave_min(mn0); mn1 = sb_wave_min(mn1); mn2 = sb_wave_min(mn2);
+  mx0 = sb_wave_max(mx0); mx1 = sb_wave_max(mx1); mx2 = sb_wave_max(mx2);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    double* r = s_red[w];
+    r[0] = mn0; r[1] = mn1; r[2] = mn2; r[3] = mx0; r[4] = mx1; r[5] = mx2;
+  }
+  __syncthreads();
+  if (threadIdx.x < SB_REC) {   // the waves in index order
+    const int f = threadIdx.x;
+    double v = s_red[0][f];
+    if (f < 3) { for (int u = 1; u < SD_TB / 64; ++u) v = fmin(v, s_red[u][f]); }
+    else { for (int u = 1; u < SD_TB / 64; ++u) v = fmax(v, s_red[u][f]); }
+    part[(size_t)c * SB_REC + f] = v;
+  }
+}
+
+// one wavefront per segment: fold its partials (lane stride, then butterfly), then the row on lane 0
+__global__ __launch_bounds__(256) void k_sb_final(const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part, uint32_t n_part, uint32_t K,
+                                                  const double* __restrict__ cen, const double* __restrict__ frame, double* __restrict__ o_lo,
+                                                  double* __restrict__ o_hi, double* __restrict__ o_half, double* __restrict__ o_center) {
+  const uint32_t k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (k >= K) return;   // (whole wavefronts; no barrier follows)
+  const uint32_t c0 = seg_chunk[k], c1 = min(seg_chunk[k + 1], n_part);   // (the bound only guards the records: the chunks fit, see the launch)
+  double mn[3], mx[3];
+#pragma unroll
+  for (int f = 0; f < 3; ++f) { mn[f] = __builtin_huge_val(); mx[f] = -__builtin_huge_val(); }
+  for (uint32_t c = c0 + lane; c < c1; c += 64) {
+    const double* r = part + (size_t)c * SB_REC;
+#pragma unroll
+    for (int f = 0; f < 3; ++f) { mn[f] = fmin(mn[f], r[f]); mx[f] = fmax(mx[f], r[3 + f]); }
+  }
+#pragma unroll
+  for (int f = 0; f < 3; ++f) { mn[f] = sb_wave_min(mn[f]); mx[f] = sb_wave_max(mx[f]); }
+  if (lane != 0) return;
+  const double* W = frame + (size_t)k * 9;
+  double mid[3];
+#pragma unroll
+  for (int f = 0; f < 3; ++f) {
+    o_lo[3 * (size_t)k + f] = mn[f];
+    o_hi[3 * (size_t)k + f] = mx[f];
+    o_half[3 * (size_t)k + f] = (mx[f] - mn[f]) * 0.5;
+    mid[f] = (mn[f] + mx[f]) * 0.5;
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    o_center[3 * (size_t)k + r] = cen[3 * (size_t)k + r] + ((W[3 * r + 0] * mid[0] + W[3 * r + 1] * mid[1]) + W[3 * r + 2] * mid[2]);
+}
+
+static bool vgs_is_tile(const vgs_ctx* c) { return c->have_region || c->n_own >= 0; }
+
+// The table of one frame in HBM, K = counts[VGS_N_KEPT] rows; valid until the next run of the stages.
+vgs_status vgs_segbox_on_device(vgs_ctx* c, int frame) {
+  if (c->sb_valid[frame]) return VGS_OK;
+  vgs_status s = vgs_segdesc_on_device(c);   // centroid3, evecs9, cov6
+  if (s != VGS_OK) return s;
+  const int64_t K = c->counts[VGS_N_KEPT], V = c->V, nf = c->Nf;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  const size_t k1 = (size_t)(K > 0 ? K : 1);
+  VGS_HIP_TRY(c, c->sb_frame[frame].ensure(9 * k1));
+  VGS_HIP_TRY(c, c->sb_lo[frame].ensure(3 * k1)); VGS_HIP_TRY(c, c->sb_hi[frame].ensure(3 * k1));
+  VGS_HIP_TRY(c, c->sb_half[frame].ensure(3 * k1)); VGS_HIP_TRY(c, c->sb_center[frame].ensure(3 * k1));
+  if (K == 0 || V == 0 || nf == 0) { c->sb_valid[frame] = true; return VGS_OK; }
+  SdPrep P;
+  if ((s = sd_prepare(c, K, P)) != VGS_OK) return s;
+  VGS_HIP_TRY(c, c->sb_part.ensure((size_t)P.n_chunks_max * SB_REC));
+  hipLaunchKernelGGL(k_sb_frames, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, c->sd_evec.p, c->sd_cov.p, (uint32_t)K,
+                     frame == VGS_BOX_UPRIGHT ? 1 : 0, c->sb_frame[frame].p);
+  hipLaunchKernelGGL(k_sb_chunks, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, P.ids, P.vp,
+                     P.seg_node, P.seg_chunk, (uint32_t)K, c->sd_cen.p, c->sb_frame[frame].p, c->sb_part.p);
+  hipLaunchKernelGGL(k_sb_final, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, P.seg_chunk, c->sb_part.p, (uint32_t)P.n_chunks_max,
+                     (uint32_t)K, c->sd_cen.p, c->sb_frame[frame].p, c->sb_lo[frame].p, c->sb_hi[frame].p, c->sb_half[frame].p,
+                     c->sb_center[frame].p);
+  VGS_HIP_TRY(c, hipGetLastError());
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->sb_valid[frame] = true;
+  return VGS_OK;
+}
+
+static vgs_status sb_check(vgs_ctx* c, int32_t frame, const char* fn) {
+  if (frame != VGS_BOX_PRINCIPAL && frame != VGS_BOX_UPRIGHT) {
+    c->err = std::string(fn) + ": frame must be VGS_BOX_PRINCIPAL (0) or VGS_BOX_UPRIGHT (1)";
+    return VGS_E_ARG;
+  }
+  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
+  if (vgs_is_tile(c)) {
+    c->err = std::string(fn) + ": a tile context (owned region / own point range) holds only part of its segments; boxes need the whole cloud in one context";
+    return VGS_E_STATE;
+  }
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_get_segment_boxes(vgs_ctx* c, int32_t frame, double* center3, double* half3, double* frame9, double* lo3, double* hi3) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = sb_check(c, frame, "vgs_get_segment_boxes");
+  if (s != VGS_OK) return s;
+  const size_t K = (size_t)c->counts[VGS_N_KEPT];
+  if (K == 0) return VGS_OK;
+  if ((s = vgs_segbox_on_device(c, frame)) != VGS_OK) return s;
+  if (center3) VGS_HIP_TRY(c, hipMemcpy(center3, c->sb_center[frame].p, 3 * K * sizeof(double), hipMemcpyDeviceToHost));
+  if (half3) VGS_HIP_TRY(c, hipMemcpy(half3, c->sb_half[frame].p, 3 * K * sizeof(double), hipMemcpyDeviceToHost));
+  if (frame9) VGS_HIP_TRY(c, hipMemcpy(frame9, c->sb_frame[frame].p, 9 * K * sizeof(double), hipMemcpyDeviceToHost));
+  if (lo3) VGS_HIP_TRY(c, hipMemcpy(lo3, c->sb_lo[frame].p, 3 * K * sizeof(double), hipMemcpyDeviceToHost));
+  if (hi3) VGS_HIP_TRY(c, hipMemcpy(hi3, c->sb_hi[frame].p, 3 * K * sizeof(double), hipMemcpyDeviceToHost));
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_get_segment_boxes_device(vgs_ctx* c, int32_t frame, const double** center3, const double** half3, const double** frame9,
+                                                   const double** lo3, const double** hi3) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = sb_check(c, frame, "vgs_get_segment_boxes_device");
+  if (s != VGS_OK) return s;
+  if ((s = vgs_segbox_on_device(c, frame)) != VGS_OK) return s;
+  if (center3) *center3 = c->sb_center[frame].p;
+  if (half3) *half3 = c->sb_half[frame].p;
+  if (frame9) *frame9 = c->sb_frame[frame].p;
+  if (lo3) *lo3 = c->sb_lo[frame].p;
+  if (hi3) *hi3 = c->sb_hi[frame].p;
+  return VGS_OK;
+}

@@ -27,9 +27,7 @@
 
 #include "vgs_context.hpp"
 
-#define SD_TB 256                   // threads of a chunk workgroup
-#define SD_PPT 8                    // points per thread of a chunk
-#define SD_CHUNK (SD_TB * SD_PPT)   // virtual points per chunk
+// SD_TB threads of a chunk workgroup, SD_PPT points per thread, SD_CHUNK = SD_TB * SD_PPT virtual points per chunk: vgs_context.hpp
 #define SD_REC 16                   // doubles per partial record: sum d[3], sum dd^T[6] (xx xy xz yy yz zz), min[3], max[3], (pad)
 
 // key of node v: its kept label, K for the nodes of dropped clusters (they sort behind every kept segment; so would a label >= K)
@@ -420,10 +418,8 @@ __global__ __launch_bounds__(256) void k_sd_algebra(const double* __restrict__ m
 static bool vgs_is_tile(const vgs_ctx* c) { return c->have_region || c->n_own >= 0; }
 
 // Steps 1-2 for labels 0 .. K-1 and the launch of step 3's grid bound: sorted node ids, virtual positions, per segment its first sorted
-// node and first chunk.  Pointers into the sd_* scratch.
-struct SdPrep { uint32_t *ids, *vp, *seg_node, *seg_chunk; int64_t n_chunks_max; };
-
-static vgs_status sd_prepare(vgs_ctx* c, int64_t K, SdPrep& o) {
+// node and first chunk.  Pointers into the sd_* scratch.  (SdPrep: vgs_context.hpp; segbox.hip runs the same steps.)
+vgs_status sd_prepare(vgs_ctx* c, int64_t K, SdPrep& o) {
   const int64_t V = c->V, nf = c->Nf;
   VGS_HIP_TRY(c, c->sd_key.ensure(2 * (size_t)V)); VGS_HIP_TRY(c, c->sd_ids.ensure(2 * (size_t)V));
   VGS_HIP_TRY(c, c->sd_vp.ensure(2 * ((size_t)V + 1)));

@@ -266,6 +266,11 @@ struct vgs_ctx {
   DevBuf<float> sd_bbox, sd_eig8;
   DevBuf<double> sd_cen, sd_cov, sd_eval, sd_evec;
   bool sd_valid = false;
+  // oriented boxes of the kept segments (segbox.hip), one table per frame (VGS_BOX_PRINCIPAL, VGS_BOX_UPRIGHT): computed on request, valid
+  // until the next run (sb_valid[frame]); the frame the extents were taken in is the table's own copy, and the chunk partials its own scratch
+  DevBuf<double> sb_part;
+  DevBuf<double> sb_frame[2], sb_lo[2], sb_hi[2], sb_half[2], sb_center[2];
+  bool sb_valid[2] = {false, false};
   // tile contexts (vgs_get_own_segment_moments / vgs_segment_descriptors_from_moments): first own point per segment, moment records
   DevBuf<uint32_t> sd_apos;
   DevBuf<double> sd_mom;
@@ -394,6 +399,15 @@ static inline vgs_status vgs_readback_end(vgs_ctx* c, void* dst, size_t bytes) {
 }
 static inline bool vgs_can_split_readback(const vgs_ctx* c) { return c->pin != nullptr && c->ev_rb != nullptr; }
 
+// The decomposition of the per-segment passes (segdesc.hip, segbox.hip): chunks of SD_CHUNK virtual points that never cross a segment.
+// sd_prepare (segdesc.hip) runs steps 1-2 of segdesc.hip's header for labels 0 .. K-1 -- sorted node ids, virtual positions, per segment
+// its first sorted node and first chunk, pointers into the sd_* scratch -- and gives the grid bound of the chunk kernels.
+#define SD_TB 256                   // threads of a chunk workgroup
+#define SD_PPT 8                    // points per thread of a chunk
+#define SD_CHUNK (SD_TB * SD_PPT)   // virtual points per chunk
+struct SdPrep { uint32_t *ids, *vp, *seg_node, *seg_chunk; int64_t n_chunks_max; };
+vgs_status sd_prepare(vgs_ctx* c, int64_t K, SdPrep& o);
+
 vgs_status vgs_cut_order(vgs_ctx* c, std::vector<uint16_t>& ord_host, std::vector<uint32_t>& k_host, bool want_lists = false,
                          const uint8_t* list_flag = nullptr, std::vector<uint32_t>* list_cnt = nullptr, std::vector<int32_t>* list_ids = nullptr);   // cutorder.hip
 void vgs_read_env_knobs(vgs_ctx* c);   // capi.hip; called by vgs_create only
@@ -416,6 +430,7 @@ vgs_status vgs_localcut_finish(vgs_ctx* c, unsigned int* n_deferred);  // waits 
 vgs_status vgs_stage_merge(vgs_ctx* c);
 vgs_status vgs_clusters_on_device(vgs_ctx* c);   // clusters.hip
 vgs_status vgs_segdesc_on_device(vgs_ctx* c);    // segdesc.hip
+vgs_status vgs_segbox_on_device(vgs_ctx* c, int frame);   // segbox.hip
 vgs_status vgs_seggraph_on_device(vgs_ctx* c);   // seggraph.hip
 vgs_status vgs_stage_vccs(vgs_ctx* c);
 vgs_status vgs_stage_svgs_group(vgs_ctx* c);
