@@ -11,7 +11,10 @@
 //   --segments <file.csv>: every rank takes part in vgs_tiles_get_segment_descriptors (a collective) and rank 0 writes the table of the
 //   global segments in the CSV format of vgs_run --segments (examples/segments_csv.hpp).
 //   --segment-graph <file.csv>: every rank takes part in vgs_tiles_get_segment_graph (a collective) and rank 0 writes the adjacency graph
-//   of the global segments in the CSV format of vgs_run --segment-graph.  The two can be combined.
+//   of the global segments in the CSV format of vgs_run --segment-graph.
+//   --segment-boxes <file.csv> [--box-frame principal|upright]: every rank takes part in vgs_tiles_get_segment_boxes (a collective; it
+//   takes the descriptor table first) and rank 0 writes the oriented boxes of the global segments in the CSV format of vgs_run
+//   --segment-boxes.  The three can be combined.
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <sys/socket.h>
@@ -50,7 +53,7 @@ static bool write_i32(const std::string& path, const std::vector<int32_t>& v) {
   return put == v.size();
 }
 
-struct Job { vgs_params p; int tx, ty; double pitch; std::string prefix, segments, graph; };
+struct Job { vgs_params p; int tx, ty; double pitch; std::string prefix, segments, graph, boxes; int box_frame = VGS_BOX_PRINCIPAL; };
 
 // one rank: load, run, save; returns 0 on success
 static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world, int64_t* kept, int64_t* n_pts, int64_t* n_rec, std::string* err) {
@@ -112,6 +115,24 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
     }
     if (sg != VGS_OK) { *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t); rc = 1; }
     else if (rank == 0 && writeGraphCsv(J.graph, edges) != 0) { *err = "cannot write " + J.graph; rc = 1; }
+  }
+  if (rc == 0 && !J.boxes.empty()) {
+    // the oriented boxes of the global segments: a collective of every rank, the same table on each; rank 0 writes it
+    const size_t k = (size_t)*kept;
+    std::vector<double> ce(3 * k + 1), ha(3 * k + 1), fr(9 * k + 1), lo(3 * k + 1), hi(3 * k + 1);
+    int64_t K = 0;
+    if (vgs_tiles_get_segment_boxes(t, J.box_frame, &K, ce.data(), ha.data(), fr.data(), lo.data(), hi.data()) != VGS_OK) {
+      *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+      rc = 1;
+    } else if (rank == 0) {
+      std::vector<pcl::ClusterBox> boxes(k);
+      for (size_t i = 0; i < k; ++i) {
+        pcl::ClusterBox& b = boxes[i];
+        for (int a = 0; a < 3; ++a) { b.center[a] = ce[3 * i + a]; b.half[a] = ha[3 * i + a]; b.lo[a] = lo[3 * i + a]; b.hi[a] = hi[3 * i + a]; }
+        for (int a = 0; a < 9; ++a) b.frame[a] = fr[9 * i + a];
+      }
+      if (writeBoxesCsv(J.boxes, boxes) != 0) { *err = "cannot write " + J.boxes; rc = 1; }
+    }
   }
   if (rc == 0) {
     labels.resize((size_t)n);
@@ -175,10 +196,17 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--graph") && a + 1 < argc) J.p.graph_size = (float)std::atof(argv[++a]);
     else if (!std::strcmp(argv[a], "--segments") && a + 1 < argc) J.segments = argv[++a];
     else if (!std::strcmp(argv[a], "--segment-graph") && a + 1 < argc) J.graph = argv[++a];
+    else if (!std::strcmp(argv[a], "--segment-boxes") && a + 1 < argc) J.boxes = argv[++a];
+    else if (!std::strcmp(argv[a], "--box-frame") && a + 1 < argc) {
+      ++a;
+      if (!std::strcmp(argv[a], "principal")) J.box_frame = VGS_BOX_PRINCIPAL;
+      else if (!std::strcmp(argv[a], "upright")) J.box_frame = VGS_BOX_UPRIGHT;
+      else { std::fprintf(stderr, "--box-frame must be principal or upright\n"); return 2; }
+    }
     else if (argv[a][0] != '-') J.prefix = argv[a];
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
-  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] <prefix>\n", argv[0]); return 2; }
+  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] <prefix>\n", argv[0]); return 2; }
   const int world = J.tx * J.ty;
   int64_t kept = 0, n_pts = 0, n_rec = 0;
   if (mode == 1) {

@@ -271,6 +271,27 @@ vgs_status vgs_get_segment_boxes(vgs_ctx* ctx, int32_t frame, double* center3, d
 /* the same table left in HBM: device pointers (any may be NULL), valid until the next run of the stages */
 vgs_status vgs_get_segment_boxes_device(vgs_ctx* ctx, int32_t frame, const double** center3, const double** half3, const double** frame9,
                                         const double** lo3, const double** hi3);
+/* Box extents of a tile context (the tiled driver, include/vgs_tiles.h: vgs_tiles_get_segment_boxes builds the global table from them).
+ * Inputs: K rows of the GLOBAL descriptor table -- centroid3, cov6, evecs9 (host arrays, all required for K > 0) -- and the frame.  The
+ * rows are uploaded, the frames W made from them by the frame rule above (the same device code), and t_j(p) taken over this context's own
+ * labelled points: exactly the points vgs_get_own_segment_moments counts in n_points (input index in the vgs_set_own_point_range range,
+ * vox_label = k, global after vgs_apply_tile_labels).  One record per label with at least one such point, in ascending label order; every
+ * output array holds up to K records and any may be NULL; *n_records is written:
+ *   label      int32   k
+ *   lo3, hi3   double  min and max of t_j over the own points of k
+ * Computed on the device every call (no cache: the driver keeps the table); a cached box table of the context itself is not touched.
+ * VGS_E_ARG for another frame value; VGS_E_STATE before the context is segmented and for a context that is not a tile context. */
+vgs_status vgs_get_own_segment_extents(vgs_ctx* ctx, int64_t K, int32_t frame, const double* centroid3, const double* cov6, const double* evecs9,
+                                       int64_t* n_records, int32_t* label, double* lo3, double* hi3);
+/* The box table from extents already folded per label (K rows of lo3 / hi3 in the frame that `frame` makes from the cov6 / evecs9 rows;
+ * centroid3 the row's c): half3, center3 and frame9 of vgs_get_segment_boxes by the same device code, on this context's GPU -- the
+ * arithmetic is not the host compiler's.  Every input is required for K > 0; any output may be NULL.  A row that no point reaches (a label
+ * without a labelled point anywhere, n_points = 0 in the tiled descriptor table) is passed as lo = hi = 0 and comes back as half = 0,
+ * center3 = its centroid3 (c plus a zero), frame9 as computed.  Uses scratch of its own: a cached box table of the context itself is not
+ * touched.  VGS_E_ARG for another frame value. */
+vgs_status vgs_segment_boxes_from_extents(vgs_ctx* ctx, int64_t K, int32_t frame, const double* centroid3, const double* cov6,
+                                          const double* evecs9, const double* lo3, const double* hi3, double* center3, double* half3,
+                                          double* frame9);
 /* Segment adjacency graph (no reference counterpart: which kept segments touch, and how strongly the local cut's weight links them).
  *   A node is a voxel (VGS) or a supervoxel (SVGS).  Only used nodes with a kept label >= 0 take part; unused voxels and the nodes of
  *   clusters dropped by the size filter are ignored.

@@ -12,7 +12,8 @@
  * voxels (code, local root, owned voxels of that root) and the number of purely local segments leave the GPU -> ncclAllGather
  * -> the same union-find over (rank, root) on every rank, size filter on global sizes -> labels applied on the GPU.  Per-segment
  * descriptors on request afterwards: a second collective of their own (vgs_tiles_get_segment_descriptors).  The segment adjacency graph
- * on request: a third collective of its own (vgs_tiles_get_segment_graph).
+ * on request: a third collective of its own (vgs_tiles_get_segment_graph).  Oriented boxes on request: the descriptor table (its collective,
+ * unless it is cached) and one collective of their own per frame (vgs_tiles_get_segment_boxes).
  */
 #ifndef VGS_TILES_H_
 #define VGS_TILES_H_
@@ -165,6 +166,39 @@ vgs_status vgs_tiles_fold_edges(int world, const int64_t* rec_off, const int32_t
                                 const int32_t* nodes_ab, const double* w_sum, const float* w_min, const float* w_max, int64_t K,
                                 int64_t* n_edges, int32_t* seg_ab_out, int64_t* n_pairs_out, int64_t* n_finite_out, int32_t* nodes_ab_out,
                                 double* w_sum_out, float* w_min_out, float* w_max_out);
+/* Oriented bounding boxes over all ranks: the fields, layout and conventions of vgs_get_segment_boxes (include/vgs.h) -- frame, center3,
+ * half3, frame9, lo3, hi3, every array K rows of doubles, any pointer may be NULL -- with K = kept_global rows; row k covers exactly the
+ * points, over all ranks, that vgs_tiles_get_point_labels labels k (the points the tiled descriptors' n_points counts: each by the rank
+ * that loaded it).  c is the centroid3 row and W the frame made from the evecs9 / cov6 rows of vgs_tiles_get_segment_descriptors, by the
+ * same device code as on one engine; lo3 / hi3 are min / max of exact fp64 projections, which do not depend on the order, so the table is
+ * the bit-exact function of the points, c and W that vgs_get_segment_boxes defines, and every rank receives the same bytes, bit-identical
+ * from call to call and from run to run on the same input and layout (a zero bound may carry either sign).  A row that no point reaches
+ * (a global label without a labelled point on any rank, n_points = 0 in the descriptor table): lo = hi = half = 0, center3 = its
+ * centroid3, frame9 as computed.
+ * VGS_E_ARG for another frame value and VGS_E_STATE before a run are decided locally (no collective).  A call with every array pointer NULL
+ * only writes *K (no collective).  Otherwise the call is COLLECTIVE while this frame's table is not cached: after one vgs_tiles_run every
+ * rank makes it.  Protocol (csrc/tiles.cpp): the global descriptor table through vgs_tiles_get_segment_descriptors' own path (nothing if
+ * it is cached, else that call's one collective) -> this rank's extents of its own points (vgs_get_own_segment_extents, one small
+ * pipeline on its GPU) -> ONE all_gather_varlen of 56-byte records (int32 label, int32 pad, lo[3], hi[3]) behind a header of record count
+ * and status word -> the same host fold on every rank (vgs_tiles_fold_extents) -> half and centre on the rank's GPU
+ * (vgs_segment_boxes_from_extents).  So the first box call costs at most two collectives, the other frame one more.  The table is cached
+ * per frame and both frames may be cached at once: a cached call makes no collective and may be made by one rank alone; the next
+ * vgs_tiles_run or vgs_tiles_set_points drops both.  Failures as in vgs_tiles_run: a rank whose local step fails still joins the exchange
+ * with its status word, returns its own error, and every other rank returns VGS_E_PEER naming it (tests inject one with
+ * VGS_TILES_FAIL_AT=boxes).  vgs_tiles_run itself gains no launch and no collective; point labels, descriptors and the graph are not
+ * touched. */
+vgs_status vgs_tiles_get_segment_boxes(vgs_tiles* t, int32_t frame, int64_t* K, double* center3, double* half3, double* frame9, double* lo3,
+                                       double* hi3);
+/* host wall time of the last box collective on this rank (the descriptor collective in front of it is not included), milliseconds: own
+ * extents on the GPU (with upload and download), the exchange, the fold, the finish on the GPU (with upload and download), total */
+enum { VGS_TILES_B_EXTENTS = 0, VGS_TILES_B_EXCHANGE = 1, VGS_TILES_B_FOLD = 2, VGS_TILES_B_FINISH = 3, VGS_TILES_B_TOTAL = 4, VGS_TILES_B_COUNT = 5 };
+vgs_status vgs_tiles_get_box_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_B_COUNT */);
+/* The extent fold on its own (host arithmetic, no context, no GPU; for tests): rank r's records are entries rec_off[r] .. rec_off[r+1] of
+ * label / lo3 / hi3 (vgs_get_own_segment_extents).  Outputs: K rows, every pointer required for K > 0.  Per label, ranks in ascending
+ * order: lo takes the smaller and hi the larger value (a zero keeps the sign met first); reached[k] = 1 if a record names k.  A row no
+ * record reaches: +inf / -inf and reached = 0.  VGS_E_ARG for a label outside 0 .. K-1. */
+vgs_status vgs_tiles_fold_extents(int world, const int64_t* rec_off, const int32_t* label, const double* lo3, const double* hi3, int64_t K,
+                                  double* lo3_out, double* hi3_out, uint8_t* reached_out);
 /* the rank's engine context (read-only use: counts, stage times) */
 vgs_ctx* vgs_tiles_context(vgs_tiles* t);
 

@@ -100,6 +100,8 @@ SYMBOLS = [
     ("vgs_segment_descriptors_from_moments", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_segment_boxes", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     ("vgs_get_segment_boxes_device", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("vgs_get_own_segment_extents", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_segment_boxes_from_extents", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_segment_graph", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_segment_graph_device", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_set_halo_labels", C.c_int, [_P, _P, _P, C.c_int64]),

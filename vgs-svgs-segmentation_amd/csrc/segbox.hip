@@ -14,11 +14,16 @@
 // Exact arithmetic: every product and sum above is one IEEE fp64 operation in the stated association (the build passes
 // -ffp-contract=off: no FMA), and min / max do not depend on the order, so the table is a function of the points, c and W alone -- a
 // float64 restatement reproduces it to the bit (tests/segment_boxes_ref.py).  A zero bound may carry either sign, as in bbox6.
-// No atomics.  The chunk kernel takes c and W as arrays per label, so a rank of the tiled driver could run it over its own points about a
-// centroid and frame handed in.  Scratch: sb_part and the sd_* scratch of sd_prepare, nothing a getter reads.  Cached per frame until the
+// No atomics.  The chunk kernel takes c and W as arrays per label, so a rank of the tiled driver runs it over its own points about a
+// centroid and frame handed in (k_sb_chunks_own, below).  Scratch: sb_part and the sd_* scratch of sd_prepare, nothing a getter reads.  Cached per frame until the
 // next run (sb_valid[frame]); vgs_segment_descriptors_from_moments may overwrite the descriptor buffers afterwards, the box table keeps
 // the frame its extents were taken in.
+// Tile contexts (the tiled driver, include/vgs_tiles.h): the global descriptor rows come in from the host, k_sb_frames makes the frames,
+// k_sb_chunks_own takes the extents of the rank's own points over the global labels and k_sb_final folds them per segment
+// (vgs_get_own_segment_extents); the driver folds all ranks' records on the host (min / max) and k_sb_final, over one partial per segment,
+// finishes the table (vgs_segment_boxes_from_extents).  Their buffers are sbt_* and sb_part: a cached table is not touched.
 #include <string.h>
+#include <vector>
 
 #include "vgs_context.hpp"
 
@@ -86,12 +91,16 @@ __device__ __forceinline__ void sb_empty_record(double* __restrict__ rec) {
 
 // One workgroup per chunk of SD_CHUNK virtual points of one segment: the chunk -> segment -> nodes walk of segdesc.hip's sd_chunk_body
 // (same staging arrays, same point of every lane and step), the projections of the header, one partial record.  Grid: the bound of
-// sd_prepare; workgroups past the real number of chunks leave at once.  cen / frame: 3 and 9 doubles per label.
-__global__ __launch_bounds__(SD_TB) void k_sb_chunks(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
-                                                     const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
-                                                     const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
-                                                     const uint32_t* __restrict__ seg_chunk, uint32_t K, const double* __restrict__ cen,
-                                                     const double* __restrict__ frame, double* __restrict__ part) {
+// sd_prepare; workgroups past the real number of chunks leave at once.  cen / frame: 3 and 9 doubles per label.  OWN (tile contexts,
+// k_sb_chunks_own): only the points whose input index perm[pos] lies in [own_first, own_end) count -- the selection of segdesc.hip's
+// k_sd_chunks_own, so the extents cover the points its n_points counts; a chunk without one writes the empty record.
+template <bool OWN>
+__device__ __forceinline__ void sb_chunk_body(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                              const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                              const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                              const uint32_t* __restrict__ seg_chunk, uint32_t K, const double* __restrict__ cen,
+                                              const double* __restrict__ frame, double* __restrict__ part,
+                                              const uint32_t* __restrict__ perm, int64_t own_first, int64_t own_end) {
   __shared__ uint32_t s_vp[SD_CHUNK];    // virtual start of the chunk's nodes
   __shared__ uint32_t s_dl[SD_CHUNK];    // sorted position - virtual position of the same (mod 2^32)
   __shared__ double s_red[SD_TB / 64][SB_REC];
@@ -133,6 +142,10 @@ __global__ __launch_bounds__(SD_TB) void k_sb_chunks(const float* __restrict__ x
       uint32_t l = 0, h = m - 1;   // the last node of the chunk that starts at or before q
       while (l < h) { const uint32_t mid = (l + h + 1) >> 1; if (s_vp[mid] <= q) l = mid; else h = mid - 1; }
       const uint32_t pos = q + s_dl[l];
+      if (OWN) {
+        const int64_t o = (int64_t)perm[pos];
+        if (o < own_first || o >= own_end) continue;
+      }
       // exact differences (a float against a double), then one fp64 operation per product and sum, in this association
       const double dx = (double)xs[pos] - cx, dy = (double)ys[pos] - cy, dz = (double)zs[pos] - cz;
       const double t0 = (w00 * dx + w10 * dy) + w20 * dz;
@@ -157,6 +170,23 @@ __global__ __launch_bounds__(SD_TB) void k_sb_chunks(const float* __restrict__ x
     else { for (int u = 1; u < SD_TB / 64; ++u) v = fmax(v, s_red[u][f]); }
     part[(size_t)c * SB_REC + f] = v;
   }
+}
+
+__global__ __launch_bounds__(SD_TB) void k_sb_chunks(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                     const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                     const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                     const uint32_t* __restrict__ seg_chunk, uint32_t K, const double* __restrict__ cen,
+                                                     const double* __restrict__ frame, double* __restrict__ part) {
+  sb_chunk_body<false>(xs, ys, zs, vox_start, ids, vp, seg_node, seg_chunk, K, cen, frame, part, nullptr, 0, 0);
+}
+
+__global__ __launch_bounds__(SD_TB) void k_sb_chunks_own(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                         const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                         const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                         const uint32_t* __restrict__ seg_chunk, uint32_t K, const double* __restrict__ cen,
+                                                         const double* __restrict__ frame, double* __restrict__ part,
+                                                         const uint32_t* __restrict__ perm, int64_t own_first, int64_t own_end) {
+  sb_chunk_body<true>(xs, ys, zs, vox_start, ids, vp, seg_node, seg_chunk, K, cen, frame, part, perm, own_first, own_end);
 }
 
 // one wavefront per segment: fold its partials (lane stride, then butterfly), then the row on lane 0
@@ -261,5 +291,108 @@ extern "C" vgs_status vgs_get_segment_boxes_device(vgs_ctx* c, int32_t frame, co
   if (frame9) *frame9 = c->sb_frame[frame].p;
   if (lo3) *lo3 = c->sb_lo[frame].p;
   if (hi3) *hi3 = c->sb_hi[frame].p;
+  return VGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ tile contexts (include/vgs_tiles.h)
+static vgs_status sbt_check_frame(vgs_ctx* c, int32_t frame, const char* fn) {
+  if (frame == VGS_BOX_PRINCIPAL || frame == VGS_BOX_UPRIGHT) return VGS_OK;
+  c->err = std::string(fn) + ": frame must be VGS_BOX_PRINCIPAL (0) or VGS_BOX_UPRIGHT (1)";
+  return VGS_E_ARG;
+}
+
+// K rows of the descriptor table from the host into sbt_in (centroid3 | cov6 | evecs9) and their frames into sbt_frame: k_sb_frames, the
+// one copy of the frame rule.  The copies are staged before they return; the launches are left on the stream.
+static vgs_status sbt_upload_frames(vgs_ctx* c, int64_t K, int32_t frame, const double* centroid3, const double* cov6, const double* evecs9) {
+  const size_t k = (size_t)K;
+  VGS_HIP_TRY(c, c->sbt_in.ensure(18 * k)); VGS_HIP_TRY(c, c->sbt_frame.ensure(9 * k)); VGS_HIP_TRY(c, c->sbt_out.ensure(12 * k));
+  double *cen = c->sbt_in.p, *cov = cen + 3 * k, *evec = cov + 6 * k;
+  VGS_HIP_TRY(c, hipMemcpyAsync(cen, centroid3, 3 * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(cov, cov6, 6 * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(evec, evecs9, 9 * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_sb_frames, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, evec, cov, (uint32_t)K,
+                     frame == VGS_BOX_UPRIGHT ? 1 : 0, c->sbt_frame.p);
+  return VGS_OK;
+}
+
+// k_sb_final over `part` into sbt_out (lo3 | hi3 | half3 | center3, K rows each), about the rows of sbt_upload_frames
+static void sbt_launch_final(vgs_ctx* c, int64_t K, const uint32_t* seg_chunk, const double* part, uint32_t n_part) {
+  const size_t k = (size_t)K;
+  double* o = c->sbt_out.p;
+  hipLaunchKernelGGL(k_sb_final, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, seg_chunk, part, n_part, (uint32_t)K, c->sbt_in.p,
+                     c->sbt_frame.p, o, o + 3 * k, o + 6 * k, o + 9 * k);
+}
+
+// This rank's extents of the global labels 0 .. K-1: sd_prepare over vox_label (global after vgs_apply_tile_labels), the own-point chunks
+// about the centroids and frames handed in, the per-segment fold of k_sb_final.  Dense on the device (K rows), compact on the host: a
+// label without an own point keeps the empty record and is left out.
+extern "C" vgs_status vgs_get_own_segment_extents(vgs_ctx* c, int64_t K, int32_t frame, const double* centroid3, const double* cov6,
+                                                  const double* evecs9, int64_t* n_records, int32_t* label, double* lo3, double* hi3) {
+  if (!c || !n_records || K < 0 || K >= (int64_t)0xffffffffLL || (K > 0 && (!centroid3 || !cov6 || !evecs9))) return VGS_E_ARG;
+  vgs_status s = sbt_check_frame(c, frame, "vgs_get_own_segment_extents");
+  if (s != VGS_OK) return s;
+  if (c->stage < ST_SEGMENTED) { c->err = "vgs_get_own_segment_extents: segment first"; return VGS_E_STATE; }
+  if (!c->have_region || c->n_own < 0) {
+    c->err = "vgs_get_own_segment_extents: a tile context (vgs_set_owned_region and vgs_set_own_point_range) only";
+    return VGS_E_STATE;
+  }
+  *n_records = 0;
+  const int64_t V = c->V, nf = c->Nf;
+  if (K == 0 || V == 0 || nf == 0) return VGS_OK;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  SdPrep P;
+  if ((s = sd_prepare(c, K, P)) != VGS_OK) return s;
+  VGS_HIP_TRY(c, c->sb_part.ensure((size_t)P.n_chunks_max * SB_REC));
+  if ((s = sbt_upload_frames(c, K, frame, centroid3, cov6, evecs9)) != VGS_OK) return s;
+  hipLaunchKernelGGL(k_sb_chunks_own, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, P.ids,
+                     P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, c->sbt_in.p, c->sbt_frame.p, c->sb_part.p, c->perm_b.p, c->own_first,
+                     c->own_first + c->n_own);
+  sbt_launch_final(c, K, P.seg_chunk, c->sb_part.p, (uint32_t)P.n_chunks_max);
+  VGS_HIP_TRY(c, hipGetLastError());
+  std::vector<double> e(6 * (size_t)K);   // lo3 | hi3
+  VGS_HIP_TRY(c, hipMemcpyAsync(e.data(), c->sbt_out.p, e.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const double* lo = e.data();
+  const double* hi = lo + 3 * (size_t)K;
+  int64_t n = 0;
+  for (int64_t k = 0; k < K; ++k) {
+    if (lo[3 * k] > hi[3 * k]) continue;   // the empty record: no own point of this label here
+    if (label) label[n] = (int32_t)k;
+    if (lo3) for (int f = 0; f < 3; ++f) lo3[3 * n + f] = lo[3 * k + f];
+    if (hi3) for (int f = 0; f < 3; ++f) hi3[3 * n + f] = hi[3 * k + f];
+    ++n;
+  }
+  *n_records = n;
+  return VGS_OK;
+}
+
+// The table from extents folded over the ranks: one partial per segment (seg_chunk[k] = k), so k_sb_final runs unchanged.
+extern "C" vgs_status vgs_segment_boxes_from_extents(vgs_ctx* c, int64_t K, int32_t frame, const double* centroid3, const double* cov6,
+                                                     const double* evecs9, const double* lo3, const double* hi3, double* center3, double* half3,
+                                                     double* frame9) {
+  if (!c || K < 0 || K >= (int64_t)0xffffffffLL || (K > 0 && (!centroid3 || !cov6 || !evecs9 || !lo3 || !hi3))) return VGS_E_ARG;
+  vgs_status s = sbt_check_frame(c, frame, "vgs_segment_boxes_from_extents");
+  if (s != VGS_OK) return s;
+  if (K == 0) return VGS_OK;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  const size_t k = (size_t)K;
+  std::vector<double> part(SB_REC * k);
+  std::vector<uint32_t> idx(k + 1);
+  for (size_t i = 0; i < k; ++i) {
+    for (int f = 0; f < 3; ++f) { part[SB_REC * i + f] = lo3[3 * i + f]; part[SB_REC * i + 3 + f] = hi3[3 * i + f]; }
+    idx[i] = (uint32_t)i;
+  }
+  idx[k] = (uint32_t)k;
+  VGS_HIP_TRY(c, c->sb_part.ensure(part.size())); VGS_HIP_TRY(c, c->sbt_idx.ensure(idx.size()));
+  if ((s = sbt_upload_frames(c, K, frame, centroid3, cov6, evecs9)) != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->sb_part.p, part.data(), part.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->sbt_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  sbt_launch_final(c, K, c->sbt_idx.p, c->sb_part.p, (uint32_t)K);
+  VGS_HIP_TRY(c, hipGetLastError());
+  const double* o = c->sbt_out.p;
+  if (half3) VGS_HIP_TRY(c, hipMemcpyAsync(half3, o + 6 * k, 3 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (center3) VGS_HIP_TRY(c, hipMemcpyAsync(center3, o + 9 * k, 3 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (frame9) VGS_HIP_TRY(c, hipMemcpyAsync(frame9, c->sbt_frame.p, 9 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VGS_OK;
 }

@@ -301,6 +301,33 @@ bool fold_edges(const std::vector<std::vector<EdgeRec>>& ranks, int64_t K, std::
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------ box extents
+// One rank's extents of one global label (vgs_get_own_segment_extents); the payload of the box exchange.  Its first entry is the header:
+// label = the rank's status word, pad = 0, lo[0] = its record count.
+struct ExtentRec {
+  int32_t label = 0, pad = 0;
+  double lo[3] = {0, 0, 0};
+  double hi[3] = {0, 0, 0};
+};
+static_assert(sizeof(ExtentRec) == 56, "ExtentRec is the exchange's wire format");
+
+// The extents of every global label 0 .. K-1 from the ranks' records, the same bytes on every rank: per label, ranks in ascending order,
+// lo takes the smaller and hi the larger (of values; a zero bound keeps the sign it met first).  A row no record reaches: +inf / -inf and
+// reached = 0.  Returns false if a record names a label outside 0 .. K-1.
+bool fold_extents(const std::vector<std::vector<ExtentRec>>& ranks, int64_t K, std::vector<double>& lo, std::vector<double>& hi,
+                  std::vector<uint8_t>& reached) {
+  const double inf = __builtin_huge_val();
+  lo.assign(3 * (size_t)K, inf); hi.assign(3 * (size_t)K, -inf); reached.assign((size_t)K, 0);
+  for (const std::vector<ExtentRec>& R : ranks)
+    for (const ExtentRec& e : R) {
+      if (e.label < 0 || (int64_t)e.label >= K) return false;
+      const size_t k = (size_t)e.label;
+      for (int a = 0; a < 3; ++a) { if (e.lo[a] < lo[3 * k + a]) lo[3 * k + a] = e.lo[a]; if (e.hi[a] > hi[3 * k + a]) hi[3 * k + a] = e.hi[a]; }
+      reached[k] = 1;
+    }
+  return true;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ driver
@@ -317,7 +344,7 @@ struct vgs_tiles {
   double times[VGS_TILES_T_COUNT] = {0};   // last run, milliseconds of host wall time per phase (vgs_tiles_get_times)
   int strict_region = 0;      // VGS_TILES_OPT_STRICT_REGION
   int fail_phase = 0;         // tests (VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT): 1 grid, 2 stages, 3 points, 4 upload (behind the last collective of set_points),
-                              // 5 descriptors (before the descriptor exchange), 6 graph (before the graph exchange)
+                              // 5 descriptors (before the descriptor exchange), 6 graph (before the graph exchange), 7 boxes (before the box exchange)
   vgs_status pending = VGS_OK;   // a local failure behind a call's last collective: the status word of the next collective carries it
   bool warned_outside = false;
   bool ran = false;              // the last vgs_tiles_run completed here
@@ -337,6 +364,10 @@ struct vgs_tiles {
   std::vector<EdgeRec> graph;
   double gtimes[VGS_TILES_G_COUNT] = {0};   // the last graph collective, milliseconds of host wall time per phase
   int64_t g_halo = 0, g_own = 0, g_bytes = 0;   // its payload: halo labels handed to the context, own edges, bytes sent
+  // the global box table of the last run per frame (vgs_tiles_get_segment_boxes), K = kept rows; valid until the next run / set_points
+  bool box_valid[2] = {false, false};
+  std::vector<double> b_center[2], b_half[2], b_frame[2], b_lo[2], b_hi[2];
+  double btimes[VGS_TILES_B_COUNT] = {0};   // the last box collective, milliseconds of host wall time per phase
   std::string err;
 };
 
@@ -386,7 +417,7 @@ vgs_status vgs_tiles_create(const vgs_params* p, int comm_kind, void* comm_handl
     // failure injection for the tests of the agreed-status protocol; read once, here
     const char* fr = std::getenv("VGS_TILES_FAIL_RANK");
     const char* fa = std::getenv("VGS_TILES_FAIL_AT");
-    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : !std::strcmp(fa, "descriptors") ? 5 : !std::strcmp(fa, "graph") ? 6 : 0;
+    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : !std::strcmp(fa, "descriptors") ? 5 : !std::strcmp(fa, "graph") ? 6 : !std::strcmp(fa, "boxes") ? 7 : 0;
   }
   vgs_status s = vgs_create(p, &t->ctx);
   if (s != VGS_OK) { delete t->comm; delete t; return s; }
@@ -419,7 +450,7 @@ vgs_status vgs_tiles_get_times(vgs_tiles* t, double* ms, int32_t n) {
 vgs_status vgs_tiles_set_points(vgs_tiles* t, const float* xyz, int64_t n, int32_t stride_bytes) {
   if (!t || (!xyz && n > 0) || n < 0 || (stride_bytes != 12 && stride_bytes != 16)) return VGS_E_ARG;
   Comm& c = *t->comm;
-  t->ran = false; t->desc_valid = false; t->graph_valid = false;
+  t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false;
   const int sf = stride_bytes / 4;
   if (!(t->pitch > 0)) {   // the largest x-extent over the ranks
     float mn = 3.0e38f, mx = -3.0e38f;
@@ -556,7 +587,7 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
   if (!t) return VGS_E_ARG;
   Comm& c = *t->comm;
   vgs_status carry = t->pending;   // a local failure behind the last collective of the previous call (upload, label write-back) travels now
-  t->ran = false; t->desc_valid = false; t->graph_valid = false;
+  t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false;
   double t0 = now_ms();
   vgs_status s = chain_grid(t, carry);
   if (s != VGS_OK) return s;
@@ -648,11 +679,8 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
 // Descriptors over the ranks: this rank's moments (one small pipeline on its GPU) -> ONE all_gather_varlen of the records with a header
 // of status word and record count -> the same host fold on every rank -> the per-segment algebra on this rank's GPU.  Same bytes on every
 // rank: the fold's inputs and order are the same everywhere, and the algebra is one deterministic device function of its inputs.
-vgs_status vgs_tiles_get_segment_descriptors(vgs_tiles* t, int64_t* K, int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3,
-                                             double* cov6, double* evals3, double* evecs9, float* eigen8) {
-  if (!t) return VGS_E_ARG;
-  if (K) *K = t->kept;
-  if (!n_points && !n_nodes && !bbox6 && !centroid3 && !cov6 && !evals3 && !evecs9 && !eigen8) return VGS_OK;   // size query: no collective
+// (the table into t->d_*: the collective when it is not cached; vgs_tiles_get_segment_boxes takes the table through here too)
+static vgs_status ensure_descriptors(vgs_tiles* t) {
   if (!t->desc_valid) {
     // a rank whose last call failed behind its last collective still comes, with that status; one that never ran does not (nor do its peers)
     if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_descriptors: vgs_tiles_run first");
@@ -713,6 +741,16 @@ vgs_status vgs_tiles_get_segment_descriptors(vgs_tiles* t, int64_t* K, int64_t* 
     t->dtimes[VGS_TILES_D_ALGEBRA] = t4 - t3; t->dtimes[VGS_TILES_D_TOTAL] = t4 - t0;
     t->desc_valid = true;
   }
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_segment_descriptors(vgs_tiles* t, int64_t* K, int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3,
+                                             double* cov6, double* evals3, double* evecs9, float* eigen8) {
+  if (!t) return VGS_E_ARG;
+  if (K) *K = t->kept;
+  if (!n_points && !n_nodes && !bbox6 && !centroid3 && !cov6 && !evals3 && !evecs9 && !eigen8) return VGS_OK;   // size query: no collective
+  const vgs_status sd = ensure_descriptors(t);
+  if (sd != VGS_OK) return sd;
   auto put = [](const auto& v, auto* dst) { if (dst) std::copy(v.begin(), v.end(), dst); };
   put(t->d_npts, n_points); put(t->d_nnodes, n_nodes); put(t->d_bbox, bbox6); put(t->d_cen, centroid3); put(t->d_cov, cov6);
   put(t->d_eval, evals3); put(t->d_evec, evecs9); put(t->d_eig8, eigen8);
@@ -722,6 +760,109 @@ vgs_status vgs_tiles_get_segment_descriptors(vgs_tiles* t, int64_t* K, int64_t* 
 vgs_status vgs_tiles_get_descriptor_times(vgs_tiles* t, double* ms, int32_t n) {
   if (!t || !ms || n < 0 || n > VGS_TILES_D_COUNT) return VGS_E_ARG;
   for (int i = 0; i < n; ++i) ms[i] = t->dtimes[i];
+  return VGS_OK;
+}
+
+// Boxes over the ranks: the global descriptor table (its own collective when it is not cached) -> this rank's extents of its own points
+// about the global centroids, in the frames made from the global rows (one small pipeline on its GPU) -> ONE all_gather_varlen of the
+// records with a header of record count and status word -> the same host fold on every rank (min / max) -> half and centre on this
+// rank's GPU.  Same bytes on every rank: min and max do not depend on the order, and the finish is one device function of its inputs.
+vgs_status vgs_tiles_get_segment_boxes(vgs_tiles* t, int32_t frame, int64_t* K, double* center3, double* half3, double* frame9, double* lo3,
+                                       double* hi3) {
+  if (!t) return VGS_E_ARG;
+  if (frame != VGS_BOX_PRINCIPAL && frame != VGS_BOX_UPRIGHT) return tfail(t, VGS_E_ARG, "vgs_tiles_get_segment_boxes: frame must be VGS_BOX_PRINCIPAL (0) or VGS_BOX_UPRIGHT (1)");
+  if (K) *K = t->kept;
+  if (!center3 && !half3 && !frame9 && !lo3 && !hi3) return VGS_OK;   // size query: no collective
+  if (!t->box_valid[frame]) {
+    if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_boxes: vgs_tiles_run first");
+    if (!t->desc_valid) {
+      // The descriptor collective ends the call on every rank alike when a status word in it says so.  A failure of this rank BEHIND that
+      // collective (it newly sets t->pending; the peers' tables are complete and they go on) travels in the box exchange's status word.
+      const vgs_status before = t->pending;
+      const vgs_status sd = ensure_descriptors(t);
+      if (sd != VGS_OK && !(before == VGS_OK && t->pending != VGS_OK)) return sd;
+    }
+    Comm& c = *t->comm;
+    const int64_t Kg = t->kept;
+    const size_t k1 = (size_t)Kg;
+    vgs_status carry = t->pending;
+    if (t->fail_phase == 7 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=boxes"; }
+    const double t0 = now_ms();
+    std::vector<ExtentRec> payload(1);
+    if (carry == VGS_OK && Kg > 0) {
+      std::vector<int32_t> lab(k1);
+      std::vector<double> lo(3 * k1), hi(3 * k1);
+      int64_t n = 0;
+      TCARRY(vgs_get_own_segment_extents(t->ctx, Kg, frame, t->d_cen.data(), t->d_cov.data(), t->d_evec.data(), &n, lab.data(), lo.data(), hi.data()));
+      if (carry == VGS_OK) {
+        payload.resize(1 + (size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+          ExtentRec& e = payload[1 + (size_t)i];
+          e.label = lab[(size_t)i];
+          for (int a = 0; a < 3; ++a) { e.lo[a] = lo[3 * (size_t)i + a]; e.hi[a] = hi[3 * (size_t)i + a]; }
+        }
+      }
+    }
+    payload[0].label = (int32_t)carry;
+    payload[0].lo[0] = (double)(payload.size() - 1);
+    const double t1 = now_ms();
+    std::vector<std::vector<ExtentRec>> gathered;
+    TCOMM(all_gather_varlen(c, payload, gathered));
+    const double t2 = now_ms();
+    {
+      int bad = -1;
+      for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].empty() || gathered[(size_t)r][0].label != 0) bad = r;
+      vgs_status a = agreed(t, carry, bad, "boxes");
+      if (a != VGS_OK) return a;
+    }
+    for (std::vector<ExtentRec>& g : gathered) g.erase(g.begin());   // the headers
+    std::vector<double> lo, hi;
+    std::vector<uint8_t> reached;
+    if (!fold_extents(gathered, Kg, lo, hi, reached)) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_boxes: a rank sent a label >= kept_global");
+    // a row no record reaches (no labelled point anywhere, n_points = 0 in the descriptor table): lo = hi = 0, so half = 0 and centre = centroid
+    for (size_t k = 0; k < k1; ++k) if (!reached[k]) for (int a = 0; a < 3; ++a) { lo[3 * k + a] = 0.0; hi[3 * k + a] = 0.0; }
+    const double t3 = now_ms();
+    std::vector<double> ce(3 * k1), ha(3 * k1), fr(9 * k1);
+    // (local, behind the collective: the rank returns its error and keeps it for the next collective, as the label write-back does)
+    const vgs_status sa = vgs_segment_boxes_from_extents(t->ctx, Kg, frame, t->d_cen.data(), t->d_cov.data(), t->d_evec.data(), lo.data(), hi.data(),
+                                                         ce.data(), ha.data(), fr.data());
+    if (sa != VGS_OK) { t->pending = sa; return tfail(t, sa, std::string("vgs_segment_boxes_from_extents: ") + vgs_last_error_string(t->ctx)); }
+    const double t4 = now_ms();
+    t->b_center[frame].swap(ce); t->b_half[frame].swap(ha); t->b_frame[frame].swap(fr); t->b_lo[frame].swap(lo); t->b_hi[frame].swap(hi);
+    t->btimes[VGS_TILES_B_EXTENTS] = t1 - t0; t->btimes[VGS_TILES_B_EXCHANGE] = t2 - t1; t->btimes[VGS_TILES_B_FOLD] = t3 - t2;
+    t->btimes[VGS_TILES_B_FINISH] = t4 - t3; t->btimes[VGS_TILES_B_TOTAL] = t4 - t0;
+    t->box_valid[frame] = true;
+  }
+  auto put = [](const std::vector<double>& v, double* dst) { if (dst) std::copy(v.begin(), v.end(), dst); };
+  put(t->b_center[frame], center3); put(t->b_half[frame], half3); put(t->b_frame[frame], frame9); put(t->b_lo[frame], lo3); put(t->b_hi[frame], hi3);
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_box_times(vgs_tiles* t, double* ms, int32_t n) {
+  if (!t || !ms || n < 0 || n > VGS_TILES_B_COUNT) return VGS_E_ARG;
+  for (int i = 0; i < n; ++i) ms[i] = t->btimes[i];
+  return VGS_OK;
+}
+
+// host arithmetic only (tests): the extent fold on flattened per-rank records
+vgs_status vgs_tiles_fold_extents(int world, const int64_t* rec_off, const int32_t* label, const double* lo3, const double* hi3, int64_t K,
+                                  double* lo3_out, double* hi3_out, uint8_t* reached_out) {
+  if (world < 1 || !rec_off || K < 0 || (K > 0 && (!lo3_out || !hi3_out || !reached_out))) return VGS_E_ARG;
+  if (rec_off[world] > 0 && (!label || !lo3 || !hi3)) return VGS_E_ARG;
+  std::vector<std::vector<ExtentRec>> ranks((size_t)world);
+  for (int r = 0; r < world; ++r) {
+    if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
+    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) {
+      ExtentRec e;
+      e.label = label[i];
+      for (int a = 0; a < 3; ++a) { e.lo[a] = lo3[3 * i + a]; e.hi[a] = hi3[3 * i + a]; }
+      ranks[(size_t)r].push_back(e);
+    }
+  }
+  std::vector<double> lo, hi;
+  std::vector<uint8_t> reached;
+  if (!fold_extents(ranks, K, lo, hi, reached)) return VGS_E_ARG;
+  std::copy(lo.begin(), lo.end(), lo3_out); std::copy(hi.begin(), hi.end(), hi3_out); std::copy(reached.begin(), reached.end(), reached_out);
   return VGS_OK;
 }
 

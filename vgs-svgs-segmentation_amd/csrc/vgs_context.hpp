@@ -271,6 +271,10 @@ struct vgs_ctx {
   DevBuf<double> sb_part;
   DevBuf<double> sb_frame[2], sb_lo[2], sb_hi[2], sb_half[2], sb_center[2];
   bool sb_valid[2] = {false, false};
+  // tile contexts (vgs_get_own_segment_extents / vgs_segment_boxes_from_extents): the descriptor rows handed in (centroid3 | cov6 | evecs9),
+  // the frames made from them, the rows that come out (lo3 | hi3 | half3 | center3), one chunk per segment; nothing a cached table reads
+  DevBuf<double> sbt_in, sbt_frame, sbt_out;
+  DevBuf<uint32_t> sbt_idx;
   // tile contexts (vgs_get_own_segment_moments / vgs_segment_descriptors_from_moments): first own point per segment, moment records
   DevBuf<uint32_t> sd_apos;
   DevBuf<double> sd_mom;

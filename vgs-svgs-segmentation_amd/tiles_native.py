@@ -26,6 +26,7 @@ _RCCL = None
 T_NAMES = ("grid", "stages", "records", "exchange", "merge", "labels", "total")
 D_NAMES = ("moments", "exchange", "fold", "algebra", "total")   # vgs_tiles_get_descriptor_times
 G_NAMES = ("halo", "own", "exchange", "fold", "total")          # vgs_tiles_get_graph_times
+B_NAMES = ("extents", "exchange", "fold", "finish", "total")    # vgs_tiles_get_box_times
 # per record / row: (field, dtype, values) of vgs_get_own_segment_moments and vgs_tiles_fold_moments, in their argument order
 MOMENT_FIELDS = (("n_points", np.int64, 1), ("n_nodes", np.int32, 1), ("bbox6", np.float32, 6), ("anchor3", np.float32, 3), ("s9", np.float64, 9))
 COMM_RCCL, COMM_LOCAL, COMM_CALLBACKS = 0, 1, 2
@@ -90,6 +91,12 @@ def lib():
         L.vgs_tiles_get_graph_payload.argtypes = [P, P, P, P]
         L.vgs_tiles_fold_edges.restype = C.c_int
         L.vgs_tiles_fold_edges.argtypes = [C.c_int, P, P, P, P, P, P, P, P, C.c_int64, P, P, P, P, P, P, P, P]
+        L.vgs_tiles_get_segment_boxes.restype = C.c_int
+        L.vgs_tiles_get_segment_boxes.argtypes = [P, C.c_int32, P, P, P, P, P, P]
+        L.vgs_tiles_get_box_times.restype = C.c_int
+        L.vgs_tiles_get_box_times.argtypes = [P, P, C.c_int32]
+        L.vgs_tiles_fold_extents.restype = C.c_int
+        L.vgs_tiles_fold_extents.argtypes = [C.c_int, P, P, P, P, C.c_int64, P, P, P]
         _TL = L
     return _TL
 
@@ -139,6 +146,25 @@ def fold_edges(tables, K):
     if st != 0:
         raise VgsError(st, "vgs_tiles_fold_edges")
     return {name: a[:E.value].copy() for name, a in out.items()}
+
+
+def fold_extents(records, K):
+    """vgs_tiles_fold_extents (host arithmetic, no GPU): records[r] = rank r's dict of label (int32), lo3 and hi3 (float64, 3 per
+    record), as vgs_get_own_segment_extents gives them; returns the K folded rows as a dict of lo3 (K, 3), hi3 (K, 3) and reached (K,
+    uint8: a record names the label)."""
+    world = len(records)
+    n = [len(r["label"]) for r in records]
+    off = np.zeros(world + 1, dtype=np.int64)
+    off[1:] = np.cumsum(n)
+    lab = np.ascontiguousarray(np.concatenate([np.asarray(r["label"]) for r in records]).astype(np.int32))
+    lo = np.ascontiguousarray(np.concatenate([np.asarray(r["lo3"], dtype=np.float64).reshape(-1, 3) for r in records]).reshape(-1))
+    hi = np.ascontiguousarray(np.concatenate([np.asarray(r["hi3"], dtype=np.float64).reshape(-1, 3) for r in records]).reshape(-1))
+    K = int(K)
+    out = {"lo3": np.zeros((max(K, 1), 3)), "hi3": np.zeros((max(K, 1), 3)), "reached": np.zeros(max(K, 1), dtype=np.uint8)}
+    st = lib().vgs_tiles_fold_extents(world, _vp(off), _vp(lab), _vp(lo), _vp(hi), K, _vp(out["lo3"]), _vp(out["hi3"]), _vp(out["reached"]))
+    if st != 0:
+        raise VgsError(st, "vgs_tiles_fold_extents")
+    return {name: a[:max(K, 0)] for name, a in out.items()}
 
 
 # ---- RCCL through ctypes: the three calls a caller needs to hand the driver a communicator ---------------------------------------
@@ -366,6 +392,42 @@ class NativeTiles:
         if st != 0:
             raise VgsError(st, L.vgs_last_error_string(h).decode())
         return out
+
+    def segment_boxes(self, frame="principal"):
+        """COLLECTIVE while this frame's table is not cached (every rank calls it after run()): the oriented boxes of the global segments
+        over all ranks, row k = the points point_labels() labels k on any rank -- the dict of Engine.segment_boxes(frame), the same
+        bytes on every rank (include/vgs_tiles.h, vgs_tiles_get_segment_boxes).  Takes the descriptor table first (its collective, unless
+        it is cached).  Cached per frame until the next run() or set_points(): later calls make no collective."""
+        from .api import Engine
+        f = int(Engine.BOX_FRAMES.get(frame, frame))
+        K = C.c_int64(0)
+        self._ck(self._L.vgs_tiles_get_segment_boxes(self._h, f, C.byref(K), *([None] * len(Engine.BOX_FIELDS))))
+        k = int(K.value)
+        out = {name: np.zeros((max(k, 1), w), dtype=dt) for name, dt, w in Engine.BOX_FIELDS}   # (K = 0 still makes the call: its status, its collective)
+        self._ck(self._L.vgs_tiles_get_segment_boxes(self._h, f, C.byref(K), *(_vp(out[name]) for name, _, _ in Engine.BOX_FIELDS)))
+        return {name: a[:k] for name, a in out.items()}
+
+    def box_times(self):
+        """the last box collective's phases on this rank, milliseconds (B_NAMES)"""
+        t = np.zeros(len(B_NAMES), dtype=np.float64)
+        self._ck(self._L.vgs_tiles_get_box_times(self._h, _vp(t), len(B_NAMES)))
+        return dict(zip(B_NAMES, (float(x) for x in t)))
+
+    def own_segment_extents(self, K, frame, d):
+        """this rank's extent records of the global labels 0 .. K-1 (vgs_get_own_segment_extents on its context; local, no collective)
+        about the centroid3 / cov6 / evecs9 rows of the global descriptor table d: a dict of label, lo3, hi3"""
+        from .api import Engine
+        L = _lib.lib()
+        h = self._ctx()
+        K = int(K)
+        rows = [np.ascontiguousarray(np.asarray(d[name], dtype=np.float64).reshape(-1)) for name in ("centroid3", "cov6", "evecs9")]
+        out = {"label": np.zeros(max(K, 1), dtype=np.int32), "lo3": np.zeros((max(K, 1), 3)), "hi3": np.zeros((max(K, 1), 3))}
+        n = C.c_int64(0)
+        st = L.vgs_get_own_segment_extents(h, K, int(Engine.BOX_FRAMES.get(frame, frame)), *(_vp(a) for a in rows), C.byref(n),
+                                           _vp(out["label"]), _vp(out["lo3"]), _vp(out["hi3"]))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        return {name: a[:n.value] for name, a in out.items()}
 
     def own_segment_moments(self, K):
         """this rank's moment records of the global labels 0 .. K-1 (vgs_get_own_segment_moments on its context; local, no collective):
