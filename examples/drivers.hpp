@@ -19,16 +19,35 @@ struct DriverGraph {
   std::multimap<uint32_t, uint32_t> adjacency;
 };
 
+// per-point attributes handed to the drivers and what comes back: getClusterFieldStats over `field` (n x channels floats, row-major) when
+// channels > 0, getClusterClassHistogram over `classes` (n int32) when n_classes > 0
+struct DriverFields {
+  std::vector<float> field;
+  int channels = 0;
+  std::vector<int32_t> classes;
+  int n_classes = 0;
+  std::vector<pcl::ClusterFieldStats> stats;
+  std::vector<pcl::ClusterClassHistogram> hist;
+};
+template <typename S>
+inline void driverFields(S& structure, DriverFields& f) {
+  if (f.channels > 0)
+    f.stats = structure.getClusterFieldStats(f.field.data(), (int64_t)(f.field.size() / (size_t)f.channels), f.channels, 4 * (int64_t)f.channels);
+  if (f.n_classes > 0) f.hist = structure.getClusterClassHistogram(f.classes.data(), (int64_t)f.classes.size(), f.n_classes);
+}
+
 // debug_prefix: when not empty, the reference's three voxel drawings (VS:510, 654, 1016) are written as
 // <prefix>_voxels.ply, <prefix>_clustered_voxels.ply, <prefix>_normals.ply
 // descriptors: when not null, receives getClusterDescriptors() (one per entry of clusters_points_idx, same order)
 // graph: when not null, receives getClusterGraph() and getClusterAdjacency() (cluster indices of clusters_points_idx)
 // boxes: when not null, receives getClusterBoxes(box_frame) (one per entry of clusters_points_idx, same order)
+// fields: when not null, its stats / hist receive getClusterFieldStats / getClusterClassHistogram of its inputs (same order)
 inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>& input_vector,
                            std::vector<std::vector<int>>& clusters_points_idx, DriverSummary* sum = nullptr,
                            const std::string& debug_prefix = std::string(), double ctor_resolution = 0.0,
                            std::vector<pcl::ClusterDescriptor>* descriptors = nullptr, DriverGraph* graph = nullptr,
-                           std::vector<pcl::ClusterBox>* boxes = nullptr, int box_frame = VGS_BOX_PRINCIPAL) {
+                           std::vector<pcl::ClusterBox>* boxes = nullptr, int box_frame = VGS_BOX_PRINCIPAL,
+                           DriverFields* fields = nullptr) {
   float voxel_size = 0.15f, graph_size = 0.5f, sig_p = 0.2f, sig_n = 0.2f, sig_o = 0.2f, sig_e = 0.2f, sig_c = 0.2f, sig_w = 2.0f,
         cut_thred = 0.3f;
   int points_min = 10, adjacency_min = 3, voxels_min = 3;
@@ -64,6 +83,7 @@ inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>&
   if (descriptors) *descriptors = voxel_structure.getClusterDescriptors();
   if (graph) { graph->edges = voxel_structure.getClusterGraph(); voxel_structure.getClusterAdjacency(graph->adjacency); }
   if (boxes) *boxes = voxel_structure.getClusterBoxes(box_frame);
+  if (fields) driverFields(voxel_structure, *fields);
   if (sum) {
     sum->points = (long)input_cloud->points.size(); sum->voxels = voxels; sum->clusters = voxel_structure.getClusterNum();
     sum->kept = (long)clusters_points_idx.size();
@@ -87,7 +107,8 @@ inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>&
 inline int segmentationSVGS(PCXYZPtr input_cloud, const std::vector<std::string>& input_vector,
                             std::vector<std::vector<int>>& clusters_points_idx, DriverSummary* sum = nullptr,
                             std::vector<pcl::ClusterDescriptor>* descriptors = nullptr, DriverGraph* graph = nullptr,
-                            std::vector<pcl::ClusterBox>* boxes = nullptr, int box_frame = VGS_BOX_PRINCIPAL) {
+                            std::vector<pcl::ClusterBox>* boxes = nullptr, int box_frame = VGS_BOX_PRINCIPAL,
+                            DriverFields* fields = nullptr) {
   // Task_File_SVGS.txt values
   float voxel_size = 0.05f, seed_size = 0.25f, graph_size = 0.5f, sig_p = 0.2f, sig_n = 0.2f, sig_o = 0.2f, sig_e = 0.2f, sig_c = 0.2f,
         sig_w = 1.0f, sig_a = 0.0f, sig_b = 0.25f, cut_thred = 0.5f;
@@ -122,6 +143,7 @@ inline int segmentationSVGS(PCXYZPtr input_cloud, const std::vector<std::string>
   if (descriptors) *descriptors = supervoxel_structure.getClusterDescriptors();
   if (graph) { graph->edges = supervoxel_structure.getClusterGraph(); supervoxel_structure.getClusterAdjacency(graph->adjacency); }
   if (boxes) *boxes = supervoxel_structure.getClusterBoxes(box_frame);
+  if (fields) driverFields(supervoxel_structure, *fields);
   if (sum) {
     sum->points = (long)input_cloud->points.size(); sum->voxels = supervoxel_structure.getVoxelNum();
     sum->supervoxels = supervoxel_structure.getSuperVoxelNum(); sum->clusters = supervoxel_structure.getClusterNum();

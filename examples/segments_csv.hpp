@@ -5,6 +5,8 @@
 // (w_sum / n_finite, NaN without a finite weight), w_min, w_max.
 // The --segment-boxes CSV of vgs_run: one row per kept cluster, row i = cluster i: label, center (3), half (3), frame (9: [r*3+j] =
 // component r of axis j), lo (3), hi (3), every value as %.17g.
+// The --segment-fields CSV of vgs_run: one row per kept cluster: label, then per field n_valid, mean, var (%.17g), min, max (%.9g); the
+// --segment-classes CSV: label, majority, majority_count, n_outside, hist_0 .. hist_{C-1}.
 #ifndef VGS_EXAMPLES_SEGMENTS_CSV_HPP_
 #define VGS_EXAMPLES_SEGMENTS_CSV_HPP_
 
@@ -58,6 +60,37 @@ inline int writeBoxesCsv(const std::string& path, const std::vector<pcl::Cluster
     for (int a = 0; a < 9; ++a) std::fprintf(f, ",%.17g", b.frame[a]);
     for (int a = 0; a < 3; ++a) std::fprintf(f, ",%.17g", b.lo[a]);
     for (int a = 0; a < 3; ++a) std::fprintf(f, ",%.17g", b.hi[a]);
+    std::fprintf(f, "\n");
+  }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
+inline int writeFieldStatsCsv(const std::string& path, const std::vector<std::string>& names, const std::vector<pcl::ClusterFieldStats>& stats) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "label");
+  for (const std::string& n : names) std::fprintf(f, ",%s_n_valid,%s_mean,%s_var,%s_min,%s_max", n.c_str(), n.c_str(), n.c_str(), n.c_str(), n.c_str());
+  std::fprintf(f, "\n");
+  for (size_t i = 0; i < stats.size(); ++i) {
+    const pcl::ClusterFieldStats& s = stats[i];
+    std::fprintf(f, "%zu", i);
+    for (size_t c = 0; c < names.size() && c < s.n_valid.size(); ++c)
+      std::fprintf(f, ",%lld,%.17g,%.17g,%.9g,%.9g", (long long)s.n_valid[c], s.mean[c], s.var[c], (double)s.vmin[c], (double)s.vmax[c]);
+    std::fprintf(f, "\n");
+  }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
+inline int writeClassHistCsv(const std::string& path, int n_classes, const std::vector<pcl::ClusterClassHistogram>& hist) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "label,majority,majority_count,n_outside");
+  for (int j = 0; j < n_classes; ++j) std::fprintf(f, ",hist_%d", j);
+  std::fprintf(f, "\n");
+  for (size_t i = 0; i < hist.size(); ++i) {
+    const pcl::ClusterClassHistogram& h = hist[i];
+    std::fprintf(f, "%zu,%d,%lld,%lld", i, (int)h.majority, (long long)h.majority_count, (long long)h.n_outside);
+    for (int64_t v : h.hist) std::fprintf(f, ",%lld", (long long)v);
     std::fprintf(f, "\n");
   }
   return std::fclose(f) == 0 ? 0 : -1;

@@ -5,6 +5,7 @@
 //   usage: vgs_run <task file> [--in <file.pcd|.ply>] [--out <file.pcd>] [--seed <n>] [--ascii] [--debug-meshes <prefix>]
 //                  [--segments <file.csv>] [--segment-graph <file.csv>] [--segment-adjacency <file.txt>]
 //                  [--segment-boxes <file.csv> [--box-frame principal|upright]]
+//                  [--segment-fields <file.csv> --fields a[,b,...]] [--segment-classes <file.csv> --class-field <name> --classes <C>]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
 // --segments writes one CSV row per kept cluster (getClusterDescriptors, row i = cluster i of the output): label, n_points, n_nodes,
@@ -16,7 +17,12 @@
 // edge), one "a,b" line per multimap entry in its iteration order.
 // --segment-boxes writes one CSV row per kept cluster (getClusterBoxes, row i = cluster i of the output): label, center (3), half (3),
 // frame (9), lo (3), hi (3), every value as %.17g; --box-frame selects the frame, principal (the default) or upright.
+// --segment-fields writes one CSV row per kept cluster (getClusterFieldStats over the fields --fields names, read from the input PCD: any
+// numeric type, COUNT 1): label, then per field n_valid, mean, var (%.17g), min, max (%.9g).  --segment-classes writes one row per kept
+// cluster (getClusterClassHistogram over the field --class-field names, classes 0 .. C-1 with C = --classes in 1 .. 1024): label, majority,
+// majority_count, n_outside, hist_0 .. hist_{C-1}.  A flag without its companions, or either with a PLY input, is a usage error (status 2).
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -38,11 +44,15 @@ static int writeAdjacency(const std::string& path, const std::multimap<uint32_t,
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::fprintf(stderr, "usage: %s <task file> [--in file.pcd] [--out file.pcd] [--seed n] [--ascii] [--debug-meshes prefix] [--segments file.csv] "
-                 "[--segment-graph file.csv] [--segment-adjacency file.txt] [--segment-boxes file.csv [--box-frame principal|upright]]\n",
+                 "[--segment-graph file.csv] [--segment-adjacency file.txt] [--segment-boxes file.csv [--box-frame principal|upright]] "
+                 "[--segment-fields file.csv --fields a[,b,...]] [--segment-classes file.csv --class-field name --classes C]\n",
                  argv[0]);
     return 2;
   }
-  std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file, boxes_file;
+  std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file, boxes_file, fields_file, classes_file, class_field;
+  std::vector<std::string> field_names;
+  bool have_fields = false, have_classes = false;
+  long n_classes = 0;
   int box_frame = VGS_BOX_PRINCIPAL;
   uint64_t seed = 0;
   bool ascii = false;
@@ -62,8 +72,32 @@ int main(int argc, char** argv) {
       else if (!std::strcmp(argv[a], "upright")) box_frame = VGS_BOX_UPRIGHT;
       else { std::fprintf(stderr, "--box-frame %s: principal or upright\n", argv[a]); return 2; }
     }
+    else if (!std::strcmp(argv[a], "--segment-fields") && a + 1 < argc) fields_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--fields") && a + 1 < argc) {
+      have_fields = true;
+      const std::string list = argv[++a];
+      for (size_t b = 0; b <= list.size();) {
+        const size_t e = std::min(list.find(',', b), list.size());
+        if (e > b) field_names.push_back(list.substr(b, e - b));
+        b = e + 1;
+      }
+    }
+    else if (!std::strcmp(argv[a], "--segment-classes") && a + 1 < argc) classes_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--class-field") && a + 1 < argc) class_field = argv[++a];
+    else if (!std::strcmp(argv[a], "--classes") && a + 1 < argc) {
+      have_classes = true;
+      char* end = nullptr;
+      n_classes = std::strtol(argv[++a], &end, 10);
+      if (end == argv[a] || *end != 0 || n_classes < 1 || n_classes > 1024) { std::fprintf(stderr, "--classes %s: a number in 1 .. 1024\n", argv[a]); return 2; }
+    }
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
+  if (!fields_file.empty() && (!have_fields || field_names.empty())) { std::fprintf(stderr, "--segment-fields needs --fields a[,b,...]\n"); return 2; }
+  if (!fields_file.empty() && field_names.size() > 64) { std::fprintf(stderr, "--fields: at most 64 fields\n"); return 2; }
+  if (!classes_file.empty() && class_field.empty()) { std::fprintf(stderr, "--segment-classes needs --class-field <name>\n"); return 2; }
+  if (!classes_file.empty() && !have_classes) { std::fprintf(stderr, "--segment-classes needs --classes <C>\n"); return 2; }
+  if (fields_file.empty() && have_fields) { std::fprintf(stderr, "--fields needs --segment-fields <file.csv>\n"); return 2; }
+  if (classes_file.empty() && (have_classes || !class_field.empty())) { std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv>\n"); return 2; }
   const std::vector<std::string> task = inputTaskTxtFile(argv[1]);
   if (task.size() < 51) { std::fprintf(stderr, "%s: not a task file (%zu lines)\n", argv[1], task.size()); return 2; }
   const int method = std::atoi(task[24].c_str());
@@ -77,7 +111,27 @@ int main(int argc, char** argv) {
   }
   PCXYZPtr cloud(new PCXYZ);
   const bool ply = in_file.size() > 4 && in_file.substr(in_file.size() - 4) == ".ply";
+  if (ply && !(fields_file.empty() && classes_file.empty())) {   // (a usage error: nothing has been loaded yet)
+    std::fprintf(stderr, "--segment-fields / --segment-classes read their fields from a PCD input, not from %s\n", in_file.c_str());
+    return 2;
+  }
   if ((ply ? inputPointCloudData2(in_file, cloud) : inputPointCloudData(in_file, cloud)) != 0) return 1;
+  DriverFields fields;
+  DriverFields* want_fields = (fields_file.empty() && classes_file.empty()) ? nullptr : &fields;
+  if (want_fields) {   // the attributes ride in the input PCD, one row per point of the cloud
+    std::string err;
+    if (!fields_file.empty()) {
+      if (vgs_io::read_pcd_fields(in_file, field_names, fields.field, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
+      fields.channels = (int)field_names.size();
+    }
+    if (!classes_file.empty()) {
+      std::vector<float> v;
+      if (vgs_io::read_pcd_fields(in_file, {class_field}, v, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
+      fields.classes.resize(v.size());
+      for (size_t i = 0; i < v.size(); ++i) fields.classes[i] = (v[i] >= -2147483648.0f && v[i] < 2147483648.0f) ? (int32_t)v[i] : -1;
+      fields.n_classes = (int)n_classes;
+    }
+  }
   std::vector<std::vector<int>> clusters;
   DriverSummary sum;
   std::vector<pcl::ClusterDescriptor> desc;
@@ -88,9 +142,9 @@ int main(int argc, char** argv) {
   std::vector<pcl::ClusterBox>* want_boxes = boxes_file.empty() ? nullptr : &boxes;
   try {
     if (method == 2) {
-      if (segmentationVGS(cloud, task, clusters, &sum, debug_prefix, 0.0, want, want_graph, want_boxes, box_frame) != 0) { std::fprintf(stderr, "cannot write the debug meshes\n"); return 1; }
+      if (segmentationVGS(cloud, task, clusters, &sum, debug_prefix, 0.0, want, want_graph, want_boxes, box_frame, want_fields) != 0) { std::fprintf(stderr, "cannot write the debug meshes\n"); return 1; }
     } else {
-      segmentationSVGS(cloud, task, clusters, &sum, want, want_graph, want_boxes, box_frame);
+      segmentationSVGS(cloud, task, clusters, &sum, want, want_graph, want_boxes, box_frame, want_fields);
     }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "error: %s\n", e.what());
@@ -100,6 +154,8 @@ int main(int argc, char** argv) {
   if (want && writeSegmentsCsv(segments_file, desc) != 0) { std::fprintf(stderr, "cannot write %s\n", segments_file.c_str()); return 1; }
   if (!graph_file.empty() && writeGraphCsv(graph_file, graph.edges) != 0) { std::fprintf(stderr, "cannot write %s\n", graph_file.c_str()); return 1; }
   if (want_boxes && writeBoxesCsv(boxes_file, boxes) != 0) { std::fprintf(stderr, "cannot write %s\n", boxes_file.c_str()); return 1; }
+  if (!fields_file.empty() && writeFieldStatsCsv(fields_file, field_names, fields.stats) != 0) { std::fprintf(stderr, "cannot write %s\n", fields_file.c_str()); return 1; }
+  if (!classes_file.empty() && writeClassHistCsv(classes_file, fields.n_classes, fields.hist) != 0) { std::fprintf(stderr, "cannot write %s\n", classes_file.c_str()); return 1; }
   if (!adjacency_file.empty() && writeAdjacency(adjacency_file, graph.adjacency) != 0) {
     std::fprintf(stderr, "cannot write %s\n", adjacency_file.c_str());
     return 1;

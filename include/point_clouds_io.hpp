@@ -17,6 +17,7 @@
 #ifndef POINT_CLOUDS_IO_HPP_
 #define POINT_CLOUDS_IO_HPP_
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -117,17 +118,11 @@ inline double pcd_value(const unsigned char* p, const PcdField& f) {
   }
 }
 
-// reads the x, y, z fields (any order, any numeric type) of a PCD file; other fields are skipped
-inline int read_pcd_xyz(const std::string& name, std::vector<pcl::PointXYZ>& pts, uint32_t* width, uint32_t* height, std::string& err) {
-  std::ifstream f(name, std::ios::binary);
-  if (!f.is_open()) { err = "cannot open " + name; return -1; }
-  PcdHeader h;
-  if (!parse_pcd_header(f, h, err)) return -1;
-  int fx = -1, fy = -1, fz = -1;
-  for (size_t k = 0; k < h.fields.size(); ++k) {
-    if (h.fields[k].name == "x") fx = (int)k; else if (h.fields[k].name == "y") fy = (int)k; else if (h.fields[k].name == "z") fz = (int)k;
-  }
-  if (fx < 0 || fy < 0 || fz < 0) { err = "PCD file has no x / y / z fields"; return -1; }
+// The body of a PCD file behind its header, in any of the three DATA layouts: the first value of the fields cols[0 .. C-1] (indices into
+// h.fields, any numeric type) of every point i goes to sink(i, c, value); other fields are skipped.  `prepare(n)` runs once the sizes have
+// been checked against the file, before the first value.  One decoder for read_pcd_xyz and read_pcd_fields.
+template <class Prepare, class Sink>
+inline int read_pcd_body(std::ifstream& f, const PcdHeader& h, const std::vector<int>& cols, Prepare&& prepare, Sink&& sink, std::string& err) {
   const size_t n = (size_t)h.points;
   uint64_t left = 0;   // bytes of the file behind the header
   {
@@ -142,24 +137,27 @@ inline int read_pcd_xyz(const std::string& name, std::vector<pcl::PointXYZ>& pts
     if (h.data == "binary_compressed" && (uint64_t)n * (uint64_t)h.point_size > 88u * left + 64u) { err = "PCD header announces more points than the file can hold"; return -1; }
   }
   try {
-  pts.assign(n, pcl::PointXYZ());
+  prepare(n);
   if (h.data == "ascii") {
     std::string line;
     size_t i = 0;
     std::vector<double> vals;
+    std::vector<double> got(cols.size());
     while (i < n && std::getline(f, line)) {
       if (line.empty() || line == "\r") continue;
       vals.clear();
       const char* s = line.c_str();
       char* e = nullptr;
       while (true) { const double v = std::strtod(s, &e); if (e == s) break; vals.push_back(v); s = e; }
-      size_t col = 0; double xyz[3] = {0, 0, 0};
+      size_t col = 0;
+      std::fill(got.begin(), got.end(), 0.0);
       for (size_t k = 0; k < h.fields.size(); ++k) {
         if (col >= vals.size()) { err = "PCD ascii row " + std::to_string(i) + " is short"; return -1; }
-        if ((int)k == fx) xyz[0] = vals[col]; else if ((int)k == fy) xyz[1] = vals[col]; else if ((int)k == fz) xyz[2] = vals[col];
+        for (size_t c = 0; c < cols.size(); ++c) if ((int)k == cols[c]) got[c] = vals[col];
         col += (size_t)h.fields[k].count;
       }
-      pts[i++] = pcl::PointXYZ((float)xyz[0], (float)xyz[1], (float)xyz[2]);
+      for (size_t c = 0; c < cols.size(); ++c) sink(i, c, got[c]);
+      ++i;
     }
     if (i != n) { err = "PCD ascii body has " + std::to_string(i) + " of " + std::to_string(n) + " points"; return -1; }
   } else if (h.data == "binary") {
@@ -168,8 +166,7 @@ inline int read_pcd_xyz(const std::string& name, std::vector<pcl::PointXYZ>& pts
     if ((size_t)f.gcount() != buf.size()) { err = "PCD binary body is truncated"; return -1; }
     for (size_t i = 0; i < n; ++i) {
       const unsigned char* p = buf.data() + i * (size_t)h.point_size;
-      pts[i] = pcl::PointXYZ((float)pcd_value(p + h.fields[fx].offset, h.fields[fx]), (float)pcd_value(p + h.fields[fy].offset, h.fields[fy]),
-                             (float)pcd_value(p + h.fields[fz].offset, h.fields[fz]));
+      for (size_t c = 0; c < cols.size(); ++c) { const PcdField& fd = h.fields[(size_t)cols[c]]; sink(i, c, pcd_value(p + fd.offset, fd)); }
     }
   } else if (h.data == "binary_compressed") {
     // two 32-bit sizes, then the LZF stream of the points stored field by field (structure of arrays)
@@ -185,8 +182,10 @@ inline int read_pcd_xyz(const std::string& name, std::vector<pcl::PointXYZ>& pts
     size_t acc = 0;
     for (size_t k = 0; k < h.fields.size(); ++k) { start[k] = acc; acc += n * (size_t)(h.fields[k].size * h.fields[k].count); }
     for (size_t i = 0; i < n; ++i) {
-      auto at = [&](int k) { return pcd_value(out.data() + start[(size_t)k] + i * (size_t)(h.fields[(size_t)k].size * h.fields[(size_t)k].count), h.fields[(size_t)k]); };
-      pts[i] = pcl::PointXYZ((float)at(fx), (float)at(fy), (float)at(fz));
+      for (size_t c = 0; c < cols.size(); ++c) {
+        const size_t k = (size_t)cols[c];
+        sink(i, c, pcd_value(out.data() + start[k] + i * (size_t)(h.fields[k].size * h.fields[k].count), h.fields[k]));
+      }
     }
   } else {
     err = "unsupported PCD DATA '" + h.data + "'";
@@ -196,9 +195,45 @@ inline int read_pcd_xyz(const std::string& name, std::vector<pcl::PointXYZ>& pts
     err = "PCD file is too large for this host's memory";
     return -1;
   }
+  return 0;
+}
+
+// reads the x, y, z fields (any order, any numeric type) of a PCD file; other fields are skipped
+inline int read_pcd_xyz(const std::string& name, std::vector<pcl::PointXYZ>& pts, uint32_t* width, uint32_t* height, std::string& err) {
+  std::ifstream f(name, std::ios::binary);
+  if (!f.is_open()) { err = "cannot open " + name; return -1; }
+  PcdHeader h;
+  if (!parse_pcd_header(f, h, err)) return -1;
+  int fx = -1, fy = -1, fz = -1;
+  for (size_t k = 0; k < h.fields.size(); ++k) {
+    if (h.fields[k].name == "x") fx = (int)k; else if (h.fields[k].name == "y") fy = (int)k; else if (h.fields[k].name == "z") fz = (int)k;
+  }
+  if (fx < 0 || fy < 0 || fz < 0) { err = "PCD file has no x / y / z fields"; return -1; }
+  if (read_pcd_body(f, h, {fx, fy, fz}, [&](size_t n) { pts.assign(n, pcl::PointXYZ()); },
+                    [&](size_t i, size_t c, double v) { (c == 0 ? pts[i].x : (c == 1 ? pts[i].y : pts[i].z)) = (float)v; }, err) != 0)
+    return -1;
   if (width) *width = (uint32_t)h.width;
   if (height) *height = (uint32_t)h.height;
   return 0;
+}
+
+// reads the named fields of a PCD file (any order, any numeric type, COUNT 1 only) as floats: out = N x C, row-major, C = field_names.size(),
+// row i = point i of the file.  A field the file does not have is an error that names it.
+inline int read_pcd_fields(const std::string& name, const std::vector<std::string>& field_names, std::vector<float>& out, std::string& err) {
+  std::ifstream f(name, std::ios::binary);
+  if (!f.is_open()) { err = "cannot open " + name; return -1; }
+  PcdHeader h;
+  if (!parse_pcd_header(f, h, err)) return -1;
+  std::vector<int> cols;
+  for (const std::string& want : field_names) {
+    int at = -1;
+    for (size_t k = 0; k < h.fields.size(); ++k) if (h.fields[k].name == want) { at = (int)k; break; }
+    if (at < 0) { err = "PCD file " + name + " has no field '" + want + "'"; return -1; }
+    if (h.fields[(size_t)at].count != 1) { err = "PCD field '" + want + "' has COUNT " + std::to_string(h.fields[(size_t)at].count) + ": only COUNT 1 is read"; return -1; }
+    cols.push_back(at);
+  }
+  const size_t C = cols.size();
+  return read_pcd_body(f, h, cols, [&](size_t n) { out.assign(n * C, 0.0f); }, [&](size_t i, size_t c, double v) { out[i * C + c] = (float)v; }, err);
 }
 
 // PLY: the vertex element's x, y, z properties (any scalar type); ascii, binary_little_endian and binary_big_endian;

@@ -334,6 +334,44 @@ vgs_status vgs_set_halo_labels(vgs_ctx* ctx, const uint64_t* code, const int32_t
  * segmented and for a context that is not a tile context. */
 vgs_status vgs_get_own_segment_graph(vgs_ctx* ctx, int64_t K, int64_t* n_edges, int32_t* seg_ab, int64_t* n_pairs, int64_t* n_finite,
                                      int32_t* nodes_ab, double* w_sum, float* w_min, float* w_max);
+/* Per-segment statistics of point attributes the CALLER supplies (no reference counterpart: what a user of a segmentation does first with
+ * intensity, colour, time, class scores or a ground-truth class).  Row k covers exactly the points whose label (vgs_get_point_labels) is k,
+ * K = counts[VGS_N_KEPT] rows; points with label -1 (outside the octree, dropped clusters) contribute nothing.  Any output pointer may be
+ * NULL; K = 0 writes nothing.  Computed on the device on every call, nothing cached (the input is the caller's).
+ * Input: n must equal counts[VGS_N_POINTS]; row i belongs to input point i; channel c of point i is the float at byte
+ * i * stride_bytes + 4 * c; stride_bytes >= 4 * n_channels and a multiple of 4; 1 <= n_channels <= 64.  VGS_E_ARG otherwise (the message
+ * names the argument).  The host variant uploads once into a buffer of the context; the device variant reads field_dev (HBM, the context's
+ * device; complete before the call) in place.
+ * Outputs, each K x n_channels, row-major.  A value is valid when it is finite: NaN and +-inf are skipped.
+ *   n_valid  int64   valid values
+ *   anchor   double  the shift of the sums.  One point p per segment, the same for every channel -- the segment's first point in the order of
+ *                    the descriptor chunks (csrc/segdesc.hip); which one is not specified, it does not change from call to call --
+ *                    anchor[k, c] = (double)field[p, c] if that value is valid, 0.0 otherwise.  Reported so that a reader can restate the
+ *                    arithmetic: it keeps a field of large offset and small spread (a GPS time) from losing its variance
+ *   mean     double  anchor + S1 / n            with d = (double)x - anchor per valid x, S1 = sum d, S2 = sum d * d, n = n_valid
+ *   var      double  max(0, S2 / n - (S1 / n) * (S1 / n))   population variance
+ *   vmin, vmax  float  min and max of the valid values (a zero may carry either sign, as in bbox6)
+ * n = 0: mean, var, vmin, vmax are NaN and anchor is 0.  Every product, quotient and sum above is one fp64 operation in the association
+ * written (no FMA).  The sums have a fixed shape (csrc/segdesc.hip's rule: the point of a lane depends on (chunk, lane, step) only, fixed
+ * butterfly, waves in index order, partials by lane stride then butterfly) and there are no float atomics: bit-identical from call to call
+ * and from engine to engine for the same cloud and parameters.
+ * VGS_E_STATE before the context is segmented and for a tile context.  No side effects: the labels and every cached table stay as they are. */
+vgs_status vgs_segment_field_stats(vgs_ctx* ctx, const float* field_host, int64_t n, int32_t n_channels, int64_t stride_bytes,
+                                   int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax);
+vgs_status vgs_segment_field_stats_device(vgs_ctx* ctx, const float* field_dev, int64_t n, int32_t n_channels, int64_t stride_bytes,
+                                          int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax);
+/* Per-segment histogram of a per-point class (segment voting; the contingency table of segments against ground-truth classes).  Rows, n,
+ * NULL outputs, K = 0, state and side effects as above; cls holds one int32 per input point; 1 <= n_classes <= 1024 (VGS_E_ARG).
+ * VGS_E_UNSUPPORTED, with the numbers in the message, if K * n_classes exceeds 2^27.
+ *   hist            int64  K x n_classes: hist[k, j] = points of segment k with class j, 0 <= j < n_classes
+ *   n_outside       int64  K: points of segment k whose class is negative or >= n_classes
+ *   majority        int32  K: the lowest j with the largest hist[k, j]; -1 when every count is 0
+ *   majority_count  int64  K: that count (0 with majority -1)
+ * Integer counts: every summation order gives the same bits.  Counted per chunk in LDS, then added to the table with integer atomics. */
+vgs_status vgs_segment_class_histogram(vgs_ctx* ctx, const int32_t* cls_host, int64_t n, int32_t n_classes, int64_t* hist, int64_t* n_outside,
+                                       int32_t* majority, int64_t* majority_count);
+vgs_status vgs_segment_class_histogram_device(vgs_ctx* ctx, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* hist,
+                                              int64_t* n_outside, int32_t* majority, int64_t* majority_count);
 
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.

@@ -153,6 +153,58 @@ inline std::vector<ClusterBox> cluster_boxes(vgs_ctx* c, int64_t k, int frame) {
 }
 }  // namespace vgs_detail
 
+// Extension (no VS / SS line): the statistics of a caller's point attribute over one kept cluster, one entry per channel, as
+// vgs_segment_field_stats (include/vgs.h) defines them
+struct ClusterFieldStats {
+  std::vector<int64_t> n_valid;          // finite values of the channel
+  std::vector<double> anchor, mean, var; // the shift of the sums; anchor + S1 / n; population variance (NaN without a finite value)
+  std::vector<float> vmin, vmax;         // min and max of the finite values (NaN without one)
+};
+// Extension (no VS / SS line): the class counts of one kept cluster, as vgs_segment_class_histogram (include/vgs.h) defines them
+struct ClusterClassHistogram {
+  std::vector<int64_t> hist;    // points per class 0 .. n_classes - 1
+  int64_t n_outside = 0;        // points whose class is negative or >= n_classes
+  int32_t majority = -1;        // the lowest class with the largest count, -1 without one
+  int64_t majority_count = 0;
+};
+
+namespace vgs_detail {
+// one row per kept cluster, in label order -- the order of getClusterIdx; stride in bytes
+inline std::vector<ClusterFieldStats> cluster_field_stats(vgs_ctx* c, int64_t k, const float* field, int64_t n, int32_t channels, int64_t stride) {
+  const size_t ch = channels > 0 ? (size_t)channels : 0, kc = (size_t)k * ch;
+  std::vector<int64_t> nv(kc + 1);
+  std::vector<double> an(kc + 1), me(kc + 1), va(kc + 1);
+  std::vector<float> mn(kc + 1), mx(kc + 1);
+  // (called for k = 0 too: the state and argument checks are the library's)
+  check(c, vgs_segment_field_stats(c, field, n, channels, stride, nv.data(), an.data(), me.data(), va.data(), mn.data(), mx.data()),
+        "vgs_segment_field_stats");
+  std::vector<ClusterFieldStats> out((size_t)k);
+  for (size_t i = 0; i < (size_t)k; ++i) {
+    ClusterFieldStats& f = out[i];
+    f.n_valid.assign(nv.begin() + i * ch, nv.begin() + (i + 1) * ch);
+    f.anchor.assign(an.begin() + i * ch, an.begin() + (i + 1) * ch);
+    f.mean.assign(me.begin() + i * ch, me.begin() + (i + 1) * ch);
+    f.var.assign(va.begin() + i * ch, va.begin() + (i + 1) * ch);
+    f.vmin.assign(mn.begin() + i * ch, mn.begin() + (i + 1) * ch);
+    f.vmax.assign(mx.begin() + i * ch, mx.begin() + (i + 1) * ch);
+  }
+  return out;
+}
+inline std::vector<ClusterClassHistogram> cluster_class_histogram(vgs_ctx* c, int64_t k, const int32_t* cls, int64_t n, int32_t n_classes) {
+  const size_t nc = n_classes > 0 ? (size_t)n_classes : 0;
+  std::vector<int64_t> hi((size_t)k * nc + 1), no((size_t)k + 1), mc((size_t)k + 1);
+  std::vector<int32_t> ma((size_t)k + 1);
+  check(c, vgs_segment_class_histogram(c, cls, n, n_classes, hi.data(), no.data(), ma.data(), mc.data()), "vgs_segment_class_histogram");
+  std::vector<ClusterClassHistogram> out((size_t)k);
+  for (size_t i = 0; i < (size_t)k; ++i) {
+    ClusterClassHistogram& h = out[i];
+    h.hist.assign(hi.begin() + i * nc, hi.begin() + (i + 1) * nc);
+    h.n_outside = no[i]; h.majority = ma[i]; h.majority_count = mc[i];
+  }
+  return out;
+}
+}  // namespace vgs_detail
+
 // Extension (no VS / SS line): one edge of the adjacency graph of the kept clusters, as vgs_get_segment_graph (include/vgs.h) defines it
 struct ClusterEdge {
   int32_t a = 0, b = 0;        // cluster indices (getClusterIdx order), a < b
@@ -320,6 +372,18 @@ class VoxelBasedSegmentation {
   }
   // Extension (no VS line): PCL's getSupervoxelAdjacency idiom over getClusterGraph -- both directions of every edge
   void getClusterAdjacency(std::multimap<uint32_t, uint32_t>& adjacency) { vgs_detail::cluster_adjacency(getClusterGraph(), adjacency); }
+  // Extension (no VS line): row i reduces a per-point attribute (n rows of `channels` floats in input order, `stride_bytes` apart) over
+  // getClusterIdx()[i]; empty before drawColorMapofPointsinClusters, like getClusterDescriptors
+  std::vector<ClusterFieldStats> getClusterFieldStats(const float* field, int64_t n, int32_t channels, int64_t stride_bytes) {
+    if (!drawn_) return {};
+    return vgs_detail::cluster_field_stats(ctx(), count(VGS_N_KEPT), field, n, channels, stride_bytes);
+  }
+  // Extension (no VS line): row i counts a per-point class (n int32 in input order) over getClusterIdx()[i]; empty before
+  // drawColorMapofPointsinClusters
+  std::vector<ClusterClassHistogram> getClusterClassHistogram(const int32_t* classes, int64_t n, int32_t n_classes) {
+    if (!drawn_) return {};
+    return vgs_detail::cluster_class_histogram(ctx(), count(VGS_N_KEPT), classes, n, n_classes);
+  }
 
   vgs_ctx* ctx() { return ctx_.get(); }
 
@@ -418,6 +482,15 @@ class SuperVoxelBasedSegmentation {
   std::vector<ClusterEdge> getClusterGraph() { return vgs_detail::cluster_graph(ctx()); }
   // Extension (no SS line): PCL's getSupervoxelAdjacency idiom over getClusterGraph -- both directions of every edge
   void getClusterAdjacency(std::multimap<uint32_t, uint32_t>& adjacency) { vgs_detail::cluster_adjacency(getClusterGraph(), adjacency); }
+  // Extension (no SS line): row i reduces a per-point attribute (n rows of `channels` floats in input order, `stride_bytes` apart) over
+  // getClusterIdx()[i]
+  std::vector<ClusterFieldStats> getClusterFieldStats(const float* field, int64_t n, int32_t channels, int64_t stride_bytes) {
+    return vgs_detail::cluster_field_stats(ctx(), count(VGS_N_KEPT), field, n, channels, stride_bytes);
+  }
+  // Extension (no SS line): row i counts a per-point class (n int32 in input order) over getClusterIdx()[i]
+  std::vector<ClusterClassHistogram> getClusterClassHistogram(const int32_t* classes, int64_t n, int32_t n_classes) {
+    return vgs_detail::cluster_class_histogram(ctx(), count(VGS_N_KEPT), classes, n, n_classes);
+  }
   vgs_ctx* ctx() { return ctx_.get(); }
 
  private:

@@ -106,6 +106,10 @@ SYMBOLS = [
     ("vgs_get_segment_graph_device", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_set_halo_labels", C.c_int, [_P, _P, _P, C.c_int64]),
     ("vgs_get_own_segment_graph", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_segment_field_stats", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("vgs_segment_field_stats_device", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("vgs_segment_class_histogram", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    ("vgs_segment_class_histogram_device", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     ("vgs_grid_state_init", C.c_int, [C.POINTER(VgsGridState)]),
     ("vgs_grid_advance", C.c_int, [_P, C.POINTER(VgsGridState)]),
     ("vgs_points_bbox", C.c_int, [_P, _P, C.POINTER(C.c_int64)]),

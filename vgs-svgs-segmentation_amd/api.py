@@ -324,6 +324,81 @@ class Engine:
         self._ck(self._L.vgs_get_segment_graph_device(self._h, C.byref(E), *(C.byref(p) for p in ps)))
         return E.value, {name: p.value for (name, _, _), p in zip(self.GRAPH_FIELDS, ps)}
 
+    # per (segment, channel): (field, dtype) of vgs_segment_field_stats, in its argument order
+    FIELD_STAT_FIELDS = (("n_valid", np.int64), ("anchor", np.float64), ("mean", np.float64), ("var", np.float64), ("vmin", np.float32),
+                         ("vmax", np.float32))
+    # per segment: (field, dtype, values per segment; 0 = n_classes) of vgs_segment_class_histogram, in its argument order
+    CLASS_HIST_FIELDS = (("hist", np.int64, 0), ("n_outside", np.int64, 1), ("majority", np.int32, 1), ("majority_count", np.int64, 1))
+
+    @staticmethod
+    def _is_torch(a):
+        return type(a).__module__.split(".")[0] == "torch"
+
+    def _device_input(self, t, dtype_name, what):
+        """A torch tensor on the context's device, complete before the library reads it on its own stream."""
+        import torch
+        if t.dtype != getattr(torch, dtype_name):
+            raise ValueError(f"{what} must be {dtype_name}")
+        if t.device.type != "cuda" or (t.device.index or 0) != int(self.params.device):
+            raise ValueError(f"{what} must be a numpy array or a torch tensor on the context's device")
+        torch.cuda.synchronize(t.device)
+
+    def segment_field_stats(self, field):
+        """Per-segment statistics of a per-point attribute, row k = the points labelled k (include/vgs.h, vgs_segment_field_stats): a dict
+        of arrays n_valid (int64), anchor, mean, var (float64), vmin, vmax (float32), each (K, C).  `field`: float32 of shape (N,) or (N, C)
+        in input order, C-contiguous or with a row stride (a multiple of 4 bytes; the channels of a row adjacent); a numpy array, or a torch
+        tensor on the context's device, which is read in place.  NaN and +-inf are skipped.  Computed on the device on every call,
+        bit-identical from call to call."""
+        K = self.counts()["kept"]
+        dev = self._is_torch(field)
+        if dev:
+            self._device_input(field, "float32", "field")
+            if field.dim() == 1:
+                field = field.unsqueeze(1)
+            if field.dim() != 2 or (field.shape[1] > 1 and field.stride(1) != 1) or (field.shape[0] > 1 and field.stride(0) < field.shape[1]):
+                raise ValueError("field must be (N,) or (N, C) with adjacent channels and a row stride of at least C")
+            n, ch = int(field.shape[0]), int(field.shape[1])
+            stride = int(field.stride(0)) * 4 if n > 1 else ch * 4
+            ptr, fn = C.c_void_p(field.data_ptr()), self._L.vgs_segment_field_stats_device
+        else:
+            field = np.asarray(field)
+            if field.dtype != np.float32:
+                raise ValueError("field must be float32")
+            if field.ndim == 1:
+                field = field[:, None]
+            if field.ndim != 2:
+                raise ValueError("field must be (N,) or (N, C)")
+            n, ch = field.shape
+            if (ch > 1 and field.strides[1] != 4) or (n > 1 and (field.strides[0] < 4 * ch or field.strides[0] % 4)):
+                field = np.ascontiguousarray(field)   # (negative, interleaved or odd strides: the library takes rows of adjacent channels, 4-byte steps)
+            stride = int(field.strides[0]) if n > 1 else ch * 4
+            ptr, fn = _ptr(field), self._L.vgs_segment_field_stats
+        out = {name: np.zeros((K, max(ch, 0)), dtype=dt) for name, dt in self.FIELD_STAT_FIELDS}
+        self._ck(fn(self._h, ptr, n, ch, stride, *(_ptr(out[name]) for name, _ in self.FIELD_STAT_FIELDS)))
+        return out
+
+    def segment_class_histogram(self, classes, n_classes):
+        """Per-segment histogram of a per-point class, row k = the points labelled k (include/vgs.h, vgs_segment_class_histogram): a dict of
+        hist (K, n_classes) int64, n_outside (K,) int64 -- points whose class is negative or >= n_classes --, majority (K,) int32 -- the
+        lowest class with the largest count, -1 without one -- and majority_count (K,) int64.  `classes`: int32 of shape (N,) in input
+        order, a numpy array or a torch tensor on the context's device."""
+        K = self.counts()["kept"]
+        nc = int(n_classes)
+        if self._is_torch(classes):
+            self._device_input(classes, "int32", "classes")
+            if classes.dim() != 1 or (classes.shape[0] > 1 and classes.stride(0) != 1):
+                raise ValueError("classes must be a contiguous (N,) tensor")
+            n, ptr, fn = int(classes.shape[0]), C.c_void_p(classes.data_ptr()), self._L.vgs_segment_class_histogram_device
+        else:
+            classes = np.asarray(classes)
+            if classes.dtype != np.int32 or classes.ndim != 1:
+                raise ValueError("classes must be int32 of shape (N,)")
+            classes = np.ascontiguousarray(classes)
+            n, ptr, fn = classes.shape[0], _ptr(classes), self._L.vgs_segment_class_histogram
+        out = {name: np.zeros((K, max(nc, 0)) if w == 0 else K, dtype=dt) for name, dt, w in self.CLASS_HIST_FIELDS}
+        self._ck(fn(self._h, ptr, n, nc, *(_ptr(out[name]) for name, _, _ in self.CLASS_HIST_FIELDS)))
+        return out
+
     # ---- a sequence of clouds: uploads of the next cloud and downloads of the last labels overlap the stages
     def stage_points(self, xyz):
         """Start the copy of the NEXT cloud (ideally a pinned array, see pinned_empty) and return at once."""
@@ -451,6 +526,19 @@ class VoxelBasedSegmentation:
             return {name: np.zeros((0, w) if w > 1 else 0, dtype=dt) for name, dt, w in Engine.GRAPH_FIELDS}
         return self._eng.segment_graph()
 
+    def getClusterFieldStats(self, field):
+        """Extension (no VS line): row i reduces `field` over getClusterIdx()[i] -- both are in label order (Engine.segment_field_stats)."""
+        if not self._drawn:
+            ch = 1 if np.ndim(field) == 1 else int(np.shape(field)[1])
+            return {name: np.zeros((0, ch), dtype=dt) for name, dt in Engine.FIELD_STAT_FIELDS}
+        return self._eng.segment_field_stats(field)
+
+    def getClusterClassHistogram(self, classes, n_classes):
+        """Extension (no VS line): row i counts `classes` over getClusterIdx()[i] -- both are in label order (Engine.segment_class_histogram)."""
+        if not self._drawn:
+            return {name: np.zeros((0, int(n_classes)) if w == 0 else 0, dtype=dt) for name, dt, w in Engine.CLASS_HIST_FIELDS}
+        return self._eng.segment_class_histogram(classes, n_classes)
+
     @property
     def engine(self):
         return self._eng
@@ -534,6 +622,14 @@ class SuperVoxelBasedSegmentation:
     def getClusterGraph(self):
         """Extension (no SS line): the adjacency graph of the kept clusters, labels = getClusterIdx() indices (Engine.segment_graph)."""
         return self._eng.segment_graph()
+
+    def getClusterFieldStats(self, field):
+        """Extension (no SS line): row i reduces `field` over getClusterIdx()[i] -- both are in label order (Engine.segment_field_stats)."""
+        return self._eng.segment_field_stats(field)
+
+    def getClusterClassHistogram(self, classes, n_classes):
+        """Extension (no SS line): row i counts `classes` over getClusterIdx()[i] -- both are in label order (Engine.segment_class_histogram)."""
+        return self._eng.segment_class_histogram(classes, n_classes)
 
     @property
     def engine(self):

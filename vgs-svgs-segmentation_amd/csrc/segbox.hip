@@ -105,29 +105,12 @@ __device__ __forceinline__ void sb_chunk_body(const float* __restrict__ xs, cons
   __shared__ uint32_t s_dl[SD_CHUNK];    // sorted position - virtual position of the same (mod 2^32)
   __shared__ double s_red[SD_TB / 64][SB_REC];
   const uint32_t c = blockIdx.x;
-  if (c >= seg_chunk[K]) return;
-  // segment of chunk c: the last k with seg_chunk[k] <= c (every segment has at least one chunk)
-  uint32_t lo = 0, hi = K - 1;
-  while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (seg_chunk[mid] <= c) lo = mid; else hi = mid - 1; }
-  const uint32_t k = lo;
-  const uint32_t n0 = seg_node[k], n1 = seg_node[k + 1];
-  const uint32_t a = vp[n0] + (c - seg_chunk[k]) * SD_CHUNK;
-  const uint32_t b = min(a + SD_CHUNK, vp[n1]);
-  if (n1 <= n0 || a >= b) {   // (cannot happen for a kept segment; an empty record keeps the fold well defined)
-    sb_empty_record(part + (size_t)c * SB_REC);
+  SdChunk wk;
+  if (!sd_walk(vox_start, ids, vp, seg_node, seg_chunk, K, s_vp, s_dl, wk)) {
+    if (wk.k != 0xffffffffu) sb_empty_record(part + (size_t)c * SB_REC);   // (an empty record keeps the fold well defined)
     return;
   }
-  // nodes that overlap [a, b): the last node starting at or before a ... the last node starting before b; at most b - a <= SD_CHUNK nodes
-  uint32_t i0 = n0, i1 = n1 - 1;
-  while (i0 < i1) { const uint32_t mid = (i0 + i1 + 1) >> 1; if (vp[mid] <= a) i0 = mid; else i1 = mid - 1; }
-  uint32_t j0 = i0 + 1, j1 = n1;
-  while (j0 < j1) { const uint32_t mid = (j0 + j1) >> 1; if (vp[mid] < b) j0 = mid + 1; else j1 = mid; }
-  const uint32_t m = min(j0 - i0, (uint32_t)SD_CHUNK);   // (the bound above; the clamp only guards the LDS arrays)
-  for (uint32_t t = threadIdx.x; t < m; t += SD_TB) {
-    const uint32_t i = i0 + t, q = vp[i];
-    s_vp[t] = q;
-    s_dl[t] = vox_start[ids[i]] - q;
-  }
+  const uint32_t k = wk.k, a = wk.a, b = wk.b, m = wk.m;
   const double* cc = cen + (size_t)k * 3;
   const double* ww = frame + (size_t)k * 9;
   const double cx = cc[0], cy = cc[1], cz = cc[2];
@@ -139,9 +122,7 @@ __device__ __forceinline__ void sb_chunk_body(const float* __restrict__ xs, cons
   for (int it = 0; it < SD_PPT; ++it) {
     const uint32_t q = a + (uint32_t)it * SD_TB + threadIdx.x;
     if (q < b) {
-      uint32_t l = 0, h = m - 1;   // the last node of the chunk that starts at or before q
-      while (l < h) { const uint32_t mid = (l + h + 1) >> 1; if (s_vp[mid] <= q) l = mid; else h = mid - 1; }
-      const uint32_t pos = q + s_dl[l];
+      const uint32_t pos = sd_pos(s_vp, s_dl, m, q);
       if (OWN) {
         const int64_t o = (int64_t)perm[pos];
         if (o < own_first || o >= own_end) continue;
@@ -222,7 +203,6 @@ __global__ __launch_bounds__(256) void k_sb_final(const uint32_t* __restrict__ s
     o_center[3 * (size_t)k + r] = cen[3 * (size_t)k + r] + ((W[3 * r + 0] * mid[0] + W[3 * r + 1] * mid[1]) + W[3 * r + 2] * mid[2]);
 }
 
-static bool vgs_is_tile(const vgs_ctx* c) { return c->have_region || c->n_own >= 0; }
 
 // The table of one frame in HBM, K = counts[VGS_N_KEPT] rows; valid until the next run of the stages.
 vgs_status vgs_segbox_on_device(vgs_ctx* c, int frame) {

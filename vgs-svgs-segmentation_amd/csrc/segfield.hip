@@ -1,0 +1,389 @@
+// segfield.hip -- per-segment statistics of point attributes the CALLER supplies (no reference counterpart: the first thing a user of a
+// segmentation does with intensity, colour, time, class scores or a ground-truth class).  Row k covers exactly the points whose label
+// (vgs_get_point_labels) is k.  Two tables:
+//   field statistics  per (segment, channel): number of finite values, an anchor, fp64 mean and population variance about it, float min / max
+//   class histogram   per (segment, class): point counts; per segment the points whose class is out of range, the majority class and its count
+// The input is in INPUT order (row i belongs to input point i), the engine's points are sorted by node: perm_b maps a sorted position to
+// the point's input index, so the pass is the decomposition of segdesc.hip -- sd_prepare: nodes sorted by label, virtual positions, chunks
+// of SD_CHUNK virtual points that never cross a segment and may split a node -- with a gather through perm_b.
+// Data flow of the field statistics, per group of SF_G channels (one partial buffer of n_chunks_max x SF_G records, whatever n_channels):
+//   k_sf_anchor  once, every channel: the value of the segment's first point in the chunk order (segdesc.hip's anchor) as a double, 0.0
+//                where that value is not finite -- one point per segment, the same for every channel
+//   k_sf_chunks  one workgroup per chunk: i = perm_b[pos], the group's channels of row i; per channel, over the finite values, S1 = sum d,
+//                S2 = sum d d with d = (double)x - anchor, the count, min and max; wavefront butterfly, the waves through LDS in index order
+//   k_sf_final   one wavefront per (segment, channel of the group) folds the partials (lane stride, then butterfly) and writes
+//                mean = anchor + S1 / n and var = max(0, S2 / n - (S1 / n) (S1 / n)), each one fp64 operation in that association (the build
+//                passes -ffp-contract=off: no FMA)
+// Determinism: the rule of segdesc.hip -- which point a lane reads depends on (chunk, lane, step) only, every fold has a fixed shape, no
+// float atomics -- so the table is bit-identical from call to call and engine to engine.
+// The histogram (k_sf_hist, k_sf_majority) holds integer counts, for which every summation order gives the same bits, so integer atomics
+// are acceptable: the chunk's workgroup counts in LDS (n_classes + 1 counters of 32 bits; a wavefront first folds the lanes that share
+// its first lane's class, so a segment of one class costs one LDS add per wavefront and step) and adds only its non-zero counters to the
+// zeroed K x n_classes table -- at most one global add per (chunk, class), never every point of the ground at one address.
+// Nothing is cached and no getter's table is touched: scratch of sd_prepare (sd_*) and buffers of its own (sf_*).
+#include <string.h>
+
+#include <string>
+
+#include "vgs_context.hpp"
+
+#define SF_G 4     // channels per pass over the points: 4 x (S1, S2, count, min, max) stay in registers
+#define SF_REC 5   // doubles per partial record of one (chunk, channel): S1, S2, count, min, max
+
+__device__ __forceinline__ double sf_wave_sum(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+  return x;
+}
+__device__ __forceinline__ double sf_wave_min(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x = fmin(x, __shfl_xor(x, m, 64));
+  return x;
+}
+__device__ __forceinline__ double sf_wave_max(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x = fmax(x, __shfl_xor(x, m, 64));
+  return x;
+}
+__device__ __forceinline__ bool sf_valid(float x) { return fabsf(x) < __builtin_huge_valf(); }   // finite: false for NaN and +-inf
+
+// anchor[k, c] for every channel: the value of the segment's first point in the chunk order, 0.0 where it is not finite.  One thread per entry.
+__global__ __launch_bounds__(256) void k_sf_anchor(const float* __restrict__ field, int64_t stride_f, uint32_t C, const uint32_t* __restrict__ perm,
+                                                   const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                   const uint32_t* __restrict__ seg_node, uint32_t K, double* __restrict__ anchor) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (uint64_t)K * C) return;
+  const uint32_t k = (uint32_t)(t / C), ch = (uint32_t)(t % C);
+  const uint32_t n0 = seg_node[k], n1 = seg_node[k + 1];
+  double v = 0.0;
+  if (n1 > n0) {
+    const float x = field[(size_t)perm[vox_start[ids[n0]]] * (size_t)stride_f + ch];
+    if (sf_valid(x)) v = (double)x;
+  }
+  anchor[t] = v;
+}
+
+// One workgroup per chunk, channels c0 .. c0 + ng - 1 (ng <= SF_G): one partial record per (chunk, channel of the group).  Grid: the bound
+// of sd_prepare; workgroups past the real number of chunks leave at once.
+__global__ __launch_bounds__(SD_TB) void k_sf_chunks(const float* __restrict__ field, int64_t stride_f, uint32_t C, uint32_t c0, uint32_t ng,
+                                                     const uint32_t* __restrict__ perm, const uint32_t* __restrict__ vox_start,
+                                                     const uint32_t* __restrict__ ids, const uint32_t* __restrict__ vp,
+                                                     const uint32_t* __restrict__ seg_node, const uint32_t* __restrict__ seg_chunk, uint32_t K,
+                                                     const double* __restrict__ anchor, double* __restrict__ part) {
+  __shared__ uint32_t s_vp[SD_CHUNK];    // virtual start of the chunk's nodes
+  __shared__ uint32_t s_dl[SD_CHUNK];    // sorted position - virtual position of the same (mod 2^32)
+  __shared__ double s_red[SD_TB / 64][SF_G][SF_REC];
+  SdChunk w;
+  double* rec = part + (size_t)blockIdx.x * (SF_G * SF_REC);
+  if (!sd_walk(vox_start, ids, vp, seg_node, seg_chunk, K, s_vp, s_dl, w)) {
+    if (w.k != 0xffffffffu && threadIdx.x < SF_G * SF_REC) {   // an empty record keeps the fold well defined
+      const int f = threadIdx.x % SF_REC;
+      rec[threadIdx.x] = f < 3 ? 0.0 : (f == 3 ? __builtin_huge_val() : -__builtin_huge_val());
+    }
+    return;
+  }
+  double an[SF_G];
+#pragma unroll
+  for (int g = 0; g < SF_G; ++g) an[g] = (uint32_t)g < ng ? anchor[(size_t)w.k * C + c0 + g] : 0.0;
+  __syncthreads();
+  double s1[SF_G], s2[SF_G], cn[SF_G];
+  float mn[SF_G], mx[SF_G];
+#pragma unroll
+  for (int g = 0; g < SF_G; ++g) { s1[g] = 0.0; s2[g] = 0.0; cn[g] = 0.0; mn[g] = __builtin_huge_valf(); mx[g] = -__builtin_huge_valf(); }
+#pragma unroll 2
+  for (int it = 0; it < SD_PPT; ++it) {
+    const uint32_t q = w.a + (uint32_t)it * SD_TB + threadIdx.x;
+    if (q < w.b) {
+      const uint32_t pos = sd_pos(s_vp, s_dl, w.m, q);
+      const float* row = field + (size_t)perm[pos] * (size_t)stride_f + c0;
+#pragma unroll
+      for (int g = 0; g < SF_G; ++g) {
+        if ((uint32_t)g < ng) {
+          const float x = row[g];
+          if (sf_valid(x)) {
+            const double d = (double)x - an[g];   // exact conversion, then one fp64 operation per difference, product and sum
+            s1[g] += d;
+            s2[g] += d * d;
+            cn[g] += 1.0;
+            mn[g] = fminf(mn[g], x);
+            mx[g] = fmaxf(mx[g], x);
+          }
+        }
+      }
+    }
+  }
+  const int wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int g = 0; g < SF_G; ++g) {
+    const double a1 = sf_wave_sum(s1[g]), a2 = sf_wave_sum(s2[g]), a3 = sf_wave_sum(cn[g]);
+    const double a4 = sf_wave_min((double)mn[g]), a5 = sf_wave_max((double)mx[g]);
+    if ((threadIdx.x & 63) == 0) {
+      double* r = s_red[wv][g];
+      r[0] = a1; r[1] = a2; r[2] = a3; r[3] = a4; r[4] = a5;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < SF_G * SF_REC) {   // the waves in index order
+    const int g = threadIdx.x / SF_REC, f = threadIdx.x % SF_REC;
+    double v = s_red[0][g][f];
+    if (f < 3) { for (int u = 1; u < SD_TB / 64; ++u) v += s_red[u][g][f]; }
+    else if (f == 3) { for (int u = 1; u < SD_TB / 64; ++u) v = fmin(v, s_red[u][g][f]); }
+    else { for (int u = 1; u < SD_TB / 64; ++u) v = fmax(v, s_red[u][g][f]); }
+    rec[threadIdx.x] = v;
+  }
+}
+
+// one wavefront per (segment, channel of the group): fold the partials (lane stride, then butterfly), then the row's entries on lane 0
+__global__ __launch_bounds__(256) void k_sf_final(const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part, uint32_t n_part, uint32_t K,
+                                                  uint32_t C, uint32_t c0, uint32_t ng, const double* __restrict__ anchor,
+                                                  int64_t* __restrict__ o_n, double* __restrict__ o_mean, double* __restrict__ o_var,
+                                                  float* __restrict__ o_min, float* __restrict__ o_max) {
+  const uint64_t wi = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (wi >= (uint64_t)K * ng) return;   // (whole wavefronts; no barrier follows)
+  const uint32_t k = (uint32_t)(wi / ng), g = (uint32_t)(wi % ng);
+  const uint32_t q0 = seg_chunk[k], q1 = min(seg_chunk[k + 1], n_part);   // (the bound only guards the records: the chunks fit, see the launch)
+  double s1 = 0.0, s2 = 0.0, cn = 0.0, mn = __builtin_huge_val(), mx = -__builtin_huge_val();
+  for (uint32_t c = q0 + lane; c < q1; c += 64) {
+    const double* r = part + ((size_t)c * SF_G + g) * SF_REC;
+    s1 += r[0]; s2 += r[1]; cn += r[2];
+    mn = fmin(mn, r[3]); mx = fmax(mx, r[4]);
+  }
+  s1 = sf_wave_sum(s1); s2 = sf_wave_sum(s2); cn = sf_wave_sum(cn);
+  mn = sf_wave_min(mn); mx = sf_wave_max(mx);
+  if (lane != 0) return;
+  const size_t o = (size_t)k * C + c0 + g;
+  o_n[o] = (int64_t)cn;
+  if (cn > 0.0) {
+    const double m1 = s1 / cn;
+    const double v = s2 / cn - m1 * m1;
+    o_mean[o] = anchor[o] + m1;
+    o_var[o] = v > 0.0 ? v : 0.0;
+    o_min[o] = (float)mn;
+    o_max[o] = (float)mx;
+  } else {
+    o_mean[o] = __builtin_nan(""); o_var[o] = __builtin_nan("");
+    o_min[o] = __builtin_nanf(""); o_max[o] = __builtin_nanf("");
+  }
+}
+
+// One workgroup per chunk: the classes of its points counted in LDS (slot n_classes: out of range), the non-zero counters added to the
+// zeroed tables.  hist: K x n_classes, n_outside: K.  Integer atomics: the sums do not depend on the order.
+__global__ __launch_bounds__(SD_TB) void k_sf_hist(const int32_t* __restrict__ cls, uint32_t n_classes, const uint32_t* __restrict__ perm,
+                                                   const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                   const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                   const uint32_t* __restrict__ seg_chunk, uint32_t K, unsigned long long* __restrict__ hist,
+                                                   unsigned long long* __restrict__ n_outside) {
+  __shared__ uint32_t s_vp[SD_CHUNK];
+  __shared__ uint32_t s_dl[SD_CHUNK];
+  __shared__ uint32_t s_cnt[1024 + 1];
+  SdChunk w;
+  if (!sd_walk(vox_start, ids, vp, seg_node, seg_chunk, K, s_vp, s_dl, w)) return;
+  for (uint32_t j = threadIdx.x; j <= n_classes; j += SD_TB) s_cnt[j] = 0;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  for (int it = 0; it < SD_PPT; ++it) {
+    const uint32_t q = w.a + (uint32_t)it * SD_TB + threadIdx.x;
+    const bool act = q < w.b;
+    uint32_t slot = 0;
+    if (act) {
+      const int32_t v = cls[perm[sd_pos(s_vp, s_dl, w.m, q)]];
+      slot = (v < 0 || (uint32_t)v >= n_classes) ? n_classes : (uint32_t)v;
+    }
+    // the lanes that share the first active lane's class fold into one add; the others add one each
+    const uint64_t am = __ballot(act);
+    if (am == 0) continue;
+    const uint32_t first = (uint32_t)__ffsll((unsigned long long)am) - 1u;
+    const uint32_t lead = __shfl(slot, (int)first, 64);
+    const uint64_t peers = __ballot(act && slot == lead);
+    if (lane == first) atomicAdd(&s_cnt[lead], (uint32_t)__popcll(peers));
+    else if (act && slot != lead) atomicAdd(&s_cnt[slot], 1u);
+  }
+  __syncthreads();
+  for (uint32_t j = threadIdx.x; j <= n_classes; j += SD_TB) {
+    const uint32_t v = s_cnt[j];
+    if (v == 0) continue;
+    if (j < n_classes) atomicAdd(hist + (size_t)w.k * n_classes + j, (unsigned long long)v);
+    else atomicAdd(n_outside + w.k, (unsigned long long)v);
+  }
+}
+
+// one wavefront per segment: the lowest class with the largest count (-1 and 0 when every count is 0)
+__global__ __launch_bounds__(256) void k_sf_majority(const unsigned long long* __restrict__ hist, uint32_t n_classes, uint32_t K,
+                                                     int32_t* __restrict__ majority, long long* __restrict__ majority_count) {
+  const uint32_t k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (k >= K) return;   // (whole wavefronts; no barrier follows)
+  unsigned long long best = 0;
+  uint32_t arg = 0xffffffffu;
+  for (uint32_t j = lane; j < n_classes; j += 64) {   // ascending j per lane: a strictly larger count only
+    const unsigned long long v = hist[(size_t)k * n_classes + j];
+    if (v > best) { best = v; arg = j; }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned long long ob = __shfl_xor(best, m, 64);
+    const uint32_t oa = __shfl_xor(arg, m, 64);
+    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+  }
+  if (lane != 0) return;
+  majority[k] = best > 0 ? (int32_t)arg : -1;
+  majority_count[k] = (long long)best;
+}
+
+static vgs_status sf_check_state(vgs_ctx* c, const char* fn) {
+  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
+  if (vgs_is_tile(c)) {
+    c->err = std::string(fn) + ": a tile context (owned region / own point range) holds only part of its segments; field statistics need the whole cloud in one context";
+    return VGS_E_STATE;
+  }
+  return VGS_OK;
+}
+
+static vgs_status sf_check_n(vgs_ctx* c, const char* fn, const void* in, int64_t n) {
+  if (n != c->N) {
+    c->err = std::string(fn) + ": n = " + std::to_string(n) + " must equal the number of points of the cloud, " + std::to_string(c->N);
+    return VGS_E_ARG;
+  }
+  if (!in && n > 0) { c->err = std::string(fn) + ": the input array is NULL"; return VGS_E_ARG; }
+  return VGS_OK;
+}
+
+static vgs_status sf_check_field(vgs_ctx* c, const char* fn, const float* field, int64_t n, int32_t n_channels, int64_t stride_bytes) {
+  vgs_status s = sf_check_state(c, fn);
+  if (s != VGS_OK) return s;
+  if ((s = sf_check_n(c, fn, field, n)) != VGS_OK) return s;
+  if (n_channels < 1 || n_channels > 64) {
+    c->err = std::string(fn) + ": n_channels = " + std::to_string(n_channels) + " must be in 1 .. 64";
+    return VGS_E_ARG;
+  }
+  if (stride_bytes < 4 * (int64_t)n_channels || stride_bytes % 4 != 0) {
+    c->err = std::string(fn) + ": stride_bytes = " + std::to_string(stride_bytes) + " must be a multiple of 4 and at least 4 * n_channels = " +
+             std::to_string(4 * (int64_t)n_channels);
+    return VGS_E_ARG;
+  }
+  return VGS_OK;
+}
+
+// the field table from a device buffer: every output a host array of K x n_channels, any may be NULL
+static vgs_status sf_field_stats(vgs_ctx* c, const float* field_dev, int32_t n_channels, int64_t stride_bytes, int64_t* n_valid, double* anchor,
+                                 double* mean, double* var, float* vmin, float* vmax) {
+  const int64_t K = c->counts[VGS_N_KEPT];
+  if (K == 0 || c->V == 0 || c->Nf == 0) return VGS_OK;
+  const uint32_t C = (uint32_t)n_channels;
+  const size_t kc = (size_t)K * C;
+  const int64_t stride_f = stride_bytes / 4;
+  SdPrep P;
+  vgs_status s = sd_prepare(c, K, P);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, c->sf_part.ensure((size_t)P.n_chunks_max * SF_G * SF_REC));
+  VGS_HIP_TRY(c, c->sf_anchor.ensure(kc)); VGS_HIP_TRY(c, c->sf_mean.ensure(kc)); VGS_HIP_TRY(c, c->sf_var.ensure(kc));
+  VGS_HIP_TRY(c, c->sf_nvalid.ensure(kc)); VGS_HIP_TRY(c, c->sf_min.ensure(kc)); VGS_HIP_TRY(c, c->sf_max.ensure(kc));
+  hipLaunchKernelGGL(k_sf_anchor, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, c->stream, field_dev, stride_f, C, c->perm_b.p, c->vox_start.p,
+                     P.ids, P.seg_node, (uint32_t)K, c->sf_anchor.p);
+  for (uint32_t c0 = 0; c0 < C; c0 += SF_G) {
+    const uint32_t ng = C - c0 < SF_G ? C - c0 : SF_G;
+    hipLaunchKernelGGL(k_sf_chunks, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, field_dev, stride_f, C, c0, ng, c->perm_b.p,
+                       c->vox_start.p, P.ids, P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, c->sf_anchor.p, c->sf_part.p);
+    hipLaunchKernelGGL(k_sf_final, dim3((unsigned)(((size_t)K * ng + 3) / 4)), dim3(256), 0, c->stream, P.seg_chunk, c->sf_part.p,
+                       (uint32_t)P.n_chunks_max, (uint32_t)K, C, c0, ng, c->sf_anchor.p, c->sf_nvalid.p, c->sf_mean.p, c->sf_var.p, c->sf_min.p,
+                       c->sf_max.p);
+  }
+  VGS_HIP_TRY(c, hipGetLastError());
+  if (n_valid) VGS_HIP_TRY(c, hipMemcpyAsync(n_valid, c->sf_nvalid.p, kc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  if (anchor) VGS_HIP_TRY(c, hipMemcpyAsync(anchor, c->sf_anchor.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (mean) VGS_HIP_TRY(c, hipMemcpyAsync(mean, c->sf_mean.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (var) VGS_HIP_TRY(c, hipMemcpyAsync(var, c->sf_var.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (vmin) VGS_HIP_TRY(c, hipMemcpyAsync(vmin, c->sf_min.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (vmax) VGS_HIP_TRY(c, hipMemcpyAsync(vmax, c->sf_max.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_segment_field_stats_device(vgs_ctx* c, const float* field_dev, int64_t n, int32_t n_channels, int64_t stride_bytes,
+                                                     int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = sf_check_field(c, "vgs_segment_field_stats_device", field_dev, n, n_channels, stride_bytes);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  return sf_field_stats(c, field_dev, n_channels, stride_bytes, n_valid, anchor, mean, var, vmin, vmax);
+}
+
+extern "C" vgs_status vgs_segment_field_stats(vgs_ctx* c, const float* field_host, int64_t n, int32_t n_channels, int64_t stride_bytes,
+                                              int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = sf_check_field(c, "vgs_segment_field_stats", field_host, n, n_channels, stride_bytes);
+  if (s != VGS_OK) return s;
+  if (c->counts[VGS_N_KEPT] == 0 || n == 0) return VGS_OK;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  // one upload, rows at the caller's stride; the last row ends with its last channel
+  const size_t bytes = (size_t)(n - 1) * (size_t)stride_bytes + 4 * (size_t)n_channels;
+  VGS_HIP_TRY(c, c->sf_in.ensure((bytes + 3) / 4));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_in.p, field_host, bytes, hipMemcpyHostToDevice, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
+  return sf_field_stats(c, c->sf_in.p, n_channels, stride_bytes, n_valid, anchor, mean, var, vmin, vmax);
+}
+
+static vgs_status sf_check_hist(vgs_ctx* c, const char* fn, const int32_t* cls, int64_t n, int32_t n_classes) {
+  vgs_status s = sf_check_state(c, fn);
+  if (s != VGS_OK) return s;
+  if ((s = sf_check_n(c, fn, cls, n)) != VGS_OK) return s;
+  if (n_classes < 1 || n_classes > 1024) {
+    c->err = std::string(fn) + ": n_classes = " + std::to_string(n_classes) + " must be in 1 .. 1024";
+    return VGS_E_ARG;
+  }
+  const int64_t K = c->counts[VGS_N_KEPT];
+  if (K * (int64_t)n_classes > ((int64_t)1 << 27)) {
+    c->err = std::string(fn) + ": " + std::to_string(K) + " segments x " + std::to_string(n_classes) + " classes = " +
+             std::to_string(K * (int64_t)n_classes) + " counters exceed the table's limit of 2^27 = " + std::to_string((int64_t)1 << 27);
+    return VGS_E_UNSUPPORTED;
+  }
+  return VGS_OK;
+}
+
+// the histogram from a device buffer: hist K x n_classes, the others K; host arrays, any may be NULL
+static vgs_status sf_class_hist(vgs_ctx* c, const int32_t* cls_dev, int32_t n_classes, int64_t* hist, int64_t* n_outside, int32_t* majority,
+                                int64_t* majority_count) {
+  const int64_t K = c->counts[VGS_N_KEPT];
+  if (K == 0 || c->V == 0 || c->Nf == 0) return VGS_OK;
+  const size_t k = (size_t)K, kc = k * (size_t)n_classes;
+  SdPrep P;
+  vgs_status s = sd_prepare(c, K, P);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, c->sf_hist.ensure(kc + 2 * k)); VGS_HIP_TRY(c, c->sf_maj.ensure(k));
+  int64_t *d_hist = c->sf_hist.p, *d_out = d_hist + kc, *d_majc = d_out + k;
+  VGS_HIP_TRY(c, hipMemsetAsync(d_hist, 0, (kc + k) * sizeof(int64_t), c->stream));
+  hipLaunchKernelGGL(k_sf_hist, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, cls_dev, (uint32_t)n_classes, c->perm_b.p, c->vox_start.p,
+                     P.ids, P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, (unsigned long long*)d_hist, (unsigned long long*)d_out);
+  hipLaunchKernelGGL(k_sf_majority, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, (const unsigned long long*)d_hist, (uint32_t)n_classes,
+                     (uint32_t)K, c->sf_maj.p, (long long*)d_majc);
+  VGS_HIP_TRY(c, hipGetLastError());
+  if (hist) VGS_HIP_TRY(c, hipMemcpyAsync(hist, d_hist, kc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  if (n_outside) VGS_HIP_TRY(c, hipMemcpyAsync(n_outside, d_out, k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  if (majority) VGS_HIP_TRY(c, hipMemcpyAsync(majority, c->sf_maj.p, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (majority_count) VGS_HIP_TRY(c, hipMemcpyAsync(majority_count, d_majc, k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_segment_class_histogram_device(vgs_ctx* c, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* hist,
+                                                         int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = sf_check_hist(c, "vgs_segment_class_histogram_device", cls_dev, n, n_classes);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  return sf_class_hist(c, cls_dev, n_classes, hist, n_outside, majority, majority_count);
+}
+
+extern "C" vgs_status vgs_segment_class_histogram(vgs_ctx* c, const int32_t* cls_host, int64_t n, int32_t n_classes, int64_t* hist,
+                                                  int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = sf_check_hist(c, "vgs_segment_class_histogram", cls_host, n, n_classes);
+  if (s != VGS_OK) return s;
+  if (c->counts[VGS_N_KEPT] == 0 || n == 0) return VGS_OK;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  VGS_HIP_TRY(c, c->sf_cls.ensure((size_t)n));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_cls.p, cls_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
+  return sf_class_hist(c, c->sf_cls.p, n_classes, hist, n_outside, majority, majority_count);
+}

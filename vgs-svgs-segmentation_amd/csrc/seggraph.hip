@@ -273,7 +273,6 @@ __global__ __launch_bounds__(64 * SG_WAVES) void k_sg_final(const uint32_t* __re
   o_max[e] = nf > 0 ? mx : __builtin_nanf("");
 }
 
-static bool vgs_is_tile(const vgs_ctx* c) { return c->have_region || c->n_own >= 0; }
 
 static VgsWeightParams sg_weight_params(const vgs_params& p) {   // (merge.hip: make_weight_params_m, the local cut's own parameters)
   VgsWeightParams W;

@@ -275,6 +275,13 @@ struct vgs_ctx {
   // the frames made from them, the rows that come out (lo3 | hi3 | half3 | center3), one chunk per segment; nothing a cached table reads
   DevBuf<double> sbt_in, sbt_frame, sbt_out;
   DevBuf<uint32_t> sbt_idx;
+  // per-segment statistics of a caller's point attributes (segfield.hip): computed on every call, nothing cached.  The host variants' upload
+  // (sf_in, sf_cls), the chunk partials of one channel group, and the tables the rows are copied out of: K x n_channels for the field
+  // statistics; K x n_classes counts, then n_outside and majority_count (K each) in sf_hist, majority in sf_maj
+  DevBuf<float> sf_in, sf_min, sf_max;
+  DevBuf<int32_t> sf_cls, sf_maj;
+  DevBuf<double> sf_part, sf_anchor, sf_mean, sf_var;
+  DevBuf<int64_t> sf_nvalid, sf_hist;
   // tile contexts (vgs_get_own_segment_moments / vgs_segment_descriptors_from_moments): first own point per segment, moment records
   DevBuf<uint32_t> sd_apos;
   DevBuf<double> sd_mom;
@@ -403,7 +410,7 @@ static inline vgs_status vgs_readback_end(vgs_ctx* c, void* dst, size_t bytes) {
 }
 static inline bool vgs_can_split_readback(const vgs_ctx* c) { return c->pin != nullptr && c->ev_rb != nullptr; }
 
-// The decomposition of the per-segment passes (segdesc.hip, segbox.hip): chunks of SD_CHUNK virtual points that never cross a segment.
+// The decomposition of the per-segment passes (segdesc.hip, segbox.hip, segfield.hip): chunks of SD_CHUNK virtual points that never cross a segment.
 // sd_prepare (segdesc.hip) runs steps 1-2 of segdesc.hip's header for labels 0 .. K-1 -- sorted node ids, virtual positions, per segment
 // its first sorted node and first chunk, pointers into the sd_* scratch -- and gives the grid bound of the chunk kernels.
 #define SD_TB 256                   // threads of a chunk workgroup
@@ -411,6 +418,52 @@ static inline bool vgs_can_split_readback(const vgs_ctx* c) { return c->pin != n
 #define SD_CHUNK (SD_TB * SD_PPT)   // virtual points per chunk
 struct SdPrep { uint32_t *ids, *vp, *seg_node, *seg_chunk; int64_t n_chunks_max; };
 vgs_status sd_prepare(vgs_ctx* c, int64_t K, SdPrep& o);
+// a tile context (the tiled driver, include/vgs_tiles.h) holds only part of its segments: the per-segment getters of one context refuse it
+static inline bool vgs_is_tile(const vgs_ctx* c) { return c->have_region || c->n_own >= 0; }
+#ifdef __HIPCC__
+// The walk of a chunk workgroup (blockIdx.x) from chunk to segment to nodes, one copy for segdesc.hip, segbox.hip and segfield.hip: the
+// segment k of the chunk, its virtual range [a, b) and its m nodes staged in s_vp (virtual start of each node) and s_dl (sorted position -
+// virtual position, mod 2^32), two LDS arrays of SD_CHUNK words.  False, with nothing staged, for a workgroup past the real number of
+// chunks (k = 0xffffffff: nothing to write) and for an empty chunk (cannot happen for a kept segment; the caller writes an empty record so
+// that the fold stays well defined).  The caller's __syncthreads follows; then sd_pos gives the sorted position of a virtual point.
+struct SdChunk { uint32_t k, n0, a, b, m; };
+__device__ __forceinline__ bool sd_walk(const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids, const uint32_t* __restrict__ vp,
+                                        const uint32_t* __restrict__ seg_node, const uint32_t* __restrict__ seg_chunk, uint32_t K,
+                                        uint32_t* __restrict__ s_vp, uint32_t* __restrict__ s_dl, SdChunk& o) {
+  const uint32_t c = blockIdx.x;
+  o.k = 0xffffffffu;
+  if (c >= seg_chunk[K]) return false;
+  // segment of chunk c: the last k with seg_chunk[k] <= c (every segment has at least one chunk)
+  uint32_t lo = 0, hi = K - 1;
+  while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (seg_chunk[mid] <= c) lo = mid; else hi = mid - 1; }
+  const uint32_t k = lo;
+  o.k = k;
+  const uint32_t n0 = seg_node[k], n1 = seg_node[k + 1];
+  const uint32_t a = vp[n0] + (c - seg_chunk[k]) * SD_CHUNK;
+  const uint32_t b = min(a + SD_CHUNK, vp[n1]);
+  if (n1 <= n0 || a >= b) return false;
+  // nodes that overlap [a, b): the last node starting at or before a ... the last node starting before b.  Every node of a kept segment
+  // holds a point, so vp rises strictly inside the segment and they are at most b - a <= SD_CHUNK nodes.
+  uint32_t i0 = n0, i1 = n1 - 1;
+  while (i0 < i1) { const uint32_t mid = (i0 + i1 + 1) >> 1; if (vp[mid] <= a) i0 = mid; else i1 = mid - 1; }
+  uint32_t j0 = i0 + 1, j1 = n1;
+  while (j0 < j1) { const uint32_t mid = (j0 + j1) >> 1; if (vp[mid] < b) j0 = mid + 1; else j1 = mid; }
+  const uint32_t m = min(j0 - i0, (uint32_t)SD_CHUNK);   // (the bound above; the clamp only guards the LDS arrays)
+  for (uint32_t t = threadIdx.x; t < m; t += SD_TB) {
+    const uint32_t i = i0 + t, q = vp[i];
+    s_vp[t] = q;
+    s_dl[t] = vox_start[ids[i]] - q;
+  }
+  o.n0 = n0; o.a = a; o.b = b; o.m = m;
+  return true;
+}
+// sorted position of the virtual point q of the chunk: the last staged node that starts at or before q
+__device__ __forceinline__ uint32_t sd_pos(const uint32_t* __restrict__ s_vp, const uint32_t* __restrict__ s_dl, uint32_t m, uint32_t q) {
+  uint32_t l = 0, h = m - 1;
+  while (l < h) { const uint32_t mid = (l + h + 1) >> 1; if (s_vp[mid] <= q) l = mid; else h = mid - 1; }
+  return q + s_dl[l];
+}
+#endif
 
 vgs_status vgs_cut_order(vgs_ctx* c, std::vector<uint16_t>& ord_host, std::vector<uint32_t>& k_host, bool want_lists = false,
                          const uint8_t* list_flag = nullptr, std::vector<uint32_t>* list_cnt = nullptr, std::vector<int32_t>* list_ids = nullptr);   // cutorder.hip

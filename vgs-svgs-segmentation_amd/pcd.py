@@ -2,7 +2,7 @@
 
 Independent of include/point_clouds_io.hpp (the C++ reader/writer used by examples/vgs_run); the tests run each
 against the other.  Supports DATA ascii | binary | binary_compressed, any field list; `read_pcd` returns the fields
-as a dict of arrays, `write_pcd` writes float32 x y z (+ optional packed rgb, + optional extra float fields).
+as a dict of arrays, `write_pcd` writes float32 x y z (+ optional packed rgb, + optional extra fields, float32 or of an integer type).
 """
 import numpy as np
 
@@ -72,28 +72,35 @@ def lzf_decompress(data: bytes, out_len: int) -> bytes:
 
 
 def write_pcd(path, xyz, mode="binary", rgb=None, extra=None, field_order=None):
-    """xyz (N,3) float32; rgb (N,) uint32 0x00RRGGBB written as PCL's packed float field; extra: dict name -> (N,) float32."""
+    """xyz (N,3) float32; rgb (N,) uint32 0x00RRGGBB written as PCL's packed float field; extra: dict name -> (N,) values, written as
+    float32 -- or, for a numpy array of an integer dtype, as that type (U 1, U 2, I 4, ...)."""
     xyz = np.ascontiguousarray(xyz, dtype=np.float32)
     n = xyz.shape[0]
     cols = {"x": xyz[:, 0], "y": xyz[:, 1], "z": xyz[:, 2]}
     if rgb is not None:
         cols["rgb"] = np.asarray(rgb, dtype=np.uint32).view(np.float32)
     for k, v in (extra or {}).items():
-        cols[k] = np.asarray(v, dtype=np.float32)
+        keep = isinstance(v, np.ndarray) and v.dtype.kind in "iu"
+        cols[k] = np.ascontiguousarray(v) if keep else np.asarray(v, dtype=np.float32)
     names = field_order or list(cols)
-    hdr = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS " + " ".join(names) + "\nSIZE " + " ".join("4" for _ in names) +
-           "\nTYPE " + " ".join("F" for _ in names) + "\nCOUNT " + " ".join("1" for _ in names) +
+    code = {np.dtype(t): c for c, t in _NP.items()}   # dtype -> (TYPE letter, SIZE)
+    kinds = [code[cols[k].dtype] for k in names]
+    hdr = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS " + " ".join(names) + "\nSIZE " + " ".join(str(s) for _, s in kinds) +
+           "\nTYPE " + " ".join(t for t, _ in kinds) + "\nCOUNT " + " ".join("1" for _ in names) +
            f"\nWIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA {mode}\n")
     with open(path, "wb") as f:
         f.write(hdr.encode())
         if mode == "ascii":
-            arr = np.stack([cols[k] for k in names], axis=1)
-            for row in arr:
-                f.write((" ".join(f"{float(v):.9g}" for v in row) + "\n").encode())
+            fmt = [(lambda v: f"{float(v):.9g}") if t == "F" else (lambda v: str(int(v))) for t, _ in kinds]
+            for row in zip(*(cols[k] for k in names)):
+                f.write((" ".join(g(v) for g, v in zip(fmt, row)) + "\n").encode())
         elif mode == "binary":
-            f.write(np.stack([cols[k] for k in names], axis=1).astype(np.float32).tobytes())
+            rec = np.zeros(n, dtype=np.dtype([(k, cols[k].dtype) for k in names]))   # packed: one point after the other
+            for k in names:
+                rec[k] = cols[k]
+            f.write(rec.tobytes())
         elif mode == "binary_compressed":
-            raw = b"".join(np.ascontiguousarray(cols[k], dtype=np.float32).tobytes() for k in names)  # field by field
+            raw = b"".join(np.ascontiguousarray(cols[k]).tobytes() for k in names)  # field by field
             comp = lzf_compress(raw)
             f.write(np.array([len(comp), len(raw)], dtype=np.uint32).tobytes())
             f.write(comp)
