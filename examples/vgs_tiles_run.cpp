@@ -14,10 +14,18 @@
 //   of the global segments in the CSV format of vgs_run --segment-graph.
 //   --segment-boxes <file.csv> [--box-frame principal|upright]: every rank takes part in vgs_tiles_get_segment_boxes (a collective; it
 //   takes the descriptor table first) and rank 0 writes the oriented boxes of the global segments in the CSV format of vgs_run
-//   --segment-boxes.  The three can be combined.
+//   --segment-boxes.
+//   --segment-fields <file.csv> --field-channels <C>: rank r reads <prefix>.<r>.fields.f32 (packed float32, C values per point, in the order
+//   of its points), every rank takes part in vgs_tiles_segment_field_stats (a collective; no attribute leaves its rank) and rank 0 writes
+//   the table in the CSV format of vgs_run --segment-fields, the channels named f0 .. f{C-1}.
+//   --segment-classes <file.csv> --classes <C>: rank r reads <prefix>.<r>.classes.i32 (one int32 per point), every rank takes part in
+//   vgs_tiles_segment_class_histogram and rank 0 writes the table in the CSV format of vgs_run --segment-classes.
+//   All of them can be combined.  A missing companion option, a value out of range (1 .. 64 channels, 1 .. 1024 classes) and an attribute
+//   file whose size does not match the rank's points are usage errors: exit status 2, before any collective.
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <sys/socket.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <hip/hip_runtime.h>
@@ -45,6 +53,24 @@ static bool read_f32(const std::string& path, std::vector<float>& out) {
   return got == out.size();
 }
 
+static bool read_i32(const std::string& path, std::vector<int32_t>& out) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) return false;
+  std::fseek(f, 0, SEEK_END);
+  const long bytes = std::ftell(f);
+  std::fseek(f, 0, SEEK_SET);
+  out.resize((size_t)bytes / 4);
+  const size_t got = std::fread(out.data(), 4, out.size(), f);
+  std::fclose(f);
+  return got == out.size();
+}
+
+// size of a file in bytes, -1 if it cannot be examined
+static long long file_bytes(const std::string& path) {
+  struct stat st;
+  return stat(path.c_str(), &st) == 0 ? (long long)st.st_size : -1;
+}
+
 static bool write_i32(const std::string& path, const std::vector<int32_t>& v) {
   FILE* f = std::fopen(path.c_str(), "wb");
   if (!f) return false;
@@ -53,12 +79,44 @@ static bool write_i32(const std::string& path, const std::vector<int32_t>& v) {
   return put == v.size();
 }
 
-struct Job { vgs_params p; int tx, ty; double pitch; std::string prefix, segments, graph, boxes; int box_frame = VGS_BOX_PRINCIPAL; };
+struct Job {
+  vgs_params p; int tx, ty; double pitch; std::string prefix, segments, graph, boxes; int box_frame = VGS_BOX_PRINCIPAL;
+  std::string fields, classes;        // --segment-fields / --segment-classes
+  int field_channels = 0, n_classes = 0;
+};
+
+static std::string rank_file(const Job& J, int rank, const char* suffix) { return J.prefix + "." + std::to_string(rank) + suffix; }
+
+// The attribute files of one rank against its points, by size alone: 0 fine, 2 a usage error (message printed).  A points file that cannot
+// be examined is left to run_rank.
+static int check_attribute_files(const Job& J, int rank) {
+  const long long pts = file_bytes(rank_file(J, rank, ".f32"));
+  if (pts < 0) return 0;
+  const long long n = pts / 12;
+  if (!J.fields.empty()) {
+    const std::string path = rank_file(J, rank, ".fields.f32");
+    const long long b = file_bytes(path);
+    if (b != n * 4 * (long long)J.field_channels) {
+      std::fprintf(stderr, "%s: %lld bytes, but %lld points x %d channels x 4 = %lld\n", path.c_str(), b, n, J.field_channels, n * 4 * (long long)J.field_channels);
+      return 2;
+    }
+  }
+  if (!J.classes.empty()) {
+    const std::string path = rank_file(J, rank, ".classes.i32");
+    const long long b = file_bytes(path);
+    if (b != n * 4) { std::fprintf(stderr, "%s: %lld bytes, but %lld points x 4 = %lld\n", path.c_str(), b, n, n * 4); return 2; }
+  }
+  return 0;
+}
 
 // one rank: load, run, save; returns 0 on success
 static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world, int64_t* kept, int64_t* n_pts, int64_t* n_rec, std::string* err) {
   std::vector<float> xyz;
   if (!read_f32(J.prefix + "." + std::to_string(rank) + ".f32", xyz)) { *err = "cannot read the points of rank " + std::to_string(rank); return 1; }
+  std::vector<float> field;
+  std::vector<int32_t> cls;
+  if (!J.fields.empty() && !read_f32(rank_file(J, rank, ".fields.f32"), field)) { *err = "cannot read the fields of rank " + std::to_string(rank); return 1; }
+  if (!J.classes.empty() && !read_i32(rank_file(J, rank, ".classes.i32"), cls)) { *err = "cannot read the classes of rank " + std::to_string(rank); return 1; }
   vgs_tiles* t = nullptr;
   vgs_status s = vgs_tiles_create(&J.p, comm_kind, comm, rank, world, J.tx, J.ty, J.pitch, 0.0, 0.0, &t);
   if (s != VGS_OK) { *err = std::string("vgs_tiles_create: ") + vgs_last_error_string(nullptr); return 1; }
@@ -134,6 +192,48 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
       if (writeBoxesCsv(J.boxes, boxes) != 0) { *err = "cannot write " + J.boxes; rc = 1; }
     }
   }
+  if (rc == 0 && !J.fields.empty()) {
+    // the statistics of this rank's attribute rows over the global segments: a collective of every rank, the same table on each
+    const size_t k = (size_t)*kept, C = (size_t)J.field_channels, kc = k * C;
+    std::vector<int64_t> nv(kc + 1);
+    std::vector<double> an(kc + 1), me(kc + 1), va(kc + 1);
+    std::vector<float> mn(kc + 1), mx(kc + 1);
+    int64_t K = 0;
+    if (vgs_tiles_segment_field_stats(t, field.data(), n, J.field_channels, 4 * (int64_t)J.field_channels, &K, nv.data(), an.data(), me.data(), va.data(),
+                                      mn.data(), mx.data()) != VGS_OK) {
+      *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+      rc = 1;
+    } else if (rank == 0) {
+      std::vector<std::string> names;
+      for (size_t ch = 0; ch < C; ++ch) names.push_back("f" + std::to_string(ch));
+      std::vector<pcl::ClusterFieldStats> stats(k);
+      for (size_t i = 0; i < k; ++i) {
+        pcl::ClusterFieldStats& f = stats[i];
+        f.n_valid.assign(nv.begin() + i * C, nv.begin() + (i + 1) * C); f.anchor.assign(an.begin() + i * C, an.begin() + (i + 1) * C);
+        f.mean.assign(me.begin() + i * C, me.begin() + (i + 1) * C); f.var.assign(va.begin() + i * C, va.begin() + (i + 1) * C);
+        f.vmin.assign(mn.begin() + i * C, mn.begin() + (i + 1) * C); f.vmax.assign(mx.begin() + i * C, mx.begin() + (i + 1) * C);
+      }
+      if (writeFieldStatsCsv(J.fields, names, stats) != 0) { *err = "cannot write " + J.fields; rc = 1; }
+    }
+  }
+  if (rc == 0 && !J.classes.empty()) {
+    const size_t k = (size_t)*kept, nc = (size_t)J.n_classes;
+    std::vector<int64_t> hi(k * nc + 1), no(k + 1), mc(k + 1);
+    std::vector<int32_t> ma(k + 1);
+    int64_t K = 0;
+    if (vgs_tiles_segment_class_histogram(t, cls.data(), n, J.n_classes, &K, hi.data(), no.data(), ma.data(), mc.data()) != VGS_OK) {
+      *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+      rc = 1;
+    } else if (rank == 0) {
+      std::vector<pcl::ClusterClassHistogram> hist(k);
+      for (size_t i = 0; i < k; ++i) {
+        pcl::ClusterClassHistogram& h = hist[i];
+        h.hist.assign(hi.begin() + i * nc, hi.begin() + (i + 1) * nc);
+        h.n_outside = no[i]; h.majority = ma[i]; h.majority_count = mc[i];
+      }
+      if (writeClassHistCsv(J.classes, J.n_classes, hist) != 0) { *err = "cannot write " + J.classes; rc = 1; }
+    }
+  }
   if (rc == 0) {
     labels.resize((size_t)n);
     if (!write_i32(J.prefix + "." + std::to_string(rank) + ".labels.i32", labels)) { *err = "cannot write the labels"; rc = 1; }
@@ -187,6 +287,7 @@ int main(int argc, char** argv) {
   J.p.voxel_size = 0.1f;
   J.tx = 1; J.ty = 1; J.pitch = 0.0;
   int mode = -1;   // 0 rccl, 1 emulate
+  bool have_channels = false, have_classes = false;
   for (int a = 1; a < argc; ++a) {
     if ((!std::strcmp(argv[a], "--rccl") || !std::strcmp(argv[a], "--emulate")) && a + 1 < argc) {
       mode = !std::strcmp(argv[a], "--emulate") ? 1 : 0;
@@ -203,13 +304,24 @@ int main(int argc, char** argv) {
       else if (!std::strcmp(argv[a], "upright")) J.box_frame = VGS_BOX_UPRIGHT;
       else { std::fprintf(stderr, "--box-frame must be principal or upright\n"); return 2; }
     }
+    else if (!std::strcmp(argv[a], "--segment-fields") && a + 1 < argc) J.fields = argv[++a];
+    else if (!std::strcmp(argv[a], "--field-channels") && a + 1 < argc) { J.field_channels = std::atoi(argv[++a]); have_channels = true; }
+    else if (!std::strcmp(argv[a], "--segment-classes") && a + 1 < argc) J.classes = argv[++a];
+    else if (!std::strcmp(argv[a], "--classes") && a + 1 < argc) { J.n_classes = std::atoi(argv[++a]); have_classes = true; }
     else if (argv[a][0] != '-') J.prefix = argv[a];
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
-  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] <prefix>\n", argv[0]); return 2; }
+  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] <prefix>\n", argv[0]); return 2; }
+  if (!J.fields.empty() && !have_channels) { std::fprintf(stderr, "--segment-fields needs --field-channels <C>\n"); return 2; }
+  if (J.fields.empty() && have_channels) { std::fprintf(stderr, "--field-channels needs --segment-fields <file.csv>\n"); return 2; }
+  if (have_channels && (J.field_channels < 1 || J.field_channels > 64)) { std::fprintf(stderr, "--field-channels must be in 1 .. 64\n"); return 2; }
+  if (!J.classes.empty() && !have_classes) { std::fprintf(stderr, "--segment-classes needs --classes <C>\n"); return 2; }
+  if (J.classes.empty() && have_classes) { std::fprintf(stderr, "--classes needs --segment-classes <file.csv>\n"); return 2; }
+  if (have_classes && (J.n_classes < 1 || J.n_classes > 1024)) { std::fprintf(stderr, "--classes must be in 1 .. 1024\n"); return 2; }
   const int world = J.tx * J.ty;
   int64_t kept = 0, n_pts = 0, n_rec = 0;
   if (mode == 1) {
+    for (int r = 0; r < world; ++r) if (check_attribute_files(J, r) != 0) return 2;
     void* group = nullptr;
     vgs_tiles_local_group_create(world, &group);
     std::vector<std::thread> th;
@@ -230,6 +342,7 @@ int main(int argc, char** argv) {
     const char* e_rank = std::getenv("RANK"); const char* e_world = std::getenv("WORLD_SIZE"); const char* e_local = std::getenv("LOCAL_RANK");
     const char* e_addr = std::getenv("MASTER_ADDR"); const char* e_port = std::getenv("MASTER_PORT");
     const int rank = e_rank ? std::atoi(e_rank) : 0;
+    if (check_attribute_files(J, rank) != 0) return 2;
     if ((e_world ? std::atoi(e_world) : 1) != world) { std::fprintf(stderr, "WORLD_SIZE does not match the %dx%d layout\n", J.tx, J.ty); return 2; }
     J.p.device = e_local ? std::atoi(e_local) : 0;
     if (hipSetDevice(J.p.device) != hipSuccess) { std::fprintf(stderr, "hipSetDevice(%d) failed\n", J.p.device); return 1; }

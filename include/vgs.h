@@ -372,6 +372,40 @@ vgs_status vgs_segment_class_histogram(vgs_ctx* ctx, const int32_t* cls_host, in
                                        int32_t* majority, int64_t* majority_count);
 vgs_status vgs_segment_class_histogram_device(vgs_ctx* ctx, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* hist,
                                               int64_t* n_outside, int32_t* majority, int64_t* majority_count);
+/* Attribute moments of a tile context (the tiled driver, include/vgs_tiles.h: vgs_tiles_segment_field_stats builds the global table from
+ * them).  No attribute travels between ranks: a rank hands in one row per point of its OWN load, in the order it gave them to the driver --
+ * own point i is cloud point own_first + i of vgs_set_own_point_range -- so n_own must equal that range's length; channels, stride_bytes and
+ * NULL rules as vgs_segment_field_stats.  Over this context's own labelled points (input index in the own range, vox_label = k, global
+ * after vgs_apply_tile_labels: the points vgs_get_own_segment_moments counts in n_points) one record per label 0 .. K-1 with at least one
+ * such point, in ascending label order -- the label set of vgs_get_own_segment_extents.  *n_records is written; every array holds up to K
+ * records (x n_channels) and any may be NULL:
+ *   label      int32   k
+ *   n_valid    int64   valid (finite) values of the channel among the own points of k; may be 0
+ *   anchor     double  the value of k's first own point in the order of the descriptor chunks, 0.0 where it is not valid
+ *   s1, s2     double  sum d and sum d * d over the valid values, d = (double)x - anchor, summed in the fixed shape of vgs_segment_field_stats
+ *   vmin, vmax float   min and max of the valid values; +inf / -inf for n_valid = 0 (anchor, s1 and s2 are 0 then)
+ * Computed on the device on every call; nothing is cached and no other table is touched.  The device variant reads field_dev in place.
+ * VGS_E_STATE before the context is segmented and for a context that is not a tile context; VGS_E_ARG as vgs_segment_field_stats. */
+vgs_status vgs_get_own_segment_field_moments(vgs_ctx* ctx, int64_t K, const float* field_host, int64_t n_own, int32_t n_channels,
+                                             int64_t stride_bytes, int64_t* n_records, int32_t* label, int64_t* n_valid, double* anchor,
+                                             double* s1, double* s2, float* vmin, float* vmax);
+vgs_status vgs_get_own_segment_field_moments_device(vgs_ctx* ctx, int64_t K, const float* field_dev, int64_t n_own, int32_t n_channels,
+                                                    int64_t stride_bytes, int64_t* n_records, int32_t* label, int64_t* n_valid, double* anchor,
+                                                    double* s1, double* s2, float* vmin, float* vmax);
+/* The field table from moments already folded per (label, channel) about `anchor` (K x n_channels each, all required for K > 0; an entry no
+ * valid value reaches: n_valid 0, sums 0, vmin +inf, vmax -inf): mean, var, vmin and vmax of vgs_segment_field_stats by the same device
+ * code, on this context's GPU -- the finishing kernel of vgs_segment_field_stats runs over one partial per entry, so the arithmetic is
+ * not the host compiler's.  NaN rows for n_valid = 0.  Any output may be NULL.  Works on any context; nothing cached is touched. */
+vgs_status vgs_segment_field_stats_from_moments(vgs_ctx* ctx, int64_t K, int32_t n_channels, const int64_t* n_valid, const double* anchor,
+                                                const double* s1, const double* s2, const float* vmin, const float* vmax, double* mean,
+                                                double* var, float* vmin_out, float* vmax_out);
+/* Class counts of a tile context: rows, n_own, state and label set as vgs_get_own_segment_field_moments; cls holds one int32 per own point;
+ * the limits of vgs_segment_class_histogram (1 .. 1024 classes, K * n_classes <= 2^27).  Compact rows: label (int32), hist (int64, n_classes
+ * per record), n_outside (int64) over the own points of each label; any may be NULL. */
+vgs_status vgs_get_own_segment_class_counts(vgs_ctx* ctx, int64_t K, const int32_t* cls_host, int64_t n_own, int32_t n_classes,
+                                            int64_t* n_records, int32_t* label, int64_t* hist, int64_t* n_outside);
+vgs_status vgs_get_own_segment_class_counts_device(vgs_ctx* ctx, int64_t K, const int32_t* cls_dev, int64_t n_own, int32_t n_classes,
+                                                   int64_t* n_records, int32_t* label, int64_t* hist, int64_t* n_outside);
 
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.

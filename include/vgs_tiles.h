@@ -13,7 +13,8 @@
  * -> the same union-find over (rank, root) on every rank, size filter on global sizes -> labels applied on the GPU.  Per-segment
  * descriptors on request afterwards: a second collective of their own (vgs_tiles_get_segment_descriptors).  The segment adjacency graph
  * on request: a third collective of its own (vgs_tiles_get_segment_graph).  Oriented boxes on request: the descriptor table (its collective,
- * unless it is cached) and one collective of their own per frame (vgs_tiles_get_segment_boxes).
+ * unless it is cached) and one collective of their own per frame (vgs_tiles_get_segment_boxes).  Statistics of the caller's point
+ * attributes on request: one collective per call, nothing cached (vgs_tiles_segment_field_stats, vgs_tiles_segment_class_histogram).
  */
 #ifndef VGS_TILES_H_
 #define VGS_TILES_H_
@@ -199,6 +200,60 @@ vgs_status vgs_tiles_get_box_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS
  * record reaches: +inf / -inf and reached = 0.  VGS_E_ARG for a label outside 0 .. K-1. */
 vgs_status vgs_tiles_fold_extents(int world, const int64_t* rec_off, const int32_t* label, const double* lo3, const double* hi3, int64_t K,
                                   double* lo3_out, double* hi3_out, uint8_t* reached_out);
+/* Per-segment statistics of point attributes the CALLER supplies, over all ranks: the tables, fields, types and NaN rules of
+ * vgs_segment_field_stats and vgs_segment_class_histogram (include/vgs.h) with K = kept_global rows; row k covers exactly the points, over
+ * all ranks, that vgs_tiles_get_point_labels labels k.  No attribute travels between ranks, only per-segment records: every point is
+ * counted by the rank that loaded it (the rule of the tiled descriptors' n_points and of the tiled boxes), so a rank hands in one row per
+ * point of its own load, in the order it gave them to vgs_tiles_set_points -- n must equal that call's n; channels, stride_bytes and the
+ * class limits as in include/vgs.h.  Outputs are host arrays of K rows, any may be NULL; *K is written.  The _device variants read the
+ * input from HBM in place (this rank's device, complete before the call).
+ * Nothing is cached, because the input is the caller's: EVERY call is collective -- after one vgs_tiles_run every rank makes it, with
+ * the same n_channels / n_classes -- and makes exactly ONE all_gather_varlen.  vgs_tiles_run gains no launch and no collective; labels,
+ * descriptors, graph and boxes are not touched.
+ * Field statistics (csrc/tiles.cpp): each rank's moments of its own rows (vgs_get_own_segment_field_moments, one small pipeline on its
+ * GPU) -> one exchange of words of 8 bytes: a header of status word, record count and n_channels, then per record the label and per
+ * channel n_valid, anchor, S1, S2 and min | max (1 + 5 n_channels words) -> the same host fold on every rank
+ * (vgs_tiles_fold_field_moments) -> mean, var, vmin and vmax on the rank's GPU (vgs_segment_field_stats_from_moments: the finishing
+ * kernel of vgs_segment_field_stats itself).  `anchor` is the folded table's own shift: per (k, channel) the anchor of the lowest rank
+ * with a valid value.  Every rank receives the same bytes, bit-identical from call to call and from run to run on the same input and
+ * layout; with one rank the table is vgs_segment_field_stats' byte for byte.
+ * Histogram: each rank's rows (vgs_get_own_segment_class_counts) -> one exchange of int64 words (header of status word, record count and
+ * n_classes; per record label, n_outside, hist[n_classes]) -> integer adds and the majority rule on the host
+ * (vgs_tiles_fold_class_counts).
+ * Failures.  VGS_E_STATE before a run is decided locally (no collective).  Everything a rank can get wrong on its own -- a wrong n, a NULL
+ * input with n > 0, a bad channel, class or stride value, a failing context call, the injected VGS_TILES_FAIL_AT=fields -- travels in the
+ * status word, so no peer waits: the failing rank returns its own status and message, the others VGS_E_PEER naming it.  Ranks that are
+ * each valid but disagree on n_channels or n_classes all return VGS_E_ARG after the exchange; the message names the lowest rank that
+ * differs from rank 0. */
+vgs_status vgs_tiles_segment_field_stats(vgs_tiles* t, const float* field_host, int64_t n, int32_t n_channels, int64_t stride_bytes, int64_t* K,
+                                         int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax);
+vgs_status vgs_tiles_segment_field_stats_device(vgs_tiles* t, const float* field_dev, int64_t n, int32_t n_channels, int64_t stride_bytes,
+                                                int64_t* K, int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax);
+vgs_status vgs_tiles_segment_class_histogram(vgs_tiles* t, const int32_t* cls_host, int64_t n, int32_t n_classes, int64_t* K, int64_t* hist,
+                                             int64_t* n_outside, int32_t* majority, int64_t* majority_count);
+vgs_status vgs_tiles_segment_class_histogram_device(vgs_tiles* t, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* K, int64_t* hist,
+                                                    int64_t* n_outside, int32_t* majority, int64_t* majority_count);
+/* host wall time of the last attribute collective on this rank (field statistics or histogram, whichever came last), milliseconds: own
+ * records on the GPU (with upload and download), the exchange, the fold, the finish on the GPU (with upload and download; 0 for the
+ * histogram, whose majority rule is part of the fold), total */
+enum { VGS_TILES_F_OWN = 0, VGS_TILES_F_EXCHANGE = 1, VGS_TILES_F_FOLD = 2, VGS_TILES_F_FINISH = 3, VGS_TILES_F_TOTAL = 4, VGS_TILES_F_COUNT = 5 };
+vgs_status vgs_tiles_get_field_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_F_COUNT */);
+/* that collective's payload on this rank: records of its own, bytes it put into the all-gather (header included, before padding) */
+vgs_status vgs_tiles_get_field_payload(vgs_tiles* t, int64_t* own_records, int64_t* bytes_sent);
+/* The attribute folds on their own (host arithmetic, no context, no GPU; for tests): rank r's records are entries rec_off[r] ..
+ * rec_off[r+1] of the arrays vgs_get_own_segment_field_moments / vgs_get_own_segment_class_counts give.  Outputs: K rows, every pointer
+ * required for K > 0.
+ * Field moments, per (label, channel), ranks in ascending order: the anchor a is the anchor of the lowest rank with n_valid > 0, whose sums
+ * are taken as they are; with delta = a_r - a in fp64 a later rank adds S1 += S1_r + n_r delta and S2 += S2_r + S1_r delta + delta S1_r
+ * + n_r delta delta; n_valid adds; vmin / vmax take min / max.  An entry no valid value reaches: n_valid 0, anchor and sums 0, +inf / -inf.
+ * Class counts: integer adds, then majority = the lowest class with the largest count, -1 and 0 when every count is 0.
+ * VGS_E_ARG for a label outside 0 .. K-1. */
+vgs_status vgs_tiles_fold_field_moments(int world, const int64_t* rec_off, const int32_t* label, int32_t n_channels, const int64_t* n_valid,
+                                        const double* anchor, const double* s1, const double* s2, const float* vmin, const float* vmax, int64_t K,
+                                        int64_t* n_valid_out, double* anchor_out, double* s1_out, double* s2_out, float* vmin_out, float* vmax_out);
+vgs_status vgs_tiles_fold_class_counts(int world, const int64_t* rec_off, const int32_t* label, int32_t n_classes, const int64_t* hist,
+                                       const int64_t* n_outside, int64_t K, int64_t* hist_out, int64_t* n_outside_out, int32_t* majority_out,
+                                       int64_t* majority_count_out);
 /* the rank's engine context (read-only use: counts, stage times) */
 vgs_ctx* vgs_tiles_context(vgs_tiles* t);
 

@@ -110,6 +110,11 @@ SYMBOLS = [
     ("vgs_segment_field_stats_device", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P]),
     ("vgs_segment_class_histogram", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     ("vgs_segment_class_histogram_device", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    ("vgs_get_own_segment_field_moments", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_get_own_segment_field_moments_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_segment_field_stats_from_moments", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_get_own_segment_class_counts", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    ("vgs_get_own_segment_class_counts_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     ("vgs_grid_state_init", C.c_int, [C.POINTER(VgsGridState)]),
     ("vgs_grid_advance", C.c_int, [_P, C.POINTER(VgsGridState)]),
     ("vgs_points_bbox", C.c_int, [_P, _P, C.POINTER(C.c_int64)]),

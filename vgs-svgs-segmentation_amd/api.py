@@ -334,14 +334,54 @@ class Engine:
     def _is_torch(a):
         return type(a).__module__.split(".")[0] == "torch"
 
-    def _device_input(self, t, dtype_name, what):
+    @staticmethod
+    def _device_input(t, dtype_name, what, device):
         """A torch tensor on the context's device, complete before the library reads it on its own stream."""
         import torch
         if t.dtype != getattr(torch, dtype_name):
             raise ValueError(f"{what} must be {dtype_name}")
-        if t.device.type != "cuda" or (t.device.index or 0) != int(self.params.device):
+        if t.device.type != "cuda" or (t.device.index or 0) != int(device):
             raise ValueError(f"{what} must be a numpy array or a torch tensor on the context's device")
         torch.cuda.synchronize(t.device)
+
+    @staticmethod
+    def _field_input(field, device):
+        """(array kept alive, pointer, n, channels, stride_bytes, on the device?) of a per-point attribute: float32 of shape (N,) or (N, C),
+        C-contiguous or with a row stride (a multiple of 4 bytes; the channels of a row adjacent); a numpy array, or a torch tensor on the
+        context's device, which is read in place."""
+        if Engine._is_torch(field):
+            Engine._device_input(field, "float32", "field", device)
+            if field.dim() == 1:
+                field = field.unsqueeze(1)
+            if field.dim() != 2 or (field.shape[1] > 1 and field.stride(1) != 1) or (field.shape[0] > 1 and field.stride(0) < field.shape[1]):
+                raise ValueError("field must be (N,) or (N, C) with adjacent channels and a row stride of at least C")
+            n, ch = int(field.shape[0]), int(field.shape[1])
+            return field, C.c_void_p(field.data_ptr()), n, ch, (int(field.stride(0)) * 4 if n > 1 else ch * 4), True
+        field = np.asarray(field)
+        if field.dtype != np.float32:
+            raise ValueError("field must be float32")
+        if field.ndim == 1:
+            field = field[:, None]
+        if field.ndim != 2:
+            raise ValueError("field must be (N,) or (N, C)")
+        n, ch = field.shape
+        if (ch > 1 and field.strides[1] != 4) or (n > 1 and (field.strides[0] < 4 * ch or field.strides[0] % 4)):
+            field = np.ascontiguousarray(field)   # (negative, interleaved or odd strides: the library takes rows of adjacent channels, 4-byte steps)
+        return field, _ptr(field), n, ch, (int(field.strides[0]) if n > 1 else ch * 4), False
+
+    @staticmethod
+    def _classes_input(classes, device):
+        """(array kept alive, pointer, n, on the device?) of a per-point class: int32 of shape (N,), numpy or a torch tensor on the device"""
+        if Engine._is_torch(classes):
+            Engine._device_input(classes, "int32", "classes", device)
+            if classes.dim() != 1 or (classes.shape[0] > 1 and classes.stride(0) != 1):
+                raise ValueError("classes must be a contiguous (N,) tensor")
+            return classes, C.c_void_p(classes.data_ptr()), int(classes.shape[0]), True
+        classes = np.asarray(classes)
+        if classes.dtype != np.int32 or classes.ndim != 1:
+            raise ValueError("classes must be int32 of shape (N,)")
+        classes = np.ascontiguousarray(classes)
+        return classes, _ptr(classes), classes.shape[0], False
 
     def segment_field_stats(self, field):
         """Per-segment statistics of a per-point attribute, row k = the points labelled k (include/vgs.h, vgs_segment_field_stats): a dict
@@ -350,29 +390,8 @@ class Engine:
         tensor on the context's device, which is read in place.  NaN and +-inf are skipped.  Computed on the device on every call,
         bit-identical from call to call."""
         K = self.counts()["kept"]
-        dev = self._is_torch(field)
-        if dev:
-            self._device_input(field, "float32", "field")
-            if field.dim() == 1:
-                field = field.unsqueeze(1)
-            if field.dim() != 2 or (field.shape[1] > 1 and field.stride(1) != 1) or (field.shape[0] > 1 and field.stride(0) < field.shape[1]):
-                raise ValueError("field must be (N,) or (N, C) with adjacent channels and a row stride of at least C")
-            n, ch = int(field.shape[0]), int(field.shape[1])
-            stride = int(field.stride(0)) * 4 if n > 1 else ch * 4
-            ptr, fn = C.c_void_p(field.data_ptr()), self._L.vgs_segment_field_stats_device
-        else:
-            field = np.asarray(field)
-            if field.dtype != np.float32:
-                raise ValueError("field must be float32")
-            if field.ndim == 1:
-                field = field[:, None]
-            if field.ndim != 2:
-                raise ValueError("field must be (N,) or (N, C)")
-            n, ch = field.shape
-            if (ch > 1 and field.strides[1] != 4) or (n > 1 and (field.strides[0] < 4 * ch or field.strides[0] % 4)):
-                field = np.ascontiguousarray(field)   # (negative, interleaved or odd strides: the library takes rows of adjacent channels, 4-byte steps)
-            stride = int(field.strides[0]) if n > 1 else ch * 4
-            ptr, fn = _ptr(field), self._L.vgs_segment_field_stats
+        field, ptr, n, ch, stride, dev = self._field_input(field, self.params.device)
+        fn = self._L.vgs_segment_field_stats_device if dev else self._L.vgs_segment_field_stats
         out = {name: np.zeros((K, max(ch, 0)), dtype=dt) for name, dt in self.FIELD_STAT_FIELDS}
         self._ck(fn(self._h, ptr, n, ch, stride, *(_ptr(out[name]) for name, _ in self.FIELD_STAT_FIELDS)))
         return out
@@ -384,17 +403,8 @@ class Engine:
         order, a numpy array or a torch tensor on the context's device."""
         K = self.counts()["kept"]
         nc = int(n_classes)
-        if self._is_torch(classes):
-            self._device_input(classes, "int32", "classes")
-            if classes.dim() != 1 or (classes.shape[0] > 1 and classes.stride(0) != 1):
-                raise ValueError("classes must be a contiguous (N,) tensor")
-            n, ptr, fn = int(classes.shape[0]), C.c_void_p(classes.data_ptr()), self._L.vgs_segment_class_histogram_device
-        else:
-            classes = np.asarray(classes)
-            if classes.dtype != np.int32 or classes.ndim != 1:
-                raise ValueError("classes must be int32 of shape (N,)")
-            classes = np.ascontiguousarray(classes)
-            n, ptr, fn = classes.shape[0], _ptr(classes), self._L.vgs_segment_class_histogram
+        classes, ptr, n, dev = self._classes_input(classes, self.params.device)
+        fn = self._L.vgs_segment_class_histogram_device if dev else self._L.vgs_segment_class_histogram
         out = {name: np.zeros((K, max(nc, 0)) if w == 0 else K, dtype=dt) for name, dt, w in self.CLASS_HIST_FIELDS}
         self._ck(fn(self._h, ptr, n, nc, *(_ptr(out[name]) for name, _, _ in self.CLASS_HIST_FIELDS)))
         return out

@@ -229,7 +229,7 @@ void vgs_destroy(vgs_ctx* c) {
   c->sd_key.release(); c->sd_ids.release(); c->sd_vp.release(); c->sd_seg.release(); c->sd_tmp.release(); c->sd_part.release();
   c->sd_npts.release(); c->sd_nnodes.release(); c->sd_bbox.release(); c->sd_eig8.release(); c->sd_cen.release(); c->sd_cov.release(); c->sd_eval.release(); c->sd_evec.release();
   c->sd_apos.release(); c->sd_mom.release();
-  c->sf_in.release(); c->sf_min.release(); c->sf_max.release(); c->sf_cls.release(); c->sf_maj.release(); c->sf_part.release(); c->sf_anchor.release();
+  c->sf_in.release(); c->sf_min.release(); c->sf_max.release(); c->sf_cls.release(); c->sf_maj.release(); c->sf_part.release(); c->sf_anchor.release(); c->sf_idx.release();
   c->sf_mean.release(); c->sf_var.release(); c->sf_nvalid.release(); c->sf_hist.release();
   c->sb_part.release(); c->sbt_in.release(); c->sbt_frame.release(); c->sbt_out.release(); c->sbt_idx.release();
   for (int f = 0; f < 2; ++f) { c->sb_frame[f].release(); c->sb_lo[f].release(); c->sb_hi[f].release(); c->sb_half[f].release(); c->sb_center[f].release(); }

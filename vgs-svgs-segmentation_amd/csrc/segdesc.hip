@@ -507,6 +507,15 @@ extern "C" vgs_status vgs_get_segment_descriptors_device(vgs_ctx* c, const int64
 }
 
 // ------------------------------------------------------------------------------------------------ tile contexts (include/vgs_tiles.h)
+// The first own point of every label 0 .. K-1 of a prepared decomposition into sd_apos (k_sd_own_anchor; left on the stream).  One launch
+// site for the descriptor moments here and the attribute moments of segfield.hip.
+vgs_status sd_own_anchor(vgs_ctx* c, int64_t K, const SdPrep& P) {
+  VGS_HIP_TRY(c, c->sd_apos.ensure((size_t)K));
+  hipLaunchKernelGGL(k_sd_own_anchor, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, c->vox_start.p, P.ids, P.seg_node, c->perm_b.p,
+                     c->own_first, c->own_first + c->n_own, (uint32_t)K, c->sd_apos.p);
+  return VGS_OK;
+}
+
 // This rank's moments of the global labels 0 .. K-1: the pipeline above over vox_label (global after vgs_apply_tile_labels), with the
 // own-point chunks, the first own point as anchor, and the owned-voxel count.  Dense on the device (K records), compact on the host.
 extern "C" vgs_status vgs_get_own_segment_moments(vgs_ctx* c, int64_t K, int64_t* n_records, int32_t* label, int64_t* n_points, int32_t* n_nodes,
@@ -524,12 +533,10 @@ extern "C" vgs_status vgs_get_own_segment_moments(vgs_ctx* c, int64_t K, int64_t
   SdPrep P;
   vgs_status s = sd_prepare(c, K, P);
   if (s != VGS_OK) return s;
-  VGS_HIP_TRY(c, c->sd_apos.ensure((size_t)K));
   VGS_HIP_TRY(c, c->sd_mom.ensure((size_t)K * SD_MREC));
   const int64_t own_end = c->own_first + c->n_own;
   const unsigned waves_grid = (unsigned)((K + 3) / 4);
-  hipLaunchKernelGGL(k_sd_own_anchor, dim3(waves_grid), dim3(256), 0, c->stream, c->vox_start.p, P.ids, P.seg_node, c->perm_b.p, c->own_first,
-                     own_end, (uint32_t)K, c->sd_apos.p);
+  if ((s = sd_own_anchor(c, K, P)) != VGS_OK) return s;
   hipLaunchKernelGGL(k_sd_chunks_own, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, P.ids, P.vp,
                      P.seg_node, P.seg_chunk, (uint32_t)K, c->sd_part.p, c->perm_b.p, c->own_first, own_end, c->sd_apos.p);
   hipLaunchKernelGGL(k_sd_own_records, dim3(waves_grid), dim3(256), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, P.ids, P.seg_node, P.seg_chunk,

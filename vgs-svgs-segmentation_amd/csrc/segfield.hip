@@ -21,8 +21,15 @@
 // its first lane's class, so a segment of one class costs one LDS add per wavefront and step) and adds only its non-zero counters to the
 // zeroed K x n_classes table -- at most one global add per (chunk, class), never every point of the ground at one address.
 // Nothing is cached and no getter's table is touched: scratch of sd_prepare (sd_*) and buffers of its own (sf_*).
+// Tile contexts (the tiled driver, include/vgs_tiles.h): a rank hands in one row per point of its OWN load (own point i = cloud point
+// own_first + i) and only per-segment records travel.  k_sd_own_anchor (segdesc.hip) gives every global label's first own point,
+// k_sf_anchor_own its values, k_sf_chunks_own / k_sf_hist_own run the chunk bodies over the own points only, k_sf_own_records folds the
+// partials as k_sf_final does and leaves n, S1, S2, min and max as they are (vgs_get_own_segment_field_moments,
+// vgs_get_own_segment_class_counts); the driver folds all ranks' records on the host and k_sf_final itself, over one partial per
+// (segment, channel), finishes the table (vgs_segment_field_stats_from_moments).
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 
 #include "vgs_context.hpp"
@@ -64,22 +71,34 @@ __global__ __launch_bounds__(256) void k_sf_anchor(const float* __restrict__ fie
 }
 
 // One workgroup per chunk, channels c0 .. c0 + ng - 1 (ng <= SF_G): one partial record per (chunk, channel of the group).  Grid: the bound
-// of sd_prepare; workgroups past the real number of chunks leave at once.
-__global__ __launch_bounds__(SD_TB) void k_sf_chunks(const float* __restrict__ field, int64_t stride_f, uint32_t C, uint32_t c0, uint32_t ng,
-                                                     const uint32_t* __restrict__ perm, const uint32_t* __restrict__ vox_start,
-                                                     const uint32_t* __restrict__ ids, const uint32_t* __restrict__ vp,
-                                                     const uint32_t* __restrict__ seg_node, const uint32_t* __restrict__ seg_chunk, uint32_t K,
-                                                     const double* __restrict__ anchor, double* __restrict__ part) {
+// of sd_prepare; workgroups past the real number of chunks leave at once.  OWN (tile contexts, k_sf_chunks_own): only the points whose
+// input index o = perm[pos] lies in [own_first, own_end) count -- the selection of segdesc.hip's k_sd_chunks_own -- and their row is
+// field + (o - own_first) * stride; a segment without an own point (anchor_pos[k] = 0xffffffff, from k_sd_own_anchor) writes the empty record.
+__device__ __forceinline__ void sf_empty_record(double* __restrict__ rec) {
+  if (threadIdx.x < SF_G * SF_REC) {
+    const int f = threadIdx.x % SF_REC;
+    rec[threadIdx.x] = f < 3 ? 0.0 : (f == 3 ? __builtin_huge_val() : -__builtin_huge_val());
+  }
+}
+
+template <bool OWN>
+__device__ __forceinline__ void sf_chunk_body(const float* __restrict__ field, int64_t stride_f, uint32_t C, uint32_t c0, uint32_t ng,
+                                              const uint32_t* __restrict__ perm, const uint32_t* __restrict__ vox_start,
+                                              const uint32_t* __restrict__ ids, const uint32_t* __restrict__ vp,
+                                              const uint32_t* __restrict__ seg_node, const uint32_t* __restrict__ seg_chunk, uint32_t K,
+                                              const double* __restrict__ anchor, double* __restrict__ part, int64_t own_first, int64_t own_end,
+                                              const uint32_t* __restrict__ anchor_pos) {
   __shared__ uint32_t s_vp[SD_CHUNK];    // virtual start of the chunk's nodes
   __shared__ uint32_t s_dl[SD_CHUNK];    // sorted position - virtual position of the same (mod 2^32)
   __shared__ double s_red[SD_TB / 64][SF_G][SF_REC];
   SdChunk w;
   double* rec = part + (size_t)blockIdx.x * (SF_G * SF_REC);
   if (!sd_walk(vox_start, ids, vp, seg_node, seg_chunk, K, s_vp, s_dl, w)) {
-    if (w.k != 0xffffffffu && threadIdx.x < SF_G * SF_REC) {   // an empty record keeps the fold well defined
-      const int f = threadIdx.x % SF_REC;
-      rec[threadIdx.x] = f < 3 ? 0.0 : (f == 3 ? __builtin_huge_val() : -__builtin_huge_val());
-    }
+    if (w.k != 0xffffffffu) sf_empty_record(rec);   // an empty record keeps the fold well defined
+    return;
+  }
+  if (OWN && anchor_pos[w.k] == 0xffffffffu) {   // no own point in this segment: nothing counts
+    sf_empty_record(rec);
     return;
   }
   double an[SF_G];
@@ -95,7 +114,13 @@ __global__ __launch_bounds__(SD_TB) void k_sf_chunks(const float* __restrict__ f
     const uint32_t q = w.a + (uint32_t)it * SD_TB + threadIdx.x;
     if (q < w.b) {
       const uint32_t pos = sd_pos(s_vp, s_dl, w.m, q);
-      const float* row = field + (size_t)perm[pos] * (size_t)stride_f + c0;
+      size_t ri = (size_t)perm[pos];
+      if (OWN) {
+        const int64_t o = (int64_t)ri;
+        if (o < own_first || o >= own_end) continue;
+        ri = (size_t)(o - own_first);
+      }
+      const float* row = field + ri * (size_t)stride_f + c0;
 #pragma unroll
       for (int g = 0; g < SF_G; ++g) {
         if ((uint32_t)g < ng) {
@@ -133,6 +158,57 @@ __global__ __launch_bounds__(SD_TB) void k_sf_chunks(const float* __restrict__ f
   }
 }
 
+__global__ __launch_bounds__(SD_TB) void k_sf_chunks(const float* __restrict__ field, int64_t stride_f, uint32_t C, uint32_t c0, uint32_t ng,
+                                                     const uint32_t* __restrict__ perm, const uint32_t* __restrict__ vox_start,
+                                                     const uint32_t* __restrict__ ids, const uint32_t* __restrict__ vp,
+                                                     const uint32_t* __restrict__ seg_node, const uint32_t* __restrict__ seg_chunk, uint32_t K,
+                                                     const double* __restrict__ anchor, double* __restrict__ part) {
+  sf_chunk_body<false>(field, stride_f, C, c0, ng, perm, vox_start, ids, vp, seg_node, seg_chunk, K, anchor, part, 0, 0, nullptr);
+}
+
+__global__ __launch_bounds__(SD_TB) void k_sf_chunks_own(const float* __restrict__ field, int64_t stride_f, uint32_t C, uint32_t c0, uint32_t ng,
+                                                         const uint32_t* __restrict__ perm, const uint32_t* __restrict__ vox_start,
+                                                         const uint32_t* __restrict__ ids, const uint32_t* __restrict__ vp,
+                                                         const uint32_t* __restrict__ seg_node, const uint32_t* __restrict__ seg_chunk, uint32_t K,
+                                                         const double* __restrict__ anchor, double* __restrict__ part, int64_t own_first,
+                                                         int64_t own_end, const uint32_t* __restrict__ anchor_pos) {
+  sf_chunk_body<true>(field, stride_f, C, c0, ng, perm, vox_start, ids, vp, seg_node, seg_chunk, K, anchor, part, own_first, own_end, anchor_pos);
+}
+
+// Tile contexts: anchor[k, c] for every channel = the value of the segment's first own point in the chunk order (anchor_pos[k], from
+// k_sd_own_anchor), 0.0 where that value is not finite and for a segment without an own point.  One thread per entry.
+__global__ __launch_bounds__(256) void k_sf_anchor_own(const float* __restrict__ field, int64_t stride_f, uint32_t C, const uint32_t* __restrict__ perm,
+                                                       const uint32_t* __restrict__ anchor_pos, int64_t own_first, int64_t own_end, uint32_t K,
+                                                       double* __restrict__ anchor) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (uint64_t)K * C) return;
+  const uint32_t k = (uint32_t)(t / C), ch = (uint32_t)(t % C);
+  const uint32_t pa = anchor_pos[k];
+  double v = 0.0;
+  if (pa != 0xffffffffu) {
+    const int64_t o = (int64_t)perm[pa];
+    if (o >= own_first && o < own_end) {   // (k_sd_own_anchor's own selection: the test only guards the read)
+      const float x = field[(size_t)(o - own_first) * (size_t)stride_f + ch];
+      if (sf_valid(x)) v = (double)x;
+    }
+  }
+  anchor[t] = v;
+}
+
+// the fold of one (segment, channel of the group) over its chunk partials, on one wavefront: lane stride, then butterfly
+__device__ __forceinline__ void sf_fold_partials(const uint32_t* seg_chunk, const double* part, uint32_t n_part, uint32_t k,
+                                                 uint32_t g, uint32_t lane, double& s1, double& s2, double& cn, double& mn, double& mx) {
+  const uint32_t q0 = seg_chunk[k], q1 = min(seg_chunk[k + 1], n_part);   // (the bound only guards the records: the chunks fit, see the launch)
+  s1 = 0.0; s2 = 0.0; cn = 0.0; mn = __builtin_huge_val(); mx = -__builtin_huge_val();
+  for (uint32_t c = q0 + lane; c < q1; c += 64) {
+    const double* r = part + ((size_t)c * SF_G + g) * SF_REC;
+    s1 += r[0]; s2 += r[1]; cn += r[2];
+    mn = fmin(mn, r[3]); mx = fmax(mx, r[4]);
+  }
+  s1 = sf_wave_sum(s1); s2 = sf_wave_sum(s2); cn = sf_wave_sum(cn);
+  mn = sf_wave_min(mn); mx = sf_wave_max(mx);
+}
+
 // one wavefront per (segment, channel of the group): fold the partials (lane stride, then butterfly), then the row's entries on lane 0
 __global__ __launch_bounds__(256) void k_sf_final(const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part, uint32_t n_part, uint32_t K,
                                                   uint32_t C, uint32_t c0, uint32_t ng, const double* __restrict__ anchor,
@@ -142,15 +218,8 @@ __global__ __launch_bounds__(256) void k_sf_final(const uint32_t* __restrict__ s
   const uint32_t lane = threadIdx.x & 63;
   if (wi >= (uint64_t)K * ng) return;   // (whole wavefronts; no barrier follows)
   const uint32_t k = (uint32_t)(wi / ng), g = (uint32_t)(wi % ng);
-  const uint32_t q0 = seg_chunk[k], q1 = min(seg_chunk[k + 1], n_part);   // (the bound only guards the records: the chunks fit, see the launch)
-  double s1 = 0.0, s2 = 0.0, cn = 0.0, mn = __builtin_huge_val(), mx = -__builtin_huge_val();
-  for (uint32_t c = q0 + lane; c < q1; c += 64) {
-    const double* r = part + ((size_t)c * SF_G + g) * SF_REC;
-    s1 += r[0]; s2 += r[1]; cn += r[2];
-    mn = fmin(mn, r[3]); mx = fmax(mx, r[4]);
-  }
-  s1 = sf_wave_sum(s1); s2 = sf_wave_sum(s2); cn = sf_wave_sum(cn);
-  mn = sf_wave_min(mn); mx = sf_wave_max(mx);
+  double s1, s2, cn, mn, mx;
+  sf_fold_partials(seg_chunk, part, n_part, k, g, lane, s1, s2, cn, mn, mx);
   if (lane != 0) return;
   const size_t o = (size_t)k * C + c0 + g;
   o_n[o] = (int64_t)cn;
@@ -167,13 +236,33 @@ __global__ __launch_bounds__(256) void k_sf_final(const uint32_t* __restrict__ s
   }
 }
 
+// Tile contexts: the fold of k_sf_final over the partials of k_sf_chunks_own, the sums left as they are -- one wavefront per (segment,
+// channel of the group) writes n, S1, S2, min and max of the rank's own points (0, 0, 0, +inf, -inf without a valid value).
+__global__ __launch_bounds__(256) void k_sf_own_records(const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part, uint32_t n_part,
+                                                        uint32_t K, uint32_t C, uint32_t c0, uint32_t ng, int64_t* __restrict__ o_n,
+                                                        double* __restrict__ o_s1, double* __restrict__ o_s2, float* __restrict__ o_min,
+                                                        float* __restrict__ o_max) {
+  const uint64_t wi = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (wi >= (uint64_t)K * ng) return;   // (whole wavefronts; no barrier follows)
+  const uint32_t k = (uint32_t)(wi / ng), g = (uint32_t)(wi % ng);
+  double s1, s2, cn, mn, mx;
+  sf_fold_partials(seg_chunk, part, n_part, k, g, lane, s1, s2, cn, mn, mx);
+  if (lane != 0) return;
+  const size_t o = (size_t)k * C + c0 + g;
+  o_n[o] = (int64_t)cn; o_s1[o] = s1; o_s2[o] = s2;
+  o_min[o] = (float)mn; o_max[o] = (float)mx;
+}
+
 // One workgroup per chunk: the classes of its points counted in LDS (slot n_classes: out of range), the non-zero counters added to the
-// zeroed tables.  hist: K x n_classes, n_outside: K.  Integer atomics: the sums do not depend on the order.
-__global__ __launch_bounds__(SD_TB) void k_sf_hist(const int32_t* __restrict__ cls, uint32_t n_classes, const uint32_t* __restrict__ perm,
-                                                   const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
-                                                   const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
-                                                   const uint32_t* __restrict__ seg_chunk, uint32_t K, unsigned long long* __restrict__ hist,
-                                                   unsigned long long* __restrict__ n_outside) {
+// zeroed tables.  hist: K x n_classes, n_outside: K.  Integer atomics: the sums do not depend on the order.  OWN (tile contexts,
+// k_sf_hist_own): only the points whose input index o = perm[pos] lies in [own_first, own_end) count, and their class is cls[o - own_first].
+template <bool OWN>
+__device__ __forceinline__ void sf_hist_body(const int32_t* __restrict__ cls, uint32_t n_classes, const uint32_t* __restrict__ perm,
+                                             const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                             const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                             const uint32_t* __restrict__ seg_chunk, uint32_t K, unsigned long long* __restrict__ hist,
+                                             unsigned long long* __restrict__ n_outside, int64_t own_first, int64_t own_end) {
   __shared__ uint32_t s_vp[SD_CHUNK];
   __shared__ uint32_t s_dl[SD_CHUNK];
   __shared__ uint32_t s_cnt[1024 + 1];
@@ -184,11 +273,19 @@ __global__ __launch_bounds__(SD_TB) void k_sf_hist(const int32_t* __restrict__ c
   const uint32_t lane = threadIdx.x & 63;
   for (int it = 0; it < SD_PPT; ++it) {
     const uint32_t q = w.a + (uint32_t)it * SD_TB + threadIdx.x;
-    const bool act = q < w.b;
+    bool act = q < w.b;
     uint32_t slot = 0;
     if (act) {
-      const int32_t v = cls[perm[sd_pos(s_vp, s_dl, w.m, q)]];
-      slot = (v < 0 || (uint32_t)v >= n_classes) ? n_classes : (uint32_t)v;
+      size_t ri = (size_t)perm[sd_pos(s_vp, s_dl, w.m, q)];
+      if (OWN) {
+        const int64_t o = (int64_t)ri;
+        act = o >= own_first && o < own_end;
+        ri = act ? (size_t)(o - own_first) : 0;
+      }
+      if (act) {
+        const int32_t v = cls[ri];
+        slot = (v < 0 || (uint32_t)v >= n_classes) ? n_classes : (uint32_t)v;
+      }
     }
     // the lanes that share the first active lane's class fold into one add; the others add one each
     const uint64_t am = __ballot(act);
@@ -206,6 +303,22 @@ __global__ __launch_bounds__(SD_TB) void k_sf_hist(const int32_t* __restrict__ c
     if (j < n_classes) atomicAdd(hist + (size_t)w.k * n_classes + j, (unsigned long long)v);
     else atomicAdd(n_outside + w.k, (unsigned long long)v);
   }
+}
+
+__global__ __launch_bounds__(SD_TB) void k_sf_hist(const int32_t* __restrict__ cls, uint32_t n_classes, const uint32_t* __restrict__ perm,
+                                                   const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                   const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                   const uint32_t* __restrict__ seg_chunk, uint32_t K, unsigned long long* __restrict__ hist,
+                                                   unsigned long long* __restrict__ n_outside) {
+  sf_hist_body<false>(cls, n_classes, perm, vox_start, ids, vp, seg_node, seg_chunk, K, hist, n_outside, 0, 0);
+}
+
+__global__ __launch_bounds__(SD_TB) void k_sf_hist_own(const int32_t* __restrict__ cls, uint32_t n_classes, const uint32_t* __restrict__ perm,
+                                                       const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
+                                                       const uint32_t* __restrict__ vp, const uint32_t* __restrict__ seg_node,
+                                                       const uint32_t* __restrict__ seg_chunk, uint32_t K, unsigned long long* __restrict__ hist,
+                                                       unsigned long long* __restrict__ n_outside, int64_t own_first, int64_t own_end) {
+  sf_hist_body<true>(cls, n_classes, perm, vox_start, ids, vp, seg_node, seg_chunk, K, hist, n_outside, own_first, own_end);
 }
 
 // one wavefront per segment: the lowest class with the largest count (-1 and 0 when every count is 0)
@@ -386,4 +499,248 @@ extern "C" vgs_status vgs_segment_class_histogram(vgs_ctx* c, const int32_t* cls
   VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_cls.p, cls_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
   return sf_class_hist(c, c->sf_cls.p, n_classes, hist, n_outside, majority, majority_count);
+}
+
+// ------------------------------------------------------------------------------------------------ tile contexts (include/vgs_tiles.h)
+static vgs_status sft_check_state(vgs_ctx* c, const char* fn) {
+  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
+  if (!c->have_region || c->n_own < 0) {
+    c->err = std::string(fn) + ": a tile context (vgs_set_owned_region and vgs_set_own_point_range) only";
+    return VGS_E_STATE;
+  }
+  return VGS_OK;
+}
+
+static vgs_status sft_check_n(vgs_ctx* c, const char* fn, const void* in, int64_t n_own) {
+  if (n_own != c->n_own) {
+    c->err = std::string(fn) + ": n_own = " + std::to_string(n_own) + " must equal the number of own points of the context, " + std::to_string(c->n_own);
+    return VGS_E_ARG;
+  }
+  if (!in && n_own > 0) { c->err = std::string(fn) + ": the input array is NULL"; return VGS_E_ARG; }
+  return VGS_OK;
+}
+
+static vgs_status sft_check_field(vgs_ctx* c, const char* fn, int64_t K, const float* field, int64_t n_own, int32_t n_channels, int64_t stride_bytes) {
+  vgs_status s = sft_check_state(c, fn);
+  if (s != VGS_OK) return s;
+  if (K < 0 || K >= (int64_t)0xffffffffLL) { c->err = std::string(fn) + ": K = " + std::to_string(K) + " is out of range"; return VGS_E_ARG; }
+  if ((s = sft_check_n(c, fn, field, n_own)) != VGS_OK) return s;
+  if (n_channels < 1 || n_channels > 64) {
+    c->err = std::string(fn) + ": n_channels = " + std::to_string(n_channels) + " must be in 1 .. 64";
+    return VGS_E_ARG;
+  }
+  if (stride_bytes < 4 * (int64_t)n_channels || stride_bytes % 4 != 0) {
+    c->err = std::string(fn) + ": stride_bytes = " + std::to_string(stride_bytes) + " must be a multiple of 4 and at least 4 * n_channels = " +
+             std::to_string(4 * (int64_t)n_channels);
+    return VGS_E_ARG;
+  }
+  return VGS_OK;
+}
+
+// the labels with an own labelled point, ascending: anchor_pos[k] != 0xffffffff (the label set of vgs_get_own_segment_extents)
+static void sft_own_labels(const std::vector<uint32_t>& apos, std::vector<int64_t>& rows) {
+  rows.clear();
+  for (size_t k = 0; k < apos.size(); ++k) if (apos[k] != 0xffffffffu) rows.push_back((int64_t)k);
+}
+
+// This rank's moments of the global labels 0 .. K-1 over its own points, from a device buffer of n_own rows: sd_prepare over vox_label
+// (global after vgs_apply_tile_labels), the first own points, their values as anchors, the own-point chunks per channel group, the fold
+// without the finish.  Dense on the device (K x n_channels), compact on the host.
+static vgs_status sft_field_moments(vgs_ctx* c, int64_t K, const float* field_dev, int32_t n_channels, int64_t stride_bytes, int64_t* n_records,
+                                    int32_t* label, int64_t* n_valid, double* anchor, double* s1, double* s2, float* vmin, float* vmax) {
+  *n_records = 0;
+  if (K == 0 || c->V == 0 || c->Nf == 0) return VGS_OK;
+  const uint32_t C = (uint32_t)n_channels;
+  const size_t kc = (size_t)K * C;
+  const int64_t stride_f = stride_bytes / 4, own_end = c->own_first + c->n_own;
+  SdPrep P;
+  vgs_status s = sd_prepare(c, K, P);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, c->sf_part.ensure((size_t)P.n_chunks_max * SF_G * SF_REC));
+  VGS_HIP_TRY(c, c->sf_anchor.ensure(kc)); VGS_HIP_TRY(c, c->sf_mean.ensure(kc)); VGS_HIP_TRY(c, c->sf_var.ensure(kc));
+  VGS_HIP_TRY(c, c->sf_nvalid.ensure(kc)); VGS_HIP_TRY(c, c->sf_min.ensure(kc)); VGS_HIP_TRY(c, c->sf_max.ensure(kc));
+  if ((s = sd_own_anchor(c, K, P)) != VGS_OK) return s;
+  hipLaunchKernelGGL(k_sf_anchor_own, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, c->stream, field_dev, stride_f, C, c->perm_b.p, c->sd_apos.p,
+                     c->own_first, own_end, (uint32_t)K, c->sf_anchor.p);
+  for (uint32_t c0 = 0; c0 < C; c0 += SF_G) {
+    const uint32_t ng = C - c0 < SF_G ? C - c0 : SF_G;
+    hipLaunchKernelGGL(k_sf_chunks_own, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, field_dev, stride_f, C, c0, ng, c->perm_b.p,
+                       c->vox_start.p, P.ids, P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, c->sf_anchor.p, c->sf_part.p, c->own_first, own_end,
+                       c->sd_apos.p);
+    hipLaunchKernelGGL(k_sf_own_records, dim3((unsigned)(((size_t)K * ng + 3) / 4)), dim3(256), 0, c->stream, P.seg_chunk, c->sf_part.p,
+                       (uint32_t)P.n_chunks_max, (uint32_t)K, C, c0, ng, c->sf_nvalid.p, c->sf_mean.p, c->sf_var.p, c->sf_min.p, c->sf_max.p);
+  }
+  VGS_HIP_TRY(c, hipGetLastError());
+  std::vector<uint32_t> apos((size_t)K);
+  std::vector<int64_t> nv(kc);
+  std::vector<double> an(kc), m1(kc), m2(kc);
+  std::vector<float> mn(kc), mx(kc);
+  VGS_HIP_TRY(c, hipMemcpyAsync(apos.data(), c->sd_apos.p, apos.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(nv.data(), c->sf_nvalid.p, kc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(an.data(), c->sf_anchor.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(m1.data(), c->sf_mean.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(m2.data(), c->sf_var.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(mn.data(), c->sf_min.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(mx.data(), c->sf_max.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::vector<int64_t> rows;
+  sft_own_labels(apos, rows);
+  for (size_t i = 0; i < rows.size(); ++i) {
+    const size_t src = (size_t)rows[i] * C, dst = i * C;
+    if (label) label[i] = (int32_t)rows[i];
+    if (n_valid) std::copy(nv.begin() + src, nv.begin() + src + C, n_valid + dst);
+    if (anchor) std::copy(an.begin() + src, an.begin() + src + C, anchor + dst);
+    if (s1) std::copy(m1.begin() + src, m1.begin() + src + C, s1 + dst);
+    if (s2) std::copy(m2.begin() + src, m2.begin() + src + C, s2 + dst);
+    if (vmin) std::copy(mn.begin() + src, mn.begin() + src + C, vmin + dst);
+    if (vmax) std::copy(mx.begin() + src, mx.begin() + src + C, vmax + dst);
+  }
+  *n_records = (int64_t)rows.size();
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_get_own_segment_field_moments_device(vgs_ctx* c, int64_t K, const float* field_dev, int64_t n_own, int32_t n_channels,
+                                                               int64_t stride_bytes, int64_t* n_records, int32_t* label, int64_t* n_valid,
+                                                               double* anchor, double* s1, double* s2, float* vmin, float* vmax) {
+  if (!c || !n_records) return VGS_E_ARG;
+  vgs_status s = sft_check_field(c, "vgs_get_own_segment_field_moments_device", K, field_dev, n_own, n_channels, stride_bytes);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  return sft_field_moments(c, K, field_dev, n_channels, stride_bytes, n_records, label, n_valid, anchor, s1, s2, vmin, vmax);
+}
+
+extern "C" vgs_status vgs_get_own_segment_field_moments(vgs_ctx* c, int64_t K, const float* field_host, int64_t n_own, int32_t n_channels,
+                                                        int64_t stride_bytes, int64_t* n_records, int32_t* label, int64_t* n_valid, double* anchor,
+                                                        double* s1, double* s2, float* vmin, float* vmax) {
+  if (!c || !n_records) return VGS_E_ARG;
+  vgs_status s = sft_check_field(c, "vgs_get_own_segment_field_moments", K, field_host, n_own, n_channels, stride_bytes);
+  if (s != VGS_OK) return s;
+  *n_records = 0;
+  if (K == 0 || n_own == 0) return VGS_OK;   // (no own point: no record)
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  // one upload, rows at the caller's stride; the last row ends with its last channel
+  const size_t bytes = (size_t)(n_own - 1) * (size_t)stride_bytes + 4 * (size_t)n_channels;
+  VGS_HIP_TRY(c, c->sf_in.ensure((bytes + 3) / 4));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_in.p, field_host, bytes, hipMemcpyHostToDevice, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
+  return sft_field_moments(c, K, c->sf_in.p, n_channels, stride_bytes, n_records, label, n_valid, anchor, s1, s2, vmin, vmax);
+}
+
+// The table from moments folded over the ranks: one partial record per (segment, channel) and seg_chunk[k] = k, so k_sf_final itself runs
+// unchanged -- its fold over one record adds zeros, its tail is the arithmetic of vgs_segment_field_stats.  Records of all channel groups
+// in one upload, group after group.
+extern "C" vgs_status vgs_segment_field_stats_from_moments(vgs_ctx* c, int64_t K, int32_t n_channels, const int64_t* n_valid, const double* anchor,
+                                                           const double* s1, const double* s2, const float* vmin, const float* vmax, double* mean,
+                                                           double* var, float* vmin_out, float* vmax_out) {
+  if (!c || K < 0 || K >= (int64_t)0xffffffffLL) return VGS_E_ARG;
+  if (n_channels < 1 || n_channels > 64) {
+    c->err = "vgs_segment_field_stats_from_moments: n_channels = " + std::to_string(n_channels) + " must be in 1 .. 64";
+    return VGS_E_ARG;
+  }
+  if (K > 0 && (!n_valid || !anchor || !s1 || !s2 || !vmin || !vmax)) { c->err = "vgs_segment_field_stats_from_moments: an input array is NULL"; return VGS_E_ARG; }
+  if (K == 0) return VGS_OK;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t C = (uint32_t)n_channels, n_groups = (C + SF_G - 1) / SF_G;
+  const size_t k = (size_t)K, kc = k * C, per_group = k * SF_G * SF_REC;
+  std::vector<double> part((size_t)n_groups * per_group, 0.0);
+  for (size_t i = 0; i < k; ++i)
+    for (uint32_t ch = 0; ch < C; ++ch) {
+      double* r = part.data() + (size_t)(ch / SF_G) * per_group + (i * SF_G + ch % SF_G) * SF_REC;
+      const size_t o = i * C + ch;
+      r[0] = s1[o]; r[1] = s2[o]; r[2] = (double)n_valid[o]; r[3] = (double)vmin[o]; r[4] = (double)vmax[o];
+    }
+  std::vector<uint32_t> idx(k + 1);
+  for (size_t i = 0; i <= k; ++i) idx[i] = (uint32_t)i;
+  VGS_HIP_TRY(c, c->sf_part.ensure(part.size())); VGS_HIP_TRY(c, c->sf_idx.ensure(idx.size()));
+  VGS_HIP_TRY(c, c->sf_anchor.ensure(kc)); VGS_HIP_TRY(c, c->sf_mean.ensure(kc)); VGS_HIP_TRY(c, c->sf_var.ensure(kc));
+  VGS_HIP_TRY(c, c->sf_nvalid.ensure(kc)); VGS_HIP_TRY(c, c->sf_min.ensure(kc)); VGS_HIP_TRY(c, c->sf_max.ensure(kc));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_part.p, part.data(), part.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_anchor.p, anchor, kc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  for (uint32_t c0 = 0; c0 < C; c0 += SF_G) {
+    const uint32_t ng = C - c0 < SF_G ? C - c0 : SF_G;
+    hipLaunchKernelGGL(k_sf_final, dim3((unsigned)((k * ng + 3) / 4)), dim3(256), 0, c->stream, c->sf_idx.p, c->sf_part.p + (size_t)(c0 / SF_G) * per_group,
+                       (uint32_t)K, (uint32_t)K, C, c0, ng, c->sf_anchor.p, c->sf_nvalid.p, c->sf_mean.p, c->sf_var.p, c->sf_min.p, c->sf_max.p);
+  }
+  VGS_HIP_TRY(c, hipGetLastError());
+  if (mean) VGS_HIP_TRY(c, hipMemcpyAsync(mean, c->sf_mean.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (var) VGS_HIP_TRY(c, hipMemcpyAsync(var, c->sf_var.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (vmin_out) VGS_HIP_TRY(c, hipMemcpyAsync(vmin_out, c->sf_min.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (vmax_out) VGS_HIP_TRY(c, hipMemcpyAsync(vmax_out, c->sf_max.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the staged records and the caller's anchor are free again as well)
+  return VGS_OK;
+}
+
+static vgs_status sft_check_counts(vgs_ctx* c, const char* fn, int64_t K, const int32_t* cls, int64_t n_own, int32_t n_classes) {
+  vgs_status s = sft_check_state(c, fn);
+  if (s != VGS_OK) return s;
+  if (K < 0 || K >= (int64_t)0xffffffffLL) { c->err = std::string(fn) + ": K = " + std::to_string(K) + " is out of range"; return VGS_E_ARG; }
+  if ((s = sft_check_n(c, fn, cls, n_own)) != VGS_OK) return s;
+  if (n_classes < 1 || n_classes > 1024) {
+    c->err = std::string(fn) + ": n_classes = " + std::to_string(n_classes) + " must be in 1 .. 1024";
+    return VGS_E_ARG;
+  }
+  if (K * (int64_t)n_classes > ((int64_t)1 << 27)) {
+    c->err = std::string(fn) + ": " + std::to_string(K) + " segments x " + std::to_string(n_classes) + " classes = " +
+             std::to_string(K * (int64_t)n_classes) + " counters exceed the table's limit of 2^27 = " + std::to_string((int64_t)1 << 27);
+    return VGS_E_UNSUPPORTED;
+  }
+  return VGS_OK;
+}
+
+// this rank's class counts of the global labels 0 .. K-1 over its own points, from a device buffer: dense on the device, compact on the host
+static vgs_status sft_class_counts(vgs_ctx* c, int64_t K, const int32_t* cls_dev, int32_t n_classes, int64_t* n_records, int32_t* label,
+                                   int64_t* hist, int64_t* n_outside) {
+  *n_records = 0;
+  if (K == 0 || c->V == 0 || c->Nf == 0) return VGS_OK;
+  const size_t k = (size_t)K, nc = (size_t)n_classes, kc = k * nc;
+  SdPrep P;
+  vgs_status s = sd_prepare(c, K, P);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, c->sf_hist.ensure(kc + 2 * k));
+  int64_t *d_hist = c->sf_hist.p, *d_out = d_hist + kc;
+  VGS_HIP_TRY(c, hipMemsetAsync(d_hist, 0, (kc + k) * sizeof(int64_t), c->stream));
+  if ((s = sd_own_anchor(c, K, P)) != VGS_OK) return s;
+  hipLaunchKernelGGL(k_sf_hist_own, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, cls_dev, (uint32_t)n_classes, c->perm_b.p,
+                     c->vox_start.p, P.ids, P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, (unsigned long long*)d_hist, (unsigned long long*)d_out,
+                     c->own_first, c->own_first + c->n_own);
+  VGS_HIP_TRY(c, hipGetLastError());
+  std::vector<uint32_t> apos(k);
+  std::vector<int64_t> h(kc + k);
+  VGS_HIP_TRY(c, hipMemcpyAsync(apos.data(), c->sd_apos.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipMemcpyAsync(h.data(), d_hist, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::vector<int64_t> rows;
+  sft_own_labels(apos, rows);
+  for (size_t i = 0; i < rows.size(); ++i) {
+    const size_t r = (size_t)rows[i];
+    if (label) label[i] = (int32_t)r;
+    if (hist) std::copy(h.begin() + r * nc, h.begin() + (r + 1) * nc, hist + i * nc);
+    if (n_outside) n_outside[i] = h[kc + r];
+  }
+  *n_records = (int64_t)rows.size();
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_get_own_segment_class_counts_device(vgs_ctx* c, int64_t K, const int32_t* cls_dev, int64_t n_own, int32_t n_classes,
+                                                              int64_t* n_records, int32_t* label, int64_t* hist, int64_t* n_outside) {
+  if (!c || !n_records) return VGS_E_ARG;
+  vgs_status s = sft_check_counts(c, "vgs_get_own_segment_class_counts_device", K, cls_dev, n_own, n_classes);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  return sft_class_counts(c, K, cls_dev, n_classes, n_records, label, hist, n_outside);
+}
+
+extern "C" vgs_status vgs_get_own_segment_class_counts(vgs_ctx* c, int64_t K, const int32_t* cls_host, int64_t n_own, int32_t n_classes,
+                                                       int64_t* n_records, int32_t* label, int64_t* hist, int64_t* n_outside) {
+  if (!c || !n_records) return VGS_E_ARG;
+  vgs_status s = sft_check_counts(c, "vgs_get_own_segment_class_counts", K, cls_host, n_own, n_classes);
+  if (s != VGS_OK) return s;
+  *n_records = 0;
+  if (K == 0 || n_own == 0) return VGS_OK;   // (no own point: no record)
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  VGS_HIP_TRY(c, c->sf_cls.ensure((size_t)n_own));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_cls.p, cls_host, (size_t)n_own * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
+  return sft_class_counts(c, K, c->sf_cls.p, n_classes, n_records, label, hist, n_outside);
 }

@@ -328,6 +328,75 @@ bool fold_extents(const std::vector<std::vector<ExtentRec>>& ranks, int64_t K, s
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------ attribute moments
+// One rank's attribute moments (vgs_get_own_segment_field_moments): per record a label and n_channels x (n_valid, anchor, S1, S2, min, max).
+// On the wire (words of 8 bytes): a header of status word, record count and n_channels, then per record the label and per channel n_valid,
+// anchor, S1, S2 and one word holding min | max (two floats): 1 + 5 n_channels words.
+struct FieldRecs {
+  std::vector<int32_t> label;
+  std::vector<int64_t> n;
+  std::vector<double> a, s1, s2;
+  std::vector<float> mn, mx;
+};
+
+// The moments of every (label, channel) from the ranks' records, the same bytes on every rank: per entry, ranks in ascending order.  The
+// anchor a is the anchor of the lowest rank with n_valid > 0, whose sums are taken as they are; a later rank's sums move to it by delta =
+// a_r - a in fp64: S1 += S1_r + n_r delta, S2 += S2_r + S1_r delta + delta S1_r + n_r delta delta (the association of fold_moments'
+// diagonal terms).  n_valid adds, min and max take min and max.  An entry no valid value reaches: n = 0, anchor 0, sums 0, +inf / -inf.
+// Returns false if a record names a label outside 0 .. K-1.
+bool fold_field_moments(const std::vector<FieldRecs>& ranks, int64_t K, int C, std::vector<int64_t>& n, std::vector<double>& a,
+                        std::vector<double>& s1, std::vector<double>& s2, std::vector<float>& mn, std::vector<float>& mx) {
+  const size_t kc = (size_t)K * (size_t)C;
+  n.assign(kc, 0); a.assign(kc, 0.0); s1.assign(kc, 0.0); s2.assign(kc, 0.0);
+  mn.assign(kc, __builtin_huge_valf()); mx.assign(kc, -__builtin_huge_valf());
+  for (const FieldRecs& R : ranks)
+    for (size_t i = 0; i < R.label.size(); ++i) {
+      if (R.label[i] < 0 || (int64_t)R.label[i] >= K) return false;
+      for (int ch = 0; ch < C; ++ch) {
+        const size_t o = (size_t)R.label[i] * (size_t)C + (size_t)ch, j = i * (size_t)C + (size_t)ch;
+        if (R.mn[j] < mn[o]) mn[o] = R.mn[j];
+        if (R.mx[j] > mx[o]) mx[o] = R.mx[j];
+        if (R.n[j] <= 0) continue;
+        if (n[o] == 0) {   // the first rank with a valid value: its anchor, its sums as they are
+          a[o] = R.a[j]; s1[o] = R.s1[j]; s2[o] = R.s2[j]; n[o] = R.n[j];
+          continue;
+        }
+        const double nr = (double)R.n[j], d = R.a[j] - a[o];
+        s1[o] += R.s1[j] + nr * d;
+        s2[o] += R.s2[j] + R.s1[j] * d + d * R.s1[j] + nr * d * d;
+        n[o] += R.n[j];
+      }
+    }
+  return true;
+}
+
+// One rank's class counts (vgs_get_own_segment_class_counts): per record a label, n_outside and n_classes counts.  On the wire (int64
+// words): a header of status word, record count and n_classes, then per record label, n_outside, hist[n_classes].
+struct ClassRecs {
+  std::vector<int32_t> label;
+  std::vector<int64_t> hist, n_outside;
+};
+
+// Integer adds per (label, class), then the majority rule of vgs_segment_class_histogram on the folded table: the lowest class with the
+// largest count, -1 and 0 when every count is 0.  Returns false if a record names a label outside 0 .. K-1.
+bool fold_class_counts(const std::vector<ClassRecs>& ranks, int64_t K, int nc, std::vector<int64_t>& hist, std::vector<int64_t>& n_outside,
+                       std::vector<int32_t>& majority, std::vector<int64_t>& majority_count) {
+  hist.assign((size_t)K * (size_t)nc, 0); n_outside.assign((size_t)K, 0); majority.assign((size_t)K, -1); majority_count.assign((size_t)K, 0);
+  for (const ClassRecs& R : ranks)
+    for (size_t i = 0; i < R.label.size(); ++i) {
+      if (R.label[i] < 0 || (int64_t)R.label[i] >= K) return false;
+      const size_t k = (size_t)R.label[i];
+      n_outside[k] += R.n_outside[i];
+      for (int j = 0; j < nc; ++j) hist[k * (size_t)nc + (size_t)j] += R.hist[i * (size_t)nc + (size_t)j];
+    }
+  for (size_t k = 0; k < (size_t)K; ++k)
+    for (int j = 0; j < nc; ++j) {
+      const int64_t v = hist[k * (size_t)nc + (size_t)j];
+      if (v > majority_count[k]) { majority_count[k] = v; majority[k] = j; }   // a strictly larger count only: the lowest class on a tie
+    }
+  return true;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ driver
@@ -344,7 +413,8 @@ struct vgs_tiles {
   double times[VGS_TILES_T_COUNT] = {0};   // last run, milliseconds of host wall time per phase (vgs_tiles_get_times)
   int strict_region = 0;      // VGS_TILES_OPT_STRICT_REGION
   int fail_phase = 0;         // tests (VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT): 1 grid, 2 stages, 3 points, 4 upload (behind the last collective of set_points),
-                              // 5 descriptors (before the descriptor exchange), 6 graph (before the graph exchange), 7 boxes (before the box exchange)
+                              // 5 descriptors (before the descriptor exchange), 6 graph (before the graph exchange), 7 boxes (before the box exchange),
+                              // 8 fields (before the exchange of vgs_tiles_segment_field_stats / vgs_tiles_segment_class_histogram)
   vgs_status pending = VGS_OK;   // a local failure behind a call's last collective: the status word of the next collective carries it
   bool warned_outside = false;
   bool ran = false;              // the last vgs_tiles_run completed here
@@ -368,6 +438,9 @@ struct vgs_tiles {
   bool box_valid[2] = {false, false};
   std::vector<double> b_center[2], b_half[2], b_frame[2], b_lo[2], b_hi[2];
   double btimes[VGS_TILES_B_COUNT] = {0};   // the last box collective, milliseconds of host wall time per phase
+  // the last attribute collective (field statistics or class histogram; nothing of it is cached): phases, own records, bytes sent
+  double ftimes[VGS_TILES_F_COUNT] = {0};
+  int64_t f_own = 0, f_bytes = 0;
   std::string err;
 };
 
@@ -417,7 +490,7 @@ vgs_status vgs_tiles_create(const vgs_params* p, int comm_kind, void* comm_handl
     // failure injection for the tests of the agreed-status protocol; read once, here
     const char* fr = std::getenv("VGS_TILES_FAIL_RANK");
     const char* fa = std::getenv("VGS_TILES_FAIL_AT");
-    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : !std::strcmp(fa, "descriptors") ? 5 : !std::strcmp(fa, "graph") ? 6 : !std::strcmp(fa, "boxes") ? 7 : 0;
+    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : !std::strcmp(fa, "descriptors") ? 5 : !std::strcmp(fa, "graph") ? 6 : !std::strcmp(fa, "boxes") ? 7 : !std::strcmp(fa, "fields") ? 8 : 0;
   }
   vgs_status s = vgs_create(p, &t->ctx);
   if (s != VGS_OK) { delete t->comm; delete t; return s; }
@@ -863,6 +936,275 @@ vgs_status vgs_tiles_fold_extents(int world, const int64_t* rec_off, const int32
   std::vector<uint8_t> reached;
   if (!fold_extents(ranks, K, lo, hi, reached)) return VGS_E_ARG;
   std::copy(lo.begin(), lo.end(), lo3_out); std::copy(hi.begin(), hi.end(), hi3_out); std::copy(reached.begin(), reached.end(), reached_out);
+  return VGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ attribute statistics
+// Field statistics over the ranks: no attribute travels, every point is counted by the rank that loaded it.  This rank's moments of its
+// own rows (one small pipeline on its GPU) -> ONE all_gather_varlen of the records behind a header of status word, record count and
+// n_channels -> the same host fold on every rank -> mean, var, min and max on this rank's GPU.  Nothing is cached (the input is the
+// caller's), so every call is collective.  Everything a rank can get wrong on its own -- n, a NULL input, the channel and stride values, a
+// failing context call -- is found by the context call and travels in the status word.
+static vgs_status tiles_field_stats(vgs_tiles* t, const char* fn, bool on_device, const float* field, int64_t n, int32_t n_channels,
+                                    int64_t stride_bytes, int64_t* K, int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin,
+                                    float* vmax) {
+  if (!t) return VGS_E_ARG;
+  if (K) *K = t->kept;
+  if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, std::string(fn) + ": vgs_tiles_run first");
+  Comm& c = *t->comm;
+  const int64_t Kg = t->kept;
+  const size_t k1 = (size_t)Kg;
+  vgs_status carry = t->pending;
+  if (t->fail_phase == 8 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=fields"; }
+  const double t0 = now_ms();
+  const bool c_ok = n_channels >= 1 && n_channels <= 64;
+  const size_t C = c_ok ? (size_t)n_channels : 0;
+  std::vector<uint64_t> payload(3, 0);
+  int64_t n_rec = 0;
+  if (carry == VGS_OK) {
+    const size_t cap = k1 * C + 1;
+    std::vector<int32_t> lab(k1 + 1);
+    std::vector<int64_t> nv(cap);
+    std::vector<double> an(cap), m1(cap), m2(cap);
+    std::vector<float> mn(cap), mx(cap);
+    // (a channel count out of range is refused by the context before it writes: no array is needed)
+    if (on_device) TCARRY(vgs_get_own_segment_field_moments_device(t->ctx, Kg, field, n, n_channels, stride_bytes, &n_rec, c_ok ? lab.data() : nullptr, c_ok ? nv.data() : nullptr, c_ok ? an.data() : nullptr, c_ok ? m1.data() : nullptr, c_ok ? m2.data() : nullptr, c_ok ? mn.data() : nullptr, c_ok ? mx.data() : nullptr));
+    else TCARRY(vgs_get_own_segment_field_moments(t->ctx, Kg, field, n, n_channels, stride_bytes, &n_rec, c_ok ? lab.data() : nullptr, c_ok ? nv.data() : nullptr, c_ok ? an.data() : nullptr, c_ok ? m1.data() : nullptr, c_ok ? m2.data() : nullptr, c_ok ? mn.data() : nullptr, c_ok ? mx.data() : nullptr));
+    if (carry == VGS_OK) {
+      payload.reserve(3 + (size_t)n_rec * (1 + 5 * C));
+      auto bits = [](double v) { uint64_t u; std::memcpy(&u, &v, 8); return u; };
+      for (size_t i = 0; i < (size_t)n_rec; ++i) {
+        payload.push_back((uint64_t)(uint32_t)lab[i]);
+        for (size_t ch = 0; ch < C; ++ch) {
+          const size_t j = i * C + ch;
+          uint32_t lo, hi;
+          std::memcpy(&lo, &mn[j], 4); std::memcpy(&hi, &mx[j], 4);
+          payload.push_back((uint64_t)nv[j]); payload.push_back(bits(an[j])); payload.push_back(bits(m1[j])); payload.push_back(bits(m2[j]));
+          payload.push_back((uint64_t)lo | ((uint64_t)hi << 32));
+        }
+      }
+    } else n_rec = 0;
+  }
+  payload[0] = (uint64_t)(uint32_t)carry;
+  payload[1] = (uint64_t)n_rec;
+  payload[2] = (uint64_t)(uint32_t)n_channels;
+  const double t1 = now_ms();
+  std::vector<std::vector<uint64_t>> gathered;
+  TCOMM(all_gather_varlen(c, payload, gathered));
+  const double t2 = now_ms();
+  {
+    int bad = -1;
+    for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].size() < 3 || gathered[(size_t)r][0] != 0) bad = r;
+    vgs_status a = agreed(t, carry, bad, "fields");
+    if (a != VGS_OK) return a;
+  }
+  for (int r = 1; r < c.world; ++r)   // every rank valid on its own, but not the same table
+    if (gathered[(size_t)r][2] != gathered[0][2])
+      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed n_channels = " + std::to_string((int32_t)gathered[(size_t)r][2]) +
+                                     ", rank 0 passed " + std::to_string((int32_t)gathered[0][2]));
+  std::vector<FieldRecs> recs((size_t)c.world);
+  for (int r = 0; r < c.world; ++r) {
+    const std::vector<uint64_t>& g = gathered[(size_t)r];
+    const size_t nr = (size_t)g[1];
+    if (g.size() != 3 + nr * (1 + 5 * C)) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
+    FieldRecs& R = recs[(size_t)r];
+    R.label.resize(nr); R.n.resize(nr * C); R.a.resize(nr * C); R.s1.resize(nr * C); R.s2.resize(nr * C); R.mn.resize(nr * C); R.mx.resize(nr * C);
+    const uint64_t* w = g.data() + 3;
+    auto dbl = [](uint64_t u) { double v; std::memcpy(&v, &u, 8); return v; };
+    for (size_t i = 0; i < nr; ++i) {
+      R.label[i] = (int32_t)(uint32_t)*w++;
+      for (size_t ch = 0; ch < C; ++ch) {
+        const size_t j = i * C + ch;
+        R.n[j] = (int64_t)w[0]; R.a[j] = dbl(w[1]); R.s1[j] = dbl(w[2]); R.s2[j] = dbl(w[3]);
+        const uint32_t lo = (uint32_t)w[4], hi = (uint32_t)(w[4] >> 32);
+        std::memcpy(&R.mn[j], &lo, 4); std::memcpy(&R.mx[j], &hi, 4);
+        w += 5;
+      }
+    }
+  }
+  std::vector<int64_t> fn_;
+  std::vector<double> fa, f1, f2;
+  std::vector<float> fmn, fmx;
+  if (!fold_field_moments(recs, Kg, (int)C, fn_, fa, f1, f2, fmn, fmx)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= kept_global");
+  const double t3 = now_ms();
+  const size_t kc = k1 * C;
+  std::vector<double> me(kc + 1), va(kc + 1);
+  std::vector<float> omn(kc + 1), omx(kc + 1);
+  // (local, behind the collective: the rank returns its error and keeps it for the next collective, as the label write-back does)
+  const vgs_status sa = vgs_segment_field_stats_from_moments(t->ctx, Kg, n_channels, fn_.data(), fa.data(), f1.data(), f2.data(), fmn.data(), fmx.data(),
+                                                             me.data(), va.data(), omn.data(), omx.data());
+  if (sa != VGS_OK) { t->pending = sa; return tfail(t, sa, std::string("vgs_segment_field_stats_from_moments: ") + vgs_last_error_string(t->ctx)); }
+  const double t4 = now_ms();
+  if (n_valid) std::copy(fn_.begin(), fn_.end(), n_valid);
+  if (anchor) std::copy(fa.begin(), fa.end(), anchor);
+  if (mean) std::copy(me.begin(), me.begin() + (ptrdiff_t)kc, mean);
+  if (var) std::copy(va.begin(), va.begin() + (ptrdiff_t)kc, var);
+  if (vmin) std::copy(omn.begin(), omn.begin() + (ptrdiff_t)kc, vmin);
+  if (vmax) std::copy(omx.begin(), omx.begin() + (ptrdiff_t)kc, vmax);
+  t->ftimes[VGS_TILES_F_OWN] = t1 - t0; t->ftimes[VGS_TILES_F_EXCHANGE] = t2 - t1; t->ftimes[VGS_TILES_F_FOLD] = t3 - t2;
+  t->ftimes[VGS_TILES_F_FINISH] = t4 - t3; t->ftimes[VGS_TILES_F_TOTAL] = t4 - t0;
+  t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(uint64_t));
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_segment_field_stats(vgs_tiles* t, const float* field_host, int64_t n, int32_t n_channels, int64_t stride_bytes, int64_t* K,
+                                         int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax) {
+  return tiles_field_stats(t, "vgs_tiles_segment_field_stats", false, field_host, n, n_channels, stride_bytes, K, n_valid, anchor, mean, var, vmin, vmax);
+}
+
+vgs_status vgs_tiles_segment_field_stats_device(vgs_tiles* t, const float* field_dev, int64_t n, int32_t n_channels, int64_t stride_bytes, int64_t* K,
+                                                int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax) {
+  return tiles_field_stats(t, "vgs_tiles_segment_field_stats_device", true, field_dev, n, n_channels, stride_bytes, K, n_valid, anchor, mean, var, vmin,
+                           vmax);
+}
+
+// The class histogram over the ranks: this rank's rows of its own points -> ONE all_gather_varlen behind a header of status word, record
+// count and n_classes -> integer adds and the majority rule on the host, the same on every rank.
+static vgs_status tiles_class_hist(vgs_tiles* t, const char* fn, bool on_device, const int32_t* cls, int64_t n, int32_t n_classes, int64_t* K,
+                                   int64_t* hist, int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
+  if (!t) return VGS_E_ARG;
+  if (K) *K = t->kept;
+  if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, std::string(fn) + ": vgs_tiles_run first");
+  Comm& c = *t->comm;
+  const int64_t Kg = t->kept;
+  const size_t k1 = (size_t)Kg;
+  vgs_status carry = t->pending;
+  if (t->fail_phase == 8 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=fields"; }
+  const double t0 = now_ms();
+  const bool c_ok = n_classes >= 1 && n_classes <= 1024 && Kg * (int64_t)n_classes <= ((int64_t)1 << 27);
+  const size_t nc = c_ok ? (size_t)n_classes : 0;
+  std::vector<int64_t> payload(3, 0);
+  int64_t n_rec = 0;
+  if (carry == VGS_OK) {
+    std::vector<int32_t> lab(k1 + 1);
+    std::vector<int64_t> hi(k1 * nc + 1), no(k1 + 1);
+    // (a class count out of range is refused by the context before it writes: no array is needed)
+    if (on_device) TCARRY(vgs_get_own_segment_class_counts_device(t->ctx, Kg, cls, n, n_classes, &n_rec, c_ok ? lab.data() : nullptr, c_ok ? hi.data() : nullptr, c_ok ? no.data() : nullptr));
+    else TCARRY(vgs_get_own_segment_class_counts(t->ctx, Kg, cls, n, n_classes, &n_rec, c_ok ? lab.data() : nullptr, c_ok ? hi.data() : nullptr, c_ok ? no.data() : nullptr));
+    if (carry == VGS_OK) {
+      payload.reserve(3 + (size_t)n_rec * (2 + nc));
+      for (size_t i = 0; i < (size_t)n_rec; ++i) {
+        payload.push_back((int64_t)lab[i]); payload.push_back(no[i]);
+        payload.insert(payload.end(), hi.begin() + (ptrdiff_t)(i * nc), hi.begin() + (ptrdiff_t)((i + 1) * nc));
+      }
+    } else n_rec = 0;
+  }
+  payload[0] = (int64_t)carry;
+  payload[1] = n_rec;
+  payload[2] = (int64_t)n_classes;
+  const double t1 = now_ms();
+  std::vector<std::vector<int64_t>> gathered;
+  TCOMM(all_gather_varlen(c, payload, gathered));
+  const double t2 = now_ms();
+  {
+    int bad = -1;
+    for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].size() < 3 || gathered[(size_t)r][0] != 0) bad = r;
+    vgs_status a = agreed(t, carry, bad, "fields");
+    if (a != VGS_OK) return a;
+  }
+  for (int r = 1; r < c.world; ++r)   // every rank valid on its own, but not the same table
+    if (gathered[(size_t)r][2] != gathered[0][2])
+      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed n_classes = " + std::to_string(gathered[(size_t)r][2]) +
+                                     ", rank 0 passed " + std::to_string(gathered[0][2]));
+  std::vector<ClassRecs> recs((size_t)c.world);
+  for (int r = 0; r < c.world; ++r) {
+    const std::vector<int64_t>& g = gathered[(size_t)r];
+    const size_t nr = (size_t)g[1];
+    if (g.size() != 3 + nr * (2 + nc)) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
+    ClassRecs& R = recs[(size_t)r];
+    R.label.resize(nr); R.n_outside.resize(nr); R.hist.resize(nr * nc);
+    const int64_t* w = g.data() + 3;
+    for (size_t i = 0; i < nr; ++i) {
+      R.label[i] = (int32_t)w[0]; R.n_outside[i] = w[1];
+      std::copy(w + 2, w + 2 + nc, R.hist.begin() + (ptrdiff_t)(i * nc));
+      w += 2 + nc;
+    }
+  }
+  std::vector<int64_t> fh, fo, fc;
+  std::vector<int32_t> fm;
+  if (!fold_class_counts(recs, Kg, (int)nc, fh, fo, fm, fc)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= kept_global");
+  const double t3 = now_ms();
+  if (hist) std::copy(fh.begin(), fh.end(), hist);
+  if (n_outside) std::copy(fo.begin(), fo.end(), n_outside);
+  if (majority) std::copy(fm.begin(), fm.end(), majority);
+  if (majority_count) std::copy(fc.begin(), fc.end(), majority_count);
+  t->ftimes[VGS_TILES_F_OWN] = t1 - t0; t->ftimes[VGS_TILES_F_EXCHANGE] = t2 - t1; t->ftimes[VGS_TILES_F_FOLD] = t3 - t2;
+  t->ftimes[VGS_TILES_F_FINISH] = 0.0; t->ftimes[VGS_TILES_F_TOTAL] = t3 - t0;   // (the majority rule is integer work inside the fold)
+  t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(int64_t));
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_segment_class_histogram(vgs_tiles* t, const int32_t* cls_host, int64_t n, int32_t n_classes, int64_t* K, int64_t* hist,
+                                             int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
+  return tiles_class_hist(t, "vgs_tiles_segment_class_histogram", false, cls_host, n, n_classes, K, hist, n_outside, majority, majority_count);
+}
+
+vgs_status vgs_tiles_segment_class_histogram_device(vgs_tiles* t, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* K, int64_t* hist,
+                                                    int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
+  return tiles_class_hist(t, "vgs_tiles_segment_class_histogram_device", true, cls_dev, n, n_classes, K, hist, n_outside, majority, majority_count);
+}
+
+vgs_status vgs_tiles_get_field_times(vgs_tiles* t, double* ms, int32_t n) {
+  if (!t || !ms || n < 0 || n > VGS_TILES_F_COUNT) return VGS_E_ARG;
+  for (int i = 0; i < n; ++i) ms[i] = t->ftimes[i];
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_field_payload(vgs_tiles* t, int64_t* own_records, int64_t* bytes_sent) {
+  if (!t) return VGS_E_ARG;
+  if (own_records) *own_records = t->f_own;
+  if (bytes_sent) *bytes_sent = t->f_bytes;
+  return VGS_OK;
+}
+
+// host arithmetic only (tests): the attribute folds on flattened per-rank records
+vgs_status vgs_tiles_fold_field_moments(int world, const int64_t* rec_off, const int32_t* label, int32_t n_channels, const int64_t* n_valid,
+                                        const double* anchor, const double* s1, const double* s2, const float* vmin, const float* vmax, int64_t K,
+                                        int64_t* n_valid_out, double* anchor_out, double* s1_out, double* s2_out, float* vmin_out, float* vmax_out) {
+  if (world < 1 || !rec_off || K < 0 || n_channels < 1 || n_channels > 64) return VGS_E_ARG;
+  if (K > 0 && (!n_valid_out || !anchor_out || !s1_out || !s2_out || !vmin_out || !vmax_out)) return VGS_E_ARG;
+  if (rec_off[world] > 0 && (!label || !n_valid || !anchor || !s1 || !s2 || !vmin || !vmax)) return VGS_E_ARG;
+  const size_t C = (size_t)n_channels;
+  std::vector<FieldRecs> ranks((size_t)world);
+  for (int r = 0; r < world; ++r) {
+    if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
+    const size_t i0 = (size_t)rec_off[r], i1 = (size_t)rec_off[r + 1];
+    FieldRecs& R = ranks[(size_t)r];
+    R.label.assign(label + i0, label + i1);
+    R.n.assign(n_valid + i0 * C, n_valid + i1 * C); R.a.assign(anchor + i0 * C, anchor + i1 * C);
+    R.s1.assign(s1 + i0 * C, s1 + i1 * C); R.s2.assign(s2 + i0 * C, s2 + i1 * C);
+    R.mn.assign(vmin + i0 * C, vmin + i1 * C); R.mx.assign(vmax + i0 * C, vmax + i1 * C);
+  }
+  std::vector<int64_t> n;
+  std::vector<double> a, m1, m2;
+  std::vector<float> mn, mx;
+  if (!fold_field_moments(ranks, K, n_channels, n, a, m1, m2, mn, mx)) return VGS_E_ARG;
+  std::copy(n.begin(), n.end(), n_valid_out); std::copy(a.begin(), a.end(), anchor_out); std::copy(m1.begin(), m1.end(), s1_out);
+  std::copy(m2.begin(), m2.end(), s2_out); std::copy(mn.begin(), mn.end(), vmin_out); std::copy(mx.begin(), mx.end(), vmax_out);
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_fold_class_counts(int world, const int64_t* rec_off, const int32_t* label, int32_t n_classes, const int64_t* hist,
+                                       const int64_t* n_outside, int64_t K, int64_t* hist_out, int64_t* n_outside_out, int32_t* majority_out,
+                                       int64_t* majority_count_out) {
+  if (world < 1 || !rec_off || K < 0 || n_classes < 1 || n_classes > 1024) return VGS_E_ARG;
+  if (K > 0 && (!hist_out || !n_outside_out || !majority_out || !majority_count_out)) return VGS_E_ARG;
+  if (rec_off[world] > 0 && (!label || !hist || !n_outside)) return VGS_E_ARG;
+  const size_t nc = (size_t)n_classes;
+  std::vector<ClassRecs> ranks((size_t)world);
+  for (int r = 0; r < world; ++r) {
+    if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
+    const size_t i0 = (size_t)rec_off[r], i1 = (size_t)rec_off[r + 1];
+    ClassRecs& R = ranks[(size_t)r];
+    R.label.assign(label + i0, label + i1);
+    R.n_outside.assign(n_outside + i0, n_outside + i1);
+    R.hist.assign(hist + i0 * nc, hist + i1 * nc);
+  }
+  std::vector<int64_t> h, o, mc;
+  std::vector<int32_t> m;
+  if (!fold_class_counts(ranks, K, n_classes, h, o, m, mc)) return VGS_E_ARG;
+  std::copy(h.begin(), h.end(), hist_out); std::copy(o.begin(), o.end(), n_outside_out);
+  std::copy(m.begin(), m.end(), majority_out); std::copy(mc.begin(), mc.end(), majority_count_out);
   return VGS_OK;
 }
 

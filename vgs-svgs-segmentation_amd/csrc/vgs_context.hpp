@@ -277,11 +277,14 @@ struct vgs_ctx {
   DevBuf<uint32_t> sbt_idx;
   // per-segment statistics of a caller's point attributes (segfield.hip): computed on every call, nothing cached.  The host variants' upload
   // (sf_in, sf_cls), the chunk partials of one channel group, and the tables the rows are copied out of: K x n_channels for the field
-  // statistics; K x n_classes counts, then n_outside and majority_count (K each) in sf_hist, majority in sf_maj
+  // statistics; K x n_classes counts, then n_outside and majority_count (K each) in sf_hist, majority in sf_maj.  Tile contexts
+// (vgs_get_own_segment_field_moments, vgs_segment_field_stats_from_moments): a rank's S1 and S2 leave through sf_mean and sf_var; the
+// folded moments come in as one partial per (segment, channel) in sf_part, one chunk per segment (sf_idx)
   DevBuf<float> sf_in, sf_min, sf_max;
   DevBuf<int32_t> sf_cls, sf_maj;
   DevBuf<double> sf_part, sf_anchor, sf_mean, sf_var;
   DevBuf<int64_t> sf_nvalid, sf_hist;
+  DevBuf<uint32_t> sf_idx;
   // tile contexts (vgs_get_own_segment_moments / vgs_segment_descriptors_from_moments): first own point per segment, moment records
   DevBuf<uint32_t> sd_apos;
   DevBuf<double> sd_mom;
@@ -418,6 +421,8 @@ static inline bool vgs_can_split_readback(const vgs_ctx* c) { return c->pin != n
 #define SD_CHUNK (SD_TB * SD_PPT)   // virtual points per chunk
 struct SdPrep { uint32_t *ids, *vp, *seg_node, *seg_chunk; int64_t n_chunks_max; };
 vgs_status sd_prepare(vgs_ctx* c, int64_t K, SdPrep& o);
+// tile contexts: the first own point of every label of that decomposition, in the chunks' order, into sd_apos (segdesc.hip: k_sd_own_anchor)
+vgs_status sd_own_anchor(vgs_ctx* c, int64_t K, const SdPrep& P);
 // a tile context (the tiled driver, include/vgs_tiles.h) holds only part of its segments: the per-segment getters of one context refuse it
 static inline bool vgs_is_tile(const vgs_ctx* c) { return c->have_region || c->n_own >= 0; }
 #ifdef __HIPCC__

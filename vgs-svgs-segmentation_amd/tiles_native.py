@@ -27,6 +27,9 @@ T_NAMES = ("grid", "stages", "records", "exchange", "merge", "labels", "total")
 D_NAMES = ("moments", "exchange", "fold", "algebra", "total")   # vgs_tiles_get_descriptor_times
 G_NAMES = ("halo", "own", "exchange", "fold", "total")          # vgs_tiles_get_graph_times
 B_NAMES = ("extents", "exchange", "fold", "finish", "total")    # vgs_tiles_get_box_times
+F_NAMES = ("own", "exchange", "fold", "finish", "total")        # vgs_tiles_get_field_times
+# per (record / row, channel): (field, dtype) of vgs_get_own_segment_field_moments and vgs_tiles_fold_field_moments, in their argument order
+FIELD_MOMENT_FIELDS = (("n_valid", np.int64), ("anchor", np.float64), ("s1", np.float64), ("s2", np.float64), ("vmin", np.float32), ("vmax", np.float32))
 # per record / row: (field, dtype, values) of vgs_get_own_segment_moments and vgs_tiles_fold_moments, in their argument order
 MOMENT_FIELDS = (("n_points", np.int64, 1), ("n_nodes", np.int32, 1), ("bbox6", np.float32, 6), ("anchor3", np.float32, 3), ("s9", np.float64, 9))
 COMM_RCCL, COMM_LOCAL, COMM_CALLBACKS = 0, 1, 2
@@ -97,6 +100,20 @@ def lib():
         L.vgs_tiles_get_box_times.argtypes = [P, P, C.c_int32]
         L.vgs_tiles_fold_extents.restype = C.c_int
         L.vgs_tiles_fold_extents.argtypes = [C.c_int, P, P, P, P, C.c_int64, P, P, P]
+        for name in ("vgs_tiles_segment_field_stats", "vgs_tiles_segment_field_stats_device"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [P, P, C.c_int64, C.c_int32, C.c_int64, P, P, P, P, P, P, P]
+        for name in ("vgs_tiles_segment_class_histogram", "vgs_tiles_segment_class_histogram_device"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [P, P, C.c_int64, C.c_int32, P, P, P, P, P]
+        L.vgs_tiles_get_field_times.restype = C.c_int
+        L.vgs_tiles_get_field_times.argtypes = [P, P, C.c_int32]
+        L.vgs_tiles_get_field_payload.restype = C.c_int
+        L.vgs_tiles_get_field_payload.argtypes = [P, P, P]
+        L.vgs_tiles_fold_field_moments.restype = C.c_int
+        L.vgs_tiles_fold_field_moments.argtypes = [C.c_int, P, P, C.c_int32, P, P, P, P, P, P, C.c_int64, P, P, P, P, P, P]
+        L.vgs_tiles_fold_class_counts.restype = C.c_int
+        L.vgs_tiles_fold_class_counts.argtypes = [C.c_int, P, P, C.c_int32, P, P, C.c_int64, P, P, P, P]
         _TL = L
     return _TL
 
@@ -164,6 +181,46 @@ def fold_extents(records, K):
     st = lib().vgs_tiles_fold_extents(world, _vp(off), _vp(lab), _vp(lo), _vp(hi), K, _vp(out["lo3"]), _vp(out["hi3"]), _vp(out["reached"]))
     if st != 0:
         raise VgsError(st, "vgs_tiles_fold_extents")
+    return {name: a[:max(K, 0)] for name, a in out.items()}
+
+
+def _rec_off(records):
+    off = np.zeros(len(records) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(r["label"]) for r in records])
+    return off
+
+
+def fold_field_moments(records, K, n_channels):
+    """vgs_tiles_fold_field_moments (host arithmetic, no GPU): records[r] = rank r's dict of label (int32) and FIELD_MOMENT_FIELDS arrays
+    (records x n_channels), as vgs_get_own_segment_field_moments gives them; returns the K folded rows as a dict of FIELD_MOMENT_FIELDS
+    arrays (K, n_channels)."""
+    K, ch = int(K), int(n_channels)
+    off = _rec_off(records)
+    lab = np.ascontiguousarray(np.concatenate([np.asarray(r["label"]) for r in records]).astype(np.int32))
+    flat = {name: np.ascontiguousarray(np.concatenate([np.asarray(r[name], dtype=dt).reshape(-1, max(ch, 1)) for r in records]).reshape(-1))
+            for name, dt in FIELD_MOMENT_FIELDS}
+    out = {name: np.zeros((max(K, 1), max(ch, 1)), dtype=dt) for name, dt in FIELD_MOMENT_FIELDS}
+    st = lib().vgs_tiles_fold_field_moments(len(records), _vp(off), _vp(lab), ch, *(_vp(flat[name]) for name, _ in FIELD_MOMENT_FIELDS), K,
+                                            *(_vp(out[name]) for name, _ in FIELD_MOMENT_FIELDS))
+    if st != 0:
+        raise VgsError(st, "vgs_tiles_fold_field_moments")
+    return {name: a[:max(K, 0)] for name, a in out.items()}
+
+
+def fold_class_counts(records, K, n_classes):
+    """vgs_tiles_fold_class_counts (host arithmetic, no GPU): records[r] = rank r's dict of label (int32), hist (records x n_classes, int64)
+    and n_outside (int64), as vgs_get_own_segment_class_counts gives them; returns the dict of Engine.segment_class_histogram()."""
+    from .api import Engine
+    K, nc = int(K), int(n_classes)
+    off = _rec_off(records)
+    lab = np.ascontiguousarray(np.concatenate([np.asarray(r["label"]) for r in records]).astype(np.int32))
+    hist = np.ascontiguousarray(np.concatenate([np.asarray(r["hist"], dtype=np.int64).reshape(-1, max(nc, 1)) for r in records]).reshape(-1))
+    nout = np.ascontiguousarray(np.concatenate([np.asarray(r["n_outside"], dtype=np.int64).reshape(-1) for r in records]))
+    out = {name: np.zeros((max(K, 1), max(nc, 1)) if w == 0 else max(K, 1), dtype=dt) for name, dt, w in Engine.CLASS_HIST_FIELDS}
+    st = lib().vgs_tiles_fold_class_counts(len(records), _vp(off), _vp(lab), nc, _vp(hist), _vp(nout), K,
+                                           *(_vp(out[name]) for name, _, _ in Engine.CLASS_HIST_FIELDS))
+    if st != 0:
+        raise VgsError(st, "vgs_tiles_fold_class_counts")
     return {name: a[:max(K, 0)] for name, a in out.items()}
 
 
@@ -260,6 +317,7 @@ class NativeTiles:
         self._h = C.c_void_p()
         self._keep = keep          # whatever the communicator handle points into (callback thunks, comm objects)
         self.rank, self.world = rank, world
+        self.params = params
         st = self._L.vgs_tiles_create(C.byref(params), comm_kind, comm_handle, rank, world, int(tiles[0]), int(tiles[1]), float(pitch),
                                       float(center[0]), float(center[1]), C.byref(self._h))
         if st != 0:
@@ -428,6 +486,90 @@ class NativeTiles:
         if st != 0:
             raise VgsError(st, L.vgs_last_error_string(h).decode())
         return {name: a[:n.value] for name, a in out.items()}
+
+    def segment_field_stats(self, field):
+        """COLLECTIVE on every call (every rank makes it after run(), with the same number of channels; nothing is cached): the statistics
+        of a per-point attribute over the global segments, row k = the points point_labels() labels k on any rank -- the dict of
+        Engine.segment_field_stats(), the same bytes on every rank (include/vgs_tiles.h, vgs_tiles_segment_field_stats).  `field`: one row
+        per point of this rank's set_points(), float32 (N,) or (N, C) with the stride rules of Engine.segment_field_stats; a numpy array,
+        or a torch tensor on this rank's device, which is read in place.  No attribute leaves the rank, only per-segment records."""
+        from .api import Engine
+        field, ptr, n, ch, stride, dev = Engine._field_input(field, self.params.device)
+        fn = self._L.vgs_tiles_segment_field_stats_device if dev else self._L.vgs_tiles_segment_field_stats
+        K = C.c_int64(0)
+        k = self._kept()
+        out = {name: np.zeros((max(k, 1), max(ch, 1)), dtype=dt) for name, dt in Engine.FIELD_STAT_FIELDS}
+        self._ck(fn(self._h, ptr, n, ch, stride, C.byref(K), *(_vp(out[name]) for name, _ in Engine.FIELD_STAT_FIELDS)))
+        return {name: a[:k, :max(ch, 0)] for name, a in out.items()}
+
+    def segment_class_histogram(self, classes, n_classes):
+        """COLLECTIVE on every call (every rank makes it after run(), with the same n_classes; nothing is cached): the class histogram of
+        the global segments over all ranks -- the dict of Engine.segment_class_histogram(), the same bytes on every rank
+        (include/vgs_tiles.h, vgs_tiles_segment_class_histogram).  `classes`: one int32 per point of this rank's set_points(), numpy or a
+        torch tensor on this rank's device."""
+        from .api import Engine
+        nc = int(n_classes)
+        classes, ptr, n, dev = Engine._classes_input(classes, self.params.device)
+        fn = self._L.vgs_tiles_segment_class_histogram_device if dev else self._L.vgs_tiles_segment_class_histogram
+        k = self._kept()
+        w1 = max(nc, 1) if nc <= 1024 else 1
+        out = {name: np.zeros((max(k, 1), w1) if w == 0 else max(k, 1), dtype=dt) for name, dt, w in Engine.CLASS_HIST_FIELDS}
+        K = C.c_int64(0)
+        self._ck(fn(self._h, ptr, n, nc, C.byref(K), *(_vp(out[name]) for name, _, _ in Engine.CLASS_HIST_FIELDS)))
+        return {name: (a[:k, :max(nc, 0)] if a.ndim == 2 else a[:k]) for name, a in out.items()}
+
+    def _kept(self):
+        """kept_global of the last run (0 before one); local"""
+        K = C.c_int64(0)
+        self._L.vgs_tiles_get_segment_descriptors(self._h, C.byref(K), *([None] * 8))
+        return int(K.value)
+
+    def field_times(self):
+        """the last attribute collective's phases on this rank, milliseconds (F_NAMES)"""
+        t = np.zeros(len(F_NAMES), dtype=np.float64)
+        self._ck(self._L.vgs_tiles_get_field_times(self._h, _vp(t), len(F_NAMES)))
+        return dict(zip(F_NAMES, (float(x) for x in t)))
+
+    def field_payload(self):
+        """the last attribute collective's payload on this rank: records of its own, bytes sent"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._ck(self._L.vgs_tiles_get_field_payload(self._h, C.byref(a), C.byref(b)))
+        return dict(own_records=a.value, bytes_sent=b.value)
+
+    def own_segment_field_moments(self, K, field):
+        """this rank's attribute moments of the global labels 0 .. K-1 over its own rows (vgs_get_own_segment_field_moments on its context;
+        local, no collective): a dict of label and FIELD_MOMENT_FIELDS arrays (records, C)"""
+        from .api import Engine
+        L = _lib.lib()
+        h = self._ctx()
+        K = int(K)
+        field, ptr, n, ch, stride, dev = Engine._field_input(field, self.params.device)
+        fn = L.vgs_get_own_segment_field_moments_device if dev else L.vgs_get_own_segment_field_moments
+        out = {"label": np.zeros(max(K, 1), dtype=np.int32)}
+        for name, dt in FIELD_MOMENT_FIELDS:
+            out[name] = np.zeros((max(K, 1), max(ch, 1)), dtype=dt)
+        nr = C.c_int64(0)
+        st = fn(h, K, ptr, n, ch, stride, C.byref(nr), _vp(out["label"]), *(_vp(out[name]) for name, _ in FIELD_MOMENT_FIELDS))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        return {name: a[:nr.value] for name, a in out.items()}
+
+    def own_segment_class_counts(self, K, classes, n_classes):
+        """this rank's class counts of the global labels 0 .. K-1 over its own rows (vgs_get_own_segment_class_counts on its context; local,
+        no collective): a dict of label, hist (records, n_classes) and n_outside"""
+        from .api import Engine
+        L = _lib.lib()
+        h = self._ctx()
+        K, nc = int(K), int(n_classes)
+        classes, ptr, n, dev = Engine._classes_input(classes, self.params.device)
+        fn = L.vgs_get_own_segment_class_counts_device if dev else L.vgs_get_own_segment_class_counts
+        out = {"label": np.zeros(max(K, 1), dtype=np.int32), "hist": np.zeros((max(K, 1), max(nc, 1)), dtype=np.int64),
+               "n_outside": np.zeros(max(K, 1), dtype=np.int64)}
+        nr = C.c_int64(0)
+        st = fn(h, K, ptr, n, nc, C.byref(nr), _vp(out["label"]), _vp(out["hist"]), _vp(out["n_outside"]))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        return {name: a[:nr.value] for name, a in out.items()}
 
     def own_segment_moments(self, K):
         """this rank's moment records of the global labels 0 .. K-1 (vgs_get_own_segment_moments on its context; local, no collective):
