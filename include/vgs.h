@@ -134,6 +134,10 @@ vgs_status svgs_segment(vgs_ctx* ctx);      /* attributes + neighbours + local c
 vgs_status svgs_get_supervoxel_labels(vgs_ctx* ctx, int32_t* labels, int32_t* max_label);
 
 /* ---- results ---------------------------------------------------------------------------- */
+/* Every getter below reports the LAST run of the stages on the CURRENT cloud and parameters, whatever the context ran before: a reused
+ * context returns what a fresh context returns for the same cloud and parameters.  That includes the empty frames -- no point, no finite
+ * point (every point's voxel and label -1), no voxel, no used voxel, no kept segment -- after which every count, list, table and schedule
+ * counter is what a fresh context gives: zeros and empty tables, never the previous cloud's numbers. */
 vgs_status vgs_get_counts(vgs_ctx* ctx, int64_t* counts /* VGS_N_COUNTS */);
 vgs_status vgs_get_stage_times(vgs_ctx* ctx, double* ms /* VGS_T_COUNT */);
 /* Schedule diagnostics of the last local cut (no reference counterpart; tests use them to see that an input reached the

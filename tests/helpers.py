@@ -377,3 +377,84 @@ def canonical_labels(lab):
         np.minimum.at(first, lab[valid], idx[valid])
         out[valid] = first[lab[valid]]
     return out
+
+
+# ---------------------------------------------------------------- everything a caller can read after run(), byte for byte
+# Schedule counters (Engine.schedule_counters) that are left out of a snapshot, each with the reason.  A counter belongs here only if two
+# FRESH engines on the same cloud and parameters report different values for it, i.e. if it depends on timing, not on state.
+# Measured on an MI355X: four fresh engines on sequence_frames' frame A (town_scene(20000), default parameters) and two on every other
+# frame agreed on all thirteen counters (and on every other key of the snapshot), so none is left out;
+# test_gpu_sequence.test_fresh_engines_agree_with_the_oracle_and_each_other repeats the comparison of two fresh engines on A in every run.
+SNAPSHOT_TIMING_COUNTERS = {}
+
+SNAPSHOT_LISTS = ("adjacency", "connect_cut", "connect_cross", "connect_final")
+SNAPSHOT_CLASSES = 7
+
+
+def snapshot_inputs(n):
+    """The caller-supplied attributes of a snapshot for a cloud of n points: a seeded 3-channel float field with some NaN and an inf, and
+    seeded classes of which some lie outside 0 .. SNAPSHOT_CLASSES - 1."""
+    rng = np.random.default_rng(1000 + n)
+    field = (rng.standard_normal((n, 3)) * np.array([1.0, 50.0, 1e-3]) + np.array([0.0, 1.0e4, 0.0])).astype(np.float32)
+    field[rng.random(n) < 0.03, 1] = np.nan
+    field[rng.random(n) < 0.01, 2] = np.inf
+    classes = rng.integers(-1, SNAPSHOT_CLASSES + 1, size=n).astype(np.int32)
+    return field, classes
+
+
+def snapshot(eng):
+    """Everything a caller can read from a segmented Engine, as a flat dict of numpy arrays: counts (no times), bbox, voxel table, point ->
+    voxel map, voxel centres, attributes, adjacency counts, the four ragged lists and the cluster lists in both element orders, node and
+    point labels, segment descriptors, oriented boxes in both frames, segment graph, the field statistics and class histogram of
+    snapshot_inputs, and the schedule counters except SNAPSHOT_TIMING_COUNTERS.  Compare two of them with assert_same_snapshot."""
+    out = {}
+
+    def put(prefix, d):
+        for k, v in d.items():
+            out[prefix + "." + k] = np.asarray(v)
+
+    c = eng.counts()
+    out["counts"] = np.array([c[k] for k in sorted(c)], dtype=np.int64)
+    out["counts.names"] = np.array(sorted(c))
+    out["bbox"] = eng.bbox()
+    put("voxel_table", eng.voxel_table())
+    out["point_voxel"] = eng.point_voxel()
+    out["voxel_centers"] = eng.voxel_centers()
+    put("attributes", eng.attributes())
+    out["adjacency_counts"] = eng.adjacency_counts()
+    for which in SNAPSHOT_LISTS:
+        for order in ("voxel_id", "reference"):
+            off, idx = eng.lists(which, order)
+            out[f"lists.{which}.{order}.offsets"], out[f"lists.{which}.{order}.ids"] = off, idx
+    out["node_labels.root"], out["node_labels.kept"] = eng.node_labels()
+    out["point_labels"] = eng.point_labels()
+    for order in ("voxel_id", "reference"):
+        off, idx = eng.clusters(order)
+        out[f"clusters.{order}.offsets"], out[f"clusters.{order}.ids"] = off, idx
+    put("segment_descriptors", eng.segment_descriptors())
+    for frame in ("principal", "upright"):
+        put("segment_boxes." + frame, eng.segment_boxes(frame))
+    put("segment_graph", eng.segment_graph())
+    field, classes = snapshot_inputs(eng.n)
+    put("segment_field_stats", eng.segment_field_stats(field))
+    put("segment_class_histogram", eng.segment_class_histogram(classes, SNAPSHOT_CLASSES))
+    sc = eng.schedule_counters()
+    names = [k for k in sc if k not in SNAPSHOT_TIMING_COUNTERS]
+    out["schedule_counters"] = np.array([sc[k] for k in names], dtype=np.int64)
+    out["schedule_counters.names"] = np.array(names)
+    return out
+
+
+def snapshot_diff(a, b):
+    """Keys whose arrays differ in dtype, shape or raw bytes (NaN payloads and signed zeros included)."""
+    bad = [k for k in sorted(set(a) | set(b)) if k not in a or k not in b]
+    for k in sorted(set(a) & set(b)):
+        x, y = np.ascontiguousarray(a[k]), np.ascontiguousarray(b[k])
+        if x.dtype != y.dtype or x.shape != y.shape or x.tobytes() != y.tobytes():
+            bad.append(k)
+    return bad
+
+
+def assert_same_snapshot(got, want, what=""):
+    bad = snapshot_diff(got, want)
+    assert not bad, f"{what}: {len(bad)} of {len(want)} results differ from the fresh engine's: {bad}"

@@ -566,6 +566,10 @@ vgs_status vgs_get_point_voxel(vgs_ctx* c, int32_t* out) {
   if (!c || !out) return VGS_E_ARG;
   if (c->stage < ST_VOXELS) { c->err = "vgs_get_point_voxel: voxelize first"; return VGS_E_STATE; }
   if (c->N == 0) return VGS_OK;
+  if (c->Nf == 0) {   // no finite point: the voxelize stage wrote neither the order nor the map (what they hold belongs to an earlier cloud)
+    for (int64_t j = 0; j < c->N; ++j) out[j] = -1;
+    return VGS_OK;
+  }
   std::vector<uint32_t> perm((size_t)c->N), pv((size_t)c->N);
   VGS_HIP_TRY(c, hipMemcpy(perm.data(), c->perm_b.p, perm.size() * 4, hipMemcpyDeviceToHost));
   VGS_HIP_TRY(c, hipMemcpy(pv.data(), c->pt_vox.p, pv.size() * 4, hipMemcpyDeviceToHost));

@@ -747,6 +747,10 @@ static DevBuf<uint32_t> s_dbg;   // per-voxel cycle / round counters of the diag
 vgs_status vgs_stage_localcut(vgs_ctx* c) {
   const int64_t U = c->U;
   c->counts[VGS_N_PAIRS] = 0;
+  // the schedule diagnostics describe THIS cut: a run that ends below without a used voxel reports what a fresh context does, zeros,
+  // not the previous cloud's numbers (lc_diag[5], "outside every kernel's limits", means "result incomplete")
+  for (int i = 0; i < 16; ++i) c->lc_diag[i] = 0;
+  for (int i = VGS_N_REATTACHED + 2; i < VGS_N_COUNTS; ++i) c->counts[i] = 0;   // handed over, class sizes
   if (c->lc_tail.open) {
     // a previous run of this stage was never completed by the merge stage (an error in between): its hand-over kernels may
     // still be running on the side streams, and they use the counters and lists this run is about to reset

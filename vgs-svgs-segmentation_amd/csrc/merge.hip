@@ -484,7 +484,12 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
   if (c->d2h_open && c->d2h_src == c->pt_label.p) std::swap(c->pt_label, c->pt_label_alt);
   VGS_HIP_TRY(c, c->pt_label.ensure(N > 0 ? N : 1));
   if (V == 0) {
-    if (N > 0) VGS_HIP_TRY(c, hipMemsetAsync(c->pt_label.p, 0xff, N * sizeof(int32_t), c->stream));
+    if (N > 0) {
+      VGS_HIP_TRY(c, hipMemsetAsync(c->pt_label.p, 0xff, N * sizeof(int32_t), c->stream));
+      VGS_HIP_TRY(c, hipEventRecord(c->ev[15], c->stream));   // label downloads order themselves behind this fill, not behind an earlier cloud's kernel
+      c->labels_event_valid = true;
+    }
+    c->pt_labels_pending = false;
     return VGS_OK;
   }
   MgParams MP;

@@ -70,7 +70,7 @@ __global__ void k_sv_set(uint32_t* p, uint32_t v) { *p = v; }
 vgs_status vgs_stage_svgs_group(vgs_ctx* c) {
   const int64_t N = c->N;
   c->V = 0; c->Nf = 0; c->U = 0;
-  if (N == 0) return VGS_OK;
+  if (N == 0) { c->counts[VGS_N_FINITE] = 0; c->counts[VGS_N_VOXELS] = 0; c->counts[VGS_N_SUPERVOXELS] = 0; return VGS_OK; }
   VGS_HIP_TRY(c, c->sv_key_a.ensure(N)); VGS_HIP_TRY(c, c->sv_key_b.ensure(N));
   VGS_HIP_TRY(c, c->perm_a.ensure(N)); VGS_HIP_TRY(c, c->perm_b.ensure(N));
   VGS_HIP_TRY(c, c->head_flag.ensure(N)); VGS_HIP_TRY(c, c->pt_vox.ensure(N));
@@ -218,6 +218,7 @@ __global__ __launch_bounds__(64) void k_sv_neighbours(const NodeRec* __restrict_
 
 vgs_status vgs_stage_svgs_neighbours(vgs_ctx* c) {
   const int64_t S = c->V;
+  c->counts[VGS_N_ADJ] = 0;   // summed on request (vgs_get_counts) from this cloud's rows, as in vgs_stage_adjacency
   if (S == 0) return VGS_OK;
   const double cell = (double)c->P.graph_size;
   const float r2 = (float)(cell * cell);
