@@ -29,13 +29,54 @@ struct MgParams {
   int64_t V;
 };
 
+// The merge front (k_cross, k_union_mutual) compacts a row before it looks anything up.  A row holds about 120 used neighbours, of
+// which about a fifth carry a connect flag and a tenth a mutual flag with t > i; only those enter the chain of dependent loads
+// (key -> used_rank -> connect-bit words / parent), and both kernels wait on loads, not on HBM's bandwidth.  So each row group first
+// reads its flags (coalesced, independent loads, several trips issued together), appends the positions of the set ones to a list
+// in LDS, and then walks the list with every lane carrying a load of the chain.  A list holds MF_CAP_TRIPS * W 16-bit positions per row
+// group (adj_stride reaches 8192); a row with more set entries is taken in rounds: fill, drain, go on behind the last trip taken.
+#define MF_CAP_TRIPS 8   // list capacity in trips of W entries: 8 * W * CX_ROWS (or UM_ROWS) * 2 bytes = 1 KB per workgroup
+// one batch of the flag pass, in two halves.  mf_load: T trips of W flags from position k0 -- unconditional loads (a position at or
+// beyond `limit` reads position 0, which every row has), so one wait covers all T and whatever else was issued beside them.
+template <int W, int T>
+__device__ __forceinline__ void mf_load(const uint8_t* __restrict__ flags, int limit, int k0, int sub, uint8_t (&f)[T]) {
+#pragma unroll
+  for (int q = 0; q < T; ++q) {
+    const int k = k0 + q * W + sub;
+    f[q] = flags[k < limit ? k : 0];
+  }
+}
+// mf_append: the positions below n whose flag is set go to `list` at `cnt`, in ascending order (`mine`: the lanes of this row group;
+// ballots of a wavefront whose groups have diverged carry zeros for the other group).  `zero`, when given, gets a 0 at every unset
+// position (the mutual flags of entries that are not connected).
+template <int W, int T>
+__device__ __forceinline__ void mf_append(const uint8_t (&f)[T], uint8_t* __restrict__ zero, int n, int k0, int sub,
+                                          unsigned long long mine, uint16_t* list, int& cnt) {
+#pragma unroll
+  for (int q = 0; q < T; ++q) {
+    const int k = k0 + q * W + sub;
+    const bool in = k < n, set = in && f[q] != 0;
+    const unsigned long long mk = __ballot(set) & mine;
+    if (set) list[cnt + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u))] = (uint16_t)k;   // set lanes below this one
+    else if (in && zero) zero[k] = 0;
+    cnt += __popcll(mk);
+  }
+}
+// LDS traffic inside one wavefront: earlier LDS writes of all lanes are visible and the compiler moves nothing across (the
+// lanes run in lockstep and a row group reads only what its own lanes wrote, so no s_barrier is needed)
+__device__ __forceinline__ void mf_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
 // ------------------------------------------------------------------ crossValidation
-// CX_ROWS rows per wavefront, 64 / CX_ROWS lanes each (see k_union_mutual: a row of about 120 entries leaves a whole
-// wavefront waiting on its chain of dependent loads; several rows per wavefront keep more of them in flight).
+// CX_ROWS rows per wavefront, 64 / CX_ROWS lanes each.  With the row compacted, the lanes of a group are what one trip of the
+// dense pass keeps in flight: 32 lanes take the connected entries of most rows (median 23, 95 % <= 56) in one or two trips.
 #ifndef CX_ROWS
 #define CX_ROWS 2
 #endif
-__global__ __launch_bounds__(64) void k_cross(const uint32_t* __restrict__ used_ids, const uint32_t* __restrict__ used_rank, int64_t U,
+// (eight wavefronts per SIMD asked for by name: the kernel's many arguments sit near the 96 scalar registers that allows)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void k_cross(const uint32_t* __restrict__ used_ids, const uint32_t* __restrict__ used_rank, int64_t U,
                                               const uint64_t* __restrict__ adj_key, const uint32_t* __restrict__ adj_cnt,
                                               int adj_stride, const uint8_t* __restrict__ conn, uint8_t* __restrict__ mutual,
                                               uint32_t* __restrict__ csize, uint32_t* __restrict__ parent,
@@ -54,31 +95,41 @@ __global__ __launch_bounds__(64) void k_cross(const uint32_t* __restrict__ used_
   // rows of the voxel lattice carry a table of where each group of equal offset length starts: the reverse entry has
   // the same length, so only that group (a handful of entries) is searched instead of the whole row
   __shared__ uint32_t s_rank4[64];   // length -> group index (256 bytes)
-  if (gtab) s_rank4[lane] = ((const uint32_t*)nrank)[lane];
-  __syncthreads();
-  const uint8_t* s_rank = (const uint8_t*)s_rank4;
+  __shared__ uint16_t s_list[CX_ROWS][MF_CAP_TRIPS * W];
+  constexpr int T = 4, CAP = MF_CAP_TRIPS * W;
+  const uint32_t rank4 = gtab ? ((const uint32_t*)nrank)[lane] : 0u;
   int64_t u;
+  bool live;
   if (work) {
     const int w = (int)blockIdx.x * CX_ROWS + grp;
-    if (w >= n_work) return;
-    u = (int64_t)work[w];
+    live = w < n_work;
+    u = live ? (int64_t)work[w] : 0;
   } else {
     const int64_t ngroups = (U + CX_ROWS - 1) / CX_ROWS;
     const int64_t g = vgs_xcd_item(blockIdx.x, ngroups);   // consecutive rows share a wavefront, consecutive groups an XCD
     u = g * CX_ROWS + grp;
-    if (g >= ngroups || u >= U) return;
+    live = g < ngroups && u < U;
+    if (!live) u = 0;
   }
-  if (pending && pending[u]) { if (sub == 0) { defer_list[atomicAdd(n_defer, 1u)] = (uint32_t)u; if (defer_flag) defer_flag[u] = 1; } return; }
-  bool touches_pending = false;
-  const uint32_t i = used_ids[u];
-  const int n = (int)adj_cnt[u];
+  // The head of the row's chain in one wait: its put-off flag, id and length, and the first batch of connect flags -- read without
+  // knowing the length (the row's allocation, adj_stride, bounds the loads; what lies behind the length is not looked at).  Lanes
+  // without a row read row 0 and leave below, behind the table's barrier.
   const uint64_t* row = adj_key + u * adj_stride;
   const uint8_t* crow = conn + u * adj_stride;
   uint8_t* mrow = mutual + u * adj_stride;
-  // a list of length <= 1 is left alone (VS:2120): it is {self}
-  int len = 0;
-  for (int k = sub; k < n; k += W) len += crow[k] ? 1 : 0;
-  for (int o = W / 2; o > 0; o >>= 1) len += __shfl_xor(len, o, 64);   // xor with o < W stays inside the row's lanes
+  const uint8_t put_off = pending ? pending[u] : (uint8_t)0;
+  const uint32_t i = used_ids[u];
+  const int n = (int)adj_cnt[u];
+  uint8_t f[T];
+  mf_load<W, T>(crow, adj_stride, 0, sub, f);
+  if (gtab) s_rank4[lane] = rank4;
+  __syncthreads();
+  const uint8_t* s_rank = (const uint8_t*)s_rank4;
+  if (!live) return;
+  if (put_off) { if (sub == 0) { defer_list[atomicAdd(n_defer, 1u)] = (uint32_t)u; if (defer_flag) defer_flag[u] = 1; } return; }
+  bool touches_pending = false;
+  uint16_t* list = s_list[grp];
+  const unsigned long long mine = (W == 64) ? ~0ull : (((1ull << W) - 1ull) << (grp * W));
   const bool own_tab = gtab && gtab[u * gstride] != 0xffffu;
   // lattice lookup (round 4): the neighbour t sits at ball offset o from i, so "i in L0(t)" is the bit of the NEGATED offset in t's row
   // of connect bits -- two dependent loads (t's row index, the word) instead of the chain rank -> group table -> binary search over
@@ -89,12 +140,24 @@ __global__ __launch_bounds__(64) void k_cross(const uint32_t* __restrict__ used_
   // first hook of the union-find (ECL-CC style): every used voxel points at its smallest trusted mutual neighbour below it.  Ids only
   // decrease along parent links, so this is a forest; it already joins most of every large segment without atomics.
   uint32_t best = i;
-  for (int k = sub; k < n; k += W) {
-    uint8_t mflag = 0;
-    if (crow[k]) {
+  // a list of length <= 1 is left alone (VS:2120): it is {self}.  Only a row whose flag pass ended in the first round can be that short.
+  bool single = false;
+  for (int k0 = 0, round = 0; k0 < n; ++round) {
+    // flag pass: the positions of the set entries, as many trips as the list is sure to hold
+    int cnt = 0;
+    for (; k0 < n && cnt + T * W <= CAP; k0 += T * W) {
+      if (k0 > 0) mf_load<W, T>(crow, n, k0, sub, f);
+      mf_append<W, T>(f, mrow, n, k0, sub, mine, list, cnt);
+    }
+    if (round == 0) single = k0 >= n && cnt <= 1;
+    mf_wave_sync();
+    // dense pass: every lane carries a connected entry
+    for (int j = sub; j < cnt; j += W) {
+      const int k = (int)list[j];
+      uint8_t mflag = 0;
       const uint64_t key = row[k];
       const uint32_t t = (uint32_t)key;
-      if (len <= 1 || t == i) {
+      if (single || t == i) {
         mflag = 1;
       } else {
         const uint32_t ut = used_rank[t];
@@ -140,12 +203,12 @@ __global__ __launch_bounds__(64) void k_cross(const uint32_t* __restrict__ used_
         }
       }
       if (mflag && t < best && (!owned || owned[i] || owned[t])) best = t;   // (tiled runs: a connection is trusted only if one endpoint is owned)
+      mrow[k] = mflag;
+      kept += mflag;
     }
-    mrow[k] = mflag;
-    kept += mflag;
+    mf_wave_sync();   // the next round's fill overwrites the list
   }
   if (pending) {   // what was written to a row that is put off is overwritten by the second pass
-    const unsigned long long mine = (W == 64) ? ~0ull : (((1ull << W) - 1ull) << (grp * W));
     if ((__ballot(touches_pending) & mine) != 0ull) {
       if (sub == 0) { defer_list[atomicAdd(n_defer, 1u)] = (uint32_t)u; if (defer_flag) defer_flag[u] = 1; }
       return;
@@ -257,11 +320,12 @@ __global__ void k_merge_init(uint32_t* __restrict__ parent, uint32_t* __restrict
   if (v < n) { parent[v] = (uint32_t)v; csize[v] = 0u; attach[v] = -1; cc_flags[v] = 0; csz[v] = 0u; }
 }
 
-// UM_ROWS rows per wavefront, 64 / UM_ROWS lanes each: a row holds about 120 entries, so a whole wavefront per row spends
-// its time waiting for three dependent loads (row header -> keys and flags -> parents); sharing the wavefront keeps several
-// rows' loads in flight at the same occupancy.
+// UM_ROWS rows per wavefront, 64 / UM_ROWS lanes each.  The row is compacted like crossValidation's (see mf_load, mf_append): a
+// fifth of its entries are mutual and half of those have t > i, so eight lanes take most rows' unions in one to three trips of the
+// dense pass, and eight rows per wavefront keep eight chains (flags -> keys -> parents) in flight at the same occupancy
+// (measured with the compacted rows: 4 rows 158 us per call, 8 rows 143 us; before the compaction 8 rows bought nothing).
 #ifndef UM_ROWS
-#define UM_ROWS 4
+#define UM_ROWS 8
 #endif
 __global__ __launch_bounds__(64) void k_union_mutual(const uint32_t* __restrict__ used_ids, int64_t U, const uint64_t* __restrict__ adj_key,
                                                      const uint32_t* __restrict__ adj_cnt, int adj_stride,
@@ -275,22 +339,42 @@ __global__ __launch_bounds__(64) void k_union_mutual(const uint32_t* __restrict_
   const int sub = threadIdx.x % W;
   if (work) { if (u >= n_work) return; u = (int64_t)work[u]; }   // the rows of a list (the second pass of crossValidation)
   if (u >= U) return;
-  if (skip && skip[u]) return;                                     // rows whose mutual flags are not final yet
-  const uint32_t i = used_ids[u];
-  const int n = (int)adj_cnt[u];
+  // the head of the row's chain in one wait: its skip flag, id and length, and the first batch of mutual flags (read without
+  // knowing the length: the row's allocation, adj_stride, bounds the loads)
+  constexpr int T = 8, CAP = MF_CAP_TRIPS * W;
   const uint64_t* row = adj_key + u * adj_stride;
   const uint8_t* mrow = mutual + u * adj_stride;
+  const uint8_t skipped = skip ? skip[u] : (uint8_t)0;             // rows whose mutual flags are not final yet
+  const uint32_t i = used_ids[u];
+  const int n = (int)adj_cnt[u];
+  uint8_t f[T];
+  mf_load<W, T>(mrow, adj_stride, 0, sub, f);
+  if (skipped) return;
   // after the first hook and the pointer jumping most neighbours already hang under the same node: equal parents mean
   // one tree, whatever other wavefronts do meanwhile (links are only ever added), and cost one load instead of two finds
   const uint32_t pi = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (int k = sub; k < n; k += W) {
-    if (!mrow[k]) continue;
-    const uint32_t t = (uint32_t)row[k];
-    // tiled runs: a connection is trusted only if one endpoint is owned (both neighbourhoods are then complete)
-    if (t > i && (!owned || owned[i] || owned[t])) {  // each mutual edge appears in both rows: union once
-      if (__hip_atomic_load(&parent[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == pi) continue;
-      uf_union(parent, i, t);
+  __shared__ uint16_t s_list[UM_ROWS][MF_CAP_TRIPS * W];
+  const int lane = threadIdx.x, grp = lane / W;
+  uint16_t* list = s_list[grp];
+  const unsigned long long mine = (W == 64) ? ~0ull : (((1ull << W) - 1ull) << (grp * W));
+  for (int k0 = 0; k0 < n;) {
+    // flag pass: the positions of the mutual entries, as many trips as the list is sure to hold
+    int cnt = 0;
+    for (; k0 < n && cnt + T * W <= CAP; k0 += T * W) {
+      if (k0 > 0) mf_load<W, T>(mrow, n, k0, sub, f);
+      mf_append<W, T>(f, nullptr, n, k0, sub, mine, list, cnt);
     }
+    mf_wave_sync();
+    // dense pass: every lane carries a mutual entry
+    for (int j = sub; j < cnt; j += W) {
+      const uint32_t t = (uint32_t)row[list[j]];
+      // tiled runs: a connection is trusted only if one endpoint is owned (both neighbourhoods are then complete)
+      if (t > i && (!owned || owned[i] || owned[t])) {  // each mutual edge appears in both rows: union once
+        if (__hip_atomic_load(&parent[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == pi) continue;
+        uf_union(parent, i, t);
+      }
+    }
+    mf_wave_sync();   // the next round's fill overwrites the list
   }
   if (sub == 0 && do_attach) {
     const int32_t t = attach[i];
