@@ -174,7 +174,11 @@ vgs_status vgs_get_lists(vgs_ctx* ctx, int32_t which, int64_t* offsets, int32_t*
  * reference's own order: cutGraphSegmentation returns its vertex list in merge-history order (every merge appends the absorbed
  * segment's vertices, VS:1986-1998, 2003-2026), crossValidation filters it in place, closestCheck appends (VS:2293-2294).
  * Computed on request by replaying the scan inside every list that was found (csrc/cutorder.hip); ties as the oracle's lean
- * flavour (the reference's std::sort of both orientations of a pair leaves them unspecified). */
+ * flavour (the reference's std::sort of both orientations of a pair leaves them unspecified).
+ * Limit of VGS_ORDER_REFERENCE: rows of any length the local cut accepts (8192 stored entries), connect lists after the local cut of up
+ * to 4224 nodes (the largest ball the local cut takes whole).  A cloud with a longer one gets VGS_E_UNSUPPORTED from
+ * vgs_get_lists_ordered (which >= 1) and vgs_get_clusters_ordered, the message naming the list's length and the limit; the default
+ * order has no such limit. */
 enum { VGS_ORDER_VOXEL_ID = 0, VGS_ORDER_REFERENCE = 1 };
 vgs_status vgs_get_lists_ordered(vgs_ctx* ctx, int32_t which, int32_t order, int64_t* offsets, int32_t* idx);
 /* voxels_adjacency_idx_[v][0] (VS:253): the number of neighbours of every node inside graph_size, itself included; 0 for a

@@ -278,6 +278,15 @@ def cut_graph(W, cut, flavour=0):
     return sorted(out[:k].tolist())
 
 
+def cut_graph_order(W, cut, flavour=1):
+    """The list of cut_graph as the cut returns it: the vertices of the centre's segment in merge-history order, unsorted."""
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    n = W.shape[0]
+    out = np.zeros(n, dtype=np.int32)
+    k = lib().ref_cut_graph(C.c_float(cut), _p(W), n, flavour, _p(out))
+    return out[:k].tolist()
+
+
 def compute_node(xyz, idx, math=0, svgs=False):
     xyz = _xyz(xyz)
     idx = np.ascontiguousarray(idx, dtype=np.int32)

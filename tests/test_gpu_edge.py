@@ -192,6 +192,13 @@ def test_neighbourhoods_above_2048_voxels(gpu, oracle, monkeypatch, wide):
         roff, ridx = ref.lists(which)
         assert np.array_equal(off, roff)
         assert ragged_sets(off, idx) == ragged_sets(roff, ridx)
+        off, idx = eng.lists(which, "reference")      # ... and element for element in the reference's own order (csrc/cutorder.hip)
+        np.testing.assert_array_equal(off, roff, err_msg=which)
+        np.testing.assert_array_equal(idx, ridx, err_msg=which)
+    off, idx = eng.clusters("reference")
+    roff, ridx = ref.lists("clusters_points")
+    np.testing.assert_array_equal(off, roff)
+    np.testing.assert_array_equal(idx, ridx)
     np.testing.assert_array_equal(eng.point_labels(), ref.labels()[0])
     assert eng.counts()["kept"] == ref.kept_clusters
 
@@ -235,6 +242,13 @@ def test_ball_of_ten_voxels_solid_block(gpu, oracle, monkeypatch, wide):
         roff, ridx = ref.lists(which)
         assert np.array_equal(off, roff)
         assert ragged_sets(off, idx) == ragged_sets(roff, ridx)
+        off, idx = eng.lists(which, "reference")      # ... and element for element in the reference's own order (csrc/cutorder.hip)
+        np.testing.assert_array_equal(off, roff, err_msg=which)
+        np.testing.assert_array_equal(idx, ridx, err_msg=which)
+    off, idx = eng.clusters("reference")
+    roff, ridx = ref.lists("clusters_points")
+    np.testing.assert_array_equal(off, roff)
+    np.testing.assert_array_equal(idx, ridx)
     np.testing.assert_array_equal(eng.point_labels(), ref.labels()[0])
     assert eng.counts()["kept"] == ref.kept_clusters
 

@@ -100,9 +100,11 @@ static __global__ void k_brick_clear(Brick* __restrict__ table, size_t H) {
 
 static inline vgs_status vgs_build_bricks(vgs_ctx* c, const NodeRec* node) {
   const int64_t V = c->V;
-  // the number of bricks is not known without a pass, V/4 slots would already be generous; size by V/2
+  // The number of bricks is not known without a pass; it is at most V (voxels that sit alone in their bricks: a lattice of voxels more
+  // than four cells apart).  The probe loops of k_brick_insert and brick_find end at an empty slot only, so the table must hold more
+  // slots than there can be bricks: sized by V / 2 it filled up on such a cloud and k_brick_insert never returned.
   uint32_t hbits = 4;
-  while ((1ull << hbits) < (uint64_t)(V / 2 + 16)) ++hbits;
+  while ((1ull << hbits) < (uint64_t)(V + 16)) ++hbits;
   c->hbits = hbits;
   const size_t H = (size_t)1 << hbits;
   VGS_HIP_TRY(c, c->hkey.ensure(H * (sizeof(Brick) / 8)));

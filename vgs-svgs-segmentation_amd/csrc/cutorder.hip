@@ -23,8 +23,12 @@
 #include <rocprim/rocprim.hpp>
 
 #include "vgs_context.hpp"
+#include "cutorder_arith.h"
 
-#define CO_MAXK 2048   // rows end at 2048 entries (the general local-cut kernel's limit)
+// Limits.  A row holds up to 8192 stored entries (the local cut's XL_M), so a row position needs 13 bits and is kept in a uint16_t.  The
+// LDS arrays below are indexed by the position INSIDE S0 only (0 .. k - 1) and hold CO_MAXK (cutorder_arith.h: 4224) entries;
+// vgs_cut_order refuses a cloud with a larger S0 on the host, from the counts of k_co_count, before k_co_eval or k_co_merge is launched.
+static_assert(CO_MAXK <= 65535, "S0 indices and segment sizes are kept in uint16_t (0xffff ends a vertex list)");
 
 // k = |S0| of every used voxel (the set flags of its connect row)
 __global__ void k_co_count(const uint8_t* __restrict__ conn, const uint32_t* __restrict__ adj_cnt, int adj_stride, int64_t U, uint32_t* __restrict__ kout) {
@@ -38,7 +42,8 @@ __global__ void k_co_count(const uint8_t* __restrict__ conn, const uint32_t* __r
   if (threadIdx.x == 0) kout[u] = (uint32_t)k;
 }
 
-// keys of the pairs inside S0 of voxel u0 + blockIdx.x: weight bits above the complemented pair id (row positions); NaN -> 0
+// keys of the pairs inside S0 of voxel u0 + blockIdx.x: weight bits above the complemented pair id; NaN -> 0.  The pair id is made of the
+// two indices inside S0 (i < j): pos[] is ascending, so it orders the pairs exactly as their row positions do.
 __global__ __launch_bounds__(256) void k_co_eval(int64_t u0, const uint64_t* __restrict__ adj_key, const uint32_t* __restrict__ adj_cnt, int adj_stride,
                                                  const uint8_t* __restrict__ conn, const NodeRec* __restrict__ node, VgsWeightParams W,
                                                  const uint64_t* __restrict__ offs, uint64_t* __restrict__ keys) {
@@ -48,35 +53,33 @@ __global__ __launch_bounds__(256) void k_co_eval(int64_t u0, const uint64_t* __r
   const int n = (int)adj_cnt[u];
   const uint64_t* row = adj_key + u * adj_stride;
   const uint8_t* crow = conn + u * adj_stride;
-  if (threadIdx.x == 0) {   // S0 in row order (a few hundred entries at most; sequential is fine for an on-request pass)
+  if (threadIdx.x == 0) {   // S0 in row order (sequential is fine for an on-request pass); k <= CO_MAXK: checked on the host
     int k = 0;
-    for (int c = 0; c < n; ++c) if (crow[c]) pos[k++] = (uint16_t)c;
-    s_k = k;
+    for (int c = 0; c < n; ++c) if (crow[c]) { if (k < CO_MAXK) pos[k] = (uint16_t)c; ++k; }
+    s_k = k < CO_MAXK ? k : CO_MAXK;
   }
   __syncthreads();
   const int k = s_k;
   const int64_t np = (int64_t)k * (k - 1) / 2;
   uint64_t* out = keys + offs[blockIdx.x];
   for (int64_t p = threadIdx.x; p < np; p += blockDim.x) {
-    // pair p in row-major order over i < j
-    int i = (int)(((double)(2 * k - 1) - sqrt((double)(2 * k - 1) * (double)(2 * k - 1) - 8.0 * (double)p)) * 0.5);
-    while (i > 0 && (int64_t)i * (2 * k - i - 1) / 2 > p) --i;
-    while ((int64_t)(i + 1) * (2 * k - i - 2) / 2 <= p) ++i;
-    const int j = i + 1 + (int)(p - (int64_t)i * (2 * k - i - 1) / 2);
+    int i, j;
+    co_pair_index(p, k, &i, &j);   // pair p in row-major order over i < j
     const int va = pos[i], vb = pos[j];
     const float w = vm_pair_weight(node[(uint32_t)row[va]], node[(uint32_t)row[vb]], W);
-    const uint32_t pid = ((uint32_t)va << 16) | (uint32_t)vb;
+    const uint32_t pid = ((uint32_t)i << 16) | (uint32_t)j;
     out[p] = (w != w) ? 0ull : (((uint64_t)vm_bits(w) << 32) | (uint64_t)(0xffffffffu - pid));
   }
 }
 
 // replay of the sequential scan (VS:1955-2001) over the sorted pairs of S0; ord[u * stride + r] = row position of the r-th
-// vertex of the returned list
+// vertex of the returned list.  Every LDS array is indexed by a position inside S0 (< k <= CO_MAXK): 5 * 2 + 4 bytes an entry, 59136 B.
+// A segment's vertex list starts at its root (a survivor is never absorbed and appends behind itself), so no head[] is kept.
 __global__ __launch_bounds__(64) void k_co_merge(int64_t u0, const uint32_t* __restrict__ adj_cnt, int adj_stride, const uint8_t* __restrict__ conn,
                                                  float cut, const uint64_t* __restrict__ offs, const uint64_t* __restrict__ keys,
                                                  uint16_t* __restrict__ ord, unsigned int* __restrict__ bad) {
-  __shared__ uint16_t pos[CO_MAXK], lidx[CO_MAXK];      // S0 in row order; row position -> index in S0
-  __shared__ uint16_t par[CO_MAXK], head[CO_MAXK], tail[CO_MAXK], nxt[CO_MAXK], ssz[CO_MAXK];
+  __shared__ uint16_t pos[CO_MAXK];      // S0 in row order
+  __shared__ uint16_t par[CO_MAXK], tail[CO_MAXK], nxt[CO_MAXK], ssz[CO_MAXK];
   __shared__ float thr[CO_MAXK];
   const int64_t u = u0 + (int64_t)blockIdx.x;
   const int n = (int)adj_cnt[u];
@@ -84,12 +87,13 @@ __global__ __launch_bounds__(64) void k_co_merge(int64_t u0, const uint32_t* __r
   const int lane = threadIdx.x;
   int k = 0;
   if (lane == 0) {
-    for (int c = 0; c < n; ++c) if (crow[c]) { pos[k] = (uint16_t)c; lidx[c] = (uint16_t)k; ++k; }
+    for (int c = 0; c < n; ++c) if (crow[c]) { if (k < CO_MAXK) pos[k] = (uint16_t)c; ++k; }   // k <= CO_MAXK: checked on the host
+    if (k > CO_MAXK) k = CO_MAXK;
   }
   k = __shfl(k, 0, 64);
   const float thr0 = vm_cut_threshold(1.0f, cut, 1);
   __syncthreads();
-  for (int i = lane; i < k; i += 64) { par[i] = (uint16_t)i; head[i] = (uint16_t)i; tail[i] = (uint16_t)i; nxt[i] = 0xffffu; ssz[i] = 1; thr[i] = thr0; }
+  for (int i = lane; i < k; i += 64) { par[i] = (uint16_t)i; tail[i] = (uint16_t)i; nxt[i] = 0xffffu; ssz[i] = 1; thr[i] = thr0; }
   __syncthreads();
   uint16_t* orow = ord + u * adj_stride;
   if (k == 0) return;
@@ -106,7 +110,8 @@ __global__ __launch_bounds__(64) void k_co_merge(int64_t u0, const uint32_t* __r
       if (lo == 0u && hi == 0u) { base = np; break; }   // NaN pairs sort last: nothing behind them merges (VS:1998: w > thr is false)
       const float w = vm_from_bits(hi);
       const uint32_t pid = 0xffffffffu - lo;
-      int a = lidx[pid >> 16], b = lidx[pid & 0xffffu];
+      int a = (int)(pid >> 16), b = (int)(pid & 0xffffu);   // indices inside S0 as k_co_eval wrote them
+      if (a >= k || b >= k) { base = np; break; }           // (never: keys of this voxel hold i < j < k)
       while (par[a] != a) a = par[a];
       while (par[b] != b) b = par[b];
       if (a == b) continue;
@@ -116,7 +121,7 @@ __global__ __launch_bounds__(64) void k_co_merge(int64_t u0, const uint32_t* __r
       if (lane == 0) {
         const int nsz = (int)ssz[keep] + (int)ssz[gone];
         par[gone] = (uint16_t)keep;
-        nxt[tail[keep]] = head[gone];    // seg_ver_idx[keep] gets the absorbed segment's vertices appended (VS:1990-1993)
+        nxt[tail[keep]] = (uint16_t)gone;    // seg_ver_idx[keep] gets the absorbed segment's vertices appended (VS:1990-1993)
         tail[keep] = tail[gone];
         ssz[keep] = (uint16_t)nsz;
         thr[keep] = vm_cut_threshold(w, cut, nsz);
@@ -127,11 +132,11 @@ __global__ __launch_bounds__(64) void k_co_merge(int64_t u0, const uint32_t* __r
   }
   __syncthreads();
   if (lane == 0) {
-    int r0 = lidx[0];   // row position 0 is the voxel itself; it is in S0
+    int r0 = 0;   // row position 0 is the voxel itself; it is in S0, as its first member
     if (!crow[0]) { atomicAdd(bad, 1u); return; }
     while (par[r0] != r0) r0 = par[r0];
     int cntv = 0;
-    for (int v = head[r0]; v != 0xffff; v = nxt[v]) { orow[cntv++] = pos[v]; if (cntv > k) break; }
+    for (int v = r0; v != 0xffff; v = nxt[v]) { if (cntv >= k) { ++cntv; break; } orow[cntv++] = pos[v]; }
     if (cntv != k) atomicAdd(bad, 1u);   // the replay must find exactly the set the hot path found
   }
 }
@@ -192,8 +197,8 @@ vgs_status vgs_cut_order(vgs_ctx* c, std::vector<uint16_t>& ord_host, std::vecto
   if (list_cnt) list_cnt->assign((size_t)U, 0);
   if (list_ids) list_ids->clear();
   if (U == 0) return VGS_OK;
-  // rows hold at most CO_MAXK entries: a longer one fails the local cut itself (VGS_E_UNSUPPORTED there); the row STRIDE (all
-  // lattice offsets of the ball) may well be larger
+  // rows hold up to 8192 stored entries (a longer one fails the local cut itself, VGS_E_UNSUPPORTED there; the row STRIDE, all lattice
+  // offsets of the ball, may well be larger); the replay kernels take a connect set of up to CO_MAXK of them -- checked below
   VGS_HIP_TRY(c, hipSetDevice(c->device));
   DevBuf<uint32_t> d_k; DevBuf<uint16_t> d_ord; DevBuf<uint64_t> d_offs, d_keys_a, d_keys_b; DevBuf<uint8_t> d_tmp; DevBuf<unsigned int> d_bad;
   auto release = [&]() { d_k.release(); d_ord.release(); d_offs.release(); d_keys_a.release(); d_keys_b.release(); d_tmp.release(); d_bad.release(); };
@@ -206,19 +211,20 @@ vgs_status vgs_cut_order(vgs_ctx* c, std::vector<uint16_t>& ord_host, std::vecto
     hipLaunchKernelGGL(k_co_count, dim3((unsigned)U), dim3(64), 0, c->stream, c->conn.p, c->adj_cnt.p, c->adj_stride, U, d_k.p);
     if ((e = hipMemcpyAsync(k_host.data(), d_k.p, (size_t)U * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) { fail(e, "copy"); break; }
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) { fail(e, "count"); break; }
+    {
+      const uint32_t kmax = *std::max_element(k_host.begin(), k_host.end());
+      if (kmax > (uint32_t)CO_MAXK) {   // before k_co_eval / k_co_merge: their LDS arrays hold CO_MAXK entries
+        c->err = "vgs_cut_order: a connect list of " + std::to_string(kmax) + " voxels; the reference order is replayed for lists of up to " +
+                 std::to_string(CO_MAXK) + " voxels";
+        st = VGS_E_UNSUPPORTED; break;
+      }
+    }
     // chunks of consecutive voxels with at most ~2^29 pairs (4 GB of keys, twice)
     const uint64_t budget = 1ull << 29;
     std::vector<uint64_t> offs;
     const VgsWeightParams W = co_weight_params(c->P);
     for (int64_t u0 = 0; u0 < U && st == VGS_OK;) {
-      offs.assign(1, 0ull);
-      int64_t u1 = u0;
-      while (u1 < U) {
-        const uint64_t k = k_host[(size_t)u1], np = k * (k - (k > 0 ? 1 : 0)) / 2;
-        if (u1 > u0 && offs.back() + np > budget) break;
-        offs.push_back(offs.back() + np);
-        ++u1;
-      }
+      const int64_t u1 = co_chunk(k_host.data(), U, u0, budget, offs);
       const int64_t m = u1 - u0;
       const uint64_t total = offs.back();
       if (total >= (1ull << 32)) { c->err = "vgs_cut_order: a single neighbourhood with more than 2^32 pairs"; st = VGS_E_UNSUPPORTED; break; }
