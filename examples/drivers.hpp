@@ -20,7 +20,7 @@ struct DriverGraph {
 };
 
 // per-point attributes handed to the drivers and what comes back: getClusterFieldStats over `field` (n x channels floats, row-major) when
-// channels > 0, getClusterClassHistogram over `classes` (n int32) when n_classes > 0
+// channels > 0, getClusterClassHistogram over `classes` (n int32) when n_classes > 0, compareClusterLabels over `truth` when have_truth
 struct DriverFields {
   std::vector<float> field;
   int channels = 0;
@@ -28,12 +28,17 @@ struct DriverFields {
   int n_classes = 0;
   std::vector<pcl::ClusterFieldStats> stats;
   std::vector<pcl::ClusterClassHistogram> hist;
+  // a reference labelling (n int32, negative = no annotation) when have_truth, and compareClusterLabels over it
+  std::vector<int32_t> truth;
+  bool have_truth = false;
+  pcl::ClusterLabelComparison matches;
 };
 template <typename S>
 inline void driverFields(S& structure, DriverFields& f) {
   if (f.channels > 0)
     f.stats = structure.getClusterFieldStats(f.field.data(), (int64_t)(f.field.size() / (size_t)f.channels), f.channels, 4 * (int64_t)f.channels);
   if (f.n_classes > 0) f.hist = structure.getClusterClassHistogram(f.classes.data(), (int64_t)f.classes.size(), f.n_classes);
+  if (f.have_truth) f.matches = structure.compareClusterLabels(f.truth.data(), (int64_t)f.truth.size());
 }
 
 // debug_prefix: when not empty, the reference's three voxel drawings (VS:510, 654, 1016) are written as

@@ -7,6 +7,8 @@
 // component r of axis j), lo (3), hi (3), every value as %.17g.
 // The --segment-fields CSV of vgs_run: one row per kept cluster: label, then per field n_valid, mean, var (%.17g), min, max (%.9g); the
 // --segment-classes CSV: label, majority, majority_count, n_outside, hist_0 .. hist_{C-1}.
+// The --segment-matches CSV of vgs_run: one row per kept cluster: label, n_annotated, n_refs, best_ref, best_n, best_iou (%.17g); the
+// --truth-matches CSV: one row per reference id: ref_id, n_points, n_dropped, best_seg, best_n, best_iou (%.17g).
 #ifndef VGS_EXAMPLES_SEGMENTS_CSV_HPP_
 #define VGS_EXAMPLES_SEGMENTS_CSV_HPP_
 
@@ -93,6 +95,26 @@ inline int writeClassHistCsv(const std::string& path, int n_classes, const std::
     for (int64_t v : h.hist) std::fprintf(f, ",%lld", (long long)v);
     std::fprintf(f, "\n");
   }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
+inline int writeSegmentMatchesCsv(const std::string& path, const pcl::ClusterLabelComparison& m) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "label,n_annotated,n_refs,best_ref,best_n,best_iou\n");
+  for (size_t i = 0; i < m.seg_annotated.size(); ++i)
+    std::fprintf(f, "%zu,%lld,%d,%d,%lld,%.17g\n", i, (long long)m.seg_annotated[i], (int)m.seg_refs[i], (int)m.seg_best_ref[i],
+                 (long long)m.seg_best_n[i], m.seg_best_iou[i]);
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
+inline int writeTruthMatchesCsv(const std::string& path, const pcl::ClusterLabelComparison& m) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "ref_id,n_points,n_dropped,best_seg,best_n,best_iou\n");
+  for (size_t i = 0; i < m.ref_id.size(); ++i)
+    std::fprintf(f, "%d,%lld,%lld,%d,%lld,%.17g\n", (int)m.ref_id[i], (long long)m.ref_points[i], (long long)m.ref_dropped[i],
+                 (int)m.ref_best_seg[i], (long long)m.ref_best_n[i], m.ref_best_iou[i]);
   return std::fclose(f) == 0 ? 0 : -1;
 }
 

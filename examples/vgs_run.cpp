@@ -6,6 +6,7 @@
 //                  [--segments <file.csv>] [--segment-graph <file.csv>] [--segment-adjacency <file.txt>]
 //                  [--segment-boxes <file.csv> [--box-frame principal|upright]]
 //                  [--segment-fields <file.csv> --fields a[,b,...]] [--segment-classes <file.csv> --class-field <name> --classes <C>]
+//                  [--segment-matches <file.csv> --truth-field <name> [--truth-matches <file.csv>]]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
 // --segments writes one CSV row per kept cluster (getClusterDescriptors, row i = cluster i of the output): label, n_points, n_nodes,
@@ -21,6 +22,12 @@
 // numeric type, COUNT 1): label, then per field n_valid, mean, var (%.17g), min, max (%.9g).  --segment-classes writes one row per kept
 // cluster (getClusterClassHistogram over the field --class-field names, classes 0 .. C-1 with C = --classes in 1 .. 1024): label, majority,
 // majority_count, n_outside, hist_0 .. hist_{C-1}.  A flag without its companions, or either with a PLY input, is a usage error (status 2).
+// --segment-matches scores the clusters against the reference labelling in the field --truth-field names (compareClusterLabels; read from
+// the input PCD as exact integers, any numeric type, COUNT 1; a negative value = no annotation; a value that is not an integer or does not
+// fit int32 ends the run with an error, nothing is rounded) and writes one CSV row per kept cluster: label, n_annotated, n_refs, best_ref,
+// best_n, best_iou (%.17g).  --truth-matches adds one row per reference id: ref_id, n_points, n_dropped, best_seg, best_n, best_iou.  A
+// second and third line on stdout carry the summary ("matches" and its twelve numbers) and the scores at IoU > 0.5 ("scores matched
+// precision recall f1 purity completeness ari", %.17g).  The same usage rules.
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
 #include <algorithm>
 #include <cmath>
@@ -45,11 +52,12 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     std::fprintf(stderr, "usage: %s <task file> [--in file.pcd] [--out file.pcd] [--seed n] [--ascii] [--debug-meshes prefix] [--segments file.csv] "
                  "[--segment-graph file.csv] [--segment-adjacency file.txt] [--segment-boxes file.csv [--box-frame principal|upright]] "
-                 "[--segment-fields file.csv --fields a[,b,...]] [--segment-classes file.csv --class-field name --classes C]\n",
+                 "[--segment-fields file.csv --fields a[,b,...]] [--segment-classes file.csv --class-field name --classes C] "
+                 "[--segment-matches file.csv --truth-field name [--truth-matches file.csv]]\n",
                  argv[0]);
     return 2;
   }
-  std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file, boxes_file, fields_file, classes_file, class_field;
+  std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file, boxes_file, fields_file, classes_file, class_field, matches_file, truth_field, truth_file;
   std::vector<std::string> field_names;
   bool have_fields = false, have_classes = false;
   long n_classes = 0;
@@ -90,6 +98,9 @@ int main(int argc, char** argv) {
       n_classes = std::strtol(argv[++a], &end, 10);
       if (end == argv[a] || *end != 0 || n_classes < 1 || n_classes > 1024) { std::fprintf(stderr, "--classes %s: a number in 1 .. 1024\n", argv[a]); return 2; }
     }
+    else if (!std::strcmp(argv[a], "--segment-matches") && a + 1 < argc) matches_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--truth-field") && a + 1 < argc) truth_field = argv[++a];
+    else if (!std::strcmp(argv[a], "--truth-matches") && a + 1 < argc) truth_file = argv[++a];
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
   if (!fields_file.empty() && (!have_fields || field_names.empty())) { std::fprintf(stderr, "--segment-fields needs --fields a[,b,...]\n"); return 2; }
@@ -98,6 +109,8 @@ int main(int argc, char** argv) {
   if (!classes_file.empty() && !have_classes) { std::fprintf(stderr, "--segment-classes needs --classes <C>\n"); return 2; }
   if (fields_file.empty() && have_fields) { std::fprintf(stderr, "--fields needs --segment-fields <file.csv>\n"); return 2; }
   if (classes_file.empty() && (have_classes || !class_field.empty())) { std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv>\n"); return 2; }
+  if (!matches_file.empty() && truth_field.empty()) { std::fprintf(stderr, "--segment-matches needs --truth-field <name>\n"); return 2; }
+  if (matches_file.empty() && (!truth_field.empty() || !truth_file.empty())) { std::fprintf(stderr, "--truth-field / --truth-matches need --segment-matches <file.csv>\n"); return 2; }
   const std::vector<std::string> task = inputTaskTxtFile(argv[1]);
   if (task.size() < 51) { std::fprintf(stderr, "%s: not a task file (%zu lines)\n", argv[1], task.size()); return 2; }
   const int method = std::atoi(task[24].c_str());
@@ -111,13 +124,13 @@ int main(int argc, char** argv) {
   }
   PCXYZPtr cloud(new PCXYZ);
   const bool ply = in_file.size() > 4 && in_file.substr(in_file.size() - 4) == ".ply";
-  if (ply && !(fields_file.empty() && classes_file.empty())) {   // (a usage error: nothing has been loaded yet)
-    std::fprintf(stderr, "--segment-fields / --segment-classes read their fields from a PCD input, not from %s\n", in_file.c_str());
+  if (ply && !(fields_file.empty() && classes_file.empty() && matches_file.empty())) {   // (a usage error: nothing has been loaded yet)
+    std::fprintf(stderr, "--segment-fields / --segment-classes / --segment-matches read their fields from a PCD input, not from %s\n", in_file.c_str());
     return 2;
   }
   if ((ply ? inputPointCloudData2(in_file, cloud) : inputPointCloudData(in_file, cloud)) != 0) return 1;
   DriverFields fields;
-  DriverFields* want_fields = (fields_file.empty() && classes_file.empty()) ? nullptr : &fields;
+  DriverFields* want_fields = (fields_file.empty() && classes_file.empty() && matches_file.empty()) ? nullptr : &fields;
   if (want_fields) {   // the attributes ride in the input PCD, one row per point of the cloud
     std::string err;
     if (!fields_file.empty()) {
@@ -130,6 +143,10 @@ int main(int argc, char** argv) {
       fields.classes.resize(v.size());
       for (size_t i = 0; i < v.size(); ++i) fields.classes[i] = (v[i] >= -2147483648.0f && v[i] < 2147483648.0f) ? (int32_t)v[i] : -1;
       fields.n_classes = (int)n_classes;
+    }
+    if (!matches_file.empty()) {
+      if (vgs_io::read_pcd_field_int32(in_file, truth_field, fields.truth, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
+      fields.have_truth = true;
     }
   }
   std::vector<std::vector<int>> clusters;
@@ -156,10 +173,18 @@ int main(int argc, char** argv) {
   if (want_boxes && writeBoxesCsv(boxes_file, boxes) != 0) { std::fprintf(stderr, "cannot write %s\n", boxes_file.c_str()); return 1; }
   if (!fields_file.empty() && writeFieldStatsCsv(fields_file, field_names, fields.stats) != 0) { std::fprintf(stderr, "cannot write %s\n", fields_file.c_str()); return 1; }
   if (!classes_file.empty() && writeClassHistCsv(classes_file, fields.n_classes, fields.hist) != 0) { std::fprintf(stderr, "cannot write %s\n", classes_file.c_str()); return 1; }
+  if (!matches_file.empty() && writeSegmentMatchesCsv(matches_file, fields.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", matches_file.c_str()); return 1; }
+  if (!truth_file.empty() && writeTruthMatchesCsv(truth_file, fields.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", truth_file.c_str()); return 1; }
   if (!adjacency_file.empty() && writeAdjacency(adjacency_file, graph.adjacency) != 0) {
     std::fprintf(stderr, "cannot write %s\n", adjacency_file.c_str());
     return 1;
   }
   std::printf("%d %ld %ld %ld %ld %ld %ld\n", method, sum.points, sum.voxels, sum.supervoxels, sum.clusters, sum.kept, sum.labelled);
+  if (!matches_file.empty()) {
+    std::printf("matches");
+    for (int i = 0; i < 12; ++i) std::printf(" %lld", (long long)fields.matches.summary[i]);
+    const pcl::ClusterLabelScores sc = pcl::clusterLabelScores(fields.matches, 0.5);
+    std::printf("\nscores %lld %.17g %.17g %.17g %.17g %.17g %.17g\n", (long long)sc.matched, sc.precision, sc.recall, sc.f1, sc.purity, sc.completeness, sc.ari);
+  }
   return 0;
 }

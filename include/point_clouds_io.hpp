@@ -236,6 +236,37 @@ inline int read_pcd_fields(const std::string& name, const std::vector<std::strin
   return read_pcd_body(f, h, cols, [&](size_t n) { out.assign(n * C, 0.0f); }, [&](size_t i, size_t c, double v) { out[i * C + c] = (float)v; }, err);
 }
 
+// reads one named field of a PCD file (any numeric type, COUNT 1 only) as exact int32 values: out[i] = the value of point i of the file.
+// The values travel as doubles, which hold every 8-, 16- and 32-bit integer and every float exactly; a value that is not an integer
+// (NaN and infinities included) or lies outside [-2^31, 2^31 - 1] is an error that names the point and the value -- nothing is rounded.
+inline int read_pcd_field_int32(const std::string& name, const std::string& field_name, std::vector<int32_t>& out, std::string& err) {
+  std::ifstream f(name, std::ios::binary);
+  if (!f.is_open()) { err = "cannot open " + name; return -1; }
+  PcdHeader h;
+  if (!parse_pcd_header(f, h, err)) return -1;
+  int at = -1;
+  for (size_t k = 0; k < h.fields.size(); ++k) if (h.fields[k].name == field_name) { at = (int)k; break; }
+  if (at < 0) { err = "PCD file " + name + " has no field '" + field_name + "'"; return -1; }
+  if (h.fields[(size_t)at].count != 1) { err = "PCD field '" + field_name + "' has COUNT " + std::to_string(h.fields[(size_t)at].count) + ": only COUNT 1 is read"; return -1; }
+  bool bad = false;
+  size_t bad_at = 0;
+  double bad_v = 0.0;
+  const int rc = read_pcd_body(f, h, {at}, [&](size_t n) { out.assign(n, 0); },
+                               [&](size_t i, size_t, double v) {
+                                 // (NaN fails the range test; a double in the range converts to int64 exactly once it is integral)
+                                 if (v >= -2147483648.0 && v <= 2147483647.0 && (double)(int64_t)v == v) { out[i] = (int32_t)(int64_t)v; return; }
+                                 if (!bad) { bad = true; bad_at = i; bad_v = v; }
+                               }, err);
+  if (rc != 0) return rc;
+  if (bad) {
+    char num[64];
+    std::snprintf(num, sizeof(num), "%.17g", bad_v);
+    err = "PCD field '" + field_name + "' of point " + std::to_string(bad_at) + " is " + num + ": not an integer that fits int32";
+    return -1;
+  }
+  return 0;
+}
+
 // PLY: the vertex element's x, y, z properties (any scalar type); ascii, binary_little_endian and binary_big_endian;
 // list properties inside the vertex element are not supported, other elements (faces) are ignored
 inline int read_ply_xyz(const std::string& name, std::vector<pcl::PointXYZ>& pts, std::string& err) {

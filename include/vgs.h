@@ -380,6 +380,57 @@ vgs_status vgs_segment_class_histogram(vgs_ctx* ctx, const int32_t* cls_host, in
                                        int32_t* majority, int64_t* majority_count);
 vgs_status vgs_segment_class_histogram_device(vgs_ctx* ctx, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* hist,
                                               int64_t* n_outside, int32_t* majority, int64_t* majority_count);
+/* Score the segmentation against a labelling of the same points that the CALLER supplies (no reference counterpart in code: the matching of
+ * segments to reference segments by which the VGS / SVGS paper counts precision, recall and F1).  The sparse contingency
+ * table between the point labels and `ref`, and the two match tables read off it.  No label is written, no other cloud is involved.
+ *   ref   one int32 per input point, row i belongs to input point i; n must equal counts[VGS_N_POINTS].  Point i is ANNOTATED iff
+ *         ref[i] >= 0; any non-negative int32 is a reference id, ids need not be dense.  A point with ref[i] < 0 takes no part in anything
+ *         below; it is only counted, in summary[1].
+ *   L[i]  the point label of vgs_get_point_labels: 0 .. K-1 (K = counts[VGS_N_KEPT]), or -1 for a dropped point.
+ * Cells: one per distinct pair (L, g) over the annotated points, in ascending (L, g) order, the L = -1 row first; n_cells rows:
+ *   cell_seg  int32  L            cell_ref  int32  g            cell_n  int64  annotated points with that pair
+ * Reference table: n_refs = G rows, one per distinct id, ascending:
+ *   ref_id        int32   the id
+ *   ref_points    int64   annotated points with that id
+ *   ref_dropped   int64   those with L = -1
+ *   ref_best_seg  int32   the kept segment L >= 0 with the largest cell_n, the lowest label on a tie; -1 when every point of the id is dropped
+ *   ref_best_n    int64   that cell_n (0 with -1)
+ *   ref_best_iou  double  (double)n / (double)(seg_annotated[ref_best_seg] + ref_points - n), n = ref_best_n: one fp64 division; 0.0 with -1
+ * Segment table: K rows:
+ *   seg_annotated int64   annotated points with label k
+ *   seg_refs      int32   distinct ids among them
+ *   seg_best_ref  int32   the id with the largest cell_n, the lowest id on a tie; -1 without an annotated point
+ *   seg_best_n    int64   that cell_n (0 with -1)
+ *   seg_best_iou  double  (double)n / (double)(seg_annotated + ref_points[seg_best_ref] - n), n = seg_best_n; 0.0 with -1
+ * summary, int64[12], C(a, 2) = a (a - 1) / 2:
+ *   0 annotated points    1 unannotated points    2 annotated points with L = -1    3 G    4 n_cells    5 segments with seg_annotated > 0
+ *   6 sum over k of seg_best_n    7 sum over the ids of ref_best_n    8 sum of C(cell_n, 2) over all cells
+ *   9 sum of C(a, 2) over the rows, a = the annotated points of the row, the L = -1 row counted as one class    10 sum of C(ref_points, 2)
+ *   11 0, reserved
+ * Everything is an integer or one division of two integers converted to double: bit-identical from call to call and from engine to engine
+ * (the integer atomics of csrc/segcompare.hip add in any order).
+ * vgs_compare_labels computes all three tables on the device into buffers of the context and returns their sizes and the summary (each
+ * of n_cells, n_refs, summary may be NULL); the host variant uploads ref once, the device variant reads ref_dev (HBM, the context's device;
+ * complete before the call) in place.  A table without rows is empty and the counts say why: a cloud without points gives zero sizes and a
+ * zero summary; without an annotated point n_cells = G = 0, the K segment rows read 0, 0, -1, 0, 0.0 and only summary[1] counts; with
+ * K = 0 every annotated point is dropped, so the cells are the L = -1 row, every ref_best_seg is -1 and the segment table is empty.  Never
+ * the previous comparison's numbers.
+ * vgs_get_label_comparison copies the tables of the last compare (any pointer may be NULL; sizes as that compare returned them, K rows for
+ * the segment table); vgs_get_label_comparison_device returns them as device pointers (NULL for a table without rows), valid until the next
+ * compare or the next run of the stages.  Both answer VGS_E_STATE when there is no comparison since the last run of the stages or the last
+ * vgs_set_points.
+ * VGS_E_ARG, the message naming the argument, for n != counts[VGS_N_POINTS] and for a NULL ref with n > 0; VGS_E_STATE before the context
+ * is segmented and for a tile context.  No side effects: labels, descriptors, boxes, graph and every other cached table stay as they are. */
+vgs_status vgs_compare_labels(vgs_ctx* ctx, const int32_t* ref_host, int64_t n, int64_t* n_cells, int64_t* n_refs, int64_t* summary /* 12 */);
+vgs_status vgs_compare_labels_device(vgs_ctx* ctx, const int32_t* ref_dev, int64_t n, int64_t* n_cells, int64_t* n_refs, int64_t* summary /* 12 */);
+vgs_status vgs_get_label_comparison(vgs_ctx* ctx, int32_t* cell_seg, int32_t* cell_ref, int64_t* cell_n, int32_t* ref_id, int64_t* ref_points,
+                                    int64_t* ref_dropped, int32_t* ref_best_seg, int64_t* ref_best_n, double* ref_best_iou, int64_t* seg_annotated,
+                                    int32_t* seg_refs, int32_t* seg_best_ref, int64_t* seg_best_n, double* seg_best_iou);
+vgs_status vgs_get_label_comparison_device(vgs_ctx* ctx, const int32_t** cell_seg, const int32_t** cell_ref, const int64_t** cell_n,
+                                           const int32_t** ref_id, const int64_t** ref_points, const int64_t** ref_dropped,
+                                           const int32_t** ref_best_seg, const int64_t** ref_best_n, const double** ref_best_iou,
+                                           const int64_t** seg_annotated, const int32_t** seg_refs, const int32_t** seg_best_ref,
+                                           const int64_t** seg_best_n, const double** seg_best_iou);
 /* Attribute moments of a tile context (the tiled driver, include/vgs_tiles.h: vgs_tiles_segment_field_stats builds the global table from
  * them).  No attribute travels between ranks: a rank hands in one row per point of its OWN load, in the order it gave them to the driver --
  * own point i is cloud point own_first + i of vgs_set_own_point_range -- so n_own must equal that range's length; channels, stride_bytes and

@@ -16,6 +16,7 @@
 #define VGS_SEGMENTATION_HPP_
 
 #include <cstdint>
+#include <limits>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -205,6 +206,62 @@ inline std::vector<ClusterClassHistogram> cluster_class_histogram(vgs_ctx* c, in
 }
 }  // namespace vgs_detail
 
+// Extension (no VS / SS line): the comparison of the clusters with a reference labelling of the same points, as vgs_compare_labels
+// (include/vgs.h) defines it: the cells (one per distinct (cluster, id) pair, ascending, cluster -1 = dropped points first), one row per
+// distinct reference id, one row per kept cluster (getClusterIdx order), and the summary
+struct ClusterLabelComparison {
+  std::vector<int32_t> cell_seg, cell_ref;
+  std::vector<int64_t> cell_n;
+  std::vector<int32_t> ref_id;
+  std::vector<int64_t> ref_points, ref_dropped;
+  std::vector<int32_t> ref_best_seg;
+  std::vector<int64_t> ref_best_n;
+  std::vector<double> ref_best_iou;
+  std::vector<int64_t> seg_annotated;
+  std::vector<int32_t> seg_refs, seg_best_ref;
+  std::vector<int64_t> seg_best_n;
+  std::vector<double> seg_best_iou;
+  int64_t summary[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
+// The scores read off a comparison: clusters matched to an id with IoU > tau (0.5 <= tau < 1), precision = matched / clusters with an
+// annotated point, recall = matched / ids, F1, purity, completeness and the adjusted Rand index over the annotated points (the dropped
+// points as one class); NaN where a denominator is zero
+struct ClusterLabelScores { int64_t matched = 0; double precision = 0, recall = 0, f1 = 0, purity = 0, completeness = 0, ari = 0; };
+inline ClusterLabelScores clusterLabelScores(const ClusterLabelComparison& c, double tau = 0.5) {
+  if (!(tau >= 0.5 && tau < 1.0)) throw std::runtime_error("clusterLabelScores: tau must lie in [0.5, 1)");
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  auto div = [nan](double a, double b) { return b != 0.0 ? a / b : nan; };
+  const int64_t* s = c.summary;
+  ClusterLabelScores o;
+  for (double v : c.seg_best_iou) o.matched += v > tau ? 1 : 0;
+  o.precision = div((double)o.matched, (double)s[5]);
+  o.recall = div((double)o.matched, (double)s[3]);
+  o.f1 = (o.precision == o.precision && o.recall == o.recall) ? div(2.0 * o.precision * o.recall, o.precision + o.recall) : nan;
+  o.purity = div((double)s[6], (double)(s[0] - s[2]));
+  o.completeness = div((double)s[7], (double)s[0]);
+  const double T = (double)(s[0] % 2 ? s[0] * ((s[0] - 1) / 2) : (s[0] / 2) * (s[0] - 1));
+  const double e = div((double)s[9] * (double)s[10], T);
+  o.ari = e == e ? div((double)s[8] - e, ((double)s[9] + (double)s[10]) / 2.0 - e) : nan;
+  return o;
+}
+
+namespace vgs_detail {
+inline ClusterLabelComparison cluster_label_comparison(vgs_ctx* c, int64_t k, const int32_t* ref, int64_t n) {
+  ClusterLabelComparison o;
+  int64_t n_cells = 0, n_refs = 0;
+  check(c, vgs_compare_labels(c, ref, n, &n_cells, &n_refs, o.summary), "vgs_compare_labels");
+  const size_t nc = (size_t)n_cells, g = (size_t)n_refs, kk = (size_t)k;
+  o.cell_seg.resize(nc); o.cell_ref.resize(nc); o.cell_n.resize(nc);
+  o.ref_id.resize(g); o.ref_points.resize(g); o.ref_dropped.resize(g); o.ref_best_seg.resize(g); o.ref_best_n.resize(g); o.ref_best_iou.resize(g);
+  o.seg_annotated.resize(kk); o.seg_refs.resize(kk); o.seg_best_ref.resize(kk); o.seg_best_n.resize(kk); o.seg_best_iou.resize(kk);
+  check(c, vgs_get_label_comparison(c, o.cell_seg.data(), o.cell_ref.data(), o.cell_n.data(), o.ref_id.data(), o.ref_points.data(),
+                                    o.ref_dropped.data(), o.ref_best_seg.data(), o.ref_best_n.data(), o.ref_best_iou.data(),
+                                    o.seg_annotated.data(), o.seg_refs.data(), o.seg_best_ref.data(), o.seg_best_n.data(), o.seg_best_iou.data()),
+        "vgs_get_label_comparison");
+  return o;
+}
+}  // namespace vgs_detail
+
 // Extension (no VS / SS line): one edge of the adjacency graph of the kept clusters, as vgs_get_segment_graph (include/vgs.h) defines it
 struct ClusterEdge {
   int32_t a = 0, b = 0;        // cluster indices (getClusterIdx order), a < b
@@ -384,6 +441,12 @@ class VoxelBasedSegmentation {
     if (!drawn_) return {};
     return vgs_detail::cluster_class_histogram(ctx(), count(VGS_N_KEPT), classes, n, n_classes);
   }
+  // Extension (no VS line): the clusters against a reference labelling (n int32 in input order, negative = no annotation); row i of the
+  // cluster table belongs to getClusterIdx()[i]; empty before drawColorMapofPointsinClusters
+  ClusterLabelComparison compareClusterLabels(const int32_t* ref, int64_t n) {
+    if (!drawn_) return {};
+    return vgs_detail::cluster_label_comparison(ctx(), count(VGS_N_KEPT), ref, n);
+  }
 
   vgs_ctx* ctx() { return ctx_.get(); }
 
@@ -490,6 +553,11 @@ class SuperVoxelBasedSegmentation {
   // Extension (no SS line): row i counts a per-point class (n int32 in input order) over getClusterIdx()[i]
   std::vector<ClusterClassHistogram> getClusterClassHistogram(const int32_t* classes, int64_t n, int32_t n_classes) {
     return vgs_detail::cluster_class_histogram(ctx(), count(VGS_N_KEPT), classes, n, n_classes);
+  }
+  // Extension (no SS line): the clusters against a reference labelling (n int32 in input order, negative = no annotation); row i of the
+  // cluster table belongs to getClusterIdx()[i]
+  ClusterLabelComparison compareClusterLabels(const int32_t* ref, int64_t n) {
+    return vgs_detail::cluster_label_comparison(ctx(), count(VGS_N_KEPT), ref, n);
   }
   vgs_ctx* ctx() { return ctx_.get(); }
 

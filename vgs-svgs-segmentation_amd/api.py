@@ -16,6 +16,35 @@ from . import _lib
 from ._lib import VgsError, VgsGridState, VgsParams
 
 
+def comparison_scores(cmp, tau=0.5):
+    """Scores of a label comparison (the dict of Engine.compare_labels, or tests/label_compare_ref.py's restatement), a pure function:
+      matched       segments whose best id overlaps them with IoU > tau.  For tau >= 0.5 a segment matches at most one id and an id at most
+                    one segment, so the same number comes out of ref_best_iou
+      precision     matched / segments with an annotated point (summary[5]);  recall  matched / G;  f1  their harmonic mean
+      purity        summary[6] / kept annotated points (summary[0] - summary[2]);  completeness  summary[7] / summary[0]
+      ari           the adjusted Rand index over the annotated points, from c = summary[8], a = summary[9], b = summary[10], n = summary[0],
+                    T = C(n, 2): (c - a b / T) / ((a + b) / 2 - a b / T), the dropped points as one class
+    Any score whose denominator is zero is NaN.  tau must lie in [0.5, 1)."""
+    tau = float(tau)
+    if not 0.5 <= tau < 1.0:
+        raise ValueError(f"tau = {tau} must lie in [0.5, 1)")
+    s = [int(v) for v in cmp["summary"]]
+    nan = float("nan")
+
+    def div(a, b):
+        return a / b if b != 0 else nan
+
+    matched = int(np.count_nonzero(np.asarray(cmp["seg_best_iou"]) > tau))
+    precision, recall = div(matched, s[5]), div(matched, s[3])
+    f1 = div(2.0 * precision * recall, precision + recall) if precision == precision and recall == recall else nan
+    n = s[0]
+    T = n * (n - 1) // 2
+    expected = div(float(s[9]) * float(s[10]), float(T))
+    ari = div(float(s[8]) - expected, (float(s[9]) + float(s[10])) / 2.0 - expected) if expected == expected else nan
+    return {"tau": tau, "matched": matched, "precision": precision, "recall": recall, "f1": f1, "purity": div(s[6], s[0] - s[2]),
+            "completeness": div(s[7], s[0]), "ari": ari}
+
+
 def default_params(method=2, **kw):
     p = VgsParams()
     L = _lib.lib()
@@ -409,6 +438,40 @@ class Engine:
         self._ck(fn(self._h, ptr, n, nc, *(_ptr(out[name]) for name, _, _ in self.CLASS_HIST_FIELDS)))
         return out
 
+    # (field, dtype, table) of vgs_get_label_comparison, in its argument order; the tables have n_cells, G and K rows
+    COMPARE_FIELDS = (("cell_seg", np.int32, "cells"), ("cell_ref", np.int32, "cells"), ("cell_n", np.int64, "cells"),
+                      ("ref_id", np.int32, "refs"), ("ref_points", np.int64, "refs"), ("ref_dropped", np.int64, "refs"),
+                      ("ref_best_seg", np.int32, "refs"), ("ref_best_n", np.int64, "refs"), ("ref_best_iou", np.float64, "refs"),
+                      ("seg_annotated", np.int64, "segs"), ("seg_refs", np.int32, "segs"), ("seg_best_ref", np.int32, "segs"),
+                      ("seg_best_n", np.int64, "segs"), ("seg_best_iou", np.float64, "segs"))
+
+    def compare_labels(self, ref):
+        """Score the segmentation against a labelling of the same points (include/vgs.h, vgs_compare_labels): the sparse contingency table
+        between point_labels() and `ref`, the reference table and the segment table, as a dict of numpy arrays -- cell_seg, cell_ref, cell_n
+        (one row per distinct (label, id) pair, ascending, the -1 row first), ref_id, ref_points, ref_dropped, ref_best_seg, ref_best_n,
+        ref_best_iou (one row per distinct id, ascending), seg_annotated, seg_refs, seg_best_ref, seg_best_n, seg_best_iou (K rows) -- plus
+        summary (int64[12]).  `ref`: int32 of shape (N,) in input order, a numpy array or a torch tensor on the context's device, which is
+        read in place; a negative id marks a point without annotation.  Computed on the device; integer counts and single fp64 quotients,
+        bit-identical from call to call.  comparison_scores() turns the dict into precision, recall, F1, purity and the Rand index."""
+        K = self.counts()["kept"]
+        ref, ptr, n, dev = self._classes_input(ref, self.params.device)
+        fn = self._L.vgs_compare_labels_device if dev else self._L.vgs_compare_labels
+        n_cells, n_refs = C.c_int64(0), C.c_int64(0)
+        summary = np.zeros(12, np.int64)
+        self._ck(fn(self._h, ptr, n, C.byref(n_cells), C.byref(n_refs), _ptr(summary)))
+        rows = {"cells": n_cells.value, "refs": n_refs.value, "segs": K}
+        out = {name: np.zeros(rows[tab], dtype=dt) for name, dt, tab in self.COMPARE_FIELDS}
+        self._ck(self._L.vgs_get_label_comparison(self._h, *(_ptr(out[name]) for name, _, _ in self.COMPARE_FIELDS)))
+        out["summary"] = summary
+        return out
+
+    def label_comparison_device(self):
+        """The tables of the last compare_labels left in HBM: {field: device pointer, None for a table without rows}, valid until the next
+        compare or the next run."""
+        ps = [C.c_void_p() for _ in self.COMPARE_FIELDS]
+        self._ck(self._L.vgs_get_label_comparison_device(self._h, *(C.byref(p) for p in ps)))
+        return {name: p.value for (name, _, _), p in zip(self.COMPARE_FIELDS, ps)}
+
     # ---- a sequence of clouds: uploads of the next cloud and downloads of the last labels overlap the stages
     def stage_points(self, xyz):
         """Start the copy of the NEXT cloud (ideally a pinned array, see pinned_empty) and return at once."""
@@ -549,6 +612,13 @@ class VoxelBasedSegmentation:
             return {name: np.zeros((0, int(n_classes)) if w == 0 else 0, dtype=dt) for name, dt, w in Engine.CLASS_HIST_FIELDS}
         return self._eng.segment_class_histogram(classes, n_classes)
 
+    def compareClusterLabels(self, ref):
+        """Extension (no VS line): the clusters against a reference labelling; row i of the cluster table belongs to getClusterIdx()[i]
+        (Engine.compare_labels).  Empty tables and a zero summary before drawColorMapofPointsinClusters."""
+        if not self._drawn:
+            return dict({name: np.zeros(0, dtype=dt) for name, dt, _ in Engine.COMPARE_FIELDS}, summary=np.zeros(12, np.int64))
+        return self._eng.compare_labels(ref)
+
     @property
     def engine(self):
         return self._eng
@@ -640,6 +710,11 @@ class SuperVoxelBasedSegmentation:
     def getClusterClassHistogram(self, classes, n_classes):
         """Extension (no SS line): row i counts `classes` over getClusterIdx()[i] -- both are in label order (Engine.segment_class_histogram)."""
         return self._eng.segment_class_histogram(classes, n_classes)
+
+    def compareClusterLabels(self, ref):
+        """Extension (no SS line): the clusters against a reference labelling; row i of the cluster table belongs to getClusterIdx()[i]
+        (Engine.compare_labels)."""
+        return self._eng.compare_labels(ref)
 
     @property
     def engine(self):

@@ -309,6 +309,19 @@ struct vgs_ctx {
   DevBuf<uint32_t> sg_nunk;
   bool sg_halo_valid = false;
   int64_t sg_own_K = -1;   // the key space of the tile table the sg_* outputs hold (-1: none)
+  // comparison with a caller's labelling (segcompare.hip): the cells, the reference table and the segment table of the last
+  // vgs_compare_labels, valid until the next compare or the next run (cmp_valid).  cmp_ref the host variant's upload; keys, flags, scans,
+  // sorts and run starts their own scratch.  Several arrays share a buffer: cell_seg | cell_ref at a stride of cmp_ann, ref_id |
+  // ref_best_seg and ref_points | ref_dropped | ref_best_n at a stride of cmp_cells, seg_annotated | seg_best_n and seg_refs |
+  // seg_best_ref at a stride of max(cmp_K, 1)
+  DevBuf<int32_t> cmp_ref, cmp_cell_i32, cmp_ref_i32, cmp_seg_i32;
+  DevBuf<int64_t> cmp_cell_n, cmp_ref_i64, cmp_seg_i64;
+  DevBuf<double> cmp_ref_iou, cmp_seg_iou;
+  DevBuf<uint64_t> cmp_key, cmp_meta;
+  DevBuf<uint32_t> cmp_work, cmp_cstart, cmp_rowstart, cmp_rsort, cmp_rstart;
+  DevBuf<uint8_t> cmp_tmp;
+  int64_t cmp_ann = 0, cmp_cells = 0, cmp_refs = 0, cmp_K = 0, cmp_summary[12] = {0};
+  bool cmp_valid = false;
   DevBuf<uint64_t> counters;  // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 
