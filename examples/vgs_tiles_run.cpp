@@ -20,8 +20,12 @@
 //   the table in the CSV format of vgs_run --segment-fields, the channels named f0 .. f{C-1}.
 //   --segment-classes <file.csv> --classes <C>: rank r reads <prefix>.<r>.classes.i32 (one int32 per point), every rank takes part in
 //   vgs_tiles_segment_class_histogram and rank 0 writes the table in the CSV format of vgs_run --segment-classes.
+//   --segment-matches <file.csv> [--truth-matches <file.csv>]: rank r reads <prefix>.<r>.truth.i32 (one int32 reference id per point,
+//   negative = not annotated), every rank takes part in vgs_tiles_compare_labels (a collective; no label and no id leaves its rank, only
+//   contingency cells) and rank 0 writes the per-segment matches, and with --truth-matches the per-id matches, in the CSV formats of
+//   vgs_run --segment-matches / --truth-matches.
 //   All of them can be combined.  A missing companion option, a value out of range (1 .. 64 channels, 1 .. 1024 classes) and an attribute
-//   file whose size does not match the rank's points are usage errors: exit status 2, before any collective.
+//   or truth file that is missing or whose size does not match the rank's points are usage errors: exit status 2, before any collective.
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <sys/socket.h>
@@ -83,6 +87,7 @@ struct Job {
   vgs_params p; int tx, ty; double pitch; std::string prefix, segments, graph, boxes; int box_frame = VGS_BOX_PRINCIPAL;
   std::string fields, classes;        // --segment-fields / --segment-classes
   int field_channels = 0, n_classes = 0;
+  std::string matches, truth_matches;   // --segment-matches / --truth-matches
 };
 
 static std::string rank_file(const Job& J, int rank, const char* suffix) { return J.prefix + "." + std::to_string(rank) + suffix; }
@@ -106,6 +111,12 @@ static int check_attribute_files(const Job& J, int rank) {
     const long long b = file_bytes(path);
     if (b != n * 4) { std::fprintf(stderr, "%s: %lld bytes, but %lld points x 4 = %lld\n", path.c_str(), b, n, n * 4); return 2; }
   }
+  if (!J.matches.empty()) {
+    const std::string path = rank_file(J, rank, ".truth.i32");
+    const long long b = file_bytes(path);
+    if (b < 0) { std::fprintf(stderr, "%s: cannot be read; --segment-matches needs one int32 for each of the %lld points of rank %d\n", path.c_str(), n, rank); return 2; }
+    if (b != n * 4) { std::fprintf(stderr, "%s: %lld bytes, but %lld points x 4 = %lld\n", path.c_str(), b, n, n * 4); return 2; }
+  }
   return 0;
 }
 
@@ -117,6 +128,8 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
   std::vector<int32_t> cls;
   if (!J.fields.empty() && !read_f32(rank_file(J, rank, ".fields.f32"), field)) { *err = "cannot read the fields of rank " + std::to_string(rank); return 1; }
   if (!J.classes.empty() && !read_i32(rank_file(J, rank, ".classes.i32"), cls)) { *err = "cannot read the classes of rank " + std::to_string(rank); return 1; }
+  std::vector<int32_t> truth;
+  if (!J.matches.empty() && !read_i32(rank_file(J, rank, ".truth.i32"), truth)) { *err = "cannot read the truth ids of rank " + std::to_string(rank); return 1; }
   vgs_tiles* t = nullptr;
   vgs_status s = vgs_tiles_create(&J.p, comm_kind, comm, rank, world, J.tx, J.ty, J.pitch, 0.0, 0.0, &t);
   if (s != VGS_OK) { *err = std::string("vgs_tiles_create: ") + vgs_last_error_string(nullptr); return 1; }
@@ -234,6 +247,28 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
       if (writeClassHistCsv(J.classes, J.n_classes, hist) != 0) { *err = "cannot write " + J.classes; rc = 1; }
     }
   }
+  if (rc == 0 && !J.matches.empty()) {
+    // the score against this rank's reference ids over the global segments: a collective of every rank, the same tables on each
+    int64_t K = 0, nc = 0, G = 0;
+    pcl::ClusterLabelComparison m;
+    if (vgs_tiles_compare_labels(t, truth.data(), n, &K, &nc, &G, m.summary) != VGS_OK) {
+      *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+      rc = 1;
+    } else if (rank == 0) {
+      m.cell_seg.resize((size_t)nc); m.cell_ref.resize((size_t)nc); m.cell_n.resize((size_t)nc);
+      m.ref_id.resize((size_t)G); m.ref_points.resize((size_t)G); m.ref_dropped.resize((size_t)G); m.ref_best_seg.resize((size_t)G);
+      m.ref_best_n.resize((size_t)G); m.ref_best_iou.resize((size_t)G);
+      m.seg_annotated.resize((size_t)K); m.seg_refs.resize((size_t)K); m.seg_best_ref.resize((size_t)K); m.seg_best_n.resize((size_t)K);
+      m.seg_best_iou.resize((size_t)K);
+      if (vgs_tiles_get_label_comparison(t, m.cell_seg.data(), m.cell_ref.data(), m.cell_n.data(), m.ref_id.data(), m.ref_points.data(), m.ref_dropped.data(),
+                                         m.ref_best_seg.data(), m.ref_best_n.data(), m.ref_best_iou.data(), m.seg_annotated.data(), m.seg_refs.data(),
+                                         m.seg_best_ref.data(), m.seg_best_n.data(), m.seg_best_iou.data()) != VGS_OK) {
+        *err = std::string("rank 0: ") + vgs_tiles_last_error_string(t);
+        rc = 1;
+      } else if (writeSegmentMatchesCsv(J.matches, m) != 0) { *err = "cannot write " + J.matches; rc = 1; }
+      else if (!J.truth_matches.empty() && writeTruthMatchesCsv(J.truth_matches, m) != 0) { *err = "cannot write " + J.truth_matches; rc = 1; }
+    }
+  }
   if (rc == 0) {
     labels.resize((size_t)n);
     if (!write_i32(J.prefix + "." + std::to_string(rank) + ".labels.i32", labels)) { *err = "cannot write the labels"; rc = 1; }
@@ -308,16 +343,19 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--field-channels") && a + 1 < argc) { J.field_channels = std::atoi(argv[++a]); have_channels = true; }
     else if (!std::strcmp(argv[a], "--segment-classes") && a + 1 < argc) J.classes = argv[++a];
     else if (!std::strcmp(argv[a], "--classes") && a + 1 < argc) { J.n_classes = std::atoi(argv[++a]); have_classes = true; }
+    else if (!std::strcmp(argv[a], "--segment-matches") && a + 1 < argc) J.matches = argv[++a];
+    else if (!std::strcmp(argv[a], "--truth-matches") && a + 1 < argc) J.truth_matches = argv[++a];
     else if (argv[a][0] != '-') J.prefix = argv[a];
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
-  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] <prefix>\n", argv[0]); return 2; }
+  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] <prefix>\n", argv[0]); return 2; }
   if (!J.fields.empty() && !have_channels) { std::fprintf(stderr, "--segment-fields needs --field-channels <C>\n"); return 2; }
   if (J.fields.empty() && have_channels) { std::fprintf(stderr, "--field-channels needs --segment-fields <file.csv>\n"); return 2; }
   if (have_channels && (J.field_channels < 1 || J.field_channels > 64)) { std::fprintf(stderr, "--field-channels must be in 1 .. 64\n"); return 2; }
   if (!J.classes.empty() && !have_classes) { std::fprintf(stderr, "--segment-classes needs --classes <C>\n"); return 2; }
   if (J.classes.empty() && have_classes) { std::fprintf(stderr, "--classes needs --segment-classes <file.csv>\n"); return 2; }
   if (have_classes && (J.n_classes < 1 || J.n_classes > 1024)) { std::fprintf(stderr, "--classes must be in 1 .. 1024\n"); return 2; }
+  if (J.matches.empty() && !J.truth_matches.empty()) { std::fprintf(stderr, "--truth-matches needs --segment-matches <file.csv>\n"); return 2; }
   const int world = J.tx * J.ty;
   int64_t kept = 0, n_pts = 0, n_rec = 0;
   if (mode == 1) {

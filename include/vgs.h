@@ -420,7 +420,9 @@ vgs_status vgs_segment_class_histogram_device(vgs_ctx* ctx, const int32_t* cls_d
  * compare or the next run of the stages.  Both answer VGS_E_STATE when there is no comparison since the last run of the stages or the last
  * vgs_set_points.
  * VGS_E_ARG, the message naming the argument, for n != counts[VGS_N_POINTS] and for a NULL ref with n > 0; VGS_E_STATE before the context
- * is segmented and for a tile context.  No side effects: labels, descriptors, boxes, graph and every other cached table stay as they are. */
+ * is segmented and for a tile context (a tile holds only part of its segments: the tiled driver scores over all ranks with
+ * vgs_tiles_compare_labels, include/vgs_tiles.h, from the two calls further down).  No side effects: labels, descriptors, boxes, graph and
+ * every other cached table stay as they are. */
 vgs_status vgs_compare_labels(vgs_ctx* ctx, const int32_t* ref_host, int64_t n, int64_t* n_cells, int64_t* n_refs, int64_t* summary /* 12 */);
 vgs_status vgs_compare_labels_device(vgs_ctx* ctx, const int32_t* ref_dev, int64_t n, int64_t* n_cells, int64_t* n_refs, int64_t* summary /* 12 */);
 vgs_status vgs_get_label_comparison(vgs_ctx* ctx, int32_t* cell_seg, int32_t* cell_ref, int64_t* cell_n, int32_t* ref_id, int64_t* ref_points,
@@ -465,6 +467,35 @@ vgs_status vgs_get_own_segment_class_counts(vgs_ctx* ctx, int64_t K, const int32
                                             int64_t* n_records, int32_t* label, int64_t* hist, int64_t* n_outside);
 vgs_status vgs_get_own_segment_class_counts_device(vgs_ctx* ctx, int64_t K, const int32_t* cls_dev, int64_t n_own, int32_t n_classes,
                                                    int64_t* n_records, int32_t* label, int64_t* hist, int64_t* n_outside);
+/* Contingency cells of a tile context (the tiled driver: vgs_tiles_compare_labels builds the global comparison from them).  No label and no
+ * reference id travels between ranks: a rank hands in one int32 per point of its OWN load, in the order it gave them to the driver -- ref[i]
+ * belongs to cloud point own_first + i of vgs_set_own_point_range, so n_own must equal that range's length -- and its label is the point
+ * label of that point, global after vgs_apply_tile_labels (-1 .. K-1).  The result is the cells of vgs_compare_labels over the own
+ * annotated points only: one per distinct pair (L, g), ascending (L, g), the L = -1 row first, with the number of own points of the pair;
+ * *n_cells of them and *n_unannotated own points with ref < 0 (either may be NULL).  They stay in the context until
+ * vgs_get_own_label_cells copies them (arrays of *n_cells rows, any may be NULL) or until the next comparison of any kind, the next run of
+ * the stages or new labels; VGS_E_STATE from the getter then.  The call discards an earlier comparison of the context (the buffers are the
+ * same) and touches no other table.  The device variant reads ref_dev in place.
+ * VGS_E_STATE before the context is segmented and for a context that is not a tile context; VGS_E_ARG for a wrong n_own, a NULL ref with
+ * n_own > 0, K outside 0 .. 2^31 - 1 and an own point whose label is not below K. */
+vgs_status vgs_own_label_cells(vgs_ctx* ctx, int64_t K, const int32_t* ref_host, int64_t n_own, int64_t* n_cells, int64_t* n_unannotated);
+vgs_status vgs_own_label_cells_device(vgs_ctx* ctx, int64_t K, const int32_t* ref_dev, int64_t n_own, int64_t* n_cells, int64_t* n_unannotated);
+vgs_status vgs_get_own_label_cells(vgs_ctx* ctx, int32_t* cell_seg, int32_t* cell_ref, int64_t* cell_n);
+/* The comparison tables from a list of cells instead of points: n_in host cells (seg, ref, n) in ANY order and with ANY number of entries
+ * for one pair -- the lists of several ranks one after another.  On this context's GPU: the merged cells (one per distinct pair, ascending
+ * (seg, ref), cell_n the int64 sum of the pair's entries), then the reference table, the segment table of K rows and the summary of
+ * vgs_compare_labels by the same kernels; summary[0] = the sum of all counts, summary[1] = n_unannotated as passed in, summary[8] over the
+ * merged cells.  Integer adds only, so the order of the input does not matter.  The tables become the context's last comparison:
+ * vgs_get_label_comparison[_device] hand them out until the next compare, the next run of the stages or vgs_set_points.  n_cells, n_refs
+ * and summary may be NULL.  n_in = 0 gives the tables of "no annotated point".  Works on any segmented context, tile or not; K is the
+ * caller's (kept_global in the driver), not the context's own count.
+ * VGS_E_ARG, the message naming the first offending input with its values, for a seg outside -1 .. K-1, a negative ref or a count below 1
+ * (found on the device in one pass, before anything is built), and for K outside 0 .. 2^31 - 1, a negative n_in or n_unannotated and a NULL
+ * array with n_in > 0.  VGS_E_UNSUPPORTED, with the numbers, for n_in >= 2^31 and for counts that add up to more than 2^32 (so that
+ * C(total, 2) fits int64).  VGS_E_STATE before the context is segmented.  After an error the context holds no comparison. */
+vgs_status vgs_label_comparison_from_cells(vgs_ctx* ctx, int64_t K, int64_t n_in, const int32_t* cell_seg, const int32_t* cell_ref,
+                                           const int64_t* cell_n, int64_t n_unannotated, int64_t* n_cells, int64_t* n_refs,
+                                           int64_t* summary /* 12 */);
 
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.

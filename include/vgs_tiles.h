@@ -15,6 +15,7 @@
  * on request: a third collective of its own (vgs_tiles_get_segment_graph).  Oriented boxes on request: the descriptor table (its collective,
  * unless it is cached) and one collective of their own per frame (vgs_tiles_get_segment_boxes).  Statistics of the caller's point
  * attributes on request: one collective per call, nothing cached (vgs_tiles_segment_field_stats, vgs_tiles_segment_class_histogram).
+ * The score against the caller's reference labels on request: one collective per call, nothing cached (vgs_tiles_compare_labels).
  */
 #ifndef VGS_TILES_H_
 #define VGS_TILES_H_
@@ -254,6 +255,40 @@ vgs_status vgs_tiles_fold_field_moments(int world, const int64_t* rec_off, const
 vgs_status vgs_tiles_fold_class_counts(int world, const int64_t* rec_off, const int32_t* label, int32_t n_classes, const int64_t* hist,
                                        const int64_t* n_outside, int64_t K, int64_t* hist_out, int64_t* n_outside_out, int32_t* majority_out,
                                        int64_t* majority_count_out);
+/* Score the segmentation against reference labels the CALLER supplies, over all ranks: the tables, fields, types, tie rules and summary of
+ * vgs_compare_labels (include/vgs.h) with K = kept_global segment rows, over the points of all ranks -- byte for byte what one context
+ * would give on the gathered points.  `ref` holds one int32 per point the rank gave to vgs_tiles_set_points, in that order (negative = not
+ * annotated); n must equal that call's n.  *K, *n_cells, *n_refs and summary[12] may be NULL.  The _device variant reads ref from HBM in
+ * place (this rank's device, complete before the call).
+ * Protocol (csrc/tiles.cpp).  Every point is counted by the rank that loaded it; no label and no reference id travels, only cells
+ * (L, g, n): the rank's cells over its own points (vgs_own_label_cells, one small pipeline on its GPU) -> ONE all_gather_varlen of int64
+ * words: a header of status word, own cell count and own unannotated count, then per cell two words, (L + 1) << 32 | g and n -- 16 bytes
+ * per cell -> the lists of all ranks, in rank order, are merged on the rank's GPU and the three tables and the summary are built there
+ * (vgs_label_comparison_from_cells with the summed unannotated count); there is no host fold.  Every rank receives the same bytes.
+ * Nothing is cached, because the input is the caller's: EVERY call is collective -- after one vgs_tiles_run every rank makes it -- and
+ * makes exactly ONE all_gather_varlen.  vgs_tiles_run gains no launch and no collective; labels, descriptors, graph, boxes and attribute
+ * tables are not touched.  One consequence of exchanging cells: a reference with one id per point has one cell per point, so the
+ * exchange is then as large as the points themselves.  That is the caller's choice of ids, not a defect.
+ * vgs_tiles_get_label_comparison copies the tables of the last tiled compare from the rank's context (the fourteen arrays of
+ * vgs_get_label_comparison, sizes as the compare returned them, K rows for the segment table; any may be NULL).  It is not collective.
+ * VGS_E_STATE when there is no compare since the last run or the last vgs_tiles_set_points.
+ * Failures.  VGS_E_STATE before a run is decided locally (no collective).  Everything a rank can get wrong on its own -- a wrong n, a NULL
+ * ref with n > 0, a failing context call, the injected VGS_TILES_FAIL_AT=compare -- travels in the status word, so no peer waits: the
+ * failing rank returns its own status and message, the others VGS_E_PEER naming it. */
+vgs_status vgs_tiles_compare_labels(vgs_tiles* t, const int32_t* ref_host, int64_t n, int64_t* K, int64_t* n_cells, int64_t* n_refs,
+                                    int64_t* summary /* 12 */);
+vgs_status vgs_tiles_compare_labels_device(vgs_tiles* t, const int32_t* ref_dev, int64_t n, int64_t* K, int64_t* n_cells, int64_t* n_refs,
+                                           int64_t* summary /* 12 */);
+vgs_status vgs_tiles_get_label_comparison(vgs_tiles* t, int32_t* cell_seg, int32_t* cell_ref, int64_t* cell_n, int32_t* ref_id,
+                                          int64_t* ref_points, int64_t* ref_dropped, int32_t* ref_best_seg, int64_t* ref_best_n,
+                                          double* ref_best_iou, int64_t* seg_annotated, int32_t* seg_refs, int32_t* seg_best_ref,
+                                          int64_t* seg_best_n, double* seg_best_iou);
+/* host wall time of the last tiled compare on this rank, milliseconds: own cells on the GPU (with upload and download), the exchange, the
+ * tables on the GPU (with the upload of the gathered cells), total */
+enum { VGS_TILES_C_OWN = 0, VGS_TILES_C_EXCHANGE = 1, VGS_TILES_C_TABLES = 2, VGS_TILES_C_TOTAL = 3, VGS_TILES_C_COUNT = 4 };
+vgs_status vgs_tiles_get_compare_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_C_COUNT */);
+/* that compare's payload on this rank: cells of its own, bytes it put into the all-gather (header included, before padding) */
+vgs_status vgs_tiles_get_compare_payload(vgs_tiles* t, int64_t* own_cells, int64_t* bytes_sent);
 /* the rank's engine context (read-only use: counts, stage times) */
 vgs_ctx* vgs_tiles_context(vgs_tiles* t);
 

@@ -114,6 +114,10 @@ SYMBOLS = [
     ("vgs_compare_labels_device", C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
     ("vgs_get_label_comparison", C.c_int, [_P] + [_P] * 14),
     ("vgs_get_label_comparison_device", C.c_int, [_P] + [_P] * 14),
+    ("vgs_own_label_cells", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("vgs_own_label_cells_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("vgs_get_own_label_cells", C.c_int, [_P, _P, _P, _P]),
+    ("vgs_label_comparison_from_cells", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P]),
     ("vgs_get_own_segment_field_moments", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_own_segment_field_moments_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_segment_field_stats_from_moments", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -465,6 +465,29 @@ class Engine:
         out["summary"] = summary
         return out
 
+    def label_comparison_from_cells(self, cell_seg, cell_ref, cell_n, n_unannotated=0, K=None):
+        """The dict of compare_labels() from a list of contingency cells instead of points (include/vgs.h,
+        vgs_label_comparison_from_cells): cell_seg, cell_ref (int32) and cell_n (int64) of equal length, in any order and with any number
+        of entries for one (segment, id) pair -- the lists several ranks counted over their own points, one after another.  The cells are
+        merged and the tables built on the device; integer adds only, so the order of the input does not matter.  summary[1] =
+        n_unannotated.  K: the number of segment rows, the engine's own kept count by default.  The tables become the engine's last
+        comparison (label_comparison_device())."""
+        K = self.counts()["kept"] if K is None else int(K)
+        seg = np.ascontiguousarray(np.asarray(cell_seg, dtype=np.int32).reshape(-1))
+        ref = np.ascontiguousarray(np.asarray(cell_ref, dtype=np.int32).reshape(-1))
+        cnt = np.ascontiguousarray(np.asarray(cell_n, dtype=np.int64).reshape(-1))
+        if not (seg.shape == ref.shape == cnt.shape):
+            raise ValueError("cell_seg, cell_ref and cell_n must have the same length")
+        n_cells, n_refs = C.c_int64(0), C.c_int64(0)
+        summary = np.zeros(12, np.int64)
+        self._ck(self._L.vgs_label_comparison_from_cells(self._h, K, seg.shape[0], _ptr(seg), _ptr(ref), _ptr(cnt), int(n_unannotated),
+                                                         C.byref(n_cells), C.byref(n_refs), _ptr(summary)))
+        rows = {"cells": n_cells.value, "refs": n_refs.value, "segs": K}
+        out = {name: np.zeros(rows[tab], dtype=dt) for name, dt, tab in self.COMPARE_FIELDS}
+        self._ck(self._L.vgs_get_label_comparison(self._h, *(_ptr(out[name]) for name, _, _ in self.COMPARE_FIELDS)))
+        out["summary"] = summary
+        return out
+
     def label_comparison_device(self):
         """The tables of the last compare_labels left in HBM: {field: device pointer, None for a table without rows}, valid until the next
         compare or the next run."""

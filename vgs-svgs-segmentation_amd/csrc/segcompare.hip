@@ -15,6 +15,18 @@
 //   6. k_cmp_seg_iou (a search of the best id per segment) and the summary sums, kept per wavefront and added once -> read-back 4
 // A row and an id of any number of cells are read in chunks of 64 (the lane-stride loops).  Positions are uint32: N < 2^31.
 // Scratch: own buffers only (cmp_*); labels, descriptors, boxes and graph are read-only here.
+//
+// The tiled driver (include/vgs_tiles.h) runs the two halves on different inputs.  Steps 1-3 over a rank's OWN points only
+// (vgs_own_label_cells: k_cmp_scan_own is step 1 with the largest label beside the largest id, so that a label not below K is refused
+// before a key is made), and steps 4-6 from a cell list that did not come from this context's points
+// (vgs_label_comparison_from_cells).  That list -- the ranks' lists one after another -- holds a pair once per rank that saw it, so it is
+// merged first, by the pipeline of steps 1-3 one level up:
+//   a. k_cmp_cells_scan   one pass over the input cells: the largest id, the sum of the counts and the FIRST input that is not a cell
+//                         (a segment outside -1 .. K-1, a negative id, a count below 1), at most three atomics per workgroup -> read-back
+//   b. k_cmp_cells_keys   key = (seg + 1) << gbits | ref
+//   c. rocprim::radix_sort_pairs of (key, count) over gbits + bits(K) bits; heads, inclusive scan, k_cmp_cell_starts as in step 3
+//   d. k_cmp_cells_sums   one thread per merged cell walks its run and adds the int64 counts (integers: any order gives the same bits),
+//                         and C(cell_n, 2) of the MERGED cell goes into the summary
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -32,7 +44,7 @@
 
 // slots of cmp_meta (uint64 each)
 enum { CM_UNANN = 0, CM_MAXID = 1, CM_NCELLS = 2, CM_NREFS = 3, CM_SEGS = 4, CM_SEGBEST = 5, CM_REFBEST = 6, CM_PAIRS_CELL = 7, CM_PAIRS_ROW = 8,
-       CM_PAIRS_REF = 9, CM_DROPPED = 10, CM_SLOTS = 16 };
+       CM_PAIRS_REF = 9, CM_DROPPED = 10, CM_TOTAL = 11, CM_BAD = 12, CM_MAXLAB = 13, CM_SLOTS = 16 };
 
 typedef unsigned long long cmp_u64;
 
@@ -98,6 +110,89 @@ __global__ __launch_bounds__(CMP_TB) void k_cmp_cell_counts(const uint32_t* __re
   for (uint32_t i = blockIdx.x * CMP_TB + threadIdx.x; i < n_cells; i += gridDim.x * CMP_TB) {
     const uint32_t e = i + 1 < n_cells ? cstart[i + 1] : n_ann;
     const cmp_u64 n = e - cstart[i];
+    cell_n[i] = (long long)n;
+    acc += cmp_pairs(n);
+  }
+  acc = cmp_wave_sum(acc);
+  if ((threadIdx.x & 63) == 0 && acc) atomicAdd(&meta[CM_PAIRS_CELL], acc);
+}
+
+// step 1 over a rank's own points (labels = pt_label + own_first, beside ref): the largest label + 1 as well, for the check against K
+__global__ __launch_bounds__(CMP_TB) void k_cmp_scan_own(const int32_t* __restrict__ labels, const int32_t* __restrict__ ref, int64_t N,
+                                                         cmp_u64* __restrict__ meta) {
+  __shared__ cmp_u64 s_un[CMP_WAVES], s_mx[CMP_WAVES], s_ml[CMP_WAVES];
+  cmp_u64 un = 0, mx = 0, ml = 0;
+  for (int64_t i = (int64_t)blockIdx.x * CMP_TB + threadIdx.x; i < N; i += (int64_t)gridDim.x * CMP_TB) {
+    const int32_t g = ref[i];
+    const int32_t l = labels[i];
+    if (g < 0) ++un; else if ((cmp_u64)g > mx) mx = (cmp_u64)g;
+    if (l >= 0 && (cmp_u64)l + 1 > ml) ml = (cmp_u64)l + 1;
+  }
+  un = cmp_wave_sum(un);
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const cmp_u64 o = __shfl_xor(mx, m, 64); mx = o > mx ? o : mx;
+    const cmp_u64 p = __shfl_xor(ml, m, 64); ml = p > ml ? p : ml;
+  }
+  if ((threadIdx.x & 63) == 0) { s_un[threadIdx.x >> 6] = un; s_mx[threadIdx.x >> 6] = mx; s_ml[threadIdx.x >> 6] = ml; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int w = 1; w < CMP_WAVES; ++w) { un += s_un[w]; mx = s_mx[w] > mx ? s_mx[w] : mx; ml = s_ml[w] > ml ? s_ml[w] : ml; }
+  if (un) atomicAdd(&meta[CM_UNANN], un);
+  if (mx) atomicMax(&meta[CM_MAXID], mx);
+  if (ml) atomicMax(&meta[CM_MAXLAB], ml);
+}
+
+// One pass over n_in input cells.  A count is clamped to 2^32 + 1 before it is added, so that 2^31 of them cannot wrap the sum and a total
+// above the limit of 2^32 is still seen as one.  CM_BAD holds n_in - i for the first input i that is not a cell, 0 when all are.
+#define CMP_COUNT_CLAMP 0x100000001ull
+__global__ __launch_bounds__(CMP_TB) void k_cmp_cells_scan(const int32_t* __restrict__ seg, const int32_t* __restrict__ ref,
+                                                           const long long* __restrict__ cnt, uint32_t n_in, uint32_t K,
+                                                           cmp_u64* __restrict__ meta) {
+  __shared__ cmp_u64 s_tot[CMP_WAVES], s_mx[CMP_WAVES], s_bad[CMP_WAVES];
+  cmp_u64 tot = 0, mx = 0, bad = 0;
+  for (uint32_t i = blockIdx.x * CMP_TB + threadIdx.x; i < n_in; i += gridDim.x * CMP_TB) {
+    const int32_t s = seg[i], g = ref[i];
+    const long long n = cnt[i];
+    if (s < -1 || (int64_t)s >= (int64_t)K || g < 0 || n < 1) {
+      const cmp_u64 b = (cmp_u64)(n_in - i);
+      if (b > bad) bad = b;
+      continue;
+    }
+    if ((cmp_u64)g > mx) mx = (cmp_u64)g;
+    tot += (cmp_u64)n < CMP_COUNT_CLAMP ? (cmp_u64)n : CMP_COUNT_CLAMP;
+  }
+  tot = cmp_wave_sum(tot);
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const cmp_u64 o = __shfl_xor(mx, m, 64); mx = o > mx ? o : mx;
+    const cmp_u64 p = __shfl_xor(bad, m, 64); bad = p > bad ? p : bad;
+  }
+  if ((threadIdx.x & 63) == 0) { s_tot[threadIdx.x >> 6] = tot; s_mx[threadIdx.x >> 6] = mx; s_bad[threadIdx.x >> 6] = bad; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int w = 1; w < CMP_WAVES; ++w) { tot += s_tot[w]; mx = s_mx[w] > mx ? s_mx[w] : mx; bad = s_bad[w] > bad ? s_bad[w] : bad; }
+  if (tot) atomicAdd(&meta[CM_TOTAL], tot);
+  if (mx) atomicMax(&meta[CM_MAXID], mx);
+  if (bad) atomicMax(&meta[CM_BAD], bad);
+}
+
+__global__ __launch_bounds__(CMP_TB) void k_cmp_cells_keys(const int32_t* __restrict__ seg, const int32_t* __restrict__ ref, uint32_t n_in,
+                                                           uint32_t gbits, uint64_t* __restrict__ key) {
+  const uint32_t i = blockIdx.x * CMP_TB + threadIdx.x;
+  if (i >= n_in) return;
+  key[i] = ((uint64_t)(uint32_t)(seg[i] + 1) << gbits) | (uint64_t)(uint32_t)ref[i];
+}
+
+// the merged cell i = the run [cstart[i], cstart[i + 1]) of the sorted input cells: its count is the sum of theirs
+__global__ __launch_bounds__(CMP_TB) void k_cmp_cells_sums(const uint32_t* __restrict__ cstart, uint32_t n_cells, uint32_t n_in,
+                                                           const long long* __restrict__ cnt, long long* __restrict__ cell_n,
+                                                           cmp_u64* __restrict__ meta) {
+  cmp_u64 acc = 0;
+  for (uint32_t i = blockIdx.x * CMP_TB + threadIdx.x; i < n_cells; i += gridDim.x * CMP_TB) {
+    const uint32_t e = i + 1 < n_cells ? cstart[i + 1] : n_in;
+    cmp_u64 n = 0;
+    for (uint32_t j = cstart[i]; j < e; ++j) n += (cmp_u64)cnt[j];
     cell_n[i] = (long long)n;
     acc += cmp_pairs(n);
   }
@@ -259,33 +354,16 @@ static vgs_status cmp_check(vgs_ctx* c, const char* fn, const int32_t* ref, int6
   return VGS_OK;
 }
 
-// the three tables from a device labelling into the cmp_* buffers; sizes and summary into the context
-static vgs_status cmp_build(vgs_ctx* c, const int32_t* ref_dev) {
-  c->cmp_valid = false;
-  const int64_t N = c->N, K = c->counts[VGS_N_KEPT];
-  c->cmp_cells = 0; c->cmp_refs = 0; c->cmp_K = K;
-  for (int i = 0; i < 12; ++i) c->cmp_summary[i] = 0;
-  if (N == 0) { c->cmp_K = 0; c->cmp_valid = true; return VGS_OK; }
-  VGS_HIP_TRY(c, c->cmp_meta.ensure(CM_SLOTS));
-  cmp_u64* meta = (cmp_u64*)c->cmp_meta.p;
-  VGS_HIP_TRY(c, hipMemsetAsync(meta, 0, CM_SLOTS * sizeof(uint64_t), c->stream));
-  hipLaunchKernelGGL(k_cmp_scan, dim3(std::min(cmp_grid((uint64_t)N), CMP_SCAN_GRID)), dim3(CMP_TB), 0, c->stream, ref_dev, N, meta);
-  VGS_HIP_TRY(c, hipGetLastError());
-  uint64_t m[CM_SLOTS];
-  VGS_READBACK(c, m, meta, 2 * sizeof(uint64_t));   // read-back 1: unannotated points, the largest id
-  const uint32_t n_ann = (uint32_t)((uint64_t)N - m[CM_UNANN]);
-  const unsigned gbits = cmp_bits(m[CM_MAXID]);
-  const size_t k1 = (size_t)K > 0 ? (size_t)K : 1;
-  VGS_HIP_TRY(c, c->cmp_seg_i64.ensure(2 * k1)); VGS_HIP_TRY(c, c->cmp_seg_i32.ensure(2 * k1)); VGS_HIP_TRY(c, c->cmp_seg_iou.ensure(k1));
-  VGS_HIP_TRY(c, c->cmp_rowstart.ensure((size_t)K + 2));
-  long long *seg_ann = (long long*)c->cmp_seg_i64.p, *seg_bn = seg_ann + k1;
-  int32_t *seg_refs = c->cmp_seg_i32.p, *seg_br = seg_refs + k1;
-  uint32_t n_cells = 0, G = 0;
+// steps 2 and 3: the cells of N points (labels beside ref, both on the device) into cmp_cell_i32 (cell_seg | cell_ref at a stride of n_ann)
+// and cmp_cell_n, after step 1 gave n_ann and the largest id
+static vgs_status cmp_point_cells(vgs_ctx* c, const int32_t* labels_dev, const int32_t* ref_dev, int64_t N, int64_t K, uint32_t n_ann, unsigned gbits,
+                                  cmp_u64* meta, uint64_t* m, uint32_t& n_cells) {
+  n_cells = 0;
   if (n_ann > 0) {
     VGS_HIP_TRY(c, c->cmp_key.ensure(2 * (size_t)N)); VGS_HIP_TRY(c, c->cmp_work.ensure(2 * (size_t)n_ann));
     uint64_t *key_in = c->cmp_key.p, *key_out = key_in + N;
     uint32_t *head = c->cmp_work.p, *inc = head + n_ann;
-    hipLaunchKernelGGL(k_cmp_keys, dim3(cmp_grid((uint64_t)N)), dim3(CMP_TB), 0, c->stream, c->pt_label.p, ref_dev, N, gbits, (uint32_t)K, key_in);
+    hipLaunchKernelGGL(k_cmp_keys, dim3(cmp_grid((uint64_t)N)), dim3(CMP_TB), 0, c->stream, labels_dev, ref_dev, N, gbits, (uint32_t)K, key_in);
     const unsigned bits = gbits + cmp_bits((uint64_t)K + 1);   // rows 0 .. K + 1
     size_t t_sort = 0, t_scan = 0;
     VGS_HIP_TRY(c, rocprim::radix_sort_keys(nullptr, t_sort, key_in, key_out, (size_t)N, 0, bits, c->stream));
@@ -306,7 +384,21 @@ static vgs_status cmp_build(vgs_ctx* c, const int32_t* ref_dev) {
                        (long long*)c->cmp_cell_n.p, meta);
   }
   c->cmp_ann = n_ann;
-  const int32_t *cell_seg = c->cmp_cell_i32.p, *cell_ref = n_ann > 0 ? cell_seg + n_ann : nullptr;
+  return VGS_OK;
+}
+
+// steps 4 to 6: the segment table of K rows, the reference table and the summary from the n_cells cells in cmp_cell_i32 (at a stride of
+// `stride`) and cmp_cell_n, whichever pipeline left them there; `total` and `unann` are summary[0] and summary[1].  The tables become the
+// context's last comparison.
+static vgs_status cmp_cell_tables(vgs_ctx* c, int64_t K, uint32_t stride, uint32_t n_cells, unsigned gbits, int64_t total, int64_t unann, cmp_u64* meta,
+                                  uint64_t* m) {
+  const size_t k1 = (size_t)K > 0 ? (size_t)K : 1;
+  VGS_HIP_TRY(c, c->cmp_seg_i64.ensure(2 * k1)); VGS_HIP_TRY(c, c->cmp_seg_i32.ensure(2 * k1)); VGS_HIP_TRY(c, c->cmp_seg_iou.ensure(k1));
+  VGS_HIP_TRY(c, c->cmp_rowstart.ensure((size_t)K + 2));
+  long long *seg_ann = (long long*)c->cmp_seg_i64.p, *seg_bn = seg_ann + k1;
+  int32_t *seg_refs = c->cmp_seg_i32.p, *seg_br = seg_refs + k1;
+  uint32_t G = 0;
+  const int32_t *cell_seg = c->cmp_cell_i32.p, *cell_ref = stride > 0 ? cell_seg + stride : nullptr;
   const long long* cell_n = (const long long*)c->cmp_cell_n.p;
   hipLaunchKernelGGL(k_cmp_row_starts, dim3(cmp_grid((uint64_t)K + 2)), dim3(CMP_TB), 0, c->stream, cell_seg, n_cells, (uint32_t)K, c->cmp_rowstart.p);
   hipLaunchKernelGGL(k_cmp_seg_rows, dim3(cmp_fold_grid(((uint64_t)K + CMP_WAVES) / CMP_WAVES)), dim3(CMP_TB), 0, c->stream, c->cmp_rowstart.p, cell_ref,
@@ -315,7 +407,7 @@ static vgs_status cmp_build(vgs_ctx* c, const int32_t* ref_dev) {
   if (n_cells > 0) {
     VGS_HIP_TRY(c, c->cmp_rsort.ensure(4 * (size_t)n_cells));
     uint32_t *rk_in = c->cmp_rsort.p, *rk_out = rk_in + n_cells, *ri_in = rk_out + n_cells, *ri_out = ri_in + n_cells;
-    uint32_t *head = c->cmp_work.p, *inc = head + n_ann;   // (free again: n_cells <= n_ann)
+    uint32_t *head = c->cmp_work.p, *inc = head + stride;   // (free again: n_cells <= stride)
     hipLaunchKernelGGL(k_cmp_ref_keys, dim3(cmp_grid(n_cells)), dim3(CMP_TB), 0, c->stream, cell_ref, n_cells, rk_in, ri_in);
     size_t t_sort = 0, t_scan2 = 0;
     VGS_HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, t_sort, rk_in, rk_out, ri_in, ri_out, (size_t)n_cells, 0, gbits, c->stream));
@@ -342,12 +434,34 @@ static vgs_status cmp_build(vgs_ctx* c, const int32_t* ref_dev) {
   VGS_HIP_TRY(c, hipGetLastError());
   VGS_READBACK(c, m, meta, CM_SLOTS * sizeof(uint64_t));   // read-back 4: the summary sums
   int64_t* s = c->cmp_summary;
-  s[0] = (int64_t)n_ann; s[1] = (int64_t)m[CM_UNANN]; s[2] = (int64_t)m[CM_DROPPED]; s[3] = (int64_t)G; s[4] = (int64_t)n_cells;
+  s[0] = total; s[1] = unann; s[2] = (int64_t)m[CM_DROPPED]; s[3] = (int64_t)G; s[4] = (int64_t)n_cells;
   s[5] = (int64_t)m[CM_SEGS]; s[6] = (int64_t)m[CM_SEGBEST]; s[7] = (int64_t)m[CM_REFBEST]; s[8] = (int64_t)m[CM_PAIRS_CELL];
   s[9] = (int64_t)m[CM_PAIRS_ROW]; s[10] = (int64_t)m[CM_PAIRS_REF]; s[11] = 0;
   c->cmp_cells = n_cells; c->cmp_refs = G;
   c->cmp_valid = true;
   return VGS_OK;
+}
+
+// the three tables from a device labelling into the cmp_* buffers; sizes and summary into the context
+static vgs_status cmp_build(vgs_ctx* c, const int32_t* ref_dev) {
+  c->cmp_valid = false; c->cmp_own_cells = -1;
+  const int64_t N = c->N, K = c->counts[VGS_N_KEPT];
+  c->cmp_cells = 0; c->cmp_refs = 0; c->cmp_K = K;
+  for (int i = 0; i < 12; ++i) c->cmp_summary[i] = 0;
+  if (N == 0) { c->cmp_K = 0; c->cmp_valid = true; return VGS_OK; }
+  VGS_HIP_TRY(c, c->cmp_meta.ensure(CM_SLOTS));
+  cmp_u64* meta = (cmp_u64*)c->cmp_meta.p;
+  VGS_HIP_TRY(c, hipMemsetAsync(meta, 0, CM_SLOTS * sizeof(uint64_t), c->stream));
+  hipLaunchKernelGGL(k_cmp_scan, dim3(std::min(cmp_grid((uint64_t)N), CMP_SCAN_GRID)), dim3(CMP_TB), 0, c->stream, ref_dev, N, meta);
+  VGS_HIP_TRY(c, hipGetLastError());
+  uint64_t m[CM_SLOTS];
+  VGS_READBACK(c, m, meta, 2 * sizeof(uint64_t));   // read-back 1: unannotated points, the largest id
+  const uint32_t n_ann = (uint32_t)((uint64_t)N - m[CM_UNANN]);
+  const unsigned gbits = cmp_bits(m[CM_MAXID]);
+  uint32_t n_cells = 0;
+  vgs_status s = cmp_point_cells(c, c->pt_label.p, ref_dev, N, K, n_ann, gbits, meta, m, n_cells);
+  if (s != VGS_OK) return s;
+  return cmp_cell_tables(c, K, n_ann, n_cells, gbits, (int64_t)n_ann, (int64_t)m[CM_UNANN], meta, m);
 }
 
 static void cmp_report(vgs_ctx* c, int64_t* n_cells, int64_t* n_refs, int64_t* summary) {
@@ -378,6 +492,174 @@ extern "C" vgs_status vgs_compare_labels(vgs_ctx* c, const int32_t* ref_host, in
   }
   if ((s = cmp_build(c, c->cmp_ref.p)) != VGS_OK) return s;
   cmp_report(c, n_cells, n_refs, summary);
+  return VGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ tile contexts (include/vgs_tiles.h)
+static vgs_status cmp_own_check(vgs_ctx* c, const char* fn, int64_t K, const int32_t* ref, int64_t n_own) {
+  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
+  if (!c->have_region || c->n_own < 0) {
+    c->err = std::string(fn) + ": a tile context (vgs_set_owned_region and vgs_set_own_point_range) only";
+    return VGS_E_STATE;
+  }
+  if (K < 0 || K > (int64_t)0x7fffffff) { c->err = std::string(fn) + ": K = " + std::to_string(K) + " is out of range"; return VGS_E_ARG; }
+  if (n_own != c->n_own) {
+    c->err = std::string(fn) + ": n_own = " + std::to_string(n_own) + " must equal the number of own points of the context, " + std::to_string(c->n_own);
+    return VGS_E_ARG;
+  }
+  if (!ref && n_own > 0) { c->err = std::string(fn) + ": ref is NULL"; return VGS_E_ARG; }
+  if (c->own_first + n_own > c->N) {
+    c->err = std::string(fn) + ": the own point range ends at " + std::to_string(c->own_first + n_own) + ", the cloud holds " + std::to_string(c->N) + " points";
+    return VGS_E_ARG;
+  }
+  return VGS_OK;
+}
+
+// steps 1-3 over the own points: pt_label[own_first + i] beside ref[i].  The cells stay in cmp_cell_i32 / cmp_cell_n (cmp_own_cells of
+// them, at a stride of cmp_ann) until vgs_get_own_label_cells copies them or another comparison takes the buffers.
+static vgs_status cmp_own_cells(vgs_ctx* c, const char* fn, int64_t K, const int32_t* ref_dev, int64_t* n_cells_out, int64_t* n_unann) {
+  c->cmp_valid = false; c->cmp_own_cells = -1;
+  if (n_cells_out) *n_cells_out = 0;
+  if (n_unann) *n_unann = 0;
+  const int64_t N = c->n_own;
+  if (N == 0) { c->cmp_ann = 0; c->cmp_own_cells = 0; return VGS_OK; }
+  vgs_status s = vgs_ensure_point_labels(c);   // a tile's merge stage leaves the scatter to whoever asks first
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, c->cmp_meta.ensure(CM_SLOTS));
+  cmp_u64* meta = (cmp_u64*)c->cmp_meta.p;
+  const int32_t* labels = c->pt_label.p + c->own_first;
+  VGS_HIP_TRY(c, hipMemsetAsync(meta, 0, CM_SLOTS * sizeof(uint64_t), c->stream));
+  hipLaunchKernelGGL(k_cmp_scan_own, dim3(std::min(cmp_grid((uint64_t)N), CMP_SCAN_GRID)), dim3(CMP_TB), 0, c->stream, labels, ref_dev, N, meta);
+  VGS_HIP_TRY(c, hipGetLastError());
+  uint64_t m[CM_SLOTS];
+  VGS_READBACK(c, m, meta, CM_SLOTS * sizeof(uint64_t));   // unannotated points, the largest id, the largest label + 1
+  if ((int64_t)m[CM_MAXLAB] > K) {
+    c->err = std::string(fn) + ": an own point has label " + std::to_string((int64_t)m[CM_MAXLAB] - 1) + ", not below K = " + std::to_string(K);
+    return VGS_E_ARG;
+  }
+  const uint32_t n_ann = (uint32_t)((uint64_t)N - m[CM_UNANN]);
+  uint32_t n_cells = 0;
+  if ((s = cmp_point_cells(c, labels, ref_dev, N, K, n_ann, cmp_bits(m[CM_MAXID]), meta, m, n_cells)) != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // ref is the caller's again
+  c->cmp_own_cells = n_cells;
+  if (n_cells_out) *n_cells_out = n_cells;
+  if (n_unann) *n_unann = (int64_t)m[CM_UNANN];
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_own_label_cells_device(vgs_ctx* c, int64_t K, const int32_t* ref_dev, int64_t n_own, int64_t* n_cells, int64_t* n_unannotated) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = cmp_own_check(c, "vgs_own_label_cells_device", K, ref_dev, n_own);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  return cmp_own_cells(c, "vgs_own_label_cells_device", K, ref_dev, n_cells, n_unannotated);
+}
+
+extern "C" vgs_status vgs_own_label_cells(vgs_ctx* c, int64_t K, const int32_t* ref_host, int64_t n_own, int64_t* n_cells, int64_t* n_unannotated) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = cmp_own_check(c, "vgs_own_label_cells", K, ref_host, n_own);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  if (n_own > 0) {
+    VGS_HIP_TRY(c, c->cmp_ref.ensure((size_t)n_own));
+    VGS_HIP_TRY(c, hipMemcpyAsync(c->cmp_ref.p, ref_host, (size_t)n_own * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
+  }
+  return cmp_own_cells(c, "vgs_own_label_cells", K, c->cmp_ref.p, n_cells, n_unannotated);
+}
+
+extern "C" vgs_status vgs_get_own_label_cells(vgs_ctx* c, int32_t* cell_seg, int32_t* cell_ref, int64_t* cell_n) {
+  if (!c) return VGS_E_ARG;
+  if (c->cmp_own_cells < 0) {
+    c->err = "vgs_get_own_label_cells: no own cells (vgs_own_label_cells first; a comparison, a run of the stages or new labels discard them)";
+    return VGS_E_STATE;
+  }
+  const size_t nc = (size_t)c->cmp_own_cells, na = (size_t)c->cmp_ann;
+  if (nc == 0) return VGS_OK;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  if (cell_seg) VGS_HIP_TRY(c, hipMemcpyAsync(cell_seg, c->cmp_cell_i32.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (cell_ref) VGS_HIP_TRY(c, hipMemcpyAsync(cell_ref, c->cmp_cell_i32.p + na, nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (cell_n) VGS_HIP_TRY(c, hipMemcpyAsync(cell_n, c->cmp_cell_n.p, nc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the tables from a cell list
+#define CMP_TOTAL_MAX 0x100000000ull   // 2^32 points: C(total, 2) fits int64
+
+extern "C" vgs_status vgs_label_comparison_from_cells(vgs_ctx* c, int64_t K, int64_t n_in, const int32_t* cell_seg, const int32_t* cell_ref,
+                                                      const int64_t* cell_n, int64_t n_unannotated, int64_t* n_cells_out, int64_t* n_refs,
+                                                      int64_t* summary) {
+  if (!c) return VGS_E_ARG;
+  const char* fn = "vgs_label_comparison_from_cells";
+  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
+  if (K < 0 || K > (int64_t)0x7fffffff) { c->err = std::string(fn) + ": K = " + std::to_string(K) + " is out of range"; return VGS_E_ARG; }
+  if (n_in < 0) { c->err = std::string(fn) + ": n_in = " + std::to_string(n_in) + " is negative"; return VGS_E_ARG; }
+  if (n_unannotated < 0) { c->err = std::string(fn) + ": n_unannotated = " + std::to_string(n_unannotated) + " is negative"; return VGS_E_ARG; }
+  if (n_in > 0 && (!cell_seg || !cell_ref || !cell_n)) { c->err = std::string(fn) + ": an input array is NULL"; return VGS_E_ARG; }
+  if (n_in >= ((int64_t)1 << 31)) {
+    c->err = std::string(fn) + ": n_in = " + std::to_string(n_in) + " input cells reach the limit of 2^31 = " + std::to_string((int64_t)1 << 31);
+    return VGS_E_UNSUPPORTED;
+  }
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  c->cmp_valid = false; c->cmp_own_cells = -1;
+  c->cmp_cells = 0; c->cmp_refs = 0; c->cmp_K = K;
+  for (int i = 0; i < 12; ++i) c->cmp_summary[i] = 0;
+  VGS_HIP_TRY(c, c->cmp_meta.ensure(CM_SLOTS));
+  cmp_u64* meta = (cmp_u64*)c->cmp_meta.p;
+  VGS_HIP_TRY(c, hipMemsetAsync(meta, 0, CM_SLOTS * sizeof(uint64_t), c->stream));
+  uint64_t m[CM_SLOTS] = {0};
+  const uint32_t n = (uint32_t)n_in;
+  uint32_t n_cells = 0;
+  unsigned gbits = 1;
+  if (n > 0) {
+    // the input cells: seg | ref in cmp_ref; keys in, keys out, counts in, counts out in cmp_key
+    VGS_HIP_TRY(c, c->cmp_ref.ensure(2 * (size_t)n)); VGS_HIP_TRY(c, c->cmp_key.ensure(4 * (size_t)n)); VGS_HIP_TRY(c, c->cmp_work.ensure(2 * (size_t)n));
+    int32_t *in_seg = c->cmp_ref.p, *in_ref = in_seg + n;
+    uint64_t *key_in = c->cmp_key.p, *key_out = key_in + n;
+    long long *cnt_in = (long long*)(key_out + n), *cnt_out = cnt_in + n;
+    uint32_t *head = c->cmp_work.p, *inc = head + n;
+    VGS_HIP_TRY(c, hipMemcpyAsync(in_seg, cell_seg, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    VGS_HIP_TRY(c, hipMemcpyAsync(in_ref, cell_ref, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    VGS_HIP_TRY(c, hipMemcpyAsync(cnt_in, cell_n, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_cmp_cells_scan, dim3(std::min(cmp_grid(n), CMP_SCAN_GRID)), dim3(CMP_TB), 0, c->stream, in_seg, in_ref, cnt_in, n, (uint32_t)K, meta);
+    VGS_HIP_TRY(c, hipGetLastError());
+    VGS_READBACK(c, m, meta, CM_SLOTS * sizeof(uint64_t));   // the largest id, the sum of the counts, the first input that is not a cell
+    if (m[CM_BAD] != 0) {
+      const size_t i = (size_t)(n - (uint32_t)m[CM_BAD]);
+      c->err = std::string(fn) + ": input cell " + std::to_string(i) + " = (seg " + std::to_string(cell_seg[i]) + ", ref " + std::to_string(cell_ref[i]) +
+               ", n " + std::to_string(cell_n[i]) + "): seg must be in -1 .. K-1 = " + std::to_string(K - 1) + ", ref >= 0 and n >= 1";
+      return VGS_E_ARG;
+    }
+    if (m[CM_TOTAL] > CMP_TOTAL_MAX) {
+      c->err = std::string(fn) + ": the counts add up to " + (m[CM_TOTAL] >= CMP_COUNT_CLAMP ? std::string("at least ") : std::string()) +
+               std::to_string(m[CM_TOTAL]) + " points, above the limit of 2^32 = " + std::to_string(CMP_TOTAL_MAX);
+      return VGS_E_UNSUPPORTED;
+    }
+    gbits = cmp_bits(m[CM_MAXID]);
+    const unsigned bits = gbits + cmp_bits((uint64_t)K);   // rows 0 .. K
+    hipLaunchKernelGGL(k_cmp_cells_keys, dim3(cmp_grid(n)), dim3(CMP_TB), 0, c->stream, in_seg, in_ref, n, gbits, key_in);
+    size_t t_sort = 0, t_scan = 0;
+    VGS_HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, t_sort, key_in, key_out, cnt_in, cnt_out, (size_t)n, 0, bits, c->stream));
+    VGS_HIP_TRY(c, rocprim::inclusive_scan(nullptr, t_scan, head, inc, (size_t)n, rocprim::plus<uint32_t>(), c->stream));
+    VGS_HIP_TRY(c, c->cmp_tmp.ensure(std::max(t_sort, t_scan)));
+    VGS_HIP_TRY(c, rocprim::radix_sort_pairs(c->cmp_tmp.p, t_sort, key_in, key_out, cnt_in, cnt_out, (size_t)n, 0, bits, c->stream));
+    hipLaunchKernelGGL(k_cmp_heads<uint64_t>, dim3(cmp_grid(n)), dim3(CMP_TB), 0, c->stream, key_out, n, head);
+    VGS_HIP_TRY(c, rocprim::inclusive_scan(c->cmp_tmp.p, t_scan, head, inc, (size_t)n, rocprim::plus<uint32_t>(), c->stream));
+    // at most one merged cell per input cell
+    VGS_HIP_TRY(c, c->cmp_cstart.ensure(n)); VGS_HIP_TRY(c, c->cmp_cell_i32.ensure(2 * (size_t)n)); VGS_HIP_TRY(c, c->cmp_cell_n.ensure(n));
+    int32_t *m_seg = c->cmp_cell_i32.p, *m_ref = m_seg + n;
+    hipLaunchKernelGGL(k_cmp_cell_starts, dim3(cmp_grid(n)), dim3(CMP_TB), 0, c->stream, key_out, head, inc, n, gbits, c->cmp_cstart.p, m_seg, m_ref, meta);
+    VGS_HIP_TRY(c, hipGetLastError());
+    VGS_READBACK(c, &m[CM_NCELLS], meta + CM_NCELLS, sizeof(uint64_t));   // the number of merged cells
+    n_cells = (uint32_t)m[CM_NCELLS];
+    hipLaunchKernelGGL(k_cmp_cells_sums, dim3(cmp_fold_grid(cmp_grid(n_cells))), dim3(CMP_TB), 0, c->stream, c->cmp_cstart.p, n_cells, n, cnt_out,
+                       (long long*)c->cmp_cell_n.p, meta);
+  }
+  c->cmp_ann = n;   // (the stride of cell_seg | cell_ref)
+  vgs_status s = cmp_cell_tables(c, K, n, n_cells, gbits, (int64_t)m[CM_TOTAL], n_unannotated, meta, m);
+  if (s != VGS_OK) return s;
+  cmp_report(c, n_cells_out, n_refs, summary);
   return VGS_OK;
 }
 

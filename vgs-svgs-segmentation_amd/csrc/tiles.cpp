@@ -414,7 +414,8 @@ struct vgs_tiles {
   int strict_region = 0;      // VGS_TILES_OPT_STRICT_REGION
   int fail_phase = 0;         // tests (VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT): 1 grid, 2 stages, 3 points, 4 upload (behind the last collective of set_points),
                               // 5 descriptors (before the descriptor exchange), 6 graph (before the graph exchange), 7 boxes (before the box exchange),
-                              // 8 fields (before the exchange of vgs_tiles_segment_field_stats / vgs_tiles_segment_class_histogram)
+                              // 8 fields (before the exchange of vgs_tiles_segment_field_stats / vgs_tiles_segment_class_histogram),
+                              // 9 compare (before the exchange of vgs_tiles_compare_labels)
   vgs_status pending = VGS_OK;   // a local failure behind a call's last collective: the status word of the next collective carries it
   bool warned_outside = false;
   bool ran = false;              // the last vgs_tiles_run completed here
@@ -441,6 +442,10 @@ struct vgs_tiles {
   // the last attribute collective (field statistics or class histogram; nothing of it is cached): phases, own records, bytes sent
   double ftimes[VGS_TILES_F_COUNT] = {0};
   int64_t f_own = 0, f_bytes = 0;
+  // the last tiled compare (its tables live in the context's cmp_* buffers; nothing of the input is cached): phases, own cells, bytes sent
+  bool cmp_valid = false;
+  double ctimes[VGS_TILES_C_COUNT] = {0};
+  int64_t c_own = 0, c_bytes = 0;
   std::string err;
 };
 
@@ -490,7 +495,7 @@ vgs_status vgs_tiles_create(const vgs_params* p, int comm_kind, void* comm_handl
     // failure injection for the tests of the agreed-status protocol; read once, here
     const char* fr = std::getenv("VGS_TILES_FAIL_RANK");
     const char* fa = std::getenv("VGS_TILES_FAIL_AT");
-    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : !std::strcmp(fa, "descriptors") ? 5 : !std::strcmp(fa, "graph") ? 6 : !std::strcmp(fa, "boxes") ? 7 : !std::strcmp(fa, "fields") ? 8 : 0;
+    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : !std::strcmp(fa, "descriptors") ? 5 : !std::strcmp(fa, "graph") ? 6 : !std::strcmp(fa, "boxes") ? 7 : !std::strcmp(fa, "fields") ? 8 : !std::strcmp(fa, "compare") ? 9 : 0;
   }
   vgs_status s = vgs_create(p, &t->ctx);
   if (s != VGS_OK) { delete t->comm; delete t; return s; }
@@ -523,7 +528,7 @@ vgs_status vgs_tiles_get_times(vgs_tiles* t, double* ms, int32_t n) {
 vgs_status vgs_tiles_set_points(vgs_tiles* t, const float* xyz, int64_t n, int32_t stride_bytes) {
   if (!t || (!xyz && n > 0) || n < 0 || (stride_bytes != 12 && stride_bytes != 16)) return VGS_E_ARG;
   Comm& c = *t->comm;
-  t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false;
+  t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false;
   const int sf = stride_bytes / 4;
   if (!(t->pitch > 0)) {   // the largest x-extent over the ranks
     float mn = 3.0e38f, mx = -3.0e38f;
@@ -660,7 +665,7 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
   if (!t) return VGS_E_ARG;
   Comm& c = *t->comm;
   vgs_status carry = t->pending;   // a local failure behind the last collective of the previous call (upload, label write-back) travels now
-  t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false;
+  t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false;
   double t0 = now_ms();
   vgs_status s = chain_grid(t, carry);
   if (s != VGS_OK) return s;
@@ -1154,6 +1159,115 @@ vgs_status vgs_tiles_get_field_payload(vgs_tiles* t, int64_t* own_records, int64
   if (!t) return VGS_E_ARG;
   if (own_records) *own_records = t->f_own;
   if (bytes_sent) *bytes_sent = t->f_bytes;
+  return VGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ score against reference labels
+// The comparison over the ranks: no label and no reference id travels, every point is counted by the rank that loaded it.  This rank's
+// cells over its own points (one small pipeline on its GPU) -> ONE all_gather_varlen of int64 words: a header of status word, own cell
+// count and own unannotated count, then per cell (L + 1) << 32 | g and the count -> the lists in rank order into
+// vgs_label_comparison_from_cells on this rank's context, which merges them and builds the tables on the GPU: there is no host fold.
+// Nothing is cached (the input is the caller's), so every call is collective.  Everything a rank can get wrong on its own -- n, a NULL
+// input, a failing context call -- is found by the context call and travels in the status word.
+static vgs_status tiles_compare(vgs_tiles* t, const char* fn, bool on_device, const int32_t* ref, int64_t n, int64_t* K, int64_t* n_cells,
+                                int64_t* n_refs, int64_t* summary) {
+  if (!t) return VGS_E_ARG;
+  if (K) *K = t->kept;
+  if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, std::string(fn) + ": vgs_tiles_run first");
+  Comm& c = *t->comm;
+  const int64_t Kg = t->kept;
+  t->cmp_valid = false;
+  vgs_status carry = t->pending;
+  if (t->fail_phase == 9 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=compare"; }
+  const double t0 = now_ms();
+  std::vector<int64_t> payload(3, 0);
+  int64_t n_own_cells = 0, n_unann = 0;
+  if (carry == VGS_OK) {
+    if (on_device) TCARRY(vgs_own_label_cells_device(t->ctx, Kg, ref, n, &n_own_cells, &n_unann));
+    else TCARRY(vgs_own_label_cells(t->ctx, Kg, ref, n, &n_own_cells, &n_unann));
+    std::vector<int32_t> cs((size_t)n_own_cells + 1), cr((size_t)n_own_cells + 1);
+    std::vector<int64_t> cn((size_t)n_own_cells + 1);
+    if (carry == VGS_OK) TCARRY(vgs_get_own_label_cells(t->ctx, cs.data(), cr.data(), cn.data()));
+    if (carry == VGS_OK) {
+      payload.resize(3 + 2 * (size_t)n_own_cells);
+      for (size_t i = 0; i < (size_t)n_own_cells; ++i) {
+        payload[3 + 2 * i] = (int64_t)(((uint64_t)(uint32_t)(cs[i] + 1) << 32) | (uint64_t)(uint32_t)cr[i]);
+        payload[4 + 2 * i] = cn[i];
+      }
+    } else { n_own_cells = 0; n_unann = 0; }
+  }
+  payload[0] = (int64_t)carry;
+  payload[1] = n_own_cells;
+  payload[2] = n_unann;
+  const double t1 = now_ms();
+  std::vector<std::vector<int64_t>> gathered;
+  TCOMM(all_gather_varlen(c, payload, gathered));
+  const double t2 = now_ms();
+  {
+    int bad = -1;
+    for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].size() < 3 || gathered[(size_t)r][0] != 0) bad = r;
+    vgs_status a = agreed(t, carry, bad, "compare");
+    if (a != VGS_OK) return a;
+  }
+  size_t n_in = 0;
+  int64_t unann = 0;
+  for (int r = 0; r < c.world; ++r) {
+    const std::vector<int64_t>& g = gathered[(size_t)r];
+    if (g[1] < 0 || g.size() != 3 + 2 * (size_t)g[1]) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
+    n_in += (size_t)g[1];
+    unann += g[2];
+  }
+  std::vector<int32_t> as(n_in + 1), ar(n_in + 1);
+  std::vector<int64_t> an(n_in + 1);
+  size_t o = 0;
+  for (int r = 0; r < c.world; ++r) {
+    const std::vector<int64_t>& g = gathered[(size_t)r];
+    for (size_t i = 0; i < (size_t)g[1]; ++i, ++o) {
+      const uint64_t w = (uint64_t)g[3 + 2 * i];
+      as[o] = (int32_t)(uint32_t)(w >> 32) - 1; ar[o] = (int32_t)(uint32_t)w; an[o] = g[4 + 2 * i];
+    }
+  }
+  // (local, behind the collective: the rank returns its error and keeps it for the next collective, as the label write-back does)
+  const vgs_status sa = vgs_label_comparison_from_cells(t->ctx, Kg, (int64_t)n_in, as.data(), ar.data(), an.data(), unann, n_cells, n_refs, summary);
+  if (sa != VGS_OK) { t->pending = sa; return tfail(t, sa, std::string("vgs_label_comparison_from_cells: ") + vgs_last_error_string(t->ctx)); }
+  const double t3 = now_ms();
+  t->ctimes[VGS_TILES_C_OWN] = t1 - t0; t->ctimes[VGS_TILES_C_EXCHANGE] = t2 - t1; t->ctimes[VGS_TILES_C_TABLES] = t3 - t2;
+  t->ctimes[VGS_TILES_C_TOTAL] = t3 - t0;
+  t->c_own = n_own_cells; t->c_bytes = (int64_t)(payload.size() * sizeof(int64_t));
+  t->cmp_valid = true;
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_compare_labels(vgs_tiles* t, const int32_t* ref_host, int64_t n, int64_t* K, int64_t* n_cells, int64_t* n_refs, int64_t* summary) {
+  return tiles_compare(t, "vgs_tiles_compare_labels", false, ref_host, n, K, n_cells, n_refs, summary);
+}
+
+vgs_status vgs_tiles_compare_labels_device(vgs_tiles* t, const int32_t* ref_dev, int64_t n, int64_t* K, int64_t* n_cells, int64_t* n_refs,
+                                           int64_t* summary) {
+  return tiles_compare(t, "vgs_tiles_compare_labels_device", true, ref_dev, n, K, n_cells, n_refs, summary);
+}
+
+vgs_status vgs_tiles_get_label_comparison(vgs_tiles* t, int32_t* cell_seg, int32_t* cell_ref, int64_t* cell_n, int32_t* ref_id, int64_t* ref_points,
+                                          int64_t* ref_dropped, int32_t* ref_best_seg, int64_t* ref_best_n, double* ref_best_iou,
+                                          int64_t* seg_annotated, int32_t* seg_refs, int32_t* seg_best_ref, int64_t* seg_best_n, double* seg_best_iou) {
+  if (!t) return VGS_E_ARG;
+  if (!t->ran || !t->cmp_valid)
+    return tfail(t, VGS_E_STATE, "vgs_tiles_get_label_comparison: no comparison since the last run or the last vgs_tiles_set_points (vgs_tiles_compare_labels first)");
+  TCTX(vgs_get_label_comparison(t->ctx, cell_seg, cell_ref, cell_n, ref_id, ref_points, ref_dropped, ref_best_seg, ref_best_n, ref_best_iou, seg_annotated,
+                                seg_refs, seg_best_ref, seg_best_n, seg_best_iou));
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_compare_times(vgs_tiles* t, double* ms, int32_t n) {
+  if (!t || !ms || n < 0 || n > VGS_TILES_C_COUNT) return VGS_E_ARG;
+  for (int i = 0; i < n; ++i) ms[i] = t->ctimes[i];
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_compare_payload(vgs_tiles* t, int64_t* own_cells, int64_t* bytes_sent) {
+  if (!t) return VGS_E_ARG;
+  if (own_cells) *own_cells = t->c_own;
+  if (bytes_sent) *bytes_sent = t->c_bytes;
   return VGS_OK;
 }
 

@@ -322,6 +322,9 @@ struct vgs_ctx {
   DevBuf<uint8_t> cmp_tmp;
   int64_t cmp_ann = 0, cmp_cells = 0, cmp_refs = 0, cmp_K = 0, cmp_summary[12] = {0};
   bool cmp_valid = false;
+  // tile contexts (vgs_own_label_cells): the cells over the own points wait in cmp_cell_i32 / cmp_cell_n at a stride of cmp_ann until
+  // vgs_get_own_label_cells; -1: none.  vgs_label_comparison_from_cells stages its input in cmp_ref (seg | ref) and cmp_key (keys, counts)
+  int64_t cmp_own_cells = -1;
   DevBuf<uint64_t> counters;  // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 

@@ -28,6 +28,7 @@ D_NAMES = ("moments", "exchange", "fold", "algebra", "total")   # vgs_tiles_get_
 G_NAMES = ("halo", "own", "exchange", "fold", "total")          # vgs_tiles_get_graph_times
 B_NAMES = ("extents", "exchange", "fold", "finish", "total")    # vgs_tiles_get_box_times
 F_NAMES = ("own", "exchange", "fold", "finish", "total")        # vgs_tiles_get_field_times
+C_NAMES = ("own", "exchange", "tables", "total")                # vgs_tiles_get_compare_times
 # per (record / row, channel): (field, dtype) of vgs_get_own_segment_field_moments and vgs_tiles_fold_field_moments, in their argument order
 FIELD_MOMENT_FIELDS = (("n_valid", np.int64), ("anchor", np.float64), ("s1", np.float64), ("s2", np.float64), ("vmin", np.float32), ("vmax", np.float32))
 # per record / row: (field, dtype, values) of vgs_get_own_segment_moments and vgs_tiles_fold_moments, in their argument order
@@ -110,6 +111,15 @@ def lib():
         L.vgs_tiles_get_field_times.argtypes = [P, P, C.c_int32]
         L.vgs_tiles_get_field_payload.restype = C.c_int
         L.vgs_tiles_get_field_payload.argtypes = [P, P, P]
+        for name in ("vgs_tiles_compare_labels", "vgs_tiles_compare_labels_device"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [P, P, C.c_int64, P, P, P, P]
+        L.vgs_tiles_get_label_comparison.restype = C.c_int
+        L.vgs_tiles_get_label_comparison.argtypes = [P] + [P] * 14
+        L.vgs_tiles_get_compare_times.restype = C.c_int
+        L.vgs_tiles_get_compare_times.argtypes = [P, P, C.c_int32]
+        L.vgs_tiles_get_compare_payload.restype = C.c_int
+        L.vgs_tiles_get_compare_payload.argtypes = [P, P, P]
         L.vgs_tiles_fold_field_moments.restype = C.c_int
         L.vgs_tiles_fold_field_moments.argtypes = [C.c_int, P, P, C.c_int32, P, P, P, P, P, P, C.c_int64, P, P, P, P, P, P]
         L.vgs_tiles_fold_class_counts.restype = C.c_int
@@ -517,6 +527,65 @@ class NativeTiles:
         K = C.c_int64(0)
         self._ck(fn(self._h, ptr, n, nc, C.byref(K), *(_vp(out[name]) for name, _, _ in Engine.CLASS_HIST_FIELDS)))
         return {name: (a[:k, :max(nc, 0)] if a.ndim == 2 else a[:k]) for name, a in out.items()}
+
+    def compare_labels(self, ref):
+        """COLLECTIVE on every call (every rank makes it after run(); nothing is cached): score the segmentation against reference labels
+        over all ranks -- the dict of Engine.compare_labels(), the same bytes on every rank, and what one engine gives on the gathered
+        points (include/vgs_tiles.h, vgs_tiles_compare_labels).  `ref`: one int32 per point of this rank's set_points(), negative = not
+        annotated; a numpy array, or a torch tensor on this rank's device, which is read in place.  No label and no id leaves the rank,
+        only contingency cells; comparison_scores() works on the result unchanged."""
+        from .api import Engine
+        ref, ptr, n, dev = Engine._classes_input(ref, self.params.device)
+        fn = self._L.vgs_tiles_compare_labels_device if dev else self._L.vgs_tiles_compare_labels
+        K, n_cells, n_refs = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        summary = np.zeros(12, np.int64)
+        self._ck(fn(self._h, ptr, n, C.byref(K), C.byref(n_cells), C.byref(n_refs), _vp(summary)))
+        out = self.label_comparison(n_cells.value, n_refs.value, K.value)
+        out["summary"] = summary
+        return out
+
+    def label_comparison(self, n_cells, n_refs, K):
+        """the tables of the last compare_labels() of this rank (vgs_tiles_get_label_comparison; local, no collective), with the sizes
+        that call returned; VgsError (VGS_E_STATE) without a compare since the last run() or set_points()"""
+        from .api import Engine
+        rows = {"cells": int(n_cells), "refs": int(n_refs), "segs": int(K)}
+        out = {name: np.zeros(max(rows[tab], 1), dtype=dt) for name, dt, tab in Engine.COMPARE_FIELDS}
+        self._ck(self._L.vgs_tiles_get_label_comparison(self._h, *(_vp(out[name]) for name, _, _ in Engine.COMPARE_FIELDS)))
+        return {name: out[name][:rows[tab]] for name, _, tab in Engine.COMPARE_FIELDS}
+
+    def compare_times(self):
+        """the last compare_labels()'s phases on this rank, milliseconds (C_NAMES)"""
+        t = np.zeros(len(C_NAMES), dtype=np.float64)
+        self._ck(self._L.vgs_tiles_get_compare_times(self._h, _vp(t), len(C_NAMES)))
+        return dict(zip(C_NAMES, (float(x) for x in t)))
+
+    def compare_payload(self):
+        """the last compare_labels()'s payload on this rank: cells of its own, bytes sent"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._ck(self._L.vgs_tiles_get_compare_payload(self._h, C.byref(a), C.byref(b)))
+        return dict(own_cells=a.value, bytes_sent=b.value)
+
+    def own_label_cells(self, K, ref):
+        """this rank's contingency cells of the global labels -1 .. K-1 over its own points (vgs_own_label_cells on its context; local, no
+        collective; it discards the context's last comparison): a dict of cell_seg, cell_ref (int32), cell_n (int64), ascending
+        (segment, id), plus n_unannotated"""
+        from .api import Engine
+        L = _lib.lib()
+        h = self._ctx()
+        ref, ptr, n, dev = Engine._classes_input(ref, self.params.device)
+        fn = L.vgs_own_label_cells_device if dev else L.vgs_own_label_cells
+        nc, nu = C.c_int64(0), C.c_int64(0)
+        st = fn(h, int(K), ptr, n, C.byref(nc), C.byref(nu))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        out = {"cell_seg": np.zeros(max(nc.value, 1), np.int32), "cell_ref": np.zeros(max(nc.value, 1), np.int32),
+               "cell_n": np.zeros(max(nc.value, 1), np.int64)}
+        st = L.vgs_get_own_label_cells(h, _vp(out["cell_seg"]), _vp(out["cell_ref"]), _vp(out["cell_n"]))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        out = {name: a[:nc.value] for name, a in out.items()}
+        out["n_unannotated"] = int(nu.value)
+        return out
 
     def _kept(self):
         """kept_global of the last run (0 before one); local"""
