@@ -2,6 +2,15 @@
 // include/vgs.h; the collectives are RCCL calls (ncclAllGather / ncclBroadcast on the caller's communicator) or, for tests
 // that run several ranks on one GPU, threads of one process meeting in shared memory.  The Python twin of this file is
 // vgs-svgs-segmentation_amd/dist.py (same protocol, same labels); protocol notes live there and in DESIGN.md section 6.
+//
+// The agreed-status protocol, once.  A rank that fails LOCALLY between two collectives must not leave while its peers are already inside
+// the next one (they would wait for ever: ADVICE r3).  So a failing step only records its status (`carry`: TCARRY, inject), the rank
+// still joins the next collective with that status in its payload's header, and every rank reads the headers and leaves with the same
+// verdict (agreed): the failing rank its own error, the others VGS_E_PEER naming the lowest failing rank.  A failure BEHIND a call's last
+// collective is returned and kept in t->pending (behind_collective), and the next collective's header carries it.  The six collectives
+// after vgs_tiles_run all read: open_collective (guard, carry = pending, injection) -> own records, header filled in -> exchange (ONE
+// all_gather_varlen + the scan of the headers) -> fold -> behind_collective(finish on this rank's GPU).  vgs_tiles_set_points, chain_grid
+// and the boundary exchange of vgs_tiles_run carry the status in payloads of their own shapes and share first_bad_rank and agreed.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -15,6 +24,7 @@
 #include <mutex>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vgs_tiles.h"
@@ -208,6 +218,15 @@ struct MomentRec {
 };
 static_assert(sizeof(MomentRec) == 128, "MomentRec is the exchange's wire format");
 
+MomentRec pack_moment(const int32_t* label, const int64_t* n_points, const int32_t* n_nodes, const float* bbox6, const float* anchor3, const double* s9, size_t i) {
+  MomentRec m;
+  m.label = label[i]; m.n_nodes = n_nodes[i]; m.n_points = n_points[i];
+  for (int a = 0; a < 6; ++a) m.bbox[a] = bbox6[6 * i + a];
+  for (int a = 0; a < 3; ++a) m.anchor[a] = anchor3[3 * i + a];
+  for (int f = 0; f < 9; ++f) m.s[f] = s9[9 * i + f];
+  return m;
+}
+
 // The moments of every global label 0 .. K-1 from the ranks' records, the same bytes on every rank: per label, ranks in ascending order.
 // The anchor is the lowest rank's with own points; another rank's sums move to it by delta = a_r - a (exact in fp64: a float minus a
 // float): S1 += S1_r + n_r delta, S2 += S2_r + S1_r delta^T + delta S1_r^T + n_r delta delta^T.  Counts add, boxes take min / max.
@@ -257,6 +276,23 @@ struct EdgeRec {
   float w_min = 0, w_max = 0;
 };
 static_assert(sizeof(EdgeRec) == 48, "EdgeRec is the exchange's wire format");
+
+EdgeRec pack_edge(const int32_t* seg_ab, const int64_t* n_pairs, const int64_t* n_finite, const int32_t* nodes_ab, const double* w_sum, const float* w_min, const float* w_max, size_t i) {
+  EdgeRec e;
+  e.a = seg_ab[2 * i]; e.b = seg_ab[2 * i + 1]; e.n_pairs = n_pairs[i]; e.n_finite = n_finite[i]; e.nodes_a = nodes_ab[2 * i]; e.nodes_b = nodes_ab[2 * i + 1];
+  e.w_sum = w_sum[i]; e.w_min = w_min[i]; e.w_max = w_max[i];
+  return e;
+}
+// the inverse, into the caller's arrays (each may be NULL)
+void unpack_edge(const EdgeRec& e, size_t i, int32_t* seg_ab, int64_t* n_pairs, int64_t* n_finite, int32_t* nodes_ab, double* w_sum, float* w_min, float* w_max) {
+  if (seg_ab) { seg_ab[2 * i] = e.a; seg_ab[2 * i + 1] = e.b; }
+  if (n_pairs) n_pairs[i] = e.n_pairs;
+  if (n_finite) n_finite[i] = e.n_finite;
+  if (nodes_ab) { nodes_ab[2 * i] = e.nodes_a; nodes_ab[2 * i + 1] = e.nodes_b; }
+  if (w_sum) w_sum[i] = e.w_sum;
+  if (w_min) w_min[i] = e.w_min;
+  if (w_max) w_max[i] = e.w_max;
+}
 
 // The edge table of the whole scene from the ranks' partial tables, the same bytes on every rank: the tables are merged by (a, b); per
 // edge the ranks are taken in ascending order.  Counts add, w_sum adds in fp64 in that order, w_min / w_max take the smaller / larger of
@@ -311,6 +347,13 @@ struct ExtentRec {
 };
 static_assert(sizeof(ExtentRec) == 56, "ExtentRec is the exchange's wire format");
 
+ExtentRec pack_extent(const int32_t* label, const double* lo3, const double* hi3, size_t i) {
+  ExtentRec e;
+  e.label = label[i];
+  for (int a = 0; a < 3; ++a) { e.lo[a] = lo3[3 * i + a]; e.hi[a] = hi3[3 * i + a]; }
+  return e;
+}
+
 // The extents of every global label 0 .. K-1 from the ranks' records, the same bytes on every rank: per label, ranks in ascending order,
 // lo takes the smaller and hi the larger (of values; a zero bound keeps the sign it met first).  A row no record reaches: +inf / -inf and
 // reached = 0.  Returns false if a record names a label outside 0 .. K-1.
@@ -338,6 +381,34 @@ struct FieldRecs {
   std::vector<double> a, s1, s2;
   std::vector<float> mn, mx;
 };
+
+// record i of flat arrays (C channels each) as 1 + 5 C wire words behind w
+void pack_field(std::vector<uint64_t>& w, const int32_t* label, const int64_t* n, const double* a, const double* s1, const double* s2, const float* mn, const float* mx, size_t C, size_t i) {
+  auto bits = [](double v) { uint64_t u; std::memcpy(&u, &v, 8); return u; };
+  w.push_back((uint64_t)(uint32_t)label[i]);
+  for (size_t ch = 0; ch < C; ++ch) {
+    const size_t j = i * C + ch;
+    uint32_t lo, hi;
+    std::memcpy(&lo, &mn[j], 4); std::memcpy(&hi, &mx[j], 4);
+    w.push_back((uint64_t)n[j]); w.push_back(bits(a[j])); w.push_back(bits(s1[j])); w.push_back(bits(s2[j]));
+    w.push_back((uint64_t)lo | ((uint64_t)hi << 32));
+  }
+}
+// the inverse: nr records of wire words
+void unpack_fields(const uint64_t* w, size_t nr, size_t C, FieldRecs& R) {
+  auto dbl = [](uint64_t u) { double v; std::memcpy(&v, &u, 8); return v; };
+  R.label.resize(nr); R.n.resize(nr * C); R.a.resize(nr * C); R.s1.resize(nr * C); R.s2.resize(nr * C); R.mn.resize(nr * C); R.mx.resize(nr * C);
+  for (size_t i = 0; i < nr; ++i) {
+    R.label[i] = (int32_t)(uint32_t)*w++;
+    for (size_t ch = 0; ch < C; ++ch) {
+      const size_t j = i * C + ch;
+      R.n[j] = (int64_t)w[0]; R.a[j] = dbl(w[1]); R.s1[j] = dbl(w[2]); R.s2[j] = dbl(w[3]);
+      const uint32_t lo = (uint32_t)w[4], hi = (uint32_t)(w[4] >> 32);
+      std::memcpy(&R.mn[j], &lo, 4); std::memcpy(&R.mx[j], &hi, 4);
+      w += 5;
+    }
+  }
+}
 
 // The moments of every (label, channel) from the ranks' records, the same bytes on every rank: per entry, ranks in ascending order.  The
 // anchor a is the anchor of the lowest rank with n_valid > 0, whose sums are taken as they are; a later rank's sums move to it by delta =
@@ -377,6 +448,20 @@ struct ClassRecs {
   std::vector<int64_t> hist, n_outside;
 };
 
+// record i of flat arrays as 2 + nc wire words behind w
+void pack_class(std::vector<int64_t>& w, const int32_t* label, const int64_t* hist, const int64_t* n_outside, size_t nc, size_t i) {
+  w.push_back((int64_t)label[i]); w.push_back(n_outside[i]);
+  w.insert(w.end(), hist + i * nc, hist + (i + 1) * nc);
+}
+// the inverse: nr records of wire words
+void unpack_classes(const int64_t* w, size_t nr, size_t nc, ClassRecs& R) {
+  R.label.resize(nr); R.n_outside.resize(nr); R.hist.resize(nr * nc);
+  for (size_t i = 0; i < nr; ++i, w += 2 + nc) {
+    R.label[i] = (int32_t)w[0]; R.n_outside[i] = w[1];
+    std::copy(w + 2, w + 2 + nc, R.hist.begin() + (ptrdiff_t)(i * nc));
+  }
+}
+
 // Integer adds per (label, class), then the majority rule of vgs_segment_class_histogram on the folded table: the lowest class with the
 // largest count, -1 and 0 when every count is 0.  Returns false if a record names a label outside 0 .. K-1.
 bool fold_class_counts(const std::vector<ClassRecs>& ranks, int64_t K, int nc, std::vector<int64_t>& hist, std::vector<int64_t>& n_outside,
@@ -397,6 +482,50 @@ bool fold_class_counts(const std::vector<ClassRecs>& ranks, int64_t K, int nc, s
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------ payload headers
+// Every payload of a post-run collective opens with a header that holds the rank's status word and its record count: the first entry of
+// a struct payload (status in its first field; the count where the record has a slot wide enough for it), the first three words of a word
+// payload (status, count, one word of the collective's own).  No receiver reads the count of a struct payload; it stays on the wire.
+void set_header(MomentRec& h, vgs_status st, size_t n) { h.label = (int32_t)st; h.n_points = (int64_t)n; }
+void set_header(EdgeRec& h, vgs_status st, size_t n) { h.a = (int32_t)st; h.n_pairs = (int64_t)n; }
+void set_header(ExtentRec& h, vgs_status st, size_t n) { h.label = (int32_t)st; h.lo[0] = (double)n; }
+template <typename W> void set_header(std::vector<W>& w, vgs_status st, int64_t n, int64_t own) { w[0] = (W)(uint32_t)st; w[1] = (W)n; w[2] = (W)own; }
+template <typename T> constexpr size_t header_len() { return std::is_integral<T>::value ? 3 : 1; }   // entries of the payload
+bool header_ok(const MomentRec& h) { return h.label == 0; }
+bool header_ok(const EdgeRec& h) { return h.a == 0; }
+bool header_ok(const ExtentRec& h) { return h.label == 0; }
+bool header_ok(uint64_t word0) { return word0 == 0; }
+bool header_ok(int64_t word0) { return word0 == 0; }
+template <typename T> void strip_headers(std::vector<std::vector<T>>& gathered) { for (std::vector<T>& g : gathered) g.erase(g.begin()); }
+
+// a table (its first n entries) into a caller's array, which may be NULL
+template <typename V, typename D> void put(const V& v, D* dst, size_t n = SIZE_MAX) { if (dst) std::copy(v.begin(), v.begin() + (ptrdiff_t)std::min(n, v.size()), dst); }
+
+// the lowest rank for which bad(rank) holds, -1 when there is none: every rank scans what it gathered in the same order, so all name the same rank
+template <typename F> int first_bad_rank(int world, F bad) {
+  for (int r = 0; r < world; ++r) if (bad(r)) return r;
+  return -1;
+}
+
+// Where a rank can be told to fail (tests of the agreed-status protocol: VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=<name>).  points, grid and
+// stages: before that phase's collective; upload: behind the last collective of vgs_tiles_set_points; the others: before the exchange of
+// that post-run collective (fields: vgs_tiles_segment_field_stats and vgs_tiles_segment_class_histogram alike).
+enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_COUNT };
+const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare"};
+
+// Phase clock of one call: lap(slot) gives the slot the host wall time since the last lap (the start, for the first), total(slot) the
+// time from the start to the last lap.  Milliseconds.  vgs_tiles_run stamps t->times as it goes; a post-run collective stamps an array of
+// its own and total(slot, dst) publishes all of it at the end, so that a call that fails leaves the last good call's times alone.
+struct Stopwatch {
+  double* ms;
+  double start, last;
+  static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  explicit Stopwatch(double* slots) : ms(slots), start(now()), last(start) {}
+  void lap(int slot) { const double t = now(); ms[slot] = t - last; last = t; }
+  void total(int slot) { ms[slot] = last - start; }
+  template <int N> void total(int slot, double (&dst)[N]) { total(slot); std::copy(ms, ms + N, dst); }
+};
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ driver
@@ -412,10 +541,7 @@ struct vgs_tiles {
   int64_t exch_sent = 0, exch_recv = 0; int exch_calls = 0;   // the last run's boundary exchange: bytes this rank sent / received, collectives it took
   double times[VGS_TILES_T_COUNT] = {0};   // last run, milliseconds of host wall time per phase (vgs_tiles_get_times)
   int strict_region = 0;      // VGS_TILES_OPT_STRICT_REGION
-  int fail_phase = 0;         // tests (VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT): 1 grid, 2 stages, 3 points, 4 upload (behind the last collective of set_points),
-                              // 5 descriptors (before the descriptor exchange), 6 graph (before the graph exchange), 7 boxes (before the box exchange),
-                              // 8 fields (before the exchange of vgs_tiles_segment_field_stats / vgs_tiles_segment_class_histogram),
-                              // 9 compare (before the exchange of vgs_tiles_compare_labels)
+  Phase fail_phase = PH_NONE;   // tests: where this rank was told to fail (inject)
   vgs_status pending = VGS_OK;   // a local failure behind a call's last collective: the status word of the next collective carries it
   bool warned_outside = false;
   bool ran = false;              // the last vgs_tiles_run completed here
@@ -452,19 +578,73 @@ struct vgs_tiles {
 static vgs_status tfail(vgs_tiles* t, vgs_status s, const std::string& msg) { t->err = msg; return s; }
 #define TCTX(call) do { vgs_status s_ = (call); if (s_ != VGS_OK) return tfail(t, s_, std::string(#call) + ": " + vgs_last_error_string(t->ctx)); } while (0)
 #define TCOMM(call) do { if (!(call)) return tfail(t, VGS_E_HIP, std::string("collective failed: ") + t->comm->err); } while (0)
-// A LOCAL failure between two collectives must not make this rank leave while its peers are already inside the next collective
-// (they would wait for ever: ADVICE r3).  So a failing step only records its status (`carry`), the rank still takes part in the
-// next collective with that status as a word of the payload, and every rank sees it there and returns: the failing rank its own
-// error, the others VGS_E_PEER naming the rank.  The caller's process then exits non-zero and the launcher ends the job.
+#define TRY(call) do { vgs_status s_ = (call); if (s_ != VGS_OK) return s_; } while (0)   // (the callee has set t->err)
+// The pieces of the agreed-status protocol (the head of this file), in the order a collective meets them.
+// A step between two collectives runs only while nothing has failed here; its failure is recorded in `carry`, never returned.  TCARRY_AS:
+// the call goes through a pointer chosen at run time, `name` is the function it points to -- the text is that of TCARRY on the call itself.
+#define TCARRY_AS(fn, name, ...) do { if (carry == VGS_OK) { vgs_status s_ = (fn)(__VA_ARGS__); if (s_ != VGS_OK) { carry = s_; t->err = std::string(name) + "(" #__VA_ARGS__ "): " + vgs_last_error_string(t->ctx); } } } while (0)
 #define TCARRY(call) do { if (carry == VGS_OK) { vgs_status s_ = (call); if (s_ != VGS_OK) { carry = s_; t->err = std::string(#call) + ": " + vgs_last_error_string(t->ctx); } } } while (0)
 
-static vgs_status agreed(vgs_tiles* t, vgs_status mine, int first_bad_rank, const char* phase) {
-  if (mine != VGS_OK) return mine;   // t->err already says what failed here
-  if (first_bad_rank >= 0) return tfail(t, VGS_E_PEER, std::string("rank ") + std::to_string(first_bad_rank) + " failed in the " + phase + " phase; this rank stops with it");
+// failure injection: a rank told to fail at `ph` records that as its local failure there, unless a real one came first
+static void inject(vgs_tiles* t, Phase ph, vgs_status& carry) {
+  if (t->fail_phase == ph && carry == VGS_OK) { carry = VGS_E_STATE; t->err = std::string("failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=") + PHASE_NAME[ph]; }
+}
+
+// opening of a collective after vgs_tiles_run: a rank that never ran and keeps no failure makes no collective (nor do its peers, in the same state)
+static vgs_status open_collective(vgs_tiles* t, const std::string& fn, Phase ph, vgs_status& carry) {
+  if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, fn + ": vgs_tiles_run first");
+  carry = t->pending;
+  inject(t, ph, carry);
   return VGS_OK;
 }
 
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// the verdict, the same on every rank from the same gathered status words
+static vgs_status agreed(vgs_tiles* t, vgs_status mine, int bad_rank, const char* phase) {
+  if (mine != VGS_OK) return mine;   // t->err already says what failed here
+  if (bad_rank >= 0) return tfail(t, VGS_E_PEER, std::string("rank ") + std::to_string(bad_rank) + " failed in the " + phase + " phase; this rank stops with it");
+  return VGS_OK;
+}
+
+// The exchange of a post-run collective: the payload, its header filled in (set_header; `carry` is the status in it), goes through ONE
+// all_gather_varlen whatever `carry` is -- no path leads round it.  A payload too short to hold a header counts as a failed rank.
+// VGS_OK: every gathered[r] opens with a header of status 0, still in place.
+template <typename T>
+static vgs_status exchange(vgs_tiles* t, vgs_status carry, const std::vector<T>& payload, const char* phase, Stopwatch& sw, int slot, std::vector<std::vector<T>>& gathered) {
+  TCOMM(all_gather_varlen(*t->comm, payload, gathered));
+  sw.lap(slot);
+  const int bad = first_bad_rank(t->comm->world, [&](int r) { return gathered[(size_t)r].size() < header_len<T>() || !header_ok(gathered[(size_t)r][0]); });
+  return agreed(t, carry, bad, phase);
+}
+
+// Behind the exchange of a word payload with `per` words a record: the header's third word must be the same on every rank where it is an
+// argument of the call (`arg` names it; NULL: the ranks' own figure) -- every rank was valid on its own, but they do not describe the
+// same table -- and every payload is as long as its header's record count says.  The same verdict on every rank, from the same words.
+template <typename W>
+static vgs_status check_word_payloads(vgs_tiles* t, const char* fn, const std::vector<std::vector<W>>& gathered, size_t per, const char* arg) {
+  auto word = [&](size_t r, int i) { return (int64_t)gathered[r][(size_t)i]; };
+  for (size_t r = 1; arg && r < gathered.size(); ++r)
+    if (word(r, 2) != word(0, 2))
+      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed " + arg + " = " + std::to_string((int32_t)word(r, 2)) + ", rank 0 passed " + std::to_string((int32_t)word(0, 2)));
+  for (size_t r = 0; r < gathered.size(); ++r)
+    if (word(r, 1) < 0 || gathered[r].size() != 3 + (size_t)word(r, 1) * per) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
+  return VGS_OK;
+}
+
+// closing: the local step behind a call's last collective; its error is returned AND kept for the next collective's header (open_collective)
+static vgs_status behind_collective(vgs_tiles* t, vgs_status s, const char* what) {
+  if (s == VGS_OK) return VGS_OK;
+  t->pending = s;
+  return tfail(t, s, std::string(what) + ": " + vgs_last_error_string(t->ctx));
+}
+
+// what a new cloud or a new run makes stale: the run itself and every table cached from it
+static void invalidate(vgs_tiles* t) { t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false; }
+
+template <int N> static vgs_status get_times(vgs_tiles* t, double (vgs_tiles::*slots)[N], double* ms, int32_t n) {
+  if (!t || !ms || n < 0 || n > N) return VGS_E_ARG;
+  std::copy(t->*slots, t->*slots + n, ms);
+  return VGS_OK;
+}
 
 extern "C" {
 
@@ -495,7 +675,8 @@ vgs_status vgs_tiles_create(const vgs_params* p, int comm_kind, void* comm_handl
     // failure injection for the tests of the agreed-status protocol; read once, here
     const char* fr = std::getenv("VGS_TILES_FAIL_RANK");
     const char* fa = std::getenv("VGS_TILES_FAIL_AT");
-    if (fr && fa && std::atoi(fr) == rank) t->fail_phase = !std::strcmp(fa, "grid") ? 1 : !std::strcmp(fa, "stages") ? 2 : !std::strcmp(fa, "points") ? 3 : !std::strcmp(fa, "upload") ? 4 : !std::strcmp(fa, "descriptors") ? 5 : !std::strcmp(fa, "graph") ? 6 : !std::strcmp(fa, "boxes") ? 7 : !std::strcmp(fa, "fields") ? 8 : !std::strcmp(fa, "compare") ? 9 : 0;
+    if (fr && fa && std::atoi(fr) == rank)
+      for (int ph = PH_NONE + 1; ph < PH_COUNT; ++ph) if (!std::strcmp(fa, PHASE_NAME[ph])) t->fail_phase = (Phase)ph;
   }
   vgs_status s = vgs_create(p, &t->ctx);
   if (s != VGS_OK) { delete t->comm; delete t; return s; }
@@ -519,16 +700,12 @@ vgs_status vgs_tiles_set_option(vgs_tiles* t, int32_t option, int64_t value) {
   return tfail(t, VGS_E_ARG, "unknown option");
 }
 
-vgs_status vgs_tiles_get_times(vgs_tiles* t, double* ms, int32_t n) {
-  if (!t || !ms || n < 0 || n > VGS_TILES_T_COUNT) return VGS_E_ARG;
-  for (int i = 0; i < n; ++i) ms[i] = t->times[i];
-  return VGS_OK;
-}
+vgs_status vgs_tiles_get_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::times, ms, n); }
 
 vgs_status vgs_tiles_set_points(vgs_tiles* t, const float* xyz, int64_t n, int32_t stride_bytes) {
   if (!t || (!xyz && n > 0) || n < 0 || (stride_bytes != 12 && stride_bytes != 16)) return VGS_E_ARG;
   Comm& c = *t->comm;
-  t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false;
+  invalidate(t);
   const int sf = stride_bytes / 4;
   if (!(t->pitch > 0)) {   // the largest x-extent over the ranks
     float mn = 3.0e38f, mx = -3.0e38f;
@@ -564,20 +741,17 @@ vgs_status vgs_tiles_set_points(vgs_tiles* t, const float* xyz, int64_t n, int32
   // a failure behind the last collective of the previous call (the label write-back at the end of vgs_tiles_run) has reached nobody
   // yet: it travels in this call's status word (it used to be cleared below and never arrived)
   vgs_status carry = t->pending;
-  if (t->fail_phase == 3 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=points"; }
+  inject(t, PH_POINTS, carry);
   if (t->strict_region && t->n_outside > 0 && carry == VGS_OK) {
     carry = VGS_E_ARG;
     t->err = std::to_string(t->n_outside) + " points lie outside this rank's region (VGS_TILES_OPT_STRICT_REGION)";
   }
   {
     // agreed status before the payload: one word per rank
-    int64_t st = (int64_t)carry;
+    const int64_t st = (int64_t)carry;
     std::vector<int64_t> all((size_t)c.world);
     TCOMM(c.all_gather(&st, all.data(), sizeof(int64_t)));
-    int bad = -1;
-    for (int r = 0; r < c.world && bad < 0; ++r) if (all[(size_t)r] != 0) bad = r;
-    vgs_status a = agreed(t, carry, bad, "point loading");
-    if (a != VGS_OK) return a;
+    TRY(agreed(t, carry, first_bad_rank(c.world, [&](int r) { return all[(size_t)r] != 0; }), "point loading"));
   }
   std::vector<std::vector<float>> strips;
   TCOMM(all_gather_varlen(c, strip, strips));
@@ -603,7 +777,7 @@ vgs_status vgs_tiles_set_points(vgs_tiles* t, const float* xyz, int64_t n, int32
   auto local_step = [&](vgs_status s, const char* what) {
     if (s != VGS_OK && t->pending == VGS_OK) { t->pending = s; t->err = std::string(what) + ": " + vgs_last_error_string(t->ctx); }
   };
-  if (t->fail_phase == 4) { t->pending = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=upload"; }
+  inject(t, PH_UPLOAD, t->pending);
   if (t->pending == VGS_OK) local_step(vgs_set_points(t->ctx, t->local.data(), (int64_t)(t->local.size() / 3), 12), "vgs_set_points");
   if (t->pending == VGS_OK) local_step(vgs_set_owned_region(t->ctx, t->lo, t->hi), "vgs_set_owned_region");
   if (t->pending == VGS_OK) local_step(vgs_set_own_point_range(t->ctx, t->own_first, t->n_own), "vgs_set_own_point_range");
@@ -619,7 +793,8 @@ static vgs_status chain_grid(vgs_tiles* t, vgs_status& carry) {
   Comm& c = *t->comm;
   float bb[6] = {0, 0, 0, 0, 0, 0};
   int64_t nf = 0;
-  if (t->fail_phase == 1) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=grid"; }
+  if (t->fail_phase == PH_GRID) carry = VGS_OK;   // (at this one site the injected failure has always replaced a kept one)
+  inject(t, PH_GRID, carry);
   TCARRY(vgs_points_bbox(t->ctx, bb, &nf));
   auto pack = [](const vgs_grid_state& g, double* v) { for (int a = 0; a < 3; ++a) { v[a] = g.min[a]; v[3 + a] = (double)g.shift[a]; } v[6] = g.depth; v[7] = g.defined; };
   auto unpack = [](vgs_grid_state& g, const double* v) { for (int a = 0; a < 3; ++a) { g.min[a] = v[a]; g.shift[a] = (uint64_t)v[3 + a]; } g.depth = (int32_t)v[6]; g.defined = (int32_t)v[7]; };
@@ -633,12 +808,7 @@ static vgs_status chain_grid(vgs_tiles* t, vgs_status& carry) {
   mine[15] = (double)carry;   // status word
   std::vector<double> all((size_t)16 * c.world);
   TCOMM(c.all_gather(mine, all.data(), sizeof(mine)));
-  {
-    int bad = -1;
-    for (int r = 0; r < c.world && bad < 0; ++r) if (all[(size_t)16 * r + 15] != 0.0) bad = r;
-    vgs_status a = agreed(t, carry, bad, "grid");
-    if (a != VGS_OK) return a;
-  }
+  TRY(agreed(t, carry, first_bad_rank(c.world, [&](int r) { return all[(size_t)16 * r + 15] != 0.0; }), "grid"));
   vgs_grid_state g;
   vgs_grid_state_init(&g);
   for (int r = 0; r < c.world; ++r) {
@@ -665,16 +835,13 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
   if (!t) return VGS_E_ARG;
   Comm& c = *t->comm;
   vgs_status carry = t->pending;   // a local failure behind the last collective of the previous call (upload, label write-back) travels now
-  t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false;
-  double t0 = now_ms();
-  vgs_status s = chain_grid(t, carry);
-  if (s != VGS_OK) return s;
-  double t1 = now_ms();
-  t->times[VGS_TILES_T_GRID] = t1 - t0;
-  if (t->fail_phase == 2 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=stages"; }
+  invalidate(t);
+  Stopwatch sw(t->times);
+  TRY(chain_grid(t, carry));
+  sw.lap(VGS_TILES_T_GRID);
+  inject(t, PH_STAGES, carry);
   TCARRY(vgs_voxelize(t->ctx)); TCARRY(vgs_features(t->ctx)); TCARRY(vgs_adjacency(t->ctx)); TCARRY(vgs_segment(t->ctx));
-  double t2 = now_ms();
-  t->times[VGS_TILES_T_STAGES] = t2 - t1;
+  sw.lap(VGS_TILES_T_STAGES);
   // only the border leaves the GPU: unique boundary voxels (code, local root, owned voxels of that root) and the number of
   // components that are local to this tile
   int64_t n = 0, nkl = 0;
@@ -686,8 +853,7 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
   if (carry != VGS_OK) { n = 0; nkl = 0; }
   mine.code.resize((size_t)n); mine.root.resize((size_t)n); mine.cnt.resize((size_t)n);
   t->n_records = n;
-  double t3 = now_ms();
-  t->times[VGS_TILES_T_RECORDS] = t3 - t2;
+  sw.lap(VGS_TILES_T_RECORDS);
   // the one data-path exchange: header (record count, local segment count, this rank's status) + records, 3 words each
   constexpr size_t HDR = 3;
   std::vector<int64_t> payload(HDR + 3 * (size_t)n);
@@ -700,12 +866,7 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
     std::vector<int64_t> fixed(cap, 0), all(cap * (size_t)c.world);
     std::copy(payload.begin(), payload.begin() + (ptrdiff_t)std::min(payload.size(), cap), fixed.begin());
     TCOMM(c.all_gather(fixed.data(), all.data(), cap * sizeof(int64_t)));
-    {
-      int bad = -1;
-      for (int r = 0; r < c.world && bad < 0; ++r) if (all[cap * (size_t)r + 2] != 0) bad = r;
-      vgs_status a = agreed(t, carry, bad, "stages");
-      if (a != VGS_OK) return a;
-    }
+    TRY(agreed(t, carry, first_bad_rank(c.world, [&](int r) { return all[cap * (size_t)r + 2] != 0; }), "stages"));
     bool fits = true;
     for (int r = 0; r < c.world; ++r) fits = fits && (HDR + 3 * (size_t)all[cap * (size_t)r]) <= cap;
     t->exch_sent = (int64_t)(cap * sizeof(int64_t)); t->exch_recv = t->exch_sent * c.world; t->exch_calls = 1;
@@ -719,8 +880,7 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
       t->exch_sent += (int64_t)sizeof(int64_t) * (1 + mx); t->exch_recv += (int64_t)sizeof(int64_t) * (1 + mx) * c.world; t->exch_calls += 2;
     }
   }
-  double t4 = now_ms();
-  t->times[VGS_TILES_T_EXCHANGE] = t4 - t3;
+  sw.lap(VGS_TILES_T_EXCHANGE);
   std::vector<RankRecords> rec((size_t)c.world);
   std::vector<int64_t> kept_local((size_t)c.world);
   for (int r = 0; r < c.world; ++r) {
@@ -734,20 +894,16 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
   std::vector<int64_t> base;
   std::vector<std::vector<int32_t>> uroot, ulabel;
   merge_boundary_compact(rec, kept_local, t->P.voxels_min, base, uroot, ulabel, t->kept);
-  double t5 = now_ms();
-  t->times[VGS_TILES_T_MERGE] = t5 - t4;
+  sw.lap(VGS_TILES_T_MERGE);
   std::vector<int32_t>& br = uroot[(size_t)c.rank];
   std::vector<int32_t>& bl = ulabel[(size_t)c.rank];
   int32_t dummy = 0;
-  // (a failure here is local and the run's last collective is behind us: this rank returns it and keeps it in t->pending; the
-  // peers -- whose results are complete -- see it in the status word of the next run's first collective, or at the launcher)
-  {
-    vgs_status sa = vgs_apply_tile_labels(t->ctx, (int32_t)base[(size_t)c.rank], br.empty() ? &dummy : br.data(), bl.empty() ? &dummy : bl.data(), (int64_t)br.size());
-    if (sa != VGS_OK) { t->pending = sa; return tfail(t, sa, std::string("vgs_apply_tile_labels: ") + vgs_last_error_string(t->ctx)); }
-  }
-  double t6 = now_ms();
-  t->times[VGS_TILES_T_LABELS] = t6 - t5;
-  t->times[VGS_TILES_T_TOTAL] = t6 - t0;
+  // (the run's last collective is behind us: the peers -- whose results are complete -- see a failure here in the status word of the
+  // next collective, or at the launcher)
+  TRY(behind_collective(t, vgs_apply_tile_labels(t->ctx, (int32_t)base[(size_t)c.rank], br.empty() ? &dummy : br.data(), bl.empty() ? &dummy : bl.data(), (int64_t)br.size()),
+                        "vgs_apply_tile_labels"));
+  sw.lap(VGS_TILES_T_LABELS);
+  sw.total(VGS_TILES_T_TOTAL);
   for (RankRecords& R : rec) { R.cnt.clear(); R.cnt.shrink_to_fit(); }
   t->run_rec.swap(rec); t->run_uroot.swap(uroot); t->run_ulabel.swap(ulabel);   // (kept for the segment graph's halo labels; nothing is copied)
   t->ran = true;
@@ -758,67 +914,44 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
 // of status word and record count -> the same host fold on every rank -> the per-segment algebra on this rank's GPU.  Same bytes on every
 // rank: the fold's inputs and order are the same everywhere, and the algebra is one deterministic device function of its inputs.
 // (the table into t->d_*: the collective when it is not cached; vgs_tiles_get_segment_boxes takes the table through here too)
-static vgs_status ensure_descriptors(vgs_tiles* t) {
-  if (!t->desc_valid) {
-    // a rank whose last call failed behind its last collective still comes, with that status; one that never ran does not (nor do its peers)
-    if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_descriptors: vgs_tiles_run first");
-    Comm& c = *t->comm;
-    const int64_t Kg = t->kept;
-    vgs_status carry = t->pending;
-    if (t->fail_phase == 5 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=descriptors"; }
-    const double t0 = now_ms();
-    std::vector<MomentRec> payload(1);
-    if (carry == VGS_OK && Kg > 0) {
-      const size_t k1 = (size_t)Kg;
-      std::vector<int32_t> lab(k1), nn(k1);
-      std::vector<int64_t> np(k1);
-      std::vector<float> bb(6 * k1), an(3 * k1);
-      std::vector<double> sm(9 * k1);
-      int64_t n = 0;
-      TCARRY(vgs_get_own_segment_moments(t->ctx, Kg, &n, lab.data(), np.data(), nn.data(), bb.data(), an.data(), sm.data()));
-      if (carry == VGS_OK) {
-        payload.resize(1 + (size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-          MomentRec& m = payload[1 + (size_t)i];
-          m.label = lab[(size_t)i]; m.n_nodes = nn[(size_t)i]; m.n_points = np[(size_t)i];
-          for (int a = 0; a < 6; ++a) m.bbox[a] = bb[6 * (size_t)i + a];
-          for (int a = 0; a < 3; ++a) m.anchor[a] = an[3 * (size_t)i + a];
-          for (int f = 0; f < 9; ++f) m.s[f] = sm[9 * (size_t)i + f];
-        }
-      }
-    }
-    payload[0].label = (int32_t)carry;
-    payload[0].n_points = (int64_t)payload.size() - 1;
-    const double t1 = now_ms();
-    std::vector<std::vector<MomentRec>> gathered;
-    TCOMM(all_gather_varlen(c, payload, gathered));
-    const double t2 = now_ms();
-    {
-      int bad = -1;
-      for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].empty() || gathered[(size_t)r][0].label != 0) bad = r;
-      vgs_status a = agreed(t, carry, bad, "descriptors");
-      if (a != VGS_OK) return a;
-    }
-    for (std::vector<MomentRec>& g : gathered) g.erase(g.begin());   // the headers
-    std::vector<int64_t> npts;
-    std::vector<int32_t> nnodes;
-    std::vector<float> bbox, anchor;
-    std::vector<double> s9;
-    if (!fold_moments(gathered, Kg, npts, nnodes, bbox, anchor, s9)) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_descriptors: a rank sent a label >= kept_global");
-    const double t3 = now_ms();
-    const size_t k1 = (size_t)Kg;
-    t->d_npts.resize(k1); t->d_nnodes.resize(k1); t->d_bbox.resize(6 * k1); t->d_cen.resize(3 * k1); t->d_cov.resize(6 * k1);
-    t->d_eval.resize(3 * k1); t->d_evec.resize(9 * k1); t->d_eig8.resize(8 * k1);
-    // (local, behind the collective: the rank returns its error and keeps it for the next collective, as the label write-back does)
-    const vgs_status sa = vgs_segment_descriptors_from_moments(t->ctx, Kg, npts.data(), nnodes.data(), bbox.data(), anchor.data(), s9.data(),
-                                                               t->d_npts.data(), t->d_nnodes.data(), t->d_bbox.data(), t->d_cen.data(), t->d_cov.data(),
-                                                               t->d_eval.data(), t->d_evec.data(), t->d_eig8.data());
-    if (sa != VGS_OK) { t->pending = sa; return tfail(t, sa, std::string("vgs_segment_descriptors_from_moments: ") + vgs_last_error_string(t->ctx)); }
-    const double t4 = now_ms();
-    t->dtimes[VGS_TILES_D_MOMENTS] = t1 - t0; t->dtimes[VGS_TILES_D_EXCHANGE] = t2 - t1; t->dtimes[VGS_TILES_D_FOLD] = t3 - t2;
-    t->dtimes[VGS_TILES_D_ALGEBRA] = t4 - t3; t->dtimes[VGS_TILES_D_TOTAL] = t4 - t0;
-    t->desc_valid = true;
+static vgs_status ensure_descriptors(vgs_tiles* t, const char* fn) {   // fn: the caller's name, for the guard's message
+  if (t->desc_valid) return VGS_OK;
+  vgs_status carry;
+  TRY(open_collective(t, fn, PH_DESCRIPTORS, carry));
+  const int64_t Kg = t->kept;
+  const size_t k1 = (size_t)Kg;
+  double ms[VGS_TILES_D_COUNT] = {0};
+  Stopwatch sw(ms);
+  std::vector<MomentRec> payload(1);
+  if (carry == VGS_OK && Kg > 0) {
+    std::vector<int32_t> lab(k1), nn(k1);
+    std::vector<int64_t> np(k1);
+    std::vector<float> bb(6 * k1), an(3 * k1);
+    std::vector<double> sm(9 * k1);
+    int64_t n = 0;
+    TCARRY(vgs_get_own_segment_moments(t->ctx, Kg, &n, lab.data(), np.data(), nn.data(), bb.data(), an.data(), sm.data()));
+    if (carry == VGS_OK) payload.reserve(1 + (size_t)n);
+    if (carry == VGS_OK) for (size_t i = 0; i < (size_t)n; ++i) payload.push_back(pack_moment(lab.data(), np.data(), nn.data(), bb.data(), an.data(), sm.data(), i));
   }
+  set_header(payload[0], carry, payload.size() - 1);
+  sw.lap(VGS_TILES_D_MOMENTS);
+  std::vector<std::vector<MomentRec>> gathered;
+  TRY(exchange(t, carry, payload, "descriptors", sw, VGS_TILES_D_EXCHANGE, gathered));
+  strip_headers(gathered);
+  std::vector<int64_t> npts;
+  std::vector<int32_t> nnodes;
+  std::vector<float> bbox, anchor;
+  std::vector<double> s9;
+  if (!fold_moments(gathered, Kg, npts, nnodes, bbox, anchor, s9)) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_descriptors: a rank sent a label >= kept_global");
+  sw.lap(VGS_TILES_D_FOLD);
+  t->d_npts.resize(k1); t->d_nnodes.resize(k1); t->d_bbox.resize(6 * k1); t->d_cen.resize(3 * k1); t->d_cov.resize(6 * k1);
+  t->d_eval.resize(3 * k1); t->d_evec.resize(9 * k1); t->d_eig8.resize(8 * k1);
+  TRY(behind_collective(t, vgs_segment_descriptors_from_moments(t->ctx, Kg, npts.data(), nnodes.data(), bbox.data(), anchor.data(), s9.data(), t->d_npts.data(), t->d_nnodes.data(),
+                                                                t->d_bbox.data(), t->d_cen.data(), t->d_cov.data(), t->d_eval.data(), t->d_evec.data(), t->d_eig8.data()),
+                        "vgs_segment_descriptors_from_moments"));
+  sw.lap(VGS_TILES_D_ALGEBRA);
+  sw.total(VGS_TILES_D_TOTAL, t->dtimes);
+  t->desc_valid = true;
   return VGS_OK;
 }
 
@@ -827,19 +960,13 @@ vgs_status vgs_tiles_get_segment_descriptors(vgs_tiles* t, int64_t* K, int64_t* 
   if (!t) return VGS_E_ARG;
   if (K) *K = t->kept;
   if (!n_points && !n_nodes && !bbox6 && !centroid3 && !cov6 && !evals3 && !evecs9 && !eigen8) return VGS_OK;   // size query: no collective
-  const vgs_status sd = ensure_descriptors(t);
-  if (sd != VGS_OK) return sd;
-  auto put = [](const auto& v, auto* dst) { if (dst) std::copy(v.begin(), v.end(), dst); };
+  TRY(ensure_descriptors(t, "vgs_tiles_get_segment_descriptors"));
   put(t->d_npts, n_points); put(t->d_nnodes, n_nodes); put(t->d_bbox, bbox6); put(t->d_cen, centroid3); put(t->d_cov, cov6);
   put(t->d_eval, evals3); put(t->d_evec, evecs9); put(t->d_eig8, eigen8);
   return VGS_OK;
 }
 
-vgs_status vgs_tiles_get_descriptor_times(vgs_tiles* t, double* ms, int32_t n) {
-  if (!t || !ms || n < 0 || n > VGS_TILES_D_COUNT) return VGS_E_ARG;
-  for (int i = 0; i < n; ++i) ms[i] = t->dtimes[i];
-  return VGS_OK;
-}
+vgs_status vgs_tiles_get_descriptor_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::dtimes, ms, n); }
 
 // Boxes over the ranks: the global descriptor table (its own collective when it is not cached) -> this rank's extents of its own points
 // about the global centroids, in the frames made from the global rows (one small pipeline on its GPU) -> ONE all_gather_varlen of the
@@ -852,75 +979,53 @@ vgs_status vgs_tiles_get_segment_boxes(vgs_tiles* t, int32_t frame, int64_t* K, 
   if (K) *K = t->kept;
   if (!center3 && !half3 && !frame9 && !lo3 && !hi3) return VGS_OK;   // size query: no collective
   if (!t->box_valid[frame]) {
-    if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_boxes: vgs_tiles_run first");
-    if (!t->desc_valid) {
-      // The descriptor collective ends the call on every rank alike when a status word in it says so.  A failure of this rank BEHIND that
-      // collective (it newly sets t->pending; the peers' tables are complete and they go on) travels in the box exchange's status word.
+    {
+      // The descriptor collective (when the table is not cached; its guard is this call's) ends the call on every rank alike when a status
+      // word in it says so.  A failure of this rank BEHIND that collective (it newly sets t->pending; the peers' tables are complete and they
+      // go on) travels in the box exchange's status word: the opening below takes it up.
       const vgs_status before = t->pending;
-      const vgs_status sd = ensure_descriptors(t);
+      const vgs_status sd = ensure_descriptors(t, "vgs_tiles_get_segment_boxes");
       if (sd != VGS_OK && !(before == VGS_OK && t->pending != VGS_OK)) return sd;
     }
-    Comm& c = *t->comm;
+    vgs_status carry;
+    TRY(open_collective(t, "vgs_tiles_get_segment_boxes", PH_BOXES, carry));
     const int64_t Kg = t->kept;
     const size_t k1 = (size_t)Kg;
-    vgs_status carry = t->pending;
-    if (t->fail_phase == 7 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=boxes"; }
-    const double t0 = now_ms();
+    double ms[VGS_TILES_B_COUNT] = {0};
+    Stopwatch sw(ms);
     std::vector<ExtentRec> payload(1);
     if (carry == VGS_OK && Kg > 0) {
       std::vector<int32_t> lab(k1);
       std::vector<double> lo(3 * k1), hi(3 * k1);
       int64_t n = 0;
       TCARRY(vgs_get_own_segment_extents(t->ctx, Kg, frame, t->d_cen.data(), t->d_cov.data(), t->d_evec.data(), &n, lab.data(), lo.data(), hi.data()));
-      if (carry == VGS_OK) {
-        payload.resize(1 + (size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-          ExtentRec& e = payload[1 + (size_t)i];
-          e.label = lab[(size_t)i];
-          for (int a = 0; a < 3; ++a) { e.lo[a] = lo[3 * (size_t)i + a]; e.hi[a] = hi[3 * (size_t)i + a]; }
-        }
-      }
+      if (carry == VGS_OK) payload.reserve(1 + (size_t)n);
+      if (carry == VGS_OK) for (size_t i = 0; i < (size_t)n; ++i) payload.push_back(pack_extent(lab.data(), lo.data(), hi.data(), i));
     }
-    payload[0].label = (int32_t)carry;
-    payload[0].lo[0] = (double)(payload.size() - 1);
-    const double t1 = now_ms();
+    set_header(payload[0], carry, payload.size() - 1);
+    sw.lap(VGS_TILES_B_EXTENTS);
     std::vector<std::vector<ExtentRec>> gathered;
-    TCOMM(all_gather_varlen(c, payload, gathered));
-    const double t2 = now_ms();
-    {
-      int bad = -1;
-      for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].empty() || gathered[(size_t)r][0].label != 0) bad = r;
-      vgs_status a = agreed(t, carry, bad, "boxes");
-      if (a != VGS_OK) return a;
-    }
-    for (std::vector<ExtentRec>& g : gathered) g.erase(g.begin());   // the headers
+    TRY(exchange(t, carry, payload, "boxes", sw, VGS_TILES_B_EXCHANGE, gathered));
+    strip_headers(gathered);
     std::vector<double> lo, hi;
     std::vector<uint8_t> reached;
     if (!fold_extents(gathered, Kg, lo, hi, reached)) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_boxes: a rank sent a label >= kept_global");
     // a row no record reaches (no labelled point anywhere, n_points = 0 in the descriptor table): lo = hi = 0, so half = 0 and centre = centroid
     for (size_t k = 0; k < k1; ++k) if (!reached[k]) for (int a = 0; a < 3; ++a) { lo[3 * k + a] = 0.0; hi[3 * k + a] = 0.0; }
-    const double t3 = now_ms();
+    sw.lap(VGS_TILES_B_FOLD);
     std::vector<double> ce(3 * k1), ha(3 * k1), fr(9 * k1);
-    // (local, behind the collective: the rank returns its error and keeps it for the next collective, as the label write-back does)
-    const vgs_status sa = vgs_segment_boxes_from_extents(t->ctx, Kg, frame, t->d_cen.data(), t->d_cov.data(), t->d_evec.data(), lo.data(), hi.data(),
-                                                         ce.data(), ha.data(), fr.data());
-    if (sa != VGS_OK) { t->pending = sa; return tfail(t, sa, std::string("vgs_segment_boxes_from_extents: ") + vgs_last_error_string(t->ctx)); }
-    const double t4 = now_ms();
+    TRY(behind_collective(t, vgs_segment_boxes_from_extents(t->ctx, Kg, frame, t->d_cen.data(), t->d_cov.data(), t->d_evec.data(), lo.data(), hi.data(), ce.data(), ha.data(), fr.data()),
+                          "vgs_segment_boxes_from_extents"));
+    sw.lap(VGS_TILES_B_FINISH);
+    sw.total(VGS_TILES_B_TOTAL, t->btimes);
     t->b_center[frame].swap(ce); t->b_half[frame].swap(ha); t->b_frame[frame].swap(fr); t->b_lo[frame].swap(lo); t->b_hi[frame].swap(hi);
-    t->btimes[VGS_TILES_B_EXTENTS] = t1 - t0; t->btimes[VGS_TILES_B_EXCHANGE] = t2 - t1; t->btimes[VGS_TILES_B_FOLD] = t3 - t2;
-    t->btimes[VGS_TILES_B_FINISH] = t4 - t3; t->btimes[VGS_TILES_B_TOTAL] = t4 - t0;
     t->box_valid[frame] = true;
   }
-  auto put = [](const std::vector<double>& v, double* dst) { if (dst) std::copy(v.begin(), v.end(), dst); };
   put(t->b_center[frame], center3); put(t->b_half[frame], half3); put(t->b_frame[frame], frame9); put(t->b_lo[frame], lo3); put(t->b_hi[frame], hi3);
   return VGS_OK;
 }
 
-vgs_status vgs_tiles_get_box_times(vgs_tiles* t, double* ms, int32_t n) {
-  if (!t || !ms || n < 0 || n > VGS_TILES_B_COUNT) return VGS_E_ARG;
-  for (int i = 0; i < n; ++i) ms[i] = t->btimes[i];
-  return VGS_OK;
-}
+vgs_status vgs_tiles_get_box_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::btimes, ms, n); }
 
 // host arithmetic only (tests): the extent fold on flattened per-rank records
 vgs_status vgs_tiles_fold_extents(int world, const int64_t* rec_off, const int32_t* label, const double* lo3, const double* hi3, int64_t K,
@@ -930,12 +1035,7 @@ vgs_status vgs_tiles_fold_extents(int world, const int64_t* rec_off, const int32
   std::vector<std::vector<ExtentRec>> ranks((size_t)world);
   for (int r = 0; r < world; ++r) {
     if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
-    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) {
-      ExtentRec e;
-      e.label = label[i];
-      for (int a = 0; a < 3; ++a) { e.lo[a] = lo3[3 * i + a]; e.hi[a] = hi3[3 * i + a]; }
-      ranks[(size_t)r].push_back(e);
-    }
+    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) ranks[(size_t)r].push_back(pack_extent(label, lo3, hi3, (size_t)i));
   }
   std::vector<double> lo, hi;
   std::vector<uint8_t> reached;
@@ -955,13 +1055,12 @@ static vgs_status tiles_field_stats(vgs_tiles* t, const char* fn, bool on_device
                                     float* vmax) {
   if (!t) return VGS_E_ARG;
   if (K) *K = t->kept;
-  if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, std::string(fn) + ": vgs_tiles_run first");
-  Comm& c = *t->comm;
+  vgs_status carry;
+  TRY(open_collective(t, fn, PH_FIELDS, carry));
   const int64_t Kg = t->kept;
   const size_t k1 = (size_t)Kg;
-  vgs_status carry = t->pending;
-  if (t->fail_phase == 8 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=fields"; }
-  const double t0 = now_ms();
+  double ms[VGS_TILES_F_COUNT] = {0};
+  Stopwatch sw(ms);
   const bool c_ok = n_channels >= 1 && n_channels <= 64;
   const size_t C = c_ok ? (size_t)n_channels : 0;
   std::vector<uint64_t> payload(3, 0);
@@ -973,81 +1072,33 @@ static vgs_status tiles_field_stats(vgs_tiles* t, const char* fn, bool on_device
     std::vector<double> an(cap), m1(cap), m2(cap);
     std::vector<float> mn(cap), mx(cap);
     // (a channel count out of range is refused by the context before it writes: no array is needed)
-    if (on_device) TCARRY(vgs_get_own_segment_field_moments_device(t->ctx, Kg, field, n, n_channels, stride_bytes, &n_rec, c_ok ? lab.data() : nullptr, c_ok ? nv.data() : nullptr, c_ok ? an.data() : nullptr, c_ok ? m1.data() : nullptr, c_ok ? m2.data() : nullptr, c_ok ? mn.data() : nullptr, c_ok ? mx.data() : nullptr));
-    else TCARRY(vgs_get_own_segment_field_moments(t->ctx, Kg, field, n, n_channels, stride_bytes, &n_rec, c_ok ? lab.data() : nullptr, c_ok ? nv.data() : nullptr, c_ok ? an.data() : nullptr, c_ok ? m1.data() : nullptr, c_ok ? m2.data() : nullptr, c_ok ? mn.data() : nullptr, c_ok ? mx.data() : nullptr));
-    if (carry == VGS_OK) {
-      payload.reserve(3 + (size_t)n_rec * (1 + 5 * C));
-      auto bits = [](double v) { uint64_t u; std::memcpy(&u, &v, 8); return u; };
-      for (size_t i = 0; i < (size_t)n_rec; ++i) {
-        payload.push_back((uint64_t)(uint32_t)lab[i]);
-        for (size_t ch = 0; ch < C; ++ch) {
-          const size_t j = i * C + ch;
-          uint32_t lo, hi;
-          std::memcpy(&lo, &mn[j], 4); std::memcpy(&hi, &mx[j], 4);
-          payload.push_back((uint64_t)nv[j]); payload.push_back(bits(an[j])); payload.push_back(bits(m1[j])); payload.push_back(bits(m2[j]));
-          payload.push_back((uint64_t)lo | ((uint64_t)hi << 32));
-        }
-      }
-    } else n_rec = 0;
+    TCARRY_AS(on_device ? vgs_get_own_segment_field_moments_device : vgs_get_own_segment_field_moments,
+              on_device ? "vgs_get_own_segment_field_moments_device" : "vgs_get_own_segment_field_moments", t->ctx, Kg, field, n, n_channels, stride_bytes, &n_rec,
+              c_ok ? lab.data() : nullptr, c_ok ? nv.data() : nullptr, c_ok ? an.data() : nullptr, c_ok ? m1.data() : nullptr, c_ok ? m2.data() : nullptr, c_ok ? mn.data() : nullptr, c_ok ? mx.data() : nullptr);
+    if (carry != VGS_OK) n_rec = 0;
+    payload.reserve(3 + (size_t)n_rec * (1 + 5 * C));
+    for (size_t i = 0; i < (size_t)n_rec; ++i) pack_field(payload, lab.data(), nv.data(), an.data(), m1.data(), m2.data(), mn.data(), mx.data(), C, i);
   }
-  payload[0] = (uint64_t)(uint32_t)carry;
-  payload[1] = (uint64_t)n_rec;
-  payload[2] = (uint64_t)(uint32_t)n_channels;
-  const double t1 = now_ms();
+  set_header(payload, carry, n_rec, (int64_t)(uint32_t)n_channels);
+  sw.lap(VGS_TILES_F_OWN);
   std::vector<std::vector<uint64_t>> gathered;
-  TCOMM(all_gather_varlen(c, payload, gathered));
-  const double t2 = now_ms();
-  {
-    int bad = -1;
-    for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].size() < 3 || gathered[(size_t)r][0] != 0) bad = r;
-    vgs_status a = agreed(t, carry, bad, "fields");
-    if (a != VGS_OK) return a;
-  }
-  for (int r = 1; r < c.world; ++r)   // every rank valid on its own, but not the same table
-    if (gathered[(size_t)r][2] != gathered[0][2])
-      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed n_channels = " + std::to_string((int32_t)gathered[(size_t)r][2]) +
-                                     ", rank 0 passed " + std::to_string((int32_t)gathered[0][2]));
-  std::vector<FieldRecs> recs((size_t)c.world);
-  for (int r = 0; r < c.world; ++r) {
-    const std::vector<uint64_t>& g = gathered[(size_t)r];
-    const size_t nr = (size_t)g[1];
-    if (g.size() != 3 + nr * (1 + 5 * C)) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
-    FieldRecs& R = recs[(size_t)r];
-    R.label.resize(nr); R.n.resize(nr * C); R.a.resize(nr * C); R.s1.resize(nr * C); R.s2.resize(nr * C); R.mn.resize(nr * C); R.mx.resize(nr * C);
-    const uint64_t* w = g.data() + 3;
-    auto dbl = [](uint64_t u) { double v; std::memcpy(&v, &u, 8); return v; };
-    for (size_t i = 0; i < nr; ++i) {
-      R.label[i] = (int32_t)(uint32_t)*w++;
-      for (size_t ch = 0; ch < C; ++ch) {
-        const size_t j = i * C + ch;
-        R.n[j] = (int64_t)w[0]; R.a[j] = dbl(w[1]); R.s1[j] = dbl(w[2]); R.s2[j] = dbl(w[3]);
-        const uint32_t lo = (uint32_t)w[4], hi = (uint32_t)(w[4] >> 32);
-        std::memcpy(&R.mn[j], &lo, 4); std::memcpy(&R.mx[j], &hi, 4);
-        w += 5;
-      }
-    }
-  }
+  TRY(exchange(t, carry, payload, "fields", sw, VGS_TILES_F_EXCHANGE, gathered));
+  TRY(check_word_payloads(t, fn, gathered, 1 + 5 * C, "n_channels"));
+  std::vector<FieldRecs> recs(gathered.size());
+  for (size_t r = 0; r < gathered.size(); ++r) unpack_fields(gathered[r].data() + 3, (size_t)gathered[r][1], C, recs[r]);
   std::vector<int64_t> fn_;
   std::vector<double> fa, f1, f2;
   std::vector<float> fmn, fmx;
   if (!fold_field_moments(recs, Kg, (int)C, fn_, fa, f1, f2, fmn, fmx)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= kept_global");
-  const double t3 = now_ms();
+  sw.lap(VGS_TILES_F_FOLD);
   const size_t kc = k1 * C;
   std::vector<double> me(kc + 1), va(kc + 1);
   std::vector<float> omn(kc + 1), omx(kc + 1);
-  // (local, behind the collective: the rank returns its error and keeps it for the next collective, as the label write-back does)
-  const vgs_status sa = vgs_segment_field_stats_from_moments(t->ctx, Kg, n_channels, fn_.data(), fa.data(), f1.data(), f2.data(), fmn.data(), fmx.data(),
-                                                             me.data(), va.data(), omn.data(), omx.data());
-  if (sa != VGS_OK) { t->pending = sa; return tfail(t, sa, std::string("vgs_segment_field_stats_from_moments: ") + vgs_last_error_string(t->ctx)); }
-  const double t4 = now_ms();
-  if (n_valid) std::copy(fn_.begin(), fn_.end(), n_valid);
-  if (anchor) std::copy(fa.begin(), fa.end(), anchor);
-  if (mean) std::copy(me.begin(), me.begin() + (ptrdiff_t)kc, mean);
-  if (var) std::copy(va.begin(), va.begin() + (ptrdiff_t)kc, var);
-  if (vmin) std::copy(omn.begin(), omn.begin() + (ptrdiff_t)kc, vmin);
-  if (vmax) std::copy(omx.begin(), omx.begin() + (ptrdiff_t)kc, vmax);
-  t->ftimes[VGS_TILES_F_OWN] = t1 - t0; t->ftimes[VGS_TILES_F_EXCHANGE] = t2 - t1; t->ftimes[VGS_TILES_F_FOLD] = t3 - t2;
-  t->ftimes[VGS_TILES_F_FINISH] = t4 - t3; t->ftimes[VGS_TILES_F_TOTAL] = t4 - t0;
+  TRY(behind_collective(t, vgs_segment_field_stats_from_moments(t->ctx, Kg, n_channels, fn_.data(), fa.data(), f1.data(), f2.data(), fmn.data(), fmx.data(), me.data(), va.data(), omn.data(), omx.data()),
+                        "vgs_segment_field_stats_from_moments"));
+  sw.lap(VGS_TILES_F_FINISH);
+  sw.total(VGS_TILES_F_TOTAL, t->ftimes);
+  put(fn_, n_valid); put(fa, anchor); put(me, mean, kc); put(va, var, kc); put(omn, vmin, kc); put(omx, vmax, kc);
   t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(uint64_t));
   return VGS_OK;
 }
@@ -1069,13 +1120,12 @@ static vgs_status tiles_class_hist(vgs_tiles* t, const char* fn, bool on_device,
                                    int64_t* hist, int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
   if (!t) return VGS_E_ARG;
   if (K) *K = t->kept;
-  if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, std::string(fn) + ": vgs_tiles_run first");
-  Comm& c = *t->comm;
+  vgs_status carry;
+  TRY(open_collective(t, fn, PH_FIELDS, carry));
   const int64_t Kg = t->kept;
   const size_t k1 = (size_t)Kg;
-  vgs_status carry = t->pending;
-  if (t->fail_phase == 8 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=fields"; }
-  const double t0 = now_ms();
+  double ms[VGS_TILES_F_COUNT] = {0};
+  Stopwatch sw(ms);
   const bool c_ok = n_classes >= 1 && n_classes <= 1024 && Kg * (int64_t)n_classes <= ((int64_t)1 << 27);
   const size_t nc = c_ok ? (size_t)n_classes : 0;
   std::vector<int64_t> payload(3, 0);
@@ -1084,57 +1134,26 @@ static vgs_status tiles_class_hist(vgs_tiles* t, const char* fn, bool on_device,
     std::vector<int32_t> lab(k1 + 1);
     std::vector<int64_t> hi(k1 * nc + 1), no(k1 + 1);
     // (a class count out of range is refused by the context before it writes: no array is needed)
-    if (on_device) TCARRY(vgs_get_own_segment_class_counts_device(t->ctx, Kg, cls, n, n_classes, &n_rec, c_ok ? lab.data() : nullptr, c_ok ? hi.data() : nullptr, c_ok ? no.data() : nullptr));
-    else TCARRY(vgs_get_own_segment_class_counts(t->ctx, Kg, cls, n, n_classes, &n_rec, c_ok ? lab.data() : nullptr, c_ok ? hi.data() : nullptr, c_ok ? no.data() : nullptr));
-    if (carry == VGS_OK) {
-      payload.reserve(3 + (size_t)n_rec * (2 + nc));
-      for (size_t i = 0; i < (size_t)n_rec; ++i) {
-        payload.push_back((int64_t)lab[i]); payload.push_back(no[i]);
-        payload.insert(payload.end(), hi.begin() + (ptrdiff_t)(i * nc), hi.begin() + (ptrdiff_t)((i + 1) * nc));
-      }
-    } else n_rec = 0;
+    TCARRY_AS(on_device ? vgs_get_own_segment_class_counts_device : vgs_get_own_segment_class_counts,
+              on_device ? "vgs_get_own_segment_class_counts_device" : "vgs_get_own_segment_class_counts", t->ctx, Kg, cls, n, n_classes, &n_rec,
+              c_ok ? lab.data() : nullptr, c_ok ? hi.data() : nullptr, c_ok ? no.data() : nullptr);
+    if (carry != VGS_OK) n_rec = 0;
+    payload.reserve(3 + (size_t)n_rec * (2 + nc));
+    for (size_t i = 0; i < (size_t)n_rec; ++i) pack_class(payload, lab.data(), hi.data(), no.data(), nc, i);
   }
-  payload[0] = (int64_t)carry;
-  payload[1] = n_rec;
-  payload[2] = (int64_t)n_classes;
-  const double t1 = now_ms();
+  set_header(payload, carry, n_rec, (int64_t)n_classes);
+  sw.lap(VGS_TILES_F_OWN);
   std::vector<std::vector<int64_t>> gathered;
-  TCOMM(all_gather_varlen(c, payload, gathered));
-  const double t2 = now_ms();
-  {
-    int bad = -1;
-    for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].size() < 3 || gathered[(size_t)r][0] != 0) bad = r;
-    vgs_status a = agreed(t, carry, bad, "fields");
-    if (a != VGS_OK) return a;
-  }
-  for (int r = 1; r < c.world; ++r)   // every rank valid on its own, but not the same table
-    if (gathered[(size_t)r][2] != gathered[0][2])
-      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed n_classes = " + std::to_string(gathered[(size_t)r][2]) +
-                                     ", rank 0 passed " + std::to_string(gathered[0][2]));
-  std::vector<ClassRecs> recs((size_t)c.world);
-  for (int r = 0; r < c.world; ++r) {
-    const std::vector<int64_t>& g = gathered[(size_t)r];
-    const size_t nr = (size_t)g[1];
-    if (g.size() != 3 + nr * (2 + nc)) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
-    ClassRecs& R = recs[(size_t)r];
-    R.label.resize(nr); R.n_outside.resize(nr); R.hist.resize(nr * nc);
-    const int64_t* w = g.data() + 3;
-    for (size_t i = 0; i < nr; ++i) {
-      R.label[i] = (int32_t)w[0]; R.n_outside[i] = w[1];
-      std::copy(w + 2, w + 2 + nc, R.hist.begin() + (ptrdiff_t)(i * nc));
-      w += 2 + nc;
-    }
-  }
+  TRY(exchange(t, carry, payload, "fields", sw, VGS_TILES_F_EXCHANGE, gathered));
+  TRY(check_word_payloads(t, fn, gathered, 2 + nc, "n_classes"));
+  std::vector<ClassRecs> recs(gathered.size());
+  for (size_t r = 0; r < gathered.size(); ++r) unpack_classes(gathered[r].data() + 3, (size_t)gathered[r][1], nc, recs[r]);
   std::vector<int64_t> fh, fo, fc;
   std::vector<int32_t> fm;
   if (!fold_class_counts(recs, Kg, (int)nc, fh, fo, fm, fc)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= kept_global");
-  const double t3 = now_ms();
-  if (hist) std::copy(fh.begin(), fh.end(), hist);
-  if (n_outside) std::copy(fo.begin(), fo.end(), n_outside);
-  if (majority) std::copy(fm.begin(), fm.end(), majority);
-  if (majority_count) std::copy(fc.begin(), fc.end(), majority_count);
-  t->ftimes[VGS_TILES_F_OWN] = t1 - t0; t->ftimes[VGS_TILES_F_EXCHANGE] = t2 - t1; t->ftimes[VGS_TILES_F_FOLD] = t3 - t2;
-  t->ftimes[VGS_TILES_F_FINISH] = 0.0; t->ftimes[VGS_TILES_F_TOTAL] = t3 - t0;   // (the majority rule is integer work inside the fold)
+  sw.lap(VGS_TILES_F_FOLD);
+  sw.total(VGS_TILES_F_TOTAL, t->ftimes);   // (VGS_TILES_F_FINISH stays 0: the majority rule is integer work inside the fold)
+  put(fh, hist); put(fo, n_outside); put(fm, majority); put(fc, majority_count);
   t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(int64_t));
   return VGS_OK;
 }
@@ -1149,11 +1168,7 @@ vgs_status vgs_tiles_segment_class_histogram_device(vgs_tiles* t, const int32_t*
   return tiles_class_hist(t, "vgs_tiles_segment_class_histogram_device", true, cls_dev, n, n_classes, K, hist, n_outside, majority, majority_count);
 }
 
-vgs_status vgs_tiles_get_field_times(vgs_tiles* t, double* ms, int32_t n) {
-  if (!t || !ms || n < 0 || n > VGS_TILES_F_COUNT) return VGS_E_ARG;
-  for (int i = 0; i < n; ++i) ms[i] = t->ftimes[i];
-  return VGS_OK;
-}
+vgs_status vgs_tiles_get_field_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::ftimes, ms, n); }
 
 vgs_status vgs_tiles_get_field_payload(vgs_tiles* t, int64_t* own_records, int64_t* bytes_sent) {
   if (!t) return VGS_E_ARG;
@@ -1173,18 +1188,16 @@ static vgs_status tiles_compare(vgs_tiles* t, const char* fn, bool on_device, co
                                 int64_t* n_refs, int64_t* summary) {
   if (!t) return VGS_E_ARG;
   if (K) *K = t->kept;
-  if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, std::string(fn) + ": vgs_tiles_run first");
-  Comm& c = *t->comm;
+  vgs_status carry;
+  TRY(open_collective(t, fn, PH_COMPARE, carry));
   const int64_t Kg = t->kept;
   t->cmp_valid = false;
-  vgs_status carry = t->pending;
-  if (t->fail_phase == 9 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=compare"; }
-  const double t0 = now_ms();
+  double ms[VGS_TILES_C_COUNT] = {0};
+  Stopwatch sw(ms);
   std::vector<int64_t> payload(3, 0);
   int64_t n_own_cells = 0, n_unann = 0;
   if (carry == VGS_OK) {
-    if (on_device) TCARRY(vgs_own_label_cells_device(t->ctx, Kg, ref, n, &n_own_cells, &n_unann));
-    else TCARRY(vgs_own_label_cells(t->ctx, Kg, ref, n, &n_own_cells, &n_unann));
+    TCARRY_AS(on_device ? vgs_own_label_cells_device : vgs_own_label_cells, on_device ? "vgs_own_label_cells_device" : "vgs_own_label_cells", t->ctx, Kg, ref, n, &n_own_cells, &n_unann);
     std::vector<int32_t> cs((size_t)n_own_cells + 1), cr((size_t)n_own_cells + 1);
     std::vector<int64_t> cn((size_t)n_own_cells + 1);
     if (carry == VGS_OK) TCARRY(vgs_get_own_label_cells(t->ctx, cs.data(), cr.data(), cn.data()));
@@ -1196,43 +1209,26 @@ static vgs_status tiles_compare(vgs_tiles* t, const char* fn, bool on_device, co
       }
     } else { n_own_cells = 0; n_unann = 0; }
   }
-  payload[0] = (int64_t)carry;
-  payload[1] = n_own_cells;
-  payload[2] = n_unann;
-  const double t1 = now_ms();
+  set_header(payload, carry, n_own_cells, n_unann);
+  sw.lap(VGS_TILES_C_OWN);
   std::vector<std::vector<int64_t>> gathered;
-  TCOMM(all_gather_varlen(c, payload, gathered));
-  const double t2 = now_ms();
-  {
-    int bad = -1;
-    for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].size() < 3 || gathered[(size_t)r][0] != 0) bad = r;
-    vgs_status a = agreed(t, carry, bad, "compare");
-    if (a != VGS_OK) return a;
-  }
+  TRY(exchange(t, carry, payload, "compare", sw, VGS_TILES_C_EXCHANGE, gathered));
+  TRY(check_word_payloads(t, fn, gathered, 2, nullptr));
   size_t n_in = 0;
   int64_t unann = 0;
-  for (int r = 0; r < c.world; ++r) {
-    const std::vector<int64_t>& g = gathered[(size_t)r];
-    if (g[1] < 0 || g.size() != 3 + 2 * (size_t)g[1]) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
-    n_in += (size_t)g[1];
-    unann += g[2];
-  }
+  for (const std::vector<int64_t>& g : gathered) { n_in += (size_t)g[1]; unann += g[2]; }
   std::vector<int32_t> as(n_in + 1), ar(n_in + 1);
   std::vector<int64_t> an(n_in + 1);
   size_t o = 0;
-  for (int r = 0; r < c.world; ++r) {
-    const std::vector<int64_t>& g = gathered[(size_t)r];
+  for (const std::vector<int64_t>& g : gathered) {
     for (size_t i = 0; i < (size_t)g[1]; ++i, ++o) {
       const uint64_t w = (uint64_t)g[3 + 2 * i];
       as[o] = (int32_t)(uint32_t)(w >> 32) - 1; ar[o] = (int32_t)(uint32_t)w; an[o] = g[4 + 2 * i];
     }
   }
-  // (local, behind the collective: the rank returns its error and keeps it for the next collective, as the label write-back does)
-  const vgs_status sa = vgs_label_comparison_from_cells(t->ctx, Kg, (int64_t)n_in, as.data(), ar.data(), an.data(), unann, n_cells, n_refs, summary);
-  if (sa != VGS_OK) { t->pending = sa; return tfail(t, sa, std::string("vgs_label_comparison_from_cells: ") + vgs_last_error_string(t->ctx)); }
-  const double t3 = now_ms();
-  t->ctimes[VGS_TILES_C_OWN] = t1 - t0; t->ctimes[VGS_TILES_C_EXCHANGE] = t2 - t1; t->ctimes[VGS_TILES_C_TABLES] = t3 - t2;
-  t->ctimes[VGS_TILES_C_TOTAL] = t3 - t0;
+  TRY(behind_collective(t, vgs_label_comparison_from_cells(t->ctx, Kg, (int64_t)n_in, as.data(), ar.data(), an.data(), unann, n_cells, n_refs, summary), "vgs_label_comparison_from_cells"));
+  sw.lap(VGS_TILES_C_TABLES);
+  sw.total(VGS_TILES_C_TOTAL, t->ctimes);
   t->c_own = n_own_cells; t->c_bytes = (int64_t)(payload.size() * sizeof(int64_t));
   t->cmp_valid = true;
   return VGS_OK;
@@ -1258,11 +1254,7 @@ vgs_status vgs_tiles_get_label_comparison(vgs_tiles* t, int32_t* cell_seg, int32
   return VGS_OK;
 }
 
-vgs_status vgs_tiles_get_compare_times(vgs_tiles* t, double* ms, int32_t n) {
-  if (!t || !ms || n < 0 || n > VGS_TILES_C_COUNT) return VGS_E_ARG;
-  for (int i = 0; i < n; ++i) ms[i] = t->ctimes[i];
-  return VGS_OK;
-}
+vgs_status vgs_tiles_get_compare_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::ctimes, ms, n); }
 
 vgs_status vgs_tiles_get_compare_payload(vgs_tiles* t, int64_t* own_cells, int64_t* bytes_sent) {
   if (!t) return VGS_E_ARG;
@@ -1282,12 +1274,9 @@ vgs_status vgs_tiles_fold_field_moments(int world, const int64_t* rec_off, const
   std::vector<FieldRecs> ranks((size_t)world);
   for (int r = 0; r < world; ++r) {
     if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
-    const size_t i0 = (size_t)rec_off[r], i1 = (size_t)rec_off[r + 1];
-    FieldRecs& R = ranks[(size_t)r];
-    R.label.assign(label + i0, label + i1);
-    R.n.assign(n_valid + i0 * C, n_valid + i1 * C); R.a.assign(anchor + i0 * C, anchor + i1 * C);
-    R.s1.assign(s1 + i0 * C, s1 + i1 * C); R.s2.assign(s2 + i0 * C, s2 + i1 * C);
-    R.mn.assign(vmin + i0 * C, vmin + i1 * C); R.mx.assign(vmax + i0 * C, vmax + i1 * C);
+    std::vector<uint64_t> w;   // through the wire words, as in the collective
+    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) pack_field(w, label, n_valid, anchor, s1, s2, vmin, vmax, C, (size_t)i);
+    unpack_fields(w.data(), (size_t)(rec_off[r + 1] - rec_off[r]), C, ranks[(size_t)r]);
   }
   std::vector<int64_t> n;
   std::vector<double> a, m1, m2;
@@ -1308,11 +1297,9 @@ vgs_status vgs_tiles_fold_class_counts(int world, const int64_t* rec_off, const 
   std::vector<ClassRecs> ranks((size_t)world);
   for (int r = 0; r < world; ++r) {
     if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
-    const size_t i0 = (size_t)rec_off[r], i1 = (size_t)rec_off[r + 1];
-    ClassRecs& R = ranks[(size_t)r];
-    R.label.assign(label + i0, label + i1);
-    R.n_outside.assign(n_outside + i0, n_outside + i1);
-    R.hist.assign(hist + i0 * nc, hist + i1 * nc);
+    std::vector<int64_t> w;   // through the wire words, as in the collective
+    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) pack_class(w, label, hist, n_outside, nc, (size_t)i);
+    unpack_classes(w.data(), (size_t)(rec_off[r + 1] - rec_off[r]), nc, ranks[(size_t)r]);
   }
   std::vector<int64_t> h, o, mc;
   std::vector<int32_t> m;
@@ -1330,12 +1317,12 @@ vgs_status vgs_tiles_get_segment_graph(vgs_tiles* t, int64_t* n_edges, int32_t* 
   if (!t || !n_edges) return VGS_E_ARG;
   *n_edges = 0;
   if (!t->graph_valid) {
-    if (!t->ran && t->pending == VGS_OK) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_graph: vgs_tiles_run first");
+    vgs_status carry;
+    TRY(open_collective(t, "vgs_tiles_get_segment_graph", PH_GRAPH, carry));
     Comm& c = *t->comm;
     const int64_t Kg = t->kept;
-    vgs_status carry = t->pending;
-    if (t->fail_phase == 6 && carry == VGS_OK) { carry = VGS_E_STATE; t->err = "failure requested by VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=graph"; }
-    const double t0 = now_ms();
+    double ms[VGS_TILES_G_COUNT] = {0};
+    Stopwatch sw(ms);
     // (code, global label) of every boundary record of the other ranks: a voxel this rank holds in its halo and counts pairs with has one
     std::vector<uint64_t> hcode;
     std::vector<int32_t> hlab;
@@ -1355,7 +1342,7 @@ vgs_status vgs_tiles_get_segment_graph(vgs_tiles* t, int64_t* n_edges, int32_t* 
     const uint64_t no_code = 0;
     const int32_t no_lab = 0;
     TCARRY(vgs_set_halo_labels(t->ctx, hcode.empty() ? &no_code : hcode.data(), hlab.empty() ? &no_lab : hlab.data(), (int64_t)hcode.size()));
-    const double t1 = now_ms();
+    sw.lap(VGS_TILES_G_HALO);
     std::vector<EdgeRec> payload(1);
     if (carry == VGS_OK) {
       int64_t E = 0;
@@ -1367,56 +1354,28 @@ vgs_status vgs_tiles_get_segment_graph(vgs_tiles* t, int64_t* n_edges, int32_t* 
         std::vector<double> ws(e1);
         std::vector<float> mn(e1), mx(e1);
         TCARRY(vgs_get_own_segment_graph(t->ctx, Kg, &E, ab.data(), np.data(), nf.data(), nd.data(), ws.data(), mn.data(), mx.data()));
-        if (carry == VGS_OK) {
-          payload.resize(1 + e1);
-          for (size_t i = 0; i < e1; ++i) {
-            EdgeRec& e = payload[1 + i];
-            e.a = ab[2 * i]; e.b = ab[2 * i + 1]; e.n_pairs = np[i]; e.n_finite = nf[i]; e.nodes_a = nd[2 * i]; e.nodes_b = nd[2 * i + 1];
-            e.w_sum = ws[i]; e.w_min = mn[i]; e.w_max = mx[i];
-          }
-        }
+        if (carry == VGS_OK) payload.reserve(1 + e1);
+        if (carry == VGS_OK) for (size_t i = 0; i < e1; ++i) payload.push_back(pack_edge(ab.data(), np.data(), nf.data(), nd.data(), ws.data(), mn.data(), mx.data(), i));
       }
     }
-    payload[0].a = (int32_t)carry;
-    payload[0].n_pairs = (int64_t)payload.size() - 1;
-    const double t2 = now_ms();
+    set_header(payload[0], carry, payload.size() - 1);
+    sw.lap(VGS_TILES_G_OWN);
     std::vector<std::vector<EdgeRec>> gathered;
-    TCOMM(all_gather_varlen(c, payload, gathered));
-    const double t3 = now_ms();
-    {
-      int bad = -1;
-      for (int r = 0; r < c.world && bad < 0; ++r) if (gathered[(size_t)r].empty() || gathered[(size_t)r][0].a != 0) bad = r;
-      vgs_status a = agreed(t, carry, bad, "graph");
-      if (a != VGS_OK) return a;
-    }
-    for (std::vector<EdgeRec>& g : gathered) g.erase(g.begin());   // the headers
+    TRY(exchange(t, carry, payload, "graph", sw, VGS_TILES_G_EXCHANGE, gathered));
+    strip_headers(gathered);
     if (!fold_edges(gathered, Kg, t->graph)) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_graph: a rank sent a table that is not sorted or names a label >= kept_global");
-    const double t4 = now_ms();
-    t->gtimes[VGS_TILES_G_HALO] = t1 - t0; t->gtimes[VGS_TILES_G_OWN] = t2 - t1; t->gtimes[VGS_TILES_G_EXCHANGE] = t3 - t2;
-    t->gtimes[VGS_TILES_G_FOLD] = t4 - t3; t->gtimes[VGS_TILES_G_TOTAL] = t4 - t0;
+    sw.lap(VGS_TILES_G_FOLD);
+    sw.total(VGS_TILES_G_TOTAL, t->gtimes);
     t->g_halo = (int64_t)hcode.size(); t->g_own = (int64_t)payload.size() - 1; t->g_bytes = (int64_t)(payload.size() * sizeof(EdgeRec));
     t->graph_valid = true;
   }
   const size_t E = t->graph.size();
   *n_edges = (int64_t)E;
-  for (size_t i = 0; i < E; ++i) {
-    const EdgeRec& e = t->graph[i];
-    if (seg_ab) { seg_ab[2 * i] = e.a; seg_ab[2 * i + 1] = e.b; }
-    if (n_pairs) n_pairs[i] = e.n_pairs;
-    if (n_finite) n_finite[i] = e.n_finite;
-    if (nodes_ab) { nodes_ab[2 * i] = e.nodes_a; nodes_ab[2 * i + 1] = e.nodes_b; }
-    if (w_sum) w_sum[i] = e.w_sum;
-    if (w_min) w_min[i] = e.w_min;
-    if (w_max) w_max[i] = e.w_max;
-  }
+  for (size_t i = 0; i < E; ++i) unpack_edge(t->graph[i], i, seg_ab, n_pairs, n_finite, nodes_ab, w_sum, w_min, w_max);
   return VGS_OK;
 }
 
-vgs_status vgs_tiles_get_graph_times(vgs_tiles* t, double* ms, int32_t n) {
-  if (!t || !ms || n < 0 || n > VGS_TILES_G_COUNT) return VGS_E_ARG;
-  for (int i = 0; i < n; ++i) ms[i] = t->gtimes[i];
-  return VGS_OK;
-}
+vgs_status vgs_tiles_get_graph_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::gtimes, ms, n); }
 
 vgs_status vgs_tiles_get_graph_payload(vgs_tiles* t, int64_t* halo_labels, int64_t* own_edges, int64_t* bytes_sent) {
   if (!t) return VGS_E_ARG;
@@ -1438,25 +1397,11 @@ vgs_status vgs_tiles_fold_edges(int world, const int64_t* rec_off, const int32_t
   if (rec_off[world] > 0 && (!seg_ab || !n_pairs || !n_finite || !nodes_ab || !w_sum || !w_min || !w_max)) return VGS_E_ARG;
   std::vector<std::vector<EdgeRec>> ranks((size_t)world);
   for (int r = 0; r < world; ++r)
-    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) {
-      EdgeRec e;
-      e.a = seg_ab[2 * i]; e.b = seg_ab[2 * i + 1]; e.n_pairs = n_pairs[i]; e.n_finite = n_finite[i]; e.nodes_a = nodes_ab[2 * i];
-      e.nodes_b = nodes_ab[2 * i + 1]; e.w_sum = w_sum[i]; e.w_min = w_min[i]; e.w_max = w_max[i];
-      ranks[(size_t)r].push_back(e);
-    }
+    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) ranks[(size_t)r].push_back(pack_edge(seg_ab, n_pairs, n_finite, nodes_ab, w_sum, w_min, w_max, (size_t)i));
   std::vector<EdgeRec> out;
   if (!fold_edges(ranks, K, out)) return VGS_E_ARG;
   *n_edges = (int64_t)out.size();
-  for (size_t i = 0; i < out.size(); ++i) {
-    const EdgeRec& e = out[i];
-    if (seg_ab_out) { seg_ab_out[2 * i] = e.a; seg_ab_out[2 * i + 1] = e.b; }
-    if (n_pairs_out) n_pairs_out[i] = e.n_pairs;
-    if (n_finite_out) n_finite_out[i] = e.n_finite;
-    if (nodes_ab_out) { nodes_ab_out[2 * i] = e.nodes_a; nodes_ab_out[2 * i + 1] = e.nodes_b; }
-    if (w_sum_out) w_sum_out[i] = e.w_sum;
-    if (w_min_out) w_min_out[i] = e.w_min;
-    if (w_max_out) w_max_out[i] = e.w_max;
-  }
+  for (size_t i = 0; i < out.size(); ++i) unpack_edge(out[i], i, seg_ab_out, n_pairs_out, n_finite_out, nodes_ab_out, w_sum_out, w_min_out, w_max_out);
   return VGS_OK;
 }
 
@@ -1469,14 +1414,7 @@ vgs_status vgs_tiles_fold_moments(int world, const int64_t* rec_off, const int32
   std::vector<std::vector<MomentRec>> ranks((size_t)world);
   for (int r = 0; r < world; ++r) {
     if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
-    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) {
-      MomentRec m;
-      m.label = label[i]; m.n_nodes = n_nodes[i]; m.n_points = n_points[i];
-      for (int a = 0; a < 6; ++a) m.bbox[a] = bbox6[6 * i + a];
-      for (int a = 0; a < 3; ++a) m.anchor[a] = anchor3[3 * i + a];
-      for (int f = 0; f < 9; ++f) m.s[f] = s9[9 * i + f];
-      ranks[(size_t)r].push_back(m);
-    }
+    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) ranks[(size_t)r].push_back(pack_moment(label, n_points, n_nodes, bbox6, anchor3, s9, (size_t)i));
   }
   std::vector<int64_t> np;
   std::vector<int32_t> nn;

@@ -391,10 +391,20 @@ class NativeTiles:
     def run(self):
         self._ck(self._L.vgs_tiles_run(self._h))
 
+    def _times(self, getter, names):
+        """one of the driver's phase clocks on this rank: name -> milliseconds of host wall time"""
+        t = np.zeros(len(names), dtype=np.float64)
+        self._ck(getter(self._h, _vp(t), len(names)))
+        return dict(zip(names, (float(x) for x in t)))
+
+    def _payload(self, getter, names):
+        """one of the driver's payload counters on this rank: name -> int64"""
+        v = [C.c_int64(0) for _ in names]
+        self._ck(getter(self._h, *(C.byref(x) for x in v)))
+        return dict(zip(names, (x.value for x in v)))
+
     def times(self):
-        t = np.zeros(len(T_NAMES), dtype=np.float64)
-        self._ck(self._L.vgs_tiles_get_times(self._h, t.ctypes.data_as(C.c_void_p), len(T_NAMES)))
-        return dict(zip(T_NAMES, (float(x) for x in t)))
+        return self._times(self._L.vgs_tiles_get_times, T_NAMES)
 
     def point_labels(self):
         out = np.zeros(max(self.n, 1), dtype=np.int32)
@@ -418,9 +428,7 @@ class NativeTiles:
 
     def descriptor_times(self):
         """the last descriptor collective's phases on this rank, milliseconds (D_NAMES)"""
-        t = np.zeros(len(D_NAMES), dtype=np.float64)
-        self._ck(self._L.vgs_tiles_get_descriptor_times(self._h, _vp(t), len(D_NAMES)))
-        return dict(zip(D_NAMES, (float(x) for x in t)))
+        return self._times(self._L.vgs_tiles_get_descriptor_times, D_NAMES)
 
     def segment_graph(self):
         """COLLECTIVE on its first call after run() (every rank makes it): the adjacency graph of the global segments over all ranks,
@@ -436,15 +444,11 @@ class NativeTiles:
 
     def graph_times(self):
         """the last graph collective's phases on this rank, milliseconds (G_NAMES)"""
-        t = np.zeros(len(G_NAMES), dtype=np.float64)
-        self._ck(self._L.vgs_tiles_get_graph_times(self._h, _vp(t), len(G_NAMES)))
-        return dict(zip(G_NAMES, (float(x) for x in t)))
+        return self._times(self._L.vgs_tiles_get_graph_times, G_NAMES)
 
     def graph_payload(self):
         """the last graph collective's payload on this rank: halo labels handed to the context, edges of its own table, bytes sent"""
-        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        self._ck(self._L.vgs_tiles_get_graph_payload(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return dict(halo_labels=a.value, own_edges=b.value, bytes_sent=c.value)
+        return self._payload(self._L.vgs_tiles_get_graph_payload, ("halo_labels", "own_edges", "bytes_sent"))
 
     def own_segment_graph(self, K):
         """this rank's partial edge table over the global labels 0 .. K-1 (vgs_get_own_segment_graph on its context; local, no
@@ -477,9 +481,7 @@ class NativeTiles:
 
     def box_times(self):
         """the last box collective's phases on this rank, milliseconds (B_NAMES)"""
-        t = np.zeros(len(B_NAMES), dtype=np.float64)
-        self._ck(self._L.vgs_tiles_get_box_times(self._h, _vp(t), len(B_NAMES)))
-        return dict(zip(B_NAMES, (float(x) for x in t)))
+        return self._times(self._L.vgs_tiles_get_box_times, B_NAMES)
 
     def own_segment_extents(self, K, frame, d):
         """this rank's extent records of the global labels 0 .. K-1 (vgs_get_own_segment_extents on its context; local, no collective)
@@ -555,15 +557,11 @@ class NativeTiles:
 
     def compare_times(self):
         """the last compare_labels()'s phases on this rank, milliseconds (C_NAMES)"""
-        t = np.zeros(len(C_NAMES), dtype=np.float64)
-        self._ck(self._L.vgs_tiles_get_compare_times(self._h, _vp(t), len(C_NAMES)))
-        return dict(zip(C_NAMES, (float(x) for x in t)))
+        return self._times(self._L.vgs_tiles_get_compare_times, C_NAMES)
 
     def compare_payload(self):
         """the last compare_labels()'s payload on this rank: cells of its own, bytes sent"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        self._ck(self._L.vgs_tiles_get_compare_payload(self._h, C.byref(a), C.byref(b)))
-        return dict(own_cells=a.value, bytes_sent=b.value)
+        return self._payload(self._L.vgs_tiles_get_compare_payload, ("own_cells", "bytes_sent"))
 
     def own_label_cells(self, K, ref):
         """this rank's contingency cells of the global labels -1 .. K-1 over its own points (vgs_own_label_cells on its context; local, no
@@ -595,15 +593,11 @@ class NativeTiles:
 
     def field_times(self):
         """the last attribute collective's phases on this rank, milliseconds (F_NAMES)"""
-        t = np.zeros(len(F_NAMES), dtype=np.float64)
-        self._ck(self._L.vgs_tiles_get_field_times(self._h, _vp(t), len(F_NAMES)))
-        return dict(zip(F_NAMES, (float(x) for x in t)))
+        return self._times(self._L.vgs_tiles_get_field_times, F_NAMES)
 
     def field_payload(self):
         """the last attribute collective's payload on this rank: records of its own, bytes sent"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        self._ck(self._L.vgs_tiles_get_field_payload(self._h, C.byref(a), C.byref(b)))
-        return dict(own_records=a.value, bytes_sent=b.value)
+        return self._payload(self._L.vgs_tiles_get_field_payload, ("own_records", "bytes_sent"))
 
     def own_segment_field_moments(self, K, field):
         """this rank's attribute moments of the global labels 0 .. K-1 over its own rows (vgs_get_own_segment_field_moments on its context;
@@ -656,9 +650,7 @@ class NativeTiles:
         return {name: a[:n.value] for name, a in out.items()}
 
     def info(self):
-        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        self._ck(self._L.vgs_tiles_get_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return dict(n_outside=a.value, n_local=b.value, n_boundary_records=c.value)
+        return self._payload(self._L.vgs_tiles_get_info, ("n_outside", "n_local", "n_boundary_records"))
 
     def exchange(self):
         """the last run's boundary exchange: bytes this rank sent / received, collectives taken"""
