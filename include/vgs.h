@@ -126,7 +126,10 @@ vgs_status vgs_run(vgs_ctx* ctx);        /* all stages for ctx's method (segment
 /* ---- SVGS ------------------------------------------------------------------------------- */
 /* segmentSupervoxelCloudWithGraphModel from a caller-supplied supervoxel labelling (what
  * pcl::SupervoxelClustering::getLabeledCloud returns, SS:283): labels_dev/labels_host hold one int32 per
- * point, 0 = unassigned; max_label = getMaxLabel().  (SS:279-421) */
+ * point, 0 = unassigned; max_label = getMaxLabel().  (SS:279-421)
+ * Only the labels 1 .. max_label - 1 make supervoxels (SS:313); a negative label, or one of max_label or above, leaves its point
+ * unassigned.  A point with a non-finite coordinate (NaN, +-inf) belongs to no supervoxel, whatever label it carries: it is left out
+ * of the supervoxel table and ends with point label -1, as in VGS. */
 vgs_status svgs_set_supervoxel_labels(vgs_ctx* ctx, const int32_t* labels_host, int32_t max_label);
 vgs_status svgs_supervoxels(vgs_ctx* ctx);  /* createSupervoxels: VCCS-style clustering on the GPU (SS:245-331) */
 vgs_status svgs_segment(vgs_ctx* ctx);      /* attributes + neighbours + local cuts + merge (SS:362-421) */

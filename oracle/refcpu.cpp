@@ -799,6 +799,10 @@ void run_svgs_from_labels(const float* xyz, int64_t n, int stride, const int* sv
   std::vector<std::vector<int>> map((size_t)max_label + 1);
   for (int64_t j = 0; j < n; ++j) {
     int l = sv_label[j];
+    // a point with a non-finite coordinate belongs to no supervoxel, whatever label the caller gave it (include/vgs.h): as in VGS it
+    // stays out of the table and ends with point label -1
+    const float* p = xyz + j * stride;
+    if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) continue;
     if (l > 0 && l <= max_label) map[l].push_back((int)j);
   }
   R.sv_points.clear();

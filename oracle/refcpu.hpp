@@ -133,7 +133,9 @@ void vccs_supervoxels(const float* xyz, int64_t n, int stride_floats, const Para
 // the same steps in double precision with libm and an eigen-solver of its own: shares no arithmetic with the device (refcpu_vccs_ref.cpp)
 void vccs_supervoxels_refmath(const float* xyz, int64_t n, int stride_floats, const Params& P, std::vector<int>& label, int& max_label);
 // vccs_mode 1: pcl::SupervoxelClustering's steps in PCL's order (sequential owners, 2-ring normals, seed rejection); unpinned
-void vccs_pcl_supervoxels(const float* xyz, int64_t n, int stride_floats, const Params& P, std::vector<int>& label, int& max_label);
+// (kept_seeds: the seeds that survive the rejection -- labels 1 .. kept_seeds are handed out, max_label is the largest still in use)
+void vccs_pcl_supervoxels(const float* xyz, int64_t n, int stride_floats, const Params& P, std::vector<int>& label, int& max_label,
+                          int* kept_seeds = nullptr);
 // ... and its independent arithmetic leg (double, libm, own eigen-solver: refcpu_vccs_ref.cpp)
 void vccs_pcl_supervoxels_refmath(const float* xyz, int64_t n, int stride_floats, const Params& P, std::vector<int>& label, int& max_label);
 

@@ -91,6 +91,14 @@ int ref_vccs_pcl(const float* xyz, int64_t n, int stride_floats, const RefParams
   std::memcpy(labels, lab.data(), lab.size() * sizeof(int));
   return max_label;
 }
+// the same, and the number of seeds that survived the rejection (labels 1 .. *kept_seeds were handed out)
+int ref_vccs_pcl_seeds(const float* xyz, int64_t n, int stride_floats, const RefParamsC* p, int* labels, int* kept_seeds) {
+  std::vector<int> lab;
+  int max_label = 0;
+  vccs_pcl_supervoxels(xyz, n, stride_floats, to_params(p), lab, max_label, kept_seeds);
+  std::memcpy(labels, lab.data(), lab.size() * sizeof(int));
+  return max_label;
+}
 int ref_vccs_pcl_refmath(const float* xyz, int64_t n, int stride_floats, const RefParamsC* p, int* labels) {
   std::vector<int> lab;
   int max_label = 0;

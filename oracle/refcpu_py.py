@@ -209,6 +209,19 @@ def vccs_pcl(xyz, params):
     return lab, int(mx)
 
 
+def vccs_pcl_seeds(xyz, params):
+    """vccs_pcl and, third, the number of seeds that survive the rejection: labels 1 .. seeds are handed out, max_label is the largest one
+    still in use at the end (the engine's counts()["supervoxels"] right after svgs_supervoxels is the number of seeds)."""
+    xyz = _xyz(xyz)
+    L = lib()
+    L.ref_vccs_pcl_seeds.restype = C.c_int
+    L.ref_vccs_pcl_seeds.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.POINTER(RefParams), C.c_void_p, C.POINTER(C.c_int)]
+    lab = np.zeros(xyz.shape[0], dtype=np.int32)
+    kept = C.c_int(0)
+    mx = L.ref_vccs_pcl_seeds(_p(xyz), xyz.shape[0], xyz.shape[1], C.byref(params), _p(lab), C.byref(kept))
+    return lab, int(mx), int(kept.value)
+
+
 def vccs_pcl_refmath(xyz, params):
     """The PCL-order steps once more in double precision with libm and an eigen-solver of their own (refcpu_vccs_ref.cpp): the independent
     leg of the engine's default supervoxel stage."""

@@ -148,7 +148,9 @@ void vccs_supervoxels(const float* xyz, int64_t n, int stride, const Params& P, 
 // adjacency octree anchors at the cloud's minimum), the seed grid is anchored at that lattice's corner, re-seeding takes the
 // nearest of the supervoxel's OWN voxels (PCL asks a kd-tree for the nearest of all), refineNormals is skipped, centroid sums
 // are integer fixed point (order-free on the GPU).
-void vccs_pcl_supervoxels(const float* xyz, int64_t n, int stride, const Params& P, std::vector<int>& label, int& max_label) {
+void vccs_pcl_supervoxels(const float* xyz, int64_t n, int stride, const Params& P, std::vector<int>& label, int& max_label,
+                          int* kept_seeds) {
+  if (kept_seeds) *kept_seeds = 0;
   VoxelTable T;
   build_voxel_table_bbox(xyz, n, stride, P.voxel_size, T);   // the adjacency octree's own lattice (round 5): box from the cloud's bounding box
   const int V = T.V();
@@ -239,6 +241,7 @@ void vccs_pcl_supervoxels(const float* xyz, int64_t n, int stride, const Params&
     if ((float)num > min_points) seeds.push_back(s);
   }
   const int K = (int)seeds.size();
+  if (kept_seeds) *kept_seeds = K;
   max_label = 0;
   if (K == 0) return;
   // expansion

@@ -108,6 +108,38 @@ int main() {
       if (got != want) { std::printf("vccs_nearest_voxel: trial %d voxel %u (d2 bits %u), all-voxel search %u (%u)\n", trial, (unsigned)got, (unsigned)(got >> 32), (unsigned)want, (unsigned)(want >> 32)); ++fails; }
     }
   }
+  {   // a caller's labelling that gives non-finite points a supervoxel's label (include/vgs.h: such a point belongs to no supervoxel):
+      // 40 supervoxels of 4 points, every 17th point with y = NaN -- the same result as with those points labelled 0, the labels above
+      // max_label, the negative ones and max_label = 0 (tests/supervoxel_scenes.py) alongside
+    uint64_t s3 = 340;
+    std::vector<float> p;
+    std::vector<int> lab;
+    for (int s = 0; s < 40; ++s)
+      for (int k = 0; k < 4; ++k) {
+        p.push_back(2.0f + 0.3f * (float)(s / 5) + 0.004f * (uni(s3) - 0.5f));
+        p.push_back(-1.0f + 0.3f * (float)(s % 5) + 0.004f * (uni(s3) - 0.5f));
+        p.push_back(1.0f + 0.004f * (uni(s3) - 0.5f));
+        lab.push_back(s + 1);
+      }
+    const int64_t m = (int64_t)lab.size();
+    std::vector<int> lab0(lab);
+    for (int64_t i = 0; i < m; i += 17) { p[3 * (size_t)i + 1] = NAN; lab0[(size_t)i] = 0; }
+    Params P;
+    P.voxel_size = 0.05f; P.seed_size = 0.25f; P.sig_w = 1.0f; P.cut_thred = 0.5f; P.math = 1; P.flavour = 1;
+    SvgsResult A, B;
+    run_svgs_from_labels(p.data(), m, 3, lab.data(), 41, P, A);
+    run_svgs_from_labels(p.data(), m, 3, lab0.data(), 41, P, B);
+    bool finite = true;
+    for (const Node& nd : A.nodes) for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(nd.c[a]);
+    if (A.nodes.size() != 40 || !finite || A.point_label != B.point_label || A.sv_points != B.sv_points || A.clusters_num != B.clusters_num) { std::printf("non-finite points under a supervoxel's label: %zu supervoxels, centroids finite %d\n", A.nodes.size(), (int)finite); ++fails; }
+    for (int64_t i = 0; i < m; i += 17) if (A.point_label[(size_t)i] != -1) { std::printf("non-finite point %ld got label %d\n", (long)i, A.point_label[(size_t)i]); ++fails; break; }
+    std::vector<int> odd(lab);
+    for (int64_t i = 0; i < m; ++i) odd[(size_t)i] = lab[(size_t)i] % 3 == 0 ? -lab[(size_t)i] : (lab[(size_t)i] % 3 == 1 ? lab[(size_t)i] + 1000 : lab[(size_t)i]);
+    SvgsResult Cn, Cz;
+    run_svgs_from_labels(p.data(), m, 3, odd.data(), 41, P, Cn);
+    run_svgs_from_labels(p.data(), m, 3, lab.data(), 0, P, Cz);
+    if (Cn.nodes.size() != 13 || !Cz.nodes.empty() || Cz.clusters_num != 0) { std::printf("odd labellings: %zu and %zu supervoxels\n", Cn.nodes.size(), Cz.nodes.size()); ++fails; }
+  }
   {   // KAT-C2 and KAT-C5
     const std::vector<float> W2 = {1.f, .9f, .2f, .9f, 1.f, .78f, .2f, .78f, 1.f};
     if (cut_graph_faithful(0.3f, W2, 3).size() != 3) { std::printf("KAT-C2 failed\n"); ++fails; }

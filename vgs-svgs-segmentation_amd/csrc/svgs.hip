@@ -28,9 +28,12 @@ __global__ void k_sv_keys(const int32_t* __restrict__ label, int64_t n, int32_t 
   if (i >= n) return;
   const int32_t l = label[i];
   // supervoxels_point_idx_ is built for k in [0, max_label): label 0 collects nothing, label max_label is skipped (SS:301-322)
-  key[i] = (l > 0 && l < max_label) ? (uint32_t)l : 0xffffffffu;
+  // a point with a non-finite coordinate belongs to no supervoxel whatever its label (include/vgs.h): as in VGS it is left out of the
+  // table, so its NaN never reaches a centroid or k_sv_cells' cell index
+  const float* p = xyz + i * stride_f;
+  const bool finite = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
+  key[i] = (finite && l > 0 && l < max_label) ? (uint32_t)l : 0xffffffffu;
   perm[i] = (uint32_t)i;
-  (void)xyz; (void)stride_f;
 }
 
 __global__ void k_sv_heads(const uint32_t* __restrict__ key, int64_t n, uint32_t* __restrict__ head) {
