@@ -33,6 +33,22 @@ struct DriverFields {
   bool have_truth = false;
   pcl::ClusterLabelComparison matches;
 };
+// point-level refinement of the cluster labels (refineClusterLabels): when `on`, the drivers put the refined clusters into
+// clusters_points_idx -- clusters in label order, points in ascending index -- and the refined labels into `labels`
+struct DriverRefine {
+  bool on = false;
+  float patch_radius = -1.0f;   // < 0: the default
+  float switch_ratio = 0.25f;
+  bool fill = true;
+  std::vector<int32_t> labels;
+};
+template <typename S>
+inline void driverRefine(S& structure, DriverRefine& r, std::vector<std::vector<int>>& clusters_points_idx) {
+  r.labels = structure.refineClusterLabels(r.patch_radius, r.switch_ratio, r.fill);
+  for (auto& c : clusters_points_idx) c.clear();
+  for (size_t i = 0; i < r.labels.size(); ++i)
+    if (r.labels[i] >= 0 && (size_t)r.labels[i] < clusters_points_idx.size()) clusters_points_idx[(size_t)r.labels[i]].push_back((int)i);
+}
 template <typename S>
 inline void driverFields(S& structure, DriverFields& f) {
   if (f.channels > 0)
@@ -47,12 +63,14 @@ inline void driverFields(S& structure, DriverFields& f) {
 // graph: when not null, receives getClusterGraph() and getClusterAdjacency() (cluster indices of clusters_points_idx)
 // boxes: when not null, receives getClusterBoxes(box_frame) (one per entry of clusters_points_idx, same order)
 // fields: when not null, its stats / hist receive getClusterFieldStats / getClusterClassHistogram of its inputs (same order)
+// refine: when not null and on, clusters_points_idx holds the clusters of refineClusterLabels instead of getClusterIdx's (the tables above
+// keep describing the voxel labels)
 inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>& input_vector,
                            std::vector<std::vector<int>>& clusters_points_idx, DriverSummary* sum = nullptr,
                            const std::string& debug_prefix = std::string(), double ctor_resolution = 0.0,
                            std::vector<pcl::ClusterDescriptor>* descriptors = nullptr, DriverGraph* graph = nullptr,
                            std::vector<pcl::ClusterBox>* boxes = nullptr, int box_frame = VGS_BOX_PRINCIPAL,
-                           DriverFields* fields = nullptr) {
+                           DriverFields* fields = nullptr, DriverRefine* refine = nullptr) {
   float voxel_size = 0.15f, graph_size = 0.5f, sig_p = 0.2f, sig_n = 0.2f, sig_o = 0.2f, sig_e = 0.2f, sig_c = 0.2f, sig_w = 2.0f,
         cut_thred = 0.3f;
   int points_min = 10, adjacency_min = 3, voxels_min = 3;
@@ -89,6 +107,7 @@ inline int segmentationVGS(PCXYZPtr input_cloud, const std::vector<std::string>&
   if (graph) { graph->edges = voxel_structure.getClusterGraph(); voxel_structure.getClusterAdjacency(graph->adjacency); }
   if (boxes) *boxes = voxel_structure.getClusterBoxes(box_frame);
   if (fields) driverFields(voxel_structure, *fields);
+  if (refine && refine->on) driverRefine(voxel_structure, *refine, clusters_points_idx);
   if (sum) {
     sum->points = (long)input_cloud->points.size(); sum->voxels = voxels; sum->clusters = voxel_structure.getClusterNum();
     sum->kept = (long)clusters_points_idx.size();
@@ -113,7 +132,7 @@ inline int segmentationSVGS(PCXYZPtr input_cloud, const std::vector<std::string>
                             std::vector<std::vector<int>>& clusters_points_idx, DriverSummary* sum = nullptr,
                             std::vector<pcl::ClusterDescriptor>* descriptors = nullptr, DriverGraph* graph = nullptr,
                             std::vector<pcl::ClusterBox>* boxes = nullptr, int box_frame = VGS_BOX_PRINCIPAL,
-                            DriverFields* fields = nullptr) {
+                            DriverFields* fields = nullptr, DriverRefine* refine = nullptr) {
   // Task_File_SVGS.txt values
   float voxel_size = 0.05f, seed_size = 0.25f, graph_size = 0.5f, sig_p = 0.2f, sig_n = 0.2f, sig_o = 0.2f, sig_e = 0.2f, sig_c = 0.2f,
         sig_w = 1.0f, sig_a = 0.0f, sig_b = 0.25f, cut_thred = 0.5f;
@@ -149,6 +168,7 @@ inline int segmentationSVGS(PCXYZPtr input_cloud, const std::vector<std::string>
   if (graph) { graph->edges = supervoxel_structure.getClusterGraph(); supervoxel_structure.getClusterAdjacency(graph->adjacency); }
   if (boxes) *boxes = supervoxel_structure.getClusterBoxes(box_frame);
   if (fields) driverFields(supervoxel_structure, *fields);
+  if (refine && refine->on) driverRefine(supervoxel_structure, *refine, clusters_points_idx);
   if (sum) {
     sum->points = (long)input_cloud->points.size(); sum->voxels = supervoxel_structure.getVoxelNum();
     sum->supervoxels = supervoxel_structure.getSuperVoxelNum(); sum->clusters = supervoxel_structure.getClusterNum();

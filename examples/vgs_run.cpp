@@ -7,6 +7,7 @@
 //                  [--segment-boxes <file.csv> [--box-frame principal|upright]]
 //                  [--segment-fields <file.csv> --fields a[,b,...]] [--segment-classes <file.csv> --class-field <name> --classes <C>]
 //                  [--segment-matches <file.csv> --truth-field <name> [--truth-matches <file.csv>]]
+//                  [--refine [--patch-radius <r>] [--switch-ratio <s>] [--no-fill]]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
 // --segments writes one CSV row per kept cluster (getClusterDescriptors, row i = cluster i of the output): label, n_points, n_nodes,
@@ -28,6 +29,10 @@
 // best_n, best_iou (%.17g).  --truth-matches adds one row per reference id: ref_id, n_points, n_dropped, best_seg, best_n, best_iou.  A
 // second and third line on stdout carry the summary ("matches" and its twelve numbers) and the scores at IoU > 0.5 ("scores matched
 // precision recall f1 purity completeness ari", %.17g).  The same usage rules.
+// --refine writes the coloured PCD from the point-level refined labels (refineClusterLabels: boundary points take the label of the nearest
+// planar patch, the points of unused voxels and dropped clusters are filled unless --no-fill): clusters in label order, points in
+// ascending index; every CSV keeps describing the voxel labels.  --patch-radius (default: the voxel size, the supervoxel size for SVGS),
+// --switch-ratio in [0, 1] (default 0.25) and --no-fill need --refine.
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
 #include <algorithm>
 #include <cmath>
@@ -53,7 +58,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "usage: %s <task file> [--in file.pcd] [--out file.pcd] [--seed n] [--ascii] [--debug-meshes prefix] [--segments file.csv] "
                  "[--segment-graph file.csv] [--segment-adjacency file.txt] [--segment-boxes file.csv [--box-frame principal|upright]] "
                  "[--segment-fields file.csv --fields a[,b,...]] [--segment-classes file.csv --class-field name --classes C] "
-                 "[--segment-matches file.csv --truth-field name [--truth-matches file.csv]]\n",
+                 "[--segment-matches file.csv --truth-field name [--truth-matches file.csv]] "
+                 "[--refine [--patch-radius r] [--switch-ratio s] [--no-fill]]\n",
                  argv[0]);
     return 2;
   }
@@ -64,6 +70,8 @@ int main(int argc, char** argv) {
   int box_frame = VGS_BOX_PRINCIPAL;
   uint64_t seed = 0;
   bool ascii = false;
+  DriverRefine refine;
+  bool refine_opts = false;
   for (int a = 2; a < argc; ++a) {
     if (!std::strcmp(argv[a], "--in") && a + 1 < argc) in_file = argv[++a];
     else if (!std::strcmp(argv[a], "--out") && a + 1 < argc) out_file = argv[++a];
@@ -101,8 +109,22 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--segment-matches") && a + 1 < argc) matches_file = argv[++a];
     else if (!std::strcmp(argv[a], "--truth-field") && a + 1 < argc) truth_field = argv[++a];
     else if (!std::strcmp(argv[a], "--truth-matches") && a + 1 < argc) truth_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--refine")) refine.on = true;
+    else if (!std::strcmp(argv[a], "--no-fill")) { refine.fill = false; refine_opts = true; }
+    else if ((!std::strcmp(argv[a], "--patch-radius") || !std::strcmp(argv[a], "--switch-ratio")) && a + 1 < argc) {
+      const bool radius = argv[a][2] == 'p';
+      char* end = nullptr;
+      const float v = std::strtof(argv[++a], &end);
+      if (end == argv[a] || *end != 0 || !std::isfinite(v) || v < 0.0f || (!radius && v > 1.0f)) {
+        std::fprintf(stderr, "%s %s: %s\n", argv[a - 1], argv[a], radius ? "a finite number, not negative" : "a number in [0, 1]");
+        return 2;
+      }
+      (radius ? refine.patch_radius : refine.switch_ratio) = v;
+      refine_opts = true;
+    }
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
+  if (refine_opts && !refine.on) { std::fprintf(stderr, "--patch-radius / --switch-ratio / --no-fill need --refine\n"); return 2; }
   if (!fields_file.empty() && (!have_fields || field_names.empty())) { std::fprintf(stderr, "--segment-fields needs --fields a[,b,...]\n"); return 2; }
   if (!fields_file.empty() && field_names.size() > 64) { std::fprintf(stderr, "--fields: at most 64 fields\n"); return 2; }
   if (!classes_file.empty() && class_field.empty()) { std::fprintf(stderr, "--segment-classes needs --class-field <name>\n"); return 2; }
@@ -159,13 +181,17 @@ int main(int argc, char** argv) {
   std::vector<pcl::ClusterBox>* want_boxes = boxes_file.empty() ? nullptr : &boxes;
   try {
     if (method == 2) {
-      if (segmentationVGS(cloud, task, clusters, &sum, debug_prefix, 0.0, want, want_graph, want_boxes, box_frame, want_fields) != 0) { std::fprintf(stderr, "cannot write the debug meshes\n"); return 1; }
+      if (segmentationVGS(cloud, task, clusters, &sum, debug_prefix, 0.0, want, want_graph, want_boxes, box_frame, want_fields, &refine) != 0) { std::fprintf(stderr, "cannot write the debug meshes\n"); return 1; }
     } else {
-      segmentationSVGS(cloud, task, clusters, &sum, want, want_graph, want_boxes, box_frame, want_fields);
+      segmentationSVGS(cloud, task, clusters, &sum, want, want_graph, want_boxes, box_frame, want_fields, &refine);
     }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "error: %s\n", e.what());
     return 1;
+  }
+  if (refine.on) {   // the summary's last number counts what the output holds
+    sum.labelled = 0;
+    for (const auto& c : clusters) sum.labelled += (long)c.size();
   }
   if (saveColoredClusters(out_file, cloud, clusters, seed, !ascii) != 0) return 1;
   if (want && writeSegmentsCsv(segments_file, desc) != 0) { std::fprintf(stderr, "cannot write %s\n", segments_file.c_str()); return 1; }

@@ -500,6 +500,61 @@ vgs_status vgs_label_comparison_from_cells(vgs_ctx* ctx, int64_t K, int64_t n_in
                                            const int64_t* cell_n, int64_t n_unannotated, int64_t* n_cells, int64_t* n_refs,
                                            int64_t* summary /* 12 */);
 
+/* Point-level label refinement at segment boundaries (no reference counterpart).  A point's label (vgs_get_point_labels) is the label of
+ * its node -- a voxel for VGS, a supervoxel for SVGS -- so segment boundaries are staircases of whole nodes, and the points of voxels with
+ * at most points_min points and of clusters with at most voxels_min voxels are -1 however close a kept segment lies.  This is a NEW output
+ * next to the existing labels: one int32 per input point, from the rule below.  vgs_get_point_labels, the cluster lists, every
+ * per-segment table and vgs_compare_labels keep reading the node labels.  All arithmetic is float32 in the written association with no
+ * FMA (csrc/vgs_math.h: vm_refine_cost).
+ *
+ * Inputs
+ * - A point p in node v.
+ * - A = kept_label[v] if v is used, else -1.
+ *
+ * Candidates of v.  A node w is a candidate when all of these hold:
+ * - w is v itself or is in v's adjacency list, as vgs_get_lists(which = 0) gives it,
+ * - w is used,
+ * - kept_label[w] >= 0,
+ * - VGS_F_POS and VGS_F_NRM are both set in w's record.
+ *
+ * Cost of w for p, with c, n the centroid and normal of w:
+ * - d = p - c
+ * - h = (n0*d0 + n1*d1) + n2*d2
+ * - q = (d0*d0 + d1*d1) + d2*d2
+ * - t = vm_sqrt(max(q - h*h, 0))
+ * - e = max(t - patch_radius, 0)
+ * - cost = h*h + e*e
+ * This is the squared distance to the node's planar patch of radius patch_radius.  A candidate whose cost is not finite is skipped (for
+ * that point it is no candidate at all).
+ *
+ * Choice
+ * - best is the candidate with the smallest (cost, node id), compared lexicographically.
+ * - c_own is the smallest cost among candidates of label A.
+ * - A >= 0 and a label-A candidate exists: the point takes label[best] only if cost_best < switch_ratio * c_own.  Otherwise it keeps A.
+ * - A >= 0 and no label-A candidate exists: the point keeps A.
+ * - A < 0 and fill != 0: the point takes label[best], or -1 when there is no candidate.
+ * - A < 0 and fill == 0: the point keeps -1.
+ * - A non-finite point keeps -1.
+ * - A point that is in no node keeps -1.
+ *
+ * A consequence: a labelled node whose candidates all carry its own label is interior and its points keep their label without any
+ * arithmetic.  Only the remaining nodes -- the WORKING nodes: labelled nodes with a candidate of another label and, with fill, unlabelled
+ * nodes with a candidate -- are examined.  For SVGS an unused supervoxel has an empty list and so no candidate.
+ *
+ * vgs_refine_params_default: patch_radius = voxel_size for VGS and seed_size for SVGS, switch_ratio = 0.25, fill = 1.
+ * vgs_refine_point_labels computes the labels on the device into a buffer of the context; counts (may be NULL): 0 working nodes, 1 points
+ * examined (the points of the working nodes), 2 labelled points whose label changed, 3 unlabelled points filled.  No float atomics and
+ * no dependence on the order of execution: the output is a function of the inputs, bit-identical from call to call.
+ * vgs_get_refined_labels copies them (N int32, input order); vgs_get_refined_labels_device hands out the device pointer.  Both are valid
+ * until the next run of the stages or the next refine, and answer VGS_E_STATE without a refine since the last run.
+ * VGS_E_STATE before the context is segmented and for a tile context; VGS_E_ARG for a negative or non-finite patch_radius and for a
+ * switch_ratio outside [0, 1] (NaN included). */
+typedef struct { float patch_radius; float switch_ratio; int32_t fill; } vgs_refine_params;
+vgs_status vgs_refine_params_default(vgs_ctx* ctx, vgs_refine_params* rp);
+vgs_status vgs_refine_point_labels(vgs_ctx* ctx, const vgs_refine_params* rp, int64_t* counts /* 4 */);
+vgs_status vgs_get_refined_labels(vgs_ctx* ctx, int32_t* labels /* N host */);
+vgs_status vgs_get_refined_labels_device(vgs_ctx* ctx, const int32_t** labels_dev /* N */);
+
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.
  * One context per GPU holds one tile plus a halo of raw points (2*graph_size + voxel_size wide).

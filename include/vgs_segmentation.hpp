@@ -246,6 +246,17 @@ inline ClusterLabelScores clusterLabelScores(const ClusterLabelComparison& c, do
 }
 
 namespace vgs_detail {
+inline std::vector<int32_t> refined_labels(vgs_ctx* c, int64_t n, float patch_radius, float switch_ratio, bool fill) {
+  vgs_refine_params rp;
+  check(c, vgs_refine_params_default(c, &rp), "vgs_refine_params_default");
+  if (patch_radius >= 0.0f) rp.patch_radius = patch_radius;
+  rp.switch_ratio = switch_ratio;
+  rp.fill = fill ? 1 : 0;
+  check(c, vgs_refine_point_labels(c, &rp, nullptr), "vgs_refine_point_labels");
+  std::vector<int32_t> out((size_t)n);
+  if (n > 0) check(c, vgs_get_refined_labels(c, out.data()), "vgs_get_refined_labels");
+  return out;
+}
 inline ClusterLabelComparison cluster_label_comparison(vgs_ctx* c, int64_t k, const int32_t* ref, int64_t n) {
   ClusterLabelComparison o;
   int64_t n_cells = 0, n_refs = 0;
@@ -448,6 +459,13 @@ class VoxelBasedSegmentation {
     return vgs_detail::cluster_label_comparison(ctx(), count(VGS_N_KEPT), ref, n);
   }
 
+  // Extension (no VS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
+  // names getClusterIdx()[i].  patch_radius < 0: the default (the voxel size); every point -1 before drawColorMapofPointsinClusters
+  std::vector<int32_t> refineClusterLabels(float patch_radius = -1.0f, float switch_ratio = 0.25f, bool fill = true) {
+    if (!drawn_) return std::vector<int32_t>((size_t)count(VGS_N_POINTS), -1);
+    return vgs_detail::refined_labels(ctx(), count(VGS_N_POINTS), patch_radius, switch_ratio, fill);
+  }
+
   vgs_ctx* ctx() { return ctx_.get(); }
 
  private:
@@ -558,6 +576,11 @@ class SuperVoxelBasedSegmentation {
   // cluster table belongs to getClusterIdx()[i]
   ClusterLabelComparison compareClusterLabels(const int32_t* ref, int64_t n) {
     return vgs_detail::cluster_label_comparison(ctx(), count(VGS_N_KEPT), ref, n);
+  }
+  // Extension (no SS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
+  // names getClusterIdx()[i].  patch_radius < 0: the default (the supervoxel size)
+  std::vector<int32_t> refineClusterLabels(float patch_radius = -1.0f, float switch_ratio = 0.25f, bool fill = true) {
+    return vgs_detail::refined_labels(ctx(), count(VGS_N_POINTS), patch_radius, switch_ratio, fill);
   }
   vgs_ctx* ctx() { return ctx_.get(); }
 

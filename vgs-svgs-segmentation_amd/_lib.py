@@ -39,6 +39,10 @@ class VgsGridState(C.Structure):
     _fields_ = [("min", C.c_double * 3), ("shift", C.c_uint64 * 3), ("depth", C.c_int32), ("defined", C.c_int32)]
 
 
+class VgsRefineParams(C.Structure):
+    _fields_ = [("patch_radius", C.c_float), ("switch_ratio", C.c_float), ("fill", C.c_int32)]
+
+
 class VgsError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"{STATUS_NAMES[status] if 0 <= status < len(STATUS_NAMES) else status}: {msg}")
@@ -123,6 +127,10 @@ SYMBOLS = [
     ("vgs_segment_field_stats_from_moments", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_own_segment_class_counts", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     ("vgs_get_own_segment_class_counts_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    ("vgs_refine_params_default", C.c_int, [_P, C.POINTER(VgsRefineParams)]),
+    ("vgs_refine_point_labels", C.c_int, [_P, C.POINTER(VgsRefineParams), _P]),
+    ("vgs_get_refined_labels", C.c_int, [_P, _P]),
+    ("vgs_get_refined_labels_device", C.c_int, [_P, C.POINTER(_P)]),
     ("vgs_grid_state_init", C.c_int, [C.POINTER(VgsGridState)]),
     ("vgs_grid_advance", C.c_int, [_P, C.POINTER(VgsGridState)]),
     ("vgs_points_bbox", C.c_int, [_P, _P, C.POINTER(C.c_int64)]),

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import VgsError, VgsGridState, VgsParams
+from ._lib import VgsError, VgsGridState, VgsParams, VgsRefineParams
 
 
 def comparison_scores(cmp, tau=0.5):
@@ -267,6 +267,35 @@ class Engine:
     def point_labels_device_ptr(self):
         p = C.c_void_p()
         self._ck(self._L.vgs_get_point_labels_device(self._h, C.byref(p)))
+        return p.value
+
+    REFINE_COUNTS = ("working_nodes", "points_examined", "points_changed", "points_filled")
+
+    def refine_labels(self, patch_radius=None, switch_ratio=0.25, fill=True):
+        """Point-level label refinement at segment boundaries (include/vgs.h, vgs_refine_point_labels): every point of a node with a
+        neighbour of another label takes the label of the node whose planar patch lies nearest, if that beats its own by switch_ratio;
+        with fill the points of unused voxels and dropped clusters take the nearest labelled neighbour's.  patch_radius None: voxel_size
+        (VGS) or seed_size (SVGS).  A new output next to point_labels(), read with refined_labels(); returns a dict of the counts
+        (REFINE_COUNTS)."""
+        rp = VgsRefineParams()
+        self._ck(self._L.vgs_refine_params_default(self._h, C.byref(rp)))
+        if patch_radius is not None:
+            rp.patch_radius = float(patch_radius)
+        rp.switch_ratio = float(switch_ratio)
+        rp.fill = 1 if fill else 0
+        cnt = np.zeros(4, dtype=np.int64)
+        self._ck(self._L.vgs_refine_point_labels(self._h, C.byref(rp), _ptr(cnt)))
+        return {name: int(v) for name, v in zip(self.REFINE_COUNTS, cnt)}
+
+    def refined_labels(self):
+        """The labels of the last refine_labels(), one int32 per input point; valid until the next run or the next refine."""
+        out = np.zeros(self.n, dtype=np.int32)
+        self._ck(self._L.vgs_get_refined_labels(self._h, _ptr(out)))
+        return out
+
+    def refined_labels_device_ptr(self):
+        p = C.c_void_p()
+        self._ck(self._L.vgs_get_refined_labels_device(self._h, C.byref(p)))
         return p.value
 
     ORDERS = {"voxel_id": 0, "reference": 1}
@@ -642,6 +671,14 @@ class VoxelBasedSegmentation:
             return dict({name: np.zeros(0, dtype=dt) for name, dt, _ in Engine.COMPARE_FIELDS}, summary=np.zeros(12, np.int64))
         return self._eng.compare_labels(ref)
 
+    def refineClusterLabels(self, patch_radius=None, switch_ratio=0.25, fill=True):
+        """Extension (no VS line): one label per input point, refined at the cluster boundaries; label i names getClusterIdx()[i]
+        (Engine.refine_labels / refined_labels).  Every point -1 before drawColorMapofPointsinClusters."""
+        if not self._drawn:
+            return np.full(self._eng.n, -1, dtype=np.int32)
+        self._eng.refine_labels(patch_radius, switch_ratio, fill)
+        return self._eng.refined_labels()
+
     @property
     def engine(self):
         return self._eng
@@ -738,6 +775,12 @@ class SuperVoxelBasedSegmentation:
         """Extension (no SS line): the clusters against a reference labelling; row i of the cluster table belongs to getClusterIdx()[i]
         (Engine.compare_labels)."""
         return self._eng.compare_labels(ref)
+
+    def refineClusterLabels(self, patch_radius=None, switch_ratio=0.25, fill=True):
+        """Extension (no SS line): one label per input point, refined at the cluster boundaries; label i names getClusterIdx()[i]
+        (Engine.refine_labels / refined_labels)."""
+        self._eng.refine_labels(patch_radius, switch_ratio, fill)
+        return self._eng.refined_labels()
 
     @property
     def engine(self):

@@ -238,6 +238,8 @@ void vgs_destroy(vgs_ctx* c) {
   c->cmp_ref.release(); c->cmp_cell_i32.release(); c->cmp_ref_i32.release(); c->cmp_seg_i32.release(); c->cmp_cell_n.release(); c->cmp_ref_i64.release(); c->cmp_seg_i64.release();
   c->cmp_ref_iou.release(); c->cmp_seg_iou.release(); c->cmp_key.release(); c->cmp_meta.release(); c->cmp_work.release(); c->cmp_cstart.release(); c->cmp_rowstart.release();
   c->cmp_rsort.release(); c->cmp_rstart.release(); c->cmp_tmp.release();
+  c->rf_label.release(); c->rf_batches.release(); c->rf_start.release(); c->rf_ids.release(); c->rf_cnt.release(); c->rf_nall.release();
+  c->rf_rows.release(); c->rf_counts.release();
   c->cl_off.release(); c->cl_idx.release(); c->conn.release(); c->evals.release(); c->lc_pending.release(); c->lc_defer.release(); c->lc_defer_flag.release(); c->csize.release(); c->attach.release(); c->cc_flags.release(); c->parent.release(); c->csz.release();
   c->vc_cen.release(); c->vc_nrm.release(); c->vc_dist.release(); c->vc_state.release(); c->vc_tile_start.release(); c->vc_cell.release(); c->vc_plive.release(); c->vc_tile_of.release(); c->vc_tchg.release(); c->vc_nbr_tiles.release(); c->vc_halo.release(); c->vc_tile_meta.release(); c->vc_pool.release(); c->vc_ring.release(); c->vc_dbg.release(); c->vc_label.release();
   c->vc_seedkey.release(); c->vc_sums.release(); c->vc_count.release(); c->vc_accu.release(); c->vc_alive.release();
@@ -280,7 +282,7 @@ vgs_status vgs_set_params(vgs_ctx* c, const vgs_params* p) {
       p->spatial_impt != o.spatial_impt || p->normal_impt != o.normal_impt || p->vccs_mode != o.vccs_mode)
     keep = ST_POINTS;
   if (c->stage > keep) c->stage = keep;
-  if (keep < ST_SEGMENTED) { c->sd_valid = false; c->sb_valid[0] = c->sb_valid[1] = false; c->sg_valid = false; c->cmp_valid = false; c->cmp_own_cells = -1; c->sg_halo_valid = false; c->sg_own_K = -1; }
+  if (keep < ST_SEGMENTED) { c->sd_valid = false; c->sb_valid[0] = c->sb_valid[1] = false; c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->cmp_own_cells = -1; c->sg_halo_valid = false; c->sg_own_K = -1; }
   // labels from svgs_supervoxels depend on voxel_size / seed_size / the three importances; a caller's own labelling does not
   if (keep == ST_POINTS && c->P.method == 3 && !c->sv_labels_external) { c->sv_have_labels = false; c->sv_max_label = 0; c->sv_label_n = -1; }
   c->P = *p;
@@ -297,7 +299,7 @@ static vgs_status set_points_common(vgs_ctx* c, int64_t n, int32_t stride_bytes)
   c->stage = ST_POINTS;
   c->sd_valid = false;      // (segdesc.hip: the descriptors belong to the last segmented cloud)
   c->sb_valid[0] = c->sb_valid[1] = false;      // (segbox.hip: so do the oriented boxes)
-  c->sg_valid = false; c->cmp_valid = false; c->cmp_own_cells = -1; c->sg_halo_valid = false; c->sg_own_K = -1;      // (seggraph.hip: so does the segment graph)
+  c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->cmp_own_cells = -1; c->sg_halo_valid = false; c->sg_own_K = -1;      // (seggraph.hip: so does the segment graph)
   c->grid_covers = false;   // (vgs_set_grid_covering vouches for one cloud)
   c->counts[VGS_N_POINTS] = n;
   for (int i = 0; i < VGS_T_COUNT; ++i) { c->times[i] = 0; c->tev_pending[i] = false; }

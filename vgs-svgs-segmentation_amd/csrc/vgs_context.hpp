@@ -325,6 +325,13 @@ struct vgs_ctx {
   // tile contexts (vgs_own_label_cells): the cells over the own points wait in cmp_cell_i32 / cmp_cell_n at a stride of cmp_ann until
   // vgs_get_own_label_cells; -1: none.  vgs_label_comparison_from_cells stages its input in cmp_ref (seg | ref) and cmp_key (keys, counts)
   int64_t cmp_own_cells = -1;
+  // point-level label refinement (refine.hip): the refined labels in input order, valid until the next run or the next refine (rf_valid).
+  // Scratch of its own: per listed node the number of point batches and their scan, the ids of the unused voxels, and for a chunk of
+  // those the adjacency rows that the hot path does not keep (keys, lengths, neighbour counts)
+  DevBuf<int32_t> rf_label;
+  DevBuf<uint32_t> rf_batches, rf_start, rf_ids, rf_cnt, rf_nall;
+  DevBuf<uint64_t> rf_rows, rf_counts;
+  bool rf_valid = false;
   DevBuf<uint64_t> counters;  // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 
@@ -510,6 +517,7 @@ vgs_status vgs_clusters_on_device(vgs_ctx* c);   // clusters.hip
 vgs_status vgs_segdesc_on_device(vgs_ctx* c);    // segdesc.hip
 vgs_status vgs_segbox_on_device(vgs_ctx* c, int frame);   // segbox.hip
 vgs_status vgs_seggraph_on_device(vgs_ctx* c);   // seggraph.hip
+vgs_status vgs_refine_on_device(vgs_ctx* c, const vgs_refine_params& rp, int64_t* counts4);   // refine.hip
 vgs_status vgs_stage_vccs(vgs_ctx* c);
 vgs_status vgs_stage_svgs_group(vgs_ctx* c);
 vgs_status vgs_stage_svgs_neighbours(vgs_ctx* c);

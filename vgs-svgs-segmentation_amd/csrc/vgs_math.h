@@ -564,6 +564,23 @@ VGS_HD float vm_weight_bound_da(const VgsNode& v1, const VgsNode& v2, const VgsW
   return vm_weight_bound_sa(dist_space, dist_angle, P);
 }
 
+// ------------------------------------------------------------------------------------------
+// Point-level label refinement (include/vgs.h: vgs_refine_point_labels; no reference counterpart)
+// ------------------------------------------------------------------------------------------
+VGS_HD bool vm_isfinite(float x) { return (vm_bits(x) & 0x7f800000u) != 0x7f800000u; }
+VGS_HD float vm_max(float a, float b) { return (a > b) ? a : b; }   // b when a is NaN
+
+// Squared distance of the point p to the planar patch of radius patch_radius about the centroid c with normal n: the square of the height
+// over the plane plus the square of what the in-plane distance exceeds the radius by.
+VGS_HD float vm_refine_cost(const float* p, const float* c, const float* n, float patch_radius) {
+  const float d0 = p[0] - c[0], d1 = p[1] - c[1], d2 = p[2] - c[2];
+  const float h = (n[0] * d0 + n[1] * d1) + n[2] * d2;
+  const float q = (d0 * d0 + d1 * d1) + d2 * d2;
+  const float t = vm_sqrt(vm_max(q - h * h, 0.0f));
+  const float e = vm_max(t - patch_radius, 0.0f);
+  return h * h + e * e;
+}
+
 // Threshold of a segment in the local cut (VS:1968-1969): seg_int - cut/size, float.
 VGS_HD float vm_cut_threshold(float seg_int, float cut, int size) { return seg_int - cut / (float)size; }
 
