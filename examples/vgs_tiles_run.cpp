@@ -24,6 +24,11 @@
 //   negative = not annotated), every rank takes part in vgs_tiles_compare_labels (a collective; no label and no id leaves its rank, only
 //   contingency cells) and rank 0 writes the per-segment matches, and with --truth-matches the per-id matches, in the CSV formats of
 //   vgs_run --segment-matches / --truth-matches.
+//   --refine [--patch-radius <r>] [--switch-ratio <s>] [--no-fill]: every rank takes part in vgs_tiles_refine_point_labels (a collective;
+//   no label of a point leaves its rank) and writes the refined label of each of its points to <prefix>.<r>.refined.i32, next to
+//   .labels.i32.  --patch-radius (finite, not negative; default the voxel size), --switch-ratio in [0, 1] (default 0.25) and --no-fill need
+//   --refine.  A second output line holds the counts "refine <working nodes> <examined> <changed> <filled> <beyond the strip>": summed
+//   over the ranks with --emulate, one line per rank (its own share, behind "rank <r>") with --rccl.
 //   All of them can be combined.  A missing companion option, a value out of range (1 .. 64 channels, 1 .. 1024 classes) and an attribute
 //   or truth file that is missing or whose size does not match the rank's points are usage errors: exit status 2, before any collective.
 #include <arpa/inet.h>
@@ -35,6 +40,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -88,6 +94,8 @@ struct Job {
   std::string fields, classes;        // --segment-fields / --segment-classes
   int field_channels = 0, n_classes = 0;
   std::string matches, truth_matches;   // --segment-matches / --truth-matches
+  bool refine = false, refine_fill = true;   // --refine, --no-fill
+  float patch_radius = -1.0f, switch_ratio = -1.0f;   // --patch-radius / --switch-ratio (negative: the context's default)
 };
 
 static std::string rank_file(const Job& J, int rank, const char* suffix) { return J.prefix + "." + std::to_string(rank) + suffix; }
@@ -121,7 +129,7 @@ static int check_attribute_files(const Job& J, int rank) {
 }
 
 // one rank: load, run, save; returns 0 on success
-static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world, int64_t* kept, int64_t* n_pts, int64_t* n_rec, std::string* err) {
+static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world, int64_t* kept, int64_t* n_pts, int64_t* n_rec, int64_t* refine_counts /* 5 */, std::string* err) {
   std::vector<float> xyz;
   if (!read_f32(J.prefix + "." + std::to_string(rank) + ".f32", xyz)) { *err = "cannot read the points of rank " + std::to_string(rank); return 1; }
   std::vector<float> field;
@@ -269,6 +277,22 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
       else if (!J.truth_matches.empty() && writeTruthMatchesCsv(J.truth_matches, m) != 0) { *err = "cannot write " + J.truth_matches; rc = 1; }
     }
   }
+  if (rc == 0 && J.refine) {
+    // the refined labels of this rank's points: a collective of every rank; each rank writes its own file
+    vgs_refine_params rp;
+    vgs_refine_params_default(vgs_tiles_context(t), &rp);
+    if (J.patch_radius >= 0.0f) rp.patch_radius = J.patch_radius;
+    if (J.switch_ratio >= 0.0f) rp.switch_ratio = J.switch_ratio;
+    rp.fill = J.refine_fill ? 1 : 0;
+    std::vector<int32_t> fine((size_t)n + 1);
+    if (vgs_tiles_refine_point_labels(t, &rp, refine_counts) != VGS_OK || vgs_tiles_get_refined_labels(t, fine.data()) != VGS_OK) {
+      *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+      rc = 1;
+    } else {
+      fine.resize((size_t)n);
+      if (!write_i32(rank_file(J, rank, ".refined.i32"), fine)) { *err = "cannot write the refined labels"; rc = 1; }
+    }
+  }
   if (rc == 0) {
     labels.resize((size_t)n);
     if (!write_i32(J.prefix + "." + std::to_string(rank) + ".labels.i32", labels)) { *err = "cannot write the labels"; rc = 1; }
@@ -322,7 +346,7 @@ int main(int argc, char** argv) {
   J.p.voxel_size = 0.1f;
   J.tx = 1; J.ty = 1; J.pitch = 0.0;
   int mode = -1;   // 0 rccl, 1 emulate
-  bool have_channels = false, have_classes = false;
+  bool have_channels = false, have_classes = false, refine_opts = false;
   for (int a = 1; a < argc; ++a) {
     if ((!std::strcmp(argv[a], "--rccl") || !std::strcmp(argv[a], "--emulate")) && a + 1 < argc) {
       mode = !std::strcmp(argv[a], "--emulate") ? 1 : 0;
@@ -345,10 +369,23 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--classes") && a + 1 < argc) { J.n_classes = std::atoi(argv[++a]); have_classes = true; }
     else if (!std::strcmp(argv[a], "--segment-matches") && a + 1 < argc) J.matches = argv[++a];
     else if (!std::strcmp(argv[a], "--truth-matches") && a + 1 < argc) J.truth_matches = argv[++a];
+    else if (!std::strcmp(argv[a], "--refine")) J.refine = true;
+    else if (!std::strcmp(argv[a], "--no-fill")) { J.refine_fill = false; refine_opts = true; }
+    else if ((!std::strcmp(argv[a], "--patch-radius") || !std::strcmp(argv[a], "--switch-ratio")) && a + 1 < argc) {
+      const bool radius = argv[a][2] == 'p';
+      char* end = nullptr;
+      const float v = std::strtof(argv[++a], &end);
+      if (end == argv[a] || *end != 0 || !std::isfinite(v) || v < 0.0f || (!radius && v > 1.0f)) {
+        std::fprintf(stderr, "%s %s: %s\n", argv[a - 1], argv[a], radius ? "a finite number, not negative" : "a number in [0, 1]");
+        return 2;
+      }
+      (radius ? J.patch_radius : J.switch_ratio) = v;
+      refine_opts = true;
+    }
     else if (argv[a][0] != '-') J.prefix = argv[a];
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
-  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] <prefix>\n", argv[0]); return 2; }
+  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] [--refine [--patch-radius r] [--switch-ratio s] [--no-fill]] <prefix>\n", argv[0]); return 2; }
   if (!J.fields.empty() && !have_channels) { std::fprintf(stderr, "--segment-fields needs --field-channels <C>\n"); return 2; }
   if (J.fields.empty() && have_channels) { std::fprintf(stderr, "--field-channels needs --segment-fields <file.csv>\n"); return 2; }
   if (have_channels && (J.field_channels < 1 || J.field_channels > 64)) { std::fprintf(stderr, "--field-channels must be in 1 .. 64\n"); return 2; }
@@ -356,8 +393,10 @@ int main(int argc, char** argv) {
   if (J.classes.empty() && have_classes) { std::fprintf(stderr, "--classes needs --segment-classes <file.csv>\n"); return 2; }
   if (have_classes && (J.n_classes < 1 || J.n_classes > 1024)) { std::fprintf(stderr, "--classes must be in 1 .. 1024\n"); return 2; }
   if (J.matches.empty() && !J.truth_matches.empty()) { std::fprintf(stderr, "--truth-matches needs --segment-matches <file.csv>\n"); return 2; }
+  if (refine_opts && !J.refine) { std::fprintf(stderr, "--patch-radius / --switch-ratio / --no-fill need --refine\n"); return 2; }
   const int world = J.tx * J.ty;
   int64_t kept = 0, n_pts = 0, n_rec = 0;
+  int64_t rcounts[5] = {0, 0, 0, 0, 0};
   if (mode == 1) {
     for (int r = 0; r < world; ++r) if (check_attribute_files(J, r) != 0) return 2;
     void* group = nullptr;
@@ -365,10 +404,10 @@ int main(int argc, char** argv) {
     std::vector<std::thread> th;
     std::vector<int> rc((size_t)world, 0);
     std::vector<std::string> errs((size_t)world);
-    std::vector<int64_t> k((size_t)world), np((size_t)world), nr((size_t)world);
+    std::vector<int64_t> k((size_t)world), np((size_t)world), nr((size_t)world), rcn(5 * (size_t)world, 0);
     for (int r = 0; r < world; ++r)
       th.emplace_back([&, r] {
-        rc[(size_t)r] = run_rank(J, VGS_TILES_COMM_LOCAL, group, r, world, &k[(size_t)r], &np[(size_t)r], &nr[(size_t)r], &errs[(size_t)r]);
+        rc[(size_t)r] = run_rank(J, VGS_TILES_COMM_LOCAL, group, r, world, &k[(size_t)r], &np[(size_t)r], &nr[(size_t)r], &rcn[5 * (size_t)r], &errs[(size_t)r]);
         if (rc[(size_t)r]) vgs_tiles_local_group_abort(group);   // the other ranks must not wait for this one
       });
     for (auto& t : th) t.join();
@@ -376,6 +415,7 @@ int main(int argc, char** argv) {
     for (int r = 0; r < world; ++r) if (rc[(size_t)r]) { std::fprintf(stderr, "error: %s\n", errs[(size_t)r].c_str()); return 1; }
     for (int r = 1; r < world; ++r) if (k[(size_t)r] != k[0]) { std::fprintf(stderr, "error: ranks disagree on the number of segments\n"); return 1; }
     kept = k[0]; n_pts = np[0]; n_rec = nr[0];
+    for (int r = 0; r < world; ++r) for (int i = 0; i < 5; ++i) rcounts[i] += rcn[5 * (size_t)r + (size_t)i];
   } else {
     const char* e_rank = std::getenv("RANK"); const char* e_world = std::getenv("WORLD_SIZE"); const char* e_local = std::getenv("LOCAL_RANK");
     const char* e_addr = std::getenv("MASTER_ADDR"); const char* e_port = std::getenv("MASTER_PORT");
@@ -390,11 +430,14 @@ int main(int argc, char** argv) {
     ncclComm_t comm;
     if (ncclCommInitRank(&comm, world, id, rank) != ncclSuccess) { std::fprintf(stderr, "rank %d: ncclCommInitRank failed\n", rank); return 1; }
     std::string err;
-    const int rc = run_rank(J, VGS_TILES_COMM_RCCL, (void*)comm, rank, world, &kept, &n_pts, &n_rec, &err);
+    const int rc = run_rank(J, VGS_TILES_COMM_RCCL, (void*)comm, rank, world, &kept, &n_pts, &n_rec, rcounts, &err);
     ncclCommDestroy(comm);
     if (rc) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
+    // (every rank its own share: a sum over the ranks would be a collective for a printout)
+    if (J.refine && rank != 0) std::printf("rank %d refine %ld %ld %ld %ld %ld\n", rank, (long)rcounts[0], (long)rcounts[1], (long)rcounts[2], (long)rcounts[3], (long)rcounts[4]);
     if (rank != 0) return 0;
   }
   std::printf("%d %ld %ld %ld\n", world, (long)kept, (long)n_pts, (long)n_rec);
+  if (J.refine) std::printf("%srefine %ld %ld %ld %ld %ld\n", mode == 1 ? "" : "rank 0 ", (long)rcounts[0], (long)rcounts[1], (long)rcounts[2], (long)rcounts[3], (long)rcounts[4]);
   return 0;
 }

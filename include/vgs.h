@@ -547,13 +547,34 @@ vgs_status vgs_label_comparison_from_cells(vgs_ctx* ctx, int64_t K, int64_t n_in
  * no dependence on the order of execution: the output is a function of the inputs, bit-identical from call to call.
  * vgs_get_refined_labels copies them (N int32, input order); vgs_get_refined_labels_device hands out the device pointer.  Both are valid
  * until the next run of the stages or the next refine, and answer VGS_E_STATE without a refine since the last run.
- * VGS_E_STATE before the context is segmented and for a tile context; VGS_E_ARG for a negative or non-finite patch_radius and for a
- * switch_ratio outside [0, 1] (NaN included). */
+ * VGS_E_STATE before the context is segmented and, from vgs_refine_point_labels, for a tile context (vgs_refine_own_point_labels below
+ * is its counterpart there); VGS_E_ARG for a negative or non-finite patch_radius and for a switch_ratio outside [0, 1] (NaN included). */
 typedef struct { float patch_radius; float switch_ratio; int32_t fill; } vgs_refine_params;
 vgs_status vgs_refine_params_default(vgs_ctx* ctx, vgs_refine_params* rp);
 vgs_status vgs_refine_point_labels(vgs_ctx* ctx, const vgs_refine_params* rp, int64_t* counts /* 4 */);
 vgs_status vgs_get_refined_labels(vgs_ctx* ctx, int32_t* labels /* N host */);
 vgs_status vgs_get_refined_labels_device(vgs_ctx* ctx, const int32_t** labels_dev /* N */);
+/* Refinement on a tile context (the tiled driver: vgs_tiles_refine_point_labels, include/vgs_tiles.h, states the rule over the ranks and
+ * who refines what).  Three local calls, none of which needs K:
+ * vgs_get_own_band_labels: (code, global label) of this rank's owned used voxels whose centre lies within reach + graph_size + 0.5
+ * voxel_size of a border line of its region (reach = max(graph_size, 0.5001 voxel_size): how far outside its region a rank still refines
+ * a node), in ascending voxel id (descending code), compacted on the device: what the other ranks need beyond the run's boundary records.  Two-call protocol: code == label == NULL computes and returns *n, the call with arrays copies those records.
+ * vgs_set_refine_halo_labels: as vgs_set_halo_labels, into a table of the refinement's own, so that neither call invalidates the other:
+ * label[k] (>= -1) is the global label of the voxel with code[k]; codes this context does not hold or owns itself are ignored; a voxel of
+ * another rank without a record stays unknown.  One record per code (two records of one code with different labels would race).  Valid
+ * until the next run of the stages or new labels of the tile.
+ * vgs_refine_own_point_labels: this rank's share of the rule.  A node is refined here when it holds points of the rank's own load and its
+ * centre lies at most reach outside the rank's region, per axis; own points elsewhere keep their point label; the points of other
+ * ranks' strips are not evaluated (-1 in the buffer).  counts (may be NULL), all this rank's share: 0 owned working nodes, 1 own points
+ * examined, 2 own labelled points changed, 3 own unlabelled points filled, 4 own points left unrefined beyond the strip.  A used
+ * candidate of a node this rank refines or counts whose label is unknown fails the call with VGS_E_UNSUPPORTED, the count in the message.
+ * vgs_get_refined_labels[_device] then serve the tile context, in the order of its whole cloud: the own points are [own_first, own_first
+ * + n_own) of vgs_set_own_point_range.
+ * VGS_E_STATE before the context is segmented, for a context that is not a tile context, and for vgs_refine_own_point_labels without
+ * halo labels since the last labels of the tile; VGS_E_ARG for the parameters as vgs_refine_point_labels and for a label below -1. */
+vgs_status vgs_get_own_band_labels(vgs_ctx* ctx, int64_t* n, uint64_t* code, int32_t* label);
+vgs_status vgs_set_refine_halo_labels(vgs_ctx* ctx, const uint64_t* code, const int32_t* label, int64_t n);
+vgs_status vgs_refine_own_point_labels(vgs_ctx* ctx, const vgs_refine_params* rp, int64_t* counts /* 5 */);
 
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.

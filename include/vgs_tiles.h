@@ -16,6 +16,7 @@
  * unless it is cached) and one collective of their own per frame (vgs_tiles_get_segment_boxes).  Statistics of the caller's point
  * attributes on request: one collective per call, nothing cached (vgs_tiles_segment_field_stats, vgs_tiles_segment_class_histogram).
  * The score against the caller's reference labels on request: one collective per call, nothing cached (vgs_tiles_compare_labels).
+ * Point-level label refinement on request: one collective per call (vgs_tiles_refine_point_labels).
  */
 #ifndef VGS_TILES_H_
 #define VGS_TILES_H_
@@ -289,6 +290,54 @@ enum { VGS_TILES_C_OWN = 0, VGS_TILES_C_EXCHANGE = 1, VGS_TILES_C_TABLES = 2, VG
 vgs_status vgs_tiles_get_compare_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_C_COUNT */);
 /* that compare's payload on this rank: cells of its own, bytes it put into the all-gather (header included, before padding) */
 vgs_status vgs_tiles_get_compare_payload(vgs_tiles* t, int64_t* own_cells, int64_t* bytes_sent);
+/* Point-level label refinement over all ranks: the rule of vgs_refine_point_labels (include/vgs.h) applied to the whole scene over the
+ * shared grid.  kept_label is the global label that vgs_tiles_get_point_labels reports, the nodes are the voxels of the shared grid, node
+ * ids compare as on one context (every rank numbers its voxels in descending code order).  Each point is evaluated by the rank that
+ * loaded it; the output is one int32 per point of the rank's own load, in the order given to vgs_tiles_set_points.  The concatenation over
+ * the ranks equals, with ==, what the rule gives on the gathered points with those global labels.
+ * Who refines what.  A rank refines a node when the node holds at least one point of its own load and the node's centre lies at most
+ * reach = max(graph_size, 0.5001 voxel_size) outside the rank's region, per axis.  That covers the nodes the rank owns, the nodes whose
+ * cube crosses its border (0.5001 voxel_size: the geometric part of the straddle test of the ownership pass) and the nodes of objects
+ * that reach over a tile's edge by up to graph_size.  With points loaded by region it covers every point: a point lies inside the cube of
+ * its voxel, so its rank owns the voxel or the cube reaches over the border into the rank's region.  Own points in any other node were
+ * loaded further outside the region than that; their rows are not complete on this rank, so they keep their label of
+ * vgs_tiles_get_point_labels and are counted in counts[4] (0 with points loaded by region, or within graph_size of it).
+ * Why the rank holds what it needs.  A refined node's centre lies at most reach outside the region, per axis.  Its candidates lie within
+ * graph_size of that centre, and their cubes end within reach + graph_size + 0.5 voxel_size of the border: with reach = graph_size that
+ * is inside the halo of 2 graph_size + voxel_size, so the adjacency row is complete and every node in it carries the same record as on
+ * its owner (the graph section above; a node's record and its used flag depend on its own points only).
+ * What the rank lacks is the LABEL of a candidate another rank owns.  The run's boundary records bring it for the rows of owned used
+ * voxels only; the rows of unused voxels (fill) and of voxels another rank owns reach further.  So every rank publishes (code, global
+ * label) of its owned used voxels whose centre lies within reach + graph_size + 0.5 voxel_size of a border line of its region -- the
+ * band; adjacent tiles share their border lines, so a candidate within reach + graph_size of a neighbour's region is in its owner's
+ * band.  The effective label of a voxel is its own label for an owned used voxel and an entry of the refinement's halo table for any
+ * other: the band records of the other ranks and, for codes they do not name, the run's boundary records.  That table is separate from
+ * the segment graph's, so neither call invalidates the other.  A used candidate whose label is still unknown fails the call on that rank
+ * (VGS_E_UNSUPPORTED, the count in the message) instead of changing the result.
+ * EVERY call is COLLECTIVE -- after one vgs_tiles_run every rank makes it, with the same parameters -- and makes exactly ONE
+ * all_gather_varlen of 16-byte records (uint64 code, int32 label, int32 pad) behind a header of two such entries: status word and fill,
+ * record count and the bits of patch_radius and switch_ratio.  The records are compacted on the device in ascending voxel id, so the
+ * payload has the same bytes from call to call.  The first call after a run carries the band; the table is kept until the next
+ * vgs_tiles_run or vgs_tiles_set_points and later calls send the header only.  rp == NULL: vgs_refine_params_default of the context.
+ * counts (may be NULL), all this rank's share, each adds over the ranks to the whole scene's figure: 0 owned working nodes, 1 own points
+ * examined, 2 own labelled points changed, 3 own unlabelled points filled, 4 own points left unrefined beyond the strip.  No float
+ * atomics: the output is bit-identical from call to call.  vgs_tiles_run gains no launch and no collective; point labels, descriptors,
+ * graph, boxes, attribute tables and comparison are not touched.
+ * vgs_tiles_get_refined_labels copies the labels of the last refine (n int32); it is not collective.  VGS_E_STATE without a refine since
+ * the last run or the last vgs_tiles_set_points.
+ * Failures.  VGS_E_STATE before a run is decided locally (no collective).  A bad parameter (negative or non-finite patch_radius,
+ * switch_ratio outside [0, 1]) and the injected VGS_TILES_FAIL_AT=refine travel in the status word: the failing rank returns its own
+ * status and message, the others VGS_E_PEER naming it.  Ranks that are each valid but disagree on a parameter all return VGS_E_ARG after
+ * the exchange; the message names the lowest rank that differs from rank 0.  A failure of the local refinement behind the exchange (the
+ * unknown label above) is returned by that rank and travels in the status word of its next collective. */
+vgs_status vgs_tiles_refine_point_labels(vgs_tiles* t, const vgs_refine_params* rp /* NULL: the context's defaults */, int64_t* counts /* 5 */);
+vgs_status vgs_tiles_get_refined_labels(vgs_tiles* t, int32_t* labels /* n */);
+/* host wall time of the last refine on this rank, milliseconds: own band records on the GPU (with their download; 0 records after the
+ * first call), the exchange, the halo table (list, upload, lookup), the refinement on the GPU, total */
+enum { VGS_TILES_R_BAND = 0, VGS_TILES_R_EXCHANGE = 1, VGS_TILES_R_TABLE = 2, VGS_TILES_R_REFINE = 3, VGS_TILES_R_TOTAL = 4, VGS_TILES_R_COUNT = 5 };
+vgs_status vgs_tiles_get_refine_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_R_COUNT */);
+/* that refine's payload on this rank: band records it sent, bytes it put into the all-gather (header included, before padding) */
+vgs_status vgs_tiles_get_refine_payload(vgs_tiles* t, int64_t* band_records, int64_t* bytes_sent);
 /* the rank's engine context (read-only use: counts, stage times) */
 vgs_ctx* vgs_tiles_context(vgs_tiles* t);
 

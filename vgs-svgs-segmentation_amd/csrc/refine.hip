@@ -175,20 +175,27 @@ __global__ __launch_bounds__(RF_TB) void k_rf_refine(const uint32_t* __restrict_
   }
 }
 
+// exclusive scan of n counts (flags, batches: in rf_batches, n + 1 entries allocated) into rf_start; the total is read back
+static vgs_status rf_scan_flags(vgs_ctx* c, size_t n, uint32_t* total) {
+  VGS_HIP_TRY(c, hipMemsetAsync(c->rf_batches.p + n, 0, 4, c->stream));
+  size_t bytes = 0;
+  VGS_HIP_TRY(c, rocprim::exclusive_scan(nullptr, bytes, c->rf_batches.p, c->rf_start.p, 0u, n + 1, rocprim::plus<uint32_t>(), c->stream));
+  VGS_HIP_TRY(c, c->sort_tmp.ensure(bytes));
+  VGS_HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.p, bytes, c->rf_batches.p, c->rf_start.p, 0u, n + 1, rocprim::plus<uint32_t>(), c->stream));
+  VGS_READBACK(c, total, c->rf_start.p + n, 4);
+  return VGS_OK;
+}
+
 // mark, scan and refine one list of nodes with their rows
 static vgs_status rf_pass(vgs_ctx* c, const uint32_t* ids, const uint64_t* rows, const uint32_t* cnt, int64_t n, const vgs_refine_params& rp) {
   if (n <= 0) return VGS_OK;
   VGS_HIP_TRY(c, c->rf_batches.ensure((size_t)n + 1)); VGS_HIP_TRY(c, c->rf_start.ensure((size_t)n + 1));
   unsigned long long* counts = (unsigned long long*)c->rf_counts.p;
-  VGS_HIP_TRY(c, hipMemsetAsync(c->rf_batches.p + n, 0, 4, c->stream));
   hipLaunchKernelGGL(k_rf_mark, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, ids, rows, cnt, (uint32_t)n, c->adj_stride, c->node.p,
                      c->vox_label.p, c->vox_start.p, rp.fill ? 1 : 0, c->rf_batches.p, counts);
-  size_t bytes = 0;
-  VGS_HIP_TRY(c, rocprim::exclusive_scan(nullptr, bytes, c->rf_batches.p, c->rf_start.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), c->stream));
-  VGS_HIP_TRY(c, c->sort_tmp.ensure(bytes));
-  VGS_HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.p, bytes, c->rf_batches.p, c->rf_start.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), c->stream));
   uint32_t n_items = 0;
-  VGS_READBACK(c, &n_items, c->rf_start.p + n, 4);
+  vgs_status s = rf_scan_flags(c, (size_t)n, &n_items);
+  if (s != VGS_OK) return s;
   if (n_items > 0)
     hipLaunchKernelGGL(k_rf_refine, dim3(n_items), dim3(RF_TB), 0, c->stream, ids, rows, cnt, (uint32_t)n, c->adj_stride, c->rf_start.p, c->node.p,
                        c->vox_label.p, c->vox_start.p, c->xs.p, c->ys.p, c->zs.p, c->perm_b.p, rp.patch_radius, rp.switch_ratio, c->rf_label.p,
@@ -240,10 +247,383 @@ vgs_status vgs_refine_on_device(vgs_ctx* c, const vgs_refine_params& rp, int64_t
   return VGS_OK;
 }
 
-static vgs_status rf_check(vgs_ctx* c, const char* fn) {
+// ---- tile contexts ---------------------------------------------------------------------------------------------------------------
+// The rule over the whole scene, this rank's share (include/vgs_tiles.h: vgs_tiles_refine_point_labels).  A rank refines the nodes that hold
+// points of its own load and whose centre lies at most RF reach = max(graph_size, 0.5001 voxel_size) outside its region, per axis -- the
+// nodes it owns, those whose cube crosses its border, and those of objects that reach over a tile's edge (scenes.tiled_urban_scene hands
+// a rank points up to 0.4 m beyond its region).  Their rows are complete here and carry the owner's node records: the candidates lie
+// within graph_size of the centre, so their cubes end within 2 graph_size + 0.5 voxel_size of the border, inside the halo of 2 graph_size
+// + voxel_size.  What differs from the single context:
+//   * labels come from a table of EFFECTIVE labels (k_rf_tile_labels): vox_label for an owned used voxel, the refinement's own halo table
+//     (vgs_set_refine_halo_labels; RF_UNKNOWN without a record) for a used voxel of another rank, -1 for an unused one;
+//   * a point takes part only when it is of the rank's own load; points of other ranks' strips are left to their ranks;
+//   * a working node is counted by its owner, so the mark pass also looks at owned nodes without own points (no batches for them);
+//   * own points of any other node (loaded further beyond the region than that) keep their point label and are counted.
+// The single-context kernels above are not touched: these are siblings, not template variants, so that their code stays as it was.
+#define RF_UNKNOWN (-2)
+#define RF_M_REFINE 1u   // mask bit 0: holds own points and lies within reach of the region: this rank refines it
+#define RF_M_OWNED 2u    // mask bit 1: owned: this rank counts it when it is a working node
+
+// the region of a tile and its grid, as k_owned (multigpu.hip) takes them: the centre of a voxel is a function of its global code and the
+// shared grid only, so every rank computes the same one
+struct RfRegion { float res_f, min_x, min_y; double lo_x, lo_y, hi_x, hi_y; };
+__device__ __forceinline__ void rf_center(const RfRegion& g, uint64_t code, double& cx, double& cy) {
+  cx = (double)vm_voxel_center(vm_compact21(code >> 2), g.res_f, g.min_x);
+  cy = (double)vm_voxel_center(vm_compact21(code >> 1), g.res_f, g.min_y);
+}
+
+// the band: owned used voxels whose centre lies within `near` of a border line of the region -- what a neighbour can reach from a node it
+// refines -- as a flag per voxel and (behind the scan) as records in ascending voxel id
+__global__ void k_rf_band_flags(const uint64_t* __restrict__ vox_code, const uint8_t* __restrict__ owned, const uint32_t* __restrict__ used_rank, int64_t V,
+                                RfRegion g, double near, uint32_t* __restrict__ flag) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  double cx, cy;
+  rf_center(g, vox_code[v], cx, cy);
+  const bool nr = fabs(cx - g.lo_x) < near || fabs(cx - g.hi_x) < near || fabs(cy - g.lo_y) < near || fabs(cy - g.hi_y) < near;
+  flag[v] = (nr && owned[v] && used_rank[v] != 0xffffffffu) ? 1u : 0u;
+}
+__global__ void k_rf_band_compact(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ excl, int64_t V, const uint64_t* __restrict__ vox_code,
+                                  const int32_t* __restrict__ vox_label, uint64_t* __restrict__ code, int32_t* __restrict__ label) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < V && flag[v]) { code[excl[v]] = vox_code[v]; label[excl[v]] = vox_label[v]; }   // (excl[v] < excl[V], the size of both arrays)
+}
+
+// one pass over V: the effective label and the mask of every voxel.  reach = 0.5001 voxel_size would be the geometric part of k_owned's
+// straddle bit 0 (multigpu.hip): the cube crosses the border.
+__global__ void k_rf_tile_labels(const uint64_t* __restrict__ vox_code, const NodeRec* __restrict__ node, const int32_t* __restrict__ vox_label,
+                                 const uint8_t* __restrict__ owned, const uint8_t* __restrict__ mix, const int32_t* __restrict__ halo, int64_t V,
+                                 RfRegion g, double reach, int32_t* __restrict__ eff, uint8_t* __restrict__ mask) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const bool own = owned[v] != 0;
+  eff[v] = (node[v].flags & VGS_F_EIG) ? (own ? vox_label[v] : halo[v]) : -1;
+  double cx, cy;
+  rf_center(g, vox_code[v], cx, cy);
+  const double dx = fmax(fmax(g.lo_x - cx, cx - g.hi_x), 0.0), dy = fmax(fmax(g.lo_y - cy, cy - g.hi_y), 0.0);   // outside the region by, per axis
+  const bool within = own || (dx <= reach && dy <= reach);
+  const bool mine = mix && mix[v] != 0;
+  mask[v] = (uint8_t)((mine && within ? RF_M_REFINE : 0u) | (own ? RF_M_OWNED : 0u));
+}
+
+// own points only: A of a refinable node, the point label elsewhere (counts[4]); -1 outside every node
+__global__ __launch_bounds__(256) void k_rf_tile_init(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ pt_vox,
+                                                      const int32_t* __restrict__ eff, const uint8_t* __restrict__ mask,
+                                                      const int32_t* __restrict__ pt_label, int64_t N, int64_t own_first, int64_t n_own,
+                                                      int32_t* __restrict__ label, unsigned long long* __restrict__ counts) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool beyond = false;
+  if (j < N) {
+    const int64_t i = (int64_t)perm[j];
+    if (i >= own_first && i < own_first + n_own) {
+      const uint32_t v = pt_vox[j];
+      int32_t out = -1;
+      if (v != 0xffffffffu) {
+        if (mask[v] & RF_M_REFINE) out = max(eff[v], -1);
+        else { out = pt_label[i]; beyond = true; }
+      }
+      label[i] = out;
+    }
+  }
+  const unsigned long long nb = (unsigned long long)__popcll(__ballot(beyond));
+  if ((threadIdx.x & 63) == 0 && nb) atomicAdd(&counts[4], nb);
+}
+
+// the unused voxels the mark pass lists with fill: refinable or owned (an owned one without own points is only counted)
+__global__ void k_rf_tile_fill_flags(const uint32_t* __restrict__ used_rank, const uint8_t* __restrict__ mask, int64_t V, uint32_t* __restrict__ flag) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < V) flag[v] = (used_rank[v] == 0xffffffffu && mask[v] != 0) ? 1u : 0u;
+}
+
+// the label w brings as a candidate of a tile: -1 when it is none, RF_UNKNOWN when it is one whose label no record brought
+__device__ __forceinline__ int32_t rf_tile_cand_label(uint32_t flags, const int32_t* __restrict__ eff, uint32_t w) {
+  const uint32_t need = VGS_F_EIG | VGS_F_POS | VGS_F_NRM;
+  if ((flags & need) != need) return -1;
+  const int32_t l = eff[w];
+  return (l >= 0 || l == RF_UNKNOWN) ? l : -1;
+}
+
+// k_rf_mark of a tile: counts[0] by the owner, batches for refinable nodes only, counts[5] = candidates of unknown label
+__global__ __launch_bounds__(256) void k_rf_tile_mark(const uint32_t* __restrict__ ids, const uint64_t* __restrict__ rows, const uint32_t* __restrict__ cnt,
+                                                      uint32_t n, int stride, const NodeRec* __restrict__ node, const int32_t* __restrict__ eff,
+                                                      const uint8_t* __restrict__ mask, const uint32_t* __restrict__ vox_start, int fill,
+                                                      uint32_t* __restrict__ batches, unsigned long long* __restrict__ counts) {
+  const uint32_t i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (i >= n) return;   // (whole wavefronts; no barrier follows)
+  const uint32_t v = ids[i];
+  const uint32_t mk = mask[v];
+  if (mk == 0) { if (lane == 0) batches[i] = 0u; return; }   // a voxel of the halo that this rank neither refines nor counts
+  const int32_t A = eff[v];
+  bool hit = false;
+  uint32_t unk = 0;
+  if (A >= 0 || fill) {
+    const uint32_t m = min(cnt[i], (uint32_t)stride);
+    const uint64_t* row = rows + (size_t)i * stride;
+    for (uint32_t k = lane; k <= m; k += 64) {   // entry m: the node itself
+      const uint32_t w = k < m ? (uint32_t)row[k] : v;
+      const int32_t L = rf_tile_cand_label(node[w].flags, eff, w);
+      unk += (L == RF_UNKNOWN || (k == m && A == RF_UNKNOWN)) ? 1u : 0u;   // (the node's own label, whatever its flags)
+      hit = hit || (L >= 0 && L != A);
+    }
+  } else if (lane == 0 && A == RF_UNKNOWN) unk = 1u;   // (not -1: a used node of another rank without a record)
+  const bool work = __ballot(hit) != 0ull;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) unk += __shfl_xor(unk, o, 64);
+  if (lane != 0) return;
+  const uint32_t npts = vox_start[v + 1] - vox_start[v];
+  batches[i] = (work && (mk & RF_M_REFINE)) ? (npts + RF_BATCH - 1) / RF_BATCH : 0u;
+  if (work && (mk & RF_M_OWNED)) atomicAdd(&counts[0], 1ull);
+  if (unk) atomicAdd(&counts[5], (unsigned long long)unk);
+}
+
+// k_rf_refine of a tile: the same staging and the same minima; a lane's point takes part only if it is of the rank's own load
+__global__ __launch_bounds__(RF_TB) void k_rf_tile_refine(const uint32_t* __restrict__ ids, const uint64_t* __restrict__ rows, const uint32_t* __restrict__ cnt,
+                                                          uint32_t n, int stride, const uint32_t* __restrict__ start, const NodeRec* __restrict__ node,
+                                                          const int32_t* __restrict__ eff, const uint32_t* __restrict__ vox_start,
+                                                          const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                          const uint32_t* __restrict__ perm, int64_t own_first, int64_t n_own, float patch_radius,
+                                                          float switch_ratio, int32_t* __restrict__ label, unsigned long long* __restrict__ counts) {
+  __shared__ float4 s_a[RF_CH];   // centroid | label
+  __shared__ float4 s_b[RF_CH];   // normal | node id
+  const uint32_t t = blockIdx.x;
+  const uint32_t lane = threadIdx.x;
+  if (t >= start[n]) return;   // (the whole workgroup)
+  uint32_t lo = 0, hi = n - 1;
+  while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (start[mid] <= t) lo = mid; else hi = mid - 1; }
+  const uint32_t i = lo;
+  const uint32_t v = ids[i];
+  const int32_t A = max(eff[v], -1);
+  const uint32_t p0 = vox_start[v] + (t - start[i]) * RF_BATCH;
+  const uint32_t p1 = min(vox_start[v + 1], p0 + RF_BATCH);
+  float p[RF_PPT][3], best[RF_PPT], cown[RF_PPT];
+  uint32_t bid[RF_PPT], dst[RF_PPT];   // dst: the point's input index, 0xffffffff when the lane has no own point there
+  int32_t blab[RF_PPT];
+  const float inf = vm_from_bits(0x7f800000u);
+#pragma unroll
+  for (int k = 0; k < RF_PPT; ++k) {
+    const uint32_t j = p0 + k * RF_TB + lane;
+    const bool in = j < p1;
+    const uint32_t pi = in ? perm[j] : 0u;
+    dst[k] = (in && (int64_t)pi >= own_first && (int64_t)pi < own_first + n_own) ? pi : 0xffffffffu;
+    p[k][0] = in ? xs[j] : 0.f; p[k][1] = in ? ys[j] : 0.f; p[k][2] = in ? zs[j] : 0.f;
+    best[k] = inf; cown[k] = inf; bid[k] = 0xffffffffu; blab[k] = -1;
+  }
+  const uint32_t m = min(cnt[i], (uint32_t)stride);
+  const uint64_t* row = rows + (size_t)i * stride;
+  for (uint32_t c0 = 0; c0 <= m; c0 += RF_CH) {   // m + 1 entries: the row, then the node itself (k_rf_refine)
+    const uint32_t nc = min((uint32_t)RF_CH, m + 1 - c0);
+    __syncthreads();
+    for (uint32_t e = lane; e < nc; e += RF_TB) {
+      const uint32_t k = c0 + e;
+      const uint32_t w = k < m ? (uint32_t)row[k] : v;
+      const NodeRec* r = node + w;
+      const int32_t L = max(rf_tile_cand_label(r->flags, eff, w), -1);   // (an unknown label fails the call: k_rf_tile_mark counted it)
+      s_a[e] = make_float4(r->c[0], r->c[1], r->c[2], __int_as_float(L));
+      s_b[e] = make_float4(r->n[0], r->n[1], r->n[2], __uint_as_float(w));
+    }
+    __syncthreads();
+    for (uint32_t e = 0; e < nc; ++e) {
+      const float4 a = s_a[e];
+      const int32_t L = __float_as_int(a.w);
+      if (L < 0) continue;   // (the same for every lane)
+      const float4 b = s_b[e];
+      const uint32_t w = __float_as_uint(b.w);
+      const float cc[3] = {a.x, a.y, a.z}, nn[3] = {b.x, b.y, b.z};
+#pragma unroll
+      for (int k = 0; k < RF_PPT; ++k) {
+        const float cost = vm_refine_cost(p[k], cc, nn, patch_radius);
+        if (!vm_isfinite(cost)) continue;
+        if (cost < best[k] || (cost == best[k] && w < bid[k])) { best[k] = cost; bid[k] = w; blab[k] = L; }
+        if (L == A && cost < cown[k]) cown[k] = cost;
+      }
+    }
+  }
+  unsigned long long n_exam = 0, n_changed = 0, n_filled = 0;
+#pragma unroll
+  for (int k = 0; k < RF_PPT; ++k) {
+    const bool in = dst[k] != 0xffffffffu;
+    int32_t out = A;
+    if (A >= 0) { if (cown[k] < inf && best[k] < switch_ratio * cown[k]) out = blab[k]; }
+    else out = blab[k];   // (an unlabelled node is listed with fill only)
+    if (in) label[dst[k]] = out;
+    n_exam += (unsigned long long)__popcll(__ballot(in));
+    n_changed += (unsigned long long)__popcll(__ballot(in && A >= 0 && out != A));
+    n_filled += (unsigned long long)__popcll(__ballot(in && A < 0 && out >= 0));
+  }
+  if (lane == 0) {
+    if (n_exam) atomicAdd(&counts[1], n_exam);
+    if (n_changed) atomicAdd(&counts[2], n_changed);
+    if (n_filled) atomicAdd(&counts[3], n_filled);
+  }
+}
+
+static RfRegion rf_region(const vgs_ctx* c) {
+  return RfRegion{c->P.voxel_size, (float)c->box.min[0], (float)c->box.min[1], c->own_lo[0], c->own_lo[1], c->own_hi[0], c->own_hi[1]};
+}
+// how far outside its region a rank still refines a node, per axis; the band of the other ranks reaches graph_size further (a candidate
+// lies within graph_size of the node) and half a voxel more, so that no rounding of a centre decides
+static double rf_reach(const vgs_ctx* c) { return std::max((double)c->P.graph_size, 0.5001 * (double)c->P.voxel_size); }
+static double rf_band_near(const vgs_ctx* c) { return rf_reach(c) + (double)c->P.graph_size + 0.5 * (double)c->P.voxel_size; }
+
+// rf_pass of a tile
+static vgs_status rf_tile_pass(vgs_ctx* c, const uint32_t* ids, const uint64_t* rows, const uint32_t* cnt, int64_t n, const vgs_refine_params& rp) {
+  if (n <= 0) return VGS_OK;
+  VGS_HIP_TRY(c, c->rf_batches.ensure((size_t)n + 1)); VGS_HIP_TRY(c, c->rf_start.ensure((size_t)n + 1));
+  unsigned long long* counts = (unsigned long long*)c->rf_counts.p;
+  hipLaunchKernelGGL(k_rf_tile_mark, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, ids, rows, cnt, (uint32_t)n, c->adj_stride, c->node.p,
+                     c->rf_eff.p, c->rf_mask.p, c->vox_start.p, rp.fill ? 1 : 0, c->rf_batches.p, counts);
+  uint32_t n_items = 0;
+  vgs_status s = rf_scan_flags(c, (size_t)n, &n_items);
+  if (s != VGS_OK) return s;
+  if (n_items > 0)
+    hipLaunchKernelGGL(k_rf_tile_refine, dim3(n_items), dim3(RF_TB), 0, c->stream, ids, rows, cnt, (uint32_t)n, c->adj_stride, c->rf_start.p, c->node.p,
+                       c->rf_eff.p, c->vox_start.p, c->xs.p, c->ys.p, c->zs.p, c->perm_b.p, c->own_first, c->n_own, rp.patch_radius, rp.switch_ratio,
+                       c->rf_label.p, counts);
+  VGS_HIP_TRY(c, hipGetLastError());
+  return VGS_OK;
+}
+
+vgs_status vgs_refine_own_on_device(vgs_ctx* c, const vgs_refine_params& rp, int64_t* counts5) {
+  c->rf_valid = false;
+  const int64_t N = c->N, V = c->V, U = c->U, nf = c->Nf;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  VGS_HIP_TRY(c, c->rf_label.ensure(N > 0 ? (size_t)N : 1)); VGS_HIP_TRY(c, c->rf_counts.ensure(8));
+  VGS_HIP_TRY(c, hipMemsetAsync(c->rf_counts.p, 0, 8 * sizeof(uint64_t), c->stream));
+  // -1 everywhere first: the points of other ranks' strips are never written by a kernel, and a cloud without a node keeps -1
+  if (N > 0) VGS_HIP_TRY(c, hipMemsetAsync(c->rf_label.p, 0xff, (size_t)N * sizeof(int32_t), c->stream));
+  const int TB = 256;
+  if (N > 0 && V > 0 && nf > 0) {
+    VGS_HIP_TRY(c, c->rf_eff.ensure((size_t)V)); VGS_HIP_TRY(c, c->rf_mask.ensure((size_t)V));
+    const unsigned nbV = (unsigned)((V + TB - 1) / TB);
+    hipLaunchKernelGGL(k_rf_tile_labels, dim3(nbV), dim3(TB), 0, c->stream, c->vox_code.p, c->node.p, c->vox_label.p, c->owned.p,
+                       c->mixsrc.p, c->rf_halo.p, V, rf_region(c), rf_reach(c), c->rf_eff.p, c->rf_mask.p);
+    hipLaunchKernelGGL(k_rf_tile_init, dim3((unsigned)((N + TB - 1) / TB)), dim3(TB), 0, c->stream, c->perm_b.p, c->pt_vox.p, c->rf_eff.p, c->rf_mask.p,
+                       c->pt_label.p, N, c->own_first, c->n_own, c->rf_label.p, (unsigned long long*)c->rf_counts.p);
+    vgs_status s = rf_tile_pass(c, c->used_ids.p, c->adj_key.p, c->adj_cnt.p, U, rp);
+    if (s != VGS_OK) return s;
+    if (rp.fill && V - U > 0 && U > 0) {   // (without a used voxel there is no candidate anywhere)
+      VGS_HIP_TRY(c, c->rf_batches.ensure((size_t)V + 1)); VGS_HIP_TRY(c, c->rf_start.ensure((size_t)V + 1));
+      hipLaunchKernelGGL(k_rf_tile_fill_flags, dim3(nbV), dim3(TB), 0, c->stream, c->used_rank.p, c->rf_mask.p, V, c->rf_batches.p);
+      uint32_t n_list = 0;
+      if ((s = rf_scan_flags(c, (size_t)V, &n_list)) != VGS_OK) return s;
+      if (n_list > 0) {
+        VGS_HIP_TRY(c, c->rf_ids.ensure((size_t)n_list));
+        hipLaunchKernelGGL(k_rf_unused_list, dim3(nbV), dim3(TB), 0, c->stream, c->rf_batches.p, c->rf_start.p, V, n_list, c->rf_ids.p);
+        VGS_HIP_TRY(c, hipGetLastError());
+        // their rows, used neighbours only, a chunk of at most 256 MB of keys at a time
+        const int64_t n_un = (int64_t)n_list;
+        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_un, ((int64_t)32 << 20) / std::max(1, c->adj_stride)));
+        VGS_HIP_TRY(c, c->rf_rows.ensure((size_t)chunk * c->adj_stride)); VGS_HIP_TRY(c, c->rf_cnt.ensure((size_t)chunk)); VGS_HIP_TRY(c, c->rf_nall.ensure((size_t)chunk));
+        for (int64_t o = 0; o < n_un; o += chunk) {
+          const int64_t m = std::min(chunk, n_un - o);
+          s = vgs_run_adjacency(c, false, c->rf_rows.p, c->rf_cnt.p, c->rf_nall.p, c->adj_r2, c->rf_ids.p + o, m);
+          if (s != VGS_OK) return s;
+          if ((s = rf_tile_pass(c, c->rf_ids.p + o, c->rf_rows.p, c->rf_cnt.p, m, rp)) != VGS_OK) return s;
+        }
+      }
+    }
+  }
+  uint64_t h[6] = {0, 0, 0, 0, 0, 0};
+  VGS_READBACK(c, h, c->rf_counts.p, sizeof(h));
+  if (h[5]) {
+    c->err = "vgs_refine_own_point_labels: " + std::to_string(h[5]) + " candidates of this rank's nodes are used voxels of another rank whose label no record brought (vgs_set_refine_halo_labels)";
+    return VGS_E_UNSUPPORTED;
+  }
+  if (counts5) for (int k = 0; k < 5; ++k) counts5[k] = (int64_t)h[k];
+  c->rf_valid = true;
+  return VGS_OK;
+}
+
+static vgs_status rf_tile_check(vgs_ctx* c, const char* fn) {
   if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
-  if (vgs_is_tile(c)) {
-    c->err = std::string(fn) + ": a tile context (owned region / own point range) holds only part of its segments; refinement needs the whole cloud in one context";
+  if (!c->have_region || c->n_own < 0) {
+    c->err = std::string(fn) + ": a tile context (vgs_set_owned_region and vgs_set_own_point_range) only";
+    return VGS_E_STATE;
+  }
+  return VGS_OK;
+}
+
+static vgs_status rf_check_params(vgs_ctx* c, const vgs_refine_params* rp, const char* fn) {
+  if (!(rp->patch_radius >= 0.f) || !std::isfinite(rp->patch_radius)) {
+    c->err = std::string(fn) + ": patch_radius must be finite and not negative";
+    return VGS_E_ARG;
+  }
+  if (!(rp->switch_ratio >= 0.f && rp->switch_ratio <= 1.f)) { c->err = std::string(fn) + ": switch_ratio must lie in [0, 1]"; return VGS_E_ARG; }
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_set_refine_halo_labels(vgs_ctx* c, const uint64_t* code, const int32_t* label, int64_t n) {
+  if (!c || n < 0 || (n > 0 && (!code || !label))) return VGS_E_ARG;
+  vgs_status s = rf_tile_check(c, "vgs_set_refine_halo_labels");
+  if (s != VGS_OK) return s;
+  for (int64_t k = 0; k < n; ++k)
+    if (label[k] < -1) { c->err = "vgs_set_refine_halo_labels: a label below -1"; return VGS_E_ARG; }
+  c->rf_halo_valid = false; c->rf_valid = false;
+  const int64_t V = c->V;
+  if (V == 0) { c->rf_halo_valid = true; return VGS_OK; }
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  VGS_HIP_TRY(c, c->rf_halo.ensure((size_t)V));
+  VGS_HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)c->rf_halo.p, RF_UNKNOWN, (size_t)V, c->stream));
+  if (n > 0) {
+    VGS_HIP_TRY(c, c->rf_hcode.ensure((size_t)n)); VGS_HIP_TRY(c, c->rf_hlab.ensure((size_t)n));
+    VGS_HIP_TRY(c, hipMemcpyAsync(c->rf_hcode.p, code, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    VGS_HIP_TRY(c, hipMemcpyAsync(c->rf_hlab.p, label, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if ((s = vgs_halo_find(c, c->rf_hcode.p, c->rf_hlab.p, n, c->rf_halo.p)) != VGS_OK) return s;   // (one record per code: the caller's)
+  }
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the upload reads the caller's arrays)
+  c->rf_halo_valid = true;
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_get_own_band_labels(vgs_ctx* c, int64_t* n, uint64_t* code, int32_t* label) {
+  if (!c || !n) return VGS_E_ARG;
+  *n = 0;
+  vgs_status s = rf_tile_check(c, "vgs_get_own_band_labels");
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  const int64_t V = c->V;
+  if ((!code && !label) || c->rf_band_n < 0) {   // two-call protocol: the size query computes, the call with arrays copies those records
+    c->rf_band_n = -1;
+    uint32_t total = 0;
+    if (V > 0) {
+      const int TB = 256;
+      const unsigned nbV = (unsigned)((V + TB - 1) / TB);
+      VGS_HIP_TRY(c, c->rf_batches.ensure((size_t)V + 1)); VGS_HIP_TRY(c, c->rf_start.ensure((size_t)V + 1));
+      hipLaunchKernelGGL(k_rf_band_flags, dim3(nbV), dim3(TB), 0, c->stream, c->vox_code.p, c->owned.p, c->used_rank.p, V, rf_region(c), rf_band_near(c),
+                         c->rf_batches.p);
+      if ((s = rf_scan_flags(c, (size_t)V, &total)) != VGS_OK) return s;
+      if (total > 0) {
+        VGS_HIP_TRY(c, c->rf_bcode.ensure((size_t)total)); VGS_HIP_TRY(c, c->rf_blab.ensure((size_t)total));
+        hipLaunchKernelGGL(k_rf_band_compact, dim3(nbV), dim3(TB), 0, c->stream, c->rf_batches.p, c->rf_start.p, V, c->vox_code.p, c->vox_label.p,
+                           c->rf_bcode.p, c->rf_blab.p);
+        VGS_HIP_TRY(c, hipGetLastError());
+        VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the copies below do not wait for the context's stream
+      }
+    }
+    c->rf_band_n = (int64_t)total;
+  }
+  *n = c->rf_band_n;
+  const size_t m = (size_t)c->rf_band_n;
+  if (code && m) VGS_HIP_TRY(c, hipMemcpy(code, c->rf_bcode.p, m * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (label && m) VGS_HIP_TRY(c, hipMemcpy(label, c->rf_blab.p, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_refine_own_point_labels(vgs_ctx* c, const vgs_refine_params* rp, int64_t* counts) {
+  if (!c || !rp) return VGS_E_ARG;
+  vgs_status s = rf_tile_check(c, "vgs_refine_own_point_labels");
+  if (s != VGS_OK) return s;
+  if ((s = rf_check_params(c, rp, "vgs_refine_own_point_labels")) != VGS_OK) return s;
+  if (!c->rf_halo_valid) { c->err = "vgs_refine_own_point_labels: no halo labels since the last labels of the tile (vgs_set_refine_halo_labels first)"; return VGS_E_STATE; }
+  return vgs_refine_own_on_device(c, *rp, counts);
+}
+
+// tile_too: the getters serve a tile context after vgs_refine_own_point_labels; vgs_refine_point_labels itself refuses one
+static vgs_status rf_check(vgs_ctx* c, const char* fn, bool tile_too = false) {
+  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
+  if (vgs_is_tile(c) && !tile_too) {
+    c->err = std::string(fn) + ": a tile context (owned region / own point range) holds only part of its segments; the tiled driver refines over all ranks (vgs_tiles_refine_point_labels, vgs_refine_own_point_labels)";
     return VGS_E_STATE;
   }
   return VGS_OK;
@@ -261,28 +641,24 @@ extern "C" vgs_status vgs_refine_point_labels(vgs_ctx* c, const vgs_refine_param
   if (!c || !rp) return VGS_E_ARG;
   vgs_status s = rf_check(c, "vgs_refine_point_labels");
   if (s != VGS_OK) return s;
-  if (!(rp->patch_radius >= 0.f) || !std::isfinite(rp->patch_radius)) {
-    c->err = "vgs_refine_point_labels: patch_radius must be finite and not negative";
-    return VGS_E_ARG;
-  }
-  if (!(rp->switch_ratio >= 0.f && rp->switch_ratio <= 1.f)) { c->err = "vgs_refine_point_labels: switch_ratio must lie in [0, 1]"; return VGS_E_ARG; }
+  if ((s = rf_check_params(c, rp, "vgs_refine_point_labels")) != VGS_OK) return s;
   return vgs_refine_on_device(c, *rp, counts);
 }
 
 extern "C" vgs_status vgs_get_refined_labels(vgs_ctx* c, int32_t* labels) {
   if (!c || !labels) return VGS_E_ARG;
-  vgs_status s = rf_check(c, "vgs_get_refined_labels");
+  vgs_status s = rf_check(c, "vgs_get_refined_labels", true);
   if (s != VGS_OK) return s;
-  if (!c->rf_valid) { c->err = "vgs_get_refined_labels: no refinement since the last run of the stages (vgs_refine_point_labels first)"; return VGS_E_STATE; }
+  if (!c->rf_valid) { c->err = "vgs_get_refined_labels: no refinement since the last run of the stages (vgs_refine_point_labels, or vgs_refine_own_point_labels on a tile context, first)"; return VGS_E_STATE; }
   if (c->N > 0) VGS_HIP_TRY(c, hipMemcpy(labels, c->rf_label.p, (size_t)c->N * 4, hipMemcpyDeviceToHost));
   return VGS_OK;
 }
 
 extern "C" vgs_status vgs_get_refined_labels_device(vgs_ctx* c, const int32_t** labels_dev) {
   if (!c || !labels_dev) return VGS_E_ARG;
-  vgs_status s = rf_check(c, "vgs_get_refined_labels_device");
+  vgs_status s = rf_check(c, "vgs_get_refined_labels_device", true);
   if (s != VGS_OK) return s;
-  if (!c->rf_valid) { c->err = "vgs_get_refined_labels_device: no refinement since the last run of the stages (vgs_refine_point_labels first)"; return VGS_E_STATE; }
+  if (!c->rf_valid) { c->err = "vgs_get_refined_labels_device: no refinement since the last run of the stages (vgs_refine_point_labels, or vgs_refine_own_point_labels on a tile context, first)"; return VGS_E_STATE; }
   *labels_dev = c->rf_label.p;
   return VGS_OK;
 }

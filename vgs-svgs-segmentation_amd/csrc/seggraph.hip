@@ -63,10 +63,8 @@ __global__ void k_sg_halo_find(const uint64_t* __restrict__ code, const int32_t*
                                int64_t V, const uint8_t* __restrict__ owned, int32_t* __restrict__ halo) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
-  const uint64_t q = code[k];
-  int64_t lo = 0, hi = V;
-  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (vox_code[mid] > q) lo = mid + 1; else hi = mid; }
-  if (lo < V && vox_code[lo] == q && !owned[lo]) halo[lo] = label[k];
+  const int64_t v = vgs_find_voxel(vox_code, V, code[k]);
+  if (v < V && !owned[v]) halo[v] = label[k];
 }
 
 __device__ __forceinline__ double sg_wave_sum(double x) {
@@ -445,6 +443,14 @@ extern "C" vgs_status vgs_get_segment_graph_device(vgs_ctx* c, int64_t* n_edges,
 }
 
 // ---- tile contexts ---------------------------------------------------------------------------------------------------------------
+vgs_status vgs_halo_find(vgs_ctx* c, const uint64_t* code_dev, const int32_t* label_dev, int64_t n, int32_t* halo_dev) {
+  if (n <= 0 || c->V == 0) return VGS_OK;
+  hipLaunchKernelGGL(k_sg_halo_find, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, code_dev, label_dev, n, c->vox_code.p, c->V, c->owned.p,
+                     halo_dev);
+  VGS_HIP_TRY(c, hipGetLastError());
+  return VGS_OK;
+}
+
 static vgs_status sg_tile_check(vgs_ctx* c, const char* fn) {
   if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
   if (!c->have_region || c->n_own < 0) {
@@ -470,9 +476,7 @@ extern "C" vgs_status vgs_set_halo_labels(vgs_ctx* c, const uint64_t* code, cons
     VGS_HIP_TRY(c, c->sg_hcode.ensure((size_t)n)); VGS_HIP_TRY(c, c->sg_hlab.ensure((size_t)n));
     VGS_HIP_TRY(c, hipMemcpyAsync(c->sg_hcode.p, code, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     VGS_HIP_TRY(c, hipMemcpyAsync(c->sg_hlab.p, label, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_sg_halo_find, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->sg_hcode.p, c->sg_hlab.p, n, c->vox_code.p, V,
-                       c->owned.p, c->sg_halo.p);
-    VGS_HIP_TRY(c, hipGetLastError());
+    if ((s = vgs_halo_find(c, c->sg_hcode.p, c->sg_hlab.p, n, c->sg_halo.p)) != VGS_OK) return s;
   }
   VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the upload reads the caller's arrays)
   c->sg_halo_valid = true;

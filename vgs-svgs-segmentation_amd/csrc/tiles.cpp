@@ -7,7 +7,7 @@
 // the next one (they would wait for ever: ADVICE r3).  So a failing step only records its status (`carry`: TCARRY, inject), the rank
 // still joins the next collective with that status in its payload's header, and every rank reads the headers and leaves with the same
 // verdict (agreed): the failing rank its own error, the others VGS_E_PEER naming the lowest failing rank.  A failure BEHIND a call's last
-// collective is returned and kept in t->pending (behind_collective), and the next collective's header carries it.  The six collectives
+// collective is returned and kept in t->pending (behind_collective), and the next collective's header carries it.  The seven collectives
 // after vgs_tiles_run all read: open_collective (guard, carry = pending, injection) -> own records, header filled in -> exchange (ONE
 // all_gather_varlen + the scan of the headers) -> fold -> behind_collective(finish on this rank's GPU).  vgs_tiles_set_points, chain_grid
 // and the boundary exchange of vgs_tiles_run carry the status in payloads of their own shapes and share first_bad_rank and agreed.
@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdio>
@@ -482,6 +483,15 @@ bool fold_class_counts(const std::vector<ClassRecs>& ranks, int64_t K, int nc, s
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------ label refinement
+// One band record of one rank (vgs_get_own_band_labels): the payload of the refinement's exchange.  Its first TWO entries are the header:
+// [0] code = the rank's status word, label = fill; [1] code = its record count, label | pad = the bits of patch_radius | switch_ratio.
+struct BandRec {
+  uint64_t code = 0;
+  int32_t label = 0, pad = 0;
+};
+static_assert(sizeof(BandRec) == 16, "BandRec is the exchange's wire format");
+
 // ------------------------------------------------------------------------------------------------ payload headers
 // Every payload of a post-run collective opens with a header that holds the rank's status word and its record count: the first entry of
 // a struct payload (status in its first field; the count where the record has a slot wide enough for it), the first three words of a word
@@ -491,9 +501,11 @@ void set_header(EdgeRec& h, vgs_status st, size_t n) { h.a = (int32_t)st; h.n_pa
 void set_header(ExtentRec& h, vgs_status st, size_t n) { h.label = (int32_t)st; h.lo[0] = (double)n; }
 template <typename W> void set_header(std::vector<W>& w, vgs_status st, int64_t n, int64_t own) { w[0] = (W)(uint32_t)st; w[1] = (W)n; w[2] = (W)own; }
 template <typename T> constexpr size_t header_len() { return std::is_integral<T>::value ? 3 : 1; }   // entries of the payload
+template <> constexpr size_t header_len<BandRec>() { return 2; }
 bool header_ok(const MomentRec& h) { return h.label == 0; }
 bool header_ok(const EdgeRec& h) { return h.a == 0; }
 bool header_ok(const ExtentRec& h) { return h.label == 0; }
+bool header_ok(const BandRec& h) { return h.code == 0; }
 bool header_ok(uint64_t word0) { return word0 == 0; }
 bool header_ok(int64_t word0) { return word0 == 0; }
 template <typename T> void strip_headers(std::vector<std::vector<T>>& gathered) { for (std::vector<T>& g : gathered) g.erase(g.begin()); }
@@ -509,9 +521,10 @@ template <typename F> int first_bad_rank(int world, F bad) {
 
 // Where a rank can be told to fail (tests of the agreed-status protocol: VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=<name>).  points, grid and
 // stages: before that phase's collective; upload: behind the last collective of vgs_tiles_set_points; the others: before the exchange of
-// that post-run collective (fields: vgs_tiles_segment_field_stats and vgs_tiles_segment_class_histogram alike).
-enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_COUNT };
-const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare"};
+// that post-run collective (fields: vgs_tiles_segment_field_stats and vgs_tiles_segment_class_histogram alike; refine:
+// vgs_tiles_refine_point_labels).
+enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_REFINE, PH_COUNT };
+const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare", "refine"};
 
 // Phase clock of one call: lap(slot) gives the slot the host wall time since the last lap (the start, for the first), total(slot) the
 // time from the start to the last lap.  Milliseconds.  vgs_tiles_run stamps t->times as it goes; a post-run collective stamps an array of
@@ -572,6 +585,12 @@ struct vgs_tiles {
   bool cmp_valid = false;
   double ctimes[VGS_TILES_C_COUNT] = {0};
   int64_t c_own = 0, c_bytes = 0;
+  // label refinement: the band table is in the context (vgs_set_refine_halo_labels) from the first refine after a run until the next run
+  // or set_points (band_valid: later calls send the header only); the refined labels are in the context too (rf_valid); the last call's
+  // phases, band records and bytes sent
+  bool band_valid = false, rf_valid = false;
+  double rtimes[VGS_TILES_R_COUNT] = {0};
+  int64_t r_band = 0, r_bytes = 0;
   std::string err;
 };
 
@@ -638,7 +657,7 @@ static vgs_status behind_collective(vgs_tiles* t, vgs_status s, const char* what
 }
 
 // what a new cloud or a new run makes stale: the run itself and every table cached from it
-static void invalidate(vgs_tiles* t) { t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false; }
+static void invalidate(vgs_tiles* t) { t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false; t->band_valid = false; t->rf_valid = false; }
 
 template <int N> static vgs_status get_times(vgs_tiles* t, double (vgs_tiles::*slots)[N], double* ms, int32_t n) {
   if (!t || !ms || n < 0 || n > N) return VGS_E_ARG;
@@ -1260,6 +1279,134 @@ vgs_status vgs_tiles_get_compare_payload(vgs_tiles* t, int64_t* own_cells, int64
   if (!t) return VGS_E_ARG;
   if (own_cells) *own_cells = t->c_own;
   if (bytes_sent) *bytes_sent = t->c_bytes;
+  return VGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ point-level label refinement
+// The refinement over the ranks (include/vgs_tiles.h): this rank's band records, compacted on its GPU (first call after a run only) -> ONE
+// all_gather_varlen of 16-byte records behind a header of status word, record count and the three parameters -> the halo table of the
+// refinement in the context: the band records of the other ranks and, for the codes they do not name, the run's boundary records as the
+// segment graph uses them -> this rank's share of the rule on its GPU (vgs_refine_own_point_labels).  No label of a point travels.
+vgs_status vgs_tiles_refine_point_labels(vgs_tiles* t, const vgs_refine_params* rp_in, int64_t* counts) {
+  if (!t) return VGS_E_ARG;
+  vgs_status carry;
+  TRY(open_collective(t, "vgs_tiles_refine_point_labels", PH_REFINE, carry));
+  Comm& c = *t->comm;
+  t->rf_valid = false;
+  double ms[VGS_TILES_R_COUNT] = {0};
+  Stopwatch sw(ms);
+  vgs_refine_params rp;
+  if (rp_in) rp = *rp_in;
+  else TCARRY(vgs_refine_params_default(t->ctx, &rp));
+  if (carry != VGS_OK && !rp_in) { rp.patch_radius = 0.f; rp.switch_ratio = 0.f; rp.fill = 0; }
+  rp.fill = rp.fill ? 1 : 0;
+  // what a rank can get wrong on its own travels in the status word (the context would refuse the same values behind the exchange)
+  if (carry == VGS_OK && (!(rp.patch_radius >= 0.f) || !std::isfinite(rp.patch_radius))) { carry = VGS_E_ARG; t->err = "vgs_tiles_refine_point_labels: patch_radius must be finite and not negative"; }
+  if (carry == VGS_OK && !(rp.switch_ratio >= 0.f && rp.switch_ratio <= 1.f)) { carry = VGS_E_ARG; t->err = "vgs_tiles_refine_point_labels: switch_ratio must lie in [0, 1]"; }
+  const bool send_band = !t->band_valid;   // (the same on every rank: set behind an exchange every rank saw succeed, dropped by run / set_points)
+  std::vector<BandRec> payload(2);
+  if (send_band && carry == VGS_OK) {
+    int64_t n = 0;
+    TCARRY(vgs_get_own_band_labels(t->ctx, &n, nullptr, nullptr));
+    if (carry == VGS_OK && n > 0) {
+      std::vector<uint64_t> code((size_t)n);
+      std::vector<int32_t> lab((size_t)n);
+      TCARRY(vgs_get_own_band_labels(t->ctx, &n, code.data(), lab.data()));
+      if (carry == VGS_OK) {
+        payload.resize(2 + (size_t)n);
+        for (size_t i = 0; i < (size_t)n; ++i) { payload[2 + i].code = code[i]; payload[2 + i].label = lab[i]; }
+      }
+    }
+  }
+  payload[0].code = (uint64_t)(uint32_t)carry; payload[0].label = rp.fill;
+  payload[1].code = (uint64_t)(payload.size() - 2);
+  std::memcpy(&payload[1].label, &rp.patch_radius, 4); std::memcpy(&payload[1].pad, &rp.switch_ratio, 4);
+  sw.lap(VGS_TILES_R_BAND);
+  std::vector<std::vector<BandRec>> gathered;
+  TRY(exchange(t, carry, payload, "refine", sw, VGS_TILES_R_EXCHANGE, gathered));
+  for (size_t r = 0; r < gathered.size(); ++r)
+    if (gathered[r].size() != 2 + (size_t)gathered[r][1].code) return tfail(t, VGS_E_STATE, "vgs_tiles_refine_point_labels: rank " + std::to_string(r) + " sent a payload of the wrong size");
+  // every rank was valid on its own; they must also describe the same refinement (the precedent of n_channels)
+  vgs_status verdict = VGS_OK;
+  for (size_t r = 1; r < gathered.size() && verdict == VGS_OK; ++r) {
+    const BandRec *a = gathered[r].data(), *b = gathered[0].data();
+    float pr[2], sr[2];
+    std::memcpy(&pr[0], &a[1].label, 4); std::memcpy(&pr[1], &b[1].label, 4); std::memcpy(&sr[0], &a[1].pad, 4); std::memcpy(&sr[1], &b[1].pad, 4);
+    if (a[0].label != b[0].label || pr[0] != pr[1] || sr[0] != sr[1]) {   // as values: 0.0 and -0.0 agree (no NaN gets here: it fails its own rank)
+      verdict = tfail(t, VGS_E_ARG, "vgs_tiles_refine_point_labels: rank " + std::to_string(r) + " passed (patch_radius, switch_ratio, fill) = (" + std::to_string(pr[0]) + ", " +
+                                        std::to_string(sr[0]) + ", " + std::to_string(a[0].label) + "), rank 0 passed (" + std::to_string(pr[1]) + ", " + std::to_string(sr[1]) + ", " +
+                                        std::to_string(b[0].label) + ")");
+    }
+  }
+  if (send_band) {
+    // The band has travelled on every rank alike: the flag follows that verdict, not this rank's upload below.  A rank whose upload fails
+    // returns its error, keeps it pending, and holds no table until the next run (its context answers VGS_E_STATE); it does not send its
+    // band a second time into headers-only peers.
+    t->band_valid = true;
+    // The halo table: the owners' band records first; a boundary record of the run adds a code that no band record names (a voxel whose
+    // cube crosses the border lies in the band, so these are voxels beyond it that the graph's rows reach).  One entry per code.
+    std::vector<uint64_t> hcode;
+    std::vector<int32_t> hlab;
+    for (int r = 0; r < c.world; ++r) {
+      if (r == c.rank) continue;
+      for (size_t i = 2; i < gathered[(size_t)r].size(); ++i) { hcode.push_back(gathered[(size_t)r][i].code); hlab.push_back(gathered[(size_t)r][i].label); }
+    }
+    std::vector<uint64_t> named(hcode);
+    std::sort(named.begin(), named.end());
+    if (t->run_rec.size() == (size_t)c.world) {
+      std::vector<std::pair<uint64_t, int32_t>> extra;
+      for (int r = 0; r < c.world; ++r) {
+        if (r == c.rank) continue;
+        const RankRecords& R = t->run_rec[(size_t)r];
+        const std::vector<int32_t>& ur = t->run_uroot[(size_t)r];
+        const std::vector<int32_t>& ul = t->run_ulabel[(size_t)r];
+        for (size_t k = 0; k < R.code.size(); ++k) {
+          if (std::binary_search(named.begin(), named.end(), R.code[k])) continue;
+          extra.emplace_back(R.code[k], ul[(size_t)(std::lower_bound(ur.begin(), ur.end(), R.root[k]) - ur.begin())]);
+        }
+      }
+      std::stable_sort(extra.begin(), extra.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+      for (size_t k = 0; k < extra.size(); ++k)
+        if (k == 0 || extra[k].first != extra[k - 1].first) { hcode.push_back(extra[k].first); hlab.push_back(extra[k].second); }   // (the lowest rank's record of a code)
+    }
+    const uint64_t no_code = 0;
+    const int32_t no_lab = 0;
+    TRY(behind_collective(t, vgs_set_refine_halo_labels(t->ctx, hcode.empty() ? &no_code : hcode.data(), hlab.empty() ? &no_lab : hlab.data(), (int64_t)hcode.size()),
+                          "vgs_set_refine_halo_labels"));
+  }
+  sw.lap(VGS_TILES_R_TABLE);
+  if (verdict != VGS_OK) return verdict;
+  int64_t cnt[5] = {0, 0, 0, 0, 0};
+  TRY(behind_collective(t, vgs_refine_own_point_labels(t->ctx, &rp, cnt), "vgs_refine_own_point_labels"));
+  sw.lap(VGS_TILES_R_REFINE);
+  sw.total(VGS_TILES_R_TOTAL, t->rtimes);
+  if (counts) std::copy(cnt, cnt + 5, counts);
+  t->r_band = (int64_t)payload.size() - 2; t->r_bytes = (int64_t)(payload.size() * sizeof(BandRec));
+  t->rf_valid = true;
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_refined_labels(vgs_tiles* t, int32_t* labels) {
+  if (!t || (!labels && t->n_own > 0)) return VGS_E_ARG;
+  if (!t->ran || !t->rf_valid)
+    return tfail(t, VGS_E_STATE, "vgs_tiles_get_refined_labels: no refinement since the last run or the last vgs_tiles_set_points (vgs_tiles_refine_point_labels first)");
+  const int32_t* dev = nullptr;
+  TCTX(vgs_get_refined_labels_device(t->ctx, &dev));
+  // the own range only: the rest of the context's cloud belongs to other ranks (the refine call has waited for its kernels)
+  if (t->n_own > 0) {
+    hipError_t e = hipSetDevice(t->P.device);
+    if (e == hipSuccess) e = hipMemcpy(labels, dev + t->own_first, (size_t)t->n_own * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return tfail(t, VGS_E_HIP, std::string("vgs_tiles_get_refined_labels: ") + hipGetErrorString(e));
+  }
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_refine_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::rtimes, ms, n); }
+
+vgs_status vgs_tiles_get_refine_payload(vgs_tiles* t, int64_t* band_records, int64_t* bytes_sent) {
+  if (!t) return VGS_E_ARG;
+  if (band_records) *band_records = t->r_band;
+  if (bytes_sent) *bytes_sent = t->r_bytes;
   return VGS_OK;
 }
 

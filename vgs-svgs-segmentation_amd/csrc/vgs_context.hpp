@@ -332,6 +332,15 @@ struct vgs_ctx {
   DevBuf<uint32_t> rf_batches, rf_start, rf_ids, rf_cnt, rf_nall;
   DevBuf<uint64_t> rf_rows, rf_counts;
   bool rf_valid = false;
+  // tile contexts (vgs_set_refine_halo_labels / vgs_get_own_band_labels / vgs_refine_own_point_labels): the global label of every voxel this
+  // rank does not own (RF_UNKNOWN without a record) -- a table of the refinement's own, beside sg_halo -- and its (code, label) upload;
+  // per voxel the effective label and the mask (bit 0 refinable, bit 1 owned); the band records (code, label) of the owned used voxels
+  // near a border line, rf_band_n of them (-1: not computed)
+  DevBuf<int32_t> rf_halo, rf_hlab, rf_eff, rf_blab;
+  DevBuf<uint64_t> rf_hcode, rf_bcode;
+  DevBuf<uint8_t> rf_mask;
+  bool rf_halo_valid = false;
+  int64_t rf_band_n = -1;
   DevBuf<uint64_t> counters;  // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 
@@ -449,6 +458,12 @@ vgs_status sd_own_anchor(vgs_ctx* c, int64_t K, const SdPrep& P);
 // a tile context (the tiled driver, include/vgs_tiles.h) holds only part of its segments: the per-segment getters of one context refuse it
 static inline bool vgs_is_tile(const vgs_ctx* c) { return c->have_region || c->n_own >= 0; }
 #ifdef __HIPCC__
+// position of the voxel with code q in vox_code (sorted, descending); V when the context does not hold it
+__device__ __forceinline__ int64_t vgs_find_voxel(const uint64_t* __restrict__ vox_code, int64_t V, uint64_t q) {
+  int64_t lo = 0, hi = V;
+  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (vox_code[mid] > q) lo = mid + 1; else hi = mid; }
+  return (lo < V && vox_code[lo] == q) ? lo : V;
+}
 // The walk of a chunk workgroup (blockIdx.x) from chunk to segment to nodes, one copy for segdesc.hip, segbox.hip and segfield.hip: the
 // segment k of the chunk, its virtual range [a, b) and its m nodes staged in s_vp (virtual start of each node) and s_dl (sorted position -
 // virtual position, mod 2^32), two LDS arrays of SD_CHUNK words.  False, with nothing staged, for a workgroup past the real number of
@@ -517,7 +532,11 @@ vgs_status vgs_clusters_on_device(vgs_ctx* c);   // clusters.hip
 vgs_status vgs_segdesc_on_device(vgs_ctx* c);    // segdesc.hip
 vgs_status vgs_segbox_on_device(vgs_ctx* c, int frame);   // segbox.hip
 vgs_status vgs_seggraph_on_device(vgs_ctx* c);   // seggraph.hip
+// tile contexts: halo[v] = label[k] for the voxel v of code[k] that this context holds and does not own, queued on the context's stream
+// (code, label: n entries in HBM; halo: V entries).  One kernel for the graph's table and the refinement's (seggraph.hip)
+vgs_status vgs_halo_find(vgs_ctx* c, const uint64_t* code_dev, const int32_t* label_dev, int64_t n, int32_t* halo_dev);
 vgs_status vgs_refine_on_device(vgs_ctx* c, const vgs_refine_params& rp, int64_t* counts4);   // refine.hip
+vgs_status vgs_refine_own_on_device(vgs_ctx* c, const vgs_refine_params& rp, int64_t* counts5);   // refine.hip, tile contexts
 vgs_status vgs_stage_vccs(vgs_ctx* c);
 vgs_status vgs_stage_svgs_group(vgs_ctx* c);
 vgs_status vgs_stage_svgs_neighbours(vgs_ctx* c);

@@ -29,6 +29,9 @@ G_NAMES = ("halo", "own", "exchange", "fold", "total")          # vgs_tiles_get_
 B_NAMES = ("extents", "exchange", "fold", "finish", "total")    # vgs_tiles_get_box_times
 F_NAMES = ("own", "exchange", "fold", "finish", "total")        # vgs_tiles_get_field_times
 C_NAMES = ("own", "exchange", "tables", "total")                # vgs_tiles_get_compare_times
+R_NAMES = ("band", "exchange", "table", "refine", "total")      # vgs_tiles_get_refine_times
+# vgs_tiles_refine_point_labels' counts, all the rank's share
+REFINE_COUNTS = ("working_nodes", "points_examined", "points_changed", "points_filled", "points_beyond_strip")
 # per (record / row, channel): (field, dtype) of vgs_get_own_segment_field_moments and vgs_tiles_fold_field_moments, in their argument order
 FIELD_MOMENT_FIELDS = (("n_valid", np.int64), ("anchor", np.float64), ("s1", np.float64), ("s2", np.float64), ("vmin", np.float32), ("vmax", np.float32))
 # per record / row: (field, dtype, values) of vgs_get_own_segment_moments and vgs_tiles_fold_moments, in their argument order
@@ -120,6 +123,14 @@ def lib():
         L.vgs_tiles_get_compare_times.argtypes = [P, P, C.c_int32]
         L.vgs_tiles_get_compare_payload.restype = C.c_int
         L.vgs_tiles_get_compare_payload.argtypes = [P, P, P]
+        L.vgs_tiles_refine_point_labels.restype = C.c_int
+        L.vgs_tiles_refine_point_labels.argtypes = [P, C.POINTER(_lib.VgsRefineParams), P]
+        L.vgs_tiles_get_refined_labels.restype = C.c_int
+        L.vgs_tiles_get_refined_labels.argtypes = [P, P]
+        L.vgs_tiles_get_refine_times.restype = C.c_int
+        L.vgs_tiles_get_refine_times.argtypes = [P, P, C.c_int32]
+        L.vgs_tiles_get_refine_payload.restype = C.c_int
+        L.vgs_tiles_get_refine_payload.argtypes = [P, P, P]
         L.vgs_tiles_fold_field_moments.restype = C.c_int
         L.vgs_tiles_fold_field_moments.argtypes = [C.c_int, P, P, C.c_int32, P, P, P, P, P, P, C.c_int64, P, P, P, P, P, P]
         L.vgs_tiles_fold_class_counts.restype = C.c_int
@@ -584,6 +595,40 @@ class NativeTiles:
         out = {name: a[:nc.value] for name, a in out.items()}
         out["n_unannotated"] = int(nu.value)
         return out
+
+    def refine_labels(self, patch_radius=None, switch_ratio=None, fill=True):
+        """COLLECTIVE on every call (every rank makes it after run(), with the same parameters): point-level label refinement over all
+        ranks -- the rule of Engine.refine_labels() on the whole scene, every point evaluated by the rank that loaded it
+        (include/vgs_tiles.h, vgs_tiles_refine_point_labels).  None: the context's default (patch_radius = voxel_size, switch_ratio =
+        0.25).  A new output next to point_labels(), read with refined_labels(); returns this rank's share of the counts
+        (REFINE_COUNTS), which add over the ranks."""
+        rp = _lib.VgsRefineParams()
+        st = _lib.lib().vgs_refine_params_default(self._ctx(), C.byref(rp))
+        if st != 0:
+            raise VgsError(st, "vgs_refine_params_default")
+        if patch_radius is not None:
+            rp.patch_radius = float(patch_radius)
+        if switch_ratio is not None:
+            rp.switch_ratio = float(switch_ratio)
+        rp.fill = 1 if fill else 0
+        cnt = np.zeros(5, dtype=np.int64)
+        self._ck(self._L.vgs_tiles_refine_point_labels(self._h, C.byref(rp), _vp(cnt)))
+        return {name: int(v) for name, v in zip(REFINE_COUNTS, cnt)}
+
+    def refined_labels(self):
+        """the labels of the last refine_labels(), one int32 per point of this rank's set_points() (local, no collective); VgsError
+        (VGS_E_STATE) without a refine since the last run() or set_points()"""
+        out = np.zeros(max(self.n, 1), dtype=np.int32)
+        self._ck(self._L.vgs_tiles_get_refined_labels(self._h, _vp(out)))
+        return out[:self.n]
+
+    def refine_times(self):
+        """the last refine_labels()'s phases on this rank, milliseconds (R_NAMES)"""
+        return self._times(self._L.vgs_tiles_get_refine_times, R_NAMES)
+
+    def refine_payload(self):
+        """the last refine_labels()'s payload on this rank: band records it sent (0 after the first call of a run), bytes sent"""
+        return self._payload(self._L.vgs_tiles_get_refine_payload, ("band_records", "bytes_sent"))
 
     def _kept(self):
         """kept_global of the last run (0 before one); local"""
