@@ -8,7 +8,8 @@ The oracle does not depend on how the tiled and the single engine number or cut 
 the tiled global label of its points (all points of a voxel must agree); the restatement runs with those labels.
   * scenes: the floor-and-wall scene of label_refine_ref split by y at 2.06 (the seam crosses the tile border), scenes.tiled_urban_scene
     in the 2x1 and 2x2 layouts and 2x2 far from the origin; fill on and off everywhere, switch_ratio 0 and 1 and patch_radius 0 on the
-    wall; preconditions from the plain engine's outputs, so that no case passes vacuously;
+    wall; preconditions from the plain engine's outputs, so that no case passes vacuously; a voxel of 5 000 points on the tile border,
+    so that each rank's share of one node spans several batches;
   * protocol: one all_gather_varlen per call, header + 16 bytes per band record on the first call and the header alone afterwards, the
     same bytes from call to call and from run to run, no side effect on labels, descriptors, graph and boxes in either order;
   * one rank equals a plain engine byte for byte; failures; points handed to the wrong rank; the front end."""
@@ -21,7 +22,7 @@ import numpy as np
 import pytest
 
 import label_refine_ref as LR
-from label_refine_scenes import WALL
+from label_refine_scenes import SPLIT5, WALL, big_boundary_voxel
 from test_gpu_tiles_segdesc import _parts, _pitch, _ranks, _same
 from test_gpu_tiles_segfields import LAYOUTS
 
@@ -32,6 +33,8 @@ EXE = os.path.join(ROOT, "examples", "vgs_tiles_run")
 N_PER = 60_000          # points per rank of the urban layouts: the restatement is a Python loop over the voxels
 HEADER = 32             # bytes of the refine payload's header: two 16-byte entries
 WALL_BORDER = 2.06      # the tile border of the wall scene, in y
+BIG_BORDER = 0.25       # the tile border through the voxel of 5 000 points (y in [0.2, 0.3]) of big_boundary_voxel
+RF_BATCH = 256          # points per work item (csrc/refine.hip)
 # (patch_radius, switch_ratio, fill); None = the context's default
 PARAMS = {"default": (None, None, True), "nofill": (None, None, False), "sr0": (None, 0.0, True), "sr1": (None, 1.0, True), "pr0": (0.0, None, True)}
 SCENES = {"wall": tuple(PARAMS), "2x1": ("default", "nofill"), "2x2": ("default", "nofill"), "2x2_far": ("default", "nofill")}
@@ -210,6 +213,47 @@ def test_the_scenes_cover_the_new_ground(gpu, name):
     rank_of = np.repeat(np.arange(len(parts)), [p.shape[0] for p in parts])
     owner = _owner(inp["centers"], tiles, pitch, center)
     print(name, preconditions(inp, rank_of, owner, _restated(gpu, name, "default")[0], name))
+
+
+def test_a_border_voxel_of_5000_points_split_between_two_ranks(gpu):
+    """label_refine_scenes.big_boundary_voxel laid out as the wall scene is, the tile border at y = 0.25 through the voxel of 5 000 points:
+    each rank's share of it spans several batches, the last one partial, and in every batch only some lanes hold a point of the rank's own
+    load.  (The other scenes give no voxel more than RF_BATCH points.)"""
+    kw = dict(SPLIT5)
+    xyz = big_boundary_voxel()
+    low = xyz[:, 1].astype(np.float64) < BIG_BORDER
+    parts = [xyz[low], xyz[~low]]                                     # rank 0's points first: the chained grid's order
+    which = ("default", "nofill")
+
+    def body(r, t, p):
+        t.set_points(p)
+        t.run()
+        labels, _ = t.point_labels()
+        return labels, {w: (t.refine_labels(*PARAMS[w]), t.refined_labels().copy()) for w in which}
+    out = _ranks(gpu, (1, 2), 4.0, parts, body, center=(0.0, BIG_BORDER), params=gpu.default_params(2, **kw))
+    for r, o in enumerate(out):
+        assert not isinstance(o, Exception), (r, o)
+    inp = _inputs(gpu, parts, kw, np.concatenate([o[0] for o in out]))
+    # from the plain engine's outputs: the voxel holds 5 000 points, is a working node, and each rank loaded more than a batch of them
+    pv = inp["point_voxel"]
+    npts = np.bincount(pv[pv >= 0], minlength=inp["attr"]["used"].shape[0])
+    big = int(np.argmax(npts))
+    assert npts[big] == 5000 and npts[big] > 2 * RF_BATCH and npts[big] % RF_BATCH != 0
+    assert LR.working_nodes(inp["attr"], inp["kept"], inp["adjacency"], False)[big]
+    rank_of = np.repeat(np.arange(2), [p.shape[0] for p in parts])
+    share = np.bincount(rank_of[pv == big], minlength=2)
+    print(share)
+    assert (share > RF_BATCH).all(), share
+    for w in which:
+        ref, rc = _ref(inp, w)
+        got = np.concatenate([o[1][w][1] for o in out])
+        counts = [o[1][w][0] for o in out]
+        print(w, counts, rc)
+        bad = np.flatnonzero(got != ref)
+        assert bad.size == 0, (w, bad.size, bad[:8], got[bad[:8]], ref[bad[:8]], pv[bad[:8]])
+        for key in ("working_nodes", "points_examined", "points_changed", "points_filled"):
+            assert sum(c[key] for c in counts) == rc[key], (w, key, counts, rc)
+        assert all(c["points_beyond_strip"] == 0 for c in counts), (w, counts)
 
 
 @pytest.mark.parametrize("name", list(SCENES))
