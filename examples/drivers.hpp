@@ -41,10 +41,22 @@ struct DriverRefine {
   float switch_ratio = 0.25f;
   bool fill = true;
   std::vector<int32_t> labels;
+  // the tables of the REFINED labels, beside the ones that describe the voxel labels: getLabelDescriptors / getLabelBoxes(box_frame) /
+  // compareClusterLabels(truth, labels) when wanted (truth: n int32, not null)
+  bool want_descriptors = false, want_boxes = false;
+  int box_frame = VGS_BOX_PRINCIPAL;
+  const std::vector<int32_t>* truth = nullptr;
+  std::vector<pcl::ClusterDescriptor> descriptors;
+  std::vector<pcl::ClusterBox> boxes;
+  pcl::ClusterLabelComparison matches;
 };
 template <typename S>
 inline void driverRefine(S& structure, DriverRefine& r, std::vector<std::vector<int>>& clusters_points_idx) {
   r.labels = structure.refineClusterLabels(r.patch_radius, r.switch_ratio, r.fill);
+  const int64_t n = (int64_t)r.labels.size();
+  if (r.want_descriptors) r.descriptors = structure.getLabelDescriptors(r.labels.data(), n);
+  if (r.want_boxes) r.boxes = structure.getLabelBoxes(r.labels.data(), n, r.box_frame);
+  if (r.truth) r.matches = structure.compareClusterLabels(r.truth->data(), (int64_t)r.truth->size(), r.labels.data());
   for (auto& c : clusters_points_idx) c.clear();
   for (size_t i = 0; i < r.labels.size(); ++i)
     if (r.labels[i] >= 0 && (size_t)r.labels[i] < clusters_points_idx.size()) clusters_points_idx[(size_t)r.labels[i]].push_back((int)i);

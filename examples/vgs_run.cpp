@@ -8,6 +8,8 @@
 //                  [--segment-fields <file.csv> --fields a[,b,...]] [--segment-classes <file.csv> --class-field <name> --classes <C>]
 //                  [--segment-matches <file.csv> --truth-field <name> [--truth-matches <file.csv>]]
 //                  [--refine [--patch-radius <r>] [--switch-ratio <s>] [--no-fill]]
+//                  [--refined-segments <file.csv>] [--refined-segment-boxes <file.csv>]
+//                  [--refined-matches <file.csv> --truth-field <name> [--refined-truth-matches <file.csv>]]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
 // --segments writes one CSV row per kept cluster (getClusterDescriptors, row i = cluster i of the output): label, n_points, n_nodes,
@@ -33,6 +35,11 @@
 // planar patch, the points of unused voxels and dropped clusters are filled unless --no-fill): clusters in label order, points in
 // ascending index; every CSV keeps describing the voxel labels.  --patch-radius (default: the voxel size, the supervoxel size for SVGS),
 // --switch-ratio in [0, 1] (default 0.25) and --no-fill need --refine.
+// --refined-segments, --refined-segment-boxes (which honours --box-frame) and --refined-matches (which reads the --truth-field that
+// --segment-matches reads; --refined-truth-matches beside it) write the same CSVs -- same writers, same columns, same exact round trip --
+// over the REFINED labels (getLabelDescriptors, getLabelBoxes, compareClusterLabels with the labels): the tables of the result the PCD
+// holds.  The flags above keep writing the voxel-label tables, and a run may write both.  --refined-matches adds the stdout lines
+// "refined-matches" and "refined-scores".  Each needs --refine (a usage error, status 2, without it).
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
 #include <algorithm>
 #include <cmath>
@@ -59,11 +66,13 @@ int main(int argc, char** argv) {
                  "[--segment-graph file.csv] [--segment-adjacency file.txt] [--segment-boxes file.csv [--box-frame principal|upright]] "
                  "[--segment-fields file.csv --fields a[,b,...]] [--segment-classes file.csv --class-field name --classes C] "
                  "[--segment-matches file.csv --truth-field name [--truth-matches file.csv]] "
-                 "[--refine [--patch-radius r] [--switch-ratio s] [--no-fill]]\n",
+                 "[--refine [--patch-radius r] [--switch-ratio s] [--no-fill]] [--refined-segments file.csv] [--refined-segment-boxes file.csv] "
+                 "[--refined-matches file.csv --truth-field name [--refined-truth-matches file.csv]]\n",
                  argv[0]);
     return 2;
   }
   std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file, boxes_file, fields_file, classes_file, class_field, matches_file, truth_field, truth_file;
+  std::string r_segments_file, r_boxes_file, r_matches_file, r_truth_file;
   std::vector<std::string> field_names;
   bool have_fields = false, have_classes = false;
   long n_classes = 0;
@@ -109,6 +118,10 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--segment-matches") && a + 1 < argc) matches_file = argv[++a];
     else if (!std::strcmp(argv[a], "--truth-field") && a + 1 < argc) truth_field = argv[++a];
     else if (!std::strcmp(argv[a], "--truth-matches") && a + 1 < argc) truth_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-segments") && a + 1 < argc) r_segments_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-segment-boxes") && a + 1 < argc) r_boxes_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-matches") && a + 1 < argc) r_matches_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-truth-matches") && a + 1 < argc) r_truth_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refine")) refine.on = true;
     else if (!std::strcmp(argv[a], "--no-fill")) { refine.fill = false; refine_opts = true; }
     else if ((!std::strcmp(argv[a], "--patch-radius") || !std::strcmp(argv[a], "--switch-ratio")) && a + 1 < argc) {
@@ -132,7 +145,16 @@ int main(int argc, char** argv) {
   if (fields_file.empty() && have_fields) { std::fprintf(stderr, "--fields needs --segment-fields <file.csv>\n"); return 2; }
   if (classes_file.empty() && (have_classes || !class_field.empty())) { std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv>\n"); return 2; }
   if (!matches_file.empty() && truth_field.empty()) { std::fprintf(stderr, "--segment-matches needs --truth-field <name>\n"); return 2; }
-  if (matches_file.empty() && (!truth_field.empty() || !truth_file.empty())) { std::fprintf(stderr, "--truth-field / --truth-matches need --segment-matches <file.csv>\n"); return 2; }
+  if (!refine.on && !(r_segments_file.empty() && r_boxes_file.empty() && r_matches_file.empty() && r_truth_file.empty())) {
+    std::fprintf(stderr, "--refined-segments / --refined-segment-boxes / --refined-matches / --refined-truth-matches need --refine\n");
+    return 2;
+  }
+  if (!r_matches_file.empty() && truth_field.empty()) { std::fprintf(stderr, "--refined-matches needs --truth-field <name>\n"); return 2; }
+  if (r_matches_file.empty() && !r_truth_file.empty()) { std::fprintf(stderr, "--refined-truth-matches needs --refined-matches <file.csv>\n"); return 2; }
+  if (matches_file.empty() && ((!truth_field.empty() && r_matches_file.empty()) || !truth_file.empty())) {
+    std::fprintf(stderr, "--truth-field / --truth-matches need --segment-matches <file.csv> (--truth-field serves --refined-matches too)\n");
+    return 2;
+  }
   const std::vector<std::string> task = inputTaskTxtFile(argv[1]);
   if (task.size() < 51) { std::fprintf(stderr, "%s: not a task file (%zu lines)\n", argv[1], task.size()); return 2; }
   const int method = std::atoi(task[24].c_str());
@@ -146,13 +168,14 @@ int main(int argc, char** argv) {
   }
   PCXYZPtr cloud(new PCXYZ);
   const bool ply = in_file.size() > 4 && in_file.substr(in_file.size() - 4) == ".ply";
-  if (ply && !(fields_file.empty() && classes_file.empty() && matches_file.empty())) {   // (a usage error: nothing has been loaded yet)
-    std::fprintf(stderr, "--segment-fields / --segment-classes / --segment-matches read their fields from a PCD input, not from %s\n", in_file.c_str());
+  const bool want_truth = !(matches_file.empty() && r_matches_file.empty());
+  if (ply && !(fields_file.empty() && classes_file.empty() && !want_truth)) {   // (a usage error: nothing has been loaded yet)
+    std::fprintf(stderr, "--segment-fields / --segment-classes / --segment-matches / --refined-matches read their fields from a PCD input, not from %s\n", in_file.c_str());
     return 2;
   }
   if ((ply ? inputPointCloudData2(in_file, cloud) : inputPointCloudData(in_file, cloud)) != 0) return 1;
   DriverFields fields;
-  DriverFields* want_fields = (fields_file.empty() && classes_file.empty() && matches_file.empty()) ? nullptr : &fields;
+  DriverFields* want_fields = (fields_file.empty() && classes_file.empty() && !want_truth) ? nullptr : &fields;
   if (want_fields) {   // the attributes ride in the input PCD, one row per point of the cloud
     std::string err;
     if (!fields_file.empty()) {
@@ -166,11 +189,15 @@ int main(int argc, char** argv) {
       for (size_t i = 0; i < v.size(); ++i) fields.classes[i] = (v[i] >= -2147483648.0f && v[i] < 2147483648.0f) ? (int32_t)v[i] : -1;
       fields.n_classes = (int)n_classes;
     }
-    if (!matches_file.empty()) {
+    if (want_truth) {
       if (vgs_io::read_pcd_field_int32(in_file, truth_field, fields.truth, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
-      fields.have_truth = true;
+      fields.have_truth = !matches_file.empty();   // (the voxel labels are scored only when their table is asked for)
+      if (!r_matches_file.empty()) refine.truth = &fields.truth;
     }
   }
+  refine.want_descriptors = !r_segments_file.empty();
+  refine.want_boxes = !r_boxes_file.empty();
+  refine.box_frame = box_frame;
   std::vector<std::vector<int>> clusters;
   DriverSummary sum;
   std::vector<pcl::ClusterDescriptor> desc;
@@ -201,6 +228,10 @@ int main(int argc, char** argv) {
   if (!classes_file.empty() && writeClassHistCsv(classes_file, fields.n_classes, fields.hist) != 0) { std::fprintf(stderr, "cannot write %s\n", classes_file.c_str()); return 1; }
   if (!matches_file.empty() && writeSegmentMatchesCsv(matches_file, fields.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", matches_file.c_str()); return 1; }
   if (!truth_file.empty() && writeTruthMatchesCsv(truth_file, fields.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", truth_file.c_str()); return 1; }
+  if (!r_segments_file.empty() && writeSegmentsCsv(r_segments_file, refine.descriptors) != 0) { std::fprintf(stderr, "cannot write %s\n", r_segments_file.c_str()); return 1; }
+  if (!r_boxes_file.empty() && writeBoxesCsv(r_boxes_file, refine.boxes) != 0) { std::fprintf(stderr, "cannot write %s\n", r_boxes_file.c_str()); return 1; }
+  if (!r_matches_file.empty() && writeSegmentMatchesCsv(r_matches_file, refine.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", r_matches_file.c_str()); return 1; }
+  if (!r_truth_file.empty() && writeTruthMatchesCsv(r_truth_file, refine.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", r_truth_file.c_str()); return 1; }
   if (!adjacency_file.empty() && writeAdjacency(adjacency_file, graph.adjacency) != 0) {
     std::fprintf(stderr, "cannot write %s\n", adjacency_file.c_str());
     return 1;
@@ -211,6 +242,12 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 12; ++i) std::printf(" %lld", (long long)fields.matches.summary[i]);
     const pcl::ClusterLabelScores sc = pcl::clusterLabelScores(fields.matches, 0.5);
     std::printf("\nscores %lld %.17g %.17g %.17g %.17g %.17g %.17g\n", (long long)sc.matched, sc.precision, sc.recall, sc.f1, sc.purity, sc.completeness, sc.ari);
+  }
+  if (!r_matches_file.empty()) {
+    std::printf("refined-matches");
+    for (int i = 0; i < 12; ++i) std::printf(" %lld", (long long)refine.matches.summary[i]);
+    const pcl::ClusterLabelScores sc = pcl::clusterLabelScores(refine.matches, 0.5);
+    std::printf("\nrefined-scores %lld %.17g %.17g %.17g %.17g %.17g %.17g\n", (long long)sc.matched, sc.precision, sc.recall, sc.f1, sc.purity, sc.completeness, sc.ari);
   }
   return 0;
 }

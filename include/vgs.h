@@ -500,6 +500,46 @@ vgs_status vgs_label_comparison_from_cells(vgs_ctx* ctx, int64_t K, int64_t n_in
                                            const int64_t* cell_n, int64_t n_unannotated, int64_t* n_cells, int64_t* n_refs,
                                            int64_t* summary /* 12 */);
 
+/* Describe and score ANY per-point labelling of the context's cloud (no reference counterpart).  The per-segment tables above describe the
+ * node labels -- a labelling that is constant on a voxel or supervoxel; these entry points take one int32 per input point that the CALLER
+ * supplies: the refined labels (vgs_get_refined_labels), ground-truth instances, anything made from the engine's output.
+ *   labels  n int32 in input order; n must equal counts[VGS_N_POINTS].  Label l belongs to row l for 0 <= l < K; l < 0 means no segment.
+ *           A label >= K is VGS_E_ARG, the message naming the first offending index and its value (found on the device in one pass,
+ *           before anything is built).  0 <= K <= 2^31 - 1; K is the caller's, not counts[VGS_N_KEPT].
+ * The host variants upload once into a buffer of the context; the _device variants read HBM (the context's device; complete before the
+ * call) in place.  Outputs are caller-allocated host arrays of K rows and any pointer may be NULL; K = 0 writes nothing.
+ * vgs_point_label_descriptors: the fields of vgs_get_segment_descriptors.  Row k covers the points i with labels[i] == k that are in the
+ * octree -- the finite points, for SVGS those of a supervoxel -- and *n_skipped (may be NULL) counts the labelled points that are not: they
+ * contribute to no row.  n_nodes is the number of distinct nodes (voxels / supervoxels) among the row's points.  A label no point carries:
+ * n_points 0, n_nodes 0, bbox6 = (+inf, +inf, +inf, -inf, -inf, -inf), zero centroid, covariance and eigenvalues, identity eigenvectors,
+ * the eigen features of zeros.
+ * vgs_point_label_boxes: the fields and the frame rule of vgs_get_segment_boxes, the frames made from the descriptor rows of THIS
+ * labelling (computed first, by the call); a label no point carries gives lo = hi = half = 0 and center3 = its centroid3.
+ * Both run the device code of the node tables -- the same chunk sums, folds, per-segment algebra and frame rule -- over the points sorted
+ * by label (csrc/pointseg.hip): no float atomics, every sum of a fixed shape, bit-identical from call to call and engine to engine; and
+ * handed the context's own point labels with K = counts[VGS_N_KEPT] they return the tables of vgs_get_segment_descriptors and
+ * vgs_get_segment_boxes byte for byte.  Computed on every call, nothing cached; scratch of their own, about 16 bytes per finite point plus
+ * the sort's storage.  No side effects: labels, refined labels, every cached table and the last comparison stay as they are.
+ * vgs_compare_point_labels: the tables of vgs_compare_labels with L[i] = seg_labels[i] if it lies in 0 .. K-1 and -1 if it is negative.
+ * Purely index-wise: a non-finite point takes part with the label the caller gave it.  Like vgs_compare_labels it makes its tables the
+ * context's last comparison: vgs_get_label_comparison[_device] serve them, K rows in the segment table.
+ * VGS_E_STATE before the context is segmented and for a tile context; VGS_E_ARG for a wrong n, a NULL labelling with n > 0, K out of
+ * range, a label >= K and a bad frame. */
+vgs_status vgs_point_label_descriptors(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_skipped, int64_t* n_points,
+                                       int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3, double* evecs9,
+                                       float* eigen8);
+vgs_status vgs_point_label_descriptors_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_skipped,
+                                              int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3,
+                                              double* evecs9, float* eigen8);
+vgs_status vgs_point_label_boxes(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, int32_t frame, double* center3, double* half3,
+                                 double* frame9, double* lo3, double* hi3);
+vgs_status vgs_point_label_boxes_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t n, int64_t K, int32_t frame, double* center3,
+                                        double* half3, double* frame9, double* lo3, double* hi3);
+vgs_status vgs_compare_point_labels(vgs_ctx* ctx, const int32_t* seg_labels_host, int64_t K, const int32_t* ref_host, int64_t n, int64_t* n_cells,
+                                    int64_t* n_refs, int64_t* summary /* 12 */);
+vgs_status vgs_compare_point_labels_device(vgs_ctx* ctx, const int32_t* seg_labels_dev, int64_t K, const int32_t* ref_dev, int64_t n,
+                                           int64_t* n_cells, int64_t* n_refs, int64_t* summary /* 12 */);
+
 /* Point-level label refinement at segment boundaries (no reference counterpart).  A point's label (vgs_get_point_labels) is the label of
  * its node -- a voxel for VGS, a supervoxel for SVGS -- so segment boundaries are staircases of whole nodes, and the points of voxels with
  * at most points_min points and of clusters with at most voxels_min voxels are -1 however close a kept segment lies.  This is a NEW output

@@ -109,15 +109,22 @@ struct ClusterDescriptor {
 
 namespace vgs_detail {
 // one row per kept cluster, in label order -- the order of getClusterIdx (cluster k of either order holds the points labelled k)
-inline std::vector<ClusterDescriptor> cluster_descriptors(vgs_ctx* c, int64_t k) {
+// labels != nullptr: the rows of that per-point labelling (n labels in 0 .. k-1 or negative) instead, as vgs_point_label_descriptors
+// defines them; *n_skipped = its labelled points outside the octree
+inline std::vector<ClusterDescriptor> cluster_descriptors(vgs_ctx* c, int64_t k, const int32_t* labels = nullptr, int64_t n = 0,
+                                                          int64_t* n_skipped = nullptr) {
   std::vector<ClusterDescriptor> out((size_t)k);
-  if (k == 0) return out;
-  std::vector<int64_t> np((size_t)k);
-  std::vector<int32_t> nn((size_t)k);
-  std::vector<float> bb((size_t)k * 6), e8((size_t)k * 8);
-  std::vector<double> ce((size_t)k * 3), cv((size_t)k * 6), ev((size_t)k * 3), vv((size_t)k * 9);
-  check(c, vgs_get_segment_descriptors(c, np.data(), nn.data(), bb.data(), ce.data(), cv.data(), ev.data(), vv.data(), e8.data()),
-        "vgs_get_segment_descriptors");
+  if (k == 0 && !labels) return out;
+  std::vector<int64_t> np((size_t)k + 1);
+  std::vector<int32_t> nn((size_t)k + 1);
+  std::vector<float> bb((size_t)k * 6 + 1), e8((size_t)k * 8 + 1);
+  std::vector<double> ce((size_t)k * 3 + 1), cv((size_t)k * 6 + 1), ev((size_t)k * 3 + 1), vv((size_t)k * 9 + 1);
+  if (labels)   // (called for k = 0 too: the state and argument checks are the library's)
+    check(c, vgs_point_label_descriptors(c, labels, n, k, n_skipped, np.data(), nn.data(), bb.data(), ce.data(), cv.data(), ev.data(), vv.data(),
+                                         e8.data()), "vgs_point_label_descriptors");
+  else
+    check(c, vgs_get_segment_descriptors(c, np.data(), nn.data(), bb.data(), ce.data(), cv.data(), ev.data(), vv.data(), e8.data()),
+          "vgs_get_segment_descriptors");
   for (size_t i = 0; i < (size_t)k; ++i) {
     ClusterDescriptor& d = out[i];
     d.n_points = np[i]; d.n_nodes = nn[i];
@@ -140,11 +147,15 @@ struct ClusterBox {
 
 namespace vgs_detail {
 // one row per kept cluster, in label order -- the order of getClusterIdx
-inline std::vector<ClusterBox> cluster_boxes(vgs_ctx* c, int64_t k, int frame) {
+// labels != nullptr: the boxes of that per-point labelling instead, as vgs_point_label_boxes defines them
+inline std::vector<ClusterBox> cluster_boxes(vgs_ctx* c, int64_t k, int frame, const int32_t* labels = nullptr, int64_t n = 0) {
   std::vector<ClusterBox> out((size_t)k);
   std::vector<double> ce((size_t)k * 3 + 1), ha((size_t)k * 3 + 1), fr((size_t)k * 9 + 1), lo((size_t)k * 3 + 1), hi((size_t)k * 3 + 1);
   // (called for k = 0 too: the state and frame checks are the library's)
-  check(c, vgs_get_segment_boxes(c, (int32_t)frame, ce.data(), ha.data(), fr.data(), lo.data(), hi.data()), "vgs_get_segment_boxes");
+  if (labels)
+    check(c, vgs_point_label_boxes(c, labels, n, k, (int32_t)frame, ce.data(), ha.data(), fr.data(), lo.data(), hi.data()), "vgs_point_label_boxes");
+  else
+    check(c, vgs_get_segment_boxes(c, (int32_t)frame, ce.data(), ha.data(), fr.data(), lo.data(), hi.data()), "vgs_get_segment_boxes");
   for (size_t i = 0; i < (size_t)k; ++i) {
     ClusterBox& b = out[i];
     for (int a = 0; a < 3; ++a) { b.center[a] = ce[3 * i + a]; b.half[a] = ha[3 * i + a]; b.lo[a] = lo[3 * i + a]; b.hi[a] = hi[3 * i + a]; }
@@ -257,10 +268,12 @@ inline std::vector<int32_t> refined_labels(vgs_ctx* c, int64_t n, float patch_ra
   if (n > 0) check(c, vgs_get_refined_labels(c, out.data()), "vgs_get_refined_labels");
   return out;
 }
-inline ClusterLabelComparison cluster_label_comparison(vgs_ctx* c, int64_t k, const int32_t* ref, int64_t n) {
+// labels != nullptr: that per-point labelling (k rows) is scored instead of the clusters' own, as vgs_compare_point_labels defines it
+inline ClusterLabelComparison cluster_label_comparison(vgs_ctx* c, int64_t k, const int32_t* ref, int64_t n, const int32_t* labels = nullptr) {
   ClusterLabelComparison o;
   int64_t n_cells = 0, n_refs = 0;
-  check(c, vgs_compare_labels(c, ref, n, &n_cells, &n_refs, o.summary), "vgs_compare_labels");
+  if (labels) check(c, vgs_compare_point_labels(c, labels, k, ref, n, &n_cells, &n_refs, o.summary), "vgs_compare_point_labels");
+  else check(c, vgs_compare_labels(c, ref, n, &n_cells, &n_refs, o.summary), "vgs_compare_labels");
   const size_t nc = (size_t)n_cells, g = (size_t)n_refs, kk = (size_t)k;
   o.cell_seg.resize(nc); o.cell_ref.resize(nc); o.cell_n.resize(nc);
   o.ref_id.resize(g); o.ref_points.resize(g); o.ref_dropped.resize(g); o.ref_best_seg.resize(g); o.ref_best_n.resize(g); o.ref_best_iou.resize(g);
@@ -454,9 +467,22 @@ class VoxelBasedSegmentation {
   }
   // Extension (no VS line): the clusters against a reference labelling (n int32 in input order, negative = no annotation); row i of the
   // cluster table belongs to getClusterIdx()[i]; empty before drawColorMapofPointsinClusters
-  ClusterLabelComparison compareClusterLabels(const int32_t* ref, int64_t n) {
+  // labels != nullptr: that per-point labelling (n int32, the clusters' label range; refineClusterLabels()' result, say) is scored instead
+  ClusterLabelComparison compareClusterLabels(const int32_t* ref, int64_t n, const int32_t* labels = nullptr) {
     if (!drawn_) return {};
-    return vgs_detail::cluster_label_comparison(ctx(), count(VGS_N_KEPT), ref, n);
+    return vgs_detail::cluster_label_comparison(ctx(), count(VGS_N_KEPT), ref, n, labels);
+  }
+  // Extension (no VS line): the descriptors and boxes of a per-point labelling with the clusters' label range (n int32 in input order,
+  // negative = no cluster; vgs_point_label_descriptors / _boxes, include/vgs.h): row i covers the points labelled i; *n_skipped = the
+  // labelled points outside the octree.  Empty before drawColorMapofPointsinClusters
+  std::vector<ClusterDescriptor> getLabelDescriptors(const int32_t* labels, int64_t n, int64_t* n_skipped = nullptr) {
+    if (n_skipped) *n_skipped = 0;
+    if (!drawn_) return {};
+    return vgs_detail::cluster_descriptors(ctx(), count(VGS_N_KEPT), labels, n, n_skipped);
+  }
+  std::vector<ClusterBox> getLabelBoxes(const int32_t* labels, int64_t n, int frame = VGS_BOX_PRINCIPAL) {
+    if (!drawn_) return {};
+    return vgs_detail::cluster_boxes(ctx(), count(VGS_N_KEPT), frame, labels, n);
   }
 
   // Extension (no VS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
@@ -574,8 +600,19 @@ class SuperVoxelBasedSegmentation {
   }
   // Extension (no SS line): the clusters against a reference labelling (n int32 in input order, negative = no annotation); row i of the
   // cluster table belongs to getClusterIdx()[i]
-  ClusterLabelComparison compareClusterLabels(const int32_t* ref, int64_t n) {
-    return vgs_detail::cluster_label_comparison(ctx(), count(VGS_N_KEPT), ref, n);
+  // labels != nullptr: that per-point labelling (n int32, the clusters' label range; refineClusterLabels()' result, say) is scored instead
+  ClusterLabelComparison compareClusterLabels(const int32_t* ref, int64_t n, const int32_t* labels = nullptr) {
+    return vgs_detail::cluster_label_comparison(ctx(), count(VGS_N_KEPT), ref, n, labels);
+  }
+  // Extension (no SS line): the descriptors and boxes of a per-point labelling with the clusters' label range (n int32 in input order,
+  // negative = no cluster; vgs_point_label_descriptors / _boxes, include/vgs.h): row i covers the points labelled i; *n_skipped = the
+  // labelled points outside the octree
+  std::vector<ClusterDescriptor> getLabelDescriptors(const int32_t* labels, int64_t n, int64_t* n_skipped = nullptr) {
+    if (n_skipped) *n_skipped = 0;
+    return vgs_detail::cluster_descriptors(ctx(), count(VGS_N_KEPT), labels, n, n_skipped);
+  }
+  std::vector<ClusterBox> getLabelBoxes(const int32_t* labels, int64_t n, int frame = VGS_BOX_PRINCIPAL) {
+    return vgs_detail::cluster_boxes(ctx(), count(VGS_N_KEPT), frame, labels, n);
   }
   // Extension (no SS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
   // names getClusterIdx()[i].  patch_radius < 0: the default (the supervoxel size)

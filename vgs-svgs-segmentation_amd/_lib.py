@@ -122,6 +122,12 @@ SYMBOLS = [
     ("vgs_own_label_cells_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("vgs_get_own_label_cells", C.c_int, [_P, _P, _P, _P]),
     ("vgs_label_comparison_from_cells", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P]),
+    ("vgs_point_label_descriptors", C.c_int, [_P, _P, C.c_int64, C.c_int64] + [_P] * 9),
+    ("vgs_point_label_descriptors_device", C.c_int, [_P, _P, C.c_int64, C.c_int64] + [_P] * 9),
+    ("vgs_point_label_boxes", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
+    ("vgs_point_label_boxes_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
+    ("vgs_compare_point_labels", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
+    ("vgs_compare_point_labels_device", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("vgs_get_own_segment_field_moments", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_own_segment_field_moments_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_segment_field_stats_from_moments", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

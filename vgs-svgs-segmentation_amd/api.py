@@ -474,21 +474,65 @@ class Engine:
                       ("seg_annotated", np.int64, "segs"), ("seg_refs", np.int32, "segs"), ("seg_best_ref", np.int32, "segs"),
                       ("seg_best_n", np.int64, "segs"), ("seg_best_iou", np.float64, "segs"))
 
-    def compare_labels(self, ref):
+    def _labels_input(self, labels, K):
+        """(array kept alive, pointer, n, on the device?, K) of a caller's per-point labelling: _classes_input's rules, K None = the
+        engine's own kept count"""
+        labels, ptr, n, dev = self._classes_input(labels, self.params.device)
+        return labels, ptr, n, dev, (self.counts()["kept"] if K is None else int(K))
+
+    def describe_labels(self, labels, K=None):
+        """Descriptors of ANY per-point labelling of the cloud (include/vgs.h, vgs_point_label_descriptors): the dict of
+        segment_descriptors(), K rows, row k = the points with labels[i] == k that are in the octree (the finite ones), plus n_skipped, the
+        labelled points that are not.  `labels`: int32 of shape (N,) in input order, a numpy array or a torch tensor on the context's
+        device, which is read in place; negative = no segment, a label >= K is an error.  K None: counts()["kept"], the range of
+        point_labels() and refined_labels().  A label no point carries gives n_points 0 and a bbox6 of (+inf x3, -inf x3).  Computed on
+        the device on every call, nothing cached; handed point_labels() it returns segment_descriptors() byte for byte."""
+        labels, ptr, n, dev, K = self._labels_input(labels, K)
+        fn = self._L.vgs_point_label_descriptors_device if dev else self._L.vgs_point_label_descriptors
+        out = {name: np.zeros((max(K, 0), w) if w > 1 else max(K, 0), dtype=dt) for name, dt, w in self.DESCRIPTOR_FIELDS}
+        skipped = C.c_int64(0)
+        self._ck(fn(self._h, ptr, n, K, C.byref(skipped), *(_ptr(out[name]) for name, _, _ in self.DESCRIPTOR_FIELDS)))
+        out["n_skipped"] = int(skipped.value)
+        return out
+
+    def label_boxes(self, labels, frame="principal", K=None):
+        """Oriented boxes of ANY per-point labelling of the cloud (include/vgs.h, vgs_point_label_boxes): the dict of segment_boxes(), K
+        rows, in the frames that describe_labels()' rows of the same labelling give.  `labels`, K as describe_labels().  A label no point
+        carries gives lo = hi = half = 0 and center = its (zero) centroid."""
+        labels, ptr, n, dev, K = self._labels_input(labels, K)
+        fn = self._L.vgs_point_label_boxes_device if dev else self._L.vgs_point_label_boxes
+        out = {name: np.zeros((max(K, 0), w), dtype=dt) for name, dt, w in self.BOX_FIELDS}
+        self._ck(fn(self._h, ptr, n, K, self._box_frame(frame), *(_ptr(out[name]) for name, _, _ in self.BOX_FIELDS)))
+        return out
+
+    def compare_labels(self, ref, labels=None, K=None):
         """Score the segmentation against a labelling of the same points (include/vgs.h, vgs_compare_labels): the sparse contingency table
         between point_labels() and `ref`, the reference table and the segment table, as a dict of numpy arrays -- cell_seg, cell_ref, cell_n
         (one row per distinct (label, id) pair, ascending, the -1 row first), ref_id, ref_points, ref_dropped, ref_best_seg, ref_best_n,
         ref_best_iou (one row per distinct id, ascending), seg_annotated, seg_refs, seg_best_ref, seg_best_n, seg_best_iou (K rows) -- plus
         summary (int64[12]).  `ref`: int32 of shape (N,) in input order, a numpy array or a torch tensor on the context's device, which is
         read in place; a negative id marks a point without annotation.  Computed on the device; integer counts and single fp64 quotients,
-        bit-identical from call to call.  comparison_scores() turns the dict into precision, recall, F1, purity and the Rand index."""
-        K = self.counts()["kept"]
-        ref, ptr, n, dev = self._classes_input(ref, self.params.device)
-        fn = self._L.vgs_compare_labels_device if dev else self._L.vgs_compare_labels
+        bit-identical from call to call.  comparison_scores() turns the dict into precision, recall, F1, purity and the Rand index.
+        `labels` (include/vgs.h, vgs_compare_point_labels): score this per-point labelling instead of point_labels() -- refined_labels(),
+        say -- with K segment rows (None: counts()["kept"]); int32 of shape (N,), negative = dropped, a label >= K is an error; numpy or a
+        torch tensor on the context's device, as `ref` is (both of one kind)."""
         n_cells, n_refs = C.c_int64(0), C.c_int64(0)
         summary = np.zeros(12, np.int64)
-        self._ck(fn(self._h, ptr, n, C.byref(n_cells), C.byref(n_refs), _ptr(summary)))
-        rows = {"cells": n_cells.value, "refs": n_refs.value, "segs": K}
+        if labels is None:
+            K = self.counts()["kept"]
+            ref, ptr, n, dev = self._classes_input(ref, self.params.device)
+            fn = self._L.vgs_compare_labels_device if dev else self._L.vgs_compare_labels
+            self._ck(fn(self._h, ptr, n, C.byref(n_cells), C.byref(n_refs), _ptr(summary)))
+        else:
+            if self._is_torch(ref) != self._is_torch(labels):
+                raise ValueError("ref and labels must both be numpy arrays or both be torch tensors on the context's device")
+            ref, ptr, n, dev = self._classes_input(ref, self.params.device)
+            labels, lptr, ln, _, K = self._labels_input(labels, K)
+            if ln != n:
+                raise ValueError("ref and labels must have the same length")
+            fn = self._L.vgs_compare_point_labels_device if dev else self._L.vgs_compare_point_labels
+            self._ck(fn(self._h, lptr, K, ptr, n, C.byref(n_cells), C.byref(n_refs), _ptr(summary)))
+        rows = {"cells": n_cells.value, "refs": n_refs.value, "segs": max(K, 0)}
         out = {name: np.zeros(rows[tab], dtype=dt) for name, dt, tab in self.COMPARE_FIELDS}
         self._ck(self._L.vgs_get_label_comparison(self._h, *(_ptr(out[name]) for name, _, _ in self.COMPARE_FIELDS)))
         out["summary"] = summary
@@ -664,12 +708,28 @@ class VoxelBasedSegmentation:
             return {name: np.zeros((0, int(n_classes)) if w == 0 else 0, dtype=dt) for name, dt, w in Engine.CLASS_HIST_FIELDS}
         return self._eng.segment_class_histogram(classes, n_classes)
 
-    def compareClusterLabels(self, ref):
+    def compareClusterLabels(self, ref, labels=None):
         """Extension (no VS line): the clusters against a reference labelling; row i of the cluster table belongs to getClusterIdx()[i]
-        (Engine.compare_labels).  Empty tables and a zero summary before drawColorMapofPointsinClusters."""
+        (Engine.compare_labels).  `labels`: score this per-point labelling (refineClusterLabels()' result, say) instead of the clusters'
+        own.  Empty tables and a zero summary before drawColorMapofPointsinClusters."""
         if not self._drawn:
             return dict({name: np.zeros(0, dtype=dt) for name, dt, _ in Engine.COMPARE_FIELDS}, summary=np.zeros(12, np.int64))
-        return self._eng.compare_labels(ref)
+        return self._eng.compare_labels(ref, labels)
+
+    def getLabelDescriptors(self, labels):
+        """Extension (no VS line): the descriptors of a per-point labelling with the clusters' label range (refineClusterLabels()' result,
+        say): row i describes the points labelled i, plus n_skipped (Engine.describe_labels).  Empty before
+        drawColorMapofPointsinClusters."""
+        if not self._drawn:
+            return dict({name: np.zeros((0, w) if w > 1 else 0, dtype=dt) for name, dt, w in Engine.DESCRIPTOR_FIELDS}, n_skipped=0)
+        return self._eng.describe_labels(labels)
+
+    def getLabelBoxes(self, labels, frame="principal"):
+        """Extension (no VS line): the oriented boxes of a per-point labelling with the clusters' label range (Engine.label_boxes).  Empty
+        before drawColorMapofPointsinClusters."""
+        if not self._drawn:
+            return {name: np.zeros((0, w), dtype=dt) for name, dt, w in Engine.BOX_FIELDS}
+        return self._eng.label_boxes(labels, frame)
 
     def refineClusterLabels(self, patch_radius=None, switch_ratio=0.25, fill=True):
         """Extension (no VS line): one label per input point, refined at the cluster boundaries; label i names getClusterIdx()[i]
@@ -771,10 +831,20 @@ class SuperVoxelBasedSegmentation:
         """Extension (no SS line): row i counts `classes` over getClusterIdx()[i] -- both are in label order (Engine.segment_class_histogram)."""
         return self._eng.segment_class_histogram(classes, n_classes)
 
-    def compareClusterLabels(self, ref):
+    def compareClusterLabels(self, ref, labels=None):
         """Extension (no SS line): the clusters against a reference labelling; row i of the cluster table belongs to getClusterIdx()[i]
-        (Engine.compare_labels)."""
-        return self._eng.compare_labels(ref)
+        (Engine.compare_labels).  `labels`: score this per-point labelling (refineClusterLabels()' result, say) instead of the clusters'
+        own."""
+        return self._eng.compare_labels(ref, labels)
+
+    def getLabelDescriptors(self, labels):
+        """Extension (no SS line): the descriptors of a per-point labelling with the clusters' label range (refineClusterLabels()' result,
+        say): row i describes the points labelled i, plus n_skipped (Engine.describe_labels)."""
+        return self._eng.describe_labels(labels)
+
+    def getLabelBoxes(self, labels, frame="principal"):
+        """Extension (no SS line): the oriented boxes of a per-point labelling with the clusters' label range (Engine.label_boxes)."""
+        return self._eng.label_boxes(labels, frame)
 
     def refineClusterLabels(self, patch_radius=None, switch_ratio=0.25, fill=True):
         """Extension (no SS line): one label per input point, refined at the cluster boundaries; label i names getClusterIdx()[i]

@@ -240,6 +240,8 @@ void vgs_destroy(vgs_ctx* c) {
   c->cmp_rsort.release(); c->cmp_rstart.release(); c->cmp_tmp.release();
   c->rf_label.release(); c->rf_batches.release(); c->rf_start.release(); c->rf_ids.release(); c->rf_cnt.release(); c->rf_nall.release();
   c->rf_rows.release(); c->rf_counts.release();
+  c->ps_in.release(); c->ps_nnodes.release(); c->ps_key.release(); c->ps_val.release(); c->ps_seg.release(); c->ps_nn.release(); c->ps_tmp.release();
+  c->ps_meta.release(); c->ps_part.release(); c->ps_d.release(); c->ps_f.release(); c->ps_npts.release();
   c->cl_off.release(); c->cl_idx.release(); c->conn.release(); c->evals.release(); c->lc_pending.release(); c->lc_defer.release(); c->lc_defer_flag.release(); c->csize.release(); c->attach.release(); c->cc_flags.release(); c->parent.release(); c->csz.release();
   c->vc_cen.release(); c->vc_nrm.release(); c->vc_dist.release(); c->vc_state.release(); c->vc_tile_start.release(); c->vc_cell.release(); c->vc_plive.release(); c->vc_tile_of.release(); c->vc_tchg.release(); c->vc_nbr_tiles.release(); c->vc_halo.release(); c->vc_tile_meta.release(); c->vc_pool.release(); c->vc_ring.release(); c->vc_dbg.release(); c->vc_label.release();
   c->vc_seedkey.release(); c->vc_sums.release(); c->vc_count.release(); c->vc_accu.release(); c->vc_alive.release();

@@ -1,0 +1,377 @@
+// pointseg.hip -- descriptors and oriented boxes of a per-POINT labelling of the context's cloud that the CALLER supplies (include/vgs.h:
+// vgs_point_label_descriptors, vgs_point_label_boxes): the refined labels, ground-truth instances, anything made from the engine's output.
+// The passes of segdesc.hip / segbox.hip sort V nodes by label and walk each node's run of points, so they can only describe a labelling
+// that is constant on a node; here the points themselves are sorted.  Row k covers the points i with labels[i] == k that xs/ys/zs hold
+// (the finite points, the ones in the octree); the row fields, the algebra and the frame rule are those of the two node passes.
+//
+// Data flow (the points sit in HBM in leaf order, perm_b gives the input index of a sorted position, pt_vox its node):
+//   1. k_ps_keys      for every sorted position pos < N: l = labels[perm[pos]]; pos < Nf: key = l if 0 <= l < K, else K, value = pos;
+//                     pos >= Nf (a point outside the octree) with l >= 0: counted as skipped; l >= K anywhere: the smallest such input
+//                     index is kept (one atomicMax of N - i per workgroup that saw one)                                 -> read-back
+//   2. one STABLE rocprim::radix_sort_pairs over the bits of K -> pos_sorted: a label's points are one run, positions ascending inside it
+//   3. k_ps_segments  one lower bound per k: the run's start; ceil(points / SD_CHUNK) chunks, none for a label without a point; exclusive
+//                     scan -> the first chunk of every label.  The chunk grid is the bound Nf / SD_CHUNK + min(K, Nf) + 1 (only a label
+//                     with a point has a ragged last chunk), launched without reading the real number back
+//   4. k_ps_chunks    one workgroup per chunk: the point of a lane is pos_sorted[a + it * SD_TB + tid], the anchor the label's first point
+//                     in that order, the partial record sd_chunk_sums' (segpass.hpp, the body k_sd_chunks runs); and the number of head
+//                     flags pt_vox[pos_sorted[q]] != pt_vox[pos_sorted[q - 1]] of the chunk, whose sum over a label is its n_nodes
+//   5. k_ps_final     one wavefront per label: sd_fold_partials, the head flags added, sd_segment_algebra -- the one copy of the algebra
+//   6. boxes: k_sb_frames (segbox.hip) over the rows of step 5, k_ps_box_chunks with sb_chunk_extents over the same pos_sorted,
+//      k_ps_box_final with the fold and the row of k_sb_final
+// A label no point carries: no chunk, so the folds are empty: n_points = n_nodes = 0, bbox6 = (+inf x3, -inf x3), a zero anchor and zero
+// sums (zero centroid, covariance and eigenvalues, identity eigenvectors, the features of zeros); its box is lo = hi = half = 0 and
+// center = centroid, the rule of vgs_segment_boxes_from_extents.
+// Why a sort and not atomics: fp64 sums by atomics depend on the order of arrival.  Sorted, every sum has a fixed shape -- which point a
+// lane reads depends on (chunk, lane, step) only -- so the tables are bit-identical from call to call and engine to engine.  And for a
+// labelling that is constant on nodes, a stable sort of the positions by label gives the very point sequence sd_prepare's virtual order
+// gives (nodes in ascending id, each node's run in order), hence the same chunks and the same anchor: handed the engine's own point
+// labels, this pass reproduces the cached tables of segdesc.hip and segbox.hip byte for byte.
+// Scratch, all in buffers of its own (ps_*; nothing a getter or a cached table reads): two key and two value arrays of Nf words = 16 B
+// per finite point, rocprim's sort storage, 3 (K + 1) words of label starts and chunk counts, one partial record and one word per chunk,
+// the K output rows, and N words for the labels of the host variants.  Nothing is cached: the input is the caller's.
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+
+#include <rocprim/rocprim.hpp>
+
+#include "segpass.hpp"
+
+typedef unsigned long long ps_u64;
+enum { PM_SKIPPED = 0, PM_BAD = 1, PM_SLOTS = 2 };   // slots of ps_meta
+#define PS_TB 256
+
+// Step 1.  perm == nullptr: the identity (a cloud without a finite point has no order).  key == nullptr: the range check alone.
+__global__ __launch_bounds__(PS_TB) void k_ps_keys(const int32_t* __restrict__ labels, const uint32_t* __restrict__ perm, int64_t N, int64_t nf,
+                                                   uint32_t K, uint32_t* __restrict__ key, uint32_t* __restrict__ val, ps_u64* __restrict__ meta) {
+  __shared__ ps_u64 s_sk[PS_TB / 64], s_bad[PS_TB / 64];
+  const int64_t pos = (int64_t)blockIdx.x * PS_TB + threadIdx.x;
+  ps_u64 sk = 0, bad = 0;
+  if (pos < N) {
+    const int64_t i = perm ? (int64_t)perm[pos] : pos;
+    const int32_t l = labels[i];
+    const bool over = l >= 0 && (uint32_t)l >= K;
+    if (over) bad = (ps_u64)(N - i);   // (the largest N - i is the first offending index)
+    if (pos < nf) {
+      if (key) { key[pos] = (l < 0 || over) ? K : (uint32_t)l; val[pos] = (uint32_t)pos; }
+    } else if (l >= 0) {
+      sk = 1;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    sk += __shfl_xor(sk, m, 64);
+    const ps_u64 o = __shfl_xor(bad, m, 64); bad = o > bad ? o : bad;
+  }
+  if ((threadIdx.x & 63) == 0) { s_sk[threadIdx.x >> 6] = sk; s_bad[threadIdx.x >> 6] = bad; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;   // at most two atomics per workgroup
+  for (int w = 1; w < PS_TB / 64; ++w) { sk += s_sk[w]; bad = s_bad[w] > bad ? s_bad[w] : bad; }
+  if (sk) atomicAdd(&meta[PM_SKIPPED], sk);
+  if (bad) atomicMax(&meta[PM_BAD], bad);
+}
+
+// Step 3.  Per label k < K: the start of its run in the sorted keys (seg_start[K] = the end of the labelled points) and its number of
+// chunks, 0 for a label without a point (nchunk[K] = 0).
+__global__ __launch_bounds__(PS_TB) void k_ps_segments(const uint32_t* __restrict__ key, uint32_t n, uint32_t K, uint32_t* __restrict__ seg_start,
+                                                       uint32_t* __restrict__ nchunk) {
+  const uint64_t k64 = (uint64_t)blockIdx.x * PS_TB + threadIdx.x;
+  if (k64 > (uint64_t)K) return;
+  const uint32_t k = (uint32_t)k64;
+  const uint32_t n0 = sd_lower_bound(key, n, k);
+  seg_start[k] = n0;
+  if (k == K) { nchunk[k] = 0; return; }
+  const uint32_t n1 = sd_lower_bound(key, n, k + 1);
+  nchunk[k] = (n1 - n0 + SD_CHUNK - 1) / SD_CHUNK;
+}
+
+// The walk of a chunk workgroup (blockIdx.x) from chunk to label: the label k of the chunk, the start s0 of the label's run and the
+// chunk's range [a, b) in pos_sorted.  False for a workgroup past the real number of chunks.
+struct PsChunk { uint32_t k, s0, a, b; };
+__device__ __forceinline__ bool ps_walk(const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_chunk, uint32_t K, PsChunk& o) {
+  const uint32_t c = blockIdx.x;
+  if (c >= seg_chunk[K]) return false;
+  // label of chunk c: the last k with seg_chunk[k] <= c -- a label without a chunk shares its value with the next one and is passed over
+  uint32_t lo = 0, hi = K - 1;
+  while (lo < hi) { const uint32_t mid = lo + ((hi - lo + 1) >> 1); if (seg_chunk[mid] <= c) lo = mid; else hi = mid - 1; }
+  o.k = lo;
+  o.s0 = seg_start[lo];
+  o.a = o.s0 + (c - seg_chunk[lo]) * SD_CHUNK;
+  o.b = min(o.a + (uint32_t)SD_CHUNK, seg_start[lo + 1]);
+  return true;
+}
+
+// Step 4.  Grid: the bound of the header; workgroups past the real number of chunks leave at once (whole workgroups, before any barrier).
+__global__ __launch_bounds__(SD_TB) void k_ps_chunks(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                     const uint32_t* __restrict__ pos_sorted, const uint32_t* __restrict__ pt_vox,
+                                                     const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_chunk, uint32_t K,
+                                                     double* __restrict__ part, uint32_t* __restrict__ nn_part) {
+  __shared__ uint32_t s_nn[SD_TB / 64];
+  PsChunk wk;
+  if (!ps_walk(seg_start, seg_chunk, K, wk)) return;
+  const uint32_t c = blockIdx.x;
+  // the anchor: the label's first point in the sorted order, the same for every chunk of the label
+  const uint32_t pa = pos_sorted[wk.s0];
+  const double ax = (double)xs[pa], ay = (double)ys[pa], az = (double)zs[pa];
+  sd_chunk_sums<false>(xs, ys, zs, wk.a, wk.b, ax, ay, az, [&](uint32_t q) { return pos_sorted[q]; }, part + (size_t)c * SD_REC, nullptr, 0, 0);
+  // distinct nodes: inside a label the positions ascend, so a node's points are adjacent and its first one carries the flag
+  uint32_t heads = 0;
+#pragma unroll 2
+  for (int it = 0; it < SD_PPT; ++it) {
+    const uint32_t q = wk.a + (uint32_t)it * SD_TB + threadIdx.x;
+    if (q < wk.b) heads += (q == wk.s0 || pt_vox[pos_sorted[q]] != pt_vox[pos_sorted[q - 1]]) ? 1u : 0u;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) heads += __shfl_xor(heads, m, 64);
+  if ((threadIdx.x & 63) == 0) s_nn[threadIdx.x >> 6] = heads;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t v = s_nn[0];
+    for (int u = 1; u < SD_TB / 64; ++u) v += s_nn[u];
+    nn_part[c] = v;
+  }
+}
+
+// Step 5.  One wavefront per label: fold its partials (lane stride, then butterfly), then everything per label on lane 0.
+__global__ __launch_bounds__(256) void k_ps_final(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                  const uint32_t* __restrict__ pos_sorted, const uint32_t* __restrict__ seg_start,
+                                                  const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part,
+                                                  const uint32_t* __restrict__ nn_part, uint32_t n_part, uint32_t K, int svgs,
+                                                  int64_t* __restrict__ o_npts, int32_t* __restrict__ o_nnodes, float* __restrict__ o_bbox,
+                                                  double* __restrict__ o_cen, double* __restrict__ o_cov, double* __restrict__ o_eval,
+                                                  double* __restrict__ o_evec, float* __restrict__ o_eig8) {
+  const uint32_t k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (k >= K) return;   // (whole wavefronts; no barrier follows)
+  const uint32_t c0 = seg_chunk[k], c1 = min(seg_chunk[k + 1], n_part);   // (the bound only guards the records: the chunks fit, see the launch)
+  // the head flags first; their sum waits in LDS, one word per wavefront, so that the fold below keeps k_sd_final's register budget
+  __shared__ uint32_t s_nn[4];
+  uint32_t nn = 0;
+  for (uint32_t c = c0 + lane; c < c1; c += 64) nn += nn_part[c];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) nn += __shfl_xor(nn, m, 64);
+  if (lane == 0) s_nn[threadIdx.x >> 6] = nn;
+  double s[9], mn[3], mx[3], cnt;
+  sd_fold_partials<false>(part, c0, c1, lane, s, mn, mx, cnt);
+  if (lane != 0) return;
+  nn = s_nn[threadIdx.x >> 6];   // (written by this lane: no barrier)
+  const uint32_t s0 = seg_start[k], n = seg_start[k + 1] - s0;
+  double anc[3] = {0.0, 0.0, 0.0};   // (a label without a point: a zero anchor)
+  if (n > 0) {
+    const uint32_t pa = pos_sorted[s0];
+    anc[0] = (double)xs[pa]; anc[1] = (double)ys[pa]; anc[2] = (double)zs[pa];
+  }
+  sd_segment_algebra(k, (int64_t)n, (int32_t)nn, mn, mx, anc, s, svgs, o_npts, o_nnodes, o_bbox, o_cen, o_cov, o_eval, o_evec, o_eig8);
+}
+
+// Step 6.  The chunks of step 4 once more, projected onto the frame of their label about its centroid.
+__global__ __launch_bounds__(SD_TB) void k_ps_box_chunks(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
+                                                         const uint32_t* __restrict__ pos_sorted, const uint32_t* __restrict__ seg_start,
+                                                         const uint32_t* __restrict__ seg_chunk, uint32_t K, const double* __restrict__ cen,
+                                                         const double* __restrict__ frame, double* __restrict__ part) {
+  PsChunk wk;
+  if (!ps_walk(seg_start, seg_chunk, K, wk)) return;
+  sb_chunk_extents<false>(xs, ys, zs, wk.a, wk.b, cen + (size_t)wk.k * 3, frame + (size_t)wk.k * 9, [&](uint32_t q) { return pos_sorted[q]; },
+                          part + (size_t)blockIdx.x * SB_REC, nullptr, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void k_ps_box_final(const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part, uint32_t n_part,
+                                                      uint32_t K, const double* __restrict__ cen, const double* __restrict__ frame,
+                                                      double* __restrict__ o_lo, double* __restrict__ o_hi, double* __restrict__ o_half,
+                                                      double* __restrict__ o_center) {
+  const uint32_t k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (k >= K) return;   // (whole wavefronts; no barrier follows)
+  const uint32_t c0 = seg_chunk[k], c1 = min(seg_chunk[k + 1], n_part);
+  double mn[3], mx[3];
+  sb_fold_partials(part, c0, c1, lane, mn, mx);
+  if (lane != 0) return;
+  if (c0 >= c1) {   // a label without a point: lo = hi = 0, so half = 0 and center = centroid plus a zero
+#pragma unroll
+    for (int f = 0; f < 3; ++f) { mn[f] = 0.0; mx[f] = 0.0; }
+  }
+  sb_box_row(k, mn, mx, cen, frame, o_lo, o_hi, o_half, o_center);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------- host
+// Step 1 alone or with the keys: the first input index whose label is not below K fails the call, the message naming it and its value.
+static vgs_status ps_scan_labels(vgs_ctx* c, const char* fn, const int32_t* labels_dev, const uint32_t* perm, int64_t N, int64_t nf, int64_t K,
+                                 uint32_t* key, uint32_t* val, int64_t* n_skipped) {
+  if (n_skipped) *n_skipped = 0;
+  if (N == 0) return VGS_OK;
+  VGS_HIP_TRY(c, c->ps_meta.ensure(PM_SLOTS));
+  ps_u64* meta = (ps_u64*)c->ps_meta.p;
+  VGS_HIP_TRY(c, hipMemsetAsync(meta, 0, PM_SLOTS * sizeof(uint64_t), c->stream));
+  hipLaunchKernelGGL(k_ps_keys, dim3((unsigned)((N + PS_TB - 1) / PS_TB)), dim3(PS_TB), 0, c->stream, labels_dev, perm, N, nf, (uint32_t)K, key, val, meta);
+  VGS_HIP_TRY(c, hipGetLastError());
+  uint64_t m[PM_SLOTS];
+  VGS_READBACK(c, m, meta, PM_SLOTS * sizeof(uint64_t));
+  if (m[PM_BAD] != 0) {
+    const int64_t i = N - (int64_t)m[PM_BAD];
+    int32_t v = 0;
+    VGS_READBACK(c, &v, labels_dev + i, sizeof(int32_t));
+    c->err = std::string(fn) + ": labels[" + std::to_string(i) + "] = " + std::to_string(v) + " is not below K = " + std::to_string(K) +
+             " (a label must be negative or in 0 .. K-1)";
+    return VGS_E_ARG;
+  }
+  if (n_skipped) *n_skipped = (int64_t)m[PM_SKIPPED];
+  return VGS_OK;
+}
+
+vgs_status vgs_check_label_range(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t n, int64_t K) {
+  return ps_scan_labels(c, fn, labels_dev, nullptr, n, n, K, nullptr, nullptr, nullptr);
+}
+
+static vgs_status ps_check(vgs_ctx* c, const char* fn, const int32_t* labels, int64_t n, int64_t K) {
+  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
+  if (vgs_is_tile(c)) {
+    c->err = std::string(fn) + ": a tile context (owned region / own point range) holds only part of the cloud; the tables of a point labelling need the whole cloud in one context";
+    return VGS_E_STATE;
+  }
+  if (n != c->N) {
+    c->err = std::string(fn) + ": n = " + std::to_string(n) + " must equal the number of points of the cloud, " + std::to_string(c->N);
+    return VGS_E_ARG;
+  }
+  if (!labels && n > 0) { c->err = std::string(fn) + ": labels is NULL"; return VGS_E_ARG; }
+  if (K < 0 || K > (int64_t)0x7fffffff) { c->err = std::string(fn) + ": K = " + std::to_string(K) + " is out of range"; return VGS_E_ARG; }
+  return VGS_OK;
+}
+
+// the K rows in HBM (ps_npts, ps_nnodes, ps_f, ps_d)
+struct PsTable {
+  int64_t* npts; int32_t* nnodes; float *bbox, *eig8;
+  double *cen, *cov, *eval, *evec;           // descriptors
+  double *frame, *lo, *hi, *half, *center;   // boxes
+};
+
+// Steps 1-5 over labels_dev, and step 6 when frame >= 0: the rows are left in the ps_* buffers (T), the stream is not waited for.
+static vgs_status ps_tables_on_device(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t K, int frame, PsTable& T, int64_t* n_skipped) {
+  const int64_t N = c->N, nf = c->Nf;
+  VGS_HIP_TRY(c, c->ps_key.ensure(2 * (size_t)nf + 1)); VGS_HIP_TRY(c, c->ps_val.ensure(2 * (size_t)nf + 1));
+  uint32_t *key_in = c->ps_key.p, *key_out = key_in + nf, *val_in = c->ps_val.p, *val_out = val_in + nf;
+  vgs_status s = ps_scan_labels(c, fn, labels_dev, nf > 0 ? c->perm_b.p : nullptr, N, nf, K, key_in, val_in, n_skipped);
+  if (s != VGS_OK) return s;
+  if (K == 0) return VGS_OK;
+  // only a label with a point has a ragged last chunk: sum over the labels of ceil(n_k / SD_CHUNK) <= floor(Nf / SD_CHUNK) + min(K, Nf)
+  const int64_t n_chunks_max = nf / SD_CHUNK + std::min(K, nf) + 1;
+  if (n_chunks_max * SD_TB >= ((int64_t)1 << 32)) {
+    c->err = std::string(fn) + ": " + std::to_string(nf) + " points under " + std::to_string(K) + " labels need up to " + std::to_string(n_chunks_max) +
+             " chunk workgroups, above the limit of one launch";
+    return VGS_E_UNSUPPORTED;
+  }
+  const size_t k = (size_t)K;
+  VGS_HIP_TRY(c, c->ps_seg.ensure(3 * (k + 1)));
+  VGS_HIP_TRY(c, c->ps_part.ensure((size_t)n_chunks_max * SD_REC)); VGS_HIP_TRY(c, c->ps_nn.ensure((size_t)n_chunks_max));
+  VGS_HIP_TRY(c, c->ps_npts.ensure(k)); VGS_HIP_TRY(c, c->ps_nnodes.ensure(k)); VGS_HIP_TRY(c, c->ps_f.ensure(14 * k));
+  VGS_HIP_TRY(c, c->ps_d.ensure(42 * k));
+  uint32_t *seg_start = c->ps_seg.p, *nchunk = seg_start + k + 1, *seg_chunk = nchunk + k + 1;
+  T.npts = c->ps_npts.p; T.nnodes = c->ps_nnodes.p; T.bbox = c->ps_f.p; T.eig8 = T.bbox + 6 * k;
+  T.cen = c->ps_d.p; T.cov = T.cen + 3 * k; T.eval = T.cov + 6 * k; T.evec = T.eval + 3 * k;
+  T.frame = T.evec + 9 * k; T.lo = T.frame + 9 * k; T.hi = T.lo + 3 * k; T.half = T.hi + 3 * k; T.center = T.half + 3 * k;
+  unsigned bits = 1;
+  while (bits < 32 && (1ull << bits) <= (unsigned long long)K) ++bits;   // keys 0 .. K
+  size_t t_sort = 0, t_scan = 0;
+  if (nf > 0) VGS_HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, t_sort, key_in, key_out, val_in, val_out, (size_t)nf, 0, bits, c->stream));
+  VGS_HIP_TRY(c, rocprim::exclusive_scan(nullptr, t_scan, nchunk, seg_chunk, 0u, k + 1, rocprim::plus<uint32_t>(), c->stream));
+  VGS_HIP_TRY(c, c->ps_tmp.ensure(std::max(t_sort, t_scan)));
+  if (nf > 0) VGS_HIP_TRY(c, rocprim::radix_sort_pairs(c->ps_tmp.p, t_sort, key_in, key_out, val_in, val_out, (size_t)nf, 0, bits, c->stream));
+  hipLaunchKernelGGL(k_ps_segments, dim3((unsigned)((k + 1 + PS_TB - 1) / PS_TB)), dim3(PS_TB), 0, c->stream, key_out, (uint32_t)nf, (uint32_t)K, seg_start,
+                     nchunk);
+  VGS_HIP_TRY(c, rocprim::exclusive_scan(c->ps_tmp.p, t_scan, nchunk, seg_chunk, 0u, k + 1, rocprim::plus<uint32_t>(), c->stream));
+  const unsigned waves_grid = (unsigned)((K + 3) / 4);
+  if (nf > 0)
+    hipLaunchKernelGGL(k_ps_chunks, dim3((unsigned)n_chunks_max), dim3(SD_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, val_out, c->pt_vox.p, seg_start,
+                       seg_chunk, (uint32_t)K, c->ps_part.p, c->ps_nn.p);
+  hipLaunchKernelGGL(k_ps_final, dim3(waves_grid), dim3(256), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, val_out, seg_start, seg_chunk, c->ps_part.p,
+                     c->ps_nn.p, (uint32_t)n_chunks_max, (uint32_t)K, c->P.method == 3 ? 1 : 0, T.npts, T.nnodes, T.bbox, T.cen, T.cov, T.eval, T.evec, T.eig8);
+  if (frame >= 0) {
+    // (the descriptor partials are folded: the same buffer takes the shorter extent records)
+    sb_launch_frames(c, T.evec, T.cov, K, frame, T.frame);
+    if (nf > 0)
+      hipLaunchKernelGGL(k_ps_box_chunks, dim3((unsigned)n_chunks_max), dim3(SD_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, val_out, seg_start, seg_chunk,
+                         (uint32_t)K, T.cen, T.frame, c->ps_part.p);
+    hipLaunchKernelGGL(k_ps_box_final, dim3(waves_grid), dim3(256), 0, c->stream, seg_chunk, c->ps_part.p, (uint32_t)n_chunks_max, (uint32_t)K, T.cen,
+                       T.frame, T.lo, T.hi, T.half, T.center);
+  }
+  VGS_HIP_TRY(c, hipGetLastError());
+  return VGS_OK;
+}
+
+// the host variants' one upload into a buffer of the context
+vgs_status vgs_upload_point_labels(vgs_ctx* c, const int32_t* labels_host, int64_t n, const int32_t** labels_dev) {
+  *labels_dev = nullptr;
+  if (n <= 0) return VGS_OK;
+  VGS_HIP_TRY(c, c->ps_in.ensure((size_t)n));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->ps_in.p, labels_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
+  *labels_dev = c->ps_in.p;
+  return VGS_OK;
+}
+
+#define PS_COPY(dst, src, count) \
+  if (dst) VGS_HIP_TRY(c, hipMemcpyAsync((dst), (src), (count) * sizeof(*(dst)), hipMemcpyDeviceToHost, c->stream))
+
+static vgs_status ps_descriptors(vgs_ctx* c, const char* fn, const int32_t* labels, bool on_device, int64_t n, int64_t K, int64_t* n_skipped,
+                                 int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3, double* evecs9,
+                                 float* eigen8) {
+  if (!c) return VGS_E_ARG;
+  vgs_status s = ps_check(c, fn, labels, n, K);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  if (!on_device && (s = vgs_upload_point_labels(c, labels, n, &labels)) != VGS_OK) return s;
+  PsTable T;
+  if ((s = ps_tables_on_device(c, fn, labels, K, -1, T, n_skipped)) != VGS_OK) return s;
+  const size_t k = (size_t)K;
+  if (k > 0) {
+    PS_COPY(n_points, T.npts, k); PS_COPY(n_nodes, T.nnodes, k); PS_COPY(bbox6, T.bbox, 6 * k); PS_COPY(centroid3, T.cen, 3 * k);
+    PS_COPY(cov6, T.cov, 6 * k); PS_COPY(evals3, T.eval, 3 * k); PS_COPY(evecs9, T.evec, 9 * k); PS_COPY(eigen8, T.eig8, 8 * k);
+  }
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the rows have arrived, and a labelling read in place is the caller's again
+  return VGS_OK;
+}
+
+static vgs_status ps_boxes(vgs_ctx* c, const char* fn, const int32_t* labels, bool on_device, int64_t n, int64_t K, int32_t frame, double* center3,
+                           double* half3, double* frame9, double* lo3, double* hi3) {
+  if (!c) return VGS_E_ARG;
+  if (frame != VGS_BOX_PRINCIPAL && frame != VGS_BOX_UPRIGHT) {
+    c->err = std::string(fn) + ": frame must be VGS_BOX_PRINCIPAL (0) or VGS_BOX_UPRIGHT (1)";
+    return VGS_E_ARG;
+  }
+  vgs_status s = ps_check(c, fn, labels, n, K);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  if (!on_device && (s = vgs_upload_point_labels(c, labels, n, &labels)) != VGS_OK) return s;
+  PsTable T;
+  if ((s = ps_tables_on_device(c, fn, labels, K, frame, T, nullptr)) != VGS_OK) return s;
+  const size_t k = (size_t)K;
+  if (k > 0) {
+    PS_COPY(center3, T.center, 3 * k); PS_COPY(half3, T.half, 3 * k); PS_COPY(frame9, T.frame, 9 * k); PS_COPY(lo3, T.lo, 3 * k); PS_COPY(hi3, T.hi, 3 * k);
+  }
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_point_label_descriptors(vgs_ctx* c, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_skipped, int64_t* n_points,
+                                                  int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3, double* evecs9,
+                                                  float* eigen8) {
+  return ps_descriptors(c, "vgs_point_label_descriptors", labels_host, false, n, K, n_skipped, n_points, n_nodes, bbox6, centroid3, cov6, evals3, evecs9,
+                        eigen8);
+}
+
+extern "C" vgs_status vgs_point_label_descriptors_device(vgs_ctx* c, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_skipped,
+                                                         int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6,
+                                                         double* evals3, double* evecs9, float* eigen8) {
+  return ps_descriptors(c, "vgs_point_label_descriptors_device", labels_dev, true, n, K, n_skipped, n_points, n_nodes, bbox6, centroid3, cov6, evals3,
+                        evecs9, eigen8);
+}
+
+extern "C" vgs_status vgs_point_label_boxes(vgs_ctx* c, const int32_t* labels_host, int64_t n, int64_t K, int32_t frame, double* center3, double* half3,
+                                            double* frame9, double* lo3, double* hi3) {
+  return ps_boxes(c, "vgs_point_label_boxes", labels_host, false, n, K, frame, center3, half3, frame9, lo3, hi3);
+}
+
+extern "C" vgs_status vgs_point_label_boxes_device(vgs_ctx* c, const int32_t* labels_dev, int64_t n, int64_t K, int32_t frame, double* center3,
+                                                   double* half3, double* frame9, double* lo3, double* hi3) {
+  return ps_boxes(c, "vgs_point_label_boxes_device", labels_dev, true, n, K, frame, center3, half3, frame9, lo3, hi3);
+}

@@ -25,9 +25,7 @@
 #include <string.h>
 #include <vector>
 
-#include "vgs_context.hpp"
-
-#define SB_REC 6   // doubles per partial record: min t[3], max t[3]
+#include "segpass.hpp"   // SB_REC doubles per partial record, and the bodies shared with pointseg.hip
 
 // The frame of segment k.  Principal: the evecs9 row.  Upright: see the header.  One thread per segment.
 __global__ __launch_bounds__(256) void k_sb_frames(const double* __restrict__ evec, const double* __restrict__ cov, uint32_t K, int upright,
@@ -73,22 +71,6 @@ __global__ __launch_bounds__(256) void k_sb_frames(const double* __restrict__ ev
   o[6] = 0.0;     o[7] = 0.0;     o[8] = 1.0;
 }
 
-__device__ __forceinline__ double sb_wave_min(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x = fmin(x, __shfl_xor(x, m, 64));
-  return x;
-}
-__device__ __forceinline__ double sb_wave_max(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x = fmax(x, __shfl_xor(x, m, 64));
-  return x;
-}
-
-// Empty partial record: +inf min, -inf max
-__device__ __forceinline__ void sb_empty_record(double* __restrict__ rec) {
-  if (threadIdx.x < SB_REC) rec[threadIdx.x] = threadIdx.x < 3 ? __builtin_huge_val() : -__builtin_huge_val();
-}
-
 // One workgroup per chunk of SD_CHUNK virtual points of one segment: the chunk -> segment -> nodes walk of segdesc.hip's sd_chunk_body
 // (same staging arrays, same point of every lane and step), the projections of the header, one partial record.  Grid: the bound of
 // sd_prepare; workgroups past the real number of chunks leave at once.  cen / frame: 3 and 9 doubles per label.  OWN (tile contexts,
@@ -103,7 +85,6 @@ __device__ __forceinline__ void sb_chunk_body(const float* __restrict__ xs, cons
                                               const uint32_t* __restrict__ perm, int64_t own_first, int64_t own_end) {
   __shared__ uint32_t s_vp[SD_CHUNK];    // virtual start of the chunk's nodes
   __shared__ uint32_t s_dl[SD_CHUNK];    // sorted position - virtual position of the same (mod 2^32)
-  __shared__ double s_red[SD_TB / 64][SB_REC];
   const uint32_t c = blockIdx.x;
   SdChunk wk;
   if (!sd_walk(vox_start, ids, vp, seg_node, seg_chunk, K, s_vp, s_dl, wk)) {
@@ -111,46 +92,9 @@ __device__ __forceinline__ void sb_chunk_body(const float* __restrict__ xs, cons
     return;
   }
   const uint32_t k = wk.k, a = wk.a, b = wk.b, m = wk.m;
-  const double* cc = cen + (size_t)k * 3;
-  const double* ww = frame + (size_t)k * 9;
-  const double cx = cc[0], cy = cc[1], cz = cc[2];
-  const double w00 = ww[0], w01 = ww[1], w02 = ww[2], w10 = ww[3], w11 = ww[4], w12 = ww[5], w20 = ww[6], w21 = ww[7], w22 = ww[8];
-  __syncthreads();
-  double mn0 = __builtin_huge_val(), mn1 = __builtin_huge_val(), mn2 = __builtin_huge_val();
-  double mx0 = -__builtin_huge_val(), mx1 = -__builtin_huge_val(), mx2 = -__builtin_huge_val();
-#pragma unroll 2
-  for (int it = 0; it < SD_PPT; ++it) {
-    const uint32_t q = a + (uint32_t)it * SD_TB + threadIdx.x;
-    if (q < b) {
-      const uint32_t pos = sd_pos(s_vp, s_dl, m, q);
-      if (OWN) {
-        const int64_t o = (int64_t)perm[pos];
-        if (o < own_first || o >= own_end) continue;
-      }
-      // exact differences (a float against a double), then one fp64 operation per product and sum, in this association
-      const double dx = (double)xs[pos] - cx, dy = (double)ys[pos] - cy, dz = (double)zs[pos] - cz;
-      const double t0 = (w00 * dx + w10 * dy) + w20 * dz;
-      const double t1 = (w01 * dx + w11 * dy) + w21 * dz;
-      const double t2 = (w02 * dx + w12 * dy) + w22 * dz;
-      mn0 = fmin(mn0, t0); mn1 = fmin(mn1, t1); mn2 = fmin(mn2, t2);
-      mx0 = fmax(mx0, t0); mx1 = fmax(mx1, t1); mx2 = fmax(mx2, t2);
-    }
-  }
-  mn0 = sb_wave_min(mn0); mn1 = sb_wave_min(mn1); mn2 = sb_wave_min(mn2);
-  mx0 = sb_wave_max(mx0); mx1 = sb_wave_max(mx1); mx2 = sb_wave_max(mx2);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    double* r = s_red[w];
-    r[0] = mn0; r[1] = mn1; r[2] = mn2; r[3] = mx0; r[4] = mx1; r[5] = mx2;
-  }
-  __syncthreads();
-  if (threadIdx.x < SB_REC) {   // the waves in index order
-    const int f = threadIdx.x;
-    double v = s_red[0][f];
-    if (f < 3) { for (int u = 1; u < SD_TB / 64; ++u) v = fmin(v, s_red[u][f]); }
-    else { for (int u = 1; u < SD_TB / 64; ++u) v = fmax(v, s_red[u][f]); }
-    part[(size_t)c * SB_REC + f] = v;
-  }
+  // the projections, the butterflies and the waves in index order: segpass.hpp (its first barrier closes the staging above)
+  sb_chunk_extents<OWN>(xs, ys, zs, a, b, cen + (size_t)k * 3, frame + (size_t)k * 9, [&](uint32_t q) { return sd_pos(s_vp, s_dl, m, q); },
+                        part + (size_t)c * SB_REC, perm, own_first, own_end);
 }
 
 __global__ __launch_bounds__(SD_TB) void k_sb_chunks(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
@@ -179,30 +123,15 @@ __global__ __launch_bounds__(256) void k_sb_final(const uint32_t* __restrict__ s
   if (k >= K) return;   // (whole wavefronts; no barrier follows)
   const uint32_t c0 = seg_chunk[k], c1 = min(seg_chunk[k + 1], n_part);   // (the bound only guards the records: the chunks fit, see the launch)
   double mn[3], mx[3];
-#pragma unroll
-  for (int f = 0; f < 3; ++f) { mn[f] = __builtin_huge_val(); mx[f] = -__builtin_huge_val(); }
-  for (uint32_t c = c0 + lane; c < c1; c += 64) {
-    const double* r = part + (size_t)c * SB_REC;
-#pragma unroll
-    for (int f = 0; f < 3; ++f) { mn[f] = fmin(mn[f], r[f]); mx[f] = fmax(mx[f], r[3 + f]); }
-  }
-#pragma unroll
-  for (int f = 0; f < 3; ++f) { mn[f] = sb_wave_min(mn[f]); mx[f] = sb_wave_max(mx[f]); }
+  sb_fold_partials(part, c0, c1, lane, mn, mx);
   if (lane != 0) return;
-  const double* W = frame + (size_t)k * 9;
-  double mid[3];
-#pragma unroll
-  for (int f = 0; f < 3; ++f) {
-    o_lo[3 * (size_t)k + f] = mn[f];
-    o_hi[3 * (size_t)k + f] = mx[f];
-    o_half[3 * (size_t)k + f] = (mx[f] - mn[f]) * 0.5;
-    mid[f] = (mn[f] + mx[f]) * 0.5;
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    o_center[3 * (size_t)k + r] = cen[3 * (size_t)k + r] + ((W[3 * r + 0] * mid[0] + W[3 * r + 1] * mid[1]) + W[3 * r + 2] * mid[2]);
+  sb_box_row(k, mn, mx, cen, frame, o_lo, o_hi, o_half, o_center);
 }
 
+// k_sb_frames over K rows of evecs9 / cov6 in HBM, left on the stream: the one launch site of the frame rule (pointseg.hip calls it too)
+void sb_launch_frames(vgs_ctx* c, const double* evec, const double* cov, int64_t K, int frame, double* out) {
+  hipLaunchKernelGGL(k_sb_frames, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, evec, cov, (uint32_t)K, frame == VGS_BOX_UPRIGHT ? 1 : 0, out);
+}
 
 // The table of one frame in HBM, K = counts[VGS_N_KEPT] rows; valid until the next run of the stages.
 vgs_status vgs_segbox_on_device(vgs_ctx* c, int frame) {
@@ -219,8 +148,7 @@ vgs_status vgs_segbox_on_device(vgs_ctx* c, int frame) {
   SdPrep P;
   if ((s = sd_prepare(c, K, P)) != VGS_OK) return s;
   VGS_HIP_TRY(c, c->sb_part.ensure((size_t)P.n_chunks_max * SB_REC));
-  hipLaunchKernelGGL(k_sb_frames, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, c->sd_evec.p, c->sd_cov.p, (uint32_t)K,
-                     frame == VGS_BOX_UPRIGHT ? 1 : 0, c->sb_frame[frame].p);
+  sb_launch_frames(c, c->sd_evec.p, c->sd_cov.p, K, frame, c->sb_frame[frame].p);
   hipLaunchKernelGGL(k_sb_chunks, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, P.ids, P.vp,
                      P.seg_node, P.seg_chunk, (uint32_t)K, c->sd_cen.p, c->sb_frame[frame].p, c->sb_part.p);
   hipLaunchKernelGGL(k_sb_final, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, P.seg_chunk, c->sb_part.p, (uint32_t)P.n_chunks_max,
@@ -290,8 +218,7 @@ static vgs_status sbt_upload_frames(vgs_ctx* c, int64_t K, int32_t frame, const 
   VGS_HIP_TRY(c, hipMemcpyAsync(cen, centroid3, 3 * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
   VGS_HIP_TRY(c, hipMemcpyAsync(cov, cov6, 6 * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
   VGS_HIP_TRY(c, hipMemcpyAsync(evec, evecs9, 9 * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_sb_frames, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, evec, cov, (uint32_t)K,
-                     frame == VGS_BOX_UPRIGHT ? 1 : 0, c->sbt_frame.p);
+  sb_launch_frames(c, evec, cov, K, frame, c->sbt_frame.p);
   return VGS_OK;
 }
 

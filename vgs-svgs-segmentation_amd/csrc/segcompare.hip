@@ -15,6 +15,8 @@
 //   6. k_cmp_seg_iou (a search of the best id per segment) and the summary sums, kept per wavefront and added once -> read-back 4
 // A row and an id of any number of cells are read in chunks of 64 (the lane-stride loops).  Positions are uint32: N < 2^31.
 // Scratch: own buffers only (cmp_*); labels, descriptors, boxes and graph are read-only here.
+// vgs_compare_point_labels runs the same six steps over a labelling of the caller's instead of the point labels, K rows of the caller's;
+// any negative label is the dropped row, and a label not below K is refused first (one pass on the device, csrc/pointseg.hip).
 //
 // The tiled driver (include/vgs_tiles.h) runs the two halves on different inputs.  Steps 1-3 over a rank's OWN points only
 // (vgs_own_label_cells: k_cmp_scan_own is step 1 with the largest label beside the largest id, so that a label not below K is refused
@@ -78,7 +80,8 @@ __global__ __launch_bounds__(CMP_TB) void k_cmp_keys(const int32_t* __restrict__
   const int64_t i = (int64_t)blockIdx.x * CMP_TB + threadIdx.x;
   if (i >= N) return;
   const int32_t g = ref[i];
-  const uint64_t row = g < 0 ? (uint64_t)K + 1 : (uint64_t)(uint32_t)(labels[i] + 1);
+  const int32_t l = labels[i];   // (any negative label is the row of the dropped points: a caller's labelling need not say -1)
+  const uint64_t row = g < 0 ? (uint64_t)K + 1 : (l < 0 ? 0ull : (uint64_t)(uint32_t)l + 1);
   key[i] = (row << gbits) | (g < 0 ? 0ull : (uint64_t)(uint32_t)g);
 }
 
@@ -442,10 +445,11 @@ static vgs_status cmp_cell_tables(vgs_ctx* c, int64_t K, uint32_t stride, uint32
   return VGS_OK;
 }
 
-// the three tables from a device labelling into the cmp_* buffers; sizes and summary into the context
-static vgs_status cmp_build(vgs_ctx* c, const int32_t* ref_dev) {
+// the three tables from a device labelling into the cmp_* buffers; sizes and summary into the context.  labels_dev, K: the labels that are
+// scored and their number of rows -- the point labels and the kept count, or a caller's (vgs_compare_point_labels)
+static vgs_status cmp_build(vgs_ctx* c, const int32_t* ref_dev, const int32_t* labels_dev, int64_t K) {
   c->cmp_valid = false; c->cmp_own_cells = -1;
-  const int64_t N = c->N, K = c->counts[VGS_N_KEPT];
+  const int64_t N = c->N;
   c->cmp_cells = 0; c->cmp_refs = 0; c->cmp_K = K;
   for (int i = 0; i < 12; ++i) c->cmp_summary[i] = 0;
   if (N == 0) { c->cmp_K = 0; c->cmp_valid = true; return VGS_OK; }
@@ -459,7 +463,7 @@ static vgs_status cmp_build(vgs_ctx* c, const int32_t* ref_dev) {
   const uint32_t n_ann = (uint32_t)((uint64_t)N - m[CM_UNANN]);
   const unsigned gbits = cmp_bits(m[CM_MAXID]);
   uint32_t n_cells = 0;
-  vgs_status s = cmp_point_cells(c, c->pt_label.p, ref_dev, N, K, n_ann, gbits, meta, m, n_cells);
+  vgs_status s = cmp_point_cells(c, labels_dev, ref_dev, N, K, n_ann, gbits, meta, m, n_cells);
   if (s != VGS_OK) return s;
   return cmp_cell_tables(c, K, n_ann, n_cells, gbits, (int64_t)n_ann, (int64_t)m[CM_UNANN], meta, m);
 }
@@ -475,7 +479,7 @@ extern "C" vgs_status vgs_compare_labels_device(vgs_ctx* c, const int32_t* ref_d
   vgs_status s = cmp_check(c, "vgs_compare_labels_device", ref_dev, n);
   if (s != VGS_OK) return s;
   VGS_HIP_TRY(c, hipSetDevice(c->device));
-  if ((s = cmp_build(c, ref_dev)) != VGS_OK) return s;
+  if ((s = cmp_build(c, ref_dev, c->pt_label.p, c->counts[VGS_N_KEPT])) != VGS_OK) return s;
   cmp_report(c, n_cells, n_refs, summary);
   return VGS_OK;
 }
@@ -490,7 +494,51 @@ extern "C" vgs_status vgs_compare_labels(vgs_ctx* c, const int32_t* ref_host, in
     VGS_HIP_TRY(c, hipMemcpyAsync(c->cmp_ref.p, ref_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
   }
-  if ((s = cmp_build(c, c->cmp_ref.p)) != VGS_OK) return s;
+  if ((s = cmp_build(c, c->cmp_ref.p, c->pt_label.p, c->counts[VGS_N_KEPT])) != VGS_OK) return s;
+  cmp_report(c, n_cells, n_refs, summary);
+  return VGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ a caller's labelling against ref
+// The same tables with L[i] = seg_labels[i] (any negative label the dropped row) and K rows of the caller's: the argument checks, one
+// pass that refuses a label not below K (pointseg.hip), then cmp_build over that array instead of the point labels.
+static vgs_status cmp_point_check(vgs_ctx* c, const char* fn, const int32_t* seg, int64_t K, const int32_t* ref, int64_t n) {
+  vgs_status s = cmp_check(c, fn, ref, n);
+  if (s != VGS_OK) return s;
+  if (!seg && n > 0) { c->err = std::string(fn) + ": seg_labels is NULL"; return VGS_E_ARG; }
+  if (K < 0 || K > (int64_t)0x7fffffff) { c->err = std::string(fn) + ": K = " + std::to_string(K) + " is out of range"; return VGS_E_ARG; }
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_compare_point_labels_device(vgs_ctx* c, const int32_t* seg_dev, int64_t K, const int32_t* ref_dev, int64_t n, int64_t* n_cells,
+                                                      int64_t* n_refs, int64_t* summary) {
+  if (!c) return VGS_E_ARG;
+  const char* fn = "vgs_compare_point_labels_device";
+  vgs_status s = cmp_point_check(c, fn, seg_dev, K, ref_dev, n);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  if ((s = vgs_check_label_range(c, fn, seg_dev, n, K)) != VGS_OK) return s;
+  if ((s = cmp_build(c, ref_dev, seg_dev, K)) != VGS_OK) return s;
+  cmp_report(c, n_cells, n_refs, summary);
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_compare_point_labels(vgs_ctx* c, const int32_t* seg_host, int64_t K, const int32_t* ref_host, int64_t n, int64_t* n_cells,
+                                               int64_t* n_refs, int64_t* summary) {
+  if (!c) return VGS_E_ARG;
+  const char* fn = "vgs_compare_point_labels";
+  vgs_status s = cmp_point_check(c, fn, seg_host, K, ref_host, n);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  const int32_t* seg_dev = nullptr;
+  if ((s = vgs_upload_point_labels(c, seg_host, n, &seg_dev)) != VGS_OK) return s;
+  if ((s = vgs_check_label_range(c, fn, seg_dev, n, K)) != VGS_OK) return s;
+  if (n > 0) {
+    VGS_HIP_TRY(c, c->cmp_ref.ensure((size_t)n));
+    VGS_HIP_TRY(c, hipMemcpyAsync(c->cmp_ref.p, ref_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
+  }
+  if ((s = cmp_build(c, c->cmp_ref.p, seg_dev, K)) != VGS_OK) return s;
   cmp_report(c, n_cells, n_refs, summary);
   return VGS_OK;
 }

@@ -25,10 +25,10 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "vgs_context.hpp"
+#include "segpass.hpp"
 
-// SD_TB threads of a chunk workgroup, SD_PPT points per thread, SD_CHUNK = SD_TB * SD_PPT virtual points per chunk: vgs_context.hpp
-#define SD_REC 16                   // doubles per partial record: sum d[3], sum dd^T[6] (xx xy xz yy yz zz), min[3], max[3], (pad)
+// SD_TB threads of a chunk workgroup, SD_PPT points per thread, SD_CHUNK = SD_TB * SD_PPT virtual points per chunk: vgs_context.hpp;
+// SD_REC doubles per partial record and the bodies shared with segbox.hip and pointseg.hip: segpass.hpp
 
 // key of node v: its kept label, K for the nodes of dropped clusters (they sort behind every kept segment; so would a label >= K)
 __global__ void k_sd_keys(const int32_t* __restrict__ vox_label, int64_t V, uint32_t K, uint32_t* __restrict__ key, uint32_t* __restrict__ ids) {
@@ -49,12 +49,6 @@ __global__ void k_sd_runlen(const uint32_t* __restrict__ key, const uint32_t* __
   len[i] = n;
 }
 
-__device__ __forceinline__ uint32_t sd_lower_bound(const uint32_t* __restrict__ key, uint32_t n, uint32_t k) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (key[mid] < k) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-
 // per segment k < K: first sorted node (seg_node[k], seg_node[K] = end of the kept nodes) and number of chunks (nchunk[K] = 0)
 __global__ void k_sd_segments(const uint32_t* __restrict__ key, uint32_t V, uint32_t K, const uint32_t* __restrict__ vp,
                               uint32_t* __restrict__ seg_node, uint32_t* __restrict__ nchunk) {
@@ -67,30 +61,6 @@ __global__ void k_sd_segments(const uint32_t* __restrict__ key, uint32_t V, uint
   const uint32_t pts = vp[n1] - vp[n0];
   const uint32_t ch = (pts + SD_CHUNK - 1) / SD_CHUNK;
   nchunk[k] = ch > 0 ? ch : 1u;   // (a kept segment holds at least one point; the guard keeps the chunk -> segment search well defined)
-}
-
-__device__ __forceinline__ double sd_wave_sum(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-  return x;
-}
-__device__ __forceinline__ float sd_wave_min(float x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x = fminf(x, __shfl_xor(x, m, 64));
-  return x;
-}
-__device__ __forceinline__ float sd_wave_max(float x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x = fmaxf(x, __shfl_xor(x, m, 64));
-  return x;
-}
-
-// Empty partial record: zero sums and count, +inf min, -inf max
-__device__ __forceinline__ void sd_empty_record(double* __restrict__ rec) {
-  if (threadIdx.x < SD_REC) {
-    const int f = threadIdx.x;
-    rec[f] = f < 9 ? 0.0 : (f < 12 ? __builtin_huge_val() : (f < 15 ? -__builtin_huge_val() : 0.0));
-  }
 }
 
 // One workgroup per chunk of SD_CHUNK virtual points of one segment.  Grid: an upper bound of the number of chunks (floor(Nf / SD_CHUNK) +
@@ -106,7 +76,6 @@ __device__ __forceinline__ void sd_chunk_body(const float* __restrict__ xs, cons
                                               const uint32_t* __restrict__ anchor_pos) {
   __shared__ uint32_t s_vp[SD_CHUNK];    // virtual start of the chunk's nodes
   __shared__ uint32_t s_dl[SD_CHUNK];    // sorted position - virtual position of the same (mod 2^32)
-  __shared__ double s_red[SD_TB / 64][SD_REC];
   const uint32_t c = blockIdx.x;
   SdChunk wk;
   if (!sd_walk(vox_start, ids, vp, seg_node, seg_chunk, K, s_vp, s_dl, wk)) {
@@ -121,49 +90,9 @@ __device__ __forceinline__ void sd_chunk_body(const float* __restrict__ xs, cons
     return;
   }
   const double ax = (double)xs[pa], ay = (double)ys[pa], az = (double)zs[pa];
-  __syncthreads();
-  double sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0, cnt = 0;
-  float mnx = __builtin_huge_valf(), mny = __builtin_huge_valf(), mnz = __builtin_huge_valf();
-  float mxx = -__builtin_huge_valf(), mxy = -__builtin_huge_valf(), mxz = -__builtin_huge_valf();
-#pragma unroll 2
-  for (int it = 0; it < SD_PPT; ++it) {
-    const uint32_t q = a + (uint32_t)it * SD_TB + threadIdx.x;
-    if (q < b) {
-      const uint32_t pos = sd_pos(s_vp, s_dl, m, q);
-      if (OWN) {
-        const int64_t o = (int64_t)perm[pos];
-        if (o < own_first || o >= own_end) continue;
-        cnt += 1.0;
-      }
-      const float x = xs[pos], y = ys[pos], z = zs[pos];
-      mnx = fminf(mnx, x); mny = fminf(mny, y); mnz = fminf(mnz, z);
-      mxx = fmaxf(mxx, x); mxy = fmaxf(mxy, y); mxz = fmaxf(mxz, z);
-      // exact differences (two floats, one double); products and sums in fp64
-      const double dx = (double)x - ax, dy = (double)y - ay, dz = (double)z - az;
-      sx += dx; sy += dy; sz += dz;
-      sxx += dx * dx; sxy += dx * dy; sxz += dx * dz; syy += dy * dy; syz += dy * dz; szz += dz * dz;
-    }
-  }
-  sx = sd_wave_sum(sx); sy = sd_wave_sum(sy); sz = sd_wave_sum(sz);
-  sxx = sd_wave_sum(sxx); sxy = sd_wave_sum(sxy); sxz = sd_wave_sum(sxz); syy = sd_wave_sum(syy); syz = sd_wave_sum(syz); szz = sd_wave_sum(szz);
-  if (OWN) cnt = sd_wave_sum(cnt);
-  mnx = sd_wave_min(mnx); mny = sd_wave_min(mny); mnz = sd_wave_min(mnz);
-  mxx = sd_wave_max(mxx); mxy = sd_wave_max(mxy); mxz = sd_wave_max(mxz);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    double* r = s_red[w];
-    r[0] = sx; r[1] = sy; r[2] = sz; r[3] = sxx; r[4] = sxy; r[5] = sxz; r[6] = syy; r[7] = syz; r[8] = szz;
-    r[9] = mnx; r[10] = mny; r[11] = mnz; r[12] = mxx; r[13] = mxy; r[14] = mxz; r[15] = OWN ? cnt : 0.0;
-  }
-  __syncthreads();
-  if (threadIdx.x < SD_REC) {   // the waves in index order
-    const int f = threadIdx.x;
-    double v = s_red[0][f];
-    if (f < 9 || (OWN && f == 15)) { for (int u = 1; u < SD_TB / 64; ++u) v += s_red[u][f]; }
-    else if (f < 12) { for (int u = 1; u < SD_TB / 64; ++u) v = fmin(v, s_red[u][f]); }
-    else if (f < 15) { for (int u = 1; u < SD_TB / 64; ++u) v = fmax(v, s_red[u][f]); }
-    part[(size_t)c * SD_REC + f] = v;
-  }
+  // the sums, the butterflies and the waves in index order: segpass.hpp (its first barrier closes the staging above)
+  sd_chunk_sums<OWN>(xs, ys, zs, a, b, ax, ay, az, [&](uint32_t q) { return sd_pos(s_vp, s_dl, m, q); }, part + (size_t)c * SD_REC, perm, own_first,
+                     own_end);
 }
 
 __global__ __launch_bounds__(SD_TB) void k_sd_chunks(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
@@ -209,122 +138,7 @@ __global__ __launch_bounds__(256) void k_sd_own_anchor(const uint32_t* __restric
   if (lane == 0) anchor_pos[k] = found;
 }
 
-// One Jacobi rotation that zeroes A[p][q] (Numerical Recipes' jacobi: A' = J^T A J, W' = W J; r = the third index)
-template <int p, int q>
-__device__ __forceinline__ void sd_jacobi_rotate(double (&A)[3][3], double (&W)[3][3]) {
-  constexpr int r = 3 - p - q;
-  const double apq = A[p][q];
-  if (apq == 0.0) return;
-  const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-  const double t = fabs(theta) > 1e150 ? 0.5 / theta : (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-  const double arp = A[r][p], arq = A[r][q];
-  A[p][p] -= t * apq;
-  A[q][q] += t * apq;
-  A[p][q] = 0.0; A[q][p] = 0.0;
-  const double nrp = cs * arp - sn * arq, nrq = sn * arp + cs * arq;
-  A[r][p] = nrp; A[p][r] = nrp; A[r][q] = nrq; A[q][r] = nrq;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double wp = W[i][p], wq = W[i][q];
-    W[i][p] = cs * wp - sn * wq;
-    W[i][q] = sn * wp + cs * wq;
-  }
-}
-
-template <int a, int b>
-__device__ __forceinline__ void sd_order_pair(double (&d)[3], double (&W)[3][3]) {
-  if (d[a] > d[b]) {
-    const double t = d[a]; d[a] = d[b]; d[b] = t;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { const double u = W[i][a]; W[i][a] = W[i][b]; W[i][b] = u; }
-  }
-}
-
-// The partials c0 .. c1 of one segment folded by one wavefront: lane stride, then butterfly; min / max come back as float values.
-// CNT: field 15 (the own-point count of k_sd_chunks_own) too.
-template <bool CNT>
-__device__ __forceinline__ void sd_fold_partials(const double* __restrict__ part, uint32_t c0, uint32_t c1, uint32_t lane, double (&s)[9],
-                                                 double (&mn)[3], double (&mx)[3], double& cnt) {
-#pragma unroll
-  for (int f = 0; f < 9; ++f) s[f] = 0.0;
-#pragma unroll
-  for (int f = 0; f < 3; ++f) { mn[f] = __builtin_huge_val(); mx[f] = -__builtin_huge_val(); }
-  if (CNT) cnt = 0.0;
-  for (uint32_t c = c0 + lane; c < c1; c += 64) {
-    const double* r = part + (size_t)c * SD_REC;
-#pragma unroll
-    for (int f = 0; f < 9; ++f) s[f] += r[f];
-#pragma unroll
-    for (int f = 0; f < 3; ++f) { mn[f] = fmin(mn[f], r[9 + f]); mx[f] = fmax(mx[f], r[12 + f]); }
-    if (CNT) cnt += r[15];
-  }
-#pragma unroll
-  for (int f = 0; f < 9; ++f) s[f] = sd_wave_sum(s[f]);
-  if (CNT) cnt = sd_wave_sum(cnt);
-#pragma unroll
-  for (int f = 0; f < 3; ++f) { mn[f] = (double)sd_wave_min((float)mn[f]); mx[f] = (double)sd_wave_max((float)mx[f]); }
-}
-
-// Row k of the table from a segment's folded moments: n points, n_nodes nodes, min / max, the anchor (a point of the segment, as
-// doubles) and s = sum d, sum d d^T (xx xy xz yy yz zz) with d = p - anchor.  Centroid, population covariance, cyclic Jacobi in fp64,
-// the sign rule and the features.  The one copy of this algebra: k_sd_final (one context) and k_sd_algebra (moments folded over tiles)
-// both call it, so equal moments give equal bytes.
-__device__ __forceinline__ void sd_segment_algebra(size_t k, int64_t n, int32_t n_nodes, const double (&mn)[3], const double (&mx)[3],
-                                                   const double (&anc)[3], const double (&s)[9], int svgs, int64_t* __restrict__ o_npts,
-                                                   int32_t* __restrict__ o_nnodes, float* __restrict__ o_bbox, double* __restrict__ o_cen,
-                                                   double* __restrict__ o_cov, double* __restrict__ o_eval, double* __restrict__ o_evec,
-                                                   float* __restrict__ o_eig8) {
-  o_npts[k] = n;
-  o_nnodes[k] = n_nodes;
-#pragma unroll
-  for (int f = 0; f < 3; ++f) { o_bbox[6 * k + f] = (float)mn[f]; o_bbox[6 * k + 3 + f] = (float)mx[f]; }
-  const double inv = n > 0 ? 1.0 / (double)n : 0.0;   // (n = 0: no point anywhere -- zero moments about the anchor)
-  const double md[3] = {s[0] * inv, s[1] * inv, s[2] * inv};
-#pragma unroll
-  for (int f = 0; f < 3; ++f) o_cen[3 * k + f] = anc[f] + md[f];
-  // population covariance about the mean: E[d d^T] - E[d] E[d]^T, d relative to a point of the segment
-  double cv[6];
-  cv[0] = s[3] * inv - md[0] * md[0]; cv[1] = s[4] * inv - md[0] * md[1]; cv[2] = s[5] * inv - md[0] * md[2];
-  cv[3] = s[6] * inv - md[1] * md[1]; cv[4] = s[7] * inv - md[1] * md[2]; cv[5] = s[8] * inv - md[2] * md[2];
-  if (n <= 1) { for (int f = 0; f < 6; ++f) cv[f] = 0.0; }
-#pragma unroll
-  for (int f = 0; f < 6; ++f) o_cov[6 * k + f] = cv[f];
-  // cyclic Jacobi in fp64 until the off-diagonal part is negligible against the diagonal
-  double A[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
-  double W[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int sweep = 0; sweep < 32; ++sweep) {
-    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-    const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-    if (off == 0.0 || off <= 1e-36 * dia) break;
-    sd_jacobi_rotate<0, 1>(A, W);
-    sd_jacobi_rotate<0, 2>(A, W);
-    sd_jacobi_rotate<1, 2>(A, W);
-  }
-  double d[3] = {A[0][0], A[1][1], A[2][2]};
-  sd_order_pair<0, 1>(d, W);
-  sd_order_pair<1, 2>(d, W);
-  sd_order_pair<0, 1>(d, W);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    // sign: the component of largest magnitude is positive (lowest index on a tie)
-    double best = W[0][j];
-    if (fabs(W[1][j]) > fabs(best)) best = W[1][j];
-    if (fabs(W[2][j]) > fabs(best)) best = W[2][j];
-    if (best < 0.0) { W[0][j] = -W[0][j]; W[1][j] = -W[1][j]; W[2][j] = -W[2][j]; }
-    d[j] = d[j] > 0.0 ? d[j] : 0.0;
-    o_eval[3 * k + j] = d[j];
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) o_evec[9 * k + 3 * r + j] = W[r][j];
-  const float ef[3] = {(float)d[0], (float)d[1], (float)d[2]};
-  float F[8];
-  vm_eigen_features(ef, svgs, F);
-#pragma unroll
-  for (int f = 0; f < 8; ++f) o_eig8[8 * k + f] = F[f];
-}
+// sd_fold_partials and sd_segment_algebra (the one copy of the per-segment algebra, with its Jacobi rotations): segpass.hpp
 
 // one wavefront per segment: fold its partials (lane stride, then butterfly), then everything per segment on lane 0
 __global__ __launch_bounds__(256) void k_sd_final(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,

@@ -341,6 +341,18 @@ struct vgs_ctx {
   DevBuf<uint8_t> rf_mask;
   bool rf_halo_valid = false;
   int64_t rf_band_n = -1;
+  // descriptors and boxes of a caller's per-point labelling (pointseg.hip): computed on every call, nothing cached.  The host variants'
+  // upload (ps_in, which vgs_compare_point_labels shares), keys in | out and sorted positions in | out (Nf words each half), label starts |
+  // chunk counts | first chunks (K + 1 words each), rocprim's storage, the chunk partials and head-flag counts, the two counters of the
+  // key pass, and the K rows the caller's arrays are copied out of: bbox6 | eigen8 in ps_f; centroid3 | cov6 | evals3 | evecs9 | frame9 |
+  // lo3 | hi3 | half3 | center3 in ps_d
+  DevBuf<int32_t> ps_in, ps_nnodes;
+  DevBuf<uint32_t> ps_key, ps_val, ps_seg, ps_nn;
+  DevBuf<uint8_t> ps_tmp;
+  DevBuf<uint64_t> ps_meta;
+  DevBuf<double> ps_part, ps_d;
+  DevBuf<float> ps_f;
+  DevBuf<int64_t> ps_npts;
   DevBuf<uint64_t> counters;  // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 
@@ -531,6 +543,12 @@ vgs_status vgs_stage_merge(vgs_ctx* c);
 vgs_status vgs_clusters_on_device(vgs_ctx* c);   // clusters.hip
 vgs_status vgs_segdesc_on_device(vgs_ctx* c);    // segdesc.hip
 vgs_status vgs_segbox_on_device(vgs_ctx* c, int frame);   // segbox.hip
+// k_sb_frames over K rows of evecs9 / cov6 in HBM, left on the context's stream: the frame rule's one launch site (segbox.hip)
+void sb_launch_frames(vgs_ctx* c, const double* evec, const double* cov, int64_t K, int frame, double* out);
+// a caller's per-point labelling (pointseg.hip): VGS_E_ARG, the message naming the first index and its value, if a label is not below K
+// (one pass on the device); and the host variants' upload into ps_in (*labels_dev = nullptr for n = 0)
+vgs_status vgs_check_label_range(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t n, int64_t K);
+vgs_status vgs_upload_point_labels(vgs_ctx* c, const int32_t* labels_host, int64_t n, const int32_t** labels_dev);
 vgs_status vgs_seggraph_on_device(vgs_ctx* c);   // seggraph.hip
 // tile contexts: halo[v] = label[k] for the voxel v of code[k] that this context holds and does not own, queued on the context's stream
 // (code, label: n entries in HBM; halo: V entries).  One kernel for the graph's table and the refinement's (seggraph.hip)
