@@ -200,7 +200,9 @@ vgs_status vgs_create(const vgs_params* p, vgs_ctx** out) {
             hipEventCreateWithFlags(&c->ev_d2h, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_rb, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_ho, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&c->ev_ho2, hipEventDisableTiming) == hipSuccess;
+            hipEventCreateWithFlags(&c->ev_ho2, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
   for (int i = 0; ok && i < 16; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
   for (int i = 0; ok && i < VGS_T_COUNT; ++i) ok = hipEventCreate(&c->tev[i][0]) == hipSuccess && hipEventCreate(&c->tev[i][1]) == hipSuccess;
   if (!ok) { g_create_err = "vgs_create: hipStreamCreate/hipEventCreate failed"; vgs_destroy(c); return VGS_E_HIP; }   // frees what exists
@@ -263,6 +265,8 @@ void vgs_destroy(vgs_ctx* c) {
   if (c->ev_rb) (void)hipEventDestroy(c->ev_rb);
   if (c->ev_ho) (void)hipEventDestroy(c->ev_ho);
   if (c->ev_ho2) (void)hipEventDestroy(c->ev_ho2);
+  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->ev_d2h) (void)hipEventDestroy(c->ev_d2h);
   delete c;
 }

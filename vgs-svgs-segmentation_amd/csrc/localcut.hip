@@ -951,7 +951,7 @@ vgs_status vgs_stage_localcut(vgs_ctx* c) {
   // workgroup waits for a contiguous hole for milliseconds (measured: 291 class-C voxels took 8.8 ms behind class A).
   // from here on the side streams carry work of this run: a failure below must make the next run wait for them
   c->pl_enabled_at_launch = false;
-  c->lc_tail.gated = false; c->lc_tail.pg_xl_queued = false;
+  c->lc_tail.gated = false; c->lc_tail.pg_xl_queued = false; c->lc_tail.rb_queued = false;
   c->lc_tail.open = true; c->lc_tail.dense = dense; c->lc_tail.grid_f = 0; c->lc_tail.grid_g = GRID_G; c->lc_tail.tail_ms = 0.f;
   VGS_HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
   VGS_HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev[2], 0));
@@ -1185,7 +1185,20 @@ vgs_status vgs_stage_localcut(vgs_ctx* c) {
 // Second half of the stage, called by the merge stage once it has nothing left to do beside the hand-over kernels: waits
 // for them, reads the stage's flags and list lengths back (one copy), finishes lists longer than their fixed grids, and
 // returns the number of rows crossValidation has put off.
-vgs_status vgs_localcut_finish(vgs_ctx* c, unsigned int* n_deferred) {
+// The finish's waits and its read-back, queued without waiting for them: a caller that is about to fill the device with other work (the
+// merge stage's first union pass: 150 k one-wavefront workgroups on URB10M) queues the copy first -- behind them its blit kernel was
+// seen waiting for a slot until the pass was nearly over (profiles/ab_merge_fork.txt).  vgs_localcut_finish on the same stream collects it.
+vgs_status vgs_localcut_finish_queue(vgs_ctx* c, hipStream_t s) {
+  if (!c->lc_tail.open || !c->pin || c->lc_tail.rb_queued) return VGS_OK;
+  VGS_HIP_TRY(c, hipStreamWaitEvent(s, c->ev[4], 0));
+  VGS_HIP_TRY(c, hipStreamWaitEvent(s, c->ev[3], 0));
+  VGS_HIP_TRY(c, hipEventRecord(c->ev[7], s));
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->pin, c->counters.p, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  c->lc_tail.rb_queued = true;
+  return VGS_OK;
+}
+
+vgs_status vgs_localcut_finish(vgs_ctx* c, hipStream_t s, unsigned int* n_deferred) {
   if (n_deferred) *n_deferred = 0;
   if (!c->lc_tail.open) return VGS_OK;
   c->lc_tail.open = false;
@@ -1219,23 +1232,29 @@ vgs_status vgs_localcut_finish(vgs_ctx* c, unsigned int* n_deferred) {
       auto kern = k_localcut<SMALL_M, SMALL_CAP, false>;
       const size_t sm = lc_smem_bytes<SMALL_M, SMALL_CAP, false>();
       VGS_HIP_TRY(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-      hipLaunchKernelGGL(kern, dim3(nw), dim3(LC_TB), sm, c->stream, ids, (int)nw, (const unsigned int*)nullptr, c->adj_key.p, c->adj_cnt.p,
+      hipLaunchKernelGGL(kern, dim3(nw), dim3(LC_TB), sm, s, ids, (int)nw, (const unsigned int*)nullptr, c->adj_key.p, c->adj_cnt.p,
                          c->adj_stride, c->node.p, LP, c->conn.p, cnt, c->evals.p, (uint32_t*)nullptr);
     } else {
       auto kern = k_localcut<LARGE_M, LARGE_CAP, false>;
       const size_t sm = lc_smem_bytes<LARGE_M, LARGE_CAP, false>();
       VGS_HIP_TRY(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-      hipLaunchKernelGGL(kern, dim3(nw), dim3(LC_TB), sm, c->stream, ids, (int)nw, (const unsigned int*)nullptr, c->adj_key.p, c->adj_cnt.p,
+      hipLaunchKernelGGL(kern, dim3(nw), dim3(LC_TB), sm, s, ids, (int)nw, (const unsigned int*)nullptr, c->adj_key.p, c->adj_cnt.p,
                          c->adj_stride, c->node.p, LP, c->conn.p, cnt, c->evals.p, ids_xl);
     }
     return VGS_OK;
   };
-  VGS_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev[4], 0));
-  VGS_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev[3], 0));
-  VGS_HIP_TRY(c, hipEventRecord(c->ev[7], c->stream));
   // one read-back: the kernels' flags (words 0-7), the lengths of the hand-over lists (word 11), the rows put off (word 13)
   unsigned long long hc[64] = {0};   // (words 58-63: the pair lists' pool and the pair-list kernel's counts)
-  VGS_READBACK(c, hc, cnt, sizeof(hc));
+  if (c->lc_tail.rb_queued) {   // (vgs_localcut_finish_queue: the waits and the copy are on stream s already)
+    c->lc_tail.rb_queued = false;
+    VGS_HIP_TRY(c, hipStreamSynchronize(s));
+    memcpy(hc, c->pin, sizeof(hc));
+  } else {
+    VGS_HIP_TRY(c, hipStreamWaitEvent(s, c->ev[4], 0));
+    VGS_HIP_TRY(c, hipStreamWaitEvent(s, c->ev[3], 0));
+    VGS_HIP_TRY(c, hipEventRecord(c->ev[7], s));
+    VGS_READBACK_ON(c, s, hc, cnt, sizeof(hc));
+  }
   const unsigned long long lc_why[4] = {hc[3], hc[4], hc[5], hc[6]};   // (the first words of hc are read again behind the kernels launched below)
   // neighbourhoods queued for the extra-large pair-list instantiation although it was not launched: their rows would never be written
   if (!c->lc_tail.pg_xl_queued && (unsigned int)(hc[56] & 0xffffffffull) != 0u) { c->err = "local cut: voxels queued for a kernel that was not launched"; return VGS_E_STATE; }
@@ -1264,9 +1283,9 @@ vgs_status vgs_localcut_finish(vgs_ctx* c, unsigned int* n_deferred) {
     }
     if (st != VGS_OK) return st;
     if (more) {
-      VGS_HIP_TRY(c, hipEventRecord(c->ev[7], c->stream));
-      VGS_HIP_TRY(c, hipMemcpyAsync(hc, cnt, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-      VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+      VGS_HIP_TRY(c, hipEventRecord(c->ev[7], s));
+      VGS_HIP_TRY(c, hipMemcpyAsync(hc, cnt, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+      VGS_HIP_TRY(c, hipStreamSynchronize(s));
     }
   }
   c->lc_diag[8] = 0;
@@ -1278,13 +1297,13 @@ vgs_status vgs_localcut_finish(vgs_ctx* c, unsigned int* n_deferred) {
     auto kern = k_localcut<XL_M, XL_CAP, false>;
     const size_t sm = lc_smem_bytes<XL_M, XL_CAP, false>();
     VGS_HIP_TRY(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-    VGS_HIP_TRY(c, hipMemsetAsync(cnt + 1, 0, sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(kern, dim3(n_xl), dim3(LC_TB), sm, c->stream, ids_xl, (int)n_xl, (const unsigned int*)nullptr, c->adj_key.p, c->adj_cnt.p,
+    VGS_HIP_TRY(c, hipMemsetAsync(cnt + 1, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(kern, dim3(n_xl), dim3(LC_TB), sm, s, ids_xl, (int)n_xl, (const unsigned int*)nullptr, c->adj_key.p, c->adj_cnt.p,
                        c->adj_stride, c->node.p, LP, c->conn.p, cnt, c->evals.p, (uint32_t*)nullptr);
     VGS_HIP_TRY(c, hipGetLastError());
-    VGS_HIP_TRY(c, hipEventRecord(c->ev[7], c->stream));
-    VGS_HIP_TRY(c, hipMemcpyAsync(hc, cnt, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VGS_HIP_TRY(c, hipEventRecord(c->ev[7], s));
+    VGS_HIP_TRY(c, hipMemcpyAsync(hc, cnt, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    VGS_HIP_TRY(c, hipStreamSynchronize(s));
     c->lc_diag[8] = (int64_t)n_xl;
   }
   if (c->cb_enabled && nf > 0) {
@@ -1295,7 +1314,7 @@ vgs_status vgs_localcut_finish(vgs_ctx* c, unsigned int* n_deferred) {
     unsigned int at = 0;
     for (int k = 0; k < 4; ++k) { L.ids[k] = ids_f + (size_t)k * U; at += nb4[k]; L.end[k] = at; }
     L.ids[4] = ids_g; at += nfg[1]; L.end[4] = at;
-    hipLaunchKernelGGL(k_conn_bits, dim3(at), dim3(64), 0, c->stream, c->lc_pending.p, U, c->adj_cnt.p, c->adj_stride, c->conn.p, c->adj_off.p,
+    hipLaunchKernelGGL(k_conn_bits, dim3(at), dim3(64), 0, s, c->lc_pending.p, U, c->adj_cnt.p, c->adj_stride, c->conn.p, c->adj_off.p,
                        c->cb_R, c->cb_words, c->conn_bits.p, L, 1);
     VGS_HIP_TRY(c, hipGetLastError());
   }

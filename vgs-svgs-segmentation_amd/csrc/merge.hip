@@ -624,7 +624,27 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
                        c->adj_stride, c->conn.p, mutual, c->csize.p, c->parent.p, gt, c->adj_gstride, c->adj_nrank.p, inv_res2,
                        c->lc_tail.open ? c->lc_pending.p : (const uint8_t*)nullptr, c->lc_defer.p, d_ndefer, (const uint32_t*)nullptr, 0,
                        cb_off, cb_lut, cb_bits, c->cb_words, early_union ? c->lc_defer_flag.p : (uint8_t*)nullptr, g_first, owned_early);
+    // The fork (early_union only).  Behind crossValidation's first pass the stage splits in two chains that share no result until the join:
+    //   main stream:  k_compress, k_union_mutual over the rows that are final -- they read the mutual flags of those rows, the put-off
+    //                 flags and `parent`, and write `parent` only; then, behind an event of the side stream, k_union_mutual over the rows
+    //                 put off, once their second crossValidation pass is through;
+    //   side stream:  the local cut's finish (read-back, rest and extra-large launches, connect bits of the handed-over voxels),
+    //                 crossValidation over the rows put off (no first hook: parent == nullptr), closestCheck with its read-backs -- they
+    //                 write the mutual flags, csize and connect bits of put-off and handed-over rows, cc_flags, attach,
+    //                 work_ids[0, n_cand) and counter words 48-53, and never touch `parent`.
+    // Read from the kernels: k_union_mutual loads the first batch of a row's mutual flags together with its skip flag, so for a put-off
+    // row that load may race with the second crossValidation pass -- the loaded bytes are dropped at `if (skipped) return` before any
+    // use (a stale or torn byte of a skipped row decides nothing); `attach` is read only under do_attach, which is 0 here.  The skip flags
+    // and the put-off list are written by the first pass alone.
+    // The side stream is the hand-over kernels' own (stream3, high priority, idle once they end): their last event is stream order there.
+    // The host blocks in the side chain's read-backs while the main stream's unions are already queued.
+    hipStream_t s = c->stream;   // where the chain from the finish to closestCheck goes
     if (early_union) {
+      VGS_HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
+      VGS_HIP_TRY(c, hipStreamWaitEvent(c->stream3, c->ev_fork, 0));
+      s = c->stream3;
+      // (the finish's read-back is queued BEFORE the unions: its copy then runs beside k_compress, not behind k_union_mutual's workgroups)
+      { vgs_status sq = vgs_localcut_finish_queue(c, s); if (sq != VGS_OK) return sq; }
       // The unions of the rows that are final go here, beside the hand-over kernels of the local cut (which leave most of the GPU
       // idle and end the critical path of the stage): pointer jumping over the first hooks, then every mutual edge of a row that
       // was not put off.  The rows put off follow behind their second crossValidation pass, without a first hook (their parents
@@ -637,10 +657,16 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     // ... then the local cut is completed (its flags and list lengths read back) and the rows put off follow
     unsigned int n_defer = 0;
     {
-      vgs_status sf = vgs_localcut_finish(c, &n_defer);
+      vgs_status sf = vgs_localcut_finish(c, s, &n_defer);
       if (sf != VGS_OK) return sf;
     }
     if (c->lc_tail.many) {
+      // (forked: the main stream joins the side chain at once -- the finish's kernels wrote rows this pass reads -- and takes the rest)
+      if (s != c->stream) {
+        VGS_HIP_TRY(c, hipEventRecord(c->ev_join, s));
+        VGS_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+        s = c->stream;
+      }
       // the first pass and its unions did not run (see above) -- or ran in part, for workgroups that started before the word was written:
       // whatever they left (hooks, unions of rows whose flags nobody wrote this run) goes, and crossValidation takes every row now
       hipLaunchKernelGGL(k_merge_init, dim3(nbV), dim3(TB), 0, c->stream, c->parent.p, c->csize.p, c->attach.p, c->cc_flags.p, c->csz.p, V);
@@ -652,9 +678,16 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
       n_defer = 0;
     }
     if (n_defer > 0) {
-      hipLaunchKernelGGL(k_cross, dim3((n_defer + CX_ROWS - 1) / CX_ROWS), dim3(64), 0, c->stream, c->used_ids.p, c->used_rank.p, U, c->adj_key.p, c->adj_cnt.p,
+      hipLaunchKernelGGL(k_cross, dim3((n_defer + CX_ROWS - 1) / CX_ROWS), dim3(64), 0, s, c->used_ids.p, c->used_rank.p, U, c->adj_key.p, c->adj_cnt.p,
                          c->adj_stride, c->conn.p, mutual, c->csize.p, early_union ? (uint32_t*)nullptr : c->parent.p, gt, c->adj_gstride, c->adj_nrank.p, inv_res2,
                          (const uint8_t*)nullptr, c->lc_defer.p, d_ndefer, c->lc_defer.p, (int)n_defer, cb_off, cb_lut, cb_bits, c->cb_words, (uint8_t*)nullptr, LcGate{nullptr, 0u});
+      if (s != c->stream) {
+        // The rows put off get their unions as soon as their flags are final, beside closestCheck: the main stream waits for this pass
+        // only (it runs behind the first union pass there by stream order).  k_union_mutual with do_attach == 0 reads the mutual flags
+        // and `parent`; closestCheck reads and writes neither.  (ev_fork is free again: the side stream's wait for it is queued.)
+        VGS_HIP_TRY(c, hipEventRecord(c->ev_fork, s));
+        VGS_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_fork, 0));
+      }
       if (early_union)
         hipLaunchKernelGGL(k_union_mutual, dim3((n_defer + UM_ROWS - 1) / UM_ROWS), dim3(64), 0, c->stream, c->used_ids.p, U, c->adj_key.p, c->adj_cnt.p,
                            c->adj_stride, mutual, c->attach.p, owned_early, c->parent.p, 0, (const uint8_t*)nullptr, c->lc_defer.p, (int)n_defer, LcGate{nullptr, 0u});
@@ -663,10 +696,12 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     VGS_HIP_TRY(c, c->work_ids.ensure((size_t)U + 16));
     unsigned int* d_ncand = (unsigned int*)(mcnt + 0);
     unsigned int* d_changed = (unsigned int*)(mcnt + 1);
-    hipLaunchKernelGGL(k_cc_candidates, dim3((unsigned)((U + TB - 1) / TB)), dim3(TB), 0, c->stream, c->used_ids.p, U, c->adj_mused.p,
+    // (256 threads also beside the union pass: one-wavefront workgroups were measured there and are slower, profiles/ab_merge_fork.txt)
+    hipLaunchKernelGGL(k_cc_candidates, dim3((unsigned)((U + TB - 1) / TB)), dim3(TB), 0, s, c->used_ids.p, U, c->adj_mused.p,
                        c->csize.p, MP.adjacency_min, c->cc_flags.p, c->work_ids.p, d_ncand);
     // Two host round trips of closestCheck (the number of candidates, the fixed-point flag) hide behind work that does not depend
     // on it: the pointer jumping over the first hooks, and the unions of the mutual edges (single-context runs only)
+    // (not with early_union: there the whole chain runs beside the first unions, on the side stream)
     const bool hide = !c->have_region && vgs_can_split_readback(c) && !early_union;
     if (hide) {
       vgs_status sb = vgs_readback_begin(c, d_ncand, 4);
@@ -676,7 +711,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
       vgs_status se = vgs_readback_end(c, &n_cand, 4);
       if (se != VGS_OK) return se;
     } else {
-      VGS_READBACK(c, &n_cand, d_ncand, 4);
+      VGS_READBACK_ON(c, s, &n_cand, d_ncand, 4);
     }
     if (n_cand > 0) {
       // fixed point of "re-attachment succeeds": passes are queued four at a time, each with its own change counter, and
@@ -684,9 +719,9 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
       // round trip per pass cost more than the passes)
       unsigned int* d_chg4 = (unsigned int*)(mcnt + 4);   // words 4-5: four 32-bit counters
       for (int round = 0; round < 1 << 18; ++round) {
-        VGS_HIP_TRY(c, hipMemsetAsync(d_chg4, 0, 16, c->stream));
+        VGS_HIP_TRY(c, hipMemsetAsync(d_chg4, 0, 16, s));
         for (int q = 0; q < 4; ++q)
-          hipLaunchKernelGGL((k_cc_pass<false>), dim3(n_cand), dim3(64), 0, c->stream, c->work_ids.p, (int)n_cand, c->used_ids.p,
+          hipLaunchKernelGGL((k_cc_pass<false>), dim3(n_cand), dim3(64), 0, s, c->work_ids.p, (int)n_cand, c->used_ids.p,
                              c->adj_key.p, c->adj_cnt.p, c->adj_mused.p, c->adj_stride, c->node.p, c->csize.p, c->cc_flags.p, MP, c->attach.p, d_chg4 + q);
         unsigned int ch = 0;
         if (hide && !united) {
@@ -698,12 +733,17 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
           vgs_status se = vgs_readback_end(c, &ch, 4);
           if (se != VGS_OK) return se;
         } else {
-          VGS_READBACK(c, &ch, d_chg4 + 3, 4);
+          VGS_READBACK_ON(c, s, &ch, d_chg4 + 3, 4);
         }
         if (!ch) break;
       }
-      hipLaunchKernelGGL((k_cc_pass<true>), dim3(n_cand), dim3(64), 0, c->stream, c->work_ids.p, (int)n_cand, c->used_ids.p, c->adj_key.p,
+      hipLaunchKernelGGL((k_cc_pass<true>), dim3(n_cand), dim3(64), 0, s, c->work_ids.p, (int)n_cand, c->used_ids.p, c->adj_key.p,
                          c->adj_cnt.p, c->adj_mused.p, c->adj_stride, c->node.p, c->csize.p, c->cc_flags.p, MP, c->attach.p, d_changed);
+    }
+    if (s != c->stream) {
+      // The join: the main stream takes closestCheck's results (attach, the candidate list) from here.
+      VGS_HIP_TRY(c, hipEventRecord(c->ev_join, s));
+      VGS_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
     }
   } else {
     VGS_HIP_TRY(c, c->conn.ensure(16));

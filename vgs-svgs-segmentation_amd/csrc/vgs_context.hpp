@@ -229,6 +229,7 @@ struct vgs_ctx {
   bool pl_enabled = false;
   bool pl_enabled_at_launch = false;   // this run queued the pair-list chain for its hand-overs (stream4 joins stream3 before the stage's last event)
   hipEvent_t ev_ho = nullptr, ev_ho2 = nullptr;   // hand-over lists built / pair-list chain done
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // merge stage: crossValidation's first pass done / the side chain beside the first unions done
   float pl_w_ring = 0.0f;      // PairLists::w_ring of this run
 
   // local cut / merge
@@ -239,7 +240,7 @@ struct vgs_ctx {
   DevBuf<uint8_t> lc_pending;
   DevBuf<uint8_t> lc_defer_flag;   // per row: the first pass of crossValidation put it off (written by every row of that pass)
   DevBuf<uint32_t> lc_defer;
-  struct { bool open = false; bool dense = true; bool gated = false; /* merge's first pass looks at LcGate's word */ bool many = false; /* ... and found LC_MANY */ unsigned int grid_f = 0, grid_g = 0, nabc[5] = {0, 0, 0, 0, 0}; float tail_ms = 0.f; bool pg_xl_queued = false; /* class D's pair-list kernel queued for the extra-large one, which was launched */ } lc_tail;
+  struct { bool open = false; bool dense = true; bool gated = false; /* merge's first pass looks at LcGate's word */ bool many = false; /* ... and found LC_MANY */ unsigned int grid_f = 0, grid_g = 0, nabc[5] = {0, 0, 0, 0, 0}; float tail_ms = 0.f; bool pg_xl_queued = false; /* class D's pair-list kernel queued for the extra-large one, which was launched */ bool rb_queued = false; /* vgs_localcut_finish_queue has queued the finish's read-back */ } lc_tail;
   int64_t lc_diag[16] = {0};   // vgs_get_schedule_counters[_ex]
   DevBuf<float> lc_ctab;      // screening table of the dense hand-over kernels (localcut.hip: lc_screen_table)
   float lc_ctab_key[8] = {0}, lc_ctab_scale = 0.0f;
@@ -426,6 +427,20 @@ static inline vgs_status vgs_readback(vgs_ctx* c, void* dst, const void* src_dev
   memcpy(dst, c->pin, bytes);
   return VGS_OK;
 }
+// The same on a stream of the caller's choice: only that stream is waited for, whatever else is queued on the others (the merge stage
+// reads closestCheck's counters on a side stream while the main stream runs the first unions).  Lower half of the pinned scratch only:
+// the upper half may hold a split read-back (below) that has not been collected yet.
+static inline vgs_status vgs_readback_on(vgs_ctx* c, hipStream_t s, void* dst, const void* src_dev, size_t bytes) {
+  if (bytes > 2048 || !c->pin) {
+    VGS_HIP_TRY(c, hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, s));
+    VGS_HIP_TRY(c, hipStreamSynchronize(s));
+    return VGS_OK;
+  }
+  VGS_HIP_TRY(c, hipMemcpyAsync(c->pin, src_dev, bytes, hipMemcpyDeviceToHost, s));
+  VGS_HIP_TRY(c, hipStreamSynchronize(s));
+  memcpy(dst, c->pin, bytes);
+  return VGS_OK;
+}
 // Longest row of connect bits the kernels hold in LDS: 624 words = a cube of 27 cells a side = balls of up to 13 voxels (the edge list of
 // the smallest one-wavefront class, 312 keys of 8 bytes, is where its row is put together).  Wider balls (up to the engine's own limit
 // of graph_size / voxel_size = 12 ... 15 by rounding) keep crossValidation's search in the neighbour's row.  (Round 4: 256 words, 9 voxels --
@@ -440,6 +455,7 @@ __device__ __forceinline__ uint32_t vgs_cb_index(uint32_t p, int R) {
 }
 #endif
 #define VGS_READBACK(ctx, dst, src, bytes) do { vgs_status _s = vgs_readback((ctx), (dst), (src), (bytes)); if (_s != VGS_OK) return _s; } while (0)
+#define VGS_READBACK_ON(ctx, s, dst, src, bytes) do { vgs_status _s = vgs_readback_on((ctx), (s), (dst), (src), (bytes)); if (_s != VGS_OK) return _s; } while (0)
 
 // The same in two halves (round 4): the copy is queued NOW, the host collects it LATER.  Kernels launched in between that do not need
 // the number run while the host makes its round trip (20-30 us of an idle GPU per read-back otherwise: profiles/r04_step_timeline.txt).
@@ -538,7 +554,8 @@ vgs_status vgs_pairlists_build(vgs_ctx* c, hipStream_t strm, const uint32_t* con
                                bool big_rows_too);
 vgs_status vgs_stage_localcut(vgs_ctx* c);   // launches everything; its hand-over kernels may still run when it returns
 vgs_status vgs_ensure_point_labels(vgs_ctx* c);   // merge.hip
-vgs_status vgs_localcut_finish(vgs_ctx* c, unsigned int* n_deferred);  // waits for them, checks the stage's flags (called by the merge stage)
+vgs_status vgs_localcut_finish_queue(vgs_ctx* c, hipStream_t s);  // queues the finish's waits and read-back on stream s without waiting (optional; the finish collects it)
+vgs_status vgs_localcut_finish(vgs_ctx* c, hipStream_t s, unsigned int* n_deferred);  // waits for them on stream s, checks the stage's flags (called by the merge stage)
 vgs_status vgs_stage_merge(vgs_ctx* c);
 vgs_status vgs_clusters_on_device(vgs_ctx* c);   // clusters.hip
 vgs_status vgs_segdesc_on_device(vgs_ctx* c);    // segdesc.hip
