@@ -581,6 +581,9 @@ bool vgs_unused_are_inert(const vgs_params& p) {
 
 static vgs_status build_hash_and_offsets(vgs_ctx* c, float* r2_out) {
   if (!c->bricks_ready) {   // (the features stage usually has queued it behind its read-back)
+    // used mask from the node records, not from the features stage's flag array: that is scratch (head_flag) which the merge stage and
+    // the boundary records reuse, and this build also serves a later adjacency stage (vgs_segment after a parameter change, tiles)
+    { vgs_status js = vgs_front_join(c); if (js != VGS_OK) return js; }   // (the records may still be on their way on the side stream)
     vgs_status bs = vgs_build_bricks(c, c->node.p);
     if (bs != VGS_OK) return bs;
   }

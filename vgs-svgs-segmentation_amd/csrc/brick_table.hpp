@@ -35,8 +35,10 @@ __device__ __forceinline__ int brick_local(uint32_t nx, uint32_t ny, uint32_t nz
 // sorted by Morton code, so the voxels of a brick are neighbours in the array: a wavefront first ORs the bits of each run
 // of equal brick keys among its lanes (segmented scan, six shuffle steps) and only the last lane of a run goes to the
 // table -- about nine times fewer probes and atomics than one insert per voxel.
-static __global__ void k_brick_insert(const uint64_t* __restrict__ vox_code, const NodeRec* __restrict__ node, int64_t V,
-                               Brick* __restrict__ table, uint32_t hbits) {
+// The used mask comes from used_flag (one word per voxel: the features stage's flags, 4 bytes of every 64-byte sector fetched) or, where
+// that scratch may have been reused since, from the node records' VGS_F_EIG (set exactly for the used voxels); both null: no used mask.
+static __global__ void k_brick_insert(const uint64_t* __restrict__ vox_code, const NodeRec* __restrict__ node, const uint32_t* __restrict__ used_flag,
+                               int64_t V, Brick* __restrict__ table, uint32_t hbits) {
   const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
   unsigned long long key = 0ull, occ = 0ull, usd = 0ull;   // key 0 = no voxel in this lane
@@ -45,7 +47,7 @@ static __global__ void k_brick_insert(const uint64_t* __restrict__ vox_code, con
     const uint64_t code = vox_code[v];
     key = brick_key(vm_compact21(code >> 2), vm_compact21(code >> 1), vm_compact21(code));
     occ = 1ull << (code & 63ull);  // == brick_local of the same coordinates
-    if (node && (node[v].flags & VGS_F_EIG)) usd = occ;
+    if (used_flag ? (used_flag[v] != 0u) : (node && (node[v].flags & VGS_F_EIG))) usd = occ;
     first = (uint32_t)v;
   }
   for (int o = 1; o < 64; o <<= 1) {
@@ -87,7 +89,8 @@ __device__ __forceinline__ int brick_find(const Brick* __restrict__ table, uint3
 }
 
 
-// builds the table for the context's current voxel set (vox_code, V) in c->hkey; node may be null (no used mask)
+// builds the table for the context's current voxel set (vox_code, V) in c->hkey; the used mask from used_flag if given, else from node,
+// else none (k_brick_insert)
 // the empty table: key / occupancy / used = 0, first = 0xffffffff (a minimum over the brick's voxel ids) -- one kernel writing whole 32-byte
 // entries (round 5: was a fill plus a strided 2-D fill of the `first` words, 25 us in front of k_brick_insert at the bench scene)
 static __global__ void k_brick_clear(Brick* __restrict__ table, size_t H) {
@@ -98,7 +101,7 @@ static __global__ void k_brick_clear(Brick* __restrict__ table, size_t H) {
   p[1] = make_ulonglong2(0ull, 0x00000000ffffffffull);   // used = 0; first = 0xffffffff, pad = 0
 }
 
-static inline vgs_status vgs_build_bricks(vgs_ctx* c, const NodeRec* node) {
+static inline vgs_status vgs_build_bricks(vgs_ctx* c, const NodeRec* node, const uint32_t* used_flag = nullptr) {
   const int64_t V = c->V;
   // The number of bricks is not known without a pass; it is at most V (voxels that sit alone in their bricks: a lattice of voxels more
   // than four cells apart).  The probe loops of k_brick_insert and brick_find end at an empty slot only, so the table must hold more
@@ -109,7 +112,8 @@ static inline vgs_status vgs_build_bricks(vgs_ctx* c, const NodeRec* node) {
   const size_t H = (size_t)1 << hbits;
   VGS_HIP_TRY(c, c->hkey.ensure(H * (sizeof(Brick) / 8)));
   hipLaunchKernelGGL(k_brick_clear, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, c->stream, (Brick*)c->hkey.p, H);
-  hipLaunchKernelGGL(k_brick_insert, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, c->stream, c->vox_code.p, node, V, (Brick*)c->hkey.p, hbits);
+  hipLaunchKernelGGL(k_brick_insert, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, c->stream, c->vox_code.p, node, used_flag, V, (Brick*)c->hkey.p,
+                     hbits);
   return VGS_OK;
 }
 

@@ -202,7 +202,9 @@ vgs_status vgs_create(const vgs_params* p, vgs_ctx** out) {
             hipEventCreateWithFlags(&c->ev_ho, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_ho2, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
+            hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&c->ev_ff_fork, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&c->ev_ff_join, hipEventDisableTiming) == hipSuccess;
   for (int i = 0; ok && i < 16; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
   for (int i = 0; ok && i < VGS_T_COUNT; ++i) ok = hipEventCreate(&c->tev[i][0]) == hipSuccess && hipEventCreate(&c->tev[i][1]) == hipSuccess;
   if (!ok) { g_create_err = "vgs_create: hipStreamCreate/hipEventCreate failed"; vgs_destroy(c); return VGS_E_HIP; }   // frees what exists
@@ -267,6 +269,8 @@ void vgs_destroy(vgs_ctx* c) {
   if (c->ev_ho2) (void)hipEventDestroy(c->ev_ho2);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+  if (c->ev_ff_fork) (void)hipEventDestroy(c->ev_ff_fork);
+  if (c->ev_ff_join) (void)hipEventDestroy(c->ev_ff_join);
   if (c->ev_d2h) (void)hipEventDestroy(c->ev_d2h);
   delete c;
 }
@@ -396,7 +400,9 @@ static vgs_status do_features(vgs_ctx* c, bool wait) {
 static vgs_status do_adjacency(vgs_ctx* c, bool wait) {
   if (!c) return VGS_E_ARG;
   if (c->stage < ST_FEATURES) { c->err = "vgs_adjacency: attributes missing"; return VGS_E_STATE; }
-  vgs_status s = timed(c, VGS_T_ADJACENCY, [&] { return vgs_stage_adjacency(c); }, wait);
+  // (vgs_run's front fork: the main stream joins the side chain behind the adjacency rows, inside this stage's clock, so that the stage
+  // clocks go on tiling the main stream; k_near_lists of the local cut is the first reader of the node records)
+  vgs_status s = timed(c, VGS_T_ADJACENCY, [&] { vgs_status sa = vgs_stage_adjacency(c); return sa != VGS_OK ? sa : vgs_front_join(c); }, wait);
   if (s == VGS_OK) c->stage = ST_ADJACENCY;
   return s;
 }
@@ -430,10 +436,18 @@ vgs_status vgs_run(vgs_ctx* c) {
     }
     return svgs_segment(c);
   }
+  // Front fork: the voxelize stage leaves the gather of the points to the features stage, which sends it and k_features to stream2 once
+  // the voxel table, the used flags and the brick table are queued here; this stream goes on with the adjacency rows; do_adjacency joins.  VGS_NO_OVERLAP and
+  // the single-stage entry points keep every kernel on this stream.  A sequence cut short waits for the side stream on the host.
   vgs_status s;
-  if ((s = do_voxelize(c, false)) != VGS_OK) return s;
-  if ((s = do_features(c, false)) != VGS_OK) return s;
-  if ((s = do_adjacency(c, false)) != VGS_OK) return s;
+  c->ff_want = vgs_can_split_readback(c) && !c->K.no_overlap;
+  s = do_voxelize(c, false);
+  c->ff_want = false;
+  if (s == VGS_OK) s = do_features(c, false);
+  c->ff_pending = false;   // (no voxel: nothing reads the points that were not gathered)
+  if (s == VGS_OK) s = do_adjacency(c, false);
+  vgs_front_abandon(c);   // (open only after an error: do_adjacency has joined)
+  if (s != VGS_OK) return s;
   if ((s = vgs_segment(c)) != VGS_OK) return s;
   c->times[VGS_T_TOTAL] = c->times[VGS_T_VOXELIZE] + c->times[VGS_T_FEATURES] + c->times[VGS_T_ADJACENCY] + c->times[VGS_T_LOCALCUT] +
                           c->times[VGS_T_MERGE];

@@ -24,7 +24,7 @@ template <int TB>
 __global__ __launch_bounds__(TB) void k_features(const float* __restrict__ xs, const float* __restrict__ ys,
                                                       const float* __restrict__ zs, const uint32_t* __restrict__ vox_start,
                                                       int64_t V, int points_min, int svgs, const uint64_t* __restrict__ vox_code,
-                                                      NodeRec* __restrict__ node, uint32_t* __restrict__ used_flag) {
+                                                      NodeRec* __restrict__ node) {
   __shared__ float lx[FEAT_TILE], ly[FEAT_TILE], lz[FEAT_TILE];
   const int64_t v0 = (int64_t)blockIdx.x * TB;
   const int64_t v = v0 + threadIdx.x;
@@ -104,7 +104,15 @@ __global__ __launch_bounds__(TB) void k_features(const float* __restrict__ xs, c
     r.flags = fl;
   }
   node[v] = r;
-  used_flag[v] = used ? 1u : 0u;
+}
+
+// Whether a voxel is used is a function of the voxel table alone (the same test as k_features'): the flags, their scan, the compaction
+// and the brick table do not wait for the node records.
+__global__ void k_used_flags(const uint32_t* __restrict__ vox_start, int64_t V, int points_min, uint32_t* __restrict__ used_flag) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const int cnt = (int)(vox_start[v + 1] - vox_start[v]);
+  used_flag[v] = (cnt > points_min) ? 1u : 0u;
 }
 
 __global__ void k_compact_used(const uint32_t* __restrict__ used_flag, const uint32_t* __restrict__ excl, int64_t V,
@@ -126,12 +134,20 @@ vgs_status vgs_stage_features(vgs_ctx* c) {
   uint32_t* used_flag = c->head_flag.p;  // free after voxelize
   uint32_t* excl = c->perm_a.p;
   const unsigned nb = (unsigned)((V + FEAT_TB - 1) / FEAT_TB);
-  if (c->P.method == 3)
-    hipLaunchKernelGGL(k_features<64>, dim3((unsigned)((V + 63) / 64)), dim3(64), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, V,
-                       -1 /* every supervoxel is used (SS:1288) */, 1, c->vox_code.p, c->node.p, used_flag);
-  else
-    hipLaunchKernelGGL(k_features<FEAT_TB>, dim3(nb), dim3(FEAT_TB), 0, c->stream, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, V,
-                       c->P.points_min, 0, c->vox_code.p, c->node.p, used_flag);
+  const int points_min = (c->P.method == 3) ? -1 /* every supervoxel is used (SS:1288) */ : c->P.points_min;
+  // k_features on stream s.  Front fork of vgs_run (c->ff_pending, set by the voxelize stage; capi.hip): not here but on the side
+  // stream behind the brick table's kernels (below), so that this stream reaches the adjacency rows without waiting for the gather.
+  auto launch_features = [&](hipStream_t s) {
+    if (c->P.method == 3)
+      hipLaunchKernelGGL(k_features<64>, dim3((unsigned)((V + 63) / 64)), dim3(64), 0, s, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, V, points_min, 1,
+                         c->vox_code.p, c->node.p);
+    else
+      hipLaunchKernelGGL(k_features<FEAT_TB>, dim3(nb), dim3(FEAT_TB), 0, s, c->xs.p, c->ys.p, c->zs.p, c->vox_start.p, V, points_min, 0,
+                         c->vox_code.p, c->node.p);
+  };
+  const bool fork = c->ff_pending && c->P.method == 2 && vgs_can_split_readback(c);
+  if (!fork) launch_features(c->stream);
+  hipLaunchKernelGGL(k_used_flags, dim3(nb), dim3(FEAT_TB), 0, c->stream, c->vox_start.p, V, points_min, used_flag);
   size_t bytes = 0;
   VGS_HIP_TRY(c, rocprim::exclusive_scan(nullptr, bytes, used_flag, excl, 0u, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
   VGS_HIP_TRY(c, c->sort_tmp.ensure(bytes));
@@ -145,7 +161,14 @@ vgs_status vgs_stage_features(vgs_ctx* c) {
     // the brick table of the adjacency stage needs the voxel codes and the used flags, not the count: it is built while the host
     // fetches the count (vgs_stage_adjacency finds bricks_ready and skips its own build)
     { vgs_status sb = vgs_readback_begin(c, d_nu, 8); if (sb != VGS_OK) return sb; }
-    { vgs_status bs = vgs_build_bricks(c, c->node.p); if (bs != VGS_OK) return bs; }
+    { vgs_status bs = vgs_build_bricks(c, nullptr, used_flag); if (bs != VGS_OK) return bs; }   // (the flags are still in place here)
+    if (fork) {
+      // the gather of the points and k_features, on the side stream from here: beside the adjacency kernels, which work on-chip.  (Any
+      // earlier and the gather, which fills the device, holds this stream's small kernels back until it ends: profiles/ab_front_fork.txt)
+      c->ff_pending = false;
+      { vgs_status sf = vgs_front_fork(c); if (sf != VGS_OK) return sf; }
+      launch_features(c->stream2);
+    }
     c->bricks_ready = true;
     { vgs_status se = vgs_readback_end(c, &nu, 8); if (se != VGS_OK) return se; }
   } else {

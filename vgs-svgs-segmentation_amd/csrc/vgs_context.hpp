@@ -145,6 +145,12 @@ struct vgs_ctx {
   hipEvent_t ev_rb = nullptr;    // split read-backs (vgs_readback_begin / _end)
   bool gathered = false;         // voxelize: the leaf-order gather was queued behind the count read-back
   bool bricks_ready = false;     // the features stage has already queued the brick table of this voxel table (behind its read-back)
+  // front fork (vgs_run, VGS route): the gather of the points and k_features run on stream2 beside the voxel table, the used flags, the
+  // brick table and the adjacency rows on the main stream
+  bool ff_want = false;          // vgs_run asks the voxelize stage to leave the gather to the fork
+  bool ff_pending = false;       // ... which it did: the features stage forks behind the brick table (vgs_front_fork)
+  bool ff_open = false;          // stream2 carries work of this run that the main stream has not joined yet (vgs_front_join)
+  hipEvent_t ev_ff_fork = nullptr, ev_ff_join = nullptr;   // the brick table's kernels queued on the main stream / side chain done
   bool staged = false;         // a cloud is on its way into xyz_buf[1 - xyz_cur]
   int64_t staged_n = 0;
   int staged_stride = 12;
@@ -473,6 +479,22 @@ static inline vgs_status vgs_readback_end(vgs_ctx* c, void* dst, size_t bytes) {
 }
 static inline bool vgs_can_split_readback(const vgs_ctx* c) { return c->pin != nullptr && c->ev_rb != nullptr; }
 
+// Front fork: the main stream waits for what stream2 carries (the gather, k_features); nothing is queued on stream2 behind it until the
+// local cut.  vgs_front_abandon is the same for a stage sequence that is cut short (an error, an early return): the host waits, so that
+// the next cloud cannot overwrite perm_b, xs/ys/zs or node under a running kernel.
+static inline vgs_status vgs_front_join(vgs_ctx* c) {
+  if (!c->ff_open) return VGS_OK;
+  VGS_HIP_TRY(c, hipEventRecord(c->ev_ff_join, c->stream2));   // (on an error ff_open stays set: the caller abandons)
+  VGS_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_ff_join, 0));
+  c->ff_open = false;
+  return VGS_OK;
+}
+static inline void vgs_front_abandon(vgs_ctx* c) {
+  if (!c->ff_open) return;
+  c->ff_open = false;
+  (void)hipStreamSynchronize(c->stream2);
+}
+
 // The decomposition of the per-segment passes (segdesc.hip, segbox.hip, segfield.hip): chunks of SD_CHUNK virtual points that never cross a segment.
 // sd_prepare (segdesc.hip) runs steps 1-2 of segdesc.hip's header for labels 0 .. K-1 -- sorted node ids, virtual positions, per segment
 // its first sorted node and first chunk, pointers into the sd_* scratch -- and gives the grid bound of the chunk kernels.
@@ -542,6 +564,7 @@ void vgs_read_env_knobs(vgs_ctx* c);   // capi.hip; called by vgs_create only
 
 // stage implementations (one .hip file each)
 vgs_status vgs_stage_voxelize(vgs_ctx* c);
+vgs_status vgs_front_fork(vgs_ctx* c);   // voxelize.hip: the gather of the points goes to stream2 (vgs_run's front fork)
 vgs_status vgs_stage_features(vgs_ctx* c);
 vgs_status vgs_stage_adjacency(vgs_ctx* c);
 vgs_status vgs_run_adjacency(vgs_ctx* c, bool full, uint64_t* out_key, uint32_t* out_cnt, uint32_t* out_nall, float r2, const uint32_t* ids = nullptr,

@@ -412,6 +412,20 @@ __global__ void k_gather_points(const float* __restrict__ xyz, int stride_f, con
 // ---------------------------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------------------------
+// Front fork (vgs_run): the leaf-order gather of the points, and k_features behind it (features.hip), leave this stream for stream2,
+// behind everything queued here so far.  All N positions are gathered (the non-finite points sit at the tail of the order; their slots
+// are never read).  From here until vgs_front_join the side stream owns xs/ys/zs and node; it reads xyz, perm_b, vox_start and vox_code,
+// which this stream leaves alone.
+vgs_status vgs_front_fork(vgs_ctx* c) {
+  const int TB = 256;
+  VGS_HIP_TRY(c, hipEventRecord(c->ev_ff_fork, c->stream));
+  VGS_HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_ff_fork, 0));
+  c->ff_open = true;
+  hipLaunchKernelGGL(k_gather_points, dim3((unsigned)((c->N + TB - 1) / TB)), dim3(TB), 0, c->stream2, c->xyz, c->stride_f, c->perm_b.p, c->N, c->xs.p,
+                     c->ys.p, c->zs.p);
+  return VGS_OK;
+}
+
 // Sequential semantics, parallel execution: only points that fall outside the current box change it, so the
 // device finds the next such point and the host replays PCL's growth rule for it.
 vgs_status vgs_grow_box_from(vgs_ctx* c, OctreeBox& box, bool record_epochs) {
@@ -516,17 +530,24 @@ static vgs_status voxelize_sorted_table(vgs_ctx* c) {
   size_t tmp_bytes = 0;
   VGS_HIP_TRY(c, sort_pairs(nullptr, tmp_bytes));
   VGS_HIP_TRY(c, c->sort_tmp.ensure(tmp_bytes));
-  VGS_HIP_TRY(c, sort_pairs(c->sort_tmp.p, tmp_bytes));
-  // sorted: code_b, perm_b (packed keys: perm_b is written by pass 1)
+  const bool fork = c->ff_want && vgs_can_split_readback(c);
   const int64_t n_tiles = (N + VR_TILE - 1) / VR_TILE;
   VGS_HIP_TRY(c, c->vox_tile.ensure((size_t)(2 * n_tiles)));
+  if (fork) {   // the gather is left to the features stage, which sends it to the side stream (vgs_front_fork)
+    VGS_HIP_TRY(c, c->xs.ensure(N + 1)); VGS_HIP_TRY(c, c->ys.ensure(N + 1)); VGS_HIP_TRY(c, c->zs.ensure(N + 1));
+    c->gathered = true; c->ff_pending = true;
+  }
+  VGS_HIP_TRY(c, sort_pairs(c->sort_tmp.p, tmp_bytes));
+  // sorted: code_b, perm_b (packed keys: perm_b is written by pass 1)
   uint32_t* tile_heads = c->vox_tile.p;            // after k_tile_offsets: heads in front of the tile
   uint32_t* tile_valid = c->vox_tile.p + n_tiles;
   unsigned long long* d_cnt = (unsigned long long*)c->counters.p;   // number of finite points, number of voxels
   hipLaunchKernelGGL((k_run_counts<KeyT>), dim3((unsigned)n_tiles), dim3(VR_TB), 0, c->stream, code_b, N, pack_shift, c->perm_b.p, tile_heads, tile_valid);
   hipLaunchKernelGGL(k_tile_offsets, dim3(1), dim3(1024), 0, c->stream, tile_heads, tile_valid, n_tiles, d_cnt);
   unsigned long long h2[2] = {0, 0};
-  if (vgs_can_split_readback(c)) {
+  if (fork) {
+    VGS_READBACK(c, h2, d_cnt, sizeof(h2));
+  } else if (vgs_can_split_readback(c)) {
     // the leaf-order gather of the points needs the sorted order only, not the counts: it runs while the host fetches them.  All N
     // positions are gathered (the non-finite points sit at the tail of the order; their slots are never read).
     { vgs_status sb = vgs_readback_begin(c, d_cnt, sizeof(h2)); if (sb != VGS_OK) return sb; }
