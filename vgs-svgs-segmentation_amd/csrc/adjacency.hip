@@ -700,7 +700,7 @@ vgs_status vgs_run_adjacency(vgs_ctx* c, bool full, uint64_t* out_key, uint32_t*
   if (c->n_off <= 1024 && !full && c->adj_mask_nb > 0 && gt && !c->K.no_adjmasks) {
     // hot path: candidates from the brick occupancy masks; rows it cannot take go through the general kernel
     VGS_HIP_TRY(c, c->work_ids.ensure(2 * (size_t)U + 16)); VGS_HIP_TRY(c, c->counters.ensure(64));
-    unsigned int* d_nredo = (unsigned int*)(c->counters.p + 40);
+    unsigned int* d_nredo = (unsigned int*)(c->counters.p + CW_ADJ_N1);
     VGS_HIP_TRY(c, hipMemsetAsync(d_nredo, 0, 8, c->stream));
 #define LAUNCH_ADJM(NBV)                                                                                                          \
     hipLaunchKernelGGL((k_adjacency_masks<240, NBV, 5>), dim3(vgs_xcd_grid(U)), dim3(64), 0, c->stream, c->vox_code.p, row_ids, U,  \
@@ -726,8 +726,8 @@ vgs_status vgs_run_adjacency(vgs_ctx* c, bool full, uint64_t* out_key, uint32_t*
     // balls of up to 12 voxels (config 2: ten): candidates from the occupancy masks of 7 x 7 x 7 bricks -- a planar neighbourhood
     // occupies 305 of the 4189 ball cells (up to 832 occupied cells are taken as candidates: the unused voxels count too); rows with more candidates, or more than 512 survivors, go down the general kernel's two passes
     VGS_HIP_TRY(c, c->work_ids.ensure(2 * (size_t)U + 16)); VGS_HIP_TRY(c, c->counters.ensure(64));
-    unsigned int* d_n1 = (unsigned int*)(c->counters.p + 40);
-    unsigned int* d_n2 = (unsigned int*)(c->counters.p + 41);
+    unsigned int* d_n1 = (unsigned int*)(c->counters.p + CW_ADJ_N1);
+    unsigned int* d_n2 = (unsigned int*)(c->counters.p + CW_ADJ_N2);
     VGS_HIP_TRY(c, hipMemsetAsync(d_n1, 0, 16, c->stream));
     uint32_t* list1 = c->work_ids.p;
     uint32_t* list2 = c->work_ids.p + U;
@@ -748,7 +748,7 @@ vgs_status vgs_run_adjacency(vgs_ctx* c, bool full, uint64_t* out_key, uint32_t*
     // A list for every lattice offset (72 KB of LDS) leaves two wavefronts per CU; surfaces fill a fraction of the ball,
     // so the first pass runs with 2048 slots (18 KB) and hands rows that overflow to a second pass over a device-side list
     VGS_HIP_TRY(c, c->work_ids.ensure((size_t)U + 16)); VGS_HIP_TRY(c, c->counters.ensure(64));
-    unsigned int* d_nredo = (unsigned int*)(c->counters.p + 40);
+    unsigned int* d_nredo = (unsigned int*)(c->counters.p + CW_ADJ_N1);
     VGS_HIP_TRY(c, hipMemsetAsync(d_nredo, 0, 4, c->stream));
     if (full) LAUNCH_ADJ(2048, true, vgs_xcd_grid(U), nullptr, d_nredo, c->work_ids.p); else LAUNCH_ADJ(2048, false, vgs_xcd_grid(U), nullptr, d_nredo, c->work_ids.p);
     const unsigned int g2 = (unsigned int)(U < 4096 ? U : 4096);   // the grid strides over the list

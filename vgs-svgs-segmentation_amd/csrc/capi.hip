@@ -81,7 +81,7 @@ void vgs_read_env_knobs(vgs_ctx* c) {
   k.a1_max = geti("VGS_A1MAX", k.a1_max); k.shell0 = getf("VGS_SHELL0", k.shell0); k.cap_frac = getf("VGS_CAPFRAC", k.cap_frac);
   k.dbg_stop = geti("VGS_DBG_STOP", k.dbg_stop); k.max_rounds = geti("VGS_ROUNDS", k.max_rounds); k.dbg_max_m = geti("VGS_DBG_MAXM", k.dbg_max_m); k.dbg_xl_from = geti("VGS_DBG_XL_FROM", k.dbg_xl_from);
   k.near_min_own = geti("VGS_NEARMINOWN", k.near_min_own); k.fv_blocks = geti("VGS_FV_BLOCKS", k.fv_blocks); k.only_class = geti("VGS_ONLY_CLASS", k.only_class);
-  k.no_dense = has("VGS_NO_DENSE"); k.no_overlap = has("VGS_NO_OVERLAP"); k.no_near = has("VGS_NO_NEAR"); k.no_adjmasks = has("VGS_NO_ADJMASKS"); k.no_connbits = has("VGS_NO_CONNBITS"); k.no_pg_xl = has("VGS_NO_PG_XL"); k.no_sort32 = has("VGS_NO_SORT32"); k.no_pairlists = has("VGS_NO_PAIRLISTS"); k.no_vote = has("VGS_NO_VOTE"); k.vote_force = geti("VGS_VOTE_FORCE", 0); k.cross_lds_kb = geti("VGS_CROSS_LDS", k.cross_lds_kb); { int vp = geti("VGS_VOTE_PERIOD", k.vote_period); if (vp >= 2 && vp <= 4096 && (vp & (vp - 1)) == 0) k.vote_period = vp; } k.pg_wide = geti("VGS_PG_WIDE", k.pg_wide); k.pg_wide_frac = geti("VGS_PG_WIDEFRAC", k.pg_wide_frac); k.pg_min_frac = geti("VGS_PG_MINFRAC", k.pg_min_frac); k.ho_grid = geti("VGS_HO_GRID", k.ho_grid);
+  k.no_dense = has("VGS_NO_DENSE"); k.no_overlap = has("VGS_NO_OVERLAP"); k.no_near = has("VGS_NO_NEAR"); k.no_adjmasks = has("VGS_NO_ADJMASKS"); k.no_connbits = has("VGS_NO_CONNBITS"); k.no_pg_xl = has("VGS_NO_PG_XL"); k.no_sort32 = has("VGS_NO_SORT32"); k.no_pairlists = has("VGS_NO_PAIRLISTS"); k.no_vote = has("VGS_NO_VOTE"); k.cross_lds_kb = geti("VGS_CROSS_LDS", k.cross_lds_kb); { int vp = geti("VGS_VOTE_PERIOD", k.vote_period); if (vp >= 2 && vp <= 4096 && (vp & (vp - 1)) == 0) k.vote_period = vp; } k.pg_wide = geti("VGS_PG_WIDE", k.pg_wide); k.pg_wide_frac = geti("VGS_PG_WIDEFRAC", k.pg_wide_frac); k.pg_min_frac = geti("VGS_PG_MINFRAC", k.pg_min_frac); k.ho_grid = geti("VGS_HO_GRID", k.ho_grid);
   k.debug = has("VGS_DEBUG");
 }
 
@@ -193,7 +193,7 @@ vgs_status vgs_create(const vgs_params* p, vgs_ctx** out) {
     vgs_destroy(c);
     return VGS_E_HIP;
   }
-  if (hipHostMalloc(&c->pin, 4096, hipHostMallocDefault) != hipSuccess) c->pin = nullptr;   // read-backs fall back to pageable copies
+  if (hipHostMalloc(&c->pin, VGS_PIN_BYTES, hipHostMallocDefault) != hipSuccess) c->pin = nullptr;   // read-backs fall back to pageable copies
   bool ok = hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking) == hipSuccess &&
             hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_h2d, hipEventDisableTiming) == hipSuccess &&
@@ -205,7 +205,7 @@ vgs_status vgs_create(const vgs_params* p, vgs_ctx** out) {
             hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_ff_fork, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ev_ff_join, hipEventDisableTiming) == hipSuccess;
-  for (int i = 0; ok && i < 16; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
+  for (int i = 0; ok && i < EV_COUNT; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
   for (int i = 0; ok && i < VGS_T_COUNT; ++i) ok = hipEventCreate(&c->tev[i][0]) == hipSuccess && hipEventCreate(&c->tev[i][1]) == hipSuccess;
   if (!ok) { g_create_err = "vgs_create: hipStreamCreate/hipEventCreate failed"; vgs_destroy(c); return VGS_E_HIP; }   // frees what exists
   vgs_read_env_knobs(c);
@@ -223,39 +223,8 @@ void vgs_destroy(vgs_ctx* c) {
   if (c->stream4) (void)hipStreamSynchronize(c->stream4);
   if (c->s_h2d) (void)hipStreamSynchronize(c->s_h2d);
   if (c->s_d2h) (void)hipStreamSynchronize(c->s_d2h);
-  c->xyz_buf[0].release(); c->xyz_buf[1].release(); c->pt_label_alt.release(); c->grow_state.release();
-  c->code_a.release(); c->code_b.release(); c->perm_a.release(); c->perm_b.release(); c->sort_tmp.release();
-  c->head_flag.release(); c->pt_vox.release(); c->vox_tile.release(); c->vox_code.release(); c->vox_start.release();
-  c->xs.release(); c->ys.release(); c->zs.release();
-  c->node.release(); c->used_ids.release(); c->used_rank.release();
-  c->hkey.release(); c->hval.release(); c->offsets.release(); c->adj_masks.release(); c->adj_gtab.release(); c->adj_nvals.release(); c->adj_nrank.release(); c->adj_key.release(); c->adj_off.release(); c->adj_cnt.release(); c->adj_mused.release();
-  c->nl_cnt.release(); c->nl_tot.release(); c->nl_ent.release(); c->lc_ctab.release(); c->pl_state.release(); c->pl_ent.release(); c->pl_work.release();
-  c->sd_key.release(); c->sd_ids.release(); c->sd_vp.release(); c->sd_seg.release(); c->sd_tmp.release(); c->sd_part.release();
-  c->sd_npts.release(); c->sd_nnodes.release(); c->sd_bbox.release(); c->sd_eig8.release(); c->sd_cen.release(); c->sd_cov.release(); c->sd_eval.release(); c->sd_evec.release();
-  c->sd_apos.release(); c->sd_mom.release();
-  c->sf_in.release(); c->sf_min.release(); c->sf_max.release(); c->sf_cls.release(); c->sf_maj.release(); c->sf_part.release(); c->sf_anchor.release(); c->sf_idx.release();
-  c->sf_mean.release(); c->sf_var.release(); c->sf_nvalid.release(); c->sf_hist.release();
-  c->sb_part.release(); c->sbt_in.release(); c->sbt_frame.release(); c->sbt_out.release(); c->sbt_idx.release();
-  for (int f = 0; f < 2; ++f) { c->sb_frame[f].release(); c->sb_lo[f].release(); c->sb_hi[f].release(); c->sb_half[f].release(); c->sb_center[f].release(); }
-  c->sg_lab.release(); c->sg_nrec.release(); c->sg_ridx.release(); c->sg_ework.release(); c->sg_meta.release(); c->sg_roff.release(); c->sg_rkey.release(); c->sg_rec.release(); c->sg_part.release(); c->sg_tmp.release();
-  c->sg_ab.release(); c->sg_nodes.release(); c->sg_npairs.release(); c->sg_nfin.release(); c->sg_wsum.release(); c->sg_wmin.release(); c->sg_wmax.release();
-  c->cmp_ref.release(); c->cmp_cell_i32.release(); c->cmp_ref_i32.release(); c->cmp_seg_i32.release(); c->cmp_cell_n.release(); c->cmp_ref_i64.release(); c->cmp_seg_i64.release();
-  c->cmp_ref_iou.release(); c->cmp_seg_iou.release(); c->cmp_key.release(); c->cmp_meta.release(); c->cmp_work.release(); c->cmp_cstart.release(); c->cmp_rowstart.release();
-  c->cmp_rsort.release(); c->cmp_rstart.release(); c->cmp_tmp.release();
-  c->rf_label.release(); c->rf_batches.release(); c->rf_start.release(); c->rf_ids.release(); c->rf_cnt.release(); c->rf_nall.release();
-  c->rf_rows.release(); c->rf_counts.release();
-  c->ps_in.release(); c->ps_nnodes.release(); c->ps_key.release(); c->ps_val.release(); c->ps_seg.release(); c->ps_nn.release(); c->ps_tmp.release();
-  c->ps_meta.release(); c->ps_part.release(); c->ps_d.release(); c->ps_f.release(); c->ps_npts.release();
-  c->cl_off.release(); c->cl_idx.release(); c->conn.release(); c->evals.release(); c->lc_pending.release(); c->lc_defer.release(); c->lc_defer_flag.release(); c->csize.release(); c->attach.release(); c->cc_flags.release(); c->parent.release(); c->csz.release();
-  c->vc_cen.release(); c->vc_nrm.release(); c->vc_dist.release(); c->vc_state.release(); c->vc_tile_start.release(); c->vc_cell.release(); c->vc_plive.release(); c->vc_tile_of.release(); c->vc_tchg.release(); c->vc_nbr_tiles.release(); c->vc_halo.release(); c->vc_tile_meta.release(); c->vc_pool.release(); c->vc_ring.release(); c->vc_dbg.release(); c->vc_label.release();
-  c->vc_seedkey.release(); c->vc_sums.release(); c->vc_count.release(); c->vc_accu.release(); c->vc_alive.release();
-  c->sv_label.release(); c->sv_key_a.release(); c->sv_key_b.release(); c->cell_code_a.release(); c->cell_code_b.release();
-  c->cell_id_a.release(); c->cell_id_b.release(); c->cell_start.release();
-  c->owned.release(); c->straddle.release(); c->mixsrc.release(); c->bnd_code.release(); c->bnd_root.release(); c->root_label.release();
-  c->bnd_code2.release(); c->bnd_root2.release(); c->bnd_cnt.release(); c->broot.release();
-  c->kept_rank.release(); c->vox_label.release(); c->pt_label.release(); c->counters.release(); c->work_ids.release();
   if (c->pin) (void)hipHostFree(c->pin);
-  for (int i = 0; i < 16; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
+  for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   for (int i = 0; i < VGS_T_COUNT; ++i) for (int k = 0; k < 2; ++k) if (c->tev[i][k]) (void)hipEventDestroy(c->tev[i][k]);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -272,7 +241,7 @@ void vgs_destroy(vgs_ctx* c) {
   if (c->ev_ff_fork) (void)hipEventDestroy(c->ev_ff_fork);
   if (c->ev_ff_join) (void)hipEventDestroy(c->ev_ff_join);
   if (c->ev_d2h) (void)hipEventDestroy(c->ev_d2h);
-  delete c;
+  delete c;   // frees every DevBuf member
 }
 
 vgs_status vgs_set_params(vgs_ctx* c, const vgs_params* p) {
@@ -653,7 +622,6 @@ static vgs_status vgs_build_lists(vgs_ctx* c, int32_t which, std::vector<std::ve
         for (uint32_t q = 0; q < cnt[(size_t)k]; ++q) l[q] = (int32_t)(uint32_t)keys[(size_t)k * c->adj_stride + q];
       }
     }
-    fk.release(); fc.release(); fn.release(); fid.release();
     if (st == VGS_E_HIP) c->err = "vgs_get_lists: full adjacency pass failed";
     return st;
   }
@@ -778,9 +746,9 @@ vgs_status vgs_get_point_labels_async(vgs_ctx* c, int32_t* labels) {
   if (c->d2h_open) { VGS_HIP_TRY(c, hipEventSynchronize(c->ev_d2h)); c->d2h_open = false; }   // one download in flight per context
   if (c->N == 0) return VGS_OK;
   { vgs_status se = vgs_ensure_point_labels(c); if (se != VGS_OK) return se; }
-  // device-side order: the copy follows the kernel that wrote the labels (ev[15], recorded behind it on the context's stream by the
+  // device-side order: the copy follows the kernel that wrote the labels (EV_LABELS_END, recorded behind it on the context's stream by the
   // merge stage and by vgs_apply_*_labels), whatever the host has or has not waited for
-  if (c->labels_event_valid) VGS_HIP_TRY(c, hipStreamWaitEvent(c->s_d2h, c->ev[15], 0));
+  if (c->labels_event_valid) VGS_HIP_TRY(c, hipStreamWaitEvent(c->s_d2h, c->ev[EV_LABELS_END], 0));
   VGS_HIP_TRY(c, hipMemcpyAsync(labels, c->pt_label.p, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->s_d2h));
   VGS_HIP_TRY(c, hipEventRecord(c->ev_d2h, c->s_d2h));
   c->d2h_open = true; c->d2h_src = c->pt_label.p;

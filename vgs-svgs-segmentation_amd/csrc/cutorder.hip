@@ -201,7 +201,6 @@ vgs_status vgs_cut_order(vgs_ctx* c, std::vector<uint16_t>& ord_host, std::vecto
   // offsets of the ball, may well be larger); the replay kernels take a connect set of up to CO_MAXK of them -- checked below
   VGS_HIP_TRY(c, hipSetDevice(c->device));
   DevBuf<uint32_t> d_k; DevBuf<uint16_t> d_ord; DevBuf<uint64_t> d_offs, d_keys_a, d_keys_b; DevBuf<uint8_t> d_tmp; DevBuf<unsigned int> d_bad;
-  auto release = [&]() { d_k.release(); d_ord.release(); d_offs.release(); d_keys_a.release(); d_keys_b.release(); d_tmp.release(); d_bad.release(); };
   vgs_status st = VGS_OK;
   auto fail = [&](hipError_t e, const char* what) { c->err = std::string("vgs_cut_order: ") + what + ": " + hipGetErrorString(e); st = VGS_E_HIP; };
   do {
@@ -265,12 +264,10 @@ vgs_status vgs_cut_order(vgs_ctx* c, std::vector<uint16_t>& ord_host, std::vecto
         if ((e = hipMemcpyAsync(list_ids->data(), d_ids.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) { fail(e, "copy"); break; }
         if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) { fail(e, "fill lists"); break; }
       } while (false);
-      d_cnt.release(); d_start.release(); d_ids.release();
       break;
     }
     ord_host.resize((size_t)U * c->adj_stride);
     if ((e = hipMemcpy(ord_host.data(), d_ord.p, ord_host.size() * 2, hipMemcpyDeviceToHost)) != hipSuccess) { fail(e, "copy"); break; }
   } while (false);
-  release();
   return st;
 }

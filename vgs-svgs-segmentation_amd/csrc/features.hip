@@ -153,7 +153,7 @@ vgs_status vgs_stage_features(vgs_ctx* c) {
   VGS_HIP_TRY(c, c->sort_tmp.ensure(bytes));
   VGS_HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.p, bytes, used_flag, excl, 0u, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
   VGS_HIP_TRY(c, c->counters.ensure(64));
-  unsigned long long* d_nu = (unsigned long long*)(c->counters.p + 36);
+  unsigned long long* d_nu = (unsigned long long*)(c->counters.p + CW_FEAT_NUSED);
   hipLaunchKernelGGL(k_compact_used, dim3(nb), dim3(FEAT_TB), 0, c->stream, used_flag, excl, V, c->used_ids.p, c->used_rank.p, d_nu);
   unsigned long long nu = 0;
   c->bricks_ready = false;

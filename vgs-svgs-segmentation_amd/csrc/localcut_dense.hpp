@@ -90,7 +90,7 @@ __global__ __launch_bounds__(TB, (MAXM <= 255 ? LD_SMALL_WG_PER_CU : 4)) void k_
 #endif
 
   auto hand_on = [&]() {   // all threads
-    if (tid == 0) { fallback[atomicAdd(n_fallback, 1u)] = u; atomicAdd(&counters[7], 1ull); }
+    if (tid == 0) { fallback[atomicAdd(n_fallback, 1u)] = u; atomicAdd(&counters[CW_LC_SLOW], 1ull); }
   };
   if (m > MAXM) { hand_on(); return; }   // not a one-wavefront voxel (cannot happen from the hand-over list)
 
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(TB, (MAXM <= 255 ? LD_SMALL_WG_PER_CU : 4)) void k_
       // More heavy edges than the list holds (a large neighbourhood on one smooth surface that the lazy schedule could not
       // finish): bands of descending weight as in phase B below, from a histogram of the weights above thr0.  Each band
       // costs another sweep, but the voxel's segment usually freezes in the first.
-      if (tid == 0) atomicAdd(&counters[0], 1ull);
+      if (tid == 0) atomicAdd(&counters[CW_LC_BANDED], 1ull);
       for (int k = tid; k < DN_ABIN; k += TB) s_hist_a[k] = 0u;
       __syncthreads();
       sweep(1, 0, 0);
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(TB, (MAXM <= 255 ? LD_SMALL_WG_PER_CU : 4)) void k_
           // queue's slots are free now), then every band -- the heaviest whole bins that fit the list -- is collected by a
           // pass of its own, sorted and merged.  Pairs merged away meanwhile only make later bands shorter.  The bands end
           // when the voxel's own segment is frozen below the next band (fact F).
-          if (tid == 0) atomicAdd(&counters[0], 1ull);
+          if (tid == 0) atomicAdd(&counters[CW_LC_BANDED], 1ull);
           uint32_t* hist = (uint32_t*)queue;
           const float scale = (float)DN_NBIN / thr0;
           auto bin_of = [&](float w) -> int { const int bb = (int)(w * scale); return bb < 0 ? 0 : (bb > DN_NBIN - 1 ? DN_NBIN - 1 : bb); };

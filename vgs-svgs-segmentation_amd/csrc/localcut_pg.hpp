@@ -111,7 +111,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_localcut_pg(const uint32_t* __
   const float cut = P.cut;
   const float thr0 = vm_cut_threshold(1.0f, cut, 1);
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
-  unsigned int n_cut = 0;   // voxels this workgroup cut (counters[63], one atomic per workgroup)
+  unsigned int n_cut = 0;   // voxels this workgroup cut (counters[CW_PG_NCUT], one atomic per workgroup)
 
   auto h_slot = [&](uint32_t key15) -> uint32_t { return (key15 * 2654435761u) >> 12; };
   auto d_cell = [&](uint32_t key15) -> int {   // cell of a packed offset in the cube, -1 outside
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_localcut_pg(const uint32_t* __
     PGP_T0();
     auto R = [&](int v) -> const NodeRec& { return node[(uint32_t)row[v]]; };
     auto hand_on = [&]() {   // all threads; the row is written by whoever takes the voxel from the fallback list
-      if (tid == 0) { fallback[atomicAdd(n_fallback, 1u)] = u; atomicAdd(&counters[7], 1ull); if (pending_mark) pending_mark[u] = 0xff; }
+      if (tid == 0) { fallback[atomicAdd(n_fallback, 1u)] = u; atomicAdd(&counters[CW_LC_SLOW], 1ull); if (pending_mark) pending_mark[u] = 0xff; }
     };
     if (m > MAXM && too_big != nullptr && orow[0] != 0xffffu) {   // the next larger instantiation takes it
       if (tid == 0) too_big[atomicAdd(n_too_big, 1u)] = u;
@@ -819,7 +819,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_localcut_pg(const uint32_t* __
               if (!(thr[r0] < wub) || s_i[S_MERGES] >= m - 1) break;
               pg_barrier();   // (the counters are rewritten at the top)
             }
-            if (tid == 0) atomicAdd(&counters[0], 1ull);   // "banded"
+            if (tid == 0) atomicAdd(&counters[CW_LC_BANDED], 1ull);   // "banded"
           }
           PGP_CNT(13, 1);
         }
@@ -874,7 +874,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_localcut_pg(const uint32_t* __
     if (process((uint32_t)__builtin_amdgcn_readfirstlane((int)u))) ++n_cut;
     pg_barrier();   // the next voxel reuses every array
   }
-  if (tid == 0 && n_cut) atomicAdd(&counters[63], (unsigned long long)n_cut);
+  if (tid == 0 && n_cut) atomicAdd(&counters[CW_PG_NCUT], (unsigned long long)n_cut);
 }
 
 #endif

@@ -30,7 +30,7 @@
 #include "nearlist.hpp"
 #include "regsort.hpp"
 
-// VGS_PROF=1 builds accumulate per-phase shader cycles (s_memtime) into counters[16..31] (diagnostics only)
+// VGS_PROF=1 builds accumulate per-phase shader cycles (s_memtime) into counters[CW_LC_PROF ..] (16 words; diagnostics only)
 #ifdef VGS_PROF
 #define LW_T0() long long _t0 = clock64()
 #define LW_ACC(slot) do { long long _t1 = clock64(); if (lane == 0) prof[slot] += (unsigned long long)(_t1 - _t0); _t0 = _t1; } while (0)
@@ -88,7 +88,6 @@
 // hand-over marks of the one-wavefront classes: pending[u] = 1 + list + LW_HO_BINS * why; k_ho_lists counts the reasons into these words
 #define LW_PENDING_LISTED 0xff   // pending[u] of a voxel that is already in a hand-over list (k_ho_lists leaves it alone)
 #define LW_HO_VOTE 0x100
-#define LW_VOTE_BASE 64    // counter words 64 .. 127
 #ifndef LW_VOTE_WORDS
 #define LW_VOTE_WORDS 64u  // words in use (a power of two <= 64).  NOT fewer: every wavefront of the bulk launch reads one of them past the scalar
                            // cache, and with 16 words (two cache lines) those reads pile up on two L2 channels -- the bulk kernel took 5.9 instead of 2.7 ms
@@ -109,7 +108,7 @@ struct LwParams {
   int near_min_own; // multi-wavefront classes: first shells from the near-pair lists only if the vertices' lists hold this many entries on average
   // One-wavefront classes, bit LW_HO_VOTE of ho_bins: is the lazy schedule worth trying on this scene at all?  Every sixteenth voxel of
   // these classes is a SAMPLE: it runs in an instantiation of its own (SAMPLED, launched beside the others), always tries, and books how it
-  // ended -- finished / gave the voxel up -- in one of 64 counter words (LW_VOTE_BASE; low / high half).  The others read one of the words
+  // ended -- finished / gave the voxel up -- in one of 64 counter words (CW_LC_VOTE; low / high half).  The others read one of the words
   // when they start and, once seven of eight samples gave up, hand their voxel over without trying.  Under centimetres of range noise
   // 98 % of the voxels work through their shells only to be handed over; the hand-over kernel reads pair lists and does not care.
   // Scheduling only: both paths give the same connect list.  (The bookkeeping is in an instantiation of its own because the kernel has
@@ -275,7 +274,7 @@ __global__ __launch_bounds__(64 * NW, MAXM <= 255 ? LW_WAVES : (NW > 1 ? (MAXM =
       // the scene's samples (see LwParams::ho_bins): a scalar load that bypasses the scalar cache, which does not see the samples'
       // atomics -- no vector register is held for it, and the wavefront that hands over leaves here
       unsigned long long vote_word;
-      const unsigned long long* vp = counters + LW_VOTE_BASE + (blockIdx.x & (LW_VOTE_WORDS - 1u));
+      const unsigned long long* vp = counters + CW_LC_VOTE + (blockIdx.x & (LW_VOTE_WORDS - 1u));
       asm volatile("s_load_dwordx2 %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(vote_word) : "s"(vp) : "memory");
       const uint32_t fin = (uint32_t)vote_word, gave = (uint32_t)(vote_word >> 32);
       if ((fin + gave >= 8u) && (gave * 8u >= (fin + gave) * 7u)) {
@@ -945,7 +944,7 @@ __global__ __launch_bounds__(64 * NW, MAXM <= 255 ? LW_WAVES : (NW > 1 ? (MAXM =
       // passes hand it to the workgroup-per-voxel kernel, which holds 8192 edges and evaluates every pair once
       // (examining all remaining pairs in this kernel and keeping the survivors only was tried: the neighbourhoods that
       // get here hold more edges above thr0 than the list, or overflow it in phase B, and are handed over anyway)
-      if (++rounds > (MAXM > 128 ? 14 : P.max_rounds)) { if (lane == 0) diag(3); bail = true; break; }
+      if (++rounds > (MAXM > 128 ? 14 : P.max_rounds)) { if (lane == 0) diag(CW_LC_WHY_SHRINK); bail = true; break; }
       // ---- 1. enumerate the pairs of this shell ----
       const int free_slots = LCAP - n_list;
       const bool use_minor = (big >= 0) && (2 * n_min < n_act);
@@ -981,10 +980,10 @@ __global__ __launch_bounds__(64 * NW, MAXM <= 255 ? LW_WAVES : (NW > 1 ? (MAXM =
       LW_CNT(8, 1);  // rounds
       if (count > free_slots) {
         // the shell holds more pairs than the list: shrink it (assume uniform density in d2) and redo
-        if (++shrink > 24 || free_slots < 32) { if (lane == 0) diag(free_slots < 32 ? 4 : 3); bail = true; break; }
+        if (++shrink > 24 || free_slots < 32) { if (lane == 0) diag(free_slots < 32 ? CW_LC_WHY_FULL : CW_LC_WHY_SHRINK); bail = true; break; }
         const float hi = final_round ? P.d2_all : cut_hi;
         cut_hi = cut_lo + (hi - cut_lo) * (0.75f * (float)free_slots / (float)count);
-        if (!(cut_hi > cut_lo)) { if (lane == 0) diag(5); bail = true; break; }
+        if (!(cut_hi > cut_lo)) { if (lane == 0) diag(CW_LC_WHY_COLLAPSE); bail = true; break; }
         continue;
       }
       shrink = 0;
@@ -1019,7 +1018,7 @@ __global__ __launch_bounds__(64 * NW, MAXM <= 255 ? LW_WAVES : (NW > 1 ? (MAXM =
           else if (n_list <= 128) sorted = regsort::sort_desc32<2>(lk, n_list, lane, wbase);
           else if (n_list <= 256) sorted = regsort::sort_desc32<4>(lk, n_list, lane, wbase);
           else sorted = regsort::sort_desc32<8>(lk, n_list, lane, wbase);
-          if (!sorted) { if (lane == 0) diag(3); bail = true; break; }
+          if (!sorted) { if (lane == 0) diag(CW_LC_WHY_SHRINK); bail = true; break; }
         } else {
           if (n_list <= 64) regsort::sort_desc<1>(lk, n_list, lane);
           else if (n_list <= 128) regsort::sort_desc<2>(lk, n_list, lane);
@@ -1166,7 +1165,7 @@ __global__ __launch_bounds__(64 * NW, MAXM <= 255 ? LW_WAVES : (NW > 1 ? (MAXM =
           qq += 64;
         }
         if (count > LCAP) {
-          if (lane == 0) diag(6);
+          if (lane == 0) diag(CW_LC_WHY_PHASEB);
           bail = true;
         } else {
           wave_sync();
@@ -1185,7 +1184,7 @@ __global__ __launch_bounds__(64 * NW, MAXM <= 255 ? LW_WAVES : (NW > 1 ? (MAXM =
       // the launch cannot end before they have -- 4 ms, whatever the wavefronts do.)
       if (SMALL && NW == 1 && (P.ho_bins & 0xff) > 1) P.pending[u] = (uint8_t)(1 + bin);
       else { fallback[(size_t)bin * P.ho_stride + atomicAdd(n_fallback + bin, 1u)] = u; P.pending[u] = LW_PENDING_LISTED; }
-      if constexpr (SAMPLED) atomicAdd(&counters[LW_VOTE_BASE + (blockIdx.x & (LW_VOTE_WORDS - 1u))], 1ull << 32);   // a sample that gave up
+      if constexpr (SAMPLED) atomicAdd(&counters[CW_LC_VOTE + (blockIdx.x & (LW_VOTE_WORDS - 1u))], 1ull << 32);   // a sample that gave up
     }
     return;
   }
@@ -1212,10 +1211,10 @@ __global__ __launch_bounds__(64 * NW, MAXM <= 255 ? LW_WAVES : (NW > 1 ? (MAXM =
     }
   }
   if (lane == 0) evals_out[u] = n_evals;  // summed on the host on request: no same-address atomics on the hot path
-  if constexpr (SAMPLED) { if (lane == 0 && m >= 2) atomicAdd(&counters[LW_VOTE_BASE + (blockIdx.x & (LW_VOTE_WORDS - 1u))], 1ull); }   // a sample that finished
+  if constexpr (SAMPLED) { if (lane == 0 && m >= 2) atomicAdd(&counters[CW_LC_VOTE + (blockIdx.x & (LW_VOTE_WORDS - 1u))], 1ull); }   // a sample that finished
 #ifdef VGS_PROF
   if (lane == 0 && dbg_out) { long long tnow = clock64(); dbg_out[4 * (size_t)u + 0] = (uint32_t)m; dbg_out[4 * (size_t)u + 1] = (uint32_t)prof[8]; dbg_out[4 * (size_t)u + 2] = (uint32_t)((tnow - t_start) >> 4); dbg_out[4 * (size_t)u + 3] = (uint32_t)n_evals; }
-  if (lane == 0) { prof[11] = 1; prof[12] = (unsigned long long)merges; prof[13] = (unsigned long long)m; for (int k = 0; k < 16; ++k) if (prof[k]) atomicAdd(&counters[16 + k], prof[k]); }
+  if (lane == 0) { prof[11] = 1; prof[12] = (unsigned long long)merges; prof[13] = (unsigned long long)m; for (int k = 0; k < 16; ++k) if (prof[k]) atomicAdd(&counters[CW_LC_PROF + k], prof[k]); }
 #endif
   };  // master
   master();

@@ -504,7 +504,7 @@ vgs_status vgs_ensure_point_labels(vgs_ctx* c) {
   const int TB = 256;
   hipLaunchKernelGGL(k_point_labels, dim3((unsigned)((c->N + TB - 1) / TB)), dim3(TB), 0, c->stream, c->perm_b.p, c->pt_vox.p, c->vox_label.p,
                      c->N, c->pt_label.p);
-  VGS_HIP_TRY(c, hipEventRecord(c->ev[15], c->stream));
+  VGS_HIP_TRY(c, hipEventRecord(c->ev[EV_LABELS_END], c->stream));
   c->labels_event_valid = true;
   VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
   return VGS_OK;
@@ -551,7 +551,6 @@ extern "C" vgs_status vgs_get_local_weights(vgs_ctx* c, int32_t node_id, int32_t
   hipError_t e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = hipMemcpy(weights, d_w.p, (size_t)total * 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(ids, d_ids.p, (size_t)n * 4, hipMemcpyDeviceToHost);
-  d_w.release(); d_ids.release();
   if (e != hipSuccess) { c->err = std::string("vgs_get_local_weights: ") + hipGetErrorString(e); return VGS_E_HIP; }
   return VGS_OK;
 }
@@ -570,7 +569,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
   if (V == 0) {
     if (N > 0) {
       VGS_HIP_TRY(c, hipMemsetAsync(c->pt_label.p, 0xff, N * sizeof(int32_t), c->stream));
-      VGS_HIP_TRY(c, hipEventRecord(c->ev[15], c->stream));   // label downloads order themselves behind this fill, not behind an earlier cloud's kernel
+      VGS_HIP_TRY(c, hipEventRecord(c->ev[EV_LABELS_END], c->stream));   // label downloads order themselves behind this fill, not behind an earlier cloud's kernel
       c->labels_event_valid = true;
     }
     c->pt_labels_pending = false;
@@ -586,10 +585,10 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
   VGS_HIP_TRY(c, c->csize.ensure(V)); VGS_HIP_TRY(c, c->attach.ensure(V)); VGS_HIP_TRY(c, c->cc_flags.ensure(V));
   VGS_HIP_TRY(c, c->parent.ensure(V)); VGS_HIP_TRY(c, c->csz.ensure(V)); VGS_HIP_TRY(c, c->kept_rank.ensure(V + 1));
   VGS_HIP_TRY(c, c->vox_label.ensure(V));
-  // this stage's counters live in words 48-55: words 0-13 still belong to the local cut, whose hand-over kernels may be running
+  // this stage's own counter words (MG_W_*, zeroed here): the local cut's hand-over kernels may still be running on theirs (counter_words.hpp)
   VGS_HIP_TRY(c, c->counters.ensure(64));
-  uint64_t* mcnt = c->counters.p + 48;
-  VGS_HIP_TRY(c, hipMemsetAsync(mcnt, 0, 8 * sizeof(uint64_t), c->stream));
+  uint64_t* mcnt = c->counters.p + CW_MG_BASE;
+  VGS_HIP_TRY(c, hipMemsetAsync(mcnt, 0, MG_W_COUNT * sizeof(uint64_t), c->stream));
   hipLaunchKernelGGL(k_merge_init, dim3(nbV), dim3(TB), 0, c->stream, c->parent.p, c->csize.p, c->attach.p, c->cc_flags.p, c->csz.p, V);
   uint8_t* mutual = nullptr;
   unsigned int n_cand = 0, n_succ = 0;
@@ -604,7 +603,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     // beside the hand-over kernels as in a single-context run.
     if (c->have_region) { vgs_status so = vgs_compute_owned(c); if (so != VGS_OK) return so; }
     const uint8_t* owned_early = c->have_region ? c->owned.p : (const uint8_t*)nullptr;
-    unsigned int* d_ndefer = (unsigned int*)(c->counters.p + 13);   // zeroed with the local cut's counters
+    unsigned int* d_ndefer = (unsigned int*)(c->counters.p + CW_MG_NDEFER);   // zeroed with the local cut's counters
     // runs whose hand-over kernels are still running: the unions of the final rows go beside them (see below)
     const bool early_union = c->lc_tail.open && !c->K.no_overlap;
     if (early_union) VGS_HIP_TRY(c, c->lc_defer_flag.ensure((size_t)U));
@@ -618,7 +617,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     // (When the hand-overs are MANY -- LcGate's word, written on the device by k_ho_lists -- this first pass would put off every row, one
     // atomic each, and the unions behind it would find nothing final: both return at once, and the plain pass over all rows follows
     // below, behind the hand-over kernels.)
-    const LcGate g_first = {(c->lc_tail.open && c->lc_tail.gated) ? (const unsigned int*)(c->counters.p + 57) : (const unsigned int*)nullptr, LC_FEW};
+    const LcGate g_first = {(c->lc_tail.open && c->lc_tail.gated) ? (const unsigned int*)(c->counters.p + CW_LC_GATE) : (const unsigned int*)nullptr, LC_FEW};
     const size_t first_lds = (c->lc_tail.open && c->K.cross_lds_kb > 0) ? (size_t)c->K.cross_lds_kb * 1024 : 0;
     hipLaunchKernelGGL(k_cross, dim3(vgs_xcd_grid((U + CX_ROWS - 1) / CX_ROWS)), dim3(64), first_lds, c->stream, c->used_ids.p, c->used_rank.p, U, c->adj_key.p, c->adj_cnt.p,
                        c->adj_stride, c->conn.p, mutual, c->csize.p, c->parent.p, gt, c->adj_gstride, c->adj_nrank.p, inv_res2,
@@ -631,7 +630,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     //   side stream:  the local cut's finish (read-back, rest and extra-large launches, connect bits of the handed-over voxels),
     //                 crossValidation over the rows put off (no first hook: parent == nullptr), closestCheck with its read-backs -- they
     //                 write the mutual flags, csize and connect bits of put-off and handed-over rows, cc_flags, attach,
-    //                 work_ids[0, n_cand) and counter words 48-53, and never touch `parent`.
+    //                 work_ids[0, n_cand) and the stage's own counter words (MG_W_*), and never touch `parent`.
     // Read from the kernels: k_union_mutual loads the first batch of a row's mutual flags together with its skip flag, so for a put-off
     // row that load may race with the second crossValidation pass -- the loaded bytes are dropped at `if (skipped) return` before any
     // use (a stale or torn byte of a skipped row decides nothing); `attach` is read only under do_attach, which is 0 here.  The skip flags
@@ -694,8 +693,8 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
     }
     // closestCheck
     VGS_HIP_TRY(c, c->work_ids.ensure((size_t)U + 16));
-    unsigned int* d_ncand = (unsigned int*)(mcnt + 0);
-    unsigned int* d_changed = (unsigned int*)(mcnt + 1);
+    unsigned int* d_ncand = (unsigned int*)(mcnt + MG_W_NCAND);
+    unsigned int* d_changed = (unsigned int*)(mcnt + MG_W_CHANGED);
     // (256 threads also beside the union pass: one-wavefront workgroups were measured there and are slower, profiles/ab_merge_fork.txt)
     hipLaunchKernelGGL(k_cc_candidates, dim3((unsigned)((U + TB - 1) / TB)), dim3(TB), 0, s, c->used_ids.p, U, c->adj_mused.p,
                        c->csize.p, MP.adjacency_min, c->cc_flags.p, c->work_ids.p, d_ncand);
@@ -717,7 +716,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
       // fixed point of "re-attachment succeeds": passes are queued four at a time, each with its own change counter, and
       // only the last counter is read back (a pass after the fixed point changes nothing and costs microseconds; a host
       // round trip per pass cost more than the passes)
-      unsigned int* d_chg4 = (unsigned int*)(mcnt + 4);   // words 4-5: four 32-bit counters
+      unsigned int* d_chg4 = (unsigned int*)(mcnt + MG_W_CHG4);   // two words: four 32-bit counters
       for (int round = 0; round < 1 << 18; ++round) {
         VGS_HIP_TRY(c, hipMemsetAsync(d_chg4, 0, 16, s));
         for (int q = 0; q < 4; ++q)
@@ -760,11 +759,11 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
                        c->have_region ? c->owned.p : (const uint8_t*)nullptr);
   hipLaunchKernelGGL(k_flatten, dim3(nbV), dim3(TB), 0, c->stream, c->parent.p, V, c->have_region ? c->owned.p : nullptr, c->csz.p);
   // cluster filter + labels (VGS_T_LABELS: this tail of the stage, measured on its own; it is part of VGS_T_MERGE)
-  VGS_HIP_TRY(c, hipEventRecord(c->ev[14], c->stream));   // ev[14], ev[15]: this tail's own pair
+  VGS_HIP_TRY(c, hipEventRecord(c->ev[EV_LABELS_BEGIN], c->stream));   // EV_LABELS_BEGIN, EV_LABELS_END: this tail's own pair
   uint32_t* keep_flag = c->head_flag.p;  // >= N >= V entries, free after features
   VGS_HIP_TRY(c, c->head_flag.ensure(V + 1));
   keep_flag = c->head_flag.p;
-  unsigned int* d_nroots = (unsigned int*)(mcnt + 2);
+  unsigned int* d_nroots = (unsigned int*)(mcnt + MG_W_NROOTS);
   hipLaunchKernelGGL(k_root_flags, dim3((unsigned)((V + 1023) / 1024)), dim3(1024), 0, c->stream, c->parent.p, c->csz.p, V, c->P.method == 3 ? -1 : c->P.voxels_min,
                      keep_flag, d_nroots);
   size_t bytes = 0;
@@ -772,7 +771,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
   VGS_HIP_TRY(c, c->sort_tmp.ensure(bytes));
   VGS_HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.p, bytes, keep_flag, c->kept_rank.p, 0u, (size_t)V, rocprim::plus<uint32_t>(), c->stream));
   hipLaunchKernelGGL(k_voxel_labels, dim3(nbV), dim3(TB), 0, c->stream, c->parent.p, keep_flag, c->kept_rank.p, V, c->vox_label.p,
-                     (unsigned int*)(mcnt + 3));
+                     (unsigned int*)(mcnt + MG_W_NKEPT));
   // (Round 4 measured the scatter-free alternative -- the point's octree key formed again from its coordinates, its voxel from the
   // brick table, label[p] written in input order: 0.26 ms against this kernel's 0.14 ms at 10 M points.  PCL's key arithmetic is
   // double precision -- three fp64 divisions per point -- and that costs more than the 4-byte scatter saves.)
@@ -782,18 +781,18 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
   if (!c->pt_labels_pending)
     hipLaunchKernelGGL(k_point_labels, dim3((unsigned)((N + TB - 1) / TB)), dim3(TB), 0, c->stream, c->perm_b.p, c->pt_vox.p, c->vox_label.p,
                        N, c->pt_label.p);
-  VGS_HIP_TRY(c, hipEventRecord(c->ev[15], c->stream));
+  VGS_HIP_TRY(c, hipEventRecord(c->ev[EV_LABELS_END], c->stream));
   c->labels_event_valid = true;
   VGS_HIP_TRY(c, hipGetLastError());
-  // one read-back: words 1-3 = re-attachments, roots, kept segments
-  uint64_t hm[4] = {0, 0, 0, 0};
+  // one read-back: MG_W_CHANGED, MG_W_NROOTS, MG_W_NKEPT = re-attachments, roots, kept segments
+  uint64_t hm[MG_W_NKEPT + 1] = {0, 0, 0, 0};
   VGS_READBACK(c, hm, mcnt, sizeof(hm));
-  { float lms = 0.f; if (hipEventElapsedTime(&lms, c->ev[14], c->ev[15]) == hipSuccess) c->times[VGS_T_LABELS] = lms; }
-  const unsigned int n_roots = (unsigned int)hm[2];
-  if (U > 0 && n_cand > 0) n_succ = (unsigned int)hm[1];
+  { float lms = 0.f; if (hipEventElapsedTime(&lms, c->ev[EV_LABELS_BEGIN], c->ev[EV_LABELS_END]) == hipSuccess) c->times[VGS_T_LABELS] = lms; }
+  const unsigned int n_roots = (unsigned int)hm[MG_W_NROOTS];
+  if (U > 0 && n_cand > 0) n_succ = (unsigned int)hm[MG_W_CHANGED];
   c->counts[VGS_N_REATTACHED] = n_succ;
   c->counts[VGS_N_CLUSTERS] = n_roots;
-  c->counts[VGS_N_KEPT] = (int64_t)(unsigned int)hm[3];
+  c->counts[VGS_N_KEPT] = (int64_t)(unsigned int)hm[MG_W_NKEPT];
   c->counts[VGS_N_ISOLATED] = n_cand;
   return VGS_OK;
 }

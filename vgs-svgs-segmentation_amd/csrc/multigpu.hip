@@ -235,7 +235,7 @@ vgs_status vgs_points_bbox(vgs_ctx* c, float* bbox6, int64_t* n_finite) {
   VGS_HIP_TRY(c, c->sort_tmp.ensure((size_t)NBLK * 6 * sizeof(float) + 16));
   VGS_HIP_TRY(c, c->counters.ensure(64));
   float* d_out = (float*)c->sort_tmp.p;
-  unsigned long long* d_n = (unsigned long long*)(c->counters.p + 34);
+  unsigned long long* d_n = (unsigned long long*)(c->counters.p + CW_MGPU_NFINITE);
   VGS_HIP_TRY(c, hipMemsetAsync(d_n, 0, 8, c->stream));
   hipLaunchKernelGGL(k_points_bbox, dim3(NBLK), dim3(256), 0, c->stream, c->xyz, c->stride_f, c->N, d_out, d_n);
   std::vector<float> h((size_t)NBLK * 6);
@@ -361,7 +361,7 @@ vgs_status vgs_get_boundary(vgs_ctx* c, int64_t* n_records, uint64_t* code, int3
     if (cap < 1024) cap = 1u << 20;
     VGS_HIP_TRY(c, c->bnd_code.ensure(cap)); VGS_HIP_TRY(c, c->bnd_root.ensure(cap));
     VGS_HIP_TRY(c, c->counters.ensure(64));
-    unsigned long long* d_n = (unsigned long long*)c->counters.p + 32;
+    unsigned long long* d_n = (unsigned long long*)c->counters.p + CW_MGPU_NREC;
     VGS_HIP_TRY(c, hipMemsetAsync(d_n, 0, 8, c->stream));
     const uint8_t* mutual = c->conn.p + (size_t)c->U * c->adj_stride;
     if (c->U > 0)
@@ -465,7 +465,7 @@ vgs_status vgs_apply_tile_labels(vgs_ctx* c, int32_t local_base, const int32_t* 
     VGS_HIP_TRY(c, c->bnd_root2.ensure(2 * (size_t)n_roots + 2)); VGS_HIP_TRY(c, c->counters.ensure(64));
     int32_t* d_root = c->bnd_root2.p;
     int32_t* d_label = c->bnd_root2.p + n_roots;
-    unsigned int* d_bad = (unsigned int*)(c->counters.p + 33);
+    unsigned int* d_bad = (unsigned int*)(c->counters.p + CW_MGPU_BAD);
     VGS_HIP_TRY(c, hipMemsetAsync(d_bad, 0, 4, c->stream));
     VGS_HIP_TRY(c, hipMemcpyAsync(d_root, root, (size_t)n_roots * 4, hipMemcpyHostToDevice, c->stream));
     VGS_HIP_TRY(c, hipMemcpyAsync(d_label, label, (size_t)n_roots * 4, hipMemcpyHostToDevice, c->stream));
@@ -481,7 +481,7 @@ vgs_status vgs_apply_tile_labels(vgs_ctx* c, int32_t local_base, const int32_t* 
   hipLaunchKernelGGL(k_point_labels2, dim3((unsigned)((N + TB - 1) / TB)), dim3(TB), 0, c->stream, c->perm_b.p, c->pt_vox.p, c->vox_label.p, N,
                      c->pt_label.p);
   c->pt_labels_pending = false;   // every point's label has just been written
-  VGS_HIP_TRY(c, hipEventRecord(c->ev[15], c->stream));   // label downloads order themselves behind this (vgs_get_point_labels_async)
+  VGS_HIP_TRY(c, hipEventRecord(c->ev[EV_LABELS_END], c->stream));   // label downloads order themselves behind this (vgs_get_point_labels_async)
   c->labels_event_valid = true;
   VGS_HIP_TRY(c, hipGetLastError());
   VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -531,7 +531,7 @@ vgs_status vgs_apply_root_labels(vgs_ctx* c, const int32_t* root, const int32_t*
   hipLaunchKernelGGL(k_point_labels2, dim3((unsigned)((N + TB - 1) / TB)), dim3(TB), 0, c->stream, c->perm_b.p, c->pt_vox.p, c->vox_label.p, N,
                      c->pt_label.p);
   c->pt_labels_pending = false;   // every point's label has just been written
-  VGS_HIP_TRY(c, hipEventRecord(c->ev[15], c->stream));   // label downloads order themselves behind this (vgs_get_point_labels_async)
+  VGS_HIP_TRY(c, hipEventRecord(c->ev[EV_LABELS_END], c->stream));   // label downloads order themselves behind this (vgs_get_point_labels_async)
   c->labels_event_valid = true;
   VGS_HIP_TRY(c, hipGetLastError());
   VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -33,13 +33,7 @@ struct PlParams {
 #define PL_GRID_SMALL 8192   // workgroups of the one-wavefront builders (they stride over the work list)
 #define PL_GRID_BIG 512
 
-// pool bookkeeping in the context's counter words (zeroed with the local cut's counters at the start of the stage)
-#define PL_W_CURSOR 58   // entries handed out
-#define PL_W_WORK 59     // length of the work list (low half), of the redo list (high half)
-#define PL_W_FULL 60     // rows that found the pool exhausted
-#define PL_W_WORK2 61    // the second build's work / redo list lengths
-#define PL_W_WORK3 42    // the third's (three builds of one run may overlap on their streams: the wide classes' rows, the many hand-overs' rows,
-                         // the rows of the neighbourhoods the dense kernel passes on)
+// pool bookkeeping: the context's counter words PL_W_* (counter_words.hpp; zeroed with the local cut's counters at the start of the stage)
 
 // (barriers that order LDS traffic only: see pg_barrier in localcut_pg.hpp; one wavefront needs no s_barrier at all)
 template <int NWV>

@@ -88,7 +88,7 @@ vgs_status vgs_stage_svgs_group(vgs_ctx* c) {
   VGS_HIP_TRY(c, c->sort_tmp.ensure(std::max(sort_bytes, scan_bytes)));
   // stable sort by label: ascending point index inside a supervoxel, like points_label_map (SS:296-306)
   VGS_HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp.p, sort_bytes, c->sv_key_a.p, c->sv_key_b.p, c->perm_a.p, c->perm_b.p, (size_t)N, 0, 32, c->stream));
-  unsigned long long* d_cnt = (unsigned long long*)c->counters.p;
+  unsigned long long* d_cnt = (unsigned long long*)c->counters.p + CW_VOX_COUNTS;
   hipLaunchKernelGGL(k_sv_heads, dim3(nb), dim3(TB), 0, c->stream, c->sv_key_b.p, N, c->head_flag.p);
   hipLaunchKernelGGL(k_sv_count_valid, dim3(1), dim3(1), 0, c->stream, c->sv_key_b.p, N, d_cnt);
   uint32_t* scan = c->perm_a.p;
@@ -255,7 +255,7 @@ vgs_status vgs_stage_svgs_neighbours(vgs_ctx* c) {
   VGS_HIP_TRY(c, c->adj_key.ensure((size_t)S * SV_ROW));
   VGS_HIP_TRY(c, c->adj_cnt.ensure(S)); VGS_HIP_TRY(c, c->adj_mused.ensure(S));
   VGS_HIP_TRY(c, c->counters.ensure(64));
-  unsigned long long* d_ovf = (unsigned long long*)c->counters.p + 40;
+  unsigned long long* d_ovf = (unsigned long long*)c->counters.p + CW_SVGS_OVF;
   VGS_HIP_TRY(c, hipMemsetAsync(d_ovf, 0, 8, c->stream));
   hipLaunchKernelGGL(k_sv_neighbours, dim3((unsigned)S), dim3(64), 0, c->stream, c->node.p, S, cell, r2, c->hkey.p, c->hval.p, hbits,
                      c->cell_start.p, c->cell_id_b.p, c->adj_key.p, c->adj_cnt.p, c->adj_mused.p, d_ovf);

@@ -988,7 +988,7 @@ static vgs_status vgs_stage_vccs_pcl(vgs_ctx* c) {
   VGS_HIP_TRY(c, c->vc_ring.ensure(RING));
   unsigned int* const d_ring = c->vc_ring.p;
   int ring_at = RING;   // (forces the first fill)
-  unsigned int* d_changed = (unsigned int*)(c->counters.p + 56);   // (the final read-back of the largest label in use)
+  unsigned int* d_changed = (unsigned int*)(c->counters.p + CW_VCCS_CHANGED);   // (the final read-back of the largest label in use)
   int cur = 0;
   unsigned int* dbg_moved = nullptr;   // VGS_DEBUG: lanes that moved a voxel, per pass and round
   if (c->K.debug) { VGS_HIP_TRY(c, c->vc_dbg.ensure(128)); VGS_HIP_TRY(c, hipMemsetAsync(c->vc_dbg.p, 0, 512, c->stream)); dbg_moved = c->vc_dbg.p; }

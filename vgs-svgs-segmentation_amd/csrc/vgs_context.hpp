@@ -18,6 +18,7 @@
 
 #include "../../include/vgs.h"
 #include "vgs_math.h"
+#include "counter_words.hpp"
 #include "pairlist.hpp"
 
 typedef VgsNode NodeRec;
@@ -34,11 +35,17 @@ __device__ __forceinline__ int64_t vgs_xcd_item(unsigned int b, int64_t n) {
 #endif
 static inline unsigned int vgs_xcd_grid(int64_t n) { return (unsigned int)(((n + 7) >> 3) << 3); }
 
-// grow-only device buffer
+// grow-only device buffer; it owns its memory (freed with the buffer: a context's members by `delete`, a local on every return path)
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }   // (std::swap of two label buffers: merge.hip)
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+  ~DevBuf() { release(); }
   hipError_t ensure(size_t n) {
     if (n <= cap) return hipSuccess;
     if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
@@ -114,7 +121,6 @@ struct VgsKnobs {
   bool no_connbits = false;  // VGS_NO_CONNBITS: crossValidation searches the neighbour's row (the path of rounds 1-3)
   bool no_pairlists = false; // VGS_NO_PAIRLISTS: no pair lists (pairlist.hpp); hand-overs and wide classes take the kernels of round 4
   bool no_vote = false;      // VGS_NO_VOTE: every one-wavefront voxel tries the lazy schedule (LwParams::vote off)
-  int vote_force = 0;        // VGS_VOTE_FORCE (diagnostics): every one-wavefront voxel that is not a sample is handed over
   int ho_grid = -1;          // VGS_HO_GRID: workgroups of the hand-over kernels of the one-wavefront classes (-1: as many as the device holds at once; 0: one per row up to 16384)
   int pg_min_frac = 8;       // VGS_PG_MINFRAC: hand-overs go through the pair lists when they are more than 1/N of the used voxels (0: never)
   int pg_wide = 1;           // VGS_PG_WIDE: neighbourhoods above 128 voxels are cut from the pair lists (0: the multi-wavefront shell classes)
@@ -132,7 +138,7 @@ struct vgs_ctx {
   hipStream_t stream4 = nullptr;
   std::string err;
   int stage = ST_NONE;
-  void* pin = nullptr;   // 4 KB of pinned host memory: small read-backs land here (a pageable destination makes the copy blocking and slower)
+  void* pin = nullptr;   // VGS_PIN_BYTES of pinned host memory: small read-backs land here (a pageable destination makes the copy blocking and slower)
 
   // input
   const float* xyz = nullptr;  // device pointer (one of xyz_buf or the caller's)
@@ -155,7 +161,7 @@ struct vgs_ctx {
   int64_t staged_n = 0;
   int staged_stride = 12;
   bool pt_labels_pending = false;    // a tile's merge stage did not scatter the per-point labels (vgs_ensure_point_labels does, on request)
-  bool labels_event_valid = false;   // ev[15] has been recorded behind the last kernel that wrote pt_label
+  bool labels_event_valid = false;   // EV_LABELS_END has been recorded behind the last kernel that wrote pt_label
   bool d2h_open = false;       // vgs_get_point_labels_async has a copy in flight ...
   const int32_t* d2h_src = nullptr;   // ... out of this buffer
   int64_t N = 0;
@@ -234,8 +240,12 @@ struct vgs_ctx {
   DevBuf<uint32_t> pl_work;    // work list of rows, redo list
   bool pl_enabled = false;
   bool pl_enabled_at_launch = false;   // this run queued the pair-list chain for its hand-overs (stream4 joins stream3 before the stage's last event)
-  hipEvent_t ev_ho = nullptr, ev_ho2 = nullptr;   // hand-over lists built / pair-list chain done
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // merge stage: crossValidation's first pass done / the side chain beside the first unions done
+  hipEvent_t ev_ho = nullptr;    // local cut: the hand-over lists are built and LcGate's word is written; stream3 (behind k_ho_lists); stream4 waits (the pair-list chain)
+  hipEvent_t ev_ho2 = nullptr;   // local cut, two meanings by path: pair-list path of the wide classes -- their rows are built; stream2; stream4 waits.  Hand-overs through
+                                 // the pair lists -- the pair-list chain is done; stream4; stream3 waits before EV_LC_HO_DONE.  (The first wait is queued before the second record.)
+  hipEvent_t ev_fork = nullptr;  // merge stage, two meanings in turn: crossValidation's first pass done; main stream; stream3 waits (the side chain).  Then, its wait queued: the
+                                 // second pass over the rows put off done; side stream; the main stream waits (their unions)
+  hipEvent_t ev_join = nullptr;  // merge stage: the side chain is done (closestCheck; or, many hand-overs, the finish alone); side stream; the main stream waits
   float pl_w_ring = 0.0f;      // PairLists::w_ring of this run
 
   // local cut / merge
@@ -246,8 +256,23 @@ struct vgs_ctx {
   DevBuf<uint8_t> lc_pending;
   DevBuf<uint8_t> lc_defer_flag;   // per row: the first pass of crossValidation put it off (written by every row of that pass)
   DevBuf<uint32_t> lc_defer;
-  struct { bool open = false; bool dense = true; bool gated = false; /* merge's first pass looks at LcGate's word */ bool many = false; /* ... and found LC_MANY */ unsigned int grid_f = 0, grid_g = 0, nabc[5] = {0, 0, 0, 0, 0}; float tail_ms = 0.f; bool pg_xl_queued = false; /* class D's pair-list kernel queued for the extra-large one, which was launched */ bool rb_queued = false; /* vgs_localcut_finish_queue has queued the finish's read-back */ } lc_tail;
+  // what the launch half of the local cut (vgs_stage_localcut) leaves for its finish (vgs_localcut_finish) and for the merge stage
+  struct LcTail {
+    bool open = false;           // the hand-over kernels of a run may still be on the side streams: nobody has collected them yet
+    bool dense = true;           // the hand-overs went to the dense / pair-list kernels (false: VGS_NO_DENSE, the general kernel's fixed grids)
+    bool gated = false;          // merge's first pass looks at LcGate's word ...
+    bool many = false;           // ... and the finish found LC_MANY in it
+    unsigned int grid_f = 0;     // workgroups of the one-wavefront classes' hand-over launch
+    unsigned int grid_g = 0;     // ... of the wide classes' (the general kernel's fixed grid)
+    unsigned int nabc[5] = {0, 0, 0, 0, 0};   // class sizes A, B, C + C0, D, A1 as the host knew them at the launch
+    float tail_ms = 0.f;         // EV_LC_MAIN_END -> EV_LC_END of the last finish
+    bool pg_xl_queued = false;   // class D's pair-list kernel queued for the extra-large one, which was launched
+    bool rb_queued = false;      // vgs_localcut_finish_queue has queued the finish's read-back
+  } lc_tail;
   int64_t lc_diag[16] = {0};   // vgs_get_schedule_counters[_ex]
+#ifdef VGS_PROF
+  DevBuf<uint32_t> lc_dbg;     // per-voxel cycle / round counters of the diagnostics build (localcut.hip)
+#endif
   DevBuf<float> lc_ctab;      // screening table of the dense hand-over kernels (localcut.hip: lc_screen_table)
   float lc_ctab_key[8] = {0}, lc_ctab_scale = 0.0f;
   bool lc_ctab_valid = false;
@@ -365,7 +390,7 @@ struct vgs_ctx {
 
   int64_t counts[VGS_N_COUNTS] = {0};
   double times[VGS_T_COUNT] = {0};
-  hipEvent_t ev[16] = {nullptr};   // 14, 15: the label tail of the merge stage (VGS_T_LABELS); 15 also orders label downloads behind the label kernel
+  hipEvent_t ev[EV_COUNT] = {nullptr};   // indexed by VgsEvent (counter_words.hpp), which says who records and who waits
   hipEvent_t tev[VGS_T_COUNT][2] = {{nullptr}};   // stage timers: begin / end of every stage, read lazily (capi.hip: timed)
   bool tev_pending[VGS_T_COUNT] = {false};
 
@@ -423,7 +448,7 @@ struct vgs_ctx {
 
 // small device -> host read-back through the context's pinned scratch, followed by a wait for the stream
 static inline vgs_status vgs_readback(vgs_ctx* c, void* dst, const void* src_dev, size_t bytes) {
-  if (bytes > 4096 || !c->pin) {
+  if (bytes > VGS_PIN_BYTES || !c->pin) {
     VGS_HIP_TRY(c, hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
     VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return VGS_OK;
@@ -437,7 +462,7 @@ static inline vgs_status vgs_readback(vgs_ctx* c, void* dst, const void* src_dev
 // reads closestCheck's counters on a side stream while the main stream runs the first unions).  Lower half of the pinned scratch only:
 // the upper half may hold a split read-back (below) that has not been collected yet.
 static inline vgs_status vgs_readback_on(vgs_ctx* c, hipStream_t s, void* dst, const void* src_dev, size_t bytes) {
-  if (bytes > 2048 || !c->pin) {
+  if (bytes > VGS_PIN_SPLIT || !c->pin) {
     VGS_HIP_TRY(c, hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, s));
     VGS_HIP_TRY(c, hipStreamSynchronize(s));
     return VGS_OK;
@@ -467,14 +492,14 @@ __device__ __forceinline__ uint32_t vgs_cb_index(uint32_t p, int R) {
 // the number run while the host makes its round trip (20-30 us of an idle GPU per read-back otherwise: profiles/r04_step_timeline.txt).
 // Uses the upper half of the pinned scratch, so that a plain vgs_readback in between does not overwrite it.
 static inline vgs_status vgs_readback_begin(vgs_ctx* c, const void* src_dev, size_t bytes) {
-  if (bytes > 2048 || !c->pin || !c->ev_rb) return VGS_E_ARG;
-  VGS_HIP_TRY(c, hipMemcpyAsync((char*)c->pin + 2048, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+  if (bytes > VGS_PIN_BYTES - VGS_PIN_SPLIT || !c->pin || !c->ev_rb) return VGS_E_ARG;
+  VGS_HIP_TRY(c, hipMemcpyAsync((char*)c->pin + VGS_PIN_SPLIT, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
   VGS_HIP_TRY(c, hipEventRecord(c->ev_rb, c->stream));
   return VGS_OK;
 }
 static inline vgs_status vgs_readback_end(vgs_ctx* c, void* dst, size_t bytes) {
   VGS_HIP_TRY(c, hipEventSynchronize(c->ev_rb));
-  memcpy(dst, (char*)c->pin + 2048, bytes);
+  memcpy(dst, (char*)c->pin + VGS_PIN_SPLIT, bytes);
   return VGS_OK;
 }
 static inline bool vgs_can_split_readback(const vgs_ctx* c) { return c->pin != nullptr && c->ev_rb != nullptr; }

@@ -541,7 +541,7 @@ static vgs_status voxelize_sorted_table(vgs_ctx* c) {
   // sorted: code_b, perm_b (packed keys: perm_b is written by pass 1)
   uint32_t* tile_heads = c->vox_tile.p;            // after k_tile_offsets: heads in front of the tile
   uint32_t* tile_valid = c->vox_tile.p + n_tiles;
-  unsigned long long* d_cnt = (unsigned long long*)c->counters.p;   // number of finite points, number of voxels
+  unsigned long long* d_cnt = (unsigned long long*)c->counters.p + CW_VOX_COUNTS;   // number of finite points, number of voxels
   hipLaunchKernelGGL((k_run_counts<KeyT>), dim3((unsigned)n_tiles), dim3(VR_TB), 0, c->stream, code_b, N, pack_shift, c->perm_b.p, tile_heads, tile_valid);
   hipLaunchKernelGGL(k_tile_offsets, dim3(1), dim3(1024), 0, c->stream, tile_heads, tile_valid, n_tiles, d_cnt);
   unsigned long long h2[2] = {0, 0};
