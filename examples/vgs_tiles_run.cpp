@@ -29,6 +29,11 @@
 //   .labels.i32.  --patch-radius (finite, not negative; default the voxel size), --switch-ratio in [0, 1] (default 0.25) and --no-fill need
 //   --refine.  A second output line holds the counts "refine <working nodes> <examined> <changed> <filled> <beyond the strip>": summed
 //   over the ranks with --emulate, one line per rank (its own share, behind "rank <r>") with --rccl.
+//   --refined-segments <file.csv>, --refined-segment-boxes <file.csv>, --refined-matches <file.csv> [--refined-truth-matches <file.csv>]:
+//   the same tables for the REFINED labels (they need --refine): every rank hands its refined labels to
+//   vgs_tiles_point_label_descriptors, vgs_tiles_point_label_boxes (in the --box-frame) and vgs_tiles_compare_point_labels (against
+//   <prefix>.<r>.truth.i32) -- collectives; no label leaves its rank -- and rank 0 writes the files, with the columns of vgs_run's
+//   --refined-segments, --refined-segment-boxes, --refined-matches and --refined-truth-matches.
 //   All of them can be combined.  A missing companion option, a value out of range (1 .. 64 channels, 1 .. 1024 classes) and an attribute
 //   or truth file that is missing or whose size does not match the rank's points are usage errors: exit status 2, before any collective.
 #include <arpa/inet.h>
@@ -94,6 +99,7 @@ struct Job {
   std::string fields, classes;        // --segment-fields / --segment-classes
   int field_channels = 0, n_classes = 0;
   std::string matches, truth_matches;   // --segment-matches / --truth-matches
+  std::string r_segments, r_boxes, r_matches, r_truth_matches;   // --refined-segments / --refined-segment-boxes / --refined-matches / --refined-truth-matches
   bool refine = false, refine_fill = true;   // --refine, --no-fill
   float patch_radius = -1.0f, switch_ratio = -1.0f;   // --patch-radius / --switch-ratio (negative: the context's default)
 };
@@ -119,13 +125,60 @@ static int check_attribute_files(const Job& J, int rank) {
     const long long b = file_bytes(path);
     if (b != n * 4) { std::fprintf(stderr, "%s: %lld bytes, but %lld points x 4 = %lld\n", path.c_str(), b, n, n * 4); return 2; }
   }
-  if (!J.matches.empty()) {
+  if (!J.matches.empty() || !J.r_matches.empty()) {
     const std::string path = rank_file(J, rank, ".truth.i32");
     const long long b = file_bytes(path);
-    if (b < 0) { std::fprintf(stderr, "%s: cannot be read; --segment-matches needs one int32 for each of the %lld points of rank %d\n", path.c_str(), n, rank); return 2; }
+    if (b < 0) { std::fprintf(stderr, "%s: cannot be read; --segment-matches / --refined-matches need one int32 for each of the %lld points of rank %d\n", path.c_str(), n, rank); return 2; }
     if (b != n * 4) { std::fprintf(stderr, "%s: %lld bytes, but %lld points x 4 = %lld\n", path.c_str(), b, n, n * 4); return 2; }
   }
   return 0;
+}
+
+// the tables as the CSV writers of segments_csv.hpp take them
+struct DescArrays {
+  std::vector<int64_t> np; std::vector<int32_t> nn; std::vector<float> bb, e8; std::vector<double> ce, cv, ev, vv;
+  explicit DescArrays(size_t k) : np(k + 1), nn(k + 1), bb(6 * k + 1), e8(8 * k + 1), ce(3 * k + 1), cv(6 * k + 1), ev(3 * k + 1), vv(9 * k + 1) {}
+};
+static int write_descriptors(const std::string& path, size_t k, const DescArrays& A) {
+  std::vector<pcl::ClusterDescriptor> desc(k);
+  for (size_t i = 0; i < k; ++i) {
+    pcl::ClusterDescriptor& d = desc[i];
+    d.n_points = A.np[i]; d.n_nodes = A.nn[i];
+    for (int a = 0; a < 6; ++a) { d.bbox[a] = A.bb[6 * i + a]; d.cov[a] = A.cv[6 * i + a]; }
+    for (int a = 0; a < 3; ++a) { d.centroid[a] = A.ce[3 * i + a]; d.evals[a] = A.ev[3 * i + a]; }
+    for (int a = 0; a < 9; ++a) d.evecs[a] = A.vv[9 * i + a];
+    for (int a = 0; a < 8; ++a) d.eigen8[a] = A.e8[8 * i + a];
+  }
+  return writeSegmentsCsv(path, desc);
+}
+struct BoxArrays {
+  std::vector<double> ce, ha, fr, lo, hi;
+  explicit BoxArrays(size_t k) : ce(3 * k + 1), ha(3 * k + 1), fr(9 * k + 1), lo(3 * k + 1), hi(3 * k + 1) {}
+};
+static int write_boxes(const std::string& path, size_t k, const BoxArrays& A) {
+  std::vector<pcl::ClusterBox> boxes(k);
+  for (size_t i = 0; i < k; ++i) {
+    pcl::ClusterBox& b = boxes[i];
+    for (int a = 0; a < 3; ++a) { b.center[a] = A.ce[3 * i + a]; b.half[a] = A.ha[3 * i + a]; b.lo[a] = A.lo[3 * i + a]; b.hi[a] = A.hi[3 * i + a]; }
+    for (int a = 0; a < 9; ++a) b.frame[a] = A.fr[9 * i + a];
+  }
+  return writeBoxesCsv(path, boxes);
+}
+// the tables of the driver's last comparison (nc cells, G ids, K segment rows; m.summary is filled) into the match files; "" on success
+static std::string write_matches(vgs_tiles* t, int64_t nc, int64_t G, int64_t K, pcl::ClusterLabelComparison& m, const std::string& seg_path,
+                                 const std::string& truth_path) {
+  m.cell_seg.resize((size_t)nc); m.cell_ref.resize((size_t)nc); m.cell_n.resize((size_t)nc);
+  m.ref_id.resize((size_t)G); m.ref_points.resize((size_t)G); m.ref_dropped.resize((size_t)G); m.ref_best_seg.resize((size_t)G);
+  m.ref_best_n.resize((size_t)G); m.ref_best_iou.resize((size_t)G);
+  m.seg_annotated.resize((size_t)K); m.seg_refs.resize((size_t)K); m.seg_best_ref.resize((size_t)K); m.seg_best_n.resize((size_t)K);
+  m.seg_best_iou.resize((size_t)K);
+  if (vgs_tiles_get_label_comparison(t, m.cell_seg.data(), m.cell_ref.data(), m.cell_n.data(), m.ref_id.data(), m.ref_points.data(), m.ref_dropped.data(),
+                                     m.ref_best_seg.data(), m.ref_best_n.data(), m.ref_best_iou.data(), m.seg_annotated.data(), m.seg_refs.data(),
+                                     m.seg_best_ref.data(), m.seg_best_n.data(), m.seg_best_iou.data()) != VGS_OK)
+    return std::string("rank 0: ") + vgs_tiles_last_error_string(t);
+  if (writeSegmentMatchesCsv(seg_path, m) != 0) return "cannot write " + seg_path;
+  if (!truth_path.empty() && writeTruthMatchesCsv(truth_path, m) != 0) return "cannot write " + truth_path;
+  return "";
 }
 
 // one rank: load, run, save; returns 0 on success
@@ -137,7 +190,7 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
   if (!J.fields.empty() && !read_f32(rank_file(J, rank, ".fields.f32"), field)) { *err = "cannot read the fields of rank " + std::to_string(rank); return 1; }
   if (!J.classes.empty() && !read_i32(rank_file(J, rank, ".classes.i32"), cls)) { *err = "cannot read the classes of rank " + std::to_string(rank); return 1; }
   std::vector<int32_t> truth;
-  if (!J.matches.empty() && !read_i32(rank_file(J, rank, ".truth.i32"), truth)) { *err = "cannot read the truth ids of rank " + std::to_string(rank); return 1; }
+  if ((!J.matches.empty() || !J.r_matches.empty()) && !read_i32(rank_file(J, rank, ".truth.i32"), truth)) { *err = "cannot read the truth ids of rank " + std::to_string(rank); return 1; }
   vgs_tiles* t = nullptr;
   vgs_status s = vgs_tiles_create(&J.p, comm_kind, comm, rank, world, J.tx, J.ty, J.pitch, 0.0, 0.0, &t);
   if (s != VGS_OK) { *err = std::string("vgs_tiles_create: ") + vgs_last_error_string(nullptr); return 1; }
@@ -152,26 +205,12 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
   if (rc == 0 && !J.segments.empty()) {
     // the descriptors of the global segments: a collective of every rank, the same table on each; rank 0 writes it
     const size_t k = (size_t)*kept;
-    std::vector<int64_t> np(k + 1);
-    std::vector<int32_t> nn(k + 1);
-    std::vector<float> bb(6 * k + 1), e8(8 * k + 1);
-    std::vector<double> ce(3 * k + 1), cv(6 * k + 1), ev(3 * k + 1), vv(9 * k + 1);
+    DescArrays A(k);
     int64_t K = 0;
-    if (vgs_tiles_get_segment_descriptors(t, &K, np.data(), nn.data(), bb.data(), ce.data(), cv.data(), ev.data(), vv.data(), e8.data()) != VGS_OK) {
+    if (vgs_tiles_get_segment_descriptors(t, &K, A.np.data(), A.nn.data(), A.bb.data(), A.ce.data(), A.cv.data(), A.ev.data(), A.vv.data(), A.e8.data()) != VGS_OK) {
       *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
       rc = 1;
-    } else if (rank == 0) {
-      std::vector<pcl::ClusterDescriptor> desc(k);
-      for (size_t i = 0; i < k; ++i) {
-        pcl::ClusterDescriptor& d = desc[i];
-        d.n_points = np[i]; d.n_nodes = nn[i];
-        for (int a = 0; a < 6; ++a) { d.bbox[a] = bb[6 * i + a]; d.cov[a] = cv[6 * i + a]; }
-        for (int a = 0; a < 3; ++a) { d.centroid[a] = ce[3 * i + a]; d.evals[a] = ev[3 * i + a]; }
-        for (int a = 0; a < 9; ++a) d.evecs[a] = vv[9 * i + a];
-        for (int a = 0; a < 8; ++a) d.eigen8[a] = e8[8 * i + a];
-      }
-      if (writeSegmentsCsv(J.segments, desc) != 0) { *err = "cannot write " + J.segments; rc = 1; }
-    }
+    } else if (rank == 0 && write_descriptors(J.segments, k, A) != 0) { *err = "cannot write " + J.segments; rc = 1; }
   }
   if (rc == 0 && !J.graph.empty()) {
     // the adjacency graph of the global segments: the first call is a collective of every rank and leaves the table cached
@@ -198,20 +237,12 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
   if (rc == 0 && !J.boxes.empty()) {
     // the oriented boxes of the global segments: a collective of every rank, the same table on each; rank 0 writes it
     const size_t k = (size_t)*kept;
-    std::vector<double> ce(3 * k + 1), ha(3 * k + 1), fr(9 * k + 1), lo(3 * k + 1), hi(3 * k + 1);
+    BoxArrays A(k);
     int64_t K = 0;
-    if (vgs_tiles_get_segment_boxes(t, J.box_frame, &K, ce.data(), ha.data(), fr.data(), lo.data(), hi.data()) != VGS_OK) {
+    if (vgs_tiles_get_segment_boxes(t, J.box_frame, &K, A.ce.data(), A.ha.data(), A.fr.data(), A.lo.data(), A.hi.data()) != VGS_OK) {
       *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
       rc = 1;
-    } else if (rank == 0) {
-      std::vector<pcl::ClusterBox> boxes(k);
-      for (size_t i = 0; i < k; ++i) {
-        pcl::ClusterBox& b = boxes[i];
-        for (int a = 0; a < 3; ++a) { b.center[a] = ce[3 * i + a]; b.half[a] = ha[3 * i + a]; b.lo[a] = lo[3 * i + a]; b.hi[a] = hi[3 * i + a]; }
-        for (int a = 0; a < 9; ++a) b.frame[a] = fr[9 * i + a];
-      }
-      if (writeBoxesCsv(J.boxes, boxes) != 0) { *err = "cannot write " + J.boxes; rc = 1; }
-    }
+    } else if (rank == 0 && write_boxes(J.boxes, k, A) != 0) { *err = "cannot write " + J.boxes; rc = 1; }
   }
   if (rc == 0 && !J.fields.empty()) {
     // the statistics of this rank's attribute rows over the global segments: a collective of every rank, the same table on each
@@ -263,18 +294,8 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
       *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
       rc = 1;
     } else if (rank == 0) {
-      m.cell_seg.resize((size_t)nc); m.cell_ref.resize((size_t)nc); m.cell_n.resize((size_t)nc);
-      m.ref_id.resize((size_t)G); m.ref_points.resize((size_t)G); m.ref_dropped.resize((size_t)G); m.ref_best_seg.resize((size_t)G);
-      m.ref_best_n.resize((size_t)G); m.ref_best_iou.resize((size_t)G);
-      m.seg_annotated.resize((size_t)K); m.seg_refs.resize((size_t)K); m.seg_best_ref.resize((size_t)K); m.seg_best_n.resize((size_t)K);
-      m.seg_best_iou.resize((size_t)K);
-      if (vgs_tiles_get_label_comparison(t, m.cell_seg.data(), m.cell_ref.data(), m.cell_n.data(), m.ref_id.data(), m.ref_points.data(), m.ref_dropped.data(),
-                                         m.ref_best_seg.data(), m.ref_best_n.data(), m.ref_best_iou.data(), m.seg_annotated.data(), m.seg_refs.data(),
-                                         m.seg_best_ref.data(), m.seg_best_n.data(), m.seg_best_iou.data()) != VGS_OK) {
-        *err = std::string("rank 0: ") + vgs_tiles_last_error_string(t);
-        rc = 1;
-      } else if (writeSegmentMatchesCsv(J.matches, m) != 0) { *err = "cannot write " + J.matches; rc = 1; }
-      else if (!J.truth_matches.empty() && writeTruthMatchesCsv(J.truth_matches, m) != 0) { *err = "cannot write " + J.truth_matches; rc = 1; }
+      const std::string e = write_matches(t, nc, G, K, m, J.matches, J.truth_matches);
+      if (!e.empty()) { *err = e; rc = 1; }
     }
   }
   if (rc == 0 && J.refine) {
@@ -291,6 +312,35 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
     } else {
       fine.resize((size_t)n);
       if (!write_i32(rank_file(J, rank, ".refined.i32"), fine)) { *err = "cannot write the refined labels"; rc = 1; }
+    }
+    // the tables of the refined labelling, K = kept rows: collectives of every rank, the same tables on each; rank 0 writes them
+    const size_t k = (size_t)*kept;
+    if (rc == 0 && !J.r_segments.empty()) {
+      DescArrays A(k);
+      int64_t skipped = 0;
+      if (vgs_tiles_point_label_descriptors(t, fine.data(), n, *kept, &skipped, A.np.data(), A.nn.data(), A.bb.data(), A.ce.data(), A.cv.data(), A.ev.data(),
+                                            A.vv.data(), A.e8.data()) != VGS_OK) {
+        *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+        rc = 1;
+      } else if (rank == 0 && write_descriptors(J.r_segments, k, A) != 0) { *err = "cannot write " + J.r_segments; rc = 1; }
+    }
+    if (rc == 0 && !J.r_boxes.empty()) {
+      BoxArrays A(k);
+      if (vgs_tiles_point_label_boxes(t, fine.data(), n, *kept, J.box_frame, A.ce.data(), A.ha.data(), A.fr.data(), A.lo.data(), A.hi.data()) != VGS_OK) {
+        *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+        rc = 1;
+      } else if (rank == 0 && write_boxes(J.r_boxes, k, A) != 0) { *err = "cannot write " + J.r_boxes; rc = 1; }
+    }
+    if (rc == 0 && !J.r_matches.empty()) {
+      int64_t nc = 0, G = 0;
+      pcl::ClusterLabelComparison m;
+      if (vgs_tiles_compare_point_labels(t, fine.data(), *kept, truth.data(), n, &nc, &G, m.summary) != VGS_OK) {
+        *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+        rc = 1;
+      } else if (rank == 0) {
+        const std::string e = write_matches(t, nc, G, *kept, m, J.r_matches, J.r_truth_matches);
+        if (!e.empty()) { *err = e; rc = 1; }
+      }
     }
   }
   if (rc == 0) {
@@ -340,6 +390,10 @@ static bool exchange_id(ncclUniqueId* id, int rank, int world, const char* addr,
   return false;
 }
 
+static void print_usage(const char* exe) {
+  std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] [--refine [--patch-radius r] [--switch-ratio s] [--no-fill] [--refined-segments file.csv] [--refined-segment-boxes file.csv] [--refined-matches file.csv [--refined-truth-matches file.csv]]] <prefix>\n", exe);
+}
+
 int main(int argc, char** argv) {
   Job J;
   vgs_params_default_vgs(&J.p);
@@ -369,6 +423,10 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--classes") && a + 1 < argc) { J.n_classes = std::atoi(argv[++a]); have_classes = true; }
     else if (!std::strcmp(argv[a], "--segment-matches") && a + 1 < argc) J.matches = argv[++a];
     else if (!std::strcmp(argv[a], "--truth-matches") && a + 1 < argc) J.truth_matches = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-segments") && a + 1 < argc) J.r_segments = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-segment-boxes") && a + 1 < argc) J.r_boxes = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-matches") && a + 1 < argc) J.r_matches = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-truth-matches") && a + 1 < argc) J.r_truth_matches = argv[++a];
     else if (!std::strcmp(argv[a], "--refine")) J.refine = true;
     else if (!std::strcmp(argv[a], "--no-fill")) { J.refine_fill = false; refine_opts = true; }
     else if ((!std::strcmp(argv[a], "--patch-radius") || !std::strcmp(argv[a], "--switch-ratio")) && a + 1 < argc) {
@@ -385,7 +443,7 @@ int main(int argc, char** argv) {
     else if (argv[a][0] != '-') J.prefix = argv[a];
     else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
   }
-  if (mode < 0 || J.prefix.empty()) { std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] [--refine [--patch-radius r] [--switch-ratio s] [--no-fill]] <prefix>\n", argv[0]); return 2; }
+  if (mode < 0 || J.prefix.empty()) { print_usage(argv[0]); return 2; }
   if (!J.fields.empty() && !have_channels) { std::fprintf(stderr, "--segment-fields needs --field-channels <C>\n"); return 2; }
   if (J.fields.empty() && have_channels) { std::fprintf(stderr, "--field-channels needs --segment-fields <file.csv>\n"); return 2; }
   if (have_channels && (J.field_channels < 1 || J.field_channels > 64)) { std::fprintf(stderr, "--field-channels must be in 1 .. 64\n"); return 2; }
@@ -394,6 +452,12 @@ int main(int argc, char** argv) {
   if (have_classes && (J.n_classes < 1 || J.n_classes > 1024)) { std::fprintf(stderr, "--classes must be in 1 .. 1024\n"); return 2; }
   if (J.matches.empty() && !J.truth_matches.empty()) { std::fprintf(stderr, "--truth-matches needs --segment-matches <file.csv>\n"); return 2; }
   if (refine_opts && !J.refine) { std::fprintf(stderr, "--patch-radius / --switch-ratio / --no-fill need --refine\n"); return 2; }
+  if (!J.refine && (!J.r_segments.empty() || !J.r_boxes.empty() || !J.r_matches.empty() || !J.r_truth_matches.empty())) {
+    std::fprintf(stderr, "--refined-segments / --refined-segment-boxes / --refined-matches / --refined-truth-matches need --refine\n");
+    print_usage(argv[0]);
+    return 2;
+  }
+  if (J.r_matches.empty() && !J.r_truth_matches.empty()) { std::fprintf(stderr, "--refined-truth-matches needs --refined-matches <file.csv>\n"); return 2; }
   const int world = J.tx * J.ty;
   int64_t kept = 0, n_pts = 0, n_rec = 0;
   int64_t rcounts[5] = {0, 0, 0, 0, 0};

@@ -539,6 +539,49 @@ vgs_status vgs_compare_point_labels(vgs_ctx* ctx, const int32_t* seg_labels_host
                                     int64_t* n_refs, int64_t* summary /* 12 */);
 vgs_status vgs_compare_point_labels_device(vgs_ctx* ctx, const int32_t* seg_labels_dev, int64_t K, const int32_t* ref_dev, int64_t n,
                                            int64_t* n_cells, int64_t* n_refs, int64_t* summary /* 12 */);
+/* The same three tables for a tile context (the tiled driver, include/vgs_tiles.h: vgs_tiles_point_label_descriptors, _boxes and
+ * vgs_tiles_compare_point_labels build the global tables from what these leave).  Tile contexts only: VGS_E_STATE before the context is
+ * segmented and on a context that is not a tile context (the three entry points above keep refusing a tile context).  In all of them
+ * `labels` holds one int32 per point of the rank's OWN load: labels[i] belongs to cloud point own_first + i of vgs_set_own_point_range and
+ * n_own must equal that range's length.  Label l belongs to row l for 0 <= l < K, a negative label to no row; a label >= K is VGS_E_ARG,
+ * the message naming the first offending own index and its value.  0 <= K <= 2^31 - 1.
+ *
+ * vgs_own_point_label_moments: one moment record per label with at least one own finite point, in ascending label order, with the fields of
+ * vgs_get_own_segment_moments -- n_points the own finite points of the label, bbox6 their exact box, anchor3 the label's first own point
+ * in the sorted order (positions ascending), s9 the fp64 sums about it -- the pipeline of vgs_point_label_descriptors restricted to the
+ * own points.  *n_skipped counts the own points with a label >= 0 that lie outside the octree (not finite).
+ *   n_nodes and the pair records.  A voxel of the shared grid can hold points that two or four ranks loaded.  A voxel is SHARED on a
+ *   rank when its run of points in that context holds at least one own and at least one other point.  The first point of a voxel inside a
+ *   label's run is counted into the record's n_nodes when the voxel is not shared; in a shared voxel it is NOT counted but written as a
+ *   pair record (voxel code, label) of 16 bytes, in sorted order (label ascending, position ascending).  The driver counts the distinct
+ *   pairs over all ranks and adds them to the folded n_nodes.  With points loaded by region (no point outside its rank's region) every
+ *   rank that loaded a point of a straddling voxel sees the other ranks' points of it -- they lie within one voxel_size per axis, inside
+ *   the halo of 2 graph_size + voxel_size -- so all of them classify it as shared and it is counted exactly once.  With points OUTSIDE a
+ *   rank's region a straddling voxel may be counted twice in n_nodes; every other field stays exact.
+ * The records stay in the context until the next call, a run of the stages or new labels; vgs_get_own_point_label_moments copies them out
+ * (*n_records rows and *n_pairs pairs; any pointer may be NULL).  Bit-identical from call to call: no float atomics, no arrival order.
+ *
+ * vgs_get_own_point_label_extents: the contract of vgs_get_own_segment_extents over the own points of the caller's labelling.
+ *
+ * vgs_own_point_label_cells: the contract of vgs_own_label_cells with L[i] = seg_labels[i] (any negative label is the dropped row)
+ * instead of the voxel label of own point i; purely index-wise, so a non-finite own point takes part.  vgs_get_own_label_cells serves the
+ * cells. */
+vgs_status vgs_own_point_label_moments(vgs_ctx* ctx, int64_t K, const int32_t* labels_host, int64_t n_own, int64_t* n_records, int64_t* n_pairs,
+                                       int64_t* n_skipped);
+vgs_status vgs_own_point_label_moments_device(vgs_ctx* ctx, int64_t K, const int32_t* labels_dev, int64_t n_own, int64_t* n_records,
+                                              int64_t* n_pairs, int64_t* n_skipped);
+vgs_status vgs_get_own_point_label_moments(vgs_ctx* ctx, int32_t* label, int64_t* n_points, int32_t* n_nodes, float* bbox6, float* anchor3,
+                                           double* s9, uint64_t* pair_code, int32_t* pair_label);
+vgs_status vgs_get_own_point_label_extents(vgs_ctx* ctx, int64_t K, int32_t frame, const int32_t* labels_host, int64_t n_own,
+                                           const double* centroid3, const double* cov6, const double* evecs9, int64_t* n_records, int32_t* label,
+                                           double* lo3, double* hi3);
+vgs_status vgs_get_own_point_label_extents_device(vgs_ctx* ctx, int64_t K, int32_t frame, const int32_t* labels_dev, int64_t n_own,
+                                                  const double* centroid3, const double* cov6, const double* evecs9, int64_t* n_records,
+                                                  int32_t* label, double* lo3, double* hi3);
+vgs_status vgs_own_point_label_cells(vgs_ctx* ctx, int64_t K, const int32_t* seg_labels_host, const int32_t* ref_host, int64_t n_own,
+                                     int64_t* n_cells, int64_t* n_unannotated);
+vgs_status vgs_own_point_label_cells_device(vgs_ctx* ctx, int64_t K, const int32_t* seg_labels_dev, const int32_t* ref_dev, int64_t n_own,
+                                            int64_t* n_cells, int64_t* n_unannotated);
 
 /* Point-level label refinement at segment boundaries (no reference counterpart).  A point's label (vgs_get_point_labels) is the label of
  * its node -- a voxel for VGS, a supervoxel for SVGS -- so segment boundaries are staircases of whole nodes, and the points of voxels with

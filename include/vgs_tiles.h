@@ -338,6 +338,64 @@ enum { VGS_TILES_R_BAND = 0, VGS_TILES_R_EXCHANGE = 1, VGS_TILES_R_TABLE = 2, VG
 vgs_status vgs_tiles_get_refine_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_R_COUNT */);
 /* that refine's payload on this rank: band records it sent, bytes it put into the all-gather (header included, before padding) */
 vgs_status vgs_tiles_get_refine_payload(vgs_tiles* t, int64_t* band_records, int64_t* bytes_sent);
+/* Tables of ANY per-point labelling the caller supplies, over all ranks: the refined labels of vgs_tiles_get_refined_labels, ground-truth
+ * instances, anything made from the driver's output.  The rows, fields, types and rules are those of vgs_point_label_descriptors,
+ * vgs_point_label_boxes and vgs_compare_point_labels (include/vgs.h) with K rows of the caller's, over the points of all ranks.  `labels`
+ * holds one int32 per point the rank gave to vgs_tiles_set_points, in that order; n must equal that call's n.  Label l belongs to row l
+ * for 0 <= l < K, a negative label to no row, a label >= K is VGS_E_ARG; 0 <= K <= 2^31 - 1, the same on every rank.  Every output may be
+ * NULL.  The _device variants read the labelling (and ref) from HBM in place (this rank's device, complete before the call).
+ * Protocol (csrc/tiles.cpp).  Every point is handled by the rank that loaded it; no point, label or id leaves its rank, only per-label
+ * records; every rank receives the same bytes; there are no float atomics, so the tables are bit-identical from call to call and run to
+ * run.  Nothing is cached, because the input is the caller's: EVERY call is collective, K = 0 included (the ranks still agree on
+ * n_skipped).  vgs_tiles_run gains no launch and no collective; the run, the cached descriptor, box and graph tables and the refine halo
+ * table are not touched.
+ *   vgs_tiles_point_label_descriptors  ONE all_gather_varlen of 128-byte entries: a header (status word, moment-record count, K,
+ *     pair-record count, own n_skipped), this rank's moment records of its own points (vgs_own_point_label_moments, one small pipeline on
+ *     its GPU; the MomentRec wire format of the descriptor exchange), then its 16-byte pair records (uint64 voxel code, int32 label, int32
+ *     pad), eight to an entry.  Behind it, the same on every rank: vgs_tiles_fold_moments, unchanged; vgs_tiles_fold_label_pairs;
+ *     n_nodes = folded n_nodes + n_nodes_add; the per-segment algebra on the rank's GPU (vgs_segment_descriptors_from_moments).
+ *     *n_skipped is the sum over the ranks.  A label no point carries on any rank gives the empty row of vgs_point_label_descriptors.
+ *   n_nodes counts the distinct voxels of the shared grid among a label's points over ALL ranks, once: a rank counts the voxels that
+ *     hold none of another rank's points and sends (code, label) for those that do (include/vgs.h, vgs_own_point_label_moments); the
+ *     distinct pairs are counted behind the exchange.  With points loaded by region every rank that loaded a point of a straddling voxel
+ *     sees the others' points of it inside its halo, so all of them send the pair and it is counted exactly once.  With points outside
+ *     a rank's region a straddling voxel may be counted twice in n_nodes; every other field stays exact.
+ *   vgs_tiles_point_label_boxes  TWO collectives: the descriptor exchange above, of THIS labelling; then one all_gather_varlen of the
+ *     56-byte extent records of the box exchange (vgs_get_own_point_label_extents), folded by vgs_tiles_fold_extents unchanged and
+ *     finished by vgs_segment_boxes_from_extents.  Nothing outlives the call.
+ *   vgs_tiles_compare_point_labels  ONE collective: the cell exchange of vgs_tiles_compare_labels (K as one more word behind the cells),
+ *     fed by vgs_own_point_label_cells, then vgs_label_comparison_from_cells.  The tables become the driver's last comparison:
+ *     vgs_tiles_get_label_comparison serves them, with K rows for the segment table.
+ * Failures.  VGS_E_STATE before a run is decided locally (no collective).  Everything a rank can get wrong on its own -- a wrong n, a NULL
+ * labelling with n > 0, K out of range, a label >= K (the message names the first offending index and its value), a bad frame, a failing
+ * context call, the injected VGS_TILES_FAIL_AT=point_labels -- travels in the status word, so no peer waits: the failing rank returns its
+ * own status and message, the others VGS_E_PEER naming it.  Ranks that are each valid but pass different K all return VGS_E_ARG after the
+ * exchange; the message names the lowest rank that differs from rank 0. */
+vgs_status vgs_tiles_point_label_descriptors(vgs_tiles* t, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_skipped, int64_t* n_points,
+                                             int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3, double* evecs9,
+                                             float* eigen8);
+vgs_status vgs_tiles_point_label_descriptors_device(vgs_tiles* t, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_skipped,
+                                                    int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6,
+                                                    double* evals3, double* evecs9, float* eigen8);
+vgs_status vgs_tiles_point_label_boxes(vgs_tiles* t, const int32_t* labels_host, int64_t n, int64_t K, int32_t frame, double* center3, double* half3,
+                                       double* frame9, double* lo3, double* hi3);
+vgs_status vgs_tiles_point_label_boxes_device(vgs_tiles* t, const int32_t* labels_dev, int64_t n, int64_t K, int32_t frame, double* center3,
+                                              double* half3, double* frame9, double* lo3, double* hi3);
+vgs_status vgs_tiles_compare_point_labels(vgs_tiles* t, const int32_t* seg_labels_host, int64_t K, const int32_t* ref_host, int64_t n, int64_t* n_cells,
+                                          int64_t* n_refs, int64_t* summary /* 12 */);
+vgs_status vgs_tiles_compare_point_labels_device(vgs_tiles* t, const int32_t* seg_labels_dev, int64_t K, const int32_t* ref_dev, int64_t n,
+                                                 int64_t* n_cells, int64_t* n_refs, int64_t* summary /* 12 */);
+/* host arithmetic only, no context (tests): per label 0 .. K-1 the number of distinct (code, label) pairs among the pair records of all
+ * ranks, rec_off[r] .. rec_off[r + 1] being rank r's.  VGS_E_ARG for a label outside 0 .. K-1. */
+vgs_status vgs_tiles_fold_label_pairs(int world, const int64_t* rec_off /* world + 1 */, const uint64_t* code, const int32_t* label, int64_t K,
+                                      int32_t* n_nodes_add /* K */);
+/* host wall time of the last descriptor or box call of a point labelling on this rank, milliseconds (a box call: both of its collectives
+ * added): own records on the GPU (with upload and download), the exchange, the host fold, the finish on the GPU, total */
+enum { VGS_TILES_L_OWN = 0, VGS_TILES_L_EXCHANGE = 1, VGS_TILES_L_FOLD = 2, VGS_TILES_L_FINISH = 3, VGS_TILES_L_TOTAL = 4, VGS_TILES_L_COUNT = 5 };
+vgs_status vgs_tiles_get_point_label_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_L_COUNT */);
+/* that call's payload on this rank: moment records and pair records of its own, bytes it put into the all-gathers (headers included,
+ * before padding) */
+vgs_status vgs_tiles_get_point_label_payload(vgs_tiles* t, int64_t* own_records, int64_t* own_pairs, int64_t* bytes_sent);
 /* the rank's engine context (read-only use: counts, stage times) */
 vgs_ctx* vgs_tiles_context(vgs_tiles* t);
 

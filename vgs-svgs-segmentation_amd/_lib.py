@@ -128,6 +128,13 @@ SYMBOLS = [
     ("vgs_point_label_boxes_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
     ("vgs_compare_point_labels", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("vgs_compare_point_labels_device", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
+    ("vgs_own_point_label_moments", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
+    ("vgs_own_point_label_moments_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
+    ("vgs_get_own_point_label_moments", C.c_int, [_P] + [_P] * 8),
+    ("vgs_get_own_point_label_extents", C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_get_own_point_label_extents_device", C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    ("vgs_own_point_label_cells", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
+    ("vgs_own_point_label_cells_device", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
     ("vgs_get_own_segment_field_moments", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_own_segment_field_moments_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_segment_field_stats_from_moments", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

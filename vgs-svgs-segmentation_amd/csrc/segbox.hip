@@ -211,7 +211,7 @@ static vgs_status sbt_check_frame(vgs_ctx* c, int32_t frame, const char* fn) {
 
 // K rows of the descriptor table from the host into sbt_in (centroid3 | cov6 | evecs9) and their frames into sbt_frame: k_sb_frames, the
 // one copy of the frame rule.  The copies are staged before they return; the launches are left on the stream.
-static vgs_status sbt_upload_frames(vgs_ctx* c, int64_t K, int32_t frame, const double* centroid3, const double* cov6, const double* evecs9) {
+vgs_status sbt_upload_frames(vgs_ctx* c, int64_t K, int32_t frame, const double* centroid3, const double* cov6, const double* evecs9) {
   const size_t k = (size_t)K;
   VGS_HIP_TRY(c, c->sbt_in.ensure(18 * k)); VGS_HIP_TRY(c, c->sbt_frame.ensure(9 * k)); VGS_HIP_TRY(c, c->sbt_out.ensure(12 * k));
   double *cen = c->sbt_in.p, *cov = cen + 3 * k, *evec = cov + 6 * k;
@@ -223,7 +223,7 @@ static vgs_status sbt_upload_frames(vgs_ctx* c, int64_t K, int32_t frame, const 
 }
 
 // k_sb_final over `part` into sbt_out (lo3 | hi3 | half3 | center3, K rows each), about the rows of sbt_upload_frames
-static void sbt_launch_final(vgs_ctx* c, int64_t K, const uint32_t* seg_chunk, const double* part, uint32_t n_part) {
+void sbt_launch_final(vgs_ctx* c, int64_t K, const uint32_t* seg_chunk, const double* part, uint32_t n_part) {
   const size_t k = (size_t)K;
   double* o = c->sbt_out.p;
   hipLaunchKernelGGL(k_sb_final, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, seg_chunk, part, n_part, (uint32_t)K, c->sbt_in.p,

@@ -565,17 +565,20 @@ static vgs_status cmp_own_check(vgs_ctx* c, const char* fn, int64_t K, const int
 
 // steps 1-3 over the own points: pt_label[own_first + i] beside ref[i].  The cells stay in cmp_cell_i32 / cmp_cell_n (cmp_own_cells of
 // them, at a stride of cmp_ann) until vgs_get_own_label_cells copies them or another comparison takes the buffers.
-static vgs_status cmp_own_cells(vgs_ctx* c, const char* fn, int64_t K, const int32_t* ref_dev, int64_t* n_cells_out, int64_t* n_unann) {
+// seg_dev: the caller's labels of the own points in their order (vgs_own_point_label_cells; checked against K before), or nullptr for
+// the engine's own point labels.
+static vgs_status cmp_own_cells(vgs_ctx* c, const char* fn, int64_t K, const int32_t* ref_dev, int64_t* n_cells_out, int64_t* n_unann,
+                                const int32_t* seg_dev = nullptr) {
   c->cmp_valid = false; c->cmp_own_cells = -1;
   if (n_cells_out) *n_cells_out = 0;
   if (n_unann) *n_unann = 0;
   const int64_t N = c->n_own;
   if (N == 0) { c->cmp_ann = 0; c->cmp_own_cells = 0; return VGS_OK; }
-  vgs_status s = vgs_ensure_point_labels(c);   // a tile's merge stage leaves the scatter to whoever asks first
+  vgs_status s = seg_dev ? VGS_OK : vgs_ensure_point_labels(c);   // a tile's merge stage leaves the scatter to whoever asks first
   if (s != VGS_OK) return s;
   VGS_HIP_TRY(c, c->cmp_meta.ensure(CM_SLOTS));
   cmp_u64* meta = (cmp_u64*)c->cmp_meta.p;
-  const int32_t* labels = c->pt_label.p + c->own_first;
+  const int32_t* labels = seg_dev ? seg_dev : c->pt_label.p + c->own_first;
   VGS_HIP_TRY(c, hipMemsetAsync(meta, 0, CM_SLOTS * sizeof(uint64_t), c->stream));
   hipLaunchKernelGGL(k_cmp_scan_own, dim3(std::min(cmp_grid((uint64_t)N), CMP_SCAN_GRID)), dim3(CMP_TB), 0, c->stream, labels, ref_dev, N, meta);
   VGS_HIP_TRY(c, hipGetLastError());
@@ -614,6 +617,45 @@ extern "C" vgs_status vgs_own_label_cells(vgs_ctx* c, int64_t K, const int32_t* 
     VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
   }
   return cmp_own_cells(c, "vgs_own_label_cells", K, c->cmp_ref.p, n_cells, n_unannotated);
+}
+
+// The same cells with L[i] = seg_labels[i] (a caller's labelling of the own points, K rows of the caller's; any negative label the dropped
+// row) instead of the point labels: purely index-wise, so a non-finite own point takes part.  A label not below K is refused first, the
+// message naming the first own index and its value (pointseg.hip).  vgs_get_own_label_cells serves the cells.
+static vgs_status cmp_own_point_check(vgs_ctx* c, const char* fn, int64_t K, const int32_t* seg, const int32_t* ref, int64_t n_own) {
+  vgs_status s = cmp_own_check(c, fn, K, ref, n_own);
+  if (s != VGS_OK) return s;
+  if (!seg && n_own > 0) { c->err = std::string(fn) + ": seg_labels is NULL"; return VGS_E_ARG; }
+  return VGS_OK;
+}
+
+extern "C" vgs_status vgs_own_point_label_cells_device(vgs_ctx* c, int64_t K, const int32_t* seg_dev, const int32_t* ref_dev, int64_t n_own,
+                                                       int64_t* n_cells, int64_t* n_unannotated) {
+  if (!c) return VGS_E_ARG;
+  const char* fn = "vgs_own_point_label_cells_device";
+  vgs_status s = cmp_own_point_check(c, fn, K, seg_dev, ref_dev, n_own);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  if ((s = vgs_check_label_range(c, fn, seg_dev, n_own, K)) != VGS_OK) return s;
+  return cmp_own_cells(c, fn, K, ref_dev, n_cells, n_unannotated, seg_dev);
+}
+
+extern "C" vgs_status vgs_own_point_label_cells(vgs_ctx* c, int64_t K, const int32_t* seg_host, const int32_t* ref_host, int64_t n_own, int64_t* n_cells,
+                                                int64_t* n_unannotated) {
+  if (!c) return VGS_E_ARG;
+  const char* fn = "vgs_own_point_label_cells";
+  vgs_status s = cmp_own_point_check(c, fn, K, seg_host, ref_host, n_own);
+  if (s != VGS_OK) return s;
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  const int32_t* seg_dev = nullptr;
+  if ((s = vgs_upload_point_labels(c, seg_host, n_own, &seg_dev)) != VGS_OK) return s;
+  if ((s = vgs_check_label_range(c, fn, seg_dev, n_own, K)) != VGS_OK) return s;
+  if (n_own > 0) {
+    VGS_HIP_TRY(c, c->cmp_ref.ensure((size_t)n_own));
+    VGS_HIP_TRY(c, hipMemcpyAsync(c->cmp_ref.p, ref_host, (size_t)n_own * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
+  }
+  return cmp_own_cells(c, fn, K, c->cmp_ref.p, n_cells, n_unannotated, seg_dev);
 }
 
 extern "C" vgs_status vgs_get_own_label_cells(vgs_ctx* c, int32_t* cell_seg, int32_t* cell_ref, int64_t* cell_n) {

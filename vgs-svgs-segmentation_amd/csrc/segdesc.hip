@@ -165,7 +165,6 @@ __global__ __launch_bounds__(256) void k_sd_final(const float* __restrict__ xs, 
 // Tile contexts: one wavefront per segment folds the partials of k_sd_chunks_own exactly as k_sd_final does, counts the segment's
 // owned voxels (lane stride, then butterfly) and writes its moment record: SD_MREC doubles = own points, owned voxels, min[3], max[3]
 // (float values), anchor[3] (the first own point's floats; 0 without one), sum d[3], sum d d^T[6].
-#define SD_MREC 20
 __global__ __launch_bounds__(256) void k_sd_own_records(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs,
                                                         const uint32_t* __restrict__ ids, const uint32_t* __restrict__ seg_node,
                                                         const uint32_t* __restrict__ seg_chunk, const double* __restrict__ part, uint32_t n_part,

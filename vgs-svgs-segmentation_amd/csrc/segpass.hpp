@@ -16,6 +16,7 @@
 
 #ifdef __HIPCC__
 #define SD_REC 16                   // doubles per partial record: sum d[3], sum dd^T[6] (xx xy xz yy yz zz), min[3], max[3], (pad)
+#define SD_MREC 20                  // doubles per moment record of a tile context: points, nodes, min[3], max[3], anchor[3], sum d[3], sum dd^T[6]
 #define SB_REC 6                    // doubles per partial record of the box pass: min t[3], max t[3]
 
 // first position of the sorted keys (n of them) that is not below k: the start of label k's run

@@ -7,7 +7,7 @@
 // the next one (they would wait for ever: ADVICE r3).  So a failing step only records its status (`carry`: TCARRY, inject), the rank
 // still joins the next collective with that status in its payload's header, and every rank reads the headers and leaves with the same
 // verdict (agreed): the failing rank its own error, the others VGS_E_PEER naming the lowest failing rank.  A failure BEHIND a call's last
-// collective is returned and kept in t->pending (behind_collective), and the next collective's header carries it.  The seven collectives
+// collective is returned and kept in t->pending (behind_collective), and the next collective's header carries it.  The collectives
 // after vgs_tiles_run all read: open_collective (guard, carry = pending, injection) -> own records, header filled in -> exchange (ONE
 // all_gather_varlen + the scan of the headers) -> fold -> behind_collective(finish on this rank's GPU).  vgs_tiles_set_points, chain_grid
 // and the boundary exchange of vgs_tiles_run carry the status in payloads of their own shapes and share first_bad_rank and agreed.
@@ -338,6 +338,30 @@ bool fold_edges(const std::vector<std::vector<EdgeRec>>& ranks, int64_t K, std::
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------ pair records of a point labelling
+// One head flag of one rank in a voxel that holds points of several ranks (vgs_own_point_label_moments): the voxel's code and the label.
+struct PairRec {
+  uint64_t code = 0;
+  int32_t label = 0, pad = 0;
+};
+static_assert(sizeof(PairRec) == 16, "PairRec is the exchange's wire format");
+
+// Per label 0 .. K-1 the number of distinct (code, label) pairs among all ranks' records: a voxel that several ranks flagged for the same
+// label is one node of that label.  The same integers on every rank whatever the order.  False for a label outside 0 .. K-1.
+bool fold_label_pairs(const std::vector<std::vector<PairRec>>& ranks, int64_t K, std::vector<int32_t>& add) {
+  add.assign((size_t)K, 0);
+  std::vector<std::pair<int32_t, uint64_t>> all;
+  for (const std::vector<PairRec>& R : ranks)
+    for (const PairRec& p : R) {
+      if (p.label < 0 || (int64_t)p.label >= K) return false;
+      all.emplace_back(p.label, p.code);
+    }
+  std::sort(all.begin(), all.end());
+  all.erase(std::unique(all.begin(), all.end()), all.end());
+  for (const auto& p : all) ++add[(size_t)p.first];
+  return true;
+}
+
 // ------------------------------------------------------------------------------------------------ box extents
 // One rank's extents of one global label (vgs_get_own_segment_extents); the payload of the box exchange.  Its first entry is the header:
 // label = the rank's status word, pad = 0, lo[0] = its record count.
@@ -522,9 +546,10 @@ template <typename F> int first_bad_rank(int world, F bad) {
 // Where a rank can be told to fail (tests of the agreed-status protocol: VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=<name>).  points, grid and
 // stages: before that phase's collective; upload: behind the last collective of vgs_tiles_set_points; the others: before the exchange of
 // that post-run collective (fields: vgs_tiles_segment_field_stats and vgs_tiles_segment_class_histogram alike; refine:
-// vgs_tiles_refine_point_labels).
-enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_REFINE, PH_COUNT };
-const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare", "refine"};
+// vgs_tiles_refine_point_labels; point_labels: the descriptor exchange of vgs_tiles_point_label_descriptors / _boxes and the cell exchange
+// of vgs_tiles_compare_point_labels).
+enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_REFINE, PH_POINT_LABELS, PH_COUNT };
+const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare", "refine", "point_labels"};
 
 // Phase clock of one call: lap(slot) gives the slot the host wall time since the last lap (the start, for the first), total(slot) the
 // time from the start to the last lap.  Milliseconds.  vgs_tiles_run stamps t->times as it goes; a post-run collective stamps an array of
@@ -591,6 +616,9 @@ struct vgs_tiles {
   bool band_valid = false, rf_valid = false;
   double rtimes[VGS_TILES_R_COUNT] = {0};
   int64_t r_band = 0, r_bytes = 0;
+  // the last table of a caller's point labelling (nothing of it is cached): phases, own moment records, own pair records, bytes sent
+  double ltimes[VGS_TILES_L_COUNT] = {0};
+  int64_t l_own = 0, l_pairs = 0, l_bytes = 0;
   std::string err;
 };
 
@@ -987,6 +1015,221 @@ vgs_status vgs_tiles_get_segment_descriptors(vgs_tiles* t, int64_t* K, int64_t* 
 
 vgs_status vgs_tiles_get_descriptor_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::dtimes, ms, n); }
 
+// ------------------------------------------------------------------------------------------------ tables of a caller's point labelling
+// Descriptors of any per-point labelling over the ranks: no point, label or id travels, every point is handled by the rank that loaded it.
+// This rank's moment and pair records of its own points (vgs_own_point_label_moments, one small pipeline on its GPU) -> ONE
+// all_gather_varlen of 128-byte entries: a header (status word, moment-record count; K, pair-record count and own n_skipped as int64 in the
+// first three slots of s), the moment records, then the 16-byte pair records, eight to an entry -> fold_moments and fold_label_pairs, the
+// same on every rank -> n_nodes = folded n_nodes + distinct pairs -> the per-segment algebra on this rank's GPU.  Nothing is cached (the
+// input is the caller's), so every call is collective, K = 0 included.  Everything a rank can get wrong on its own is found by the context
+// call and travels in the status word; ranks that are each valid but pass different K all leave with VGS_E_ARG behind the exchange.
+namespace {
+struct LabelTable {
+  std::vector<int64_t> npts;
+  std::vector<int32_t> nnodes;
+  std::vector<float> bbox, eig8;
+  std::vector<double> cen, cov, eval, evec;
+  int64_t n_skipped = 0;
+};
+constexpr size_t PAIRS_PER_ENTRY = sizeof(MomentRec) / sizeof(PairRec);
+}  // namespace
+
+static vgs_status label_descriptors(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t n, int64_t K, vgs_status carry,
+                                    double* ms, LabelTable& D) {
+  Stopwatch sw(ms);
+  std::vector<MomentRec> payload(1);
+  int64_t n_rec = 0, n_pairs = 0, n_skip = 0;
+  if (carry == VGS_OK) {
+    TCARRY_AS(on_device ? vgs_own_point_label_moments_device : vgs_own_point_label_moments,
+              on_device ? "vgs_own_point_label_moments_device" : "vgs_own_point_label_moments", t->ctx, K, labels, n, &n_rec, &n_pairs, &n_skip);
+    if (carry != VGS_OK) { n_rec = 0; n_pairs = 0; n_skip = 0; }
+    const size_t nr = (size_t)n_rec, np = (size_t)n_pairs;
+    std::vector<int32_t> lab(nr + 1), nn(nr + 1), pl(np + 1);
+    std::vector<int64_t> pts(nr + 1);
+    std::vector<float> bb(6 * nr + 1), an(3 * nr + 1);
+    std::vector<double> sm(9 * nr + 1);
+    std::vector<uint64_t> pc(np + 1);
+    if (carry == VGS_OK) TCARRY(vgs_get_own_point_label_moments(t->ctx, lab.data(), pts.data(), nn.data(), bb.data(), an.data(), sm.data(), pc.data(), pl.data()));
+    if (carry == VGS_OK) {
+      payload.reserve(1 + nr + (np + PAIRS_PER_ENTRY - 1) / PAIRS_PER_ENTRY);
+      for (size_t i = 0; i < nr; ++i) payload.push_back(pack_moment(lab.data(), pts.data(), nn.data(), bb.data(), an.data(), sm.data(), i));
+      payload.resize(1 + nr + (np + PAIRS_PER_ENTRY - 1) / PAIRS_PER_ENTRY);
+      PairRec* pr = reinterpret_cast<PairRec*>(payload.data() + 1 + nr);
+      for (size_t i = 0; i < np; ++i) { pr[i].code = pc[i]; pr[i].label = pl[i]; pr[i].pad = 0; }
+    } else { n_rec = 0; n_pairs = 0; n_skip = 0; }
+  }
+  set_header(payload[0], carry, (size_t)n_rec);
+  {
+    const int64_t w[3] = {K, n_pairs, n_skip};
+    std::memcpy(payload[0].s, w, sizeof(w));
+  }
+  sw.lap(VGS_TILES_L_OWN);
+  std::vector<std::vector<MomentRec>> gathered;
+  TRY(exchange(t, carry, payload, "point_labels", sw, VGS_TILES_L_EXCHANGE, gathered));
+  // every rank was valid on its own: do they describe the same table, and is every payload as long as its header says?
+  const size_t world = gathered.size();
+  std::vector<int64_t> hk(world), hp(world), hs(world), hr(world);
+  for (size_t r = 0; r < world; ++r) {
+    int64_t w[3];
+    std::memcpy(w, gathered[r][0].s, sizeof(w));
+    hk[r] = w[0]; hp[r] = w[1]; hs[r] = w[2]; hr[r] = gathered[r][0].n_points;
+  }
+  for (size_t r = 1; r < world; ++r)
+    if (hk[r] != hk[0]) return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed K = " + std::to_string(hk[r]) + ", rank 0 passed " + std::to_string(hk[0]));
+  for (size_t r = 0; r < world; ++r)
+    if (hr[r] < 0 || hp[r] < 0 || gathered[r].size() != 1 + (size_t)hr[r] + ((size_t)hp[r] + PAIRS_PER_ENTRY - 1) / PAIRS_PER_ENTRY)
+      return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
+  std::vector<std::vector<MomentRec>> recs(world);
+  std::vector<std::vector<PairRec>> pairs(world);
+  D.n_skipped = 0;
+  for (size_t r = 0; r < world; ++r) {
+    recs[r].assign(gathered[r].begin() + 1, gathered[r].begin() + 1 + (ptrdiff_t)hr[r]);
+    pairs[r].resize((size_t)hp[r]);
+    if (hp[r] > 0) std::memcpy(pairs[r].data(), gathered[r].data() + 1 + hr[r], (size_t)hp[r] * sizeof(PairRec));
+    D.n_skipped += hs[r];
+  }
+  const size_t k1 = (size_t)K;
+  std::vector<int64_t> npts;
+  std::vector<int32_t> nnodes, add;
+  std::vector<float> bbox, anchor;
+  std::vector<double> s9;
+  if (!fold_moments(recs, K, npts, nnodes, bbox, anchor, s9) || !fold_label_pairs(pairs, K, add)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= K");
+  for (size_t k = 0; k < k1; ++k) nnodes[k] += add[k];
+  sw.lap(VGS_TILES_L_FOLD);
+  D.npts.resize(k1); D.nnodes.resize(k1); D.bbox.resize(6 * k1); D.cen.resize(3 * k1); D.cov.resize(6 * k1); D.eval.resize(3 * k1); D.evec.resize(9 * k1);
+  D.eig8.resize(8 * k1);
+  TRY(behind_collective(t, vgs_segment_descriptors_from_moments(t->ctx, K, npts.data(), nnodes.data(), bbox.data(), anchor.data(), s9.data(), D.npts.data(), D.nnodes.data(),
+                                                                D.bbox.data(), D.cen.data(), D.cov.data(), D.eval.data(), D.evec.data(), D.eig8.data()),
+                        "vgs_segment_descriptors_from_moments"));
+  sw.lap(VGS_TILES_L_FINISH);
+  sw.total(VGS_TILES_L_TOTAL);
+  t->l_own = n_rec; t->l_pairs = n_pairs; t->l_bytes = (int64_t)(payload.size() * sizeof(MomentRec));
+  return VGS_OK;
+}
+
+static vgs_status tiles_label_descriptors(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t n, int64_t K, int64_t* n_skipped,
+                                          int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3,
+                                          double* evecs9, float* eigen8) {
+  if (!t) return VGS_E_ARG;
+  vgs_status carry;
+  TRY(open_collective(t, fn, PH_POINT_LABELS, carry));
+  double ms[VGS_TILES_L_COUNT] = {0};
+  LabelTable D;
+  TRY(label_descriptors(t, fn, on_device, labels, n, K, carry, ms, D));
+  std::copy(ms, ms + VGS_TILES_L_COUNT, t->ltimes);
+  if (n_skipped) *n_skipped = D.n_skipped;
+  put(D.npts, n_points); put(D.nnodes, n_nodes); put(D.bbox, bbox6); put(D.cen, centroid3); put(D.cov, cov6); put(D.eval, evals3); put(D.evec, evecs9);
+  put(D.eig8, eigen8);
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_point_label_descriptors(vgs_tiles* t, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_skipped, int64_t* n_points,
+                                             int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3, double* evecs9,
+                                             float* eigen8) {
+  return tiles_label_descriptors(t, "vgs_tiles_point_label_descriptors", false, labels_host, n, K, n_skipped, n_points, n_nodes, bbox6, centroid3, cov6, evals3,
+                                 evecs9, eigen8);
+}
+
+vgs_status vgs_tiles_point_label_descriptors_device(vgs_tiles* t, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_skipped, int64_t* n_points,
+                                                    int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3, double* evecs9,
+                                                    float* eigen8) {
+  return tiles_label_descriptors(t, "vgs_tiles_point_label_descriptors_device", true, labels_dev, n, K, n_skipped, n_points, n_nodes, bbox6, centroid3, cov6,
+                                 evals3, evecs9, eigen8);
+}
+
+// Boxes of a caller's point labelling: TWO collectives -- the descriptor exchange above, of THIS labelling, then one exchange of this rank's
+// extent records (vgs_get_own_point_label_extents about the global centroids, in the frames made from the global rows), folded by
+// fold_extents and finished by vgs_segment_boxes_from_extents.  A bad frame travels in the first status word.  Nothing outlives the call.
+static vgs_status tiles_label_boxes(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t n, int64_t K, int32_t frame,
+                                    double* center3, double* half3, double* frame9, double* lo3, double* hi3) {
+  if (!t) return VGS_E_ARG;
+  vgs_status carry;
+  TRY(open_collective(t, fn, PH_POINT_LABELS, carry));
+  if (carry == VGS_OK && frame != VGS_BOX_PRINCIPAL && frame != VGS_BOX_UPRIGHT) {
+    carry = VGS_E_ARG;
+    t->err = std::string(fn) + ": frame must be VGS_BOX_PRINCIPAL (0) or VGS_BOX_UPRIGHT (1)";
+  }
+  double ms[VGS_TILES_L_COUNT] = {0};
+  LabelTable D;
+  {
+    // a failure of this rank BEHIND the first collective (it newly sets t->pending; the peers' tables are complete and they go on) travels
+    // in the second exchange's status word
+    const vgs_status before = t->pending;
+    const vgs_status sd = label_descriptors(t, fn, on_device, labels, n, K, carry, ms, D);
+    if (sd != VGS_OK && !(before == VGS_OK && t->pending != VGS_OK)) return sd;
+  }
+  carry = t->pending;
+  const size_t k1 = (size_t)K;
+  double ms2[VGS_TILES_L_COUNT] = {0};
+  Stopwatch sw(ms2);
+  std::vector<ExtentRec> payload(1);
+  if (carry == VGS_OK && K > 0) {
+    std::vector<int32_t> lab(k1);
+    std::vector<double> lo(3 * k1), hi(3 * k1);
+    int64_t nr = 0;
+    TCARRY_AS(on_device ? vgs_get_own_point_label_extents_device : vgs_get_own_point_label_extents,
+              on_device ? "vgs_get_own_point_label_extents_device" : "vgs_get_own_point_label_extents", t->ctx, K, frame, labels, n, D.cen.data(), D.cov.data(),
+              D.evec.data(), &nr, lab.data(), lo.data(), hi.data());
+    if (carry == VGS_OK) payload.reserve(1 + (size_t)nr);
+    if (carry == VGS_OK) for (size_t i = 0; i < (size_t)nr; ++i) payload.push_back(pack_extent(lab.data(), lo.data(), hi.data(), i));
+  }
+  set_header(payload[0], carry, payload.size() - 1);
+  sw.lap(VGS_TILES_L_OWN);
+  std::vector<std::vector<ExtentRec>> gathered;
+  TRY(exchange(t, carry, payload, "point_labels", sw, VGS_TILES_L_EXCHANGE, gathered));
+  strip_headers(gathered);
+  std::vector<double> lo, hi;
+  std::vector<uint8_t> reached;
+  if (!fold_extents(gathered, K, lo, hi, reached)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= K");
+  // a row no record reaches (no labelled point anywhere): lo = hi = 0, so half = 0 and centre = centroid
+  for (size_t k = 0; k < k1; ++k) if (!reached[k]) for (int a = 0; a < 3; ++a) { lo[3 * k + a] = 0.0; hi[3 * k + a] = 0.0; }
+  sw.lap(VGS_TILES_L_FOLD);
+  std::vector<double> ce(3 * k1), ha(3 * k1), fr(9 * k1);
+  TRY(behind_collective(t, vgs_segment_boxes_from_extents(t->ctx, K, frame, D.cen.data(), D.cov.data(), D.evec.data(), lo.data(), hi.data(), ce.data(), ha.data(), fr.data()),
+                        "vgs_segment_boxes_from_extents"));
+  sw.lap(VGS_TILES_L_FINISH);
+  sw.total(VGS_TILES_L_TOTAL);
+  for (int i = 0; i < VGS_TILES_L_COUNT; ++i) t->ltimes[i] = ms[i] + ms2[i];   // both collectives of the call
+  t->l_bytes += (int64_t)(payload.size() * sizeof(ExtentRec));
+  put(ce, center3); put(ha, half3); put(fr, frame9); put(lo, lo3); put(hi, hi3);
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_point_label_boxes(vgs_tiles* t, const int32_t* labels_host, int64_t n, int64_t K, int32_t frame, double* center3, double* half3,
+                                       double* frame9, double* lo3, double* hi3) {
+  return tiles_label_boxes(t, "vgs_tiles_point_label_boxes", false, labels_host, n, K, frame, center3, half3, frame9, lo3, hi3);
+}
+
+vgs_status vgs_tiles_point_label_boxes_device(vgs_tiles* t, const int32_t* labels_dev, int64_t n, int64_t K, int32_t frame, double* center3,
+                                              double* half3, double* frame9, double* lo3, double* hi3) {
+  return tiles_label_boxes(t, "vgs_tiles_point_label_boxes_device", true, labels_dev, n, K, frame, center3, half3, frame9, lo3, hi3);
+}
+
+vgs_status vgs_tiles_get_point_label_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::ltimes, ms, n); }
+
+vgs_status vgs_tiles_get_point_label_payload(vgs_tiles* t, int64_t* own_records, int64_t* own_pairs, int64_t* bytes_sent) {
+  if (!t) return VGS_E_ARG;
+  if (own_records) *own_records = t->l_own;
+  if (own_pairs) *own_pairs = t->l_pairs;
+  if (bytes_sent) *bytes_sent = t->l_bytes;
+  return VGS_OK;
+}
+
+// host arithmetic only (tests): the pair fold on flattened per-rank records
+vgs_status vgs_tiles_fold_label_pairs(int world, const int64_t* rec_off, const uint64_t* code, const int32_t* label, int64_t K, int32_t* n_nodes_add) {
+  if (world < 1 || !rec_off || K < 0 || (K > 0 && !n_nodes_add)) return VGS_E_ARG;
+  if (rec_off[world] > 0 && (!code || !label)) return VGS_E_ARG;
+  std::vector<std::vector<PairRec>> ranks((size_t)world);
+  for (int r = 0; r < world; ++r) {
+    if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
+    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) { PairRec p; p.code = code[i]; p.label = label[i]; ranks[(size_t)r].push_back(p); }
+  }
+  std::vector<int32_t> add;
+  if (!fold_label_pairs(ranks, K, add)) return VGS_E_ARG;
+  std::copy(add.begin(), add.end(), n_nodes_add);
+  return VGS_OK;
+}
+
 // Boxes over the ranks: the global descriptor table (its own collective when it is not cached) -> this rank's extents of its own points
 // about the global centroids, in the frames made from the global rows (one small pipeline on its GPU) -> ONE all_gather_varlen of the
 // records with a header of record count and status word -> the same host fold on every rank (min / max) -> half and centre on this
@@ -1203,20 +1446,26 @@ vgs_status vgs_tiles_get_field_payload(vgs_tiles* t, int64_t* own_records, int64
 // vgs_label_comparison_from_cells on this rank's context, which merges them and builds the tables on the GPU: there is no host fold.
 // Nothing is cached (the input is the caller's), so every call is collective.  Everything a rank can get wrong on its own -- n, a NULL
 // input, a failing context call -- is found by the context call and travels in the status word.
+// POINT (vgs_tiles_compare_point_labels): the cells pair a labelling of the caller's (seg, K_in rows; vgs_own_point_label_cells) with ref
+// instead of the run's labels; K_in travels as one more word behind the cells, and ranks that pass different K all leave with VGS_E_ARG.
 static vgs_status tiles_compare(vgs_tiles* t, const char* fn, bool on_device, const int32_t* ref, int64_t n, int64_t* K, int64_t* n_cells,
-                                int64_t* n_refs, int64_t* summary) {
+                                int64_t* n_refs, int64_t* summary, bool point = false, const int32_t* seg = nullptr, int64_t K_in = 0) {
   if (!t) return VGS_E_ARG;
   if (K) *K = t->kept;
   vgs_status carry;
-  TRY(open_collective(t, fn, PH_COMPARE, carry));
-  const int64_t Kg = t->kept;
+  TRY(open_collective(t, fn, point ? PH_POINT_LABELS : PH_COMPARE, carry));
+  const int64_t Kg = point ? K_in : t->kept;
   t->cmp_valid = false;
   double ms[VGS_TILES_C_COUNT] = {0};
   Stopwatch sw(ms);
   std::vector<int64_t> payload(3, 0);
   int64_t n_own_cells = 0, n_unann = 0;
   if (carry == VGS_OK) {
-    TCARRY_AS(on_device ? vgs_own_label_cells_device : vgs_own_label_cells, on_device ? "vgs_own_label_cells_device" : "vgs_own_label_cells", t->ctx, Kg, ref, n, &n_own_cells, &n_unann);
+    if (point)
+      TCARRY_AS(on_device ? vgs_own_point_label_cells_device : vgs_own_point_label_cells,
+                on_device ? "vgs_own_point_label_cells_device" : "vgs_own_point_label_cells", t->ctx, Kg, seg, ref, n, &n_own_cells, &n_unann);
+    else
+      TCARRY_AS(on_device ? vgs_own_label_cells_device : vgs_own_label_cells, on_device ? "vgs_own_label_cells_device" : "vgs_own_label_cells", t->ctx, Kg, ref, n, &n_own_cells, &n_unann);
     std::vector<int32_t> cs((size_t)n_own_cells + 1), cr((size_t)n_own_cells + 1);
     std::vector<int64_t> cn((size_t)n_own_cells + 1);
     if (carry == VGS_OK) TCARRY(vgs_get_own_label_cells(t->ctx, cs.data(), cr.data(), cn.data()));
@@ -1229,9 +1478,16 @@ static vgs_status tiles_compare(vgs_tiles* t, const char* fn, bool on_device, co
     } else { n_own_cells = 0; n_unann = 0; }
   }
   set_header(payload, carry, n_own_cells, n_unann);
+  if (point) payload.push_back(Kg);
   sw.lap(VGS_TILES_C_OWN);
   std::vector<std::vector<int64_t>> gathered;
-  TRY(exchange(t, carry, payload, "compare", sw, VGS_TILES_C_EXCHANGE, gathered));
+  TRY(exchange(t, carry, payload, point ? "point_labels" : "compare", sw, VGS_TILES_C_EXCHANGE, gathered));
+  if (point) {
+    for (size_t r = 1; r < gathered.size(); ++r)
+      if (gathered[r].back() != gathered[0].back())
+        return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed K = " + std::to_string(gathered[r].back()) + ", rank 0 passed " + std::to_string(gathered[0].back()));
+    for (std::vector<int64_t>& g : gathered) g.pop_back();
+  }
   TRY(check_word_payloads(t, fn, gathered, 2, nullptr));
   size_t n_in = 0;
   int64_t unann = 0;
@@ -1260,6 +1516,16 @@ vgs_status vgs_tiles_compare_labels(vgs_tiles* t, const int32_t* ref_host, int64
 vgs_status vgs_tiles_compare_labels_device(vgs_tiles* t, const int32_t* ref_dev, int64_t n, int64_t* K, int64_t* n_cells, int64_t* n_refs,
                                            int64_t* summary) {
   return tiles_compare(t, "vgs_tiles_compare_labels_device", true, ref_dev, n, K, n_cells, n_refs, summary);
+}
+
+vgs_status vgs_tiles_compare_point_labels(vgs_tiles* t, const int32_t* seg_labels_host, int64_t K, const int32_t* ref_host, int64_t n, int64_t* n_cells,
+                                          int64_t* n_refs, int64_t* summary) {
+  return tiles_compare(t, "vgs_tiles_compare_point_labels", false, ref_host, n, nullptr, n_cells, n_refs, summary, true, seg_labels_host, K);
+}
+
+vgs_status vgs_tiles_compare_point_labels_device(vgs_tiles* t, const int32_t* seg_labels_dev, int64_t K, const int32_t* ref_dev, int64_t n,
+                                                 int64_t* n_cells, int64_t* n_refs, int64_t* summary) {
+  return tiles_compare(t, "vgs_tiles_compare_point_labels_device", true, ref_dev, n, nullptr, n_cells, n_refs, summary, true, seg_labels_dev, K);
 }
 
 vgs_status vgs_tiles_get_label_comparison(vgs_tiles* t, int32_t* cell_seg, int32_t* cell_ref, int64_t* cell_n, int32_t* ref_id, int64_t* ref_points,

@@ -385,6 +385,19 @@ struct vgs_ctx {
   DevBuf<double> ps_part, ps_d;
   DevBuf<float> ps_f;
   DevBuf<int64_t> ps_npts;
+  // tile contexts (vgs_own_point_label_moments): the shared-voxel flags (V bytes), pair flags | their scan (Nf words each), the compacted
+  // pair records; the moment records use ps_d.  The compact records wait on the host until vgs_get_own_point_label_moments: pso_K rows
+  // were asked for (-1: none; a run of the stages or new labels discard them)
+  DevBuf<uint8_t> ps_shared;
+  DevBuf<uint32_t> ps_flag;
+  DevBuf<uint64_t> ps_pcode;
+  DevBuf<int32_t> ps_plab;
+  std::vector<int32_t> pso_label, pso_nnodes, pso_plab;
+  std::vector<int64_t> pso_npts;
+  std::vector<float> pso_bbox, pso_anchor;
+  std::vector<double> pso_s9;
+  std::vector<uint64_t> pso_pcode;
+  int64_t pso_K = -1;
   DevBuf<uint64_t> counters;  // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 
@@ -610,6 +623,10 @@ vgs_status vgs_segdesc_on_device(vgs_ctx* c);    // segdesc.hip
 vgs_status vgs_segbox_on_device(vgs_ctx* c, int frame);   // segbox.hip
 // k_sb_frames over K rows of evecs9 / cov6 in HBM, left on the context's stream: the frame rule's one launch site (segbox.hip)
 void sb_launch_frames(vgs_ctx* c, const double* evec, const double* cov, int64_t K, int frame, double* out);
+// tile contexts (segbox.hip; pointseg.hip runs them over a caller's labelling): K rows of the global descriptor table from the host into
+// sbt_in and their frames into sbt_frame; k_sb_final over chunk partials into sbt_out (lo3 | hi3 | half3 | center3)
+vgs_status sbt_upload_frames(vgs_ctx* c, int64_t K, int32_t frame, const double* centroid3, const double* cov6, const double* evecs9);
+void sbt_launch_final(vgs_ctx* c, int64_t K, const uint32_t* seg_chunk, const double* part, uint32_t n_part);
 // a caller's per-point labelling (pointseg.hip): VGS_E_ARG, the message naming the first index and its value, if a label is not below K
 // (one pass on the device); and the host variants' upload into ps_in (*labels_dev = nullptr for n = 0)
 vgs_status vgs_check_label_range(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t n, int64_t K);

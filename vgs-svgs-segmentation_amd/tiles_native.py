@@ -30,6 +30,7 @@ B_NAMES = ("extents", "exchange", "fold", "finish", "total")    # vgs_tiles_get_
 F_NAMES = ("own", "exchange", "fold", "finish", "total")        # vgs_tiles_get_field_times
 C_NAMES = ("own", "exchange", "tables", "total")                # vgs_tiles_get_compare_times
 R_NAMES = ("band", "exchange", "table", "refine", "total")      # vgs_tiles_get_refine_times
+L_NAMES = ("own", "exchange", "fold", "finish", "total")        # vgs_tiles_get_point_label_times
 # vgs_tiles_refine_point_labels' counts, all the rank's share
 REFINE_COUNTS = ("working_nodes", "points_examined", "points_changed", "points_filled", "points_beyond_strip")
 # per (record / row, channel): (field, dtype) of vgs_get_own_segment_field_moments and vgs_tiles_fold_field_moments, in their argument order
@@ -131,6 +132,21 @@ def lib():
         L.vgs_tiles_get_refine_times.argtypes = [P, P, C.c_int32]
         L.vgs_tiles_get_refine_payload.restype = C.c_int
         L.vgs_tiles_get_refine_payload.argtypes = [P, P, P]
+        for name in ("vgs_tiles_point_label_descriptors", "vgs_tiles_point_label_descriptors_device"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [P, P, C.c_int64, C.c_int64] + [P] * 9
+        for name in ("vgs_tiles_point_label_boxes", "vgs_tiles_point_label_boxes_device"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [P, P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, P]
+        for name in ("vgs_tiles_compare_point_labels", "vgs_tiles_compare_point_labels_device"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [P, P, C.c_int64, P, C.c_int64, P, P, P]
+        L.vgs_tiles_fold_label_pairs.restype = C.c_int
+        L.vgs_tiles_fold_label_pairs.argtypes = [C.c_int, P, P, P, C.c_int64, P]
+        L.vgs_tiles_get_point_label_times.restype = C.c_int
+        L.vgs_tiles_get_point_label_times.argtypes = [P, P, C.c_int32]
+        L.vgs_tiles_get_point_label_payload.restype = C.c_int
+        L.vgs_tiles_get_point_label_payload.argtypes = [P, P, P, P]
         L.vgs_tiles_fold_field_moments.restype = C.c_int
         L.vgs_tiles_fold_field_moments.argtypes = [C.c_int, P, P, C.c_int32, P, P, P, P, P, P, C.c_int64, P, P, P, P, P, P]
         L.vgs_tiles_fold_class_counts.restype = C.c_int
@@ -203,6 +219,22 @@ def fold_extents(records, K):
     if st != 0:
         raise VgsError(st, "vgs_tiles_fold_extents")
     return {name: a[:max(K, 0)] for name, a in out.items()}
+
+
+def fold_label_pairs(records, K):
+    """vgs_tiles_fold_label_pairs (host arithmetic, no GPU): records[r] = rank r's dict of pair_code (uint64) and pair_label (int32), as
+    vgs_get_own_point_label_moments gives them; returns n_nodes_add (K,) int32: per label the distinct (code, label) pairs of all ranks."""
+    world = len(records)
+    K = int(K)
+    off = np.zeros(world + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(r["pair_label"]) for r in records])
+    code = np.ascontiguousarray(np.concatenate([np.asarray(r["pair_code"], dtype=np.uint64).reshape(-1) for r in records]))
+    lab = np.ascontiguousarray(np.concatenate([np.asarray(r["pair_label"], dtype=np.int32).reshape(-1) for r in records]))
+    out = np.zeros(max(K, 1), dtype=np.int32)
+    st = lib().vgs_tiles_fold_label_pairs(world, _vp(off), _vp(code), _vp(lab), K, _vp(out))
+    if st != 0:
+        raise VgsError(st, "vgs_tiles_fold_label_pairs")
+    return out[:max(K, 0)]
 
 
 def _rec_off(records):
@@ -541,13 +573,95 @@ class NativeTiles:
         self._ck(fn(self._h, ptr, n, nc, C.byref(K), *(_vp(out[name]) for name, _, _ in Engine.CLASS_HIST_FIELDS)))
         return {name: (a[:k, :max(nc, 0)] if a.ndim == 2 else a[:k]) for name, a in out.items()}
 
-    def compare_labels(self, ref):
+    def describe_labels(self, labels, K):
+        """COLLECTIVE on every call (every rank makes it after run(), with the same K; nothing is cached): descriptors of ANY per-point
+        labelling over all ranks -- the dict of Engine.describe_labels() on the gathered points, K rows plus n_skipped, the same bytes on
+        every rank (include/vgs_tiles.h, vgs_tiles_point_label_descriptors).  `labels`: one int32 per point of this rank's set_points(),
+        negative = no segment, a label >= K is an error; a numpy array, or a torch tensor on this rank's device, which is read in place.
+        No point and no label leaves the rank, only per-label records."""
+        from .api import Engine
+        labels, ptr, n, dev = Engine._classes_input(labels, self.params.device)
+        fn = self._L.vgs_tiles_point_label_descriptors_device if dev else self._L.vgs_tiles_point_label_descriptors
+        K = int(K)
+        k = K if 0 <= K <= 0x7fffffff else 0
+        out = {name: np.zeros((max(k, 1), w) if w > 1 else max(k, 1), dtype=dt) for name, dt, w in Engine.DESCRIPTOR_FIELDS}
+        skipped = C.c_int64(0)
+        self._ck(fn(self._h, ptr, n, K, C.byref(skipped), *(_vp(out[name]) for name, _, _ in Engine.DESCRIPTOR_FIELDS)))
+        out = {name: a[:k] for name, a in out.items()}
+        out["n_skipped"] = int(skipped.value)
+        return out
+
+    def label_boxes(self, labels, frame, K):
+        """COLLECTIVE on every call, two collectives (every rank makes it after run(), with the same K and frame; nothing is cached):
+        oriented boxes of ANY per-point labelling over all ranks -- the dict of Engine.label_boxes() on the gathered points, the same
+        bytes on every rank (include/vgs_tiles.h, vgs_tiles_point_label_boxes).  `labels`, K as describe_labels()."""
+        from .api import Engine
+        labels, ptr, n, dev = Engine._classes_input(labels, self.params.device)
+        fn = self._L.vgs_tiles_point_label_boxes_device if dev else self._L.vgs_tiles_point_label_boxes
+        K = int(K)
+        k = K if 0 <= K <= 0x7fffffff else 0
+        out = {name: np.zeros((max(k, 1), w), dtype=dt) for name, dt, w in Engine.BOX_FIELDS}
+        self._ck(fn(self._h, ptr, n, K, int(Engine.BOX_FRAMES.get(frame, frame)), *(_vp(out[name]) for name, _, _ in Engine.BOX_FIELDS)))
+        return {name: a[:k] for name, a in out.items()}
+
+    def point_label_times(self):
+        """the last describe_labels() / label_boxes()'s phases on this rank, milliseconds (L_NAMES; label_boxes: both collectives added)"""
+        return self._times(self._L.vgs_tiles_get_point_label_times, L_NAMES)
+
+    def point_label_payload(self):
+        """the last describe_labels() / label_boxes()'s payload on this rank: moment records and pair records of its own, bytes sent"""
+        return self._payload(self._L.vgs_tiles_get_point_label_payload, ("own_records", "own_pairs", "bytes_sent"))
+
+    def own_point_label_moments(self, K, labels):
+        """this rank's moment and pair records of a labelling of its own points (vgs_own_point_label_moments on its context; local, no
+        collective): a dict of label and MOMENT_FIELDS arrays (one row per label with an own finite point), pair_code (uint64) and
+        pair_label (int32) -- the head flags in voxels that hold another rank's points too --, plus n_skipped"""
+        from .api import Engine
+        L = _lib.lib()
+        h = self._ctx()
+        labels, ptr, n, dev = Engine._classes_input(labels, self.params.device)
+        fn = L.vgs_own_point_label_moments_device if dev else L.vgs_own_point_label_moments
+        nr, npair, nskip = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        st = fn(h, int(K), ptr, n, C.byref(nr), C.byref(npair), C.byref(nskip))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        out = {"label": np.zeros(max(nr.value, 1), dtype=np.int32)}
+        for name, dt, w in MOMENT_FIELDS:
+            out[name] = np.zeros((max(nr.value, 1), w) if w > 1 else max(nr.value, 1), dtype=dt)
+        pc, pl = np.zeros(max(npair.value, 1), dtype=np.uint64), np.zeros(max(npair.value, 1), dtype=np.int32)
+        st = L.vgs_get_own_point_label_moments(h, _vp(out["label"]), *(_vp(out[name]) for name, _, _ in MOMENT_FIELDS), _vp(pc), _vp(pl))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        out = {name: a[:nr.value] for name, a in out.items()}
+        out["pair_code"], out["pair_label"], out["n_skipped"] = pc[:npair.value], pl[:npair.value], int(nskip.value)
+        return out
+
+    def compare_labels(self, ref, labels=None, K=None):
         """COLLECTIVE on every call (every rank makes it after run(); nothing is cached): score the segmentation against reference labels
         over all ranks -- the dict of Engine.compare_labels(), the same bytes on every rank, and what one engine gives on the gathered
         points (include/vgs_tiles.h, vgs_tiles_compare_labels).  `ref`: one int32 per point of this rank's set_points(), negative = not
         annotated; a numpy array, or a torch tensor on this rank's device, which is read in place.  No label and no id leaves the rank,
-        only contingency cells; comparison_scores() works on the result unchanged."""
+        only contingency cells; comparison_scores() works on the result unchanged.
+        `labels` (vgs_tiles_compare_point_labels): score this labelling of the rank's points instead of point_labels() -- refined_labels(),
+        say -- with K segment rows, the same K on every rank; negative = dropped, a label >= K is an error; numpy or a torch tensor on
+        this rank's device, as `ref` is (both of one kind)."""
         from .api import Engine
+        if labels is not None:
+            if Engine._is_torch(ref) != Engine._is_torch(labels):
+                raise ValueError("ref and labels must both be numpy arrays or both be torch tensors on the rank's device")
+            if K is None:
+                raise ValueError("K is required with labels")
+            ref, ptr, n, dev = Engine._classes_input(ref, self.params.device)
+            labels, lptr, ln, _ = Engine._classes_input(labels, self.params.device)
+            if ln != n:
+                raise ValueError("ref and labels must have the same length")
+            fn = self._L.vgs_tiles_compare_point_labels_device if dev else self._L.vgs_tiles_compare_point_labels
+            n_cells, n_refs = C.c_int64(0), C.c_int64(0)
+            summary = np.zeros(12, np.int64)
+            self._ck(fn(self._h, lptr, int(K), ptr, n, C.byref(n_cells), C.byref(n_refs), _vp(summary)))
+            out = self.label_comparison(n_cells.value, n_refs.value, max(int(K), 0))
+            out["summary"] = summary
+            return out
         ref, ptr, n, dev = Engine._classes_input(ref, self.params.device)
         fn = self._L.vgs_tiles_compare_labels_device if dev else self._L.vgs_tiles_compare_labels
         K, n_cells, n_refs = C.c_int64(0), C.c_int64(0), C.c_int64(0)
