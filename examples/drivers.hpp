@@ -20,12 +20,14 @@ struct DriverGraph {
 };
 
 // per-point attributes handed to the drivers and what comes back: getClusterFieldStats over `field` (n x channels floats, row-major) when
-// channels > 0, getClusterClassHistogram over `classes` (n int32) when n_classes > 0, compareClusterLabels over `truth` when have_truth
+// channels > 0, getClusterClassHistogram over `classes` (n int32) when n_classes > 0, compareClusterLabels over `truth` when have_truth;
+// want_stats / want_hist off: the input is loaded for the refined labels' table only (DriverRefine::fields)
 struct DriverFields {
   std::vector<float> field;
   int channels = 0;
   std::vector<int32_t> classes;
   int n_classes = 0;
+  bool want_stats = true, want_hist = true;
   std::vector<pcl::ClusterFieldStats> stats;
   std::vector<pcl::ClusterClassHistogram> hist;
   // a reference labelling (n int32, negative = no annotation) when have_truth, and compareClusterLabels over it
@@ -42,8 +44,12 @@ struct DriverRefine {
   bool fill = true;
   std::vector<int32_t> labels;
   // the tables of the REFINED labels, beside the ones that describe the voxel labels: getLabelDescriptors / getLabelBoxes(box_frame) /
-  // compareClusterLabels(truth, labels) when wanted (truth: n int32, not null)
-  bool want_descriptors = false, want_boxes = false;
+  // compareClusterLabels(truth, labels) when wanted (truth: n int32, not null); getLabelFieldStats / getLabelClassHistogram over the
+  // field / classes of `fields` when wanted
+  bool want_descriptors = false, want_boxes = false, want_stats = false, want_hist = false;
+  const DriverFields* fields = nullptr;
+  std::vector<pcl::ClusterFieldStats> stats;
+  std::vector<pcl::ClusterClassHistogram> hist;
   int box_frame = VGS_BOX_PRINCIPAL;
   const std::vector<int32_t>* truth = nullptr;
   std::vector<pcl::ClusterDescriptor> descriptors;
@@ -57,15 +63,20 @@ inline void driverRefine(S& structure, DriverRefine& r, std::vector<std::vector<
   if (r.want_descriptors) r.descriptors = structure.getLabelDescriptors(r.labels.data(), n);
   if (r.want_boxes) r.boxes = structure.getLabelBoxes(r.labels.data(), n, r.box_frame);
   if (r.truth) r.matches = structure.compareClusterLabels(r.truth->data(), (int64_t)r.truth->size(), r.labels.data());
+  if (r.want_stats && r.fields && r.fields->channels > 0)
+    r.stats = structure.getLabelFieldStats(r.labels.data(), r.fields->field.data(), (int64_t)(r.fields->field.size() / (size_t)r.fields->channels),
+                                           r.fields->channels, 4 * (int64_t)r.fields->channels);
+  if (r.want_hist && r.fields && r.fields->n_classes > 0)
+    r.hist = structure.getLabelClassHistogram(r.labels.data(), r.fields->classes.data(), (int64_t)r.fields->classes.size(), r.fields->n_classes);
   for (auto& c : clusters_points_idx) c.clear();
   for (size_t i = 0; i < r.labels.size(); ++i)
     if (r.labels[i] >= 0 && (size_t)r.labels[i] < clusters_points_idx.size()) clusters_points_idx[(size_t)r.labels[i]].push_back((int)i);
 }
 template <typename S>
 inline void driverFields(S& structure, DriverFields& f) {
-  if (f.channels > 0)
+  if (f.channels > 0 && f.want_stats)
     f.stats = structure.getClusterFieldStats(f.field.data(), (int64_t)(f.field.size() / (size_t)f.channels), f.channels, 4 * (int64_t)f.channels);
-  if (f.n_classes > 0) f.hist = structure.getClusterClassHistogram(f.classes.data(), (int64_t)f.classes.size(), f.n_classes);
+  if (f.n_classes > 0 && f.want_hist) f.hist = structure.getClusterClassHistogram(f.classes.data(), (int64_t)f.classes.size(), f.n_classes);
   if (f.have_truth) f.matches = structure.compareClusterLabels(f.truth.data(), (int64_t)f.truth.size());
 }
 

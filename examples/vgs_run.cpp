@@ -9,6 +9,7 @@
 //                  [--segment-matches <file.csv> --truth-field <name> [--truth-matches <file.csv>]]
 //                  [--refine [--patch-radius <r>] [--switch-ratio <s>] [--no-fill]]
 //                  [--refined-segments <file.csv>] [--refined-segment-boxes <file.csv>]
+//                  [--refined-segment-fields <file.csv> --fields a[,b,...]] [--refined-segment-classes <file.csv> --class-field <name> --classes <C>]
 //                  [--refined-matches <file.csv> --truth-field <name> [--refined-truth-matches <file.csv>]]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
@@ -40,6 +41,9 @@
 // over the REFINED labels (getLabelDescriptors, getLabelBoxes, compareClusterLabels with the labels): the tables of the result the PCD
 // holds.  The flags above keep writing the voxel-label tables, and a run may write both.  --refined-matches adds the stdout lines
 // "refined-matches" and "refined-scores".  Each needs --refine (a usage error, status 2, without it).
+// --refined-segment-fields and --refined-segment-classes write the files of --segment-fields / --segment-classes -- same writers, same
+// columns -- over the REFINED labels (getLabelFieldStats, getLabelClassHistogram), from the same --fields / --class-field / --classes,
+// which may be given for a refined file alone.  Both need --refine and a PCD input.
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
 #include <algorithm>
 #include <cmath>
@@ -67,12 +71,13 @@ int main(int argc, char** argv) {
                  "[--segment-fields file.csv --fields a[,b,...]] [--segment-classes file.csv --class-field name --classes C] "
                  "[--segment-matches file.csv --truth-field name [--truth-matches file.csv]] "
                  "[--refine [--patch-radius r] [--switch-ratio s] [--no-fill]] [--refined-segments file.csv] [--refined-segment-boxes file.csv] "
+                 "[--refined-segment-fields file.csv --fields a[,b,...]] [--refined-segment-classes file.csv --class-field name --classes C] "
                  "[--refined-matches file.csv --truth-field name [--refined-truth-matches file.csv]]\n",
                  argv[0]);
     return 2;
   }
   std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file, boxes_file, fields_file, classes_file, class_field, matches_file, truth_field, truth_file;
-  std::string r_segments_file, r_boxes_file, r_matches_file, r_truth_file;
+  std::string r_segments_file, r_boxes_file, r_matches_file, r_truth_file, r_fields_file, r_classes_file;
   std::vector<std::string> field_names;
   bool have_fields = false, have_classes = false;
   long n_classes = 0;
@@ -120,6 +125,8 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--truth-matches") && a + 1 < argc) truth_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-segments") && a + 1 < argc) r_segments_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-segment-boxes") && a + 1 < argc) r_boxes_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-segment-fields") && a + 1 < argc) r_fields_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-segment-classes") && a + 1 < argc) r_classes_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-matches") && a + 1 < argc) r_matches_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-truth-matches") && a + 1 < argc) r_truth_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refine")) refine.on = true;
@@ -139,14 +146,25 @@ int main(int argc, char** argv) {
   }
   if (refine_opts && !refine.on) { std::fprintf(stderr, "--patch-radius / --switch-ratio / --no-fill need --refine\n"); return 2; }
   if (!fields_file.empty() && (!have_fields || field_names.empty())) { std::fprintf(stderr, "--segment-fields needs --fields a[,b,...]\n"); return 2; }
-  if (!fields_file.empty() && field_names.size() > 64) { std::fprintf(stderr, "--fields: at most 64 fields\n"); return 2; }
+  if (!r_fields_file.empty() && (!have_fields || field_names.empty())) { std::fprintf(stderr, "--refined-segment-fields needs --fields a[,b,...]\n"); return 2; }
+  if (!r_classes_file.empty() && class_field.empty()) { std::fprintf(stderr, "--refined-segment-classes needs --class-field <name>\n"); return 2; }
+  if (!r_classes_file.empty() && !have_classes) { std::fprintf(stderr, "--refined-segment-classes needs --classes <C>\n"); return 2; }
+  if (!(fields_file.empty() && r_fields_file.empty()) && field_names.size() > 64) { std::fprintf(stderr, "--fields: at most 64 fields\n"); return 2; }
   if (!classes_file.empty() && class_field.empty()) { std::fprintf(stderr, "--segment-classes needs --class-field <name>\n"); return 2; }
   if (!classes_file.empty() && !have_classes) { std::fprintf(stderr, "--segment-classes needs --classes <C>\n"); return 2; }
-  if (fields_file.empty() && have_fields) { std::fprintf(stderr, "--fields needs --segment-fields <file.csv>\n"); return 2; }
-  if (classes_file.empty() && (have_classes || !class_field.empty())) { std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv>\n"); return 2; }
+  if (fields_file.empty() && r_fields_file.empty() && have_fields) {
+    std::fprintf(stderr, "--fields needs --segment-fields <file.csv> (or --refined-segment-fields)\n");
+    return 2;
+  }
+  if (classes_file.empty() && r_classes_file.empty() && (have_classes || !class_field.empty())) {
+    std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv> (or --refined-segment-classes)\n");
+    return 2;
+  }
   if (!matches_file.empty() && truth_field.empty()) { std::fprintf(stderr, "--segment-matches needs --truth-field <name>\n"); return 2; }
-  if (!refine.on && !(r_segments_file.empty() && r_boxes_file.empty() && r_matches_file.empty() && r_truth_file.empty())) {
-    std::fprintf(stderr, "--refined-segments / --refined-segment-boxes / --refined-matches / --refined-truth-matches need --refine\n");
+  if (!refine.on && !(r_segments_file.empty() && r_boxes_file.empty() && r_matches_file.empty() && r_truth_file.empty() && r_fields_file.empty() &&
+                      r_classes_file.empty())) {
+    std::fprintf(stderr, "--refined-segments / --refined-segment-boxes / --refined-segment-fields / --refined-segment-classes / --refined-matches / "
+                 "--refined-truth-matches need --refine\n");
     return 2;
   }
   if (!r_matches_file.empty() && truth_field.empty()) { std::fprintf(stderr, "--refined-matches needs --truth-field <name>\n"); return 2; }
@@ -169,25 +187,29 @@ int main(int argc, char** argv) {
   PCXYZPtr cloud(new PCXYZ);
   const bool ply = in_file.size() > 4 && in_file.substr(in_file.size() - 4) == ".ply";
   const bool want_truth = !(matches_file.empty() && r_matches_file.empty());
-  if (ply && !(fields_file.empty() && classes_file.empty() && !want_truth)) {   // (a usage error: nothing has been loaded yet)
-    std::fprintf(stderr, "--segment-fields / --segment-classes / --segment-matches / --refined-matches read their fields from a PCD input, not from %s\n", in_file.c_str());
+  const bool any_fields = !(fields_file.empty() && r_fields_file.empty()), any_classes = !(classes_file.empty() && r_classes_file.empty());
+  if (ply && (any_fields || any_classes || want_truth)) {   // (a usage error: nothing has been loaded yet)
+    std::fprintf(stderr, "--segment-fields / --segment-classes / --refined-segment-fields / --refined-segment-classes / --segment-matches / "
+                 "--refined-matches read their fields from a PCD input, not from %s\n", in_file.c_str());
     return 2;
   }
   if ((ply ? inputPointCloudData2(in_file, cloud) : inputPointCloudData(in_file, cloud)) != 0) return 1;
   DriverFields fields;
-  DriverFields* want_fields = (fields_file.empty() && classes_file.empty() && !want_truth) ? nullptr : &fields;
+  DriverFields* want_fields = (!any_fields && !any_classes && !want_truth) ? nullptr : &fields;
   if (want_fields) {   // the attributes ride in the input PCD, one row per point of the cloud
     std::string err;
-    if (!fields_file.empty()) {
+    if (any_fields) {
       if (vgs_io::read_pcd_fields(in_file, field_names, fields.field, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
       fields.channels = (int)field_names.size();
+      fields.want_stats = !fields_file.empty();
     }
-    if (!classes_file.empty()) {
+    if (any_classes) {
       std::vector<float> v;
       if (vgs_io::read_pcd_fields(in_file, {class_field}, v, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
       fields.classes.resize(v.size());
       for (size_t i = 0; i < v.size(); ++i) fields.classes[i] = (v[i] >= -2147483648.0f && v[i] < 2147483648.0f) ? (int32_t)v[i] : -1;
       fields.n_classes = (int)n_classes;
+      fields.want_hist = !classes_file.empty();
     }
     if (want_truth) {
       if (vgs_io::read_pcd_field_int32(in_file, truth_field, fields.truth, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
@@ -197,6 +219,9 @@ int main(int argc, char** argv) {
   }
   refine.want_descriptors = !r_segments_file.empty();
   refine.want_boxes = !r_boxes_file.empty();
+  refine.want_stats = !r_fields_file.empty();
+  refine.want_hist = !r_classes_file.empty();
+  refine.fields = &fields;
   refine.box_frame = box_frame;
   std::vector<std::vector<int>> clusters;
   DriverSummary sum;
@@ -230,6 +255,8 @@ int main(int argc, char** argv) {
   if (!truth_file.empty() && writeTruthMatchesCsv(truth_file, fields.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", truth_file.c_str()); return 1; }
   if (!r_segments_file.empty() && writeSegmentsCsv(r_segments_file, refine.descriptors) != 0) { std::fprintf(stderr, "cannot write %s\n", r_segments_file.c_str()); return 1; }
   if (!r_boxes_file.empty() && writeBoxesCsv(r_boxes_file, refine.boxes) != 0) { std::fprintf(stderr, "cannot write %s\n", r_boxes_file.c_str()); return 1; }
+  if (!r_fields_file.empty() && writeFieldStatsCsv(r_fields_file, field_names, refine.stats) != 0) { std::fprintf(stderr, "cannot write %s\n", r_fields_file.c_str()); return 1; }
+  if (!r_classes_file.empty() && writeClassHistCsv(r_classes_file, fields.n_classes, refine.hist) != 0) { std::fprintf(stderr, "cannot write %s\n", r_classes_file.c_str()); return 1; }
   if (!r_matches_file.empty() && writeSegmentMatchesCsv(r_matches_file, refine.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", r_matches_file.c_str()); return 1; }
   if (!r_truth_file.empty() && writeTruthMatchesCsv(r_truth_file, refine.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", r_truth_file.c_str()); return 1; }
   if (!adjacency_file.empty() && writeAdjacency(adjacency_file, graph.adjacency) != 0) {

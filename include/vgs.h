@@ -539,7 +539,48 @@ vgs_status vgs_compare_point_labels(vgs_ctx* ctx, const int32_t* seg_labels_host
                                     int64_t* n_refs, int64_t* summary /* 12 */);
 vgs_status vgs_compare_point_labels_device(vgs_ctx* ctx, const int32_t* seg_labels_dev, int64_t K, const int32_t* ref_dev, int64_t n,
                                            int64_t* n_cells, int64_t* n_refs, int64_t* summary /* 12 */);
-/* The same three tables for a tile context (the tiled driver, include/vgs_tiles.h: vgs_tiles_point_label_descriptors, _boxes and
+/* Field statistics and class histogram of ANY per-point labelling: the two attribute tables of vgs_segment_field_stats and
+ * vgs_segment_class_histogram with K rows of the caller's labelling instead of the node labels -- mean intensity or colour, or the
+ * majority class, of the refined segments, which the node pass cannot give (a boundary voxel may hold two or three labels).
+ *   labels  the rules of vgs_point_label_descriptors: n int32 in input order, n == counts[VGS_N_POINTS]; label l is row l for 0 <= l < K,
+ *           a negative label no row; a label >= K is VGS_E_ARG, the message naming the first offending index and its value (found on the
+ *           device before anything is built); 0 <= K <= 2^31 - 1, K the caller's.
+ *   field, n_channels, stride_bytes, cls, n_classes   exactly as vgs_segment_field_stats / vgs_segment_class_histogram: 1 .. 64 channels,
+ *           the stride a multiple of 4 and at least 4 * n_channels, 1 .. 1024 classes; a finite value is valid, NaN and +-inf are skipped.
+ * The host variants take BOTH arrays on the host and upload each once into buffers of the context; the _device variants read both in place
+ * in HBM (the context's device; complete before the call).
+ * Row k covers the points i with labels[i] == k that are in the octree -- the finite points, for SVGS those of a supervoxel: the set
+ * vgs_point_label_descriptors counts in n_points.  *n_skipped (may be NULL) counts the labelled points that are not.  So n_valid[k, c] <=
+ * n_points[k], and hist[k, :].sum() + n_outside[k] == n_points[k] of vgs_point_label_descriptors for the same labelling.
+ * Field outputs, each K x n_channels, the definitions of vgs_segment_field_stats: n_valid; anchor[k, c] = the value of the label's first
+ * point in the sorted order of csrc/pointseg.hip (octree positions sorted by label, positions ascending inside a label), 0.0 where that
+ * value is not finite; mean = anchor + S1 / n, var = max(0, S2 / n - (S1 / n) * (S1 / n)), each one fp64 operation (no FMA); vmin, vmax
+ * float.  A label no octree point carries: n_valid 0, anchor 0, mean, var, vmin and vmax NaN.
+ * Histogram outputs, the definitions of vgs_segment_class_histogram: hist K x n_classes; n_outside, majority (the lowest class with the
+ * largest count), majority_count K rows; majority -1 with count 0 for a row without counts, a label no point carries included.
+ * VGS_E_UNSUPPORTED, with the numbers in the message, if K * n_channels or K * n_classes exceeds 2^27.  K = 0 writes nothing and returns
+ * VGS_OK, but still validates and still counts *n_skipped.  Any output pointer may be NULL.
+ * Two guarantees (csrc/pointfield.hip):
+ *   1. bit-identical from call to call and from engine to engine: no float atomics, every sum of a fixed shape (the rule of
+ *      vgs_segment_field_stats over the points sorted by label; the histogram adds integers);
+ *   2. handed the context's own vgs_get_point_labels with K = counts[VGS_N_KEPT], the two calls return vgs_segment_field_stats and
+ *      vgs_segment_class_histogram byte for byte, anchor included (the same device code over the same point sequence).
+ * VGS_E_STATE before the context is segmented, and on a tile context: the tiled driver has no call for these tables yet.  VGS_E_ARG for a
+ * wrong n, a NULL array with n > 0, bad channels, stride, classes or K, and a label >= K.  Computed on every call, nothing cached; no side
+ * effects: labels, refined labels, every cached table and the context's last comparison stay as they are. */
+vgs_status vgs_point_label_field_stats(vgs_ctx* ctx, const int32_t* labels_host, int64_t K, const float* field_host, int64_t n,
+                                       int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor,
+                                       double* mean, double* var, float* vmin, float* vmax);
+vgs_status vgs_point_label_field_stats_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t K, const float* field_dev, int64_t n,
+                                              int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor,
+                                              double* mean, double* var, float* vmin, float* vmax);
+vgs_status vgs_point_label_class_histogram(vgs_ctx* ctx, const int32_t* labels_host, int64_t K, const int32_t* cls_host, int64_t n,
+                                           int32_t n_classes, int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority,
+                                           int64_t* majority_count);
+vgs_status vgs_point_label_class_histogram_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t K, const int32_t* cls_dev, int64_t n,
+                                                  int32_t n_classes, int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority,
+                                                  int64_t* majority_count);
+/* Descriptors, boxes and scores of a point labelling for a tile context (the tiled driver, include/vgs_tiles.h: vgs_tiles_point_label_descriptors, _boxes and
  * vgs_tiles_compare_point_labels build the global tables from what these leave).  Tile contexts only: VGS_E_STATE before the context is
  * segmented and on a context that is not a tile context (the three entry points above keep refusing a tile context).  In all of them
  * `labels` holds one int32 per point of the rank's OWN load: labels[i] belongs to cloud point own_first + i of vgs_set_own_point_range and

@@ -182,14 +182,21 @@ struct ClusterClassHistogram {
 
 namespace vgs_detail {
 // one row per kept cluster, in label order -- the order of getClusterIdx; stride in bytes
-inline std::vector<ClusterFieldStats> cluster_field_stats(vgs_ctx* c, int64_t k, const float* field, int64_t n, int32_t channels, int64_t stride) {
+// labels != nullptr: the rows of that per-point labelling (n labels in 0 .. k-1 or negative) instead, as vgs_point_label_field_stats /
+// vgs_point_label_class_histogram define them; *n_skipped = its labelled points outside the octree
+inline std::vector<ClusterFieldStats> cluster_field_stats(vgs_ctx* c, int64_t k, const float* field, int64_t n, int32_t channels, int64_t stride,
+                                                          const int32_t* labels = nullptr, int64_t* n_skipped = nullptr) {
   const size_t ch = channels > 0 ? (size_t)channels : 0, kc = (size_t)k * ch;
   std::vector<int64_t> nv(kc + 1);
   std::vector<double> an(kc + 1), me(kc + 1), va(kc + 1);
   std::vector<float> mn(kc + 1), mx(kc + 1);
   // (called for k = 0 too: the state and argument checks are the library's)
-  check(c, vgs_segment_field_stats(c, field, n, channels, stride, nv.data(), an.data(), me.data(), va.data(), mn.data(), mx.data()),
-        "vgs_segment_field_stats");
+  if (labels)
+    check(c, vgs_point_label_field_stats(c, labels, k, field, n, channels, stride, n_skipped, nv.data(), an.data(), me.data(), va.data(), mn.data(),
+                                         mx.data()), "vgs_point_label_field_stats");
+  else
+    check(c, vgs_segment_field_stats(c, field, n, channels, stride, nv.data(), an.data(), me.data(), va.data(), mn.data(), mx.data()),
+          "vgs_segment_field_stats");
   std::vector<ClusterFieldStats> out((size_t)k);
   for (size_t i = 0; i < (size_t)k; ++i) {
     ClusterFieldStats& f = out[i];
@@ -202,11 +209,16 @@ inline std::vector<ClusterFieldStats> cluster_field_stats(vgs_ctx* c, int64_t k,
   }
   return out;
 }
-inline std::vector<ClusterClassHistogram> cluster_class_histogram(vgs_ctx* c, int64_t k, const int32_t* cls, int64_t n, int32_t n_classes) {
+inline std::vector<ClusterClassHistogram> cluster_class_histogram(vgs_ctx* c, int64_t k, const int32_t* cls, int64_t n, int32_t n_classes,
+                                                                  const int32_t* labels = nullptr, int64_t* n_skipped = nullptr) {
   const size_t nc = n_classes > 0 ? (size_t)n_classes : 0;
   std::vector<int64_t> hi((size_t)k * nc + 1), no((size_t)k + 1), mc((size_t)k + 1);
   std::vector<int32_t> ma((size_t)k + 1);
-  check(c, vgs_segment_class_histogram(c, cls, n, n_classes, hi.data(), no.data(), ma.data(), mc.data()), "vgs_segment_class_histogram");
+  if (labels)
+    check(c, vgs_point_label_class_histogram(c, labels, k, cls, n, n_classes, n_skipped, hi.data(), no.data(), ma.data(), mc.data()),
+          "vgs_point_label_class_histogram");
+  else
+    check(c, vgs_segment_class_histogram(c, cls, n, n_classes, hi.data(), no.data(), ma.data(), mc.data()), "vgs_segment_class_histogram");
   std::vector<ClusterClassHistogram> out((size_t)k);
   for (size_t i = 0; i < (size_t)k; ++i) {
     ClusterClassHistogram& h = out[i];
@@ -484,6 +496,21 @@ class VoxelBasedSegmentation {
     if (!drawn_) return {};
     return vgs_detail::cluster_boxes(ctx(), count(VGS_N_KEPT), frame, labels, n);
   }
+  // Extension (no VS line): the field statistics and the class histogram of a per-point labelling (n int32 in input order, negative = no
+  // row; vgs_point_label_field_stats / vgs_point_label_class_histogram, include/vgs.h): K rows, row i over the points labelled i; K < 0:
+  // the clusters' label range; *n_skipped = the labelled points outside the octree.  Empty before drawColorMapofPointsinClusters
+  std::vector<ClusterFieldStats> getLabelFieldStats(const int32_t* labels, const float* field, int64_t n, int32_t channels, int64_t stride_bytes,
+                                                    int64_t K = -1, int64_t* n_skipped = nullptr) {
+    if (n_skipped) *n_skipped = 0;
+    if (!drawn_) return {};
+    return vgs_detail::cluster_field_stats(ctx(), K < 0 ? count(VGS_N_KEPT) : K, field, n, channels, stride_bytes, labels, n_skipped);
+  }
+  std::vector<ClusterClassHistogram> getLabelClassHistogram(const int32_t* labels, const int32_t* classes, int64_t n, int32_t n_classes,
+                                                            int64_t K = -1, int64_t* n_skipped = nullptr) {
+    if (n_skipped) *n_skipped = 0;
+    if (!drawn_) return {};
+    return vgs_detail::cluster_class_histogram(ctx(), K < 0 ? count(VGS_N_KEPT) : K, classes, n, n_classes, labels, n_skipped);
+  }
 
   // Extension (no VS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
   // names getClusterIdx()[i].  patch_radius < 0: the default (the voxel size); every point -1 before drawColorMapofPointsinClusters
@@ -613,6 +640,19 @@ class SuperVoxelBasedSegmentation {
   }
   std::vector<ClusterBox> getLabelBoxes(const int32_t* labels, int64_t n, int frame = VGS_BOX_PRINCIPAL) {
     return vgs_detail::cluster_boxes(ctx(), count(VGS_N_KEPT), frame, labels, n);
+  }
+  // Extension (no SS line): the field statistics and the class histogram of a per-point labelling (n int32 in input order, negative = no
+  // row; vgs_point_label_field_stats / vgs_point_label_class_histogram, include/vgs.h): K rows, row i over the points labelled i; K < 0:
+  // the clusters' label range; *n_skipped = the labelled points outside the octree
+  std::vector<ClusterFieldStats> getLabelFieldStats(const int32_t* labels, const float* field, int64_t n, int32_t channels, int64_t stride_bytes,
+                                                    int64_t K = -1, int64_t* n_skipped = nullptr) {
+    if (n_skipped) *n_skipped = 0;
+    return vgs_detail::cluster_field_stats(ctx(), K < 0 ? count(VGS_N_KEPT) : K, field, n, channels, stride_bytes, labels, n_skipped);
+  }
+  std::vector<ClusterClassHistogram> getLabelClassHistogram(const int32_t* labels, const int32_t* classes, int64_t n, int32_t n_classes,
+                                                            int64_t K = -1, int64_t* n_skipped = nullptr) {
+    if (n_skipped) *n_skipped = 0;
+    return vgs_detail::cluster_class_histogram(ctx(), K < 0 ? count(VGS_N_KEPT) : K, classes, n, n_classes, labels, n_skipped);
   }
   // Extension (no SS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
   // names getClusterIdx()[i].  patch_radius < 0: the default (the supervoxel size)

@@ -128,6 +128,10 @@ SYMBOLS = [
     ("vgs_point_label_boxes_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
     ("vgs_compare_point_labels", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("vgs_compare_point_labels_device", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
+    ("vgs_point_label_field_stats", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64] + [_P] * 7),
+    ("vgs_point_label_field_stats_device", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64] + [_P] * 7),
+    ("vgs_point_label_class_histogram", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32] + [_P] * 5),
+    ("vgs_point_label_class_histogram_device", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32] + [_P] * 5),
     ("vgs_own_point_label_moments", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("vgs_own_point_label_moments_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("vgs_get_own_point_label_moments", C.c_int, [_P] + [_P] * 8),

@@ -505,6 +505,47 @@ class Engine:
         self._ck(fn(self._h, ptr, n, K, self._box_frame(frame), *(_ptr(out[name]) for name, _, _ in self.BOX_FIELDS)))
         return out
 
+    def _label_table_inputs(self, labels, other, what, K):
+        """_labels_input for label_field_stats / label_class_histogram: labels and the attribute array both numpy or both torch tensors on
+        the device.  (The library takes one n for both: the callers hand it the length that is not the cloud's, if one is not, so that
+        its own VGS_E_ARG names the number.)"""
+        if self._is_torch(labels) != self._is_torch(other):
+            raise ValueError(f"labels and {what} must both be numpy arrays or both be torch tensors on the context's device")
+        return self._labels_input(labels, K)
+
+    def label_field_stats(self, labels, field, K=None):
+        """Field statistics of ANY per-point labelling of the cloud (include/vgs.h, vgs_point_label_field_stats): the dict of
+        segment_field_stats() with K rows, row k = the points with labels[i] == k that are in the octree, plus n_skipped, the labelled
+        points that are not.  `labels`, K as describe_labels(); `field` as segment_field_stats(); both numpy arrays or both torch tensors
+        on the context's device, which are read in place.  A label no point carries gives n_valid 0, anchor 0 and NaN.  Computed on the
+        device on every call, nothing cached, bit-identical from call to call; handed point_labels() it returns segment_field_stats(field)
+        byte for byte."""
+        labels, lptr, ln, dev, K = self._label_table_inputs(labels, field, "field", K)
+        field, ptr, n, ch, stride, _ = self._field_input(field, self.params.device)
+        fn = self._L.vgs_point_label_field_stats_device if dev else self._L.vgs_point_label_field_stats
+        out = {name: np.zeros((max(K, 0), max(ch, 0)), dtype=dt) for name, dt in self.FIELD_STAT_FIELDS}
+        skipped = C.c_int64(0)
+        self._ck(fn(self._h, lptr, K, ptr, ln if ln != self.n else n, ch, stride, C.byref(skipped),
+                    *(_ptr(out[name]) for name, _ in self.FIELD_STAT_FIELDS)))
+        out["n_skipped"] = int(skipped.value)
+        return out
+
+    def label_class_histogram(self, labels, classes, n_classes, K=None):
+        """Class histogram of ANY per-point labelling of the cloud (include/vgs.h, vgs_point_label_class_histogram): the dict of
+        segment_class_histogram() with K rows over the octree points of every label, plus n_skipped.  `labels`, K as describe_labels();
+        `classes` as segment_class_histogram(); both numpy arrays or both torch tensors on the context's device.  hist.sum(1) + n_outside
+        equals describe_labels(labels, K)["n_points"]; handed point_labels() it returns segment_class_histogram() byte for byte."""
+        nc = int(n_classes)
+        labels, lptr, ln, dev, K = self._label_table_inputs(labels, classes, "classes", K)
+        classes, ptr, n, _ = self._classes_input(classes, self.params.device)
+        fn = self._L.vgs_point_label_class_histogram_device if dev else self._L.vgs_point_label_class_histogram
+        out = {name: np.zeros((max(K, 0), max(nc, 0)) if w == 0 else max(K, 0), dtype=dt) for name, dt, w in self.CLASS_HIST_FIELDS}
+        skipped = C.c_int64(0)
+        self._ck(fn(self._h, lptr, K, ptr, ln if ln != self.n else n, nc, C.byref(skipped),
+                    *(_ptr(out[name]) for name, _, _ in self.CLASS_HIST_FIELDS)))
+        out["n_skipped"] = int(skipped.value)
+        return out
+
     def compare_labels(self, ref, labels=None, K=None):
         """Score the segmentation against a labelling of the same points (include/vgs.h, vgs_compare_labels): the sparse contingency table
         between point_labels() and `ref`, the reference table and the segment table, as a dict of numpy arrays -- cell_seg, cell_ref, cell_n

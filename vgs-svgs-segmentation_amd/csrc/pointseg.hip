@@ -93,22 +93,6 @@ __global__ __launch_bounds__(PS_TB) void k_ps_segments(const uint32_t* __restric
   nchunk[k] = (n1 - n0 + SD_CHUNK - 1) / SD_CHUNK;
 }
 
-// The walk of a chunk workgroup (blockIdx.x) from chunk to label: the label k of the chunk, the start s0 of the label's run and the
-// chunk's range [a, b) in pos_sorted.  False for a workgroup past the real number of chunks.
-struct PsChunk { uint32_t k, s0, a, b; };
-__device__ __forceinline__ bool ps_walk(const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_chunk, uint32_t K, PsChunk& o) {
-  const uint32_t c = blockIdx.x;
-  if (c >= seg_chunk[K]) return false;
-  // label of chunk c: the last k with seg_chunk[k] <= c -- a label without a chunk shares its value with the next one and is passed over
-  uint32_t lo = 0, hi = K - 1;
-  while (lo < hi) { const uint32_t mid = lo + ((hi - lo + 1) >> 1); if (seg_chunk[mid] <= c) lo = mid; else hi = mid - 1; }
-  o.k = lo;
-  o.s0 = seg_start[lo];
-  o.a = o.s0 + (c - seg_chunk[lo]) * SD_CHUNK;
-  o.b = min(o.a + (uint32_t)SD_CHUNK, seg_start[lo + 1]);
-  return true;
-}
-
 // Step 4.  Grid: the bound of the header; workgroups past the real number of chunks leave at once (whole workgroups, before any barrier).
 // TILE (k_ps_own_chunks, tile contexts): pos_sorted holds the rank's own labelled points only.  A head flag in a voxel that other ranks'
 // points share (shared[v], k_ps_shared) is not counted: it is written to flag[q] and leaves as a pair record (k_ps_pairs), so that the
@@ -346,8 +330,8 @@ struct PsTable {
 // Steps 1-3: the finite points that carry a label 0 .. K-1, sorted by label, and the chunks of every label.  labels_dev holds n_lab entries
 // for the input indices own_first .. (one context: 0 and N; a tile context: its own point range, so that only own points are sorted).
 // Left on the stream; sorted = false (nothing queued behind the range check) for K = 0.  tmp_extra: bytes of ps_tmp the caller needs later.
-struct PsSort { bool sorted; uint32_t *key, *pos, *seg_start, *seg_chunk; int64_t n_chunks_max; };
-static vgs_status ps_sort_points(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t own_first, int64_t n_lab, int64_t K, size_t tmp_extra,
+// (PsSort: vgs_context.hpp; pointfield.hip runs the attribute tables over the same sort.)
+vgs_status ps_sort_points(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t own_first, int64_t n_lab, int64_t K, size_t tmp_extra,
                                  int64_t* n_skipped, PsSort& S) {
   const int64_t N = c->N, nf = c->Nf;
   S.sorted = false;

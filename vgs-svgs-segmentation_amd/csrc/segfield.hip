@@ -32,27 +32,7 @@
 #include <algorithm>
 #include <string>
 
-#include "vgs_context.hpp"
-
-#define SF_G 4     // channels per pass over the points: 4 x (S1, S2, count, min, max) stay in registers
-#define SF_REC 5   // doubles per partial record of one (chunk, channel): S1, S2, count, min, max
-
-__device__ __forceinline__ double sf_wave_sum(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-  return x;
-}
-__device__ __forceinline__ double sf_wave_min(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x = fmin(x, __shfl_xor(x, m, 64));
-  return x;
-}
-__device__ __forceinline__ double sf_wave_max(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x = fmax(x, __shfl_xor(x, m, 64));
-  return x;
-}
-__device__ __forceinline__ bool sf_valid(float x) { return fabsf(x) < __builtin_huge_valf(); }   // finite: false for NaN and +-inf
+#include "segpass.hpp"
 
 // anchor[k, c] for every channel: the value of the segment's first point in the chunk order, 0.0 where it is not finite.  One thread per entry.
 __global__ __launch_bounds__(256) void k_sf_anchor(const float* __restrict__ field, int64_t stride_f, uint32_t C, const uint32_t* __restrict__ perm,
@@ -90,7 +70,6 @@ __device__ __forceinline__ void sf_chunk_body(const float* __restrict__ field, i
                                               const uint32_t* __restrict__ anchor_pos) {
   __shared__ uint32_t s_vp[SD_CHUNK];    // virtual start of the chunk's nodes
   __shared__ uint32_t s_dl[SD_CHUNK];    // sorted position - virtual position of the same (mod 2^32)
-  __shared__ double s_red[SD_TB / 64][SF_G][SF_REC];
   SdChunk w;
   double* rec = part + (size_t)blockIdx.x * (SF_G * SF_REC);
   if (!sd_walk(vox_start, ids, vp, seg_node, seg_chunk, K, s_vp, s_dl, w)) {
@@ -104,58 +83,7 @@ __device__ __forceinline__ void sf_chunk_body(const float* __restrict__ field, i
   double an[SF_G];
 #pragma unroll
   for (int g = 0; g < SF_G; ++g) an[g] = (uint32_t)g < ng ? anchor[(size_t)w.k * C + c0 + g] : 0.0;
-  __syncthreads();
-  double s1[SF_G], s2[SF_G], cn[SF_G];
-  float mn[SF_G], mx[SF_G];
-#pragma unroll
-  for (int g = 0; g < SF_G; ++g) { s1[g] = 0.0; s2[g] = 0.0; cn[g] = 0.0; mn[g] = __builtin_huge_valf(); mx[g] = -__builtin_huge_valf(); }
-#pragma unroll 2
-  for (int it = 0; it < SD_PPT; ++it) {
-    const uint32_t q = w.a + (uint32_t)it * SD_TB + threadIdx.x;
-    if (q < w.b) {
-      const uint32_t pos = sd_pos(s_vp, s_dl, w.m, q);
-      size_t ri = (size_t)perm[pos];
-      if (OWN) {
-        const int64_t o = (int64_t)ri;
-        if (o < own_first || o >= own_end) continue;
-        ri = (size_t)(o - own_first);
-      }
-      const float* row = field + ri * (size_t)stride_f + c0;
-#pragma unroll
-      for (int g = 0; g < SF_G; ++g) {
-        if ((uint32_t)g < ng) {
-          const float x = row[g];
-          if (sf_valid(x)) {
-            const double d = (double)x - an[g];   // exact conversion, then one fp64 operation per difference, product and sum
-            s1[g] += d;
-            s2[g] += d * d;
-            cn[g] += 1.0;
-            mn[g] = fminf(mn[g], x);
-            mx[g] = fmaxf(mx[g], x);
-          }
-        }
-      }
-    }
-  }
-  const int wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int g = 0; g < SF_G; ++g) {
-    const double a1 = sf_wave_sum(s1[g]), a2 = sf_wave_sum(s2[g]), a3 = sf_wave_sum(cn[g]);
-    const double a4 = sf_wave_min((double)mn[g]), a5 = sf_wave_max((double)mx[g]);
-    if ((threadIdx.x & 63) == 0) {
-      double* r = s_red[wv][g];
-      r[0] = a1; r[1] = a2; r[2] = a3; r[3] = a4; r[4] = a5;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < SF_G * SF_REC) {   // the waves in index order
-    const int g = threadIdx.x / SF_REC, f = threadIdx.x % SF_REC;
-    double v = s_red[0][g][f];
-    if (f < 3) { for (int u = 1; u < SD_TB / 64; ++u) v += s_red[u][g][f]; }
-    else if (f == 3) { for (int u = 1; u < SD_TB / 64; ++u) v = fmin(v, s_red[u][g][f]); }
-    else { for (int u = 1; u < SD_TB / 64; ++u) v = fmax(v, s_red[u][g][f]); }
-    rec[threadIdx.x] = v;
-  }
+  sf_chunk_sums<OWN>(field, stride_f, c0, ng, w.a, w.b, an, [&](uint32_t q) { return sd_pos(s_vp, s_dl, w.m, q); }, perm, own_first, own_end, rec);
 }
 
 __global__ __launch_bounds__(SD_TB) void k_sf_chunks(const float* __restrict__ field, int64_t stride_f, uint32_t C, uint32_t c0, uint32_t ng,
@@ -257,6 +185,19 @@ __global__ __launch_bounds__(256) void k_sf_own_records(const uint32_t* __restri
 // One workgroup per chunk: the classes of its points counted in LDS (slot n_classes: out of range), the non-zero counters added to the
 // zeroed tables.  hist: K x n_classes, n_outside: K.  Integer atomics: the sums do not depend on the order.  OWN (tile contexts,
 // k_sf_hist_own): only the points whose input index o = perm[pos] lies in [own_first, own_end) count, and their class is cls[o - own_first].
+// the walk of sf_hist_chunk over the node labelling: sd_walk stages the chunk's nodes, sd_pos finds a virtual point
+struct SfNodeWalk {
+  const uint32_t *vox_start, *ids, *vp, *seg_node, *seg_chunk;
+  uint32_t K;
+  uint32_t *s_vp, *s_dl;
+  SdChunk w;
+  __device__ __forceinline__ bool begin(uint32_t& k, uint32_t& a, uint32_t& b) {
+    if (!sd_walk(vox_start, ids, vp, seg_node, seg_chunk, K, s_vp, s_dl, w)) return false;
+    k = w.k; a = w.a; b = w.b;
+    return true;
+  }
+  __device__ __forceinline__ uint32_t pos(uint32_t q) const { return sd_pos(s_vp, s_dl, w.m, q); }
+};
 template <bool OWN>
 __device__ __forceinline__ void sf_hist_body(const int32_t* __restrict__ cls, uint32_t n_classes, const uint32_t* __restrict__ perm,
                                              const uint32_t* __restrict__ vox_start, const uint32_t* __restrict__ ids,
@@ -265,44 +206,7 @@ __device__ __forceinline__ void sf_hist_body(const int32_t* __restrict__ cls, ui
                                              unsigned long long* __restrict__ n_outside, int64_t own_first, int64_t own_end) {
   __shared__ uint32_t s_vp[SD_CHUNK];
   __shared__ uint32_t s_dl[SD_CHUNK];
-  __shared__ uint32_t s_cnt[1024 + 1];
-  SdChunk w;
-  if (!sd_walk(vox_start, ids, vp, seg_node, seg_chunk, K, s_vp, s_dl, w)) return;
-  for (uint32_t j = threadIdx.x; j <= n_classes; j += SD_TB) s_cnt[j] = 0;
-  __syncthreads();
-  const uint32_t lane = threadIdx.x & 63;
-  for (int it = 0; it < SD_PPT; ++it) {
-    const uint32_t q = w.a + (uint32_t)it * SD_TB + threadIdx.x;
-    bool act = q < w.b;
-    uint32_t slot = 0;
-    if (act) {
-      size_t ri = (size_t)perm[sd_pos(s_vp, s_dl, w.m, q)];
-      if (OWN) {
-        const int64_t o = (int64_t)ri;
-        act = o >= own_first && o < own_end;
-        ri = act ? (size_t)(o - own_first) : 0;
-      }
-      if (act) {
-        const int32_t v = cls[ri];
-        slot = (v < 0 || (uint32_t)v >= n_classes) ? n_classes : (uint32_t)v;
-      }
-    }
-    // the lanes that share the first active lane's class fold into one add; the others add one each
-    const uint64_t am = __ballot(act);
-    if (am == 0) continue;
-    const uint32_t first = (uint32_t)__ffsll((unsigned long long)am) - 1u;
-    const uint32_t lead = __shfl(slot, (int)first, 64);
-    const uint64_t peers = __ballot(act && slot == lead);
-    if (lane == first) atomicAdd(&s_cnt[lead], (uint32_t)__popcll(peers));
-    else if (act && slot != lead) atomicAdd(&s_cnt[slot], 1u);
-  }
-  __syncthreads();
-  for (uint32_t j = threadIdx.x; j <= n_classes; j += SD_TB) {
-    const uint32_t v = s_cnt[j];
-    if (v == 0) continue;
-    if (j < n_classes) atomicAdd(hist + (size_t)w.k * n_classes + j, (unsigned long long)v);
-    else atomicAdd(n_outside + w.k, (unsigned long long)v);
-  }
+  sf_hist_chunk<OWN>(cls, n_classes, perm, SfNodeWalk{vox_start, ids, vp, seg_node, seg_chunk, K, s_vp, s_dl, {}}, hist, n_outside, own_first, own_end);
 }
 
 __global__ __launch_bounds__(SD_TB) void k_sf_hist(const int32_t* __restrict__ cls, uint32_t n_classes, const uint32_t* __restrict__ perm,
@@ -342,6 +246,18 @@ __global__ __launch_bounds__(256) void k_sf_majority(const unsigned long long* _
   if (lane != 0) return;
   majority[k] = best > 0 ? (int32_t)arg : -1;
   majority_count[k] = (long long)best;
+}
+
+// the launch sites of the two folds for the passes of other files (pointfield.hip): k_sf_final over the partials of one channel group,
+// k_sf_majority over a K x n_classes table; left on the context's stream
+void sf_launch_final(vgs_ctx* c, const uint32_t* seg_chunk, const double* part, uint32_t n_part, int64_t K, uint32_t C, uint32_t c0, uint32_t ng,
+                     const double* anchor, int64_t* o_n, double* o_mean, double* o_var, float* o_min, float* o_max) {
+  hipLaunchKernelGGL(k_sf_final, dim3((unsigned)(((size_t)K * ng + 3) / 4)), dim3(256), 0, c->stream, seg_chunk, part, n_part, (uint32_t)K, C, c0, ng, anchor,
+                     o_n, o_mean, o_var, o_min, o_max);
+}
+void sf_launch_majority(vgs_ctx* c, const int64_t* hist, int32_t n_classes, int64_t K, int32_t* majority, int64_t* majority_count) {
+  hipLaunchKernelGGL(k_sf_majority, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, (const unsigned long long*)hist, (uint32_t)n_classes,
+                     (uint32_t)K, majority, (long long*)majority_count);
 }
 
 static vgs_status sf_check_state(vgs_ctx* c, const char* fn) {
@@ -398,9 +314,8 @@ static vgs_status sf_field_stats(vgs_ctx* c, const float* field_dev, int32_t n_c
     const uint32_t ng = C - c0 < SF_G ? C - c0 : SF_G;
     hipLaunchKernelGGL(k_sf_chunks, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, field_dev, stride_f, C, c0, ng, c->perm_b.p,
                        c->vox_start.p, P.ids, P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, c->sf_anchor.p, c->sf_part.p);
-    hipLaunchKernelGGL(k_sf_final, dim3((unsigned)(((size_t)K * ng + 3) / 4)), dim3(256), 0, c->stream, P.seg_chunk, c->sf_part.p,
-                       (uint32_t)P.n_chunks_max, (uint32_t)K, C, c0, ng, c->sf_anchor.p, c->sf_nvalid.p, c->sf_mean.p, c->sf_var.p, c->sf_min.p,
-                       c->sf_max.p);
+    sf_launch_final(c, P.seg_chunk, c->sf_part.p, (uint32_t)P.n_chunks_max, K, C, c0, ng, c->sf_anchor.p, c->sf_nvalid.p, c->sf_mean.p, c->sf_var.p,
+                    c->sf_min.p, c->sf_max.p);
   }
   VGS_HIP_TRY(c, hipGetLastError());
   if (n_valid) VGS_HIP_TRY(c, hipMemcpyAsync(n_valid, c->sf_nvalid.p, kc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
@@ -468,8 +383,7 @@ static vgs_status sf_class_hist(vgs_ctx* c, const int32_t* cls_dev, int32_t n_cl
   VGS_HIP_TRY(c, hipMemsetAsync(d_hist, 0, (kc + k) * sizeof(int64_t), c->stream));
   hipLaunchKernelGGL(k_sf_hist, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, cls_dev, (uint32_t)n_classes, c->perm_b.p, c->vox_start.p,
                      P.ids, P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, (unsigned long long*)d_hist, (unsigned long long*)d_out);
-  hipLaunchKernelGGL(k_sf_majority, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, (const unsigned long long*)d_hist, (uint32_t)n_classes,
-                     (uint32_t)K, c->sf_maj.p, (long long*)d_majc);
+  sf_launch_majority(c, d_hist, n_classes, K, c->sf_maj.p, d_majc);
   VGS_HIP_TRY(c, hipGetLastError());
   if (hist) VGS_HIP_TRY(c, hipMemcpyAsync(hist, d_hist, kc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   if (n_outside) VGS_HIP_TRY(c, hipMemcpyAsync(n_outside, d_out, k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
@@ -659,8 +573,8 @@ extern "C" vgs_status vgs_segment_field_stats_from_moments(vgs_ctx* c, int64_t K
   VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_anchor.p, anchor, kc * sizeof(double), hipMemcpyHostToDevice, c->stream));
   for (uint32_t c0 = 0; c0 < C; c0 += SF_G) {
     const uint32_t ng = C - c0 < SF_G ? C - c0 : SF_G;
-    hipLaunchKernelGGL(k_sf_final, dim3((unsigned)((k * ng + 3) / 4)), dim3(256), 0, c->stream, c->sf_idx.p, c->sf_part.p + (size_t)(c0 / SF_G) * per_group,
-                       (uint32_t)K, (uint32_t)K, C, c0, ng, c->sf_anchor.p, c->sf_nvalid.p, c->sf_mean.p, c->sf_var.p, c->sf_min.p, c->sf_max.p);
+    sf_launch_final(c, c->sf_idx.p, c->sf_part.p + (size_t)(c0 / SF_G) * per_group, (uint32_t)K, K, C, c0, ng, c->sf_anchor.p, c->sf_nvalid.p, c->sf_mean.p,
+                    c->sf_var.p, c->sf_min.p, c->sf_max.p);
   }
   VGS_HIP_TRY(c, hipGetLastError());
   if (mean) VGS_HIP_TRY(c, hipMemcpyAsync(mean, c->sf_mean.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));

@@ -9,6 +9,10 @@
 //   sd_segment_algebra  a row of the descriptor table from folded moments (centroid, covariance, Jacobi, sign rule, features)
 //   sb_chunk_extents    the partial record of one chunk of the box pass: min / max of the projections onto a frame
 //   sb_fold_partials, sb_box_row   the same fold for the extents, and a row of the box table from them
+//   sf_chunk_sums       the partial records of one chunk of the attribute pass (segfield.hip, pointfield.hip): per channel S1, S2, count,
+//                       min, max over the finite values
+//   sf_hist_chunk       the class counts of one chunk: LDS counters, ballot fold, integer adds to the table; the chunk comes from a walk
+//                       object (segfield.hip: sd_walk / sd_pos over staged nodes; pointfield.hip: ps_walk over pos_sorted)
 #ifndef VGS_SEGPASS_HPP_
 #define VGS_SEGPASS_HPP_
 
@@ -318,6 +322,161 @@ __device__ __forceinline__ void sb_box_row(size_t k, const double (&mn)[3], cons
   for (int r = 0; r < 3; ++r)
     o_center[3 * k + r] = cen[3 * k + r] + ((W[3 * r + 0] * mid[0] + W[3 * r + 1] * mid[1]) + W[3 * r + 2] * mid[2]);
 }
+
+// ------------------------------------------------------------------------------------- chunks of a per-point labelling (ps_sort_points)
+// The walk of a chunk workgroup (blockIdx.x) from chunk to label: the label k of the chunk, the start s0 of the label's run and the
+// chunk's range [a, b) in pos_sorted.  False for a workgroup past the real number of chunks.
+struct PsChunk { uint32_t k, s0, a, b; };
+__device__ __forceinline__ bool ps_walk(const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_chunk, uint32_t K, PsChunk& o) {
+  const uint32_t c = blockIdx.x;
+  if (c >= seg_chunk[K]) return false;
+  // label of chunk c: the last k with seg_chunk[k] <= c -- a label without a chunk shares its value with the next one and is passed over
+  uint32_t lo = 0, hi = K - 1;
+  while (lo < hi) { const uint32_t mid = lo + ((hi - lo + 1) >> 1); if (seg_chunk[mid] <= c) lo = mid; else hi = mid - 1; }
+  o.k = lo;
+  o.s0 = seg_start[lo];
+  o.a = o.s0 + (c - seg_chunk[lo]) * SD_CHUNK;
+  o.b = min(o.a + (uint32_t)SD_CHUNK, seg_start[lo + 1]);
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the attribute passes
+// segfield.hip walks the points of the node labelling (pos_of = sd_pos over the staged nodes), pointfield.hip those of a caller's per-point
+// labelling (pos_of = pos_sorted[q]); the row of a point is field + perm[pos] * stride.
+#define SF_G 4     // channels per pass over the points: 4 x (S1, S2, count, min, max) stay in registers
+#define SF_REC 5   // doubles per partial record of one (chunk, channel): S1, S2, count, min, max
+
+__device__ __forceinline__ double sf_wave_sum(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+  return x;
+}
+__device__ __forceinline__ double sf_wave_min(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x = fmin(x, __shfl_xor(x, m, 64));
+  return x;
+}
+__device__ __forceinline__ double sf_wave_max(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x = fmax(x, __shfl_xor(x, m, 64));
+  return x;
+}
+__device__ __forceinline__ bool sf_valid(float x) { return fabsf(x) < __builtin_huge_valf(); }   // finite: false for NaN and +-inf
+
+// The partial records of the chunk [a, b) of virtual points (b - a <= SD_CHUNK) for the channels c0 .. c0 + ng - 1 (ng <= SF_G) of the
+// field, about the anchors an[]: per channel, over the finite values, S1 = sum d, S2 = sum d d with d = (double)x - anchor, the count,
+// min and max.  The point of a lane at step `it` is pos_of(a + it * SD_TB + tid); wavefront butterfly, the waves through LDS in index
+// order.  OWN (tile contexts): only the points whose input index o = perm[pos] lies in [own_first, own_end) count, and their row is
+// field + (o - own_first) * stride.  Every thread of the workgroup calls it (two barriers inside; the first also covers what the caller
+// staged in LDS for pos_of).
+template <bool OWN, typename PosOf>
+__device__ __forceinline__ void sf_chunk_sums(const float* __restrict__ field, int64_t stride_f, uint32_t c0, uint32_t ng, uint32_t a, uint32_t b,
+                                              const double (&an)[SF_G], PosOf pos_of, const uint32_t* __restrict__ perm, int64_t own_first,
+                                              int64_t own_end, double* __restrict__ rec) {
+  __shared__ double s_red[SD_TB / 64][SF_G][SF_REC];
+  __syncthreads();
+  double s1[SF_G], s2[SF_G], cn[SF_G];
+  float mn[SF_G], mx[SF_G];
+#pragma unroll
+  for (int g = 0; g < SF_G; ++g) { s1[g] = 0.0; s2[g] = 0.0; cn[g] = 0.0; mn[g] = __builtin_huge_valf(); mx[g] = -__builtin_huge_valf(); }
+#pragma unroll 2
+  for (int it = 0; it < SD_PPT; ++it) {
+    const uint32_t q = a + (uint32_t)it * SD_TB + threadIdx.x;
+    if (q < b) {
+      const uint32_t pos = pos_of(q);
+      size_t ri = (size_t)perm[pos];
+      if (OWN) {
+        const int64_t o = (int64_t)ri;
+        if (o < own_first || o >= own_end) continue;
+        ri = (size_t)(o - own_first);
+      }
+      const float* row = field + ri * (size_t)stride_f + c0;
+#pragma unroll
+      for (int g = 0; g < SF_G; ++g) {
+        if ((uint32_t)g < ng) {
+          const float x = row[g];
+          if (sf_valid(x)) {
+            const double d = (double)x - an[g];   // exact conversion, then one fp64 operation per difference, product and sum
+            s1[g] += d;
+            s2[g] += d * d;
+            cn[g] += 1.0;
+            mn[g] = fminf(mn[g], x);
+            mx[g] = fmaxf(mx[g], x);
+          }
+        }
+      }
+    }
+  }
+  const int wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int g = 0; g < SF_G; ++g) {
+    const double a1 = sf_wave_sum(s1[g]), a2 = sf_wave_sum(s2[g]), a3 = sf_wave_sum(cn[g]);
+    const double a4 = sf_wave_min((double)mn[g]), a5 = sf_wave_max((double)mx[g]);
+    if ((threadIdx.x & 63) == 0) {
+      double* r = s_red[wv][g];
+      r[0] = a1; r[1] = a2; r[2] = a3; r[3] = a4; r[4] = a5;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < SF_G * SF_REC) {   // the waves in index order
+    const int g = threadIdx.x / SF_REC, f = threadIdx.x % SF_REC;
+    double v = s_red[0][g][f];
+    if (f < 3) { for (int u = 1; u < SD_TB / 64; ++u) v += s_red[u][g][f]; }
+    else if (f == 3) { for (int u = 1; u < SD_TB / 64; ++u) v = fmin(v, s_red[u][g][f]); }
+    else { for (int u = 1; u < SD_TB / 64; ++u) v = fmax(v, s_red[u][g][f]); }
+    rec[threadIdx.x] = v;
+  }
+}
+
+// One workgroup per chunk: the classes of its points counted in LDS (slot n_classes: out of range; a wavefront first folds the lanes that
+// share its first active lane's class into one add), the non-zero counters added to the zeroed tables hist (K x n_classes) and n_outside
+// (K).  Integer atomics: the sums do not depend on the order.  walk.begin(k, a, b) gives the chunk's label and its range [a, b) of virtual
+// points (false: the workgroup has no chunk) and may stage what walk.pos(q), the sorted position of the virtual point q, reads from LDS --
+// the barrier behind the zeroing covers it.  OWN as in sf_chunk_sums, the class of an own point being cls[o - own_first].
+template <bool OWN, typename Walk>
+__device__ __forceinline__ void sf_hist_chunk(const int32_t* __restrict__ cls, uint32_t n_classes, const uint32_t* __restrict__ perm, Walk walk,
+                                              unsigned long long* __restrict__ hist, unsigned long long* __restrict__ n_outside, int64_t own_first,
+                                              int64_t own_end) {
+  __shared__ uint32_t s_cnt[1024 + 1];
+  uint32_t k, a, b;
+  if (!walk.begin(k, a, b)) return;
+  for (uint32_t j = threadIdx.x; j <= n_classes; j += SD_TB) s_cnt[j] = 0;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  for (int it = 0; it < SD_PPT; ++it) {
+    const uint32_t q = a + (uint32_t)it * SD_TB + threadIdx.x;
+    bool act = q < b;
+    uint32_t slot = 0;
+    if (act) {
+      size_t ri = (size_t)perm[walk.pos(q)];
+      if (OWN) {
+        const int64_t o = (int64_t)ri;
+        act = o >= own_first && o < own_end;
+        ri = act ? (size_t)(o - own_first) : 0;
+      }
+      if (act) {
+        const int32_t v = cls[ri];
+        slot = (v < 0 || (uint32_t)v >= n_classes) ? n_classes : (uint32_t)v;
+      }
+    }
+    // the lanes that share the first active lane's class fold into one add; the others add one each
+    const uint64_t am = __ballot(act);
+    if (am == 0) continue;
+    const uint32_t first = (uint32_t)__ffsll((unsigned long long)am) - 1u;
+    const uint32_t lead = __shfl(slot, (int)first, 64);
+    const uint64_t peers = __ballot(act && slot == lead);
+    if (lane == first) atomicAdd(&s_cnt[lead], (uint32_t)__popcll(peers));
+    else if (act && slot != lead) atomicAdd(&s_cnt[slot], 1u);
+  }
+  __syncthreads();
+  for (uint32_t j = threadIdx.x; j <= n_classes; j += SD_TB) {
+    const uint32_t v = s_cnt[j];
+    if (v == 0) continue;
+    if (j < n_classes) atomicAdd(hist + (size_t)k * n_classes + j, (unsigned long long)v);
+    else atomicAdd(n_outside + k, (unsigned long long)v);
+  }
+}
+
 #endif   // __HIPCC__
 
 #endif

@@ -631,6 +631,17 @@ void sbt_launch_final(vgs_ctx* c, int64_t K, const uint32_t* seg_chunk, const do
 // (one pass on the device); and the host variants' upload into ps_in (*labels_dev = nullptr for n = 0)
 vgs_status vgs_check_label_range(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t n, int64_t K);
 vgs_status vgs_upload_point_labels(vgs_ctx* c, const int32_t* labels_host, int64_t n, const int32_t** labels_dev);
+// steps 1-3 of pointseg.hip's header: the octree points that carry a label 0 .. K-1 sorted by label (pos: sorted positions, a label's run ascending), per label the start of its
+// run (seg_start, K + 1 words) and its first chunk (seg_chunk, K + 1 words), in the ps_* scratch and left on the stream; the grid bound of
+// the chunk kernels.  sorted = false (nothing queued behind the range check) for K = 0.  pointfield.hip runs its kernels over the same sort
+struct PsSort { bool sorted; uint32_t *key, *pos, *seg_start, *seg_chunk; int64_t n_chunks_max; };
+vgs_status ps_sort_points(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t own_first, int64_t n_lab, int64_t K, size_t tmp_extra,
+                          int64_t* n_skipped, PsSort& S);
+// the folds of segfield.hip for pointfield.hip: k_sf_final over the chunk partials of one channel group (seg_chunk: K + 1 first chunks),
+// k_sf_majority over a K x n_classes table; left on the context's stream
+void sf_launch_final(vgs_ctx* c, const uint32_t* seg_chunk, const double* part, uint32_t n_part, int64_t K, uint32_t C, uint32_t c0, uint32_t ng,
+                     const double* anchor, int64_t* o_n, double* o_mean, double* o_var, float* o_min, float* o_max);
+void sf_launch_majority(vgs_ctx* c, const int64_t* hist, int32_t n_classes, int64_t K, int32_t* majority, int64_t* majority_count);
 vgs_status vgs_seggraph_on_device(vgs_ctx* c);   // seggraph.hip
 // tile contexts: halo[v] = label[k] for the voxel v of code[k] that this context holds and does not own, queued on the context's stream
 // (code, label: n entries in HBM; halo: V entries).  One kernel for the graph's table and the refinement's (seggraph.hip)
