@@ -34,6 +34,11 @@
 //   vgs_tiles_point_label_descriptors, vgs_tiles_point_label_boxes (in the --box-frame) and vgs_tiles_compare_point_labels (against
 //   <prefix>.<r>.truth.i32) -- collectives; no label leaves its rank -- and rank 0 writes the files, with the columns of vgs_run's
 //   --refined-segments, --refined-segment-boxes, --refined-matches and --refined-truth-matches.
+//   --refined-segment-fields <file.csv> --field-channels <C>, --refined-segment-classes <file.csv> --classes <C>: the attribute tables of the
+//   REFINED labels (they need --refine), from the same <prefix>.<r>.fields.f32 / <prefix>.<r>.classes.i32: every rank hands its refined
+//   labels and its rows to vgs_tiles_point_label_field_stats / vgs_tiles_point_label_class_histogram (collectives; nothing of a point
+//   leaves its rank) and rank 0 writes the files, with the columns of vgs_run's --refined-segment-fields / --refined-segment-classes.
+//   --field-channels and --classes serve the node option and the refined one alike.
 //   All of them can be combined.  A missing companion option, a value out of range (1 .. 64 channels, 1 .. 1024 classes) and an attribute
 //   or truth file that is missing or whose size does not match the rank's points are usage errors: exit status 2, before any collective.
 #include <arpa/inet.h>
@@ -100,6 +105,7 @@ struct Job {
   int field_channels = 0, n_classes = 0;
   std::string matches, truth_matches;   // --segment-matches / --truth-matches
   std::string r_segments, r_boxes, r_matches, r_truth_matches;   // --refined-segments / --refined-segment-boxes / --refined-matches / --refined-truth-matches
+  std::string r_fields, r_classes;    // --refined-segment-fields / --refined-segment-classes
   bool refine = false, refine_fill = true;   // --refine, --no-fill
   float patch_radius = -1.0f, switch_ratio = -1.0f;   // --patch-radius / --switch-ratio (negative: the context's default)
 };
@@ -112,7 +118,7 @@ static int check_attribute_files(const Job& J, int rank) {
   const long long pts = file_bytes(rank_file(J, rank, ".f32"));
   if (pts < 0) return 0;
   const long long n = pts / 12;
-  if (!J.fields.empty()) {
+  if (!J.fields.empty() || !J.r_fields.empty()) {
     const std::string path = rank_file(J, rank, ".fields.f32");
     const long long b = file_bytes(path);
     if (b != n * 4 * (long long)J.field_channels) {
@@ -120,7 +126,7 @@ static int check_attribute_files(const Job& J, int rank) {
       return 2;
     }
   }
-  if (!J.classes.empty()) {
+  if (!J.classes.empty() || !J.r_classes.empty()) {
     const std::string path = rank_file(J, rank, ".classes.i32");
     const long long b = file_bytes(path);
     if (b != n * 4) { std::fprintf(stderr, "%s: %lld bytes, but %lld points x 4 = %lld\n", path.c_str(), b, n, n * 4); return 2; }
@@ -164,6 +170,36 @@ static int write_boxes(const std::string& path, size_t k, const BoxArrays& A) {
   }
   return writeBoxesCsv(path, boxes);
 }
+// a field table of k rows x C channels (the channels named f0 .. f{C-1}) and a class table of k rows x nc classes
+struct FieldArrays {
+  std::vector<int64_t> nv; std::vector<double> an, me, va; std::vector<float> mn, mx;
+  explicit FieldArrays(size_t kc) : nv(kc + 1), an(kc + 1), me(kc + 1), va(kc + 1), mn(kc + 1), mx(kc + 1) {}
+};
+static int write_field_stats(const std::string& path, size_t k, size_t C, const FieldArrays& A) {
+  std::vector<std::string> names;
+  for (size_t ch = 0; ch < C; ++ch) names.push_back("f" + std::to_string(ch));
+  std::vector<pcl::ClusterFieldStats> stats(k);
+  for (size_t i = 0; i < k; ++i) {
+    pcl::ClusterFieldStats& f = stats[i];
+    f.n_valid.assign(A.nv.begin() + i * C, A.nv.begin() + (i + 1) * C); f.anchor.assign(A.an.begin() + i * C, A.an.begin() + (i + 1) * C);
+    f.mean.assign(A.me.begin() + i * C, A.me.begin() + (i + 1) * C); f.var.assign(A.va.begin() + i * C, A.va.begin() + (i + 1) * C);
+    f.vmin.assign(A.mn.begin() + i * C, A.mn.begin() + (i + 1) * C); f.vmax.assign(A.mx.begin() + i * C, A.mx.begin() + (i + 1) * C);
+  }
+  return writeFieldStatsCsv(path, names, stats);
+}
+struct ClassArrays {
+  std::vector<int64_t> hi, no, mc; std::vector<int32_t> ma;
+  ClassArrays(size_t k, size_t nc) : hi(k * nc + 1), no(k + 1), mc(k + 1), ma(k + 1) {}
+};
+static int write_class_hist(const std::string& path, size_t k, size_t nc, const ClassArrays& A) {
+  std::vector<pcl::ClusterClassHistogram> hist(k);
+  for (size_t i = 0; i < k; ++i) {
+    pcl::ClusterClassHistogram& h = hist[i];
+    h.hist.assign(A.hi.begin() + i * nc, A.hi.begin() + (i + 1) * nc);
+    h.n_outside = A.no[i]; h.majority = A.ma[i]; h.majority_count = A.mc[i];
+  }
+  return writeClassHistCsv(path, (int)nc, hist);
+}
 // the tables of the driver's last comparison (nc cells, G ids, K segment rows; m.summary is filled) into the match files; "" on success
 static std::string write_matches(vgs_tiles* t, int64_t nc, int64_t G, int64_t K, pcl::ClusterLabelComparison& m, const std::string& seg_path,
                                  const std::string& truth_path) {
@@ -187,8 +223,8 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
   if (!read_f32(J.prefix + "." + std::to_string(rank) + ".f32", xyz)) { *err = "cannot read the points of rank " + std::to_string(rank); return 1; }
   std::vector<float> field;
   std::vector<int32_t> cls;
-  if (!J.fields.empty() && !read_f32(rank_file(J, rank, ".fields.f32"), field)) { *err = "cannot read the fields of rank " + std::to_string(rank); return 1; }
-  if (!J.classes.empty() && !read_i32(rank_file(J, rank, ".classes.i32"), cls)) { *err = "cannot read the classes of rank " + std::to_string(rank); return 1; }
+  if ((!J.fields.empty() || !J.r_fields.empty()) && !read_f32(rank_file(J, rank, ".fields.f32"), field)) { *err = "cannot read the fields of rank " + std::to_string(rank); return 1; }
+  if ((!J.classes.empty() || !J.r_classes.empty()) && !read_i32(rank_file(J, rank, ".classes.i32"), cls)) { *err = "cannot read the classes of rank " + std::to_string(rank); return 1; }
   std::vector<int32_t> truth;
   if ((!J.matches.empty() || !J.r_matches.empty()) && !read_i32(rank_file(J, rank, ".truth.i32"), truth)) { *err = "cannot read the truth ids of rank " + std::to_string(rank); return 1; }
   vgs_tiles* t = nullptr;
@@ -246,45 +282,23 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
   }
   if (rc == 0 && !J.fields.empty()) {
     // the statistics of this rank's attribute rows over the global segments: a collective of every rank, the same table on each
-    const size_t k = (size_t)*kept, C = (size_t)J.field_channels, kc = k * C;
-    std::vector<int64_t> nv(kc + 1);
-    std::vector<double> an(kc + 1), me(kc + 1), va(kc + 1);
-    std::vector<float> mn(kc + 1), mx(kc + 1);
+    const size_t k = (size_t)*kept, C = (size_t)J.field_channels;
+    FieldArrays A(k * C);
     int64_t K = 0;
-    if (vgs_tiles_segment_field_stats(t, field.data(), n, J.field_channels, 4 * (int64_t)J.field_channels, &K, nv.data(), an.data(), me.data(), va.data(),
-                                      mn.data(), mx.data()) != VGS_OK) {
+    if (vgs_tiles_segment_field_stats(t, field.data(), n, J.field_channels, 4 * (int64_t)J.field_channels, &K, A.nv.data(), A.an.data(), A.me.data(), A.va.data(),
+                                      A.mn.data(), A.mx.data()) != VGS_OK) {
       *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
       rc = 1;
-    } else if (rank == 0) {
-      std::vector<std::string> names;
-      for (size_t ch = 0; ch < C; ++ch) names.push_back("f" + std::to_string(ch));
-      std::vector<pcl::ClusterFieldStats> stats(k);
-      for (size_t i = 0; i < k; ++i) {
-        pcl::ClusterFieldStats& f = stats[i];
-        f.n_valid.assign(nv.begin() + i * C, nv.begin() + (i + 1) * C); f.anchor.assign(an.begin() + i * C, an.begin() + (i + 1) * C);
-        f.mean.assign(me.begin() + i * C, me.begin() + (i + 1) * C); f.var.assign(va.begin() + i * C, va.begin() + (i + 1) * C);
-        f.vmin.assign(mn.begin() + i * C, mn.begin() + (i + 1) * C); f.vmax.assign(mx.begin() + i * C, mx.begin() + (i + 1) * C);
-      }
-      if (writeFieldStatsCsv(J.fields, names, stats) != 0) { *err = "cannot write " + J.fields; rc = 1; }
-    }
+    } else if (rank == 0 && write_field_stats(J.fields, k, C, A) != 0) { *err = "cannot write " + J.fields; rc = 1; }
   }
   if (rc == 0 && !J.classes.empty()) {
     const size_t k = (size_t)*kept, nc = (size_t)J.n_classes;
-    std::vector<int64_t> hi(k * nc + 1), no(k + 1), mc(k + 1);
-    std::vector<int32_t> ma(k + 1);
+    ClassArrays A(k, nc);
     int64_t K = 0;
-    if (vgs_tiles_segment_class_histogram(t, cls.data(), n, J.n_classes, &K, hi.data(), no.data(), ma.data(), mc.data()) != VGS_OK) {
+    if (vgs_tiles_segment_class_histogram(t, cls.data(), n, J.n_classes, &K, A.hi.data(), A.no.data(), A.ma.data(), A.mc.data()) != VGS_OK) {
       *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
       rc = 1;
-    } else if (rank == 0) {
-      std::vector<pcl::ClusterClassHistogram> hist(k);
-      for (size_t i = 0; i < k; ++i) {
-        pcl::ClusterClassHistogram& h = hist[i];
-        h.hist.assign(hi.begin() + i * nc, hi.begin() + (i + 1) * nc);
-        h.n_outside = no[i]; h.majority = ma[i]; h.majority_count = mc[i];
-      }
-      if (writeClassHistCsv(J.classes, J.n_classes, hist) != 0) { *err = "cannot write " + J.classes; rc = 1; }
-    }
+    } else if (rank == 0 && write_class_hist(J.classes, k, nc, A) != 0) { *err = "cannot write " + J.classes; rc = 1; }
   }
   if (rc == 0 && !J.matches.empty()) {
     // the score against this rank's reference ids over the global segments: a collective of every rank, the same tables on each
@@ -342,6 +356,26 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
         if (!e.empty()) { *err = e; rc = 1; }
       }
     }
+    if (rc == 0 && !J.r_fields.empty()) {
+      const size_t C = (size_t)J.field_channels;
+      FieldArrays A(k * C);
+      int64_t skipped = 0;
+      if (vgs_tiles_point_label_field_stats(t, fine.data(), *kept, field.data(), n, J.field_channels, 4 * (int64_t)J.field_channels, &skipped, A.nv.data(),
+                                            A.an.data(), A.me.data(), A.va.data(), A.mn.data(), A.mx.data()) != VGS_OK) {
+        *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+        rc = 1;
+      } else if (rank == 0 && write_field_stats(J.r_fields, k, C, A) != 0) { *err = "cannot write " + J.r_fields; rc = 1; }
+    }
+    if (rc == 0 && !J.r_classes.empty()) {
+      const size_t nc = (size_t)J.n_classes;
+      ClassArrays A(k, nc);
+      int64_t skipped = 0;
+      if (vgs_tiles_point_label_class_histogram(t, fine.data(), *kept, cls.data(), n, J.n_classes, &skipped, A.hi.data(), A.no.data(), A.ma.data(),
+                                                A.mc.data()) != VGS_OK) {
+        *err = std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+        rc = 1;
+      } else if (rank == 0 && write_class_hist(J.r_classes, k, nc, A) != 0) { *err = "cannot write " + J.r_classes; rc = 1; }
+    }
   }
   if (rc == 0) {
     labels.resize((size_t)n);
@@ -391,7 +425,7 @@ static bool exchange_id(ncclUniqueId* id, int rank, int world, const char* addr,
 }
 
 static void print_usage(const char* exe) {
-  std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] [--refine [--patch-radius r] [--switch-ratio s] [--no-fill] [--refined-segments file.csv] [--refined-segment-boxes file.csv] [--refined-matches file.csv [--refined-truth-matches file.csv]]] <prefix>\n", exe);
+  std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] [--refine [--patch-radius r] [--switch-ratio s] [--no-fill] [--refined-segments file.csv] [--refined-segment-boxes file.csv] [--refined-matches file.csv [--refined-truth-matches file.csv]] [--refined-segment-fields file.csv --field-channels C] [--refined-segment-classes file.csv --classes C]] <prefix>\n", exe);
 }
 
 int main(int argc, char** argv) {
@@ -427,6 +461,8 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--refined-segment-boxes") && a + 1 < argc) J.r_boxes = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-matches") && a + 1 < argc) J.r_matches = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-truth-matches") && a + 1 < argc) J.r_truth_matches = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-segment-fields") && a + 1 < argc) J.r_fields = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-segment-classes") && a + 1 < argc) J.r_classes = argv[++a];
     else if (!std::strcmp(argv[a], "--refine")) J.refine = true;
     else if (!std::strcmp(argv[a], "--no-fill")) { J.refine_fill = false; refine_opts = true; }
     else if ((!std::strcmp(argv[a], "--patch-radius") || !std::strcmp(argv[a], "--switch-ratio")) && a + 1 < argc) {
@@ -445,15 +481,19 @@ int main(int argc, char** argv) {
   }
   if (mode < 0 || J.prefix.empty()) { print_usage(argv[0]); return 2; }
   if (!J.fields.empty() && !have_channels) { std::fprintf(stderr, "--segment-fields needs --field-channels <C>\n"); return 2; }
-  if (J.fields.empty() && have_channels) { std::fprintf(stderr, "--field-channels needs --segment-fields <file.csv>\n"); return 2; }
+  if (!J.r_fields.empty() && !have_channels) { std::fprintf(stderr, "--refined-segment-fields needs --field-channels <C>\n"); return 2; }
+  if (J.fields.empty() && J.r_fields.empty() && have_channels) { std::fprintf(stderr, "--field-channels needs --segment-fields <file.csv>\n"); return 2; }
   if (have_channels && (J.field_channels < 1 || J.field_channels > 64)) { std::fprintf(stderr, "--field-channels must be in 1 .. 64\n"); return 2; }
   if (!J.classes.empty() && !have_classes) { std::fprintf(stderr, "--segment-classes needs --classes <C>\n"); return 2; }
-  if (J.classes.empty() && have_classes) { std::fprintf(stderr, "--classes needs --segment-classes <file.csv>\n"); return 2; }
+  if (!J.r_classes.empty() && !have_classes) { std::fprintf(stderr, "--refined-segment-classes needs --classes <C>\n"); return 2; }
+  if (J.classes.empty() && J.r_classes.empty() && have_classes) { std::fprintf(stderr, "--classes needs --segment-classes <file.csv>\n"); return 2; }
   if (have_classes && (J.n_classes < 1 || J.n_classes > 1024)) { std::fprintf(stderr, "--classes must be in 1 .. 1024\n"); return 2; }
   if (J.matches.empty() && !J.truth_matches.empty()) { std::fprintf(stderr, "--truth-matches needs --segment-matches <file.csv>\n"); return 2; }
   if (refine_opts && !J.refine) { std::fprintf(stderr, "--patch-radius / --switch-ratio / --no-fill need --refine\n"); return 2; }
-  if (!J.refine && (!J.r_segments.empty() || !J.r_boxes.empty() || !J.r_matches.empty() || !J.r_truth_matches.empty())) {
-    std::fprintf(stderr, "--refined-segments / --refined-segment-boxes / --refined-matches / --refined-truth-matches need --refine\n");
+  if (!J.refine && (!J.r_segments.empty() || !J.r_boxes.empty() || !J.r_matches.empty() || !J.r_truth_matches.empty() || !J.r_fields.empty() ||
+                    !J.r_classes.empty())) {
+    std::fprintf(stderr, "--refined-segments / --refined-segment-boxes / --refined-matches / --refined-truth-matches / --refined-segment-fields / "
+                         "--refined-segment-classes need --refine\n");
     print_usage(argv[0]);
     return 2;
   }

@@ -565,7 +565,9 @@ vgs_status vgs_compare_point_labels_device(vgs_ctx* ctx, const int32_t* seg_labe
  *      vgs_segment_field_stats over the points sorted by label; the histogram adds integers);
  *   2. handed the context's own vgs_get_point_labels with K = counts[VGS_N_KEPT], the two calls return vgs_segment_field_stats and
  *      vgs_segment_class_histogram byte for byte, anchor included (the same device code over the same point sequence).
- * VGS_E_STATE before the context is segmented, and on a tile context: the tiled driver has no call for these tables yet.  VGS_E_ARG for a
+ * VGS_E_STATE before the context is segmented, and on a tile context: a rank holds only part of the cloud, and the tables over all ranks are
+ * vgs_tiles_point_label_field_stats and vgs_tiles_point_label_class_histogram of the tiled driver (include/vgs_tiles.h), built from
+ * vgs_own_point_label_field_moments and vgs_own_point_label_class_counts below.  VGS_E_ARG for a
  * wrong n, a NULL array with n > 0, bad channels, stride, classes or K, and a label >= K.  Computed on every call, nothing cached; no side
  * effects: labels, refined labels, every cached table and the context's last comparison stay as they are. */
 vgs_status vgs_point_label_field_stats(vgs_ctx* ctx, const int32_t* labels_host, int64_t K, const float* field_host, int64_t n,
@@ -623,6 +625,35 @@ vgs_status vgs_own_point_label_cells(vgs_ctx* ctx, int64_t K, const int32_t* seg
                                      int64_t* n_cells, int64_t* n_unannotated);
 vgs_status vgs_own_point_label_cells_device(vgs_ctx* ctx, int64_t K, const int32_t* seg_labels_dev, const int32_t* ref_dev, int64_t n_own,
                                             int64_t* n_cells, int64_t* n_unannotated);
+/* Attribute moments and class counts of a point labelling for a tile context (the tiled driver: vgs_tiles_point_label_field_stats and
+ * vgs_tiles_point_label_class_histogram build the global tables from them).  Tile contexts only: VGS_E_STATE before the context is segmented
+ * and on a context that is not a tile context (vgs_point_label_field_stats and vgs_point_label_class_histogram keep refusing a tile
+ * context).  labels, field and cls hold one row per point of the rank's OWN load: row i belongs to cloud point own_first + i of
+ * vgs_set_own_point_range and n_own must equal that range's length.  The label rules are those of vgs_own_point_label_moments: label l is
+ * row l for 0 <= l < K, a negative label no row, a label >= K is VGS_E_ARG, the message naming the first offending own index and its value;
+ * 0 <= K <= 2^31 - 1.  Channels, stride_bytes and classes as vgs_point_label_field_stats / vgs_point_label_class_histogram, the limit of
+ * 2^27 entries (VGS_E_UNSUPPORTED) included.  The host variants take both arrays on the host, the _device variants read both in place.
+ * One compact record per label with at least one own point in the octree, in ascending label order; *n_records of them, every array holds
+ * up to min(K, n_own) records.  The record fields are exactly those of vgs_get_own_segment_field_moments and
+ * vgs_get_own_segment_class_counts: anchor[k, c] = the value of the label's first own point in the sorted order of csrc/pointseg.hip
+ * (pos_sorted[seg_start[k]] of the own points), 0.0 where it is not finite; s1, s2 the sums about it over the finite values in the fixed
+ * shape of vgs_point_label_field_stats; vmin / vmax +inf / -inf for n_valid = 0.  *n_skipped counts the own points with a label >= 0 that
+ * lie outside the octree.  Any output pointer may be NULL.  One sort per call whatever the channel count (csrc/pointfield.hip: the kernel
+ * bodies of the single-context tables with own-row indexing); bit-identical from call to call.  Nothing is cached; no other table, no
+ * labels, no own records of vgs_own_point_label_moments and no last comparison are touched. */
+vgs_status vgs_own_point_label_field_moments(vgs_ctx* ctx, int64_t K, const int32_t* labels_host, const float* field_host, int64_t n_own,
+                                             int32_t n_channels, int64_t stride_bytes, int64_t* n_records, int64_t* n_skipped, int32_t* label,
+                                             int64_t* n_valid, double* anchor, double* s1, double* s2, float* vmin, float* vmax);
+vgs_status vgs_own_point_label_field_moments_device(vgs_ctx* ctx, int64_t K, const int32_t* labels_dev, const float* field_dev, int64_t n_own,
+                                                    int32_t n_channels, int64_t stride_bytes, int64_t* n_records, int64_t* n_skipped,
+                                                    int32_t* label, int64_t* n_valid, double* anchor, double* s1, double* s2, float* vmin,
+                                                    float* vmax);
+vgs_status vgs_own_point_label_class_counts(vgs_ctx* ctx, int64_t K, const int32_t* labels_host, const int32_t* cls_host, int64_t n_own,
+                                            int32_t n_classes, int64_t* n_records, int64_t* n_skipped, int32_t* label, int64_t* hist,
+                                            int64_t* n_outside);
+vgs_status vgs_own_point_label_class_counts_device(vgs_ctx* ctx, int64_t K, const int32_t* labels_dev, const int32_t* cls_dev, int64_t n_own,
+                                                   int32_t n_classes, int64_t* n_records, int64_t* n_skipped, int32_t* label, int64_t* hist,
+                                                   int64_t* n_outside);
 
 /* Point-level label refinement at segment boundaries (no reference counterpart).  A point's label (vgs_get_point_labels) is the label of
  * its node -- a voxel for VGS, a supervoxel for SVGS -- so segment boundaries are staircases of whole nodes, and the points of voxels with

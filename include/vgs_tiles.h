@@ -235,7 +235,8 @@ vgs_status vgs_tiles_segment_class_histogram(vgs_tiles* t, const int32_t* cls_ho
                                              int64_t* n_outside, int32_t* majority, int64_t* majority_count);
 vgs_status vgs_tiles_segment_class_histogram_device(vgs_tiles* t, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* K, int64_t* hist,
                                                     int64_t* n_outside, int32_t* majority, int64_t* majority_count);
-/* host wall time of the last attribute collective on this rank (field statistics or histogram, whichever came last), milliseconds: own
+/* host wall time of the last attribute collective on this rank (field statistics or histogram, of the node labels or of a caller's point
+ * labelling -- vgs_tiles_point_label_field_stats / _class_histogram stamp the same slots -- whichever came last), milliseconds: own
  * records on the GPU (with upload and download), the exchange, the fold, the finish on the GPU (with upload and download; 0 for the
  * histogram, whose majority rule is part of the fold), total */
 enum { VGS_TILES_F_OWN = 0, VGS_TILES_F_EXCHANGE = 1, VGS_TILES_F_FOLD = 2, VGS_TILES_F_FINISH = 3, VGS_TILES_F_TOTAL = 4, VGS_TILES_F_COUNT = 5 };
@@ -385,6 +386,41 @@ vgs_status vgs_tiles_compare_point_labels(vgs_tiles* t, const int32_t* seg_label
                                           int64_t* n_refs, int64_t* summary /* 12 */);
 vgs_status vgs_tiles_compare_point_labels_device(vgs_tiles* t, const int32_t* seg_labels_dev, int64_t K, const int32_t* ref_dev, int64_t n,
                                                  int64_t* n_cells, int64_t* n_refs, int64_t* summary /* 12 */);
+/* Field statistics and class histogram of ANY per-point labelling the caller supplies, over all ranks: the tables, fields, types and NaN
+ * rules of vgs_point_label_field_stats and vgs_point_label_class_histogram (include/vgs.h) with K rows of the caller's, over the points of
+ * all ranks -- mean intensity or majority class of the REFINED segments of a tiled scene, which the node tables above cannot give (a
+ * boundary voxel holds two or three refined labels).  labels, field and cls hold one row per point the rank gave to vgs_tiles_set_points,
+ * in that order; n must equal that call's n.  Label rules as vgs_tiles_point_label_descriptors; channels, stride_bytes, classes and the
+ * limit of 2^27 entries (VGS_E_UNSUPPORTED) as in include/vgs.h.  Outputs are host arrays of K rows, any may be NULL.  The _device variants
+ * read both inputs from HBM in place (this rank's device, complete before the call).
+ * Protocol (csrc/tiles.cpp).  No point, label or attribute leaves its rank; every point is counted once, by the rank that loaded it.  No
+ * field counts nodes, so a voxel that holds points of several ranks needs no pair records: the folds add per-point quantities only.
+ * Nothing is cached: EVERY call is collective, K = 0 included (the ranks still agree on n_skipped), and makes exactly ONE
+ * all_gather_varlen of 8-byte words: a header of five words (status word, record count, n_channels or n_classes, K, the rank's own
+ * n_skipped), then the rank's records of its own points (vgs_own_point_label_field_moments / vgs_own_point_label_class_counts, one sort
+ * and one small pipeline on its GPU) in the wire format of the two exchanges above, unchanged.  Behind it, the same on every rank:
+ * vgs_tiles_fold_field_moments then vgs_segment_field_stats_from_moments, or vgs_tiles_fold_class_counts (the majority rule is part of the
+ * fold); both folds unchanged.  *n_skipped is the sum over the ranks.  `anchor` is the folded table's own shift: per (k, channel) the
+ * anchor of the lowest rank with a valid value.  A label no point carries on any rank gives the empty row of the single-context calls.
+ * Every rank receives the same bytes, bit-identical from call to call and run to run; with one rank the table is the single context's byte
+ * for byte.  vgs_tiles_run gains no launch and no collective; the run, all cached tables and the refine halo table are not touched.
+ * Failures.  VGS_E_STATE before a run is decided locally (no collective).  Everything a rank can get wrong on its own -- a wrong n, a NULL
+ * array with n > 0, bad channels, classes or stride, K out of range, a label >= K (the message names the first offending index and its
+ * value), a failing context call, the injected VGS_TILES_FAIL_AT=point_labels -- travels in the status word: the failing rank returns its
+ * own status and message, the others VGS_E_PEER naming it.  Ranks that are each valid but disagree on K, n_channels or n_classes all
+ * return VGS_E_ARG after the exchange; the message names the lowest rank that differs from rank 0.
+ * The calls stamp the slots of vgs_tiles_get_field_times and vgs_tiles_get_field_payload. */
+vgs_status vgs_tiles_point_label_field_stats(vgs_tiles* t, const int32_t* labels_host, int64_t K, const float* field_host, int64_t n, int32_t n_channels,
+                                             int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor, double* mean, double* var,
+                                             float* vmin, float* vmax);
+vgs_status vgs_tiles_point_label_field_stats_device(vgs_tiles* t, const int32_t* labels_dev, int64_t K, const float* field_dev, int64_t n,
+                                                    int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor,
+                                                    double* mean, double* var, float* vmin, float* vmax);
+vgs_status vgs_tiles_point_label_class_histogram(vgs_tiles* t, const int32_t* labels_host, int64_t K, const int32_t* cls_host, int64_t n, int32_t n_classes,
+                                                 int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority, int64_t* majority_count);
+vgs_status vgs_tiles_point_label_class_histogram_device(vgs_tiles* t, const int32_t* labels_dev, int64_t K, const int32_t* cls_dev, int64_t n,
+                                                        int32_t n_classes, int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority,
+                                                        int64_t* majority_count);
 /* host arithmetic only, no context (tests): per label 0 .. K-1 the number of distinct (code, label) pairs among the pair records of all
  * ranks, rec_off[r] .. rec_off[r + 1] being rank r's.  VGS_E_ARG for a label outside 0 .. K-1. */
 vgs_status vgs_tiles_fold_label_pairs(int world, const int64_t* rec_off /* world + 1 */, const uint64_t* code, const int32_t* label, int64_t K,

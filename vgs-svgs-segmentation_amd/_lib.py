@@ -139,6 +139,10 @@ SYMBOLS = [
     ("vgs_get_own_point_label_extents_device", C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_own_point_label_cells", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
     ("vgs_own_point_label_cells_device", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
+    ("vgs_own_point_label_field_moments", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int64] + [_P] * 9),
+    ("vgs_own_point_label_field_moments_device", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int64] + [_P] * 9),
+    ("vgs_own_point_label_class_counts", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int32] + [_P] * 5),
+    ("vgs_own_point_label_class_counts_device", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int32] + [_P] * 5),
     ("vgs_get_own_segment_field_moments", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_get_own_segment_field_moments_device", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("vgs_segment_field_stats_from_moments", C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -248,12 +248,17 @@ __global__ __launch_bounds__(256) void k_sf_majority(const unsigned long long* _
   majority_count[k] = (long long)best;
 }
 
-// the launch sites of the two folds for the passes of other files (pointfield.hip): k_sf_final over the partials of one channel group,
-// k_sf_majority over a K x n_classes table; left on the context's stream
+// the launch sites of the folds for the passes of other files (pointfield.hip): k_sf_final and, for tile contexts, k_sf_own_records over
+// the partials of one channel group, k_sf_majority over a K x n_classes table; left on the context's stream
 void sf_launch_final(vgs_ctx* c, const uint32_t* seg_chunk, const double* part, uint32_t n_part, int64_t K, uint32_t C, uint32_t c0, uint32_t ng,
                      const double* anchor, int64_t* o_n, double* o_mean, double* o_var, float* o_min, float* o_max) {
   hipLaunchKernelGGL(k_sf_final, dim3((unsigned)(((size_t)K * ng + 3) / 4)), dim3(256), 0, c->stream, seg_chunk, part, n_part, (uint32_t)K, C, c0, ng, anchor,
                      o_n, o_mean, o_var, o_min, o_max);
+}
+void sf_launch_own_records(vgs_ctx* c, const uint32_t* seg_chunk, const double* part, uint32_t n_part, int64_t K, uint32_t C, uint32_t c0, uint32_t ng,
+                           int64_t* o_n, double* o_s1, double* o_s2, float* o_min, float* o_max) {
+  hipLaunchKernelGGL(k_sf_own_records, dim3((unsigned)(((size_t)K * ng + 3) / 4)), dim3(256), 0, c->stream, seg_chunk, part, n_part, (uint32_t)K, C, c0, ng,
+                     o_n, o_s1, o_s2, o_min, o_max);
 }
 void sf_launch_majority(vgs_ctx* c, const int64_t* hist, int32_t n_classes, int64_t K, int32_t* majority, int64_t* majority_count) {
   hipLaunchKernelGGL(k_sf_majority, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, c->stream, (const unsigned long long*)hist, (uint32_t)n_classes,

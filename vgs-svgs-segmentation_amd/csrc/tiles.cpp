@@ -546,8 +546,8 @@ template <typename F> int first_bad_rank(int world, F bad) {
 // Where a rank can be told to fail (tests of the agreed-status protocol: VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=<name>).  points, grid and
 // stages: before that phase's collective; upload: behind the last collective of vgs_tiles_set_points; the others: before the exchange of
 // that post-run collective (fields: vgs_tiles_segment_field_stats and vgs_tiles_segment_class_histogram alike; refine:
-// vgs_tiles_refine_point_labels; point_labels: the descriptor exchange of vgs_tiles_point_label_descriptors / _boxes and the cell exchange
-// of vgs_tiles_compare_point_labels).
+// vgs_tiles_refine_point_labels; point_labels: the descriptor exchange of vgs_tiles_point_label_descriptors / _boxes, the cell exchange
+// of vgs_tiles_compare_point_labels and the record exchange of vgs_tiles_point_label_field_stats / _class_histogram).
 enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_REFINE, PH_POINT_LABELS, PH_COUNT };
 const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare", "refine", "point_labels"};
 
@@ -603,7 +603,8 @@ struct vgs_tiles {
   bool box_valid[2] = {false, false};
   std::vector<double> b_center[2], b_half[2], b_frame[2], b_lo[2], b_hi[2];
   double btimes[VGS_TILES_B_COUNT] = {0};   // the last box collective, milliseconds of host wall time per phase
-  // the last attribute collective (field statistics or class histogram; nothing of it is cached): phases, own records, bytes sent
+  // the last attribute collective (field statistics or class histogram, of the node labels or of a caller's point labelling; nothing of
+  // it is cached): phases, own records, bytes sent
   double ftimes[VGS_TILES_F_COUNT] = {0};
   int64_t f_own = 0, f_bytes = 0;
   // the last tiled compare (its tables live in the context's cmp_* buffers; nothing of the input is cached): phases, own cells, bytes sent
@@ -674,6 +675,26 @@ static vgs_status check_word_payloads(vgs_tiles* t, const char* fn, const std::v
       return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed " + arg + " = " + std::to_string((int32_t)word(r, 2)) + ", rank 0 passed " + std::to_string((int32_t)word(0, 2)));
   for (size_t r = 0; r < gathered.size(); ++r)
     if (word(r, 1) < 0 || gathered[r].size() != 3 + (size_t)word(r, 1) * per) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
+  return VGS_OK;
+}
+
+constexpr size_t LF_HEADER = 5;   // header words of vgs_tiles_point_label_field_stats / _class_histogram
+// Behind the exchange of a point labelling's attribute records (a header of LF_HEADER words: status, record count, n_channels or n_classes,
+// K, own n_skipped): every rank was valid on its own -- do they describe the same table (words 3 and 2: K and `arg`), and is every
+// payload as long as its header says?  The same verdict on every rank, from the same words.
+template <typename W>
+static vgs_status check_label_payloads(vgs_tiles* t, const char* fn, const std::vector<std::vector<W>>& gathered, size_t per, const char* arg) {
+  auto word = [&](size_t r, size_t i) { return (int64_t)gathered[r][i]; };
+  for (size_t r = 0; r < gathered.size(); ++r)
+    if (gathered[r].size() < LF_HEADER) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
+  for (size_t r = 1; r < gathered.size(); ++r) {
+    if (word(r, 3) != word(0, 3))
+      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed K = " + std::to_string(word(r, 3)) + ", rank 0 passed " + std::to_string(word(0, 3)));
+    if (word(r, 2) != word(0, 2))
+      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed " + arg + " = " + std::to_string((int32_t)word(r, 2)) + ", rank 0 passed " + std::to_string((int32_t)word(0, 2)));
+  }
+  for (size_t r = 0; r < gathered.size(); ++r)
+    if (word(r, 1) < 0 || gathered[r].size() != LF_HEADER + (size_t)word(r, 1) * per) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
   return VGS_OK;
 }
 
@@ -1428,6 +1449,155 @@ vgs_status vgs_tiles_segment_class_histogram(vgs_tiles* t, const int32_t* cls_ho
 vgs_status vgs_tiles_segment_class_histogram_device(vgs_tiles* t, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* K, int64_t* hist,
                                                     int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
   return tiles_class_hist(t, "vgs_tiles_segment_class_histogram_device", true, cls_dev, n, n_classes, K, hist, n_outside, majority, majority_count);
+}
+
+// The two attribute tables of a caller's point labelling over the ranks (K rows of the caller's).  The protocol of the two calls above with
+// the records of vgs_own_point_label_field_moments / vgs_own_point_label_class_counts: ONE all_gather_varlen of 8-byte words -- a header of
+// FIVE words (status word, record count, n_channels or n_classes, K, this rank's own n_skipped), then the records in the wire format of
+// pack_field / pack_class, unchanged -> the same folds, unchanged -> (fields) vgs_segment_field_stats_from_moments.  No field counts nodes,
+// and every point is counted once, by the rank that loaded it: a voxel shared by ranks needs no pair records here.  Nothing is cached, so
+// every call is collective, K = 0 included (the ranks still agree on n_skipped).  Everything a rank can get wrong on its own is found by
+// the context call and travels in the status word; ranks that are each valid but disagree on K or on n_channels / n_classes all leave with
+// VGS_E_ARG behind the exchange.
+namespace {
+// the records a rank can have: one per label with an own point; 0 where the context refuses the call before it writes
+size_t label_record_cap(const vgs_tiles* t, int64_t K, int64_t per_label, bool per_ok) {
+  if (!per_ok || K < 0 || K > (int64_t)0x7fffffff || K * per_label > ((int64_t)1 << 27)) return 0;
+  return (size_t)std::min(K, std::max<int64_t>(t->n_own, 0));
+}
+}  // namespace
+
+static vgs_status tiles_label_field_stats(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t K, const float* field, int64_t n,
+                                          int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor, double* mean,
+                                          double* var, float* vmin, float* vmax) {
+  if (!t) return VGS_E_ARG;
+  vgs_status carry;
+  TRY(open_collective(t, fn, PH_POINT_LABELS, carry));
+  double ms[VGS_TILES_F_COUNT] = {0};
+  Stopwatch sw(ms);
+  const bool c_ok = n_channels >= 1 && n_channels <= 64;
+  const size_t C = c_ok ? (size_t)n_channels : 0;
+  std::vector<uint64_t> payload(LF_HEADER, 0);
+  int64_t n_rec = 0, n_skip = 0;
+  if (carry == VGS_OK) {
+    const size_t cap = label_record_cap(t, K, n_channels, c_ok);
+    const bool w = cap > 0;   // (a call the context refuses writes nothing; so does one without a record)
+    std::vector<int32_t> lab(cap + 1);
+    std::vector<int64_t> nv(cap * C + 1);
+    std::vector<double> an(cap * C + 1), m1(cap * C + 1), m2(cap * C + 1);
+    std::vector<float> mn(cap * C + 1), mx(cap * C + 1);
+    TCARRY_AS(on_device ? vgs_own_point_label_field_moments_device : vgs_own_point_label_field_moments,
+              on_device ? "vgs_own_point_label_field_moments_device" : "vgs_own_point_label_field_moments", t->ctx, K, labels, field, n, n_channels, stride_bytes,
+              &n_rec, &n_skip, w ? lab.data() : nullptr, w ? nv.data() : nullptr, w ? an.data() : nullptr, w ? m1.data() : nullptr, w ? m2.data() : nullptr,
+              w ? mn.data() : nullptr, w ? mx.data() : nullptr);
+    if (carry != VGS_OK || !w) { n_rec = 0; }
+    if (carry != VGS_OK) n_skip = 0;
+    payload.reserve(LF_HEADER + (size_t)n_rec * (1 + 5 * C));
+    for (size_t i = 0; i < (size_t)n_rec; ++i) pack_field(payload, lab.data(), nv.data(), an.data(), m1.data(), m2.data(), mn.data(), mx.data(), C, i);
+  }
+  set_header(payload, carry, n_rec, (int64_t)(uint32_t)n_channels);
+  payload[3] = (uint64_t)K; payload[4] = (uint64_t)n_skip;
+  sw.lap(VGS_TILES_F_OWN);
+  std::vector<std::vector<uint64_t>> gathered;
+  TRY(exchange(t, carry, payload, "point_labels", sw, VGS_TILES_F_EXCHANGE, gathered));
+  TRY(check_label_payloads(t, fn, gathered, 1 + 5 * C, "n_channels"));
+  std::vector<FieldRecs> recs(gathered.size());
+  int64_t skipped = 0;
+  for (size_t r = 0; r < gathered.size(); ++r) {
+    unpack_fields(gathered[r].data() + LF_HEADER, (size_t)gathered[r][1], C, recs[r]);
+    skipped += (int64_t)gathered[r][4];
+  }
+  std::vector<int64_t> fn_;
+  std::vector<double> fa, f1, f2;
+  std::vector<float> fmn, fmx;
+  if (!fold_field_moments(recs, K, (int)C, fn_, fa, f1, f2, fmn, fmx)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= K");
+  sw.lap(VGS_TILES_F_FOLD);
+  const size_t kc = (size_t)K * C;
+  std::vector<double> me(kc + 1), va(kc + 1);
+  std::vector<float> omn(kc + 1), omx(kc + 1);
+  TRY(behind_collective(t, vgs_segment_field_stats_from_moments(t->ctx, K, n_channels, fn_.data(), fa.data(), f1.data(), f2.data(), fmn.data(), fmx.data(), me.data(), va.data(), omn.data(), omx.data()),
+                        "vgs_segment_field_stats_from_moments"));
+  sw.lap(VGS_TILES_F_FINISH);
+  sw.total(VGS_TILES_F_TOTAL, t->ftimes);
+  if (n_skipped) *n_skipped = skipped;
+  put(fn_, n_valid); put(fa, anchor); put(me, mean, kc); put(va, var, kc); put(omn, vmin, kc); put(omx, vmax, kc);
+  t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(uint64_t));
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_point_label_field_stats(vgs_tiles* t, const int32_t* labels_host, int64_t K, const float* field_host, int64_t n, int32_t n_channels,
+                                             int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor, double* mean, double* var,
+                                             float* vmin, float* vmax) {
+  return tiles_label_field_stats(t, "vgs_tiles_point_label_field_stats", false, labels_host, K, field_host, n, n_channels, stride_bytes, n_skipped, n_valid,
+                                 anchor, mean, var, vmin, vmax);
+}
+
+vgs_status vgs_tiles_point_label_field_stats_device(vgs_tiles* t, const int32_t* labels_dev, int64_t K, const float* field_dev, int64_t n,
+                                                    int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor,
+                                                    double* mean, double* var, float* vmin, float* vmax) {
+  return tiles_label_field_stats(t, "vgs_tiles_point_label_field_stats_device", true, labels_dev, K, field_dev, n, n_channels, stride_bytes, n_skipped,
+                                 n_valid, anchor, mean, var, vmin, vmax);
+}
+
+static vgs_status tiles_label_class_hist(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t K, const int32_t* cls, int64_t n,
+                                         int32_t n_classes, int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority,
+                                         int64_t* majority_count) {
+  if (!t) return VGS_E_ARG;
+  vgs_status carry;
+  TRY(open_collective(t, fn, PH_POINT_LABELS, carry));
+  double ms[VGS_TILES_F_COUNT] = {0};
+  Stopwatch sw(ms);
+  const bool c_ok = n_classes >= 1 && n_classes <= 1024;
+  const size_t nc = c_ok ? (size_t)n_classes : 0;
+  std::vector<int64_t> payload(LF_HEADER, 0);
+  int64_t n_rec = 0, n_skip = 0;
+  if (carry == VGS_OK) {
+    const size_t cap = label_record_cap(t, K, n_classes, c_ok);
+    const bool w = cap > 0;
+    std::vector<int32_t> lab(cap + 1);
+    std::vector<int64_t> hi(cap * nc + 1), no(cap + 1);
+    TCARRY_AS(on_device ? vgs_own_point_label_class_counts_device : vgs_own_point_label_class_counts,
+              on_device ? "vgs_own_point_label_class_counts_device" : "vgs_own_point_label_class_counts", t->ctx, K, labels, cls, n, n_classes, &n_rec, &n_skip,
+              w ? lab.data() : nullptr, w ? hi.data() : nullptr, w ? no.data() : nullptr);
+    if (carry != VGS_OK || !w) { n_rec = 0; }
+    if (carry != VGS_OK) n_skip = 0;
+    payload.reserve(LF_HEADER + (size_t)n_rec * (2 + nc));
+    for (size_t i = 0; i < (size_t)n_rec; ++i) pack_class(payload, lab.data(), hi.data(), no.data(), nc, i);
+  }
+  set_header(payload, carry, n_rec, (int64_t)n_classes);
+  payload[3] = K; payload[4] = n_skip;
+  sw.lap(VGS_TILES_F_OWN);
+  std::vector<std::vector<int64_t>> gathered;
+  TRY(exchange(t, carry, payload, "point_labels", sw, VGS_TILES_F_EXCHANGE, gathered));
+  TRY(check_label_payloads(t, fn, gathered, 2 + nc, "n_classes"));
+  std::vector<ClassRecs> recs(gathered.size());
+  int64_t skipped = 0;
+  for (size_t r = 0; r < gathered.size(); ++r) {
+    unpack_classes(gathered[r].data() + LF_HEADER, (size_t)gathered[r][1], nc, recs[r]);
+    skipped += gathered[r][4];
+  }
+  std::vector<int64_t> fh, fo, fc;
+  std::vector<int32_t> fm;
+  if (!fold_class_counts(recs, K, (int)nc, fh, fo, fm, fc)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= K");
+  sw.lap(VGS_TILES_F_FOLD);
+  sw.total(VGS_TILES_F_TOTAL, t->ftimes);   // (VGS_TILES_F_FINISH stays 0: the majority rule is integer work inside the fold)
+  if (n_skipped) *n_skipped = skipped;
+  put(fh, hist); put(fo, n_outside); put(fm, majority); put(fc, majority_count);
+  t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(int64_t));
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_point_label_class_histogram(vgs_tiles* t, const int32_t* labels_host, int64_t K, const int32_t* cls_host, int64_t n, int32_t n_classes,
+                                                 int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
+  return tiles_label_class_hist(t, "vgs_tiles_point_label_class_histogram", false, labels_host, K, cls_host, n, n_classes, n_skipped, hist, n_outside,
+                                majority, majority_count);
+}
+
+vgs_status vgs_tiles_point_label_class_histogram_device(vgs_tiles* t, const int32_t* labels_dev, int64_t K, const int32_t* cls_dev, int64_t n,
+                                                        int32_t n_classes, int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority,
+                                                        int64_t* majority_count) {
+  return tiles_label_class_hist(t, "vgs_tiles_point_label_class_histogram_device", true, labels_dev, K, cls_dev, n, n_classes, n_skipped, hist, n_outside,
+                                majority, majority_count);
 }
 
 vgs_status vgs_tiles_get_field_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::ftimes, ms, n); }

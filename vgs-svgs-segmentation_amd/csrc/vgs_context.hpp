@@ -638,7 +638,10 @@ struct PsSort { bool sorted; uint32_t *key, *pos, *seg_start, *seg_chunk; int64_
 vgs_status ps_sort_points(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t own_first, int64_t n_lab, int64_t K, size_t tmp_extra,
                           int64_t* n_skipped, PsSort& S);
 // the folds of segfield.hip for pointfield.hip: k_sf_final over the chunk partials of one channel group (seg_chunk: K + 1 first chunks),
-// k_sf_majority over a K x n_classes table; left on the context's stream
+// k_sf_own_records over the same for a tile context (raw n, S1, S2, min, max), k_sf_majority over a K x n_classes table; left on the
+// context's stream
+void sf_launch_own_records(vgs_ctx* c, const uint32_t* seg_chunk, const double* part, uint32_t n_part, int64_t K, uint32_t C, uint32_t c0, uint32_t ng,
+                           int64_t* o_n, double* o_s1, double* o_s2, float* o_min, float* o_max);
 void sf_launch_final(vgs_ctx* c, const uint32_t* seg_chunk, const double* part, uint32_t n_part, int64_t K, uint32_t C, uint32_t c0, uint32_t ng,
                      const double* anchor, int64_t* o_n, double* o_mean, double* o_var, float* o_min, float* o_max);
 void sf_launch_majority(vgs_ctx* c, const int64_t* hist, int32_t n_classes, int64_t K, int32_t* majority, int64_t* majority_count);

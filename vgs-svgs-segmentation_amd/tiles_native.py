@@ -141,6 +141,12 @@ def lib():
         for name in ("vgs_tiles_compare_point_labels", "vgs_tiles_compare_point_labels_device"):
             getattr(L, name).restype = C.c_int
             getattr(L, name).argtypes = [P, P, C.c_int64, P, C.c_int64, P, P, P]
+        for name in ("vgs_tiles_point_label_field_stats", "vgs_tiles_point_label_field_stats_device"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [P, P, C.c_int64, P, C.c_int64, C.c_int32, C.c_int64] + [P] * 7
+        for name in ("vgs_tiles_point_label_class_histogram", "vgs_tiles_point_label_class_histogram_device"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [P, P, C.c_int64, P, C.c_int64, C.c_int32] + [P] * 5
         L.vgs_tiles_fold_label_pairs.restype = C.c_int
         L.vgs_tiles_fold_label_pairs.argtypes = [C.c_int, P, P, P, C.c_int64, P]
         L.vgs_tiles_get_point_label_times.restype = C.c_int
@@ -634,6 +640,101 @@ class NativeTiles:
             raise VgsError(st, L.vgs_last_error_string(h).decode())
         out = {name: a[:nr.value] for name, a in out.items()}
         out["pair_code"], out["pair_label"], out["n_skipped"] = pc[:npair.value], pl[:npair.value], int(nskip.value)
+        return out
+
+    def _label_table_inputs(self, labels, other, what):
+        """labels of label_field_stats / label_class_histogram and the own-record calls: labels and the attribute array both numpy or both
+        torch tensors on the rank's device -> (array kept alive, pointer, n, on the device?)"""
+        from .api import Engine
+        if Engine._is_torch(labels) != Engine._is_torch(other):
+            raise ValueError(f"labels and {what} must both be numpy arrays or both be torch tensors on the rank's device")
+        return Engine._classes_input(labels, self.params.device)
+
+    def label_field_stats(self, labels, field, K):
+        """COLLECTIVE on every call (every rank makes it after run(), with the same K and number of channels; nothing is cached): field
+        statistics of ANY per-point labelling over all ranks -- the dict of Engine.label_field_stats() on the gathered points, K rows plus
+        n_skipped (the sum over the ranks), the same bytes on every rank (include/vgs_tiles.h, vgs_tiles_point_label_field_stats).
+        `labels` as describe_labels(), `field` as segment_field_stats(): one row per point of this rank's set_points(); both numpy arrays
+        or both torch tensors on this rank's device, which are read in place.  No point, label or attribute leaves the rank, only
+        per-label records."""
+        from .api import Engine
+        labels, lptr, ln, dev = self._label_table_inputs(labels, field, "field")
+        field, ptr, n, ch, stride, _ = Engine._field_input(field, self.params.device)
+        fn = self._L.vgs_tiles_point_label_field_stats_device if dev else self._L.vgs_tiles_point_label_field_stats
+        K = int(K)
+        k = K if 0 <= K <= 0x7fffffff and K * max(ch, 1) <= 1 << 27 else 0
+        out = {name: np.zeros((max(k, 1), max(ch, 1)), dtype=dt) for name, dt in Engine.FIELD_STAT_FIELDS}
+        skipped = C.c_int64(0)
+        # (the library takes one n for both arrays: it is handed the length that is not this rank's, if one is not, so that it names it)
+        self._ck(fn(self._h, lptr, K, ptr, ln if ln != self.n else n, ch, stride, C.byref(skipped), *(_vp(out[name]) for name, _ in Engine.FIELD_STAT_FIELDS)))
+        out = {name: a[:k, :max(ch, 0)] for name, a in out.items()}
+        out["n_skipped"] = int(skipped.value)
+        return out
+
+    def label_class_histogram(self, labels, classes, n_classes, K):
+        """COLLECTIVE on every call (every rank makes it after run(), with the same K and n_classes; nothing is cached): the class
+        histogram of ANY per-point labelling over all ranks -- the dict of Engine.label_class_histogram() on the gathered points, K rows
+        plus n_skipped, the same bytes on every rank (include/vgs_tiles.h, vgs_tiles_point_label_class_histogram).  `labels` as
+        describe_labels(), `classes` as segment_class_histogram(); both numpy arrays or both torch tensors on this rank's device."""
+        from .api import Engine
+        nc = int(n_classes)
+        labels, lptr, ln, dev = self._label_table_inputs(labels, classes, "classes")
+        classes, ptr, n, _ = Engine._classes_input(classes, self.params.device)
+        fn = self._L.vgs_tiles_point_label_class_histogram_device if dev else self._L.vgs_tiles_point_label_class_histogram
+        K = int(K)
+        ok = 0 <= K <= 0x7fffffff and 1 <= nc <= 1024 and K * nc <= 1 << 27
+        k, w1 = (K, nc) if ok else (0, 1)
+        out = {name: np.zeros((max(k, 1), w1) if w == 0 else max(k, 1), dtype=dt) for name, dt, w in Engine.CLASS_HIST_FIELDS}
+        skipped = C.c_int64(0)
+        self._ck(fn(self._h, lptr, K, ptr, ln if ln != self.n else n, nc, C.byref(skipped), *(_vp(out[name]) for name, _, _ in Engine.CLASS_HIST_FIELDS)))
+        out = {name: (a[:k, :nc if ok else 0] if a.ndim == 2 else a[:k]) for name, a in out.items()}
+        out["n_skipped"] = int(skipped.value)
+        return out
+
+    def own_point_label_field_moments(self, K, labels, field):
+        """this rank's attribute moments of a labelling of its own points (vgs_own_point_label_field_moments on its context; local, no
+        collective): a dict of label and FIELD_MOMENT_FIELDS arrays (records, C), one record per label with an own point in the octree,
+        plus n_skipped"""
+        from .api import Engine
+        L = _lib.lib()
+        h = self._ctx()
+        K = int(K)
+        labels, lptr, ln, dev = self._label_table_inputs(labels, field, "field")
+        field, ptr, n, ch, stride, _ = Engine._field_input(field, self.params.device)
+        fn = L.vgs_own_point_label_field_moments_device if dev else L.vgs_own_point_label_field_moments
+        cap = min(K, max(ln, 0)) if 0 <= K <= 0x7fffffff else 0   # (one record per label with an own point)
+        out = {"label": np.zeros(max(cap, 1), dtype=np.int32)}
+        for name, dt in FIELD_MOMENT_FIELDS:
+            out[name] = np.zeros((max(cap, 1), max(ch, 1)), dtype=dt)
+        nr, nskip = C.c_int64(0), C.c_int64(0)
+        st = fn(h, K, lptr, ptr, ln if ln != self.n else n, ch, stride, C.byref(nr), C.byref(nskip), _vp(out["label"]),
+                *(_vp(out[name]) for name, _ in FIELD_MOMENT_FIELDS))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        out = {name: a[:nr.value] for name, a in out.items()}
+        out["n_skipped"] = int(nskip.value)
+        return out
+
+    def own_point_label_class_counts(self, K, labels, classes, n_classes):
+        """this rank's class counts of a labelling of its own points (vgs_own_point_label_class_counts on its context; local, no
+        collective): a dict of label, hist (records, n_classes) and n_outside, plus n_skipped"""
+        from .api import Engine
+        L = _lib.lib()
+        h = self._ctx()
+        K, nc = int(K), int(n_classes)
+        labels, lptr, ln, dev = self._label_table_inputs(labels, classes, "classes")
+        classes, ptr, n, _ = Engine._classes_input(classes, self.params.device)
+        fn = L.vgs_own_point_label_class_counts_device if dev else L.vgs_own_point_label_class_counts
+        cap = min(K, max(ln, 0)) if 0 <= K <= 0x7fffffff else 0
+        w1 = nc if 1 <= nc <= 1024 else 1
+        out = {"label": np.zeros(max(cap, 1), dtype=np.int32), "hist": np.zeros((max(cap, 1), w1), dtype=np.int64),
+               "n_outside": np.zeros(max(cap, 1), dtype=np.int64)}
+        nr, nskip = C.c_int64(0), C.c_int64(0)
+        st = fn(h, K, lptr, ptr, ln if ln != self.n else n, nc, C.byref(nr), C.byref(nskip), _vp(out["label"]), _vp(out["hist"]), _vp(out["n_outside"]))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        out = {name: a[:nr.value] for name, a in out.items()}
+        out["n_skipped"] = int(nskip.value)
         return out
 
     def compare_labels(self, ref, labels=None, K=None):
