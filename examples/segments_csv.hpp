@@ -67,6 +67,20 @@ inline int writeBoxesCsv(const std::string& path, const std::vector<pcl::Cluster
   return std::fclose(f) == 0 ? 0 : -1;
 }
 
+// one row per connected part of a labelling (getLabelComponents), in part order: part, label, n_points, n_nodes, first_node, and
+// largest = 1 for the part with the most points of its label
+inline int writeComponentsCsv(const std::string& path, const pcl::LabelComponents& c) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "part,label,n_points,n_nodes,first_node,largest\n");
+  for (size_t p = 0; p < c.part_label.size(); ++p) {
+    const int32_t l = c.part_label[p];
+    const bool largest = l >= 0 && (size_t)l < c.label_largest.size() && c.label_largest[(size_t)l] == (int32_t)p;
+    std::fprintf(f, "%zu,%d,%lld,%d,%d,%d\n", p, (int)l, (long long)c.part_points[p], (int)c.part_nodes[p], (int)c.part_first_node[p], largest ? 1 : 0);
+  }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
 inline int writeFieldStatsCsv(const std::string& path, const std::vector<std::string>& names, const std::vector<pcl::ClusterFieldStats>& stats) {
   FILE* f = std::fopen(path.c_str(), "w");
   if (!f) return -1;

@@ -11,6 +11,8 @@
 //                  [--refined-segments <file.csv>] [--refined-segment-boxes <file.csv>]
 //                  [--refined-segment-fields <file.csv> --fields a[,b,...]] [--refined-segment-classes <file.csv> --class-field <name> --classes <C>]
 //                  [--refined-matches <file.csv> --truth-field <name> [--refined-truth-matches <file.csv>]]
+//                  [--refined-components <file.csv>] [--class-components <file.csv> --class-field <name> --classes <C>]
+//                  [--component-ids <file.i32>]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
 // --segments writes one CSV row per kept cluster (getClusterDescriptors, row i = cluster i of the output): label, n_points, n_nodes,
@@ -44,6 +46,13 @@
 // --refined-segment-fields and --refined-segment-classes write the files of --segment-fields / --segment-classes -- same writers, same
 // columns -- over the REFINED labels (getLabelFieldStats, getLabelClassHistogram), from the same --fields / --class-field / --classes,
 // which may be given for a refined file alone.  Both need --refine and a PCD input.
+// --refined-components writes one CSV row per connected part of the REFINED labels (getLabelComponents: two (label, node) pairs are joined
+// when either node's adjacency row holds the other): part, label, n_points, n_nodes, first_node, largest (1 for the part with the most
+// points of its label) -- the stranded islands a refinement left per cluster.  It needs --refine.  --class-components writes the same
+// table for the integer class field --class-field names (read from the input PCD as exact integers, like --truth-field; a negative value =
+// no class; classes 0 .. C-1 with C = --classes, a class >= C ends the run with an error): the instances of every class over the scene's
+// own neighbourhood graph.  It needs --class-field, --classes and a PCD input.  --component-ids writes the part of every point (int32,
+// input order, -1 = none) of whichever of the two tables was asked for, raw; with both, or with neither, it is a usage error.
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
 #include <algorithm>
 #include <cmath>
@@ -72,12 +81,14 @@ int main(int argc, char** argv) {
                  "[--segment-matches file.csv --truth-field name [--truth-matches file.csv]] "
                  "[--refine [--patch-radius r] [--switch-ratio s] [--no-fill]] [--refined-segments file.csv] [--refined-segment-boxes file.csv] "
                  "[--refined-segment-fields file.csv --fields a[,b,...]] [--refined-segment-classes file.csv --class-field name --classes C] "
-                 "[--refined-matches file.csv --truth-field name [--refined-truth-matches file.csv]]\n",
+                 "[--refined-matches file.csv --truth-field name [--refined-truth-matches file.csv]] "
+                 "[--refined-components file.csv] [--class-components file.csv --class-field name --classes C] [--component-ids file.i32]\n",
                  argv[0]);
     return 2;
   }
   std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file, boxes_file, fields_file, classes_file, class_field, matches_file, truth_field, truth_file;
   std::string r_segments_file, r_boxes_file, r_matches_file, r_truth_file, r_fields_file, r_classes_file;
+  std::string r_parts_file, c_parts_file, part_ids_file;
   std::vector<std::string> field_names;
   bool have_fields = false, have_classes = false;
   long n_classes = 0;
@@ -129,6 +140,9 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--refined-segment-classes") && a + 1 < argc) r_classes_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-matches") && a + 1 < argc) r_matches_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-truth-matches") && a + 1 < argc) r_truth_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-components") && a + 1 < argc) r_parts_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--class-components") && a + 1 < argc) c_parts_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--component-ids") && a + 1 < argc) part_ids_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refine")) refine.on = true;
     else if (!std::strcmp(argv[a], "--no-fill")) { refine.fill = false; refine_opts = true; }
     else if ((!std::strcmp(argv[a], "--patch-radius") || !std::strcmp(argv[a], "--switch-ratio")) && a + 1 < argc) {
@@ -150,14 +164,22 @@ int main(int argc, char** argv) {
   if (!r_classes_file.empty() && class_field.empty()) { std::fprintf(stderr, "--refined-segment-classes needs --class-field <name>\n"); return 2; }
   if (!r_classes_file.empty() && !have_classes) { std::fprintf(stderr, "--refined-segment-classes needs --classes <C>\n"); return 2; }
   if (!(fields_file.empty() && r_fields_file.empty()) && field_names.size() > 64) { std::fprintf(stderr, "--fields: at most 64 fields\n"); return 2; }
+  if (!c_parts_file.empty() && class_field.empty()) { std::fprintf(stderr, "--class-components needs --class-field <name>\n"); return 2; }
+  if (!c_parts_file.empty() && !have_classes) { std::fprintf(stderr, "--class-components needs --classes <C>\n"); return 2; }
+  if (!r_parts_file.empty() && !refine.on) { std::fprintf(stderr, "--refined-components needs --refine\n"); return 2; }
+  if (!part_ids_file.empty() && r_parts_file.empty() == c_parts_file.empty()) {
+    std::fprintf(stderr, "--component-ids writes the parts of exactly one of --refined-components and --class-components (%s given)\n",
+                 r_parts_file.empty() ? "neither" : "both");
+    return 2;
+  }
   if (!classes_file.empty() && class_field.empty()) { std::fprintf(stderr, "--segment-classes needs --class-field <name>\n"); return 2; }
   if (!classes_file.empty() && !have_classes) { std::fprintf(stderr, "--segment-classes needs --classes <C>\n"); return 2; }
   if (fields_file.empty() && r_fields_file.empty() && have_fields) {
     std::fprintf(stderr, "--fields needs --segment-fields <file.csv> (or --refined-segment-fields)\n");
     return 2;
   }
-  if (classes_file.empty() && r_classes_file.empty() && (have_classes || !class_field.empty())) {
-    std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv> (or --refined-segment-classes)\n");
+  if (classes_file.empty() && r_classes_file.empty() && c_parts_file.empty() && (have_classes || !class_field.empty())) {
+    std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv> (or --refined-segment-classes, --class-components)\n");
     return 2;
   }
   if (!matches_file.empty() && truth_field.empty()) { std::fprintf(stderr, "--segment-matches needs --truth-field <name>\n"); return 2; }
@@ -188,14 +210,14 @@ int main(int argc, char** argv) {
   const bool ply = in_file.size() > 4 && in_file.substr(in_file.size() - 4) == ".ply";
   const bool want_truth = !(matches_file.empty() && r_matches_file.empty());
   const bool any_fields = !(fields_file.empty() && r_fields_file.empty()), any_classes = !(classes_file.empty() && r_classes_file.empty());
-  if (ply && (any_fields || any_classes || want_truth)) {   // (a usage error: nothing has been loaded yet)
+  if (ply && (any_fields || any_classes || want_truth || !c_parts_file.empty())) {   // (a usage error: nothing has been loaded yet)
     std::fprintf(stderr, "--segment-fields / --segment-classes / --refined-segment-fields / --refined-segment-classes / --segment-matches / "
-                 "--refined-matches read their fields from a PCD input, not from %s\n", in_file.c_str());
+                 "--refined-matches / --class-components read their fields from a PCD input, not from %s\n", in_file.c_str());
     return 2;
   }
   if ((ply ? inputPointCloudData2(in_file, cloud) : inputPointCloudData(in_file, cloud)) != 0) return 1;
   DriverFields fields;
-  DriverFields* want_fields = (!any_fields && !any_classes && !want_truth) ? nullptr : &fields;
+  DriverFields* want_fields = (!any_fields && !any_classes && !want_truth && c_parts_file.empty()) ? nullptr : &fields;
   if (want_fields) {   // the attributes ride in the input PCD, one row per point of the cloud
     std::string err;
     if (any_fields) {
@@ -211,6 +233,10 @@ int main(int argc, char** argv) {
       fields.n_classes = (int)n_classes;
       fields.want_hist = !classes_file.empty();
     }
+    if (!c_parts_file.empty()) {
+      if (vgs_io::read_pcd_field_int32(in_file, class_field, fields.part_classes, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
+      fields.parts_K = (int64_t)n_classes;
+    }
     if (want_truth) {
       if (vgs_io::read_pcd_field_int32(in_file, truth_field, fields.truth, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
       fields.have_truth = !matches_file.empty();   // (the voxel labels are scored only when their table is asked for)
@@ -221,6 +247,7 @@ int main(int argc, char** argv) {
   refine.want_boxes = !r_boxes_file.empty();
   refine.want_stats = !r_fields_file.empty();
   refine.want_hist = !r_classes_file.empty();
+  refine.want_components = !r_parts_file.empty();
   refine.fields = &fields;
   refine.box_frame = box_frame;
   std::vector<std::vector<int>> clusters;
@@ -259,6 +286,14 @@ int main(int argc, char** argv) {
   if (!r_classes_file.empty() && writeClassHistCsv(r_classes_file, fields.n_classes, refine.hist) != 0) { std::fprintf(stderr, "cannot write %s\n", r_classes_file.c_str()); return 1; }
   if (!r_matches_file.empty() && writeSegmentMatchesCsv(r_matches_file, refine.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", r_matches_file.c_str()); return 1; }
   if (!r_truth_file.empty() && writeTruthMatchesCsv(r_truth_file, refine.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", r_truth_file.c_str()); return 1; }
+  if (!r_parts_file.empty() && writeComponentsCsv(r_parts_file, refine.components) != 0) { std::fprintf(stderr, "cannot write %s\n", r_parts_file.c_str()); return 1; }
+  if (!c_parts_file.empty() && writeComponentsCsv(c_parts_file, fields.parts) != 0) { std::fprintf(stderr, "cannot write %s\n", c_parts_file.c_str()); return 1; }
+  if (!part_ids_file.empty()) {
+    const std::vector<int32_t>& ids = r_parts_file.empty() ? fields.parts.part_of_point : refine.components.part_of_point;
+    FILE* f = std::fopen(part_ids_file.c_str(), "wb");
+    const bool ok = f && std::fwrite(ids.data(), sizeof(int32_t), ids.size(), f) == ids.size();
+    if (!f || std::fclose(f) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", part_ids_file.c_str()); return 1; }
+  }
   if (!adjacency_file.empty() && writeAdjacency(adjacency_file, graph.adjacency) != 0) {
     std::fprintf(stderr, "cannot write %s\n", adjacency_file.c_str());
     return 1;

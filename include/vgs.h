@@ -731,6 +731,46 @@ vgs_status vgs_get_own_band_labels(vgs_ctx* ctx, int64_t* n, uint64_t* code, int
 vgs_status vgs_set_refine_halo_labels(vgs_ctx* ctx, const uint64_t* code, const int32_t* label, int64_t n);
 vgs_status vgs_refine_own_point_labels(vgs_ctx* ctx, const vgs_refine_params* rp, int64_t* counts /* 5 */);
 
+/* Connected parts of ANY per-point labelling of the cloud (no reference counterpart).  The tables above treat a label as a set of points;
+ * this one says whether that set is one object or several, over the scene's own neighbourhood graph: the stranded islands a refinement
+ * left per segment, the instances of a semantic class, whether a labelling is spatially coherent at graph_size.
+ *
+ * Input.  labels[i] for every input point i < N; negative = no label; 0 <= labels[i] < K, K the caller's choice: the contract of
+ * vgs_point_label_descriptors, the first offending index of a label >= K reported as there (VGS_E_ARG).
+ * Nodes.  Voxels for VGS, supervoxels for SVGS: what vgs_get_point_voxel returns.  A point with no node (a non-finite point, a point
+ * outside the octree) is outside the whole pass: it gets part id -1 and counts in n_skipped if its label is >= 0.
+ * Vertices.  The distinct pairs (label l, node v) with at least one point of v carrying l.
+ * Edges.  (l, v) and (l, w) are joined when w is in the adjacency row of v OR v is in the row of w, the rows those of
+ * vgs_get_lists(which = 0): every node, used or not, every neighbour.  (The hot path stores rows for used nodes only, and these may be
+ * pruned to used neighbours; the rows of the other nodes that hold a labelled point are built on request.  An edge is honoured when
+ * either endpoint's row has it.)
+ * Part.  A connected component of that graph; all points of (l, v) belong to the part of (l, v).
+ * Numbering.  Parts are numbered 0 .. C-1 in ascending (label, smallest node id of the part): the project's own cluster order inside
+ * each label.  The parts of label k are the contiguous range label_first[k] .. label_first[k + 1] - 1.
+ * Outputs:
+ *   part_of_point    int32  [N]      part id of every point, input order; -1 as above and for an unlabelled point
+ *   part_label       int32  [C]      label of the part
+ *   part_points      int64  [C]      points in the part
+ *   part_nodes       int32  [C]      nodes in the part
+ *   part_first_node  int32  [C]      smallest node id of the part
+ *   label_first      int64  [K + 1]  first part of each label (label_first[K] = C)
+ *   label_largest    int32  [K]      part with the most points of each label, the lowest id on a tie; -1 for a label no point carries
+ * Everything is integer: the tables are bit-identical from call to call and from engine to engine.  No point, no finite point, no node,
+ * K = 0 or all labels negative: C = 0 and every part id -1.
+ * vgs_point_label_components[_device] computes the result on the device into buffers of the context (the _device variant reads the
+ * labels in place); n_parts = C and n_skipped may be NULL.  vgs_get_point_label_components copies the tables out, any pointer may be
+ * NULL; vgs_get_point_label_components_device hands out the device pointers (NULL for a table without rows).  Both are valid until the
+ * next vgs_point_label_components or the next run of the stages, and answer VGS_E_STATE without a result since the last run.
+ * VGS_E_STATE before the context is segmented, and for a tile context: it holds part of the cloud and of the graph only, and parts
+ * across the ranks of the tiled driver are not computed.  VGS_E_ARG for n != N, a NULL labelling, K outside 0 .. 2^31 - 1. */
+vgs_status vgs_point_label_components(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_skipped);
+vgs_status vgs_point_label_components_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_skipped);
+vgs_status vgs_get_point_label_components(vgs_ctx* ctx, int32_t* part_of_point, int32_t* part_label, int64_t* part_points, int32_t* part_nodes,
+                                          int32_t* part_first_node, int64_t* label_first, int32_t* label_largest);
+vgs_status vgs_get_point_label_components_device(vgs_ctx* ctx, const int32_t** part_of_point, const int32_t** part_label,
+                                                 const int64_t** part_points, const int32_t** part_nodes, const int32_t** part_first_node,
+                                                 const int64_t** label_first, const int32_t** label_largest);
+
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.
  * One context per GPU holds one tile plus a halo of raw points (2*graph_size + voxel_size wide).

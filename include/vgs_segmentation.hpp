@@ -298,6 +298,32 @@ inline ClusterLabelComparison cluster_label_comparison(vgs_ctx* c, int64_t k, co
 }
 }  // namespace vgs_detail
 
+// Extension (no VS / SS line): the connected parts of a per-point labelling over the node adjacency, as vgs_point_label_components
+// (include/vgs.h) defines them: the part of every point (-1: no label or no node), one row per part in ascending (label, smallest node id
+// of the part), and per label its first part (K + 1 entries) and its largest (-1 for a label no point carries)
+struct LabelComponents {
+  std::vector<int32_t> part_of_point, part_label;
+  std::vector<int64_t> part_points;
+  std::vector<int32_t> part_nodes, part_first_node;
+  std::vector<int64_t> label_first;
+  std::vector<int32_t> label_largest;
+  int64_t n_skipped = 0;   // labelled points outside the octree
+};
+
+namespace vgs_detail {
+inline LabelComponents label_components(vgs_ctx* c, int64_t k, const int32_t* labels, int64_t n) {
+  LabelComponents o;
+  int64_t n_parts = 0;
+  check(c, vgs_point_label_components(c, labels, n, k, &n_parts, &o.n_skipped), "vgs_point_label_components");
+  const size_t C = (size_t)n_parts, K = (size_t)k;
+  o.part_of_point.resize((size_t)n); o.part_label.resize(C); o.part_points.resize(C); o.part_nodes.resize(C); o.part_first_node.resize(C);
+  o.label_first.resize(K + 1); o.label_largest.resize(K);
+  check(c, vgs_get_point_label_components(c, o.part_of_point.data(), o.part_label.data(), o.part_points.data(), o.part_nodes.data(),
+                                          o.part_first_node.data(), o.label_first.data(), o.label_largest.data()), "vgs_get_point_label_components");
+  return o;
+}
+}  // namespace vgs_detail
+
 // Extension (no VS / SS line): one edge of the adjacency graph of the kept clusters, as vgs_get_segment_graph (include/vgs.h) defines it
 struct ClusterEdge {
   int32_t a = 0, b = 0;        // cluster indices (getClusterIdx order), a < b
@@ -512,6 +538,19 @@ class VoxelBasedSegmentation {
     return vgs_detail::cluster_class_histogram(ctx(), K < 0 ? count(VGS_N_KEPT) : K, classes, n, n_classes, labels, n_skipped);
   }
 
+  // Extension (no VS line): the connected parts of a per-point labelling (n int32 in input order, negative = no label) over the voxel
+  // adjacency (vgs_point_label_components, include/vgs.h); K < 0: the clusters' label range.  No part, every point -1, before
+  // drawColorMapofPointsinClusters
+  LabelComponents getLabelComponents(const int32_t* labels, int64_t n, int64_t K = -1) {
+    if (!drawn_) {
+      LabelComponents o;
+      o.part_of_point.assign((size_t)count(VGS_N_POINTS), -1);
+      o.label_first.assign(1, 0);
+      return o;
+    }
+    return vgs_detail::label_components(ctx(), K < 0 ? count(VGS_N_KEPT) : K, labels, n);
+  }
+
   // Extension (no VS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
   // names getClusterIdx()[i].  patch_radius < 0: the default (the voxel size); every point -1 before drawColorMapofPointsinClusters
   std::vector<int32_t> refineClusterLabels(float patch_radius = -1.0f, float switch_ratio = 0.25f, bool fill = true) {
@@ -653,6 +692,11 @@ class SuperVoxelBasedSegmentation {
                                                             int64_t K = -1, int64_t* n_skipped = nullptr) {
     if (n_skipped) *n_skipped = 0;
     return vgs_detail::cluster_class_histogram(ctx(), K < 0 ? count(VGS_N_KEPT) : K, classes, n, n_classes, labels, n_skipped);
+  }
+  // Extension (no SS line): the connected parts of a per-point labelling (n int32 in input order, negative = no label) over the supervoxel
+  // adjacency (vgs_point_label_components, include/vgs.h); K < 0: the clusters' label range
+  LabelComponents getLabelComponents(const int32_t* labels, int64_t n, int64_t K = -1) {
+    return vgs_detail::label_components(ctx(), K < 0 ? count(VGS_N_KEPT) : K, labels, n);
   }
   // Extension (no SS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
   // names getClusterIdx()[i].  patch_radius < 0: the default (the supervoxel size)

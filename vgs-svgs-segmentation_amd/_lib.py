@@ -155,6 +155,10 @@ SYMBOLS = [
     ("vgs_get_own_band_labels", C.c_int, [_P, C.POINTER(C.c_int64), _P, _P]),
     ("vgs_set_refine_halo_labels", C.c_int, [_P, _P, _P, C.c_int64]),
     ("vgs_refine_own_point_labels", C.c_int, [_P, C.POINTER(VgsRefineParams), _P]),
+    ("vgs_point_label_components", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("vgs_point_label_components_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("vgs_get_point_label_components", C.c_int, [_P] + [_P] * 7),
+    ("vgs_get_point_label_components_device", C.c_int, [_P] + [_P] * 7),
     ("vgs_grid_state_init", C.c_int, [C.POINTER(VgsGridState)]),
     ("vgs_grid_advance", C.c_int, [_P, C.POINTER(VgsGridState)]),
     ("vgs_points_bbox", C.c_int, [_P, _P, C.POINTER(C.c_int64)]),

@@ -546,6 +546,45 @@ class Engine:
         out["n_skipped"] = int(skipped.value)
         return out
 
+    # (field, dtype, table) of vgs_get_point_label_components, in its argument order; the tables have N, C, K + 1 and K rows
+    COMPONENT_FIELDS = (("part_of_point", np.int32, "points"), ("part_label", np.int32, "parts"), ("part_points", np.int64, "parts"),
+                        ("part_nodes", np.int32, "parts"), ("part_first_node", np.int32, "parts"), ("label_first", np.int64, "first"),
+                        ("label_largest", np.int32, "labels"))
+
+    def label_components(self, labels, K=None):
+        """Connected parts of ANY per-point labelling of the cloud (include/vgs.h, vgs_point_label_components): a dict of numpy arrays --
+        part_of_point (N, int32; -1 for a point without label or without node), part_label, part_points (int64), part_nodes,
+        part_first_node (C rows, parts in ascending (label, smallest node id)), label_first (K + 1, int64: the parts of label k are
+        label_first[k] .. label_first[k + 1] - 1), label_largest (K; -1 for a label no point carries) -- plus n_parts = C and n_skipped,
+        the labelled points outside the octree.  Two vertices (label, node) are joined when either node's row of lists(0) holds the other.
+        `labels`: int32 of shape (N,) in input order, a numpy array or a torch tensor on the context's device, which is read in place;
+        negative = no label, a label >= K is an error.  K None: max(label) + 1 (0 for an empty or all-negative labelling) -- the range
+        of a class field or of instance ids is the caller's, not the engine's kept count.  Computed on the device; integers only,
+        bit-identical from call to call.  part_of_point is itself a labelling with K = n_parts: every label_* table applies to it."""
+        if K is None:
+            if self._is_torch(labels):
+                K = max(int(labels.max().item()) + 1, 0) if labels.numel() > 0 else 0
+            else:
+                a = np.asarray(labels)
+                K = max(int(a.max()) + 1, 0) if a.size > 0 else 0
+        labels, ptr, n, dev, K = self._labels_input(labels, K)
+        fn = self._L.vgs_point_label_components_device if dev else self._L.vgs_point_label_components
+        n_parts, skipped = C.c_int64(0), C.c_int64(0)
+        self._ck(fn(self._h, ptr, n, K, C.byref(n_parts), C.byref(skipped)))
+        rows = {"points": self.n, "parts": n_parts.value, "first": max(K, 0) + 1, "labels": max(K, 0)}
+        out = {name: np.zeros(rows[tab], dtype=dt) for name, dt, tab in self.COMPONENT_FIELDS}
+        self._ck(self._L.vgs_get_point_label_components(self._h, *(_ptr(out[name]) for name, _, _ in self.COMPONENT_FIELDS)))
+        out["n_parts"] = int(n_parts.value)
+        out["n_skipped"] = int(skipped.value)
+        return out
+
+    def label_components_device(self):
+        """The tables of the last label_components left in HBM: {field: device pointer, None for a table without rows}, valid until the
+        next label_components or the next run."""
+        ps = [C.c_void_p() for _ in self.COMPONENT_FIELDS]
+        self._ck(self._L.vgs_get_point_label_components_device(self._h, *(C.byref(p) for p in ps)))
+        return {name: p.value for (name, _, _), p in zip(self.COMPONENT_FIELDS, ps)}
+
     def compare_labels(self, ref, labels=None, K=None):
         """Score the segmentation against a labelling of the same points (include/vgs.h, vgs_compare_labels): the sparse contingency table
         between point_labels() and `ref`, the reference table and the segment table, as a dict of numpy arrays -- cell_seg, cell_ref, cell_n
@@ -772,6 +811,17 @@ class VoxelBasedSegmentation:
             return {name: np.zeros((0, w), dtype=dt) for name, dt, w in Engine.BOX_FIELDS}
         return self._eng.label_boxes(labels, frame)
 
+    def getLabelComponents(self, labels):
+        """Extension (no VS line): the connected parts of a per-point labelling with the clusters' label range (refineClusterLabels()'
+        result, say) over the voxel adjacency: the dict of Engine.label_components with K = getClusterNum().  No part and every point -1
+        before drawColorMapofPointsinClusters."""
+        if not self._drawn:
+            rows = {"points": self._eng.n, "parts": 0, "first": 1, "labels": 0}
+            out = {name: np.zeros(rows[tab], dtype=dt) for name, dt, tab in Engine.COMPONENT_FIELDS}
+            out["part_of_point"][:] = -1
+            return dict(out, n_parts=0, n_skipped=0)
+        return self._eng.label_components(labels, self._eng.counts()["kept"])
+
     def refineClusterLabels(self, patch_radius=None, switch_ratio=0.25, fill=True):
         """Extension (no VS line): one label per input point, refined at the cluster boundaries; label i names getClusterIdx()[i]
         (Engine.refine_labels / refined_labels).  Every point -1 before drawColorMapofPointsinClusters."""
@@ -886,6 +936,11 @@ class SuperVoxelBasedSegmentation:
     def getLabelBoxes(self, labels, frame="principal"):
         """Extension (no SS line): the oriented boxes of a per-point labelling with the clusters' label range (Engine.label_boxes)."""
         return self._eng.label_boxes(labels, frame)
+
+    def getLabelComponents(self, labels):
+        """Extension (no SS line): the connected parts of a per-point labelling with the clusters' label range over the supervoxel
+        adjacency: the dict of Engine.label_components with K = getClusterNum()."""
+        return self._eng.label_components(labels, self._eng.counts()["kept"])
 
     def refineClusterLabels(self, patch_radius=None, switch_ratio=0.25, fill=True):
         """Extension (no SS line): one label per input point, refined at the cluster boundaries; label i names getClusterIdx()[i]

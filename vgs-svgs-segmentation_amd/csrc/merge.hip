@@ -21,6 +21,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "vgs_context.hpp"
+#include "unionfind.hpp"
 
 struct MgParams {
   VgsWeightParams W;
@@ -293,25 +294,7 @@ __global__ __launch_bounds__(64) void k_cc_pass(const uint32_t* __restrict__ can
 }
 
 // ------------------------------------------------------------------ connected components
-__device__ __forceinline__ uint32_t uf_find(uint32_t* parent, uint32_t x) {
-  // path halving: parents only ever move towards the root (smaller ids), so a stale write is still an ancestor
-  while (true) {
-    const uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p == x) return x;
-    const uint32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (g != p) __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = g;
-  }
-}
-__device__ __forceinline__ void uf_union(uint32_t* parent, uint32_t a, uint32_t b) {
-  while (true) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return;
-    const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-    if (atomicCAS(&parent[hi], hi, lo) == hi) return;
-  }
-}
+// (uf_find, uf_union, uf_root: unionfind.hpp, shared with labelcc.hip)
 
 // one pass instead of five fills: parent = identity, the per-voxel tables of the stage at their start values
 __global__ void k_merge_init(uint32_t* __restrict__ parent, uint32_t* __restrict__ csize, int32_t* __restrict__ attach,
@@ -401,17 +384,7 @@ __global__ void k_compress(uint32_t* __restrict__ parent, int64_t V) {
   if (r != (uint32_t)v) __hip_atomic_store(&parent[v], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The unions are complete: every voxel gets its ROOT as parent.  The walk must not write on the way (no path halving
-// here): a halving store of another thread that lands after this voxel's final store would leave it pointing at an
-// ancestor below the root, and the labels read parent[v] as the root (seen once in ~20 runs of a 90 k-point scene as a
-// voxel dropped from its segment).  With read-only walks the only writes are the final ones, each a root.
-__device__ __forceinline__ uint32_t uf_root(const uint32_t* parent, uint32_t x) {
-  while (true) {
-    const uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p == x) return x;
-    x = p;
-  }
-}
+// The unions are complete: every voxel gets its ROOT as parent, by the read-only walk of uf_root (unionfind.hpp says why it must not write).
 __device__ __forceinline__ void k_flatten_body(uint32_t* __restrict__ parent, int64_t V, const uint8_t* __restrict__ owned, uint32_t* __restrict__ csz,
                                                uint32_t* s_root, unsigned int* s_cnt);
 __global__ void k_flatten(uint32_t* __restrict__ parent, int64_t V, const uint8_t* __restrict__ owned, uint32_t* __restrict__ csz) {
@@ -559,7 +532,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
   c->cl_valid = false;   // (clusters.hip: the cluster lists on the device belong to the labels of the last run)
   c->sd_valid = false;   // (segdesc.hip: so do the segment descriptors)
   c->sb_valid[0] = c->sb_valid[1] = false;   // (segbox.hip: and the oriented boxes)
-  c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->cmp_own_cells = -1; c->pso_K = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1;   // (seggraph.hip: and the segment graph)
+  c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->cmp_own_cells = -1; c->pso_K = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1;   // (seggraph.hip: and the segment graph)
   const int64_t V = c->V, U = c->U, N = c->N;
   c->bnd_unique = -1;  // tile protocol results belong to the previous segmentation
   c->counts[VGS_N_CLUSTERS] = 0; c->counts[VGS_N_KEPT] = 0; c->counts[VGS_N_ISOLATED] = 0; c->counts[VGS_N_REATTACHED] = 0;

@@ -398,6 +398,19 @@ struct vgs_ctx {
   std::vector<double> pso_s9;
   std::vector<uint64_t> pso_pcode;
   int64_t pso_K = -1;
+  // connected parts of a caller's per-point labelling (labelcc.hip): the result of the last vgs_point_label_components, valid until the
+  // next one or the next run of the stages (lcc_valid) -- part of every point (N), label, points, nodes and first node of every part
+  // (lcc_C rows), first part (lcc_K + 1) and largest part (lcc_K) of every label.  Scratch of its own: head flags and their scan (Nf + 1
+  // words each), the vertex arrays node | label | first point | parent | root | part (vertices + 1 words each) and the scan over them,
+  // the lowest | highest vertex of every node (V words each), the first vertex (K + 1) and the fold word (K) of every label, the list
+  // (vertex | node) of the vertices of unused voxels.  The sort is
+  // pointseg.hip's (ps_*), the rows built for unused voxels sit in refine.hip's chunk (rf_rows, rf_cnt, rf_nall).  (lc_* is the local cut's.)
+  DevBuf<int32_t> lcc_pop, lcc_plabel, lcc_pnodes, lcc_pfirst, lcc_llargest;
+  DevBuf<int64_t> lcc_ppoints, lcc_lfirst;
+  DevBuf<uint32_t> lcc_flag, lcc_vex, lcc_vtx, lcc_vscan, lcc_vfirst, lcc_uv, lcc_nidx;
+  DevBuf<uint64_t> lcc_lmax;
+  int64_t lcc_C = 0, lcc_K = 0;
+  bool lcc_valid = false;
   DevBuf<uint64_t> counters;  // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 
