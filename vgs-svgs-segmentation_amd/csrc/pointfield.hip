@@ -32,12 +32,17 @@
 // the own range's start, and k_sf_own_records (segfield.hip, through sf_launch_own_records) in place of k_sf_final: the sums leave as they
 // are (vgs_own_point_label_field_moments, vgs_own_point_label_class_counts), the driver folds all ranks' records on the host and
 // vgs_segment_field_stats_from_moments finishes the table.
+// Host side: the drivers, uploads, copy-out and argument rules are attrpass.hpp's, one copy shared with segfield.hip.  This file gives them
+// the source of a point labelling (pf_source: ps_sort_points over the cloud or over the own range), its launch lines and record rule (the
+// attr_* specialisations for PsSort) and the order of the checks (pf_check, then the table's own rules); the eight entry points of a
+// table go through one function with an on_device flag (pf_field_entry, pf_hist_entry), a record set selecting the tile context's calls.
+// After a failure too an entry waits for the stream (attr_settle): arrays read in place are the caller's again.
 #include <string.h>
 
 #include <algorithm>
 #include <string>
 
-#include "segpass.hpp"
+#include "attrpass.hpp"
 
 // Step 2.  One thread per (label, channel).  row0: the input index of the field's first row (0; a tile context: own_first -- the sorted
 // points are own points there, so the row index is never negative).
@@ -115,393 +120,184 @@ __global__ __launch_bounds__(SD_TB) void k_pf_own_hist(const int32_t* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------------- host
-// the checks both tables share: the state, the labelling (the rules of vgs_point_label_descriptors) and the attribute array
-static vgs_status pf_check(vgs_ctx* c, const char* fn, const int32_t* labels, int64_t K, const void* in, int64_t n) {
-  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
-  if (vgs_is_tile(c)) {
-    c->err = std::string(fn) + ": a tile context (owned region / own point range) holds only part of the cloud, and the attribute tables of a point labelling over all ranks are vgs_tiles_point_label_field_stats and vgs_tiles_point_label_class_histogram of the tiled driver";
-    return VGS_E_STATE;
-  }
-  if (n != c->N) {
-    c->err = std::string(fn) + ": n = " + std::to_string(n) + " must equal the number of points of the cloud, " + std::to_string(c->N);
-    return VGS_E_ARG;
-  }
-  if (!labels && n > 0) { c->err = std::string(fn) + ": labels is NULL"; return VGS_E_ARG; }
-  if (!in && n > 0) { c->err = std::string(fn) + ": the input array is NULL"; return VGS_E_ARG; }
-  if (K < 0 || K > (int64_t)0x7fffffff) { c->err = std::string(fn) + ": K = " + std::to_string(K) + " is out of range"; return VGS_E_ARG; }
+// The source of a caller's per-point labelling (attrpass.hpp): ps_sort_points over labels_dev -- one context: the whole cloud; a tile
+// context (own): its own point range alone, one label per own point.  K = 0 (nothing sorted): validated, the skipped points counted,
+// nothing to write.  No point in the octree: one context still writes the empty rows, a tile context has no record.
+static vgs_status pf_source(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t K, bool own, int64_t* n_skipped, AttrSource<PsSort>& S) {
+  S.K = K;
+  S.own = own;
+  S.own_first = own ? c->own_first : 0;
+  S.own_end = S.own_first + (own ? c->n_own : c->N);
+  vgs_status s = ps_sort_points(c, fn, labels_dev, S.own_first, S.own_end - S.own_first, K, 0, n_skipped, S.d);
+  if (s != VGS_OK || !S.d.sorted) return s;
+  S.seg_chunk = S.d.seg_chunk;
+  S.n_chunks_max = S.d.n_chunks_max;
+  S.chunks = c->Nf > 0;
+  S.live = S.chunks || !own;
   return VGS_OK;
 }
 
-static vgs_status pf_check_field(vgs_ctx* c, const char* fn, const int32_t* labels, int64_t K, const float* field, int64_t n, int32_t n_channels,
-                                 int64_t stride_bytes) {
-  vgs_status s = pf_check(c, fn, labels, K, field, n);
-  if (s != VGS_OK) return s;
-  if (n_channels < 1 || n_channels > 64) {
-    c->err = std::string(fn) + ": n_channels = " + std::to_string(n_channels) + " must be in 1 .. 64";
-    return VGS_E_ARG;
-  }
-  if (stride_bytes < 4 * (int64_t)n_channels || stride_bytes % 4 != 0) {
-    c->err = std::string(fn) + ": stride_bytes = " + std::to_string(stride_bytes) + " must be a multiple of 4 and at least 4 * n_channels = " +
-             std::to_string(4 * (int64_t)n_channels);
-    return VGS_E_ARG;
-  }
-  if (K * (int64_t)n_channels > ((int64_t)1 << 27)) {
-    c->err = std::string(fn) + ": " + std::to_string(K) + " labels x " + std::to_string(n_channels) + " channels = " +
-             std::to_string(K * (int64_t)n_channels) + " entries exceed the table's limit of 2^27 = " + std::to_string((int64_t)1 << 27);
-    return VGS_E_UNSUPPORTED;
-  }
+// row0 of k_pf_anchor is the source's own_first: 0 for one context
+template <> vgs_status attr_launch_anchor<PsSort>(vgs_ctx* c, const AttrSource<PsSort>& S, const float* field, int64_t stride_f, uint32_t C) {
+  hipLaunchKernelGGL(k_pf_anchor, dim3((unsigned)(((size_t)S.K * C + 255) / 256)), dim3(256), 0, c->stream, field, stride_f, C, c->perm_b.p, S.d.pos,
+                     S.d.seg_start, (uint32_t)S.K, S.own_first, c->sf_anchor.p);
   return VGS_OK;
 }
 
-static vgs_status pf_check_hist(vgs_ctx* c, const char* fn, const int32_t* labels, int64_t K, const int32_t* cls, int64_t n, int32_t n_classes) {
-  vgs_status s = pf_check(c, fn, labels, K, cls, n);
-  if (s != VGS_OK) return s;
-  if (n_classes < 1 || n_classes > 1024) {
-    c->err = std::string(fn) + ": n_classes = " + std::to_string(n_classes) + " must be in 1 .. 1024";
-    return VGS_E_ARG;
-  }
-  if (K * (int64_t)n_classes > ((int64_t)1 << 27)) {
-    c->err = std::string(fn) + ": " + std::to_string(K) + " labels x " + std::to_string(n_classes) + " classes = " +
-             std::to_string(K * (int64_t)n_classes) + " counters exceed the table's limit of 2^27 = " + std::to_string((int64_t)1 << 27);
-    return VGS_E_UNSUPPORTED;
-  }
+template <> void attr_launch_chunks<PsSort>(vgs_ctx* c, const AttrSource<PsSort>& S, const float* field, int64_t stride_f, uint32_t C, uint32_t c0, uint32_t ng) {
+  const dim3 grid((unsigned)S.n_chunks_max);
+  if (S.own)
+    hipLaunchKernelGGL(k_pf_own_chunks, grid, dim3(SD_TB), 0, c->stream, field, stride_f, C, c0, ng, c->perm_b.p, S.d.pos, S.d.seg_start, S.d.seg_chunk,
+                       (uint32_t)S.K, c->sf_anchor.p, c->sf_part.p, S.own_first, S.own_end);
+  else
+    hipLaunchKernelGGL(k_pf_chunks, grid, dim3(SD_TB), 0, c->stream, field, stride_f, C, c0, ng, c->perm_b.p, S.d.pos, S.d.seg_start, S.d.seg_chunk,
+                       (uint32_t)S.K, c->sf_anchor.p, c->sf_part.p);
+}
+
+template <> vgs_status attr_launch_hist<PsSort>(vgs_ctx* c, const AttrSource<PsSort>& S, const int32_t* cls, uint32_t n_classes, unsigned long long* hist,
+                                   unsigned long long* n_outside) {
+  const dim3 grid((unsigned)S.n_chunks_max);
+  if (S.own)
+    hipLaunchKernelGGL(k_pf_own_hist, grid, dim3(SD_TB), 0, c->stream, cls, n_classes, c->perm_b.p, S.d.pos, S.d.seg_start, S.d.seg_chunk, (uint32_t)S.K, hist,
+                       n_outside, S.own_first, S.own_end);
+  else
+    hipLaunchKernelGGL(k_pf_hist, grid, dim3(SD_TB), 0, c->stream, cls, n_classes, c->perm_b.p, S.d.pos, S.d.seg_start, S.d.seg_chunk, (uint32_t)S.K, hist,
+                       n_outside);
   return VGS_OK;
 }
 
-#define PF_COPY(dst, src, count) \
-  if (dst) VGS_HIP_TRY(c, hipMemcpyAsync((dst), (src), (count) * sizeof(*(dst)), hipMemcpyDeviceToHost, c->stream))
+// the labels with an own point in the octree leave a record: a run of seg_start (K + 1 words) that is not empty
+template <> size_t attr_rule_words<PsSort>(vgs_ctx*, const AttrSource<PsSort>& S, const uint32_t** dev) { *dev = S.d.seg_start; return (size_t)S.K + 1; }
+template <> bool attr_has_record<PsSort>(const AttrSource<PsSort>&, const uint32_t* seg_start, size_t k) { return seg_start[k + 1] > seg_start[k]; }
 
-// the field table of labels_dev over field_dev, both in HBM: every output a host array of K x n_channels, any may be NULL
-static vgs_status pf_field_stats(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t K, const float* field_dev, int32_t n_channels,
-                                 int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin,
-                                 float* vmax) {
-  PsSort S;
-  vgs_status s = ps_sort_points(c, fn, labels_dev, 0, c->N, K, 0, n_skipped, S);
+// The rules both tables share, in this family's order: the state, the labelling (the rules of vgs_point_label_descriptors; own: of
+// vgs_own_point_label_moments) and the attribute array.  own: the calls of a tile context, n the rank's own points.
+static vgs_status pf_check(vgs_ctx* c, const char* fn, bool own, const int32_t* labels, int64_t K, const void* in, int64_t n) {
+  vgs_status s = attr_check_segmented(c, fn);
   if (s != VGS_OK) return s;
-  if (!S.sorted) return VGS_OK;   // K = 0: validated, the skipped points counted, nothing to write
-  const uint32_t C = (uint32_t)n_channels;
-  const size_t kc = (size_t)K * C;
-  const int64_t stride_f = stride_bytes / 4;
-  VGS_HIP_TRY(c, c->sf_part.ensure((size_t)S.n_chunks_max * SF_G * SF_REC));
-  VGS_HIP_TRY(c, c->sf_anchor.ensure(kc)); VGS_HIP_TRY(c, c->sf_mean.ensure(kc)); VGS_HIP_TRY(c, c->sf_var.ensure(kc));
-  VGS_HIP_TRY(c, c->sf_nvalid.ensure(kc)); VGS_HIP_TRY(c, c->sf_min.ensure(kc)); VGS_HIP_TRY(c, c->sf_max.ensure(kc));
-  hipLaunchKernelGGL(k_pf_anchor, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, c->stream, field_dev, stride_f, C, c->perm_b.p, S.pos, S.seg_start,
-                     (uint32_t)K, (int64_t)0, c->sf_anchor.p);
-  for (uint32_t c0 = 0; c0 < C; c0 += SF_G) {
-    const uint32_t ng = C - c0 < SF_G ? C - c0 : SF_G;
-    if (c->Nf > 0)
-      hipLaunchKernelGGL(k_pf_chunks, dim3((unsigned)S.n_chunks_max), dim3(SD_TB), 0, c->stream, field_dev, stride_f, C, c0, ng, c->perm_b.p, S.pos,
-                         S.seg_start, S.seg_chunk, (uint32_t)K, c->sf_anchor.p, c->sf_part.p);
-    sf_launch_final(c, S.seg_chunk, c->sf_part.p, (uint32_t)S.n_chunks_max, K, C, c0, ng, c->sf_anchor.p, c->sf_nvalid.p, c->sf_mean.p, c->sf_var.p,
-                    c->sf_min.p, c->sf_max.p);
+  if (own) {
+    if ((s = attr_check_tile_only(c, fn)) != VGS_OK || (s = attr_check_K(c, fn, K, (int64_t)0x7fffffff)) != VGS_OK) return s;
+    s = attr_check_n(c, fn, "n_own", n, "own points of the context", c->n_own);
+  } else {
+    if (vgs_is_tile(c))
+      return attr_fail(c, fn, VGS_E_STATE, "a tile context (owned region / own point range) holds only part of the cloud, and the attribute tables of a point labelling over all ranks are vgs_tiles_point_label_field_stats and vgs_tiles_point_label_class_histogram of the tiled driver");
+    s = attr_check_n(c, fn, "n", n, "points of the cloud", c->N);
   }
-  VGS_HIP_TRY(c, hipGetLastError());
-  PF_COPY(n_valid, c->sf_nvalid.p, kc); PF_COPY(anchor, c->sf_anchor.p, kc); PF_COPY(mean, c->sf_mean.p, kc); PF_COPY(var, c->sf_var.p, kc);
-  PF_COPY(vmin, c->sf_min.p, kc); PF_COPY(vmax, c->sf_max.p, kc);
+  if (s != VGS_OK || (s = attr_check_array(c, fn, "labels", labels, n)) != VGS_OK || (s = attr_check_array(c, fn, "the input array", in, n)) != VGS_OK) return s;
+  if (!own) return attr_check_K(c, fn, K, (int64_t)0x7fffffff);
+  if (c->own_first < 0 || c->own_first + n > c->N)
+    return attr_fail(c, fn, VGS_E_ARG, "the own point range ends at " + std::to_string(c->own_first + n) + ", the cloud holds " + std::to_string(c->N) + " points");
   return VGS_OK;
+}
+
+// The eight entry points of a table come through one function.  R = NULL: one context, dense rows.  R given: a tile context, compact
+// records.  labels and the attribute array are both in HBM (on_device) or both the host's, uploaded here.
+static vgs_status pf_field_run(vgs_ctx* c, const char* fn, bool on_device, const int32_t* labels, int64_t K, const float* field, int64_t n,
+                               int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, const AttrRecords* R, const AttrFieldOut& O) {
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  vgs_status s = VGS_OK;
+  if (!on_device && ((s = vgs_upload_point_labels(c, labels, n, &labels)) != VGS_OK || (s = attr_upload_field(c, &field, n, n_channels, stride_bytes)) != VGS_OK))
+    return s;
+  AttrSource<PsSort> S;
+  if ((s = pf_source(c, fn, labels, K, R != nullptr, n_skipped, S)) != VGS_OK) return s;
+  return attr_field_table(c, S, field, n_channels, stride_bytes, R, O);
 }
 
 static vgs_status pf_field_entry(vgs_ctx* c, const char* fn, bool on_device, const int32_t* labels, int64_t K, const float* field, int64_t n,
-                                 int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor, double* mean,
-                                 double* var, float* vmin, float* vmax) {
+                                 int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, const AttrRecords* R, const AttrFieldOut& O) {
   if (!c) return VGS_E_ARG;
+  if (R && R->n_records) *R->n_records = 0;
   if (n_skipped) *n_skipped = 0;
-  vgs_status s = pf_check_field(c, fn, labels, K, field, n, n_channels, stride_bytes);
-  if (s != VGS_OK) return s;
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  if (!on_device) {
-    if ((s = vgs_upload_point_labels(c, labels, n, &labels)) != VGS_OK) return s;
-    if (n > 0) {
-      // one upload, rows at the caller's stride; the last row ends with its last channel
-      const size_t bytes = (size_t)(n - 1) * (size_t)stride_bytes + 4 * (size_t)n_channels;
-      VGS_HIP_TRY(c, c->sf_in.ensure((bytes + 3) / 4));
-      VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_in.p, field, bytes, hipMemcpyHostToDevice, c->stream));
-      VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
-      field = c->sf_in.p;
-    }
-  }
-  s = pf_field_stats(c, fn, labels, K, field, n_channels, stride_bytes, n_skipped, n_valid, anchor, mean, var, vmin, vmax);
-  // the rows have arrived, and arrays read in place are the caller's again -- after a failure as well
-  const hipError_t e = hipStreamSynchronize(c->stream);
-  if (s == VGS_OK) VGS_HIP_TRY(c, e);
-  return s;
+  vgs_status s = pf_check(c, fn, R != nullptr, labels, K, field, n);
+  if (s != VGS_OK || (s = attr_check_channels(c, fn, n_channels)) != VGS_OK || (s = attr_check_stride(c, fn, n_channels, stride_bytes)) != VGS_OK ||
+      (s = attr_check_limit(c, fn, K, "labels", n_channels, "channels", "entries")) != VGS_OK)
+    return s;
+  return attr_settle(c, pf_field_run(c, fn, on_device, labels, K, field, n, n_channels, stride_bytes, n_skipped, R, O));
 }
 
-// the histogram of labels_dev over cls_dev, both in HBM: hist K x n_classes, the others K; host arrays, any may be NULL
-static vgs_status pf_class_hist(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t K, const int32_t* cls_dev, int32_t n_classes,
-                                int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
-  PsSort S;
-  vgs_status s = ps_sort_points(c, fn, labels_dev, 0, c->N, K, 0, n_skipped, S);
-  if (s != VGS_OK) return s;
-  if (!S.sorted) return VGS_OK;
-  const size_t k = (size_t)K, kc = k * (size_t)n_classes;
-  VGS_HIP_TRY(c, c->sf_hist.ensure(kc + 2 * k)); VGS_HIP_TRY(c, c->sf_maj.ensure(k));
-  int64_t *d_hist = c->sf_hist.p, *d_out = d_hist + kc, *d_majc = d_out + k;
-  VGS_HIP_TRY(c, hipMemsetAsync(d_hist, 0, (kc + k) * sizeof(int64_t), c->stream));
-  if (c->Nf > 0)
-    hipLaunchKernelGGL(k_pf_hist, dim3((unsigned)S.n_chunks_max), dim3(SD_TB), 0, c->stream, cls_dev, (uint32_t)n_classes, c->perm_b.p, S.pos, S.seg_start,
-                       S.seg_chunk, (uint32_t)K, (unsigned long long*)d_hist, (unsigned long long*)d_out);
-  sf_launch_majority(c, d_hist, n_classes, K, c->sf_maj.p, d_majc);
-  VGS_HIP_TRY(c, hipGetLastError());
-  PF_COPY(hist, d_hist, kc); PF_COPY(n_outside, d_out, k); PF_COPY(majority, c->sf_maj.p, k); PF_COPY(majority_count, d_majc, k);
-  return VGS_OK;
+static vgs_status pf_hist_run(vgs_ctx* c, const char* fn, bool on_device, const int32_t* labels, int64_t K, const int32_t* cls, int64_t n,
+                              int32_t n_classes, int64_t* n_skipped, const AttrRecords* R, const AttrHistOut& O) {
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  vgs_status s = VGS_OK;
+  if (!on_device && ((s = vgs_upload_point_labels(c, labels, n, &labels)) != VGS_OK || (s = attr_upload_classes(c, &cls, n)) != VGS_OK)) return s;
+  AttrSource<PsSort> S;
+  if ((s = pf_source(c, fn, labels, K, R != nullptr, n_skipped, S)) != VGS_OK) return s;
+  return attr_hist_table(c, S, cls, n_classes, R, O);
 }
 
 static vgs_status pf_hist_entry(vgs_ctx* c, const char* fn, bool on_device, const int32_t* labels, int64_t K, const int32_t* cls, int64_t n,
-                                int32_t n_classes, int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority,
-                                int64_t* majority_count) {
+                                int32_t n_classes, int64_t* n_skipped, const AttrRecords* R, const AttrHistOut& O) {
   if (!c) return VGS_E_ARG;
+  if (R && R->n_records) *R->n_records = 0;
   if (n_skipped) *n_skipped = 0;
-  vgs_status s = pf_check_hist(c, fn, labels, K, cls, n, n_classes);
-  if (s != VGS_OK) return s;
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  if (!on_device) {
-    if ((s = vgs_upload_point_labels(c, labels, n, &labels)) != VGS_OK) return s;
-    if (n > 0) {
-      VGS_HIP_TRY(c, c->sf_cls.ensure((size_t)n));
-      VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_cls.p, cls, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-      VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
-      cls = c->sf_cls.p;
-    }
-  }
-  s = pf_class_hist(c, fn, labels, K, cls, n_classes, n_skipped, hist, n_outside, majority, majority_count);
-  const hipError_t e = hipStreamSynchronize(c->stream);
-  if (s == VGS_OK) VGS_HIP_TRY(c, e);
-  return s;
+  vgs_status s = pf_check(c, fn, R != nullptr, labels, K, cls, n);
+  if (s != VGS_OK || (s = attr_check_classes(c, fn, n_classes)) != VGS_OK ||
+      (s = attr_check_limit(c, fn, K, "labels", n_classes, "classes", "counters")) != VGS_OK)
+    return s;
+  return attr_settle(c, pf_hist_run(c, fn, on_device, labels, K, cls, n, n_classes, n_skipped, R, O));
 }
 
 extern "C" vgs_status vgs_point_label_field_stats(vgs_ctx* c, const int32_t* labels_host, int64_t K, const float* field_host, int64_t n,
                                                   int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor,
                                                   double* mean, double* var, float* vmin, float* vmax) {
-  return pf_field_entry(c, "vgs_point_label_field_stats", false, labels_host, K, field_host, n, n_channels, stride_bytes, n_skipped, n_valid, anchor, mean,
-                        var, vmin, vmax);
+  return pf_field_entry(c, "vgs_point_label_field_stats", false, labels_host, K, field_host, n, n_channels, stride_bytes, n_skipped, nullptr,
+                        {n_valid, anchor, mean, var, vmin, vmax});
 }
 
 extern "C" vgs_status vgs_point_label_field_stats_device(vgs_ctx* c, const int32_t* labels_dev, int64_t K, const float* field_dev, int64_t n,
                                                          int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid,
                                                          double* anchor, double* mean, double* var, float* vmin, float* vmax) {
-  return pf_field_entry(c, "vgs_point_label_field_stats_device", true, labels_dev, K, field_dev, n, n_channels, stride_bytes, n_skipped, n_valid, anchor,
-                        mean, var, vmin, vmax);
+  return pf_field_entry(c, "vgs_point_label_field_stats_device", true, labels_dev, K, field_dev, n, n_channels, stride_bytes, n_skipped, nullptr,
+                        {n_valid, anchor, mean, var, vmin, vmax});
 }
 
 extern "C" vgs_status vgs_point_label_class_histogram(vgs_ctx* c, const int32_t* labels_host, int64_t K, const int32_t* cls_host, int64_t n,
                                                       int32_t n_classes, int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority,
                                                       int64_t* majority_count) {
-  return pf_hist_entry(c, "vgs_point_label_class_histogram", false, labels_host, K, cls_host, n, n_classes, n_skipped, hist, n_outside, majority,
-                       majority_count);
+  return pf_hist_entry(c, "vgs_point_label_class_histogram", false, labels_host, K, cls_host, n, n_classes, n_skipped, nullptr,
+                       {hist, n_outside, majority, majority_count});
 }
 
 extern "C" vgs_status vgs_point_label_class_histogram_device(vgs_ctx* c, const int32_t* labels_dev, int64_t K, const int32_t* cls_dev, int64_t n,
                                                              int32_t n_classes, int64_t* n_skipped, int64_t* hist, int64_t* n_outside,
                                                              int32_t* majority, int64_t* majority_count) {
-  return pf_hist_entry(c, "vgs_point_label_class_histogram_device", true, labels_dev, K, cls_dev, n, n_classes, n_skipped, hist, n_outside, majority,
-                       majority_count);
+  return pf_hist_entry(c, "vgs_point_label_class_histogram_device", true, labels_dev, K, cls_dev, n, n_classes, n_skipped, nullptr,
+                       {hist, n_outside, majority, majority_count});
 }
 
 // ------------------------------------------------------------------------------------------------ tile contexts (include/vgs_tiles.h)
-// the checks both record calls share: the state, the labelling (the rules of vgs_own_point_label_moments) and the attribute array
-static vgs_status pfo_check(vgs_ctx* c, const char* fn, const int32_t* labels, int64_t K, const void* in, int64_t n_own) {
-  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
-  if (!c->have_region || c->n_own < 0) {
-    c->err = std::string(fn) + ": a tile context (vgs_set_owned_region and vgs_set_own_point_range) only";
-    return VGS_E_STATE;
-  }
-  if (K < 0 || K > (int64_t)0x7fffffff) { c->err = std::string(fn) + ": K = " + std::to_string(K) + " is out of range"; return VGS_E_ARG; }
-  if (n_own != c->n_own) {
-    c->err = std::string(fn) + ": n_own = " + std::to_string(n_own) + " must equal the number of own points of the context, " + std::to_string(c->n_own);
-    return VGS_E_ARG;
-  }
-  if (!labels && n_own > 0) { c->err = std::string(fn) + ": labels is NULL"; return VGS_E_ARG; }
-  if (!in && n_own > 0) { c->err = std::string(fn) + ": the input array is NULL"; return VGS_E_ARG; }
-  if (c->own_first < 0 || c->own_first + n_own > c->N) {
-    c->err = std::string(fn) + ": the own point range ends at " + std::to_string(c->own_first + n_own) + ", the cloud holds " + std::to_string(c->N) + " points";
-    return VGS_E_ARG;
-  }
-  return VGS_OK;
-}
-
-// the labels with an own point in the octree, ascending: a run that is not empty (seg_start, K + 1 words in HBM)
-static vgs_status pfo_own_labels(vgs_ctx* c, const uint32_t* seg_start, int64_t K, std::vector<int64_t>& rows) {
-  std::vector<uint32_t> st((size_t)K + 1);
-  VGS_HIP_TRY(c, hipMemcpyAsync(st.data(), seg_start, st.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  rows.clear();
-  for (int64_t k = 0; k < K; ++k) if (st[(size_t)k + 1] > st[(size_t)k]) rows.push_back(k);
-  return VGS_OK;
-}
-
-// rows of a dense device table (K rows of `per` entries) into a compact host array, which may be NULL
-template <typename T>
-static vgs_status pfo_compact(vgs_ctx* c, const T* dev, int64_t K, size_t per, const std::vector<int64_t>& rows, T* out) {
-  if (!out || rows.empty()) return VGS_OK;
-  std::vector<T> h((size_t)K * per);
-  VGS_HIP_TRY(c, hipMemcpyAsync(h.data(), dev, h.size() * sizeof(T), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t i = 0; i < rows.size(); ++i) std::copy(h.begin() + (size_t)rows[i] * per, h.begin() + ((size_t)rows[i] + 1) * per, out + i * per);
-  return VGS_OK;
-}
-
-// This rank's raw moments of the caller's labels 0 .. K-1 over its own octree points, labels_dev and field_dev in HBM (n_own rows each):
-// the sort of the own points, their anchors, the own-row chunks per channel group, the fold without the finish.  Dense on the device
-// (K x n_channels), compact on the host.
-static vgs_status pfo_field_moments(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t K, const float* field_dev, int32_t n_channels,
-                                    int64_t stride_bytes, int64_t* n_records, int64_t* n_skipped, int32_t* label, int64_t* n_valid, double* anchor,
-                                    double* s1, double* s2, float* vmin, float* vmax) {
-  PsSort S;
-  vgs_status s = ps_sort_points(c, fn, labels_dev, c->own_first, c->n_own, K, 0, n_skipped, S);
-  if (s != VGS_OK) return s;
-  if (!S.sorted || c->Nf == 0) return VGS_OK;   // K = 0 or no point in the octree: validated, the skipped points counted, no record
-  const uint32_t C = (uint32_t)n_channels;
-  const size_t kc = (size_t)K * C;
-  const int64_t stride_f = stride_bytes / 4, own_end = c->own_first + c->n_own;
-  VGS_HIP_TRY(c, c->sf_part.ensure((size_t)S.n_chunks_max * SF_G * SF_REC));
-  VGS_HIP_TRY(c, c->sf_anchor.ensure(kc)); VGS_HIP_TRY(c, c->sf_mean.ensure(kc)); VGS_HIP_TRY(c, c->sf_var.ensure(kc));
-  VGS_HIP_TRY(c, c->sf_nvalid.ensure(kc)); VGS_HIP_TRY(c, c->sf_min.ensure(kc)); VGS_HIP_TRY(c, c->sf_max.ensure(kc));
-  hipLaunchKernelGGL(k_pf_anchor, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, c->stream, field_dev, stride_f, C, c->perm_b.p, S.pos, S.seg_start,
-                     (uint32_t)K, c->own_first, c->sf_anchor.p);
-  for (uint32_t c0 = 0; c0 < C; c0 += SF_G) {
-    const uint32_t ng = C - c0 < SF_G ? C - c0 : SF_G;
-    hipLaunchKernelGGL(k_pf_own_chunks, dim3((unsigned)S.n_chunks_max), dim3(SD_TB), 0, c->stream, field_dev, stride_f, C, c0, ng, c->perm_b.p, S.pos,
-                       S.seg_start, S.seg_chunk, (uint32_t)K, c->sf_anchor.p, c->sf_part.p, c->own_first, own_end);
-    sf_launch_own_records(c, S.seg_chunk, c->sf_part.p, (uint32_t)S.n_chunks_max, K, C, c0, ng, c->sf_nvalid.p, c->sf_mean.p, c->sf_var.p, c->sf_min.p,
-                          c->sf_max.p);
-  }
-  VGS_HIP_TRY(c, hipGetLastError());
-  std::vector<int64_t> rows;
-  if ((s = pfo_own_labels(c, S.seg_start, K, rows)) != VGS_OK) return s;
-  if (label) for (size_t i = 0; i < rows.size(); ++i) label[i] = (int32_t)rows[i];
-  if ((s = pfo_compact(c, c->sf_nvalid.p, K, C, rows, n_valid)) != VGS_OK) return s;
-  if ((s = pfo_compact(c, c->sf_anchor.p, K, C, rows, anchor)) != VGS_OK) return s;
-  if ((s = pfo_compact(c, c->sf_mean.p, K, C, rows, s1)) != VGS_OK) return s;
-  if ((s = pfo_compact(c, c->sf_var.p, K, C, rows, s2)) != VGS_OK) return s;
-  if ((s = pfo_compact(c, c->sf_min.p, K, C, rows, vmin)) != VGS_OK) return s;
-  if ((s = pfo_compact(c, c->sf_max.p, K, C, rows, vmax)) != VGS_OK) return s;
-  if (n_records) *n_records = (int64_t)rows.size();
-  return VGS_OK;
-}
-
-static vgs_status pfo_field_entry(vgs_ctx* c, const char* fn, bool on_device, int64_t K, const int32_t* labels, const float* field, int64_t n_own,
-                                  int32_t n_channels, int64_t stride_bytes, int64_t* n_records, int64_t* n_skipped, int32_t* label, int64_t* n_valid,
-                                  double* anchor, double* s1, double* s2, float* vmin, float* vmax) {
-  if (!c) return VGS_E_ARG;
-  if (n_records) *n_records = 0;
-  if (n_skipped) *n_skipped = 0;
-  vgs_status s = pfo_check(c, fn, labels, K, field, n_own);
-  if (s != VGS_OK) return s;
-  if (n_channels < 1 || n_channels > 64) {
-    c->err = std::string(fn) + ": n_channels = " + std::to_string(n_channels) + " must be in 1 .. 64";
-    return VGS_E_ARG;
-  }
-  if (stride_bytes < 4 * (int64_t)n_channels || stride_bytes % 4 != 0) {
-    c->err = std::string(fn) + ": stride_bytes = " + std::to_string(stride_bytes) + " must be a multiple of 4 and at least 4 * n_channels = " +
-             std::to_string(4 * (int64_t)n_channels);
-    return VGS_E_ARG;
-  }
-  if (K * (int64_t)n_channels > ((int64_t)1 << 27)) {
-    c->err = std::string(fn) + ": " + std::to_string(K) + " labels x " + std::to_string(n_channels) + " channels = " +
-             std::to_string(K * (int64_t)n_channels) + " entries exceed the table's limit of 2^27 = " + std::to_string((int64_t)1 << 27);
-    return VGS_E_UNSUPPORTED;
-  }
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  if (!on_device) {
-    if ((s = vgs_upload_point_labels(c, labels, n_own, &labels)) != VGS_OK) return s;
-    if (n_own > 0) {
-      // one upload, rows at the caller's stride; the last row ends with its last channel
-      const size_t bytes = (size_t)(n_own - 1) * (size_t)stride_bytes + 4 * (size_t)n_channels;
-      VGS_HIP_TRY(c, c->sf_in.ensure((bytes + 3) / 4));
-      VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_in.p, field, bytes, hipMemcpyHostToDevice, c->stream));
-      VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
-      field = c->sf_in.p;
-    }
-  }
-  s = pfo_field_moments(c, fn, labels, K, field, n_channels, stride_bytes, n_records, n_skipped, label, n_valid, anchor, s1, s2, vmin, vmax);
-  // arrays read in place are the caller's again -- after a failure as well
-  const hipError_t e = hipStreamSynchronize(c->stream);
-  if (s == VGS_OK) VGS_HIP_TRY(c, e);
-  return s;
-}
-
-// this rank's class counts of the caller's labels over its own octree points: dense on the device, compact on the host
-static vgs_status pfo_class_counts(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t K, const int32_t* cls_dev, int32_t n_classes,
-                                   int64_t* n_records, int64_t* n_skipped, int32_t* label, int64_t* hist, int64_t* n_outside) {
-  PsSort S;
-  vgs_status s = ps_sort_points(c, fn, labels_dev, c->own_first, c->n_own, K, 0, n_skipped, S);
-  if (s != VGS_OK) return s;
-  if (!S.sorted || c->Nf == 0) return VGS_OK;
-  const size_t k = (size_t)K, nc = (size_t)n_classes, kc = k * nc;
-  VGS_HIP_TRY(c, c->sf_hist.ensure(kc + 2 * k));
-  int64_t *d_hist = c->sf_hist.p, *d_out = d_hist + kc;
-  VGS_HIP_TRY(c, hipMemsetAsync(d_hist, 0, (kc + k) * sizeof(int64_t), c->stream));
-  hipLaunchKernelGGL(k_pf_own_hist, dim3((unsigned)S.n_chunks_max), dim3(SD_TB), 0, c->stream, cls_dev, (uint32_t)n_classes, c->perm_b.p, S.pos, S.seg_start,
-                     S.seg_chunk, (uint32_t)K, (unsigned long long*)d_hist, (unsigned long long*)d_out, c->own_first, c->own_first + c->n_own);
-  VGS_HIP_TRY(c, hipGetLastError());
-  std::vector<int64_t> rows;
-  if ((s = pfo_own_labels(c, S.seg_start, K, rows)) != VGS_OK) return s;
-  if (label) for (size_t i = 0; i < rows.size(); ++i) label[i] = (int32_t)rows[i];
-  if ((s = pfo_compact(c, (const int64_t*)d_hist, K, nc, rows, hist)) != VGS_OK) return s;
-  if ((s = pfo_compact(c, (const int64_t*)d_out, K, 1, rows, n_outside)) != VGS_OK) return s;
-  if (n_records) *n_records = (int64_t)rows.size();
-  return VGS_OK;
-}
-
-static vgs_status pfo_hist_entry(vgs_ctx* c, const char* fn, bool on_device, int64_t K, const int32_t* labels, const int32_t* cls, int64_t n_own,
-                                 int32_t n_classes, int64_t* n_records, int64_t* n_skipped, int32_t* label, int64_t* hist, int64_t* n_outside) {
-  if (!c) return VGS_E_ARG;
-  if (n_records) *n_records = 0;
-  if (n_skipped) *n_skipped = 0;
-  vgs_status s = pfo_check(c, fn, labels, K, cls, n_own);
-  if (s != VGS_OK) return s;
-  if (n_classes < 1 || n_classes > 1024) {
-    c->err = std::string(fn) + ": n_classes = " + std::to_string(n_classes) + " must be in 1 .. 1024";
-    return VGS_E_ARG;
-  }
-  if (K * (int64_t)n_classes > ((int64_t)1 << 27)) {
-    c->err = std::string(fn) + ": " + std::to_string(K) + " labels x " + std::to_string(n_classes) + " classes = " +
-             std::to_string(K * (int64_t)n_classes) + " counters exceed the table's limit of 2^27 = " + std::to_string((int64_t)1 << 27);
-    return VGS_E_UNSUPPORTED;
-  }
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  if (!on_device) {
-    if ((s = vgs_upload_point_labels(c, labels, n_own, &labels)) != VGS_OK) return s;
-    if (n_own > 0) {
-      VGS_HIP_TRY(c, c->sf_cls.ensure((size_t)n_own));
-      VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_cls.p, cls, (size_t)n_own * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-      VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
-      cls = c->sf_cls.p;
-    }
-  }
-  s = pfo_class_counts(c, fn, labels, K, cls, n_classes, n_records, n_skipped, label, hist, n_outside);
-  const hipError_t e = hipStreamSynchronize(c->stream);
-  if (s == VGS_OK) VGS_HIP_TRY(c, e);
-  return s;
-}
-
+// This rank's raw moments and class counts of the caller's labels 0 .. K-1 over its own octree points, n_own labels and rows: dense on
+// the device, compact on the host.
 extern "C" vgs_status vgs_own_point_label_field_moments(vgs_ctx* c, int64_t K, const int32_t* labels_host, const float* field_host, int64_t n_own,
                                                         int32_t n_channels, int64_t stride_bytes, int64_t* n_records, int64_t* n_skipped,
                                                         int32_t* label, int64_t* n_valid, double* anchor, double* s1, double* s2, float* vmin,
                                                         float* vmax) {
-  return pfo_field_entry(c, "vgs_own_point_label_field_moments", false, K, labels_host, field_host, n_own, n_channels, stride_bytes, n_records, n_skipped,
-                         label, n_valid, anchor, s1, s2, vmin, vmax);
+  const AttrRecords R = {n_records, label};
+  return pf_field_entry(c, "vgs_own_point_label_field_moments", false, labels_host, K, field_host, n_own, n_channels, stride_bytes, n_skipped, &R,
+                        {n_valid, anchor, s1, s2, vmin, vmax});
 }
 
 extern "C" vgs_status vgs_own_point_label_field_moments_device(vgs_ctx* c, int64_t K, const int32_t* labels_dev, const float* field_dev, int64_t n_own,
                                                                int32_t n_channels, int64_t stride_bytes, int64_t* n_records, int64_t* n_skipped,
                                                                int32_t* label, int64_t* n_valid, double* anchor, double* s1, double* s2,
                                                                float* vmin, float* vmax) {
-  return pfo_field_entry(c, "vgs_own_point_label_field_moments_device", true, K, labels_dev, field_dev, n_own, n_channels, stride_bytes, n_records,
-                         n_skipped, label, n_valid, anchor, s1, s2, vmin, vmax);
+  const AttrRecords R = {n_records, label};
+  return pf_field_entry(c, "vgs_own_point_label_field_moments_device", true, labels_dev, K, field_dev, n_own, n_channels, stride_bytes, n_skipped, &R,
+                        {n_valid, anchor, s1, s2, vmin, vmax});
 }
 
 extern "C" vgs_status vgs_own_point_label_class_counts(vgs_ctx* c, int64_t K, const int32_t* labels_host, const int32_t* cls_host, int64_t n_own,
                                                        int32_t n_classes, int64_t* n_records, int64_t* n_skipped, int32_t* label, int64_t* hist,
                                                        int64_t* n_outside) {
-  return pfo_hist_entry(c, "vgs_own_point_label_class_counts", false, K, labels_host, cls_host, n_own, n_classes, n_records, n_skipped, label, hist,
-                        n_outside);
+  const AttrRecords R = {n_records, label};
+  return pf_hist_entry(c, "vgs_own_point_label_class_counts", false, labels_host, K, cls_host, n_own, n_classes, n_skipped, &R,
+                       {hist, n_outside, nullptr, nullptr});
 }
 
 extern "C" vgs_status vgs_own_point_label_class_counts_device(vgs_ctx* c, int64_t K, const int32_t* labels_dev, const int32_t* cls_dev, int64_t n_own,
                                                               int32_t n_classes, int64_t* n_records, int64_t* n_skipped, int32_t* label,
                                                               int64_t* hist, int64_t* n_outside) {
-  return pfo_hist_entry(c, "vgs_own_point_label_class_counts_device", true, K, labels_dev, cls_dev, n_own, n_classes, n_records, n_skipped, label, hist,
-                        n_outside);
+  const AttrRecords R = {n_records, label};
+  return pf_hist_entry(c, "vgs_own_point_label_class_counts_device", true, labels_dev, K, cls_dev, n_own, n_classes, n_skipped, &R,
+                       {hist, n_outside, nullptr, nullptr});
 }

@@ -297,9 +297,6 @@ extern "C" vgs_status vgs_segment_boxes_from_extents(vgs_ctx* c, int64_t K, int3
   sbt_launch_final(c, K, c->sbt_idx.p, c->sb_part.p, (uint32_t)K);
   VGS_HIP_TRY(c, hipGetLastError());
   const double* o = c->sbt_out.p;
-  if (half3) VGS_HIP_TRY(c, hipMemcpyAsync(half3, o + 6 * k, 3 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (center3) VGS_HIP_TRY(c, hipMemcpyAsync(center3, o + 9 * k, 3 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (frame9) VGS_HIP_TRY(c, hipMemcpyAsync(frame9, c->sbt_frame.p, 9 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return VGS_OK;
+  const RowCol col[3] = {{half3, o + 6 * k, 3 * sizeof(double)}, {center3, o + 9 * k, 3 * sizeof(double)}, {frame9, c->sbt_frame.p, 9 * sizeof(double)}};
+  return vgs_copy_rows(c, k, col, 3);
 }

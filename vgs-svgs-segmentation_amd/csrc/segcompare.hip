@@ -667,11 +667,8 @@ extern "C" vgs_status vgs_get_own_label_cells(vgs_ctx* c, int32_t* cell_seg, int
   const size_t nc = (size_t)c->cmp_own_cells, na = (size_t)c->cmp_ann;
   if (nc == 0) return VGS_OK;
   VGS_HIP_TRY(c, hipSetDevice(c->device));
-  if (cell_seg) VGS_HIP_TRY(c, hipMemcpyAsync(cell_seg, c->cmp_cell_i32.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (cell_ref) VGS_HIP_TRY(c, hipMemcpyAsync(cell_ref, c->cmp_cell_i32.p + na, nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (cell_n) VGS_HIP_TRY(c, hipMemcpyAsync(cell_n, c->cmp_cell_n.p, nc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return VGS_OK;
+  const RowCol col[3] = {{cell_seg, c->cmp_cell_i32.p, sizeof(int32_t)}, {cell_ref, c->cmp_cell_i32.p + na, sizeof(int32_t)}, {cell_n, c->cmp_cell_n.p, sizeof(int64_t)}};
+  return vgs_copy_rows(c, nc, col, 3);
 }
 
 // ------------------------------------------------------------------------------------------------ the tables from a cell list

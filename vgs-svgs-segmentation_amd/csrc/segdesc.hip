@@ -399,15 +399,9 @@ extern "C" vgs_status vgs_segment_descriptors_from_moments(vgs_ctx* c, int64_t K
   hipLaunchKernelGGL(k_sd_algebra, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, c->sd_mom.p, (uint32_t)K, c->P.method == 3 ? 1 : 0,
                      c->sd_npts.p, c->sd_nnodes.p, c->sd_bbox.p, c->sd_cen.p, c->sd_cov.p, c->sd_eval.p, c->sd_evec.p, c->sd_eig8.p);
   VGS_HIP_TRY(c, hipGetLastError());
-  const size_t k = (size_t)K;
-  if (n_points_out) VGS_HIP_TRY(c, hipMemcpyAsync(n_points_out, c->sd_npts.p, k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  if (n_nodes_out) VGS_HIP_TRY(c, hipMemcpyAsync(n_nodes_out, c->sd_nnodes.p, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (bbox6_out) VGS_HIP_TRY(c, hipMemcpyAsync(bbox6_out, c->sd_bbox.p, 6 * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (centroid3) VGS_HIP_TRY(c, hipMemcpyAsync(centroid3, c->sd_cen.p, 3 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (cov6) VGS_HIP_TRY(c, hipMemcpyAsync(cov6, c->sd_cov.p, 6 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (evals3) VGS_HIP_TRY(c, hipMemcpyAsync(evals3, c->sd_eval.p, 3 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (evecs9) VGS_HIP_TRY(c, hipMemcpyAsync(evecs9, c->sd_evec.p, 9 * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (eigen8) VGS_HIP_TRY(c, hipMemcpyAsync(eigen8, c->sd_eig8.p, 8 * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return VGS_OK;
+  const RowCol col[8] = {{n_points_out, c->sd_npts.p, sizeof(int64_t)}, {n_nodes_out, c->sd_nnodes.p, sizeof(int32_t)},
+                          {bbox6_out, c->sd_bbox.p, 6 * sizeof(float)},  {centroid3, c->sd_cen.p, 3 * sizeof(double)},
+                          {cov6, c->sd_cov.p, 6 * sizeof(double)},       {evals3, c->sd_eval.p, 3 * sizeof(double)},
+                          {evecs9, c->sd_evec.p, 9 * sizeof(double)},    {eigen8, c->sd_eig8.p, 8 * sizeof(float)}};
+  return vgs_copy_rows(c, (size_t)K, col, 8);
 }

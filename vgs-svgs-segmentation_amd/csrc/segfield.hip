@@ -27,12 +27,17 @@
 // partials as k_sf_final does and leaves n, S1, S2, min and max as they are (vgs_get_own_segment_field_moments,
 // vgs_get_own_segment_class_counts); the driver folds all ranks' records on the host and k_sf_final itself, over one partial per
 // (segment, channel), finishes the table (vgs_segment_field_stats_from_moments).
+// Host side: the drivers, uploads, copy-out and argument rules are attrpass.hpp's, one copy shared with pointfield.hip.  This file gives
+// them the source of the node labelling (sf_source: sd_prepare, for a tile context with the own range), its launch lines and record rule
+// (the attr_* specialisations for SdPrep) and the order of the checks (sf_check, then the table's own rules); the eight entry
+// points of a table go through one function with an on_device flag (sf_field_entry, sf_hist_entry), a record set selecting the tile
+// context's calls.  The folds' launch sites (sf_launch_*) are exported for both files' passes.
 #include <string.h>
 
 #include <algorithm>
 #include <string>
 
-#include "segpass.hpp"
+#include "attrpass.hpp"
 
 // anchor[k, c] for every channel: the value of the segment's first point in the chunk order, 0.0 where it is not finite.  One thread per entry.
 __global__ __launch_bounds__(256) void k_sf_anchor(const float* __restrict__ field, int64_t stride_f, uint32_t C, const uint32_t* __restrict__ perm,
@@ -248,8 +253,9 @@ __global__ __launch_bounds__(256) void k_sf_majority(const unsigned long long* _
   majority_count[k] = (long long)best;
 }
 
-// the launch sites of the folds for the passes of other files (pointfield.hip): k_sf_final and, for tile contexts, k_sf_own_records over
-// the partials of one channel group, k_sf_majority over a K x n_classes table; left on the context's stream
+// ---------------------------------------------------------------------------------------------------------------------- host
+// the launch sites of the folds, for the drivers of attrpass.hpp: k_sf_final and, for tile contexts, k_sf_own_records over the partials
+// of one channel group, k_sf_majority over a K x n_classes table; left on the context's stream
 void sf_launch_final(vgs_ctx* c, const uint32_t* seg_chunk, const double* part, uint32_t n_part, int64_t K, uint32_t C, uint32_t c0, uint32_t ng,
                      const double* anchor, int64_t* o_n, double* o_mean, double* o_var, float* o_min, float* o_max) {
   hipLaunchKernelGGL(k_sf_final, dim3((unsigned)(((size_t)K * ng + 3) / 4)), dim3(256), 0, c->stream, seg_chunk, part, n_part, (uint32_t)K, C, c0, ng, anchor,
@@ -265,284 +271,173 @@ void sf_launch_majority(vgs_ctx* c, const int64_t* hist, int32_t n_classes, int6
                      (uint32_t)K, majority, (long long*)majority_count);
 }
 
-static vgs_status sf_check_state(vgs_ctx* c, const char* fn) {
-  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
-  if (vgs_is_tile(c)) {
-    c->err = std::string(fn) + ": a tile context (owned region / own point range) holds only part of its segments; field statistics need the whole cloud in one context";
-    return VGS_E_STATE;
-  }
-  return VGS_OK;
-}
-
-static vgs_status sf_check_n(vgs_ctx* c, const char* fn, const void* in, int64_t n) {
-  if (n != c->N) {
-    c->err = std::string(fn) + ": n = " + std::to_string(n) + " must equal the number of points of the cloud, " + std::to_string(c->N);
-    return VGS_E_ARG;
-  }
-  if (!in && n > 0) { c->err = std::string(fn) + ": the input array is NULL"; return VGS_E_ARG; }
-  return VGS_OK;
-}
-
-static vgs_status sf_check_field(vgs_ctx* c, const char* fn, const float* field, int64_t n, int32_t n_channels, int64_t stride_bytes) {
-  vgs_status s = sf_check_state(c, fn);
-  if (s != VGS_OK) return s;
-  if ((s = sf_check_n(c, fn, field, n)) != VGS_OK) return s;
-  if (n_channels < 1 || n_channels > 64) {
-    c->err = std::string(fn) + ": n_channels = " + std::to_string(n_channels) + " must be in 1 .. 64";
-    return VGS_E_ARG;
-  }
-  if (stride_bytes < 4 * (int64_t)n_channels || stride_bytes % 4 != 0) {
-    c->err = std::string(fn) + ": stride_bytes = " + std::to_string(stride_bytes) + " must be a multiple of 4 and at least 4 * n_channels = " +
-             std::to_string(4 * (int64_t)n_channels);
-    return VGS_E_ARG;
-  }
-  return VGS_OK;
-}
-
-// the field table from a device buffer: every output a host array of K x n_channels, any may be NULL
-static vgs_status sf_field_stats(vgs_ctx* c, const float* field_dev, int32_t n_channels, int64_t stride_bytes, int64_t* n_valid, double* anchor,
-                                 double* mean, double* var, float* vmin, float* vmax) {
-  const int64_t K = c->counts[VGS_N_KEPT];
+// The source of the node labelling (attrpass.hpp): sd_prepare for the labels 0 .. K-1 of vox_label -- one context: its kept segments; a
+// tile context (own): the global labels after vgs_apply_tile_labels, only the own points counting.  Without a segment, a voxel or a point
+// in the octree nothing is written.  A tile context's first own points (sd_own_anchor into sd_apos) are queued by the first launch below.
+static vgs_status sf_source(vgs_ctx* c, int64_t K, bool own, AttrSource<SdPrep>& S) {
+  S.K = K;
+  S.own = own;
   if (K == 0 || c->V == 0 || c->Nf == 0) return VGS_OK;
-  const uint32_t C = (uint32_t)n_channels;
-  const size_t kc = (size_t)K * C;
-  const int64_t stride_f = stride_bytes / 4;
-  SdPrep P;
-  vgs_status s = sd_prepare(c, K, P);
+  vgs_status s = sd_prepare(c, K, S.d);
   if (s != VGS_OK) return s;
-  VGS_HIP_TRY(c, c->sf_part.ensure((size_t)P.n_chunks_max * SF_G * SF_REC));
-  VGS_HIP_TRY(c, c->sf_anchor.ensure(kc)); VGS_HIP_TRY(c, c->sf_mean.ensure(kc)); VGS_HIP_TRY(c, c->sf_var.ensure(kc));
-  VGS_HIP_TRY(c, c->sf_nvalid.ensure(kc)); VGS_HIP_TRY(c, c->sf_min.ensure(kc)); VGS_HIP_TRY(c, c->sf_max.ensure(kc));
-  hipLaunchKernelGGL(k_sf_anchor, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, c->stream, field_dev, stride_f, C, c->perm_b.p, c->vox_start.p,
-                     P.ids, P.seg_node, (uint32_t)K, c->sf_anchor.p);
-  for (uint32_t c0 = 0; c0 < C; c0 += SF_G) {
-    const uint32_t ng = C - c0 < SF_G ? C - c0 : SF_G;
-    hipLaunchKernelGGL(k_sf_chunks, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, field_dev, stride_f, C, c0, ng, c->perm_b.p,
-                       c->vox_start.p, P.ids, P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, c->sf_anchor.p, c->sf_part.p);
-    sf_launch_final(c, P.seg_chunk, c->sf_part.p, (uint32_t)P.n_chunks_max, K, C, c0, ng, c->sf_anchor.p, c->sf_nvalid.p, c->sf_mean.p, c->sf_var.p,
-                    c->sf_min.p, c->sf_max.p);
-  }
-  VGS_HIP_TRY(c, hipGetLastError());
-  if (n_valid) VGS_HIP_TRY(c, hipMemcpyAsync(n_valid, c->sf_nvalid.p, kc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  if (anchor) VGS_HIP_TRY(c, hipMemcpyAsync(anchor, c->sf_anchor.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (mean) VGS_HIP_TRY(c, hipMemcpyAsync(mean, c->sf_mean.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (var) VGS_HIP_TRY(c, hipMemcpyAsync(var, c->sf_var.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (vmin) VGS_HIP_TRY(c, hipMemcpyAsync(vmin, c->sf_min.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (vmax) VGS_HIP_TRY(c, hipMemcpyAsync(vmax, c->sf_max.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  S.seg_chunk = S.d.seg_chunk;
+  S.n_chunks_max = S.d.n_chunks_max;
+  S.live = S.chunks = true;
+  if (own) { S.own_first = c->own_first; S.own_end = c->own_first + c->n_own; }
   return VGS_OK;
 }
 
-extern "C" vgs_status vgs_segment_field_stats_device(vgs_ctx* c, const float* field_dev, int64_t n, int32_t n_channels, int64_t stride_bytes,
-                                                     int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax) {
-  if (!c) return VGS_E_ARG;
-  vgs_status s = sf_check_field(c, "vgs_segment_field_stats_device", field_dev, n, n_channels, stride_bytes);
+template <> vgs_status attr_launch_anchor<SdPrep>(vgs_ctx* c, const AttrSource<SdPrep>& S, const float* field, int64_t stride_f, uint32_t C) {
+  const dim3 grid((unsigned)(((size_t)S.K * C + 255) / 256));
+  if (!S.own) {
+    hipLaunchKernelGGL(k_sf_anchor, grid, dim3(256), 0, c->stream, field, stride_f, C, c->perm_b.p, c->vox_start.p, S.d.ids, S.d.seg_node, (uint32_t)S.K,
+                       c->sf_anchor.p);
+    return VGS_OK;
+  }
+  vgs_status s = sd_own_anchor(c, S.K, S.d);
   if (s != VGS_OK) return s;
+  hipLaunchKernelGGL(k_sf_anchor_own, grid, dim3(256), 0, c->stream, field, stride_f, C, c->perm_b.p, c->sd_apos.p, S.own_first, S.own_end, (uint32_t)S.K,
+                     c->sf_anchor.p);
+  return VGS_OK;
+}
+
+template <> void attr_launch_chunks<SdPrep>(vgs_ctx* c, const AttrSource<SdPrep>& S, const float* field, int64_t stride_f, uint32_t C, uint32_t c0, uint32_t ng) {
+  const dim3 grid((unsigned)S.n_chunks_max);
+  if (S.own)
+    hipLaunchKernelGGL(k_sf_chunks_own, grid, dim3(SD_TB), 0, c->stream, field, stride_f, C, c0, ng, c->perm_b.p, c->vox_start.p, S.d.ids, S.d.vp, S.d.seg_node,
+                       S.d.seg_chunk, (uint32_t)S.K, c->sf_anchor.p, c->sf_part.p, S.own_first, S.own_end, c->sd_apos.p);
+  else
+    hipLaunchKernelGGL(k_sf_chunks, grid, dim3(SD_TB), 0, c->stream, field, stride_f, C, c0, ng, c->perm_b.p, c->vox_start.p, S.d.ids, S.d.vp, S.d.seg_node,
+                       S.d.seg_chunk, (uint32_t)S.K, c->sf_anchor.p, c->sf_part.p);
+}
+
+template <> vgs_status attr_launch_hist<SdPrep>(vgs_ctx* c, const AttrSource<SdPrep>& S, const int32_t* cls, uint32_t n_classes, unsigned long long* hist,
+                                   unsigned long long* n_outside) {
+  const dim3 grid((unsigned)S.n_chunks_max);
+  if (!S.own) {
+    hipLaunchKernelGGL(k_sf_hist, grid, dim3(SD_TB), 0, c->stream, cls, n_classes, c->perm_b.p, c->vox_start.p, S.d.ids, S.d.vp, S.d.seg_node, S.d.seg_chunk,
+                       (uint32_t)S.K, hist, n_outside);
+    return VGS_OK;
+  }
+  vgs_status s = sd_own_anchor(c, S.K, S.d);   // (the record rule reads sd_apos)
+  if (s != VGS_OK) return s;
+  hipLaunchKernelGGL(k_sf_hist_own, grid, dim3(SD_TB), 0, c->stream, cls, n_classes, c->perm_b.p, c->vox_start.p, S.d.ids, S.d.vp, S.d.seg_node, S.d.seg_chunk,
+                     (uint32_t)S.K, hist, n_outside, S.own_first, S.own_end);
+  return VGS_OK;
+}
+
+// the labels with an own labelled point leave a record: sd_apos[k] != 0xffffffff (the label set of vgs_get_own_segment_extents)
+template <> size_t attr_rule_words<SdPrep>(vgs_ctx* c, const AttrSource<SdPrep>& S, const uint32_t** dev) { *dev = c->sd_apos.p; return (size_t)S.K; }
+template <> bool attr_has_record<SdPrep>(const AttrSource<SdPrep>&, const uint32_t* apos, size_t k) { return apos[k] != 0xffffffffu; }
+
+// The rules both tables share, in this family's order.  own: the calls of a tile context, K the global label count and n the rank's own
+// points; otherwise one context with the whole cloud.
+static vgs_status sf_check(vgs_ctx* c, const char* fn, bool own, int64_t K, const void* in, int64_t n) {
+  vgs_status s = attr_check_segmented(c, fn);
+  if (s != VGS_OK) return s;
+  if (own) {
+    if ((s = attr_check_tile_only(c, fn)) != VGS_OK || (s = attr_check_K(c, fn, K, (int64_t)0xfffffffeLL)) != VGS_OK) return s;
+    s = attr_check_n(c, fn, "n_own", n, "own points of the context", c->n_own);
+  } else {
+    if (vgs_is_tile(c))
+      return attr_fail(c, fn, VGS_E_STATE, "a tile context (owned region / own point range) holds only part of its segments; field statistics need the whole cloud in one context");
+    s = attr_check_n(c, fn, "n", n, "points of the cloud", c->N);
+  }
+  return s != VGS_OK ? s : attr_check_array(c, fn, "the input array", in, n);
+}
+
+// The eight entry points of a table come through one function.  R = NULL: one context, K its kept count, dense rows.  R given: a tile
+// context, K the caller's, compact records (n_records is required and zeroed once the arguments hold).  A host variant without a segment
+// or a point returns before the device is touched.
+static vgs_status sf_field_run(vgs_ctx* c, bool on_device, int64_t K, const float* field, int64_t n, int32_t n_channels, int64_t stride_bytes,
+                               const AttrRecords* R, const AttrFieldOut& O) {
   VGS_HIP_TRY(c, hipSetDevice(c->device));
-  return sf_field_stats(c, field_dev, n_channels, stride_bytes, n_valid, anchor, mean, var, vmin, vmax);
+  vgs_status s = on_device ? VGS_OK : attr_upload_field(c, &field, n, n_channels, stride_bytes);
+  AttrSource<SdPrep> S;
+  if (s != VGS_OK || (s = sf_source(c, K, R != nullptr, S)) != VGS_OK) return s;
+  return attr_field_table(c, S, field, n_channels, stride_bytes, R, O);
+}
+
+static vgs_status sf_field_entry(vgs_ctx* c, const char* fn, bool on_device, int64_t K, const float* field, int64_t n, int32_t n_channels,
+                                 int64_t stride_bytes, const AttrRecords* R, const AttrFieldOut& O) {
+  if (!c || (R && !R->n_records)) return VGS_E_ARG;
+  if (!R) K = c->counts[VGS_N_KEPT];
+  vgs_status s = sf_check(c, fn, R != nullptr, K, field, n);
+  if (s != VGS_OK || (s = attr_check_channels(c, fn, n_channels)) != VGS_OK || (s = attr_check_stride(c, fn, n_channels, stride_bytes)) != VGS_OK) return s;
+  if (R) *R->n_records = 0;
+  if (!on_device && (K == 0 || n == 0)) return VGS_OK;
+  return attr_settle(c, sf_field_run(c, on_device, K, field, n, n_channels, stride_bytes, R, O));
+}
+
+static vgs_status sf_hist_run(vgs_ctx* c, bool on_device, int64_t K, const int32_t* cls, int64_t n, int32_t n_classes, const AttrRecords* R,
+                              const AttrHistOut& O) {
+  VGS_HIP_TRY(c, hipSetDevice(c->device));
+  vgs_status s = on_device ? VGS_OK : attr_upload_classes(c, &cls, n);
+  AttrSource<SdPrep> S;
+  if (s != VGS_OK || (s = sf_source(c, K, R != nullptr, S)) != VGS_OK) return s;
+  return attr_hist_table(c, S, cls, n_classes, R, O);
+}
+
+static vgs_status sf_hist_entry(vgs_ctx* c, const char* fn, bool on_device, int64_t K, const int32_t* cls, int64_t n, int32_t n_classes,
+                                const AttrRecords* R, const AttrHistOut& O) {
+  if (!c || (R && !R->n_records)) return VGS_E_ARG;
+  if (!R) K = c->counts[VGS_N_KEPT];
+  vgs_status s = sf_check(c, fn, R != nullptr, K, cls, n);
+  if (s != VGS_OK || (s = attr_check_classes(c, fn, n_classes)) != VGS_OK ||
+      (s = attr_check_limit(c, fn, K, "segments", n_classes, "classes", "counters")) != VGS_OK)
+    return s;
+  if (R) *R->n_records = 0;
+  if (!on_device && (K == 0 || n == 0)) return VGS_OK;
+  return attr_settle(c, sf_hist_run(c, on_device, K, cls, n, n_classes, R, O));
 }
 
 extern "C" vgs_status vgs_segment_field_stats(vgs_ctx* c, const float* field_host, int64_t n, int32_t n_channels, int64_t stride_bytes,
                                               int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax) {
-  if (!c) return VGS_E_ARG;
-  vgs_status s = sf_check_field(c, "vgs_segment_field_stats", field_host, n, n_channels, stride_bytes);
-  if (s != VGS_OK) return s;
-  if (c->counts[VGS_N_KEPT] == 0 || n == 0) return VGS_OK;
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  // one upload, rows at the caller's stride; the last row ends with its last channel
-  const size_t bytes = (size_t)(n - 1) * (size_t)stride_bytes + 4 * (size_t)n_channels;
-  VGS_HIP_TRY(c, c->sf_in.ensure((bytes + 3) / 4));
-  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_in.p, field_host, bytes, hipMemcpyHostToDevice, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
-  return sf_field_stats(c, c->sf_in.p, n_channels, stride_bytes, n_valid, anchor, mean, var, vmin, vmax);
+  return sf_field_entry(c, "vgs_segment_field_stats", false, 0, field_host, n, n_channels, stride_bytes, nullptr, {n_valid, anchor, mean, var, vmin, vmax});
 }
 
-static vgs_status sf_check_hist(vgs_ctx* c, const char* fn, const int32_t* cls, int64_t n, int32_t n_classes) {
-  vgs_status s = sf_check_state(c, fn);
-  if (s != VGS_OK) return s;
-  if ((s = sf_check_n(c, fn, cls, n)) != VGS_OK) return s;
-  if (n_classes < 1 || n_classes > 1024) {
-    c->err = std::string(fn) + ": n_classes = " + std::to_string(n_classes) + " must be in 1 .. 1024";
-    return VGS_E_ARG;
-  }
-  const int64_t K = c->counts[VGS_N_KEPT];
-  if (K * (int64_t)n_classes > ((int64_t)1 << 27)) {
-    c->err = std::string(fn) + ": " + std::to_string(K) + " segments x " + std::to_string(n_classes) + " classes = " +
-             std::to_string(K * (int64_t)n_classes) + " counters exceed the table's limit of 2^27 = " + std::to_string((int64_t)1 << 27);
-    return VGS_E_UNSUPPORTED;
-  }
-  return VGS_OK;
-}
-
-// the histogram from a device buffer: hist K x n_classes, the others K; host arrays, any may be NULL
-static vgs_status sf_class_hist(vgs_ctx* c, const int32_t* cls_dev, int32_t n_classes, int64_t* hist, int64_t* n_outside, int32_t* majority,
-                                int64_t* majority_count) {
-  const int64_t K = c->counts[VGS_N_KEPT];
-  if (K == 0 || c->V == 0 || c->Nf == 0) return VGS_OK;
-  const size_t k = (size_t)K, kc = k * (size_t)n_classes;
-  SdPrep P;
-  vgs_status s = sd_prepare(c, K, P);
-  if (s != VGS_OK) return s;
-  VGS_HIP_TRY(c, c->sf_hist.ensure(kc + 2 * k)); VGS_HIP_TRY(c, c->sf_maj.ensure(k));
-  int64_t *d_hist = c->sf_hist.p, *d_out = d_hist + kc, *d_majc = d_out + k;
-  VGS_HIP_TRY(c, hipMemsetAsync(d_hist, 0, (kc + k) * sizeof(int64_t), c->stream));
-  hipLaunchKernelGGL(k_sf_hist, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, cls_dev, (uint32_t)n_classes, c->perm_b.p, c->vox_start.p,
-                     P.ids, P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, (unsigned long long*)d_hist, (unsigned long long*)d_out);
-  sf_launch_majority(c, d_hist, n_classes, K, c->sf_maj.p, d_majc);
-  VGS_HIP_TRY(c, hipGetLastError());
-  if (hist) VGS_HIP_TRY(c, hipMemcpyAsync(hist, d_hist, kc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  if (n_outside) VGS_HIP_TRY(c, hipMemcpyAsync(n_outside, d_out, k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  if (majority) VGS_HIP_TRY(c, hipMemcpyAsync(majority, c->sf_maj.p, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (majority_count) VGS_HIP_TRY(c, hipMemcpyAsync(majority_count, d_majc, k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return VGS_OK;
-}
-
-extern "C" vgs_status vgs_segment_class_histogram_device(vgs_ctx* c, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* hist,
-                                                         int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
-  if (!c) return VGS_E_ARG;
-  vgs_status s = sf_check_hist(c, "vgs_segment_class_histogram_device", cls_dev, n, n_classes);
-  if (s != VGS_OK) return s;
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  return sf_class_hist(c, cls_dev, n_classes, hist, n_outside, majority, majority_count);
+extern "C" vgs_status vgs_segment_field_stats_device(vgs_ctx* c, const float* field_dev, int64_t n, int32_t n_channels, int64_t stride_bytes,
+                                                     int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax) {
+  return sf_field_entry(c, "vgs_segment_field_stats_device", true, 0, field_dev, n, n_channels, stride_bytes, nullptr, {n_valid, anchor, mean, var, vmin, vmax});
 }
 
 extern "C" vgs_status vgs_segment_class_histogram(vgs_ctx* c, const int32_t* cls_host, int64_t n, int32_t n_classes, int64_t* hist,
                                                   int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
-  if (!c) return VGS_E_ARG;
-  vgs_status s = sf_check_hist(c, "vgs_segment_class_histogram", cls_host, n, n_classes);
-  if (s != VGS_OK) return s;
-  if (c->counts[VGS_N_KEPT] == 0 || n == 0) return VGS_OK;
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  VGS_HIP_TRY(c, c->sf_cls.ensure((size_t)n));
-  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_cls.p, cls_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
-  return sf_class_hist(c, c->sf_cls.p, n_classes, hist, n_outside, majority, majority_count);
+  return sf_hist_entry(c, "vgs_segment_class_histogram", false, 0, cls_host, n, n_classes, nullptr, {hist, n_outside, majority, majority_count});
+}
+
+extern "C" vgs_status vgs_segment_class_histogram_device(vgs_ctx* c, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* hist,
+                                                         int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
+  return sf_hist_entry(c, "vgs_segment_class_histogram_device", true, 0, cls_dev, n, n_classes, nullptr, {hist, n_outside, majority, majority_count});
 }
 
 // ------------------------------------------------------------------------------------------------ tile contexts (include/vgs_tiles.h)
-static vgs_status sft_check_state(vgs_ctx* c, const char* fn) {
-  if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
-  if (!c->have_region || c->n_own < 0) {
-    c->err = std::string(fn) + ": a tile context (vgs_set_owned_region and vgs_set_own_point_range) only";
-    return VGS_E_STATE;
-  }
-  return VGS_OK;
-}
-
-static vgs_status sft_check_n(vgs_ctx* c, const char* fn, const void* in, int64_t n_own) {
-  if (n_own != c->n_own) {
-    c->err = std::string(fn) + ": n_own = " + std::to_string(n_own) + " must equal the number of own points of the context, " + std::to_string(c->n_own);
-    return VGS_E_ARG;
-  }
-  if (!in && n_own > 0) { c->err = std::string(fn) + ": the input array is NULL"; return VGS_E_ARG; }
-  return VGS_OK;
-}
-
-static vgs_status sft_check_field(vgs_ctx* c, const char* fn, int64_t K, const float* field, int64_t n_own, int32_t n_channels, int64_t stride_bytes) {
-  vgs_status s = sft_check_state(c, fn);
-  if (s != VGS_OK) return s;
-  if (K < 0 || K >= (int64_t)0xffffffffLL) { c->err = std::string(fn) + ": K = " + std::to_string(K) + " is out of range"; return VGS_E_ARG; }
-  if ((s = sft_check_n(c, fn, field, n_own)) != VGS_OK) return s;
-  if (n_channels < 1 || n_channels > 64) {
-    c->err = std::string(fn) + ": n_channels = " + std::to_string(n_channels) + " must be in 1 .. 64";
-    return VGS_E_ARG;
-  }
-  if (stride_bytes < 4 * (int64_t)n_channels || stride_bytes % 4 != 0) {
-    c->err = std::string(fn) + ": stride_bytes = " + std::to_string(stride_bytes) + " must be a multiple of 4 and at least 4 * n_channels = " +
-             std::to_string(4 * (int64_t)n_channels);
-    return VGS_E_ARG;
-  }
-  return VGS_OK;
-}
-
-// the labels with an own labelled point, ascending: anchor_pos[k] != 0xffffffff (the label set of vgs_get_own_segment_extents)
-static void sft_own_labels(const std::vector<uint32_t>& apos, std::vector<int64_t>& rows) {
-  rows.clear();
-  for (size_t k = 0; k < apos.size(); ++k) if (apos[k] != 0xffffffffu) rows.push_back((int64_t)k);
-}
-
-// This rank's moments of the global labels 0 .. K-1 over its own points, from a device buffer of n_own rows: sd_prepare over vox_label
-// (global after vgs_apply_tile_labels), the first own points, their values as anchors, the own-point chunks per channel group, the fold
-// without the finish.  Dense on the device (K x n_channels), compact on the host.
-static vgs_status sft_field_moments(vgs_ctx* c, int64_t K, const float* field_dev, int32_t n_channels, int64_t stride_bytes, int64_t* n_records,
-                                    int32_t* label, int64_t* n_valid, double* anchor, double* s1, double* s2, float* vmin, float* vmax) {
-  *n_records = 0;
-  if (K == 0 || c->V == 0 || c->Nf == 0) return VGS_OK;
-  const uint32_t C = (uint32_t)n_channels;
-  const size_t kc = (size_t)K * C;
-  const int64_t stride_f = stride_bytes / 4, own_end = c->own_first + c->n_own;
-  SdPrep P;
-  vgs_status s = sd_prepare(c, K, P);
-  if (s != VGS_OK) return s;
-  VGS_HIP_TRY(c, c->sf_part.ensure((size_t)P.n_chunks_max * SF_G * SF_REC));
-  VGS_HIP_TRY(c, c->sf_anchor.ensure(kc)); VGS_HIP_TRY(c, c->sf_mean.ensure(kc)); VGS_HIP_TRY(c, c->sf_var.ensure(kc));
-  VGS_HIP_TRY(c, c->sf_nvalid.ensure(kc)); VGS_HIP_TRY(c, c->sf_min.ensure(kc)); VGS_HIP_TRY(c, c->sf_max.ensure(kc));
-  if ((s = sd_own_anchor(c, K, P)) != VGS_OK) return s;
-  hipLaunchKernelGGL(k_sf_anchor_own, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, c->stream, field_dev, stride_f, C, c->perm_b.p, c->sd_apos.p,
-                     c->own_first, own_end, (uint32_t)K, c->sf_anchor.p);
-  for (uint32_t c0 = 0; c0 < C; c0 += SF_G) {
-    const uint32_t ng = C - c0 < SF_G ? C - c0 : SF_G;
-    hipLaunchKernelGGL(k_sf_chunks_own, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, field_dev, stride_f, C, c0, ng, c->perm_b.p,
-                       c->vox_start.p, P.ids, P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, c->sf_anchor.p, c->sf_part.p, c->own_first, own_end,
-                       c->sd_apos.p);
-    hipLaunchKernelGGL(k_sf_own_records, dim3((unsigned)(((size_t)K * ng + 3) / 4)), dim3(256), 0, c->stream, P.seg_chunk, c->sf_part.p,
-                       (uint32_t)P.n_chunks_max, (uint32_t)K, C, c0, ng, c->sf_nvalid.p, c->sf_mean.p, c->sf_var.p, c->sf_min.p, c->sf_max.p);
-  }
-  VGS_HIP_TRY(c, hipGetLastError());
-  std::vector<uint32_t> apos((size_t)K);
-  std::vector<int64_t> nv(kc);
-  std::vector<double> an(kc), m1(kc), m2(kc);
-  std::vector<float> mn(kc), mx(kc);
-  VGS_HIP_TRY(c, hipMemcpyAsync(apos.data(), c->sd_apos.p, apos.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipMemcpyAsync(nv.data(), c->sf_nvalid.p, kc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipMemcpyAsync(an.data(), c->sf_anchor.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipMemcpyAsync(m1.data(), c->sf_mean.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipMemcpyAsync(m2.data(), c->sf_var.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipMemcpyAsync(mn.data(), c->sf_min.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipMemcpyAsync(mx.data(), c->sf_max.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  std::vector<int64_t> rows;
-  sft_own_labels(apos, rows);
-  for (size_t i = 0; i < rows.size(); ++i) {
-    const size_t src = (size_t)rows[i] * C, dst = i * C;
-    if (label) label[i] = (int32_t)rows[i];
-    if (n_valid) std::copy(nv.begin() + src, nv.begin() + src + C, n_valid + dst);
-    if (anchor) std::copy(an.begin() + src, an.begin() + src + C, anchor + dst);
-    if (s1) std::copy(m1.begin() + src, m1.begin() + src + C, s1 + dst);
-    if (s2) std::copy(m2.begin() + src, m2.begin() + src + C, s2 + dst);
-    if (vmin) std::copy(mn.begin() + src, mn.begin() + src + C, vmin + dst);
-    if (vmax) std::copy(mx.begin() + src, mx.begin() + src + C, vmax + dst);
-  }
-  *n_records = (int64_t)rows.size();
-  return VGS_OK;
+// This rank's moments and class counts of the global labels 0 .. K-1 over its own points, n_own rows: dense on the device, compact on the host.
+extern "C" vgs_status vgs_get_own_segment_field_moments(vgs_ctx* c, int64_t K, const float* field_host, int64_t n_own, int32_t n_channels,
+                                                        int64_t stride_bytes, int64_t* n_records, int32_t* label, int64_t* n_valid, double* anchor,
+                                                        double* s1, double* s2, float* vmin, float* vmax) {
+  const AttrRecords R = {n_records, label};
+  return sf_field_entry(c, "vgs_get_own_segment_field_moments", false, K, field_host, n_own, n_channels, stride_bytes, &R, {n_valid, anchor, s1, s2, vmin, vmax});
 }
 
 extern "C" vgs_status vgs_get_own_segment_field_moments_device(vgs_ctx* c, int64_t K, const float* field_dev, int64_t n_own, int32_t n_channels,
                                                                int64_t stride_bytes, int64_t* n_records, int32_t* label, int64_t* n_valid,
                                                                double* anchor, double* s1, double* s2, float* vmin, float* vmax) {
-  if (!c || !n_records) return VGS_E_ARG;
-  vgs_status s = sft_check_field(c, "vgs_get_own_segment_field_moments_device", K, field_dev, n_own, n_channels, stride_bytes);
-  if (s != VGS_OK) return s;
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  return sft_field_moments(c, K, field_dev, n_channels, stride_bytes, n_records, label, n_valid, anchor, s1, s2, vmin, vmax);
+  const AttrRecords R = {n_records, label};
+  return sf_field_entry(c, "vgs_get_own_segment_field_moments_device", true, K, field_dev, n_own, n_channels, stride_bytes, &R,
+                        {n_valid, anchor, s1, s2, vmin, vmax});
 }
 
-extern "C" vgs_status vgs_get_own_segment_field_moments(vgs_ctx* c, int64_t K, const float* field_host, int64_t n_own, int32_t n_channels,
-                                                        int64_t stride_bytes, int64_t* n_records, int32_t* label, int64_t* n_valid, double* anchor,
-                                                        double* s1, double* s2, float* vmin, float* vmax) {
-  if (!c || !n_records) return VGS_E_ARG;
-  vgs_status s = sft_check_field(c, "vgs_get_own_segment_field_moments", K, field_host, n_own, n_channels, stride_bytes);
-  if (s != VGS_OK) return s;
-  *n_records = 0;
-  if (K == 0 || n_own == 0) return VGS_OK;   // (no own point: no record)
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  // one upload, rows at the caller's stride; the last row ends with its last channel
-  const size_t bytes = (size_t)(n_own - 1) * (size_t)stride_bytes + 4 * (size_t)n_channels;
-  VGS_HIP_TRY(c, c->sf_in.ensure((bytes + 3) / 4));
-  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_in.p, field_host, bytes, hipMemcpyHostToDevice, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
-  return sft_field_moments(c, K, c->sf_in.p, n_channels, stride_bytes, n_records, label, n_valid, anchor, s1, s2, vmin, vmax);
+extern "C" vgs_status vgs_get_own_segment_class_counts(vgs_ctx* c, int64_t K, const int32_t* cls_host, int64_t n_own, int32_t n_classes,
+                                                       int64_t* n_records, int32_t* label, int64_t* hist, int64_t* n_outside) {
+  const AttrRecords R = {n_records, label};
+  return sf_hist_entry(c, "vgs_get_own_segment_class_counts", false, K, cls_host, n_own, n_classes, &R, {hist, n_outside, nullptr, nullptr});
+}
+
+extern "C" vgs_status vgs_get_own_segment_class_counts_device(vgs_ctx* c, int64_t K, const int32_t* cls_dev, int64_t n_own, int32_t n_classes,
+                                                              int64_t* n_records, int32_t* label, int64_t* hist, int64_t* n_outside) {
+  const AttrRecords R = {n_records, label};
+  return sf_hist_entry(c, "vgs_get_own_segment_class_counts_device", true, K, cls_dev, n_own, n_classes, &R, {hist, n_outside, nullptr, nullptr});
 }
 
 // The table from moments folded over the ranks: one partial record per (segment, channel) and seg_chunk[k] = k, so k_sf_final itself runs
@@ -552,10 +447,8 @@ extern "C" vgs_status vgs_segment_field_stats_from_moments(vgs_ctx* c, int64_t K
                                                            const double* s1, const double* s2, const float* vmin, const float* vmax, double* mean,
                                                            double* var, float* vmin_out, float* vmax_out) {
   if (!c || K < 0 || K >= (int64_t)0xffffffffLL) return VGS_E_ARG;
-  if (n_channels < 1 || n_channels > 64) {
-    c->err = "vgs_segment_field_stats_from_moments: n_channels = " + std::to_string(n_channels) + " must be in 1 .. 64";
-    return VGS_E_ARG;
-  }
+  vgs_status s = attr_check_channels(c, "vgs_segment_field_stats_from_moments", n_channels);
+  if (s != VGS_OK) return s;
   if (K > 0 && (!n_valid || !anchor || !s1 || !s2 || !vmin || !vmax)) { c->err = "vgs_segment_field_stats_from_moments: an input array is NULL"; return VGS_E_ARG; }
   if (K == 0) return VGS_OK;
   VGS_HIP_TRY(c, hipSetDevice(c->device));
@@ -571,8 +464,7 @@ extern "C" vgs_status vgs_segment_field_stats_from_moments(vgs_ctx* c, int64_t K
   std::vector<uint32_t> idx(k + 1);
   for (size_t i = 0; i <= k; ++i) idx[i] = (uint32_t)i;
   VGS_HIP_TRY(c, c->sf_part.ensure(part.size())); VGS_HIP_TRY(c, c->sf_idx.ensure(idx.size()));
-  VGS_HIP_TRY(c, c->sf_anchor.ensure(kc)); VGS_HIP_TRY(c, c->sf_mean.ensure(kc)); VGS_HIP_TRY(c, c->sf_var.ensure(kc));
-  VGS_HIP_TRY(c, c->sf_nvalid.ensure(kc)); VGS_HIP_TRY(c, c->sf_min.ensure(kc)); VGS_HIP_TRY(c, c->sf_max.ensure(kc));
+  if ((s = attr_ensure_field_rows(c, kc)) != VGS_OK) return s;
   VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_part.p, part.data(), part.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_anchor.p, anchor, kc * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -582,84 +474,7 @@ extern "C" vgs_status vgs_segment_field_stats_from_moments(vgs_ctx* c, int64_t K
                     c->sf_var.p, c->sf_min.p, c->sf_max.p);
   }
   VGS_HIP_TRY(c, hipGetLastError());
-  if (mean) VGS_HIP_TRY(c, hipMemcpyAsync(mean, c->sf_mean.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (var) VGS_HIP_TRY(c, hipMemcpyAsync(var, c->sf_var.p, kc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (vmin_out) VGS_HIP_TRY(c, hipMemcpyAsync(vmin_out, c->sf_min.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (vmax_out) VGS_HIP_TRY(c, hipMemcpyAsync(vmax_out, c->sf_max.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the staged records and the caller's anchor are free again as well)
-  return VGS_OK;
-}
-
-static vgs_status sft_check_counts(vgs_ctx* c, const char* fn, int64_t K, const int32_t* cls, int64_t n_own, int32_t n_classes) {
-  vgs_status s = sft_check_state(c, fn);
-  if (s != VGS_OK) return s;
-  if (K < 0 || K >= (int64_t)0xffffffffLL) { c->err = std::string(fn) + ": K = " + std::to_string(K) + " is out of range"; return VGS_E_ARG; }
-  if ((s = sft_check_n(c, fn, cls, n_own)) != VGS_OK) return s;
-  if (n_classes < 1 || n_classes > 1024) {
-    c->err = std::string(fn) + ": n_classes = " + std::to_string(n_classes) + " must be in 1 .. 1024";
-    return VGS_E_ARG;
-  }
-  if (K * (int64_t)n_classes > ((int64_t)1 << 27)) {
-    c->err = std::string(fn) + ": " + std::to_string(K) + " segments x " + std::to_string(n_classes) + " classes = " +
-             std::to_string(K * (int64_t)n_classes) + " counters exceed the table's limit of 2^27 = " + std::to_string((int64_t)1 << 27);
-    return VGS_E_UNSUPPORTED;
-  }
-  return VGS_OK;
-}
-
-// this rank's class counts of the global labels 0 .. K-1 over its own points, from a device buffer: dense on the device, compact on the host
-static vgs_status sft_class_counts(vgs_ctx* c, int64_t K, const int32_t* cls_dev, int32_t n_classes, int64_t* n_records, int32_t* label,
-                                   int64_t* hist, int64_t* n_outside) {
-  *n_records = 0;
-  if (K == 0 || c->V == 0 || c->Nf == 0) return VGS_OK;
-  const size_t k = (size_t)K, nc = (size_t)n_classes, kc = k * nc;
-  SdPrep P;
-  vgs_status s = sd_prepare(c, K, P);
-  if (s != VGS_OK) return s;
-  VGS_HIP_TRY(c, c->sf_hist.ensure(kc + 2 * k));
-  int64_t *d_hist = c->sf_hist.p, *d_out = d_hist + kc;
-  VGS_HIP_TRY(c, hipMemsetAsync(d_hist, 0, (kc + k) * sizeof(int64_t), c->stream));
-  if ((s = sd_own_anchor(c, K, P)) != VGS_OK) return s;
-  hipLaunchKernelGGL(k_sf_hist_own, dim3((unsigned)P.n_chunks_max), dim3(SD_TB), 0, c->stream, cls_dev, (uint32_t)n_classes, c->perm_b.p,
-                     c->vox_start.p, P.ids, P.vp, P.seg_node, P.seg_chunk, (uint32_t)K, (unsigned long long*)d_hist, (unsigned long long*)d_out,
-                     c->own_first, c->own_first + c->n_own);
-  VGS_HIP_TRY(c, hipGetLastError());
-  std::vector<uint32_t> apos(k);
-  std::vector<int64_t> h(kc + k);
-  VGS_HIP_TRY(c, hipMemcpyAsync(apos.data(), c->sd_apos.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipMemcpyAsync(h.data(), d_hist, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  std::vector<int64_t> rows;
-  sft_own_labels(apos, rows);
-  for (size_t i = 0; i < rows.size(); ++i) {
-    const size_t r = (size_t)rows[i];
-    if (label) label[i] = (int32_t)r;
-    if (hist) std::copy(h.begin() + r * nc, h.begin() + (r + 1) * nc, hist + i * nc);
-    if (n_outside) n_outside[i] = h[kc + r];
-  }
-  *n_records = (int64_t)rows.size();
-  return VGS_OK;
-}
-
-extern "C" vgs_status vgs_get_own_segment_class_counts_device(vgs_ctx* c, int64_t K, const int32_t* cls_dev, int64_t n_own, int32_t n_classes,
-                                                              int64_t* n_records, int32_t* label, int64_t* hist, int64_t* n_outside) {
-  if (!c || !n_records) return VGS_E_ARG;
-  vgs_status s = sft_check_counts(c, "vgs_get_own_segment_class_counts_device", K, cls_dev, n_own, n_classes);
-  if (s != VGS_OK) return s;
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  return sft_class_counts(c, K, cls_dev, n_classes, n_records, label, hist, n_outside);
-}
-
-extern "C" vgs_status vgs_get_own_segment_class_counts(vgs_ctx* c, int64_t K, const int32_t* cls_host, int64_t n_own, int32_t n_classes,
-                                                       int64_t* n_records, int32_t* label, int64_t* hist, int64_t* n_outside) {
-  if (!c || !n_records) return VGS_E_ARG;
-  vgs_status s = sft_check_counts(c, "vgs_get_own_segment_class_counts", K, cls_host, n_own, n_classes);
-  if (s != VGS_OK) return s;
-  *n_records = 0;
-  if (K == 0 || n_own == 0) return VGS_OK;   // (no own point: no record)
-  VGS_HIP_TRY(c, hipSetDevice(c->device));
-  VGS_HIP_TRY(c, c->sf_cls.ensure((size_t)n_own));
-  VGS_HIP_TRY(c, hipMemcpyAsync(c->sf_cls.p, cls_host, (size_t)n_own * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the caller's array is free again, whatever follows
-  return sft_class_counts(c, K, c->sf_cls.p, n_classes, n_records, label, hist, n_outside);
+  const RowCol col[4] = {{mean, c->sf_mean.p, C * sizeof(double)}, {var, c->sf_var.p, C * sizeof(double)},
+                          {vmin_out, c->sf_min.p, C * sizeof(float)}, {vmax_out, c->sf_max.p, C * sizeof(float)}};
+  return vgs_copy_rows(c, k, col, 4);   // (its wait frees the staged records and the caller's anchor as well)
 }

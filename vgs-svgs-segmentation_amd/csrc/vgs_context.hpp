@@ -498,6 +498,15 @@ static inline vgs_status vgs_readback_on(vgs_ctx* c, hipStream_t s, void* dst, c
   memcpy(dst, c->pin, bytes);
   return VGS_OK;
 }
+// Optional outputs of a getter: one column is the host destination (NULL: not wanted), its rows in HBM and the bytes of a row.
+// vgs_copy_rows copies n_rows rows of every wanted column and waits for the stream once.
+struct RowCol { void* dst; const void* src; size_t row_bytes; };
+static inline vgs_status vgs_copy_rows(vgs_ctx* c, size_t n_rows, const RowCol* col, int n_col) {
+  for (int i = 0; i < n_col; ++i)
+    if (col[i].dst) VGS_HIP_TRY(c, hipMemcpyAsync(col[i].dst, col[i].src, n_rows * col[i].row_bytes, hipMemcpyDeviceToHost, c->stream));
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return VGS_OK;
+}
 // Longest row of connect bits the kernels hold in LDS: 624 words = a cube of 27 cells a side = balls of up to 13 voxels (the edge list of
 // the smallest one-wavefront class, 312 keys of 8 bytes, is where its row is put together).  Wider balls (up to the engine's own limit
 // of graph_size / voxel_size = 12 ... 15 by rounding) keep crossValidation's search in the neighbour's row.  (Round 4: 256 words, 9 voxels --
