@@ -67,6 +67,22 @@ inline int writeBoxesCsv(const std::string& path, const std::vector<pcl::Cluster
   return std::fclose(f) == 0 ? 0 : -1;
 }
 
+// the same rows for the parts of a labelling over the ranks of the tiled driver (vgs_tiles_get_point_label_components): the shared-grid code
+// of the part's first node in place of the node id, which means nothing across ranks
+inline int writeTileComponentsCsv(const std::string& path, const std::vector<int32_t>& part_label, const std::vector<int64_t>& part_points,
+                                  const std::vector<int32_t>& part_nodes, const std::vector<uint64_t>& part_first_code,
+                                  const std::vector<int32_t>& label_largest) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "part,label,n_points,n_nodes,first_code,largest\n");
+  for (size_t p = 0; p < part_label.size(); ++p) {
+    const int32_t l = part_label[p];
+    const bool largest = l >= 0 && (size_t)l < label_largest.size() && label_largest[(size_t)l] == (int32_t)p;
+    std::fprintf(f, "%zu,%d,%lld,%d,%llu,%d\n", p, (int)l, (long long)part_points[p], (int)part_nodes[p], (unsigned long long)part_first_code[p], largest ? 1 : 0);
+  }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
 // one row per connected part of a labelling (getLabelComponents), in part order: part, label, n_points, n_nodes, first_node, and
 // largest = 1 for the part with the most points of its label
 inline int writeComponentsCsv(const std::string& path, const pcl::LabelComponents& c) {

@@ -39,6 +39,11 @@
 //   labels and its rows to vgs_tiles_point_label_field_stats / vgs_tiles_point_label_class_histogram (collectives; nothing of a point
 //   leaves its rank) and rank 0 writes the files, with the columns of vgs_run's --refined-segment-fields / --refined-segment-classes.
 //   --field-channels and --classes serve the node option and the refined one alike.
+//   --refined-components <file.csv> (needs --refine), --class-components <file.csv> --classes <C> (over <prefix>.<r>.classes.i32): the
+//   connected parts of the refined labels, or of the classes, over all ranks -- every rank hands its labels to
+//   vgs_tiles_point_label_components (two collectives; no label leaves its rank) and rank 0 writes one row per part with the columns of
+//   vgs_run's --refined-components / --class-components, the shared-grid code of the part's first node (first_code) in place of the node.
+//   --component-ids: every rank also writes the part of each of its points to <prefix>.<r>.parts.i32; it serves exactly one of the two.
 //   All of them can be combined.  A missing companion option, a value out of range (1 .. 64 channels, 1 .. 1024 classes) and an attribute
 //   or truth file that is missing or whose size does not match the rank's points are usage errors: exit status 2, before any collective.
 #include <arpa/inet.h>
@@ -106,6 +111,8 @@ struct Job {
   std::string matches, truth_matches;   // --segment-matches / --truth-matches
   std::string r_segments, r_boxes, r_matches, r_truth_matches;   // --refined-segments / --refined-segment-boxes / --refined-matches / --refined-truth-matches
   std::string r_fields, r_classes;    // --refined-segment-fields / --refined-segment-classes
+  std::string r_parts, c_parts;       // --refined-components / --class-components
+  bool part_ids = false;              // --component-ids
   bool refine = false, refine_fill = true;   // --refine, --no-fill
   float patch_radius = -1.0f, switch_ratio = -1.0f;   // --patch-radius / --switch-ratio (negative: the context's default)
 };
@@ -126,7 +133,7 @@ static int check_attribute_files(const Job& J, int rank) {
       return 2;
     }
   }
-  if (!J.classes.empty() || !J.r_classes.empty()) {
+  if (!J.classes.empty() || !J.r_classes.empty() || !J.c_parts.empty()) {
     const std::string path = rank_file(J, rank, ".classes.i32");
     const long long b = file_bytes(path);
     if (b != n * 4) { std::fprintf(stderr, "%s: %lld bytes, but %lld points x 4 = %lld\n", path.c_str(), b, n, n * 4); return 2; }
@@ -217,6 +224,23 @@ static std::string write_matches(vgs_tiles* t, int64_t nc, int64_t G, int64_t K,
   return "";
 }
 
+// The connected parts of a labelling of this rank's points with K labels: two collectives of every rank, the same table on each; rank 0
+// writes the CSV, every rank its part ids when asked.  "" on success.
+static std::string write_components(vgs_tiles* t, const Job& J, int rank, const std::vector<int32_t>& lab, int64_t n, int64_t K, const std::string& path) {
+  int64_t C = 0, skipped = 0;
+  if (vgs_tiles_point_label_components(t, lab.data(), n, K, &C, &skipped) != VGS_OK) return std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+  const size_t c = (size_t)C, k = (size_t)K;
+  std::vector<int32_t> ids((size_t)n + 1), pl(c + 1), pn(c + 1), ll(k + 1);
+  std::vector<int64_t> pp(c + 1), lf(k + 2);
+  std::vector<uint64_t> pc(c + 1);
+  if (vgs_tiles_get_point_label_components(t, ids.data(), pl.data(), pp.data(), pn.data(), pc.data(), lf.data(), ll.data()) != VGS_OK)
+    return std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+  pl.resize(c); pp.resize(c); pn.resize(c); pc.resize(c); ll.resize(k); ids.resize((size_t)n);
+  if (rank == 0 && writeTileComponentsCsv(path, pl, pp, pn, pc, ll) != 0) return "cannot write " + path;
+  if (J.part_ids && !write_i32(rank_file(J, rank, ".parts.i32"), ids)) return "cannot write the part ids";
+  return "";
+}
+
 // one rank: load, run, save; returns 0 on success
 static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world, int64_t* kept, int64_t* n_pts, int64_t* n_rec, int64_t* refine_counts /* 5 */, std::string* err) {
   std::vector<float> xyz;
@@ -224,7 +248,7 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
   std::vector<float> field;
   std::vector<int32_t> cls;
   if ((!J.fields.empty() || !J.r_fields.empty()) && !read_f32(rank_file(J, rank, ".fields.f32"), field)) { *err = "cannot read the fields of rank " + std::to_string(rank); return 1; }
-  if ((!J.classes.empty() || !J.r_classes.empty()) && !read_i32(rank_file(J, rank, ".classes.i32"), cls)) { *err = "cannot read the classes of rank " + std::to_string(rank); return 1; }
+  if ((!J.classes.empty() || !J.r_classes.empty() || !J.c_parts.empty()) && !read_i32(rank_file(J, rank, ".classes.i32"), cls)) { *err = "cannot read the classes of rank " + std::to_string(rank); return 1; }
   std::vector<int32_t> truth;
   if ((!J.matches.empty() || !J.r_matches.empty()) && !read_i32(rank_file(J, rank, ".truth.i32"), truth)) { *err = "cannot read the truth ids of rank " + std::to_string(rank); return 1; }
   vgs_tiles* t = nullptr;
@@ -376,6 +400,16 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
         rc = 1;
       } else if (rank == 0 && write_class_hist(J.r_classes, k, nc, A) != 0) { *err = "cannot write " + J.r_classes; rc = 1; }
     }
+    if (rc == 0 && !J.r_parts.empty()) {
+      fine.resize((size_t)n + 1);
+      const std::string e = write_components(t, J, rank, fine, n, *kept, J.r_parts);
+      if (!e.empty()) { *err = e; rc = 1; }
+    }
+  }
+  if (rc == 0 && !J.c_parts.empty()) {
+    cls.resize((size_t)n + 1);
+    const std::string e = write_components(t, J, rank, cls, n, J.n_classes, J.c_parts);
+    if (!e.empty()) { *err = e; rc = 1; }
   }
   if (rc == 0) {
     labels.resize((size_t)n);
@@ -425,7 +459,7 @@ static bool exchange_id(ncclUniqueId* id, int rank, int world, const char* addr,
 }
 
 static void print_usage(const char* exe) {
-  std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] [--refine [--patch-radius r] [--switch-ratio s] [--no-fill] [--refined-segments file.csv] [--refined-segment-boxes file.csv] [--refined-matches file.csv [--refined-truth-matches file.csv]] [--refined-segment-fields file.csv --field-channels C] [--refined-segment-classes file.csv --classes C]] <prefix>\n", exe);
+  std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] [--refine [--patch-radius r] [--switch-ratio s] [--no-fill] [--refined-segments file.csv] [--refined-segment-boxes file.csv] [--refined-matches file.csv [--refined-truth-matches file.csv]] [--refined-segment-fields file.csv --field-channels C] [--refined-segment-classes file.csv --classes C] [--refined-components file.csv]] [--class-components file.csv --classes C] [--component-ids] <prefix>\n", exe);
 }
 
 int main(int argc, char** argv) {
@@ -463,6 +497,9 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--refined-truth-matches") && a + 1 < argc) J.r_truth_matches = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-segment-fields") && a + 1 < argc) J.r_fields = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-segment-classes") && a + 1 < argc) J.r_classes = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-components") && a + 1 < argc) J.r_parts = argv[++a];
+    else if (!std::strcmp(argv[a], "--class-components") && a + 1 < argc) J.c_parts = argv[++a];
+    else if (!std::strcmp(argv[a], "--component-ids")) J.part_ids = true;
     else if (!std::strcmp(argv[a], "--refine")) J.refine = true;
     else if (!std::strcmp(argv[a], "--no-fill")) { J.refine_fill = false; refine_opts = true; }
     else if ((!std::strcmp(argv[a], "--patch-radius") || !std::strcmp(argv[a], "--switch-ratio")) && a + 1 < argc) {
@@ -486,14 +523,21 @@ int main(int argc, char** argv) {
   if (have_channels && (J.field_channels < 1 || J.field_channels > 64)) { std::fprintf(stderr, "--field-channels must be in 1 .. 64\n"); return 2; }
   if (!J.classes.empty() && !have_classes) { std::fprintf(stderr, "--segment-classes needs --classes <C>\n"); return 2; }
   if (!J.r_classes.empty() && !have_classes) { std::fprintf(stderr, "--refined-segment-classes needs --classes <C>\n"); return 2; }
-  if (J.classes.empty() && J.r_classes.empty() && have_classes) { std::fprintf(stderr, "--classes needs --segment-classes <file.csv>\n"); return 2; }
-  if (have_classes && (J.n_classes < 1 || J.n_classes > 1024)) { std::fprintf(stderr, "--classes must be in 1 .. 1024\n"); return 2; }
+  if (!J.c_parts.empty() && !have_classes) { std::fprintf(stderr, "--class-components needs --classes <C>\n"); print_usage(argv[0]); return 2; }
+  if (J.classes.empty() && J.r_classes.empty() && J.c_parts.empty() && have_classes) { std::fprintf(stderr, "--classes needs --segment-classes <file.csv>\n"); return 2; }
+  if (have_classes && (J.n_classes < 1 || J.n_classes > 1024)) { std::fprintf(stderr, "--classes must be in 1 .. 1024\n"); print_usage(argv[0]); return 2; }
+  if (J.part_ids && J.r_parts.empty() == J.c_parts.empty()) {
+    std::fprintf(stderr, J.r_parts.empty() ? "--component-ids needs --refined-components or --class-components\n"
+                                           : "--component-ids serves one table: exactly one of --refined-components and --class-components\n");
+    print_usage(argv[0]);
+    return 2;
+  }
   if (J.matches.empty() && !J.truth_matches.empty()) { std::fprintf(stderr, "--truth-matches needs --segment-matches <file.csv>\n"); return 2; }
   if (refine_opts && !J.refine) { std::fprintf(stderr, "--patch-radius / --switch-ratio / --no-fill need --refine\n"); return 2; }
   if (!J.refine && (!J.r_segments.empty() || !J.r_boxes.empty() || !J.r_matches.empty() || !J.r_truth_matches.empty() || !J.r_fields.empty() ||
-                    !J.r_classes.empty())) {
+                    !J.r_classes.empty() || !J.r_parts.empty())) {
     std::fprintf(stderr, "--refined-segments / --refined-segment-boxes / --refined-matches / --refined-truth-matches / --refined-segment-fields / "
-                         "--refined-segment-classes need --refine\n");
+                         "--refined-segment-classes / --refined-components need --refine\n");
     print_usage(argv[0]);
     return 2;
   }

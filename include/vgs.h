@@ -762,7 +762,7 @@ vgs_status vgs_refine_own_point_labels(vgs_ctx* ctx, const vgs_refine_params* rp
  * NULL; vgs_get_point_label_components_device hands out the device pointers (NULL for a table without rows).  Both are valid until the
  * next vgs_point_label_components or the next run of the stages, and answer VGS_E_STATE without a result since the last run.
  * VGS_E_STATE before the context is segmented, and for a tile context: it holds part of the cloud and of the graph only, and parts
- * across the ranks of the tiled driver are not computed.  VGS_E_ARG for n != N, a NULL labelling, K outside 0 .. 2^31 - 1. */
+ * across the ranks of the tiled driver are not computed by this call (vgs_tiles_point_label_components, include/vgs_tiles.h, is).  VGS_E_ARG for n != N, a NULL labelling, K outside 0 .. 2^31 - 1. */
 vgs_status vgs_point_label_components(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_skipped);
 vgs_status vgs_point_label_components_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_skipped);
 vgs_status vgs_get_point_label_components(vgs_ctx* ctx, int32_t* part_of_point, int32_t* part_label, int64_t* part_points, int32_t* part_nodes,
@@ -770,6 +770,37 @@ vgs_status vgs_get_point_label_components(vgs_ctx* ctx, int32_t* part_of_point, 
 vgs_status vgs_get_point_label_components_device(vgs_ctx* ctx, const int32_t** part_of_point, const int32_t** part_label,
                                                  const int64_t** part_points, const int32_t** part_nodes, const int32_t** part_first_node,
                                                  const int64_t** label_first, const int32_t** label_largest);
+/* Tile contexts (vgs_set_owned_region and vgs_set_own_point_range; VGS only): a rank's share of the connected parts of a labelling over
+ * all ranks of the tiled driver.  include/vgs_tiles.h (vgs_tiles_point_label_components) states the definition and the protocol these
+ * four steps serve; csrc/labelcc_tiles.hip has the kernels.  Every call answers VGS_E_STATE on a plain context and before a run.
+ * vgs_own_point_label_parts[_device]: `labels` holds one int32 per point of the rank's OWN load (labels[i] belongs to cloud point
+ * own_first + i, n must equal the own range's length; label rules as vgs_own_point_label_moments).  The pass of
+ * vgs_point_label_components over the own points alone: the LOCAL parts, numbered in ascending (label, smallest local node id), and
+ * the BAND records -- (voxel code, label, local part) of every own vertex whose node centre lies within graph_size + voxel_size of a
+ * border line of the owned region (an infinite border never matches), in ascending (label, node) order.  n_parts, n_band, n_skipped may
+ * be NULL.  The rows of an own vertex's node are complete on the rank when its points were loaded by region (include/vgs_tiles.h).
+ * vgs_get_own_point_label_parts copies out, per local part, label, points, nodes and the shared-grid code of its first node, and the
+ * band records; any pointer may be NULL.
+ * vgs_link_point_label_parts: the OTHER ranks' band records (code, label, rank, part; host arrays of n entries, any order).  A code this
+ * context does not hold drops out.  For every own band vertex (l, v) and every neighbour w != v in v's adjacency row (stored, or built
+ * on request for an unused voxel) every record (code of w, l, s, p) gives the triple (own local part, s, p).  The triples are sorted and
+ * unique; vgs_get_point_label_part_links copies them out (*n_links entries each).  The equal key itself (w = v, a voxel with points of
+ * two ranks) is not a link: the driver's fold unites equal (code, label) keys.
+ * vgs_apply_point_label_part_ids: `map` gives the global part of every local part (n = the own call's *n_parts); one gather writes the
+ * part id of every own point, in the order of the rank's load, -1 for a point without a part.  vgs_get_point_label_part_ids copies
+ * them out (n = the own range's length), the _device variant hands out the device pointer (NULL without own points).
+ * All results stay until the next vgs_own_point_label_parts or the next run of the stages. */
+vgs_status vgs_own_point_label_parts(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_band, int64_t* n_skipped);
+vgs_status vgs_own_point_label_parts_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_band,
+                                            int64_t* n_skipped);
+vgs_status vgs_get_own_point_label_parts(vgs_ctx* ctx, int32_t* part_label, int64_t* part_points, int32_t* part_nodes, uint64_t* part_first_code,
+                                         uint64_t* band_code, int32_t* band_label, int32_t* band_part);
+vgs_status vgs_link_point_label_parts(vgs_ctx* ctx, const uint64_t* code, const int32_t* label, const int32_t* rank, const int32_t* part, int64_t n,
+                                      int64_t* n_links);
+vgs_status vgs_get_point_label_part_links(vgs_ctx* ctx, int32_t* own_part, int32_t* rank, int32_t* part);
+vgs_status vgs_apply_point_label_part_ids(vgs_ctx* ctx, const int32_t* map, int64_t n);
+vgs_status vgs_get_point_label_part_ids(vgs_ctx* ctx, int32_t* part_of_point, int64_t n);
+vgs_status vgs_get_point_label_part_ids_device(vgs_ctx* ctx, const int32_t** part_of_point);
 
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.

@@ -432,6 +432,71 @@ vgs_status vgs_tiles_get_point_label_times(vgs_tiles* t, double* ms, int32_t n /
 /* that call's payload on this rank: moment records and pair records of its own, bytes it put into the all-gathers (headers included,
  * before padding) */
 vgs_status vgs_tiles_get_point_label_payload(vgs_tiles* t, int64_t* own_records, int64_t* own_pairs, int64_t* bytes_sent);
+/* Connected parts of ANY per-point labelling the caller supplies, over all ranks: is a refined segment, or a semantic class, of a scene
+ * larger than one GPU one object or several?  A part that crosses a tile border is invisible to any single rank.
+ * Definition: that of vgs_point_label_components (include/vgs.h) over the whole scene; the nodes are the voxels of the shared grid.
+ *   Vertices.  The distinct pairs (label, voxel code) with at least one point, on any rank, that carries the label in that voxel.  A voxel
+ *     that holds points of several ranks under the same label is ONE vertex.
+ *   Edges.  As on one context: (l, v) and (l, w) are joined when w is in v's adjacency row or v in w's.
+ *   Numbering.  Ascending (label, smallest node id of the part).  Every rank numbers voxels in descending code order, so this is ascending
+ *     label, then DESCENDING largest voxel code of the part.
+ * The result equals what one context's vgs_point_label_components gives on the gathered points (the ranks' loads concatenated in rank
+ * order, the order the shared grid is chained in): part_of_point concatenated over the ranks, part_label, part_points, part_nodes,
+ * label_first, label_largest, n_parts and n_skipped (the sum over the ranks).  part_first_node means nothing across ranks; the table gives
+ * part_first_code instead, the shared-grid code of that node.  Everything is integer; every rank receives the same bytes, bit-identical
+ * from call to call and from run to run.  labels: one int32 per point the rank gave to vgs_tiles_set_points, in that order; n must equal
+ * that call's n; label rules as vgs_tiles_point_label_descriptors.  The _device variant reads the labels from HBM in place.
+ * Precondition, as for vgs_tiles_refine_point_labels and n_nodes: the points are loaded by region.  Outside it the rows of a node further
+ * outside the rank's region than graph_size are not complete on the rank, and a part may come apart there.
+ * Protocol (csrc/tiles.cpp, csrc/labelcc_tiles.hip): TWO all_gather_varlen of 8-byte words per call, K = 0 included; nothing is cached.
+ *   1. Own parts on each rank's GPU (vgs_own_point_label_parts): the pass of one context over the rank's own points.  Complete because an
+ *      own vertex's node holds an own point, so its cube meets the region; its row ends within graph_size + voxel_size of the border,
+ *      inside the halo of 2 graph_size + voxel_size.
+ *   2. Exchange 1: a header of four words (status word, band count, K, own n_skipped), then two words a BAND record (code; label << 32 |
+ *      local part).  The band: the own vertices whose node centre lies within near = graph_size + voxel_size of a border line of the
+ *      region.  That is enough: a vertex w of another rank adjacent to v holds a point of that rank's region, so w's centre is outside
+ *      this region or at most half a voxel inside it, and v is within graph_size of it per axis.  Outer tiles are open ended, and an
+ *      infinite border never matches.
+ *   3. Cross links on each rank's GPU (vgs_link_point_label_parts) over the OTHER ranks' band records: for every own band vertex (l, v) and
+ *      every neighbour w != v of v's row, one triple (own local part, rank, part) for every record with key (l, w); sorted and unique.
+ *      Each rank walks only the rows of its own vertices, which are complete on it: r finds w in row(v), s finds v in row(w), and the
+ *      union over the ranks is the "either row" rule.  A stored row pruned to used neighbours is covered by the other side's full row.
+ *   4. Exchange 2: a header of four words (status word -- a failure of step 3 travels here --, part count, link count, K), three words a
+ *      local part (label << 32 | nodes; points; code of its first node), two words a link (own part << 32 | rank; part).
+ *   5. The same host fold on every rank (vgs_tiles_fold_label_parts): a union-find over (rank, local part), united along the links and
+ *      along EQUAL (code, label) keys among the band records of different ranks -- the shared voxel, which always lies in both bands.  A key
+ *      with m records is one node: m - 1 comes off the merged part's node count.  Label, points (sum), nodes (sum - surplus), first code
+ *      (max); sorted by (label ascending, first code descending); label_first; label_largest (most points, lowest id on a tie).
+ *   6. vgs_apply_point_label_part_ids: one gather writes the part id of every own point, in the order of the rank's load.
+ * The result is kept, like the refined labels, until the next call, the next run or the next vgs_tiles_set_points;
+ * vgs_tiles_get_point_label_components copies it out (part_of_point: n entries of this rank; the tables: n_parts rows, K + 1 and K
+ * rows); any pointer may be NULL; it is not collective and answers VGS_E_STATE without a result.  vgs_tiles_run gains no launch and no
+ * collective; the call invalidates no cached descriptor, box or graph table, no refine halo table, not the refined labels, and does not
+ * change the last comparison.
+ * Failures: the contract of vgs_tiles_point_label_descriptors.  VGS_E_STATE before a run is decided locally (no collective).  A wrong n, a
+ * NULL labelling, K out of range, a label >= K (the message names the first offending index and its value), a failing context call and
+ * the injected VGS_TILES_FAIL_AT=components travel in the status word of exchange 1: the failing rank returns its own status and message,
+ * the others VGS_E_PEER naming it.  Ranks that are each valid but disagree on K all return VGS_E_ARG behind exchange 1. */
+vgs_status vgs_tiles_point_label_components(vgs_tiles* t, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_skipped);
+vgs_status vgs_tiles_point_label_components_device(vgs_tiles* t, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_skipped);
+vgs_status vgs_tiles_get_point_label_components(vgs_tiles* t, int32_t* part_of_point /* n */, int32_t* part_label, int64_t* part_points,
+                                                int32_t* part_nodes, uint64_t* part_first_code, int64_t* label_first, int32_t* label_largest);
+/* host arithmetic only, no context (tests): step 5 on flattened per-rank records, rank r's entries being off[r] .. off[r + 1] of the local
+ * parts, the band records and the links.  map: the global part of every local part (part_off[world] entries); the out_ tables hold at
+ * most part_off[world] rows, *n_parts of them written; label_first K + 1 and label_largest K rows.  Any output may be NULL.  VGS_E_ARG
+ * for a label outside 0 .. K-1, a link or band record naming a part that does not exist, or a link between different labels. */
+vgs_status vgs_tiles_fold_label_parts(int world, int64_t K, const int64_t* part_off, const int32_t* part_label, const int64_t* part_points,
+                                      const int32_t* part_nodes, const uint64_t* part_first_code, const int64_t* band_off, const uint64_t* band_code,
+                                      const int32_t* band_label, const int32_t* band_part, const int64_t* link_off, const int32_t* link_own,
+                                      const int32_t* link_rank, const int32_t* link_part, int64_t* n_parts, int32_t* map, int32_t* out_label,
+                                      int64_t* out_points, int32_t* out_nodes, uint64_t* out_first_code, int64_t* label_first, int32_t* label_largest);
+/* host wall time of the last components call on this rank, milliseconds: own parts on the GPU (with upload and download), exchange 1,
+ * the link step on the GPU, exchange 2, the host fold, the part ids on the GPU, total */
+enum { VGS_TILES_CC_OWN = 0, VGS_TILES_CC_EXCHANGE1 = 1, VGS_TILES_CC_LINK = 2, VGS_TILES_CC_EXCHANGE2 = 3, VGS_TILES_CC_FOLD = 4, VGS_TILES_CC_APPLY = 5,
+       VGS_TILES_CC_TOTAL = 6, VGS_TILES_CC_COUNT = 7 };
+vgs_status vgs_tiles_get_point_label_component_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_CC_COUNT */);
+/* that call's payload on this rank: band records, local parts and link triples of its own, bytes it put into the two all-gathers */
+vgs_status vgs_tiles_get_point_label_component_payload(vgs_tiles* t, int64_t* band_records, int64_t* parts, int64_t* links, int64_t* bytes_sent);
 /* the rank's engine context (read-only use: counts, stage times) */
 vgs_ctx* vgs_tiles_context(vgs_tiles* t);
 

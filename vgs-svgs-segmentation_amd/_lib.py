@@ -157,6 +157,14 @@ SYMBOLS = [
     ("vgs_refine_own_point_labels", C.c_int, [_P, C.POINTER(VgsRefineParams), _P]),
     ("vgs_point_label_components", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
     ("vgs_point_label_components_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("vgs_own_point_label_parts", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
+    ("vgs_own_point_label_parts_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
+    ("vgs_get_own_point_label_parts", C.c_int, [_P] * 8),
+    ("vgs_link_point_label_parts", C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P]),
+    ("vgs_get_point_label_part_links", C.c_int, [_P] * 4),
+    ("vgs_apply_point_label_part_ids", C.c_int, [_P, _P, C.c_int64]),
+    ("vgs_get_point_label_part_ids", C.c_int, [_P, _P, C.c_int64]),
+    ("vgs_get_point_label_part_ids_device", C.c_int, [_P, _P]),
     ("vgs_get_point_label_components", C.c_int, [_P] + [_P] * 7),
     ("vgs_get_point_label_components_device", C.c_int, [_P] + [_P] * 7),
     ("vgs_grid_state_init", C.c_int, [C.POINTER(VgsGridState)]),

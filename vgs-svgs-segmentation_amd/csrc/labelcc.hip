@@ -44,6 +44,9 @@
 // rows) stays until the next call or the next run of the stages (lcc_valid).  Scratch: the sort's 16 B per finite point (ps_*), 8 B per
 // finite point of head flags and their scan, 24 B per vertex (+ 4 B flags and 4 B scan per vertex), 8 B per node (nlo | nhi), 8 B per label,
 // refine.hip's row chunk.
+// Tile contexts: the calls of include/vgs.h refuse them (a tile holds part of the cloud and of the graph), but the pass itself runs over a
+// tile's OWN points as step 1 of the parts across the ranks of the tiled driver (vgs_label_parts_on_device with the own point range;
+// labelcc_tiles.hip reads the vertex arrays it leaves in lcc_vtx and adds the band, the cross links and the global ids).
 // (The context's lc_* members belong to the local cut, hence lcc_*.)
 #include <string.h>
 
@@ -312,13 +315,17 @@ static vgs_status lc_check(vgs_ctx* c, const char* fn, const int32_t* labels, in
   return VGS_OK;
 }
 
-static vgs_status lc_on_device(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t K, int64_t* n_parts, int64_t* n_skipped) {
+// The pass over labels_dev: n_lab entries for the input indices own_first .. own_first + n_lab - 1 (one context: 0 and N; a tile context, for
+// labelcc_tiles.hip: its own point range -- k_ps_keys gives every other position the key K, so the vertices are those of own points only).
+// The vertex arrays stay in lcc_vtx (lcc_nv vertices, six arrays of lcc_nv + 1 words: LcVtx) until the next call.
+vgs_status vgs_label_parts_on_device(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t own_first, int64_t n_lab, int64_t K, int64_t* n_parts,
+                                     int64_t* n_skipped) {
   const int64_t N = c->N, nf = c->Nf, V = c->V, U = c->U;
   const size_t k = (size_t)K;
-  c->lcc_valid = false;
+  c->lcc_valid = false; c->lcc_nv = 0; c->lct_own = c->lct_linked = c->lct_applied = false;
   VGS_HIP_TRY(c, c->lcc_pop.ensure(N > 0 ? (size_t)N : 1)); VGS_HIP_TRY(c, c->lcc_lfirst.ensure(k + 1)); VGS_HIP_TRY(c, c->lcc_llargest.ensure(k + 1));
   PsSort S;
-  vgs_status s = ps_sort_points(c, fn, labels_dev, 0, N, K, 0, n_skipped, S);
+  vgs_status s = ps_sort_points(c, fn, labels_dev, own_first, n_lab, K, 0, n_skipped, S);
   if (s != VGS_OK) return s;
   if (N > 0) VGS_HIP_TRY(c, hipMemsetAsync(c->lcc_pop.p, 0xff, (size_t)N * sizeof(int32_t), c->stream));
   uint32_t nv = 0, C = 0;
@@ -387,7 +394,7 @@ static vgs_status lc_on_device(vgs_ctx* c, const char* fn, const int32_t* labels
     if (k > 0) VGS_HIP_TRY(c, hipMemsetAsync(c->lcc_llargest.p, 0xff, k * sizeof(int32_t), c->stream));
   }
   VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the tables are complete, and a labelling read in place is the caller's again
-  c->lcc_C = (int64_t)C; c->lcc_K = K; c->lcc_valid = true;
+  c->lcc_C = (int64_t)C; c->lcc_K = K; c->lcc_nv = nv; c->lcc_valid = true;
   if (n_parts) *n_parts = (int64_t)C;
   return VGS_OK;
 }
@@ -402,7 +409,7 @@ static vgs_status lc_components(vgs_ctx* c, const char* fn, const int32_t* label
   VGS_HIP_TRY(c, hipSetDevice(c->device));
   c->lcc_valid = false;
   if (!on_device && (s = vgs_upload_point_labels(c, labels, n, &labels)) != VGS_OK) return s;
-  return lc_on_device(c, fn, labels, K, n_parts, n_skipped);
+  return vgs_label_parts_on_device(c, fn, labels, 0, c->N, K, n_parts, n_skipped);
 }
 
 extern "C" vgs_status vgs_point_label_components(vgs_ctx* c, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_skipped) {

@@ -44,6 +44,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "vgs_context.hpp"
+#include "tile_region.hpp"
 
 #define RF_TB 64                      // one wavefront per work item
 #define RF_PPT 4                      // points per lane
@@ -343,11 +344,7 @@ vgs_status vgs_refine_on_device(vgs_ctx* c, const vgs_refine_params& rp, int64_t
 // ---- tile contexts ---------------------------------------------------------------------------------------------------------------
 // the region of a tile and its grid, as k_owned (multigpu.hip) takes them: the centre of a voxel is a function of its global code and the
 // shared grid only, so every rank computes the same one
-struct RfRegion { float res_f, min_x, min_y; double lo_x, lo_y, hi_x, hi_y; };
-__device__ __forceinline__ void rf_center(const RfRegion& g, uint64_t code, double& cx, double& cy) {
-  cx = (double)vm_voxel_center(vm_compact21(code >> 2), g.res_f, g.min_x);
-  cy = (double)vm_voxel_center(vm_compact21(code >> 1), g.res_f, g.min_y);
-}
+// (RfRegion, rf_center, rf_region: tile_region.hpp, shared with labelcc_tiles.hip)
 
 // the band: owned used voxels whose centre lies within `near` of a border line of the region -- what a neighbour can reach from a node it
 // refines -- as a flag per voxel and (behind the scan) as records in ascending voxel id
@@ -406,9 +403,6 @@ __global__ __launch_bounds__(256) void k_rf_tile_init(const uint32_t* __restrict
   if ((threadIdx.x & 63) == 0 && nb) atomicAdd(&counts[4], nb);
 }
 
-static RfRegion rf_region(const vgs_ctx* c) {
-  return RfRegion{c->P.voxel_size, (float)c->box.min[0], (float)c->box.min[1], c->own_lo[0], c->own_lo[1], c->own_hi[0], c->own_hi[1]};
-}
 // how far outside its region a rank still refines a node, per axis; the band of the other ranks reaches graph_size further (a candidate
 // lies within graph_size of the node) and half a voxel more, so that no rounding of a centre decides
 static double rf_reach(const vgs_ctx* c) { return std::max((double)c->P.graph_size, 0.5001 * (double)c->P.voxel_size); }

@@ -547,9 +547,10 @@ template <typename F> int first_bad_rank(int world, F bad) {
 // stages: before that phase's collective; upload: behind the last collective of vgs_tiles_set_points; the others: before the exchange of
 // that post-run collective (fields: vgs_tiles_segment_field_stats and vgs_tiles_segment_class_histogram alike; refine:
 // vgs_tiles_refine_point_labels; point_labels: the descriptor exchange of vgs_tiles_point_label_descriptors / _boxes, the cell exchange
-// of vgs_tiles_compare_point_labels and the record exchange of vgs_tiles_point_label_field_stats / _class_histogram).
-enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_REFINE, PH_POINT_LABELS, PH_COUNT };
-const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare", "refine", "point_labels"};
+// of vgs_tiles_compare_point_labels and the record exchange of vgs_tiles_point_label_field_stats / _class_histogram; components: the
+// first exchange of vgs_tiles_point_label_components).
+enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_REFINE, PH_POINT_LABELS, PH_COMPONENTS, PH_COUNT };
+const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare", "refine", "point_labels", "components"};
 
 // Phase clock of one call: lap(slot) gives the slot the host wall time since the last lap (the start, for the first), total(slot) the
 // time from the start to the last lap.  Milliseconds.  vgs_tiles_run stamps t->times as it goes; a post-run collective stamps an array of
@@ -620,6 +621,15 @@ struct vgs_tiles {
   // the last table of a caller's point labelling (nothing of it is cached): phases, own moment records, own pair records, bytes sent
   double ltimes[VGS_TILES_L_COUNT] = {0};
   int64_t l_own = 0, l_pairs = 0, l_bytes = 0;
+  // the connected parts of the last labelling (vgs_tiles_point_label_components): the global tables, K = cc_K; the part ids of the own
+  // points are in the context.  Valid until the next call, the next run or set_points.  Phases, band records, parts, links, bytes sent
+  bool cc_valid = false;
+  int64_t cc_K = 0;
+  std::vector<int32_t> cc_label, cc_nodes, cc_largest;
+  std::vector<int64_t> cc_points, cc_first;
+  std::vector<uint64_t> cc_code;
+  double cctimes[VGS_TILES_CC_COUNT] = {0};
+  int64_t cc_band = 0, cc_parts = 0, cc_links = 0, cc_bytes = 0;
   std::string err;
 };
 
@@ -706,7 +716,7 @@ static vgs_status behind_collective(vgs_tiles* t, vgs_status s, const char* what
 }
 
 // what a new cloud or a new run makes stale: the run itself and every table cached from it
-static void invalidate(vgs_tiles* t) { t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false; t->band_valid = false; t->rf_valid = false; }
+static void invalidate(vgs_tiles* t) { t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false; t->band_valid = false; t->rf_valid = false; t->cc_valid = false; }
 
 template <int N> static vgs_status get_times(vgs_tiles* t, double (vgs_tiles::*slots)[N], double* ms, int32_t n) {
   if (!t || !ms || n < 0 || n > N) return VGS_E_ARG;
@@ -1843,6 +1853,270 @@ vgs_status vgs_tiles_get_refine_payload(vgs_tiles* t, int64_t* band_records, int
   if (!t) return VGS_E_ARG;
   if (band_records) *band_records = t->r_band;
   if (bytes_sent) *bytes_sent = t->r_bytes;
+  return VGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ parts of a labelling
+// The fold of vgs_tiles_point_label_components, the same on every rank (include/vgs_tiles.h): a union-find over (rank, local part) --
+// unite along the links, unite along EQUAL (code, label) keys among the band records of different ranks (the shared voxel; a key with m
+// records is one node, m - 1 comes off the merged part's node count) -- then label, points (sum), nodes (sum - surplus) and first code
+// (max) of every part, sorted by (label ascending, first code descending).  Flat arrays, rank r's entries being off[r] .. off[r + 1].
+namespace {
+struct PartsIn {
+  int world; int64_t K;
+  const int64_t* p_off; const int32_t* p_label; const int64_t* p_points; const int32_t* p_nodes; const uint64_t* p_code;
+  const int64_t* b_off; const uint64_t* b_code; const int32_t* b_label; const int32_t* b_part;
+  const int64_t* l_off; const int32_t* l_own; const int32_t* l_rank; const int32_t* l_part;
+};
+struct PartsOut {
+  std::vector<int32_t> map, label, nodes, largest;
+  std::vector<int64_t> points, first;
+  std::vector<uint64_t> code;
+};
+// false: `why` says what the records got wrong
+bool fold_label_parts(const PartsIn& I, PartsOut& O, std::string& why) {
+  const int world = I.world;
+  const int64_t K = I.K;
+  for (int r = 0; r < world; ++r)
+    if (I.p_off[r + 1] < I.p_off[r] || I.b_off[r + 1] < I.b_off[r] || I.l_off[r + 1] < I.l_off[r]) { why = "offsets must not decrease"; return false; }
+  if (I.p_off[0] != 0 || I.b_off[0] != 0 || I.l_off[0] != 0) { why = "offsets must start at 0"; return false; }
+  const size_t P = (size_t)I.p_off[world];
+  if (P > (size_t)0x7fffffff) { why = "more than 2^31 - 1 local parts"; return false; }
+  for (size_t p = 0; p < P; ++p)
+    if (I.p_label[p] < 0 || (int64_t)I.p_label[p] >= K) { why = "part " + std::to_string(p) + " carries label " + std::to_string(I.p_label[p]) + ", outside 0 .. K-1"; return false; }
+  std::vector<uint32_t> parent(P);
+  for (size_t p = 0; p < P; ++p) parent[p] = (uint32_t)p;
+  auto find = [&](uint32_t x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
+  auto unite = [&](uint32_t a, uint32_t b) { a = find(a); b = find(b); if (a != b) { if (a < b) parent[b] = a; else parent[a] = b; } };
+  for (int r = 0; r < world; ++r) {
+    const int64_t np = I.p_off[r + 1] - I.p_off[r];
+    for (int64_t i = I.l_off[r]; i < I.l_off[r + 1]; ++i) {
+      const int32_t s = I.l_rank[i];
+      if (I.l_own[i] < 0 || (int64_t)I.l_own[i] >= np || s < 0 || s >= world || I.l_part[i] < 0 || (int64_t)I.l_part[i] >= I.p_off[s + 1] - I.p_off[s])
+        { why = "link " + std::to_string(i - I.l_off[r]) + " of rank " + std::to_string(r) + " names a part that does not exist"; return false; }
+      const uint32_t a = (uint32_t)(I.p_off[r] + I.l_own[i]), b = (uint32_t)(I.p_off[s] + I.l_part[i]);
+      if (I.p_label[a] != I.p_label[b]) { why = "link " + std::to_string(i - I.l_off[r]) + " of rank " + std::to_string(r) + " joins parts of different labels"; return false; }
+      unite(a, b);
+    }
+  }
+  // the shared voxels: equal (code, label) among the band records
+  struct Key { uint64_t code; int32_t label; uint32_t part; };
+  std::vector<Key> keys;
+  keys.reserve((size_t)I.b_off[world]);
+  for (int r = 0; r < world; ++r) {
+    const int64_t np = I.p_off[r + 1] - I.p_off[r];
+    for (int64_t i = I.b_off[r]; i < I.b_off[r + 1]; ++i) {
+      if (I.b_part[i] < 0 || (int64_t)I.b_part[i] >= np) { why = "band record " + std::to_string(i - I.b_off[r]) + " of rank " + std::to_string(r) + " names a part that does not exist"; return false; }
+      const uint32_t g = (uint32_t)(I.p_off[r] + I.b_part[i]);
+      if (I.p_label[g] != I.b_label[i]) { why = "band record " + std::to_string(i - I.b_off[r]) + " of rank " + std::to_string(r) + " and its part carry different labels"; return false; }
+      keys.push_back(Key{I.b_code[i], I.b_label[i], g});
+    }
+  }
+  std::sort(keys.begin(), keys.end(), [](const Key& x, const Key& y) { return x.code != y.code ? x.code < y.code : x.label != y.label ? x.label < y.label : x.part < y.part; });
+  std::vector<int64_t> surplus(P, 0);
+  for (size_t i = 1; i < keys.size(); ++i)
+    if (keys[i].code == keys[i - 1].code && keys[i].label == keys[i - 1].label) { unite(keys[i].part, keys[i - 1].part); ++surplus[keys[i].part]; }
+  // the merged parts
+  std::vector<int64_t> pts(P, 0), nds(P, 0);
+  std::vector<uint64_t> code(P, 0);
+  std::vector<uint32_t> roots;
+  for (size_t p = 0; p < P; ++p) {
+    const uint32_t r = find((uint32_t)p);
+    if (r == (uint32_t)p) roots.push_back(r);
+    pts[r] += I.p_points[p]; nds[r] += (int64_t)I.p_nodes[p] - surplus[p]; code[r] = std::max(code[r], I.p_code[p]);
+  }
+  std::sort(roots.begin(), roots.end(), [&](uint32_t a, uint32_t b) {
+    return I.p_label[a] != I.p_label[b] ? I.p_label[a] < I.p_label[b] : code[a] != code[b] ? code[a] > code[b] : a < b; });
+  const size_t C = roots.size();
+  std::vector<int32_t> id_of(P, -1);
+  O.label.resize(C); O.nodes.resize(C); O.points.resize(C); O.code.resize(C);
+  for (size_t g = 0; g < C; ++g) {
+    const uint32_t r = roots[g];
+    id_of[r] = (int32_t)g; O.label[g] = I.p_label[r]; O.points[g] = pts[r]; O.nodes[g] = (int32_t)nds[r]; O.code[g] = code[r];
+  }
+  O.map.resize(P);
+  for (size_t p = 0; p < P; ++p) O.map[p] = id_of[find((uint32_t)p)];
+  O.first.assign((size_t)K + 1, 0); O.largest.assign((size_t)K, -1);
+  for (size_t g = 0; g < C; ++g) ++O.first[(size_t)O.label[g] + 1];
+  for (size_t k = 0; k < (size_t)K; ++k) O.first[k + 1] += O.first[k];   // the parts of label k: first[k] .. first[k + 1] - 1
+  for (size_t g = 0; g < C; ++g) {
+    int32_t& best = O.largest[(size_t)O.label[g]];
+    if (best < 0 || O.points[g] > O.points[(size_t)best]) best = (int32_t)g;   // a strictly larger count only: the lowest id on a tie
+  }
+  return true;
+}
+}  // namespace
+
+vgs_status vgs_tiles_fold_label_parts(int world, int64_t K, const int64_t* part_off, const int32_t* part_label, const int64_t* part_points,
+                                      const int32_t* part_nodes, const uint64_t* part_first_code, const int64_t* band_off, const uint64_t* band_code,
+                                      const int32_t* band_label, const int32_t* band_part, const int64_t* link_off, const int32_t* link_own,
+                                      const int32_t* link_rank, const int32_t* link_part, int64_t* n_parts, int32_t* map, int32_t* out_label,
+                                      int64_t* out_points, int32_t* out_nodes, uint64_t* out_first_code, int64_t* label_first, int32_t* label_largest) {
+  if (world < 1 || K < 0 || K > (int64_t)0x7fffffff || !part_off || !band_off || !link_off) return VGS_E_ARG;
+  if (part_off[world] > 0 && (!part_label || !part_points || !part_nodes || !part_first_code)) return VGS_E_ARG;
+  if (band_off[world] > 0 && (!band_code || !band_label || !band_part)) return VGS_E_ARG;
+  if (link_off[world] > 0 && (!link_own || !link_rank || !link_part)) return VGS_E_ARG;
+  const PartsIn I{world, K, part_off, part_label, part_points, part_nodes, part_first_code, band_off, band_code, band_label, band_part, link_off, link_own, link_rank, link_part};
+  PartsOut O;
+  std::string why;
+  if (!fold_label_parts(I, O, why)) return VGS_E_ARG;
+  if (n_parts) *n_parts = (int64_t)O.label.size();
+  put(O.map, map); put(O.label, out_label); put(O.points, out_points); put(O.nodes, out_nodes); put(O.code, out_first_code);
+  put(O.first, label_first); put(O.largest, label_largest);
+  return VGS_OK;
+}
+
+// The connected parts of a caller's point labelling over the ranks (include/vgs_tiles.h states the definition, the band argument and the
+// shared-voxel rule).  TWO all_gather_varlen of 8-byte words per call, nothing cached:
+//   own parts on this rank's GPU (vgs_own_point_label_parts) -> exchange 1: a header of four words (status, band count, K, own n_skipped)
+//   and two words a band record (code; label << 32 | local part) -> cross links on this rank's GPU over the other ranks' records
+//   (vgs_link_point_label_parts) -> exchange 2: a header of four words (status -- a failure of the link step travels here --, part count,
+//   link count, K), three words a local part (label << 32 | nodes; points; first code), two words a link (own part << 32 | rank; part)
+//   -> fold_label_parts, the same on every rank -> the part ids of the own points through this rank's map (vgs_apply_point_label_part_ids).
+constexpr size_t CC_HEADER = 4;
+static vgs_status tiles_label_components(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t n, int64_t K, int64_t* n_parts,
+                                         int64_t* n_skipped) {
+  if (!t) return VGS_E_ARG;
+  if (n_parts) *n_parts = 0;
+  if (n_skipped) *n_skipped = 0;
+  vgs_status carry;
+  TRY(open_collective(t, fn, PH_COMPONENTS, carry));
+  Comm& c = *t->comm;
+  const size_t world = (size_t)c.world;
+  t->cc_valid = false;
+  double ms[VGS_TILES_CC_COUNT] = {0};
+  Stopwatch sw(ms);
+  // step 1: own parts and band records
+  int64_t n_own_parts = 0, n_band = 0, n_skip = 0;
+  TCARRY_AS(on_device ? vgs_own_point_label_parts_device : vgs_own_point_label_parts, on_device ? "vgs_own_point_label_parts_device" : "vgs_own_point_label_parts",
+            t->ctx, labels, n, K, &n_own_parts, &n_band, &n_skip);
+  if (carry != VGS_OK) { n_own_parts = 0; n_band = 0; n_skip = 0; }
+  std::vector<int32_t> p_label((size_t)n_own_parts + 1), p_nodes((size_t)n_own_parts + 1), b_label((size_t)n_band + 1), b_part((size_t)n_band + 1);
+  std::vector<int64_t> p_points((size_t)n_own_parts + 1);
+  std::vector<uint64_t> p_code((size_t)n_own_parts + 1), b_code((size_t)n_band + 1);
+  TCARRY(vgs_get_own_point_label_parts(t->ctx, p_label.data(), p_points.data(), p_nodes.data(), p_code.data(), b_code.data(), b_label.data(), b_part.data()));
+  if (carry != VGS_OK) { n_own_parts = 0; n_band = 0; n_skip = 0; }
+  std::vector<uint64_t> pay1(CC_HEADER + 2 * (size_t)n_band);
+  pay1[0] = (uint64_t)(uint32_t)carry; pay1[1] = (uint64_t)n_band; pay1[2] = (uint64_t)K; pay1[3] = (uint64_t)n_skip;
+  for (size_t i = 0; i < (size_t)n_band; ++i) {
+    pay1[CC_HEADER + 2 * i] = b_code[i];
+    pay1[CC_HEADER + 2 * i + 1] = ((uint64_t)(uint32_t)b_label[i] << 32) | (uint64_t)(uint32_t)b_part[i];
+  }
+  sw.lap(VGS_TILES_CC_OWN);
+  std::vector<std::vector<uint64_t>> g1;
+  TRY(exchange(t, carry, pay1, "components", sw, VGS_TILES_CC_EXCHANGE1, g1));
+  // every rank was valid on its own: do they describe the same table, and is every payload as long as its header says?
+  for (size_t r = 0; r < world; ++r)
+    if (g1[r].size() < CC_HEADER || g1[r].size() != CC_HEADER + 2 * (size_t)g1[r][1]) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
+  for (size_t r = 1; r < world; ++r)
+    if (g1[r][2] != g1[0][2])
+      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed K = " + std::to_string((int64_t)g1[r][2]) + ", rank 0 passed " + std::to_string((int64_t)g1[0][2]));
+  int64_t skipped = 0;
+  for (size_t r = 0; r < world; ++r) skipped += (int64_t)g1[r][3];
+  // step 3: the cross links over the other ranks' band records
+  std::vector<uint64_t> f_code;
+  std::vector<int32_t> f_label, f_rank, f_part;
+  for (size_t r = 0; r < world; ++r) {
+    if ((int)r == c.rank) continue;
+    for (size_t i = 0; i < (size_t)g1[r][1]; ++i) {
+      const uint64_t w = g1[r][CC_HEADER + 2 * i + 1];
+      f_code.push_back(g1[r][CC_HEADER + 2 * i]); f_label.push_back((int32_t)(uint32_t)(w >> 32)); f_rank.push_back((int32_t)r); f_part.push_back((int32_t)(uint32_t)w);
+    }
+  }
+  int64_t n_links = 0;
+  TCARRY(vgs_link_point_label_parts(t->ctx, f_code.data(), f_label.data(), f_rank.data(), f_part.data(), (int64_t)f_code.size(), &n_links));
+  if (carry != VGS_OK) n_links = 0;
+  std::vector<int32_t> l_own((size_t)n_links + 1), l_rank((size_t)n_links + 1), l_part((size_t)n_links + 1);
+  TCARRY(vgs_get_point_label_part_links(t->ctx, l_own.data(), l_rank.data(), l_part.data()));
+  if (carry != VGS_OK) n_links = 0;
+  const size_t np = carry == VGS_OK ? (size_t)n_own_parts : 0, nl = (size_t)n_links;
+  std::vector<uint64_t> pay2(CC_HEADER + 3 * np + 2 * nl);
+  pay2[0] = (uint64_t)(uint32_t)carry; pay2[1] = (uint64_t)np; pay2[2] = (uint64_t)nl; pay2[3] = (uint64_t)K;
+  for (size_t i = 0; i < np; ++i) {
+    uint64_t* w = pay2.data() + CC_HEADER + 3 * i;
+    w[0] = ((uint64_t)(uint32_t)p_label[i] << 32) | (uint64_t)(uint32_t)p_nodes[i]; w[1] = (uint64_t)p_points[i]; w[2] = p_code[i];
+  }
+  for (size_t i = 0; i < nl; ++i) {
+    uint64_t* w = pay2.data() + CC_HEADER + 3 * np + 2 * i;
+    w[0] = ((uint64_t)(uint32_t)l_own[i] << 32) | (uint64_t)(uint32_t)l_rank[i]; w[1] = (uint64_t)(uint32_t)l_part[i];
+  }
+  sw.lap(VGS_TILES_CC_LINK);
+  std::vector<std::vector<uint64_t>> g2;
+  TRY(exchange(t, carry, pay2, "components", sw, VGS_TILES_CC_EXCHANGE2, g2));
+  for (size_t r = 0; r < world; ++r)
+    if (g2[r].size() < CC_HEADER || g2[r].size() != CC_HEADER + 3 * (size_t)g2[r][1] + 2 * (size_t)g2[r][2])
+      return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
+  // step 5: the fold
+  std::vector<int64_t> p_off(world + 1, 0), b_off(world + 1, 0), l_off(world + 1, 0);
+  for (size_t r = 0; r < world; ++r) { p_off[r + 1] = p_off[r] + (int64_t)g2[r][1]; b_off[r + 1] = b_off[r] + (int64_t)g1[r][1]; l_off[r + 1] = l_off[r] + (int64_t)g2[r][2]; }
+  std::vector<int32_t> ap_label((size_t)p_off[world]), ap_nodes((size_t)p_off[world]), ab_label((size_t)b_off[world]), ab_part((size_t)b_off[world]);
+  std::vector<int32_t> al_own((size_t)l_off[world]), al_rank((size_t)l_off[world]), al_part((size_t)l_off[world]);
+  std::vector<int64_t> ap_points((size_t)p_off[world]);
+  std::vector<uint64_t> ap_code((size_t)p_off[world]), ab_code((size_t)b_off[world]);
+  for (size_t r = 0; r < world; ++r) {
+    const size_t rp = (size_t)g2[r][1];
+    for (size_t i = 0; i < rp; ++i) {
+      const uint64_t* w = g2[r].data() + CC_HEADER + 3 * i;
+      const size_t o = (size_t)p_off[r] + i;
+      ap_label[o] = (int32_t)(uint32_t)(w[0] >> 32); ap_nodes[o] = (int32_t)(uint32_t)w[0]; ap_points[o] = (int64_t)w[1]; ap_code[o] = w[2];
+    }
+    for (size_t i = 0; i < (size_t)g2[r][2]; ++i) {
+      const uint64_t* w = g2[r].data() + CC_HEADER + 3 * rp + 2 * i;
+      const size_t o = (size_t)l_off[r] + i;
+      al_own[o] = (int32_t)(uint32_t)(w[0] >> 32); al_rank[o] = (int32_t)(uint32_t)w[0]; al_part[o] = (int32_t)(uint32_t)w[1];
+    }
+    for (size_t i = 0; i < (size_t)g1[r][1]; ++i) {
+      const uint64_t w = g1[r][CC_HEADER + 2 * i + 1];
+      const size_t o = (size_t)b_off[r] + i;
+      ab_code[o] = g1[r][CC_HEADER + 2 * i]; ab_label[o] = (int32_t)(uint32_t)(w >> 32); ab_part[o] = (int32_t)(uint32_t)w;
+    }
+  }
+  const PartsIn I{(int)world, K, p_off.data(), ap_label.data(), ap_points.data(), ap_nodes.data(), ap_code.data(), b_off.data(), ab_code.data(), ab_label.data(),
+                  ab_part.data(), l_off.data(), al_own.data(), al_rank.data(), al_part.data()};
+  PartsOut O;
+  std::string bad;
+  if (!fold_label_parts(I, O, bad)) return tfail(t, VGS_E_ARG, std::string(fn) + ": " + bad);
+  sw.lap(VGS_TILES_CC_FOLD);
+  // step 6: the part ids of the own points
+  const int32_t none = 0;
+  const int64_t mine = p_off[(size_t)c.rank + 1] - p_off[(size_t)c.rank];
+  TRY(behind_collective(t, vgs_apply_point_label_part_ids(t->ctx, mine > 0 ? O.map.data() + p_off[(size_t)c.rank] : &none, mine), "vgs_apply_point_label_part_ids"));
+  sw.lap(VGS_TILES_CC_APPLY);
+  sw.total(VGS_TILES_CC_TOTAL, t->cctimes);
+  t->cc_label.swap(O.label); t->cc_nodes.swap(O.nodes); t->cc_points.swap(O.points); t->cc_code.swap(O.code); t->cc_first.swap(O.first); t->cc_largest.swap(O.largest);
+  t->cc_K = K; t->cc_valid = true;
+  t->cc_band = n_band; t->cc_parts = (int64_t)np; t->cc_links = (int64_t)nl; t->cc_bytes = (int64_t)((pay1.size() + pay2.size()) * sizeof(uint64_t));
+  if (n_parts) *n_parts = (int64_t)t->cc_label.size();
+  if (n_skipped) *n_skipped = skipped;
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_point_label_components(vgs_tiles* t, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_skipped) {
+  return tiles_label_components(t, "vgs_tiles_point_label_components", false, labels_host, n, K, n_parts, n_skipped);
+}
+vgs_status vgs_tiles_point_label_components_device(vgs_tiles* t, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_skipped) {
+  return tiles_label_components(t, "vgs_tiles_point_label_components_device", true, labels_dev, n, K, n_parts, n_skipped);
+}
+
+vgs_status vgs_tiles_get_point_label_components(vgs_tiles* t, int32_t* part_of_point, int32_t* part_label, int64_t* part_points, int32_t* part_nodes,
+                                                uint64_t* part_first_code, int64_t* label_first, int32_t* label_largest) {
+  if (!t) return VGS_E_ARG;
+  if (!t->ran || !t->cc_valid)
+    return tfail(t, VGS_E_STATE, "vgs_tiles_get_point_label_components: no label components since the last run or the last vgs_tiles_set_points (vgs_tiles_point_label_components first)");
+  if (part_of_point && t->n_own > 0) TCTX(vgs_get_point_label_part_ids(t->ctx, part_of_point, t->n_own));
+  put(t->cc_label, part_label); put(t->cc_points, part_points); put(t->cc_nodes, part_nodes); put(t->cc_code, part_first_code);
+  put(t->cc_first, label_first); put(t->cc_largest, label_largest);
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_point_label_component_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::cctimes, ms, n); }
+
+vgs_status vgs_tiles_get_point_label_component_payload(vgs_tiles* t, int64_t* band_records, int64_t* parts, int64_t* links, int64_t* bytes_sent) {
+  if (!t) return VGS_E_ARG;
+  if (band_records) *band_records = t->cc_band;
+  if (parts) *parts = t->cc_parts;
+  if (links) *links = t->cc_links;
+  if (bytes_sent) *bytes_sent = t->cc_bytes;
   return VGS_OK;
 }
 

@@ -410,7 +410,18 @@ struct vgs_ctx {
   DevBuf<uint32_t> lcc_flag, lcc_vex, lcc_vtx, lcc_vscan, lcc_vfirst, lcc_uv, lcc_nidx;
   DevBuf<uint64_t> lcc_lmax;
   int64_t lcc_C = 0, lcc_K = 0;
+  uint32_t lcc_nv = 0;   // vertices of the last pass (the arrays of lcc_vtx hold lcc_nv + 1 words each)
   bool lcc_valid = false;
+  // the parts of a labelling across the ranks of the tiled driver (labelcc_tiles.hip; include/vgs.h, vgs_own_point_label_parts): the band
+  // records of the last own pass (lct_band rows: code, label, local part, vertex), the code of every local part's first node, the other
+  // ranks' records as looked up and sorted (key = label << 32 | local node, value = index of the record), the link triples, the map from
+  // local to global part and the own points' global part ids (n_own words).  lct_own / lct_linked / lct_applied: how far the last call got.
+  DevBuf<uint64_t> lct_bcode, lct_pcode, lct_fcode, lct_key, lct_key2;
+  DevBuf<int32_t> lct_blabel, lct_bpart, lct_flabel, lct_frank, lct_fpart, lct_map, lct_ids;
+  DevBuf<uint32_t> lct_bvtx, lct_flag, lct_scan, lct_val, lct_val2, lct_list, lct_count;
+  DevBuf<uint32_t> lct_link, lct_link2;   // four words a triple: own part, rank, part, 0
+  int64_t lct_band = 0, lct_links = 0, lct_K = 0;
+  bool lct_own = false, lct_linked = false, lct_applied = false;
   DevBuf<uint64_t> counters;  // device-side counters (pairs, flags)
   DevBuf<uint32_t> work_ids;   // scratch index lists
 
@@ -667,6 +678,9 @@ void sf_launch_own_records(vgs_ctx* c, const uint32_t* seg_chunk, const double* 
 void sf_launch_final(vgs_ctx* c, const uint32_t* seg_chunk, const double* part, uint32_t n_part, int64_t K, uint32_t C, uint32_t c0, uint32_t ng,
                      const double* anchor, int64_t* o_n, double* o_mean, double* o_var, float* o_min, float* o_max);
 void sf_launch_majority(vgs_ctx* c, const int64_t* hist, int32_t n_classes, int64_t K, int32_t* majority, int64_t* majority_count);
+// labelcc.hip's pass over the points own_first .. own_first + n_lab - 1 (labelcc_tiles.hip runs it over a tile context's own points)
+vgs_status vgs_label_parts_on_device(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t own_first, int64_t n_lab, int64_t K, int64_t* n_parts,
+                                     int64_t* n_skipped);
 vgs_status vgs_seggraph_on_device(vgs_ctx* c);   // seggraph.hip
 // tile contexts: halo[v] = label[k] for the voxel v of code[k] that this context holds and does not own, queued on the context's stream
 // (code, label: n entries in HBM; halo: V entries).  One kernel for the graph's table and the refinement's (seggraph.hip)

@@ -31,6 +31,12 @@ F_NAMES = ("own", "exchange", "fold", "finish", "total")        # vgs_tiles_get_
 C_NAMES = ("own", "exchange", "tables", "total")                # vgs_tiles_get_compare_times
 R_NAMES = ("band", "exchange", "table", "refine", "total")      # vgs_tiles_get_refine_times
 L_NAMES = ("own", "exchange", "fold", "finish", "total")        # vgs_tiles_get_point_label_times
+CC_NAMES = ("own", "exchange1", "link", "exchange2", "fold", "apply", "total")   # vgs_tiles_get_point_label_component_times
+# (field, dtype, table) of vgs_tiles_get_point_label_components, in its argument order: Engine.COMPONENT_FIELDS with the shared-grid code
+# of a part's first node in place of the node id
+COMPONENT_FIELDS = (("part_of_point", np.int32, "points"), ("part_label", np.int32, "parts"), ("part_points", np.int64, "parts"),
+                    ("part_nodes", np.int32, "parts"), ("part_first_code", np.uint64, "parts"), ("label_first", np.int64, "first"),
+                    ("label_largest", np.int32, "labels"))
 # vgs_tiles_refine_point_labels' counts, all the rank's share
 REFINE_COUNTS = ("working_nodes", "points_examined", "points_changed", "points_filled", "points_beyond_strip")
 # per (record / row, channel): (field, dtype) of vgs_get_own_segment_field_moments and vgs_tiles_fold_field_moments, in their argument order
@@ -153,6 +159,17 @@ def lib():
         L.vgs_tiles_get_point_label_times.argtypes = [P, P, C.c_int32]
         L.vgs_tiles_get_point_label_payload.restype = C.c_int
         L.vgs_tiles_get_point_label_payload.argtypes = [P, P, P, P]
+        for name in ("vgs_tiles_point_label_components", "vgs_tiles_point_label_components_device"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [P, P, C.c_int64, C.c_int64, P, P]
+        L.vgs_tiles_get_point_label_components.restype = C.c_int
+        L.vgs_tiles_get_point_label_components.argtypes = [P] * 8
+        L.vgs_tiles_fold_label_parts.restype = C.c_int
+        L.vgs_tiles_fold_label_parts.argtypes = [C.c_int, C.c_int64] + [P] * 21
+        L.vgs_tiles_get_point_label_component_times.restype = C.c_int
+        L.vgs_tiles_get_point_label_component_times.argtypes = [P, P, C.c_int32]
+        L.vgs_tiles_get_point_label_component_payload.restype = C.c_int
+        L.vgs_tiles_get_point_label_component_payload.argtypes = [P, P, P, P, P]
         L.vgs_tiles_fold_field_moments.restype = C.c_int
         L.vgs_tiles_fold_field_moments.argtypes = [C.c_int, P, P, C.c_int32, P, P, P, P, P, P, C.c_int64, P, P, P, P, P, P]
         L.vgs_tiles_fold_class_counts.restype = C.c_int
@@ -241,6 +258,41 @@ def fold_label_pairs(records, K):
     if st != 0:
         raise VgsError(st, "vgs_tiles_fold_label_pairs")
     return out[:max(K, 0)]
+
+
+def fold_label_parts(records, K):
+    """vgs_tiles_fold_label_parts (host arithmetic, no GPU): step 5 of vgs_tiles_point_label_components.  records[r] = rank r's dict of
+    part_label (int32), part_points (int64), part_nodes (int32), part_first_code (uint64), band_code (uint64), band_label, band_part
+    (int32) -- what NativeTiles.own_point_label_parts() gives -- and link_own, link_rank, link_part (int32; absent = no link).  Returns
+    the global table as a dict: part_label, part_points, part_nodes, part_first_code, label_first (K + 1), label_largest (K), n_parts,
+    and map, the list of every rank's array from local to global part."""
+    world, K = len(records), int(K)
+
+    def cat(name, dt):
+        return np.ascontiguousarray(np.concatenate([np.asarray(r.get(name, ()), dtype=dt).reshape(-1) for r in records] + [np.zeros(0, dtype=dt)]))
+
+    def off(name):
+        o = np.zeros(world + 1, dtype=np.int64)
+        o[1:] = np.cumsum([len(r.get(name, ())) for r in records])
+        return o
+    p_off, b_off, l_off = off("part_label"), off("band_label"), off("link_own")
+    ins = [cat("part_label", np.int32), cat("part_points", np.int64), cat("part_nodes", np.int32), cat("part_first_code", np.uint64)]
+    band = [cat("band_code", np.uint64), cat("band_label", np.int32), cat("band_part", np.int32)]
+    link = [cat("link_own", np.int32), cat("link_rank", np.int32), cat("link_part", np.int32)]
+    P, k = max(int(p_off[-1]), 1), max(K, 0)
+    n_parts = C.c_int64(0)
+    out = {"map": np.zeros(P, dtype=np.int32), "part_label": np.zeros(P, dtype=np.int32), "part_points": np.zeros(P, dtype=np.int64),
+           "part_nodes": np.zeros(P, dtype=np.int32), "part_first_code": np.zeros(P, dtype=np.uint64),
+           "label_first": np.zeros(k + 1, dtype=np.int64), "label_largest": np.zeros(max(k, 1), dtype=np.int32)}
+    st = lib().vgs_tiles_fold_label_parts(world, K, _vp(p_off), *(_vp(a) for a in ins), _vp(b_off), *(_vp(a) for a in band), _vp(l_off),
+                                          *(_vp(a) for a in link), C.byref(n_parts), *(_vp(out[name]) for name in out))
+    if st != 0:
+        raise VgsError(st, "vgs_tiles_fold_label_parts")
+    c = int(n_parts.value)
+    res = {name: out[name][:c] for name in ("part_label", "part_points", "part_nodes", "part_first_code")}
+    res["label_first"], res["label_largest"], res["n_parts"] = out["label_first"], out["label_largest"][:k], c
+    res["map"] = [out["map"][int(p_off[r]):int(p_off[r + 1])] for r in range(world)]
+    return res
 
 
 def _rec_off(records):
@@ -641,6 +693,80 @@ class NativeTiles:
         out = {name: a[:nr.value] for name, a in out.items()}
         out["pair_code"], out["pair_label"], out["n_skipped"] = pc[:npair.value], pl[:npair.value], int(nskip.value)
         return out
+
+    def label_components(self, labels, K):
+        """COLLECTIVE on every call, two collectives (every rank makes it after run(), with the same K; nothing is cached): the connected
+        parts of ANY per-point labelling over all ranks -- the dict of Engine.label_components() on the gathered points, with
+        part_first_code (uint64, the shared-grid code of the part's first node) in place of part_first_node; part_of_point holds this
+        rank's points, every table the same bytes on every rank (include/vgs_tiles.h, vgs_tiles_point_label_components).  `labels`, K as
+        describe_labels().  The result stays in the driver until the next call, the next run or the next set_points()."""
+        from .api import Engine
+        labels, ptr, n, dev = Engine._classes_input(labels, self.params.device)
+        fn = self._L.vgs_tiles_point_label_components_device if dev else self._L.vgs_tiles_point_label_components
+        K = int(K)
+        n_parts, skipped = C.c_int64(0), C.c_int64(0)
+        self._ck(fn(self._h, ptr, n, K, C.byref(n_parts), C.byref(skipped)))
+        out = self.label_components_result(n_parts.value, K)
+        out["n_skipped"] = int(skipped.value)
+        return out
+
+    def label_components_result(self, n_parts, K):
+        """the tables of the last label_components() (vgs_tiles_get_point_label_components; local, no collective)"""
+        rows = {"points": self.n, "parts": int(n_parts), "first": max(int(K), 0) + 1, "labels": max(int(K), 0)}
+        out = {name: np.zeros(max(rows[tab], 1), dtype=dt) for name, dt, tab in COMPONENT_FIELDS}
+        self._ck(self._L.vgs_tiles_get_point_label_components(self._h, *(_vp(out[name]) for name, _, _ in COMPONENT_FIELDS)))
+        out = {name: out[name][:rows[tab]] for name, _, tab in COMPONENT_FIELDS}
+        out["n_parts"] = int(n_parts)
+        return out
+
+    def label_component_times(self):
+        """the last label_components()'s phases on this rank, milliseconds (CC_NAMES)"""
+        return self._times(self._L.vgs_tiles_get_point_label_component_times, CC_NAMES)
+
+    def label_component_payload(self):
+        """the last label_components()'s payload on this rank: band records, local parts and links of its own, bytes sent"""
+        return self._payload(self._L.vgs_tiles_get_point_label_component_payload, ("band_records", "parts", "links", "bytes_sent"))
+
+    def own_point_label_parts(self, labels, K):
+        """this rank's local parts and band records of a labelling of its own points (vgs_own_point_label_parts on its context; local, no
+        collective): a dict of part_label, part_points, part_nodes, part_first_code (one row per local part), band_code, band_label,
+        band_part (one row per band vertex), plus n_skipped"""
+        from .api import Engine
+        L = _lib.lib()
+        h = self._ctx()
+        labels, ptr, n, dev = Engine._classes_input(labels, self.params.device)
+        fn = L.vgs_own_point_label_parts_device if dev else L.vgs_own_point_label_parts
+        npart, nband, nskip = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        st = fn(h, ptr, n, int(K), C.byref(npart), C.byref(nband), C.byref(nskip))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        fields = (("part_label", np.int32, npart.value), ("part_points", np.int64, npart.value), ("part_nodes", np.int32, npart.value),
+                  ("part_first_code", np.uint64, npart.value), ("band_code", np.uint64, nband.value), ("band_label", np.int32, nband.value),
+                  ("band_part", np.int32, nband.value))
+        out = {name: np.zeros(max(m, 1), dtype=dt) for name, dt, m in fields}
+        st = L.vgs_get_own_point_label_parts(h, *(_vp(out[name]) for name, _, _ in fields))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        out = {name: out[name][:m] for name, _, m in fields}
+        out["n_skipped"] = int(nskip.value)
+        return out
+
+    def link_point_label_parts(self, code, label, rank, part):
+        """this rank's cross links over other ranks' band records (vgs_link_point_label_parts behind own_point_label_parts(); local, no
+        collective): a dict of link_own, link_rank, link_part (int32), sorted and unique"""
+        L = _lib.lib()
+        h = self._ctx()
+        code = np.ascontiguousarray(code, dtype=np.uint64)
+        label, rank, part = (np.ascontiguousarray(a, dtype=np.int32) for a in (label, rank, part))
+        nl = C.c_int64(0)
+        st = L.vgs_link_point_label_parts(h, _vp(code), _vp(label), _vp(rank), _vp(part), int(code.shape[0]), C.byref(nl))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        out = {name: np.zeros(max(nl.value, 1), dtype=np.int32) for name in ("link_own", "link_rank", "link_part")}
+        st = L.vgs_get_point_label_part_links(h, *(_vp(a) for a in out.values()))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        return {name: a[:nl.value] for name, a in out.items()}
 
     def _label_table_inputs(self, labels, other, what):
         """labels of label_field_stats / label_class_histogram and the own-record calls: labels and the attribute array both numpy or both
