@@ -111,7 +111,9 @@ def _check(gpu, parts, out, F, CL, two_ranks=True):
         assert (lab_ranks.sum(axis=1) >= 2).any()          # at least one checked segment has points on two ranks
     for r, o in enumerate(out):
         assert o["kept"] == kept and o["second"] and o["rerun"] and o["untouched"], r
-        assert o["times"]["total"] > 0 and o["times"]["exchange"] >= 0 and o["payload"]["bytes_sent"] >= 24
+        assert o["times"]["total"] > 0 and o["times"]["exchange"] >= 0
+        # the wire size of the call the getter last saw (the statistics of the last channel count): a 24-byte header, 8 + 40 C bytes a record
+        assert o["payload"]["bytes_sent"] == 24 + o["payload"]["own_records"] * (8 + 40 * list(F)[-1]), (r, o["payload"])
     for ch in F:
         got = out[0]["stats"][ch]
         field = np.concatenate(F[ch])

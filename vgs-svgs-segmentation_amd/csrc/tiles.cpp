@@ -9,8 +9,12 @@
 // verdict (agreed): the failing rank its own error, the others VGS_E_PEER naming the lowest failing rank.  A failure BEHIND a call's last
 // collective is returned and kept in t->pending (behind_collective), and the next collective's header carries it.  The collectives
 // after vgs_tiles_run all read: open_collective (guard, carry = pending, injection) -> own records, header filled in -> exchange (ONE
-// all_gather_varlen + the scan of the headers) -> fold -> behind_collective(finish on this rank's GPU).  vgs_tiles_set_points, chain_grid
-// and the boundary exchange of vgs_tiles_run carry the status in payloads of their own shapes and share first_bad_rank and agreed.
+// all_gather_varlen + the scan of the headers) -> check_payloads / fold -> behind_collective(finish on this rank's GPU).
+// vgs_tiles_set_points, chain_grid and the boundary exchange of vgs_tiles_run carry the status in payloads of their own shapes and share
+// first_bad_rank and agreed.
+// The per-segment tables exist for two labellings, the run's own node labels and a caller's per-point labels (Labelling), and each table
+// kind has ONE driver that serves both: moment_collective (descriptors), extent_collective (boxes), attribute_collective<Codec> (field
+// statistics, class histogram), tiles_compare (scores).  A public entry fills in the Labelling, calls the driver and places the table.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -519,7 +523,9 @@ static_assert(sizeof(BandRec) == 16, "BandRec is the exchange's wire format");
 // ------------------------------------------------------------------------------------------------ payload headers
 // Every payload of a post-run collective opens with a header that holds the rank's status word and its record count: the first entry of
 // a struct payload (status in its first field; the count where the record has a slot wide enough for it), the first three words of a word
-// payload (status, count, one word of the collective's own).  No receiver reads the count of a struct payload; it stays on the wire.
+// payload (status, count, one word of the collective's own; the attribute records of a point labelling add two).  The moment entries'
+// count is read behind the exchange (their header also holds K, the pair count and n_skipped in s); no receiver reads an edge or extent
+// payload's count, which stays on the wire.
 void set_header(MomentRec& h, vgs_status st, size_t n) { h.label = (int32_t)st; h.n_points = (int64_t)n; }
 void set_header(EdgeRec& h, vgs_status st, size_t n) { h.a = (int32_t)st; h.n_pairs = (int64_t)n; }
 void set_header(ExtentRec& h, vgs_status st, size_t n) { h.label = (int32_t)st; h.lo[0] = (double)n; }
@@ -545,10 +551,11 @@ template <typename F> int first_bad_rank(int world, F bad) {
 
 // Where a rank can be told to fail (tests of the agreed-status protocol: VGS_TILES_FAIL_RANK / VGS_TILES_FAIL_AT=<name>).  points, grid and
 // stages: before that phase's collective; upload: behind the last collective of vgs_tiles_set_points; the others: before the exchange of
-// that post-run collective (fields: vgs_tiles_segment_field_stats and vgs_tiles_segment_class_histogram alike; refine:
-// vgs_tiles_refine_point_labels; point_labels: the descriptor exchange of vgs_tiles_point_label_descriptors / _boxes, the cell exchange
-// of vgs_tiles_compare_point_labels and the record exchange of vgs_tiles_point_label_field_stats / _class_histogram; components: the
-// first exchange of vgs_tiles_point_label_components).
+// a post-run collective, and the name is the phase word of the peers' VGS_E_PEER.  descriptors, boxes, fields, compare: the tables of the
+// node labelling (fields: statistics and histogram alike); point_labels: every table of a caller's point labelling -- the moment exchange
+// of vgs_tiles_point_label_descriptors / _boxes, the cell exchange of vgs_tiles_compare_point_labels, the record exchange of
+// vgs_tiles_point_label_field_stats / _class_histogram; refine: vgs_tiles_refine_point_labels; components: the first exchange of
+// vgs_tiles_point_label_components.
 enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_REFINE, PH_POINT_LABELS, PH_COMPONENTS, PH_COUNT };
 const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare", "refine", "point_labels", "components"};
 
@@ -564,6 +571,43 @@ struct Stopwatch {
   void total(int slot) { ms[slot] = last - start; }
   template <int N> void total(int slot, double (&dst)[N]) { total(slot); std::copy(ms, ms + N, dst); }
 };
+
+// the phases of a table's collective: dtimes, btimes, ftimes and ltimes share the five slots
+enum { T_OWN, T_EXCHANGE, T_FOLD, T_FINISH, T_TOTAL, T_COUNT };
+static_assert(VGS_TILES_D_MOMENTS == T_OWN && VGS_TILES_B_EXTENTS == T_OWN && VGS_TILES_F_OWN == T_OWN && VGS_TILES_L_OWN == T_OWN, "slot 0");
+static_assert(VGS_TILES_D_EXCHANGE == T_EXCHANGE && VGS_TILES_B_EXCHANGE == T_EXCHANGE && VGS_TILES_F_EXCHANGE == T_EXCHANGE && VGS_TILES_L_EXCHANGE == T_EXCHANGE, "slot 1");
+static_assert(VGS_TILES_D_FOLD == T_FOLD && VGS_TILES_B_FOLD == T_FOLD && VGS_TILES_F_FOLD == T_FOLD && VGS_TILES_L_FOLD == T_FOLD, "slot 2");
+static_assert(VGS_TILES_D_ALGEBRA == T_FINISH && VGS_TILES_B_FINISH == T_FINISH && VGS_TILES_F_FINISH == T_FINISH && VGS_TILES_L_FINISH == T_FINISH, "slot 3");
+static_assert(VGS_TILES_D_TOTAL == T_TOTAL && VGS_TILES_B_TOTAL == T_TOTAL && VGS_TILES_F_TOTAL == T_TOTAL && VGS_TILES_L_TOTAL == T_TOTAL, "slot 4");
+static_assert(VGS_TILES_D_COUNT == T_COUNT && VGS_TILES_B_COUNT == T_COUNT && VGS_TILES_F_COUNT == T_COUNT && VGS_TILES_L_COUNT == T_COUNT, "five slots");
+
+// The labelling a per-segment table is made for, which is all a table's driver is told of it.  Node: the run's own labels, K = kept rows,
+// nothing of the caller's.  Point: one label per own point of the caller's, K rows of the caller's, on the host or on the device.
+struct Labelling {
+  const char* fn;         // the public function that was called, for the guard and the messages
+  Phase phase;            // where VGS_TILES_FAIL_AT strikes; PHASE_NAME[phase] is the phase word of VGS_E_PEER
+  bool point;
+  // Which variant of the public entry was called: a `_device` entry is handed device pointers for EVERY array of the caller's, so this
+  // says where the labels live (point) and where the attribute rows of an attribute call live (node and point alike).  The node
+  // descriptors and boxes take nothing of the caller's and never read it.
+  bool on_device;
+  // point: the labels and their number.  (The rows of an attribute are counted by the codec: the node family has rows but no labels;
+  // the public point entries take one n for both arrays.)
+  const int32_t* labels;
+  int64_t n;
+  int64_t K;              // rows of the table
+  const char* limit;      // what every label stays below, for the bad-label message
+};
+
+// the tables the drivers fill: the descriptor rows (n_skipped: of a point labelling, summed over the ranks) and the boxes of one frame
+struct DescTable {
+  std::vector<int64_t> npts;
+  std::vector<int32_t> nnodes;
+  std::vector<float> bbox, eig8;
+  std::vector<double> cen, cov, eval, evec;
+  int64_t n_skipped = 0;
+};
+struct BoxTable { std::vector<double> center, half, frame, lo, hi; };
 
 }  // namespace
 
@@ -586,10 +630,7 @@ struct vgs_tiles {
   bool ran = false;              // the last vgs_tiles_run completed here
   // the global descriptor table of the last run (vgs_tiles_get_segment_descriptors), K = kept rows; valid until the next run / set_points
   bool desc_valid = false;
-  std::vector<int64_t> d_npts;
-  std::vector<int32_t> d_nnodes;
-  std::vector<float> d_bbox, d_eig8;
-  std::vector<double> d_cen, d_cov, d_eval, d_evec;
+  DescTable desc;
   double dtimes[VGS_TILES_D_COUNT] = {0};   // the last descriptor collective, milliseconds of host wall time per phase
   // what the last run's boundary exchange brought (vgs_tiles_get_segment_graph turns it into the halo labels): every rank's records
   // (code, root) and the global label of every (rank, root)
@@ -602,7 +643,7 @@ struct vgs_tiles {
   int64_t g_halo = 0, g_own = 0, g_bytes = 0;   // its payload: halo labels handed to the context, own edges, bytes sent
   // the global box table of the last run per frame (vgs_tiles_get_segment_boxes), K = kept rows; valid until the next run / set_points
   bool box_valid[2] = {false, false};
-  std::vector<double> b_center[2], b_half[2], b_frame[2], b_lo[2], b_hi[2];
+  BoxTable box[2];
   double btimes[VGS_TILES_B_COUNT] = {0};   // the last box collective, milliseconds of host wall time per phase
   // the last attribute collective (field statistics or class histogram, of the node labels or of a caller's point labelling; nothing of
   // it is cached): phases, own records, bytes sent
@@ -674,37 +715,26 @@ static vgs_status exchange(vgs_tiles* t, vgs_status carry, const std::vector<T>&
   return agreed(t, carry, bad, phase);
 }
 
-// Behind the exchange of a word payload with `per` words a record: the header's third word must be the same on every rank where it is an
-// argument of the call (`arg` names it; NULL: the ranks' own figure) -- every rank was valid on its own, but they do not describe the
-// same table -- and every payload is as long as its header's record count says.  The same verdict on every rank, from the same words.
-template <typename W>
-static vgs_status check_word_payloads(vgs_tiles* t, const char* fn, const std::vector<std::vector<W>>& gathered, size_t per, const char* arg) {
-  auto word = [&](size_t r, int i) { return (int64_t)gathered[r][(size_t)i]; };
-  for (size_t r = 1; arg && r < gathered.size(); ++r)
-    if (word(r, 2) != word(0, 2))
-      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed " + arg + " = " + std::to_string((int32_t)word(r, 2)) + ", rank 0 passed " + std::to_string((int32_t)word(0, 2)));
-  for (size_t r = 0; r < gathered.size(); ++r)
-    if (word(r, 1) < 0 || gathered[r].size() != 3 + (size_t)word(r, 1) * per) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
-  return VGS_OK;
+// The two verdicts behind an exchange in which every rank was valid on its own, the same on every rank from the same gathered words: the
+// ranks do not describe the same table (`what`: an argument of the call that must be the same everywhere), or a payload is not as long as
+// its header says.
+static vgs_status disagree(vgs_tiles* t, const char* fn, size_t r, const char* what, int64_t vr, int64_t v0) {
+  return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed " + what + " = " + std::to_string(vr) + ", rank 0 passed " + std::to_string(v0));
 }
+static vgs_status wrong_size(vgs_tiles* t, const char* fn, size_t r) { return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size"); }
 
-constexpr size_t LF_HEADER = 5;   // header words of vgs_tiles_point_label_field_stats / _class_histogram
-// Behind the exchange of a point labelling's attribute records (a header of LF_HEADER words: status, record count, n_channels or n_classes,
-// K, own n_skipped): every rank was valid on its own -- do they describe the same table (words 3 and 2: K and `arg`), and is every
-// payload as long as its header says?  The same verdict on every rank, from the same words.
+// Behind the exchange of a word payload: a header of `header` words (status, record count, then the collective's own), `per` words a
+// record.  The header words named in `same` are arguments of the call and must agree over the ranks, in that order of precedence.
+struct AgreedWord { size_t at; const char* name; };
+constexpr size_t LF_HEADER = 5;   // header words of a point labelling's attribute records: status, record count, n_channels or n_classes, K, own n_skipped
 template <typename W>
-static vgs_status check_label_payloads(vgs_tiles* t, const char* fn, const std::vector<std::vector<W>>& gathered, size_t per, const char* arg) {
+static vgs_status check_payloads(vgs_tiles* t, const char* fn, const std::vector<std::vector<W>>& gathered, size_t header, size_t per, const std::vector<AgreedWord>& same) {
   auto word = [&](size_t r, size_t i) { return (int64_t)gathered[r][i]; };
+  for (size_t r = 0; r < gathered.size(); ++r) if (gathered[r].size() < header) return wrong_size(t, fn, r);
+  for (size_t r = 1; r < gathered.size(); ++r)
+    for (const AgreedWord& a : same) if (word(r, a.at) != word(0, a.at)) return disagree(t, fn, r, a.name, word(r, a.at), word(0, a.at));
   for (size_t r = 0; r < gathered.size(); ++r)
-    if (gathered[r].size() < LF_HEADER) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
-  for (size_t r = 1; r < gathered.size(); ++r) {
-    if (word(r, 3) != word(0, 3))
-      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed K = " + std::to_string(word(r, 3)) + ", rank 0 passed " + std::to_string(word(0, 3)));
-    if (word(r, 2) != word(0, 2))
-      return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed " + arg + " = " + std::to_string((int32_t)word(r, 2)) + ", rank 0 passed " + std::to_string((int32_t)word(0, 2)));
-  }
-  for (size_t r = 0; r < gathered.size(); ++r)
-    if (word(r, 1) < 0 || gathered[r].size() != LF_HEADER + (size_t)word(r, 1) * per) return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
+    if (word(r, 1) < 0 || gathered[r].size() != header + (size_t)word(r, 1) * per) return wrong_size(t, fn, r);
   return VGS_OK;
 }
 
@@ -721,6 +751,317 @@ static void invalidate(vgs_tiles* t) { t->ran = false; t->desc_valid = false; t-
 template <int N> static vgs_status get_times(vgs_tiles* t, double (vgs_tiles::*slots)[N], double* ms, int32_t n) {
   if (!t || !ms || n < 0 || n > N) return VGS_E_ARG;
   std::copy(t->*slots, t->*slots + n, ms);
+  return VGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ descriptors and boxes: the drivers
+static Labelling node_labelling(const vgs_tiles* t, const char* fn, Phase ph, bool on_device = false) { return Labelling{fn, ph, false, on_device, nullptr, 0, t->kept, "kept_global"}; }
+static Labelling point_labelling(const char* fn, bool on_device, const int32_t* labels, int64_t n, int64_t K) { return Labelling{fn, PH_POINT_LABELS, true, on_device, labels, n, K, "K"}; }
+static vgs_status bad_label(vgs_tiles* t, const Labelling& L) { return tfail(t, VGS_E_STATE, std::string(L.fn) + ": a rank sent a label >= " + L.limit); }
+
+namespace {
+constexpr size_t PAIRS_PER_ENTRY = sizeof(MomentRec) / sizeof(PairRec);
+struct MomentSent { int64_t own = 0, pairs = 0, bytes = 0; };   // this rank's payload: moment records, pair records, bytes
+}  // namespace
+
+// The moment collective: the descriptors of either labelling.  No point, label or id travels, every point is handled by the rank that
+// loaded it.  This rank's moment records of its own points (one small pipeline on its GPU; a point labelling also has pair records, the
+// head flags of the voxels that hold points of several ranks) -> ONE all_gather_varlen of 128-byte entries: a header (status word,
+// moment-record count; K, pair-record count and own n_skipped as int64 in the first three slots of s), the moment records, then the
+// 16-byte pair records, eight to an entry -> fold_moments and fold_label_pairs, the same on every rank -> n_nodes = folded n_nodes +
+// distinct pairs -> the per-segment algebra on this rank's GPU.  Same bytes on every rank: the folds' inputs and order are the same
+// everywhere, and the algebra is one deterministic device function of its inputs.  Everything a rank can get wrong on its own is found by
+// the context call and travels in the status word; ranks that are each valid but pass different K all leave with VGS_E_ARG behind the
+// exchange.  The caller has opened the collective (`carry`) and places the table, the times and the payload figures.
+static vgs_status moment_collective(vgs_tiles* t, const Labelling& L, vgs_status carry, double (&ms)[T_COUNT], DescTable& D, MomentSent& sent) {
+  const int64_t K = L.K;
+  Stopwatch sw(ms);
+  int64_t n_rec = 0, n_pairs = 0, n_skip = 0;
+  std::vector<MomentRec> payload(1);
+  {   // (the staging arrays are gone before the fold asks for its tables)
+    std::vector<int32_t> lab, nn, pl;
+    std::vector<int64_t> pts;
+    std::vector<float> bb, an;
+    std::vector<double> sm;
+    std::vector<uint64_t> pc;
+    auto room = [&](size_t nr, size_t np) {
+      lab.resize(nr + 1); nn.resize(nr + 1); pts.resize(nr + 1); bb.resize(6 * nr + 1); an.resize(3 * nr + 1); sm.resize(9 * nr + 1); pc.resize(np + 1); pl.resize(np + 1);
+    };
+    if (L.point) {   // count, then fetch; K = 0 included (nothing is cached and the ranks still agree on n_skipped)
+      TCARRY_AS(L.on_device ? vgs_own_point_label_moments_device : vgs_own_point_label_moments,
+                L.on_device ? "vgs_own_point_label_moments_device" : "vgs_own_point_label_moments", t->ctx, K, L.labels, L.n, &n_rec, &n_pairs, &n_skip);
+      if (carry == VGS_OK) room((size_t)n_rec, (size_t)n_pairs);
+      TCARRY(vgs_get_own_point_label_moments(t->ctx, lab.data(), pts.data(), nn.data(), bb.data(), an.data(), sm.data(), pc.data(), pl.data()));
+    } else if (K > 0) {   // at most one record per kept segment and no pair record: a node lies in one rank's region
+      room((size_t)K, 0);
+      TCARRY(vgs_get_own_segment_moments(t->ctx, K, &n_rec, lab.data(), pts.data(), nn.data(), bb.data(), an.data(), sm.data()));
+    }
+    if (carry != VGS_OK) { n_rec = 0; n_pairs = 0; n_skip = 0; }
+    const size_t nr = (size_t)n_rec, np = (size_t)n_pairs;
+    payload.resize(1 + nr + (np + PAIRS_PER_ENTRY - 1) / PAIRS_PER_ENTRY);
+    for (size_t i = 0; i < nr; ++i) payload[1 + i] = pack_moment(lab.data(), pts.data(), nn.data(), bb.data(), an.data(), sm.data(), i);
+    PairRec* pr = reinterpret_cast<PairRec*>(payload.data() + 1 + nr);
+    for (size_t i = 0; i < np; ++i) { pr[i].code = pc[i]; pr[i].label = pl[i]; pr[i].pad = 0; }
+  }
+  const size_t k1 = (size_t)K;
+  set_header(payload[0], carry, (size_t)n_rec);
+  const int64_t own_words[3] = {K, n_pairs, n_skip};
+  std::memcpy(payload[0].s, own_words, sizeof(own_words));
+  sw.lap(T_OWN);
+  std::vector<std::vector<MomentRec>> gathered;
+  TRY(exchange(t, carry, payload, PHASE_NAME[L.phase], sw, T_EXCHANGE, gathered));
+  // every rank was valid on its own: do they describe the same table, and is every payload as long as its header says?
+  const size_t world = gathered.size();
+  std::vector<int64_t> hk(world), hp(world), hr(world);
+  D.n_skipped = 0;
+  for (size_t r = 0; r < world; ++r) {
+    int64_t w[3];
+    std::memcpy(w, gathered[r][0].s, sizeof(w));
+    hk[r] = w[0]; hp[r] = w[1]; D.n_skipped += w[2]; hr[r] = gathered[r][0].n_points;
+  }
+  for (size_t r = 1; r < world; ++r) if (hk[r] != hk[0]) return disagree(t, L.fn, r, "K", hk[r], hk[0]);
+  for (size_t r = 0; r < world; ++r)
+    if (hr[r] < 0 || hp[r] < 0 || gathered[r].size() != 1 + (size_t)hr[r] + ((size_t)hp[r] + PAIRS_PER_ENTRY - 1) / PAIRS_PER_ENTRY) return wrong_size(t, L.fn, r);
+  std::vector<std::vector<MomentRec>> recs(world);
+  std::vector<std::vector<PairRec>> pairs(world);
+  for (size_t r = 0; r < world; ++r) {
+    recs[r].assign(gathered[r].begin() + 1, gathered[r].begin() + 1 + (ptrdiff_t)hr[r]);
+    pairs[r].resize((size_t)hp[r]);
+    if (hp[r] > 0) std::memcpy(pairs[r].data(), gathered[r].data() + 1 + hr[r], (size_t)hp[r] * sizeof(PairRec));
+  }
+  std::vector<int64_t> npts;
+  std::vector<int32_t> nnodes, add;
+  std::vector<float> bbox, anchor;
+  std::vector<double> s9;
+  if (!fold_moments(recs, K, npts, nnodes, bbox, anchor, s9) || !fold_label_pairs(pairs, K, add)) return bad_label(t, L);
+  for (size_t k = 0; k < k1; ++k) nnodes[k] += add[k];
+  sw.lap(T_FOLD);
+  D.npts.resize(k1); D.nnodes.resize(k1); D.bbox.resize(6 * k1); D.cen.resize(3 * k1); D.cov.resize(6 * k1); D.eval.resize(3 * k1); D.evec.resize(9 * k1);
+  D.eig8.resize(8 * k1);
+  TRY(behind_collective(t, vgs_segment_descriptors_from_moments(t->ctx, K, npts.data(), nnodes.data(), bbox.data(), anchor.data(), s9.data(), D.npts.data(), D.nnodes.data(),
+                                                                D.bbox.data(), D.cen.data(), D.cov.data(), D.eval.data(), D.evec.data(), D.eig8.data()),
+                        "vgs_segment_descriptors_from_moments"));
+  sw.lap(T_FINISH);
+  sw.total(T_TOTAL);
+  sent.own = n_rec; sent.pairs = n_pairs; sent.bytes = (int64_t)(payload.size() * sizeof(MomentRec));
+  return VGS_OK;
+}
+
+// The extent collective: the boxes of either labelling about the rows `D` of its descriptor table.  This rank's extents of its own points
+// about the global centroids, in the frames made from the global rows (one small pipeline on its GPU) -> ONE all_gather_varlen of 56-byte
+// records behind a header of status word and record count -> the same host fold on every rank (min / max) -> half and centre on this
+// rank's GPU.  Same bytes on every rank: min and max do not depend on the order, and the finish is one device function of its inputs.
+// The caller has made the table `D` and opened the collective (`carry`); it places the boxes, the times and the bytes sent.
+static vgs_status extent_collective(vgs_tiles* t, const Labelling& L, int32_t frame, vgs_status carry, const DescTable& D, double (&ms)[T_COUNT], BoxTable& B, int64_t& bytes) {
+  const int64_t K = L.K;
+  const size_t k1 = (size_t)K;
+  Stopwatch sw(ms);
+  std::vector<ExtentRec> payload(1);
+  if (carry == VGS_OK && K > 0) {
+    std::vector<int32_t> lab(k1);
+    std::vector<double> lo(3 * k1), hi(3 * k1);
+    int64_t n = 0;
+    if (L.point)
+      TCARRY_AS(L.on_device ? vgs_get_own_point_label_extents_device : vgs_get_own_point_label_extents,
+                L.on_device ? "vgs_get_own_point_label_extents_device" : "vgs_get_own_point_label_extents", t->ctx, K, frame, L.labels, L.n, D.cen.data(), D.cov.data(),
+                D.evec.data(), &n, lab.data(), lo.data(), hi.data());
+    else
+      TCARRY(vgs_get_own_segment_extents(t->ctx, K, frame, D.cen.data(), D.cov.data(), D.evec.data(), &n, lab.data(), lo.data(), hi.data()));
+    if (carry == VGS_OK) payload.reserve(1 + (size_t)n);
+    if (carry == VGS_OK) for (size_t i = 0; i < (size_t)n; ++i) payload.push_back(pack_extent(lab.data(), lo.data(), hi.data(), i));
+  }
+  set_header(payload[0], carry, payload.size() - 1);
+  sw.lap(T_OWN);
+  std::vector<std::vector<ExtentRec>> gathered;
+  TRY(exchange(t, carry, payload, PHASE_NAME[L.phase], sw, T_EXCHANGE, gathered));
+  strip_headers(gathered);
+  std::vector<double> lo, hi;
+  std::vector<uint8_t> reached;
+  if (!fold_extents(gathered, K, lo, hi, reached)) return bad_label(t, L);
+  // a row no record reaches (no labelled point anywhere, n_points = 0 in the descriptor table): lo = hi = 0, so half = 0 and centre = centroid
+  for (size_t k = 0; k < k1; ++k) if (!reached[k]) for (int a = 0; a < 3; ++a) { lo[3 * k + a] = 0.0; hi[3 * k + a] = 0.0; }
+  sw.lap(T_FOLD);
+  std::vector<double> ce(3 * k1), ha(3 * k1), fr(9 * k1);
+  TRY(behind_collective(t, vgs_segment_boxes_from_extents(t->ctx, K, frame, D.cen.data(), D.cov.data(), D.evec.data(), lo.data(), hi.data(), ce.data(), ha.data(), fr.data()),
+                        "vgs_segment_boxes_from_extents"));
+  sw.lap(T_FINISH);
+  sw.total(T_TOTAL);
+  B.center.swap(ce); B.half.swap(ha); B.frame.swap(fr); B.lo.swap(lo); B.hi.swap(hi);
+  bytes = (int64_t)(payload.size() * sizeof(ExtentRec));
+  return VGS_OK;
+}
+
+// The first of a call's two collectives (the descriptors a box call needs) ends the call on every rank alike when a status word in it says
+// so.  A failure of this rank BEHIND that collective (it newly sets t->pending; the peers' tables are complete and they go on) does not:
+// it travels in the second exchange's status word, which the caller takes from t->pending.
+template <typename Step> static vgs_status first_of_two(vgs_tiles* t, Step step) {
+  const vgs_status before = t->pending;
+  const vgs_status s = step();
+  return s != VGS_OK && before == VGS_OK && t->pending != VGS_OK ? VGS_OK : s;
+}
+
+static bool bad_frame(vgs_tiles* t, const char* fn, int32_t frame) {
+  if (frame == VGS_BOX_PRINCIPAL || frame == VGS_BOX_UPRIGHT) return false;
+  t->err = std::string(fn) + ": frame must be VGS_BOX_PRINCIPAL (0) or VGS_BOX_UPRIGHT (1)";
+  return true;
+}
+
+static void put_descriptors(const DescTable& D, int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3, double* evecs9, float* eigen8) {
+  put(D.npts, n_points); put(D.nnodes, n_nodes); put(D.bbox, bbox6); put(D.cen, centroid3); put(D.cov, cov6); put(D.eval, evals3); put(D.evec, evecs9); put(D.eig8, eigen8);
+}
+static void put_boxes(const BoxTable& B, double* center3, double* half3, double* frame9, double* lo3, double* hi3) {
+  put(B.center, center3); put(B.half, half3); put(B.frame, frame9); put(B.lo, lo3); put(B.hi, hi3);
+}
+
+// ------------------------------------------------------------------------------------------------ attribute statistics: the driver
+// The attribute collective: field statistics and class histograms of either labelling.  No attribute travels, every point is counted once,
+// by the rank that loaded it (so a voxel shared by ranks needs no pair records here).  This rank's records of its own rows (one small
+// pipeline on its GPU) -> ONE all_gather_varlen of 8-byte words: a header, then the records in the codec's wire format -> the same host
+// fold on every rank -> (fields) mean, var, min and max on this rank's GPU.  The header: status word, record count, n_channels or
+// n_classes; a point labelling adds K and this rank's own n_skipped (LF_HEADER words in all).  Nothing is cached (the input is the
+// caller's), so every call is collective, K = 0 included.  Everything a rank can get wrong on its own -- n, a NULL input, the channel and
+// stride values, a failing context call -- is found by the context call and travels in the status word; ranks that are each valid but
+// disagree on K or on n_channels / n_classes all leave with VGS_E_ARG behind the exchange.
+namespace {
+// the records a rank can have: one per kept segment, or per label with an own point; 0 where the context refuses the call before it
+// writes (K x per_label counters bound both tables of a point labelling and the histogram of the node labelling)
+size_t record_cap(const vgs_tiles* t, const Labelling& L, int64_t per_label, bool per_ok, bool node_limit) {
+  if (!per_ok || L.K < 0 || L.K > (int64_t)0x7fffffff || ((L.point || node_limit) && L.K * per_label > ((int64_t)1 << 27))) return 0;
+  return (size_t)(L.point ? std::min(L.K, std::max<int64_t>(t->n_own, 0)) : L.K);
+}
+
+// What the collective is told of a table kind: the wire word and the words of a record, the own records (the context call, packed
+// behind the header; no record where the call fails or the context refuses it), unpack, the fold, the finish on the device (FINISH: its
+// name; none for the histogram, whose majority rule is integer work inside the fold) and the caller's arrays.  One object per call: it
+// holds the folded table.
+struct FieldCodec {
+  using Word = uint64_t;
+  using Recs = FieldRecs;
+  static constexpr const char* ARG = "n_channels";
+  static constexpr const char* FINISH = "vgs_segment_field_stats_from_moments";
+  static constexpr bool NODE_LIMIT = false;
+  const float* field; int64_t n; int32_t count; int64_t stride_bytes;
+  int64_t* o_n; double *o_anchor, *o_mean, *o_var; float *o_min, *o_max;
+  std::vector<int64_t> fn;
+  std::vector<double> fa, f1, f2, me, va;
+  std::vector<float> fmn, fmx, omn, omx;
+  FieldCodec(const float* field_, int64_t n_, int32_t n_channels, int64_t stride, int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax)
+      : field(field_), n(n_), count(n_channels), stride_bytes(stride), o_n(n_valid), o_anchor(anchor), o_mean(mean), o_var(var), o_min(vmin), o_max(vmax) {}
+  bool ok() const { return count >= 1 && count <= 64; }
+  size_t C() const { return ok() ? (size_t)count : 0; }
+  size_t words() const { return 1 + 5 * C(); }
+  int64_t header() const { return (int64_t)(uint32_t)count; }
+  void own(vgs_tiles* t, const Labelling& L, size_t cap, vgs_status& carry, int64_t& n_rec, int64_t& n_skip, std::vector<Word>& payload) const {
+    const size_t c = cap * C() + 1;
+    std::vector<int32_t> lab(cap + 1);
+    std::vector<int64_t> nv(c);
+    std::vector<double> an(c), m1(c), m2(c);
+    std::vector<float> mn(c), mx(c);
+    auto p = [cap](auto& v) { return cap > 0 ? v.data() : nullptr; };   // (a call the context refuses writes nothing; so does one without a record)
+    if (L.point)
+      TCARRY_AS(L.on_device ? vgs_own_point_label_field_moments_device : vgs_own_point_label_field_moments,
+                L.on_device ? "vgs_own_point_label_field_moments_device" : "vgs_own_point_label_field_moments", t->ctx, L.K, L.labels, field, n, count, stride_bytes,
+                &n_rec, &n_skip, p(lab), p(nv), p(an), p(m1), p(m2), p(mn), p(mx));
+    else
+      TCARRY_AS(L.on_device ? vgs_get_own_segment_field_moments_device : vgs_get_own_segment_field_moments,
+                L.on_device ? "vgs_get_own_segment_field_moments_device" : "vgs_get_own_segment_field_moments", t->ctx, L.K, field, n, count, stride_bytes, &n_rec,
+                p(lab), p(nv), p(an), p(m1), p(m2), p(mn), p(mx));
+    if (carry != VGS_OK || cap == 0) n_rec = 0;
+    payload.reserve(payload.size() + (size_t)n_rec * words());
+    for (size_t i = 0; i < (size_t)n_rec; ++i) pack_field(payload, lab.data(), nv.data(), an.data(), m1.data(), m2.data(), mn.data(), mx.data(), C(), i);
+  }
+  void unpack(const Word* w, size_t nr, Recs& R) const { unpack_fields(w, nr, C(), R); }
+  bool fold(const std::vector<Recs>& ranks, int64_t K) { return fold_field_moments(ranks, K, (int)C(), fn, fa, f1, f2, fmn, fmx); }
+  vgs_status finish(vgs_ctx* ctx, int64_t K) {
+    const size_t kc = (size_t)K * C() + 1;
+    me.resize(kc); va.resize(kc); omn.resize(kc); omx.resize(kc);
+    return vgs_segment_field_stats_from_moments(ctx, K, count, fn.data(), fa.data(), f1.data(), f2.data(), fmn.data(), fmx.data(), me.data(), va.data(), omn.data(), omx.data());
+  }
+  void place(int64_t K) const {
+    const size_t kc = (size_t)K * C();
+    put(fn, o_n); put(fa, o_anchor); put(me, o_mean, kc); put(va, o_var, kc); put(omn, o_min, kc); put(omx, o_max, kc);
+  }
+};
+
+struct ClassCodec {
+  using Word = int64_t;
+  using Recs = ClassRecs;
+  static constexpr const char* ARG = "n_classes";
+  static constexpr const char* FINISH = nullptr;
+  static constexpr bool NODE_LIMIT = true;
+  const int32_t* cls; int64_t n; int32_t count;
+  int64_t *o_hist, *o_outside; int32_t* o_majority; int64_t* o_count;
+  std::vector<int32_t> fm;
+  std::vector<int64_t> fh, fo, fc;
+  ClassCodec(const int32_t* cls_, int64_t n_, int32_t n_classes, int64_t* hist, int64_t* n_outside, int32_t* majority, int64_t* majority_count)
+      : cls(cls_), n(n_), count(n_classes), o_hist(hist), o_outside(n_outside), o_majority(majority), o_count(majority_count) {}
+  bool ok() const { return count >= 1 && count <= 1024; }
+  size_t nc() const { return ok() ? (size_t)count : 0; }
+  size_t words() const { return 2 + nc(); }
+  int64_t header() const { return (int64_t)count; }
+  void own(vgs_tiles* t, const Labelling& L, size_t cap, vgs_status& carry, int64_t& n_rec, int64_t& n_skip, std::vector<Word>& payload) const {
+    std::vector<int32_t> lab(cap + 1);
+    std::vector<int64_t> hi(cap * nc() + 1), no(cap + 1);
+    auto p = [cap](auto& v) { return cap > 0 ? v.data() : nullptr; };
+    if (L.point)
+      TCARRY_AS(L.on_device ? vgs_own_point_label_class_counts_device : vgs_own_point_label_class_counts,
+                L.on_device ? "vgs_own_point_label_class_counts_device" : "vgs_own_point_label_class_counts", t->ctx, L.K, L.labels, cls, n, count, &n_rec, &n_skip,
+                p(lab), p(hi), p(no));
+    else
+      TCARRY_AS(L.on_device ? vgs_get_own_segment_class_counts_device : vgs_get_own_segment_class_counts,
+                L.on_device ? "vgs_get_own_segment_class_counts_device" : "vgs_get_own_segment_class_counts", t->ctx, L.K, cls, n, count, &n_rec, p(lab), p(hi), p(no));
+    if (carry != VGS_OK || cap == 0) n_rec = 0;
+    payload.reserve(payload.size() + (size_t)n_rec * words());
+    for (size_t i = 0; i < (size_t)n_rec; ++i) pack_class(payload, lab.data(), hi.data(), no.data(), nc(), i);
+  }
+  void unpack(const Word* w, size_t nr, Recs& R) const { unpack_classes(w, nr, nc(), R); }
+  bool fold(const std::vector<Recs>& ranks, int64_t K) { return fold_class_counts(ranks, K, (int)nc(), fh, fo, fm, fc); }
+  vgs_status finish(vgs_ctx*, int64_t) { return VGS_OK; }
+  void place(int64_t) const { put(fh, o_hist); put(fo, o_outside); put(fm, o_majority); put(fc, o_count); }
+};
+}  // namespace
+
+template <typename Codec>
+static vgs_status attribute_collective(vgs_tiles* t, const Labelling& L, Codec A, int64_t* n_skipped) {
+  using W = typename Codec::Word;
+  vgs_status carry;
+  TRY(open_collective(t, L.fn, L.phase, carry));
+  double ms[T_COUNT] = {0};
+  Stopwatch sw(ms);
+  const size_t header = L.point ? LF_HEADER : 3, per = A.words();
+  std::vector<W> payload(header, 0);
+  int64_t n_rec = 0, n_skip = 0;
+  if (carry == VGS_OK) {
+    const size_t cap = record_cap(t, L, A.count, A.ok(), Codec::NODE_LIMIT);
+    A.own(t, L, cap, carry, n_rec, n_skip, payload);   // (its staging arrays are gone before the fold asks for its tables)
+    if (carry != VGS_OK) n_skip = 0;
+  }
+  set_header(payload, carry, n_rec, A.header());
+  if (L.point) { payload[3] = (W)L.K; payload[4] = (W)n_skip; }
+  sw.lap(T_OWN);
+  std::vector<std::vector<W>> gathered;
+  TRY(exchange(t, carry, payload, PHASE_NAME[L.phase], sw, T_EXCHANGE, gathered));
+  // every rank was valid on its own: do they describe the same table, and is every payload as long as its header says?
+  std::vector<AgreedWord> same;
+  if (L.point) same.push_back({3, "K"});
+  same.push_back({2, Codec::ARG});
+  TRY(check_payloads(t, L.fn, gathered, header, per, same));
+  std::vector<typename Codec::Recs> recs(gathered.size());
+  int64_t skipped = 0;
+  for (size_t r = 0; r < gathered.size(); ++r) {
+    A.unpack(gathered[r].data() + header, (size_t)gathered[r][1], recs[r]);
+    if (L.point) skipped += (int64_t)gathered[r][4];
+  }
+  if (!A.fold(recs, L.K)) return bad_label(t, L);
+  sw.lap(T_FOLD);
+  if constexpr (Codec::FINISH != nullptr) {   // (the histogram's VGS_TILES_F_FINISH stays 0)
+    TRY(behind_collective(t, A.finish(t->ctx, L.K), Codec::FINISH));
+    sw.lap(T_FINISH);
+  }
+  sw.total(T_TOTAL, t->ftimes);
+  if (n_skipped) *n_skipped = skipped;
+  A.place(L.K);
+  t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(W));
   return VGS_OK;
 }
 
@@ -988,47 +1329,17 @@ vgs_status vgs_tiles_run(vgs_tiles* t) {
   return VGS_OK;
 }
 
-// Descriptors over the ranks: this rank's moments (one small pipeline on its GPU) -> ONE all_gather_varlen of the records with a header
-// of status word and record count -> the same host fold on every rank -> the per-segment algebra on this rank's GPU.  Same bytes on every
-// rank: the fold's inputs and order are the same everywhere, and the algebra is one deterministic device function of its inputs.
-// (the table into t->d_*: the collective when it is not cached; vgs_tiles_get_segment_boxes takes the table through here too)
-static vgs_status ensure_descriptors(vgs_tiles* t, const char* fn) {   // fn: the caller's name, for the guard's message
+// ------------------------------------------------------------------------------------------------ tables of the node labelling
+// The table into t->desc: the moment collective when it is not cached (vgs_tiles_get_segment_boxes takes the table through here too).
+static vgs_status ensure_descriptors(vgs_tiles* t, const char* fn) {   // fn: the public function that was called, for the guard's message
   if (t->desc_valid) return VGS_OK;
+  const Labelling L = node_labelling(t, fn, PH_DESCRIPTORS);
   vgs_status carry;
-  TRY(open_collective(t, fn, PH_DESCRIPTORS, carry));
-  const int64_t Kg = t->kept;
-  const size_t k1 = (size_t)Kg;
-  double ms[VGS_TILES_D_COUNT] = {0};
-  Stopwatch sw(ms);
-  std::vector<MomentRec> payload(1);
-  if (carry == VGS_OK && Kg > 0) {
-    std::vector<int32_t> lab(k1), nn(k1);
-    std::vector<int64_t> np(k1);
-    std::vector<float> bb(6 * k1), an(3 * k1);
-    std::vector<double> sm(9 * k1);
-    int64_t n = 0;
-    TCARRY(vgs_get_own_segment_moments(t->ctx, Kg, &n, lab.data(), np.data(), nn.data(), bb.data(), an.data(), sm.data()));
-    if (carry == VGS_OK) payload.reserve(1 + (size_t)n);
-    if (carry == VGS_OK) for (size_t i = 0; i < (size_t)n; ++i) payload.push_back(pack_moment(lab.data(), np.data(), nn.data(), bb.data(), an.data(), sm.data(), i));
-  }
-  set_header(payload[0], carry, payload.size() - 1);
-  sw.lap(VGS_TILES_D_MOMENTS);
-  std::vector<std::vector<MomentRec>> gathered;
-  TRY(exchange(t, carry, payload, "descriptors", sw, VGS_TILES_D_EXCHANGE, gathered));
-  strip_headers(gathered);
-  std::vector<int64_t> npts;
-  std::vector<int32_t> nnodes;
-  std::vector<float> bbox, anchor;
-  std::vector<double> s9;
-  if (!fold_moments(gathered, Kg, npts, nnodes, bbox, anchor, s9)) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_descriptors: a rank sent a label >= kept_global");
-  sw.lap(VGS_TILES_D_FOLD);
-  t->d_npts.resize(k1); t->d_nnodes.resize(k1); t->d_bbox.resize(6 * k1); t->d_cen.resize(3 * k1); t->d_cov.resize(6 * k1);
-  t->d_eval.resize(3 * k1); t->d_evec.resize(9 * k1); t->d_eig8.resize(8 * k1);
-  TRY(behind_collective(t, vgs_segment_descriptors_from_moments(t->ctx, Kg, npts.data(), nnodes.data(), bbox.data(), anchor.data(), s9.data(), t->d_npts.data(), t->d_nnodes.data(),
-                                                                t->d_bbox.data(), t->d_cen.data(), t->d_cov.data(), t->d_eval.data(), t->d_evec.data(), t->d_eig8.data()),
-                        "vgs_segment_descriptors_from_moments"));
-  sw.lap(VGS_TILES_D_ALGEBRA);
-  sw.total(VGS_TILES_D_TOTAL, t->dtimes);
+  TRY(open_collective(t, fn, L.phase, carry));
+  double ms[T_COUNT] = {0};
+  MomentSent sent;
+  TRY(moment_collective(t, L, carry, ms, t->desc, sent));
+  std::copy(ms, ms + T_COUNT, t->dtimes);
   t->desc_valid = true;
   return VGS_OK;
 }
@@ -1039,201 +1350,74 @@ vgs_status vgs_tiles_get_segment_descriptors(vgs_tiles* t, int64_t* K, int64_t* 
   if (K) *K = t->kept;
   if (!n_points && !n_nodes && !bbox6 && !centroid3 && !cov6 && !evals3 && !evecs9 && !eigen8) return VGS_OK;   // size query: no collective
   TRY(ensure_descriptors(t, "vgs_tiles_get_segment_descriptors"));
-  put(t->d_npts, n_points); put(t->d_nnodes, n_nodes); put(t->d_bbox, bbox6); put(t->d_cen, centroid3); put(t->d_cov, cov6);
-  put(t->d_eval, evals3); put(t->d_evec, evecs9); put(t->d_eig8, eigen8);
+  put_descriptors(t->desc, n_points, n_nodes, bbox6, centroid3, cov6, evals3, evecs9, eigen8);
   return VGS_OK;
 }
 
 vgs_status vgs_tiles_get_descriptor_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::dtimes, ms, n); }
 
 // ------------------------------------------------------------------------------------------------ tables of a caller's point labelling
-// Descriptors of any per-point labelling over the ranks: no point, label or id travels, every point is handled by the rank that loaded it.
-// This rank's moment and pair records of its own points (vgs_own_point_label_moments, one small pipeline on its GPU) -> ONE
-// all_gather_varlen of 128-byte entries: a header (status word, moment-record count; K, pair-record count and own n_skipped as int64 in the
-// first three slots of s), the moment records, then the 16-byte pair records, eight to an entry -> fold_moments and fold_label_pairs, the
-// same on every rank -> n_nodes = folded n_nodes + distinct pairs -> the per-segment algebra on this rank's GPU.  Nothing is cached (the
-// input is the caller's), so every call is collective, K = 0 included.  Everything a rank can get wrong on its own is found by the context
-// call and travels in the status word; ranks that are each valid but pass different K all leave with VGS_E_ARG behind the exchange.
-namespace {
-struct LabelTable {
-  std::vector<int64_t> npts;
-  std::vector<int32_t> nnodes;
-  std::vector<float> bbox, eig8;
-  std::vector<double> cen, cov, eval, evec;
-  int64_t n_skipped = 0;
-};
-constexpr size_t PAIRS_PER_ENTRY = sizeof(MomentRec) / sizeof(PairRec);
-}  // namespace
-
-static vgs_status label_descriptors(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t n, int64_t K, vgs_status carry,
-                                    double* ms, LabelTable& D) {
-  Stopwatch sw(ms);
-  std::vector<MomentRec> payload(1);
-  int64_t n_rec = 0, n_pairs = 0, n_skip = 0;
-  if (carry == VGS_OK) {
-    TCARRY_AS(on_device ? vgs_own_point_label_moments_device : vgs_own_point_label_moments,
-              on_device ? "vgs_own_point_label_moments_device" : "vgs_own_point_label_moments", t->ctx, K, labels, n, &n_rec, &n_pairs, &n_skip);
-    if (carry != VGS_OK) { n_rec = 0; n_pairs = 0; n_skip = 0; }
-    const size_t nr = (size_t)n_rec, np = (size_t)n_pairs;
-    std::vector<int32_t> lab(nr + 1), nn(nr + 1), pl(np + 1);
-    std::vector<int64_t> pts(nr + 1);
-    std::vector<float> bb(6 * nr + 1), an(3 * nr + 1);
-    std::vector<double> sm(9 * nr + 1);
-    std::vector<uint64_t> pc(np + 1);
-    if (carry == VGS_OK) TCARRY(vgs_get_own_point_label_moments(t->ctx, lab.data(), pts.data(), nn.data(), bb.data(), an.data(), sm.data(), pc.data(), pl.data()));
-    if (carry == VGS_OK) {
-      payload.reserve(1 + nr + (np + PAIRS_PER_ENTRY - 1) / PAIRS_PER_ENTRY);
-      for (size_t i = 0; i < nr; ++i) payload.push_back(pack_moment(lab.data(), pts.data(), nn.data(), bb.data(), an.data(), sm.data(), i));
-      payload.resize(1 + nr + (np + PAIRS_PER_ENTRY - 1) / PAIRS_PER_ENTRY);
-      PairRec* pr = reinterpret_cast<PairRec*>(payload.data() + 1 + nr);
-      for (size_t i = 0; i < np; ++i) { pr[i].code = pc[i]; pr[i].label = pl[i]; pr[i].pad = 0; }
-    } else { n_rec = 0; n_pairs = 0; n_skip = 0; }
-  }
-  set_header(payload[0], carry, (size_t)n_rec);
-  {
-    const int64_t w[3] = {K, n_pairs, n_skip};
-    std::memcpy(payload[0].s, w, sizeof(w));
-  }
-  sw.lap(VGS_TILES_L_OWN);
-  std::vector<std::vector<MomentRec>> gathered;
-  TRY(exchange(t, carry, payload, "point_labels", sw, VGS_TILES_L_EXCHANGE, gathered));
-  // every rank was valid on its own: do they describe the same table, and is every payload as long as its header says?
-  const size_t world = gathered.size();
-  std::vector<int64_t> hk(world), hp(world), hs(world), hr(world);
-  for (size_t r = 0; r < world; ++r) {
-    int64_t w[3];
-    std::memcpy(w, gathered[r][0].s, sizeof(w));
-    hk[r] = w[0]; hp[r] = w[1]; hs[r] = w[2]; hr[r] = gathered[r][0].n_points;
-  }
-  for (size_t r = 1; r < world; ++r)
-    if (hk[r] != hk[0]) return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed K = " + std::to_string(hk[r]) + ", rank 0 passed " + std::to_string(hk[0]));
-  for (size_t r = 0; r < world; ++r)
-    if (hr[r] < 0 || hp[r] < 0 || gathered[r].size() != 1 + (size_t)hr[r] + ((size_t)hp[r] + PAIRS_PER_ENTRY - 1) / PAIRS_PER_ENTRY)
-      return tfail(t, VGS_E_STATE, std::string(fn) + ": rank " + std::to_string(r) + " sent a payload of the wrong size");
-  std::vector<std::vector<MomentRec>> recs(world);
-  std::vector<std::vector<PairRec>> pairs(world);
-  D.n_skipped = 0;
-  for (size_t r = 0; r < world; ++r) {
-    recs[r].assign(gathered[r].begin() + 1, gathered[r].begin() + 1 + (ptrdiff_t)hr[r]);
-    pairs[r].resize((size_t)hp[r]);
-    if (hp[r] > 0) std::memcpy(pairs[r].data(), gathered[r].data() + 1 + hr[r], (size_t)hp[r] * sizeof(PairRec));
-    D.n_skipped += hs[r];
-  }
-  const size_t k1 = (size_t)K;
-  std::vector<int64_t> npts;
-  std::vector<int32_t> nnodes, add;
-  std::vector<float> bbox, anchor;
-  std::vector<double> s9;
-  if (!fold_moments(recs, K, npts, nnodes, bbox, anchor, s9) || !fold_label_pairs(pairs, K, add)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= K");
-  for (size_t k = 0; k < k1; ++k) nnodes[k] += add[k];
-  sw.lap(VGS_TILES_L_FOLD);
-  D.npts.resize(k1); D.nnodes.resize(k1); D.bbox.resize(6 * k1); D.cen.resize(3 * k1); D.cov.resize(6 * k1); D.eval.resize(3 * k1); D.evec.resize(9 * k1);
-  D.eig8.resize(8 * k1);
-  TRY(behind_collective(t, vgs_segment_descriptors_from_moments(t->ctx, K, npts.data(), nnodes.data(), bbox.data(), anchor.data(), s9.data(), D.npts.data(), D.nnodes.data(),
-                                                                D.bbox.data(), D.cen.data(), D.cov.data(), D.eval.data(), D.evec.data(), D.eig8.data()),
-                        "vgs_segment_descriptors_from_moments"));
-  sw.lap(VGS_TILES_L_FINISH);
-  sw.total(VGS_TILES_L_TOTAL);
-  t->l_own = n_rec; t->l_pairs = n_pairs; t->l_bytes = (int64_t)(payload.size() * sizeof(MomentRec));
-  return VGS_OK;
-}
-
-static vgs_status tiles_label_descriptors(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t n, int64_t K, int64_t* n_skipped,
-                                          int64_t* n_points, int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3,
-                                          double* evecs9, float* eigen8) {
-  if (!t) return VGS_E_ARG;
+// Descriptors: the moment collective of THIS labelling.  Nothing is cached (the input is the caller's), so every call is collective.
+static vgs_status tiles_label_descriptors(vgs_tiles* t, const Labelling& L, int64_t* n_skipped, int64_t* n_points, int32_t* n_nodes, float* bbox6,
+                                          double* centroid3, double* cov6, double* evals3, double* evecs9, float* eigen8) {
   vgs_status carry;
-  TRY(open_collective(t, fn, PH_POINT_LABELS, carry));
-  double ms[VGS_TILES_L_COUNT] = {0};
-  LabelTable D;
-  TRY(label_descriptors(t, fn, on_device, labels, n, K, carry, ms, D));
-  std::copy(ms, ms + VGS_TILES_L_COUNT, t->ltimes);
+  TRY(open_collective(t, L.fn, L.phase, carry));
+  double ms[T_COUNT] = {0};
+  DescTable D;
+  MomentSent sent;
+  TRY(moment_collective(t, L, carry, ms, D, sent));
+  std::copy(ms, ms + T_COUNT, t->ltimes);
+  t->l_own = sent.own; t->l_pairs = sent.pairs; t->l_bytes = sent.bytes;
   if (n_skipped) *n_skipped = D.n_skipped;
-  put(D.npts, n_points); put(D.nnodes, n_nodes); put(D.bbox, bbox6); put(D.cen, centroid3); put(D.cov, cov6); put(D.eval, evals3); put(D.evec, evecs9);
-  put(D.eig8, eigen8);
+  put_descriptors(D, n_points, n_nodes, bbox6, centroid3, cov6, evals3, evecs9, eigen8);
   return VGS_OK;
 }
 
 vgs_status vgs_tiles_point_label_descriptors(vgs_tiles* t, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_skipped, int64_t* n_points,
                                              int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3, double* evecs9,
                                              float* eigen8) {
-  return tiles_label_descriptors(t, "vgs_tiles_point_label_descriptors", false, labels_host, n, K, n_skipped, n_points, n_nodes, bbox6, centroid3, cov6, evals3,
-                                 evecs9, eigen8);
+  if (!t) return VGS_E_ARG;
+  return tiles_label_descriptors(t, point_labelling("vgs_tiles_point_label_descriptors", false, labels_host, n, K), n_skipped, n_points, n_nodes, bbox6, centroid3,
+                                 cov6, evals3, evecs9, eigen8);
 }
 
 vgs_status vgs_tiles_point_label_descriptors_device(vgs_tiles* t, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_skipped, int64_t* n_points,
                                                     int32_t* n_nodes, float* bbox6, double* centroid3, double* cov6, double* evals3, double* evecs9,
                                                     float* eigen8) {
-  return tiles_label_descriptors(t, "vgs_tiles_point_label_descriptors_device", true, labels_dev, n, K, n_skipped, n_points, n_nodes, bbox6, centroid3, cov6,
-                                 evals3, evecs9, eigen8);
+  if (!t) return VGS_E_ARG;
+  return tiles_label_descriptors(t, point_labelling("vgs_tiles_point_label_descriptors_device", true, labels_dev, n, K), n_skipped, n_points, n_nodes, bbox6,
+                                 centroid3, cov6, evals3, evecs9, eigen8);
 }
 
-// Boxes of a caller's point labelling: TWO collectives -- the descriptor exchange above, of THIS labelling, then one exchange of this rank's
-// extent records (vgs_get_own_point_label_extents about the global centroids, in the frames made from the global rows), folded by
-// fold_extents and finished by vgs_segment_boxes_from_extents.  A bad frame travels in the first status word.  Nothing outlives the call.
-static vgs_status tiles_label_boxes(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t n, int64_t K, int32_t frame,
-                                    double* center3, double* half3, double* frame9, double* lo3, double* hi3) {
-  if (!t) return VGS_E_ARG;
+// Boxes: TWO collectives -- the moment collective of THIS labelling, then the extent collective about its rows.  A bad frame travels in the
+// first status word.  Nothing outlives the call; the times are the sums over both collectives, the bytes too.
+static vgs_status tiles_label_boxes(vgs_tiles* t, const Labelling& L, int32_t frame, double* center3, double* half3, double* frame9, double* lo3, double* hi3) {
   vgs_status carry;
-  TRY(open_collective(t, fn, PH_POINT_LABELS, carry));
-  if (carry == VGS_OK && frame != VGS_BOX_PRINCIPAL && frame != VGS_BOX_UPRIGHT) {
-    carry = VGS_E_ARG;
-    t->err = std::string(fn) + ": frame must be VGS_BOX_PRINCIPAL (0) or VGS_BOX_UPRIGHT (1)";
-  }
-  double ms[VGS_TILES_L_COUNT] = {0};
-  LabelTable D;
-  {
-    // a failure of this rank BEHIND the first collective (it newly sets t->pending; the peers' tables are complete and they go on) travels
-    // in the second exchange's status word
-    const vgs_status before = t->pending;
-    const vgs_status sd = label_descriptors(t, fn, on_device, labels, n, K, carry, ms, D);
-    if (sd != VGS_OK && !(before == VGS_OK && t->pending != VGS_OK)) return sd;
-  }
-  carry = t->pending;
-  const size_t k1 = (size_t)K;
-  double ms2[VGS_TILES_L_COUNT] = {0};
-  Stopwatch sw(ms2);
-  std::vector<ExtentRec> payload(1);
-  if (carry == VGS_OK && K > 0) {
-    std::vector<int32_t> lab(k1);
-    std::vector<double> lo(3 * k1), hi(3 * k1);
-    int64_t nr = 0;
-    TCARRY_AS(on_device ? vgs_get_own_point_label_extents_device : vgs_get_own_point_label_extents,
-              on_device ? "vgs_get_own_point_label_extents_device" : "vgs_get_own_point_label_extents", t->ctx, K, frame, labels, n, D.cen.data(), D.cov.data(),
-              D.evec.data(), &nr, lab.data(), lo.data(), hi.data());
-    if (carry == VGS_OK) payload.reserve(1 + (size_t)nr);
-    if (carry == VGS_OK) for (size_t i = 0; i < (size_t)nr; ++i) payload.push_back(pack_extent(lab.data(), lo.data(), hi.data(), i));
-  }
-  set_header(payload[0], carry, payload.size() - 1);
-  sw.lap(VGS_TILES_L_OWN);
-  std::vector<std::vector<ExtentRec>> gathered;
-  TRY(exchange(t, carry, payload, "point_labels", sw, VGS_TILES_L_EXCHANGE, gathered));
-  strip_headers(gathered);
-  std::vector<double> lo, hi;
-  std::vector<uint8_t> reached;
-  if (!fold_extents(gathered, K, lo, hi, reached)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= K");
-  // a row no record reaches (no labelled point anywhere): lo = hi = 0, so half = 0 and centre = centroid
-  for (size_t k = 0; k < k1; ++k) if (!reached[k]) for (int a = 0; a < 3; ++a) { lo[3 * k + a] = 0.0; hi[3 * k + a] = 0.0; }
-  sw.lap(VGS_TILES_L_FOLD);
-  std::vector<double> ce(3 * k1), ha(3 * k1), fr(9 * k1);
-  TRY(behind_collective(t, vgs_segment_boxes_from_extents(t->ctx, K, frame, D.cen.data(), D.cov.data(), D.evec.data(), lo.data(), hi.data(), ce.data(), ha.data(), fr.data()),
-                        "vgs_segment_boxes_from_extents"));
-  sw.lap(VGS_TILES_L_FINISH);
-  sw.total(VGS_TILES_L_TOTAL);
-  for (int i = 0; i < VGS_TILES_L_COUNT; ++i) t->ltimes[i] = ms[i] + ms2[i];   // both collectives of the call
-  t->l_bytes += (int64_t)(payload.size() * sizeof(ExtentRec));
-  put(ce, center3); put(ha, half3); put(fr, frame9); put(lo, lo3); put(hi, hi3);
+  TRY(open_collective(t, L.fn, L.phase, carry));
+  if (carry == VGS_OK && bad_frame(t, L.fn, frame)) carry = VGS_E_ARG;
+  double ms[T_COUNT] = {0}, ms2[T_COUNT] = {0};
+  DescTable D;
+  MomentSent sent;
+  TRY(first_of_two(t, [&] { return moment_collective(t, L, carry, ms, D, sent); }));
+  BoxTable B;
+  int64_t bytes = 0;
+  TRY(extent_collective(t, L, frame, t->pending, D, ms2, B, bytes));
+  for (int i = 0; i < T_COUNT; ++i) t->ltimes[i] = ms[i] + ms2[i];
+  t->l_own = sent.own; t->l_pairs = sent.pairs; t->l_bytes = sent.bytes + bytes;
+  put_boxes(B, center3, half3, frame9, lo3, hi3);
   return VGS_OK;
 }
 
 vgs_status vgs_tiles_point_label_boxes(vgs_tiles* t, const int32_t* labels_host, int64_t n, int64_t K, int32_t frame, double* center3, double* half3,
                                        double* frame9, double* lo3, double* hi3) {
-  return tiles_label_boxes(t, "vgs_tiles_point_label_boxes", false, labels_host, n, K, frame, center3, half3, frame9, lo3, hi3);
+  if (!t) return VGS_E_ARG;
+  return tiles_label_boxes(t, point_labelling("vgs_tiles_point_label_boxes", false, labels_host, n, K), frame, center3, half3, frame9, lo3, hi3);
 }
 
 vgs_status vgs_tiles_point_label_boxes_device(vgs_tiles* t, const int32_t* labels_dev, int64_t n, int64_t K, int32_t frame, double* center3,
                                               double* half3, double* frame9, double* lo3, double* hi3) {
-  return tiles_label_boxes(t, "vgs_tiles_point_label_boxes_device", true, labels_dev, n, K, frame, center3, half3, frame9, lo3, hi3);
+  if (!t) return VGS_E_ARG;
+  return tiles_label_boxes(t, point_labelling("vgs_tiles_point_label_boxes_device", true, labels_dev, n, K), frame, center3, half3, frame9, lo3, hi3);
 }
 
 vgs_status vgs_tiles_get_point_label_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::ltimes, ms, n); }
@@ -1261,60 +1445,27 @@ vgs_status vgs_tiles_fold_label_pairs(int world, const int64_t* rec_off, const u
   return VGS_OK;
 }
 
-// Boxes over the ranks: the global descriptor table (its own collective when it is not cached) -> this rank's extents of its own points
-// about the global centroids, in the frames made from the global rows (one small pipeline on its GPU) -> ONE all_gather_varlen of the
-// records with a header of record count and status word -> the same host fold on every rank (min / max) -> half and centre on this
-// rank's GPU.  Same bytes on every rank: min and max do not depend on the order, and the finish is one device function of its inputs.
+// Boxes of the node labelling: the global descriptor table (its own collective when it is not cached; its guard is this call's), then the
+// extent collective about its rows; cached per frame.  A bad frame is refused here, before any collective.
 vgs_status vgs_tiles_get_segment_boxes(vgs_tiles* t, int32_t frame, int64_t* K, double* center3, double* half3, double* frame9, double* lo3,
                                        double* hi3) {
+  const char* fn = "vgs_tiles_get_segment_boxes";
   if (!t) return VGS_E_ARG;
-  if (frame != VGS_BOX_PRINCIPAL && frame != VGS_BOX_UPRIGHT) return tfail(t, VGS_E_ARG, "vgs_tiles_get_segment_boxes: frame must be VGS_BOX_PRINCIPAL (0) or VGS_BOX_UPRIGHT (1)");
+  if (bad_frame(t, fn, frame)) return VGS_E_ARG;
   if (K) *K = t->kept;
   if (!center3 && !half3 && !frame9 && !lo3 && !hi3) return VGS_OK;   // size query: no collective
   if (!t->box_valid[frame]) {
-    {
-      // The descriptor collective (when the table is not cached; its guard is this call's) ends the call on every rank alike when a status
-      // word in it says so.  A failure of this rank BEHIND that collective (it newly sets t->pending; the peers' tables are complete and they
-      // go on) travels in the box exchange's status word: the opening below takes it up.
-      const vgs_status before = t->pending;
-      const vgs_status sd = ensure_descriptors(t, "vgs_tiles_get_segment_boxes");
-      if (sd != VGS_OK && !(before == VGS_OK && t->pending != VGS_OK)) return sd;
-    }
+    TRY(first_of_two(t, [&] { return ensure_descriptors(t, fn); }));
+    const Labelling L = node_labelling(t, fn, PH_BOXES);
     vgs_status carry;
-    TRY(open_collective(t, "vgs_tiles_get_segment_boxes", PH_BOXES, carry));
-    const int64_t Kg = t->kept;
-    const size_t k1 = (size_t)Kg;
-    double ms[VGS_TILES_B_COUNT] = {0};
-    Stopwatch sw(ms);
-    std::vector<ExtentRec> payload(1);
-    if (carry == VGS_OK && Kg > 0) {
-      std::vector<int32_t> lab(k1);
-      std::vector<double> lo(3 * k1), hi(3 * k1);
-      int64_t n = 0;
-      TCARRY(vgs_get_own_segment_extents(t->ctx, Kg, frame, t->d_cen.data(), t->d_cov.data(), t->d_evec.data(), &n, lab.data(), lo.data(), hi.data()));
-      if (carry == VGS_OK) payload.reserve(1 + (size_t)n);
-      if (carry == VGS_OK) for (size_t i = 0; i < (size_t)n; ++i) payload.push_back(pack_extent(lab.data(), lo.data(), hi.data(), i));
-    }
-    set_header(payload[0], carry, payload.size() - 1);
-    sw.lap(VGS_TILES_B_EXTENTS);
-    std::vector<std::vector<ExtentRec>> gathered;
-    TRY(exchange(t, carry, payload, "boxes", sw, VGS_TILES_B_EXCHANGE, gathered));
-    strip_headers(gathered);
-    std::vector<double> lo, hi;
-    std::vector<uint8_t> reached;
-    if (!fold_extents(gathered, Kg, lo, hi, reached)) return tfail(t, VGS_E_STATE, "vgs_tiles_get_segment_boxes: a rank sent a label >= kept_global");
-    // a row no record reaches (no labelled point anywhere, n_points = 0 in the descriptor table): lo = hi = 0, so half = 0 and centre = centroid
-    for (size_t k = 0; k < k1; ++k) if (!reached[k]) for (int a = 0; a < 3; ++a) { lo[3 * k + a] = 0.0; hi[3 * k + a] = 0.0; }
-    sw.lap(VGS_TILES_B_FOLD);
-    std::vector<double> ce(3 * k1), ha(3 * k1), fr(9 * k1);
-    TRY(behind_collective(t, vgs_segment_boxes_from_extents(t->ctx, Kg, frame, t->d_cen.data(), t->d_cov.data(), t->d_evec.data(), lo.data(), hi.data(), ce.data(), ha.data(), fr.data()),
-                          "vgs_segment_boxes_from_extents"));
-    sw.lap(VGS_TILES_B_FINISH);
-    sw.total(VGS_TILES_B_TOTAL, t->btimes);
-    t->b_center[frame].swap(ce); t->b_half[frame].swap(ha); t->b_frame[frame].swap(fr); t->b_lo[frame].swap(lo); t->b_hi[frame].swap(hi);
+    TRY(open_collective(t, fn, L.phase, carry));   // (takes up a failure behind the descriptor collective)
+    double ms[T_COUNT] = {0};
+    int64_t bytes = 0;
+    TRY(extent_collective(t, L, frame, carry, t->desc, ms, t->box[frame], bytes));
+    std::copy(ms, ms + T_COUNT, t->btimes);
     t->box_valid[frame] = true;
   }
-  put(t->b_center[frame], center3); put(t->b_half[frame], half3); put(t->b_frame[frame], frame9); put(t->b_lo[frame], lo3); put(t->b_hi[frame], hi3);
+  put_boxes(t->box[frame], center3, half3, frame9, lo3, hi3);
   return VGS_OK;
 }
 
@@ -1338,276 +1489,61 @@ vgs_status vgs_tiles_fold_extents(int world, const int64_t* rec_off, const int32
 }
 
 // ------------------------------------------------------------------------------------------------ attribute statistics
-// Field statistics over the ranks: no attribute travels, every point is counted by the rank that loaded it.  This rank's moments of its
-// own rows (one small pipeline on its GPU) -> ONE all_gather_varlen of the records behind a header of status word, record count and
-// n_channels -> the same host fold on every rank -> mean, var, min and max on this rank's GPU.  Nothing is cached (the input is the
-// caller's), so every call is collective.  Everything a rank can get wrong on its own -- n, a NULL input, the channel and stride values, a
-// failing context call -- is found by the context call and travels in the status word.
-static vgs_status tiles_field_stats(vgs_tiles* t, const char* fn, bool on_device, const float* field, int64_t n, int32_t n_channels,
-                                    int64_t stride_bytes, int64_t* K, int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin,
-                                    float* vmax) {
-  if (!t) return VGS_E_ARG;
-  if (K) *K = t->kept;
-  vgs_status carry;
-  TRY(open_collective(t, fn, PH_FIELDS, carry));
-  const int64_t Kg = t->kept;
-  const size_t k1 = (size_t)Kg;
-  double ms[VGS_TILES_F_COUNT] = {0};
-  Stopwatch sw(ms);
-  const bool c_ok = n_channels >= 1 && n_channels <= 64;
-  const size_t C = c_ok ? (size_t)n_channels : 0;
-  std::vector<uint64_t> payload(3, 0);
-  int64_t n_rec = 0;
-  if (carry == VGS_OK) {
-    const size_t cap = k1 * C + 1;
-    std::vector<int32_t> lab(k1 + 1);
-    std::vector<int64_t> nv(cap);
-    std::vector<double> an(cap), m1(cap), m2(cap);
-    std::vector<float> mn(cap), mx(cap);
-    // (a channel count out of range is refused by the context before it writes: no array is needed)
-    TCARRY_AS(on_device ? vgs_get_own_segment_field_moments_device : vgs_get_own_segment_field_moments,
-              on_device ? "vgs_get_own_segment_field_moments_device" : "vgs_get_own_segment_field_moments", t->ctx, Kg, field, n, n_channels, stride_bytes, &n_rec,
-              c_ok ? lab.data() : nullptr, c_ok ? nv.data() : nullptr, c_ok ? an.data() : nullptr, c_ok ? m1.data() : nullptr, c_ok ? m2.data() : nullptr, c_ok ? mn.data() : nullptr, c_ok ? mx.data() : nullptr);
-    if (carry != VGS_OK) n_rec = 0;
-    payload.reserve(3 + (size_t)n_rec * (1 + 5 * C));
-    for (size_t i = 0; i < (size_t)n_rec; ++i) pack_field(payload, lab.data(), nv.data(), an.data(), m1.data(), m2.data(), mn.data(), mx.data(), C, i);
-  }
-  set_header(payload, carry, n_rec, (int64_t)(uint32_t)n_channels);
-  sw.lap(VGS_TILES_F_OWN);
-  std::vector<std::vector<uint64_t>> gathered;
-  TRY(exchange(t, carry, payload, "fields", sw, VGS_TILES_F_EXCHANGE, gathered));
-  TRY(check_word_payloads(t, fn, gathered, 1 + 5 * C, "n_channels"));
-  std::vector<FieldRecs> recs(gathered.size());
-  for (size_t r = 0; r < gathered.size(); ++r) unpack_fields(gathered[r].data() + 3, (size_t)gathered[r][1], C, recs[r]);
-  std::vector<int64_t> fn_;
-  std::vector<double> fa, f1, f2;
-  std::vector<float> fmn, fmx;
-  if (!fold_field_moments(recs, Kg, (int)C, fn_, fa, f1, f2, fmn, fmx)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= kept_global");
-  sw.lap(VGS_TILES_F_FOLD);
-  const size_t kc = k1 * C;
-  std::vector<double> me(kc + 1), va(kc + 1);
-  std::vector<float> omn(kc + 1), omx(kc + 1);
-  TRY(behind_collective(t, vgs_segment_field_stats_from_moments(t->ctx, Kg, n_channels, fn_.data(), fa.data(), f1.data(), f2.data(), fmn.data(), fmx.data(), me.data(), va.data(), omn.data(), omx.data()),
-                        "vgs_segment_field_stats_from_moments"));
-  sw.lap(VGS_TILES_F_FINISH);
-  sw.total(VGS_TILES_F_TOTAL, t->ftimes);
-  put(fn_, n_valid); put(fa, anchor); put(me, mean, kc); put(va, var, kc); put(omn, vmin, kc); put(omx, vmax, kc);
-  t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(uint64_t));
-  return VGS_OK;
-}
-
+// the node labelling: row k covers the points that the run labels k, K = kept rows
 vgs_status vgs_tiles_segment_field_stats(vgs_tiles* t, const float* field_host, int64_t n, int32_t n_channels, int64_t stride_bytes, int64_t* K,
                                          int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax) {
-  return tiles_field_stats(t, "vgs_tiles_segment_field_stats", false, field_host, n, n_channels, stride_bytes, K, n_valid, anchor, mean, var, vmin, vmax);
+  if (!t) return VGS_E_ARG;
+  if (K) *K = t->kept;
+  return attribute_collective(t, node_labelling(t, "vgs_tiles_segment_field_stats", PH_FIELDS), FieldCodec(field_host, n, n_channels, stride_bytes, n_valid, anchor, mean, var, vmin, vmax), nullptr);
 }
 
 vgs_status vgs_tiles_segment_field_stats_device(vgs_tiles* t, const float* field_dev, int64_t n, int32_t n_channels, int64_t stride_bytes, int64_t* K,
                                                 int64_t* n_valid, double* anchor, double* mean, double* var, float* vmin, float* vmax) {
-  return tiles_field_stats(t, "vgs_tiles_segment_field_stats_device", true, field_dev, n, n_channels, stride_bytes, K, n_valid, anchor, mean, var, vmin,
-                           vmax);
-}
-
-// The class histogram over the ranks: this rank's rows of its own points -> ONE all_gather_varlen behind a header of status word, record
-// count and n_classes -> integer adds and the majority rule on the host, the same on every rank.
-static vgs_status tiles_class_hist(vgs_tiles* t, const char* fn, bool on_device, const int32_t* cls, int64_t n, int32_t n_classes, int64_t* K,
-                                   int64_t* hist, int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
   if (!t) return VGS_E_ARG;
   if (K) *K = t->kept;
-  vgs_status carry;
-  TRY(open_collective(t, fn, PH_FIELDS, carry));
-  const int64_t Kg = t->kept;
-  const size_t k1 = (size_t)Kg;
-  double ms[VGS_TILES_F_COUNT] = {0};
-  Stopwatch sw(ms);
-  const bool c_ok = n_classes >= 1 && n_classes <= 1024 && Kg * (int64_t)n_classes <= ((int64_t)1 << 27);
-  const size_t nc = c_ok ? (size_t)n_classes : 0;
-  std::vector<int64_t> payload(3, 0);
-  int64_t n_rec = 0;
-  if (carry == VGS_OK) {
-    std::vector<int32_t> lab(k1 + 1);
-    std::vector<int64_t> hi(k1 * nc + 1), no(k1 + 1);
-    // (a class count out of range is refused by the context before it writes: no array is needed)
-    TCARRY_AS(on_device ? vgs_get_own_segment_class_counts_device : vgs_get_own_segment_class_counts,
-              on_device ? "vgs_get_own_segment_class_counts_device" : "vgs_get_own_segment_class_counts", t->ctx, Kg, cls, n, n_classes, &n_rec,
-              c_ok ? lab.data() : nullptr, c_ok ? hi.data() : nullptr, c_ok ? no.data() : nullptr);
-    if (carry != VGS_OK) n_rec = 0;
-    payload.reserve(3 + (size_t)n_rec * (2 + nc));
-    for (size_t i = 0; i < (size_t)n_rec; ++i) pack_class(payload, lab.data(), hi.data(), no.data(), nc, i);
-  }
-  set_header(payload, carry, n_rec, (int64_t)n_classes);
-  sw.lap(VGS_TILES_F_OWN);
-  std::vector<std::vector<int64_t>> gathered;
-  TRY(exchange(t, carry, payload, "fields", sw, VGS_TILES_F_EXCHANGE, gathered));
-  TRY(check_word_payloads(t, fn, gathered, 2 + nc, "n_classes"));
-  std::vector<ClassRecs> recs(gathered.size());
-  for (size_t r = 0; r < gathered.size(); ++r) unpack_classes(gathered[r].data() + 3, (size_t)gathered[r][1], nc, recs[r]);
-  std::vector<int64_t> fh, fo, fc;
-  std::vector<int32_t> fm;
-  if (!fold_class_counts(recs, Kg, (int)nc, fh, fo, fm, fc)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= kept_global");
-  sw.lap(VGS_TILES_F_FOLD);
-  sw.total(VGS_TILES_F_TOTAL, t->ftimes);   // (VGS_TILES_F_FINISH stays 0: the majority rule is integer work inside the fold)
-  put(fh, hist); put(fo, n_outside); put(fm, majority); put(fc, majority_count);
-  t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(int64_t));
-  return VGS_OK;
+  return attribute_collective(t, node_labelling(t, "vgs_tiles_segment_field_stats_device", PH_FIELDS, true), FieldCodec(field_dev, n, n_channels, stride_bytes, n_valid, anchor, mean, var, vmin, vmax), nullptr);
 }
 
 vgs_status vgs_tiles_segment_class_histogram(vgs_tiles* t, const int32_t* cls_host, int64_t n, int32_t n_classes, int64_t* K, int64_t* hist,
                                              int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
-  return tiles_class_hist(t, "vgs_tiles_segment_class_histogram", false, cls_host, n, n_classes, K, hist, n_outside, majority, majority_count);
+  if (!t) return VGS_E_ARG;
+  if (K) *K = t->kept;
+  return attribute_collective(t, node_labelling(t, "vgs_tiles_segment_class_histogram", PH_FIELDS), ClassCodec(cls_host, n, n_classes, hist, n_outside, majority, majority_count), nullptr);
 }
 
 vgs_status vgs_tiles_segment_class_histogram_device(vgs_tiles* t, const int32_t* cls_dev, int64_t n, int32_t n_classes, int64_t* K, int64_t* hist,
                                                     int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
-  return tiles_class_hist(t, "vgs_tiles_segment_class_histogram_device", true, cls_dev, n, n_classes, K, hist, n_outside, majority, majority_count);
-}
-
-// The two attribute tables of a caller's point labelling over the ranks (K rows of the caller's).  The protocol of the two calls above with
-// the records of vgs_own_point_label_field_moments / vgs_own_point_label_class_counts: ONE all_gather_varlen of 8-byte words -- a header of
-// FIVE words (status word, record count, n_channels or n_classes, K, this rank's own n_skipped), then the records in the wire format of
-// pack_field / pack_class, unchanged -> the same folds, unchanged -> (fields) vgs_segment_field_stats_from_moments.  No field counts nodes,
-// and every point is counted once, by the rank that loaded it: a voxel shared by ranks needs no pair records here.  Nothing is cached, so
-// every call is collective, K = 0 included (the ranks still agree on n_skipped).  Everything a rank can get wrong on its own is found by
-// the context call and travels in the status word; ranks that are each valid but disagree on K or on n_channels / n_classes all leave with
-// VGS_E_ARG behind the exchange.
-namespace {
-// the records a rank can have: one per label with an own point; 0 where the context refuses the call before it writes
-size_t label_record_cap(const vgs_tiles* t, int64_t K, int64_t per_label, bool per_ok) {
-  if (!per_ok || K < 0 || K > (int64_t)0x7fffffff || K * per_label > ((int64_t)1 << 27)) return 0;
-  return (size_t)std::min(K, std::max<int64_t>(t->n_own, 0));
-}
-}  // namespace
-
-static vgs_status tiles_label_field_stats(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t K, const float* field, int64_t n,
-                                          int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor, double* mean,
-                                          double* var, float* vmin, float* vmax) {
   if (!t) return VGS_E_ARG;
-  vgs_status carry;
-  TRY(open_collective(t, fn, PH_POINT_LABELS, carry));
-  double ms[VGS_TILES_F_COUNT] = {0};
-  Stopwatch sw(ms);
-  const bool c_ok = n_channels >= 1 && n_channels <= 64;
-  const size_t C = c_ok ? (size_t)n_channels : 0;
-  std::vector<uint64_t> payload(LF_HEADER, 0);
-  int64_t n_rec = 0, n_skip = 0;
-  if (carry == VGS_OK) {
-    const size_t cap = label_record_cap(t, K, n_channels, c_ok);
-    const bool w = cap > 0;   // (a call the context refuses writes nothing; so does one without a record)
-    std::vector<int32_t> lab(cap + 1);
-    std::vector<int64_t> nv(cap * C + 1);
-    std::vector<double> an(cap * C + 1), m1(cap * C + 1), m2(cap * C + 1);
-    std::vector<float> mn(cap * C + 1), mx(cap * C + 1);
-    TCARRY_AS(on_device ? vgs_own_point_label_field_moments_device : vgs_own_point_label_field_moments,
-              on_device ? "vgs_own_point_label_field_moments_device" : "vgs_own_point_label_field_moments", t->ctx, K, labels, field, n, n_channels, stride_bytes,
-              &n_rec, &n_skip, w ? lab.data() : nullptr, w ? nv.data() : nullptr, w ? an.data() : nullptr, w ? m1.data() : nullptr, w ? m2.data() : nullptr,
-              w ? mn.data() : nullptr, w ? mx.data() : nullptr);
-    if (carry != VGS_OK || !w) { n_rec = 0; }
-    if (carry != VGS_OK) n_skip = 0;
-    payload.reserve(LF_HEADER + (size_t)n_rec * (1 + 5 * C));
-    for (size_t i = 0; i < (size_t)n_rec; ++i) pack_field(payload, lab.data(), nv.data(), an.data(), m1.data(), m2.data(), mn.data(), mx.data(), C, i);
-  }
-  set_header(payload, carry, n_rec, (int64_t)(uint32_t)n_channels);
-  payload[3] = (uint64_t)K; payload[4] = (uint64_t)n_skip;
-  sw.lap(VGS_TILES_F_OWN);
-  std::vector<std::vector<uint64_t>> gathered;
-  TRY(exchange(t, carry, payload, "point_labels", sw, VGS_TILES_F_EXCHANGE, gathered));
-  TRY(check_label_payloads(t, fn, gathered, 1 + 5 * C, "n_channels"));
-  std::vector<FieldRecs> recs(gathered.size());
-  int64_t skipped = 0;
-  for (size_t r = 0; r < gathered.size(); ++r) {
-    unpack_fields(gathered[r].data() + LF_HEADER, (size_t)gathered[r][1], C, recs[r]);
-    skipped += (int64_t)gathered[r][4];
-  }
-  std::vector<int64_t> fn_;
-  std::vector<double> fa, f1, f2;
-  std::vector<float> fmn, fmx;
-  if (!fold_field_moments(recs, K, (int)C, fn_, fa, f1, f2, fmn, fmx)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= K");
-  sw.lap(VGS_TILES_F_FOLD);
-  const size_t kc = (size_t)K * C;
-  std::vector<double> me(kc + 1), va(kc + 1);
-  std::vector<float> omn(kc + 1), omx(kc + 1);
-  TRY(behind_collective(t, vgs_segment_field_stats_from_moments(t->ctx, K, n_channels, fn_.data(), fa.data(), f1.data(), f2.data(), fmn.data(), fmx.data(), me.data(), va.data(), omn.data(), omx.data()),
-                        "vgs_segment_field_stats_from_moments"));
-  sw.lap(VGS_TILES_F_FINISH);
-  sw.total(VGS_TILES_F_TOTAL, t->ftimes);
-  if (n_skipped) *n_skipped = skipped;
-  put(fn_, n_valid); put(fa, anchor); put(me, mean, kc); put(va, var, kc); put(omn, vmin, kc); put(omx, vmax, kc);
-  t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(uint64_t));
-  return VGS_OK;
+  if (K) *K = t->kept;
+  return attribute_collective(t, node_labelling(t, "vgs_tiles_segment_class_histogram_device", PH_FIELDS, true), ClassCodec(cls_dev, n, n_classes, hist, n_outside, majority, majority_count), nullptr);
 }
 
+// a caller's point labelling: row k covers the own points, over all ranks, that the caller labels k, K rows of the caller's
 vgs_status vgs_tiles_point_label_field_stats(vgs_tiles* t, const int32_t* labels_host, int64_t K, const float* field_host, int64_t n, int32_t n_channels,
                                              int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor, double* mean, double* var,
                                              float* vmin, float* vmax) {
-  return tiles_label_field_stats(t, "vgs_tiles_point_label_field_stats", false, labels_host, K, field_host, n, n_channels, stride_bytes, n_skipped, n_valid,
-                                 anchor, mean, var, vmin, vmax);
+  if (!t) return VGS_E_ARG;
+  return attribute_collective(t, point_labelling("vgs_tiles_point_label_field_stats", false, labels_host, n, K), FieldCodec(field_host, n, n_channels, stride_bytes, n_valid, anchor, mean, var, vmin, vmax), n_skipped);
 }
 
 vgs_status vgs_tiles_point_label_field_stats_device(vgs_tiles* t, const int32_t* labels_dev, int64_t K, const float* field_dev, int64_t n,
                                                     int32_t n_channels, int64_t stride_bytes, int64_t* n_skipped, int64_t* n_valid, double* anchor,
                                                     double* mean, double* var, float* vmin, float* vmax) {
-  return tiles_label_field_stats(t, "vgs_tiles_point_label_field_stats_device", true, labels_dev, K, field_dev, n, n_channels, stride_bytes, n_skipped,
-                                 n_valid, anchor, mean, var, vmin, vmax);
-}
-
-static vgs_status tiles_label_class_hist(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t K, const int32_t* cls, int64_t n,
-                                         int32_t n_classes, int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority,
-                                         int64_t* majority_count) {
   if (!t) return VGS_E_ARG;
-  vgs_status carry;
-  TRY(open_collective(t, fn, PH_POINT_LABELS, carry));
-  double ms[VGS_TILES_F_COUNT] = {0};
-  Stopwatch sw(ms);
-  const bool c_ok = n_classes >= 1 && n_classes <= 1024;
-  const size_t nc = c_ok ? (size_t)n_classes : 0;
-  std::vector<int64_t> payload(LF_HEADER, 0);
-  int64_t n_rec = 0, n_skip = 0;
-  if (carry == VGS_OK) {
-    const size_t cap = label_record_cap(t, K, n_classes, c_ok);
-    const bool w = cap > 0;
-    std::vector<int32_t> lab(cap + 1);
-    std::vector<int64_t> hi(cap * nc + 1), no(cap + 1);
-    TCARRY_AS(on_device ? vgs_own_point_label_class_counts_device : vgs_own_point_label_class_counts,
-              on_device ? "vgs_own_point_label_class_counts_device" : "vgs_own_point_label_class_counts", t->ctx, K, labels, cls, n, n_classes, &n_rec, &n_skip,
-              w ? lab.data() : nullptr, w ? hi.data() : nullptr, w ? no.data() : nullptr);
-    if (carry != VGS_OK || !w) { n_rec = 0; }
-    if (carry != VGS_OK) n_skip = 0;
-    payload.reserve(LF_HEADER + (size_t)n_rec * (2 + nc));
-    for (size_t i = 0; i < (size_t)n_rec; ++i) pack_class(payload, lab.data(), hi.data(), no.data(), nc, i);
-  }
-  set_header(payload, carry, n_rec, (int64_t)n_classes);
-  payload[3] = K; payload[4] = n_skip;
-  sw.lap(VGS_TILES_F_OWN);
-  std::vector<std::vector<int64_t>> gathered;
-  TRY(exchange(t, carry, payload, "point_labels", sw, VGS_TILES_F_EXCHANGE, gathered));
-  TRY(check_label_payloads(t, fn, gathered, 2 + nc, "n_classes"));
-  std::vector<ClassRecs> recs(gathered.size());
-  int64_t skipped = 0;
-  for (size_t r = 0; r < gathered.size(); ++r) {
-    unpack_classes(gathered[r].data() + LF_HEADER, (size_t)gathered[r][1], nc, recs[r]);
-    skipped += gathered[r][4];
-  }
-  std::vector<int64_t> fh, fo, fc;
-  std::vector<int32_t> fm;
-  if (!fold_class_counts(recs, K, (int)nc, fh, fo, fm, fc)) return tfail(t, VGS_E_STATE, std::string(fn) + ": a rank sent a label >= K");
-  sw.lap(VGS_TILES_F_FOLD);
-  sw.total(VGS_TILES_F_TOTAL, t->ftimes);   // (VGS_TILES_F_FINISH stays 0: the majority rule is integer work inside the fold)
-  if (n_skipped) *n_skipped = skipped;
-  put(fh, hist); put(fo, n_outside); put(fm, majority); put(fc, majority_count);
-  t->f_own = n_rec; t->f_bytes = (int64_t)(payload.size() * sizeof(int64_t));
-  return VGS_OK;
+  return attribute_collective(t, point_labelling("vgs_tiles_point_label_field_stats_device", true, labels_dev, n, K), FieldCodec(field_dev, n, n_channels, stride_bytes, n_valid, anchor, mean, var, vmin, vmax), n_skipped);
 }
 
 vgs_status vgs_tiles_point_label_class_histogram(vgs_tiles* t, const int32_t* labels_host, int64_t K, const int32_t* cls_host, int64_t n, int32_t n_classes,
                                                  int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority, int64_t* majority_count) {
-  return tiles_label_class_hist(t, "vgs_tiles_point_label_class_histogram", false, labels_host, K, cls_host, n, n_classes, n_skipped, hist, n_outside,
-                                majority, majority_count);
+  if (!t) return VGS_E_ARG;
+  return attribute_collective(t, point_labelling("vgs_tiles_point_label_class_histogram", false, labels_host, n, K), ClassCodec(cls_host, n, n_classes, hist, n_outside, majority, majority_count), n_skipped);
 }
 
 vgs_status vgs_tiles_point_label_class_histogram_device(vgs_tiles* t, const int32_t* labels_dev, int64_t K, const int32_t* cls_dev, int64_t n,
                                                         int32_t n_classes, int64_t* n_skipped, int64_t* hist, int64_t* n_outside, int32_t* majority,
                                                         int64_t* majority_count) {
-  return tiles_label_class_hist(t, "vgs_tiles_point_label_class_histogram_device", true, labels_dev, K, cls_dev, n, n_classes, n_skipped, hist, n_outside,
-                                majority, majority_count);
+  if (!t) return VGS_E_ARG;
+  return attribute_collective(t, point_labelling("vgs_tiles_point_label_class_histogram_device", true, labels_dev, n, K), ClassCodec(cls_dev, n, n_classes, hist, n_outside, majority, majority_count), n_skipped);
 }
 
 vgs_status vgs_tiles_get_field_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::ftimes, ms, n); }
@@ -1664,11 +1600,10 @@ static vgs_status tiles_compare(vgs_tiles* t, const char* fn, bool on_device, co
   TRY(exchange(t, carry, payload, point ? "point_labels" : "compare", sw, VGS_TILES_C_EXCHANGE, gathered));
   if (point) {
     for (size_t r = 1; r < gathered.size(); ++r)
-      if (gathered[r].back() != gathered[0].back())
-        return tfail(t, VGS_E_ARG, std::string(fn) + ": rank " + std::to_string(r) + " passed K = " + std::to_string(gathered[r].back()) + ", rank 0 passed " + std::to_string(gathered[0].back()));
+      if (gathered[r].back() != gathered[0].back()) return disagree(t, fn, r, "K", gathered[r].back(), gathered[0].back());
     for (std::vector<int64_t>& g : gathered) g.pop_back();
   }
-  TRY(check_word_payloads(t, fn, gathered, 2, nullptr));
+  TRY(check_payloads(t, fn, gathered, 3, 2, {}));   // (the third header word is the rank's own figure: nothing to agree on)
   size_t n_in = 0;
   int64_t unann = 0;
   for (const std::vector<int64_t>& g : gathered) { n_in += (size_t)g[1]; unann += g[2]; }
