@@ -22,7 +22,7 @@ struct DriverGraph {
 // per-point attributes handed to the drivers and what comes back: getClusterFieldStats over `field` (n x channels floats, row-major) when
 // channels > 0, getClusterClassHistogram over `classes` (n int32) when n_classes > 0, compareClusterLabels over `truth` when have_truth;
 // want_stats / want_hist off: the input is loaded for the refined labels' table only (DriverRefine::fields); getLabelComponents over
-// `part_classes` (n int32, negative = no class) with parts_K labels when parts_K >= 0
+// `part_classes` (n int32, negative = no class) with parts_K labels when parts_K >= 0, getLabelGraph over the same when want_parts_graph
 struct DriverFields {
   std::vector<float> field;
   int channels = 0;
@@ -38,6 +38,8 @@ struct DriverFields {
   std::vector<int32_t> part_classes;
   int64_t parts_K = -1;
   pcl::LabelComponents parts;
+  bool want_parts = true, want_parts_graph = false;
+  pcl::LabelGraph parts_graph;
 };
 // point-level refinement of the cluster labels (refineClusterLabels): when `on`, the drivers put the refined clusters into
 // clusters_points_idx -- clusters in label order, points in ascending index -- and the refined labels into `labels`
@@ -49,9 +51,10 @@ struct DriverRefine {
   std::vector<int32_t> labels;
   // the tables of the REFINED labels, beside the ones that describe the voxel labels: getLabelDescriptors / getLabelBoxes(box_frame) /
   // compareClusterLabels(truth, labels) when wanted (truth: n int32, not null); getLabelFieldStats / getLabelClassHistogram over the
-  // field / classes of `fields` when wanted; getLabelComponents when wanted
-  bool want_descriptors = false, want_boxes = false, want_stats = false, want_hist = false, want_components = false;
+  // field / classes of `fields` when wanted; getLabelComponents and getLabelGraph when wanted
+  bool want_descriptors = false, want_boxes = false, want_stats = false, want_hist = false, want_components = false, want_graph = false;
   pcl::LabelComponents components;
+  pcl::LabelGraph graph;
   const DriverFields* fields = nullptr;
   std::vector<pcl::ClusterFieldStats> stats;
   std::vector<pcl::ClusterClassHistogram> hist;
@@ -74,6 +77,7 @@ inline void driverRefine(S& structure, DriverRefine& r, std::vector<std::vector<
   if (r.want_hist && r.fields && r.fields->n_classes > 0)
     r.hist = structure.getLabelClassHistogram(r.labels.data(), r.fields->classes.data(), (int64_t)r.fields->classes.size(), r.fields->n_classes);
   if (r.want_components) r.components = structure.getLabelComponents(r.labels.data(), n);
+  if (r.want_graph) r.graph = structure.getLabelGraph(r.labels.data(), n);
   for (auto& c : clusters_points_idx) c.clear();
   for (size_t i = 0; i < r.labels.size(); ++i)
     if (r.labels[i] >= 0 && (size_t)r.labels[i] < clusters_points_idx.size()) clusters_points_idx[(size_t)r.labels[i]].push_back((int)i);
@@ -84,7 +88,8 @@ inline void driverFields(S& structure, DriverFields& f) {
     f.stats = structure.getClusterFieldStats(f.field.data(), (int64_t)(f.field.size() / (size_t)f.channels), f.channels, 4 * (int64_t)f.channels);
   if (f.n_classes > 0 && f.want_hist) f.hist = structure.getClusterClassHistogram(f.classes.data(), (int64_t)f.classes.size(), f.n_classes);
   if (f.have_truth) f.matches = structure.compareClusterLabels(f.truth.data(), (int64_t)f.truth.size());
-  if (f.parts_K >= 0) f.parts = structure.getLabelComponents(f.part_classes.data(), (int64_t)f.part_classes.size(), f.parts_K);
+  if (f.parts_K >= 0 && f.want_parts) f.parts = structure.getLabelComponents(f.part_classes.data(), (int64_t)f.part_classes.size(), f.parts_K);
+  if (f.parts_K >= 0 && f.want_parts_graph) f.parts_graph = structure.getLabelGraph(f.part_classes.data(), (int64_t)f.part_classes.size(), f.parts_K);
 }
 
 // debug_prefix: when not empty, the reference's three voxel drawings (VS:510, 654, 1016) are written as

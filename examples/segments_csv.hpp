@@ -50,6 +50,20 @@ inline int writeGraphCsv(const std::string& path, const std::vector<pcl::Cluster
   return std::fclose(f) == 0 ? 0 : -1;
 }
 
+// the --refined-graph / --class-graph CSV of vgs_run: one row per edge of the adjacency graph of a per-point labelling (getLabelGraph),
+// ascending (a, b): the columns of --segment-graph plus n_shared behind b
+inline int writeLabelGraphCsv(const std::string& path, const pcl::LabelGraph& g) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return -1;
+  std::fprintf(f, "a,b,n_shared,n_pairs,n_finite,nodes_a,nodes_b,w_mean,w_min,w_max\n");
+  for (const pcl::LabelEdge& e : g.edges) {
+    const double mean = e.n_finite > 0 ? e.w_sum / (double)e.n_finite : std::nan("");
+    std::fprintf(f, "%d,%d,%lld,%lld,%lld,%d,%d,%.17g,%.9g,%.9g\n", (int)e.a, (int)e.b, (long long)e.n_shared, (long long)e.n_pairs,
+                 (long long)e.n_finite, (int)e.nodes_a, (int)e.nodes_b, mean, (double)e.w_min, (double)e.w_max);
+  }
+  return std::fclose(f) == 0 ? 0 : -1;
+}
+
 inline int writeBoxesCsv(const std::string& path, const std::vector<pcl::ClusterBox>& boxes) {
   FILE* f = std::fopen(path.c_str(), "w");
   if (!f) return -1;

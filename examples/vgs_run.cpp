@@ -13,6 +13,7 @@
 //                  [--refined-matches <file.csv> --truth-field <name> [--refined-truth-matches <file.csv>]]
 //                  [--refined-components <file.csv>] [--class-components <file.csv> --class-field <name> --classes <C>]
 //                  [--component-ids <file.i32>]
+//                  [--refined-graph <file.csv>] [--class-graph <file.csv> --class-field <name> --classes <C>]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
 // --segments writes one CSV row per kept cluster (getClusterDescriptors, row i = cluster i of the output): label, n_points, n_nodes,
@@ -53,6 +54,10 @@
 // no class; classes 0 .. C-1 with C = --classes, a class >= C ends the run with an error): the instances of every class over the scene's
 // own neighbourhood graph.  It needs --class-field, --classes and a PCD input.  --component-ids writes the part of every point (int32,
 // input order, -1 = none) of whichever of the two tables was asked for, raw; with both, or with neither, it is a usage error.
+// --refined-graph writes one CSV row per edge of the adjacency graph of the REFINED labels (getLabelGraph, ascending (a, b)): a, b,
+// n_shared (nodes that hold points of both), then the columns of --segment-graph over the contacts of a and b -- n_pairs, n_finite,
+// nodes_a, nodes_b, w_mean, w_min, w_max, doubles as %.17g, floats as %.9g.  It needs --refine.  --class-graph writes the same table for
+// the class field of --class-components (same reading, same rules): which classes touch, and across how much boundary.
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
 #include <algorithm>
 #include <cmath>
@@ -82,13 +87,14 @@ int main(int argc, char** argv) {
                  "[--refine [--patch-radius r] [--switch-ratio s] [--no-fill]] [--refined-segments file.csv] [--refined-segment-boxes file.csv] "
                  "[--refined-segment-fields file.csv --fields a[,b,...]] [--refined-segment-classes file.csv --class-field name --classes C] "
                  "[--refined-matches file.csv --truth-field name [--refined-truth-matches file.csv]] "
-                 "[--refined-components file.csv] [--class-components file.csv --class-field name --classes C] [--component-ids file.i32]\n",
+                 "[--refined-components file.csv] [--class-components file.csv --class-field name --classes C] [--component-ids file.i32] "
+                 "[--refined-graph file.csv] [--class-graph file.csv --class-field name --classes C]\n",
                  argv[0]);
     return 2;
   }
   std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file, boxes_file, fields_file, classes_file, class_field, matches_file, truth_field, truth_file;
   std::string r_segments_file, r_boxes_file, r_matches_file, r_truth_file, r_fields_file, r_classes_file;
-  std::string r_parts_file, c_parts_file, part_ids_file;
+  std::string r_parts_file, c_parts_file, part_ids_file, r_graph_file, c_graph_file;
   std::vector<std::string> field_names;
   bool have_fields = false, have_classes = false;
   long n_classes = 0;
@@ -143,6 +149,8 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--refined-components") && a + 1 < argc) r_parts_file = argv[++a];
     else if (!std::strcmp(argv[a], "--class-components") && a + 1 < argc) c_parts_file = argv[++a];
     else if (!std::strcmp(argv[a], "--component-ids") && a + 1 < argc) part_ids_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--refined-graph") && a + 1 < argc) r_graph_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--class-graph") && a + 1 < argc) c_graph_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refine")) refine.on = true;
     else if (!std::strcmp(argv[a], "--no-fill")) { refine.fill = false; refine_opts = true; }
     else if ((!std::strcmp(argv[a], "--patch-radius") || !std::strcmp(argv[a], "--switch-ratio")) && a + 1 < argc) {
@@ -167,6 +175,9 @@ int main(int argc, char** argv) {
   if (!c_parts_file.empty() && class_field.empty()) { std::fprintf(stderr, "--class-components needs --class-field <name>\n"); return 2; }
   if (!c_parts_file.empty() && !have_classes) { std::fprintf(stderr, "--class-components needs --classes <C>\n"); return 2; }
   if (!r_parts_file.empty() && !refine.on) { std::fprintf(stderr, "--refined-components needs --refine\n"); return 2; }
+  if (!c_graph_file.empty() && class_field.empty()) { std::fprintf(stderr, "--class-graph needs --class-field <name>\n"); return 2; }
+  if (!c_graph_file.empty() && !have_classes) { std::fprintf(stderr, "--class-graph needs --classes <C>\n"); return 2; }
+  if (!r_graph_file.empty() && !refine.on) { std::fprintf(stderr, "--refined-graph needs --refine\n"); return 2; }
   if (!part_ids_file.empty() && r_parts_file.empty() == c_parts_file.empty()) {
     std::fprintf(stderr, "--component-ids writes the parts of exactly one of --refined-components and --class-components (%s given)\n",
                  r_parts_file.empty() ? "neither" : "both");
@@ -178,8 +189,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--fields needs --segment-fields <file.csv> (or --refined-segment-fields)\n");
     return 2;
   }
-  if (classes_file.empty() && r_classes_file.empty() && c_parts_file.empty() && (have_classes || !class_field.empty())) {
-    std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv> (or --refined-segment-classes, --class-components)\n");
+  if (classes_file.empty() && r_classes_file.empty() && c_parts_file.empty() && c_graph_file.empty() && (have_classes || !class_field.empty())) {
+    std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv> (or --refined-segment-classes, --class-components, --class-graph)\n");
     return 2;
   }
   if (!matches_file.empty() && truth_field.empty()) { std::fprintf(stderr, "--segment-matches needs --truth-field <name>\n"); return 2; }
@@ -210,14 +221,15 @@ int main(int argc, char** argv) {
   const bool ply = in_file.size() > 4 && in_file.substr(in_file.size() - 4) == ".ply";
   const bool want_truth = !(matches_file.empty() && r_matches_file.empty());
   const bool any_fields = !(fields_file.empty() && r_fields_file.empty()), any_classes = !(classes_file.empty() && r_classes_file.empty());
-  if (ply && (any_fields || any_classes || want_truth || !c_parts_file.empty())) {   // (a usage error: nothing has been loaded yet)
+  const bool class_labels = !(c_parts_file.empty() && c_graph_file.empty());   // the class field read as a labelling of its own
+  if (ply && (any_fields || any_classes || want_truth || class_labels)) {   // (a usage error: nothing has been loaded yet)
     std::fprintf(stderr, "--segment-fields / --segment-classes / --refined-segment-fields / --refined-segment-classes / --segment-matches / "
-                 "--refined-matches / --class-components read their fields from a PCD input, not from %s\n", in_file.c_str());
+                 "--refined-matches / --class-components / --class-graph read their fields from a PCD input, not from %s\n", in_file.c_str());
     return 2;
   }
   if ((ply ? inputPointCloudData2(in_file, cloud) : inputPointCloudData(in_file, cloud)) != 0) return 1;
   DriverFields fields;
-  DriverFields* want_fields = (!any_fields && !any_classes && !want_truth && c_parts_file.empty()) ? nullptr : &fields;
+  DriverFields* want_fields = (!any_fields && !any_classes && !want_truth && !class_labels) ? nullptr : &fields;
   if (want_fields) {   // the attributes ride in the input PCD, one row per point of the cloud
     std::string err;
     if (any_fields) {
@@ -233,9 +245,11 @@ int main(int argc, char** argv) {
       fields.n_classes = (int)n_classes;
       fields.want_hist = !classes_file.empty();
     }
-    if (!c_parts_file.empty()) {
+    if (class_labels) {
       if (vgs_io::read_pcd_field_int32(in_file, class_field, fields.part_classes, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
       fields.parts_K = (int64_t)n_classes;
+      fields.want_parts = !c_parts_file.empty();
+      fields.want_parts_graph = !c_graph_file.empty();
     }
     if (want_truth) {
       if (vgs_io::read_pcd_field_int32(in_file, truth_field, fields.truth, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
@@ -248,6 +262,7 @@ int main(int argc, char** argv) {
   refine.want_stats = !r_fields_file.empty();
   refine.want_hist = !r_classes_file.empty();
   refine.want_components = !r_parts_file.empty();
+  refine.want_graph = !r_graph_file.empty();
   refine.fields = &fields;
   refine.box_frame = box_frame;
   std::vector<std::vector<int>> clusters;
@@ -288,6 +303,8 @@ int main(int argc, char** argv) {
   if (!r_truth_file.empty() && writeTruthMatchesCsv(r_truth_file, refine.matches) != 0) { std::fprintf(stderr, "cannot write %s\n", r_truth_file.c_str()); return 1; }
   if (!r_parts_file.empty() && writeComponentsCsv(r_parts_file, refine.components) != 0) { std::fprintf(stderr, "cannot write %s\n", r_parts_file.c_str()); return 1; }
   if (!c_parts_file.empty() && writeComponentsCsv(c_parts_file, fields.parts) != 0) { std::fprintf(stderr, "cannot write %s\n", c_parts_file.c_str()); return 1; }
+  if (!r_graph_file.empty() && writeLabelGraphCsv(r_graph_file, refine.graph) != 0) { std::fprintf(stderr, "cannot write %s\n", r_graph_file.c_str()); return 1; }
+  if (!c_graph_file.empty() && writeLabelGraphCsv(c_graph_file, fields.parts_graph) != 0) { std::fprintf(stderr, "cannot write %s\n", c_graph_file.c_str()); return 1; }
   if (!part_ids_file.empty()) {
     const std::vector<int32_t>& ids = r_parts_file.empty() ? fields.parts.part_of_point : refine.components.part_of_point;
     FILE* f = std::fopen(part_ids_file.c_str(), "wb");

@@ -770,6 +770,50 @@ vgs_status vgs_get_point_label_components(vgs_ctx* ctx, int32_t* part_of_point, 
 vgs_status vgs_get_point_label_components_device(vgs_ctx* ctx, const int32_t** part_of_point, const int32_t** part_label,
                                                  const int64_t** part_points, const int32_t** part_nodes, const int32_t** part_first_node,
                                                  const int64_t** label_first, const int32_t** label_largest);
+/* Adjacency graph of ANY per-point labelling of the cloud (no reference counterpart): vgs_get_segment_graph for labels that need not be
+ * constant on a node -- which refined segments, which parts of vgs_point_label_components, which instances or classes touch each other,
+ * across how much boundary, and how strongly the local cut's weight links them there.
+ *
+ * Input, nodes, vertices and rows are exactly those of vgs_point_label_components: labels[i] per input point, negative = none,
+ * 0 <= labels[i] < K, the first offending index of a label >= K reported with VGS_E_ARG; nodes are what vgs_get_point_voxel returns;
+ * vertices are the distinct pairs (label, node) with a point; two nodes v, w are ADJACENT when w is in the row of v or v in the row of w,
+ * the rows those of vgs_get_lists(which = 0) (the rows of unused voxels that hold a labelled point are built on request, VGS only); a
+ * labelled point without a node counts in n_skipped.
+ * Contact of labels a < b: an unordered pair of vertices {(a, v), (b, w)} with v != w and v, w adjacent.  Each contact is counted once,
+ * whichever row holds the entry.
+ * Shared node of a, b: a node v with both (a, v) and (b, v) as vertices.
+ * Edge {a < b}: at least one contact or one shared node.  Edges are listed in ascending (a, b); E = their number.
+ * With several labels per node one node pair can carry contacts of several edges, and two contacts of one edge: {(a, v), (b, w)} and
+ * {(a, w), (b, v)} when both nodes carry both labels.
+ * Per edge (E rows):
+ *   seg_ab    int32 x2  a, b
+ *   n_shared  int64     shared nodes
+ *   n_pairs   int64     contacts
+ *   n_finite  int64     contacts between two USED nodes whose weight is not NaN
+ *   nodes_ab  int32 x2  the vertices of a that are in at least one contact of this edge, and those of b (a shared node alone does not count)
+ *   w_sum     double    sum of the weights over those n_finite contacts
+ *   w_min, w_max float  their extrema; NaN when n_finite == 0
+ * The weight of a contact is vm_pair_weight(node[min(v, w)], node[max(v, w)], W), the lower node id first: the entry that
+ * vgs_get_local_weights reports for that ordered pair.  A contact with an unused endpoint has no weight and counts in n_pairs only.
+ * When every node carries one label and only used kept nodes are labelled -- vgs_get_point_labels with K = counts[VGS_N_KEPT] --
+ * n_shared is 0 and every other field is the field of vgs_get_segment_graph.
+ * The integer fields, w_min and w_max are functions of the contact set alone; w_sum is summed in fp64 in a fixed shape without float
+ * atomics (csrc/labelgraph.hip): the table is bit-identical from call to call and from engine to engine.  E = 0 for K <= 1, no vertex,
+ * or neither contact nor shared node.  VGS_E_UNSUPPORTED for more than 2^31 (vertex, other label) records.
+ * vgs_point_label_graph[_device] computes the table on the device into buffers of the context (the _device variant reads the labels in
+ * place); n_edges = E and n_skipped may be NULL.  vgs_get_point_label_graph copies it out, any pointer may be NULL;
+ * vgs_get_point_label_graph_device hands out E and the device pointers (NULL for E = 0).  Both are valid until the next
+ * vgs_point_label_graph or the next run of the stages, and answer VGS_E_STATE without a result since the last run.  No other table, no
+ * labels and no result of vgs_point_label_components are touched.
+ * VGS_E_STATE before the context is segmented, and for a tile context: it holds part of the cloud and of the graph only, and the graph of a
+ * labelling across the ranks of the tiled driver is not computed.  VGS_E_ARG for n != N, a NULL labelling, K outside 0 .. 2^31 - 1. */
+vgs_status vgs_point_label_graph(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_edges, int64_t* n_skipped);
+vgs_status vgs_point_label_graph_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_edges, int64_t* n_skipped);
+vgs_status vgs_get_point_label_graph(vgs_ctx* ctx, int32_t* seg_ab, int64_t* n_shared, int64_t* n_pairs, int64_t* n_finite, int32_t* nodes_ab,
+                                     double* w_sum, float* w_min, float* w_max);
+vgs_status vgs_get_point_label_graph_device(vgs_ctx* ctx, int64_t* n_edges, const int32_t** seg_ab, const int64_t** n_shared,
+                                            const int64_t** n_pairs, const int64_t** n_finite, const int32_t** nodes_ab, const double** w_sum,
+                                            const float** w_min, const float** w_max);
 /* Tile contexts (vgs_set_owned_region and vgs_set_own_point_range; VGS only): a rank's share of the connected parts of a labelling over
  * all ranks of the tiled driver.  include/vgs_tiles.h (vgs_tiles_point_label_components) states the definition and the protocol these
  * four steps serve; csrc/labelcc_tiles.hip has the kernels.  Every call answers VGS_E_STATE on a plain context and before a run.

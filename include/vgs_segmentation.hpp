@@ -355,6 +355,41 @@ inline std::vector<ClusterEdge> cluster_graph(vgs_ctx* c) {
   }
   return out;
 }
+}  // namespace vgs_detail
+
+// Extension (no VS / SS line): one edge of the adjacency graph of a per-point labelling, as vgs_point_label_graph (include/vgs.h) defines
+// it: ClusterEdge's fields over the CONTACTS of labels a < b (pairs of adjacent nodes, one carrying a and the other b), plus the nodes
+// that carry both
+struct LabelEdge : ClusterEdge {
+  int64_t n_shared = 0;
+};
+struct LabelGraph {
+  std::vector<LabelEdge> edges;   // ascending (a, b)
+  int64_t n_skipped = 0;          // labelled points outside the octree
+};
+
+namespace vgs_detail {
+inline LabelGraph label_graph(vgs_ctx* c, int64_t k, const int32_t* labels, int64_t n) {
+  LabelGraph o;
+  int64_t E = 0;
+  check(c, vgs_point_label_graph(c, labels, n, k, &E, &o.n_skipped), "vgs_point_label_graph");
+  o.edges.resize((size_t)E);
+  if (E == 0) return o;
+  std::vector<int32_t> ab((size_t)E * 2), nd((size_t)E * 2);
+  std::vector<int64_t> ns((size_t)E), np((size_t)E), nf((size_t)E);
+  std::vector<double> ws((size_t)E);
+  std::vector<float> mn((size_t)E), mx((size_t)E);
+  check(c, vgs_get_point_label_graph(c, ab.data(), ns.data(), np.data(), nf.data(), nd.data(), ws.data(), mn.data(), mx.data()),
+        "vgs_get_point_label_graph");
+  for (size_t i = 0; i < o.edges.size(); ++i) {
+    LabelEdge& e = o.edges[i];
+    e.a = ab[2 * i]; e.b = ab[2 * i + 1];
+    e.n_shared = ns[i]; e.n_pairs = np[i]; e.n_finite = nf[i];
+    e.nodes_a = nd[2 * i]; e.nodes_b = nd[2 * i + 1];
+    e.w_sum = ws[i]; e.w_min = mn[i]; e.w_max = mx[i];
+  }
+  return o;
+}
 // PCL's getSupervoxelAdjacency idiom: both directions of every edge, keyed by cluster index
 inline void cluster_adjacency(const std::vector<ClusterEdge>& g, std::multimap<uint32_t, uint32_t>& adjacency) {
   adjacency.clear();
@@ -550,6 +585,12 @@ class VoxelBasedSegmentation {
     }
     return vgs_detail::label_components(ctx(), K < 0 ? count(VGS_N_KEPT) : K, labels, n);
   }
+  // Extension (no VS line): the adjacency graph of a per-point labelling (vgs_point_label_graph, include/vgs.h), labels and K as
+  // getLabelComponents.  No edge before drawColorMapofPointsinClusters
+  LabelGraph getLabelGraph(const int32_t* labels, int64_t n, int64_t K = -1) {
+    if (!drawn_) return {};
+    return vgs_detail::label_graph(ctx(), K < 0 ? count(VGS_N_KEPT) : K, labels, n);
+  }
 
   // Extension (no VS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
   // names getClusterIdx()[i].  patch_radius < 0: the default (the voxel size); every point -1 before drawColorMapofPointsinClusters
@@ -697,6 +738,11 @@ class SuperVoxelBasedSegmentation {
   // adjacency (vgs_point_label_components, include/vgs.h); K < 0: the clusters' label range
   LabelComponents getLabelComponents(const int32_t* labels, int64_t n, int64_t K = -1) {
     return vgs_detail::label_components(ctx(), K < 0 ? count(VGS_N_KEPT) : K, labels, n);
+  }
+  // Extension (no SS line): the adjacency graph of a per-point labelling (vgs_point_label_graph, include/vgs.h), labels and K as
+  // getLabelComponents
+  LabelGraph getLabelGraph(const int32_t* labels, int64_t n, int64_t K = -1) {
+    return vgs_detail::label_graph(ctx(), K < 0 ? count(VGS_N_KEPT) : K, labels, n);
   }
   // Extension (no SS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
   // names getClusterIdx()[i].  patch_radius < 0: the default (the supervoxel size)

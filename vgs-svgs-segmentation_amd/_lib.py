@@ -167,6 +167,10 @@ SYMBOLS = [
     ("vgs_get_point_label_part_ids_device", C.c_int, [_P, _P]),
     ("vgs_get_point_label_components", C.c_int, [_P] + [_P] * 7),
     ("vgs_get_point_label_components_device", C.c_int, [_P] + [_P] * 7),
+    ("vgs_point_label_graph", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("vgs_point_label_graph_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("vgs_get_point_label_graph", C.c_int, [_P] + [_P] * 8),
+    ("vgs_get_point_label_graph_device", C.c_int, [_P, C.POINTER(C.c_int64)] + [_P] * 8),
     ("vgs_grid_state_init", C.c_int, [C.POINTER(VgsGridState)]),
     ("vgs_grid_advance", C.c_int, [_P, C.POINTER(VgsGridState)]),
     ("vgs_points_bbox", C.c_int, [_P, _P, C.POINTER(C.c_int64)]),

@@ -585,6 +585,42 @@ class Engine:
         self._ck(self._L.vgs_get_point_label_components_device(self._h, *(C.byref(p) for p in ps)))
         return {name: p.value for (name, _, _), p in zip(self.COMPONENT_FIELDS, ps)}
 
+    # per edge: (field, dtype, values per edge) of vgs_get_point_label_graph, in its argument order
+    LABEL_GRAPH_FIELDS = (("seg_ab", np.int32, 2), ("n_shared", np.int64, 1), ("n_pairs", np.int64, 1), ("n_finite", np.int64, 1),
+                          ("nodes_ab", np.int32, 2), ("w_sum", np.float64, 1), ("w_min", np.float32, 1), ("w_max", np.float32, 1))
+
+    def label_graph(self, labels, K=None):
+        """Adjacency graph of ANY per-point labelling of the cloud (include/vgs.h, vgs_point_label_graph): a dict of numpy arrays, one row
+        per edge {a < b} in ascending (a, b) -- seg_ab (E, 2), n_shared (nodes that carry both labels), n_pairs (contacts: pairs of
+        adjacent nodes, one carrying a and the other b, each counted once), n_finite, nodes_ab (E, 2: the (label, node) vertices of a
+        and of b that are in a contact), w_sum, w_min, w_max (the local cut's weight over the contacts between two used nodes) -- plus
+        n_edges = E and n_skipped, the labelled points outside the octree.  Adjacency is that of label_components(): either node's row
+        of lists(0) holds the other.  `labels`, K as label_components() (K None: max(label) + 1).  Computed on the device, bit-identical
+        from call to call; handed point_labels() with K = counts()["kept"] it returns segment_graph() with n_shared = 0."""
+        if K is None:
+            if self._is_torch(labels):
+                K = max(int(labels.max().item()) + 1, 0) if labels.numel() > 0 else 0
+            else:
+                a = np.asarray(labels)
+                K = max(int(a.max()) + 1, 0) if a.size > 0 else 0
+        labels, ptr, n, dev, K = self._labels_input(labels, K)
+        fn = self._L.vgs_point_label_graph_device if dev else self._L.vgs_point_label_graph
+        E, skipped = C.c_int64(0), C.c_int64(0)
+        self._ck(fn(self._h, ptr, n, K, C.byref(E), C.byref(skipped)))
+        out = {name: np.zeros((E.value, w) if w > 1 else E.value, dtype=dt) for name, dt, w in self.LABEL_GRAPH_FIELDS}
+        self._ck(self._L.vgs_get_point_label_graph(self._h, *(_ptr(out[name]) for name, _, _ in self.LABEL_GRAPH_FIELDS)))
+        out["n_edges"] = int(E.value)
+        out["n_skipped"] = int(skipped.value)
+        return out
+
+    def label_graph_device(self):
+        """The table of the last label_graph left in HBM: (E, {field: device pointer, None for E = 0}), valid until the next label_graph
+        or the next run."""
+        E = C.c_int64(0)
+        ps = [C.c_void_p() for _ in self.LABEL_GRAPH_FIELDS]
+        self._ck(self._L.vgs_get_point_label_graph_device(self._h, C.byref(E), *(C.byref(p) for p in ps)))
+        return E.value, {name: p.value for (name, _, _), p in zip(self.LABEL_GRAPH_FIELDS, ps)}
+
     def compare_labels(self, ref, labels=None, K=None):
         """Score the segmentation against a labelling of the same points (include/vgs.h, vgs_compare_labels): the sparse contingency table
         between point_labels() and `ref`, the reference table and the segment table, as a dict of numpy arrays -- cell_seg, cell_ref, cell_n

@@ -47,6 +47,8 @@
 // Tile contexts: the calls of include/vgs.h refuse them (a tile holds part of the cloud and of the graph), but the pass itself runs over a
 // tile's OWN points as step 1 of the parts across the ranks of the tiled driver (vgs_label_parts_on_device with the own point range;
 // labelcc_tiles.hip reads the vertex arrays it leaves in lcc_vtx and adds the band, the cross links and the global ids).
+// Steps 1 and 2 are a function of their own (vgs_label_vertices_on_device): labelgraph.hip builds the adjacency graph of a labelling on
+// the same vertex list, in the same scratch.
 // (The context's lc_* members belong to the local cut, hence lcc_*.)
 #include <string.h>
 
@@ -285,9 +287,6 @@ static vgs_status lc_scan(vgs_ctx* c, uint32_t* in, uint32_t* out, size_t n) {
   return VGS_OK;
 }
 
-// the vertex arrays, nv + 1 words each, in lcc_vtx
-struct LcVtx { uint32_t *node, *label, *q, *parent, *root, *part; };
-
 // both link kernels over one list of n items (items == nullptr: all vertices against the stored rows)
 static vgs_status lc_link(vgs_ctx* c, const LcVtx& X, const uint32_t* items, uint32_t n, const uint32_t* used_rank, const uint64_t* rows,
                           const uint32_t* cnt, int back) {
@@ -315,6 +314,39 @@ static vgs_status lc_check(vgs_ctx* c, const char* fn, const int32_t* labels, in
   return VGS_OK;
 }
 
+// Steps 1 and 2 for this pass and for labelgraph.hip: the sort (S; n_skipped as ps_sort_points counts it), the vertices in (label, node)
+// order (nv of them, X: six arrays of nv + 1 words in lcc_vtx, of which node, label, q and parent = itself are written), nlo | nhi in
+// lcc_nidx and the first vertex of every label in lcc_vfirst, all left on the context's stream.  nv = 0: nothing behind the sort is built.
+vgs_status vgs_label_vertices_on_device(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t own_first, int64_t n_lab, int64_t K,
+                                        int64_t* n_skipped, PsSort& S, uint32_t* n_vertices, LcVtx& X) {
+  const int64_t nf = c->Nf, V = c->V;
+  const size_t k = (size_t)K;
+  *n_vertices = 0;
+  X = LcVtx{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  vgs_status s = ps_sort_points(c, fn, labels_dev, own_first, n_lab, K, 0, n_skipped, S);
+  if (s != VGS_OK) return s;
+  uint32_t nv = 0;
+  if (S.sorted && nf > 0 && V > 0) {
+    VGS_HIP_TRY(c, c->lcc_flag.ensure((size_t)nf + 1)); VGS_HIP_TRY(c, c->lcc_vex.ensure((size_t)nf + 1));
+    hipLaunchKernelGGL(k_lc_heads, dim3(lc_grid((uint64_t)nf + 1)), dim3(LC_TB), 0, c->stream, S.key, S.pos, c->pt_vox.p, nf, (uint32_t)K, c->lcc_flag.p);
+    if ((s = lc_scan(c, c->lcc_flag.p, c->lcc_vex.p, (size_t)nf + 1)) != VGS_OK) return s;
+    VGS_READBACK(c, &nv, c->lcc_vex.p + nf, 4);
+  }
+  if (nv == 0) return VGS_OK;
+  const size_t w = (size_t)nv + 1;
+  VGS_HIP_TRY(c, c->lcc_vtx.ensure(6 * w)); VGS_HIP_TRY(c, c->lcc_vfirst.ensure(k + 1)); VGS_HIP_TRY(c, c->lcc_vscan.ensure(w));
+  X.node = c->lcc_vtx.p; X.label = X.node + w; X.q = X.label + w; X.parent = X.q + w; X.root = X.parent + w; X.part = X.root + w;
+  VGS_HIP_TRY(c, c->lcc_nidx.ensure(2 * (size_t)V));   // nlo | nhi
+  VGS_HIP_TRY(c, hipMemsetAsync(c->lcc_nidx.p, 0xff, (size_t)V * sizeof(uint32_t), c->stream));
+  VGS_HIP_TRY(c, hipMemsetAsync(c->lcc_nidx.p + V, 0, (size_t)V * sizeof(uint32_t), c->stream));
+  hipLaunchKernelGGL(k_lc_vertices, dim3(lc_grid((uint64_t)nf)), dim3(LC_TB), 0, c->stream, c->lcc_flag.p, c->lcc_vex.p, S.key, S.pos, c->pt_vox.p, nf, nv,
+                     X.node, X.label, X.q, X.parent, c->lcc_nidx.p, c->lcc_nidx.p + V);
+  hipLaunchKernelGGL(k_lc_vfirst, dim3(lc_grid(k + 1)), dim3(LC_TB), 0, c->stream, S.seg_start, c->lcc_vex.p, (uint32_t)K, nv, c->lcc_vfirst.p, X.q);
+  VGS_HIP_TRY(c, hipGetLastError());
+  *n_vertices = nv;
+  return VGS_OK;
+}
+
 // The pass over labels_dev: n_lab entries for the input indices own_first .. own_first + n_lab - 1 (one context: 0 and N; a tile context, for
 // labelcc_tiles.hip: its own point range -- k_ps_keys gives every other position the key K, so the vertices are those of own points only).
 // The vertex arrays stay in lcc_vtx (lcc_nv vertices, six arrays of lcc_nv + 1 words: LcVtx) until the next call.
@@ -325,28 +357,13 @@ vgs_status vgs_label_parts_on_device(vgs_ctx* c, const char* fn, const int32_t* 
   c->lcc_valid = false; c->lcc_nv = 0; c->lct_own = c->lct_linked = c->lct_applied = false;
   VGS_HIP_TRY(c, c->lcc_pop.ensure(N > 0 ? (size_t)N : 1)); VGS_HIP_TRY(c, c->lcc_lfirst.ensure(k + 1)); VGS_HIP_TRY(c, c->lcc_llargest.ensure(k + 1));
   PsSort S;
-  vgs_status s = ps_sort_points(c, fn, labels_dev, own_first, n_lab, K, 0, n_skipped, S);
+  LcVtx X;
+  uint32_t nv = 0, C = 0;
+  vgs_status s = vgs_label_vertices_on_device(c, fn, labels_dev, own_first, n_lab, K, n_skipped, S, &nv, X);
   if (s != VGS_OK) return s;
   if (N > 0) VGS_HIP_TRY(c, hipMemsetAsync(c->lcc_pop.p, 0xff, (size_t)N * sizeof(int32_t), c->stream));
-  uint32_t nv = 0, C = 0;
-  if (S.sorted && nf > 0 && V > 0) {
-    VGS_HIP_TRY(c, c->lcc_flag.ensure((size_t)nf + 1)); VGS_HIP_TRY(c, c->lcc_vex.ensure((size_t)nf + 1));
-    hipLaunchKernelGGL(k_lc_heads, dim3(lc_grid((uint64_t)nf + 1)), dim3(LC_TB), 0, c->stream, S.key, S.pos, c->pt_vox.p, nf, (uint32_t)K, c->lcc_flag.p);
-    if ((s = lc_scan(c, c->lcc_flag.p, c->lcc_vex.p, (size_t)nf + 1)) != VGS_OK) return s;
-    VGS_READBACK(c, &nv, c->lcc_vex.p + nf, 4);
-  }
   if (nv > 0) {
     const size_t w = (size_t)nv + 1;
-    VGS_HIP_TRY(c, c->lcc_vtx.ensure(6 * w)); VGS_HIP_TRY(c, c->lcc_vfirst.ensure(k + 1)); VGS_HIP_TRY(c, c->lcc_vscan.ensure(w));
-    LcVtx X;
-    X.node = c->lcc_vtx.p; X.label = X.node + w; X.q = X.label + w; X.parent = X.q + w; X.root = X.parent + w; X.part = X.root + w;
-    VGS_HIP_TRY(c, c->lcc_nidx.ensure(2 * (size_t)V));   // nlo | nhi
-    VGS_HIP_TRY(c, hipMemsetAsync(c->lcc_nidx.p, 0xff, (size_t)V * sizeof(uint32_t), c->stream));
-    VGS_HIP_TRY(c, hipMemsetAsync(c->lcc_nidx.p + V, 0, (size_t)V * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_lc_vertices, dim3(lc_grid((uint64_t)nf)), dim3(LC_TB), 0, c->stream, c->lcc_flag.p, c->lcc_vex.p, S.key, S.pos, c->pt_vox.p, nf, nv,
-                       X.node, X.label, X.q, X.parent, c->lcc_nidx.p, c->lcc_nidx.p + V);
-    hipLaunchKernelGGL(k_lc_vfirst, dim3(lc_grid(k + 1)), dim3(LC_TB), 0, c->stream, S.seg_start, c->lcc_vex.p, (uint32_t)K, nv, c->lcc_vfirst.p, X.q);
-    VGS_HIP_TRY(c, hipGetLastError());
     // the stored rows: every vertex of a used node
     const bool vgs = c->P.method == 2;
     if (U > 0 && (s = lc_link(c, X, nullptr, nv, c->used_rank.p, c->adj_key.p, c->adj_cnt.p, vgs ? LC_BACK_NEVER : LC_BACK_ALWAYS)) != VGS_OK) return s;

@@ -93,6 +93,23 @@ struct SgPart {
   float w_min, w_max;
 };
 
+// graph of a point labelling (labelgraph.hip): one record per (vertex (A, u), other label B) as the vertex's own row walk sees it, and one
+// proxy record per contact that the other endpoint's row lacks (a = the other vertex's label, b = the walker's); one partial per chunk
+struct LgRec {
+  double w_sum;
+  uint32_t cnt, n_finite;   // contacts counted from this side, and those with a finite weight
+  int32_t a, b;             // the label of the record's vertex, the other label
+  float w_min, w_max;
+  uint32_t t;               // the record's vertex: its position in (node, label) order
+  uint32_t flags;           // LG_CONTACT: the vertex is in a contact of {a, b}; LG_SHARED: its node carries b too
+};
+struct LgPart {
+  double w_sum;
+  int64_t n_pairs, n_finite, n_shared;
+  int32_t nodes_a, nodes_b;
+  float w_min, w_max;
+};
+
 enum Stage { ST_NONE = 0, ST_POINTS = 1, ST_VOXELS = 2, ST_FEATURES = 3, ST_ADJACENCY = 4, ST_SEGMENTED = 5 };
 
 // Diagnostics / schedule-tuning knobs (none changes a result).  Read from the environment ONCE, when the context is created
@@ -412,6 +429,21 @@ struct vgs_ctx {
   int64_t lcc_C = 0, lcc_K = 0;
   uint32_t lcc_nv = 0;   // vertices of the last pass (the arrays of lcc_vtx hold lcc_nv + 1 words each)
   bool lcc_valid = false;
+  // adjacency graph of a caller's per-point labelling (labelgraph.hip): the table of the last vgs_point_label_graph (lg_E rows), valid
+  // until the next one or the next run of the stages (lg_valid).  Scratch of its own: per vertex the record count and first record, per
+  // record the record, two sort keys and two indices twice, the edge work words, the chunk partials; the vertex arrays are labelcc.hip's
+  // (lcc_vtx and the rest of its scratch), the sort pointseg.hip's (ps_*), the rows built for unused voxels refine.hip's chunk.
+  DevBuf<uint32_t> lg_nrec, lg_ridx, lg_tkey, lg_ework, lg_meta;
+  DevBuf<uint64_t> lg_roff, lg_rkey;
+  DevBuf<LgRec> lg_rec;
+  DevBuf<LgPart> lg_part;
+  DevBuf<uint8_t> lg_tmp;
+  DevBuf<int32_t> lg_ab, lg_nodes;
+  DevBuf<int64_t> lg_nshared, lg_npairs, lg_nfin;
+  DevBuf<double> lg_wsum;
+  DevBuf<float> lg_wmin, lg_wmax;
+  int64_t lg_E = 0;
+  bool lg_valid = false;
   // the parts of a labelling across the ranks of the tiled driver (labelcc_tiles.hip; include/vgs.h, vgs_own_point_label_parts): the band
   // records of the last own pass (lct_band rows: code, label, local part, vertex), the code of every local part's first node, the other
   // ranks' records as looked up and sorted (key = label << 32 | local node, value = index of the record), the link triples, the map from
@@ -681,6 +713,10 @@ void sf_launch_majority(vgs_ctx* c, const int64_t* hist, int32_t n_classes, int6
 // labelcc.hip's pass over the points own_first .. own_first + n_lab - 1 (labelcc_tiles.hip runs it over a tile context's own points)
 vgs_status vgs_label_parts_on_device(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t own_first, int64_t n_lab, int64_t K, int64_t* n_parts,
                                      int64_t* n_skipped);
+// its steps 1 and 2, shared with labelgraph.hip: the sort and the vertex arrays (nv + 1 words each, in lcc_vtx), in (label, node) order
+struct LcVtx { uint32_t *node, *label, *q, *parent, *root, *part; };
+vgs_status vgs_label_vertices_on_device(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t own_first, int64_t n_lab, int64_t K,
+                                        int64_t* n_skipped, PsSort& S, uint32_t* n_vertices, LcVtx& X);
 vgs_status vgs_seggraph_on_device(vgs_ctx* c);   // seggraph.hip
 // tile contexts: halo[v] = label[k] for the voxel v of code[k] that this context holds and does not own, queued on the context's stream
 // (code, label: n entries in HBM; halo: V entries).  One kernel for the graph's table and the refinement's (seggraph.hip)
