@@ -44,6 +44,10 @@
 //   vgs_tiles_point_label_components (two collectives; no label leaves its rank) and rank 0 writes one row per part with the columns of
 //   vgs_run's --refined-components / --class-components, the shared-grid code of the part's first node (first_code) in place of the node.
 //   --component-ids: every rank also writes the part of each of its points to <prefix>.<r>.parts.i32; it serves exactly one of the two.
+//   --refined-graph <file.csv> (needs --refine), --class-graph <file.csv> --classes <C> (over <prefix>.<r>.classes.i32): the adjacency
+//   graph of the refined labels, or of the classes, over all ranks -- every rank hands its labels to vgs_tiles_point_label_graph (two
+//   collectives; no label leaves its rank) and rank 0 writes one row per edge with the columns and the writer of vgs_run's
+//   --refined-graph / --class-graph.  A path that cannot be opened for writing is a usage error too.
 //   All of them can be combined.  A missing companion option, a value out of range (1 .. 64 channels, 1 .. 1024 classes) and an attribute
 //   or truth file that is missing or whose size does not match the rank's points are usage errors: exit status 2, before any collective.
 #include <arpa/inet.h>
@@ -113,6 +117,7 @@ struct Job {
   std::string r_fields, r_classes;    // --refined-segment-fields / --refined-segment-classes
   std::string r_parts, c_parts;       // --refined-components / --class-components
   bool part_ids = false;              // --component-ids
+  std::string r_lgraph, c_lgraph;     // --refined-graph / --class-graph
   bool refine = false, refine_fill = true;   // --refine, --no-fill
   float patch_radius = -1.0f, switch_ratio = -1.0f;   // --patch-radius / --switch-ratio (negative: the context's default)
 };
@@ -133,7 +138,7 @@ static int check_attribute_files(const Job& J, int rank) {
       return 2;
     }
   }
-  if (!J.classes.empty() || !J.r_classes.empty() || !J.c_parts.empty()) {
+  if (!J.classes.empty() || !J.r_classes.empty() || !J.c_parts.empty() || !J.c_lgraph.empty()) {
     const std::string path = rank_file(J, rank, ".classes.i32");
     const long long b = file_bytes(path);
     if (b != n * 4) { std::fprintf(stderr, "%s: %lld bytes, but %lld points x 4 = %lld\n", path.c_str(), b, n, n * 4); return 2; }
@@ -143,6 +148,20 @@ static int check_attribute_files(const Job& J, int rank) {
     const long long b = file_bytes(path);
     if (b < 0) { std::fprintf(stderr, "%s: cannot be read; --segment-matches / --refined-matches need one int32 for each of the %lld points of rank %d\n", path.c_str(), n, rank); return 2; }
     if (b != n * 4) { std::fprintf(stderr, "%s: %lld bytes, but %lld points x 4 = %lld\n", path.c_str(), b, n, n * 4); return 2; }
+  }
+  return 0;
+}
+
+// The graph files of --refined-graph / --class-graph, which rank 0 writes at the very end: 0 fine, 2 a path that cannot be opened for
+// writing (message printed).  The last of the refusals; a file the probe itself created is removed again.
+static int check_graph_paths(const Job& J) {
+  for (const std::string* path : {&J.r_lgraph, &J.c_lgraph}) {
+    if (path->empty()) continue;
+    const bool was_there = file_bytes(*path) >= 0;
+    FILE* f = std::fopen(path->c_str(), "ab");
+    if (!f) { std::fprintf(stderr, "cannot write %s\n", path->c_str()); return 2; }
+    std::fclose(f);
+    if (!was_there) std::remove(path->c_str());
   }
   return 0;
 }
@@ -241,6 +260,29 @@ static std::string write_components(vgs_tiles* t, const Job& J, int rank, const 
   return "";
 }
 
+// The adjacency graph of a labelling of this rank's points with K labels: two collectives of every rank, the same table on each; rank 0
+// writes the CSV.  "" on success.
+static std::string write_label_graph(vgs_tiles* t, int rank, const std::vector<int32_t>& lab, int64_t n, int64_t K, const std::string& path) {
+  pcl::LabelGraph g;
+  int64_t E = 0;
+  if (vgs_tiles_point_label_graph(t, lab.data(), n, K, &E, &g.n_skipped) != VGS_OK) return std::string("rank ") + std::to_string(rank) + ": " + vgs_tiles_last_error_string(t);
+  if (rank != 0) return "";
+  const size_t e1 = (size_t)E;
+  std::vector<int32_t> ab(2 * e1 + 2), nd(2 * e1 + 2);
+  std::vector<int64_t> ns(e1 + 1), np(e1 + 1), nf(e1 + 1);
+  std::vector<double> ws(e1 + 1);
+  std::vector<float> mn(e1 + 1), mx(e1 + 1);
+  if (vgs_tiles_get_point_label_graph(t, ab.data(), ns.data(), np.data(), nf.data(), nd.data(), ws.data(), mn.data(), mx.data()) != VGS_OK)
+    return std::string("rank 0: ") + vgs_tiles_last_error_string(t);
+  g.edges.resize(e1);
+  for (size_t i = 0; i < e1; ++i) {
+    pcl::LabelEdge& e = g.edges[i];
+    e.a = ab[2 * i]; e.b = ab[2 * i + 1]; e.n_shared = ns[i]; e.n_pairs = np[i]; e.n_finite = nf[i]; e.nodes_a = nd[2 * i]; e.nodes_b = nd[2 * i + 1];
+    e.w_sum = ws[i]; e.w_min = mn[i]; e.w_max = mx[i];
+  }
+  return writeLabelGraphCsv(path, g) != 0 ? "cannot write " + path : "";
+}
+
 // one rank: load, run, save; returns 0 on success
 static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world, int64_t* kept, int64_t* n_pts, int64_t* n_rec, int64_t* refine_counts /* 5 */, std::string* err) {
   std::vector<float> xyz;
@@ -248,7 +290,7 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
   std::vector<float> field;
   std::vector<int32_t> cls;
   if ((!J.fields.empty() || !J.r_fields.empty()) && !read_f32(rank_file(J, rank, ".fields.f32"), field)) { *err = "cannot read the fields of rank " + std::to_string(rank); return 1; }
-  if ((!J.classes.empty() || !J.r_classes.empty() || !J.c_parts.empty()) && !read_i32(rank_file(J, rank, ".classes.i32"), cls)) { *err = "cannot read the classes of rank " + std::to_string(rank); return 1; }
+  if ((!J.classes.empty() || !J.r_classes.empty() || !J.c_parts.empty() || !J.c_lgraph.empty()) && !read_i32(rank_file(J, rank, ".classes.i32"), cls)) { *err = "cannot read the classes of rank " + std::to_string(rank); return 1; }
   std::vector<int32_t> truth;
   if ((!J.matches.empty() || !J.r_matches.empty()) && !read_i32(rank_file(J, rank, ".truth.i32"), truth)) { *err = "cannot read the truth ids of rank " + std::to_string(rank); return 1; }
   vgs_tiles* t = nullptr;
@@ -405,10 +447,20 @@ static int run_rank(const Job& J, int comm_kind, void* comm, int rank, int world
       const std::string e = write_components(t, J, rank, fine, n, *kept, J.r_parts);
       if (!e.empty()) { *err = e; rc = 1; }
     }
+    if (rc == 0 && !J.r_lgraph.empty()) {
+      fine.resize((size_t)n + 1);
+      const std::string e = write_label_graph(t, rank, fine, n, *kept, J.r_lgraph);
+      if (!e.empty()) { *err = e; rc = 1; }
+    }
   }
   if (rc == 0 && !J.c_parts.empty()) {
     cls.resize((size_t)n + 1);
     const std::string e = write_components(t, J, rank, cls, n, J.n_classes, J.c_parts);
+    if (!e.empty()) { *err = e; rc = 1; }
+  }
+  if (rc == 0 && !J.c_lgraph.empty()) {
+    cls.resize((size_t)n + 1);
+    const std::string e = write_label_graph(t, rank, cls, n, J.n_classes, J.c_lgraph);
     if (!e.empty()) { *err = e; rc = 1; }
   }
   if (rc == 0) {
@@ -459,7 +511,7 @@ static bool exchange_id(ncclUniqueId* id, int rank, int world, const char* addr,
 }
 
 static void print_usage(const char* exe) {
-  std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] [--refine [--patch-radius r] [--switch-ratio s] [--no-fill] [--refined-segments file.csv] [--refined-segment-boxes file.csv] [--refined-matches file.csv [--refined-truth-matches file.csv]] [--refined-segment-fields file.csv --field-channels C] [--refined-segment-classes file.csv --classes C] [--refined-components file.csv]] [--class-components file.csv --classes C] [--component-ids] <prefix>\n", exe);
+  std::fprintf(stderr, "usage: %s (--rccl|--emulate) <tx>x<ty> [--pitch m] [--voxel m] [--graph m] [--segments file.csv] [--segment-graph file.csv] [--segment-boxes file.csv [--box-frame principal|upright]] [--segment-fields file.csv --field-channels C] [--segment-classes file.csv --classes C] [--segment-matches file.csv [--truth-matches file.csv]] [--refine [--patch-radius r] [--switch-ratio s] [--no-fill] [--refined-segments file.csv] [--refined-segment-boxes file.csv] [--refined-matches file.csv [--refined-truth-matches file.csv]] [--refined-segment-fields file.csv --field-channels C] [--refined-segment-classes file.csv --classes C] [--refined-components file.csv] [--refined-graph file.csv]] [--class-components file.csv --classes C] [--component-ids] [--class-graph file.csv --classes C] <prefix>\n", exe);
 }
 
 int main(int argc, char** argv) {
@@ -500,6 +552,8 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--refined-components") && a + 1 < argc) J.r_parts = argv[++a];
     else if (!std::strcmp(argv[a], "--class-components") && a + 1 < argc) J.c_parts = argv[++a];
     else if (!std::strcmp(argv[a], "--component-ids")) J.part_ids = true;
+    else if (!std::strcmp(argv[a], "--refined-graph") && a + 1 < argc) J.r_lgraph = argv[++a];
+    else if (!std::strcmp(argv[a], "--class-graph") && a + 1 < argc) J.c_lgraph = argv[++a];
     else if (!std::strcmp(argv[a], "--refine")) J.refine = true;
     else if (!std::strcmp(argv[a], "--no-fill")) { J.refine_fill = false; refine_opts = true; }
     else if ((!std::strcmp(argv[a], "--patch-radius") || !std::strcmp(argv[a], "--switch-ratio")) && a + 1 < argc) {
@@ -524,7 +578,8 @@ int main(int argc, char** argv) {
   if (!J.classes.empty() && !have_classes) { std::fprintf(stderr, "--segment-classes needs --classes <C>\n"); return 2; }
   if (!J.r_classes.empty() && !have_classes) { std::fprintf(stderr, "--refined-segment-classes needs --classes <C>\n"); return 2; }
   if (!J.c_parts.empty() && !have_classes) { std::fprintf(stderr, "--class-components needs --classes <C>\n"); print_usage(argv[0]); return 2; }
-  if (J.classes.empty() && J.r_classes.empty() && J.c_parts.empty() && have_classes) { std::fprintf(stderr, "--classes needs --segment-classes <file.csv>\n"); return 2; }
+  if (!J.c_lgraph.empty() && !have_classes) { std::fprintf(stderr, "--class-graph needs --classes <C>\n"); print_usage(argv[0]); return 2; }
+  if (J.classes.empty() && J.r_classes.empty() && J.c_parts.empty() && J.c_lgraph.empty() && have_classes) { std::fprintf(stderr, "--classes needs --segment-classes <file.csv>\n"); return 2; }
   if (have_classes && (J.n_classes < 1 || J.n_classes > 1024)) { std::fprintf(stderr, "--classes must be in 1 .. 1024\n"); print_usage(argv[0]); return 2; }
   if (J.part_ids && J.r_parts.empty() == J.c_parts.empty()) {
     std::fprintf(stderr, J.r_parts.empty() ? "--component-ids needs --refined-components or --class-components\n"
@@ -542,11 +597,13 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (J.r_matches.empty() && !J.r_truth_matches.empty()) { std::fprintf(stderr, "--refined-truth-matches needs --refined-matches <file.csv>\n"); return 2; }
+  if (!J.r_lgraph.empty() && !J.refine) { std::fprintf(stderr, "--refined-graph needs --refine\n"); print_usage(argv[0]); return 2; }
   const int world = J.tx * J.ty;
   int64_t kept = 0, n_pts = 0, n_rec = 0;
   int64_t rcounts[5] = {0, 0, 0, 0, 0};
   if (mode == 1) {
     for (int r = 0; r < world; ++r) if (check_attribute_files(J, r) != 0) return 2;
+    if (check_graph_paths(J) != 0) return 2;
     void* group = nullptr;
     vgs_tiles_local_group_create(world, &group);
     std::vector<std::thread> th;
@@ -569,6 +626,7 @@ int main(int argc, char** argv) {
     const char* e_addr = std::getenv("MASTER_ADDR"); const char* e_port = std::getenv("MASTER_PORT");
     const int rank = e_rank ? std::atoi(e_rank) : 0;
     if (check_attribute_files(J, rank) != 0) return 2;
+    if (rank == 0 && check_graph_paths(J) != 0) return 2;
     if ((e_world ? std::atoi(e_world) : 1) != world) { std::fprintf(stderr, "WORLD_SIZE does not match the %dx%d layout\n", J.tx, J.ty); return 2; }
     J.p.device = e_local ? std::atoi(e_local) : 0;
     if (hipSetDevice(J.p.device) != hipSuccess) { std::fprintf(stderr, "hipSetDevice(%d) failed\n", J.p.device); return 1; }

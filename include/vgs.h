@@ -806,7 +806,7 @@ vgs_status vgs_get_point_label_components_device(vgs_ctx* ctx, const int32_t** p
  * vgs_point_label_graph or the next run of the stages, and answer VGS_E_STATE without a result since the last run.  No other table, no
  * labels and no result of vgs_point_label_components are touched.
  * VGS_E_STATE before the context is segmented, and for a tile context: it holds part of the cloud and of the graph only, and the graph of a
- * labelling across the ranks of the tiled driver is not computed.  VGS_E_ARG for n != N, a NULL labelling, K outside 0 .. 2^31 - 1. */
+ * labelling across the ranks of the tiled driver is not computed by this call (vgs_tiles_point_label_graph does).  VGS_E_ARG for n != N, a NULL labelling, K outside 0 .. 2^31 - 1. */
 vgs_status vgs_point_label_graph(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_edges, int64_t* n_skipped);
 vgs_status vgs_point_label_graph_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_edges, int64_t* n_skipped);
 vgs_status vgs_get_point_label_graph(vgs_ctx* ctx, int32_t* seg_ab, int64_t* n_shared, int64_t* n_pairs, int64_t* n_finite, int32_t* nodes_ab,
@@ -845,6 +845,32 @@ vgs_status vgs_get_point_label_part_links(vgs_ctx* ctx, int32_t* own_part, int32
 vgs_status vgs_apply_point_label_part_ids(vgs_ctx* ctx, const int32_t* map, int64_t n);
 vgs_status vgs_get_point_label_part_ids(vgs_ctx* ctx, int32_t* part_of_point, int64_t n);
 vgs_status vgs_get_point_label_part_ids_device(vgs_ctx* ctx, const int32_t** part_of_point);
+/* Tile contexts: a rank's share of the adjacency graph of a labelling over all ranks of the tiled driver.  include/vgs_tiles.h
+ * (vgs_tiles_point_label_graph) states the counting rule and the protocol these steps serve; csrc/labelgraph_tiles.hip has the kernels.
+ * Every call answers VGS_E_STATE on a plain context and before a run.
+ * vgs_own_point_label_band[_device]: `labels` as in vgs_own_point_label_parts.  The (label, node) vertices of the own points, without
+ * the union-find of the parts pass, and the BAND records -- (voxel code, label) of every own vertex whose node centre lies within
+ * graph_size + voxel_size of a border line of the owned region, in ascending (label, node) order; none for K <= 1.  n_band and n_skipped
+ * may be NULL.  vgs_get_own_point_label_band copies the records out; either pointer may be NULL.  The pass overwrites the vertex arrays
+ * of vgs_own_point_label_parts (whose later steps then answer VGS_E_STATE until the next own parts), and the reverse.
+ * vgs_own_point_label_graph: the OTHER ranks' band records (code, label; host arrays of n_foreign entries, any order).  A code this
+ * context does not hold and a label outside 0 .. K-1 drop out; the rest is merged with the own vertices, a vertex two ranks publish
+ * being one vertex.  The walk of vgs_point_label_graph then runs over the merged list under the rule of include/vgs_tiles.h: vertices at
+ * owned nodes walk in full, vertices at non-owned unused nodes only speak for owned vertices when the stored rows are pruned, every
+ * other vertex is left to its owner.  *n_edges = the rows of this rank's PARTIAL table, in ascending (a, b).
+ * vgs_get_own_point_label_graph copies the partial table out (fields and types of vgs_get_point_label_graph; any pointer may be
+ * NULL); the sum of the ranks' partial tables is the table of the whole scene (vgs_tiles_fold_label_edges).
+ * vgs_get_own_point_label_graph_counts (for the driver's payload figures): band records of the last own pass, foreign records whose code
+ * was found in the local grid -- counted before the label check, so a record dropped for a label outside 0 .. K-1 is among them --,
+ * partial edges.
+ * All results stay until the next vgs_own_point_label_band, the next vgs_own_point_label_parts or the next run of the stages. */
+vgs_status vgs_own_point_label_band(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_band, int64_t* n_skipped);
+vgs_status vgs_own_point_label_band_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_band, int64_t* n_skipped);
+vgs_status vgs_get_own_point_label_band(vgs_ctx* ctx, uint64_t* code, int32_t* label);
+vgs_status vgs_own_point_label_graph(vgs_ctx* ctx, const uint64_t* code, const int32_t* label, int64_t n_foreign, int64_t* n_edges);
+vgs_status vgs_get_own_point_label_graph(vgs_ctx* ctx, int32_t* seg_ab, int64_t* n_shared, int64_t* n_pairs, int64_t* n_finite, int32_t* nodes_ab,
+                                         double* w_sum, float* w_min, float* w_max);
+vgs_status vgs_get_own_point_label_graph_counts(vgs_ctx* ctx, int64_t* n_band, int64_t* n_hits, int64_t* n_edges);
 
 /* ---- multi-GPU support (spatial tiles) -------------------------------------- */
 /* The reference is single-process; these entry points are what a tiled driver needs around the same stages.

@@ -497,6 +497,70 @@ enum { VGS_TILES_CC_OWN = 0, VGS_TILES_CC_EXCHANGE1 = 1, VGS_TILES_CC_LINK = 2, 
 vgs_status vgs_tiles_get_point_label_component_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_CC_COUNT */);
 /* that call's payload on this rank: band records, local parts and link triples of its own, bytes it put into the two all-gathers */
 vgs_status vgs_tiles_get_point_label_component_payload(vgs_tiles* t, int64_t* band_records, int64_t* parts, int64_t* links, int64_t* bytes_sent);
+/* Adjacency graph of ANY per-point labelling the caller supplies, over all ranks: which refined segments, parts or classes of a scene
+ * larger than one GPU touch, across how much boundary and how strongly (vgs_tiles_get_segment_graph describes the voxel labels only).
+ * Definition: that of vgs_point_label_graph (include/vgs.h) over the whole scene, the nodes being the voxels of the shared grid.  Every
+ * rank receives the same table with the fields, types, edge order and NaN rules of vgs_get_point_label_graph.  It equals what one
+ * context's vgs_point_label_graph gives on the gathered points (the ranks' loads concatenated in rank order): seg_ab, n_shared, n_pairs,
+ * n_finite, nodes_ab, w_min, w_max byte for byte; w_sum within 1e-10 relative, because the ranks' partial sums are added in rank order
+ * and the summation shape differs from one context's.  With one rank the table is the single context's byte for byte, w_sum included.
+ * The table is bit-identical from call to call.  n_skipped is the sum over the ranks.  VGS only.  No point and no label of a point leaves
+ * its rank.  labels, n, K and the _device variant: as vgs_tiles_point_label_components; so is the precondition (points loaded by region).
+ * COUNTING RULE.  Every voxel of the shared grid has exactly one owner, the rank whose region holds its centre (vgs_compute_owned).  A
+ * vertex (label, node) exists when any rank holds a point with that label in that node.  EVERY RECORD OF csrc/labelgraph.hip LIVES ON
+ * THE RANK THAT OWNS THE NODE OF THE VERTEX IT SPEAKS FOR -- a vertex's own per-label records and the proxy records written on its
+ * behalf alike.  Hence:
+ *   Contacts.  A contact {(A, u), (B, x)} is counted by the walker of its counting side exactly as on one context (the walker of u counts
+ *     it at entry x when u < x or x's row lacks u), and that walker runs on owner(u) only.  Node ids are in descending code order of the
+ *     same grid on every rank, so the comparison agrees across ranks; with VGS "x's row holds u" depends on whether x is used alone, and
+ *     node records of halo voxels equal their owner's, so the predicate agrees as well.
+ *   Shared nodes.  A shared node is counted by its owner.
+ *   nodes_ab.  A vertex's own record and all its proxies are on one rank, so the fold's "first record of a vertex counts it" rule counts
+ *     it once over all ranks.  A proxy arises only under pruned stored rows, from the built row of an unused node x towards a used node u:
+ *     on owner(u) the vertices at NON-OWNED unused nodes of the merged list walk their built rows in a proxy-only mode (no record of
+ *     their own, no counts, only proxies whose target node is owned), and a vertex at an owned node writes no proxy whose target node it
+ *     does not own.  Without pruned rows no non-owned vertex walks.
+ * What a rank needs for this is the complete label set of every owned node and of every node adjacent to one.  Labels of its own points
+ * it has; labels carried by another rank's points arrive as that rank's band records (code, label) -- the band of
+ * vgs_tiles_point_label_components: own vertices whose node centre lies within graph_size + voxel_size of a border line (DESIGN.md 8 has
+ * the argument).
+ * Protocol (csrc/tiles.cpp, csrc/labelgraph_tiles.hip): TWO all_gather_varlen per call, K <= 1 included; nothing is cached.
+ *   1. Own pass on each rank's GPU (vgs_own_point_label_band): the (label, node) vertices of the own points, the band records.
+ *   2. Exchange 1: a header record (status word, band count, K, own n_skipped), then 16 bytes a band record (code, label).
+ *   3. Merged vertices and 4. the walk on each rank's GPU (vgs_own_point_label_graph): the other ranks' records looked up in the local
+ *      grid (a code the rank does not hold drops out), concatenated with the own vertices, sorted, unique -- a vertex two ranks publish is
+ *      one vertex; then the walk in tile mode and the unchanged sort, chunk and fold pipeline give the rank's partial table.
+ *   5. Exchange 2: a header record (status word, record count), then 56 bytes an edge of the partial table.
+ *   6. The same host fold on every rank (vgs_tiles_fold_label_edges): the tables merged by (a, b), ranks in ascending order; n_shared,
+ *      n_pairs, n_finite and nodes_ab add, w_sum adds in fp64 in rank order, the extrema come from the ranks with n_finite > 0.
+ * The table is kept until the next call, the next run or the next vgs_tiles_set_points; vgs_tiles_get_point_label_graph copies it out
+ * (n_edges rows; any pointer may be NULL), is not collective and answers VGS_E_STATE without a result.  vgs_tiles_run gains no launch
+ * and no collective.  The call's own pass overwrites the vertex arrays of vgs_tiles_point_label_components' own pass, so it drops that
+ * call's result (vgs_tiles_get_point_label_components answers VGS_E_STATE until the next components call); a components call leaves the
+ * graph's table alone.  No other cached table is touched.
+ * Failures: the contract of vgs_tiles_point_label_components.  VGS_E_STATE before a run is decided locally.  A local failure of step 1
+ * and the injected VGS_TILES_FAIL_AT=label_graph travel in the header of exchange 1, a failure of steps 3 and 4 in that of exchange 2:
+ * the failing rank returns its own status and message, the others VGS_E_PEER naming it.  Ranks that disagree on K all return VGS_E_ARG. */
+vgs_status vgs_tiles_point_label_graph(vgs_tiles* t, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_edges, int64_t* n_skipped);
+vgs_status vgs_tiles_point_label_graph_device(vgs_tiles* t, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_edges, int64_t* n_skipped);
+vgs_status vgs_tiles_get_point_label_graph(vgs_tiles* t, int32_t* seg_ab, int64_t* n_shared, int64_t* n_pairs, int64_t* n_finite, int32_t* nodes_ab,
+                                           double* w_sum, float* w_min, float* w_max);
+/* host arithmetic only, no context (tests): step 6 on flattened per-rank partial tables, rank r's edges being rec_off[r] ..
+ * rec_off[r + 1].  The outputs hold at most rec_off[world] rows, *n_edges of them written; any output array may be NULL.  VGS_E_ARG for
+ * a label outside 0 .. K-1, a >= b, or a rank table that is not strictly ascending in (a, b). */
+vgs_status vgs_tiles_fold_label_edges(int world, int64_t K, const int64_t* rec_off /* world + 1 */, const int32_t* seg_ab, const int64_t* n_shared,
+                                      const int64_t* n_pairs, const int64_t* n_finite, const int32_t* nodes_ab, const double* w_sum,
+                                      const float* w_min, const float* w_max, int64_t* n_edges, int32_t* seg_ab_out, int64_t* n_shared_out,
+                                      int64_t* n_pairs_out, int64_t* n_finite_out, int32_t* nodes_ab_out, double* w_sum_out, float* w_min_out,
+                                      float* w_max_out);
+/* host wall time of the last label-graph call on this rank, milliseconds: the own pass on the GPU (with upload and download), exchange
+ * 1, the partial table on the GPU, exchange 2, the host fold, total */
+enum { VGS_TILES_LG_OWN = 0, VGS_TILES_LG_EXCHANGE1 = 1, VGS_TILES_LG_TABLE = 2, VGS_TILES_LG_EXCHANGE2 = 3, VGS_TILES_LG_FOLD = 4, VGS_TILES_LG_TOTAL = 5,
+       VGS_TILES_LG_COUNT = 6 };
+vgs_status vgs_tiles_get_label_graph_times(vgs_tiles* t, double* ms, int32_t n /* <= VGS_TILES_LG_COUNT */);
+/* that call's payload on this rank: band records of its own, other ranks' records whose code it found in its grid, edges of its partial table,
+ * bytes it put into the two all-gathers */
+vgs_status vgs_tiles_get_label_graph_payload(vgs_tiles* t, int64_t* band_records, int64_t* foreign_hits, int64_t* own_edges, int64_t* bytes_sent);
 /* the rank's engine context (read-only use: counts, stage times) */
 vgs_ctx* vgs_tiles_context(vgs_tiles* t);
 

@@ -171,6 +171,12 @@ SYMBOLS = [
     ("vgs_point_label_graph_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
     ("vgs_get_point_label_graph", C.c_int, [_P] + [_P] * 8),
     ("vgs_get_point_label_graph_device", C.c_int, [_P, C.POINTER(C.c_int64)] + [_P] * 8),
+    ("vgs_own_point_label_band", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("vgs_own_point_label_band_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    ("vgs_get_own_point_label_band", C.c_int, [_P, _P, _P]),
+    ("vgs_own_point_label_graph", C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    ("vgs_get_own_point_label_graph", C.c_int, [_P] + [_P] * 8),
+    ("vgs_get_own_point_label_graph_counts", C.c_int, [_P, _P, _P, _P]),
     ("vgs_grid_state_init", C.c_int, [C.POINTER(VgsGridState)]),
     ("vgs_grid_advance", C.c_int, [_P, C.POINTER(VgsGridState)]),
     ("vgs_points_bbox", C.c_int, [_P, _P, C.POINTER(C.c_int64)]),

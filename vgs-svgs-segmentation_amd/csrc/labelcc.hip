@@ -354,7 +354,7 @@ vgs_status vgs_label_parts_on_device(vgs_ctx* c, const char* fn, const int32_t* 
                                      int64_t* n_skipped) {
   const int64_t N = c->N, nf = c->Nf, V = c->V, U = c->U;
   const size_t k = (size_t)K;
-  c->lcc_valid = false; c->lcc_nv = 0; c->lct_own = c->lct_linked = c->lct_applied = false;
+  c->lcc_valid = false; c->lcc_nv = 0; c->lct_own = c->lct_linked = c->lct_applied = false; c->lgt_own = c->lgt_valid = false;
   VGS_HIP_TRY(c, c->lcc_pop.ensure(N > 0 ? (size_t)N : 1)); VGS_HIP_TRY(c, c->lcc_lfirst.ensure(k + 1)); VGS_HIP_TRY(c, c->lcc_llargest.ensure(k + 1));
   PsSort S;
   LcVtx X;

@@ -74,7 +74,8 @@ __global__ __launch_bounds__(LT_TB) void k_lt_band_records(const uint32_t* __res
   if (i >= (uint64_t)nv || !flag[i]) return;
   const uint32_t o = excl[i];
   if (o >= cap) return;   // (cap is the scan's own total: the bound only guards the arrays)
-  code[o] = vox_code[vnode[i]]; label[o] = (int32_t)vlabel[i]; part[o] = (int32_t)vpart[i]; vtx[o] = (uint32_t)i;
+  code[o] = vox_code[vnode[i]]; label[o] = (int32_t)vlabel[i];
+  if (vpart) { part[o] = (int32_t)vpart[i]; vtx[o] = (uint32_t)i; }   // (nullptr: the label graph's band, code and label only)
 }
 __global__ __launch_bounds__(LT_TB) void k_lt_part_codes(const int32_t* __restrict__ p_first, const uint64_t* __restrict__ vox_code, uint32_t C, int64_t V,
                                                          uint64_t* __restrict__ p_code) {
@@ -210,6 +211,39 @@ static vgs_status lt_check(vgs_ctx* c, const char* fn) {
   return VGS_OK;
 }
 
+// the band records of nv vertices, compacted in ascending vertex order (vpart == nullptr: code and label only, lct_bpart and lct_bvtx are
+// left alone); the stream is waited for
+vgs_status vgs_lt_band_on_device(vgs_ctx* c, const uint32_t* vnode, const uint32_t* vlabel, const uint32_t* vpart, uint32_t nv, uint32_t* n_band) {
+  *n_band = 0;
+  if (nv == 0) return VGS_OK;
+  const size_t w = (size_t)nv + 1;
+  uint32_t nb = 0;
+  vgs_status s;
+  VGS_HIP_TRY(c, c->lct_flag.ensure(w)); VGS_HIP_TRY(c, c->lct_scan.ensure(w));
+  hipLaunchKernelGGL(k_lt_band_flags, dim3(lt_grid(w)), dim3(LT_TB), 0, c->stream, vnode, c->vox_code.p, nv, rf_region(c), lt_near(c), c->lct_flag.p);
+  if ((s = lt_scan(c, c->lct_flag.p, c->lct_scan.p, w)) != VGS_OK) return s;
+  VGS_READBACK(c, &nb, c->lct_scan.p + nv, 4);
+  if (nb > 0) {
+    VGS_HIP_TRY(c, c->lct_bcode.ensure(nb)); VGS_HIP_TRY(c, c->lct_blabel.ensure(nb));
+    if (vpart) { VGS_HIP_TRY(c, c->lct_bpart.ensure(nb)); VGS_HIP_TRY(c, c->lct_bvtx.ensure(nb)); }
+    hipLaunchKernelGGL(k_lt_band_records, dim3(lt_grid(nv)), dim3(LT_TB), 0, c->stream, c->lct_flag.p, c->lct_scan.p, vnode, vlabel, vpart, c->vox_code.p, nv, nb,
+                       c->lct_bcode.p, c->lct_blabel.p, vpart ? c->lct_bpart.p : nullptr, vpart ? c->lct_bvtx.p : nullptr);
+  }
+  VGS_HIP_TRY(c, hipGetLastError());
+  VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *n_band = nb;
+  return VGS_OK;
+}
+
+// the lookup of n records in the local grid (k_lt_find), left on the stream
+vgs_status vgs_lt_find_on_device(vgs_ctx* c, const uint64_t* code_dev, const int32_t* label_dev, int64_t n, uint64_t* key, uint32_t* val,
+                                 unsigned long long* counts) {
+  if (n <= 0) return VGS_OK;
+  hipLaunchKernelGGL(k_lt_find, dim3(lt_grid((uint64_t)n)), dim3(LT_TB), 0, c->stream, code_dev, label_dev, n, c->vox_code.p, c->V, key, val, counts);
+  VGS_HIP_TRY(c, hipGetLastError());
+  return VGS_OK;
+}
+
 static vgs_status lt_own(vgs_ctx* c, const char* fn, const int32_t* labels, bool on_device, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_band,
                          int64_t* n_skipped) {
   if (!c) return VGS_E_ARG;
@@ -218,7 +252,7 @@ static vgs_status lt_own(vgs_ctx* c, const char* fn, const int32_t* labels, bool
   if (n_skipped) *n_skipped = 0;
   vgs_status s = lt_check(c, fn);
   if (s != VGS_OK) return s;
-  c->lcc_valid = false; c->lct_own = c->lct_linked = c->lct_applied = false;
+  c->lcc_valid = false; c->lct_own = c->lct_linked = c->lct_applied = false; c->lgt_own = c->lgt_valid = false;
   if (n != c->n_own) {
     c->err = std::string(fn) + ": n = " + std::to_string(n) + " must equal the number of own points of the context, " + std::to_string(c->n_own);
     return VGS_E_ARG;
@@ -238,18 +272,9 @@ static vgs_status lt_own(vgs_ctx* c, const char* fn, const int32_t* labels, bool
   if (nv > 0 && C > 0) {
     const size_t w = (size_t)nv + 1;
     const uint32_t *vnode = c->lcc_vtx.p, *vlabel = vnode + w, *vpart = vnode + 5 * w;
-    VGS_HIP_TRY(c, c->lct_flag.ensure(w)); VGS_HIP_TRY(c, c->lct_scan.ensure(w)); VGS_HIP_TRY(c, c->lct_pcode.ensure((size_t)C));
-    hipLaunchKernelGGL(k_lt_band_flags, dim3(lt_grid(w)), dim3(LT_TB), 0, c->stream, vnode, c->vox_code.p, nv, rf_region(c), lt_near(c), c->lct_flag.p);
+    VGS_HIP_TRY(c, c->lct_pcode.ensure((size_t)C));
     hipLaunchKernelGGL(k_lt_part_codes, dim3(lt_grid((uint64_t)C)), dim3(LT_TB), 0, c->stream, c->lcc_pfirst.p, c->vox_code.p, (uint32_t)C, c->V, c->lct_pcode.p);
-    if ((s = lt_scan(c, c->lct_flag.p, c->lct_scan.p, w)) != VGS_OK) return s;
-    VGS_READBACK(c, &nb, c->lct_scan.p + nv, 4);
-    if (nb > 0) {
-      VGS_HIP_TRY(c, c->lct_bcode.ensure(nb)); VGS_HIP_TRY(c, c->lct_blabel.ensure(nb)); VGS_HIP_TRY(c, c->lct_bpart.ensure(nb)); VGS_HIP_TRY(c, c->lct_bvtx.ensure(nb));
-      hipLaunchKernelGGL(k_lt_band_records, dim3(lt_grid(nv)), dim3(LT_TB), 0, c->stream, c->lct_flag.p, c->lct_scan.p, vnode, vlabel, vpart, c->vox_code.p, nv, nb,
-                         c->lct_bcode.p, c->lct_blabel.p, c->lct_bpart.p, c->lct_bvtx.p);
-    }
-    VGS_HIP_TRY(c, hipGetLastError());
-    VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((s = vgs_lt_band_on_device(c, vnode, vlabel, vpart, nv, &nb)) != VGS_OK) return s;
   }
   c->lct_band = (int64_t)nb; c->lct_links = 0; c->lct_K = K; c->lct_own = true;
   if (n_parts) *n_parts = C;
@@ -329,8 +354,7 @@ extern "C" vgs_status vgs_link_point_label_parts(vgs_ctx* c, const uint64_t* cod
     VGS_HIP_TRY(c, hipMemcpyAsync(c->lct_fpart.p, part, m * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     unsigned long long* counts = (unsigned long long*)c->lct_count.p;
     VGS_HIP_TRY(c, hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(k_lt_find, dim3(lt_grid(m)), dim3(LT_TB), 0, c->stream, c->lct_fcode.p, c->lct_flabel.p, n, c->vox_code.p, V, c->lct_key.p, c->lct_val.p, counts);
-    VGS_HIP_TRY(c, hipGetLastError());
+    if ((s = vgs_lt_find_on_device(c, c->lct_fcode.p, c->lct_flabel.p, n, c->lct_key.p, c->lct_val.p, counts)) != VGS_OK) return s;
     size_t t_sort = 0;
     VGS_HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, t_sort, c->lct_key.p, c->lct_key2.p, c->lct_val.p, c->lct_val2.p, m, 0, 64, c->stream));
     VGS_HIP_TRY(c, c->ps_tmp.ensure(t_sort));

@@ -21,6 +21,10 @@
 //   4. - 6. seggraph.hip's pipeline restated over these records: stable radix sort by min * K + max, heads, starts, chunk partials of
 //      LG_CHUNK records, final fold (k_lg_heads, k_lg_starts, k_lg_nchunk, k_lg_chunks, k_lg_final).
 //
+// The walk itself is labelgraph_walk.hpp's lg_walk_body, which labelgraph_tiles.hip's kernel calls in tile mode; step 2 and steps 3 to 6
+// are host functions of their own (vgs_lg_vertices_by_node, vgs_lg_table_from_walk) that the tile context runs with its walk in place of
+// the plain one.
+//
 // Every contact is counted once.  Let R(x) be the row this pass reads for node x and "x holds y" mean y in R(x); {v, w} is adjacent when
 // v holds w or w holds v.  Both endpoints of a contact carry a vertex, so both rows are walked.  The walker of u, at entry x, counts the
 // contact when  u < x  or  x does not hold u.  If both rows hold the pair only the lower id has u < x; if only one row holds it, that
@@ -60,15 +64,11 @@
 
 #include "vgs_context.hpp"
 #include "wavefold.hpp"
+#include "labelgraph_walk.hpp"   // LG_WAVES, LG_NONE, the record flags, LG_HOLDS_*, lg_lower and the walk itself
 
 #define LG_TB 256
-#define LG_WAVES 4                 // wavefronts per workgroup of the row, chunk and edge kernels
 #define LG_PPL 4                   // records per lane of a chunk
 #define LG_CHUNK (64 * LG_PPL)     // records per chunk (seggraph.hip's SG_CHUNK: the same fold shape)
-#define LG_NONE 0xffffffffu
-#define LG_CONTACT 1u
-#define LG_SHARED 2u
-enum { LG_HOLDS_ALWAYS = 0, LG_HOLDS_UNUSED = 1, LG_HOLDS_SEARCH = 2 };
 
 // Step 2.  iota for the sort's values; behind the sort the label of every position and the run of every node
 __global__ __launch_bounds__(LG_TB) void k_lg_iota(uint32_t nv, uint32_t* __restrict__ out) {
@@ -105,16 +105,10 @@ __global__ __launch_bounds__(LG_TB) void k_lg_unused_list(const uint32_t* __rest
   if (flag[t] && o < cap) un_node[o] = v;      // (cap = the number of flags: the bound only guards the list)
 }
 
-// first position of slab[b .. e) whose label is not below l
-__device__ __forceinline__ uint32_t lg_lower(const uint32_t* __restrict__ slab, uint32_t b, uint32_t e, int32_t l) {
-  while (b < e) { const uint32_t mid = (b + e) >> 1; if ((int32_t)slab[mid] < l) b = mid + 1; else e = mid; }
-  return b;
-}
-
 // Step 3.  One wavefront per position t = vertex (A, u).  urow == nullptr: the stored rows (a node without one has an empty row if
 // no_row_is_empty -- SVGS -- and leaves otherwise); urow != nullptr: the rows built for the unused nodes row0 .. row0 + n_rows - 1 of the
 // list, every other vertex leaves.  WRITE = false: n_rec[t] = its records, and the proxies among them are added to meta[2]; WRITE =
-// true: the records at rec_off[t] ...  The file header has the counting rule and what a proxy is.
+// true: the records at rec_off[t] ...  The file header has the counting rule and what a proxy is; the walk is labelgraph_walk.hpp's.
 template <bool WRITE>
 __global__ __launch_bounds__(64 * LG_WAVES) void k_lg_rows(uint32_t nv, const uint32_t* __restrict__ snode, const uint32_t* __restrict__ slab,
                                                            const uint32_t* __restrict__ nbeg, const uint32_t* __restrict__ nend,
@@ -126,119 +120,8 @@ __global__ __launch_bounds__(64 * LG_WAVES) void k_lg_rows(uint32_t nv, const ui
                                                            uint32_t* __restrict__ n_rec, const uint64_t* __restrict__ rec_off, LgRec* __restrict__ rec,
                                                            uint64_t* __restrict__ rkey, uint32_t* __restrict__ tkey, uint32_t* __restrict__ ridx,
                                                            uint32_t* __restrict__ meta) {
-  const uint32_t t = blockIdx.x * LG_WAVES + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (t >= nv) return;   // (whole wavefronts; no barrier follows)
-  const uint32_t u = snode[t];
-  const int32_t A = (int32_t)slab[t];
-  const uint32_t ru = used_rank[u];
-  const uint64_t* row = nullptr;
-  uint32_t n = 0;
-  if (urow == nullptr) {
-    if (ru != LG_NONE) { row = adj_key + (int64_t)ru * adj_stride; n = min(adj_cnt[ru], (uint32_t)adj_stride); }
-    else if (!no_row_is_empty) return;
-  } else {
-    const uint32_t j = urow[t];
-    if (j == LG_NONE || j < row0 || j - row0 >= n_rows) return;
-    row = rows + (int64_t)(j - row0) * adj_stride;
-    n = min(rows_cnt[j - row0], (uint32_t)adj_stride);
-  }
-  const uint32_t ub = nbeg[u], ue = nend[u];
-  uint64_t o = 0;
-  if (WRITE) o = rec_off[t];
-  uint32_t k = 0, n_proxy = 0;
-  int32_t cur = -1;   // the label this walk folds (none on the first walk)
-  while (true) {
-    int nxt = INT_MAX;
-    int c_cnt = 0, c_fin = 0;
-    bool seen = false, shared = false;
-    double s = 0.0;
-    float mn = __builtin_huge_valf(), mx = -__builtin_huge_valf();
-    if (lane == 0) {   // u's own other labels
-      uint32_t p = lg_lower(slab, ub, ue, cur);
-      if (p < ue && (int32_t)slab[p] == cur) { shared = cur >= 0; ++p; }
-      if (p < ue && (int32_t)slab[p] == A) ++p;
-      if (p < ue) nxt = (int)slab[p];
-    }
-    for (uint32_t base = 0; base < n; base += 64) {
-      const uint32_t j = base + lane;
-      bool proxy = false;
-      uint32_t px = 0;
-      if (j < n) {
-        const uint64_t e = row[j];
-        const uint32_t x = (uint32_t)e;
-        const uint32_t xb = nbeg[x], xe = nend[x];
-        if (x != u && xb != xe) {   // (a stored row starts with its own node)
-          uint32_t p = xe - xb == 1u ? xb + ((int32_t)slab[xb] < cur ? 1u : 0u) : lg_lower(slab, xb, xe, cur);
-          const bool has = cur >= 0 && p < xe && (int32_t)slab[p] == cur;
-          uint32_t q = has ? p + 1u : p;
-          if (q < xe && (int32_t)slab[q] == A) ++q;
-          if (q < xe) nxt = min(nxt, (int)slab[q]);
-          if (has) {
-            seen = true;
-            const uint32_t rx = used_rank[x];
-            bool hx = true;
-            if (holds == LG_HOLDS_UNUSED) hx = rx == LG_NONE;
-            else if (holds == LG_HOLDS_SEARCH)
-              hx = rx != LG_NONE && sg_in_row(adj_key + (int64_t)rx * adj_stride, min(adj_cnt[rx], (uint32_t)adj_stride), (e & 0xffffffff00000000ull) | (uint64_t)u, u);
-            if (u < x || !hx) {
-              ++c_cnt;
-              if (ru != LG_NONE && rx != LG_NONE) {
-                // the lower id first: vgs_get_local_weights' entry of that ordered pair
-                const float w = u < x ? vm_pair_weight(node[u], node[x], W) : vm_pair_weight(node[x], node[u], W);
-                if (!isnan(w)) { ++c_fin; s += (double)w; mn = fminf(mn, w); mx = fmaxf(mx, w); }
-              }
-            }
-            if (!hx) { proxy = true; px = p; }
-          }
-        }
-      }
-      const unsigned long long pm = __ballot(proxy);
-      if (pm != 0ull) {
-        if (WRITE && proxy) {
-          const uint64_t at = o + k + (uint32_t)__popcll(pm & ((1ull << lane) - 1ull));
-          if (at < (uint64_t)R) {   // (the count walk sized the range: the bound only guards the arrays)
-            LgRec q;
-            q.w_sum = 0.0; q.cnt = 0u; q.n_finite = 0u; q.a = cur; q.b = A; q.w_min = __builtin_huge_valf(); q.w_max = -__builtin_huge_valf();
-            q.t = px; q.flags = LG_CONTACT;
-            rec[at] = q;
-            const uint64_t lo = (uint64_t)(A < cur ? A : cur), hi = (uint64_t)(A < cur ? cur : A);
-            rkey[at] = lo * (uint64_t)K + hi;
-            tkey[at] = px;
-            ridx[at] = (uint32_t)at;
-          }
-        }
-        k += (uint32_t)__popcll(pm);
-        n_proxy += (uint32_t)__popcll(pm);
-      }
-    }
-    if (cur >= 0) {
-      if (WRITE) {
-        c_cnt = sg_wave_sum(c_cnt); c_fin = sg_wave_sum(c_fin);
-        s = sg_wave_sum(s); mn = sg_wave_min(mn); mx = sg_wave_max(mx);
-        const bool any_seen = __ballot(seen) != 0ull, any_shared = __ballot(shared) != 0ull;
-        const uint64_t at = o + k;
-        if (lane == 0 && at < (uint64_t)R) {
-          LgRec q;
-          q.w_sum = s; q.cnt = (uint32_t)c_cnt; q.n_finite = (uint32_t)c_fin; q.a = A; q.b = cur; q.w_min = mn; q.w_max = mx;
-          q.t = t; q.flags = (any_seen ? LG_CONTACT : 0u) | (any_shared ? LG_SHARED : 0u);
-          rec[at] = q;
-          const uint64_t lo = (uint64_t)(A < cur ? A : cur), hi = (uint64_t)(A < cur ? cur : A);
-          rkey[at] = lo * (uint64_t)K + hi;
-          tkey[at] = t;
-          ridx[at] = (uint32_t)at;
-        }
-      }
-      ++k;
-    }
-    nxt = sg_wave_min(nxt);
-    if (nxt == INT_MAX) break;
-    cur = nxt;
-  }
-  if (!WRITE && lane == 0) {
-    n_rec[t] = k;
-    if (n_proxy) atomicAdd(&meta[2], n_proxy);   // (an integer count: the same whatever the order)
-  }
+  lg_walk_body<WRITE, false>(nv, snode, slab, nbeg, nend, used_rank, adj_key, adj_cnt, adj_stride, urow, row0, n_rows, rows, rows_cnt, no_row_is_empty, holds, node,
+                             W, K, R, n_rec, rec_off, rec, rkey, tkey, ridx, meta, nullptr);
 }
 
 // with proxies: the edge keys in the order of the sort by vertex
@@ -364,15 +247,6 @@ static vgs_status lg_scan(vgs_ctx* c, uint32_t* in, uint32_t* out, size_t n) {
   return VGS_OK;
 }
 
-// what the row kernel needs besides the rows, and where the records go
-struct LgWalk {
-  uint32_t nv, K, R;
-  const uint32_t *snode, *slab, *nbeg, *nend;
-  VgsWeightParams W;
-  uint64_t* rkey;
-  uint32_t *tkey, *ridx;
-};
-
 // the row kernel over the stored rows (urow == nullptr) or over the built rows row0 .. row0 + n_rows - 1
 template <bool WRITE>
 static void lg_launch_rows(vgs_ctx* c, const LgWalk& G, const uint32_t* urow, uint32_t row0, uint32_t n_rows, int holds) {
@@ -399,18 +273,19 @@ static vgs_status lg_walk(vgs_ctx* c, const LgWalk& G, const uint32_t* urow, con
   return VGS_OK;
 }
 
-static vgs_status lg_build(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t K, int64_t* n_skipped) {
-  const int64_t V = c->V, U = c->U;
-  c->lg_valid = false; c->lg_E = 0;
-  c->lcc_nv = 0; c->lct_own = c->lct_linked = c->lct_applied = false;   // (the vertex arrays of the last parts pass are overwritten)
-  PsSort S;
-  LcVtx X;
-  uint32_t nv = 0;
-  vgs_status s = vgs_label_vertices_on_device(c, fn, labels_dev, 0, c->N, K, n_skipped, S, &nv, X);
-  if (s != VGS_OK) return s;
-  if (nv == 0 || K <= 1) { VGS_HIP_TRY(c, hipStreamSynchronize(c->stream)); c->lg_valid = true; return VGS_OK; }
-  // step 2: the vertices by node.  parent = iota, root = nodes sorted, part = vertices sorted; afterwards parent = the labels in that order
-  const size_t w = (size_t)nv + 1;
+// the unused nodes with a vertex and every vertex's row among them: what the plain walk needs besides LgWalk
+struct LgPlainRows { const uint32_t *urow, *un_node; uint32_t n_un; int64_t chunk; };
+static vgs_status lg_walk_plain(vgs_ctx* c, const LgWalk& G, bool write, void* arg) {
+  const LgPlainRows& P = *(const LgPlainRows*)arg;
+  if (write) return lg_walk<true>(c, G, P.urow, P.un_node, P.n_un, P.chunk, (int64_t)P.n_un <= P.chunk);
+  return lg_walk<false>(c, G, P.urow, P.un_node, P.n_un, P.chunk, false);
+}
+
+// Step 2: the vertices X (nv of them, in (label, node) order) by node.  parent = iota, root = nodes sorted, part = vertices sorted;
+// afterwards parent = the labels in that order
+vgs_status vgs_lg_vertices_by_node(vgs_ctx* c, const LcVtx& X, uint32_t nv, int64_t K, LgWalk& G) {
+  const int64_t V = c->V;
+  VGS_HIP_TRY(c, c->lcc_nidx.ensure(2 * (size_t)V));
   uint32_t *snode = X.root, *sperm = X.part, *slab = X.parent, *nbeg = c->lcc_nidx.p, *nend = c->lcc_nidx.p + V;
   unsigned vbits = 1;
   while (vbits < 32 && (1ull << vbits) < (unsigned long long)V) ++vbits;
@@ -422,33 +297,24 @@ static vgs_status lg_build(vgs_ctx* c, const char* fn, const int32_t* labels_dev
   VGS_HIP_TRY(c, hipMemsetAsync(c->lcc_nidx.p, 0, 2 * (size_t)V * sizeof(uint32_t), c->stream));
   hipLaunchKernelGGL(k_lg_node_runs, dim3(lg_grid(nv)), dim3(LG_TB), 0, c->stream, snode, sperm, X.label, nv, slab, nbeg, nend);
   VGS_HIP_TRY(c, hipGetLastError());
-  // VGS: the distinct unused nodes with a vertex, and every vertex's row among them (the head flags are spent: lcc_flag takes these)
-  const bool vgs = c->P.method == 2;
-  uint32_t n_un = 0;
-  uint32_t *urow = nullptr, *un_node = nullptr;
-  int64_t chunk = 1;
-  if (vgs && V - U > 0) {
-    hipLaunchKernelGGL(k_lg_unused_flags, dim3(lg_grid(w)), dim3(LG_TB), 0, c->stream, snode, c->used_rank.p, nv, c->lcc_flag.p);
-    if ((s = lg_scan(c, c->lcc_flag.p, c->lcc_vscan.p, w)) != VGS_OK) return s;
-    VGS_READBACK(c, &n_un, c->lcc_vscan.p + nv, 4);
-    if (n_un > 0) {
-      VGS_HIP_TRY(c, c->lcc_uv.ensure((size_t)nv + n_un));
-      urow = c->lcc_uv.p; un_node = urow + nv;
-      hipLaunchKernelGGL(k_lg_unused_list, dim3(lg_grid(nv)), dim3(LG_TB), 0, c->stream, c->lcc_flag.p, c->lcc_vscan.p, snode, c->used_rank.p, nv, n_un,
-                         un_node, urow);
-      VGS_HIP_TRY(c, hipGetLastError());
-      chunk = std::max<int64_t>(1, std::min<int64_t>(n_un, ((int64_t)32 << 20) / std::max(1, c->adj_stride)));   // at most 256 MB of keys
-      VGS_HIP_TRY(c, c->rf_rows.ensure((size_t)chunk * c->adj_stride)); VGS_HIP_TRY(c, c->rf_cnt.ensure((size_t)chunk)); VGS_HIP_TRY(c, c->rf_nall.ensure((size_t)chunk));
-    }
-  }
+  G.nv = nv; G.K = (uint32_t)K; G.R = 0; G.snode = snode; G.slab = slab; G.nbeg = nbeg; G.nend = nend; G.W = lg_weight_params(c->P);
+  G.rkey = nullptr; G.tkey = nullptr; G.ridx = nullptr;
+  return VGS_OK;
+}
+
+// Steps 3 to 6 behind a walk of the caller's choice (the plain one, or labelgraph_tiles.hip's): count, scan, write; the sorts; heads,
+// starts, chunk partials, fold.  The table is in lg_ab ... lg_wmax, lg_E rows, when the stream has been waited for -- which it has.
+vgs_status vgs_lg_table_from_walk(vgs_ctx* c, const char* fn, LgWalk& G, LgWalkFn walk, void* arg) {
+  const uint32_t nv = G.nv;
+  const int64_t K = (int64_t)G.K;
+  const size_t w = (size_t)nv + 1;
+  vgs_status s;
+  c->lg_E = 0;
   // step 3: count, scan, write
   VGS_HIP_TRY(c, c->lg_nrec.ensure(w)); VGS_HIP_TRY(c, c->lg_roff.ensure(w)); VGS_HIP_TRY(c, c->lg_meta.ensure(4));
   VGS_HIP_TRY(c, hipMemsetAsync(c->lg_meta.p, 0, 4 * sizeof(uint32_t), c->stream));
   VGS_HIP_TRY(c, hipMemsetAsync(c->lg_nrec.p, 0, w * sizeof(uint32_t), c->stream));
-  LgWalk G;
-  G.nv = nv; G.K = (uint32_t)K; G.R = 0; G.snode = snode; G.slab = slab; G.nbeg = nbeg; G.nend = nend; G.W = lg_weight_params(c->P);
-  G.rkey = nullptr; G.tkey = nullptr; G.ridx = nullptr;
-  if ((s = lg_walk<false>(c, G, urow, un_node, n_un, chunk, false)) != VGS_OK) return s;
+  if ((s = walk(c, G, false, arg)) != VGS_OK) return s;
   size_t t_scan0 = 0;
   VGS_HIP_TRY(c, rocprim::exclusive_scan(nullptr, t_scan0, c->lg_nrec.p, c->lg_roff.p, (uint64_t)0, w, rocprim::plus<uint64_t>(), c->stream));
   VGS_HIP_TRY(c, c->lg_tmp.ensure(t_scan0));
@@ -457,7 +323,8 @@ static vgs_status lg_build(vgs_ctx* c, const char* fn, const int32_t* labels_dev
   uint32_t meta[4] = {0, 0, 0, 0};
   VGS_READBACK(c, &R64, c->lg_roff.p + nv, 8);   // read-back: the number of records ...
   VGS_READBACK(c, meta, c->lg_meta.p, sizeof(meta));   // ... and of the proxies among them
-  if (R64 == 0) { c->lg_valid = true; return VGS_OK; }
+  if (R64 == 0) return VGS_OK;
+  // (this refusal is what lets lg_walk_body keep a record's position in one 32-bit word, in k_lg_rows and k_lgt_rows alike)
   if (R64 >= (1ull << 31)) { c->err = std::string(fn) + ": more than 2^31 (vertex, neighbour label) records"; return VGS_E_UNSUPPORTED; }
   const uint32_t R = (uint32_t)R64;
   const bool proxies = meta[2] != 0;
@@ -468,7 +335,7 @@ static vgs_status lg_build(vgs_ctx* c, const char* fn, const int32_t* labels_dev
   uint32_t *idx_a = c->lg_ridx.p, *idx_b = idx_a + R;
   uint32_t *head = c->lg_ework.p, *inc = head + (R + 1), *estart = inc + (R + 1), *nch = estart + (R + 1);
   G.R = R; G.rkey = key_a; G.tkey = c->lg_tkey.p; G.ridx = idx_a;
-  if ((s = lg_walk<true>(c, G, urow, un_node, n_un, chunk, (int64_t)n_un <= chunk)) != VGS_OK) return s;
+  if ((s = walk(c, G, true, arg)) != VGS_OK) return s;
   // step 4: (with proxies) the stable sort by vertex, then the stable sort by edge
   unsigned bits = 1, tbits = 1;
   const unsigned long long kk = (unsigned long long)K * (unsigned long long)K;   // keys 0 .. K^2 - 1
@@ -509,14 +376,53 @@ static vgs_status lg_build(vgs_ctx* c, const char* fn, const int32_t* labels_dev
                      E, c->lg_ab.p, c->lg_nshared.p, c->lg_npairs.p, c->lg_nfin.p, c->lg_nodes.p, c->lg_wsum.p, c->lg_wmin.p, c->lg_wmax.p);
   VGS_HIP_TRY(c, hipGetLastError());
   VGS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // the table is complete, and a labelling read in place is the caller's again
-  c->lg_E = E; c->lg_valid = true;
+  c->lg_E = E;
+  return VGS_OK;
+}
+
+static vgs_status lg_build(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t K, int64_t* n_skipped) {
+  const int64_t V = c->V, U = c->U;
+  c->lg_valid = false; c->lg_E = 0; c->lgt_own = c->lgt_valid = false;
+  c->lcc_nv = 0; c->lct_own = c->lct_linked = c->lct_applied = false;   // (the vertex arrays of the last parts pass are overwritten)
+  PsSort S;
+  LcVtx X;
+  uint32_t nv = 0;
+  vgs_status s = vgs_label_vertices_on_device(c, fn, labels_dev, 0, c->N, K, n_skipped, S, &nv, X);
+  if (s != VGS_OK) return s;
+  if (nv == 0 || K <= 1) { VGS_HIP_TRY(c, hipStreamSynchronize(c->stream)); c->lg_valid = true; return VGS_OK; }
+  LgWalk G;
+  if ((s = vgs_lg_vertices_by_node(c, X, nv, K, G)) != VGS_OK) return s;
+  const size_t w = (size_t)nv + 1;
+  const uint32_t* snode = G.snode;
+  // VGS: the distinct unused nodes with a vertex, and every vertex's row among them (the head flags are spent: lcc_flag takes these)
+  const bool vgs = c->P.method == 2;
+  uint32_t n_un = 0;
+  uint32_t *urow = nullptr, *un_node = nullptr;
+  int64_t chunk = 1;
+  if (vgs && V - U > 0) {
+    hipLaunchKernelGGL(k_lg_unused_flags, dim3(lg_grid(w)), dim3(LG_TB), 0, c->stream, snode, c->used_rank.p, nv, c->lcc_flag.p);
+    if ((s = lg_scan(c, c->lcc_flag.p, c->lcc_vscan.p, w)) != VGS_OK) return s;
+    VGS_READBACK(c, &n_un, c->lcc_vscan.p + nv, 4);
+    if (n_un > 0) {
+      VGS_HIP_TRY(c, c->lcc_uv.ensure((size_t)nv + n_un));
+      urow = c->lcc_uv.p; un_node = urow + nv;
+      hipLaunchKernelGGL(k_lg_unused_list, dim3(lg_grid(nv)), dim3(LG_TB), 0, c->stream, c->lcc_flag.p, c->lcc_vscan.p, snode, c->used_rank.p, nv, n_un,
+                         un_node, urow);
+      VGS_HIP_TRY(c, hipGetLastError());
+      chunk = std::max<int64_t>(1, std::min<int64_t>(n_un, ((int64_t)32 << 20) / std::max(1, c->adj_stride)));   // at most 256 MB of keys
+      VGS_HIP_TRY(c, c->rf_rows.ensure((size_t)chunk * c->adj_stride)); VGS_HIP_TRY(c, c->rf_cnt.ensure((size_t)chunk)); VGS_HIP_TRY(c, c->rf_nall.ensure((size_t)chunk));
+    }
+  }
+  LgPlainRows P{urow, un_node, n_un, chunk};
+  if ((s = vgs_lg_table_from_walk(c, fn, G, lg_walk_plain, &P)) != VGS_OK) return s;
+  c->lg_valid = true;
   return VGS_OK;
 }
 
 static vgs_status lg_check(vgs_ctx* c, const char* fn, const int32_t* labels, int64_t n, int64_t K) {
   if (c->stage < ST_SEGMENTED) { c->err = std::string(fn) + ": segment first"; return VGS_E_STATE; }
   if (vgs_is_tile(c)) {
-    c->err = std::string(fn) + ": a tile context (owned region / own point range) holds only part of the cloud and of its neighbourhood graph; the adjacency graph of a labelling across the ranks of the tiled driver is not computed";
+    c->err = std::string(fn) + ": a tile context (owned region / own point range) holds only part of the cloud and of its neighbourhood graph; the adjacency graph of a labelling across the ranks of the tiled driver is not computed by this call: vgs_tiles_point_label_graph";
     return VGS_E_STATE;
   }
   if (n != c->N) {
@@ -553,7 +459,7 @@ extern "C" vgs_status vgs_point_label_graph_device(vgs_ctx* c, const int32_t* la
 static vgs_status lg_result(vgs_ctx* c, const char* fn) {
   if (!c) return VGS_E_ARG;
   if (vgs_is_tile(c)) {
-    c->err = std::string(fn) + ": a tile context holds only part of the cloud; the adjacency graph of a labelling across the ranks of the tiled driver is not computed";
+    c->err = std::string(fn) + ": a tile context holds only part of the cloud; the adjacency graph of a labelling across the ranks of the tiled driver is not computed by this call: vgs_tiles_point_label_graph";
     return VGS_E_STATE;
   }
   if (c->stage < ST_SEGMENTED || !c->lg_valid) {

@@ -342,6 +342,33 @@ bool fold_edges(const std::vector<std::vector<EdgeRec>>& ranks, int64_t K, std::
   return true;
 }
 
+// One edge of one rank's partial table of a point labelling's graph (vgs_get_own_point_label_graph): EdgeRec and the shared nodes; the
+// payload of that graph's second exchange.  Its first entry is the header, as EdgeRec's.
+struct LabelEdgeRec {
+  EdgeRec e;
+  int64_t n_shared = 0;
+};
+static_assert(sizeof(LabelEdgeRec) == 56, "LabelEdgeRec is the exchange's wire format");
+
+// fold_edges over the ranks' partial tables of a point labelling; n_shared adds like the other counts
+bool fold_label_edges(const std::vector<std::vector<LabelEdgeRec>>& ranks, int64_t K, std::vector<LabelEdgeRec>& out) {
+  std::vector<std::vector<EdgeRec>> plain(ranks.size());
+  for (size_t r = 0; r < ranks.size(); ++r) { plain[r].reserve(ranks[r].size()); for (const LabelEdgeRec& q : ranks[r]) plain[r].push_back(q.e); }
+  std::vector<EdgeRec> folded;
+  if (!fold_edges(plain, K, folded)) return false;
+  out.assign(folded.size(), LabelEdgeRec());
+  for (size_t i = 0; i < folded.size(); ++i) out[i].e = folded[i];
+  for (const std::vector<LabelEdgeRec>& R : ranks) {   // both ascending in (a, b): one pass per rank
+    size_t j = 0;
+    for (const LabelEdgeRec& q : R) {
+      while (j < out.size() && (out[j].e.a != q.e.a || out[j].e.b != q.e.b)) ++j;
+      if (j == out.size()) return false;
+      out[j].n_shared += q.n_shared;
+    }
+  }
+  return true;
+}
+
 // ------------------------------------------------------------------------------------------------ pair records of a point labelling
 // One head flag of one rank in a voxel that holds points of several ranks (vgs_own_point_label_moments): the voxel's code and the label.
 struct PairRec {
@@ -536,6 +563,7 @@ bool header_ok(const MomentRec& h) { return h.label == 0; }
 bool header_ok(const EdgeRec& h) { return h.a == 0; }
 bool header_ok(const ExtentRec& h) { return h.label == 0; }
 bool header_ok(const BandRec& h) { return h.code == 0; }
+bool header_ok(const LabelEdgeRec& h) { return h.e.a == 0; }
 bool header_ok(uint64_t word0) { return word0 == 0; }
 bool header_ok(int64_t word0) { return word0 == 0; }
 template <typename T> void strip_headers(std::vector<std::vector<T>>& gathered) { for (std::vector<T>& g : gathered) g.erase(g.begin()); }
@@ -555,9 +583,9 @@ template <typename F> int first_bad_rank(int world, F bad) {
 // node labelling (fields: statistics and histogram alike); point_labels: every table of a caller's point labelling -- the moment exchange
 // of vgs_tiles_point_label_descriptors / _boxes, the cell exchange of vgs_tiles_compare_point_labels, the record exchange of
 // vgs_tiles_point_label_field_stats / _class_histogram; refine: vgs_tiles_refine_point_labels; components: the first exchange of
-// vgs_tiles_point_label_components.
-enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_REFINE, PH_POINT_LABELS, PH_COMPONENTS, PH_COUNT };
-const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare", "refine", "point_labels", "components"};
+// vgs_tiles_point_label_components; label_graph: the first exchange of vgs_tiles_point_label_graph.
+enum Phase { PH_NONE, PH_GRID, PH_STAGES, PH_POINTS, PH_UPLOAD, PH_DESCRIPTORS, PH_GRAPH, PH_BOXES, PH_FIELDS, PH_COMPARE, PH_REFINE, PH_POINT_LABELS, PH_COMPONENTS, PH_LABEL_GRAPH, PH_COUNT };
+const char* const PHASE_NAME[PH_COUNT] = {"", "grid", "stages", "points", "upload", "descriptors", "graph", "boxes", "fields", "compare", "refine", "point_labels", "components", "label_graph"};
 
 // Phase clock of one call: lap(slot) gives the slot the host wall time since the last lap (the start, for the first), total(slot) the
 // time from the start to the last lap.  Milliseconds.  vgs_tiles_run stamps t->times as it goes; a post-run collective stamps an array of
@@ -671,6 +699,12 @@ struct vgs_tiles {
   std::vector<uint64_t> cc_code;
   double cctimes[VGS_TILES_CC_COUNT] = {0};
   int64_t cc_band = 0, cc_parts = 0, cc_links = 0, cc_bytes = 0;
+  // the adjacency graph of the last labelling (vgs_tiles_point_label_graph): the global table.  Valid until the next call, the next run
+  // or set_points.  Phases, band records, foreign records found, own edges, bytes sent
+  bool lg_valid = false;
+  std::vector<LabelEdgeRec> lgraph;
+  double lgtimes[VGS_TILES_LG_COUNT] = {0};
+  int64_t lg_band = 0, lg_hits = 0, lg_own = 0, lg_bytes = 0;
   std::string err;
 };
 
@@ -746,7 +780,7 @@ static vgs_status behind_collective(vgs_tiles* t, vgs_status s, const char* what
 }
 
 // what a new cloud or a new run makes stale: the run itself and every table cached from it
-static void invalidate(vgs_tiles* t) { t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false; t->band_valid = false; t->rf_valid = false; t->cc_valid = false; }
+static void invalidate(vgs_tiles* t) { t->ran = false; t->desc_valid = false; t->graph_valid = false; t->box_valid[0] = t->box_valid[1] = false; t->cmp_valid = false; t->band_valid = false; t->rf_valid = false; t->cc_valid = false; t->lg_valid = false; }
 
 template <int N> static vgs_status get_times(vgs_tiles* t, double (vgs_tiles::*slots)[N], double* ms, int32_t n) {
   if (!t || !ms || n < 0 || n > N) return VGS_E_ARG;
@@ -2052,6 +2086,149 @@ vgs_status vgs_tiles_get_point_label_component_payload(vgs_tiles* t, int64_t* ba
   if (parts) *parts = t->cc_parts;
   if (links) *links = t->cc_links;
   if (bytes_sent) *bytes_sent = t->cc_bytes;
+  return VGS_OK;
+}
+
+// The adjacency graph of a caller's point labelling over the ranks (include/vgs_tiles.h states the counting rule).  TWO all_gather_varlen
+// per call, nothing cached:
+//   own vertices and band records on this rank's GPU (vgs_own_point_label_band) -> exchange 1: BandRec, a header of two entries ([0]
+//   code = status word, label = K; [1] code = band count, label | pad = own n_skipped), then (code, label) -> the merged vertices, the
+//   tile walk and the pipeline on this rank's GPU over the other ranks' records (vgs_own_point_label_graph) -> exchange 2: LabelEdgeRec,
+//   a header entry (a = status word -- a failure of the GPU step travels here --, n_pairs = record count), then the partial table ->
+//   fold_label_edges, the same on every rank.
+static vgs_status tiles_label_graph(vgs_tiles* t, const char* fn, bool on_device, const int32_t* labels, int64_t n, int64_t K, int64_t* n_edges,
+                                    int64_t* n_skipped) {
+  if (!t) return VGS_E_ARG;
+  if (n_edges) *n_edges = 0;
+  if (n_skipped) *n_skipped = 0;
+  vgs_status carry;
+  TRY(open_collective(t, fn, PH_LABEL_GRAPH, carry));
+  Comm& c = *t->comm;
+  const size_t world = (size_t)c.world;
+  t->lg_valid = false;
+  t->cc_valid = false;   // (the own pass overwrites the vertex arrays of the parts pass: its part ids in the context go with them)
+  double ms[VGS_TILES_LG_COUNT] = {0};
+  Stopwatch sw(ms);
+  // step 1: own vertices and band records
+  int64_t n_band = 0, n_skip = 0;
+  TCARRY_AS(on_device ? vgs_own_point_label_band_device : vgs_own_point_label_band, on_device ? "vgs_own_point_label_band_device" : "vgs_own_point_label_band",
+            t->ctx, labels, n, K, &n_band, &n_skip);
+  if (carry != VGS_OK) { n_band = 0; n_skip = 0; }
+  std::vector<uint64_t> b_code((size_t)n_band + 1);
+  std::vector<int32_t> b_label((size_t)n_band + 1);
+  TCARRY(vgs_get_own_point_label_band(t->ctx, b_code.data(), b_label.data()));
+  if (carry != VGS_OK) { n_band = 0; n_skip = 0; }
+  std::vector<BandRec> pay1(2 + (size_t)n_band);
+  pay1[0].code = (uint64_t)(uint32_t)carry; pay1[0].label = (int32_t)K;   // (K outside int32 has failed above: nobody compares it)
+  pay1[1].code = (uint64_t)n_band; pay1[1].label = (int32_t)(uint32_t)((uint64_t)n_skip & 0xffffffffull); pay1[1].pad = (int32_t)(uint32_t)((uint64_t)n_skip >> 32);
+  for (size_t i = 0; i < (size_t)n_band; ++i) { pay1[2 + i].code = b_code[i]; pay1[2 + i].label = b_label[i]; }
+  sw.lap(VGS_TILES_LG_OWN);
+  std::vector<std::vector<BandRec>> g1;
+  TRY(exchange(t, carry, pay1, "label_graph", sw, VGS_TILES_LG_EXCHANGE1, g1));
+  for (size_t r = 0; r < world; ++r) if (g1[r].size() != 2 + (size_t)g1[r][1].code) return wrong_size(t, fn, r);
+  for (size_t r = 1; r < world; ++r) if (g1[r][0].label != g1[0][0].label) return disagree(t, fn, r, "K", g1[r][0].label, g1[0][0].label);
+  int64_t skipped = 0;
+  for (size_t r = 0; r < world; ++r) skipped += (int64_t)(((uint64_t)(uint32_t)g1[r][1].pad << 32) | (uint64_t)(uint32_t)g1[r][1].label);
+  // steps 3 and 4: the other ranks' records, the merged vertices, the walk, the partial table
+  std::vector<uint64_t> f_code;
+  std::vector<int32_t> f_label;
+  for (size_t r = 0; r < world; ++r) {
+    if ((int)r == c.rank) continue;
+    for (size_t i = 2; i < g1[r].size(); ++i) { f_code.push_back(g1[r][i].code); f_label.push_back(g1[r][i].label); }
+  }
+  int64_t E = 0, hits = 0;
+  TCARRY(vgs_own_point_label_graph(t->ctx, f_code.data(), f_label.data(), (int64_t)f_code.size(), &E));
+  if (carry != VGS_OK) E = 0;
+  const size_t e1 = (size_t)E;
+  std::vector<int32_t> ab(2 * e1 + 2), nd(2 * e1 + 2);
+  std::vector<int64_t> ns(e1 + 1), np(e1 + 1), nf(e1 + 1);
+  std::vector<double> ws(e1 + 1);
+  std::vector<float> mn(e1 + 1), mx(e1 + 1);
+  TCARRY(vgs_get_own_point_label_graph(t->ctx, ab.data(), ns.data(), np.data(), nf.data(), nd.data(), ws.data(), mn.data(), mx.data()));
+  TCARRY(vgs_get_own_point_label_graph_counts(t->ctx, nullptr, &hits, nullptr));
+  std::vector<LabelEdgeRec> pay2(1);
+  if (carry == VGS_OK) {
+    pay2.reserve(1 + e1);
+    for (size_t i = 0; i < e1; ++i) {
+      LabelEdgeRec q;
+      q.e = pack_edge(ab.data(), np.data(), nf.data(), nd.data(), ws.data(), mn.data(), mx.data(), i);
+      q.n_shared = ns[i];
+      pay2.push_back(q);
+    }
+  }
+  set_header(pay2[0].e, carry, pay2.size() - 1);
+  sw.lap(VGS_TILES_LG_TABLE);
+  std::vector<std::vector<LabelEdgeRec>> g2;
+  TRY(exchange(t, carry, pay2, "label_graph", sw, VGS_TILES_LG_EXCHANGE2, g2));
+  for (size_t r = 0; r < world; ++r) if (g2[r][0].e.n_pairs < 0 || g2[r].size() != 1 + (size_t)g2[r][0].e.n_pairs) return wrong_size(t, fn, r);
+  strip_headers(g2);
+  // step 6: the fold
+  if (!fold_label_edges(g2, std::max<int64_t>(K, 0), t->lgraph)) return tfail(t, VGS_E_ARG, std::string(fn) + ": a rank sent a table that is not sorted or names a label outside 0 .. K-1");
+  sw.lap(VGS_TILES_LG_FOLD);
+  sw.total(VGS_TILES_LG_TOTAL, t->lgtimes);
+  t->lg_valid = true;
+  t->lg_band = n_band; t->lg_hits = hits; t->lg_own = (int64_t)pay2.size() - 1;
+  t->lg_bytes = (int64_t)(pay1.size() * sizeof(BandRec) + pay2.size() * sizeof(LabelEdgeRec));
+  if (n_edges) *n_edges = (int64_t)t->lgraph.size();
+  if (n_skipped) *n_skipped = skipped;
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_point_label_graph(vgs_tiles* t, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_edges, int64_t* n_skipped) {
+  return tiles_label_graph(t, "vgs_tiles_point_label_graph", false, labels_host, n, K, n_edges, n_skipped);
+}
+vgs_status vgs_tiles_point_label_graph_device(vgs_tiles* t, const int32_t* labels_dev, int64_t n, int64_t K, int64_t* n_edges, int64_t* n_skipped) {
+  return tiles_label_graph(t, "vgs_tiles_point_label_graph_device", true, labels_dev, n, K, n_edges, n_skipped);
+}
+
+vgs_status vgs_tiles_get_point_label_graph(vgs_tiles* t, int32_t* seg_ab, int64_t* n_shared, int64_t* n_pairs, int64_t* n_finite, int32_t* nodes_ab,
+                                           double* w_sum, float* w_min, float* w_max) {
+  if (!t) return VGS_E_ARG;
+  if (!t->ran || !t->lg_valid)
+    return tfail(t, VGS_E_STATE, "vgs_tiles_get_point_label_graph: no label graph since the last run or the last vgs_tiles_set_points (vgs_tiles_point_label_graph first)");
+  for (size_t i = 0; i < t->lgraph.size(); ++i) {
+    unpack_edge(t->lgraph[i].e, i, seg_ab, n_pairs, n_finite, nodes_ab, w_sum, w_min, w_max);
+    if (n_shared) n_shared[i] = t->lgraph[i].n_shared;
+  }
+  return VGS_OK;
+}
+
+vgs_status vgs_tiles_get_label_graph_times(vgs_tiles* t, double* ms, int32_t n) { return get_times(t, &vgs_tiles::lgtimes, ms, n); }
+
+vgs_status vgs_tiles_get_label_graph_payload(vgs_tiles* t, int64_t* band_records, int64_t* foreign_hits, int64_t* own_edges, int64_t* bytes_sent) {
+  if (!t) return VGS_E_ARG;
+  if (band_records) *band_records = t->lg_band;
+  if (foreign_hits) *foreign_hits = t->lg_hits;
+  if (own_edges) *own_edges = t->lg_own;
+  if (bytes_sent) *bytes_sent = t->lg_bytes;
+  return VGS_OK;
+}
+
+// host arithmetic only (tests): the label-graph fold on flattened per-rank partial tables
+vgs_status vgs_tiles_fold_label_edges(int world, int64_t K, const int64_t* rec_off, const int32_t* seg_ab, const int64_t* n_shared, const int64_t* n_pairs,
+                                      const int64_t* n_finite, const int32_t* nodes_ab, const double* w_sum, const float* w_min, const float* w_max,
+                                      int64_t* n_edges, int32_t* seg_ab_out, int64_t* n_shared_out, int64_t* n_pairs_out, int64_t* n_finite_out,
+                                      int32_t* nodes_ab_out, double* w_sum_out, float* w_min_out, float* w_max_out) {
+  if (world < 1 || !rec_off || K < 0 || K > (int64_t)0x7fffffffLL || !n_edges) return VGS_E_ARG;
+  *n_edges = 0;
+  if (rec_off[0] != 0) return VGS_E_ARG;
+  for (int r = 0; r < world; ++r) if (rec_off[r + 1] < rec_off[r]) return VGS_E_ARG;
+  if (rec_off[world] > 0 && (!seg_ab || !n_shared || !n_pairs || !n_finite || !nodes_ab || !w_sum || !w_min || !w_max)) return VGS_E_ARG;
+  std::vector<std::vector<LabelEdgeRec>> ranks((size_t)world);
+  for (int r = 0; r < world; ++r)
+    for (int64_t i = rec_off[r]; i < rec_off[r + 1]; ++i) {
+      LabelEdgeRec q;
+      q.e = pack_edge(seg_ab, n_pairs, n_finite, nodes_ab, w_sum, w_min, w_max, (size_t)i);
+      q.n_shared = n_shared[i];
+      ranks[(size_t)r].push_back(q);
+    }
+  std::vector<LabelEdgeRec> out;
+  if (!fold_label_edges(ranks, K, out)) return VGS_E_ARG;
+  *n_edges = (int64_t)out.size();
+  for (size_t i = 0; i < out.size(); ++i) {
+    unpack_edge(out[i].e, i, seg_ab_out, n_pairs_out, n_finite_out, nodes_ab_out, w_sum_out, w_min_out, w_max_out);
+    if (n_shared_out) n_shared_out[i] = out[i].n_shared;
+  }
   return VGS_OK;
 }
 

@@ -444,6 +444,16 @@ struct vgs_ctx {
   DevBuf<float> lg_wmin, lg_wmax;
   int64_t lg_E = 0;
   bool lg_valid = false;
+  // a tile context's share of the label graph across the ranks of the tiled driver (labelgraph_tiles.hip; include/vgs.h,
+  // vgs_own_point_label_band): the own vertices of the last own pass stay in lcc_vtx (lgt_nv of them) and its band records in lct_bcode /
+  // lct_blabel (lgt_band rows) until vgs_own_point_label_graph merges them with the other ranks' records -- the merged vertex arrays node |
+  // label | iota, labels | nodes sorted | vertices sorted (merged + 1 words each), the unused flags and their scan (merged + 1 words
+  // each); the keys of the merge use lct_key / lct_key2 / lct_val, the partial table is in lg_ab ... lg_wmax (lg_E rows).  lgt_own: an
+  // own pass waits for its records; lgt_valid: the partial table is there.  Both are dropped by the next run of the stages.
+  DevBuf<uint32_t> lgt_vtx, lgt_flag, lgt_scan;
+  uint32_t lgt_nv = 0;
+  int64_t lgt_K = 0, lgt_band = 0, lgt_hits = 0;
+  bool lgt_own = false, lgt_valid = false;
   // the parts of a labelling across the ranks of the tiled driver (labelcc_tiles.hip; include/vgs.h, vgs_own_point_label_parts): the band
   // records of the last own pass (lct_band rows: code, label, local part, vertex), the code of every local part's first node, the other
   // ranks' records as looked up and sorted (key = label << 32 | local node, value = index of the record), the link triples, the map from
@@ -717,6 +727,25 @@ vgs_status vgs_label_parts_on_device(vgs_ctx* c, const char* fn, const int32_t* 
 struct LcVtx { uint32_t *node, *label, *q, *parent, *root, *part; };
 vgs_status vgs_label_vertices_on_device(vgs_ctx* c, const char* fn, const int32_t* labels_dev, int64_t own_first, int64_t n_lab, int64_t K,
                                         int64_t* n_skipped, PsSort& S, uint32_t* n_vertices, LcVtx& X);
+// labelgraph.hip behind the vertex list, for labelgraph_tiles.hip: what the row kernels need besides the rows, and where the records go;
+// step 2 (the vertices X by node: fills G); steps 3 to 6 behind a walk of the caller's -- walk(write = false) counts the records of
+// every vertex into lg_nrec, walk(write = true) writes them -- into lg_ab ... lg_wmax, lg_E rows, the stream waited for
+struct LgWalk {
+  uint32_t nv, K, R;
+  const uint32_t *snode, *slab, *nbeg, *nend;
+  VgsWeightParams W;
+  uint64_t* rkey;
+  uint32_t *tkey, *ridx;
+};
+typedef vgs_status (*LgWalkFn)(vgs_ctx* c, const LgWalk& G, bool write, void* arg);
+vgs_status vgs_lg_vertices_by_node(vgs_ctx* c, const LcVtx& X, uint32_t nv, int64_t K, LgWalk& G);
+vgs_status vgs_lg_table_from_walk(vgs_ctx* c, const char* fn, LgWalk& G, LgWalkFn walk, void* arg);
+// labelcc_tiles.hip's band and lookup steps, for labelgraph_tiles.hip: the band records of nv vertices (code, label, vpart[vertex],
+// vertex) into lct_bcode / lct_blabel / lct_bpart / lct_bvtx (vpart == nullptr: the first two only), the stream waited for; n records (code, label) in HBM looked up in the
+// local grid, key[k] = label << 32 | node or all ones, val[k] = k, counts[0] += hits, left on the stream
+vgs_status vgs_lt_band_on_device(vgs_ctx* c, const uint32_t* vnode, const uint32_t* vlabel, const uint32_t* vpart, uint32_t nv, uint32_t* n_band);
+vgs_status vgs_lt_find_on_device(vgs_ctx* c, const uint64_t* code_dev, const int32_t* label_dev, int64_t n, uint64_t* key, uint32_t* val,
+                                 unsigned long long* counts);
 vgs_status vgs_seggraph_on_device(vgs_ctx* c);   // seggraph.hip
 // tile contexts: halo[v] = label[k] for the voxel v of code[k] that this context holds and does not own, queued on the context's stream
 // (code, label: n entries in HBM; halo: V entries).  One kernel for the graph's table and the refinement's (seggraph.hip)

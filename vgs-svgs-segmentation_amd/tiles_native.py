@@ -31,6 +31,7 @@ F_NAMES = ("own", "exchange", "fold", "finish", "total")        # vgs_tiles_get_
 C_NAMES = ("own", "exchange", "tables", "total")                # vgs_tiles_get_compare_times
 R_NAMES = ("band", "exchange", "table", "refine", "total")      # vgs_tiles_get_refine_times
 L_NAMES = ("own", "exchange", "fold", "finish", "total")        # vgs_tiles_get_point_label_times
+LG_NAMES = ("own", "exchange1", "table", "exchange2", "fold", "total")   # vgs_tiles_get_label_graph_times
 CC_NAMES = ("own", "exchange1", "link", "exchange2", "fold", "apply", "total")   # vgs_tiles_get_point_label_component_times
 # (field, dtype, table) of vgs_tiles_get_point_label_components, in its argument order: Engine.COMPONENT_FIELDS with the shared-grid code
 # of a part's first node in place of the node id
@@ -170,6 +171,17 @@ def lib():
         L.vgs_tiles_get_point_label_component_times.argtypes = [P, P, C.c_int32]
         L.vgs_tiles_get_point_label_component_payload.restype = C.c_int
         L.vgs_tiles_get_point_label_component_payload.argtypes = [P, P, P, P, P]
+        for name in ("vgs_tiles_point_label_graph", "vgs_tiles_point_label_graph_device"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [P, P, C.c_int64, C.c_int64, P, P]
+        L.vgs_tiles_get_point_label_graph.restype = C.c_int
+        L.vgs_tiles_get_point_label_graph.argtypes = [P] * 9
+        L.vgs_tiles_fold_label_edges.restype = C.c_int
+        L.vgs_tiles_fold_label_edges.argtypes = [C.c_int, C.c_int64] + [P] * 18
+        L.vgs_tiles_get_label_graph_times.restype = C.c_int
+        L.vgs_tiles_get_label_graph_times.argtypes = [P, P, C.c_int32]
+        L.vgs_tiles_get_label_graph_payload.restype = C.c_int
+        L.vgs_tiles_get_label_graph_payload.argtypes = [P, P, P, P, P]
         L.vgs_tiles_fold_field_moments.restype = C.c_int
         L.vgs_tiles_fold_field_moments.argtypes = [C.c_int, P, P, C.c_int32, P, P, P, P, P, P, C.c_int64, P, P, P, P, P, P]
         L.vgs_tiles_fold_class_counts.restype = C.c_int
@@ -292,6 +304,31 @@ def fold_label_parts(records, K):
     res = {name: out[name][:c] for name in ("part_label", "part_points", "part_nodes", "part_first_code")}
     res["label_first"], res["label_largest"], res["n_parts"] = out["label_first"], out["label_largest"][:k], c
     res["map"] = [out["map"][int(p_off[r]):int(p_off[r + 1])] for r in range(world)]
+    return res
+
+
+def _label_graph_fields():
+    from .api import Engine
+    return Engine.LABEL_GRAPH_FIELDS
+
+
+def fold_label_edges(records, K):
+    """vgs_tiles_fold_label_edges (host arithmetic, no GPU): step 6 of vgs_tiles_point_label_graph.  records[r] = rank r's partial table
+    as a dict of the fields of Engine.label_graph() -- what NativeTiles.own_point_label_graph() gives.  Returns the folded table in the
+    same form, with n_edges."""
+    fields = _label_graph_fields()
+    world, K = len(records), int(K)
+    off = np.zeros(world + 1, dtype=np.int64)
+    off[1:] = np.cumsum([np.asarray(r["seg_ab"]).reshape(-1, 2).shape[0] for r in records])
+    ins = [np.ascontiguousarray(np.concatenate([np.asarray(r[name], dtype=dt).reshape(-1) for r in records] + [np.zeros(0, dtype=dt)])) for name, dt, _ in fields]
+    R = max(int(off[-1]), 1)
+    out = {name: np.zeros((R, w) if w > 1 else R, dtype=dt) for name, dt, w in fields}
+    E = C.c_int64(0)
+    st = lib().vgs_tiles_fold_label_edges(world, K, _vp(off), *(_vp(a) for a in ins), C.byref(E), *(_vp(out[name]) for name, _, _ in fields))
+    if st != 0:
+        raise VgsError(st, "vgs_tiles_fold_label_edges")
+    res = {name: out[name][:E.value] for name, _, _ in fields}
+    res["n_edges"] = int(E.value)
     return res
 
 
@@ -767,6 +804,77 @@ class NativeTiles:
         if st != 0:
             raise VgsError(st, L.vgs_last_error_string(h).decode())
         return {name: a[:nl.value] for name, a in out.items()}
+
+    def label_graph(self, labels, K):
+        """COLLECTIVE on every call, two collectives (every rank makes it after run(), with the same K; nothing is cached): the adjacency
+        graph of ANY per-point labelling over all ranks -- the dict of Engine.label_graph() on the gathered points, the same bytes on every
+        rank, w_sum summed over the ranks' partial sums in rank order (include/vgs_tiles.h, vgs_tiles_point_label_graph).  `labels`, K as
+        label_components().  The table stays in the driver until the next call, the next run or the next set_points()."""
+        from .api import Engine
+        labels, ptr, n, dev = Engine._classes_input(labels, self.params.device)
+        fn = self._L.vgs_tiles_point_label_graph_device if dev else self._L.vgs_tiles_point_label_graph
+        E, skipped = C.c_int64(0), C.c_int64(0)
+        self._ck(fn(self._h, ptr, n, int(K), C.byref(E), C.byref(skipped)))
+        out = self.label_graph_result(E.value)
+        out["n_skipped"] = int(skipped.value)
+        return out
+
+    def label_graph_result(self, n_edges):
+        """the table of the last label_graph() (vgs_tiles_get_point_label_graph; local, no collective)"""
+        E = int(n_edges)
+        fields = _label_graph_fields()
+        buf = {name: np.zeros((max(E, 1), w) if w > 1 else max(E, 1), dtype=dt) for name, dt, w in fields}
+        self._ck(self._L.vgs_tiles_get_point_label_graph(self._h, *(_vp(buf[name]) for name, _, _ in fields)))
+        out = {name: buf[name][:E] for name, _, _ in fields}
+        out["n_edges"] = E
+        return out
+
+    def label_graph_times(self):
+        """the last label_graph()'s phases on this rank, milliseconds (LG_NAMES)"""
+        return self._times(self._L.vgs_tiles_get_label_graph_times, LG_NAMES)
+
+    def label_graph_payload(self):
+        """the last label_graph()'s payload on this rank: band records of its own, other ranks' records found in its grid, edges of its
+        partial table, bytes sent"""
+        return self._payload(self._L.vgs_tiles_get_label_graph_payload, ("band_records", "foreign_hits", "own_edges", "bytes_sent"))
+
+    def own_point_label_band(self, labels, K):
+        """this rank's band records of a labelling of its own points (vgs_own_point_label_band on its context; local, no collective): a
+        dict of band_code (uint64), band_label (int32) and n_skipped"""
+        from .api import Engine
+        L = _lib.lib()
+        h = self._ctx()
+        labels, ptr, n, dev = Engine._classes_input(labels, self.params.device)
+        fn = L.vgs_own_point_label_band_device if dev else L.vgs_own_point_label_band
+        nband, nskip = C.c_int64(0), C.c_int64(0)
+        st = fn(h, ptr, n, int(K), C.byref(nband), C.byref(nskip))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        code, lab = np.zeros(max(nband.value, 1), dtype=np.uint64), np.zeros(max(nband.value, 1), dtype=np.int32)
+        st = L.vgs_get_own_point_label_band(h, _vp(code), _vp(lab))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        return dict(band_code=code[:nband.value], band_label=lab[:nband.value], n_skipped=int(nskip.value))
+
+    def own_point_label_graph(self, code, label):
+        """this rank's partial table over other ranks' band records (vgs_own_point_label_graph behind own_point_label_band(); local, no
+        collective): the dict of Engine.label_graph() without n_skipped"""
+        L = _lib.lib()
+        h = self._ctx()
+        code = np.ascontiguousarray(code, dtype=np.uint64)
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        E = C.c_int64(0)
+        st = L.vgs_own_point_label_graph(h, _vp(code), _vp(label), int(code.shape[0]), C.byref(E))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        fields = _label_graph_fields()
+        buf = {name: np.zeros((max(E.value, 1), w) if w > 1 else max(E.value, 1), dtype=dt) for name, dt, w in fields}
+        st = L.vgs_get_own_point_label_graph(h, *(_vp(buf[name]) for name, _, _ in fields))
+        if st != 0:
+            raise VgsError(st, L.vgs_last_error_string(h).decode())
+        out = {name: buf[name][:E.value] for name, _, _ in fields}
+        out["n_edges"] = int(E.value)
+        return out
 
     def _label_table_inputs(self, labels, other, what):
         """labels of label_field_stats / label_class_histogram and the own-record calls: labels and the attribute array both numpy or both
