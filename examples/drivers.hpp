@@ -19,10 +19,20 @@ struct DriverGraph {
   std::multimap<uint32_t, uint32_t> adjacency;
 };
 
+// absorbLabelParts over a labelling the drivers hold (the refined labels, or the class field of DriverFields) when `on`
+struct DriverAbsorb {
+  bool on = false;
+  int64_t min_points = 0, island_points = 0;
+  int32_t max_rounds = 8;
+  bool drop = false;
+  pcl::AbsorbedLabels out;
+};
+
 // per-point attributes handed to the drivers and what comes back: getClusterFieldStats over `field` (n x channels floats, row-major) when
 // channels > 0, getClusterClassHistogram over `classes` (n int32) when n_classes > 0, compareClusterLabels over `truth` when have_truth;
 // want_stats / want_hist off: the input is loaded for the refined labels' table only (DriverRefine::fields); getLabelComponents over
-// `part_classes` (n int32, negative = no class) with parts_K labels when parts_K >= 0, getLabelGraph over the same when want_parts_graph
+// `part_classes` (n int32, negative = no class) with parts_K labels when parts_K >= 0, getLabelGraph over the same when want_parts_graph,
+// absorbLabelParts over the same when absorb.on
 struct DriverFields {
   std::vector<float> field;
   int channels = 0;
@@ -40,6 +50,7 @@ struct DriverFields {
   pcl::LabelComponents parts;
   bool want_parts = true, want_parts_graph = false;
   pcl::LabelGraph parts_graph;
+  DriverAbsorb absorb;
 };
 // point-level refinement of the cluster labels (refineClusterLabels): when `on`, the drivers put the refined clusters into
 // clusters_points_idx -- clusters in label order, points in ascending index -- and the refined labels into `labels`
@@ -51,10 +62,12 @@ struct DriverRefine {
   std::vector<int32_t> labels;
   // the tables of the REFINED labels, beside the ones that describe the voxel labels: getLabelDescriptors / getLabelBoxes(box_frame) /
   // compareClusterLabels(truth, labels) when wanted (truth: n int32, not null); getLabelFieldStats / getLabelClassHistogram over the
-  // field / classes of `fields` when wanted; getLabelComponents and getLabelGraph when wanted
+  // field / classes of `fields` when wanted; getLabelComponents and getLabelGraph when wanted; absorbLabelParts when absorb.on (last:
+  // every table above describes the refined labels themselves)
   bool want_descriptors = false, want_boxes = false, want_stats = false, want_hist = false, want_components = false, want_graph = false;
   pcl::LabelComponents components;
   pcl::LabelGraph graph;
+  DriverAbsorb absorb;
   const DriverFields* fields = nullptr;
   std::vector<pcl::ClusterFieldStats> stats;
   std::vector<pcl::ClusterClassHistogram> hist;
@@ -78,6 +91,8 @@ inline void driverRefine(S& structure, DriverRefine& r, std::vector<std::vector<
     r.hist = structure.getLabelClassHistogram(r.labels.data(), r.fields->classes.data(), (int64_t)r.fields->classes.size(), r.fields->n_classes);
   if (r.want_components) r.components = structure.getLabelComponents(r.labels.data(), n);
   if (r.want_graph) r.graph = structure.getLabelGraph(r.labels.data(), n);
+  if (r.absorb.on)
+    r.absorb.out = structure.absorbLabelParts(r.labels.data(), n, r.absorb.min_points, r.absorb.island_points, r.absorb.max_rounds, r.absorb.drop);
   for (auto& c : clusters_points_idx) c.clear();
   for (size_t i = 0; i < r.labels.size(); ++i)
     if (r.labels[i] >= 0 && (size_t)r.labels[i] < clusters_points_idx.size()) clusters_points_idx[(size_t)r.labels[i]].push_back((int)i);
@@ -90,6 +105,9 @@ inline void driverFields(S& structure, DriverFields& f) {
   if (f.have_truth) f.matches = structure.compareClusterLabels(f.truth.data(), (int64_t)f.truth.size());
   if (f.parts_K >= 0 && f.want_parts) f.parts = structure.getLabelComponents(f.part_classes.data(), (int64_t)f.part_classes.size(), f.parts_K);
   if (f.parts_K >= 0 && f.want_parts_graph) f.parts_graph = structure.getLabelGraph(f.part_classes.data(), (int64_t)f.part_classes.size(), f.parts_K);
+  if (f.parts_K >= 0 && f.absorb.on)
+    f.absorb.out = structure.absorbLabelParts(f.part_classes.data(), (int64_t)f.part_classes.size(), f.absorb.min_points, f.absorb.island_points,
+                                              f.absorb.max_rounds, f.absorb.drop, f.parts_K);
 }
 
 // debug_prefix: when not empty, the reference's three voxel drawings (VS:510, 654, 1016) are written as

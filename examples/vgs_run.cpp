@@ -14,6 +14,7 @@
 //                  [--refined-components <file.csv>] [--class-components <file.csv> --class-field <name> --classes <C>]
 //                  [--component-ids <file.i32>]
 //                  [--refined-graph <file.csv>] [--class-graph <file.csv> --class-field <name> --classes <C>]
+//                  [--absorbed-labels <file.i32> [--absorb-islands <points>] [--absorb-min-points <points>] [--absorb-rounds <r>] [--absorb-drop]]
 // --debug-meshes (VGS only) also writes the reference's voxel drawings as <prefix>_voxels.ply, _clustered_voxels.ply, _normals.ply.
 // --in / --out replace the path + name entries of the task file (the shipped ones hold Windows paths).
 // --segments writes one CSV row per kept cluster (getClusterDescriptors, row i = cluster i of the output): label, n_points, n_nodes,
@@ -58,6 +59,13 @@
 // n_shared (nodes that hold points of both), then the columns of --segment-graph over the contacts of a and b -- n_pairs, n_finite,
 // nodes_a, nodes_b, w_mean, w_min, w_max, doubles as %.17g, floats as %.9g.  It needs --refine.  --class-graph writes the same table for
 // the class field of --class-components (same reading, same rules): which classes touch, and across how much boundary.
+// --absorbed-labels writes one label per point (int32, input order, -1 = none, raw like --component-ids): the source labelling with its
+// stranded and small connected parts absorbed into the neighbour they touch most (absorbLabelParts).  The source is --refine (the refined
+// labels, K = the kept clusters) or --class-field <name> --classes <C> (the class field, read like --class-components); with both it is a
+// usage error.  At least one threshold is needed: --absorb-islands <points> (parts below it that are not the largest of their label)
+// and/or --absorb-min-points <points> (any part below it); --absorb-rounds <r> (0 .. 64, default 8) caps the rounds, --absorb-drop gives
+// what is still too small afterwards -1.  A further stdout line carries the eight counts: "absorbed rounds parts points candidates
+// candidate_points dropped parts_left skipped".  With --refine every --refined-* table keeps describing the refined labels.
 // Prints "<method> <points> <voxels> <supervoxels> <all clusters> <kept clusters> <labelled points>".
 #include <algorithm>
 #include <cmath>
@@ -88,13 +96,16 @@ int main(int argc, char** argv) {
                  "[--refined-segment-fields file.csv --fields a[,b,...]] [--refined-segment-classes file.csv --class-field name --classes C] "
                  "[--refined-matches file.csv --truth-field name [--refined-truth-matches file.csv]] "
                  "[--refined-components file.csv] [--class-components file.csv --class-field name --classes C] [--component-ids file.i32] "
-                 "[--refined-graph file.csv] [--class-graph file.csv --class-field name --classes C]\n",
+                 "[--refined-graph file.csv] [--class-graph file.csv --class-field name --classes C] "
+                 "[--absorbed-labels file.i32 [--absorb-islands points] [--absorb-min-points points] [--absorb-rounds r] [--absorb-drop]]\n",
                  argv[0]);
     return 2;
   }
   std::string in_file, out_file, debug_prefix, segments_file, graph_file, adjacency_file, boxes_file, fields_file, classes_file, class_field, matches_file, truth_field, truth_file;
   std::string r_segments_file, r_boxes_file, r_matches_file, r_truth_file, r_fields_file, r_classes_file;
-  std::string r_parts_file, c_parts_file, part_ids_file, r_graph_file, c_graph_file;
+  std::string r_parts_file, c_parts_file, part_ids_file, r_graph_file, c_graph_file, absorbed_file;
+  DriverAbsorb absorb;
+  bool absorb_opts = false, absorb_threshold = false;
   std::vector<std::string> field_names;
   bool have_fields = false, have_classes = false;
   long n_classes = 0;
@@ -151,6 +162,21 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[a], "--component-ids") && a + 1 < argc) part_ids_file = argv[++a];
     else if (!std::strcmp(argv[a], "--refined-graph") && a + 1 < argc) r_graph_file = argv[++a];
     else if (!std::strcmp(argv[a], "--class-graph") && a + 1 < argc) c_graph_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--absorbed-labels") && a + 1 < argc) absorbed_file = argv[++a];
+    else if (!std::strcmp(argv[a], "--absorb-drop")) { absorb.drop = true; absorb_opts = true; }
+    else if ((!std::strcmp(argv[a], "--absorb-islands") || !std::strcmp(argv[a], "--absorb-min-points") || !std::strcmp(argv[a], "--absorb-rounds")) &&
+             a + 1 < argc) {
+      const char which = argv[a][9];   // i, m or r
+      char* end = nullptr;
+      const long long v = std::strtoll(argv[++a], &end, 10);
+      if (end == argv[a] || *end != 0 || v < 0 || (which == 'r' && v > 64)) {
+        std::fprintf(stderr, "%s %s: %s\n", argv[a - 1], argv[a], which == 'r' ? "a number in 0 .. 64" : "a number of points, not negative");
+        return 2;
+      }
+      if (which == 'i') absorb.island_points = v; else if (which == 'm') absorb.min_points = v; else absorb.max_rounds = (int32_t)v;
+      absorb_opts = true;
+      if (which != 'r') absorb_threshold = true;
+    }
     else if (!std::strcmp(argv[a], "--refine")) refine.on = true;
     else if (!std::strcmp(argv[a], "--no-fill")) { refine.fill = false; refine_opts = true; }
     else if ((!std::strcmp(argv[a], "--patch-radius") || !std::strcmp(argv[a], "--switch-ratio")) && a + 1 < argc) {
@@ -178,6 +204,23 @@ int main(int argc, char** argv) {
   if (!c_graph_file.empty() && class_field.empty()) { std::fprintf(stderr, "--class-graph needs --class-field <name>\n"); return 2; }
   if (!c_graph_file.empty() && !have_classes) { std::fprintf(stderr, "--class-graph needs --classes <C>\n"); return 2; }
   if (!r_graph_file.empty() && !refine.on) { std::fprintf(stderr, "--refined-graph needs --refine\n"); return 2; }
+  if (absorb_opts && absorbed_file.empty()) {
+    std::fprintf(stderr, "--absorb-islands / --absorb-min-points / --absorb-rounds / --absorb-drop need --absorbed-labels <file.i32>\n");
+    return 2;
+  }
+  const bool absorb_class = !absorbed_file.empty() && !refine.on;   // the class field is the source
+  if (!absorbed_file.empty()) {
+    const bool cls = have_classes || !class_field.empty();
+    if (refine.on == cls) {
+      std::fprintf(stderr, "--absorbed-labels absorbs the labels of exactly one of --refine and --class-field <name> --classes <C> (%s given)\n",
+                   cls ? "both" : "neither");
+      return 2;
+    }
+    if (absorb_class && class_field.empty()) { std::fprintf(stderr, "--absorbed-labels needs --class-field <name>\n"); return 2; }
+    if (absorb_class && !have_classes) { std::fprintf(stderr, "--absorbed-labels needs --classes <C>\n"); return 2; }
+    if (!absorb_threshold) { std::fprintf(stderr, "--absorbed-labels needs --absorb-islands <points> and/or --absorb-min-points <points>\n"); return 2; }
+  }
+  absorb.on = !absorbed_file.empty();
   if (!part_ids_file.empty() && r_parts_file.empty() == c_parts_file.empty()) {
     std::fprintf(stderr, "--component-ids writes the parts of exactly one of --refined-components and --class-components (%s given)\n",
                  r_parts_file.empty() ? "neither" : "both");
@@ -189,8 +232,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--fields needs --segment-fields <file.csv> (or --refined-segment-fields)\n");
     return 2;
   }
-  if (classes_file.empty() && r_classes_file.empty() && c_parts_file.empty() && c_graph_file.empty() && (have_classes || !class_field.empty())) {
-    std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv> (or --refined-segment-classes, --class-components, --class-graph)\n");
+  if (classes_file.empty() && r_classes_file.empty() && c_parts_file.empty() && c_graph_file.empty() && !absorb_class && (have_classes || !class_field.empty())) {
+    std::fprintf(stderr, "--class-field / --classes need --segment-classes <file.csv> (or --refined-segment-classes, --class-components, --class-graph, --absorbed-labels)\n");
     return 2;
   }
   if (!matches_file.empty() && truth_field.empty()) { std::fprintf(stderr, "--segment-matches needs --truth-field <name>\n"); return 2; }
@@ -221,10 +264,10 @@ int main(int argc, char** argv) {
   const bool ply = in_file.size() > 4 && in_file.substr(in_file.size() - 4) == ".ply";
   const bool want_truth = !(matches_file.empty() && r_matches_file.empty());
   const bool any_fields = !(fields_file.empty() && r_fields_file.empty()), any_classes = !(classes_file.empty() && r_classes_file.empty());
-  const bool class_labels = !(c_parts_file.empty() && c_graph_file.empty());   // the class field read as a labelling of its own
+  const bool class_labels = !(c_parts_file.empty() && c_graph_file.empty()) || absorb_class;   // the class field read as a labelling of its own
   if (ply && (any_fields || any_classes || want_truth || class_labels)) {   // (a usage error: nothing has been loaded yet)
     std::fprintf(stderr, "--segment-fields / --segment-classes / --refined-segment-fields / --refined-segment-classes / --segment-matches / "
-                 "--refined-matches / --class-components / --class-graph read their fields from a PCD input, not from %s\n", in_file.c_str());
+                 "--refined-matches / --class-components / --class-graph / --absorbed-labels read their fields from a PCD input, not from %s\n", in_file.c_str());
     return 2;
   }
   if ((ply ? inputPointCloudData2(in_file, cloud) : inputPointCloudData(in_file, cloud)) != 0) return 1;
@@ -250,6 +293,7 @@ int main(int argc, char** argv) {
       fields.parts_K = (int64_t)n_classes;
       fields.want_parts = !c_parts_file.empty();
       fields.want_parts_graph = !c_graph_file.empty();
+      if (absorb_class) fields.absorb = absorb;
     }
     if (want_truth) {
       if (vgs_io::read_pcd_field_int32(in_file, truth_field, fields.truth, err) != 0) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
@@ -263,6 +307,7 @@ int main(int argc, char** argv) {
   refine.want_hist = !r_classes_file.empty();
   refine.want_components = !r_parts_file.empty();
   refine.want_graph = !r_graph_file.empty();
+  if (absorb.on && !absorb_class) refine.absorb = absorb;
   refine.fields = &fields;
   refine.box_frame = box_frame;
   std::vector<std::vector<int>> clusters;
@@ -311,11 +356,21 @@ int main(int argc, char** argv) {
     const bool ok = f && std::fwrite(ids.data(), sizeof(int32_t), ids.size(), f) == ids.size();
     if (!f || std::fclose(f) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", part_ids_file.c_str()); return 1; }
   }
+  const pcl::AbsorbedLabels& absorbed = absorb_class ? fields.absorb.out : refine.absorb.out;
+  if (absorb.on) {
+    FILE* f = std::fopen(absorbed_file.c_str(), "wb");
+    const bool ok = f && std::fwrite(absorbed.labels.data(), sizeof(int32_t), absorbed.labels.size(), f) == absorbed.labels.size();
+    if (!f || std::fclose(f) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", absorbed_file.c_str()); return 1; }
+  }
   if (!adjacency_file.empty() && writeAdjacency(adjacency_file, graph.adjacency) != 0) {
     std::fprintf(stderr, "cannot write %s\n", adjacency_file.c_str());
     return 1;
   }
   std::printf("%d %ld %ld %ld %ld %ld %ld\n", method, sum.points, sum.voxels, sum.supervoxels, sum.clusters, sum.kept, sum.labelled);
+  if (absorb.on)
+    std::printf("absorbed %lld %lld %lld %lld %lld %lld %lld %lld\n", (long long)absorbed.rounds, (long long)absorbed.parts_absorbed,
+                (long long)absorbed.points_relabelled, (long long)absorbed.candidates_left, (long long)absorbed.candidate_points_left,
+                (long long)absorbed.points_dropped, (long long)absorbed.n_parts, (long long)absorbed.n_skipped);
   if (!matches_file.empty()) {
     std::printf("matches");
     for (int i = 0; i < 12; ++i) std::printf(" %lld", (long long)fields.matches.summary[i]);

@@ -761,6 +761,8 @@ vgs_status vgs_refine_own_point_labels(vgs_ctx* ctx, const vgs_refine_params* rp
  * labels in place); n_parts = C and n_skipped may be NULL.  vgs_get_point_label_components copies the tables out, any pointer may be
  * NULL; vgs_get_point_label_components_device hands out the device pointers (NULL for a table without rows).  Both are valid until the
  * next vgs_point_label_components or the next run of the stages, and answer VGS_E_STATE without a result since the last run.
+ * vgs_absorb_point_label_parts runs this pass in the same buffers every round: it discards the result (VGS_E_STATE from the getters
+ * until the next vgs_point_label_components).
  * VGS_E_STATE before the context is segmented, and for a tile context: it holds part of the cloud and of the graph only, and parts
  * across the ranks of the tiled driver are not computed by this call (vgs_tiles_point_label_components, include/vgs_tiles.h, is).  VGS_E_ARG for n != N, a NULL labelling, K outside 0 .. 2^31 - 1. */
 vgs_status vgs_point_label_components(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_parts, int64_t* n_skipped);
@@ -805,6 +807,8 @@ vgs_status vgs_get_point_label_components_device(vgs_ctx* ctx, const int32_t** p
  * vgs_get_point_label_graph_device hands out E and the device pointers (NULL for E = 0).  Both are valid until the next
  * vgs_point_label_graph or the next run of the stages, and answer VGS_E_STATE without a result since the last run.  No other table, no
  * labels and no result of vgs_point_label_components are touched.
+ * vgs_absorb_point_label_parts runs this pass in the same buffers every round: it discards the table (VGS_E_STATE from the getters
+ * until the next vgs_point_label_graph).
  * VGS_E_STATE before the context is segmented, and for a tile context: it holds part of the cloud and of the graph only, and the graph of a
  * labelling across the ranks of the tiled driver is not computed by this call (vgs_tiles_point_label_graph does).  VGS_E_ARG for n != N, a NULL labelling, K outside 0 .. 2^31 - 1. */
 vgs_status vgs_point_label_graph(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, int64_t* n_edges, int64_t* n_skipped);
@@ -814,6 +818,60 @@ vgs_status vgs_get_point_label_graph(vgs_ctx* ctx, int32_t* seg_ab, int64_t* n_s
 vgs_status vgs_get_point_label_graph_device(vgs_ctx* ctx, int64_t* n_edges, const int32_t** seg_ab, const int64_t** n_shared,
                                             const int64_t** n_pairs, const int64_t** n_finite, const int32_t** nodes_ab, const double** w_sum,
                                             const float** w_min, const float** w_max);
+/* Absorb the stranded and the small connected parts of ANY per-point labelling of the cloud into the neighbour they touch most (no
+ * reference counterpart): the clean-up every region-growing or graph segmenter ships, as one call that takes a labelling and returns one.
+ *
+ * Input.  The contract of vgs_point_label_components: labels[i] for every input point i < N; negative = no label; 0 <= labels[i] < K,
+ * the first offending index of a label >= K reported with VGS_E_ARG.  The input is never written.
+ * Parameters (vgs_absorb_params; vgs_absorb_params_default gives min_points = 0, island_points = 0, max_rounds = 8, drop = 0, which is
+ * the identity):
+ *   min_points     int64 >= 0   parts below it are candidates, the largest part of a label included
+ *   island_points  int64 >= 0   parts below it that are NOT the largest part of their label are candidates
+ *   max_rounds     int32 0..64  the cap on the applied rounds
+ *   drop           int32        != 0: what is still a candidate at the end loses its label
+ * EVALUATION of a labelling L:
+ *   1. cmp = vgs_point_label_components(L, K): C parts, P = part_of_point.
+ *   2. g = vgs_point_label_graph(P, C), the graph OF THE PARTS.  Parts of one label are never adjacent, so every edge joins two labels.
+ *      Only seg_ab, n_shared and n_pairs are used.
+ *   3. threshold(p) = min_points if p == label_largest[part_label[p]], else max(min_points, island_points).
+ *   4. Part p is a CANDIDATE iff part_points[p] < threshold(p) -- strictly: a part of exactly the threshold stays.  Every other part is
+ *      STABLE.
+ *   5. A candidate p has a TARGET if it has at least one edge {p, q} with q stable: the q with the largest triple
+ *      (n_shared + n_pairs, part_points[q], -q), compared lexicographically -- most boundary, then the bigger part, then the lower part
+ *      id.  A candidate never targets a candidate, which rules out swaps and cycles.
+ * ROUNDS.  For r = 0, 1, ...: evaluate L.  If r == max_rounds, or no candidate has a target, this is the FINAL evaluation: stop.
+ * Otherwise every point of every candidate p with a target takes part_label[target(p)], all other points keep their label -- one APPLIED
+ * round -- and the next round evaluates the new labelling.  An absorbed part touches its target through a contact or a shared node, so
+ * it becomes connected to it: C falls by at least one per applied round and the loop ends without the cap, which only bounds the time.
+ * After the final evaluation.  With drop != 0 every point of every candidate of the final evaluation, with or without a target, gets -1:
+ * the output then has no candidate under the same parameters.  Without drop, when the loop ended before the cap, every remaining
+ * candidate has no stable neighbour.
+ * Points outside the pass.  A labelled point without a node (non-finite, or outside the octree) keeps its label under every parameter
+ * and counts in n_skipped.  Unlabelled points stay as they are (a negative value is copied through): filling them is
+ * vgs_refine_point_labels' job.
+ * Outputs:
+ *   labels_out  int32 [N]  input order; values in -1 .. K-1 for an input whose negative values are -1
+ *   counts      int64 [8]  0 applied rounds, 1 parts absorbed and 2 points relabelled, both summed over the rounds, 3 candidates of the
+ *                          final evaluation, 4 their points, 5 points dropped, 6 C of the final evaluation, 7 n_skipped
+ * Everything is integer: the result is bit-identical from call to call and from engine to engine.  The score deliberately does not use
+ * w_sum (DESIGN.md 8 says why).
+ * vgs_absorb_point_label_parts[_device] computes the result on the device into a buffer of the context (the _device variant reads the
+ * labels in place); counts may be NULL.  vgs_get_absorbed_point_labels copies it out, vgs_get_absorbed_point_labels_device hands out the
+ * device pointer (NULL for N = 0).  Both are valid until the next absorb call or the next run of the stages and answer VGS_E_STATE
+ * without a result since the last run.  The call OVERWRITES the context's results of vgs_point_label_components and
+ * vgs_point_label_graph: their getters answer VGS_E_STATE afterwards until their own next compute call.  No other table and no label
+ * buffer is touched: the point labels and the refined labels stay as they are.
+ * VGS_E_STATE before the context is segmented, and for a tile context: it holds part of the cloud and of the graph only, and the call
+ * across the ranks of the tiled driver does not exist yet.  VGS_E_ARG for n != N, a NULL labelling or NULL params, K outside
+ * 0 .. 2^31 - 1, a negative threshold, max_rounds outside 0 .. 64.  VGS_E_UNSUPPORTED of an inner pass is passed on with its message. */
+typedef struct { int64_t min_points; int64_t island_points; int32_t max_rounds; int32_t drop; } vgs_absorb_params;
+vgs_status vgs_absorb_params_default(vgs_absorb_params* ap);
+vgs_status vgs_absorb_point_label_parts(vgs_ctx* ctx, const int32_t* labels_host, int64_t n, int64_t K, const vgs_absorb_params* ap,
+                                        int64_t* counts /* 8, may be NULL */);
+vgs_status vgs_absorb_point_label_parts_device(vgs_ctx* ctx, const int32_t* labels_dev, int64_t n, int64_t K, const vgs_absorb_params* ap,
+                                               int64_t* counts /* 8, may be NULL */);
+vgs_status vgs_get_absorbed_point_labels(vgs_ctx* ctx, int32_t* out /* N */);
+vgs_status vgs_get_absorbed_point_labels_device(vgs_ctx* ctx, const int32_t** out);
 /* Tile contexts (vgs_set_owned_region and vgs_set_own_point_range; VGS only): a rank's share of the connected parts of a labelling over
  * all ranks of the tiled driver.  include/vgs_tiles.h (vgs_tiles_point_label_components) states the definition and the protocol these
  * four steps serve; csrc/labelcc_tiles.hip has the kernels.  Every call answers VGS_E_STATE on a plain context and before a run.

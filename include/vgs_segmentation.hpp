@@ -368,6 +368,15 @@ struct LabelGraph {
   int64_t n_skipped = 0;          // labelled points outside the octree
 };
 
+// Extension (no VS / SS line): a per-point labelling with its stranded and small connected parts absorbed into the neighbour they touch
+// most, as vgs_absorb_point_label_parts (include/vgs.h) defines it, and the eight counts of the call
+struct AbsorbedLabels {
+  std::vector<int32_t> labels;   // input order; -1 for a dropped point
+  int64_t rounds = 0, parts_absorbed = 0, points_relabelled = 0;   // applied rounds; parts and points, summed over them
+  int64_t candidates_left = 0, candidate_points_left = 0;          // of the final evaluation
+  int64_t points_dropped = 0, n_parts = 0, n_skipped = 0;          // n_parts: of the final evaluation
+};
+
 namespace vgs_detail {
 inline LabelGraph label_graph(vgs_ctx* c, int64_t k, const int32_t* labels, int64_t n) {
   LabelGraph o;
@@ -388,6 +397,21 @@ inline LabelGraph label_graph(vgs_ctx* c, int64_t k, const int32_t* labels, int6
     e.nodes_a = nd[2 * i]; e.nodes_b = nd[2 * i + 1];
     e.w_sum = ws[i]; e.w_min = mn[i]; e.w_max = mx[i];
   }
+  return o;
+}
+// the call of vgs_absorb_point_label_parts and its result
+inline AbsorbedLabels absorb_label_parts(vgs_ctx* c, int64_t k, const int32_t* labels, int64_t n, int64_t min_points, int64_t island_points,
+                                         int32_t max_rounds, bool drop) {
+  AbsorbedLabels o;
+  vgs_absorb_params ap;
+  check(c, vgs_absorb_params_default(&ap), "vgs_absorb_params_default");
+  ap.min_points = min_points; ap.island_points = island_points; ap.max_rounds = max_rounds; ap.drop = drop ? 1 : 0;
+  int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  check(c, vgs_absorb_point_label_parts(c, labels, n, k, &ap, counts), "vgs_absorb_point_label_parts");
+  o.labels.resize((size_t)n);
+  check(c, vgs_get_absorbed_point_labels(c, o.labels.data()), "vgs_get_absorbed_point_labels");
+  o.rounds = counts[0]; o.parts_absorbed = counts[1]; o.points_relabelled = counts[2]; o.candidates_left = counts[3];
+  o.candidate_points_left = counts[4]; o.points_dropped = counts[5]; o.n_parts = counts[6]; o.n_skipped = counts[7];
   return o;
 }
 // PCL's getSupervoxelAdjacency idiom: both directions of every edge, keyed by cluster index
@@ -591,6 +615,15 @@ class VoxelBasedSegmentation {
     if (!drawn_) return {};
     return vgs_detail::label_graph(ctx(), K < 0 ? count(VGS_N_KEPT) : K, labels, n);
   }
+  // Extension (no VS line): the labelling with its parts below min_points points -- below island_points for a part that is not the
+  // largest of its label -- absorbed into the neighbour they touch most, for at most max_rounds rounds; drop: what is still too small
+  // afterwards gets -1 (vgs_absorb_point_label_parts, include/vgs.h).  labels and K as getLabelComponents.  The labelling itself, no
+  // round, before drawColorMapofPointsinClusters
+  AbsorbedLabels absorbLabelParts(const int32_t* labels, int64_t n, int64_t min_points, int64_t island_points, int32_t max_rounds = 8,
+                                  bool drop = false, int64_t K = -1) {
+    if (!drawn_) { AbsorbedLabels o; o.labels.assign(labels, labels + (n > 0 ? n : 0)); return o; }
+    return vgs_detail::absorb_label_parts(ctx(), K < 0 ? count(VGS_N_KEPT) : K, labels, n, min_points, island_points, max_rounds, drop);
+  }
 
   // Extension (no VS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
   // names getClusterIdx()[i].  patch_radius < 0: the default (the voxel size); every point -1 before drawColorMapofPointsinClusters
@@ -743,6 +776,12 @@ class SuperVoxelBasedSegmentation {
   // getLabelComponents
   LabelGraph getLabelGraph(const int32_t* labels, int64_t n, int64_t K = -1) {
     return vgs_detail::label_graph(ctx(), K < 0 ? count(VGS_N_KEPT) : K, labels, n);
+  }
+  // Extension (no SS line): the labelling with its small parts absorbed into the neighbour they touch most
+  // (vgs_absorb_point_label_parts, include/vgs.h), labels and K as getLabelComponents
+  AbsorbedLabels absorbLabelParts(const int32_t* labels, int64_t n, int64_t min_points, int64_t island_points, int32_t max_rounds = 8,
+                                  bool drop = false, int64_t K = -1) {
+    return vgs_detail::absorb_label_parts(ctx(), K < 0 ? count(VGS_N_KEPT) : K, labels, n, min_points, island_points, max_rounds, drop);
   }
   // Extension (no SS line): one label per input point, refined at the cluster boundaries (vgs_refine_point_labels, include/vgs.h); label i
   // names getClusterIdx()[i].  patch_radius < 0: the default (the supervoxel size)

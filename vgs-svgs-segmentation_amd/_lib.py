@@ -43,6 +43,10 @@ class VgsRefineParams(C.Structure):
     _fields_ = [("patch_radius", C.c_float), ("switch_ratio", C.c_float), ("fill", C.c_int32)]
 
 
+class AbsorbParams(C.Structure):
+    _fields_ = [("min_points", C.c_int64), ("island_points", C.c_int64), ("max_rounds", C.c_int32), ("drop", C.c_int32)]
+
+
 class VgsError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"{STATUS_NAMES[status] if 0 <= status < len(STATUS_NAMES) else status}: {msg}")
@@ -171,6 +175,11 @@ SYMBOLS = [
     ("vgs_point_label_graph_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
     ("vgs_get_point_label_graph", C.c_int, [_P] + [_P] * 8),
     ("vgs_get_point_label_graph_device", C.c_int, [_P, C.POINTER(C.c_int64)] + [_P] * 8),
+    ("vgs_absorb_params_default", C.c_int, [C.POINTER(AbsorbParams)]),
+    ("vgs_absorb_point_label_parts", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.POINTER(AbsorbParams), _P]),
+    ("vgs_absorb_point_label_parts_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.POINTER(AbsorbParams), _P]),
+    ("vgs_get_absorbed_point_labels", C.c_int, [_P, _P]),
+    ("vgs_get_absorbed_point_labels_device", C.c_int, [_P, C.POINTER(_P)]),
     ("vgs_own_point_label_band", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
     ("vgs_own_point_label_band_device", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
     ("vgs_get_own_point_label_band", C.c_int, [_P, _P, _P]),

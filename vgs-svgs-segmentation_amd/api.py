@@ -621,6 +621,47 @@ class Engine:
         self._ck(self._L.vgs_get_point_label_graph_device(self._h, C.byref(E), *(C.byref(p) for p in ps)))
         return E.value, {name: p.value for (name, _, _), p in zip(self.LABEL_GRAPH_FIELDS, ps)}
 
+    # the eight counts of vgs_absorb_point_label_parts, in their order
+    ABSORB_COUNTS = ("rounds", "parts_absorbed", "points_relabelled", "candidates_left", "candidate_points_left", "points_dropped",
+                     "n_parts", "n_skipped")
+
+    def absorb_label_parts(self, labels, min_points=0, island_points=0, max_rounds=8, drop=False, K=None):
+        """Absorb the stranded and the small connected parts of ANY per-point labelling into the neighbour they touch most (include/vgs.h,
+        vgs_absorb_point_label_parts, which states the rule): a part of label_components(labels) with fewer than min_points points, or
+        fewer than island_points when it is not the largest part of its label, takes the label of the stable part it shares the most
+        boundary with (n_shared + n_pairs of label_graph over the parts; then the bigger part, then the lower part id); repeated for at
+        most max_rounds rounds, since a small part's only neighbour can itself be small.  drop: what is still a candidate at the end
+        gets -1.  `labels`, K as label_components() (K None: max(label) + 1); the input is never written.  Returns a dict: labels (numpy
+        int32, N, input order) and the eight counts by name (ABSORB_COUNTS).  Integers only, bit-identical from call to call.  The call
+        overwrites the results of label_components() and label_graph(): their *_device() getters raise until their next compute call."""
+        if K is None:
+            if self._is_torch(labels):
+                K = max(int(labels.max().item()) + 1, 0) if labels.numel() > 0 else 0
+            else:
+                a = np.asarray(labels)
+                K = max(int(a.max()) + 1, 0) if a.size > 0 else 0
+        labels, ptr, n, dev, K = self._labels_input(labels, K)
+        fn = self._L.vgs_absorb_point_label_parts_device if dev else self._L.vgs_absorb_point_label_parts
+        ap = _lib.AbsorbParams(int(min_points), int(island_points), int(max_rounds), 1 if drop else 0)
+        counts = np.zeros(8, dtype=np.int64)
+        self._ck(fn(self._h, ptr, n, K, C.byref(ap), _ptr(counts)))
+        out = {"labels": self.absorbed_labels()}
+        out.update({name: int(v) for name, v in zip(self.ABSORB_COUNTS, counts)})
+        return out
+
+    def absorbed_labels(self):
+        """The labelling of the last absorb_label_parts (numpy int32, N, input order), valid until the next one or the next run."""
+        out = np.zeros(self.n, dtype=np.int32)
+        self._ck(self._L.vgs_get_absorbed_point_labels(self._h, _ptr(out)))
+        return out
+
+    def absorbed_labels_device_ptr(self):
+        """The same labelling left in HBM: its device pointer (None for an empty cloud), valid until the next absorb_label_parts or the
+        next run."""
+        p = C.c_void_p()
+        self._ck(self._L.vgs_get_absorbed_point_labels_device(self._h, C.byref(p)))
+        return p.value
+
     def compare_labels(self, ref, labels=None, K=None):
         """Score the segmentation against a labelling of the same points (include/vgs.h, vgs_compare_labels): the sparse contingency table
         between point_labels() and `ref`, the reference table and the segment table, as a dict of numpy arrays -- cell_seg, cell_ref, cell_n

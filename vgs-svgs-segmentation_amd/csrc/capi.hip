@@ -261,7 +261,7 @@ vgs_status vgs_set_params(vgs_ctx* c, const vgs_params* p) {
       p->spatial_impt != o.spatial_impt || p->normal_impt != o.normal_impt || p->vccs_mode != o.vccs_mode)
     keep = ST_POINTS;
   if (c->stage > keep) c->stage = keep;
-  if (keep < ST_SEGMENTED) { c->sd_valid = false; c->sb_valid[0] = c->sb_valid[1] = false; c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->lg_valid = false; c->lgt_own = c->lgt_valid = false; c->cmp_own_cells = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1; }
+  if (keep < ST_SEGMENTED) { c->sd_valid = false; c->sb_valid[0] = c->sb_valid[1] = false; c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->lg_valid = false; c->la_valid = false; c->lgt_own = c->lgt_valid = false; c->cmp_own_cells = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1; }
   // labels from svgs_supervoxels depend on voxel_size / seed_size / the three importances; a caller's own labelling does not
   if (keep == ST_POINTS && c->P.method == 3 && !c->sv_labels_external) { c->sv_have_labels = false; c->sv_max_label = 0; c->sv_label_n = -1; }
   c->P = *p;
@@ -278,7 +278,7 @@ static vgs_status set_points_common(vgs_ctx* c, int64_t n, int32_t stride_bytes)
   c->stage = ST_POINTS;
   c->sd_valid = false;      // (segdesc.hip: the descriptors belong to the last segmented cloud)
   c->sb_valid[0] = c->sb_valid[1] = false;      // (segbox.hip: so do the oriented boxes)
-  c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->lg_valid = false; c->lgt_own = c->lgt_valid = false; c->cmp_own_cells = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1;      // (seggraph.hip: so does the segment graph)
+  c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->lg_valid = false; c->la_valid = false; c->lgt_own = c->lgt_valid = false; c->cmp_own_cells = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1;      // (seggraph.hip: so does the segment graph)
   c->grid_covers = false;   // (vgs_set_grid_covering vouches for one cloud)
   c->counts[VGS_N_POINTS] = n;
   for (int i = 0; i < VGS_T_COUNT; ++i) { c->times[i] = 0; c->tev_pending[i] = false; }

@@ -532,7 +532,7 @@ vgs_status vgs_stage_merge(vgs_ctx* c) {
   c->cl_valid = false;   // (clusters.hip: the cluster lists on the device belong to the labels of the last run)
   c->sd_valid = false;   // (segdesc.hip: so do the segment descriptors)
   c->sb_valid[0] = c->sb_valid[1] = false;   // (segbox.hip: and the oriented boxes)
-  c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->lg_valid = false; c->lgt_own = c->lgt_valid = false; c->cmp_own_cells = -1; c->pso_K = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1;   // (seggraph.hip: and the segment graph)
+  c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->lg_valid = false; c->la_valid = false; c->lgt_own = c->lgt_valid = false; c->cmp_own_cells = -1; c->pso_K = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1;   // (seggraph.hip: and the segment graph)
   const int64_t V = c->V, U = c->U, N = c->N;
   c->bnd_unique = -1;  // tile protocol results belong to the previous segmentation
   c->counts[VGS_N_CLUSTERS] = 0; c->counts[VGS_N_KEPT] = 0; c->counts[VGS_N_ISOLATED] = 0; c->counts[VGS_N_REATTACHED] = 0;

@@ -448,7 +448,7 @@ vgs_status vgs_get_boundary_roots(vgs_ctx* c, int64_t* n_records, uint64_t* code
 }
 
 vgs_status vgs_apply_tile_labels(vgs_ctx* c, int32_t local_base, const int32_t* root, const int32_t* label, int64_t n_roots) {
-  if (c) { c->cl_valid = false; c->sd_valid = false; c->sb_valid[0] = c->sb_valid[1] = false; c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->lg_valid = false; c->lgt_own = c->lgt_valid = false; c->cmp_own_cells = -1; c->pso_K = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1; }
+  if (c) { c->cl_valid = false; c->sd_valid = false; c->sb_valid[0] = c->sb_valid[1] = false; c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->lg_valid = false; c->la_valid = false; c->lgt_own = c->lgt_valid = false; c->cmp_own_cells = -1; c->pso_K = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1; }
   if (!c || (n_roots > 0 && (!root || !label))) return VGS_E_ARG;
   if (c->stage < ST_SEGMENTED || c->bnd_unique < 0) { c->err = "vgs_apply_tile_labels: vgs_get_boundary_roots first"; return VGS_E_STATE; }
   VGS_HIP_TRY(c, hipSetDevice(c->device));
@@ -510,7 +510,7 @@ vgs_status vgs_get_owned_roots(vgs_ctx* c, int64_t* n_roots, int32_t* root, int3
 }
 
 vgs_status vgs_apply_root_labels(vgs_ctx* c, const int32_t* root, const int32_t* label, int64_t n_roots) {
-  if (c) { c->cl_valid = false; c->sd_valid = false; c->sb_valid[0] = c->sb_valid[1] = false; c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->lg_valid = false; c->lgt_own = c->lgt_valid = false; c->cmp_own_cells = -1; c->pso_K = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1; }
+  if (c) { c->cl_valid = false; c->sd_valid = false; c->sb_valid[0] = c->sb_valid[1] = false; c->sg_valid = false; c->cmp_valid = false; c->rf_valid = false; c->lcc_valid = false; c->lg_valid = false; c->la_valid = false; c->lgt_own = c->lgt_valid = false; c->cmp_own_cells = -1; c->pso_K = -1; c->sg_halo_valid = false; c->sg_own_K = -1; c->rf_halo_valid = false; c->rf_band_n = -1; }
   if (!c || (n_roots > 0 && (!root || !label))) return VGS_E_ARG;
   if (c->stage < ST_SEGMENTED) { c->err = "vgs_apply_root_labels: segment first"; return VGS_E_STATE; }
   VGS_HIP_TRY(c, hipSetDevice(c->device));

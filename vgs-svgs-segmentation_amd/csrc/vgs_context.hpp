@@ -444,6 +444,16 @@ struct vgs_ctx {
   DevBuf<float> lg_wmin, lg_wmax;
   int64_t lg_E = 0;
   bool lg_valid = false;
+  // absorbing the small parts of a caller's per-point labelling (labelabsorb.hip): the labelling of the last vgs_absorb_point_label_parts
+  // (la_out, N words), valid until the next one or the next run of the stages (la_valid), and the second labelling the rounds alternate
+  // with (la_alt, N words).  Scratch of its own: per part the candidate flag, the target and the run begin | end of its records, per edge
+  // of the graph of the parts the sort's keys in | out and values in | out, rocprim's storage, the counter words.  Every round runs
+  // labelcc.hip and labelgraph.hip in their own buffers: lcc_valid and lg_valid are false behind the call.
+  DevBuf<int32_t> la_out, la_alt, la_target;
+  DevBuf<uint8_t> la_cand, la_tmp;
+  DevBuf<uint32_t> la_key, la_val, la_run;
+  DevBuf<uint64_t> la_cnt;
+  bool la_valid = false;
   // a tile context's share of the label graph across the ranks of the tiled driver (labelgraph_tiles.hip; include/vgs.h,
   // vgs_own_point_label_band): the own vertices of the last own pass stay in lcc_vtx (lgt_nv of them) and its band records in lct_bcode /
   // lct_blabel (lgt_band rows) until vgs_own_point_label_graph merges them with the other ranks' records -- the merged vertex arrays node |
